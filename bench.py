@@ -383,10 +383,54 @@ def stress_leg(steps=8, warmup=3, check=True):
     return out
 
 
-def measure(w, args, device, label, reps, cpu_steps, chunk_plan, pmc_section=None):
+DUMP_BUDGET_BYTES = 64 << 20          # --dump-outputs: all files together
+DUMP_MAX_ELEMENTS = 4 << 20           # ... an array longer than this is written as a fixed, seeded sample of its elements
+
+
+def timed_outputs(eng):
+    """What a caller of the timed path (htm_run) reads back after its last step: the Temporal Memory's State -- cell
+    activation and prediction, winner cells, and the distal State (projections.py:195-203).  The Spatial Pooler's fields
+    are not readable while a streamed call is outstanding (HTM_RUN_CONTINUE); the active columns are in the cell activation."""
+    from bithtm_amd import _lib as L
+    from bithtm_amd.engine import words_to_bool
+    info = eng.check_capacity()
+    K = eng.cell_dim
+    out = dict(
+        cell_activation=words_to_bool(eng.read(L.F_CELL_ACTIVATION, np.uint32, eng.cell_words), K),
+        cell_prediction=words_to_bool(eng.read(L.F_CELL_PREDICTION, np.uint32, eng.cell_words), K),
+        winner_cell=np.sort(eng.read(L.F_WINNER_CELL, np.int32, info.winner_cells)))
+    d = eng.read_distal()
+    if d is not None:
+        out.update(d)
+    return out
+
+
+def dump_outputs(arrays, directory):
+    """`arrays` -> directory/<name>.npy in float32 (bool, float32) or float64 (integers, float64); an array of more than
+    DUMP_MAX_ELEMENTS elements is replaced by the elements at a fixed, seeded set of flat indices (written beside it as
+    <name>_index.npy)."""
+    os.makedirs(directory, exist_ok=True)
+    files = {}
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        if a.size > DUMP_MAX_ELEMENTS:
+            idx = np.sort(np.random.RandomState(0).choice(a.size, DUMP_MAX_ELEMENTS, replace=False))
+            files[name + "_index"] = idx.astype(np.float64)
+            a = a.reshape(-1)[idx]
+        files[name] = a.astype(np.float32 if a.dtype in (np.bool_, np.float32) else np.float64)
+    total = sum(a.nbytes for a in files.values())
+    if total > DUMP_BUDGET_BYTES:
+        raise ValueError(f"--dump-outputs: {total} bytes exceed the {DUMP_BUDGET_BYTES}-byte budget")
+    for name, a in files.items():
+        np.save(os.path.join(directory, name + ".npy"), a)
+    log(f"[bench] wrote {len(files)} arrays ({total / 2**20:.1f} MB) of the last timed step to {directory}")
+
+
+def measure(w, args, device, label, reps, cpu_steps, chunk_plan, pmc_section=None, dump=None):
     """One workload through the bench protocol: untimed pre-training to the learned state, R repetitions of [W warm-up
     steps, exactly K timed steps] called as a streaming caller calls, per-launch HIP-event times of the timed schedule,
-    the roofline object, and (cpu_steps > 0) the oracle timed from the same state + the parity check of the call pattern."""
+    the roofline object, and (cpu_steps > 0) the oracle timed from the same state + the parity check of the call pattern.
+    `dump`: a directory for the outputs of the last timed step (dump_outputs)."""
     t_setup = time.perf_counter()
     noisy, perm = make_inputs(w)
     htm = build_htm(w, perm, device)
@@ -428,6 +472,8 @@ def measure(w, args, device, label, reps, cpu_steps, chunk_plan, pmc_section=Non
         eng.run(bank, n_bank, args.steps, **stream)
         eng.sync()
         rates.append(args.steps / (time.perf_counter() - t0))
+    if dump:                                             # untimed: the state the last timed step left
+        dump_outputs(timed_outputs(eng), dump)
     eng.run(bank, n_bank, 4, **run)                      # untimed: ends the stream (no Spatial Pooler work left outstanding)
     eng.sync()
     info = eng.check_capacity()
@@ -557,7 +603,8 @@ def run_single(args):
     if args.large_pool_only:
         return large_pool_leg(args, device)
     reps = args.reps if args.reps > 0 else max(3, min(15, -(-4000 // max(args.steps, 1))))
-    m = measure(w, args, device, "headline", reps, 0 if args.no_cpu_baseline else args.cpu_steps, (5, 20, 5))
+    m = measure(w, args, device, "headline", reps, 0 if args.no_cpu_baseline else args.cpu_steps, (5, 20, 5),
+                dump=args.dump_outputs)
     gc.collect()                                        # (the legs need the device to themselves: memory, and CU slots -- DESIGN.md)
     large = None
     if not args.no_large_pool and not args.columns:
@@ -621,7 +668,12 @@ def main():
     ap.add_argument("--stress-only", action="store_true", help="run only the configs[4] leg and print its object (profiling)")
     ap.add_argument("--no-graph", action="store_true")
     ap.add_argument("--no-pipeline", action="store_true", help="one role per launch (what the profiled replay always does)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the headline's last timed step computed to DIR/<name>.npy "
+                         "(bench_outputs/ in the tree is ignored by git)")
     args = ap.parse_args()
+    if args.dump_outputs and (args.stress_only or args.large_pool_only or args.gpus > 1):
+        ap.error("--dump-outputs writes the single-GPU headline's outputs")
     if args.stress_only:
         print(json.dumps(stress_leg(check=not args.no_cpu_baseline)), flush=True)
         return

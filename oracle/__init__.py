@@ -11,13 +11,13 @@ configs[4] pool against the keyed generator) may import it -- there only as the 
 Nothing under `bithtm_amd/` imports it.
 
 Parity status: PINNED.  `tests/golden/generate_golden.py` runs the *unmodified* reference
-(imported read-only from /root/reference in the build container) through its own
+(imported read-only from a checkout named by BITHTM_REFERENCE) through its own
 constructor hooks (`boosting=`, `inhibition=`: networks.py:16,22-24) and with
 `np.random.rand` replaced by the keyed generator of `oracle.keyed_rng`; every per-step
 output of that run is committed under `tests/golden/*.npz` and
 `tests/test_oracle_golden.py` replays them through this oracle bit-for-bit.
-`tests/test_oracle_vs_reference.py` repeats the comparison live whenever /root/reference
-is importable.
+`tests/test_oracle_vs_reference.py` replays lock-step runs of the reference recorded the
+same way (`tests/golden/generate_lockstep.py`, `tests/golden/lockstep_*.npz`).
 """
 
 from .keyed_rng import draw24, STREAM_LEAST_USED, STREAM_GROWTH, STREAM_SEGMENT_JITTER  # noqa: F401

@@ -1,7 +1,7 @@
 """NumPy restatement of the bitHTM timestep (Spatial Pooler + Temporal Memory).
 
 TEST INFRASTRUCTURE ONLY (see oracle/__init__.py).  Every function cites the reference
-lines it restates; paths are relative to /root/reference.  The restatement is written in
+lines it restates; paths are relative to the reference checkout.  The restatement is written in
 the *pull* form the GPU uses (one fixed-width row of presynaptic ids per segment) instead
 of the reference's mirrored push/pull store, and it replaces the three places where the
 reference's result is implementation-defined by the documented policies:

@@ -13,11 +13,12 @@ This file supplies
                           what the draw is for (which cells / segments), because the
                           reference only passes a shape.
 
-None of this is imported by the product.  It needs /root/reference on sys.path only for the
+None of this is imported by the product.  It needs the reference on sys.path only for the
 frame's function names; it contains no reference code.
 """
 
 import contextlib
+import os
 import sys
 
 import numpy as np
@@ -108,8 +109,12 @@ def keyed_rand(seed, cell_dim):
         np.random.rand = original
 
 
-def import_reference(path="/root/reference"):
-    """Import the reference package read-only (build container only)."""
+def import_reference(path=None):
+    """Import the reference package read-only from a checkout of cokwa/bitHTM: `path`, or the directory the environment
+    variable BITHTM_REFERENCE names (only the scripts that record tests/golden/ need it)."""
+    path = path or os.environ.get("BITHTM_REFERENCE")
+    if not path or not os.path.isdir(os.path.join(path, "bithtm")):
+        raise RuntimeError("set BITHTM_REFERENCE to a checkout of the reference (cokwa/bitHTM): the directory that holds bithtm/")
     if path not in sys.path:
         sys.path.insert(0, path)
     import bithtm  # noqa: F401

@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
 """Generate the golden vectors under tests/golden/ from the UNMODIFIED reference.
 
-Runs only in the build container (needs /root/reference, which never travels to the GPU
-box).  Usage:   python tests/golden/generate_golden.py
+Needs a checkout of the reference (cokwa/bitHTM).  Usage:
+    BITHTM_REFERENCE=<checkout> python tests/golden/generate_golden.py
 
 What is recorded
   traj_*.npz   multi-step trajectories of the reference HierarchicalTemporalMemory

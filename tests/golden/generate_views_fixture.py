@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Records tests/golden/views_copy_custom.npz (run in the build container, where the reference is importable).
+"""Records tests/golden/views_copy_custom.npz (needs a checkout of the reference: BITHTM_REFERENCE=<checkout>).
 
 What it pins: the reference-layout view of the segment store (bithtm_amd.projections.SegmentProjectionView --
 `output_edge`, `output_permanence`, `invalid_output_edge`, `get_output_edge_target`, `segment_bundle`) is what the
@@ -46,6 +46,32 @@ def view_digest(view, seg_cell):
         out.append(zlib.crc32(np.int64(seg_cell[s]).tobytes() + t[order].tobytes() +
                               view.output_permanence[s][ok][order].astype(np.float32).tobytes()))
     return np.array(out, dtype=np.uint32)
+
+
+def oracle_record(cfg=CONFIG):
+    """Every array of the fixture computed from the oracle alone: the state after cfg["steps"] steps through the view, and
+    its next step (learning off) in the layout the textbook Temporal Memory's outputs are recorded in."""
+    C, K = cfg["column_dim"], cfg["cell_dim"]
+    np.random.seed(cfg["seed"])
+    ora = HTMOracle(cfg["input_dim"], C, K, seed=cfg["seed"])
+    xs = inputs(cfg)
+    for t in range(cfg["steps"]):
+        ora.step(xs[t])
+    tm = ora.temporal_memory
+    S = tm.S
+    view = SegmentProjectionView(tm.presyn[:S], tm.perm[:S], C * K)
+    nxt_sp, nxt_tm = ora.step(xs[cfg["steps"]], learning=False)
+    od = nxt_tm.distal_state
+    return dict(
+        {k: np.asarray(v) for k, v in cfg.items()},
+        segments=np.int64(S), view_digest=view_digest(view, tm.seg_cell[:S]), output_edges=view.output_edges[:, 0],
+        next_active_column=nxt_sp.active_column,
+        textbook_active_cells=np.sort(nxt_tm.active_cell[0] * K + nxt_tm.active_cell[1]).astype(np.int64),
+        textbook_prediction=np.packbits(nxt_tm.cell_prediction.reshape(-1), bitorder="little"),
+        textbook_bursting=nxt_tm.active_column_bursting[:, 0],
+        textbook_matching=np.sort(od.matching_segment).astype(np.int64),
+        textbook_active_segments=np.sort(od.matching_segment[od.matching_segment_active]).astype(np.int64),
+        textbook_potential=od.segment_potential.astype(np.int64))
 
 
 def main(path=os.path.join(HERE, "views_copy_custom.npz")):

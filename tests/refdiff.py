@@ -1,8 +1,12 @@
 """Lock-step comparison helper: unmodified reference (through its hooks) vs. the oracle.
 
-Used by tests/test_oracle_vs_reference.py (live, build container only) and by
-tests/golden/generate_golden.py (to record golden vectors).  Not collected by pytest.
+Used live by tests/golden/generate_golden.py and tests/golden/generate_lockstep.py (to record golden vectors: they need a
+checkout of the reference), and by tests/test_oracle_vs_reference.py to replay the recorded lock-step runs
+(tests/golden/lockstep_*.npz) through the oracle alone.  Not collected by pytest.
 """
+
+import hashlib
+from types import SimpleNamespace
 
 import numpy as np
 
@@ -159,3 +163,166 @@ def run_lockstep(ref, seed, input_dim, column_dim, cell_dim, patterns, density, 
     stats["segments"] = ora.temporal_memory.S
     stats["slots"] = ora.temporal_memory.slots
     return stats, ref_htm, ora
+
+
+# ---- recorded lock-step runs (tests/golden/lockstep_*.npz): what compare_step / compare_store compare, one digest per field
+
+def digest(a):
+    """Eight bytes that stand for an array's shape and values as np.array_equal compares them: booleans and integers are
+    hashed as int64, floats as float64 (so an int32 and an int64 array of equal values, or a float32 array and its float64
+    widening, give one digest)."""
+    a = np.asarray(a)
+    a = a.astype(np.float64) + 0.0 if a.dtype.kind == "f" else a.astype(np.int64)
+    h = hashlib.blake2b(repr(a.shape).encode(), digest_size=8)
+    h.update(np.ascontiguousarray(a).tobytes())
+    return np.frombuffer(h.digest(), dtype="<u8")[0]
+
+
+def step_fields(sp, tm):
+    """The per-step outputs compare_step compares, in its order (active_column in the order it was returned)."""
+    d = tm.distal_state
+    return dict(active_column=sp.active_column, overlaps=sp.overlaps, boosted=sp.boosted_overlaps,
+                bursting=tm.active_column_bursting, cell_activation=tm.cell_activation, cell_prediction=tm.cell_prediction,
+                active_cell_cols=tm.active_cell[0], active_cell_cells=tm.active_cell[1],
+                winner_cell_cols=tm.winner_cell[0], winner_cell_cells=tm.winner_cell[1],
+                segment_potential=d.segment_potential, matching_segment=d.matching_segment,
+                matching_segment_activation=d.matching_segment_activation, matching_segment_active=d.matching_segment_active,
+                prediction=d.prediction, max_jittered_potential=d.max_jittered_potential,
+                matching_segment_jittered_potential=d.matching_segment_jittered_potential)
+
+
+def store_fields(seg_cell, presyn, perm, nsyn, segcount, sp_permanence, duty_cycle):
+    """What compare_store compares: the store in canonical form (permanences and duty cycles by their bits)."""
+    syn = canonical_synapses(seg_cell, presyn, perm)
+    return dict(seg_cell=seg_cell, seg_nsyn=nsyn, segcount=segcount,
+                syn_cell=np.array([x[0] for x in syn], dtype=np.int64),
+                syn_count=np.array([len(x[1]) for x in syn], dtype=np.int64),
+                syn_presyn=np.concatenate([x[1] for x in syn]) if syn else np.zeros(0, np.int64),
+                syn_perm_bits=np.concatenate([x[2].view(np.int32) for x in syn]) if syn else np.zeros(0, np.int32),
+                sp_permanence=sp_permanence, duty_cycle_bits=np.asarray(duty_cycle, dtype=np.float32).view(np.int32))
+
+
+def oracle_store_fields(ora):
+    tm, S = ora.temporal_memory, ora.temporal_memory.S
+    return store_fields(tm.seg_cell[:S], tm.presyn[:S], tm.perm[:S], tm.seg_nsyn[:S], tm.segcount,
+                        ora.spatial_pooler.permanence, ora.spatial_pooler.duty_cycle)
+
+
+def reference_store_fields(ref_htm):
+    seg_cell, presyn, perm, nsyn, bundle_segments = reference_store(ref_htm.temporal_memory)
+    rsp = ref_htm.spatial_pooler
+    return store_fields(seg_cell, presyn, perm, nsyn, bundle_segments, rsp.proximal_projection.permanence, rsp.boosting.duty_cycle)
+
+
+def record_lockstep(ref, path, seed, input_dim, column_dim, cell_dim, patterns, density, noise, steps, store_every=10,
+                    learning_schedule=None, jump=0.0, epsilon=None, prev_schedule=None, extra=None):
+    """run_lockstep (asserting equality every step, as live) and write to `path` the reference's side of it: the per-step
+    learning flag and prev_state distance, one digest per field of step_fields every step, one per field of store_fields at
+    every store check, and the initial Spatial Pooler permanences' digest.  replay_lockstep runs the oracle against it."""
+    digests, stores, store_steps, learning, back, names = [], [], [], [], [], {}
+
+    def record(t, x, learn, ref_sp, ref_tm, ref_htm):
+        learning.append(learn)
+        names.setdefault("step", list(step_fields(ref_sp, ref_tm)))
+        b = None if prev_schedule is None else prev_schedule(t)
+        back.append(-1 if b is None else b)
+        digests.append([digest(a) for a in step_fields(ref_sp, ref_tm).values()])
+        if t % store_every == 0 or t == steps - 1:
+            store_steps.append(t)
+            names.setdefault("store", list(reference_store_fields(ref_htm)))
+            stores.append([digest(a) for a in reference_store_fields(ref_htm).values()])
+
+    np.random.seed(seed)
+    perm0 = ref.projections.DenseProjection(input_dim, column_dim).permanence      # what build_pair's reference will draw
+    stats, ref_htm, ora = run_lockstep(ref, seed, input_dim, column_dim, cell_dim, patterns, density, noise, steps,
+                                       store_every=store_every, learning_schedule=learning_schedule, record=record, jump=jump,
+                                       epsilon=epsilon, prev_schedule=prev_schedule)
+    cfg = dict(seed=seed, input_dim=input_dim, column_dim=column_dim, cell_dim=cell_dim, patterns=patterns, density=density,
+               noise=noise, steps=steps, jump=jump, epsilon=np.nan if epsilon is None else epsilon)
+    np.savez_compressed(
+        path, **{k: np.asarray(v) for k, v in cfg.items()}, **(extra or {}),
+        learning=np.array(learning, dtype=np.bool_), back=np.array(back, dtype=np.int32),
+        step_field_names=np.array(names["step"]), step_digest=np.array(digests, dtype=np.uint64),
+        store_field_names=np.array(names["store"]), store_steps=np.array(store_steps, dtype=np.int32),
+        store_digest=np.array(stores, dtype=np.uint64), permanence_digest=np.uint64(digest(perm0)),
+        segments=np.int64(stats["segments"]))
+    return stats, ref_htm, ora
+
+
+def load_lockstep(path):
+    z = np.load(path)
+    return {k: z[k] for k in z.files}
+
+
+def replay_lockstep(rec):
+    """The oracle through a recorded lock-step run (record_lockstep): the same inputs, learning flags and prev_state
+    distances; every field of every step, and the store at every recorded check, must give the reference's digest.
+    Returns the oracle (HTMOracle)."""
+    seed, I, C, K = (int(rec[k]) for k in ("seed", "input_dim", "column_dim", "cell_dim"))
+    patterns, steps = int(rec["patterns"]), int(rec["steps"])
+    density, noise, jump, epsilon = (float(rec[k]) for k in ("density", "noise", "jump", "epsilon"))
+    np.random.seed(seed)
+    ora = HTMOracle(I, C, K, active_columns=round(C * 0.02), seed=seed)
+    assert digest(ora.spatial_pooler.permanence) == rec["permanence_digest"], "initial SP permanences"
+    if not np.isnan(epsilon):
+        ora.temporal_memory.eps = np.float32(epsilon)
+    bank, rng = make_inputs(seed + 1, patterns, I, density)
+    names, store_names = [str(n) for n in rec["step_field_names"]], [str(n) for n in rec["store_field_names"]]
+    stores = dict(zip(rec["store_steps"].tolist(), rec["store_digest"]))
+    assert len(rec["step_digest"]) == steps and len(rec["learning"]) == steps
+    hist = [None]
+    for t in range(steps):
+        x = bank[pattern_index(t, patterns, jump, rng)] ^ (rng.rand(I) < noise)
+        learning, back = bool(rec["learning"][t]), int(rec["back"][t])
+        if back < 0:
+            sp, tm = ora.step(x, learning=learning)
+        else:
+            sp = ora.spatial_pooler.step(x, learning=learning)
+            tm = ora.temporal_memory.step(sp.active_column, learning=learning, prev_state=hist[max(len(hist) - back, 1)])
+        hist.append(tm)
+        fields = step_fields(sp, tm)
+        assert list(fields) == names
+        for n, a, want in zip(names, fields.values(), rec["step_digest"][t]):
+            assert digest(a) == want, f"step {t}: {n} differs from the reference's"
+        if t in stores:
+            fields = oracle_store_fields(ora)
+            assert list(fields) == store_names
+            for n, a, want in zip(store_names, fields.values(), stores[t]):
+                assert digest(a) == want, f"step {t}: store field {n} differs from the reference's"
+    return ora
+
+
+# ---- the calls the reference makes to np.random.rand, replayed without it: stand-ins with the names and locals of the
+# reference's three callers (networks.py:87, projections.py:120, :235), which is all bithtm_amd.reference_bridge looks at
+
+def evaluate_cell_least_used(relevant_column, shape):
+    return np.random.rand(*shape)
+
+
+def add_edge(learning_output, winner_input, shape):
+    return np.random.rand(*shape)
+
+
+def fill_jittered_potential_info(state, shape):
+    return np.random.rand(*shape)
+
+
+RAND_CALLERS = ("evaluate_cell_least_used", "add_edge", "fill_jittered_potential_info")
+
+
+def call_rand_as(where, args, shape):
+    """np.random.rand(*shape) from a stand-in for the reference's function `where` with the arrays `args` as its locals."""
+    if where == "evaluate_cell_least_used":
+        return evaluate_cell_least_used(args[0], shape)
+    if where == "add_edge":
+        return add_edge(args[0], args[1], shape)
+    return fill_jittered_potential_info(SimpleNamespace(matching_segment=args[0]), shape)
+
+
+def rand_call_args(where, names):
+    """The locals of the reference's caller `where` that decide its draws."""
+    if where == "evaluate_cell_least_used":
+        return (np.asarray(names["relevant_column"], dtype=np.int64),)
+    if where == "add_edge":
+        return np.asarray(names["learning_output"], dtype=np.int64), np.asarray(names["winner_input"], dtype=np.int64)
+    return (np.asarray(names["state"].matching_segment, dtype=np.int64),)

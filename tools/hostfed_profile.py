@@ -1,5 +1,5 @@
 import os, sys
-sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import bench
 w = dict(bench.WORKLOAD)
 noisy, perm = bench.make_inputs(w)
