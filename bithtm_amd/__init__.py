@@ -15,3 +15,4 @@ from .regularizations import ExponentialBoosting, GlobalInhibition  # noqa: F401
 SpatialPooler = networks.SpatialPooler
 TemporalMemory = networks.TemporalMemory
 HierarchicalTemporalMemory = networks.HierarchicalTemporalMemory
+RunRecord = networks.RunRecord

@@ -39,6 +39,16 @@ class HtmInfo(C.Structure):
     ]
 
 
+class HtmStepRecord(C.Structure):
+    _fields_ = [(name, C.c_int32) for name in (
+        "active_columns", "bursting_columns", "predicted_columns_before", "predicted_columns", "active_cells", "winner_cells",
+        "segments", "new_segments")]
+
+
+class HtmRunRecord(C.Structure):
+    _fields_ = [("struct_bytes", C.c_uint32), ("records", C.c_void_p), ("active_column", C.c_void_p), ("column_prediction", C.c_void_p)]
+
+
 # htm_field
 F_ACTIVE_COLUMN, F_OVERLAPS, F_BOOSTED, F_DUTY_CYCLE, F_CELL_ACTIVATION, F_CELL_PREDICTION = 1, 2, 3, 4, 5, 6
 F_WINNER_WORDS, F_BURSTING, F_WINNER_CELL, F_SEG_CELL, F_SEG_NSYN, F_SEG_PRESYN, F_SEG_PERM = 7, 8, 9, 10, 11, 12, 13
@@ -63,6 +73,9 @@ EXPORTS = {
     "htm_tm_scan": (C.c_int, [C.c_void_p, C.c_void_p]),
     "htm_run": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     "htm_prepare": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
+    "htm_run_recorded": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(HtmRunRecord)]),
+    "htm_prepare_recorded": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
+    "htm_graph_count": (C.c_int, [C.c_void_p]),
     "htm_run_plan": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32]),
     "htm_bank_upload": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_void_p)]),
     "htm_shard_record_bytes": (C.c_int64, [C.c_void_p]),
@@ -93,6 +106,18 @@ EXPORTS = {
     "htm_trace_read": (C.c_int64, [C.c_void_p, C.c_void_p, C.c_int64]),
 }
 
+# The HIP runtime calls the binding makes itself -- the device buffers of run(record=...) -- resolved through the library's own
+# handle, i.e. in exactly the runtime the library is linked against (a second runtime in the process, such as one a torch
+# wheel bundles, would be a different device context: its pointers are not the library's).
+HIP_EXPORTS = {
+    "hipSetDevice": (C.c_int, [C.c_int]),
+    "hipMalloc": (C.c_int, [C.POINTER(C.c_void_p), C.c_size_t]),
+    "hipFree": (C.c_int, [C.c_void_p]),
+    "hipMemcpy": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]),
+    "hipGetErrorString": (C.c_char_p, [C.c_int]),
+}
+HIP_MEMCPY_DEVICE_TO_HOST = 2
+
 _lib = None
 
 
@@ -113,7 +138,7 @@ def load():
         lib = C.CDLL(path)
     except OSError as e:
         raise ImportError(f"cannot load {path}: {e}. There is no CPU fallback.") from e
-    for name, (restype, argtypes) in EXPORTS.items():
+    for name, (restype, argtypes) in list(EXPORTS.items()) + list(HIP_EXPORTS.items()):
         fn = getattr(lib, name)          # AttributeError if the symbol is missing
         fn.restype = restype
         fn.argtypes = argtypes

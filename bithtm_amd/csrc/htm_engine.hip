@@ -36,6 +36,7 @@
 #include "htm_sp_kernels.h"
 #include "htm_tm_kernels.h"
 #include "htm_pipeline.h"
+#include "htm_record.h"
 
 // ------------------------------------------------------------------------------------------
 // host side
@@ -92,7 +93,11 @@ struct htm_handle {
     bool import_keep;                     // htm_import_begin(HTM_IMPORT_PREV_STATE): the commit leaves the store, the step index and the sticky flags alone
     bool phase_open;                      // ... phases of the current (not yet closed) timestep have run: the Spatial Pooler
                                           // fields htm_read returns are that step's
-    // graphs keyed by (parity, learning, bank, n_inputs)
+    // recorded runs (htm_run_recorded): the device descriptor every record launch reads, and whether the steps being enqueued
+    // (or captured) now are recorded -- only inside such a call
+    RecDev *d_rec;
+    bool recording;
+    // graphs keyed by (parity + 2 if recorded, learning, bank, n_inputs)
     std::map<std::tuple<int, int, const void *, int>, hipGraphExec_t> graphs;
     // state import staging (htm_write of the MATCH_* / SEG_POTENTIAL fields, applied at commit)
     std::vector<int> imp_pot, imp_match_seg;
@@ -496,10 +501,19 @@ static void enqueue_rest(htm_handle *h, int p, const uint32_t *bank, int n_input
     }
 }
 
+// grid of the record launches (htm_record.h): REC_BLOCKS_MIN, or more where the winner list needs a thread per entry
+static int rec_blocks(const Dev &d) { return std::max(REC_BLOCKS_MIN, (d.k + 255) / 256); }
+
+// the record of the step of parity p, behind its last launch (htm_record.h); nothing outside a recorded call
+static void enqueue_record(htm_handle *h, int p) {
+    if (h->recording) LAUNCH(h, "record", k_rec_step, rec_blocks(h->d), 256, h->d, p, h->d_rec);
+}
+
 static int enqueue_step(htm_handle *h, const uint32_t *bank, int n_inputs, int learning, StepPlan plan, const uint32_t *host_input = nullptr) {
     if (!plan.sp_done && !plan.next_sp) enqueue_sp_front(h, bank, n_inputs, (int)(h->step_host & 1), step_wmode(h), host_input);
     enqueue_cold_start(h, bank, n_inputs, learning, plan);
     enqueue_rest(h, (int)(h->step_host & 1), bank, n_inputs, learning, plan);
+    enqueue_record(h, (int)(h->step_host & 1));
     h->step_host += 1;
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) { h->err = std::string("kernel launch: ") + hipGetErrorString(e); return HTM_ERR_HIP; }
@@ -1277,9 +1291,11 @@ extern "C" int htm_tm_scan(htm_handle *h, const uint32_t *active_words) {
     return HTM_OK;
 }
 
-// htm_run, or (dry) only the capture + instantiation of every hipGraph that htm_run call would replay
+// htm_run, or (dry) only the capture + instantiation of every hipGraph that htm_run call would replay.  record: the call is
+// recorded (htm_run_recorded / htm_prepare_recorded; rec = its buffers, checked by the caller, NULL when dry); rec_open: ...
+// and its descriptor is already filled (the rest of a call)
 static int run_or_prepare(htm_handle *h, const uint32_t *device_inputs, int32_t n_inputs, int32_t n_steps, int32_t learning,
-                          int32_t use_graph, bool dry) {
+                          int32_t use_graph, bool dry, bool record = false, const htm_run_record *rec = nullptr, bool rec_open = false) {
     if (h) flush_tail(h);
     if (!h || !device_inputs || n_inputs < 1 || n_steps < 0) return HTM_ERR_ARGUMENT;
     if (!h->cfg.enable_sp || !h->cfg.enable_tm) { h->err = "htm_run needs a handle with SP and TM"; return HTM_ERR_STATE; }
@@ -1302,6 +1318,14 @@ static int run_or_prepare(htm_handle *h, const uint32_t *device_inputs, int32_t 
     const bool cont = (use_graph & 4) && pipeline && n_steps > 0;
     if (dry && !graph) return HTM_OK;
     if (!dry) { int rc = close_open_phases(h); if (rc) return rc; }
+    struct RecordingOff { htm_handle *h; ~RecordingOff() { h->recording = false; } } recording_off{h};
+    if (record && !rec_open && !dry && n_steps > 0) {
+        // the descriptor of this call, and the columns the last completed step predicts (predicted_columns_before of record 0)
+        HIPCHK(h, hipMemsetAsync(h->d_rec, 0, sizeof(RecDev), h->stream));
+        LAUNCH(h, "record", k_rec_begin, rec_blocks(h->d), 256, h->d, (int)((h->step_host + 1) & 1), h->d_rec, rec->records,
+               rec->active_column, rec->column_prediction, (uint32_t)h->step_host, n_steps);
+    }
+    h->recording = record || rec_open;
     // The SP is ahead but the pipelined schedule is gone (another handle with its own stream has appeared on the device since,
     // or this call asks for HTM_RUN_NO_PIPELINE): the coming step is run as the LAST step of the run that went ahead -- its
     // launches hold no select finish, so nothing in them waits for another block -- and the rest of the call unpipelined.
@@ -1312,6 +1336,7 @@ static int run_or_prepare(htm_handle *h, const uint32_t *device_inputs, int32_t 
             const StepPlan last{true, false, false};
             if (h->ahead_lean) enqueue_lean(h, p, learning, device_inputs, n_inputs, last);
             else enqueue_pipelined(h, p, learning, device_inputs, n_inputs, last);
+            enqueue_record(h, p);
             h->step_host += 1;
             // (the four-launch schedule had begun the step after it: that front is never consumed)
             HIPCHK(h, hipMemsetAsync(h->d.hist0 + (size_t)(h->step_host & 1) * HIST0_PAR, 0, (size_t)HIST0_PAR * 4, h->stream));
@@ -1319,7 +1344,7 @@ static int run_or_prepare(htm_handle *h, const uint32_t *device_inputs, int32_t 
             hipError_t e = hipGetLastError();
             if (e != hipSuccess) { h->err = std::string("kernel launch: ") + hipGetErrorString(e); return HTM_ERR_HIP; }
         }
-        return run_or_prepare(h, device_inputs, n_inputs, n_steps - 1, learning, use_graph, false);
+        return run_or_prepare(h, device_inputs, n_inputs, n_steps - 1, learning, use_graph, false, false, nullptr, h->recording);
     }
     // Graphs hold the launches of one step, or of up to kGraphSteps consecutive steady-state steps (a graph
     // launch boundary costs about 5 us more than a kernel boundary inside a graph: tools/step_timeline.py).
@@ -1351,13 +1376,16 @@ static int run_or_prepare(htm_handle *h, const uint32_t *device_inputs, int32_t 
             if (!plan.sp_done && !plan.next_sp) enqueue_sp_front(h, device_inputs, n_inputs, p, step_wmode(h));    // eager
             enqueue_cold_start(h, device_inputs, n_inputs, learning, plan);                         // eager: first step of a pipelined run
         }
-        auto key = std::make_tuple(p, learning * 16 + (plan.sp_done ? 4 : 0) + (plan.next_sp ? 2 : 0) + (plan.next_front ? 1 : 0) + 32 * scan_spec_blocks(h) + (scan_pool_is_large(h) ? (1 << 20) : 0) + (h->emit_fused ? (1 << 21) : 0) + (span << 22) + (lean ? 8 : 0) + (step_wmode(h) ? (1 << 19) : 0),
+        auto key = std::make_tuple(p + (h->recording ? 2 : 0), learning * 16 + (plan.sp_done ? 4 : 0) + (plan.next_sp ? 2 : 0) + (plan.next_front ? 1 : 0) + 32 * scan_spec_blocks(h) + (scan_pool_is_large(h) ? (1 << 20) : 0) + (h->emit_fused ? (1 << 21) : 0) + (span << 22) + (lean ? 8 : 0) + (step_wmode(h) ? (1 << 19) : 0),
                                    (const void *)device_inputs, n_inputs);
         auto it = h->graphs.find(key);
         if (it == h->graphs.end()) {
             hipGraph_t graph_obj;
             HIPCHK(h, hipStreamBeginCapture(h->stream, hipStreamCaptureModeThreadLocal));
-            for (int i = 0; i < span; ++i) enqueue_rest(h, (p + i) & 1, device_inputs, n_inputs, learning, plan);
+            for (int i = 0; i < span; ++i) {
+                enqueue_rest(h, (p + i) & 1, device_inputs, n_inputs, learning, plan);
+                enqueue_record(h, (p + i) & 1);
+            }
             hipError_t e = hipStreamEndCapture(h->stream, &graph_obj);
             if (e != hipSuccess) { h->err = std::string("hipStreamEndCapture: ") + hipGetErrorString(e); return HTM_ERR_HIP; }
             hipGraphExec_t exec;
@@ -1392,6 +1420,42 @@ extern "C" int htm_run(htm_handle *h, const uint32_t *device_inputs, int32_t n_i
 
 extern "C" int htm_prepare(htm_handle *h, const uint32_t *device_inputs, int32_t n_inputs, int32_t n_steps, int32_t learning, int32_t use_graph) {
     return run_or_prepare(h, device_inputs, n_inputs, n_steps, learning, use_graph, true);
+}
+
+// htm_run with a per-step record (include/bithtm_hip.h).  dry (htm_prepare_recorded): the graphs only -- they do not depend
+// on the buffers, so there is no rec to check.
+static int run_recorded(htm_handle *h, const uint32_t *device_inputs, int32_t n_inputs, int32_t n_steps, int32_t learning,
+                        int32_t use_graph, const htm_run_record *rec, bool dry) {
+    if (!h) return HTM_ERR_ARGUMENT;
+    if (h->world > 1) { h->err = "htm_run_recorded: a sharded handle has no recorded run"; return HTM_ERR_STATE; }
+    // (k_rec_step sums its counts in 24-bit fields of one word: RecDev::acc)
+    if (h->d.C >= (1 << 24)) { h->err = "htm_run_recorded: column_dim must be below 2^24"; return HTM_ERR_STATE; }
+    if (!dry) {
+        if (rec->struct_bytes != sizeof(htm_run_record)) { h->err = "htm_run_recorded: struct_bytes != sizeof(htm_run_record)"; return HTM_ERR_ARGUMENT; }
+        if (!rec->records && !rec->active_column && !rec->column_prediction) { h->err = "htm_run_recorded: no record buffer given"; return HTM_ERR_ARGUMENT; }
+    }
+    if (!h->d_rec) {
+        HIPCHK(h, hipSetDevice(h->device));
+        int rc = dalloc(h, &h->d_rec, 1);
+        if (rc) return rc;
+    }
+    return run_or_prepare(h, device_inputs, n_inputs, n_steps, learning, use_graph, dry, true, rec);
+}
+
+extern "C" int htm_run_recorded(htm_handle *h, const uint32_t *device_inputs, int32_t n_inputs, int32_t n_steps, int32_t learning,
+                                int32_t use_graph, const htm_run_record *rec) {
+    if (!rec) return run_or_prepare(h, device_inputs, n_inputs, n_steps, learning, use_graph, false);
+    return run_recorded(h, device_inputs, n_inputs, n_steps, learning, use_graph, rec, false);
+}
+
+extern "C" int htm_prepare_recorded(htm_handle *h, const uint32_t *device_inputs, int32_t n_inputs, int32_t n_steps, int32_t learning,
+                                    int32_t use_graph) {
+    return run_recorded(h, device_inputs, n_inputs, n_steps, learning, use_graph, nullptr, true);
+}
+
+extern "C" int htm_graph_count(htm_handle *h) {
+    if (!h) return HTM_ERR_ARGUMENT;
+    return (int)std::min<size_t>(h->graphs.size() + h->shard_graphs.size(), 0x7fffffff);
 }
 
 extern "C" int htm_run_plan(htm_handle *h, int32_t n_steps, int32_t use_graph) {

@@ -32,6 +32,11 @@ def pack_bits(bits, words):
     return out.view(np.uint32)
 
 
+# run(record=...): the per-step fields htm_run_recorded can write, and the counts of one htm_step_record in its order
+RECORD_FIELDS = ("counters", "active_column", "column_prediction")
+RECORD_COUNTERS = tuple(name for name, _ in L.HtmStepRecord._fields_)
+
+
 def words_per_column(cell_dim):
     """32-bit words of cells per column in the device's dense cell arrays: one up to 32 cells, two up to 64."""
     return max(1, -(-int(cell_dim) // 32))
@@ -117,6 +122,8 @@ class Engine:
         self.h = handle
         self.steps = 0
         self._banks = []
+        self.device = int(device)
+        self._record_bufs = {}                      # run(record=...): device buffers kept for the next recorded call
         if self.has_sp:
             c0, c1 = self.column_range          # a sharded handle only ever reads its own rows
             self.set_permanence(proximal.permanence[c0:c1] if hasattr(type(proximal), "permanence") else proximal._permanence[c0:c1],
@@ -126,7 +133,9 @@ class Engine:
     def __del__(self):
         h, self.h = getattr(self, "h", None), None
         if h:
-            self.lib.htm_destroy(h)
+            self.lib.htm_destroy(h)             # (synchronises its stream: the record buffers are idle after it)
+        for ptr, _ in getattr(self, "_record_bufs", {}).values():
+            self.lib.hipFree(ptr)
 
     # ---- plumbing
     def _check(self, rc, what):
@@ -291,16 +300,75 @@ class Engine:
         self._check(self.lib.htm_bank_upload(self.h, packed.ctypes.data_as(C.c_void_p), n, C.byref(ptr)), "htm_bank_upload")
         return ptr.value
 
-    def run(self, device_bank, n_inputs, n_steps, learning=True, use_graph=True, pipeline=True, continuing=False):
-        """`continuing`: the next call is another run() on the same bank (HTM_RUN_CONTINUE, include/bithtm_hip.h)."""
+    def run(self, device_bank, n_inputs, n_steps, learning=True, use_graph=True, pipeline=True, continuing=False, record=None):
+        """`continuing`: the next call is another run() on the same bank (HTM_RUN_CONTINUE, include/bithtm_hip.h).
+        `record`: None, or the fields of a per-step record to keep (RECORD_FIELDS): the call then goes to htm_run_recorded and
+        returns {field: numpy array over the n_steps steps} -- "counters" int32[n, 8] (htm_step_record, RECORD_COUNTERS order),
+        "active_column" int32[n, k], "column_prediction" uint32[n, ceil(C / 32)] -- read back after one synchronisation."""
         flags = (1 if use_graph else 0) | (0 if pipeline else 2) | (4 if continuing else 0)
-        self._check(self.lib.htm_run(self.h, C.c_void_p(device_bank), int(n_inputs), int(n_steps), int(bool(learning)),
-                                     flags), "htm_run")
+        if record is None:
+            self._check(self.lib.htm_run(self.h, C.c_void_p(device_bank), int(n_inputs), int(n_steps), int(bool(learning)),
+                                         flags), "htm_run")
+            self.steps += n_steps
+            return None
+        fields = tuple(record)
+        unknown = set(fields) - set(RECORD_FIELDS)
+        if unknown or not fields:
+            raise ValueError(f"record: fields from {RECORD_FIELDS}, at least one (got {fields})")
+        n = int(n_steps)
+        shapes = {"counters": (len(RECORD_COUNTERS), np.int32), "active_column": (self.active_columns, np.int32),
+                  "column_prediction": ((self.column_dim + 31) // 32, np.uint32)}
+        ptrs = {f: self._record_buffer(f, max(n, 1) * shapes[f][0]) for f in fields}
+        rec = L.HtmRunRecord()
+        rec.struct_bytes = C.sizeof(L.HtmRunRecord)
+        rec.records, rec.active_column, rec.column_prediction = (ptrs.get(f) for f in RECORD_FIELDS)
+        self._check(self.lib.htm_run_recorded(self.h, C.c_void_p(device_bank), int(n_inputs), n, int(bool(learning)), flags,
+                                              C.byref(rec)), "htm_run_recorded")
         self.steps += n_steps
+        self.sync()                                 # (the records are written on the engine's stream)
+        return {f: self._record_read(f, n * shapes[f][0], shapes[f][1]).reshape(n, shapes[f][0]) for f in fields}
 
-    def prepare(self, device_bank, n_inputs, n_steps, learning=True, use_graph=True, pipeline=True, continuing=False):
-        """Build (capture + instantiate) the hipGraphs the run() call with these arguments will replay."""
+    # The record buffers are device memory of the HIP runtime the library itself is linked against (_lib.HIP_EXPORTS), kept for
+    # the next recorded call and grown geometrically.
+    def _record_buffer(self, field, elements):
+        """Device address of a buffer of at least `elements` 32-bit words for one record field."""
+        ptr, size = self._record_bufs.get(field, (None, 0))
+        if ptr is None or size < elements:
+            size = max(elements, 2 * size)
+            new = C.c_void_p()
+            self._hip_check(self.lib.hipSetDevice(self.device), "hipSetDevice")
+            self._hip_check(self.lib.hipMalloc(C.byref(new), 4 * size), f"hipMalloc({4 * size} bytes)")
+            if ptr is not None:
+                self.sync()
+                self.lib.hipFree(ptr)
+            ptr = new.value
+            self._record_bufs[field] = (ptr, size)
+        return ptr
+
+    def _record_read(self, field, elements, dtype):
+        """The first `elements` words of a record buffer (after sync())."""
+        out = np.empty(elements, dtype=dtype)
+        if elements:
+            self._hip_check(self.lib.hipMemcpy(out.ctypes.data_as(C.c_void_p), self._record_bufs[field][0], 4 * elements,
+                                               L.HIP_MEMCPY_DEVICE_TO_HOST), "hipMemcpy")
+        return out
+
+    def _hip_check(self, rc, what):
+        if rc != 0:
+            raise HtmError(f"{what} failed ({rc}): {self.lib.hipGetErrorString(rc).decode()}")
+
+    def graph_count(self):
+        """hipGraphs this engine holds (htm_graph_count: captured and instantiated so far)."""
+        return self._check(self.lib.htm_graph_count(self.h), "htm_graph_count")
+
+    def prepare(self, device_bank, n_inputs, n_steps, learning=True, use_graph=True, pipeline=True, continuing=False, record=False):
+        """Build (capture + instantiate) the hipGraphs the run() call with these arguments will replay (`record`: a recorded
+        run(), whatever its fields -- htm_prepare_recorded)."""
         flags = (1 if use_graph else 0) | (0 if pipeline else 2) | (4 if continuing else 0)
+        if record:
+            self._check(self.lib.htm_prepare_recorded(self.h, C.c_void_p(device_bank), int(n_inputs), int(n_steps),
+                                                      int(bool(learning)), flags), "htm_prepare_recorded")
+            return
         self._check(self.lib.htm_prepare(self.h, C.c_void_p(device_bank), int(n_inputs), int(n_steps), int(bool(learning)),
                                          flags), "htm_prepare")
 

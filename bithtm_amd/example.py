@@ -4,6 +4,7 @@ the three counters: :55-57), so that its output can be compared line by line.
 
     python -m bithtm_amd.example --epochs 8
     python -m bithtm_amd.example --epochs 8 --batched   # one C-ABI call per epoch, hipGraph replay
+    python -m bithtm_amd.example --epochs 8 --batched_report   # ... recorded: the per-step lines of the default mode
     python -m bithtm_amd.example --epochs 8 --use_reference_implementation   # example.py:30,36-37 (needs the user's `bithtm`)
 """
 
@@ -38,6 +39,9 @@ def parse(argv):
     ap.add_argument("--batched", action="store_true",
                     help="run each epoch with HierarchicalTemporalMemory.run (no per-step read-back) and "
                          "report timesteps/s per epoch instead of the per-step counters")
+    ap.add_argument("--batched_report", action="store_true",
+                    help="run each epoch as one recorded HierarchicalTemporalMemory.run and print the per-step counters "
+                         "from its record (the same lines as the default mode)")
     return ap.parse_args(argv)
 
 
@@ -86,14 +90,24 @@ def run_batched(htm, bank, opts, out):
         print(f"epoch {epoch:{width}d}: {rate:.0f} timesteps/s, {htm.engine.info().segments} segments", file=out)
 
 
+def run_batched_report(htm, bank, opts, out):
+    # (one draw of the epoch's noise: the same MT19937 values, in the same order, as run_stepwise's draw per step)
+    report = Report(opts, htm.spatial_pooler.active_columns)
+    for epoch in range(opts.epochs):
+        noisy = bank ^ (np.random.rand(*bank.shape) < opts.input_noise_probability)
+        rec = htm.run(noisy, len(noisy), record=True)
+        for index, (b, c, i) in enumerate(zip(rec.bursting_columns, rec.correct_columns, rec.incorrect_columns)):
+            print(report.line(epoch, index, int(b), int(c), int(i)), file=out)
+
+
 def main(argv=None, out=sys.stdout):
     opts = parse(argv)
     bank = np.random.rand(opts.input_patterns, opts.input_dim) < opts.input_density
     if opts.use_reference_implementation:
         # example.py:7-12: the same network with `temporal_memory=` the textbook implementation -- the user's package, imported
         # at the user's request (this package ships no copy of it and no CPU path of its own)
-        if opts.batched:
-            raise SystemExit("--batched runs the fused device step; --use_reference_implementation steps a host-side Temporal Memory")
+        if opts.batched or opts.batched_report:
+            raise SystemExit("--batched / --batched_report run the fused device step; --use_reference_implementation steps a host-side Temporal Memory")
         try:
             from bithtm.reference_implementations import TemporalMemory as ReferenceTemporalMemory
         except ImportError as e:
@@ -103,7 +117,7 @@ def main(argv=None, out=sys.stdout):
     else:
         htm = HierarchicalTemporalMemory(opts.input_dim, opts.column_dim, opts.cell_dim, seed=opts.seed)
     began = time.time()
-    (run_batched if opts.batched else run_stepwise)(htm, bank, opts, out)
+    (run_batched if opts.batched else run_batched_report if opts.batched_report else run_stepwise)(htm, bank, opts, out)
     print(f"{time.time() - began} seconds.", file=out)
 
 

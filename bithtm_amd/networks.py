@@ -26,7 +26,7 @@ import weakref
 import numpy as np
 
 from . import _lib as L
-from .engine import Engine, words_to_bool
+from .engine import RECORD_COUNTERS, RECORD_FIELDS, Engine, words_to_bool
 from .projections import DenseProjection, PredictiveProjection
 from .regularizations import ExponentialBoosting, GlobalInhibition, _Placeholder
 
@@ -441,6 +441,56 @@ class _DistalState:
         self.__dict__.update(d)
 
 
+class RunRecord:
+    """What HierarchicalTemporalMemory.run(record=...) returns: one numpy array per field over the steps of the call, step i
+    of the call in row i (include/bithtm_hip.h, htm_run_recorded, for the meaning of every count).
+      step_index                     int64[steps]   timesteps processed before each step (the engine's step index)
+      active_columns, bursting_columns, predicted_columns_before, predicted_columns, active_cells, winner_cells, segments,
+      new_segments                   int32[steps]   the counters ("counters"; None when not recorded)
+      active_column                  int32[steps, k]   sp_state.active_column of each step ("active_column", else None)
+      column_prediction              bool[steps, C]    cell_prediction.any(axis=1) of each step ("column_prediction", else None)
+    and, from the counters, the per-step report of example.py:55-57 and the raw anomaly score:
+      correct_columns   = active_columns - bursting_columns
+      incorrect_columns = predicted_columns_before - correct_columns
+      anomaly_score     = 1 - correct_columns / active_columns   (float64; 0 for a step without active columns)"""
+
+    def __init__(self, step_index, counters=None, active_column=None, column_prediction=None):
+        self.step_index = np.asarray(step_index, dtype=np.int64)
+        self.fields = tuple(f for f, v in zip(RECORD_FIELDS, (counters, active_column, column_prediction)) if v is not None)
+        for i, name in enumerate(RECORD_COUNTERS):
+            setattr(self, name, None if counters is None else np.ascontiguousarray(counters[:, i], dtype=np.int32))
+        self.active_column = active_column
+        self.column_prediction = column_prediction
+
+    def __len__(self):
+        return len(self.step_index)
+
+    @property
+    def correct_columns(self):
+        return None if self.active_columns is None else self.active_columns - self.bursting_columns
+
+    @property
+    def incorrect_columns(self):
+        return None if self.active_columns is None else self.predicted_columns_before - self.correct_columns
+
+    @property
+    def anomaly_score(self):
+        if self.active_columns is None:
+            return None
+        active = self.active_columns.astype(np.float64)
+        return np.where(active > 0, 1.0 - self.correct_columns / np.maximum(active, 1.0), 0.0)
+
+
+def _record_fields(record):
+    """run(record=...) -> the fields asked for: True = the counters; else a tuple of RECORD_FIELDS names."""
+    if record is True:
+        return ("counters",)
+    fields = (record,) if isinstance(record, str) else tuple(record)
+    if not fields or set(fields) - set(RECORD_FIELDS):
+        raise ValueError(f"record: True or a tuple of {RECORD_FIELDS} (got {record!r})")
+    return tuple(f for f in RECORD_FIELDS if f in fields)
+
+
 class HierarchicalTemporalMemory:
     """networks.py:131-149.  With default (or bithtm_amd) components both layers share ONE device
     engine and a timestep is a single C-ABI call (`htm_step`)."""
@@ -549,15 +599,19 @@ class HierarchicalTemporalMemory:
         with np.load(path) as z:
             self.load_state_dict({k: z[k] for k in z.files})
 
-    def run(self, inputs, steps, learning=True, use_graph=True, pipeline=True, continuing=False):
+    def run(self, inputs, steps, learning=True, use_graph=True, pipeline=True, continuing=False, record=None):
         """`steps` timesteps over the rows of the boolean matrix `inputs`, cycled, with the input
         bank resident in device memory and no per-step host work (the loop of example.py:48-53).
-        Returns nothing; read `temporal_memory.last_state` or call process() afterwards.  `continuing=True`: the
+        Returns None; read `temporal_memory.last_state` or call process() afterwards.  `continuing=True`: the
         caller streams its input in chunks and the next call is another run() on the same inputs (HTM_RUN_CONTINUE:
-        the Spatial Pooler keeps working ahead across the calls; finish with a run() without it)."""
+        the Spatial Pooler keeps working ahead across the calls; finish with a run() without it).
+        `record`: a per-step record written on the device and read back once per call (htm_run_recorded) -- True for the
+        counters, or a tuple of "counters", "active_column", "column_prediction"; the call then returns a RunRecord over
+        its `steps` steps."""
         eng = self._fused_engine("run()")
         if not self.spatial_pooler._plain:
             raise RuntimeError("run() keeps the whole loop on the device: not available with plug-in objects that live on the host")
+        fields = None if record is None else _record_fields(record)
         retire_states(eng)
         inputs = np.asarray(inputs, dtype=np.bool_)
         key = (inputs.shape, inputs.tobytes())
@@ -568,7 +622,7 @@ class HierarchicalTemporalMemory:
         # the free segments are expected to last (2 x active_columns new segments per step: every column bursting, twice),
         # with a look at the pool between them.  An overflow inside a batch is still reported, never silent.
         auto, k = getattr(eng, "_auto_grow", False), self.active_columns
-        done = 0
+        done, parts, first_step = 0, [], eng.steps
         while done < steps:
             n = steps - done
             if auto:
@@ -581,11 +635,24 @@ class HierarchicalTemporalMemory:
                     _grow_if_needed(eng, 2 * k, force_check=True)
                 n = max(1, min(n, eng._free_segments // (2 * k) - 1))
             last = done + n >= steps
-            eng.run(bank[1], inputs.shape[0], n, learning=learning, use_graph=use_graph, pipeline=pipeline, continuing=continuing and last)
+            part = eng.run(bank[1], inputs.shape[0], n, learning=learning, use_graph=use_graph, pipeline=pipeline,
+                           continuing=continuing and last, record=fields)
+            if fields is not None:
+                parts.append(part)
             self._streaming = bool(continuing and last and pipeline)
             done += n
         self.temporal_memory._new_state(None)
         eng.check_capacity()
+        if fields is None:
+            return None
+        # (one contiguous record, however many batches the pool's growth cut the call into)
+        empty = {"counters": np.zeros((0, len(RECORD_COUNTERS)), np.int32), "active_column": np.zeros((0, k), np.int32),
+                 "column_prediction": np.zeros((0, (self.column_dim + 31) // 32), np.uint32)}
+        whole = {f: np.concatenate([p[f] for p in parts]) if parts else empty[f] for f in fields}
+        if "column_prediction" in whole:
+            words = np.ascontiguousarray(whole["column_prediction"])
+            whole["column_prediction"] = np.unpackbits(words.view(np.uint8), axis=1, bitorder="little")[:, :self.column_dim].astype(bool)
+        return RunRecord(first_step + np.arange(steps, dtype=np.int64), **whole)
 
 
 def _grow_if_needed(eng, per_step, every=128, force_check=False):

@@ -256,6 +256,54 @@ int htm_prepare(htm_handle *h, const uint32_t *device_inputs, int32_t n_inputs, 
 #define HTM_PLAN_SCAN_LARGE 8
 int htm_run_plan(htm_handle *h, int32_t n_steps, int32_t use_graph);
 
+/* htm_run with a per-step record, written on the device and read back by the caller once per call (the per-step report of
+ * example.py:55-57 without a State read-back per step).  Record i belongs to the i-th step of THIS call; "the state before"
+ * a step is the reference's last_state before its process() call (for a fresh handle: no predictions).
+ *   htm_step_record      eight int32 counts per step, in reference terms:
+ *     active_columns            len(sp_state.active_column)
+ *     bursting_columns          tm_state.active_column_bursting.sum()                      (networks.py:97)
+ *     predicted_columns_before  last_state.cell_prediction.any(axis=1).sum() of the state before the step
+ *     predicted_columns         the same for this step's cell_prediction                   (networks.py:122)
+ *     active_cells              len(tm_state.active_cell[0])
+ *     winner_cells              len(tm_state.winner_cell[0])
+ *     segments                  htm_info.segments after the step
+ *     new_segments              htm_info.recycled_segments + appended_segments of the step
+ *   htm_run_record       struct_bytes = sizeof(htm_run_record), then DEVICE pointers, NULL = not requested (at least one set):
+ *     records                   htm_step_record[n_steps]
+ *     active_column             int32[n_steps * k]: sp_state.active_column of each step, ascending
+ *     column_prediction         uint32[n_steps * ceil(C / 32)]: bit c of a step's words = cell_prediction[c].any()
+ * Buffer sizes are the caller's contract, as for htm_run's bank.  rec == NULL: exactly htm_run.  All use_graph bits keep their
+ * meaning; the records of a continuing call (HTM_RUN_CONTINUE) hold its own steps only, never the step the Spatial Pooler has
+ * begun ahead.  The graphs of recorded steps are captured once (htm_prepare_recorded builds them ahead, as htm_prepare does
+ * for htm_run) and read the buffers from a descriptor the call fills on the device: another call with other buffers
+ * replays the same graphs.  A column-sharded handle, or column_dim of 2^24 or more: HTM_ERR_STATE; a wrong struct_bytes or no
+ * buffer: HTM_ERR_ARGUMENT. */
+typedef struct htm_step_record {
+    int32_t active_columns;
+    int32_t bursting_columns;
+    int32_t predicted_columns_before;
+    int32_t predicted_columns;
+    int32_t active_cells;
+    int32_t winner_cells;
+    int32_t segments;
+    int32_t new_segments;
+} htm_step_record;
+
+typedef struct htm_run_record {
+    uint32_t struct_bytes;              /* sizeof(htm_run_record), checked */
+    htm_step_record *records;           /* device, [n_steps], or NULL */
+    int32_t *active_column;             /* device, [n_steps * active_columns], or NULL */
+    uint32_t *column_prediction;        /* device, [n_steps * ceil(column_dim / 32)], or NULL */
+} htm_run_record;
+
+int htm_run_recorded(htm_handle *h, const uint32_t *device_inputs, int32_t n_inputs, int32_t n_steps, int32_t learning,
+                     int32_t use_graph, const htm_run_record *rec);
+int htm_prepare_recorded(htm_handle *h, const uint32_t *device_inputs, int32_t n_inputs, int32_t n_steps, int32_t learning,
+                         int32_t use_graph);
+/* hipGraphs the handle holds (captured and instantiated by htm_run / htm_prepare / htm_shard_run and their recorded forms);
+ * diagnostic: a recorded call with other buffers replays the graphs of the one before and adds none. */
+int htm_graph_count(htm_handle *h);
+
 /* Convenience for callers without their own device allocator: copy n_inputs packed inputs
  * (ceil(input_dim/32) host words each, as for htm_step) into a handle-owned device bank laid out
  * as htm_run expects, and return its device address.  Freed by htm_destroy. */
