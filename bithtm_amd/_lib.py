@@ -75,6 +75,8 @@ EXPORTS = {
     "htm_prepare": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     "htm_run_recorded": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(HtmRunRecord)]),
     "htm_prepare_recorded": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
+    "htm_reset": (C.c_int, [C.c_void_p]),
+    "htm_set_run_resets": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32]),
     "htm_graph_count": (C.c_int, [C.c_void_p]),
     "htm_run_plan": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32]),
     "htm_bank_upload": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_void_p)]),
@@ -116,6 +118,7 @@ HIP_EXPORTS = {
     "hipMemcpy": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]),
     "hipGetErrorString": (C.c_char_p, [C.c_int]),
 }
+HIP_MEMCPY_HOST_TO_DEVICE = 1
 HIP_MEMCPY_DEVICE_TO_HOST = 2
 
 _lib = None

@@ -37,6 +37,7 @@
 #include "htm_tm_kernels.h"
 #include "htm_pipeline.h"
 #include "htm_record.h"
+#include "htm_reset.h"
 
 // ------------------------------------------------------------------------------------------
 // host side
@@ -97,7 +98,13 @@ struct htm_handle {
     // (or captured) now are recorded -- only inside such a call
     RecDev *d_rec;
     bool recording;
-    // graphs keyed by (parity + 2 if recorded, learning, bank, n_inputs)
+    // sequence resets of htm_run (htm_set_run_resets): the caller's device bits and bank size, the device descriptor the reset
+    // launches read (filled by each call that has bits), and whether the steps being enqueued (or captured) now reset
+    const uint32_t *reset_bits;
+    int reset_n;
+    ResetDev *d_reset;
+    bool resetting;
+    // graphs keyed by (parity + 2 if recorded + 4 if resetting, learning, bank, n_inputs)
     std::map<std::tuple<int, int, const void *, int>, hipGraphExec_t> graphs;
     // state import staging (htm_write of the MATCH_* / SEG_POTENTIAL fields, applied at commit)
     std::vector<int> imp_pot, imp_match_seg;
@@ -490,7 +497,16 @@ static void enqueue_cold_start(htm_handle *h, const uint32_t *bank, int n_inputs
     LAUNCH(h, "sp_select", k_sel_pass, h->sel_blocks, RB, d, 1, p ^ 1);
 }
 
+// grid of the reset launch (htm_reset.h): a grid-stride pass over the cell words and per-cell maxima
+static int reset_blocks(const Dev &d) { return std::max(1, std::min(1024, (d.C * d.KP + 255) / 256)); }
+
+// in a run with reset bits: the reset of the step of parity p if its bank row asks for one (before its activation role)
+static void enqueue_run_reset(htm_handle *h, int p) {
+    if (h->resetting) LAUNCH(h, "tm_reset", k_tm_reset, reset_blocks(h->d), 256, h->d, p, h->d_reset, h->recording ? h->d_rec : nullptr, 0u);
+}
+
 static void enqueue_rest(htm_handle *h, int p, const uint32_t *bank, int n_inputs, int learning, StepPlan plan) {
+    enqueue_run_reset(h, p);
     if ((plan.sp_done || plan.next_sp) && can_lean(h)) {
         enqueue_lean(h, p, learning, bank, n_inputs, plan);
     } else if (plan.sp_done || plan.next_sp) {
@@ -1316,9 +1332,14 @@ static int run_or_prepare(htm_handle *h, const uint32_t *device_inputs, int32_t 
     // keep looking ahead past the end of this call -- where the pipelined schedule is available (the flag is a promise of
     // the caller's, not a demand: without the schedule the call simply leaves nothing outstanding)
     const bool cont = (use_graph & 4) && pipeline && n_steps > 0;
+    if (h->reset_bits && h->reset_n != n_inputs) { h->err = "htm_run: the reset bits were set for a bank of another n_inputs (htm_set_run_resets)"; return HTM_ERR_ARGUMENT; }
     if (dry && !graph) return HTM_OK;
     if (!dry) { int rc = close_open_phases(h); if (rc) return rc; }
-    struct RecordingOff { htm_handle *h; ~RecordingOff() { h->recording = false; } } recording_off{h};
+    struct RecordingOff { htm_handle *h; ~RecordingOff() { h->recording = false; h->resetting = false; } } recording_off{h};
+    if (h->reset_bits && !h->d_reset) { int rc = dalloc(h, &h->d_reset, 1); if (rc) return rc; }
+    if (h->reset_bits && !rec_open && !dry && n_steps > 0)
+        LAUNCH(h, "tm_reset", k_reset_begin, 1, 64, h->d_reset, h->reset_bits, (int32_t)n_inputs);
+    h->resetting = h->reset_bits != nullptr;
     if (record && !rec_open && !dry && n_steps > 0) {
         // the descriptor of this call, and the columns the last completed step predicts (predicted_columns_before of record 0)
         HIPCHK(h, hipMemsetAsync(h->d_rec, 0, sizeof(RecDev), h->stream));
@@ -1334,6 +1355,7 @@ static int run_or_prepare(htm_handle *h, const uint32_t *device_inputs, int32_t 
         {
             const int p = (int)(h->step_host & 1);
             const StepPlan last{true, false, false};
+            enqueue_run_reset(h, p);
             if (h->ahead_lean) enqueue_lean(h, p, learning, device_inputs, n_inputs, last);
             else enqueue_pipelined(h, p, learning, device_inputs, n_inputs, last);
             enqueue_record(h, p);
@@ -1376,7 +1398,7 @@ static int run_or_prepare(htm_handle *h, const uint32_t *device_inputs, int32_t 
             if (!plan.sp_done && !plan.next_sp) enqueue_sp_front(h, device_inputs, n_inputs, p, step_wmode(h));    // eager
             enqueue_cold_start(h, device_inputs, n_inputs, learning, plan);                         // eager: first step of a pipelined run
         }
-        auto key = std::make_tuple(p + (h->recording ? 2 : 0), learning * 16 + (plan.sp_done ? 4 : 0) + (plan.next_sp ? 2 : 0) + (plan.next_front ? 1 : 0) + 32 * scan_spec_blocks(h) + (scan_pool_is_large(h) ? (1 << 20) : 0) + (h->emit_fused ? (1 << 21) : 0) + (span << 22) + (lean ? 8 : 0) + (step_wmode(h) ? (1 << 19) : 0),
+        auto key = std::make_tuple(p + (h->recording ? 2 : 0) + (h->resetting ? 4 : 0), learning * 16 + (plan.sp_done ? 4 : 0) + (plan.next_sp ? 2 : 0) + (plan.next_front ? 1 : 0) + 32 * scan_spec_blocks(h) + (scan_pool_is_large(h) ? (1 << 20) : 0) + (h->emit_fused ? (1 << 21) : 0) + (span << 22) + (lean ? 8 : 0) + (step_wmode(h) ? (1 << 19) : 0),
                                    (const void *)device_inputs, n_inputs);
         auto it = h->graphs.find(key);
         if (it == h->graphs.end()) {
@@ -2452,6 +2474,33 @@ extern "C" int htm_import_commit(htm_handle *h, int32_t segments, int32_t matchi
         }
         HIPCHK(h, hipStreamSynchronize(h->stream));
     }
+    return HTM_OK;
+}
+
+// A sequence reset on the device (htm_reset.h): after the held-back tail, one launch, no host copy, no wait.
+extern "C" int htm_reset(htm_handle *h) {
+    if (!h) return HTM_ERR_ARGUMENT;
+    flush_tail(h);
+    REJECT_WHEN_AHEAD(h);
+    if (h->world > 1) { h->err = "htm_reset: not available on a column-sharded handle"; return HTM_ERR_STATE; }
+    if (h->shard_open) { h->err = "htm_reset: a step opened with htm_shard_begin is not finished"; return HTM_ERR_STATE; }
+    if (!h->cfg.enable_tm) { h->err = "htm_reset: the handle has no Temporal Memory"; return HTM_ERR_STATE; }
+    HIPCHK(h, hipSetDevice(h->device));
+    int rc = close_open_phases(h);
+    if (rc) return rc;
+    LAUNCH(h, "tm_reset", k_tm_reset, reset_blocks(h->d), 256, h->d, (int)(h->step_host & 1), (const ResetDev *)nullptr, (RecDev *)nullptr,
+           (uint32_t)h->step_host);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) { h->err = std::string("kernel launch: ") + hipGetErrorString(e); return HTM_ERR_HIP; }
+    return HTM_OK;
+}
+
+extern "C" int htm_set_run_resets(htm_handle *h, const uint32_t *device_bits, int32_t n_inputs) {
+    if (!h) return HTM_ERR_ARGUMENT;
+    if (device_bits && n_inputs < 1) { h->err = "htm_set_run_resets: n_inputs must be at least 1"; return HTM_ERR_ARGUMENT; }
+    if (h->world > 1) { h->err = "htm_set_run_resets: not available on a column-sharded handle"; return HTM_ERR_STATE; }
+    h->reset_bits = device_bits;
+    h->reset_n = device_bits ? n_inputs : 0;
     return HTM_OK;
 }
 

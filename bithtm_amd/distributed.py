@@ -130,6 +130,10 @@ class ShardedHTM:
     compute = process
 
     # ---- checkpoint / hand-off: the state of the whole model, as an unsharded handle exports and imports it
+    def reset(self):
+        """Sequence resets are not available on column-sharded models (htm_reset rejects a sharded handle)."""
+        raise NotImplementedError("sequence resets are not available on a column-sharded model")
+
     def export_tm_state(self):
         """Collective: every rank contributes its part (torch.distributed.all_gather_object; not a fast path)."""
         import torch.distributed as dist
@@ -209,6 +213,10 @@ class LocalGroup:
         self._check(self.lib.htm_shard_group_step(self._handles, self.world, None, 1, packed.ctypes.data_as(C.c_void_p), int(bool(learning))))
         for e in self.engines:
             e.steps += 1
+
+    def reset(self):
+        """Sequence resets are not available on column-sharded models (htm_reset rejects a sharded handle)."""
+        raise NotImplementedError("sequence resets are not available on a column-sharded model")
 
     def export_tm_state(self):
         return merge_shard_states([e.export_tm_state() for e in self.engines], self.column_dim, self.cell_dim)

@@ -124,6 +124,7 @@ class Engine:
         self._banks = []
         self.device = int(device)
         self._record_bufs = {}                      # run(record=...): device buffers kept for the next recorded call
+        self._reset_bufs = {}                       # run(resets=...): packed reset bits per content
         if self.has_sp:
             c0, c1 = self.column_range          # a sharded handle only ever reads its own rows
             self.set_permanence(proximal.permanence[c0:c1] if hasattr(type(proximal), "permanence") else proximal._permanence[c0:c1],
@@ -135,6 +136,8 @@ class Engine:
         if h:
             self.lib.htm_destroy(h)             # (synchronises its stream: the record buffers are idle after it)
         for ptr, _ in getattr(self, "_record_bufs", {}).values():
+            self.lib.hipFree(ptr)
+        for ptr in getattr(self, "_reset_bufs", {}).values():
             self.lib.hipFree(ptr)
 
     # ---- plumbing
@@ -200,6 +203,34 @@ class Engine:
             self.write(L.F_CELL_MAX_JITTER, np.asarray(distal.max_jittered_potential, dtype=np.float32).view(np.uint32), np.uint32)
         self._check(self.lib.htm_import_commit(self.h, int(S), int(M), len(winners), int(distal is not None), int(winner_flat is not None)),
                     "htm_import_commit")
+
+    def reset(self):
+        """A sequence reset (htm_reset): the previous step becomes TemporalMemory.get_empty_state() on the device -- what
+        import_prev_state of the empty state leaves, without the host copies."""
+        self._check(self.lib.htm_reset(self.h), "htm_reset")
+
+    def upload_resets(self, resets):
+        """bool[n] (reset before every step that reads bank row r) -> device address of the packed bits htm_set_run_resets
+        takes.  Kept by the engine per content (freed with it)."""
+        bits = np.ascontiguousarray(np.asarray(resets, dtype=np.bool_).ravel())
+        key = (bits.size, bits.tobytes())
+        bufs = self._reset_bufs
+        if key not in bufs:
+            words = np.zeros((bits.size + 31) // 32 * 4, dtype=np.uint8)
+            pb = np.packbits(bits, bitorder="little")
+            words[:pb.size] = pb
+            ptr = C.c_void_p()
+            self._hip_check(self.lib.hipSetDevice(self.device), "hipSetDevice")
+            self._hip_check(self.lib.hipMalloc(C.byref(ptr), words.size), f"hipMalloc({words.size} bytes)")
+            self._hip_check(self.lib.hipMemcpy(ptr, words.ctypes.data_as(C.c_void_p), words.size, L.HIP_MEMCPY_HOST_TO_DEVICE),
+                            "hipMemcpy")
+            bufs[key] = ptr.value
+        return bufs[key]
+
+    def set_run_resets(self, device_bits, n_inputs):
+        """Reset bits of the later run() / prepare() calls on banks of n_inputs rows (htm_set_run_resets); None clears them."""
+        self._check(self.lib.htm_set_run_resets(self.h, C.c_void_p(device_bits) if device_bits else None, int(n_inputs)),
+                    "htm_set_run_resets")
 
     def set_epsilon(self, epsilon):
         """TemporalMemory.process(epsilon=) (networks.py:91): 0 < epsilon <= 1, compared as float32; stays until set again."""
@@ -300,7 +331,19 @@ class Engine:
         self._check(self.lib.htm_bank_upload(self.h, packed.ctypes.data_as(C.c_void_p), n, C.byref(ptr)), "htm_bank_upload")
         return ptr.value
 
-    def run(self, device_bank, n_inputs, n_steps, learning=True, use_graph=True, pipeline=True, continuing=False, record=None):
+    def run(self, device_bank, n_inputs, n_steps, learning=True, use_graph=True, pipeline=True, continuing=False, record=None,
+            resets=None):
+        """`resets`: None, or the device address of reset bits for this bank (upload_resets): a sequence reset before every
+        step that reads a row whose bit is set (htm_set_run_resets, set for this call only)."""
+        if resets is None:
+            return self._run(device_bank, n_inputs, n_steps, learning, use_graph, pipeline, continuing, record)
+        self.set_run_resets(resets, n_inputs)
+        try:
+            return self._run(device_bank, n_inputs, n_steps, learning, use_graph, pipeline, continuing, record)
+        finally:
+            self.set_run_resets(None, 0)
+
+    def _run(self, device_bank, n_inputs, n_steps, learning=True, use_graph=True, pipeline=True, continuing=False, record=None):
         """`continuing`: the next call is another run() on the same bank (HTM_RUN_CONTINUE, include/bithtm_hip.h).
         `record`: None, or the fields of a per-step record to keep (RECORD_FIELDS): the call then goes to htm_run_recorded and
         returns {field: numpy array over the n_steps steps} -- "counters" int32[n, 8] (htm_step_record, RECORD_COUNTERS order),
@@ -361,9 +404,16 @@ class Engine:
         """hipGraphs this engine holds (htm_graph_count: captured and instantiated so far)."""
         return self._check(self.lib.htm_graph_count(self.h), "htm_graph_count")
 
-    def prepare(self, device_bank, n_inputs, n_steps, learning=True, use_graph=True, pipeline=True, continuing=False, record=False):
+    def prepare(self, device_bank, n_inputs, n_steps, learning=True, use_graph=True, pipeline=True, continuing=False, record=False,
+                resets=None):
         """Build (capture + instantiate) the hipGraphs the run() call with these arguments will replay (`record`: a recorded
-        run(), whatever its fields -- htm_prepare_recorded)."""
+        run(), whatever its fields -- htm_prepare_recorded; `resets`: a run with reset bits, whichever)."""
+        if resets is not None:
+            self.set_run_resets(resets, n_inputs)
+            try:
+                return self.prepare(device_bank, n_inputs, n_steps, learning, use_graph, pipeline, continuing, record)
+            finally:
+                self.set_run_resets(None, 0)
         flags = (1 if use_graph else 0) | (0 if pipeline else 2) | (4 if continuing else 0)
         if record:
             self._check(self.lib.htm_prepare_recorded(self.h, C.c_void_p(device_bank), int(n_inputs), int(n_steps),

@@ -5,6 +5,7 @@ the three counters: :55-57), so that its output can be compared line by line.
     python -m bithtm_amd.example --epochs 8
     python -m bithtm_amd.example --epochs 8 --batched   # one C-ABI call per epoch, hipGraph replay
     python -m bithtm_amd.example --epochs 8 --batched_report   # ... recorded: the per-step lines of the default mode
+    python -m bithtm_amd.example --epochs 8 --sequence_length 10   # a sequence reset before every 10th pattern
     python -m bithtm_amd.example --epochs 8 --use_reference_implementation   # example.py:30,36-37 (needs the user's `bithtm`)
 """
 
@@ -42,7 +43,17 @@ def parse(argv):
     ap.add_argument("--batched_report", action="store_true",
                     help="run each epoch as one recorded HierarchicalTemporalMemory.run and print the per-step counters "
                          "from its record (the same lines as the default mode)")
+    ap.add_argument("--sequence_length", type=int, default=0,
+                    help="the bank is sequences of this many patterns: a sequence reset before every such pattern (0: none).  "
+                         "Stepwise with the reference's idiom, `last_state = get_empty_state()`; batched with run(resets=)")
     return ap.parse_args(argv)
+
+
+def reset_rows(opts):
+    """The patterns a sequence starts with (a reset before each), or None."""
+    if opts.sequence_length <= 0:
+        return None
+    return np.arange(opts.input_patterns) % opts.sequence_length == 0
 
 
 def digits(n):
@@ -73,6 +84,8 @@ def run_stepwise(htm, bank, opts, out):
     report = Report(opts, htm.spatial_pooler.active_columns)
     for epoch in range(opts.epochs):
         for index, pattern in enumerate(bank):
+            if opts.sequence_length > 0 and index % opts.sequence_length == 0:
+                htm.temporal_memory.last_state = htm.temporal_memory.get_empty_state()
             predicted_columns = htm.temporal_memory.last_state.cell_prediction.any(axis=1)
             flips = np.random.rand(opts.input_dim) < opts.input_noise_probability
             states = htm.process(pattern ^ flips)
@@ -84,7 +97,7 @@ def run_batched(htm, bank, opts, out):
     for epoch in range(opts.epochs):
         noisy = bank ^ (np.random.rand(*bank.shape) < opts.input_noise_probability)
         began = time.time()
-        htm.run(noisy, len(noisy))
+        htm.run(noisy, len(noisy), resets=reset_rows(opts))
         htm.engine.sync()
         rate = len(noisy) / (time.time() - began)
         print(f"epoch {epoch:{width}d}: {rate:.0f} timesteps/s, {htm.engine.info().segments} segments", file=out)
@@ -95,7 +108,7 @@ def run_batched_report(htm, bank, opts, out):
     report = Report(opts, htm.spatial_pooler.active_columns)
     for epoch in range(opts.epochs):
         noisy = bank ^ (np.random.rand(*bank.shape) < opts.input_noise_probability)
-        rec = htm.run(noisy, len(noisy), record=True)
+        rec = htm.run(noisy, len(noisy), record=True, resets=reset_rows(opts))
         for index, (b, c, i) in enumerate(zip(rec.bursting_columns, rec.correct_columns, rec.incorrect_columns)):
             print(report.line(epoch, index, int(b), int(c), int(i)), file=out)
 

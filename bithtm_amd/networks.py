@@ -268,6 +268,7 @@ class TemporalMemory:
         self._last_ref = None             # weak: an unread State costs nothing
         self._last_cols = None
         self._empty_state = self.get_empty_state()                                   # networks.py:57
+        self._was_reset = False           # reset() since the last step: last_state is the empty state
 
     def _bind(self, engine, fused):
         self._engine, self._fused = engine, fused
@@ -323,6 +324,8 @@ class TemporalMemory:
         the device if somebody asks for it."""
         if not self._own_distal:
             return self._host_last if self._host_last is not None else self._empty_state
+        if self._was_reset:
+            return self._empty_state
         st = self._last_ref() if self._last_ref is not None else None
         if st is None:
             if self._engine is None or self._engine.steps == 0:
@@ -330,9 +333,37 @@ class TemporalMemory:
             st = self._new_state(self._last_cols)
         return st
 
+    @last_state.setter
+    def last_state(self, state):
+        """The reference's sequence reset, `tm.last_state = tm.get_empty_state()` (networks.py:57-65,91-93): assigning an
+        empty State (no predicted cell, distal_state None) is reset(); assigning the current last_state changes nothing.
+        Any other State cannot be adopted here -- process(prev_state=...) takes it for one step."""
+        if state is self.last_state:
+            return
+        if _is_empty_state(state):
+            self.reset()
+            return
+        raise ValueError("last_state only takes get_empty_state() (a sequence reset) or itself; "
+                         "pass any other State to process(prev_state=...)")
+
+    def reset(self):
+        """A sequence reset: the next step runs as after `last_state = get_empty_state()` -- no predictions (every active
+        column bursts), no distal state (no learning of the distal segments in that step), no winner cells.  The segment
+        store, the step index and epsilon stay.  On the device (htm_reset: one launch, no host copy, no wait); a model whose
+        distal projection lives on the host only forgets its host-side last state."""
+        if not self._own_distal:
+            self._host_last = None
+            return
+        if self._engine is not None and self._engine.steps > 0:
+            retire_states(self._engine)
+            self._engine.reset()
+        self._last_ref = None
+        self._was_reset = True
+
     def _new_state(self, active_column=None):
         st = self.State(self._engine, self._engine.steps, active_column)
         self._last_ref, self._last_cols = weakref.ref(st), active_column
+        self._was_reset = False
         return st
 
     def process(self, sp_state, prev_state=None, learning=True, return_winner_cell=True, epsilon=1e-8):
@@ -344,9 +375,12 @@ class TemporalMemory:
             return self._process_host(sp_state, prev_state, learning, return_winner_cell, epsilon)
         adopt = None
         if prev_state is not None and prev_state is not self.last_state:
-            d = prev_state.distal_state                                     # (reading the fields materialises a lazy State)
-            adopt = (prev_state.cell_prediction, prev_state.cell_activation,
-                     None if prev_state.winner_cell is None else self.flatten_cell(prev_state.winner_cell), d)
+            if _is_empty_state(prev_state):                                 # a sequence reset: htm_reset, not the host import
+                adopt = "reset"
+            else:
+                d = prev_state.distal_state                                 # (reading the fields materialises a lazy State)
+                adopt = (prev_state.cell_prediction, prev_state.cell_activation,
+                         None if prev_state.winner_cell is None else self.flatten_cell(prev_state.winner_cell), d)
         if not 0.0 < epsilon <= 1.0:
             raise NotImplementedError("epsilon must lie in (0, 1]")
         if self._fused:
@@ -370,7 +404,9 @@ class TemporalMemory:
             if getattr(eng, "_epsilon", 1e-8) != epsilon:
                 eng.set_epsilon(epsilon)
                 eng._epsilon = epsilon
-        if adopt is not None:
+        if adopt == "reset":
+            eng.reset()
+        elif adopt is not None:
             eng.import_prev_state(*adopt)
         eng.tm_step(active_column, learning=learning, return_winner_cell=return_winner_cell)
         return self._new_state(active_column)
@@ -432,6 +468,11 @@ class TemporalMemory:
         return st
 
     compute = process
+
+
+def _is_empty_state(state):
+    """get_empty_state() as the step after it sees it: no predicted cell and no distal state (networks.py:59-65)."""
+    return state.distal_state is None and not np.any(np.asarray(state.cell_prediction))
 
 
 class _DistalState:
@@ -568,6 +609,15 @@ class HierarchicalTemporalMemory:
 
     compute = process
 
+    def reset(self):
+        """A sequence reset before the next step: `temporal_memory.last_state = temporal_memory.get_empty_state()`, the
+        reference's idiom (networks.py:57-65,91-93), which this also accepts.  See TemporalMemory.reset."""
+        reset = getattr(self.temporal_memory, "reset", None)
+        if callable(reset):
+            reset()
+        else:                                       # a plug-in Temporal Memory with the reference's interface only
+            self.temporal_memory.last_state = self.temporal_memory.get_empty_state()
+
     # ---- checkpoint / resume (the reference has none; SURVEY section 5).  The dictionary holds the
     # reference's own arrays: DenseProjection.permanence, ExponentialBoosting.duty_cycle, and the
     # SparseProjection / PredictiveProjection store + last State in the layout of oracle export_state.
@@ -591,6 +641,7 @@ class HierarchicalTemporalMemory:
         eng.write(L.F_DUTY_CYCLE, np.asarray(state["sp_duty_cycle"], dtype=np.float32), np.float32)
         eng.import_tm_state({k[3:]: v for k, v in state.items() if k.startswith("tm_")})
         self.temporal_memory._last_ref = None
+        self.temporal_memory._was_reset = False
 
     def save(self, path):
         np.savez_compressed(path, **self.state_dict())
@@ -599,7 +650,7 @@ class HierarchicalTemporalMemory:
         with np.load(path) as z:
             self.load_state_dict({k: z[k] for k in z.files})
 
-    def run(self, inputs, steps, learning=True, use_graph=True, pipeline=True, continuing=False, record=None):
+    def run(self, inputs, steps, learning=True, use_graph=True, pipeline=True, continuing=False, record=None, resets=None):
         """`steps` timesteps over the rows of the boolean matrix `inputs`, cycled, with the input
         bank resident in device memory and no per-step host work (the loop of example.py:48-53).
         Returns None; read `temporal_memory.last_state` or call process() afterwards.  `continuing=True`: the
@@ -607,7 +658,9 @@ class HierarchicalTemporalMemory:
         the Spatial Pooler keeps working ahead across the calls; finish with a run() without it).
         `record`: a per-step record written on the device and read back once per call (htm_run_recorded) -- True for the
         counters, or a tuple of "counters", "active_column", "column_prediction"; the call then returns a RunRecord over
-        its `steps` steps."""
+        its `steps` steps.
+        `resets`: a bool per row of `inputs` -- a sequence reset (see reset()) before every step that reads a row whose flag is
+        set, on the device inside the run; the flags are uploaded beside the bank and kept with it."""
         eng = self._fused_engine("run()")
         if not self.spatial_pooler._plain:
             raise RuntimeError("run() keeps the whole loop on the device: not available with plug-in objects that live on the host")
@@ -618,6 +671,10 @@ class HierarchicalTemporalMemory:
         bank = getattr(self, "_bank", None)
         if bank is None or bank[0] != key:
             self._bank = bank = (key, eng.upload_bank(inputs))
+        if resets is not None:
+            resets = np.asarray(resets, dtype=np.bool_).ravel()
+            if resets.shape != (inputs.shape[0],):
+                raise ValueError(f"resets: one flag per row of inputs ({inputs.shape[0]}), got {resets.shape[0]}")
         # A pool left at its default size grows like the reference's arrays (utils.py:113-135): the run is cut into batches
         # the free segments are expected to last (2 x active_columns new segments per step: every column bursting, twice),
         # with a look at the pool between them.  An overflow inside a batch is still reported, never silent.
@@ -636,7 +693,8 @@ class HierarchicalTemporalMemory:
                 n = max(1, min(n, eng._free_segments // (2 * k) - 1))
             last = done + n >= steps
             part = eng.run(bank[1], inputs.shape[0], n, learning=learning, use_graph=use_graph, pipeline=pipeline,
-                           continuing=continuing and last, record=fields)
+                           continuing=continuing and last, record=fields,
+                           resets=None if resets is None else eng.upload_resets(resets))
             if fields is not None:
                 parts.append(part)
             self._streaming = bool(continuing and last and pipeline)

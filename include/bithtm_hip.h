@@ -300,6 +300,30 @@ int htm_run_recorded(htm_handle *h, const uint32_t *device_inputs, int32_t n_inp
                      int32_t use_graph, const htm_run_record *rec);
 int htm_prepare_recorded(htm_handle *h, const uint32_t *device_inputs, int32_t n_inputs, int32_t n_steps, int32_t learning,
                          int32_t use_graph);
+/* Sequence resets.  A reset before step t makes step t run as the reference does after
+ * `tm.last_state = tm.get_empty_state()` (networks.py:57-65,91-93): the state before it has no predictions, so every active
+ * column bursts; distal_state is None, so there are no best-matching cells (winners are the least-used cells, keyed draw
+ * stream 1 as usual) and no distal_projection.update -- no reinforcement, punishment, growth or new segments in step t
+ * (projections.py:257-259); winner_cell is None.  The segment store, the Spatial Pooler, the step index (so the keyed draws
+ * of later steps are those of a run without the reset), epsilon and the sticky capacity flags stay what they are.  In a
+ * recorded run a reset step's "state before" is that empty state: predicted_columns_before = 0.
+ *
+ * htm_reset: the handle's previous step becomes that empty state, on the device (one launch on the handle's stream, no host
+ * copy, no wait) -- what htm_import_begin(HTM_IMPORT_PREV_STATE) + htm_write of get_empty_state()'s fields + htm_import_commit
+ * leave, and what htm_read then returns.  For htm_step, htm_tm_step and htm_sp_phase / htm_tm_update / htm_tm_scan callers
+ * alike, between two steps.  HTM_ERR_STATE while the handle is ahead (HTM_RUN_CONTINUE), while a step opened with
+ * htm_shard_begin is not finished, on a column-sharded handle and on a handle without a Temporal Memory.
+ *
+ * htm_set_run_resets: reset bits of the later htm_run / htm_run_recorded / htm_prepare / htm_prepare_recorded calls on banks of
+ * n_inputs rows.  device_bits: DEVICE words, 32 bits each, bit r of word r / 32 = reset before every step that reads bank
+ * row r (step t reads row t % n_inputs), so the bits cycle with the bank across epochs and HTM_RUN_CONTINUE calls.  The
+ * words are read by the run while it executes: they must stay valid, as the bank must.  NULL clears the bits (runs then
+ * launch and capture exactly what they did without them).  A run on a bank of another n_inputs while bits are set:
+ * HTM_ERR_ARGUMENT.  The graphs of runs with resets are captured once and read the bits through a descriptor the call fills
+ * on the device: a call with other bits replays the same graphs.  A column-sharded handle: HTM_ERR_STATE. */
+int htm_reset(htm_handle *h);
+int htm_set_run_resets(htm_handle *h, const uint32_t *device_bits, int32_t n_inputs);
+
 /* hipGraphs the handle holds (captured and instantiated by htm_run / htm_prepare / htm_shard_run and their recorded forms);
  * diagnostic: a recorded call with other buffers replays the graphs of the one before and adds none. */
 int htm_graph_count(htm_handle *h);
