@@ -1,21 +1,25 @@
 #!/usr/bin/env python3
 """Headline benchmark: HTM timesteps/s (SP + TM, learning on) at 65 536 columns x 32 cells.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full]
 
 One "step" = one full timestep of the hot path (SpatialPooler.process + TemporalMemory.process
 with learning, networks.py:146-149) over one synthetic input.  The input bank (Bernoulli-sparse
 patterns, cycled, with flip noise: BASELINE.md section 4) is resident in HBM before the timed
 region.  Prints ONE JSON line (rank 0).
 
-Besides the contract fields the line carries
+A plain run does only what the headline needs: the untimed setup, the timed repetitions, --dump-outputs if given, and
+the line with the contract fields, `config` and `repetitions`.  With --full the line also carries
   roofline      the dominant launch of the TIMED schedule: algorithmic bytes of its roles (formulas in DESIGN.md
                 section 4 and in role_bytes below) / its average duration, measured here with HIP events on the
                 engine's stream over an eager replay of the same schedule; every launch is listed;
-  cpu_baseline  the NumPy oracle (a port of the reference's CPU path) timed on this box's host
-                cores from the same learned state, on a bounded sample of steps;
+  cpu_baseline  the NumPy oracle (a port of the reference's CPU path) timed on the host cores from the same learned
+                state, on a bounded sample of steps, and the parity check of the timed call pattern against it;
+  large_pool    the headline shape with a larger learned pool, through the same protocol (large_pool_leg);
+  host_fed      the reference's example.py loop, one host-fed htm.process(x) per timestep (host_fed_leg);
   stress        BASELINE.json configs[4] as far as one GPU holds it: one rank's pre-populated shard (133.7 M
                 segments) inside an 8-rank group, its segment scan against the HBM roofline.
+--no-cpu-baseline, --no-large-pool, --no-host-fed and --no-stress drop single parts of a --full run.
 
 The model is brought to the learned state (10 passes over the pattern bank) in untimed setup, whatever --warmup
 says; `value` is the median of several repetitions of [W warm-up steps, exactly K timed steps].
@@ -426,11 +430,11 @@ def dump_outputs(arrays, directory):
     log(f"[bench] wrote {len(files)} arrays ({total / 2**20:.1f} MB) of the last timed step to {directory}")
 
 
-def measure(w, args, device, label, reps, cpu_steps, chunk_plan, pmc_section=None, dump=None):
+def measure(w, args, device, label, reps, cpu_steps, chunk_plan, pmc_section=None, dump=None, full=True):
     """One workload through the bench protocol: untimed pre-training to the learned state, R repetitions of [W warm-up
-    steps, exactly K timed steps] called as a streaming caller calls, per-launch HIP-event times of the timed schedule,
-    the roofline object, and (cpu_steps > 0) the oracle timed from the same state + the parity check of the call pattern.
-    `dump`: a directory for the outputs of the last timed step (dump_outputs)."""
+    steps, exactly K timed steps] called as a streaming caller calls, and (full) per-launch HIP-event times of the timed
+    schedule, the roofline object, and (cpu_steps > 0) the oracle timed from the same state + the parity check of the call
+    pattern.  `dump`: a directory for the outputs of the last timed step (dump_outputs)."""
     t_setup = time.perf_counter()
     noisy, perm = make_inputs(w)
     htm = build_htm(w, perm, device)
@@ -482,6 +486,10 @@ def measure(w, args, device, label, reps, cpu_steps, chunk_plan, pmc_section=Non
         f"{', large-pool scan' if plan['scan_large'] else ''}): median {steps_per_s:.0f} timesteps/s "
         f"(min {min(rates):.0f}, max {max(rates):.0f}); S={info.segments}; "
         f"select fallbacks so far: {info.select_fallbacks} of {info.step_index} steps, crowded bins cut to a sub-bin: {info.select_zoom_steps}")
+    if not full:
+        return dict(steps_per_s=steps_per_s, rates=rates, k=k, pretrain=pretrain, segments=int(info.segments),
+                    launches_per_step=None,             # (counted in the profiled replay below)
+                    plan=plan, streamed=bool(stream["continuing"]), pipeline=pipeline)
 
     # per-launch device time (HIP events on the engine's stream) of the TIMED schedule, then of the same
     # workload with one role per launch; both eager (events cannot be read out of a graph replay)
@@ -604,7 +612,23 @@ def run_single(args):
         return large_pool_leg(args, device)
     reps = args.reps if args.reps > 0 else max(3, min(15, -(-4000 // max(args.steps, 1))))
     m = measure(w, args, device, "headline", reps, 0 if args.no_cpu_baseline else args.cpu_steps, (5, 20, 5),
-                dump=args.dump_outputs)
+                dump=args.dump_outputs, full=args.full)
+    steps_per_s, k = m["steps_per_s"], m["k"]
+    out = dict(
+        metric="HTM timesteps/sec (SP + TM, learning on), 65536 cols x 32 cells", value=round(steps_per_s, 1),
+        unit="timesteps/s", n_gpus=1, steps=args.steps, warmup=args.warmup, ms_per_step=round(1e3 / steps_per_s, 5),
+        higher_is_better=True, scaling="strong", vs_baseline=None, dtype="u32 bit-packed / f64 + f32 permanences",
+        data="synthetic",
+        config=dict(workload="configs[2]: 65536 columns x 32 cells, SP + TM learning on, 1 MI355X",
+                    input_dim=w["input_dim"], column_dim=w["column_dim"], cell_dim=w["cell_dim"], active_columns=k,
+                    patterns=w["patterns"], input_density=w["density"], flip_noise=w["noise"],
+                    pretrain_steps=m["pretrain"], segments=m["segments"], segment_slots=w["segment_slots"],
+                    # what the TIMED call did (htm_run_plan): calls of fewer than 64 steps launch eagerly whatever was asked
+                    hip_graph=m["plan"]["hip_graph"], hip_graph_requested=not args.no_graph, pipelined=m["plan"]["pipelined"],
+                    launches_per_step=m["launches_per_step"], repetitions=reps, streamed_calls=m["streamed"]),
+        repetitions=[round(r, 1) for r in m["rates"]])
+    if not args.full:
+        return out
     gc.collect()                                        # (the legs need the device to themselves: memory, and CU slots -- DESIGN.md)
     large = None
     if not args.no_large_pool and not args.columns:
@@ -630,24 +654,10 @@ def run_single(args):
         except Exception as e:
             log(f"[bench] configs[4] leg failed: {e!r}")
             stress = dict(error=repr(e))
-
-    steps_per_s, k = m["steps_per_s"], m["k"]
-    return dict(
-        metric="HTM timesteps/sec (SP + TM, learning on), 65536 cols x 32 cells", value=round(steps_per_s, 1),
-        unit="timesteps/s", n_gpus=1, steps=args.steps, warmup=args.warmup, ms_per_step=round(1e3 / steps_per_s, 5),
-        higher_is_better=True, scaling="strong", vs_baseline=None, dtype="u32 bit-packed / f64 + f32 permanences",
-        data="synthetic",
-        config=dict(workload="configs[2]: 65536 columns x 32 cells, SP + TM learning on, 1 MI355X",
-                    input_dim=w["input_dim"], column_dim=w["column_dim"], cell_dim=w["cell_dim"], active_columns=k,
-                    patterns=w["patterns"], input_density=w["density"], flip_noise=w["noise"],
-                    pretrain_steps=m["pretrain"], segments=m["segments"], segment_slots=w["segment_slots"],
-                    # what the TIMED call did (htm_run_plan): calls of fewer than 64 steps launch eagerly whatever was asked
-                    hip_graph=m["plan"]["hip_graph"], hip_graph_requested=not args.no_graph, pipelined=m["plan"]["pipelined"],
-                    launches_per_step=m["launches_per_step"], repetitions=reps, streamed_calls=m["streamed"]),
-        repetitions=[round(r, 1) for r in m["rates"]],
-        roofline=m["roofline"], cpu_baseline=m["cpu"], large_pool=large, host_fed=host_fed, stress=stress,
-        role_us_one_per_launch={n: round(v, 2) for n, v in m["role_us"].items()},
-        role_bytes={n: int(v) for n, v in m["role_bytes"].items()})
+    out.update(roofline=m["roofline"], cpu_baseline=m["cpu"], large_pool=large, host_fed=host_fed, stress=stress,
+               role_us_one_per_launch={n: round(v, 2) for n, v in m["role_us"].items()},
+               role_bytes={n: int(v) for n, v in m["role_bytes"].items()})
+    return out
 
 
 def main():
@@ -658,6 +668,9 @@ def main():
     ap.add_argument("--columns", type=int, default=0, help="override column_dim (debugging)")
     ap.add_argument("--pretrain", type=int, default=-1, help="untimed pre-training steps (default: 10 passes over the pattern bank)")
     ap.add_argument("--reps", type=int, default=0, help="timed repetitions (default: enough for about 4000 timed steps, 3..15)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline does not need: roofline, cpu_baseline and parity, large_pool, "
+                         "host_fed, stress (minutes)")
     ap.add_argument("--cpu-steps", type=int, default=100, help="timesteps of the NumPy oracle timed for cpu_baseline (and checked against the GPU)")
     ap.add_argument("--large-cpu-steps", type=int, default=69, help="... of the large_pool leg's parity check")
     ap.add_argument("--no-large-pool", action="store_true", help="skip the large_pool leg (the headline shape with 350 patterns)")

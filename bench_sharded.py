@@ -9,10 +9,11 @@ their cells and their cells' segments.
 The protocol is bench.py's, so that the N = 1 and the N > 1 lines lie on one curve:
   * every rank brings the UNSHARDED model to the learned state in untimed setup (10 passes over the pattern bank on its own
     GPU: 15 ms, identical on every rank), and hands that state to its shard (state import into a column-sharded handle);
-  * a parity leg: the sharded model and, on rank 0, the NumPy oracle step the same timesteps from that state -- the
-    oracle's time is the line's cpu_baseline, its outputs the check of the sharded path at the full size;
+  * a parity leg: the sharded model and, on rank 0 with --full, the NumPy oracle step the same timesteps from that state --
+    the oracle's time is the line's cpu_baseline, its outputs the check of the sharded path at the full size;
   * R repetitions of [W warm-up steps, exactly K timed steps between two barrier + synchronize fences], max over the
-    ranks per repetition, `value` = the median repetition.
+    ranks per repetition, `value` = the median repetition;
+  * with --full, the roofline object from a profiled replay.
 
 BITHTM_DIST_BACKEND=gloo and BITHTM_SINGLE_DEVICE=1 rehearse the multi-process flow on a box with one GPU (the
 step is then split around a host-staged gather); the default is backend "nccl" (= RCCL over xGMI) on
@@ -113,12 +114,13 @@ def run_sharded(args):
         torch.cuda.synchronize()
 
     # ---- parity leg (and, on rank 0, the CPU baseline): n_check timesteps from the imported state, sharded on the GPUs and
-    # as the NumPy oracle on rank 0's host
+    # (--full) as the NumPy oracle on rank 0's host.  The GPU steps run in a plain run too: the timed region starts after them.
     n_check = max(1, min(args.cpu_steps, 40)) if not args.no_cpu_baseline else 0
     cpu = None
     if n_check:
         htm.run(bank, n_bank, n_check)
         fence()
+    if n_check and args.full:
         info = eng.check_capacity()
         mine = dict(active=eng.read(L.F_ACTIVE_COLUMN, np.int32, k), act=eng.read(L.F_CELL_ACTIVATION, np.uint32, C),
                     pred=eng.read(L.F_CELL_PREDICTION, np.uint32, C)[c0:c1], winner=eng.read(L.F_WINNER_CELL, np.int32, info.winner_cells),
@@ -183,34 +185,34 @@ def run_sharded(args):
     # per-launch device time on this rank (HIP events on the engine's stream) over a short profiled replay (eager; every
     # rank takes part, the exchange is collective).  The dominant launch is the arg-max over ALL launches of the step.
     roofline = None
-    try:
-        prof_steps = max(min(args.steps, 100), 20)
-        eng.profile(True)
-        htm.run(bank, n_bank, prof_steps)
-        prof = {n: v for n, v in eng.profile_read().items() if v[1]}
-        eng.profile(False)
-        if rank == 0 and prof:
-            store = eng.read_store()
-            live = store["seg_gid"] >= 0
-            info2 = eng.info()
-            lb = shard_launch_bytes(w, world, k, int(live.sum()), int(store["seg_nsyn"][live].sum()), info2.work_items, info2.matching_segments)
-            us = {n: 1e3 * ms / cnt for n, (ms, cnt) in prof.items()}
-            steady = {n: v for n, v in us.items() if prof[n][1] >= prof_steps // 2 and n in lb}      # (the launches every step has)
-            dominant = max(steady, key=lambda n: steady[n])
-            ach = lb[dominant] / us[dominant] / 1e3
-            kernel_of = {"shard_overlap": "k_shard_overlap", "shard_candidates": "k_sp_emit", "shard_select": "k_shard_select", "tm_mid": "k_mid_rows",
-                         "tm_learn+tm_scan+shard_overlap": "k_learn_scan_overlap", "tm_learn+tm_scan": "k_learn_scan_emit", "tm_learn": "k_tm_learn", "tm_scan": "k_tm_scan"}
-            roofline = dict(bound="hbm", kernel=f"{kernel_of.get(dominant, dominant)} ({dominant}, rank 0's share)", achieved=round(ach, 1), peak=bench.HBM_PEAK_GBS,
-                            unit="GB/s", frac=round(ach / bench.HBM_PEAK_GBS, 4), traffic=None,
-                            bytes_per_launch=int(lb[dominant]), avg_launch_us=round(us[dominant], 2),
-                            rank0_kernels_us_per_step=round(sum(steady.values()), 1),
-                            launches={n: dict(kernel=kernel_of.get(n, n), us=round(v, 2), bytes=int(lb.get(n, 0)), per_step=prof[n][1] >= prof_steps // 2) for n, v in us.items()})
-            # (PMC counters of the sharded launches: recorded by tools/collect_profiles.sh from the two-rank rehearsal on one GPU)
-            # (no recorded PMC pass of the sharded launches: rocprofv3 crashes on all ranks in one process, and a launcher that
-            # starts the ranks is an exec chain the profiler's preload cannot follow on this pool -- traffic stays null)
-            roofline.update(traffic=None, traffic_source="no PMC pass of the sharded launches could be recorded on a one-GPU box (profiles/README.md)")
-    except Exception as e:                           # the roofline object is a report, never a reason to lose the line
-        bench.log(f"[bench_sharded] roofline pass skipped: {e!r}")
+    if args.full:
+        try:
+            prof_steps = max(min(args.steps, 100), 20)
+            eng.profile(True)
+            htm.run(bank, n_bank, prof_steps)
+            prof = {n: v for n, v in eng.profile_read().items() if v[1]}
+            eng.profile(False)
+            if rank == 0 and prof:
+                store = eng.read_store()
+                live = store["seg_gid"] >= 0
+                info2 = eng.info()
+                lb = shard_launch_bytes(w, world, k, int(live.sum()), int(store["seg_nsyn"][live].sum()), info2.work_items, info2.matching_segments)
+                us = {n: 1e3 * ms / cnt for n, (ms, cnt) in prof.items()}
+                steady = {n: v for n, v in us.items() if prof[n][1] >= prof_steps // 2 and n in lb}      # (the launches every step has)
+                dominant = max(steady, key=lambda n: steady[n])
+                ach = lb[dominant] / us[dominant] / 1e3
+                kernel_of = {"shard_overlap": "k_shard_overlap", "shard_candidates": "k_sp_emit", "shard_select": "k_shard_select", "tm_mid": "k_mid_rows",
+                             "tm_learn+tm_scan+shard_overlap": "k_learn_scan_overlap", "tm_learn+tm_scan": "k_learn_scan_emit", "tm_learn": "k_tm_learn", "tm_scan": "k_tm_scan"}
+                roofline = dict(bound="hbm", kernel=f"{kernel_of.get(dominant, dominant)} ({dominant}, rank 0's share)", achieved=round(ach, 1), peak=bench.HBM_PEAK_GBS,
+                                unit="GB/s", frac=round(ach / bench.HBM_PEAK_GBS, 4), traffic=None,
+                                bytes_per_launch=int(lb[dominant]), avg_launch_us=round(us[dominant], 2),
+                                rank0_kernels_us_per_step=round(sum(steady.values()), 1),
+                                launches={n: dict(kernel=kernel_of.get(n, n), us=round(v, 2), bytes=int(lb.get(n, 0)), per_step=prof[n][1] >= prof_steps // 2) for n, v in us.items()})
+                # (no recorded PMC pass of the sharded launches: rocprofv3 crashes on all ranks in one process, and cannot follow
+                # the ranks a launcher starts -- traffic stays null)
+                roofline.update(traffic=None, traffic_source="no PMC pass of the sharded launches could be recorded on a one-GPU box (profiles/README.md)")
+        except Exception as e:                           # the roofline object is a report, never a reason to lose the line
+            bench.log(f"[bench_sharded] roofline pass skipped: {e!r}")
     out = None
     if rank == 0:
         steps_per_s = args.steps / dt
