@@ -77,6 +77,8 @@ EXPORTS = {
     "htm_prepare_recorded": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     "htm_reset": (C.c_int, [C.c_void_p]),
     "htm_set_run_resets": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32]),
+    "htm_predicted_input": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "htm_set_run_predicted_input": (C.c_int, [C.c_void_p, C.c_void_p]),
     "htm_graph_count": (C.c_int, [C.c_void_p]),
     "htm_run_plan": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32]),
     "htm_bank_upload": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_void_p)]),

@@ -38,6 +38,7 @@
 #include "htm_pipeline.h"
 #include "htm_record.h"
 #include "htm_reset.h"
+#include "htm_decode.h"
 #include "htm_group.h"
 
 // ------------------------------------------------------------------------------------------
@@ -105,7 +106,14 @@ struct htm_handle {
     int reset_n;
     ResetDev *d_reset;
     bool resetting;
-    // graphs keyed by (parity + 2 if recorded + 4 if resetting, learning, bank, n_inputs)
+    // predicted-input decoding (htm_set_run_predicted_input): the caller's device rows, the device descriptor the decoding
+    // launches read (filled by each call that decodes), whether the steps being enqueued (or captured) now are decoded, and the
+    // output row of htm_predicted_input
+    int32_t *pin_out;
+    PinDev *d_pin;
+    bool decoding;
+    int32_t *d_pin_buf;
+    // graphs keyed by (parity + 2 if recorded + 4 if resetting + 8 if decoding, learning, bank, n_inputs)
     std::map<std::tuple<int, int, const void *, int>, hipGraphExec_t> graphs;
     // state import staging (htm_write of the MATCH_* / SEG_POTENTIAL fields, applied at commit)
     std::vector<int> imp_pot, imp_match_seg;
@@ -526,11 +534,25 @@ static void enqueue_record(htm_handle *h, int p) {
     if (h->recording) LAUNCH(h, "record", k_rec_step, rec_blocks(h->d), 256, h->d, p, h->d_rec);
 }
 
+// the predicted-input votes of the step of parity p, behind its last launch (htm_decode.h); nothing outside a decoding call
+static void enqueue_decode(htm_handle *h, int p) {
+    if (h->decoding) LAUNCH(h, "predicted_input", k_pin_step, pin_blocks(h->d.C), 256, h->d, p, (const PinDev *)h->d_pin);
+}
+
+// The four-launch schedule applies the permanence rows of step t + 1 inside step t (k_mid_rows, rows_ahead = 1), before step t's
+// scan has set its predictions: behind that scan the mask is no longer the one the votes of step t are taken on.  A decoding
+// call of such a handle runs unpipelined (every other schedule applies the rows of step t within step t).
+static bool decode_unpipelined(const htm_handle *h) { return h->pin_out && !can_lean(h); }
+
+// grid of the launch that zeroes a decoding call's n x I votes (grid-stride)
+static int pin_begin_blocks(int n, int I) { return (int)std::max<size_t>(1, std::min<size_t>(1024, ((size_t)n * I + 255) / 256)); }
+
 static int enqueue_step(htm_handle *h, const uint32_t *bank, int n_inputs, int learning, StepPlan plan, const uint32_t *host_input = nullptr) {
     if (!plan.sp_done && !plan.next_sp) enqueue_sp_front(h, bank, n_inputs, (int)(h->step_host & 1), step_wmode(h), host_input);
     enqueue_cold_start(h, bank, n_inputs, learning, plan);
     enqueue_rest(h, (int)(h->step_host & 1), bank, n_inputs, learning, plan);
     enqueue_record(h, (int)(h->step_host & 1));
+    enqueue_decode(h, (int)(h->step_host & 1));
     h->step_host += 1;
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) { h->err = std::string("kernel launch: ") + hipGetErrorString(e); return HTM_ERR_HIP; }
@@ -1310,9 +1332,10 @@ extern "C" int htm_tm_scan(htm_handle *h, const uint32_t *active_words) {
 
 // htm_run, or (dry) only the capture + instantiation of every hipGraph that htm_run call would replay.  record: the call is
 // recorded (htm_run_recorded / htm_prepare_recorded; rec = its buffers, checked by the caller, NULL when dry); rec_open: ...
-// and its descriptor is already filled (the rest of a call)
+// and its descriptor is already filled (the rest of a call); pin_open: the same for the decoding descriptor
 static int run_or_prepare(htm_handle *h, const uint32_t *device_inputs, int32_t n_inputs, int32_t n_steps, int32_t learning,
-                          int32_t use_graph, bool dry, bool record = false, const htm_run_record *rec = nullptr, bool rec_open = false) {
+                          int32_t use_graph, bool dry, bool record = false, const htm_run_record *rec = nullptr, bool rec_open = false,
+                          bool pin_open = false) {
     if (h) flush_tail(h);
     if (!h || !device_inputs || n_inputs < 1 || n_steps < 0) return HTM_ERR_ARGUMENT;
     if (!h->cfg.enable_sp || !h->cfg.enable_tm) { h->err = "htm_run needs a handle with SP and TM"; return HTM_ERR_STATE; }
@@ -1324,7 +1347,7 @@ static int run_or_prepare(htm_handle *h, const uint32_t *device_inputs, int32_t 
     // about 7 us later than a kernel launch does, and the host submits three launches per 30-us step with time to spare --
     // measured, 20 steps per call: 615 against 638 us; from 64 steps on the graphs are level and then ahead)
     const bool graph = (use_graph & 1) && !h->profile && n_steps >= h->eager_below;
-    const bool pipeline = !(use_graph & 2) && can_pipeline(h);
+    const bool pipeline = !(use_graph & 2) && can_pipeline(h) && !decode_unpipelined(h);
     const bool resume = sp_is_ahead(h);            // the previous call left the SP one step (and a front) ahead
     if (resume && (h->ahead_bank != device_inputs || h->ahead_n_inputs != n_inputs || h->ahead_learning != learning)) {
         h->err = "htm_run: the previous call ended with HTM_RUN_CONTINUE; this one must use the same bank, n_inputs and learning flag";
@@ -1336,7 +1359,7 @@ static int run_or_prepare(htm_handle *h, const uint32_t *device_inputs, int32_t 
     if (h->reset_bits && h->reset_n != n_inputs) { h->err = "htm_run: the reset bits were set for a bank of another n_inputs (htm_set_run_resets)"; return HTM_ERR_ARGUMENT; }
     if (dry && !graph) return HTM_OK;
     if (!dry) { int rc = close_open_phases(h); if (rc) return rc; }
-    struct RecordingOff { htm_handle *h; ~RecordingOff() { h->recording = false; h->resetting = false; } } recording_off{h};
+    struct RecordingOff { htm_handle *h; ~RecordingOff() { h->recording = false; h->resetting = false; h->decoding = false; } } recording_off{h};
     if (h->reset_bits && !h->d_reset) { int rc = dalloc(h, &h->d_reset, 1); if (rc) return rc; }
     if (h->reset_bits && !rec_open && !dry && n_steps > 0)
         LAUNCH(h, "tm_reset", k_reset_begin, 1, 64, h->d_reset, h->reset_bits, (int32_t)n_inputs);
@@ -1347,7 +1370,11 @@ static int run_or_prepare(htm_handle *h, const uint32_t *device_inputs, int32_t 
         LAUNCH(h, "record", k_rec_begin, rec_blocks(h->d), 256, h->d, (int)((h->step_host + 1) & 1), h->d_rec, rec->records,
                rec->active_column, rec->column_prediction, (uint32_t)h->step_host, n_steps);
     }
-    h->recording = record || rec_open;
+    h->recording = record;
+    if (h->pin_out && !h->d_pin) { int rc = dalloc(h, &h->d_pin, 1); if (rc) return rc; }
+    if (h->pin_out && !pin_open && !dry && n_steps > 0)
+        LAUNCH(h, "predicted_input", k_pin_begin, pin_begin_blocks(n_steps, h->d.I), 256, h->d_pin, h->pin_out, (uint32_t)h->step_host, n_steps, h->d.I);
+    h->decoding = h->pin_out != nullptr;
     // The SP is ahead but the pipelined schedule is gone (another handle with its own stream has appeared on the device since,
     // or this call asks for HTM_RUN_NO_PIPELINE): the coming step is run as the LAST step of the run that went ahead -- its
     // launches hold no select finish, so nothing in them waits for another block -- and the rest of the call unpipelined.
@@ -1360,6 +1387,7 @@ static int run_or_prepare(htm_handle *h, const uint32_t *device_inputs, int32_t 
             if (h->ahead_lean) enqueue_lean(h, p, learning, device_inputs, n_inputs, last);
             else enqueue_pipelined(h, p, learning, device_inputs, n_inputs, last);
             enqueue_record(h, p);
+            enqueue_decode(h, p);
             h->step_host += 1;
             // (the four-launch schedule had begun the step after it: that front is never consumed)
             HIPCHK(h, hipMemsetAsync(h->d.hist0 + (size_t)(h->step_host & 1) * HIST0_PAR, 0, (size_t)HIST0_PAR * 4, h->stream));
@@ -1367,7 +1395,7 @@ static int run_or_prepare(htm_handle *h, const uint32_t *device_inputs, int32_t 
             hipError_t e = hipGetLastError();
             if (e != hipSuccess) { h->err = std::string("kernel launch: ") + hipGetErrorString(e); return HTM_ERR_HIP; }
         }
-        return run_or_prepare(h, device_inputs, n_inputs, n_steps - 1, learning, use_graph, false, false, nullptr, h->recording);
+        return run_or_prepare(h, device_inputs, n_inputs, n_steps - 1, learning, use_graph, false, h->recording, nullptr, h->recording, h->decoding);
     }
     // Graphs hold the launches of one step, or of up to kGraphSteps consecutive steady-state steps (a graph
     // launch boundary costs about 5 us more than a kernel boundary inside a graph: tools/step_timeline.py).
@@ -1399,7 +1427,7 @@ static int run_or_prepare(htm_handle *h, const uint32_t *device_inputs, int32_t 
             if (!plan.sp_done && !plan.next_sp) enqueue_sp_front(h, device_inputs, n_inputs, p, step_wmode(h));    // eager
             enqueue_cold_start(h, device_inputs, n_inputs, learning, plan);                         // eager: first step of a pipelined run
         }
-        auto key = std::make_tuple(p + (h->recording ? 2 : 0) + (h->resetting ? 4 : 0), learning * 16 + (plan.sp_done ? 4 : 0) + (plan.next_sp ? 2 : 0) + (plan.next_front ? 1 : 0) + 32 * scan_spec_blocks(h) + (scan_pool_is_large(h) ? (1 << 20) : 0) + (h->emit_fused ? (1 << 21) : 0) + (span << 22) + (lean ? 8 : 0) + (step_wmode(h) ? (1 << 19) : 0),
+        auto key = std::make_tuple(p + (h->recording ? 2 : 0) + (h->resetting ? 4 : 0) + (h->decoding ? 8 : 0), learning * 16 + (plan.sp_done ? 4 : 0) + (plan.next_sp ? 2 : 0) + (plan.next_front ? 1 : 0) + 32 * scan_spec_blocks(h) + (scan_pool_is_large(h) ? (1 << 20) : 0) + (h->emit_fused ? (1 << 21) : 0) + (span << 22) + (lean ? 8 : 0) + (step_wmode(h) ? (1 << 19) : 0),
                                    (const void *)device_inputs, n_inputs);
         auto it = h->graphs.find(key);
         if (it == h->graphs.end()) {
@@ -1408,6 +1436,7 @@ static int run_or_prepare(htm_handle *h, const uint32_t *device_inputs, int32_t 
             for (int i = 0; i < span; ++i) {
                 enqueue_rest(h, (p + i) & 1, device_inputs, n_inputs, learning, plan);
                 enqueue_record(h, (p + i) & 1);
+                enqueue_decode(h, (p + i) & 1);
             }
             hipError_t e = hipStreamEndCapture(h->stream, &graph_obj);
             if (e != hipSuccess) { h->err = std::string("hipStreamEndCapture: ") + hipGetErrorString(e); return HTM_ERR_HIP; }
@@ -1487,7 +1516,7 @@ extern "C" int htm_run_plan(htm_handle *h, int32_t n_steps, int32_t use_graph) {
     refresh_exchange_mode(h);
     if (h->seg_pinned) { const int seen = *(volatile int *)h->seg_pinned; h->seg_hint = std::max(h->seg_hint, seen); }
     const bool graph = (use_graph & 1) && !h->profile && n_steps >= h->eager_below;
-    const bool pipeline = !(use_graph & 2) && can_pipeline(h) && n_steps > 1;
+    const bool pipeline = !(use_graph & 2) && can_pipeline(h) && !decode_unpipelined(h) && n_steps > 1;
     return (graph ? HTM_PLAN_GRAPH : 0) | (pipeline ? HTM_PLAN_PIPELINED : 0) | (pipeline && can_lean(h) ? HTM_PLAN_LEAN : 0) |
            (scan_pool_is_large(h) ? HTM_PLAN_SCAN_LARGE : 0);
 }
@@ -2505,6 +2534,40 @@ extern "C" int htm_set_run_resets(htm_handle *h, const uint32_t *device_bits, in
     return HTM_OK;
 }
 
+// Predicted-input decoding (htm_decode.h): a handle whose Spatial Pooler and Temporal Memory are both the device's own
+static int pin_refuse(htm_handle *h, const char *what) {
+    if (h->world > 1) { h->err = std::string(what) + ": not available on a column-sharded handle"; return HTM_ERR_STATE; }
+    if (!h->cfg.enable_sp || !h->cfg.enable_tm) { h->err = std::string(what) + ": needs a handle with the device's own Spatial Pooler and Temporal Memory"; return HTM_ERR_STATE; }
+    return 0;
+}
+
+extern "C" int htm_set_run_predicted_input(htm_handle *h, int32_t *device_votes) {
+    if (!h) return HTM_ERR_ARGUMENT;
+    if (device_votes) { int rc = pin_refuse(h, "htm_set_run_predicted_input"); if (rc) return rc; }
+    h->pin_out = device_votes;
+    return HTM_OK;
+}
+
+// After the held-back tail: the output row zeroed, one launch, a synchronising copy (as htm_read)
+extern "C" int htm_predicted_input(htm_handle *h, int32_t *host_dst) {
+    if (!h || !host_dst) return HTM_ERR_ARGUMENT;
+    flush_tail(h);
+    REJECT_WHEN_AHEAD(h);
+    int rc = pin_refuse(h, "htm_predicted_input");
+    if (rc) return rc;
+    if (h->shard_open || h->phase_open) { h->err = "htm_predicted_input: a step of the handle is open (htm_shard_begin / htm_sp_phase)"; return HTM_ERR_STATE; }
+    HIPCHK(h, hipSetDevice(h->device));
+    const Dev &d = h->d;
+    if (!h->d_pin_buf) { rc = dalloc(h, &h->d_pin_buf, d.I); if (rc) return rc; }
+    HIPCHK(h, hipMemsetAsync(h->d_pin_buf, 0, (size_t)d.I * 4, h->stream));
+    LAUNCH(h, "predicted_input", k_pin, pin_blocks(d.C), 256, d, (int)((h->step_host + 1) & 1), h->d_pin_buf);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) { h->err = std::string("kernel launch: ") + hipGetErrorString(e); return HTM_ERR_HIP; }
+    HIPCHK(h, hipMemcpyAsync(host_dst, h->d_pin_buf, (size_t)d.I * 4, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return HTM_OK;
+}
+
 extern "C" int htm_profile(htm_handle *h, int32_t enable) {
     if (!h) return HTM_ERR_ARGUMENT;
     if (h) flush_tail(h);
@@ -2567,14 +2630,16 @@ struct htm_group {
     std::vector<Dev> host_tab;                // what d_tab holds: each member's Dev with every select digit launched
     Dev *d_tab;
     RecDev **d_recs;                          // each member's record descriptor (htm_handle::d_rec)
+    PinDev **d_pins;                          // each member's decoding descriptor (htm_handle::d_pin)
     uint32_t *stage;                          // htm_group_step: [n][W] staged host inputs
     const uint32_t **stage_tab;               // ... and the bank table that points into it
     // device tables of the members' banks / record buffers, one per distinct set (graphs hold the bank table's address)
     std::map<std::vector<const uint32_t *>, const uint32_t **> bank_tabs;
     std::map<std::vector<const void *>, GrpRecArgs *> rec_tabs;
-    // graphs keyed by (parity + 2 if recorded, learning, tail form, spec, span, bank table, n_inputs)
+    std::map<std::vector<int32_t *>, int32_t **> pin_tabs;      // the members' decoding outputs (htm_set_run_predicted_input)
+    // graphs keyed by (parity + 2 if recorded + 4 if decoding, learning, tail form, spec, span, bank table, n_inputs)
     std::map<std::tuple<int, int, int, int, int, const void *, int>, hipGraphExec_t> graphs;
-    bool recording;
+    bool recording, decoding;
 };
 
 #define GHIPCHK(g, call)                                                                         \
@@ -2654,26 +2719,30 @@ extern "C" int htm_group_create(htm_handle *const *members, int32_t n, htm_group
     g->stream = h0->stream;
     g->mixed = false;
     for (const htm_handle *h : g->m) g->mixed |= h->stream != g->stream;
-    g->d_tab = nullptr; g->d_recs = nullptr;
+    g->d_tab = nullptr; g->d_recs = nullptr; g->d_pins = nullptr;
     g->stage = nullptr; g->stage_tab = nullptr;
-    g->recording = false;
+    g->recording = g->decoding = false;
     auto fail = [&](int rc) { g_create_error = g->err; htm_group_destroy(g); return rc; };
     if (hipSetDevice(g->device) != hipSuccess) { g->err = "htm_group_create: hipSetDevice failed"; return fail(HTM_ERR_HIP); }
     g->host_tab.resize(n);
     std::vector<RecDev *> recs(n);
+    std::vector<PinDev *> pins(n);
     for (int i = 0; i < n; ++i) {
         htm_handle *h = g->m[i];
         flush_tail(h);
         if (!h->d_rec && dalloc(h, &h->d_rec, 1)) { g->err = h->err; return fail(HTM_ERR_HIP); }
+        if (!h->d_pin && dalloc(h, &h->d_pin, 1)) { g->err = h->err; return fail(HTM_ERR_HIP); }
         if (hipStreamSynchronize(h->stream) != hipSuccess) { g->err = "htm_group_create: hipStreamSynchronize failed"; return fail(HTM_ERR_HIP); }
         g->host_tab[i] = h->d;
         g->host_tab[i].sel_passes = h->sel_passes_full;
         recs[i] = h->d_rec;
+        pins[i] = h->d_pin;
     }
     const int W = h0->d.W;
     int rc = 0;
     rc |= galloc(g, &g->d_tab, n);
     rc |= galloc(g, &g->d_recs, n);
+    rc |= galloc(g, &g->d_pins, n);
     rc |= galloc(g, &g->stage, (size_t)n * W);
     rc |= galloc(g, (uint32_t ***)&g->stage_tab, n);
     if (rc) return fail(HTM_ERR_HIP);
@@ -2683,6 +2752,7 @@ extern "C" int htm_group_create(htm_handle *const *members, int32_t n, htm_group
     if (hipMemset(g->stage, 0, (size_t)n * W * 4) != hipSuccess ||
         hipMemcpy(g->d_tab, g->host_tab.data(), (size_t)n * sizeof(Dev), hipMemcpyHostToDevice) != hipSuccess ||
         hipMemcpy(g->d_recs, recs.data(), (size_t)n * sizeof(RecDev *), hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(g->d_pins, pins.data(), (size_t)n * sizeof(PinDev *), hipMemcpyHostToDevice) != hipSuccess ||
         hipMemcpy((void *)g->stage_tab, stage_rows.data(), (size_t)n * sizeof(uint32_t *), hipMemcpyHostToDevice) != hipSuccess) {
         g->err = std::string("htm_group_create: ") + hipGetErrorString(hipGetLastError());
         return fail(HTM_ERR_HIP);
@@ -2771,6 +2841,10 @@ static void group_enqueue_step(htm_group *g, const uint32_t *const *banks, int n
         const dim3 g_rec(rec_blocks(d), B);
         LAUNCH_ON(h, s, 0, "group:record", kgrp_rec_step, g_rec, 256, tab, p, g->d_recs);
     }
+    if (g->decoding) {
+        const dim3 g_pin(pin_blocks(d.C), B);
+        LAUNCH_ON(h, s, 0, "group:predicted_input", kgrp_pin_step, g_pin, 256, tab, p, g->d_pins);
+    }
 }
 
 // every refusal of a group call, before anything is enqueued
@@ -2823,7 +2897,7 @@ static int group_run(htm_group *g, const uint32_t **bank_tab, int n_inputs, int 
     htm_handle *h0 = g->m[0];
     const hipStream_t s = g->stream;
     learning = learning ? 1 : 0;
-    struct RecordingOff { htm_group *g; ~RecordingOff() { g->recording = false; } } recording_off{g};
+    struct RecordingOff { htm_group *g; ~RecordingOff() { g->recording = false; g->decoding = false; } } recording_off{g};
     if (records) {
         std::vector<GrpRecArgs> rows(B);
         std::vector<const void *> key;
@@ -2839,6 +2913,18 @@ static int group_run(htm_group *g, const uint32_t **bank_tab, int n_inputs, int 
         LAUNCH_ON(h0, s, 0, "group:record", kgrp_rec_begin, g_rec, 256, g->d_tab, (int)((h0->step_host + 1) & 1), g->d_recs, args, n_steps);
         g->recording = true;
     }
+    // members with decoding outputs (htm_set_run_predicted_input): their rows zeroed and every member's descriptor filled (the
+    // others' with no rows), then one decoding launch behind each step
+    std::vector<int32_t *> outs(B);
+    for (int i = 0; i < B; ++i) outs[i] = g->m[i]->pin_out;
+    if (std::any_of(outs.begin(), outs.end(), [](int32_t *o) { return o != nullptr; })) {
+        int32_t **out_tab = nullptr;
+        int rc = group_table(g, g->pin_tabs, outs, outs.data(), &out_tab);
+        if (rc) return rc;
+        const dim3 g_begin(pin_begin_blocks(n_steps, h0->d.I), B);
+        LAUNCH_ON(h0, s, 0, "group:predicted_input", kgrp_pin_begin, g_begin, 256, g->d_tab, (int)((h0->step_host + 1) & 1), g->d_pins, out_tab, n_steps);
+        g->decoding = true;
+    }
     const GroupForm f = group_form(g);
     const bool graph = (use_graph & 1) && !h0->profile && n_steps >= h0->eager_below;
     const int span_max = h0->graph_steps;
@@ -2851,7 +2937,7 @@ static int group_run(htm_group *g, const uint32_t **bank_tab, int n_inputs, int 
             continue;
         }
         const int span = n_steps - t >= span_max ? span_max : 1;
-        auto key = std::make_tuple(p + (g->recording ? 2 : 0), learning, (f.fuse ? 1 : 0) + (f.large ? 2 : 0), f.spec, span,
+        auto key = std::make_tuple(p + (g->recording ? 2 : 0) + (g->decoding ? 4 : 0), learning, (f.fuse ? 1 : 0) + (f.large ? 2 : 0), f.spec, span,
                                    (const void *)bank_tab, n_inputs);
         auto it = g->graphs.find(key);
         if (it == g->graphs.end()) {

@@ -134,6 +134,10 @@ class ShardedHTM:
         """Sequence resets are not available on column-sharded models (htm_reset rejects a sharded handle)."""
         raise NotImplementedError("sequence resets are not available on a column-sharded model")
 
+    def predicted_input(self):
+        """Predicted-input decoding is not available on column-sharded models (htm_predicted_input rejects a sharded handle)."""
+        raise NotImplementedError("predicted_input() is not available on a column-sharded model")
+
     def export_tm_state(self):
         """Collective: every rank contributes its part (torch.distributed.all_gather_object; not a fast path)."""
         import torch.distributed as dist
@@ -217,6 +221,10 @@ class LocalGroup:
     def reset(self):
         """Sequence resets are not available on column-sharded models (htm_reset rejects a sharded handle)."""
         raise NotImplementedError("sequence resets are not available on a column-sharded model")
+
+    def predicted_input(self):
+        """Predicted-input decoding is not available on column-sharded models (htm_predicted_input rejects a sharded handle)."""
+        raise NotImplementedError("predicted_input() is not available on a column-sharded model")
 
     def export_tm_state(self):
         return merge_shard_states([e.export_tm_state() for e in self.engines], self.column_dim, self.cell_dim)

@@ -33,7 +33,7 @@ def pack_bits(bits, words):
 
 
 # run(record=...): the per-step fields htm_run_recorded can write, and the counts of one htm_step_record in its order
-RECORD_FIELDS = ("counters", "active_column", "column_prediction")
+RECORD_FIELDS = ("counters", "active_column", "column_prediction", "predicted_input")
 RECORD_COUNTERS = tuple(name for name, _ in L.HtmStepRecord._fields_)
 
 
@@ -347,7 +347,8 @@ class Engine:
         """`continuing`: the next call is another run() on the same bank (HTM_RUN_CONTINUE, include/bithtm_hip.h).
         `record`: None, or the fields of a per-step record to keep (RECORD_FIELDS): the call then goes to htm_run_recorded and
         returns {field: numpy array over the n_steps steps} -- "counters" int32[n, 8] (htm_step_record, RECORD_COUNTERS order),
-        "active_column" int32[n, k], "column_prediction" uint32[n, ceil(C / 32)] -- read back after one synchronisation."""
+        "active_column" int32[n, k], "column_prediction" uint32[n, ceil(C / 32)], "predicted_input" int32[n, input_dim] (the
+        votes of htm_set_run_predicted_input, set for this call only) -- read back after one synchronisation."""
         flags = (1 if use_graph else 0) | (0 if pipeline else 2) | (4 if continuing else 0)
         if record is None:
             self._check(self.lib.htm_run(self.h, C.c_void_p(device_bank), int(n_inputs), int(n_steps), int(bool(learning)),
@@ -359,17 +360,41 @@ class Engine:
         if unknown or not fields:
             raise ValueError(f"record: fields from {RECORD_FIELDS}, at least one (got {fields})")
         n = int(n_steps)
-        shapes = {"counters": (len(RECORD_COUNTERS), np.int32), "active_column": (self.active_columns, np.int32),
-                  "column_prediction": ((self.column_dim + 31) // 32, np.uint32)}
+        shapes = self.record_shapes()
         ptrs = {f: self._record_buffer(f, max(n, 1) * shapes[f][0]) for f in fields}
         rec = L.HtmRunRecord()
         rec.struct_bytes = C.sizeof(L.HtmRunRecord)
-        rec.records, rec.active_column, rec.column_prediction = (ptrs.get(f) for f in RECORD_FIELDS)
-        self._check(self.lib.htm_run_recorded(self.h, C.c_void_p(device_bank), int(n_inputs), n, int(bool(learning)), flags,
-                                              C.byref(rec)), "htm_run_recorded")
+        rec.records, rec.active_column, rec.column_prediction = (ptrs.get(f) for f in RECORD_FIELDS[:3])
+        if "predicted_input" in fields:
+            self.set_run_predicted_input(ptrs["predicted_input"])
+        try:
+            if fields == ("predicted_input",):
+                self._check(self.lib.htm_run(self.h, C.c_void_p(device_bank), int(n_inputs), n, int(bool(learning)), flags), "htm_run")
+            else:
+                self._check(self.lib.htm_run_recorded(self.h, C.c_void_p(device_bank), int(n_inputs), n, int(bool(learning)), flags,
+                                                      C.byref(rec)), "htm_run_recorded")
+        finally:
+            if "predicted_input" in fields:
+                self.set_run_predicted_input(None)
         self.steps += n_steps
         self.sync()                                 # (the records are written on the engine's stream)
         return {f: self._record_read(f, n * shapes[f][0], shapes[f][1]).reshape(n, shapes[f][0]) for f in fields}
+
+    def record_shapes(self):
+        """{record field: (int32 words per step, dtype)} of this engine's shape."""
+        return {"counters": (len(RECORD_COUNTERS), np.int32), "active_column": (self.active_columns, np.int32),
+                "column_prediction": ((self.column_dim + 31) // 32, np.uint32), "predicted_input": (self.input_dim, np.int32)}
+
+    def set_run_predicted_input(self, device_votes):
+        """Decoding rows of the later run() calls and group calls (htm_set_run_predicted_input); None clears them."""
+        self._check(self.lib.htm_set_run_predicted_input(self.h, C.c_void_p(device_votes) if device_votes else None),
+                    "htm_set_run_predicted_input")
+
+    def predicted_input(self):
+        """int32[input_dim]: the predicted-input votes of the current state (htm_predicted_input)."""
+        out = np.empty(self.input_dim, dtype=np.int32)
+        self._check(self.lib.htm_predicted_input(self.h, out.ctypes.data_as(C.c_void_p)), "htm_predicted_input")
+        return out
 
     # The record buffers are device memory of the HIP runtime the library itself is linked against (_lib.HIP_EXPORTS), kept for
     # the next recorded call and grown geometrically.

@@ -146,17 +146,24 @@ class ModelGroup:
         return True
 
     def _records(self, fields, n):
-        """Per member: the record buffers of n steps (the members' own, as run(record=) uses) -> HtmRunRecord array, shapes."""
+        """Per member: the record buffers of n steps (the members' own, as run(record=) uses) -> HtmRunRecord array (None when
+        only "predicted_input" is asked for), shapes.  "predicted_input": each member's decoding rows are set (_unset_votes
+        clears them)."""
         recs = (L.HtmRunRecord * len(self.models))()
         shapes = {}
         for i, m in enumerate(self.models):
             e = m.engine
-            shapes = {"counters": (len(L.HtmStepRecord._fields_), np.int32), "active_column": (e.active_columns, np.int32),
-                      "column_prediction": ((e.column_dim + 31) // 32, np.uint32)}
+            shapes = e.record_shapes()
             ptrs = {f: e._record_buffer(f, max(n, 1) * shapes[f][0]) for f in fields}
             recs[i].struct_bytes = C.sizeof(L.HtmRunRecord)
             recs[i].records, recs[i].active_column, recs[i].column_prediction = (ptrs.get(f) for f in ("counters", "active_column", "column_prediction"))
-        return recs, shapes
+            if "predicted_input" in fields:
+                e.set_run_predicted_input(ptrs["predicted_input"])
+        return (None if fields == ("predicted_input",) else recs), shapes
+
+    def _unset_votes(self):
+        for m in self.models:
+            m.engine.set_run_predicted_input(None)
 
     def _read_records(self, fields, n, shapes):
         self.models[0].engine.sync()            # (the group enqueues on the first member's stream)
@@ -208,8 +215,11 @@ class ModelGroup:
                             "htm_group_run")
             else:
                 recs, shapes = self._records(fields, n)
-                self._check(self.lib.htm_group_run(self._g, banks, inputs.shape[1], n, int(bool(learning)), int(bool(use_graph)), recs),
-                            "htm_group_run")
+                try:
+                    self._check(self.lib.htm_group_run(self._g, banks, inputs.shape[1], n, int(bool(learning)), int(bool(use_graph)), recs),
+                                "htm_group_run")
+                finally:
+                    self._unset_votes()
                 for i, part in enumerate(self._read_records(fields, n, shapes)):
                     parts[i].append(part)
             for m in self.models:
@@ -222,7 +232,7 @@ class ModelGroup:
             m.engine.check_capacity()
         if fields is None:
             return None
-        return [_join_record(p, fields, f, steps, k, m.column_dim) for p, f, m in zip(parts, first, self.models)]
+        return [_join_record(p, fields, f, steps, k, m.column_dim, m.engine.input_dim) for p, f, m in zip(parts, first, self.models)]
 
     def process(self, X, learning=True, record=True):
         """One timestep of every member, member i on X[i] (bool [B, input_dim]) -- its own process(X[i]) at once.  Returns a

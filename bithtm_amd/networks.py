@@ -490,18 +490,21 @@ class RunRecord:
       new_segments                   int32[steps]   the counters ("counters"; None when not recorded)
       active_column                  int32[steps, k]   sp_state.active_column of each step ("active_column", else None)
       column_prediction              bool[steps, C]    cell_prediction.any(axis=1) of each step ("column_prediction", else None)
+      predicted_input                int32[steps, input_dim]   the predicted-input votes of the state each step leaves
+                                                       (HierarchicalTemporalMemory.predicted_input; "predicted_input", else None)
     and, from the counters, the per-step report of example.py:55-57 and the raw anomaly score:
       correct_columns   = active_columns - bursting_columns
       incorrect_columns = predicted_columns_before - correct_columns
       anomaly_score     = 1 - correct_columns / active_columns   (float64; 0 for a step without active columns)"""
 
-    def __init__(self, step_index, counters=None, active_column=None, column_prediction=None):
+    def __init__(self, step_index, counters=None, active_column=None, column_prediction=None, predicted_input=None):
         self.step_index = np.asarray(step_index, dtype=np.int64)
-        self.fields = tuple(f for f, v in zip(RECORD_FIELDS, (counters, active_column, column_prediction)) if v is not None)
+        self.fields = tuple(f for f, v in zip(RECORD_FIELDS, (counters, active_column, column_prediction, predicted_input)) if v is not None)
         for i, name in enumerate(RECORD_COUNTERS):
             setattr(self, name, None if counters is None else np.ascontiguousarray(counters[:, i], dtype=np.int32))
         self.active_column = active_column
         self.column_prediction = column_prediction
+        self.predicted_input = predicted_input
 
     def __len__(self):
         return len(self.step_index)
@@ -662,8 +665,8 @@ class HierarchicalTemporalMemory:
         caller streams its input in chunks and the next call is another run() on the same inputs (HTM_RUN_CONTINUE:
         the Spatial Pooler keeps working ahead across the calls; finish with a run() without it).
         `record`: a per-step record written on the device and read back once per call (htm_run_recorded) -- True for the
-        counters, or a tuple of "counters", "active_column", "column_prediction"; the call then returns a RunRecord over
-        its `steps` steps.
+        counters, or a tuple of "counters", "active_column", "column_prediction", "predicted_input"; the call then returns a
+        RunRecord over its `steps` steps.
         `resets`: a bool per row of `inputs` -- a sequence reset (see reset()) before every step that reads a row whose flag is
         set, on the device inside the run; the flags are uploaded beside the bank and kept with it."""
         eng = self._fused_engine("run()")
@@ -708,14 +711,26 @@ class HierarchicalTemporalMemory:
         eng.check_capacity()
         if fields is None:
             return None
-        return _join_record(parts, fields, first_step, steps, k, self.column_dim)
+        return _join_record(parts, fields, first_step, steps, k, self.column_dim, eng.input_dim)
+
+    def predicted_input(self):
+        """Which input the model expects next: int32[input_dim], the votes of the predicted columns for the inputs they are
+        connected to -- for the state the last step left, (pp.permanence[tm_state.cell_prediction.any(axis=1)] >=
+        pp.permanence_threshold).sum(axis=0) with pp = spatial_pooler.proximal_projection (include/bithtm_hip.h,
+        htm_predicted_input).  One launch and one read-back of input_dim words."""
+        eng = self._engine
+        if eng is None:
+            raise RuntimeError("predicted_input() decodes on the device: not available with a layer or a distal projection that lives on the host")
+        if not self.spatial_pooler._plain:
+            raise RuntimeError("predicted_input() decodes on the device: not available with plug-in Spatial Pooler objects that live on the host")
+        return eng.predicted_input()
 
 
-def _join_record(parts, fields, first_step, steps, k, column_dim):
+def _join_record(parts, fields, first_step, steps, k, column_dim, input_dim=0):
     """One contiguous RunRecord from the per-batch records of a run(record=...) (Engine.run's dicts), however many batches the
     pool's growth cut the call into."""
     empty = {"counters": np.zeros((0, len(RECORD_COUNTERS)), np.int32), "active_column": np.zeros((0, k), np.int32),
-             "column_prediction": np.zeros((0, (column_dim + 31) // 32), np.uint32)}
+             "column_prediction": np.zeros((0, (column_dim + 31) // 32), np.uint32), "predicted_input": np.zeros((0, input_dim), np.int32)}
     whole = {f: np.concatenate([p[f] for p in parts]) if parts else empty[f] for f in fields}
     if "column_prediction" in whole:
         words = np.ascontiguousarray(whole["column_prediction"])

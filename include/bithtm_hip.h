@@ -323,6 +323,32 @@ int htm_prepare_recorded(htm_handle *h, const uint32_t *device_inputs, int32_t n
  * on the device: a call with other bits replays the same graphs.  A column-sharded handle: HTM_ERR_STATE. */
 int htm_reset(htm_handle *h);
 int htm_set_run_resets(htm_handle *h, const uint32_t *device_bits, int32_t n_inputs);
+/* Predicted-input decoding: which input the state expects next, as the top-down pass of the Spatial Pooler's proximal
+ * projection over the predicted columns.  The votes of a state are int32[input_dim]:
+ *   votes[i] = number of columns c with a predicted cell (cell_prediction.any(axis=1), networks.py:30-33,122) whose
+ *              connection to input i is connected (permanence[c, i] >= permanence_threshold, projections.py:18-21)
+ * -- the reference's (pp.permanence[tm_state.cell_prediction.any(axis=1)] >= pp.permanence_threshold).sum(axis=0) with
+ * pp = spatial_pooler.proximal_projection, right after the step that left the state.  The prediction is the one step t makes
+ * about step t + 1, and the mask is the one after step t's Spatial Pooler update: the one step t + 1's overlap reads, so
+ * votes_t . x_{t+1} = the sum of step t+1's overlaps over the columns step t predicts.  A state without predictions (a fresh
+ * handle, a reset) gives zeros.
+ *
+ * htm_predicted_input: the votes of the handle's current state (after htm_step, htm_run, a group call, htm_reset or an
+ * import) into host_dst[input_dim]: after the held-back tail, one launch and a synchronising copy, as htm_read.
+ * HTM_ERR_STATE while the handle is ahead (HTM_RUN_CONTINUE), while a step opened with htm_shard_begin or htm_sp_phase is not
+ * finished, on a column-sharded handle and on a handle without the device's own Spatial Pooler and Temporal Memory.
+ *
+ * htm_set_run_predicted_input: DEVICE rows of votes for the later htm_run / htm_run_recorded calls, and for the htm_group_run /
+ * htm_group_step calls of groups the handle is a member of: such a call of n_steps steps writes n_steps x input_dim int32,
+ * the votes of the state its step i leaves in row i (taken behind that step, so a reset before the next step does not change
+ * them).  The rows must stay valid while the call executes.  htm_prepare / htm_prepare_recorded capture the graphs of such
+ * calls.  NULL clears the rows (calls then launch and capture exactly what they did without them).  The graphs of decoding
+ * calls are captured once and read the rows through a descriptor the call fills on the device.  Where the handle's run would
+ * take the four-launch pipelined schedule (it applies the Spatial Pooler's rows of step t + 1 before step t's predictions
+ * exist), decoding calls run unpipelined, and htm_run_plan reports them so.  HTM_ERR_STATE on a column-sharded handle and on a
+ * handle without the device's own Spatial Pooler and Temporal Memory. */
+int htm_predicted_input(htm_handle *h, int32_t *host_dst);
+int htm_set_run_predicted_input(htm_handle *h, int32_t *device_votes);
 
 /* hipGraphs the handle holds (captured and instantiated by htm_run / htm_prepare / htm_shard_run and their recorded forms);
  * diagnostic: a recorded call with other buffers replays the graphs of the one before and adds none. */
@@ -473,6 +499,10 @@ int64_t htm_trace_read(htm_handle *h, uint64_t *dst, int64_t count);
  *
  * htm_group_step: one step of every member on host inputs: packed_inputs holds n rows of ceil(input_dim / 32) words, row i
  * for member i (copied into a group-owned staging bank).  records as for htm_group_run, one step each.
+ *
+ * Both write the predicted-input votes of every member that has decoding rows set (htm_set_run_predicted_input) into those
+ * rows, step i of the call in row i, one launch per step for all members (a group applies each step's Spatial Pooler rows
+ * within that step).
  *
  * Afterwards every per-member call works as after htm_run: htm_read, htm_get_info, htm_step, htm_run, export / import. */
 typedef struct htm_group htm_group;
