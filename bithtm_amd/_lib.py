@@ -113,6 +113,8 @@ EXPORTS = {
     "htm_group_last_error": (C.c_char_p, [C.c_void_p]),
     "htm_group_run": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(HtmRunRecord)]),
     "htm_group_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(HtmRunRecord)]),
+    "htm_create_view": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p)]),
+    "htm_device_bytes": (C.c_int64, [C.c_void_p]),
 }
 
 # The HIP runtime calls the binding makes itself -- the device buffers of run(record=...) -- resolved through the library's own

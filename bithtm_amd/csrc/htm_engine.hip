@@ -131,7 +131,30 @@ struct htm_handle {
     std::vector<std::vector<std::pair<hipEvent_t, hipEvent_t>>> prof_events;
     std::vector<double> prof_ms;
     std::vector<long long> prof_n;
+    // inference views (htm_create_view): the weights' allocations while the handle has no view (then they move to `shared`),
+    // the reference-counted weights a parent and its views share, whether this handle is a view, and the weights' generation
+    // (HtmShared::wgen) the view's per-cell maxima were last made against
+    std::vector<void *> weight_allocs;
+    struct HtmShared *shared;
+    bool is_view;
+    long long seen_wgen;
+    uint32_t dense_step;                  // (the host word a view's counter block takes cm_dense_step from)
+    int64_t own_bytes;                    // device bytes this handle allocated itself (htm_device_bytes)
+    int knob_shared_scan, knob_shared_members;    // BITHTM_SHARED_SCAN (0: off), BITHTM_SHARED_SCAN_MEMBERS (cap of M; 0: none)
 };
+
+// The weights of a parent and its inference views (htm_create_view): freed, with the parent's own stream if it created one, when
+// the last of them is destroyed.  parent: null once the parent is destroyed (its weights then no longer change).  wgen: bumped by
+// every parent call that may change the weights (weights_touched).
+struct HtmShared {
+    std::vector<void *> allocs;
+    hipStream_t stream;
+    bool own_stream;
+    htm_handle *parent;
+    int refs;
+    long long wgen;
+};
+static std::mutex g_shared_mutex;
 
 // Live handles, per process.  The in-kernel select finish (k_sp_emit / k_open_emit) makes the blocks of one grid
 // wait for each other, which is only safe while nothing else can hold the CU slots that grid needs: kernels of
@@ -185,8 +208,17 @@ static int dalloc(htm_handle *h, T **p, size_t count) {
     e = hipMemsetAsync(q, 0, bytes, h->stream);
     if (e != hipSuccess) { h->err = std::string("hipMemsetAsync: ") + hipGetErrorString(e); return HTM_ERR_HIP; }
     h->allocs.push_back(q);
+    h->own_bytes += (int64_t)bytes;
     *p = (T *)q;
     return 0;
+}
+
+// ... of the weights (what an inference view aliases instead of allocating)
+template <typename T>
+static int dalloc_weights(htm_handle *h, T **p, size_t count) {
+    const int rc = dalloc(h, p, count);
+    if (!rc) { h->weight_allocs.push_back(h->allocs.back()); h->allocs.pop_back(); }
+    return rc;
 }
 
 static int prof_slot(htm_handle *h, const char *name) {
@@ -578,8 +610,22 @@ extern "C" void htm_destroy(htm_handle *h) {
     for (hipEvent_t e : h->prof_all) hipEventDestroy(e);
     if (h->rccl_comm && g_rccl_destroy) g_rccl_destroy(h->rccl_comm);
     for (void *p : h->allocs) hipFree(p);
+    for (void *p : h->weight_allocs) hipFree(p);
     if (h->seg_pinned) hipHostFree(h->seg_pinned);
     if (h->own_stream) hipStreamDestroy(h->stream);
+    if (HtmShared *sh = h->shared) {              // the last of a parent and its views frees the weights (and the parent's stream)
+        bool last;
+        {
+            std::lock_guard<std::mutex> lock(g_shared_mutex);
+            if (sh->parent == h) sh->parent = nullptr;
+            last = --sh->refs == 0;
+        }
+        if (last) {
+            for (void *p : sh->allocs) hipFree(p);
+            if (sh->own_stream) hipStreamDestroy(sh->stream);
+            delete sh;
+        }
+    }
     delete h;
 }
 
@@ -587,6 +633,104 @@ static int fail_create(htm_handle *h, const std::string &msg, int code) {
     g_create_error = msg;
     if (h) { h->err = msg; htm_destroy(h); }
     return code;
+}
+
+// The device state of a handle in two parts.  The weights -- what learning changes and an inference view aliases (htm_create_view):
+// the SP permanences and connected mask, the segment store.
+static int alloc_weights(htm_handle *h) {
+    Dev &d = h->d;
+    const htm_config *cfg = &h->cfg;
+    const size_t C = d.C;
+    int rc = 0;
+    if (cfg->enable_sp) {
+        rc |= dalloc_weights(h, &d.perm, C * d.Ipad);
+        rc |= dalloc_weights(h, &d.mask, C * d.W);
+    }
+    if (cfg->enable_tm) {
+        const size_t S = d.Lcap, E = d.E, KP = d.KP;
+        rc |= dalloc_weights(h, &d.seg_cell, S);
+        rc |= dalloc_weights(h, &d.seg_nsyn, S);
+        rc |= dalloc_weights(h, &d.presyn, S * E);
+        rc |= dalloc_weights(h, &d.sperm, S * E);
+        rc |= dalloc_weights(h, &d.segcount, C * KP);
+    }
+    return rc;
+}
+
+// ... and everything one input stream carries from step to step (a view owns its own)
+static int alloc_stream_state(htm_handle *h) {
+    Dev &d = h->d;
+    const htm_config *cfg = &h->cfg;
+    const int world = h->world;
+    int rc = 0;
+    const size_t C = d.C, k = d.k;
+    rc |= dalloc(h, &d.ctr, 1);
+    rc |= dalloc(h, &d.active_cols[0], k + 8);     // (+8: the TM's list pass reads 8 entries per thread)
+    rc |= dalloc(h, &d.active_cols[1], k + 8);
+    if (cfg->enable_sp) {
+        rc |= dalloc(h, &d.duty, C);
+        for (int q = 0; q < 2; ++q) {
+            rc |= dalloc(h, &d.overlap[q], C);
+            rc |= dalloc(h, &d.boosted[q], C);
+            rc |= dalloc(h, &d.key[q], C);
+        }
+        rc |= dalloc(h, &d.hist, (size_t)2 * SEL_MAX_PASSES * SEL_BINS);
+        rc |= dalloc(h, &d.hist0, (size_t)2 * HIST0_PAR);
+        rc |= dalloc(h, &d.sel_blk, (C + 255) / 256);
+        rc |= dalloc(h, &d.sel_rec, (C + 255) / 256 * 32);
+        rc |= dalloc(h, &d.input_stage, (size_t)d.W);
+    }
+    if (cfg->enable_tm) {
+        const size_t S = d.Lcap, G = d.Scap;        // local rows (= ids on an unsharded handle), segment ids
+        const size_t KP = d.KP, WPC = d.WPC;
+        for (int q = 0; q < 2; ++q) {
+            rc |= dalloc(h, &d.act[q], C * WPC);
+            rc |= dalloc(h, &d.pred[q], C * WPC);
+            rc |= dalloc(h, &d.winners[q], k * KP);
+        }
+        rc |= dalloc(h, &d.win[0], C * WPC);
+        rc |= dalloc(h, &d.win[1], C * WPC);
+        d.colwords = (int)((C + 63) / 64) * 2;
+        // (the emit blocks write the bitmap words of whole 256-column blocks)
+        const size_t colwords_padded = (size_t)((C + 255) / 256) * 8;
+        rc |= dalloc(h, &d.colbits[0], colwords_padded);
+        rc |= dalloc(h, &d.colbits[1], colwords_padded);
+        rc |= dalloc(h, &d.bursting, k);
+        rc |= dalloc(h, &d.actw_id, k * WPC + 8);
+        rc |= dalloc(h, &d.winw_idx, k * WPC + 8);
+        rc |= dalloc(h, &d.actcnt, k * WPC + 8);
+        rc |= dalloc(h, &d.act_list, k * WPC + 16);   // (staged into LDS in 16-byte units)
+        rc |= dalloc(h, &d.col_rank[0], colwords_padded);
+        rc |= dalloc(h, &d.col_rank[1], colwords_padded);
+        rc |= dalloc(h, &d.unacc_word, k * WPC + 8);
+        rc |= dalloc(h, &d.fan, (size_t)2 * FAN_COUNTERS * FAN_STRIDE);
+        rc |= dalloc(h, &d.unacc_list, k * KP);
+        for (int q = 0; q < 2; ++q) {
+            rc |= dalloc(h, &d.cellmax[q], C * KP);
+            rc |= dalloc(h, &d.match_bits[q], (S + 255) / 256 * 8);
+        }
+        rc |= dalloc(h, &d.seg_info, S);
+        rc |= dalloc(h, &d.seg_jit, S);
+        // (the learning role's own buffers: a view, which never learns, keeps them too -- its kernels are the parent's, and
+        // none of them is told that a buffer is missing)
+        rc |= dalloc(h, &d.work, (size_t)d.work_cap);
+        rc |= dalloc(h, &d.recyc_cnt, (G + 1023) / 1024);
+        rc |= dalloc(h, &d.recyc_cnt2, ((G + 1023) / 1024 + 1023) / 1024 + 1);
+        rc |= dalloc(h, &d.recyc_need, 2 * k * KP);
+        rc |= dalloc(h, &d.dead_list, (size_t)1 + DEAD_CAP);
+        if (world > 1) {
+            rc |= dalloc(h, &d.seg_gid, S);
+            rc |= dalloc(h, &d.g2l, G);
+            rc |= dalloc(h, &d.dead_bits, (G + 31) / 32 + 32);
+            rc |= dalloc(h, &d.lfree, S);
+            rc |= dalloc(h, &d.asg_gid, k * 32);
+            rc |= dalloc(h, &d.cand_cols, (size_t)d.n_cand + 8);
+            if (!rc && (hipMemsetAsync(d.seg_gid, 0xFF, S * 4, h->stream) != hipSuccess ||
+                        hipMemsetAsync(d.g2l, 0xFF, G * 4, h->stream) != hipSuccess)) { h->err = "hipMemsetAsync failed"; rc = HTM_ERR_HIP; }
+        }
+        rc |= dalloc(h, &h->d_cols_stage, k);
+    }
+    return rc;
 }
 
 extern "C" int htm_create(const htm_config *cfg, htm_handle **out) {
@@ -689,79 +833,8 @@ extern "C" int htm_create(const htm_config *cfg, htm_handle **out) {
     d.sample = cfg->segment_sampling_synapses;
     d.seed = cfg->seed;
 
-    int rc = 0;
-    const size_t C = d.C, k = d.k;
-    rc |= dalloc(h, &d.ctr, 1);
-    rc |= dalloc(h, &d.active_cols[0], k + 8);     // (+8: the TM's list pass reads 8 entries per thread)
-    rc |= dalloc(h, &d.active_cols[1], k + 8);
-    if (cfg->enable_sp) {
-        rc |= dalloc(h, &d.perm, C * d.Ipad);
-        rc |= dalloc(h, &d.mask, C * d.W);
-        rc |= dalloc(h, &d.duty, C);
-        for (int q = 0; q < 2; ++q) {
-            rc |= dalloc(h, &d.overlap[q], C);
-            rc |= dalloc(h, &d.boosted[q], C);
-            rc |= dalloc(h, &d.key[q], C);
-        }
-        rc |= dalloc(h, &d.hist, (size_t)2 * SEL_MAX_PASSES * SEL_BINS);
-        rc |= dalloc(h, &d.hist0, (size_t)2 * HIST0_PAR);
-        rc |= dalloc(h, &d.sel_blk, (C + 255) / 256);
-        rc |= dalloc(h, &d.sel_rec, (C + 255) / 256 * 32);
-        rc |= dalloc(h, &d.input_stage, (size_t)d.W);
-    }
-    if (cfg->enable_tm) {
-        const size_t S = d.Lcap, E = d.E, G = d.Scap;        // local rows (= ids on an unsharded handle), slots, segment ids
-        const size_t KP = d.KP, WPC = d.WPC;
-        for (int q = 0; q < 2; ++q) {
-            rc |= dalloc(h, &d.act[q], C * WPC);
-            rc |= dalloc(h, &d.pred[q], C * WPC);
-            rc |= dalloc(h, &d.winners[q], k * KP);
-        }
-        rc |= dalloc(h, &d.win[0], C * WPC);
-        rc |= dalloc(h, &d.win[1], C * WPC);
-        d.colwords = (int)((C + 63) / 64) * 2;
-        // (the emit blocks write the bitmap words of whole 256-column blocks)
-        const size_t colwords_padded = (size_t)((C + 255) / 256) * 8;
-        rc |= dalloc(h, &d.colbits[0], colwords_padded);
-        rc |= dalloc(h, &d.colbits[1], colwords_padded);
-        rc |= dalloc(h, &d.bursting, k);
-        rc |= dalloc(h, &d.actw_id, k * WPC + 8);
-        rc |= dalloc(h, &d.winw_idx, k * WPC + 8);
-        rc |= dalloc(h, &d.actcnt, k * WPC + 8);
-        rc |= dalloc(h, &d.act_list, k * WPC + 16);   // (staged into LDS in 16-byte units)
-        rc |= dalloc(h, &d.col_rank[0], colwords_padded);
-        rc |= dalloc(h, &d.col_rank[1], colwords_padded);
-        rc |= dalloc(h, &d.unacc_word, k * WPC + 8);
-        rc |= dalloc(h, &d.fan, (size_t)2 * FAN_COUNTERS * FAN_STRIDE);
-        rc |= dalloc(h, &d.unacc_list, k * KP);
-        rc |= dalloc(h, &d.seg_cell, S);
-        rc |= dalloc(h, &d.seg_nsyn, S);
-        rc |= dalloc(h, &d.presyn, S * E);
-        rc |= dalloc(h, &d.sperm, S * E);
-        rc |= dalloc(h, &d.segcount, C * KP);
-        for (int q = 0; q < 2; ++q) {
-            rc |= dalloc(h, &d.cellmax[q], C * KP);
-            rc |= dalloc(h, &d.match_bits[q], (S + 255) / 256 * 8);
-        }
-        rc |= dalloc(h, &d.seg_info, S);
-        rc |= dalloc(h, &d.seg_jit, S);
-        rc |= dalloc(h, &d.work, (size_t)d.work_cap);
-        rc |= dalloc(h, &d.recyc_cnt, (G + 1023) / 1024);
-        rc |= dalloc(h, &d.recyc_cnt2, ((G + 1023) / 1024 + 1023) / 1024 + 1);
-        rc |= dalloc(h, &d.recyc_need, 2 * k * KP);
-        rc |= dalloc(h, &d.dead_list, (size_t)1 + DEAD_CAP);
-        if (world > 1) {
-            rc |= dalloc(h, &d.seg_gid, S);
-            rc |= dalloc(h, &d.g2l, G);
-            rc |= dalloc(h, &d.dead_bits, (G + 31) / 32 + 32);
-            rc |= dalloc(h, &d.lfree, S);
-            rc |= dalloc(h, &d.asg_gid, k * 32);
-            rc |= dalloc(h, &d.cand_cols, (size_t)d.n_cand + 8);
-            if (!rc && (hipMemsetAsync(d.seg_gid, 0xFF, S * 4, h->stream) != hipSuccess ||
-                        hipMemsetAsync(d.g2l, 0xFF, G * 4, h->stream) != hipSuccess)) { h->err = "hipMemsetAsync failed"; rc = HTM_ERR_HIP; }
-        }
-        rc |= dalloc(h, &h->d_cols_stage, k);
-    }
+    int rc = alloc_weights(h);
+    rc |= alloc_stream_state(h);
     if (rc) return fail_create(h, h->err, HTM_ERR_HIP);
     // lanes per SP row: the smallest power of two >= W4, at most 64
     h->G = 1;
@@ -812,6 +885,11 @@ extern "C" int htm_create(const htm_config *cfg, htm_handle **out) {
     // (0: scan blocks with fixed shares, nothing joining; else every block of the launch joins the scan)
     h->knob_scan_dyn = getenv("BITHTM_SCAN_DYN") ? atoi(getenv("BITHTM_SCAN_DYN")) != 0 : 1;
     h->knob_defer_tail = getenv("BITHTM_DEFER_TAIL") ? atoi(getenv("BITHTM_DEFER_TAIL")) != 0 : 1;
+    // groups of inference views: 1 = one scan of the shared store for up to M members at a time; 0 (the default: at the bench shape it
+    // reads 6.4 times fewer bytes than the per-member scans yet takes 2.6 times longer) = a scan per member;
+    // and a cap of M (test knob: several member chunks at small shapes)
+    h->knob_shared_scan = getenv("BITHTM_SHARED_SCAN") ? atoi(getenv("BITHTM_SHARED_SCAN")) != 0 : 0;
+    h->knob_shared_members = getenv("BITHTM_SHARED_SCAN_MEMBERS") ? std::max(0, atoi(getenv("BITHTM_SHARED_SCAN_MEMBERS"))) : 0;
     h->tail_pending = false;
     h->tail_p = 0;
     h->lean_overlap_blocks = getenv("BITHTM_LEAN_OVERLAP") ? std::max(1, atoi(getenv("BITHTM_LEAN_OVERLAP"))) : h->sp_blocks * (RB / 256);
@@ -918,6 +996,154 @@ extern "C" int htm_create(const htm_config *cfg, htm_handle **out) {
     return HTM_OK;
 }
 
+// ------------------------------------------------------------------------------------------
+// Inference views (htm_create_view)
+
+#define REFUSE_ON_VIEW(h, what)                                                                                   \
+    do {                                                                                                          \
+        if ((h)->is_view) {                                                                                       \
+            (h)->err = std::string(what) + ": not available on an inference view (it shares its parent's weights and never learns)"; \
+            return HTM_ERR_STATE;                                                                                 \
+        }                                                                                                         \
+    } while (0)
+
+// a parent call that may change the weights: the views' per-cell maxima were made against rows that may since have moved to
+// other cells, and their next learning role clears all of them (cm_dense_step, as after a state import)
+static void weights_touched(htm_handle *h) {
+    if (h->shared && !h->is_view) {
+        std::lock_guard<std::mutex> lock(g_shared_mutex);
+        h->shared->wgen += 1;
+    }
+}
+
+// The start of every stepping call on a view (and a no-op on any other handle): the parent's held-back launch goes first, a parent
+// that is ahead refuses the call, and the parent's segment count comes over on the shared stream (not a captured node: this runs
+// before any capture).  learning != 0 is refused.
+static int view_enter(htm_handle *h, int learning) {
+    if (!h->is_view) return 0;
+    if (learning) { h->err = "an inference view steps with learning = 0 only (it shares its parent's weights)"; return HTM_ERR_STATE; }
+    htm_handle *par;
+    long long wgen;
+    {
+        std::lock_guard<std::mutex> lock(g_shared_mutex);
+        par = h->shared->parent;
+        wgen = h->shared->wgen;
+    }
+    HIPCHK(h, hipSetDevice(h->device));
+    if (par) {
+        flush_tail(par);
+        if (sp_is_ahead(par)) {
+            h->err = "the view's parent is ahead (its htm_run ended with HTM_RUN_CONTINUE): finish the parent's run first";
+            return HTM_ERR_STATE;
+        }
+        HIPCHK(h, hipMemcpyAsync(&h->d.ctr->S, &par->d.ctr->S, sizeof(int32_t), hipMemcpyDeviceToDevice, h->stream));
+        if (par->seg_pinned) { const int seen = *(volatile int *)par->seg_pinned; par->seg_hint = std::max(par->seg_hint, seen); }
+        h->seg_hint = std::max(h->seg_hint, par->seg_hint);
+    }
+    if (wgen != h->seen_wgen) {
+        h->seen_wgen = wgen;
+        h->dense_step = (uint32_t)h->step_host + 1u;
+        HIPCHK(h, hipMemcpyAsync(&h->d.ctr->cm_dense_step, &h->dense_step, sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));     // (the source is a host word the next call rewrites)
+    }
+    return 0;
+}
+
+extern "C" int htm_create_view(htm_handle *parent, htm_handle **out) {
+    if (!out) return fail_create(nullptr, "htm_create_view: null argument", HTM_ERR_ARGUMENT);
+    *out = nullptr;
+    if (!parent) return fail_create(nullptr, "htm_create_view: null parent", HTM_ERR_ARGUMENT);
+    if (parent->is_view) return fail_create(nullptr, "htm_create_view: the parent is a view itself (make views of the model that owns the weights)", HTM_ERR_STATE);
+    if (!parent->cfg.enable_sp || !parent->cfg.enable_tm) return fail_create(nullptr, "htm_create_view: the parent needs a Spatial Pooler and a Temporal Memory", HTM_ERR_STATE);
+    if (parent->world > 1) return fail_create(nullptr, "htm_create_view: the parent is column-sharded", HTM_ERR_STATE);
+    if (parent->cfg.cell_dim > 64) return fail_create(nullptr, "htm_create_view: cell_dim above 64", HTM_ERR_STATE);
+    if (parent->phase_open || parent->shard_open) return fail_create(nullptr, "htm_create_view: the parent has a step open (htm_sp_phase)", HTM_ERR_STATE);
+    if (hipSetDevice(parent->device) != hipSuccess) return fail_create(nullptr, "htm_create_view: hipSetDevice failed", HTM_ERR_HIP);
+    flush_tail(parent);
+    if (sp_is_ahead(parent)) return fail_create(nullptr, "htm_create_view: the parent is ahead (htm_run ended with HTM_RUN_CONTINUE)", HTM_ERR_STATE);
+    {   // the parent's weights become shared (once): they, and the parent's own stream, now live as long as the last view
+        std::lock_guard<std::mutex> lock(g_shared_mutex);
+        if (!parent->shared) {
+            HtmShared *sh = new HtmShared();
+            sh->allocs.swap(parent->weight_allocs);
+            sh->stream = parent->stream;
+            sh->own_stream = parent->own_stream;
+            sh->parent = parent;
+            sh->refs = 1;
+            sh->wgen = 0;
+            parent->own_stream = false;
+            parent->shared = sh;
+        }
+    }
+    // the parent's scalars and launch sizes (knobs included); none of its buffers, graphs, events or descriptors
+    htm_handle *h = new htm_handle(*parent);
+    h->err.clear();
+    h->allocs.clear();
+    h->weight_allocs.clear();
+    h->graphs.clear();
+    h->shard_graphs.clear();
+    h->prof_events.clear(); h->prof_names.clear(); h->prof_ms.clear(); h->prof_n.clear(); h->prof_all.clear();
+    h->imp_pot.clear(); h->imp_match_seg.clear(); h->imp_seg_cell.clear(); h->imp_seg_nsyn.clear(); h->imp_presyn.clear();
+    h->imp_perm.clear(); h->imp_match_info.clear(); h->imp_match_jit.clear();
+    h->own_stream = false;
+    h->profile = false;
+    h->prof_last = nullptr;
+    h->d_cols_stage = nullptr;
+    h->shard_bank = nullptr;
+    h->rccl_comm = nullptr;
+    h->shard_send = h->shard_recv = nullptr;
+    h->seg_pinned = nullptr;
+    h->ahead_bank = nullptr;
+    h->d_rec = nullptr; h->recording = false;
+    h->reset_bits = nullptr; h->reset_n = 0; h->d_reset = nullptr; h->resetting = false;
+    h->pin_out = nullptr; h->d_pin = nullptr; h->decoding = false; h->d_pin_buf = nullptr;
+    h->tail_pending = false;
+    h->knob_defer_tail = 0;                          // (a view's step is whole when its call returns: see view_enter)
+    h->import_keep = false;
+    h->own_bytes = 0;
+    h->is_view = true;
+    // (the shared scan's knobs are the view's own, read now: a group's form follows its first member's)
+    h->knob_shared_scan = getenv("BITHTM_SHARED_SCAN") ? atoi(getenv("BITHTM_SHARED_SCAN")) != 0 : 0;
+    h->knob_shared_members = getenv("BITHTM_SHARED_SCAN_MEMBERS") ? std::max(0, atoi(getenv("BITHTM_SHARED_SCAN_MEMBERS"))) : 0;
+    {
+        std::lock_guard<std::mutex> lock(g_shared_mutex);
+        h->shared->refs += 1;
+        h->seen_wgen = h->shared->wgen;
+    }
+    Dev &d = h->d;
+    d.trace = nullptr;
+    const Dev &pd = parent->d;
+    int rc = alloc_stream_state(h);
+    if (!rc && getenv("BITHTM_TRACE")) rc = dalloc(h, &d.trace, (size_t)8 * 4096 * 2);
+    if (rc) return fail_create(h, h->err, HTM_ERR_HIP);
+    // the parent's duty cycles and counter block, then a sequence reset (htm_reset.h) -- and the learning role's counts and the
+    // sticky capacity flags start clean
+    bool ok = hipMemcpyAsync(d.duty, pd.duty, (size_t)d.C * sizeof(float), hipMemcpyDeviceToDevice, h->stream) == hipSuccess &&
+              hipMemcpyAsync(d.ctr, pd.ctr, sizeof(Counters), hipMemcpyDeviceToDevice, h->stream) == hipSuccess &&
+              hipMemsetAsync(d.ctr->n_work, 0, sizeof(d.ctr->n_work), h->stream) == hipSuccess &&
+              hipMemsetAsync(d.ctr->n_bind, 0, sizeof(d.ctr->n_bind), h->stream) == hipSuccess &&
+              hipMemsetAsync(&d.ctr->error, 0, sizeof(int32_t), h->stream) == hipSuccess;
+    if (ok) {
+        hipLaunchKernelGGL(k_tm_reset, dim3(reset_blocks(d)), dim3(256), 0, h->stream, d, (int)(h->step_host & 1), (const ResetDev *)nullptr,
+                           (RecDev *)nullptr, (uint32_t)h->step_host);
+        ok = hipGetLastError() == hipSuccess;
+    }
+    if (hipHostMalloc((void **)&h->seg_pinned, sizeof(int), hipHostMallocDefault) == hipSuccess) *h->seg_pinned = parent->seg_hint; else h->seg_pinned = nullptr;
+    if (!ok || hipStreamSynchronize(h->stream) != hipSuccess) return fail_create(h, "htm_create_view: copying the parent's stream state failed", HTM_ERR_HIP);
+    {
+        std::lock_guard<std::mutex> lock(g_registry_mutex);
+        g_registry.push_back(h);
+    }
+    refresh_exchange_mode(h);
+    *out = h;
+    return HTM_OK;
+}
+
+extern "C" int64_t htm_device_bytes(htm_handle *h) {
+    if (!h) return HTM_ERR_ARGUMENT;
+    return h->own_bytes;
+}
+
 // TemporalMemory.process(..., epsilon=) (networks.py:91): the tolerance of the "best matching" / "least used" ties
 // (networks.py:81,88; projections.py:267), compared as float32.  0 < epsilon <= 1: the other uses (prediction > epsilon,
 // potential < epsilon) then mean what they mean at 1e-8.  Kernels get it with their arguments: cached graphs are dropped.
@@ -969,7 +1195,9 @@ static int check_rows(htm_handle *h, const void *rows, int row_begin, int row_co
 }
 
 extern "C" int htm_sp_set_permanence(htm_handle *h, const double *rows, int32_t row_begin, int32_t row_count) {
+    if (h) REFUSE_ON_VIEW(h, "htm_sp_set_permanence");
     if (h) flush_tail(h);
+    if (h) weights_touched(h);
     int rc = check_rows(h, rows, row_begin, row_count);
     if (rc) return rc;
     REJECT_WHEN_AHEAD(h);
@@ -1026,8 +1254,11 @@ extern "C" int htm_step(htm_handle *h, const uint32_t *packed_input, int32_t lea
     if (!h->cfg.enable_sp || !h->cfg.enable_tm) { h->err = "htm_step needs a handle with SP and TM"; return HTM_ERR_STATE; }
     if (h->world > 1) { h->err = "sharded handle: use htm_shard_begin / htm_shard_finish"; return HTM_ERR_STATE; }
     HIPCHK(h, hipSetDevice(h->device));
+    int rc = view_enter(h, learning);
+    if (rc) return rc;
+    if (learning) weights_touched(h);
     refresh_exchange_mode(h);
-    int rc = close_open_phases(h);
+    rc = close_open_phases(h);
     if (rc) return rc;
     if (h->d.W > ARG_INPUT_WORDS) {                 // (an input too wide for the launch's arguments: staged by a copy)
         flush_tail(h);
@@ -1124,6 +1355,8 @@ extern "C" int htm_sp_phase(htm_handle *h, int32_t phase, const void *data, int6
     REJECT_WHEN_AHEAD(h);
     if (!h->cfg.enable_sp) { h->err = "handle has no Spatial Pooler"; return HTM_ERR_STATE; }
     if (h->world > 1) { h->err = "htm_sp_phase: not available on a column-sharded handle"; return HTM_ERR_STATE; }
+    REFUSE_ON_VIEW(h, "htm_sp_phase");
+    if (phase == HTM_SP_LEARN) weights_touched(h);
     HIPCHK(h, hipSetDevice(h->device));
     refresh_exchange_mode(h);
     Dev &d = h->d;
@@ -1207,6 +1440,11 @@ extern "C" int htm_tm_step(htm_handle *h, const int32_t *active_column, int32_t 
     if (!h->cfg.enable_tm) { h->err = "handle has no Temporal Memory"; return HTM_ERR_STATE; }
     Dev &d = h->d;
     if (n < 0 || n > d.k) { h->err = "htm_tm_step: more active columns than active_columns"; return HTM_ERR_ARGUMENT; }
+    {
+        const int rc = view_enter(h, learning);
+        if (rc) return rc;
+        if (learning) weights_touched(h);
+    }
     std::vector<int> cols(active_column, active_column + n);
     std::sort(cols.begin(), cols.end());
     for (int i = 0; i < n; ++i)
@@ -1239,6 +1477,8 @@ extern "C" int htm_tm_update(htm_handle *h, const int32_t *columns, const uint32
     REJECT_WHEN_AHEAD(h);
     if (!h->cfg.enable_tm) { h->err = "handle has no Temporal Memory"; return HTM_ERR_STATE; }
     if (h->world > 1) { h->err = "htm_tm_update: not available on a column-sharded handle"; return HTM_ERR_STATE; }
+    REFUSE_ON_VIEW(h, "htm_tm_update");
+    weights_touched(h);
     Dev &d = h->d;
     if (n < 0 || n > d.k) { h->err = "htm_tm_update: more columns with learning cells than active_columns"; return HTM_ERR_ARGUMENT; }
     // ascending columns (the order of the winner list, networks.py:103-104 under the ascending-column policy)
@@ -1307,6 +1547,10 @@ extern "C" int htm_tm_scan(htm_handle *h, const uint32_t *active_words) {
     REJECT_WHEN_AHEAD(h);
     if (!h->cfg.enable_tm) { h->err = "handle has no Temporal Memory"; return HTM_ERR_STATE; }
     if (h->world > 1) { h->err = "htm_tm_scan: not available on a column-sharded handle"; return HTM_ERR_STATE; }
+    {
+        const int rc = view_enter(h, 0);
+        if (rc) return rc;
+    }
     Dev &d = h->d;
     HIPCHK(h, hipSetDevice(h->device));
     const int p = (int)(h->step_host & 1);
@@ -1341,6 +1585,11 @@ static int run_or_prepare(htm_handle *h, const uint32_t *device_inputs, int32_t 
     if (!h->cfg.enable_sp || !h->cfg.enable_tm) { h->err = "htm_run needs a handle with SP and TM"; return HTM_ERR_STATE; }
     if (h->world > 1) { h->err = "sharded handle: use htm_shard_begin / htm_shard_finish"; return HTM_ERR_STATE; }
     HIPCHK(h, hipSetDevice(h->device));
+    {
+        const int rc = view_enter(h, learning);
+        if (rc) return rc;
+    }
+    if (learning && !dry && n_steps > 0) weights_touched(h);
     refresh_exchange_mode(h);
     learning = learning ? 1 : 0;
     // (a short call is launched eagerly whatever the flag says: a graph launch on an idle device starts its first kernel
@@ -1572,6 +1821,7 @@ static int shard_enqueue_finish(htm_handle *h, const uint32_t *bank, int n_input
 extern "C" int htm_shard_begin(htm_handle *h, const uint32_t *device_inputs, int32_t n_inputs, const uint32_t *packed_input,
                                int32_t learning, void *send_device) {
     if (!h || !send_device || (!device_inputs == !packed_input)) return HTM_ERR_ARGUMENT;
+    REFUSE_ON_VIEW(h, "htm_shard_begin");
     if (h->world < 2) { h->err = "htm_shard_begin: handle is not sharded"; return HTM_ERR_STATE; }
     if (h->shard_open) { h->err = "htm_shard_begin: previous step not finished"; return HTM_ERR_STATE; }
     HIPCHK(h, hipSetDevice(h->device));
@@ -1595,6 +1845,7 @@ extern "C" int htm_shard_begin(htm_handle *h, const uint32_t *device_inputs, int
 
 extern "C" int htm_shard_finish(htm_handle *h, const void *recv_device, int32_t learning) {
     if (!h || !recv_device) return HTM_ERR_ARGUMENT;
+    REFUSE_ON_VIEW(h, "htm_shard_finish");
     if (h->world < 2 || !h->shard_open) { h->err = "htm_shard_finish: no step in progress"; return HTM_ERR_STATE; }
     HIPCHK(h, hipSetDevice(h->device));
     h->shard_open = false;
@@ -1701,6 +1952,7 @@ extern "C" int htm_rccl_selftest(int32_t device) {
 
 extern "C" int htm_shard_comm_init(htm_handle *h, const void *unique_id128) {
     if (!h || !unique_id128) return HTM_ERR_ARGUMENT;
+    REFUSE_ON_VIEW(h, "htm_shard_comm_init");
     if (h->world < 2) { h->err = "htm_shard_comm_init: handle is not sharded"; return HTM_ERR_STATE; }
     if (h->rccl_comm) { h->err = "htm_shard_comm_init: already initialised"; return HTM_ERR_STATE; }
     if (const char *err = load_rccl()) { h->err = err; return HTM_ERR_HIP; }
@@ -1826,6 +2078,7 @@ extern "C" int htm_shard_group_step(htm_handle *const *handles, int32_t n, const
 
 extern "C" int htm_shard_step(htm_handle *h, const uint32_t *device_inputs, int32_t n_inputs, const uint32_t *packed_input, int32_t learning) {
     if (!h || (!device_inputs == !packed_input)) return HTM_ERR_ARGUMENT;
+    REFUSE_ON_VIEW(h, "htm_shard_step");
     if (h->world < 2 || !h->rccl_comm) { h->err = "htm_shard_step: needs a sharded handle after htm_shard_comm_init"; return HTM_ERR_STATE; }
     if (h->shard_open) { h->err = "htm_shard_step: a step opened with htm_shard_begin is not finished"; return HTM_ERR_STATE; }
     HIPCHK(h, hipSetDevice(h->device));
@@ -1952,6 +2205,7 @@ static int shard_run(htm_handle *const *hs, int n, const uint32_t *const *banks,
 
 extern "C" int htm_shard_run(htm_handle *h, const uint32_t *device_inputs, int32_t n_inputs, int32_t n_steps, int32_t learning, int32_t use_graph) {
     if (!h || !device_inputs || n_inputs < 1 || n_steps < 0) return HTM_ERR_ARGUMENT;
+    REFUSE_ON_VIEW(h, "htm_shard_run");
     if (h->world < 2 || !h->rccl_comm) { h->err = "htm_shard_run: needs a sharded handle after htm_shard_comm_init"; return HTM_ERR_STATE; }
     if (h->shard_open) { h->err = "htm_shard_run: a step opened with htm_shard_begin is not finished"; return HTM_ERR_STATE; }
     htm_handle *hs[1] = {h};
@@ -1980,6 +2234,8 @@ extern "C" int htm_shard_group_run(htm_handle *const *handles, int32_t n, const 
 extern "C" int htm_populate(htm_handle *h, int64_t cell_begin, int64_t cell_end, int32_t segments_per_cell, int32_t synapses,
                             double perm_lo, double perm_hi, uint32_t seed) {
     if (!h) return HTM_ERR_ARGUMENT;
+    REFUSE_ON_VIEW(h, "htm_populate");
+    weights_touched(h);
     if (h) flush_tail(h);
     if (!h->cfg.enable_tm) { h->err = "handle has no Temporal Memory"; return HTM_ERR_STATE; }
     Dev &d = h->d;
@@ -2289,6 +2545,10 @@ extern "C" int htm_write(htm_handle *h, int32_t field, const void *src, int64_t 
     if (!h || (!src && count > 0) || count < 0) return HTM_ERR_ARGUMENT;
     if (h) flush_tail(h);
     REJECT_WHEN_AHEAD(h);
+    if (field == HTM_F_SEG_CELL || field == HTM_F_SEG_NSYN || field == HTM_F_SEG_PRESYN || field == HTM_F_SEG_PERM || field == HTM_F_SEGCOUNT) {
+        REFUSE_ON_VIEW(h, "htm_write of a weight field");
+        weights_touched(h);
+    }
     HIPCHK(h, hipSetDevice(h->device));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     Dev &d = h->d;
@@ -2352,6 +2612,7 @@ extern "C" int htm_import_begin(htm_handle *h, int64_t step_index) {
     if (h) flush_tail(h);
     REJECT_WHEN_AHEAD(h);
     if (h->world > 1 && step_index == HTM_IMPORT_PREV_STATE) { h->err = "prev_state adoption is not available on a column-sharded handle"; return HTM_ERR_STATE; }
+    if (step_index != HTM_IMPORT_PREV_STATE) REFUSE_ON_VIEW(h, "a state import (other than HTM_IMPORT_PREV_STATE)");
     if (h->shard_open) { h->err = "htm_import_begin: a step opened with htm_shard_begin is not finished"; return HTM_ERR_STATE; }
     HIPCHK(h, hipSetDevice(h->device));
     HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -2378,6 +2639,8 @@ extern "C" int htm_import_commit(htm_handle *h, int32_t segments, int32_t matchi
     Dev &d = h->d;
     const bool keep = h->import_keep;              // TemporalMemory.process(prev_state=X): the previous step's State only
     h->import_keep = false;
+    if (!keep) REFUSE_ON_VIEW(h, "a state import (other than HTM_IMPORT_PREV_STATE)");
+    if (!keep) weights_touched(h);
     Counters c;
     int rc = read_counters(h, &c);
     if (rc) return rc;
@@ -2516,7 +2779,9 @@ extern "C" int htm_reset(htm_handle *h) {
     if (h->shard_open) { h->err = "htm_reset: a step opened with htm_shard_begin is not finished"; return HTM_ERR_STATE; }
     if (!h->cfg.enable_tm) { h->err = "htm_reset: the handle has no Temporal Memory"; return HTM_ERR_STATE; }
     HIPCHK(h, hipSetDevice(h->device));
-    int rc = close_open_phases(h);
+    int rc = view_enter(h, 0);
+    if (rc) return rc;
+    rc = close_open_phases(h);
     if (rc) return rc;
     LAUNCH(h, "tm_reset", k_tm_reset, reset_blocks(h->d), 256, h->d, (int)(h->step_host & 1), (const ResetDev *)nullptr, (RecDev *)nullptr,
            (uint32_t)h->step_host);
@@ -2556,6 +2821,8 @@ extern "C" int htm_predicted_input(htm_handle *h, int32_t *host_dst) {
     int rc = pin_refuse(h, "htm_predicted_input");
     if (rc) return rc;
     if (h->shard_open || h->phase_open) { h->err = "htm_predicted_input: a step of the handle is open (htm_shard_begin / htm_sp_phase)"; return HTM_ERR_STATE; }
+    rc = view_enter(h, 0);
+    if (rc) return rc;
     HIPCHK(h, hipSetDevice(h->device));
     const Dev &d = h->d;
     if (!h->d_pin_buf) { rc = dalloc(h, &h->d_pin_buf, d.I); if (rc) return rc; }
@@ -2640,6 +2907,10 @@ struct htm_group {
     // graphs keyed by (parity + 2 if recorded + 4 if decoding, learning, tail form, spec, span, bank table, n_inputs)
     std::map<std::tuple<int, int, int, int, int, const void *, int>, hipGraphExec_t> graphs;
     bool recording, decoding;
+    // inference views (htm_create_view): some member is a view; every member aliases one set of weights (then the steps with
+    // learning = 0 scan the store once per chunk of share_m members: kgrp_scan_shared, share_chunks x share_blocks blocks)
+    bool has_view, shared;
+    int share_m, share_chunks, share_blocks;
 };
 
 #define GHIPCHK(g, call)                                                                         \
@@ -2724,6 +2995,30 @@ extern "C" int htm_group_create(htm_handle *const *members, int32_t n, htm_group
     g->recording = g->decoding = false;
     auto fail = [&](int rc) { g_create_error = g->err; htm_group_destroy(g); return rc; };
     if (hipSetDevice(g->device) != hipSuccess) { g->err = "htm_group_create: hipSetDevice failed"; return fail(HTM_ERR_HIP); }
+    g->has_view = false;
+    g->shared = true;
+    for (const htm_handle *h : g->m) {
+        g->has_view |= h->is_view;
+        g->shared &= h->d.presyn == h0->d.presyn && h->d.perm == h0->d.perm;
+    }
+    g->shared = g->shared && g->has_view && h0->knob_shared_scan;
+    g->share_m = g->share_chunks = g->share_blocks = 0;
+    if (g->shared) {
+        // M: the members whose column bitmaps fit 64 KiB of LDS beside each other (at most GRP_SHARED_MMAX, and the knob's cap);
+        // the grid: the blocks of that LDS size resident at once, at most one per 64 rows of the pool
+        const size_t per = (size_t)h0->d.colwords * 4;
+        int M = (int)std::min<size_t>(GRP_SHARED_MMAX, std::max<size_t>(1, (64 * 1024) / per));
+        if (h0->knob_shared_members > 0) M = std::min(M, h0->knob_shared_members);
+        M = std::min(M, n);
+        g->share_m = M;
+        g->share_chunks = (n + M - 1) / M;
+        int per_cu = 0;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void *)kgrp_scan_shared, 256, (size_t)M * per) != hipSuccess || per_cu < 1) {
+            (void)hipGetLastError();
+            per_cu = 1;
+        }
+        g->share_blocks = std::max(1, std::min(h0->scan_blocks, per_cu * h0->cus));
+    }
     g->host_tab.resize(n);
     std::vector<RecDev *> recs(n);
     std::vector<PinDev *> pins(n);
@@ -2776,7 +3071,7 @@ static int group_table(htm_group *g, std::map<K, T *> &tabs, const K &key, const
 }
 
 // How the group's steps are launched: the form of the tail and the scan's speculation, from the most conservative member
-struct GroupForm { bool fuse, large; int spec; };
+struct GroupForm { bool fuse, large, shared; int spec; };
 
 static GroupForm group_form(htm_group *g) {
     int lo = 1 << 30, hi = 0;
@@ -2791,6 +3086,7 @@ static GroupForm group_form(htm_group *g) {
     f.large = h0->knob_scan_large >= 0 ? h0->knob_scan_large != 0 : hi > h0->scan_large_above;
     f.fuse = h0->knob_fuse_tm && !f.large && scan_lds(h0->d, 1) <= 64 * 1024;
     f.spec = std::min(lo / SCAN_SEGS, h0->scan_blocks) & ~63;
+    f.shared = false;                               // (set by the caller for a step without learning)
     return f;
 }
 
@@ -2811,7 +3107,20 @@ static void group_enqueue_step(htm_group *g, const uint32_t *const *banks, int n
     const dim3 g_mid(1 + n_cls + rows_mid + h->zero_blocks, B);
     LAUNCH_ON(h, s, 0, "group:tm_mid", kgrp_middle, g_mid, 256, tab, p, learning, n_cls, banks, n_inputs, rows_mid);
     const int epl = learn_epl(d);
-    if (f.fuse) {
+    if (f.shared) {
+        // every member's learning role (with learning = 0: the previous scan's per-cell maxima cleared, nothing else), then ONE
+        // pass over the shared store for each chunk of share_m members (htm_group.h)
+        const dim3 g_learn(kLearnBlocks, B);
+        const size_t lds = learn_lds(epl);
+        switch (epl) {
+            case 1: LAUNCH_ON(h, s, lds, "group:tm_learn", kgrp_learn<1>, g_learn, RB, tab, p); break;
+            case 2: LAUNCH_ON(h, s, lds, "group:tm_learn", kgrp_learn<2>, g_learn, RB, tab, p); break;
+            case 4: LAUNCH_ON(h, s, lds, "group:tm_learn", kgrp_learn<4>, g_learn, RB, tab, p); break;
+            default: LAUNCH_ON(h, s, lds, "group:tm_learn", kgrp_learn<8>, g_learn, RB, tab, p); break;
+        }
+        const dim3 g_scan(g->share_blocks, g->share_chunks);
+        LAUNCH_ON(h, s, (size_t)g->share_m * d.colwords * 4, "group:tm_scan_shared", kgrp_scan_shared, g_scan, 256, tab, B, g->share_m, p);
+    } else if (f.fuse) {
         const size_t lds = std::max(learn_lds(epl, 256), scan_lds(d, 1));
         const dim3 g_tail(h->lean_learn_blocks + h->lean_scan_blocks + rows_tail, B);
         const char *name = rows_tail ? "group:tm_learn+tm_scan+sp_learn" : "group:tm_learn+tm_scan";
@@ -2862,6 +3171,10 @@ static int group_check(htm_group *g, const uint32_t *const *banks, const htm_run
             return HTM_ERR_STATE;
         }
         if (banks && !banks[i]) { g->err = who + ": null bank"; return HTM_ERR_ARGUMENT; }
+        if (h->is_view) {
+            std::lock_guard<std::mutex> lock(g_shared_mutex);
+            if (h->shared->parent && sp_is_ahead(h->shared->parent)) { g->err = who + ": the view's parent is ahead (HTM_RUN_CONTINUE)"; return HTM_ERR_STATE; }
+        }
         if (records) {
             const htm_run_record &r = records[i];
             if (r.struct_bytes != sizeof(htm_run_record)) { g->err = who + ": struct_bytes != sizeof(htm_run_record)"; return HTM_ERR_ARGUMENT; }
@@ -2877,6 +3190,7 @@ static int group_check(htm_group *g, const uint32_t *const *banks, const htm_run
 static int group_join(htm_group *g) {
     for (htm_handle *h : g->m) {
         flush_tail(h);
+        if (int rc = view_enter(h, 0)) { g->err = h->err; return rc; }
         if (close_open_phases(h)) { g->err = h->err; return HTM_ERR_HIP; }
         if (h->stream != g->stream) GHIPCHK(g, hipStreamSynchronize(h->stream));
     }
@@ -2925,7 +3239,8 @@ static int group_run(htm_group *g, const uint32_t **bank_tab, int n_inputs, int 
         LAUNCH_ON(h0, s, 0, "group:predicted_input", kgrp_pin_begin, g_begin, 256, g->d_tab, (int)((h0->step_host + 1) & 1), g->d_pins, out_tab, n_steps);
         g->decoding = true;
     }
-    const GroupForm f = group_form(g);
+    GroupForm f = group_form(g);
+    f.shared = g->shared && !learning;
     const bool graph = (use_graph & 1) && !h0->profile && n_steps >= h0->eager_below;
     const int span_max = h0->graph_steps;
     int p = (int)(h0->step_host & 1);
@@ -2937,7 +3252,7 @@ static int group_run(htm_group *g, const uint32_t **bank_tab, int n_inputs, int 
             continue;
         }
         const int span = n_steps - t >= span_max ? span_max : 1;
-        auto key = std::make_tuple(p + (g->recording ? 2 : 0) + (g->decoding ? 4 : 0), learning, (f.fuse ? 1 : 0) + (f.large ? 2 : 0), f.spec, span,
+        auto key = std::make_tuple(p + (g->recording ? 2 : 0) + (g->decoding ? 4 : 0), learning, (f.fuse ? 1 : 0) + (f.large ? 2 : 0) + (f.shared ? 4 : 0), f.spec, span,
                                    (const void *)bank_tab, n_inputs);
         auto it = g->graphs.find(key);
         if (it == g->graphs.end()) {
@@ -2958,6 +3273,7 @@ static int group_run(htm_group *g, const uint32_t **bank_tab, int n_inputs, int 
     for (htm_handle *h : g->m) {
         h->step_host += n_steps;
         h->window_known = true;                   // (every select leaves the next step's window behind)
+        if (learning) weights_touched(h);
     }
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) { g->err = std::string("kernel launch: ") + hipGetErrorString(e); return HTM_ERR_HIP; }
@@ -2972,6 +3288,7 @@ extern "C" int htm_group_run(htm_group *g, const uint32_t *const *device_banks, 
                              int32_t use_graph, const htm_run_record *records) {
     if (!g) return HTM_ERR_ARGUMENT;
     if (!device_banks || n_inputs < 1 || n_steps < 0) { g->err = "htm_group_run: need device_banks, n_inputs >= 1 and n_steps >= 0"; return HTM_ERR_ARGUMENT; }
+    if (learning && g->has_view) { g->err = "htm_group_run: a group with inference views steps with learning = 0 only"; return HTM_ERR_STATE; }
     int rc = group_check(g, device_banks, records);
     if (rc || n_steps == 0) return rc;
     GHIPCHK(g, hipSetDevice(g->device));
@@ -2987,6 +3304,7 @@ extern "C" int htm_group_run(htm_group *g, const uint32_t *const *device_banks, 
 extern "C" int htm_group_step(htm_group *g, const uint32_t *packed_inputs, int32_t learning, const htm_run_record *records) {
     if (!g) return HTM_ERR_ARGUMENT;
     if (!packed_inputs) { g->err = "htm_group_step: null packed_inputs"; return HTM_ERR_ARGUMENT; }
+    if (learning && g->has_view) { g->err = "htm_group_step: a group with inference views steps with learning = 0 only"; return HTM_ERR_STATE; }
     int rc = group_check(g, nullptr, records);
     if (rc) return rc;
     GHIPCHK(g, hipSetDevice(g->device));

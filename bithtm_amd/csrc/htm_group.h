@@ -121,4 +121,127 @@ __global__ __launch_bounds__(256) void kgrp_rec_step(const Dev *__restrict__ tab
     role_rec_step(tab[blockIdx.y], p, recs[blockIdx.y]);
 }
 
+// ------------------------------------------------------------------------------------------
+// Inference views (htm_create_view): a group whose members all alias ONE segment store, stepped without
+// learning.  kgrp_scan replaces nothing of the store between its members' scans, yet reads every row once per member; this scan
+// reads each row once per chunk of M members (grid y = chunk).  The block stages the M members' column bitmaps in LDS (colwords
+// words each, M * colwords * 4 <= 64 KiB), and each wave takes groups of 16 rows as role_scan does (8 lanes per row, two rows
+// per lane group, 4 synapses per lane and chunk of 32).  Every chunk of a row is loaded ONCE; for each member the wave tests
+// the chunk's synapses against that member's bitmap, gathers that member's active-cell words for the hits and adds potential
+// and connected counts (the connected flag is presyn bit 31, as the solo scan reads it) into the member's own accumulators
+// (registers: GRP_SHARED_MMAX x 2 per lane).  A matching row is then published into each member's own buffers with the
+// member's own jitter key (its step index) -- seg_info, seg_jit, match bits, per-cell maxima, prediction bits -- exactly
+// what role_scan publishes, so the members end bit-identical to their per-member scans (only the order of the atomics
+// differs, and atomicMax / atomicOr do not depend on it).  Block 0 does role_scan's counter housekeeping for each member.
+//
+// Not carried over from role_scan: the speculative first batch (n_spec -- the loads of a block's first rows before the segment
+// count arrives: one round trip per block, and this grid is only the blocks resident at once, each streaming many groups), the
+// early-out of rows that cannot match (per member it would need the hit counts of every member before any gather -- the gathers
+// are of hits only, most rows have few), and the LDS tables of the three-launch schedule.  Rows on a learning role's work list
+// (SEG_BUSY) are skipped as role_scan skips them; with learning = 0 there are none.
+// The members' learning role (kgrp_learn, learning = 0) runs before this launch: it clears the previous scan's maxima.
+#define GRP_SHARED_MMAX 16
+
+__global__ __launch_bounds__(256) void kgrp_scan_shared(const Dev *__restrict__ tab, int B, int M, int p) {
+    const int m0 = (int)blockIdx.y * M, nm = min(M, B - m0);
+    const Dev &d = tab[m0];                          // (the store: the same rows in every member's descriptor)
+    const int cw = d.colwords, lk = d.LK;
+    uint32_t *s_bits = (uint32_t *)dyn_lds;          // [nm][cw]
+    for (int m = 0; m < nm; ++m) {
+        const uint32_t *src = tab[m0 + m].colbits[p];
+        for (int i = threadIdx.x; i < cw; i += 256) s_bits[m * cw + i] = src[i];
+    }
+    if (blockIdx.x == 0 && (int)threadIdx.x < nm) {  // role_scan's housekeeping, member by member
+        Counters *c = tab[m0 + (int)threadIdx.x].ctr;
+        c->step[p ^ 1] = c->step[p] + 1;
+        c->has_distal = 1;
+        c->n_work[p ^ 1] = 0;
+        c->n_bind[p ^ 1] = 0;
+    }
+    __syncthreads();
+    const int S = d.ctr->S;                          // (equal in every member: copied from the parent by each call)
+    const int wave = threadIdx.x >> 6, gi = (threadIdx.x & 63) >> 3, l = threadIdx.x & 7;
+    const int n_waves = (int)gridDim.x * 4;
+    for (int g = (int)blockIdx.x * 4 + wave; g * 16 < S; g += n_waves) {
+        int seg[2], n[2];
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {
+            seg[u] = g * 16 + u * 8 + gi;
+            const int nn = seg[u] < S ? d.seg_nsyn[seg[u]] : 0;
+            n[u] = (nn & (int)SEG_BUSY) ? 0 : nn;
+        }
+        uint32_t acc[GRP_SHARED_MMAX][2];
+#pragma unroll
+        for (int m = 0; m < GRP_SHARED_MMAX; ++m) acc[m][0] = acc[m][1] = 0u;
+        for (int c = 0; __any(n[0] > c * 32 || n[1] > c * 32); ++c) {
+            uint32_t e[8], valid = 0u;
+#pragma unroll
+            for (int u = 0; u < 2; ++u) {
+                int4 v = make_int4(0, 0, 0, 0);
+                if (n[u] > c * 32) v = *(const int4 *)(d.presyn + (size_t)seg[u] * d.E + c * 32 + l * 4);
+                const int nv = min(max(n[u] - c * 32 - l * 4, 0), 4);
+                valid |= ((1u << nv) - 1u) << (4 * u);
+                e[4 * u] = (uint32_t)v.x; e[4 * u + 1] = (uint32_t)v.y; e[4 * u + 2] = (uint32_t)v.z; e[4 * u + 3] = (uint32_t)v.w;
+            }
+#pragma unroll
+            for (int i = 0; i < 8; ++i) e[i] = ((valid >> i) & 1u) ? e[i] : 0u;     // (a slot past the row's count names nothing)
+#pragma unroll
+            for (int m = 0; m < GRP_SHARED_MMAX; ++m) {
+                if (m < nm) {                        // (block-uniform)
+                    const uint32_t *bits = s_bits + m * cw;
+                    uint32_t hit = 0u;
+#pragma unroll
+                    for (int i = 0; i < 8; ++i) {
+                        const uint32_t w = bits[(e[i] & SYN_CELL) >> (lk + 5)];
+                        hit |= ((w >> ((e[i] >> lk) & 31)) & 1u) << i;
+                    }
+                    hit &= valid;
+                    if (hit) {
+                        const uint32_t *act = tab[m0 + m].act[p];
+#pragma unroll
+                        for (int i = 0; i < 8; ++i)
+                            if ((hit >> i) & 1u) {
+                                const uint32_t a = (act[(e[i] & SYN_CELL) >> 5] >> (e[i] & 31)) & 1u;
+                                acc[m][i >> 2] += a + ((a & (e[i] >> 31)) << 16);     // potential (:247) | connected-active << 16 (:171-172)
+                            }
+                    }
+                }
+            }
+        }
+#pragma unroll
+        for (int m = 0; m < GRP_SHARED_MMAX; ++m) {
+            if (m < nm) {
+                const Dev &dm = tab[m0 + m];
+                bool matching[2];
+                int pot[2], conn[2];
+#pragma unroll
+                for (int u = 0; u < 2; ++u) {
+                    const uint32_t sum = (uint32_t)group8_sum_first((int)acc[m][u]);      // (valid in the row's first lane only)
+                    pot[u] = (int)(sum & 0xFFFFu);
+                    conn[u] = (int)(sum >> 16);
+                    matching[u] = l == 0 && seg[u] < S && pot[u] >= dm.match_thr;        // :247
+                }
+                if (__any(matching[0] || matching[1])) {
+                    const uint32_t base3 = htm_stream_base(dm.seed, HTM_STREAM_SEGMENT_JITTER, dm.ctr->step[p]);
+#pragma unroll
+                    for (int u = 0; u < 2; ++u)
+                        if (matching[u]) {
+                            const int cell = d.seg_cell[seg[u]];
+                            const float jit = htm_jitter((float)pot[u], htm_draw24(base3, (uint32_t)seg[u], 0u));   // :234-235
+                            const bool active = conn[u] >= dm.act_thr;                       // :250
+                            atomicMax(&dm.cellmax[p][cell], __float_as_uint(jit));          // :237
+                            if (active) atomicOr(&dm.pred[p][cell >> 5], 1u << (cell & 31));   // :251
+                            dm.seg_info[seg[u]] = (uint32_t)pot[u] | ((uint32_t)conn[u] << 12) | 0x40000000u | (active ? 0x80000000u : 0u);
+                            dm.seg_jit[seg[u]] = jit;
+                        }
+                }
+                const u64 b0 = __ballot(matching[0]), b1 = __ballot(matching[1]);      // (role_scan's gathering of the 16 bits)
+                const uint32_t bits = (uint32_t)(((b0 & 0x0101010101010101ull) * 0x0102040810204080ull) >> 56) |
+                                      ((uint32_t)(((b1 & 0x0101010101010101ull) * 0x0102040810204080ull) >> 56) << 8);
+                if ((threadIdx.x & 63) == 0 && bits) atomicOr(&dm.match_bits[p][g >> 1], bits << (16 * (g & 1)));
+            }
+        }
+    }
+}
+
 #endif

@@ -131,6 +131,34 @@ class Engine:
                                 row_begin=c0)
             self.words = self.info().words_per_row
 
+    # the parent's attributes an inference view shares (shape, configuration, step index; not its buffers)
+    _VIEW_ATTRS = ("lib", "input_dim", "column_dim", "cell_dim", "active_columns", "has_sp", "has_tm", "cell_words", "shard_rank",
+                   "shard_world", "column_range", "segment_capacity", "segment_slots", "seed", "device", "words", "steps", "_stream_owner")
+
+    @classmethod
+    def view_of(cls, parent):
+        """An inference view of `parent` (htm_create_view): a handle that aliases the parent's weights and owns its stream
+        state, starting as the parent would be after reset().  It steps with learning=False only."""
+        v = cls.__new__(cls)
+        for a in cls._VIEW_ATTRS:
+            if a in parent.__dict__:
+                setattr(v, a, parent.__dict__[a])
+        handle = C.c_void_p()
+        rc = v.lib.htm_create_view(parent.h, C.byref(handle))
+        if rc != 0:
+            raise HtmError(f"htm_create_view failed ({rc}): {v.lib.htm_last_error(None).decode()}")
+        v.h = handle
+        v._banks = []
+        v._record_bufs = {}
+        v._reset_bufs = {}
+        v._auto_grow = False                        # (the parent's pool grows; a view never adds a segment)
+        v.is_view = True
+        return v
+
+    def device_bytes(self):
+        """Device bytes this handle allocated itself (a view does not count the weights it shares: htm_device_bytes)."""
+        return int(self._check(self.lib.htm_device_bytes(self.h), "htm_device_bytes"))
+
     def __del__(self):
         h, self.h = getattr(self, "h", None), None
         if h:

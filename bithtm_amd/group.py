@@ -9,6 +9,9 @@ of them, and every member ends bit-identical to the same model stepped alone.
     group.run(inputs, steps)                  # inputs: bool [64, n_inputs, 1000]; member i cycles through inputs[i]
     rec = group.process(x)                    # x: bool [64, 1000], one tick of every member; rec.anomaly_score[i]
     group.models[3].process(x[3])             # members stay ordinary models between group calls
+
+    views = ModelGroup.views(trained, 16)     # 16 inference views of one trained model: one copy of the weights, and the
+    views.run(inputs, steps)                  # store scanned once per step for up to M of them together (learning=False)
 """
 
 import ctypes as C
@@ -17,7 +20,8 @@ import numpy as np
 
 from . import _lib as L
 from .engine import HtmError, pack_bits
-from .networks import (HierarchicalTemporalMemory, RunRecord, _grow_if_needed, _join_record, _record_fields, retire_states)
+from .networks import (HierarchicalTemporalMemory, InferenceView, RunRecord, _grow_if_needed, _join_record, _record_fields,
+                       retire_states)
 
 
 class SharedStream:
@@ -78,13 +82,35 @@ class ModelGroup:
             for attr in ("input_dim", "column_dim", "cell_dim", "active_columns", "segment_capacity", "segment_slots"):
                 if getattr(e, attr) != getattr(e0, attr):
                     raise ValueError(f"member {i}: {attr} {getattr(e, attr)} differs from member 0's {getattr(e0, attr)}")
-            if getattr(e, "_auto_grow", False) != getattr(e0, "_auto_grow", False):
+            if not self._has_views(models) and getattr(e, "_auto_grow", False) != getattr(e0, "_auto_grow", False):
                 raise ValueError(f"member {i}: either every member's segment pool is default-sized (and grows) or none is")
         self.models = models
         self.lib = L.load()
         self._g = None
         self._engines = None
         self._build()
+
+    @staticmethod
+    def _has_views(models):
+        return any(isinstance(m, InferenceView) for m in models)
+
+    @classmethod
+    def views(cls, parent, n):
+        """A group of n inference views of `parent` (parent.inference_view() n times): n input streams over one copy of its
+        weights, stepped with learning=False.  The views' scan reads the shared segment store once per step for up to M of
+        them at a time (M: as many members' column bitmaps as fit 64 KiB of LDS, at most 16)."""
+        if n < 1:
+            raise ValueError("ModelGroup.views: n must be at least 1")
+        return cls([parent.inference_view() for _ in range(int(n))])
+
+    def _learning(self, learning):
+        """learning=None: False for a group with inference views, True for any other (as before); True with views: ValueError."""
+        views = self._has_views(self.models)
+        if learning is None:
+            return not views
+        if learning and views:
+            raise ValueError("a group with inference views steps with learning=False only (its views share their parent's weights)")
+        return bool(learning)
 
     @classmethod
     def create(cls, n, input_dim, column_dim, cell_dim, seeds=None, active_columns=None, device=0, **kw):
@@ -127,6 +153,9 @@ class ModelGroup:
         for i, m in enumerate(self.models):
             if getattr(m, "_streaming", False):
                 raise ValueError(f"member {i} is in the middle of a streamed run() (continuing=True): end the stream first")
+        for m in self.models:
+            if isinstance(m, InferenceView):
+                m._check_parent()
         if self._g is None or any(m.engine is not e for m, e in zip(self.models, self._engines)):
             self._build()
 
@@ -183,9 +212,11 @@ class ModelGroup:
             ptrs.append(bank[1])
         return (C.c_void_p * len(ptrs))(*ptrs)
 
-    def run(self, inputs, steps, learning=True, use_graph=True, record=None, resets=None):
+    def run(self, inputs, steps, learning=None, use_graph=True, record=None, resets=None):
         """`steps` timesteps of every member, member i over the rows of inputs[i] (bool [B, n_inputs, input_dim]), cycled, as
-        its own run(inputs[i], steps) would.  Returns None, or (`record`: as run(record=)) one RunRecord per member."""
+        its own run(inputs[i], steps) would.  Returns None, or (`record`: as run(record=)) one RunRecord per member.
+        learning=None: True, or False in a group with inference views (which refuses True)."""
+        learning = self._learning(learning)
         if resets is not None:
             raise NotImplementedError("sequence resets inside a group run are not available yet (the follow-up: k_tm_reset per "
                                       "member inside the group's launches); reset members with model.reset() between group calls")
@@ -198,7 +229,7 @@ class ModelGroup:
             retire_states(m.engine)
         self._current()
         k = self.models[0].active_columns
-        auto = getattr(self.models[0].engine, "_auto_grow", False)
+        auto = getattr(self.models[0].engine, "_auto_grow", False) and not self._has_views(self.models)
         first = [m.engine.steps for m in self.models]
         parts = [[] for _ in self.models]
         done = 0
@@ -234,9 +265,11 @@ class ModelGroup:
             return None
         return [_join_record(p, fields, f, steps, k, m.column_dim, m.engine.input_dim) for p, f, m in zip(parts, first, self.models)]
 
-    def process(self, X, learning=True, record=True):
+    def process(self, X, learning=None, record=True):
         """One timestep of every member, member i on X[i] (bool [B, input_dim]) -- its own process(X[i]) at once.  Returns a
-        RunRecord whose row i is member i's step (its step_index, counters and anomaly_score), or None with record=False."""
+        RunRecord whose row i is member i's step (its step_index, counters and anomaly_score), or None with record=False.
+        learning=None: True, or False in a group with inference views (which refuses True)."""
+        learning = self._learning(learning)
         X = np.asarray(X, dtype=np.bool_)
         B = len(self.models)
         e0 = self.models[0].engine
@@ -245,7 +278,7 @@ class ModelGroup:
         for m in self.models:
             retire_states(m.engine)
         self._current()
-        if getattr(e0, "_auto_grow", False):
+        if getattr(e0, "_auto_grow", False) and not self._has_views(self.models):
             self._grow(self.models[0].active_columns, False)
         words = (e0.input_dim + 31) // 32
         packed = np.ascontiguousarray(np.stack([pack_bits(x, words) for x in X]), dtype=np.uint32)

@@ -21,6 +21,7 @@ Differences from the reference, all documented in DESIGN.md:
     (networks.py:134,143-144; example.py:7-12 swaps the Temporal Memory) take any object with `process`.
 """
 
+import copy
 import weakref
 
 import numpy as np
@@ -713,6 +714,24 @@ class HierarchicalTemporalMemory:
             return None
         return _join_record(parts, fields, first_step, steps, k, self.column_dim, eng.input_dim)
 
+    def inference_view(self):
+        """An InferenceView of this model: a model that shares this one's weights -- the Spatial Pooler's permanences, the segment
+        store -- in device memory and steps a stream of its own with learning=False (htm_create_view).  It starts as this model
+        would be after reset(): same duty cycles and step index, no Temporal Memory state.  This model may keep learning; its
+        views always step on its current weights.  Many views in a ModelGroup read the store once per step together."""
+        eng = self._engine
+        if eng is None or not self.spatial_pooler._plain:
+            raise ValueError("inference_view() needs both layers on the device (one engine): this model has a layer, a distal "
+                             "projection or plug-in objects that live on the host")
+        if getattr(self.temporal_memory, "cell_dim", 0) > 64:
+            raise ValueError("inference_view(): cell_dim above 64 steps on the host")
+        if eng.shard_world > 1:
+            raise ValueError("inference_view(): views of column-sharded models are not available")
+        if getattr(self, "_streaming", False):
+            raise ValueError("inference_view(): this model is in the middle of a streamed run() (continuing=True): end the stream first")
+        retire_states(eng)
+        return InferenceView(self)
+
     def predicted_input(self):
         """Which input the model expects next: int32[input_dim], the votes of the predicted columns for the inputs they are
         connected to -- for the state the last step left, (pp.permanence[tm_state.cell_prediction.any(axis=1)] >=
@@ -724,6 +743,83 @@ class HierarchicalTemporalMemory:
         if not self.spatial_pooler._plain:
             raise RuntimeError("predicted_input() decodes on the device: not available with plug-in Spatial Pooler objects that live on the host")
         return eng.predicted_input()
+
+
+class InferenceView(HierarchicalTemporalMemory):
+    """A model that shares its parent's weights in device memory and owns only its stream state (HierarchicalTemporalMemory.
+    inference_view(); include/bithtm_hip.h htm_create_view).  process() and run() default to learning=False, and learning=True
+    raises ValueError; reset(), predicted_input(), last_state and the States work as on the parent.  state_dict(), save(),
+    load_state_dict() and grow_pool() raise ValueError: save the parent.  A view is a member of a ModelGroup like any model.
+
+    The parent may keep learning between view calls; a view always steps on the parent's current weights.  If the parent's
+    engine is re-created (grow_pool(), by hand or by its growing default pool), the view raises ValueError: make new views."""
+
+    def __init__(self, parent):
+        eng = Engine.view_of(parent._engine)
+        self.column_dim, self.cell_dim, self.active_columns = parent.column_dim, parent.cell_dim, parent.active_columns
+        sp, tm = copy.copy(parent.spatial_pooler), copy.copy(parent.temporal_memory)
+        # (the view's own copies of the parameter objects, bound to the view's engine: they read the shared weights through it,
+        # and hold no reference to the parent's engine -- which goes when the parent does)
+        sp.proximal_projection, sp.boosting = copy.copy(sp.proximal_projection), copy.copy(sp.boosting)
+        tm.distal_projection = copy.copy(tm.distal_projection)
+        sp._bind(eng, True)
+        tm._bind(eng, True)
+        tm._last_ref, tm._last_cols, tm._host_last = None, None, None
+        tm._was_reset = True
+        self.spatial_pooler, self.temporal_memory = sp, tm
+        self._engine = eng
+        self._parent = weakref.ref(parent)
+        self._parent_engine = weakref.ref(parent._engine)
+
+    def _check_parent(self):
+        parent = self._parent()
+        if parent is not None and parent._engine is not self._parent_engine():
+            raise ValueError("the parent model's engine was re-created (grow_pool() or its pool's growth) since this view was "
+                             "made: this view still holds the old weights; make a new view with parent.inference_view()")
+
+    @staticmethod
+    def _no_learning(learning, what):
+        if learning:
+            raise ValueError(f"{what}: an inference view steps with learning=False only (it shares its parent's weights)")
+
+    def process(self, input, learning=False):
+        self._no_learning(learning, "process()")
+        self._check_parent()
+        return super().process(input, learning=False)
+
+    compute = process
+
+    def run(self, inputs, steps, learning=False, use_graph=True, pipeline=True, continuing=False, record=None, resets=None):
+        self._no_learning(learning, "run()")
+        self._check_parent()
+        return super().run(inputs, steps, learning=False, use_graph=use_graph, pipeline=pipeline, continuing=continuing,
+                           record=record, resets=resets)
+
+    def reset(self):
+        self._check_parent()
+        super().reset()
+
+    def predicted_input(self):
+        self._check_parent()
+        return super().predicted_input()
+
+    def inference_view(self):
+        raise ValueError("inference_view() of a view: make views of the model that owns the weights")
+
+    def state_dict(self):
+        raise ValueError("state_dict() of an inference view: it shares its parent's weights; save the parent instead")
+
+    def save(self, path):
+        raise ValueError("save() of an inference view: it shares its parent's weights; save the parent instead")
+
+    def load_state_dict(self, state):
+        raise ValueError("load_state_dict() on an inference view: load the parent and make new views")
+
+    def load(self, path):
+        raise ValueError("load() on an inference view: load the parent and make new views")
+
+    def grow_pool(self, segment_capacity=None, segment_slots=None):
+        raise ValueError("grow_pool() on an inference view: its pool is its parent's; grow the parent and make new views")
 
 
 def _join_record(parts, fields, first_step, steps, k, column_dim, input_dim=0):

@@ -513,6 +513,40 @@ int htm_group_run(htm_group *g, const uint32_t *const *device_banks, int32_t n_i
                   int32_t use_graph, const htm_run_record *records);
 int htm_group_step(htm_group *g, const uint32_t *packed_inputs, int32_t learning, const htm_run_record *records);
 
+/* Inference views: many input streams stepped over ONE copy of a trained model's weights.
+ *
+ * htm_create_view: a new handle whose device state ALIASES the parent's weights -- the Spatial Pooler's permanences and
+ * connected mask, the segment store (owner cells, synapse counts, presynaptic cells, permanences, segments per cell) -- and
+ * OWNS its stream state: duty cycles, overlaps and select state, cell words, winner list, the last scan's matching segments and
+ * per-cell maxima, the counter block, the record / reset / decoding descriptors.  The view starts as its parent would be right
+ * after htm_reset: same duty cycles, step index, seed, epsilon and configuration; empty Temporal Memory state.  Stepping a view
+ * (learning = 0 only) therefore equals stepping a full copy of the parent (export + import) after htm_reset with learning = 0.
+ * The parent must be unsharded, with SP and TM, not a view itself and not ahead (HTM_RUN_CONTINUE): HTM_ERR_STATE otherwise.
+ *
+ * Lifetime: the weights (and the parent's own stream, if it created one) are reference-counted: freed when the last of the
+ * parent and its views is destroyed, in any order of the htm_destroy calls.
+ *
+ * Ordering: a view enqueues on its parent's stream.  Every stepping call on a view (htm_step, htm_run*, htm_prepare*,
+ * htm_reset, htm_predicted_input, htm_tm_step, htm_tm_scan, group calls with view members) first lets the parent's held-back
+ * launch go, refuses with HTM_ERR_STATE while the parent is ahead (HTM_RUN_CONTINUE), and copies the parent's segment count
+ * into the view's counter block (a device-to-device copy on the shared stream).  A view thus always sees the parent's current
+ * weights; the parent may keep learning between view calls.  A view holds no launch back across calls.
+ *
+ * Refused on a view (HTM_ERR_STATE, nothing enqueued): learning != 0; writes of weight fields (htm_write of SEG_* / SEGCOUNT,
+ * htm_sp_set_permanence, htm_populate, htm_tm_update, htm_sp_phase); state import other than HTM_IMPORT_PREV_STATE; the shard
+ * entry points; a view of a view.
+ *
+ * htm_device_bytes: the device bytes this handle allocated itself (a view does not count the weights it aliases), or
+ * HTM_ERR_ARGUMENT for NULL.
+ *
+ * Groups take view members as any others.  A group call with learning != 0 and a view member is refused.  With the environment
+ * knob BITHTM_SHARED_SCAN=1 (read when the group's first member is created), a group whose members all alias one set of weights
+ * (views of one parent, with or without the parent) and that has a view member scans the store ONCE per step for up to M
+ * members at a time (kgrp_scan_shared: M member bitmaps in LDS, at most 64 KiB; BITHTM_SHARED_SCAN_MEMBERS caps M),
+ * bit-identical to the per-member scan.  It is off by default: it reads fewer bytes but measured slower. */
+int htm_create_view(htm_handle *parent, htm_handle **out);
+int64_t htm_device_bytes(htm_handle *h);
+
 #ifdef __cplusplus
 }
 #endif
