@@ -20,6 +20,7 @@
 #include <stdio.h>
 #include <string.h>
 #include <algorithm>
+#include <climits>
 #include <chrono>
 #include <map>
 #include <mutex>
@@ -49,9 +50,52 @@ struct ncclUniqueIdBytes { char internal[128]; };      // ncclUniqueId (rccl.h: 
 static thread_local std::string g_create_error;
 static int (*g_rccl_destroy)(void *) = nullptr;        // ncclCommDestroy once RCCL is loaded
 
+// The environment's knobs (tuning and test knobs), read when a handle is created (read_knobs; an inference view takes its
+// parent's: htm_create_view).  The knobs of launch sizes read 0 when they are not given (a given one is at least 1), and
+// BITHTM_SEL_LAUNCH_DIGITS -1: size_launches derives those.
+struct Knobs {
+    int graph_steps, eager_below;         // BITHTM_GRAPH_STEPS, BITHTM_EAGER_BELOW
+    bool trace;                           // BITHTM_TRACE given (and BITHTM_TRACE_UNTIL)
+    uint32_t trace_until;
+    int lean, lean2_classify, lean2_order, step_split, fuse_tm, shard_window, step_window, tail_rows, scan_large, scan_large_above, scan_dyn;
+    int defer_tail, shared_scan, shared_members;
+    int lean_overlap, lean_learn, lean_learn_large, lean_scan, lean_scan_large, scan_blocks, sel_launch_digits;
+    int cand_d, cand_pairwise, cls_rows_max, win_offset, cand_zoom, cand_speculate, cand_take_all, poll_delay, cand_others;   // (Dev's)
+};
+
+// Launch sizes of a handle, derived once from its shape, its knobs and the device (size_launches)
+struct Sizes {
+    int G;                                // lanes per SP row
+    int sp_blocks, sel_blocks, c256_blocks, s1024_blocks, scan_blocks, zero_blocks, cus;
+    int lean_learn_blocks, lean_learn_blocks_large, lean_scan_blocks, lean_scan_blocks_large, lean_overlap_blocks, lean2_classify_blocks;
+    int lean_resident_large;              // blocks of the large-pool k_learn_scan_emit that are resident at once
+    bool emit_fits, emit_fits_open;       // the emit grid is resident at once in k_sp_emit / in k_open_emit, as far as this handle's own grids go
+    bool emit_fits_lean;                  // ... and in k_learn_scan_emit
+    int sel_passes_fused, sel_passes_full; // launched select digits with / without the in-kernel finish
+};
+
+// What the launches of a captured graph depend on besides the handle's fixed sizes.  htm_run: the step's parity, the call's
+// modes, its StepPlan and schedule, the scan's form, the span of steps, the bank
+struct RunGraphKey {
+    int p; bool recording, resetting, decoding; int learning; bool sp_done, next_sp, next_front, lean; int spec; bool large, emit_fused, wmode;
+    int span; const void *bank; int n_inputs;
+    auto tie() const { return std::tie(p, recording, resetting, decoding, learning, sp_done, next_sp, next_front, lean, spec, large, emit_fused, wmode, span, bank, n_inputs); }
+    bool operator<(const RunGraphKey &o) const { return tie() < o.tie(); }
+};
+
+// ... htm_shard_run / htm_shard_group_run: per rank the scan blocks known to have segments, the scan's form and the exchange mode;
+// rank 0's bank
+struct ShardGraphKey {
+    int p, learning; bool front_done, front_next; int span, ranks, n_inputs; std::vector<std::tuple<int, bool, bool>> per_rank; const void *bank;
+    auto tie() const { return std::tie(p, learning, front_done, front_next, span, ranks, n_inputs, per_rank, bank); }
+    bool operator<(const ShardGraphKey &o) const { return tie() < o.tie(); }
+};
+
 struct htm_handle {
     htm_config cfg;
     Dev d;
+    Knobs knob;
+    Sizes sz;
     int device;
     hipStream_t stream;
     bool own_stream;
@@ -61,34 +105,19 @@ struct htm_handle {
     int *d_cols_stage;                    // stand-alone TM: active columns
     int rank, world;                      // column sharding
     const uint32_t *shard_bank;           // input of the step between htm_shard_begin and _finish
-    int shard_n_inputs;
+    int shard_n_inputs = 1;
     bool shard_open;
     bool shard_graph_ok;                  // htm_shard_comm_init's preflight: this communicator's all-gather replays correctly from a captured hipGraph
     int shard_front_wmode;                // htm_shard_run: the histogram form of the overlap computed ahead for the coming step
-    // keyed by the exact launch parameters: (parity | learning | front flags | span, ranks, n_inputs, per rank: scan blocks known to have
-    // segments, scan form, exchange mode) and the bank -- (on rank 0's handle for a group in one process)
-    std::map<std::pair<std::vector<int>, const void *>, hipGraphExec_t> shard_graphs;
+    std::map<ShardGraphKey, hipGraphExec_t> shard_graphs;     // (on rank 0's handle for a group in one process)
     void *rccl_comm;                      // ncclComm_t of htm_shard_comm_init (the exchange of htm_shard_step)
     unsigned char *shard_send, *shard_recv;   // ... and its device buffers
-    int G;                                // lanes per SP row
-    int graph_steps;                      // steady-state steps per captured graph (BITHTM_GRAPH_STEPS)
-    int eager_below;                      // calls of fewer steps than this launch eagerly (BITHTM_EAGER_BELOW)
     bool emit_fused, emit_fused_open;     // the emit grid is resident at once in k_sp_emit / in k_open_emit (refreshed per call)
-    bool emit_fits_lean;                  // ... and in k_learn_scan_emit
-    int knob_lean, knob_fuse_tm, knob_shard_window, knob_scan_large, knob_step_window, knob_tail_rows, knob_step_split;
-    int scan_large_above;                 // segments above which the scan takes its streaming (large-pool) form (BITHTM_SCAN_LARGE_ABOVE)
-    int knob_scan_dyn;                    // the large-pool form of the last launch: every block joins the streaming scan when its own role is done (BITHTM_SCAN_DYN)
-    int lean_resident_large;              // blocks of the large-pool k_learn_scan_emit that are resident at once
-    int knob_defer_tail;                  // htm_step holds a step's last launch back for the next call's first (BITHTM_DEFER_TAIL)
-    bool tail_pending;                    // ... and one is held back now: the learning role and the scan of the step of parity tail_p
+    bool tail_pending;                    // htm_step holds back the learning role and the scan of the step of parity tail_p
     int tail_p;
-    bool window_known;                    // a select has run on this handle since it was created / imported into: Counters::sel_win is meaningful      // environment knobs, read when the handle is created
-    bool emit_fits, emit_fits_open;       // ... as far as this handle's own grids go (fixed at creation)
-    int sel_passes_fused, sel_passes_full; // launched select digits with / without the in-kernel finish
+    bool window_known;                    // a select has run on this handle since it was created / imported into: Counters::sel_win is meaningful
     int seg_hint;                         // a lower bound of the segment count (see scan_spec_blocks)
     int *seg_pinned;                      // pinned word the end of each htm_run copies the count into
-    int sp_blocks, sel_blocks, c256_blocks, s1024_blocks, scan_blocks, zero_blocks, lean_learn_blocks, lean_learn_blocks_large, lean_scan_blocks, lean_scan_blocks_large, lean_overlap_blocks, lean2_classify_blocks, lean2_order, cus;
-    bool lean2_classify_set;               // BITHTM_LEAN2_CLASSIFY given: that many classification blocks whatever the pool's size
     const uint32_t *ahead_bank;           // htm_run ended with HTM_RUN_CONTINUE on this bank: the SP has done the next step
     int ahead_n_inputs, ahead_learning;   //   and the front of the one after it
     bool ahead_lean;                      //   ... in the three-launch schedule (else the four-launch one)
@@ -113,8 +142,7 @@ struct htm_handle {
     PinDev *d_pin;
     bool decoding;
     int32_t *d_pin_buf;
-    // graphs keyed by (parity + 2 if recorded + 4 if resetting + 8 if decoding, learning, bank, n_inputs)
-    std::map<std::tuple<int, int, const void *, int>, hipGraphExec_t> graphs;
+    std::map<RunGraphKey, hipGraphExec_t> graphs;
     // state import staging (htm_write of the MATCH_* / SEG_POTENTIAL fields, applied at commit)
     std::vector<int> imp_pot, imp_match_seg;
     // ... on a column-sharded handle also the per-segment arrays (written for ALL segment ids; the commit keeps the rows of
@@ -140,7 +168,6 @@ struct htm_handle {
     long long seen_wgen;
     uint32_t dense_step;                  // (the host word a view's counter block takes cm_dense_step from)
     int64_t own_bytes;                    // device bytes this handle allocated itself (htm_device_bytes)
-    int knob_shared_scan, knob_shared_members;    // BITHTM_SHARED_SCAN (0: off), BITHTM_SHARED_SCAN_MEMBERS (cap of M; 0: none)
 };
 
 // The weights of a parent and its inference views (htm_create_view): freed, with the parent's own stream if it created one, when
@@ -171,9 +198,9 @@ static void refresh_exchange_mode(htm_handle *h) {
         for (const htm_handle *o : g_registry)
             if (o != h && o->device == h->device && o->stream != h->stream) solo = false;
     }
-    h->emit_fused = h->emit_fits && solo;
-    h->emit_fused_open = h->emit_fits_open && solo;
-    h->d.sel_passes = h->emit_fused ? h->sel_passes_fused : h->sel_passes_full;
+    h->emit_fused = h->sz.emit_fits && solo;
+    h->emit_fused_open = h->sz.emit_fits_open && solo;
+    h->d.sel_passes = h->emit_fused ? h->sz.sel_passes_fused : h->sz.sel_passes_full;
 }
 
 #define HIPCHK(h, call)                                                                          \
@@ -195,6 +222,50 @@ static bool sp_is_ahead(const htm_handle *h) { return h->ahead_bank != nullptr; 
             return HTM_ERR_STATE;                                                                                 \
         }                                                                                                         \
     } while (0)
+
+// the status of the launches just enqueued
+static int launch_status(std::string &err) {
+    const hipError_t e = hipGetLastError();
+    if (e == hipSuccess) return HTM_OK;
+    err = std::string("kernel launch: ") + hipGetErrorString(e);
+    return HTM_ERR_HIP;
+}
+
+// the segment count the end of the last run left in the pinned word (read without a wait: a lower bound) ...
+static void refresh_seg_hint(htm_handle *h) {
+    if (h->seg_pinned) h->seg_hint = std::max(h->seg_hint, (int)*(volatile int *)h->seg_pinned);
+}
+
+// ... and the copy that leaves it there, queued at the end of a run: `count` is the counter of the rows the scan covers
+// (&Counters::S, or a shard's &Counters::L)
+static hipError_t hand_back_segments(htm_handle *h, const int32_t *count, hipStream_t stream) {
+    return h->seg_pinned ? hipMemcpyAsync(h->seg_pinned, count, sizeof(int), hipMemcpyDeviceToHost, stream) : hipSuccess;
+}
+
+// The graph `key` names in `graphs`: found, or what `enqueue` launches captured on `stream` (enqueue returns 0, or an error
+// status with err set), instantiated and kept.  nullptr: the capture or the instantiation failed (err says which).  The
+// captured hipGraph_t is destroyed either way.
+template <typename Key, typename Enqueue>
+static hipGraphExec_t cached_graph(std::map<Key, hipGraphExec_t> &graphs, const Key &key, hipStream_t stream, std::string &err, Enqueue enqueue) {
+    auto it = graphs.find(key);
+    if (it != graphs.end()) return it->second;
+    hipError_t e = hipStreamBeginCapture(stream, hipStreamCaptureModeThreadLocal);
+    if (e != hipSuccess) { err = std::string("hipStreamBeginCapture: ") + hipGetErrorString(e); return nullptr; }
+    const int rc = enqueue();
+    hipGraph_t graph = nullptr;
+    hipGraphExec_t exec = nullptr;
+    e = hipStreamEndCapture(stream, &graph);
+    if (rc) {
+    } else if (e != hipSuccess || !graph) {
+        err = std::string("hipStreamEndCapture: ") + hipGetErrorString(e);
+    } else if ((e = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0)) != hipSuccess) {
+        err = std::string("hipGraphInstantiate: ") + hipGetErrorString(e);
+        exec = nullptr;
+    }
+    if (graph) hipGraphDestroy(graph);
+    if (exec) graphs.emplace(key, exec);
+    return exec;
+}
 
 template <typename T>
 static int dalloc(htm_handle *h, T **p, size_t count) {
@@ -264,27 +335,26 @@ static size_t lean_scan_lds(const Dev &d) { return lean_tab(d) ? scan_lds_tab(d)
 static const int kClassifyBlocks = 384;           // x 256 segments per pass of the learn / punish classification
 static const int kLearnBlocks = 256;               // x RB/64 waves: one wave per learning / punished segment
 
+// Each family of kernel instantiations is a table (kt_*), by the learning role's width (learn_epl: 1, 2, 4, 8 -> epl_slot) or by
+// the scan's form (scan_slot: large pool with / without the column bitmap in LDS, small pool with / without it).  A table stands
+// before the first launch from it: the order in which kernels are first named is the order of their code in the code object.
+static int epl_slot(const Dev &d) { const int e = learn_epl(d); return e == 1 ? 0 : e == 2 ? 1 : e == 4 ? 2 : 3; }
+static int scan_slot(bool large, bool use_lds) { return (large ? 0 : 2) + (use_lds ? 0 : 1); }
+static decltype(&k_tm_learn<1>) const kt_tm_learn[4] = {k_tm_learn<1>, k_tm_learn<2>, k_tm_learn<4>, k_tm_learn<8>};
+
 static void launch_learn(htm_handle *h, int p) {
-    Dev &d = h->d;
-    const int epl = learn_epl(d);
-    const size_t lds = learn_lds(epl);
-    switch (epl) {
-        case 1: LAUNCH_ON(h, h->stream, lds, "tm_learn", k_tm_learn<1>, kLearnBlocks, RB, d, p); break;
-        case 2: LAUNCH_ON(h, h->stream, lds, "tm_learn", k_tm_learn<2>, kLearnBlocks, RB, d, p); break;
-        case 4: LAUNCH_ON(h, h->stream, lds, "tm_learn", k_tm_learn<4>, kLearnBlocks, RB, d, p); break;
-        default: LAUNCH_ON(h, h->stream, lds, "tm_learn", k_tm_learn<8>, kLearnBlocks, RB, d, p); break;
-    }
+    LAUNCH_ON(h, h->stream, learn_lds(learn_epl(h->d)), "tm_learn", kt_tm_learn[epl_slot(h->d)], kLearnBlocks, RB, h->d, p);
 }
 
 // scan blocks that certainly have segments: the count only grows, and the host sees it now and then
 // (htm_get_info, state import, and a copy queued at the end of every htm_run)
 // (rounded down to a multiple of 64 blocks: the value is baked into captured graphs)
-static int scan_spec_blocks(const htm_handle *h) { return std::min(h->seg_hint / SCAN_SEGS, h->scan_blocks) & ~63; }
+static int scan_spec_blocks(const htm_handle *h) { return std::min(h->seg_hint / SCAN_SEGS, h->sz.scan_blocks) & ~63; }
 
 // more segments than three rounds of resident blocks: the scan is bandwidth-bound (see k_tm_scan)
 static bool scan_pool_is_large(const htm_handle *h) {
-    if (h->knob_scan_large >= 0) return h->knob_scan_large != 0;      // (BITHTM_SCAN_LARGE: tuning knob)
-    return h->seg_hint > h->scan_large_above;
+    if (h->knob.scan_large >= 0) return h->knob.scan_large != 0;      // (BITHTM_SCAN_LARGE: tuning knob)
+    return h->seg_hint > h->knob.scan_large_above;
 }
 
 static void launch_scan(htm_handle *h, int p, int use_lds) {
@@ -292,23 +362,19 @@ static void launch_scan(htm_handle *h, int p, int use_lds) {
     const int spec = scan_spec_blocks(h);
     if (scan_pool_is_large(h) && use_lds && scan_lds(d, 1) > 16 * 1024) {
         // a big column bitmap (32 KB at 262 144 columns): one copy per 1024-thread block, two blocks per CU
-        const int blocks = std::max(1, std::min((d.Lcap + 255) / 256, 2 * h->cus));
+        const int blocks = std::max(1, std::min((d.Lcap + 255) / 256, 2 * h->sz.cus));
         LAUNCH_ON(h, h->stream, scan_lds(d, 1), "tm_scan_wide", (k_tm_scan_wide<true>), blocks, 1024, d, p, 0);
         return;
     }
-    if (scan_pool_is_large(h)) {
-        if (use_lds) LAUNCH_ON(h, h->stream, scan_lds(d, 1), "tm_scan_large", (k_tm_scan<true, 1>), h->scan_blocks, 256, d, p, spec);
-        else LAUNCH_ON(h, h->stream, scan_lds(d, 0), "tm_scan_large", (k_tm_scan<false, 1>), h->scan_blocks, 256, d, p, spec);
-    } else {
-        if (use_lds) LAUNCH_ON(h, h->stream, scan_lds(d, 1), "tm_scan", (k_tm_scan<true, 6>), h->scan_blocks, 256, d, p, spec);
-        else LAUNCH_ON(h, h->stream, scan_lds(d, 0), "tm_scan", (k_tm_scan<false, 6>), h->scan_blocks, 256, d, p, spec);
-    }
+    static decltype(&k_tm_scan<true, 1>) const kt_tm_scan[4] = {k_tm_scan<true, 1>, k_tm_scan<false, 1>, k_tm_scan<true, 6>, k_tm_scan<false, 6>};
+    const bool large = scan_pool_is_large(h);
+    LAUNCH_ON(h, h->stream, scan_lds(d, use_lds), large ? "tm_scan_large" : "tm_scan", kt_tm_scan[scan_slot(large, use_lds)], h->sz.scan_blocks, 256, d, p, spec);
 }
 
 // the windowed one-pass select (win_bin) outside the three-launch schedule too: the histogram is finished inside the emit
 // grid, so only where that grid's blocks may wait for each other (BITHTM_STEP_WINDOW=0: two launched digits, as before)
 // (and only once a select has left a window behind: the first step of a handle, or after a state import, takes the digits)
-static int step_wmode(const htm_handle *h) { return h->emit_fused && h->knob_step_window && h->world == 1 && h->window_known ? 1 : 0; }
+static int step_wmode(const htm_handle *h) { return h->emit_fused && h->knob.step_window && h->world == 1 && h->window_known ? 1 : 0; }
 
 // Front of SpatialPooler.process for the step with parity sp: overlap + boost + histogram (the windowed one, or the top
 // key digit and then the remaining select digits).  host_input: the packed input of a host-fed step (it rides in the
@@ -319,12 +385,12 @@ static void enqueue_sp_front(htm_handle *h, const uint32_t *bank, int n_inputs, 
         PackedInputArg in;
         memset(&in, 0, sizeof(in));
         memcpy(in.w, host_input, (size_t)((d.I + 31) / 32) * 4);
-        LAUNCH(h, "sp_overlap", k_sp_overlap_arg, h->sp_blocks, RB, d, in, h->G, p, wmode);
+        LAUNCH(h, "sp_overlap", k_sp_overlap_arg, h->sz.sp_blocks, RB, d, in, h->sz.G, p, wmode);
     } else {
-        LAUNCH(h, "sp_overlap", k_sp_overlap, h->sp_blocks, RB, d, bank, n_inputs, h->G, p, p, 0, wmode);
+        LAUNCH(h, "sp_overlap", k_sp_overlap, h->sz.sp_blocks, RB, d, bank, n_inputs, h->sz.G, p, p, 0, wmode);
     }
     if (!wmode)
-        for (int pass = 1; pass < d.sel_passes; ++pass) LAUNCH(h, "sp_select", k_sel_pass, h->sel_blocks, RB, d, pass, p);
+        for (int pass = 1; pass < d.sel_passes; ++pass) LAUNCH(h, "sp_select", k_sel_pass, h->sz.sel_blocks, RB, d, pass, p);
 }
 
 // Rest of SpatialPooler.process: count + emit.  mode = EMIT_ALL: all of it, with the TM's per-column
@@ -333,8 +399,8 @@ static void enqueue_sp_front(htm_handle *h, const uint32_t *bank, int n_inputs, 
 static void enqueue_sp_back(htm_handle *h, const uint32_t *bank, int n_inputs, int p, int want_winner, int mode, bool sp_learn, int wmode = 0) {
     Dev &d = h->d;
     const int fused = h->emit_fused;               // all blocks co-resident: count inside emit
-    if (!fused) LAUNCH(h, "sp_count", k_sp_count, h->c256_blocks, 256, d, p);
-    LAUNCH(h, "sp_emit", k_sp_emit, h->c256_blocks, 256, d, p, want_winner, fused, mode, fused ? wmode : 0, h->c256_blocks);
+    if (!fused) LAUNCH(h, "sp_count", k_sp_count, h->sz.c256_blocks, 256, d, p);
+    LAUNCH(h, "sp_emit", k_sp_emit, h->sz.c256_blocks, 256, d, p, want_winner, fused, mode, fused ? wmode : 0, h->sz.c256_blocks);
     h->window_known = true;                         // (every select leaves the next step's window behind)
     // (a forked graph branch for this independent update was measured at +17..29 us per step on
     // this runtime, against 2.3 us for one more kernel in the chain: tools/launch_overhead.hip)
@@ -348,21 +414,21 @@ static void enqueue_sp_back(htm_handle *h, const uint32_t *bank, int n_inputs, i
 // the learning role and the scan: one launch (the learning waves scan their own rows), unless the pool is large (the
 // streaming scan kernels) or somebody is timing the roles one by one (unsharded handles under htm_profile)
 static bool tm_tail_fused(const htm_handle *h) {
-    return h->knob_fuse_tm && !(h->profile && h->world == 1) && !scan_pool_is_large(h) && scan_lds(h->d, 1) <= 64 * 1024;
+    return h->knob.fuse_tm && !(h->profile && h->world == 1) && !scan_pool_is_large(h) && scan_lds(h->d, 1) <= 64 * 1024;
 }
+
+// k_learn_scan_emit by the form of its scan (lse_kernel): the small-pool scan without its LDS tables (what the fused tail launches) ...
+enum { LSE_TAB, LSE_PLAIN, LSE_LARGE };
+static decltype(&k_learn_scan_emit<1, 6>) const kt_lse_plain[4] = {k_learn_scan_emit<1, 6, false>, k_learn_scan_emit<2, 6, false>,
+                                                                   k_learn_scan_emit<4, 6, false>, k_learn_scan_emit<8, 6, false>};
 
 // the learning role and the scan of the step of parity p, nothing beside them
 static void enqueue_tm_tail(htm_handle *h, int p) {
     Dev &d = h->d;
     if (tm_tail_fused(h)) {
-        const int epl = learn_epl(d), n_learn = h->lean_learn_blocks, n_scan = h->lean_scan_blocks, spec = scan_spec_blocks(h);
+        const int epl = learn_epl(d), n_learn = h->sz.lean_learn_blocks, n_scan = h->sz.lean_scan_blocks, spec = scan_spec_blocks(h);
         const size_t lds = std::max(learn_lds(epl, 256), scan_lds(d, 1));
-        switch (epl) {
-            case 1: LAUNCH_ON(h, h->stream, lds, "tm_learn+tm_scan", (k_learn_scan_emit<1, 6>), n_learn + n_scan, 256, d, p, 0, n_learn, n_scan, spec); break;
-            case 2: LAUNCH_ON(h, h->stream, lds, "tm_learn+tm_scan", (k_learn_scan_emit<2, 6>), n_learn + n_scan, 256, d, p, 0, n_learn, n_scan, spec); break;
-            case 4: LAUNCH_ON(h, h->stream, lds, "tm_learn+tm_scan", (k_learn_scan_emit<4, 6>), n_learn + n_scan, 256, d, p, 0, n_learn, n_scan, spec); break;
-            default: LAUNCH_ON(h, h->stream, lds, "tm_learn+tm_scan", (k_learn_scan_emit<8, 6>), n_learn + n_scan, 256, d, p, 0, n_learn, n_scan, spec); break;
-        }
+        LAUNCH_ON(h, h->stream, lds, "tm_learn+tm_scan", kt_lse_plain[epl_slot(d)], n_learn + n_scan, 256, d, p, 0, n_learn, n_scan, spec);
     } else {
         launch_learn(h, p);
         launch_scan(h, p, scan_lds(d, 1) <= 64 * 1024);
@@ -378,6 +444,8 @@ static void flush_tail(htm_handle *h) {
     enqueue_tm_tail(h, h->tail_p);
 }
 
+static decltype(&k_learn_scan_tail<1>) const kt_learn_scan_tail[4] = {k_learn_scan_tail<1>, k_learn_scan_tail<2>, k_learn_scan_tail<4>, k_learn_scan_tail<8>};
+
 // defer_tail: the last launch is held back (htm_step: see flush_tail); the permanence rows then ride in the middle launch
 static void enqueue_tm(htm_handle *h, int n_active, int learning, int want_winner, int p,
                        const uint32_t *bank, int n_inputs, bool sp_rows, int front_wmode = -1, bool defer_tail = false) {
@@ -387,25 +455,23 @@ static void enqueue_tm(htm_handle *h, int n_active, int learning, int want_winne
     int n_sp_rows = (sp_rows && learning && h->cfg.enable_sp) ? d.k : 0;
     // an unsharded step's permanence rows ride in that launch (the middle launch is left with the Temporal Memory's chain);
     // a shard's stay in the middle launch: the coming step's overlap, which reads them, may ride in the last one
-    const int n_tail_rows = (fuse && h->world == 1 && h->knob_tail_rows && !defer_tail) ? n_sp_rows : 0;
+    const int n_tail_rows = (fuse && h->world == 1 && h->knob.tail_rows && !defer_tail) ? n_sp_rows : 0;
     if (n_tail_rows) n_sp_rows = 0;
     const int n_duty = h->world > 1 ? (d.c1 - d.c0 + 255) / 256 : 0;      // (unsharded: the emit role updates the duty cycle)
-    LAUNCH(h, "tm_mid", k_mid_rows, 1 + n_cls + n_sp_rows + n_duty + h->zero_blocks, 256, d, p, n_active, want_winner, learning, n_cls, bank, n_inputs, n_sp_rows, 0, n_duty);
+    LAUNCH(h, "tm_mid", k_mid_rows, 1 + n_cls + n_sp_rows + n_duty + h->sz.zero_blocks, 256, d, p, n_active, want_winner, learning, n_cls, bank, n_inputs, n_sp_rows, 0, n_duty);
     if (defer_tail) { h->tail_pending = true; h->tail_p = p; return; }
     if (fuse && (front_wmode >= 0 || n_tail_rows)) {
-        const int epl = learn_epl(d), n_learn = h->lean_learn_blocks, n_scan = h->lean_scan_blocks, spec = scan_spec_blocks(h);
+        const int epl = learn_epl(d), n_learn = h->sz.lean_learn_blocks, n_scan = h->sz.lean_scan_blocks, spec = scan_spec_blocks(h);
         const size_t lds = std::max(std::max(learn_lds(epl, 256), scan_lds(d, 1)), (size_t)SEL_BINS * 4);
-        const int grid = n_learn + n_scan + (n_tail_rows ? n_tail_rows : h->lean_overlap_blocks);
+        const int grid = n_learn + n_scan + (n_tail_rows ? n_tail_rows : h->sz.lean_overlap_blocks);
         const char *name = n_tail_rows ? "tm_learn+tm_scan+sp_learn" : "tm_learn+tm_scan+shard_overlap";
-#define LAUNCH_LST(E_) LAUNCH_ON(h, h->stream, lds, name, (k_learn_scan_tail<E_>), grid, 256, d, p, n_learn, n_scan, spec, bank, n_inputs, h->G, front_wmode, n_tail_rows)
-        switch (epl) { case 1: LAUNCH_LST(1); break; case 2: LAUNCH_LST(2); break; case 4: LAUNCH_LST(4); break; default: LAUNCH_LST(8); break; }
-#undef LAUNCH_LST
+        LAUNCH_ON(h, h->stream, lds, name, kt_learn_scan_tail[epl_slot(d)], grid, 256, d, p, n_learn, n_scan, spec, bank, n_inputs, h->sz.G, front_wmode, n_tail_rows);
         return;
     }
     enqueue_tm_tail(h, p);
     // (a large pool streams through kernels of its own: the front as a launch behind them)
     if (front_wmode >= 0)
-        LAUNCH(h, "shard_overlap", k_shard_overlap, h->sp_blocks, RB, d, bank, n_inputs, h->G, p, front_wmode, 1);
+        LAUNCH(h, "shard_overlap", k_shard_overlap, h->sz.sp_blocks, RB, d, bank, n_inputs, h->sz.G, p, front_wmode, 1);
 }
 
 // How a step is launched inside htm_run.
@@ -427,8 +493,21 @@ static bool can_pipeline(const htm_handle *h) {
 // the three-launch schedule (htm_pipeline.h): the scan's LDS bitmap, one select histogram, the learning role and the
 // scan in one launch.  BITHTM_LEAN=0: the four-launch schedule below.
 static bool can_lean(const htm_handle *h) {
-    return h->knob_lean && can_pipeline(h) && scan_lds(h->d, 1) <= 64 * 1024 && h->emit_fits_lean;
+    return h->knob.lean && can_pipeline(h) && scan_lds(h->d, 1) <= 64 * 1024 && h->sz.emit_fits_lean;
 }
+
+// ... the streaming large-pool scan (which reads the cell words from memory: with the LDS tables it measured 3 % slower -- the
+// LDS pipe is one of the things that bound it), and the small-pool scan with its LDS tables (lean_tab)
+static decltype(&k_learn_scan_emit<1, 6>) const kt_lse_large[4] = {k_learn_scan_emit<1, 4, false>, k_learn_scan_emit<2, 4, false>,
+                                                                   k_learn_scan_emit<4, 4, false>, k_learn_scan_emit<8, 4, false>};
+static decltype(&k_learn_scan_emit<1, 6>) const kt_lse_tab[4] = {k_learn_scan_emit<1, 6, true>, k_learn_scan_emit<2, 6, true>,
+                                                                 k_learn_scan_emit<4, 6, true>, k_learn_scan_emit<8, 6, true>};
+static decltype(&k_learn_scan_emit<1, 6>) lse_kernel(const Dev &d, int form) {
+    return (form == LSE_TAB ? kt_lse_tab : form == LSE_LARGE ? kt_lse_large : kt_lse_plain)[epl_slot(d)];
+}
+
+// the form of k_learn_scan_emit this handle launches now (its occupancy is asked for at creation: size_launches)
+static int lse_form(const htm_handle *h) { return scan_pool_is_large(h) ? LSE_LARGE : lean_tab(h->d) ? LSE_TAB : LSE_PLAIN; }
 
 // the last launch of a step in the two- and three-launch schedules: learn(p) + scan(p) beside the select finish + winner list of the
 // step of the other parity (n_emit blocks of it, or none)
@@ -441,26 +520,25 @@ static void launch_learn_scan_emit(htm_handle *h, int p, int n_emit) {
     // per work item (a large learned pool has ~2 800 a step), so that no block joins late because its waves had second items.
     // BITHTM_SCAN_DYN=0: scan blocks with fixed shares -- more of them than are resident at once (as the select finish's and the
     // learning role's blocks leave, the dispatcher fills their slots; the 768 of the small-pool form left the launch 13 % longer).
-    const bool large = scan_pool_is_large(h), dyn = large && h->knob_scan_dyn > 0;
-    const int n_learn = dyn ? h->lean_learn_blocks_large : h->lean_learn_blocks;
-    int n_scan = large ? h->lean_scan_blocks_large : h->lean_scan_blocks;
-    if (dyn) n_scan = std::max(64, h->lean_resident_large - n_emit - n_learn);
+    const bool large = scan_pool_is_large(h), dyn = large && h->knob.scan_dyn > 0;
+    const int n_learn = dyn ? h->sz.lean_learn_blocks_large : h->sz.lean_learn_blocks;
+    int n_scan = large ? h->sz.lean_scan_blocks_large : h->sz.lean_scan_blocks;
+    if (dyn) n_scan = std::max(64, h->sz.lean_resident_large - n_emit - n_learn);
     const int grid = n_emit + n_learn + n_scan;
     if (large && !dyn) n_scan = -n_scan;
     const int spec = dyn ? 0 : scan_spec_blocks(h);
     // (the launch's name says which form of the scan it holds: htm_profile_read is how tests and bench.py tell)
-    const char *lse_name = scan_pool_is_large(h) ? "tm_learn+tm_scan_large+sp_emit" : "tm_learn+tm_scan+sp_emit";
-#define LAUNCH_LSE(EPL_, MINW_, TAB_) LAUNCH_ON(h, h->stream, lds, lse_name, (k_learn_scan_emit<EPL_, MINW_, TAB_>), grid, 256, d, p, n_emit, n_learn, n_scan, spec)
-    if (scan_pool_is_large(h)) {
-        // (the streaming form reads the cell words from memory: with the LDS tables of the small-pool form it measured 3 % slower --
-        // the LDS pipe is one of the things that bound it)
-        switch (epl) { case 1: LAUNCH_LSE(1, 4, false); break; case 2: LAUNCH_LSE(2, 4, false); break; case 4: LAUNCH_LSE(4, 4, false); break; default: LAUNCH_LSE(8, 4, false); break; }
-    } else if (lean_tab(d)) {
-        switch (epl) { case 1: LAUNCH_LSE(1, 6, true); break; case 2: LAUNCH_LSE(2, 6, true); break; case 4: LAUNCH_LSE(4, 6, true); break; default: LAUNCH_LSE(8, 6, true); break; }
-    } else {
-        switch (epl) { case 1: LAUNCH_LSE(1, 6, false); break; case 2: LAUNCH_LSE(2, 6, false); break; case 4: LAUNCH_LSE(4, 6, false); break; default: LAUNCH_LSE(8, 6, false); break; }
-    }
-#undef LAUNCH_LSE
+    const char *lse_name = large ? "tm_learn+tm_scan_large+sp_emit" : "tm_learn+tm_scan+sp_emit";
+    LAUNCH_ON(h, h->stream, lds, lse_name, lse_kernel(d, lse_form(h)), grid, 256, d, p, n_emit, n_learn, n_scan, spec);
+}
+
+// classification blocks of k_act_mid_rows (the two-launch schedule's first launch)
+// (a large pool has a classification block read ~250 match words and classify tens of them: more blocks there, though they
+// are not all resident from the start -- 350-pattern pool of the bench, 1.6 M segments: 32 blocks 11.7 k timesteps/s, 128: 13.3, 256: 13.3,
+// 384: 13.1; three launches: 12.8)
+static int lean2_classify_blocks(const htm_handle *h, int learning) {
+    if (!learning) return 0;
+    return scan_pool_is_large(h) && !h->knob.lean2_classify ? std::max(h->sz.lean2_classify_blocks, 192) : h->sz.lean2_classify_blocks;
 }
 
 // sp_done: the winner list of this step exists (the previous step's last launch, or the cold start).  next_sp: select
@@ -468,56 +546,40 @@ static void launch_learn_scan_emit(htm_handle *h, int p, int n_emit) {
 static void enqueue_lean(htm_handle *h, int p, int learning, const uint32_t *bank, int n_inputs, StepPlan plan) {
     Dev &d = h->d;
     const int n_act = (d.k * d.KP + 255) / 256, n_rows = learning ? d.k : 0;
-    const int n_cls = learning ? kClassifyBlocks : 0, n_ov = plan.next_sp ? h->lean_overlap_blocks : 0;
-    if (h->knob_lean == 2) {                        // the two-launch schedule: both of these in one (htm_pipeline.h)
-        // (a large pool has a classification block read ~250 match words and classify tens of them: more blocks there, though they
-        // are not all resident from the start -- 350-pattern pool of the bench, 1.6 M segments: 32 blocks 11.7 k timesteps/s, 128: 13.3, 256: 13.3,
-        // 384: 13.1; three launches: 12.8)
-        const int n_cls2 = !learning ? 0 : (scan_pool_is_large(h) && !h->lean2_classify_set) ? std::max(h->lean2_classify_blocks, 192) : h->lean2_classify_blocks;
-        const int n_duty = n_ov ? 0 : h->c256_blocks, n_clear = d.WPC * h->c256_blocks;
+    const int n_cls = learning ? kClassifyBlocks : 0, n_ov = plan.next_sp ? h->sz.lean_overlap_blocks : 0;
+    if (h->knob.lean == 2) {                        // the two-launch schedule: both of these in one (htm_pipeline.h)
+        const int n_cls2 = lean2_classify_blocks(h, learning);
+        const int n_duty = n_ov ? 0 : h->sz.c256_blocks, n_clear = d.WPC * h->sz.c256_blocks;
         LAUNCH_ON(h, h->stream, (size_t)SEL_BINS * 4, "tm_activate+tm_mid+sp_learn+sp_overlap", k_act_mid_rows,
-                  n_act + 1 + n_cls2 + n_rows + n_ov + n_duty + n_clear + h->zero_blocks, 256, d, p, d.k, n_act, learning, n_cls2, bank, n_inputs, n_rows, h->G, n_ov,
-                  n_duty, n_clear, h->lean2_order);
+                  n_act + 1 + n_cls2 + n_rows + n_ov + n_duty + n_clear + h->sz.zero_blocks, 256, d, p, d.k, n_act, learning, n_cls2, bank, n_inputs, n_rows, h->sz.G, n_ov,
+                  n_duty, n_clear, h->knob.lean2_order);
     } else {
-        LAUNCH(h, "tm_activate+sp_learn", k_act_rows, n_act + n_rows + (1 + d.WPC) * h->c256_blocks, 256, d, p, d.k, n_act, bank, n_inputs, n_rows, h->c256_blocks);
-        LAUNCH_ON(h, h->stream, (size_t)SEL_BINS * 4, "tm_mid+sp_overlap", k_mid_overlap, 1 + n_cls + n_ov + h->zero_blocks, 256, d, p, d.k, 1, learning, n_cls,
-                  bank, n_inputs, h->G, n_ov);
+        LAUNCH(h, "tm_activate+sp_learn", k_act_rows, n_act + n_rows + (1 + d.WPC) * h->sz.c256_blocks, 256, d, p, d.k, n_act, bank, n_inputs, n_rows, h->sz.c256_blocks);
+        LAUNCH_ON(h, h->stream, (size_t)SEL_BINS * 4, "tm_mid+sp_overlap", k_mid_overlap, 1 + n_cls + n_ov + h->sz.zero_blocks, 256, d, p, d.k, 1, learning, n_cls,
+                  bank, n_inputs, h->sz.G, n_ov);
     }
-    launch_learn_scan_emit(h, p, plan.next_sp ? h->c256_blocks : 0);
+    launch_learn_scan_emit(h, p, plan.next_sp ? h->sz.c256_blocks : 0);
 }
+
+static decltype(&k_learn_overlap<1>) const kt_learn_overlap[4] = {k_learn_overlap<1>, k_learn_overlap<2>, k_learn_overlap<4>, k_learn_overlap<8>};
+static decltype(&k_scan_sel<true, 1>) const kt_scan_sel[4] = {k_scan_sel<true, 1>, k_scan_sel<false, 1>, k_scan_sel<true, 6>, k_scan_sel<false, 6>};
 
 // the four launches of a pipelined step (see the kernels): step p's Temporal Memory beside SP work of
 // the following steps
 static void enqueue_pipelined(htm_handle *h, int p, int learning, const uint32_t *bank, int n_inputs, StepPlan plan) {
     Dev &d = h->d;
     const int n_cls = learning ? kClassifyBlocks : 0;
-    const int n_emit = plan.next_sp ? h->c256_blocks : 0;
+    const int n_emit = plan.next_sp ? h->sz.c256_blocks : 0;
     LAUNCH_ON(h, h->stream, sizeof(EmitShared), "tm_activate+sp_emit", k_open_emit, n_emit + (d.k * d.KP + 255) / 256, 256, d, p, n_emit, d.k);
-    const int n_rows = (plan.next_sp && learning) ? d.k : 0, n_duty = plan.next_sp ? h->c256_blocks : 0;
-    LAUNCH(h, "tm_mid+sp_learn", k_mid_rows, 1 + n_cls + n_rows + n_duty + h->zero_blocks, 256, d, p, d.k, 1, learning, n_cls, bank, n_inputs, n_rows, 1, n_duty);
-    {
-        const int epl = learn_epl(d);
-        const size_t lds = std::max(learn_lds(epl), (size_t)SEL_BINS * 4);
-        const int grid = kLearnBlocks + (plan.next_front ? h->sp_blocks : 0);
-        switch (epl) {       // the front is that of step + 2: same parity as this step
-            case 1: LAUNCH_ON(h, h->stream, lds, "tm_learn+sp_overlap", k_learn_overlap<1>, grid, RB, d, p, kLearnBlocks, bank, n_inputs, h->G, p, 2); break;
-            case 2: LAUNCH_ON(h, h->stream, lds, "tm_learn+sp_overlap", k_learn_overlap<2>, grid, RB, d, p, kLearnBlocks, bank, n_inputs, h->G, p, 2); break;
-            case 4: LAUNCH_ON(h, h->stream, lds, "tm_learn+sp_overlap", k_learn_overlap<4>, grid, RB, d, p, kLearnBlocks, bank, n_inputs, h->G, p, 2); break;
-            default: LAUNCH_ON(h, h->stream, lds, "tm_learn+sp_overlap", k_learn_overlap<8>, grid, RB, d, p, kLearnBlocks, bank, n_inputs, h->G, p, 2); break;
-        }
-    }
-    const int use_lds = scan_lds(d, 1) <= 64 * 1024;
-    const int n_sel = plan.next_front ? 64 : 0, n_clear = plan.next_sp ? h->c256_blocks : 0;
-    const size_t lds = std::max(scan_lds(d, use_lds), sizeof(SelShared));
-    const int grid = h->scan_blocks + n_sel + n_clear;
-    const int spec = scan_spec_blocks(h);
-    if (scan_pool_is_large(h)) {
-        if (use_lds) LAUNCH_ON(h, h->stream, lds, "tm_scan_large+sp_select", (k_scan_sel<true, 1>), grid, 256, d, p, n_sel, n_clear, p, spec);
-        else LAUNCH_ON(h, h->stream, lds, "tm_scan_large+sp_select", (k_scan_sel<false, 1>), grid, 256, d, p, n_sel, n_clear, p, spec);
-    } else {
-        if (use_lds) LAUNCH_ON(h, h->stream, lds, "tm_scan+sp_select", (k_scan_sel<true, 6>), grid, 256, d, p, n_sel, n_clear, p, spec);
-        else LAUNCH_ON(h, h->stream, lds, "tm_scan+sp_select", (k_scan_sel<false, 6>), grid, 256, d, p, n_sel, n_clear, p, spec);
-    }
+    const int n_rows = (plan.next_sp && learning) ? d.k : 0, n_duty = plan.next_sp ? h->sz.c256_blocks : 0;
+    LAUNCH(h, "tm_mid+sp_learn", k_mid_rows, 1 + n_cls + n_rows + n_duty + h->sz.zero_blocks, 256, d, p, d.k, 1, learning, n_cls, bank, n_inputs, n_rows, 1, n_duty);
+    // (the front is that of step + 2: same parity as this step)
+    LAUNCH_ON(h, h->stream, std::max(learn_lds(learn_epl(d)), (size_t)SEL_BINS * 4), "tm_learn+sp_overlap", kt_learn_overlap[epl_slot(d)],
+              kLearnBlocks + (plan.next_front ? h->sz.sp_blocks : 0), RB, d, p, kLearnBlocks, bank, n_inputs, h->sz.G, p, 2);
+    const bool use_lds = scan_lds(d, 1) <= 64 * 1024, large = scan_pool_is_large(h);
+    const int n_sel = plan.next_front ? 64 : 0, n_clear = plan.next_sp ? h->sz.c256_blocks : 0;
+    LAUNCH_ON(h, h->stream, std::max(scan_lds(d, use_lds), sizeof(SelShared)), large ? "tm_scan_large+sp_select" : "tm_scan+sp_select",
+              kt_scan_sel[scan_slot(large, use_lds)], h->sz.scan_blocks + n_sel + n_clear, 256, d, p, n_sel, n_clear, p, scan_spec_blocks(h));
 }
 
 // work of a step that is not captured in its graph: the first step of a pipelined run has no SP work
@@ -534,8 +596,8 @@ static void enqueue_cold_start(htm_handle *h, const uint32_t *bank, int n_inputs
     }
     enqueue_sp_front(h, bank, n_inputs, p, wmode);
     enqueue_sp_back(h, bank, n_inputs, p, 1, EMIT_DUTY | EMIT_CLEAR, learning != 0, wmode);
-    LAUNCH(h, "sp_overlap", k_sp_overlap, h->sp_blocks, RB, d, bank, n_inputs, h->G, p, p ^ 1, 1, 0);
-    LAUNCH(h, "sp_select", k_sel_pass, h->sel_blocks, RB, d, 1, p ^ 1);
+    LAUNCH(h, "sp_overlap", k_sp_overlap, h->sz.sp_blocks, RB, d, bank, n_inputs, h->sz.G, p, p ^ 1, 1, 0);
+    LAUNCH(h, "sp_select", k_sel_pass, h->sz.sel_blocks, RB, d, 1, p ^ 1);
 }
 
 // grid of the reset launch (htm_reset.h): a grid-stride pass over the cell words and per-cell maxima
@@ -586,9 +648,7 @@ static int enqueue_step(htm_handle *h, const uint32_t *bank, int n_inputs, int l
     enqueue_record(h, (int)(h->step_host & 1));
     enqueue_decode(h, (int)(h->step_host & 1));
     h->step_host += 1;
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { h->err = std::string("kernel launch: ") + hipGetErrorString(e); return HTM_ERR_HIP; }
-    return 0;
+    return launch_status(h->err);
 }
 
 extern "C" int htm_abi_version(void) { return BITHTM_ABI_VERSION; }
@@ -730,7 +790,165 @@ static int alloc_stream_state(htm_handle *h) {
         }
         rc |= dalloc(h, &h->d_cols_stage, k);
     }
+    if (h->knob.trace) rc |= dalloc(h, &d.trace, (size_t)8 * 4096 * 2);
     return rc;
+}
+
+// The environment, read here only: a knob's text, or an integer knob -- dflt when it is not given, else its value clamped to
+// [lo, hi] -- or a flag (a given value is on unless it reads 0)
+static const char *env_str(const char *name) { return getenv(name); }
+static int env_int(const char *name, int dflt, int lo = INT_MIN, int hi = INT_MAX) {
+    const char *e = env_str(name);
+    return e ? std::max(lo, std::min(hi, atoi(e))) : dflt;
+}
+static int env_flag(const char *name, int dflt) {
+    const char *e = env_str(name);
+    return e ? atoi(e) != 0 : dflt;
+}
+
+static Knobs read_knobs() {
+    Knobs k;
+    k.graph_steps = env_int("BITHTM_GRAPH_STEPS", 16, 1, 256);
+    k.eager_below = env_int("BITHTM_EAGER_BELOW", 64, 0);
+    k.trace = env_str("BITHTM_TRACE") != nullptr;
+    const char *until = env_str("BITHTM_TRACE_UNTIL");
+    k.trace_until = until ? (uint32_t)strtoul(until, nullptr, 10) : 0xFFFFFFFFu;
+    k.lean = env_int("BITHTM_LEAN", 2, 0, 2);
+    k.lean2_classify = env_int("BITHTM_LEAN2_CLASSIFY", 0, 1);
+    // the host-fed step (htm_step): select finish alone + k_act_mid_rows, instead of select finish with the activation in its blocks +
+    // k_mid_rows (BITHTM_STEP_SPLIT=0: as before)
+    k.step_split = env_flag("BITHTM_STEP_SPLIT", 1);
+    {   // the grid order of k_act_mid_rows' roles (hex digits: 0 activation, 1 middle, 2 rows, 3 overlap); a permutation with 0 before 1
+        // (measured at the bench shape, 8 waves per SIMD: 0312 42.4 k timesteps/s, 0321 41.9, 0123 41.2, 3201 40.2)
+        const char *e = env_str("BITHTM_LEAN2_ORDER");
+        const int o = e ? (int)strtol(e, nullptr, 16) : 0x0312;
+        int seen = 0, pos[4] = {-1, -1, -1, -1};
+        for (int i = 0; i < 4; ++i) { const int r = (o >> (4 * (3 - i))) & 15; if (r < 4) { seen |= 1 << r; pos[r] = i; } }
+        k.lean2_order = (o >= 0 && o <= 0x3333 && seen == 15 && pos[0] < pos[1]) ? o : 0x0312;
+    }
+    k.fuse_tm = env_flag("BITHTM_FUSE_TM", 1);
+    k.shard_window = env_flag("BITHTM_SHARD_WINDOW", 1);
+    k.scan_large = env_int("BITHTM_SCAN_LARGE", -1);
+    // (test knob: a small model crosses the threshold in the middle of a run, as the headline shape does with more patterns)
+    k.scan_large_above = env_int("BITHTM_SCAN_LARGE_ABOVE", 3 * 1536 * SCAN_SEGS, 0);
+    k.step_window = env_flag("BITHTM_STEP_WINDOW", 1);
+    k.tail_rows = env_flag("BITHTM_TAIL_ROWS", 1);
+    // (0: scan blocks with fixed shares, nothing joining; else every block of the launch joins the scan)
+    k.scan_dyn = env_flag("BITHTM_SCAN_DYN", 1);
+    k.defer_tail = env_flag("BITHTM_DEFER_TAIL", 1);
+    // groups of inference views: 1 = one scan of the shared store for up to M members at a time; 0 (the default: at the bench shape it
+    // reads 6.4 times fewer bytes than the per-member scans yet takes 2.6 times longer, DESIGN.md section 13) = a scan per member;
+    // and a cap of M (test knob: several member chunks at small shapes)
+    k.shared_scan = env_flag("BITHTM_SHARED_SCAN", 0);
+    k.shared_members = env_int("BITHTM_SHARED_SCAN_MEMBERS", 0, 0);
+    k.lean_overlap = env_int("BITHTM_LEAN_OVERLAP", 0, 1);
+    k.lean_learn = env_int("BITHTM_LEAN_LEARN", 0, 1);
+    k.lean_learn_large = env_int("BITHTM_LEAN_LEARN_LARGE", 0, 1);
+    k.lean_scan = env_int("BITHTM_LEAN_SCAN", 0, 1);
+    k.lean_scan_large = env_int("BITHTM_LEAN_SCAN_LARGE", 0, 1);
+    k.scan_blocks = env_int("BITHTM_SCAN_BLOCKS", 0, 1);
+    // test knobs: more launched digits (smaller buckets); fewer record slots (forces the fallback)
+    k.sel_launch_digits = env_int("BITHTM_SEL_LAUNCH_DIGITS", -1, 0);
+    k.cand_d = env_int("BITHTM_CAND_D", CAND_D, 0, CAND_D);
+    k.cand_pairwise = env_int("BITHTM_CAND_PAIRWISE", CAND_PAIRWISE, 0);
+    k.cls_rows_max = env_int("BITHTM_CLASSIFY_WORDS_ABOVE", -1, 0);
+    k.win_offset = env_int("BITHTM_SEL_WINDOW_OFFSET", 0, 0);
+    k.cand_zoom = env_int("BITHTM_CAND_ZOOM", -1);      // (the pairs above which a merge is cut to a sub-bin; -1 = more pairs than blocks by a quarter)
+    k.cand_speculate = env_flag("BITHTM_CAND_SPECULATE", 1);     // (0 = always the general path)
+    k.cand_take_all = env_flag("BITHTM_CAND_TAKE_ALL", 1);       // (0 = a shard's local select always cuts exactly)
+    k.poll_delay = env_int("BITHTM_POLL_DELAY", 7, 0, 64);      // (the select finish's first look at the other blocks' records: x 256 clocks after its own)
+    k.cand_others = env_int("BITHTM_CAND_OTHERS", CAND_OTHERS, 0, CAND_OTHERS);
+    return k;
+}
+
+// The launch sizes of a new handle (h->sz, and the select's digits in its Dev): from its shape, its knobs and what the runtime
+// says is resident at once on the device
+static void size_launches(htm_handle *h) {
+    Dev &d = h->d;
+    const Knobs &k = h->knob;
+    Sizes &z = h->sz;
+    // lanes per SP row: the smallest power of two >= W4, at most 64
+    z.G = 1;
+    while (z.G < d.W4 && z.G < 64) z.G <<= 1;
+    // few fat blocks for the kernels that flush a histogram: every block adds into the same few
+    // hot bins and same-address global atomics are slow (~88 per us per address)
+    const int rows_per_block = (RB / 64) * 4 * (64 / z.G);   // waves x 4 row groups in flight
+    z.sp_blocks = std::max(1, std::min((d.c1 - d.c0 + rows_per_block - 1) / rows_per_block, 256));
+    z.sel_blocks = std::max(1, std::min((d.sel_hi - d.sel_lo + RB - 1) / RB, 128));
+    z.c256_blocks = (d.sel_hi - d.sel_lo + 255) / 256;        // blocks of the emit role: 256 columns of the select's range each
+    z.s1024_blocks = std::max(1, (d.Scap + 1023) / 1024);
+    z.scan_blocks = std::max(1, std::min((d.Lcap + SCAN_SEGS - 1) / SCAN_SEGS, 2048));
+    if (z.scan_blocks > 256) z.scan_blocks = (z.scan_blocks + 255) & ~255;     // (role_scan: whole groups of 256 blocks)
+    z.zero_blocks = std::max(1, std::min((d.Lcap / 128 + 4095) / 4096, 1024));     // k_mid_rows: 16 stores of 16 bytes per thread at most
+    // the three-launch schedule: waves of one 256-thread block per work item in the steady state; the scan's waves take
+    // two groups of segments each, so that emit + learn + scan are all resident at once (tuning knobs)
+    z.lean_overlap_blocks = k.lean_overlap ? k.lean_overlap : z.sp_blocks * (RB / 256);
+    z.lean_learn_blocks = k.lean_learn ? k.lean_learn : 512;
+    z.lean_learn_blocks_large = k.lean_learn_large ? k.lean_learn_large : k.lean_learn ? z.lean_learn_blocks : 768;
+    z.lean_scan_blocks = k.lean_scan ? k.lean_scan : (z.scan_blocks > 512 ? std::max(256, (z.scan_blocks * 3 / 8 + 255) & ~255) : z.scan_blocks);
+    z.lean_scan_blocks_large = k.lean_scan_large ? k.lean_scan_large : k.lean_scan ? z.lean_scan_blocks : z.scan_blocks;
+    if (k.scan_blocks) z.scan_blocks = k.scan_blocks;      // (tuning knob: the defaults above stay)
+    hipDeviceProp_t prop;
+    const bool have_prop = hipGetDeviceProperties(&prop, h->device) == hipSuccess;
+    z.cus = have_prop ? prop.multiProcessorCount : 256;
+    // boosted = float32 factor x integer overlap <= input_dim has at most 24 + bit_length(I)
+    // significant bits, so the low 53 - 24 - bit_length(I) bits of every key are zero and the
+    // radix passes that would only see them are skipped.
+    int B = 0;
+    while ((1ll << B) <= (long long)d.I) ++B;
+    const int informative = std::min(64, 64 - (29 - B) - KEY_SHIFT);      // (select_key moves the bits up by KEY_SHIFT)
+    d.sel_passes = std::max(1, std::min(SEL_MAX_PASSES, (informative + SEL_DIGIT - 1) / SEL_DIGIT));
+    d.low_zero = 64 - informative;            // key bits [0, low_zero) are zero in every key
+    // Emit grids whose blocks are all resident at once finish the select inside k_sp_emit (two digits
+    // by launches, the rest through the record exchange, in which blocks wait for each other).  What
+    // fits is asked of the runtime, kernel by kernel, not assumed.
+    int per_cu_emit = 0, per_cu_open = 0;
+    if (have_prop && hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu_emit, (const void *)k_sp_emit, 256, 0) == hipSuccess &&
+        hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu_open, (const void *)k_open_emit, 256, sizeof(EmitShared)) == hipSuccess) {
+        z.emit_fits = z.c256_blocks <= std::min(1024, per_cu_emit * z.cus);
+        // the pipelined launch puts the activation blocks of the current step behind the emit blocks
+        z.emit_fits_open = z.emit_fits && z.c256_blocks + (d.k * d.KP + 255) / 256 <= std::min(1024, per_cu_open * z.cus);
+        // the three-launch schedule: the emit blocks come first in the grid of the learn + scan + emit kernel
+        // (asked of every form launch_learn_scan_emit may launch for this handle -- LDS tables or not, small-pool or
+        // large-pool scan: they differ in launch bounds and registers -- and the smallest answer counts)
+        int per_cu_lean = 1 << 30;
+        z.lean_resident_large = 1 << 30;
+        const size_t lean_lds = std::max(std::max(learn_lds(learn_epl(d), 256), lean_scan_lds(d)), sizeof(EmitShared));
+        bool asked = h->cfg.enable_tm && z.emit_fits && lean_lds <= 64 * 1024;
+        for (int form = LSE_TAB; asked && form <= LSE_LARGE; ++form) {
+            if (form == LSE_TAB && !lean_tab(d)) continue;           // (never launched without the tables)
+            int per_cu = 0;
+            asked = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void *)lse_kernel(d, form), 256, lean_lds) == hipSuccess;
+            per_cu_lean = std::min(per_cu_lean, per_cu);
+            if (asked && form == LSE_LARGE) z.lean_resident_large = per_cu * z.cus;
+        }
+        z.emit_fits_lean = asked && z.c256_blocks <= std::min(1024, per_cu_lean * z.cus);
+        if (z.lean_resident_large == (1 << 30)) z.lean_resident_large = 4 * z.cus;
+    } else {
+        (void)hipGetLastError();
+        z.emit_fits = z.emit_fits_open = z.emit_fits_lean = false;
+        z.lean_resident_large = 1024;
+    }
+    if (k.lean2_classify) {
+        z.lean2_classify_blocks = k.lean2_classify;
+    } else {
+        // the two-launch schedule's first launch: as many classification blocks as are resident BESIDE the activation, the
+        // overlap and the winner rows -- a block that waits for a slot starts a round late, and the middle role's blocks wait for
+        // the activation whenever they start (bench shape: 164 + 512 + 1 311 + 1 of 2 048 slots leave 60; small models get 384)
+        int per_cu = 0, resident = 1536;
+        if (have_prop && hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void *)k_act_mid_rows, 256, (size_t)SEL_BINS * 4) == hipSuccess)
+            resident = per_cu * z.cus;
+        else
+            (void)hipGetLastError();
+        const int others = (d.k * d.KP + 255) / 256 + z.lean_overlap_blocks + d.k + 1;
+        // (... but no more than 32 where they leave fewer than 128: measured at the bench shape, 60 free slots -- 32 blocks 42.4 k
+        // timesteps/s, 40: 41.9, 56: 41.6)
+        const int room = (resident - others) & ~7;
+        z.lean2_classify_blocks = room >= 128 ? std::min(kClassifyBlocks, room) : 32;
+    }
+    z.sel_passes_full = d.sel_passes;
+    z.sel_passes_fused = std::min(d.sel_passes, 2);
+    if (k.sel_launch_digits >= 0) z.sel_passes_fused = std::max(2, std::min(d.sel_passes, k.sel_launch_digits));
 }
 
 extern "C" int htm_create(const htm_config *cfg, htm_handle **out) {
@@ -763,38 +981,19 @@ extern "C" int htm_create(const htm_config *cfg, htm_handle **out) {
     htm_handle *h = new htm_handle();
     h->cfg = *cfg;
     h->device = cfg->device;
-    h->profile = false;
-    h->prof_last = nullptr;
-    h->step_host = 0;
-    h->d_cols_stage = nullptr;
     h->rank = world > 1 ? cfg->shard_rank : 0;
     h->world = world;
-    h->shard_bank = nullptr;
-    h->shard_n_inputs = 1;
-    h->shard_open = false;
-    h->window_known = false;
-    h->shard_front_wmode = 0;
-    h->shard_graph_ok = false;
-    h->rccl_comm = nullptr;
-    h->shard_send = h->shard_recv = nullptr;
-    h->phase_active = 0;
-    h->phase_open = false;
-    h->import_keep = false;
-    h->ahead_bank = nullptr;
-    h->ahead_n_inputs = h->ahead_learning = 0;
-    h->ahead_lean = false;
+    h->knob = read_knobs();
     hipError_t e = hipSetDevice(cfg->device);
     if (e != hipSuccess) return fail_create(h, std::string("hipSetDevice: ") + hipGetErrorString(e), HTM_ERR_HIP);
     if (cfg->use_caller_stream) {
         h->stream = (hipStream_t)cfg->stream;          // NULL = the default stream
-        h->own_stream = false;
     } else {
         e = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking);
         if (e != hipSuccess) return fail_create(h, std::string("hipStreamCreate: ") + hipGetErrorString(e), HTM_ERR_HIP);
         h->own_stream = true;
     }
     Dev &d = h->d;
-    memset(&d, 0, sizeof(d));
     d.I = cfg->enable_sp ? cfg->input_dim : 0;
     d.W = ((d.I + 127) / 128) * 4;
     d.W4 = d.W / 4;
@@ -832,159 +1031,14 @@ extern "C" int htm_create(const htm_config *cfg, htm_handle **out) {
     d.act_thr = cfg->segment_activation_threshold; d.match_thr = cfg->segment_matching_threshold;
     d.sample = cfg->segment_sampling_synapses;
     d.seed = cfg->seed;
-
+    const Knobs &k = h->knob;                       // (test knobs, in the kernels' arguments)
+    d.trace_until = k.trace_until; d.cand_d = k.cand_d; d.cand_pairwise = k.cand_pairwise; d.cls_rows_max = k.cls_rows_max; d.win_offset = k.win_offset;
+    d.cand_zoom = k.cand_zoom; d.cand_speculate = k.cand_speculate; d.cand_take_all = k.cand_take_all; d.poll_delay = k.poll_delay; d.cand_others = k.cand_others;
     int rc = alloc_weights(h);
     rc |= alloc_stream_state(h);
     if (rc) return fail_create(h, h->err, HTM_ERR_HIP);
-    // lanes per SP row: the smallest power of two >= W4, at most 64
-    h->G = 1;
-    h->seg_hint = 0;
-    h->graph_steps = 16;
-    if (const char *e = getenv("BITHTM_GRAPH_STEPS")) h->graph_steps = std::max(1, std::min(256, atoi(e)));
-    h->eager_below = 64;
-    if (const char *e = getenv("BITHTM_EAGER_BELOW")) h->eager_below = std::max(0, atoi(e));
-    h->seg_pinned = nullptr;
     if (hipHostMalloc((void **)&h->seg_pinned, sizeof(int), hipHostMallocDefault) == hipSuccess) *h->seg_pinned = 0; else h->seg_pinned = nullptr;
-    while (h->G < d.W4 && h->G < 64) h->G <<= 1;
-    // few fat blocks for the kernels that flush a histogram: every block adds into the same few
-    // hot bins and same-address global atomics are slow (~88 per us per address)
-    const int rows_per_block = (RB / 64) * 4 * (64 / h->G);   // waves x 4 row groups in flight
-    h->sp_blocks = std::max(1, std::min((d.c1 - d.c0 + rows_per_block - 1) / rows_per_block, 256));
-    d.trace = nullptr;
-    if (getenv("BITHTM_TRACE")) rc |= dalloc(h, &d.trace, (size_t)8 * 4096 * 2);
-    d.trace_until = getenv("BITHTM_TRACE_UNTIL") ? (uint32_t)strtoul(getenv("BITHTM_TRACE_UNTIL"), nullptr, 10) : 0xFFFFFFFFu;
-    h->sel_blocks = std::max(1, std::min((d.sel_hi - d.sel_lo + RB - 1) / RB, 128));
-    h->c256_blocks = (d.sel_hi - d.sel_lo + 255) / 256;        // blocks of the emit role: 256 columns of the select's range each
-    h->s1024_blocks = std::max(1, (d.Scap + 1023) / 1024);
-    h->scan_blocks = std::max(1, std::min((d.Lcap + SCAN_SEGS - 1) / SCAN_SEGS, 2048));
-    if (h->scan_blocks > 256) h->scan_blocks = (h->scan_blocks + 255) & ~255;     // (role_scan: whole groups of 256 blocks)
-    h->zero_blocks = std::max(1, std::min((d.Lcap / 128 + 4095) / 4096, 1024));     // k_mid_rows: 16 stores of 16 bytes per thread at most
-    // the three-launch schedule: waves of one 256-thread block per work item in the steady state; the scan's waves take
-    // two groups of segments each, so that emit + learn + scan are all resident at once (tuning knobs)
-    // launches per step of htm_run's pipelined schedule -- 2 (the default): two (k_act_mid_rows + k_learn_scan_emit); 1: three; 0: four
-    h->knob_lean = getenv("BITHTM_LEAN") ? std::max(0, std::min(2, atoi(getenv("BITHTM_LEAN")))) : 2;
-    h->lean2_classify_blocks = getenv("BITHTM_LEAN2_CLASSIFY") ? std::max(1, atoi(getenv("BITHTM_LEAN2_CLASSIFY"))) : kClassifyBlocks;
-    h->lean2_classify_set = getenv("BITHTM_LEAN2_CLASSIFY") != nullptr;
-    // the host-fed step (htm_step): select finish alone + k_act_mid_rows, instead of select finish with the activation in its blocks +
-    // k_mid_rows (BITHTM_STEP_SPLIT=0: as before)
-    h->knob_step_split = getenv("BITHTM_STEP_SPLIT") ? atoi(getenv("BITHTM_STEP_SPLIT")) != 0 : 1;
-    {   // the grid order of k_act_mid_rows' roles (hex digits: 0 activation, 1 middle, 2 rows, 3 overlap); a permutation with 0 before 1
-        // (measured at the bench shape, 8 waves per SIMD: 0312 42.4 k timesteps/s, 0321 41.9, 0123 41.2, 3201 40.2)
-        const int o = getenv("BITHTM_LEAN2_ORDER") ? (int)strtol(getenv("BITHTM_LEAN2_ORDER"), nullptr, 16) : 0x0312;
-        int seen = 0, pos[4] = {-1, -1, -1, -1};
-        for (int i = 0; i < 4; ++i) { const int r = (o >> (4 * (3 - i))) & 15; if (r < 4) { seen |= 1 << r; pos[r] = i; } }
-        h->lean2_order = (o >= 0 && o <= 0x3333 && seen == 15 && pos[0] < pos[1]) ? o : 0x0312;
-    }
-    h->knob_fuse_tm = getenv("BITHTM_FUSE_TM") ? atoi(getenv("BITHTM_FUSE_TM")) != 0 : 1;
-    h->knob_shard_window = getenv("BITHTM_SHARD_WINDOW") ? atoi(getenv("BITHTM_SHARD_WINDOW")) != 0 : 1;
-    h->knob_scan_large = getenv("BITHTM_SCAN_LARGE") ? atoi(getenv("BITHTM_SCAN_LARGE")) : -1;
-    // (test knob: a small model crosses the threshold in the middle of a run, as the headline shape does with more patterns)
-    h->scan_large_above = getenv("BITHTM_SCAN_LARGE_ABOVE") ? std::max(0, atoi(getenv("BITHTM_SCAN_LARGE_ABOVE"))) : 3 * 1536 * SCAN_SEGS;
-    h->knob_step_window = getenv("BITHTM_STEP_WINDOW") ? atoi(getenv("BITHTM_STEP_WINDOW")) != 0 : 1;
-    h->knob_tail_rows = getenv("BITHTM_TAIL_ROWS") ? atoi(getenv("BITHTM_TAIL_ROWS")) != 0 : 1;
-    // (0: scan blocks with fixed shares, nothing joining; else every block of the launch joins the scan)
-    h->knob_scan_dyn = getenv("BITHTM_SCAN_DYN") ? atoi(getenv("BITHTM_SCAN_DYN")) != 0 : 1;
-    h->knob_defer_tail = getenv("BITHTM_DEFER_TAIL") ? atoi(getenv("BITHTM_DEFER_TAIL")) != 0 : 1;
-    // groups of inference views: 1 = one scan of the shared store for up to M members at a time; 0 (the default: at the bench shape it
-    // reads 6.4 times fewer bytes than the per-member scans yet takes 2.6 times longer, DESIGN.md section 13) = a scan per member;
-    // and a cap of M (test knob: several member chunks at small shapes)
-    h->knob_shared_scan = getenv("BITHTM_SHARED_SCAN") ? atoi(getenv("BITHTM_SHARED_SCAN")) != 0 : 0;
-    h->knob_shared_members = getenv("BITHTM_SHARED_SCAN_MEMBERS") ? std::max(0, atoi(getenv("BITHTM_SHARED_SCAN_MEMBERS"))) : 0;
-    h->tail_pending = false;
-    h->tail_p = 0;
-    h->lean_overlap_blocks = getenv("BITHTM_LEAN_OVERLAP") ? std::max(1, atoi(getenv("BITHTM_LEAN_OVERLAP"))) : h->sp_blocks * (RB / 256);
-    h->lean_learn_blocks = getenv("BITHTM_LEAN_LEARN") ? std::max(1, atoi(getenv("BITHTM_LEAN_LEARN"))) : 512;
-    h->lean_learn_blocks_large = getenv("BITHTM_LEAN_LEARN_LARGE") ? std::max(1, atoi(getenv("BITHTM_LEAN_LEARN_LARGE"))) : getenv("BITHTM_LEAN_LEARN") ? h->lean_learn_blocks : 768;
-    h->lean_scan_blocks = getenv("BITHTM_LEAN_SCAN") ? std::max(1, atoi(getenv("BITHTM_LEAN_SCAN"))) : (h->scan_blocks > 512 ? std::max(256, (h->scan_blocks * 3 / 8 + 255) & ~255) : h->scan_blocks);
-    h->lean_scan_blocks_large = getenv("BITHTM_LEAN_SCAN_LARGE") ? std::max(1, atoi(getenv("BITHTM_LEAN_SCAN_LARGE"))) : getenv("BITHTM_LEAN_SCAN") ? h->lean_scan_blocks : h->scan_blocks;
-    {
-        hipDeviceProp_t prop;
-        h->cus = hipGetDeviceProperties(&prop, h->device) == hipSuccess ? prop.multiProcessorCount : 256;
-    }
-    if (const char *e = getenv("BITHTM_SCAN_BLOCKS")) h->scan_blocks = std::max(1, atoi(e));      // tuning knob
-    // boosted = float32 factor x integer overlap <= input_dim has at most 24 + bit_length(I)
-    // significant bits, so the low 53 - 24 - bit_length(I) bits of every key are zero and the
-    // radix passes that would only see them are skipped.
-    {
-        int B = 0;
-        while ((1ll << B) <= (long long)d.I) ++B;
-        const int informative = std::min(64, 64 - (29 - B) - KEY_SHIFT);      // (select_key moves the bits up by KEY_SHIFT)
-        d.sel_passes = std::max(1, std::min(SEL_MAX_PASSES, (informative + SEL_DIGIT - 1) / SEL_DIGIT));
-        d.low_zero = 64 - informative;            // key bits [0, low_zero) are zero in every key
-        // Emit grids whose blocks are all resident at once finish the select inside k_sp_emit (two digits
-        // by launches, the rest through the record exchange, in which blocks wait for each other).  What
-        // fits is asked of the runtime, kernel by kernel, not assumed.
-        {
-            const int c256 = (d.sel_hi - d.sel_lo + 255) / 256;
-            hipDeviceProp_t prop;
-            int per_cu_emit = 0, per_cu_open = 0;
-            if (hipGetDeviceProperties(&prop, h->device) == hipSuccess &&
-                hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu_emit, (const void *)k_sp_emit, 256, 0) == hipSuccess &&
-                hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu_open, (const void *)k_open_emit, 256, sizeof(EmitShared)) == hipSuccess) {
-                const int cus = prop.multiProcessorCount;
-                h->emit_fits = c256 <= std::min(1024, per_cu_emit * cus);
-                // the pipelined launch puts the activation blocks of the current step behind the emit blocks
-                h->emit_fits_open = h->emit_fits && c256 + (d.k * d.KP + 255) / 256 <= std::min(1024, per_cu_open * cus);
-                // the three-launch schedule: the emit blocks come first in the grid of the learn + scan + emit kernel
-                // (asked of every instantiation enqueue_lean may launch for this handle -- LDS tables or not, small-pool or
-                // large-pool scan: they differ in launch bounds and registers -- and the smallest answer counts)
-                int per_cu_lean = 1 << 30;
-                h->lean_resident_large = 1 << 30;
-                const size_t lean_lds = std::max(std::max(learn_lds(learn_epl(d), 256), lean_scan_lds(d)), sizeof(EmitShared));
-                const int epl = learn_epl(d);
-#define LSE_VARIANTS(E_) {(const void *)k_learn_scan_emit<E_, 6, true>, (const void *)k_learn_scan_emit<E_, 6, false>, (const void *)k_learn_scan_emit<E_, 4, false>}
-                const void *kerns[4][3] = {LSE_VARIANTS(1), LSE_VARIANTS(2), LSE_VARIANTS(4), LSE_VARIANTS(8)};
-#undef LSE_VARIANTS
-                bool asked = cfg->enable_tm && h->emit_fits && lean_lds <= 64 * 1024;
-                for (int v = 0; asked && v < 3; ++v) {
-                    if (v == 0 && !lean_tab(d)) continue;           // (never launched without the tables)
-                    int per_cu = 0;
-                    asked = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kerns[epl == 1 ? 0 : epl == 2 ? 1 : epl == 4 ? 2 : 3][v], 256, lean_lds) == hipSuccess;
-                    per_cu_lean = std::min(per_cu_lean, per_cu);
-                    if (asked && v == 2) h->lean_resident_large = per_cu * cus;      // (the large-pool form)
-                }
-                h->emit_fits_lean = asked && c256 <= std::min(1024, per_cu_lean * cus);
-                if (h->lean_resident_large == (1 << 30)) h->lean_resident_large = 4 * cus;
-            } else {
-                (void)hipGetLastError();
-                h->emit_fits = h->emit_fits_open = h->emit_fits_lean = false;
-                h->lean_resident_large = 1024;
-            }
-        }
-        if (!getenv("BITHTM_LEAN2_CLASSIFY")) {
-            // the two-launch schedule's first launch: as many classification blocks as are resident BESIDE the activation, the
-            // overlap and the winner rows -- a block that waits for a slot starts a round late, and the middle role's blocks wait for
-            // the activation whenever they start (bench shape: 164 + 512 + 1 311 + 1 of 2 048 slots leave 60; small models get 384)
-            hipDeviceProp_t prop;
-            int per_cu = 0, resident = 1536;
-            if (hipGetDeviceProperties(&prop, h->device) == hipSuccess &&
-                hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void *)k_act_mid_rows, 256, (size_t)SEL_BINS * 4) == hipSuccess)
-                resident = per_cu * prop.multiProcessorCount;
-            else
-                (void)hipGetLastError();
-            const int others = (d.k * d.KP + 255) / 256 + h->lean_overlap_blocks + d.k + 1;
-            // (... but no more than 32 where they leave fewer than 128: measured at the bench shape, 60 free slots -- 32 blocks 42.4 k
-            // timesteps/s, 40: 41.9, 56: 41.6)
-            const int room = (resident - others) & ~7;
-            h->lean2_classify_blocks = room >= 128 ? std::min(kClassifyBlocks, room) : 32;
-        }
-        h->sel_passes_full = d.sel_passes;
-        h->sel_passes_fused = std::min(d.sel_passes, 2);
-        // test knobs: more launched digits (smaller buckets); fewer record slots (forces the fallback)
-        if (const char *e = getenv("BITHTM_SEL_LAUNCH_DIGITS")) h->sel_passes_fused = std::max(2, std::min(d.sel_passes, atoi(e)));
-        d.cand_d = CAND_D;
-        if (const char *e = getenv("BITHTM_CAND_D")) d.cand_d = std::max(0, std::min(CAND_D, atoi(e)));
-        d.cand_pairwise = CAND_PAIRWISE;
-        if (const char *e = getenv("BITHTM_CAND_PAIRWISE")) d.cand_pairwise = std::max(0, atoi(e));     // test knobs
-        d.cls_rows_max = getenv("BITHTM_CLASSIFY_WORDS_ABOVE") ? std::max(0, atoi(getenv("BITHTM_CLASSIFY_WORDS_ABOVE"))) : -1;
-        d.win_offset = getenv("BITHTM_SEL_WINDOW_OFFSET") ? std::max(0, atoi(getenv("BITHTM_SEL_WINDOW_OFFSET"))) : 0;
-        d.cand_zoom = getenv("BITHTM_CAND_ZOOM") ? atoi(getenv("BITHTM_CAND_ZOOM")) : -1;      // (test knob: the pairs above which a merge is cut to a sub-bin; -1 = more pairs than blocks by a quarter)
-        d.cand_speculate = getenv("BITHTM_CAND_SPECULATE") ? atoi(getenv("BITHTM_CAND_SPECULATE")) != 0 : 1;     // (test knob: 0 = always the general path)
-        d.cand_take_all = getenv("BITHTM_CAND_TAKE_ALL") ? atoi(getenv("BITHTM_CAND_TAKE_ALL")) != 0 : 1;      // (test knob: 0 = a shard's local select always cuts exactly)
-        d.poll_delay = getenv("BITHTM_POLL_DELAY") ? std::max(0, std::min(64, atoi(getenv("BITHTM_POLL_DELAY")))) : 7;     // (the select finish's first look at the other blocks' records: x 256 clocks after its own)
-        d.cand_others = CAND_OTHERS;
-        if (const char *e = getenv("BITHTM_CAND_OTHERS")) d.cand_others = std::max(0, std::min(CAND_OTHERS, atoi(e)));
-    }
+    size_launches(h);
     e = hipStreamSynchronize(h->stream);
     if (e != hipSuccess) return fail_create(h, std::string("hipStreamSynchronize: ") + hipGetErrorString(e), HTM_ERR_HIP);
     {
@@ -1037,7 +1091,7 @@ static int view_enter(htm_handle *h, int learning) {
             return HTM_ERR_STATE;
         }
         HIPCHK(h, hipMemcpyAsync(&h->d.ctr->S, &par->d.ctr->S, sizeof(int32_t), hipMemcpyDeviceToDevice, h->stream));
-        if (par->seg_pinned) { const int seen = *(volatile int *)par->seg_pinned; par->seg_hint = std::max(par->seg_hint, seen); }
+        refresh_seg_hint(par);
         h->seg_hint = std::max(h->seg_hint, par->seg_hint);
     }
     if (wgen != h->seen_wgen) {
@@ -1075,46 +1129,38 @@ extern "C" int htm_create_view(htm_handle *parent, htm_handle **out) {
             parent->shared = sh;
         }
     }
-    // the parent's scalars and launch sizes (knobs included); none of its buffers, graphs, events or descriptors
-    htm_handle *h = new htm_handle(*parent);
-    h->err.clear();
-    h->allocs.clear();
-    h->weight_allocs.clear();
-    h->graphs.clear();
-    h->shard_graphs.clear();
-    h->prof_events.clear(); h->prof_names.clear(); h->prof_ms.clear(); h->prof_n.clear(); h->prof_all.clear();
-    h->imp_pot.clear(); h->imp_match_seg.clear(); h->imp_seg_cell.clear(); h->imp_seg_nsyn.clear(); h->imp_presyn.clear();
-    h->imp_perm.clear(); h->imp_match_info.clear(); h->imp_match_jit.clear();
-    h->own_stream = false;
-    h->profile = false;
-    h->prof_last = nullptr;
-    h->d_cols_stage = nullptr;
-    h->shard_bank = nullptr;
-    h->rccl_comm = nullptr;
-    h->shard_send = h->shard_recv = nullptr;
-    h->seg_pinned = nullptr;
-    h->ahead_bank = nullptr;
-    h->d_rec = nullptr; h->recording = false;
-    h->reset_bits = nullptr; h->reset_n = 0; h->d_reset = nullptr; h->resetting = false;
-    h->pin_out = nullptr; h->d_pin = nullptr; h->decoding = false; h->d_pin_buf = nullptr;
-    h->tail_pending = false;
-    h->knob_defer_tail = 0;                          // (a view's step is whole when its call returns: see view_enter)
-    h->import_keep = false;
-    h->own_bytes = 0;
+    // a fresh handle with the parent's shape, weights, knobs and launch sizes and where its stream is (step, segment count, select
+    // window); its own stream state -- and none of the parent's buffers, graphs, events or descriptors
+    htm_handle *h = new htm_handle();
+    h->cfg = parent->cfg;
+    h->device = parent->device;
+    h->stream = parent->stream;
+    h->rank = parent->rank;
+    h->world = parent->world;
+    h->d = parent->d;                                // (alloc_stream_state replaces the stream state's buffers)
+    h->d.trace = nullptr;
+    h->knob = parent->knob;
+    h->sz = parent->sz;
+    h->step_host = parent->step_host;
+    h->seg_hint = parent->seg_hint;
+    h->window_known = parent->window_known;
     h->is_view = true;
-    // (the shared scan's knobs are the view's own, read now: a group's form follows its first member's)
-    h->knob_shared_scan = getenv("BITHTM_SHARED_SCAN") ? atoi(getenv("BITHTM_SHARED_SCAN")) != 0 : 0;
-    h->knob_shared_members = getenv("BITHTM_SHARED_SCAN_MEMBERS") ? std::max(0, atoi(getenv("BITHTM_SHARED_SCAN_MEMBERS"))) : 0;
+    h->knob.defer_tail = 0;                          // (a view's step is whole when its call returns: see view_enter)
+    {   // (the shared scan's knobs are the view's own, read now: a group's form follows its first member's; and its own trace)
+        const Knobs now = read_knobs();
+        h->knob.shared_scan = now.shared_scan;
+        h->knob.shared_members = now.shared_members;
+        h->knob.trace = now.trace;
+    }
     {
         std::lock_guard<std::mutex> lock(g_shared_mutex);
+        h->shared = parent->shared;
         h->shared->refs += 1;
         h->seen_wgen = h->shared->wgen;
     }
     Dev &d = h->d;
-    d.trace = nullptr;
     const Dev &pd = parent->d;
     int rc = alloc_stream_state(h);
-    if (!rc && getenv("BITHTM_TRACE")) rc = dalloc(h, &d.trace, (size_t)8 * 4096 * 2);
     if (rc) return fail_create(h, h->err, HTM_ERR_HIP);
     // the parent's duty cycles and counter block, then a sequence reset (htm_reset.h) -- and the learning role's counts and the
     // sticky capacity flags start clean
@@ -1248,6 +1294,8 @@ static int stage_input(htm_handle *h, const uint32_t *packed_input) {
     return 0;
 }
 
+static decltype(&k_learn_scan_front<1>) const kt_learn_scan_front[4] = {k_learn_scan_front<1>, k_learn_scan_front<2>, k_learn_scan_front<4>, k_learn_scan_front<8>};
+
 extern "C" int htm_step(htm_handle *h, const uint32_t *packed_input, int32_t learning) {
     if (!h || !packed_input) return HTM_ERR_ARGUMENT;
     REJECT_WHEN_AHEAD(h);
@@ -1269,37 +1317,35 @@ extern "C" int htm_step(htm_handle *h, const uint32_t *packed_input, int32_t lea
     // NEXT input and nothing the next step's overlap touches -- they are held back and ride beside that overlap (the
     // permanence rows, which the overlap does read, in the middle launch instead).  Any other call lets them go first.
     Dev &d = h->d;
-    if (h->knob_defer_tail && d.W <= ARG_INPUT_WORDS && tm_tail_fused(h) && !h->profile) {
+    if (h->knob.defer_tail && d.W <= ARG_INPUT_WORDS && tm_tail_fused(h) && !h->profile) {
         const int p = (int)(h->step_host & 1), wmode = step_wmode(h);
         // the held-back learning role and scan of the step before ride beside THIS step's select finish (k_learn_scan_emit, the last
         // launch of htm_run's schedules) where that launch is available: the overlap then has the first launch to itself (4.5 us), and the
         // select finish -- 7 us of a chain on 256 blocks -- no longer has the GPU to itself.  (The activation, which reads the
         // predictions that scan leaves, has moved behind it: k_act_mid_rows.)
-        const bool ride_emit = h->knob_step_split && h->tail_pending && wmode && h->emit_fused && can_lean(h);
+        const bool ride_emit = h->knob.step_split && h->tail_pending && wmode && h->emit_fused && can_lean(h);
         bool emitted = false;
         if (ride_emit) {
             enqueue_sp_front(h, d.input_stage, 1, p, wmode, packed_input);
             h->tail_pending = false;
-            launch_learn_scan_emit(h, h->tail_p, h->c256_blocks);
+            launch_learn_scan_emit(h, h->tail_p, h->sz.c256_blocks);
             h->window_known = true;
             emitted = true;
         } else if (h->tail_pending) {
             PackedInputArg in;
             memset(&in, 0, sizeof(in));
             memcpy(in.w, packed_input, (size_t)((d.I + 31) / 32) * 4);
-            const int epl = learn_epl(d), n_learn = h->lean_learn_blocks, n_scan = h->lean_scan_blocks, spec = scan_spec_blocks(h);
+            const int epl = learn_epl(d), n_learn = h->sz.lean_learn_blocks, n_scan = h->sz.lean_scan_blocks, spec = scan_spec_blocks(h);
             const size_t lds = std::max(std::max(learn_lds(epl, 256), scan_lds(d, 1)), (size_t)(SEL_BINS + ARG_INPUT_WORDS) * 4);
-            const int grid = n_learn + n_scan + h->lean_overlap_blocks;
+            const int grid = n_learn + n_scan + h->sz.lean_overlap_blocks;
             h->tail_pending = false;
-#define LAUNCH_LSF(E_) LAUNCH_ON(h, h->stream, lds, "tm_learn+tm_scan+sp_overlap", (k_learn_scan_front<E_>), grid, 256, d, h->tail_p, n_learn, n_scan, spec, in, h->G, p, wmode)
-            switch (epl) { case 1: LAUNCH_LSF(1); break; case 2: LAUNCH_LSF(2); break; case 4: LAUNCH_LSF(4); break; default: LAUNCH_LSF(8); break; }
-#undef LAUNCH_LSF
+            LAUNCH_ON(h, h->stream, lds, "tm_learn+tm_scan+sp_overlap", kt_learn_scan_front[epl_slot(d)], grid, 256, d, h->tail_p, n_learn, n_scan, spec, in, h->sz.G, p, wmode);
             if (!wmode)
-                for (int pass = 1; pass < d.sel_passes; ++pass) LAUNCH(h, "sp_select", k_sel_pass, h->sel_blocks, RB, d, pass, p);
+                for (int pass = 1; pass < d.sel_passes; ++pass) LAUNCH(h, "sp_select", k_sel_pass, h->sz.sel_blocks, RB, d, pass, p);
         } else {
             enqueue_sp_front(h, d.input_stage, 1, p, wmode, packed_input);
         }
-        if (h->knob_step_split) {
+        if (h->knob.step_split) {
             // the select finish on its own (winner list and column bitmap, nothing else), then the two-launch schedule's first launch
             // in the form its last step takes: activation -> fan-in -> middle role beside the winner rows, the duty cycle and the
             // clears (k_act_mid_rows without an overlap role).  The activation no longer waits at the end of the select finish's
@@ -1307,10 +1353,10 @@ extern "C" int htm_step(htm_handle *h, const uint32_t *packed_input, int32_t lea
             if (!emitted) enqueue_sp_back(h, d.input_stage, 1, p, 1, 0, false, wmode);
             const int lrn = learning ? 1 : 0;
             const int n_act = (d.k * d.KP + 255) / 256, n_rows = lrn ? d.k : 0;
-            const int n_cls2 = !lrn ? 0 : (scan_pool_is_large(h) && !h->lean2_classify_set) ? std::max(h->lean2_classify_blocks, 192) : h->lean2_classify_blocks;
-            const int n_duty = h->c256_blocks, n_clear = d.WPC * h->c256_blocks;
-            LAUNCH_ON(h, h->stream, 0, "tm_activate+tm_mid+sp_learn", k_act_mid_rows, n_act + 1 + n_cls2 + n_rows + n_duty + n_clear + h->zero_blocks, 256,
-                      d, p, d.k, n_act, lrn, n_cls2, d.input_stage, 1, n_rows, h->G, 0, n_duty, n_clear, h->lean2_order);
+            const int n_cls2 = lean2_classify_blocks(h, lrn);
+            const int n_duty = h->sz.c256_blocks, n_clear = d.WPC * h->sz.c256_blocks;
+            LAUNCH_ON(h, h->stream, 0, "tm_activate+tm_mid+sp_learn", k_act_mid_rows, n_act + 1 + n_cls2 + n_rows + n_duty + n_clear + h->sz.zero_blocks, 256,
+                      d, p, d.k, n_act, lrn, n_cls2, d.input_stage, 1, n_rows, h->sz.G, 0, n_duty, n_clear, h->knob.lean2_order);
             h->tail_pending = true;
             h->tail_p = p;
         } else {
@@ -1318,9 +1364,7 @@ extern "C" int htm_step(htm_handle *h, const uint32_t *packed_input, int32_t lea
             enqueue_tm(h, d.k, learning ? 1 : 0, 1, p, d.input_stage, 1, true, -1, true);
         }
         h->step_host += 1;
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) { h->err = std::string("kernel launch: ") + hipGetErrorString(e); return HTM_ERR_HIP; }
-        return HTM_OK;
+        return launch_status(h->err);
     }
     flush_tail(h);
     return enqueue_step(h, h->d.input_stage, 1, learning ? 1 : 0, StepPlan{false, false, false}, packed_input);
@@ -1371,7 +1415,7 @@ extern "C" int htm_sp_phase(htm_handle *h, int32_t phase, const void *data, int6
             if (!data) return HTM_ERR_ARGUMENT;
             int rc = stage_input(h, (const uint32_t *)data);
             if (rc) return rc;
-            LAUNCH(h, "sp_overlap", k_sp_overlap, h->sp_blocks, RB, d, d.input_stage, 1, h->G, p, p, 0, 0);
+            LAUNCH(h, "sp_overlap", k_sp_overlap, h->sz.sp_blocks, RB, d, d.input_stage, 1, h->sz.G, p, p, 0, 0);
             break;
         }
         case HTM_SP_BOOST: {                       // ExponentialBoosting.process on overlaps from the host; data = int32[C]
@@ -1388,7 +1432,7 @@ extern "C" int htm_sp_phase(htm_handle *h, int32_t phase, const void *data, int6
                 HIPCHK(h, hipStreamSynchronize(h->stream));
                 LAUNCH(h, "sp_keys", k_sp_keys, std::min((d.C + RB - 1) / RB, 256), RB, d, p, 0);
             }
-            for (int pass = 1; pass < d.sel_passes; ++pass) LAUNCH(h, "sp_select", k_sel_pass, h->sel_blocks, RB, d, pass, p);
+            for (int pass = 1; pass < d.sel_passes; ++pass) LAUNCH(h, "sp_select", k_sel_pass, h->sz.sel_blocks, RB, d, pass, p);
             enqueue_sp_back(h, d.input_stage, 1, p, 0, 0, false);          // the list and its bitmap, nothing else
             break;
         }
@@ -1428,9 +1472,7 @@ extern "C" int htm_sp_phase(htm_handle *h, int32_t phase, const void *data, int6
     }
     if (phase == HTM_SP_SELECT) h->phase_active = d.k;
     h->phase_open = phase != HTM_SP_COMMIT;
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { h->err = std::string("kernel launch: ") + hipGetErrorString(e); return HTM_ERR_HIP; }
-    return HTM_OK;
+    return launch_status(h->err);
 }
 
 extern "C" int htm_tm_step(htm_handle *h, const int32_t *active_column, int32_t n, int32_t learning, int32_t return_winner_cell) {
@@ -1527,7 +1569,7 @@ extern "C" int htm_tm_update(htm_handle *h, const int32_t *columns, const uint32
     hipLaunchKernelGGL(k_tm_ext_winners, dim3(std::min((d.C + 255) / 256, 1024)), dim3(256), 0, h->stream, d, p, d_cols, d_ww, d_uw, n, 0);
     if (n) hipLaunchKernelGGL(k_tm_ext_winners, dim3((n * WPC + 255) / 256), dim3(256), 0, h->stream, d, p, d_cols, d_ww, d_uw, n, 1);
     d.punish = d_pun;                               // (kernels take Dev by value: set for the middle launch only)
-    LAUNCH(h, "tm_mid", k_mid_rows, 1 + kClassifyBlocks + h->zero_blocks, 256, d, p, n, 1, 1, kClassifyBlocks, nullptr, 1, 0, 0, 0);
+    LAUNCH(h, "tm_mid", k_mid_rows, 1 + kClassifyBlocks + h->sz.zero_blocks, 256, d, p, n, 1, 1, kClassifyBlocks, nullptr, 1, 0, 0, 0);
     d.punish = nullptr;
     launch_learn(h, p);
     hipError_t e = hipGetLastError();
@@ -1595,7 +1637,7 @@ static int run_or_prepare(htm_handle *h, const uint32_t *device_inputs, int32_t 
     // (a short call is launched eagerly whatever the flag says: a graph launch on an idle device starts its first kernel
     // about 7 us later than a kernel launch does, and the host submits three launches per 30-us step with time to spare --
     // measured, 20 steps per call: 615 against 638 us; from 64 steps on the graphs are level and then ahead)
-    const bool graph = (use_graph & 1) && !h->profile && n_steps >= h->eager_below;
+    const bool graph = (use_graph & 1) && !h->profile && n_steps >= h->knob.eager_below;
     const bool pipeline = !(use_graph & 2) && can_pipeline(h) && !decode_unpipelined(h);
     const bool resume = sp_is_ahead(h);            // the previous call left the SP one step (and a front) ahead
     if (resume && (h->ahead_bank != device_inputs || h->ahead_n_inputs != n_inputs || h->ahead_learning != learning)) {
@@ -1641,8 +1683,8 @@ static int run_or_prepare(htm_handle *h, const uint32_t *device_inputs, int32_t 
             // (the four-launch schedule had begun the step after it: that front is never consumed)
             HIPCHK(h, hipMemsetAsync(h->d.hist0 + (size_t)(h->step_host & 1) * HIST0_PAR, 0, (size_t)HIST0_PAR * 4, h->stream));
             h->ahead_bank = nullptr;
-            hipError_t e = hipGetLastError();
-            if (e != hipSuccess) { h->err = std::string("kernel launch: ") + hipGetErrorString(e); return HTM_ERR_HIP; }
+            const int rc = launch_status(h->err);
+            if (rc) return rc;
         }
         return run_or_prepare(h, device_inputs, n_inputs, n_steps - 1, learning, use_graph, false, h->recording, nullptr, h->recording, h->decoding);
     }
@@ -1650,8 +1692,8 @@ static int run_or_prepare(htm_handle *h, const uint32_t *device_inputs, int32_t 
     // launch boundary costs about 5 us more than a kernel boundary inside a graph: tools/step_timeline.py).
     // Nothing in a graph depends on the step index: kernels read it, and with it the bank row, from
     // the device counter.
-    const int kGraphSteps = h->graph_steps;
-    if (h->seg_pinned) { const int seen = *(volatile int *)h->seg_pinned; h->seg_hint = std::max(h->seg_hint, seen); }      // what the last run left
+    const int kGraphSteps = h->knob.graph_steps;
+    refresh_seg_hint(h);                            // what the last run left
     bool sp_done = resume;                          // the SP has already done the coming step
     long long step = h->step_host;
     for (int t = 0; t < n_steps;) {
@@ -1676,26 +1718,19 @@ static int run_or_prepare(htm_handle *h, const uint32_t *device_inputs, int32_t 
             if (!plan.sp_done && !plan.next_sp) enqueue_sp_front(h, device_inputs, n_inputs, p, step_wmode(h));    // eager
             enqueue_cold_start(h, device_inputs, n_inputs, learning, plan);                         // eager: first step of a pipelined run
         }
-        auto key = std::make_tuple(p + (h->recording ? 2 : 0) + (h->resetting ? 4 : 0) + (h->decoding ? 8 : 0), learning * 16 + (plan.sp_done ? 4 : 0) + (plan.next_sp ? 2 : 0) + (plan.next_front ? 1 : 0) + 32 * scan_spec_blocks(h) + (scan_pool_is_large(h) ? (1 << 20) : 0) + (h->emit_fused ? (1 << 21) : 0) + (span << 22) + (lean ? 8 : 0) + (step_wmode(h) ? (1 << 19) : 0),
-                                   (const void *)device_inputs, n_inputs);
-        auto it = h->graphs.find(key);
-        if (it == h->graphs.end()) {
-            hipGraph_t graph_obj;
-            HIPCHK(h, hipStreamBeginCapture(h->stream, hipStreamCaptureModeThreadLocal));
+        const RunGraphKey key{p, h->recording, h->resetting, h->decoding, learning, plan.sp_done, plan.next_sp, plan.next_front, lean,
+                              scan_spec_blocks(h), scan_pool_is_large(h), h->emit_fused, step_wmode(h) != 0, span, device_inputs, n_inputs};
+        const hipGraphExec_t exec = cached_graph(h->graphs, key, h->stream, h->err, [&] {
             for (int i = 0; i < span; ++i) {
                 enqueue_rest(h, (p + i) & 1, device_inputs, n_inputs, learning, plan);
                 enqueue_record(h, (p + i) & 1);
                 enqueue_decode(h, (p + i) & 1);
             }
-            hipError_t e = hipStreamEndCapture(h->stream, &graph_obj);
-            if (e != hipSuccess) { h->err = std::string("hipStreamEndCapture: ") + hipGetErrorString(e); return HTM_ERR_HIP; }
-            hipGraphExec_t exec;
-            HIPCHK(h, hipGraphInstantiate(&exec, graph_obj, nullptr, nullptr, 0));
-            hipGraphDestroy(graph_obj);
-            it = h->graphs.emplace(key, exec).first;
-        }
+            return 0;
+        });
+        if (!exec) return HTM_ERR_HIP;
         if (!dry) {
-            HIPCHK(h, hipGraphLaunch(it->second, h->stream));
+            HIPCHK(h, hipGraphLaunch(exec, h->stream));
             h->step_host += span;
         }
         step += span;
@@ -1710,7 +1745,7 @@ static int run_or_prepare(htm_handle *h, const uint32_t *device_inputs, int32_t 
         h->ahead_n_inputs = n_inputs;
         h->ahead_learning = learning;
         // leave the segment count where the next call finds it (no wait: it may see the one before)
-        if (h->seg_pinned) HIPCHK(h, hipMemcpyAsync(h->seg_pinned, &h->d.ctr->S, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hand_back_segments(h, &h->d.ctr->S, h->stream));
     }
     return HTM_OK;
 }
@@ -1763,8 +1798,8 @@ extern "C" int htm_run_plan(htm_handle *h, int32_t n_steps, int32_t use_graph) {
     if (!h || n_steps < 0) return HTM_ERR_ARGUMENT;
     if (!h->cfg.enable_sp || !h->cfg.enable_tm || h->world > 1) { h->err = "htm_run_plan: htm_run needs an unsharded handle with SP and TM"; return HTM_ERR_STATE; }
     refresh_exchange_mode(h);
-    if (h->seg_pinned) { const int seen = *(volatile int *)h->seg_pinned; h->seg_hint = std::max(h->seg_hint, seen); }
-    const bool graph = (use_graph & 1) && !h->profile && n_steps >= h->eager_below;
+    refresh_seg_hint(h);
+    const bool graph = (use_graph & 1) && !h->profile && n_steps >= h->knob.eager_below;
     const bool pipeline = !(use_graph & 2) && can_pipeline(h) && !decode_unpipelined(h) && n_steps > 1;
     return (graph ? HTM_PLAN_GRAPH : 0) | (pipeline ? HTM_PLAN_PIPELINED : 0) | (pipeline && can_lean(h) ? HTM_PLAN_LEAN : 0) |
            (scan_pool_is_large(h) ? HTM_PLAN_SCAN_LARGE : 0);
@@ -1791,16 +1826,16 @@ static int shard_enqueue_begin(htm_handle *h, const uint32_t *bank, int n_inputs
     // BITHTM_SHARD_WINDOW=0: two launched digits.  While another handle with a stream of its own is live on the device the
     // blocks of a grid must not wait for each other: every digit by a launch, the counts by k_sp_count -- same candidates)
     const int fused = h->emit_fused ? 1 : 0;
-    const int wmode = fused ? h->knob_shard_window : 0;
+    const int wmode = fused ? h->knob.shard_window : 0;
     if (front_done && h->shard_front_wmode != wmode) {       // the exchange mode changed since the front was computed: start over
         HIPCHK(h, hipMemsetAsync(d.hist0 + (size_t)p * HIST0_PAR, 0, (size_t)HIST0_PAR * 4, h->stream));
         front_done = false;
     }
-    if (!front_done) LAUNCH(h, "shard_overlap", k_shard_overlap, h->sp_blocks, RB, d, bank, n_inputs, h->G, p, wmode, 0);
+    if (!front_done) LAUNCH(h, "shard_overlap", k_shard_overlap, h->sz.sp_blocks, RB, d, bank, n_inputs, h->sz.G, p, wmode, 0);
     if (!wmode)
-        for (int pass = 1; pass < d.sel_passes; ++pass) LAUNCH(h, "sp_select", k_sel_pass, h->sel_blocks, RB, d, pass, p);
-    if (!fused) LAUNCH(h, "sp_count", k_sp_count, h->c256_blocks, 256, d, p);
-    LAUNCH(h, "shard_candidates", k_sp_emit, h->c256_blocks + std::min((d.C + 255) / 256, 64), 256, d, p, 1, fused, EMIT_LOCAL, wmode, h->c256_blocks);
+        for (int pass = 1; pass < d.sel_passes; ++pass) LAUNCH(h, "sp_select", k_sel_pass, h->sz.sel_blocks, RB, d, pass, p);
+    if (!fused) LAUNCH(h, "sp_count", k_sp_count, h->sz.c256_blocks, 256, d, p);
+    LAUNCH(h, "shard_candidates", k_sp_emit, h->sz.c256_blocks + std::min((d.C + 255) / 256, 64), 256, d, p, 1, fused, EMIT_LOCAL, wmode, h->sz.c256_blocks);
     return 0;
 }
 
@@ -1809,13 +1844,11 @@ static int shard_enqueue_finish(htm_handle *h, const uint32_t *bank, int n_input
     Dev &d = h->d;
     const int p = (int)(h->step_host & 1);
     LAUNCH(h, "shard_select", k_shard_select, h->world + 1, 1024, d, (const unsigned char *)recv_device, p);      // (+ 1: the death reports)
-    const int wmode = h->emit_fused ? h->knob_shard_window : 0;
+    const int wmode = h->emit_fused ? h->knob.shard_window : 0;
     enqueue_tm(h, d.k, learning, 1, p, bank, n_inputs, true, front_next ? wmode : -1);
     if (front_next) h->shard_front_wmode = wmode;
     h->step_host += 1;
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { h->err = std::string("kernel launch: ") + hipGetErrorString(e); return HTM_ERR_HIP; }
-    return 0;
+    return launch_status(h->err);
 }
 
 extern "C" int htm_shard_begin(htm_handle *h, const uint32_t *device_inputs, int32_t n_inputs, const uint32_t *packed_input,
@@ -2149,7 +2182,7 @@ static int shard_run(htm_handle *const *hs, int n, const uint32_t *const *banks,
         refresh_exchange_mode(h);
         int rc = ensure_shard_buffers(h);
         if (rc) return rc;
-        if (h->seg_pinned) { const int seen = *(volatile int *)h->seg_pinned; h->seg_hint = std::max(h->seg_hint, seen); }
+        refresh_seg_hint(h);
         if (h->profile) graph = false;
     }
     if (n == 1 && !h0->shard_graph_ok) graph = false;      // (this communicator's collective does not replay from a graph: the preflight said so)
@@ -2167,39 +2200,29 @@ static int shard_run(htm_handle *const *hs, int n, const uint32_t *const *banks,
             t += span;
             continue;
         }
-        std::vector<int> params{(int)(h0->step_host & 1) | learning << 1 | (fd ? 4 : 0) | (fn ? 8 : 0) | span << 4, n, n_inputs};
-        for (int r = 0; r < n; ++r) {         // what the launches of a rank depend on besides its arguments
-            params.push_back(scan_spec_blocks(hs[r]));
-            params.push_back((scan_pool_is_large(hs[r]) ? 1 : 0) | (hs[r]->emit_fused ? 2 : 0));
-        }
-        auto key = std::make_pair(params, (const void *)banks[0]);
-        auto it = h0->shard_graphs.find(key);
-        if (it == h0->shard_graphs.end()) {
+        ShardGraphKey key{(int)(h0->step_host & 1), learning, fd, fn, span, n, n_inputs, {}, banks[0]};
+        for (int r = 0; r < n; ++r)             // what the launches of a rank depend on besides its arguments
+            key.per_rank.emplace_back(scan_spec_blocks(hs[r]), scan_pool_is_large(hs[r]), hs[r]->emit_fused);
+        const hipGraphExec_t exec = cached_graph(h0->shard_graphs, key, h0->stream, h0->err, [&] {
             std::vector<long long> saved((size_t)n);
             for (int r = 0; r < n; ++r) saved[(size_t)r] = hs[r]->step_host;
-            hipGraph_t graph_obj = nullptr;
-            hipError_t e = hipStreamBeginCapture(h0->stream, hipStreamCaptureModeThreadLocal);
-            int rc = e == hipSuccess ? shard_enqueue_steps(hs, n, banks, n_inputs, learning, span, fd, fn) : HTM_ERR_HIP;
-            hipError_t e2 = e == hipSuccess ? hipStreamEndCapture(h0->stream, &graph_obj) : e;
+            const int rc = shard_enqueue_steps(hs, n, banks, n_inputs, learning, span, fd, fn);
             for (int r = 0; r < n; ++r) hs[r]->step_host = saved[(size_t)r];      // (captured, not run)
-            hipGraphExec_t exec = nullptr;
-            if (rc == 0 && e2 == hipSuccess && graph_obj && hipGraphInstantiate(&exec, graph_obj, nullptr, nullptr, 0) != hipSuccess) exec = nullptr;
-            if (graph_obj) hipGraphDestroy(graph_obj);
-            if (!exec) {                            // (a collective that cannot be captured on this runtime: launch eagerly from here on)
-                (void)hipGetLastError();
-                graph = false;
-                h0->err.clear();
-                continue;
-            }
-            it = h0->shard_graphs.emplace(key, exec).first;
+            return rc;
+        });
+        if (!exec) {                                // (a collective that cannot be captured on this runtime: launch eagerly from here on)
+            (void)hipGetLastError();
+            graph = false;
+            h0->err.clear();
+            continue;
         }
-        HIPCHK(h0, hipGraphLaunch(it->second, h0->stream));
+        HIPCHK(h0, hipGraphLaunch(exec, h0->stream));
         for (int r = 0; r < n; ++r) hs[r]->step_host += span;
         t += span;
     }
     if (n_steps > 0)
         for (int r = 0; r < n; ++r)
-            if (hs[r]->seg_pinned) HIPCHK(hs[r], hipMemcpyAsync(hs[r]->seg_pinned, &hs[r]->d.ctr->L, sizeof(int), hipMemcpyDeviceToHost, hs[r]->stream));
+            HIPCHK(hs[r], hand_back_segments(hs[r], &hs[r]->d.ctr->L, hs[r]->stream));
     return HTM_OK;
 }
 
@@ -2251,7 +2274,7 @@ extern "C" int htm_populate(htm_handle *h, int64_t cell_begin, int64_t cell_end,
     const int64_t own = std::max<int64_t>(own_hi - own_lo, 0) * segments_per_cell;
     if (total > d.Scap || own > d.Lcap) { h->err = "htm_populate: pool too small (segment_capacity / segment_capacity_local)"; return HTM_ERR_CAPACITY; }
     if (own > 0) {
-        const int64_t blocks = std::min<int64_t>((own + 3) / 4, (int64_t)h->cus * 64);
+        const int64_t blocks = std::min<int64_t>((own + 3) / 4, (int64_t)h->sz.cus * 64);
         hipLaunchKernelGGL(k_tm_populate, dim3((unsigned)blocks), dim3(256), 0, h->stream, d, (long long)cell_begin, (long long)own_lo, (long long)own,
                            segments_per_cell, synapses, perm_lo, perm_hi, seed);
     }
@@ -2760,8 +2783,8 @@ extern "C" int htm_import_commit(htm_handle *h, int32_t segments, int32_t matchi
         if (winner_cells > 0) hipLaunchKernelGGL(k_tm_winner_bits, dim3((winner_cells + 255) / 256), dim3(256), 0, h->stream, d, q, winner_cells);
         if (!keep) {
             if (h->world == 1) {                    // (a shard's counts came with its dead bits, above)
-                HIPCHK(h, hipMemsetAsync(d.recyc_cnt2, 0, ((size_t)(h->s1024_blocks + 1023) / 1024 + 1) * sizeof(int), h->stream));
-                hipLaunchKernelGGL(k_tm_recount, dim3(h->s1024_blocks), dim3(256), 0, h->stream, d);
+                HIPCHK(h, hipMemsetAsync(d.recyc_cnt2, 0, ((size_t)(h->sz.s1024_blocks + 1023) / 1024 + 1) * sizeof(int), h->stream));
+                hipLaunchKernelGGL(k_tm_recount, dim3(h->sz.s1024_blocks), dim3(256), 0, h->stream, d);
             }
             hipLaunchKernelGGL(k_tm_flag_connected, dim3(std::min(4096, std::max(1, (int)(((long long)rows * d.E + 255) / 256)))), dim3(256), 0, h->stream, d);
         }
@@ -2785,9 +2808,7 @@ extern "C" int htm_reset(htm_handle *h) {
     if (rc) return rc;
     LAUNCH(h, "tm_reset", k_tm_reset, reset_blocks(h->d), 256, h->d, (int)(h->step_host & 1), (const ResetDev *)nullptr, (RecDev *)nullptr,
            (uint32_t)h->step_host);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { h->err = std::string("kernel launch: ") + hipGetErrorString(e); return HTM_ERR_HIP; }
-    return HTM_OK;
+    return launch_status(h->err);
 }
 
 extern "C" int htm_set_run_resets(htm_handle *h, const uint32_t *device_bits, int32_t n_inputs) {
@@ -2828,8 +2849,8 @@ extern "C" int htm_predicted_input(htm_handle *h, int32_t *host_dst) {
     if (!h->d_pin_buf) { rc = dalloc(h, &h->d_pin_buf, d.I); if (rc) return rc; }
     HIPCHK(h, hipMemsetAsync(h->d_pin_buf, 0, (size_t)d.I * 4, h->stream));
     LAUNCH(h, "predicted_input", k_pin, pin_blocks(d.C), 256, d, (int)((h->step_host + 1) & 1), h->d_pin_buf);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { h->err = std::string("kernel launch: ") + hipGetErrorString(e); return HTM_ERR_HIP; }
+    rc = launch_status(h->err);
+    if (rc) return rc;
     HIPCHK(h, hipMemcpyAsync(host_dst, h->d_pin_buf, (size_t)d.I * 4, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return HTM_OK;
@@ -2886,6 +2907,13 @@ extern "C" int htm_profile_read(htm_handle *h, int32_t max_kernels, const char *
 // Model groups (htm_group.h): B members of one shape, every launch of a step covering all of them
 // (grid y = member).  The group enqueues on its first member's stream.
 
+// ... htm_group_run: the step's parity, the call's modes, the form of the group's launches (GroupForm), the span, the bank table
+struct GroupGraphKey {
+    int p; bool recording, decoding; int learning; bool fuse, large, shared; int spec, span; const void *bank_tab; int n_inputs;
+    auto tie() const { return std::tie(p, recording, decoding, learning, fuse, large, shared, spec, span, bank_tab, n_inputs); }
+    bool operator<(const GroupGraphKey &o) const { return tie() < o.tie(); }
+};
+
 struct htm_group {
     std::vector<htm_handle *> m;
     int n;
@@ -2904,8 +2932,7 @@ struct htm_group {
     std::map<std::vector<const uint32_t *>, const uint32_t **> bank_tabs;
     std::map<std::vector<const void *>, GrpRecArgs *> rec_tabs;
     std::map<std::vector<int32_t *>, int32_t **> pin_tabs;      // the members' decoding outputs (htm_set_run_predicted_input)
-    // graphs keyed by (parity + 2 if recorded + 4 if decoding, learning, tail form, spec, span, bank table, n_inputs)
-    std::map<std::tuple<int, int, int, int, int, const void *, int>, hipGraphExec_t> graphs;
+    std::map<GroupGraphKey, hipGraphExec_t> graphs;
     bool recording, decoding;
     // inference views (htm_create_view): some member is a view; every member aliases one set of weights (then the steps with
     // learning = 0 scan the store once per chunk of share_m members: kgrp_scan_shared, share_chunks x share_blocks blocks)
@@ -2957,9 +2984,9 @@ static const char *group_mismatch(const htm_handle *a, const htm_handle *b) {
     if (a->cfg.active_columns != b->cfg.active_columns) return "active_columns";
     if (a->cfg.segment_capacity != b->cfg.segment_capacity) return "segment_capacity";
     if (a->cfg.segment_slots != b->cfg.segment_slots) return "segment_slots";
-    if (a->G != b->G || a->sp_blocks != b->sp_blocks || a->sel_blocks != b->sel_blocks || a->c256_blocks != b->c256_blocks ||
-        a->scan_blocks != b->scan_blocks || a->zero_blocks != b->zero_blocks || a->lean_learn_blocks != b->lean_learn_blocks ||
-        a->lean_scan_blocks != b->lean_scan_blocks || a->sel_passes_full != b->sel_passes_full)
+    if (a->sz.G != b->sz.G || a->sz.sp_blocks != b->sz.sp_blocks || a->sz.sel_blocks != b->sz.sel_blocks || a->sz.c256_blocks != b->sz.c256_blocks ||
+        a->sz.scan_blocks != b->sz.scan_blocks || a->sz.zero_blocks != b->sz.zero_blocks || a->sz.lean_learn_blocks != b->sz.lean_learn_blocks ||
+        a->sz.lean_scan_blocks != b->sz.lean_scan_blocks || a->sz.sel_passes_full != b->sz.sel_passes_full)
         return "launch sizes (tuning knobs of the environment)";
     return nullptr;
 }
@@ -2988,27 +3015,21 @@ extern "C" int htm_group_create(htm_handle *const *members, int32_t n, htm_group
     g->n = n;
     g->device = h0->device;
     g->stream = h0->stream;
-    g->mixed = false;
     for (const htm_handle *h : g->m) g->mixed |= h->stream != g->stream;
-    g->d_tab = nullptr; g->d_recs = nullptr; g->d_pins = nullptr;
-    g->stage = nullptr; g->stage_tab = nullptr;
-    g->recording = g->decoding = false;
     auto fail = [&](int rc) { g_create_error = g->err; htm_group_destroy(g); return rc; };
     if (hipSetDevice(g->device) != hipSuccess) { g->err = "htm_group_create: hipSetDevice failed"; return fail(HTM_ERR_HIP); }
-    g->has_view = false;
     g->shared = true;
     for (const htm_handle *h : g->m) {
         g->has_view |= h->is_view;
         g->shared &= h->d.presyn == h0->d.presyn && h->d.perm == h0->d.perm;
     }
-    g->shared = g->shared && g->has_view && h0->knob_shared_scan;
-    g->share_m = g->share_chunks = g->share_blocks = 0;
+    g->shared = g->shared && g->has_view && h0->knob.shared_scan;
     if (g->shared) {
         // M: the members whose column bitmaps fit 64 KiB of LDS beside each other (at most GRP_SHARED_MMAX, and the knob's cap);
         // the grid: the blocks of that LDS size resident at once, at most one per 64 rows of the pool
         const size_t per = (size_t)h0->d.colwords * 4;
         int M = (int)std::min<size_t>(GRP_SHARED_MMAX, std::max<size_t>(1, (64 * 1024) / per));
-        if (h0->knob_shared_members > 0) M = std::min(M, h0->knob_shared_members);
+        if (h0->knob.shared_members > 0) M = std::min(M, h0->knob.shared_members);
         M = std::min(M, n);
         g->share_m = M;
         g->share_chunks = (n + M - 1) / M;
@@ -3017,7 +3038,7 @@ extern "C" int htm_group_create(htm_handle *const *members, int32_t n, htm_group
             (void)hipGetLastError();
             per_cu = 1;
         }
-        g->share_blocks = std::max(1, std::min(h0->scan_blocks, per_cu * h0->cus));
+        g->share_blocks = std::max(1, std::min(h0->sz.scan_blocks, per_cu * h0->sz.cus));
     }
     g->host_tab.resize(n);
     std::vector<RecDev *> recs(n);
@@ -3029,7 +3050,7 @@ extern "C" int htm_group_create(htm_handle *const *members, int32_t n, htm_group
         if (!h->d_pin && dalloc(h, &h->d_pin, 1)) { g->err = h->err; return fail(HTM_ERR_HIP); }
         if (hipStreamSynchronize(h->stream) != hipSuccess) { g->err = "htm_group_create: hipStreamSynchronize failed"; return fail(HTM_ERR_HIP); }
         g->host_tab[i] = h->d;
-        g->host_tab[i].sel_passes = h->sel_passes_full;
+        g->host_tab[i].sel_passes = h->sz.sel_passes_full;
         recs[i] = h->d_rec;
         pins[i] = h->d_pin;
     }
@@ -3077,18 +3098,22 @@ static GroupForm group_form(htm_group *g) {
     int lo = 1 << 30, hi = 0;
     for (int i = 0; i < g->n; ++i) {
         htm_handle *h = g->m[i];
-        if (h->seg_pinned) { const int own = *(volatile int *)h->seg_pinned; h->seg_hint = std::max(h->seg_hint, own); }
+        refresh_seg_hint(h);
         lo = std::min(lo, h->seg_hint);
         hi = std::max(hi, h->seg_hint);
     }
     const htm_handle *h0 = g->m[0];
     GroupForm f;
-    f.large = h0->knob_scan_large >= 0 ? h0->knob_scan_large != 0 : hi > h0->scan_large_above;
-    f.fuse = h0->knob_fuse_tm && !f.large && scan_lds(h0->d, 1) <= 64 * 1024;
-    f.spec = std::min(lo / SCAN_SEGS, h0->scan_blocks) & ~63;
+    f.large = h0->knob.scan_large >= 0 ? h0->knob.scan_large != 0 : hi > h0->knob.scan_large_above;
+    f.fuse = h0->knob.fuse_tm && !f.large && scan_lds(h0->d, 1) <= 64 * 1024;
+    f.spec = std::min(lo / SCAN_SEGS, h0->sz.scan_blocks) & ~63;
     f.shared = false;                               // (set by the caller for a step without learning)
     return f;
 }
+
+static decltype(&kgrp_learn<1>) const kt_grp_learn[4] = {kgrp_learn<1>, kgrp_learn<2>, kgrp_learn<4>, kgrp_learn<8>};
+static decltype(&kgrp_tail<1>) const kt_grp_tail[4] = {kgrp_tail<1>, kgrp_tail<2>, kgrp_tail<4>, kgrp_tail<8>};
+static decltype(&kgrp_scan<true, 1>) const kt_grp_scan[4] = {kgrp_scan<true, 1>, kgrp_scan<false, 1>, kgrp_scan<true, 6>, kgrp_scan<false, 6>};
 
 // one step of every member (parity p): the one-role-per-launch schedule of enqueue_rest, unfused (htm_group.h)
 static void group_enqueue_step(htm_group *g, const uint32_t *const *banks, int n_inputs, int learning, int p, const GroupForm &f) {
@@ -3097,53 +3122,32 @@ static void group_enqueue_step(htm_group *g, const uint32_t *const *banks, int n
     const hipStream_t s = g->stream;
     const int B = g->n;
     const Dev *tab = g->d_tab;
-    const dim3 g_sp(h->sp_blocks, B), g_sel(h->sel_blocks, B), g_256(h->c256_blocks, B);
-    LAUNCH_ON(h, s, 0, "group:sp_overlap", kgrp_overlap, g_sp, RB, tab, banks, n_inputs, h->G, p);
-    for (int pass = 1; pass < h->sel_passes_full; ++pass) LAUNCH_ON(h, s, 0, "group:sp_select", kgrp_select, g_sel, RB, tab, pass, p);
+    const dim3 g_sp(h->sz.sp_blocks, B), g_sel(h->sz.sel_blocks, B), g_256(h->sz.c256_blocks, B);
+    LAUNCH_ON(h, s, 0, "group:sp_overlap", kgrp_overlap, g_sp, RB, tab, banks, n_inputs, h->sz.G, p);
+    for (int pass = 1; pass < h->sz.sel_passes_full; ++pass) LAUNCH_ON(h, s, 0, "group:sp_select", kgrp_select, g_sel, RB, tab, pass, p);
     LAUNCH_ON(h, s, 0, "group:sp_count", kgrp_count, g_256, 256, tab, p);
     LAUNCH_ON(h, s, 0, "group:sp_emit", kgrp_emit, g_256, 256, tab, p);
     const int n_cls = learning ? kClassifyBlocks : 0, n_rows = learning ? d.k : 0;
     const int rows_mid = f.fuse ? 0 : n_rows, rows_tail = f.fuse ? n_rows : 0;
-    const dim3 g_mid(1 + n_cls + rows_mid + h->zero_blocks, B);
+    const dim3 g_mid(1 + n_cls + rows_mid + h->sz.zero_blocks, B);
     LAUNCH_ON(h, s, 0, "group:tm_mid", kgrp_middle, g_mid, 256, tab, p, learning, n_cls, banks, n_inputs, rows_mid);
     const int epl = learn_epl(d);
-    if (f.shared) {
-        // every member's learning role (with learning = 0: the previous scan's per-cell maxima cleared, nothing else), then ONE
-        // pass over the shared store for each chunk of share_m members (htm_group.h)
-        const dim3 g_learn(kLearnBlocks, B);
-        const size_t lds = learn_lds(epl);
-        switch (epl) {
-            case 1: LAUNCH_ON(h, s, lds, "group:tm_learn", kgrp_learn<1>, g_learn, RB, tab, p); break;
-            case 2: LAUNCH_ON(h, s, lds, "group:tm_learn", kgrp_learn<2>, g_learn, RB, tab, p); break;
-            case 4: LAUNCH_ON(h, s, lds, "group:tm_learn", kgrp_learn<4>, g_learn, RB, tab, p); break;
-            default: LAUNCH_ON(h, s, lds, "group:tm_learn", kgrp_learn<8>, g_learn, RB, tab, p); break;
-        }
-        const dim3 g_scan(g->share_blocks, g->share_chunks);
-        LAUNCH_ON(h, s, (size_t)g->share_m * d.colwords * 4, "group:tm_scan_shared", kgrp_scan_shared, g_scan, 256, tab, B, g->share_m, p);
-    } else if (f.fuse) {
+    if (f.fuse && !f.shared) {
         const size_t lds = std::max(learn_lds(epl, 256), scan_lds(d, 1));
-        const dim3 g_tail(h->lean_learn_blocks + h->lean_scan_blocks + rows_tail, B);
-        const char *name = rows_tail ? "group:tm_learn+tm_scan+sp_learn" : "group:tm_learn+tm_scan";
-#define LAUNCH_GT(E_) LAUNCH_ON(h, s, lds, name, kgrp_tail<E_>, g_tail, 256, tab, p, h->lean_learn_blocks, h->lean_scan_blocks, f.spec, banks, n_inputs)
-        switch (epl) { case 1: LAUNCH_GT(1); break; case 2: LAUNCH_GT(2); break; case 4: LAUNCH_GT(4); break; default: LAUNCH_GT(8); break; }
-#undef LAUNCH_GT
+        const dim3 g_tail(h->sz.lean_learn_blocks + h->sz.lean_scan_blocks + rows_tail, B);
+        LAUNCH_ON(h, s, lds, rows_tail ? "group:tm_learn+tm_scan+sp_learn" : "group:tm_learn+tm_scan", kt_grp_tail[epl_slot(d)], g_tail, 256, tab, p,
+                  h->sz.lean_learn_blocks, h->sz.lean_scan_blocks, f.spec, banks, n_inputs);
     } else {
-        const size_t lds = learn_lds(epl);
-        const dim3 g_learn(kLearnBlocks, B), g_scan(h->scan_blocks, B);
-        switch (epl) {
-            case 1: LAUNCH_ON(h, s, lds, "group:tm_learn", kgrp_learn<1>, g_learn, RB, tab, p); break;
-            case 2: LAUNCH_ON(h, s, lds, "group:tm_learn", kgrp_learn<2>, g_learn, RB, tab, p); break;
-            case 4: LAUNCH_ON(h, s, lds, "group:tm_learn", kgrp_learn<4>, g_learn, RB, tab, p); break;
-            default: LAUNCH_ON(h, s, lds, "group:tm_learn", kgrp_learn<8>, g_learn, RB, tab, p); break;
-        }
-        const bool use_lds = scan_lds(d, 1) <= 64 * 1024;
-        const char *name = f.large ? "group:tm_scan_large" : "group:tm_scan";
-        if (f.large) {
-            if (use_lds) LAUNCH_ON(h, s, scan_lds(d, 1), name, (kgrp_scan<true, 1>), g_scan, 256, tab, p, f.spec);
-            else LAUNCH_ON(h, s, scan_lds(d, 0), name, (kgrp_scan<false, 1>), g_scan, 256, tab, p, f.spec);
+        // (f.shared: every member's learning role -- with learning = 0 the previous scan's per-cell maxima cleared, nothing else --
+        // then ONE pass over the shared store for each chunk of share_m members: htm_group.h)
+        LAUNCH_ON(h, s, learn_lds(epl), "group:tm_learn", kt_grp_learn[epl_slot(d)], dim3(kLearnBlocks, B), RB, tab, p);
+        if (f.shared) {
+            LAUNCH_ON(h, s, (size_t)g->share_m * d.colwords * 4, "group:tm_scan_shared", kgrp_scan_shared, dim3(g->share_blocks, g->share_chunks), 256, tab, B,
+                      g->share_m, p);
         } else {
-            if (use_lds) LAUNCH_ON(h, s, scan_lds(d, 1), name, (kgrp_scan<true, 6>), g_scan, 256, tab, p, f.spec);
-            else LAUNCH_ON(h, s, scan_lds(d, 0), name, (kgrp_scan<false, 6>), g_scan, 256, tab, p, f.spec);
+            const bool use_lds = scan_lds(d, 1) <= 64 * 1024;
+            LAUNCH_ON(h, s, scan_lds(d, use_lds), f.large ? "group:tm_scan_large" : "group:tm_scan", kt_grp_scan[scan_slot(f.large, use_lds)], dim3(h->sz.scan_blocks, B), 256,
+                      tab, p, f.spec);
         }
     }
     if (g->recording) {
@@ -3241,8 +3245,8 @@ static int group_run(htm_group *g, const uint32_t **bank_tab, int n_inputs, int 
     }
     GroupForm f = group_form(g);
     f.shared = g->shared && !learning;
-    const bool graph = (use_graph & 1) && !h0->profile && n_steps >= h0->eager_below;
-    const int span_max = h0->graph_steps;
+    const bool graph = (use_graph & 1) && !h0->profile && n_steps >= h0->knob.eager_below;
+    const int span_max = h0->knob.graph_steps;
     int p = (int)(h0->step_host & 1);
     for (int t = 0; t < n_steps;) {
         if (!graph) {
@@ -3252,21 +3256,13 @@ static int group_run(htm_group *g, const uint32_t **bank_tab, int n_inputs, int 
             continue;
         }
         const int span = n_steps - t >= span_max ? span_max : 1;
-        auto key = std::make_tuple(p + (g->recording ? 2 : 0) + (g->decoding ? 4 : 0), learning, (f.fuse ? 1 : 0) + (f.large ? 2 : 0) + (f.shared ? 4 : 0), f.spec, span,
-                                   (const void *)bank_tab, n_inputs);
-        auto it = g->graphs.find(key);
-        if (it == g->graphs.end()) {
-            hipGraph_t graph_obj;
-            GHIPCHK(g, hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
+        const GroupGraphKey key{p, g->recording, g->decoding, learning, f.fuse, f.large, f.shared, f.spec, span, bank_tab, n_inputs};
+        const hipGraphExec_t exec = cached_graph(g->graphs, key, s, g->err, [&] {
             for (int i = 0; i < span; ++i) group_enqueue_step(g, bank_tab, n_inputs, learning, (p + i) & 1, f);
-            hipError_t e = hipStreamEndCapture(s, &graph_obj);
-            if (e != hipSuccess) { g->err = std::string("hipStreamEndCapture: ") + hipGetErrorString(e); return HTM_ERR_HIP; }
-            hipGraphExec_t exec;
-            GHIPCHK(g, hipGraphInstantiate(&exec, graph_obj, nullptr, nullptr, 0));
-            hipGraphDestroy(graph_obj);
-            it = g->graphs.emplace(key, exec).first;
-        }
-        GHIPCHK(g, hipGraphLaunch(it->second, s));
+            return 0;
+        });
+        if (!exec) return HTM_ERR_HIP;
+        GHIPCHK(g, hipGraphLaunch(exec, s));
         p ^= span & 1;
         t += span;
     }
@@ -3275,11 +3271,10 @@ static int group_run(htm_group *g, const uint32_t **bank_tab, int n_inputs, int 
         h->window_known = true;                   // (every select leaves the next step's window behind)
         if (learning) weights_touched(h);
     }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { g->err = std::string("kernel launch: ") + hipGetErrorString(e); return HTM_ERR_HIP; }
+    const int rc = launch_status(g->err);
+    if (rc) return rc;
     // leave each member's segment count where its next call -- group or solo -- finds it, as htm_run does (no wait)
-    for (htm_handle *h : g->m)
-        if (h->seg_pinned) GHIPCHK(g, hipMemcpyAsync(h->seg_pinned, &h->d.ctr->S, sizeof(int), hipMemcpyDeviceToHost, s));
+    for (htm_handle *h : g->m) GHIPCHK(g, hand_back_segments(h, &h->d.ctr->S, s));
     if (g->mixed) GHIPCHK(g, hipStreamSynchronize(s));
     return HTM_OK;
 }

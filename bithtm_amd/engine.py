@@ -388,13 +388,8 @@ class Engine:
         if unknown or not fields:
             raise ValueError(f"record: fields from {RECORD_FIELDS}, at least one (got {fields})")
         n = int(n_steps)
-        shapes = self.record_shapes()
-        ptrs = {f: self._record_buffer(f, max(n, 1) * shapes[f][0]) for f in fields}
         rec = L.HtmRunRecord()
-        rec.struct_bytes = C.sizeof(L.HtmRunRecord)
-        rec.records, rec.active_column, rec.column_prediction = (ptrs.get(f) for f in RECORD_FIELDS[:3])
-        if "predicted_input" in fields:
-            self.set_run_predicted_input(ptrs["predicted_input"])
+        shapes = self._record_args(fields, n, rec)
         try:
             if fields == ("predicted_input",):
                 self._check(self.lib.htm_run(self.h, C.c_void_p(device_bank), int(n_inputs), n, int(bool(learning)), flags), "htm_run")
@@ -407,6 +402,17 @@ class Engine:
         self.steps += n_steps
         self.sync()                                 # (the records are written on the engine's stream)
         return {f: self._record_read(f, n * shapes[f][0], shapes[f][1]).reshape(n, shapes[f][0]) for f in fields}
+
+    def _record_args(self, fields, n, rec):
+        """The record buffers of n steps for `fields` into `rec` (an HtmRunRecord) and, for "predicted_input", the decoding rows
+        (set_run_predicted_input: the caller clears them) -> record_shapes()."""
+        shapes = self.record_shapes()
+        ptrs = {f: self._record_buffer(f, max(n, 1) * shapes[f][0]) for f in fields}
+        rec.struct_bytes = C.sizeof(L.HtmRunRecord)
+        rec.records, rec.active_column, rec.column_prediction = (ptrs.get(f) for f in RECORD_FIELDS[:3])
+        if "predicted_input" in fields:
+            self.set_run_predicted_input(ptrs["predicted_input"])
+        return shapes
 
     def record_shapes(self):
         """{record field: (int32 words per step, dtype)} of this engine's shape."""

@@ -20,7 +20,7 @@ import numpy as np
 
 from . import _lib as L
 from .engine import HtmError, pack_bits
-from .networks import (HierarchicalTemporalMemory, InferenceView, RunRecord, _grow_if_needed, _join_record, _record_fields,
+from .networks import (HierarchicalTemporalMemory, InferenceView, RunRecord, _cached_bank, _grow_if_needed, _join_record, _record_fields,
                        retire_states)
 
 
@@ -181,13 +181,7 @@ class ModelGroup:
         recs = (L.HtmRunRecord * len(self.models))()
         shapes = {}
         for i, m in enumerate(self.models):
-            e = m.engine
-            shapes = e.record_shapes()
-            ptrs = {f: e._record_buffer(f, max(n, 1) * shapes[f][0]) for f in fields}
-            recs[i].struct_bytes = C.sizeof(L.HtmRunRecord)
-            recs[i].records, recs[i].active_column, recs[i].column_prediction = (ptrs.get(f) for f in ("counters", "active_column", "column_prediction"))
-            if "predicted_input" in fields:
-                e.set_run_predicted_input(ptrs["predicted_input"])
+            shapes = m.engine._record_args(fields, n, recs[i])
         return (None if fields == ("predicted_input",) else recs), shapes
 
     def _unset_votes(self):
@@ -203,13 +197,7 @@ class ModelGroup:
 
     def _banks(self, inputs):
         """Each member's device bank of its rows of `inputs`, uploaded once and cached as run() caches it."""
-        ptrs = []
-        for m, x in zip(self.models, inputs):
-            key = (x.shape, x.tobytes())
-            bank = getattr(m, "_bank", None)
-            if bank is None or bank[0] != key:
-                m._bank = bank = (key, m.engine.upload_bank(x))
-            ptrs.append(bank[1])
+        ptrs = [_cached_bank(m, m.engine, x) for m, x in zip(self.models, inputs)]
         return (C.c_void_p * len(ptrs))(*ptrs)
 
     def run(self, inputs, steps, learning=None, use_graph=True, record=None, resets=None):

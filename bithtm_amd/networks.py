@@ -676,10 +676,7 @@ class HierarchicalTemporalMemory:
         fields = None if record is None else _record_fields(record)
         retire_states(eng)
         inputs = np.asarray(inputs, dtype=np.bool_)
-        key = (inputs.shape, inputs.tobytes())
-        bank = getattr(self, "_bank", None)
-        if bank is None or bank[0] != key:
-            self._bank = bank = (key, eng.upload_bank(inputs))
+        bank = _cached_bank(self, eng, inputs)
         if resets is not None:
             resets = np.asarray(resets, dtype=np.bool_).ravel()
             if resets.shape != (inputs.shape[0],):
@@ -697,11 +694,11 @@ class HierarchicalTemporalMemory:
                         raise RuntimeError("the segment pool has to grow in the middle of a streamed run(): end the stream (a run() without continuing=True) first")
                     self.grow_pool(*eng._grow_to)
                     eng = self._engine
-                    self._bank = bank = (key, eng.upload_bank(inputs))
+                    bank = _cached_bank(self, eng, inputs, fresh=True)
                     _grow_if_needed(eng, 2 * k, force_check=True)
                 n = max(1, min(n, eng._free_segments // (2 * k) - 1))
             last = done + n >= steps
-            part = eng.run(bank[1], inputs.shape[0], n, learning=learning, use_graph=use_graph, pipeline=pipeline,
+            part = eng.run(bank, inputs.shape[0], n, learning=learning, use_graph=use_graph, pipeline=pipeline,
                            continuing=continuing and last, record=fields,
                            resets=None if resets is None else eng.upload_resets(resets))
             if fields is not None:
@@ -820,6 +817,16 @@ class InferenceView(HierarchicalTemporalMemory):
 
     def grow_pool(self, segment_capacity=None, segment_slots=None):
         raise ValueError("grow_pool() on an inference view: its pool is its parent's; grow the parent and make new views")
+
+
+def _cached_bank(owner, eng, inputs, fresh=False):
+    """The device bank of `inputs` (bool [n, input_dim]) on `eng`: uploaded once and kept on `owner` until the inputs change
+    (fresh: uploaded again -- a new engine)."""
+    key = (inputs.shape, inputs.tobytes())
+    bank = getattr(owner, "_bank", None)
+    if fresh or bank is None or bank[0] != key:
+        owner._bank = bank = (key, eng.upload_bank(inputs))
+    return bank[1]
 
 
 def _join_record(parts, fields, first_step, steps, k, column_dim, input_dim=0):
