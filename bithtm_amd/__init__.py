@@ -11,6 +11,7 @@ from . import networks
 from .networks import InferenceView  # noqa: F401
 from .engine import CapacityError, HtmError  # noqa: F401
 from .group import ModelGroup  # noqa: F401
+from .stack import RegionStack  # noqa: F401
 from .projections import DenseProjection, PredictiveProjection  # noqa: F401
 from .regularizations import ExponentialBoosting, GlobalInhibition  # noqa: F401
 

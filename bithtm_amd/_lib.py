@@ -115,6 +115,7 @@ EXPORTS = {
     "htm_group_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(HtmRunRecord)]),
     "htm_create_view": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p)]),
     "htm_device_bytes": (C.c_int64, [C.c_void_p]),
+    "htm_pack_columns": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int32]),
 }
 
 # The HIP runtime calls the binding makes itself -- the device buffers of run(record=...) -- resolved through the library's own

@@ -40,6 +40,7 @@
 #include "htm_record.h"
 #include "htm_reset.h"
 #include "htm_decode.h"
+#include "htm_stack.h"
 #include "htm_group.h"
 
 // ------------------------------------------------------------------------------------------
@@ -2349,7 +2350,8 @@ extern "C" int htm_get_info(htm_handle *h, htm_info *out) {
                  ((c.error & 2) ? " synapse slots (segment_slots)" : "") + ((c.error & 4) ? " work list / growth staging" : "") +
                  ((c.error & 8) ? " dead-segment report (DEAD_CAP)" : "") +
                  ((c.error & 16) ? " (internal) block hand-off timed out in k_sp_emit" : "") +
-                 ((c.error & 32) ? " (internal) the middle role's wait for the activation blocks timed out in k_act_mid_rows" : "");
+                 ((c.error & 32) ? " (internal) the middle role's wait for the activation blocks timed out in k_act_mid_rows" : "") +
+                 ((c.error & 64) ? " (not a capacity) htm_pack_columns met a column id outside this handle's input range" : "");
         return HTM_ERR_CAPACITY;          // *out is filled in all the same
     }
     return HTM_OK;
@@ -2854,6 +2856,26 @@ extern "C" int htm_predicted_input(htm_handle *h, int32_t *host_dst) {
     HIPCHK(h, hipMemcpyAsync(host_dst, h->d_pin_buf, (size_t)d.I * 4, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return HTM_OK;
+}
+
+// Region stacks (htm_stack.h): bank rows for h from the active-column lists a lower region's recorded run left on the device
+extern "C" int htm_pack_columns(htm_handle *h, const int32_t *device_lists, int32_t k, int32_t n_rows, int32_t stride,
+                                uint32_t *device_bank, int32_t bank_rows, int32_t first_row) {
+    if (!h || !device_lists || !device_bank) return HTM_ERR_ARGUMENT;
+    if (k < 1 || stride < 1 || n_rows < 0 || bank_rows < 1 || first_row < 0 || first_row >= bank_rows) {
+        h->err = "htm_pack_columns: k >= 1, stride >= 1, n_rows >= 0, bank_rows >= 1 and 0 <= first_row < bank_rows";
+        return HTM_ERR_ARGUMENT;
+    }
+    if (((uintptr_t)device_bank & 15) != 0) { h->err = "htm_pack_columns: the bank must be 16-byte aligned"; return HTM_ERR_ARGUMENT; }
+    if (!h->cfg.enable_sp) { h->err = "htm_pack_columns: needs a handle with the device's own Spatial Pooler (its input rows are packed)"; return HTM_ERR_STATE; }
+    if (h->world > 1) { h->err = "htm_pack_columns: not available on a column-sharded handle"; return HTM_ERR_STATE; }
+    REJECT_WHEN_AHEAD(h);
+    if (pack_lds(h->d) > PACK_LDS_MAX) { h->err = "htm_pack_columns: an input row of this handle does not fit the LDS (input_dim above 524288)"; return HTM_ERR_ARGUMENT; }
+    if (n_rows == 0) return HTM_OK;
+    HIPCHK(h, hipSetDevice(h->device));
+    LAUNCH_ON(h, h->stream, pack_lds(h->d), "pack_columns", k_pack_columns, n_rows, PACK_THREADS, h->d, device_lists, k, stride, device_bank,
+              bank_rows, first_row);
+    return launch_status(h->err);
 }
 
 extern "C" int htm_profile(htm_handle *h, int32_t enable) {

@@ -377,42 +377,57 @@ class Engine:
         returns {field: numpy array over the n_steps steps} -- "counters" int32[n, 8] (htm_step_record, RECORD_COUNTERS order),
         "active_column" int32[n, k], "column_prediction" uint32[n, ceil(C / 32)], "predicted_input" int32[n, input_dim] (the
         votes of htm_set_run_predicted_input, set for this call only) -- read back after one synchronisation."""
-        flags = (1 if use_graph else 0) | (0 if pipeline else 2) | (4 if continuing else 0)
         if record is None:
-            self._check(self.lib.htm_run(self.h, C.c_void_p(device_bank), int(n_inputs), int(n_steps), int(bool(learning)),
-                                         flags), "htm_run")
-            self.steps += n_steps
+            self.run_into(device_bank, n_inputs, n_steps, {}, learning, use_graph, pipeline, continuing)
             return None
         fields = tuple(record)
         unknown = set(fields) - set(RECORD_FIELDS)
         if unknown or not fields:
             raise ValueError(f"record: fields from {RECORD_FIELDS}, at least one (got {fields})")
         n = int(n_steps)
+        shapes = self.record_shapes()
+        self.run_into(device_bank, n_inputs, n, {f: self._record_buffer(f, max(n, 1) * shapes[f][0]) for f in fields}, learning, use_graph,
+                      pipeline, continuing)
+        self.sync()                                 # (the records are written on the engine's stream)
+        return {f: self._record_read(f, n * shapes[f][0], shapes[f][1]).reshape(n, shapes[f][0]) for f in fields}
+
+    def run_into(self, device_bank, n_inputs, n_steps, buffers, learning=True, use_graph=True, pipeline=True, continuing=False):
+        """The run of _run, enqueued only: `buffers` = {record field: device address of its n_steps rows} (record_shapes() words
+        per row; empty: a plain htm_run).  The records stay on the device: nothing is synchronised and nothing read back -- the
+        caller orders its own work behind the engine's stream (region stacks feed "active_column" to htm_pack_columns)."""
+        flags = (1 if use_graph else 0) | (0 if pipeline else 2) | (4 if continuing else 0)
+        n = int(n_steps)
         rec = L.HtmRunRecord()
-        shapes = self._record_args(fields, n, rec)
+        self._record_ptrs(buffers, rec)
         try:
-            if fields == ("predicted_input",):
+            if not set(buffers) - {"predicted_input"}:
                 self._check(self.lib.htm_run(self.h, C.c_void_p(device_bank), int(n_inputs), n, int(bool(learning)), flags), "htm_run")
             else:
                 self._check(self.lib.htm_run_recorded(self.h, C.c_void_p(device_bank), int(n_inputs), n, int(bool(learning)), flags,
                                                       C.byref(rec)), "htm_run_recorded")
         finally:
-            if "predicted_input" in fields:
+            if "predicted_input" in buffers:
                 self.set_run_predicted_input(None)
-        self.steps += n_steps
-        self.sync()                                 # (the records are written on the engine's stream)
-        return {f: self._record_read(f, n * shapes[f][0], shapes[f][1]).reshape(n, shapes[f][0]) for f in fields}
+        self.steps += n
+
+    def pack_columns(self, device_lists, k, n_rows, stride, device_bank, bank_rows, first_row):
+        """Bank rows of this engine from recorded active-column lists (htm_pack_columns): enqueued on its stream, no wait."""
+        self._check(self.lib.htm_pack_columns(self.h, C.c_void_p(device_lists), int(k), int(n_rows), int(stride), C.c_void_p(device_bank),
+                                              int(bank_rows), int(first_row)), "htm_pack_columns")
 
     def _record_args(self, fields, n, rec):
         """The record buffers of n steps for `fields` into `rec` (an HtmRunRecord) and, for "predicted_input", the decoding rows
         (set_run_predicted_input: the caller clears them) -> record_shapes()."""
         shapes = self.record_shapes()
-        ptrs = {f: self._record_buffer(f, max(n, 1) * shapes[f][0]) for f in fields}
+        self._record_ptrs({f: self._record_buffer(f, max(n, 1) * shapes[f][0]) for f in fields}, rec)
+        return shapes
+
+    def _record_ptrs(self, ptrs, rec):
+        """{field: device address} into `rec`; "predicted_input": the decoding rows are set (the caller clears them)."""
         rec.struct_bytes = C.sizeof(L.HtmRunRecord)
         rec.records, rec.active_column, rec.column_prediction = (ptrs.get(f) for f in RECORD_FIELDS[:3])
-        if "predicted_input" in fields:
+        if "predicted_input" in ptrs:
             self.set_run_predicted_input(ptrs["predicted_input"])
-        return shapes
 
     def record_shapes(self):
         """{record field: (int32 words per step, dtype)} of this engine's shape."""

@@ -1,0 +1,362 @@
+"""Region stacks: regions on top of each other, each reading the active columns of the one below (DESIGN.md section 14;
+include/bithtm_hip.h, htm_pack_columns).
+
+In reference terms a stack of L levels is L HierarchicalTemporalMemory objects with input_dim[l + 1] == column_dim[l].  Level 0
+steps on every input; level l + 1 makes its step u after level l has finished its steps u * s_l .. (u + 1) * s_l - 1 (s_l: the
+link's stride, default 1), on the bool vector with a bit for every column in sp_state.active_column of any step of that window.
+Level l draws with seed + l.  Nothing flows downwards.
+
+    stack = RegionStack(1000, [(65536, 32), (8192, 32)], strides=[4])
+    stack.run(inputs, 2000)                       # the device path: no host work between the levels
+    sp1, tm1 = stack.process(x)[1] or (None, None)  # the reference's loop, through the host: None in the middle of a window
+    stack.levels[1].predicted_input()             # the levels stay ordinary models for reading
+"""
+
+import ctypes as C
+import os
+
+import numpy as np
+
+from . import _lib as L
+from .group import SharedStream
+from .networks import HierarchicalTemporalMemory, InferenceView, _cached_bank, _grow_if_needed, _join_record, _record_fields, retire_states
+
+CHUNK_STEPS = 2048              # level-0 steps per chunk of run() (BITHTM_STACK_CHUNK; rounded down to a multiple of the strides' product)
+
+
+def _refuse_level(i, m):
+    """Why model i cannot be a level of a stack (ValueError), or None."""
+    if isinstance(m, InferenceView):
+        return f"level {i} is an inference view (a stack's levels learn; stacks of views are not available)"
+    if not isinstance(m, HierarchicalTemporalMemory):
+        return f"level {i} is a {type(m).__name__}, not a HierarchicalTemporalMemory (column-sharded models cannot be stacked)"
+    if getattr(m.temporal_memory, "cell_dim", m.cell_dim) > 64 or m.cell_dim > 64:
+        return f"level {i} has cell_dim {m.cell_dim} > 64: its Temporal Memory steps on the host"
+    if m.engine is None or not getattr(m.spatial_pooler, "_plain", False):
+        return f"level {i} has a layer, a distal projection or plug-in objects that live on the host"
+    if m.engine.shard_world > 1:
+        return f"level {i} is column-sharded"
+    if getattr(m, "_streaming", False):
+        return f"level {i} is in the middle of a streamed run() (continuing=True): end the stream first"
+    return None
+
+
+def _check_strides(strides, links):
+    strides = [1] * links if strides is None else [int(s) for s in strides]
+    if len(strides) != links or any(s < 1 for s in strides):
+        raise ValueError(f"strides: {links} integers >= 1 (one per link between two levels), got {strides}")
+    return strides
+
+
+class RegionStack:
+    """L fused HierarchicalTemporalMemory models chained through their active columns (see the module's docstring).  `levels`:
+    a list of (column_dim, cell_dim) or (column_dim, cell_dim, active_columns), bottom first; `strides`: one per link.  All
+    levels enqueue on ONE stream (so each keeps its fastest schedule, and the device path needs no events between them)."""
+
+    def __init__(self, input_dim, levels, strides=None, seed=0, device=0):
+        levels = [tuple(int(v) for v in lv) for lv in levels]
+        if not levels or any(len(lv) not in (2, 3) for lv in levels):
+            raise ValueError("levels: a non-empty list of (column_dim, cell_dim) or (column_dim, cell_dim, active_columns)")
+        strides = _check_strides(strides, len(levels) - 1)
+        for i, lv in enumerate(levels):
+            if lv[0] < 1 or lv[1] < 1 or (len(lv) == 3 and not 1 <= lv[2] <= lv[0]):
+                raise ValueError(f"level {i}: column_dim and cell_dim >= 1, 1 <= active_columns <= column_dim (got {lv})")
+            if lv[1] > 64:
+                raise ValueError(f"level {i} has cell_dim {lv[1]} > 64: its Temporal Memory steps on the host")
+        if int(input_dim) < 1:
+            raise ValueError(f"input_dim must be at least 1 (got {input_dim})")
+        stream = SharedStream(device)
+        models, below = [], int(input_dim)
+        for i, lv in enumerate(levels):
+            models.append(HierarchicalTemporalMemory(below, lv[0], lv[1], active_columns=lv[2] if len(lv) == 3 else None,
+                                                     seed=int(seed) + i, device=device, stream=stream))
+            below = lv[0]
+        self._setup(models, strides)
+
+    @classmethod
+    def of(cls, models, strides=None):
+        """A stack over existing fused models, bottom first.  ValueError if the dims do not chain (input_dim of a level is not
+        the column_dim of the one below), if a model has plug-in objects on the host, cell_dim above 64, is column-sharded, an
+        inference view or in a streamed run, or if the models do not share one stream (ModelGroup.create and
+        HierarchicalTemporalMemory(stream=) make models that do)."""
+        models = list(models)
+        if not models:
+            raise ValueError("a region stack needs at least one level")
+        strides = _check_strides(strides, len(models) - 1)
+        for i in range(1, len(models)):
+            lower = getattr(models[i - 1], "column_dim", None)
+            upper = getattr(getattr(models[i], "spatial_pooler", None), "input_dim", None)
+            if lower is not None and upper is not None and lower != upper:
+                raise ValueError(f"level {i}: input_dim {upper} is not level {i - 1}'s column_dim {lower}")
+        for i, m in enumerate(models):
+            why = _refuse_level(i, m)
+            if why:
+                raise ValueError(why)
+            if any(models[j] is m for j in range(i)):
+                raise ValueError(f"level {i} is a lower level again")
+        for i in range(1, len(models)):
+            if models[i].engine.input_dim != models[i - 1].column_dim:
+                raise ValueError(f"level {i}: input_dim {models[i].engine.input_dim} is not level {i - 1}'s column_dim {models[i - 1].column_dim}")
+        s0 = models[0].engine.stream_handle()
+        for i, m in enumerate(models):
+            if m.engine.stream_handle() != s0 or m.engine.device != models[0].engine.device:
+                raise ValueError(f"level {i} enqueues on another stream than level 0: create the models on one stream "
+                                 "(HierarchicalTemporalMemory(stream=...), ModelGroup.create)")
+        self = cls.__new__(cls)
+        self._setup(models, strides)
+        return self
+
+    def _setup(self, models, strides):
+        self.levels = models
+        self.strides = list(strides)
+        self._period = [1]                          # level-0 steps per step of level l
+        for s in self.strides:
+            self._period.append(self._period[-1] * s)
+        self._S = self._period[-1]
+        self._steps = 0                             # the stack's own step counter: windows are counted from it, nothing resets it
+        self._window = [np.zeros(m.column_dim, dtype=np.bool_) for m in models[:-1]]     # process(): the open window of each link
+        self.chunk_steps = int(os.environ.get("BITHTM_STACK_CHUNK", CHUNK_STEPS))
+        self.lib = L.load()
+        self._bufs = {}                             # run(): device buffers {(level, name): (address, 32-bit words)}
+        self.last_run_chunks = []                   # run(), diagnostic: (level-0 steps, graph_count() of every level) after each chunk
+
+    def __len__(self):
+        return len(self.levels)
+
+    def __del__(self):
+        bufs, self._bufs = getattr(self, "_bufs", {}), {}
+        if bufs:
+            for m in getattr(self, "levels", []):
+                if m.engine is not None and m.engine.h:
+                    m.engine.sync()
+            for ptr, _ in bufs.values():
+                self.lib.hipFree(ptr)
+
+    @property
+    def steps(self):
+        """Inputs the stack has processed (process() calls and run() steps)."""
+        return self._steps
+
+    # ---- the reference's loop
+    def process(self, x, learning=True):
+        """One input: level 0 steps, and every upper level whose window this step completes.  Returns a list with one entry per
+        level: (sp_state, tm_state) for the levels that stepped, None for the levels in the middle of a window.
+
+        This is the reference's own loop and it goes through the host between the levels: it reads each level's active columns
+        back, ORs them into a host accumulator and calls the next level's process().  It is the convenience path and the
+        parity yardstick of run(), not the fast path: run() keeps the whole loop on the device."""
+        self._check_levels()
+        out = [None] * len(self.levels)
+        for l, m in enumerate(self.levels):
+            out[l] = m.process(x, learning=learning)
+            if l + 1 == len(self.levels):
+                break
+            window = self._window[l]
+            window[m.engine.read(L.F_ACTIVE_COLUMN, np.int32, m.engine.active_columns)] = True
+            if (self._steps + 1) % self._period[l + 1]:
+                break                               # (the window of the link above is still open)
+            x = window.copy()
+            window[:] = False
+        self._steps += 1
+        return out
+
+    compute = process
+
+    def reset(self):
+        """A sequence reset of EVERY level before the next input (HierarchicalTemporalMemory.reset).  Only between windows: when
+        the steps taken are a multiple of the product of the strides (ValueError otherwise)."""
+        if self._steps % self._S:
+            raise ValueError(f"reset(): the stack has taken {self._steps} steps, not a multiple of {self._S} (the product of the "
+                             "strides): an upper level is in the middle of a window")
+        for m in self.levels:
+            m.reset()
+
+    # ---- the device path
+    def _check_levels(self):
+        for i, m in enumerate(self.levels):
+            if getattr(m, "_streaming", False):
+                raise ValueError(f"level {i} is in the middle of a streamed run() (continuing=True): end the stream first")
+
+    def _buffer(self, level, name, words):
+        """Device address of the stack's buffer (level, name) of at least `words` 32-bit words (kept, grown when too small)."""
+        ptr, size = self._bufs.get((level, name), (None, 0))
+        if ptr is None or size < words:
+            eng = self.levels[0].engine
+            new = C.c_void_p()
+            eng._hip_check(self.lib.hipSetDevice(eng.device), "hipSetDevice")
+            eng._hip_check(self.lib.hipMalloc(C.byref(new), 4 * words), f"hipMalloc({4 * words} bytes)")
+            if ptr is not None:
+                eng.sync()                          # (one stream: everything that used the old buffer is behind this)
+                self.lib.hipFree(ptr)
+            ptr = new.value
+            self._bufs[(level, name)] = (ptr, words)
+        return ptr
+
+    def _read_buffer(self, level, name, words, dtype):
+        out = np.empty(words, dtype=dtype)
+        if words:
+            eng = self.levels[0].engine
+            eng._hip_check(self.lib.hipMemcpy(out.ctypes.data_as(C.c_void_p), self._bufs[(level, name)][0], 4 * words,
+                                              L.HIP_MEMCPY_DEVICE_TO_HOST), "hipMemcpy")
+        return out
+
+    def run(self, inputs, steps, learning=True, use_graph=True, record=None, resets=None):
+        """`steps` inputs from the rows of the boolean matrix `inputs`, cycled (as HierarchicalTemporalMemory.run), through all
+        levels on the device: per chunk of at most `chunk_steps` level-0 steps, level 0 runs recorded (its active columns stay
+        in device memory), htm_pack_columns packs them into level 1's bank, level 1 runs over it, and so on -- one stream, no
+        host wait inside a chunk.  The state every level is left in equals that of the same inputs given one by one to
+        process().  `steps` and the steps taken so far must be multiples of the product of the strides (ValueError): no
+        half-filled window is carried across calls.
+        `record`: as HierarchicalTemporalMemory.run; the call then returns one RunRecord per level (level l's over its
+        steps / (s_0 .. s_{l-1}) steps), read back after one synchronisation at the end of the call.
+        `resets`: a bool per row of `inputs`: a sequence reset of every level before each step that reads a flagged row.  Flagged
+        rows must be multiples of the strides' product, and the number of rows must divide by it when steps exceeds it, so
+        that every reset stands on a window boundary of every level (ValueError otherwise)."""
+        S, nl = self._S, len(self.levels)
+        steps = int(steps)
+        if steps < 0 or steps % S or self._steps % S:
+            raise ValueError(f"run(): steps ({steps}) and the steps taken so far ({self._steps}) must be multiples of {S}, the product "
+                             "of the strides")
+        self._check_levels()
+        fields = None if record is None else _record_fields(record)
+        m0 = self.levels[0]
+        inputs = np.asarray(inputs, dtype=np.bool_)
+        if inputs.ndim != 2 or inputs.shape[0] < 1 or inputs.shape[1] != m0.engine.input_dim:
+            raise ValueError(f"inputs: bool [n_inputs, {m0.engine.input_dim}], got {inputs.shape}")
+        n_rows = inputs.shape[0]
+        flags = None                                # flags[i]: a reset before the i-th step of this call
+        if resets is not None:
+            resets = np.asarray(resets, dtype=np.bool_).ravel()
+            if resets.shape != (n_rows,):
+                raise ValueError(f"resets: one flag per row of inputs ({n_rows}), got {resets.shape[0]}")
+            flagged = np.flatnonzero(resets)
+            if (flagged % S).any():
+                raise ValueError(f"resets: flagged rows must be multiples of {S}, the product of the strides (got rows {flagged[flagged % S != 0][:8].tolist()})")
+            if flagged.size and steps > n_rows and n_rows % S:
+                raise ValueError(f"resets: {steps} steps cycle through {n_rows} rows, which is not a multiple of {S} (the product of the "
+                                 "strides): the cycled flags would leave the window boundaries")
+            i = np.arange(steps, dtype=np.int64)
+            flags = resets[(m0.engine.steps + i) % n_rows]
+            if ((self._steps + i)[flags] % S).any():
+                raise ValueError(f"resets: a flagged row is read at a stack step that is not a multiple of {S} (level 0 has taken "
+                                 f"{m0.engine.steps} steps, the stack {self._steps})")
+        for m in self.levels:
+            retire_states(m.engine)
+        period = self._period
+        chunk = max(S, min(max(self.chunk_steps, 1), max(steps, 1)) // S * S)
+        first = [m.engine.steps for m in self.levels]
+        shapes = [m.engine.record_shapes() for m in self.levels]
+        # what each level records: the user's fields over the whole call (read back at its end), and, below another level, its
+        # active columns -- over one chunk if the user did not ask for them
+        rows = []
+        for l, m in enumerate(self.levels):
+            want = dict.fromkeys(fields or (), steps // period[l])
+            if l + 1 < nl:
+                want.setdefault("active_column", chunk // period[l])
+            rows.append(want)
+        self.last_run_chunks = []
+        bank = _cached_bank(m0, m0.engine, inputs)
+        done = 0
+        while done < steps:
+            n = min(chunk, steps - done)
+            for l, m in enumerate(self.levels):     # default-sized pools grow as in single-model runs: a look between chunks
+                eng, k = m.engine, m.active_columns
+                if getattr(eng, "_auto_grow", False):
+                    if _grow_if_needed(eng, 2 * k, force_check=True):
+                        m.grow_pool(*eng._grow_to)
+                        eng = m.engine
+                        _grow_if_needed(eng, 2 * k, force_check=True)
+                        if l == 0:
+                            bank = _cached_bank(m0, eng, inputs, fresh=True)
+                    n = min(n, max(S, (eng._free_segments // (2 * k) - 1) * period[l] // S * S))
+            below = None                            # device address of the active-column lists of the level below, this chunk
+            for l, m in enumerate(self.levels):
+                eng = m.engine
+                n_l, done_l = n // period[l], done // period[l]
+                bufs = {}
+                for f, total in rows[l].items():
+                    w = shapes[l][f][0]
+                    whole = fields is not None and f in fields
+                    bufs[f] = self._buffer(l, f, max(total, 1) * w) + (4 * done_l * w if whole else 0)
+                if l == 0:
+                    level_bank, bank_rows = bank, n_rows
+                    bits = None if resets is None else eng.upload_resets(resets)
+                else:
+                    # (a run reads bank row step_index % n_inputs of ITS handle: the chunk's rows start at that row)
+                    level_bank, bank_rows = self._buffer(l, "bank", (chunk // period[l]) * eng.words), n_l
+                    first_row = eng.steps % n_l
+                    lower = self.levels[l - 1]
+                    eng.pack_columns(below, lower.active_columns, n_l, self.strides[l - 1], level_bank, n_l, first_row)
+                    bits = None
+                    if flags is not None:           # a flag on a level-0 step = a flag on the upper step whose window starts there
+                        row_flags = np.zeros(n_l, dtype=np.bool_)
+                        row_flags[(first_row + np.arange(n_l)) % n_l] = flags[done:done + n:period[l]]
+                        bits = eng.upload_resets(row_flags)
+                if bits is not None:
+                    eng.set_run_resets(bits, bank_rows)
+                try:
+                    # (no HTM_RUN_CONTINUE: an upper level working ahead would read a row of the next chunk before it is packed,
+                    # and every level is at rest between chunks, where the pools are looked at)
+                    eng.run_into(level_bank, bank_rows, n_l, bufs, learning=learning, use_graph=use_graph)
+                finally:
+                    if bits is not None:
+                        eng.set_run_resets(None, 0)
+                m._streaming = False
+                below = bufs.get("active_column")
+            done += n
+            self._steps += n
+            self.last_run_chunks.append((n, tuple(m.engine.graph_count() for m in self.levels)))
+        for m in self.levels:
+            m.temporal_memory._new_state(None)
+        for m in self.levels:
+            m.engine.check_capacity()               # (synchronises: an overflow is reported by the call it happened in)
+        if fields is None:
+            return None
+        out = []
+        for l, m in enumerate(self.levels):
+            total = steps // period[l]
+            part = {f: self._read_buffer(l, f, total * shapes[l][f][0], shapes[l][f][1]).reshape(total, shapes[l][f][0]) for f in fields}
+            out.append(_join_record([part], fields, first[l], total, m.active_columns, m.column_dim, m.engine.input_dim))
+        return out
+
+    # ---- checkpoints
+    def state_dict(self):
+        """The levels' own dictionaries under the prefixes l0_, l1_, ..., with `stack_steps`, `strides` and the open window of
+        every link (`link<l>_window`: all False between windows)."""
+        out = {}
+        for l, m in enumerate(self.levels):
+            out.update({f"l{l}_{k}": v for k, v in m.state_dict().items()})
+        out["stack_steps"] = np.int64(self._steps)
+        out["strides"] = np.asarray(self.strides, dtype=np.int64)
+        for l, w in enumerate(self._window):
+            out[f"link{l}_window"] = w.copy()
+        return out
+
+    def load_state_dict(self, state):
+        """ValueError if the dictionary is of a stack of other shapes or strides."""
+        strides = np.asarray(state.get("strides", ()), dtype=np.int64).ravel().tolist() if "strides" in state else None
+        if strides != self.strides or "stack_steps" not in state:
+            raise ValueError(f"load_state_dict(): the state's strides {strides} are not this stack's {self.strides}")
+        parts = []
+        for l, m in enumerate(self.levels):
+            part = {k[len(f"l{l}_"):]: v for k, v in state.items() if k.startswith(f"l{l}_")}
+            perm, pred = part.get("sp_permanence"), part.get("tm_prev_prediction")
+            want = (m.column_dim, m.engine.input_dim)
+            if perm is None or pred is None or tuple(np.shape(perm)) != want or tuple(np.shape(pred)) != (m.column_dim, m.cell_dim):
+                raise ValueError(f"load_state_dict(): level {l} of the state is not {want[1]} -> {m.column_dim} x {m.cell_dim}")
+            parts.append(part)
+        if any(k.startswith(f"l{len(self.levels)}_") for k in state):
+            raise ValueError(f"load_state_dict(): the state has more than this stack's {len(self.levels)} levels")
+        for m, part in zip(self.levels, parts):
+            m.load_state_dict(part)
+        self._steps = int(state["stack_steps"])
+        for l, w in enumerate(self._window):
+            w[:] = np.asarray(state[f"link{l}_window"], dtype=np.bool_) if f"link{l}_window" in state else False
+
+    def save(self, path):
+        np.savez_compressed(path, **self.state_dict())
+
+    def load(self, path):
+        with np.load(path) as z:
+            self.load_state_dict({k: z[k] for k in z.files})
+

@@ -96,7 +96,8 @@ typedef struct htm_info {
     int32_t has_winner_cells;           /* last_state.winner_cell is not None */
     int32_t capacity_error;             /* sticky: 1 = segment pool, 2 = synapse slots, 4 = work list / growth staging,
                                            8 = dead-segment report of a sharded handle, 16 = (internal) a block of the
-                                           in-kernel select exchange never arrived: the step's result is invalid */
+                                           in-kernel select exchange never arrived: the step's result is invalid, 64 = htm_pack_columns met a
+                                           column id outside this handle's input range */
     int32_t words_per_row;              /* packed input words per SP row (input_dim padded to 128 bits) */
     int32_t new_segment_requests;       /* last step: winners without a matching segment (projections.py:271) */
     int32_t recycled_segments;          /* last step: of those, served by recycling (projections.py:80-85) */
@@ -546,6 +547,28 @@ int htm_group_step(htm_group *g, const uint32_t *packed_inputs, int32_t learning
  * bit-identical to the per-member scan.  It is off by default: it reads fewer bytes but measured slower. */
 int htm_create_view(htm_handle *parent, htm_handle **out);
 int64_t htm_device_bytes(htm_handle *h);
+
+/* Region stacks: L regions on top of each other, region l + 1 reading region l's active columns.  In
+ * reference terms a stack is L HierarchicalTemporalMemory objects with input_dim[l+1] == column_dim[l]; the upper one's step u is
+ *   x = np.zeros(column_dim[l], bool); x[sp_state.active_column] = True  for the sp_state (networks.py:29,34) of each of the
+ *   lower one's steps u * stride .. (u + 1) * stride - 1;  upper.process(x, learning)          (networks.py:146-149)
+ * The link is feed-forward, so the lower region runs a chunk of steps as a recorded run (htm_run_recorded: active_column into a
+ * device buffer), htm_pack_columns turns the lists into the upper region's bank, and the upper region runs over it (htm_run),
+ * all on one stream and without the host.
+ *
+ * Bank rows for `dst` (input_dim = the column_dim the lists index) from recorded active-column lists:
+ * row (first_row + r) % bank_rows of device_bank, r in [0, n_rows), = OR over j in [0, stride) of the bits
+ * device_lists[(r * stride + j) * k + 0..k).  Rows in dst's bank layout (words_per_row of htm_info, pad bits 0).
+ * Enqueued on dst's stream; no copy, no wait.
+ *
+ * A run reads bank row step_index % n_inputs: for a bank that holds exactly the rows of the coming run, pass bank_rows = n_rows
+ * and first_row = step_index % bank_rows.  An id outside [0, input_dim) sets no bit and raises bit 64 of htm_info.capacity_error
+ * (sticky).  Rows outside the n_rows written keep their contents.  HTM_ERR_ARGUMENT: NULL pointers, k < 1, stride < 1,
+ * n_rows < 0, bank_rows < 1, first_row outside [0, bank_rows), a bank that is not 16-byte aligned, an input_dim whose row does
+ * not fit the kernel's LDS (above 524 288).  HTM_ERR_STATE: a handle without the device's Spatial Pooler, a column-sharded
+ * handle, a handle that is ahead (HTM_RUN_CONTINUE). */
+int htm_pack_columns(htm_handle *dst, const int32_t *device_lists, int32_t k, int32_t n_rows, int32_t stride,
+                     uint32_t *device_bank, int32_t bank_rows, int32_t first_row);
 
 #ifdef __cplusplus
 }
