@@ -116,6 +116,8 @@ EXPORTS = {
     "htm_create_view": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p)]),
     "htm_device_bytes": (C.c_int64, [C.c_void_p]),
     "htm_pack_columns": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int32]),
+    "htm_encode_votes": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int32]),
+    "htm_set_run_feedback": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32]),
 }
 
 # The HIP runtime calls the binding makes itself -- the device buffers of run(record=...) -- resolved through the library's own

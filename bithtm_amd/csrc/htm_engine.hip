@@ -41,6 +41,7 @@
 #include "htm_reset.h"
 #include "htm_decode.h"
 #include "htm_stack.h"
+#include "htm_forecast.h"
 #include "htm_group.h"
 
 // ------------------------------------------------------------------------------------------
@@ -78,9 +79,9 @@ struct Sizes {
 // What the launches of a captured graph depend on besides the handle's fixed sizes.  htm_run: the step's parity, the call's
 // modes, its StepPlan and schedule, the scan's form, the span of steps, the bank
 struct RunGraphKey {
-    int p; bool recording, resetting, decoding; int learning; bool sp_done, next_sp, next_front, lean; int spec; bool large, emit_fused, wmode;
+    int p; bool recording, resetting, decoding, feeding; int learning; bool sp_done, next_sp, next_front, lean; int spec; bool large, emit_fused, wmode;
     int span; const void *bank; int n_inputs;
-    auto tie() const { return std::tie(p, recording, resetting, decoding, learning, sp_done, next_sp, next_front, lean, spec, large, emit_fused, wmode, span, bank, n_inputs); }
+    auto tie() const { return std::tie(p, recording, resetting, decoding, feeding, learning, sp_done, next_sp, next_front, lean, spec, large, emit_fused, wmode, span, bank, n_inputs); }
     bool operator<(const RunGraphKey &o) const { return tie() < o.tie(); }
 };
 
@@ -143,6 +144,14 @@ struct htm_handle {
     PinDev *d_pin;
     bool decoding;
     int32_t *d_pin_buf;
+    // run feedback (htm_set_run_feedback): the bank whose runs write their next row and its size, the device descriptor the
+    // feedback launches read (filled when the feedback is set), the scratch votes row (zero between uses: htm_forecast.h), and
+    // whether the steps being enqueued (or captured) now feed back
+    uint32_t *feed_bank;
+    int feed_n;
+    FeedDev *d_feed;
+    int32_t *d_feed_votes;
+    bool feeding;
     std::map<RunGraphKey, hipGraphExec_t> graphs;
     // state import staging (htm_write of the MATCH_* / SEG_POTENTIAL fields, applied at commit)
     std::vector<int> imp_pot, imp_match_seg;
@@ -639,6 +648,14 @@ static void enqueue_decode(htm_handle *h, int p) {
 // call of such a handle runs unpipelined (every other schedule applies the rows of step t within step t).
 static bool decode_unpipelined(const htm_handle *h) { return h->pin_out && !can_lean(h); }
 
+// Run feedback (htm_forecast.h): behind the step of parity p, the votes of the state it leaves into the scratch row, then the
+// bank row the next step reads.  That step's overlap must come behind these two launches: a feeding call runs unpipelined.
+static void enqueue_feed(htm_handle *h, int p) {
+    if (!h->feeding) return;
+    LAUNCH(h, "feedback_votes", k_feed_votes, pin_blocks(h->d.C), 256, h->d, p, (const FeedDev *)h->d_feed);
+    LAUNCH(h, "feedback_encode", k_feed_step, 1, ENC_THREADS, h->d, p, (const FeedDev *)h->d_feed);
+}
+
 // grid of the launch that zeroes a decoding call's n x I votes (grid-stride)
 static int pin_begin_blocks(int n, int I) { return (int)std::max<size_t>(1, std::min<size_t>(1024, ((size_t)n * I + 255) / 256)); }
 
@@ -648,6 +665,7 @@ static int enqueue_step(htm_handle *h, const uint32_t *bank, int n_inputs, int l
     enqueue_rest(h, (int)(h->step_host & 1), bank, n_inputs, learning, plan);
     enqueue_record(h, (int)(h->step_host & 1));
     enqueue_decode(h, (int)(h->step_host & 1));
+    enqueue_feed(h, (int)(h->step_host & 1));
     h->step_host += 1;
     return launch_status(h->err);
 }
@@ -1639,8 +1657,14 @@ static int run_or_prepare(htm_handle *h, const uint32_t *device_inputs, int32_t 
     // about 7 us later than a kernel launch does, and the host submits three launches per 30-us step with time to spare --
     // measured, 20 steps per call: 615 against 638 us; from 64 steps on the graphs are level and then ahead)
     const bool graph = (use_graph & 1) && !h->profile && n_steps >= h->knob.eager_below;
-    const bool pipeline = !(use_graph & 2) && can_pipeline(h) && !decode_unpipelined(h);
+    const bool pipeline = !(use_graph & 2) && can_pipeline(h) && !decode_unpipelined(h) && !h->feed_bank;
     const bool resume = sp_is_ahead(h);            // the previous call left the SP one step (and a front) ahead
+    if (h->feed_bank) {                            // (htm_set_run_feedback: what a feeding call refuses)
+        if (learning) { h->err = "htm_run: run feedback is set (htm_set_run_feedback): learning must be 0"; return HTM_ERR_ARGUMENT; }
+        if (h->feed_bank != device_inputs || h->feed_n != n_inputs) { h->err = "htm_run: run feedback was set for another bank or n_inputs (htm_set_run_feedback)"; return HTM_ERR_ARGUMENT; }
+        if (h->reset_bits) { h->err = "htm_run: run feedback and reset bits are set at the same time (htm_set_run_feedback, htm_set_run_resets)"; return HTM_ERR_ARGUMENT; }
+        if (resume) { h->err = "htm_run: run feedback is set while the Spatial Pooler is ahead (HTM_RUN_CONTINUE)"; return HTM_ERR_STATE; }
+    }
     if (resume && (h->ahead_bank != device_inputs || h->ahead_n_inputs != n_inputs || h->ahead_learning != learning)) {
         h->err = "htm_run: the previous call ended with HTM_RUN_CONTINUE; this one must use the same bank, n_inputs and learning flag";
         return HTM_ERR_STATE;
@@ -1651,7 +1675,7 @@ static int run_or_prepare(htm_handle *h, const uint32_t *device_inputs, int32_t 
     if (h->reset_bits && h->reset_n != n_inputs) { h->err = "htm_run: the reset bits were set for a bank of another n_inputs (htm_set_run_resets)"; return HTM_ERR_ARGUMENT; }
     if (dry && !graph) return HTM_OK;
     if (!dry) { int rc = close_open_phases(h); if (rc) return rc; }
-    struct RecordingOff { htm_handle *h; ~RecordingOff() { h->recording = false; h->resetting = false; h->decoding = false; } } recording_off{h};
+    struct RecordingOff { htm_handle *h; ~RecordingOff() { h->recording = false; h->resetting = false; h->decoding = false; h->feeding = false; } } recording_off{h};
     if (h->reset_bits && !h->d_reset) { int rc = dalloc(h, &h->d_reset, 1); if (rc) return rc; }
     if (h->reset_bits && !rec_open && !dry && n_steps > 0)
         LAUNCH(h, "tm_reset", k_reset_begin, 1, 64, h->d_reset, h->reset_bits, (int32_t)n_inputs);
@@ -1667,6 +1691,7 @@ static int run_or_prepare(htm_handle *h, const uint32_t *device_inputs, int32_t 
     if (h->pin_out && !pin_open && !dry && n_steps > 0)
         LAUNCH(h, "predicted_input", k_pin_begin, pin_begin_blocks(n_steps, h->d.I), 256, h->d_pin, h->pin_out, (uint32_t)h->step_host, n_steps, h->d.I);
     h->decoding = h->pin_out != nullptr;
+    h->feeding = h->feed_bank != nullptr;
     // The SP is ahead but the pipelined schedule is gone (another handle with its own stream has appeared on the device since,
     // or this call asks for HTM_RUN_NO_PIPELINE): the coming step is run as the LAST step of the run that went ahead -- its
     // launches hold no select finish, so nothing in them waits for another block -- and the rest of the call unpipelined.
@@ -1719,13 +1744,14 @@ static int run_or_prepare(htm_handle *h, const uint32_t *device_inputs, int32_t 
             if (!plan.sp_done && !plan.next_sp) enqueue_sp_front(h, device_inputs, n_inputs, p, step_wmode(h));    // eager
             enqueue_cold_start(h, device_inputs, n_inputs, learning, plan);                         // eager: first step of a pipelined run
         }
-        const RunGraphKey key{p, h->recording, h->resetting, h->decoding, learning, plan.sp_done, plan.next_sp, plan.next_front, lean,
+        const RunGraphKey key{p, h->recording, h->resetting, h->decoding, h->feeding, learning, plan.sp_done, plan.next_sp, plan.next_front, lean,
                               scan_spec_blocks(h), scan_pool_is_large(h), h->emit_fused, step_wmode(h) != 0, span, device_inputs, n_inputs};
         const hipGraphExec_t exec = cached_graph(h->graphs, key, h->stream, h->err, [&] {
             for (int i = 0; i < span; ++i) {
                 enqueue_rest(h, (p + i) & 1, device_inputs, n_inputs, learning, plan);
                 enqueue_record(h, (p + i) & 1);
                 enqueue_decode(h, (p + i) & 1);
+                enqueue_feed(h, (p + i) & 1);
             }
             return 0;
         });
@@ -1801,7 +1827,7 @@ extern "C" int htm_run_plan(htm_handle *h, int32_t n_steps, int32_t use_graph) {
     refresh_exchange_mode(h);
     refresh_seg_hint(h);
     const bool graph = (use_graph & 1) && !h->profile && n_steps >= h->knob.eager_below;
-    const bool pipeline = !(use_graph & 2) && can_pipeline(h) && !decode_unpipelined(h) && n_steps > 1;
+    const bool pipeline = !(use_graph & 2) && can_pipeline(h) && !decode_unpipelined(h) && !h->feed_bank && n_steps > 1;
     return (graph ? HTM_PLAN_GRAPH : 0) | (pipeline ? HTM_PLAN_PIPELINED : 0) | (pipeline && can_lean(h) ? HTM_PLAN_LEAN : 0) |
            (scan_pool_is_large(h) ? HTM_PLAN_SCAN_LARGE : 0);
 }
@@ -2858,6 +2884,68 @@ extern "C" int htm_predicted_input(htm_handle *h, int32_t *host_dst) {
     return HTM_OK;
 }
 
+// Closed-loop forecasting (htm_forecast.h).  The scratch votes row and the descriptor, allocated when first needed.
+static int feed_alloc(htm_handle *h) {
+    HIPCHK(h, hipSetDevice(h->device));
+    if (!h->d_feed_votes) { int rc = dalloc(h, &h->d_feed_votes, h->d.I); if (rc) return rc; }      // (zeroed: dalloc)
+    if (!h->d_feed) { int rc = dalloc(h, &h->d_feed, 1); if (rc) return rc; }
+    return 0;
+}
+
+static int feed_check_args(htm_handle *h, const char *what, int32_t min_votes, int32_t max_bits, const uint32_t *bank, int32_t rows) {
+    if (min_votes < 1 || max_bits < 0 || rows < 1) { h->err = std::string(what) + ": min_votes >= 1, max_bits >= 0 and at least one bank row"; return HTM_ERR_ARGUMENT; }
+    if (((uintptr_t)bank & 15) != 0) { h->err = std::string(what) + ": the bank must be 16-byte aligned"; return HTM_ERR_ARGUMENT; }
+    return 0;
+}
+
+// After the held-back tail: the votes of the current state into the scratch row, then the row encoded; no copy, no wait
+extern "C" int htm_encode_votes(htm_handle *h, int32_t min_votes, int32_t max_bits, uint32_t *device_bank, int32_t bank_rows, int32_t row) {
+    if (!h || !device_bank) return HTM_ERR_ARGUMENT;
+    flush_tail(h);
+    int rc = feed_check_args(h, "htm_encode_votes", min_votes, max_bits, device_bank, bank_rows);
+    if (rc) return rc;
+    if (row < 0 || row >= bank_rows) { h->err = "htm_encode_votes: 0 <= row < bank_rows"; return HTM_ERR_ARGUMENT; }
+    REJECT_WHEN_AHEAD(h);
+    rc = pin_refuse(h, "htm_encode_votes");
+    if (rc) return rc;
+    if (h->shard_open || h->phase_open) { h->err = "htm_encode_votes: a step of the handle is open (htm_shard_begin / htm_sp_phase)"; return HTM_ERR_STATE; }
+    rc = view_enter(h, 0);
+    if (rc) return rc;
+    rc = feed_alloc(h);
+    if (rc) return rc;
+    const Dev &d = h->d;
+    LAUNCH(h, "feedback_votes", k_pin, pin_blocks(d.C), 256, d, (int)((h->step_host + 1) & 1), h->d_feed_votes);
+    LAUNCH(h, "feedback_encode", k_encode, 1, ENC_THREADS, d, h->d_feed_votes, (int)min_votes, (int)max_bits, device_bank + (size_t)row * d.W);
+    return launch_status(h->err);
+}
+
+extern "C" int htm_set_run_feedback(htm_handle *h, uint32_t *device_bank, int32_t n_inputs, int32_t min_votes, int32_t max_bits) {
+    if (!h) return HTM_ERR_ARGUMENT;
+    if (!device_bank) {                             // cleared: the descriptor too (group launches read it)
+        h->feed_bank = nullptr;
+        h->feed_n = 0;
+        if (h->d_feed) {
+            HIPCHK(h, hipSetDevice(h->device));
+            LAUNCH(h, "feedback_set", k_feed_set, 1, 64, h->d_feed, (uint32_t *)nullptr, h->d_feed_votes, 0, 1, 0);
+            return launch_status(h->err);
+        }
+        return HTM_OK;
+    }
+    int rc = pin_refuse(h, "htm_set_run_feedback");
+    if (rc) return rc;
+    rc = feed_check_args(h, "htm_set_run_feedback", min_votes, max_bits, device_bank, n_inputs);
+    if (rc) return rc;
+    REJECT_WHEN_AHEAD(h);
+    rc = feed_alloc(h);
+    if (rc) return rc;
+    LAUNCH(h, "feedback_set", k_feed_set, 1, 64, h->d_feed, device_bank, h->d_feed_votes, n_inputs, min_votes, max_bits);
+    rc = launch_status(h->err);
+    if (rc) return rc;
+    h->feed_bank = device_bank;
+    h->feed_n = n_inputs;
+    return HTM_OK;
+}
+
 // Region stacks (htm_stack.h): bank rows for h from the active-column lists a lower region's recorded run left on the device
 extern "C" int htm_pack_columns(htm_handle *h, const int32_t *device_lists, int32_t k, int32_t n_rows, int32_t stride,
                                 uint32_t *device_bank, int32_t bank_rows, int32_t first_row) {
@@ -2931,8 +3019,8 @@ extern "C" int htm_profile_read(htm_handle *h, int32_t max_kernels, const char *
 
 // ... htm_group_run: the step's parity, the call's modes, the form of the group's launches (GroupForm), the span, the bank table
 struct GroupGraphKey {
-    int p; bool recording, decoding; int learning; bool fuse, large, shared; int spec, span; const void *bank_tab; int n_inputs;
-    auto tie() const { return std::tie(p, recording, decoding, learning, fuse, large, shared, spec, span, bank_tab, n_inputs); }
+    int p; bool recording, decoding, feeding; int learning; bool fuse, large, shared; int spec, span; const void *bank_tab; int n_inputs;
+    auto tie() const { return std::tie(p, recording, decoding, feeding, learning, fuse, large, shared, spec, span, bank_tab, n_inputs); }
     bool operator<(const GroupGraphKey &o) const { return tie() < o.tie(); }
 };
 
@@ -2948,6 +3036,7 @@ struct htm_group {
     Dev *d_tab;
     RecDev **d_recs;                          // each member's record descriptor (htm_handle::d_rec)
     PinDev **d_pins;                          // each member's decoding descriptor (htm_handle::d_pin)
+    FeedDev **d_feeds;                        // each member's feedback descriptor (htm_handle::d_feed)
     uint32_t *stage;                          // htm_group_step: [n][W] staged host inputs
     const uint32_t **stage_tab;               // ... and the bank table that points into it
     // device tables of the members' banks / record buffers, one per distinct set (graphs hold the bank table's address)
@@ -2955,7 +3044,7 @@ struct htm_group {
     std::map<std::vector<const void *>, GrpRecArgs *> rec_tabs;
     std::map<std::vector<int32_t *>, int32_t **> pin_tabs;      // the members' decoding outputs (htm_set_run_predicted_input)
     std::map<GroupGraphKey, hipGraphExec_t> graphs;
-    bool recording, decoding;
+    bool recording, decoding, feeding;
     // inference views (htm_create_view): some member is a view; every member aliases one set of weights (then the steps with
     // learning = 0 scan the store once per chunk of share_m members: kgrp_scan_shared, share_chunks x share_blocks blocks)
     bool has_view, shared;
@@ -3065,22 +3154,26 @@ extern "C" int htm_group_create(htm_handle *const *members, int32_t n, htm_group
     g->host_tab.resize(n);
     std::vector<RecDev *> recs(n);
     std::vector<PinDev *> pins(n);
+    std::vector<FeedDev *> feeds(n);
     for (int i = 0; i < n; ++i) {
         htm_handle *h = g->m[i];
         flush_tail(h);
         if (!h->d_rec && dalloc(h, &h->d_rec, 1)) { g->err = h->err; return fail(HTM_ERR_HIP); }
         if (!h->d_pin && dalloc(h, &h->d_pin, 1)) { g->err = h->err; return fail(HTM_ERR_HIP); }
+        if (!h->d_feed && dalloc(h, &h->d_feed, 1)) { g->err = h->err; return fail(HTM_ERR_HIP); }      // (zeroed: no feedback)
         if (hipStreamSynchronize(h->stream) != hipSuccess) { g->err = "htm_group_create: hipStreamSynchronize failed"; return fail(HTM_ERR_HIP); }
         g->host_tab[i] = h->d;
         g->host_tab[i].sel_passes = h->sz.sel_passes_full;
         recs[i] = h->d_rec;
         pins[i] = h->d_pin;
+        feeds[i] = h->d_feed;
     }
     const int W = h0->d.W;
     int rc = 0;
     rc |= galloc(g, &g->d_tab, n);
     rc |= galloc(g, &g->d_recs, n);
     rc |= galloc(g, &g->d_pins, n);
+    rc |= galloc(g, &g->d_feeds, n);
     rc |= galloc(g, &g->stage, (size_t)n * W);
     rc |= galloc(g, (uint32_t ***)&g->stage_tab, n);
     if (rc) return fail(HTM_ERR_HIP);
@@ -3091,6 +3184,7 @@ extern "C" int htm_group_create(htm_handle *const *members, int32_t n, htm_group
         hipMemcpy(g->d_tab, g->host_tab.data(), (size_t)n * sizeof(Dev), hipMemcpyHostToDevice) != hipSuccess ||
         hipMemcpy(g->d_recs, recs.data(), (size_t)n * sizeof(RecDev *), hipMemcpyHostToDevice) != hipSuccess ||
         hipMemcpy(g->d_pins, pins.data(), (size_t)n * sizeof(PinDev *), hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(g->d_feeds, feeds.data(), (size_t)n * sizeof(FeedDev *), hipMemcpyHostToDevice) != hipSuccess ||
         hipMemcpy((void *)g->stage_tab, stage_rows.data(), (size_t)n * sizeof(uint32_t *), hipMemcpyHostToDevice) != hipSuccess) {
         g->err = std::string("htm_group_create: ") + hipGetErrorString(hipGetLastError());
         return fail(HTM_ERR_HIP);
@@ -3180,10 +3274,15 @@ static void group_enqueue_step(htm_group *g, const uint32_t *const *banks, int n
         const dim3 g_pin(pin_blocks(d.C), B);
         LAUNCH_ON(h, s, 0, "group:predicted_input", kgrp_pin_step, g_pin, 256, tab, p, g->d_pins);
     }
+    if (g->feeding) {                              // (members without feedback leave both launches at once: htm_forecast.h)
+        const dim3 g_pin(pin_blocks(d.C), B);
+        LAUNCH_ON(h, s, 0, "group:feedback_votes", kgrp_feed_votes, g_pin, 256, tab, p, g->d_feeds);
+        LAUNCH_ON(h, s, 0, "group:feedback_encode", kgrp_feed_step, dim3(1, B), ENC_THREADS, tab, p, g->d_feeds);
+    }
 }
 
 // every refusal of a group call, before anything is enqueued
-static int group_check(htm_group *g, const uint32_t *const *banks, const htm_run_record *records) {
+static int group_check(htm_group *g, const uint32_t *const *banks, const htm_run_record *records, int n_inputs = 1, int learning = 0) {
     const htm_handle *h0 = g->m[0];
     for (int i = 0; i < g->n; ++i) {
         const htm_handle *h = g->m[i];
@@ -3197,6 +3296,10 @@ static int group_check(htm_group *g, const uint32_t *const *banks, const htm_run
             return HTM_ERR_STATE;
         }
         if (banks && !banks[i]) { g->err = who + ": null bank"; return HTM_ERR_ARGUMENT; }
+        if (h->feed_bank) {                         // (htm_set_run_feedback: the refusals of htm_run)
+            if (!banks || h->feed_bank != banks[i] || h->feed_n != n_inputs) { g->err = who + ": run feedback was set for another bank or n_inputs (htm_set_run_feedback)"; return HTM_ERR_ARGUMENT; }
+            if (learning) { g->err = who + ": run feedback is set (htm_set_run_feedback): learning must be 0"; return HTM_ERR_ARGUMENT; }
+        }
         if (h->is_view) {
             std::lock_guard<std::mutex> lock(g_shared_mutex);
             if (h->shared->parent && sp_is_ahead(h->shared->parent)) { g->err = who + ": the view's parent is ahead (HTM_RUN_CONTINUE)"; return HTM_ERR_STATE; }
@@ -3237,7 +3340,7 @@ static int group_run(htm_group *g, const uint32_t **bank_tab, int n_inputs, int 
     htm_handle *h0 = g->m[0];
     const hipStream_t s = g->stream;
     learning = learning ? 1 : 0;
-    struct RecordingOff { htm_group *g; ~RecordingOff() { g->recording = false; g->decoding = false; } } recording_off{g};
+    struct RecordingOff { htm_group *g; ~RecordingOff() { g->recording = false; g->decoding = false; g->feeding = false; } } recording_off{g};
     if (records) {
         std::vector<GrpRecArgs> rows(B);
         std::vector<const void *> key;
@@ -3265,6 +3368,7 @@ static int group_run(htm_group *g, const uint32_t **bank_tab, int n_inputs, int 
         LAUNCH_ON(h0, s, 0, "group:predicted_input", kgrp_pin_begin, g_begin, 256, g->d_tab, (int)((h0->step_host + 1) & 1), g->d_pins, out_tab, n_steps);
         g->decoding = true;
     }
+    g->feeding = std::any_of(g->m.begin(), g->m.end(), [](const htm_handle *h) { return h->feed_bank != nullptr; });
     GroupForm f = group_form(g);
     f.shared = g->shared && !learning;
     const bool graph = (use_graph & 1) && !h0->profile && n_steps >= h0->knob.eager_below;
@@ -3278,7 +3382,7 @@ static int group_run(htm_group *g, const uint32_t **bank_tab, int n_inputs, int 
             continue;
         }
         const int span = n_steps - t >= span_max ? span_max : 1;
-        const GroupGraphKey key{p, g->recording, g->decoding, learning, f.fuse, f.large, f.shared, f.spec, span, bank_tab, n_inputs};
+        const GroupGraphKey key{p, g->recording, g->decoding, g->feeding, learning, f.fuse, f.large, f.shared, f.spec, span, bank_tab, n_inputs};
         const hipGraphExec_t exec = cached_graph(g->graphs, key, s, g->err, [&] {
             for (int i = 0; i < span; ++i) group_enqueue_step(g, bank_tab, n_inputs, learning, (p + i) & 1, f);
             return 0;
@@ -3306,7 +3410,7 @@ extern "C" int htm_group_run(htm_group *g, const uint32_t *const *device_banks, 
     if (!g) return HTM_ERR_ARGUMENT;
     if (!device_banks || n_inputs < 1 || n_steps < 0) { g->err = "htm_group_run: need device_banks, n_inputs >= 1 and n_steps >= 0"; return HTM_ERR_ARGUMENT; }
     if (learning && g->has_view) { g->err = "htm_group_run: a group with inference views steps with learning = 0 only"; return HTM_ERR_STATE; }
-    int rc = group_check(g, device_banks, records);
+    int rc = group_check(g, device_banks, records, n_inputs, learning);
     if (rc || n_steps == 0) return rc;
     GHIPCHK(g, hipSetDevice(g->device));
     rc = group_join(g);

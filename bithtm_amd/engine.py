@@ -445,6 +445,33 @@ class Engine:
         self._check(self.lib.htm_predicted_input(self.h, out.ctypes.data_as(C.c_void_p)), "htm_predicted_input")
         return out
 
+    def encode_votes(self, min_votes, max_bits, device_bank, bank_rows, row):
+        """Row `row` of a device bank = the current state's votes encoded (htm_encode_votes): enqueued on the engine's stream, no
+        wait."""
+        self._check(self.lib.htm_encode_votes(self.h, int(min_votes), int(max_bits), C.c_void_p(device_bank), int(bank_rows), int(row)),
+                    "htm_encode_votes")
+
+    def set_run_feedback(self, device_bank, n_inputs=0, min_votes=1, max_bits=0):
+        """Later run() calls and group calls on this bank write each step's encoded votes into the row the next step reads
+        (htm_set_run_feedback); None clears it."""
+        self._check(self.lib.htm_set_run_feedback(self.h, C.c_void_p(device_bank) if device_bank else None, int(n_inputs), int(min_votes),
+                                                  int(max_bits)), "htm_set_run_feedback")
+
+    def zero_bank(self, rows):
+        """Device address of a handle-owned bank of `rows` all-zero rows (htm_bank_upload)."""
+        ptr = C.c_void_p()
+        zeros = np.zeros((int(rows), (self.input_dim + 31) // 32), dtype=np.uint32)
+        self._check(self.lib.htm_bank_upload(self.h, zeros.ctypes.data_as(C.c_void_p), int(rows), C.byref(ptr)), "htm_bank_upload")
+        return ptr.value
+
+    def read_bank(self, device_bank, rows):
+        """bool[rows, input_dim]: the rows of a device bank, after a synchronisation."""
+        self.sync()
+        out = np.empty((int(rows), self.words), dtype=np.uint32)
+        self._hip_check(self.lib.hipMemcpy(out.ctypes.data_as(C.c_void_p), C.c_void_p(device_bank), out.nbytes, L.HIP_MEMCPY_DEVICE_TO_HOST),
+                        "hipMemcpy")
+        return np.unpackbits(out.view(np.uint8), axis=1, bitorder="little")[:, :self.input_dim].astype(np.bool_)
+
     # The record buffers are device memory of the HIP runtime the library itself is linked against (_lib.HIP_EXPORTS), kept for
     # the next recorded call and grown geometrically.
     def _record_buffer(self, field, elements):

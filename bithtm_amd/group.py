@@ -20,8 +20,8 @@ import numpy as np
 
 from . import _lib as L
 from .engine import HtmError, pack_bits
-from .networks import (HierarchicalTemporalMemory, InferenceView, RunRecord, _cached_bank, _grow_if_needed, _join_record, _record_fields,
-                       retire_states)
+from .networks import (HierarchicalTemporalMemory, InferenceView, RunRecord, _cached_bank, _encode_params, _grow_if_needed, _join_record,
+                       _record_fields, retire_states)
 
 
 class SharedStream:
@@ -252,6 +252,59 @@ class ModelGroup:
         if fields is None:
             return None
         return [_join_record(p, fields, f, steps, k, m.column_dim, m.engine.input_dim) for p, f, m in zip(parts, first, self.models)]
+
+    # forecast(): steps per feeding group run (see HierarchicalTemporalMemory.forecast_chunk)
+    forecast_chunk = 1024
+
+    def forecast(self, steps, min_votes=1, max_bits=0, record=None, use_graph=True):
+        """Every member's forecast(steps, min_votes, max_bits) at once: each member rolls forward from its own state on its own
+        encoded votes, one launch sequence per step for all members.  min_votes / max_bits: one value, or one per member.
+        Returns bool [B, steps, input_dim]; with `record` (as run(record=)) the pair (rows, one RunRecord per member)."""
+        B, steps = len(self.models), int(steps)
+        params = [_encode_params(a, b) for a, b in zip(np.broadcast_to(np.asarray(min_votes), (B,)), np.broadcast_to(np.asarray(max_bits), (B,)))]
+        fields = None if record is None else _record_fields(record)
+        engines = [m._forecast_engine("forecast()") for m in self.models]
+        for e in engines:
+            retire_states(e)
+        self._current()
+        engines = [m.engine for m in self.models]
+        chunk, k = int(self.forecast_chunk), self.models[0].active_columns
+        ptrs = [m._zero_bank(e, chunk + 1) for m, e in zip(self.models, engines)]
+        banks = (C.c_void_p * B)(*ptrs)
+        rows = np.zeros((B, steps, engines[0].input_dim), dtype=np.bool_)
+        first = [e.steps for e in engines]
+        parts = [[] for _ in self.models]
+        done = 0
+        while done < steps:
+            n = min(chunk, steps - done)
+            start = [e.steps for e in engines]
+            recs = shapes = None
+            try:
+                for e, ptr, (mv, mb) in zip(engines, ptrs, params):
+                    e.encode_votes(mv, mb, ptr, chunk + 1, e.steps % (chunk + 1))
+                    e.set_run_feedback(ptr, chunk + 1, mv, mb)
+                if fields is not None:
+                    recs, shapes = self._records(fields, n)
+                self._check(self.lib.htm_group_run(self._g, banks, chunk + 1, n, 0, int(bool(use_graph)), recs), "htm_group_run")
+            finally:
+                for e in engines:
+                    e.set_run_feedback(None)
+                if fields is not None:
+                    self._unset_votes()
+            for e in engines:
+                e.steps += n
+            if fields is not None:
+                for i, part in enumerate(self._read_records(fields, n, shapes)):
+                    parts[i].append(part)
+            for i, (e, ptr) in enumerate(zip(engines, ptrs)):
+                rows[i, done:done + n] = e.read_bank(ptr, chunk + 1)[(start[i] + np.arange(n)) % (chunk + 1)]
+            done += n
+        for m in self.models:
+            m.temporal_memory._new_state(None)
+            m.engine.check_capacity()
+        if fields is None:
+            return rows
+        return rows, [_join_record(p, fields, f, steps, k, m.column_dim, m.engine.input_dim) for p, f, m in zip(parts, first, self.models)]
 
     def process(self, X, learning=None, record=True):
         """One timestep of every member, member i on X[i] (bool [B, input_dim]) -- its own process(X[i]) at once.  Returns a

@@ -741,6 +741,96 @@ class HierarchicalTemporalMemory:
             raise RuntimeError("predicted_input() decodes on the device: not available with plug-in Spatial Pooler objects that live on the host")
         return eng.predicted_input()
 
+    # forecast(): steps per feeding run (the device bank holds one row more); an attribute so that a caller, or a test, can cut a
+    # forecast into smaller runs
+    forecast_chunk = 1024
+
+    def _forecast_engine(self, what):
+        eng = self._fused_engine(what)
+        if not self.spatial_pooler._plain:
+            raise RuntimeError(f"{what} keeps the whole loop on the device: not available with plug-in objects that live on the host")
+        if getattr(self, "_streaming", False):
+            raise RuntimeError(f"{what} in the middle of a streamed run() (continuing=True): end the stream first")
+        return eng
+
+    def _zero_bank(self, eng, rows):
+        """A device bank of `rows` rows on `eng` for forecast() / predicted_bits(), kept (so that the graphs of feeding runs, which
+        are keyed by the bank, are reused across calls) until the engine is re-created."""
+        banks = getattr(self, "_forecast_banks", None)
+        if banks is None or banks[0]() is not eng:
+            self._forecast_banks = banks = (weakref.ref(eng), {})
+        if rows not in banks[1]:
+            banks[1][rows] = eng.zero_bank(rows)
+        return banks[1][rows]
+
+    def predicted_bits(self, min_votes=1, max_bits=0):
+        """bool[input_dim]: the input the model expects next, as forecast() would feed it back -- encode_votes(predicted_input(),
+        min_votes, max_bits), encoded on the device (htm_encode_votes): one launch sequence and one read-back of a packed row."""
+        min_votes, max_bits = _encode_params(min_votes, max_bits)
+        eng = self._forecast_engine("predicted_bits()")
+        retire_states(eng)
+        bank = self._zero_bank(eng, 1)
+        eng.encode_votes(min_votes, max_bits, bank, 1, 0)
+        return eng.read_bank(bank, 1)[0]
+
+    def forecast(self, steps, min_votes=1, max_bits=0, record=None, use_graph=True, learning=False):
+        """What the model expects over the next `steps` steps: from its current state, `steps` times
+            x = encode_votes(predicted_input(), min_votes, max_bits);  process(x, learning=False)
+        with the whole loop on the device (htm_set_run_feedback: each step's votes are encoded into the bank row the next step
+        reads).  Returns the x of every step, bool[steps, input_dim]; with `record` (as run(record=)) the pair (rows, RunRecord).
+        The state it leaves, and everything the record holds, are those of that loop bit for bit.  An input with fewer than
+        min_votes votes is never set, so a row may be empty -- and stays empty once the model predicts nothing.  learning=True
+        (learning from the model's own output) raises ValueError.  To look ahead without moving this model's own stream,
+        forecast on a view:  view = htm.inference_view(); view.run(context, n); view.forecast(k)."""
+        if learning:
+            raise ValueError("forecast(): learning from the model's own output is not available (learning=False only)")
+        min_votes, max_bits = _encode_params(min_votes, max_bits)
+        eng = self._forecast_engine("forecast()")
+        fields = None if record is None else _record_fields(record)
+        retire_states(eng)
+        chunk = int(self.forecast_chunk)
+        bank = self._zero_bank(eng, chunk + 1)
+        rows = np.zeros((int(steps), eng.input_dim), dtype=np.bool_)
+        done, parts, first_step = 0, [], eng.steps
+        while done < steps:
+            n, s0 = min(chunk, steps - done), eng.steps
+            eng.encode_votes(min_votes, max_bits, bank, chunk + 1, s0 % (chunk + 1))
+            eng.set_run_feedback(bank, chunk + 1, min_votes, max_bits)
+            try:
+                part = eng.run(bank, chunk + 1, n, learning=False, use_graph=use_graph, record=fields)
+            finally:
+                eng.set_run_feedback(None)
+            rows[done:done + n] = eng.read_bank(bank, chunk + 1)[(s0 + np.arange(n)) % (chunk + 1)]
+            if fields is not None:
+                parts.append(part)
+            done += n
+        self.temporal_memory._new_state(None)
+        eng.check_capacity()
+        if fields is None:
+            return rows
+        return rows, _join_record(parts, fields, first_step, int(steps), self.active_columns, self.column_dim, eng.input_dim)
+
+
+def _encode_params(min_votes, max_bits):
+    min_votes, max_bits = int(min_votes), int(max_bits)
+    if min_votes < 1 or max_bits < 0:
+        raise ValueError(f"min_votes must be at least 1 and max_bits at least 0 (0 = no cap); got {min_votes}, {max_bits}")
+    return min_votes, max_bits
+
+
+def encode_votes(votes, min_votes=1, max_bits=0):
+    """The input row forecast() feeds back for the votes of predicted_input(): bool[input_dim], votes >= min_votes, and with
+    max_bits > 0 at most the max_bits inputs with the most votes (ties at the cut-off go to the lower input index).  The NumPy
+    definition of what htm_encode_votes computes on the device."""
+    min_votes, max_bits = _encode_params(min_votes, max_bits)
+    votes = np.asarray(votes)
+    x = votes >= min_votes
+    if max_bits and x.sum() > max_bits:
+        keep = np.lexsort((np.arange(votes.size), -votes.astype(np.int64)))[:max_bits]
+        x = np.zeros(votes.size, dtype=np.bool_)
+        x[keep] = True
+    return x
+
 
 class InferenceView(HierarchicalTemporalMemory):
     """A model that shares its parent's weights in device memory and owns only its stream state (HierarchicalTemporalMemory.
@@ -799,6 +889,14 @@ class InferenceView(HierarchicalTemporalMemory):
     def predicted_input(self):
         self._check_parent()
         return super().predicted_input()
+
+    def predicted_bits(self, min_votes=1, max_bits=0):
+        self._check_parent()
+        return super().predicted_bits(min_votes, max_bits)
+
+    def forecast(self, steps, min_votes=1, max_bits=0, record=None, use_graph=True, learning=False):
+        self._check_parent()
+        return super().forecast(steps, min_votes, max_bits, record=record, use_graph=use_graph, learning=learning)
 
     def inference_view(self):
         raise ValueError("inference_view() of a view: make views of the model that owns the weights")

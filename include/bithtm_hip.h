@@ -570,6 +570,32 @@ int64_t htm_device_bytes(htm_handle *h);
 int htm_pack_columns(htm_handle *dst, const int32_t *device_lists, int32_t k, int32_t n_rows, int32_t stride,
                      uint32_t *device_bank, int32_t bank_rows, int32_t first_row);
 
+/* Closed-loop forecasting: what the model expects over the next n steps, its own predicted input fed back
+ * as the next input on the device.  With votes = the predicted-input votes of a state (htm_predicted_input above),
+ *   encode(votes, min_votes, max_bits):  x = votes >= min_votes; if max_bits > 0 and x.sum() > max_bits, only the max_bits inputs
+ *   with the most votes stay set, ties at the cut-off going to the LOWER input index (np.lexsort((arange(I), -votes))[:max_bits]).
+ * An input with fewer than min_votes votes is never set: a row may hold fewer than max_bits bits, or none.  Rows are bank rows
+ * (words_per_row words, pad bits 0, every word written).
+ *
+ * htm_encode_votes: row `row` of device_bank (bank_rows rows) = encode(votes of the handle's current state).  After the held-back
+ * tail, two launches on the handle's stream; no copy, no wait.  HTM_ERR_STATE as htm_predicted_input; HTM_ERR_ARGUMENT: NULL,
+ * min_votes < 1, max_bits < 0, bank_rows < 1, row outside [0, bank_rows), a bank that is not 16-byte aligned.
+ *
+ * htm_set_run_feedback: the later htm_run / htm_run_recorded / htm_prepare / htm_prepare_recorded calls on exactly this bank and
+ * n_inputs, and the htm_group_run calls whose bank for this member is this bank, write behind the step with index s
+ *   bank row (s + 1) % n_inputs = encode(votes of the state that step leaves)
+ * -- the row step s + 1 reads.  With row s0 % n_inputs seeded by htm_encode_votes, a run of n <= n_inputs - 1 steps from step
+ * index s0 is n steps of the loop  x = encode(votes); htm_step(x, learning = 0), and leaves the x of its steps in the bank.  NULL
+ * clears the feedback (calls then launch and capture exactly what they did without it).  A feeding call runs unpipelined
+ * whatever use_graph says (step s + 1's overlap cannot start before step s's scan; htm_run_plan reports it so) and ignores
+ * HTM_RUN_CONTINUE; its graphs are captured once and read the parameters through a descriptor this call fills on the device.
+ * While feedback is set, HTM_ERR_ARGUMENT for a run with learning != 0, on another bank or n_inputs, or with reset bits set
+ * (htm_set_run_resets); htm_group_step refuses a member with feedback.  A group may mix members with and without feedback.
+ * HTM_ERR_STATE on a column-sharded handle, on a handle without the device's own Spatial Pooler and Temporal Memory and while the
+ * handle is ahead (HTM_RUN_CONTINUE); HTM_ERR_ARGUMENT for min_votes < 1, max_bits < 0, n_inputs < 1 and a misaligned bank. */
+int htm_encode_votes(htm_handle *h, int32_t min_votes, int32_t max_bits, uint32_t *device_bank, int32_t bank_rows, int32_t row);
+int htm_set_run_feedback(htm_handle *h, uint32_t *device_bank, int32_t n_inputs, int32_t min_votes, int32_t max_bits);
+
 #ifdef __cplusplus
 }
 #endif
