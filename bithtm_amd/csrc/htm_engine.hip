@@ -43,6 +43,7 @@
 #include "htm_stack.h"
 #include "htm_forecast.h"
 #include "htm_group.h"
+#include "htm_tm_feed.h"
 
 // ------------------------------------------------------------------------------------------
 // host side
@@ -91,6 +92,13 @@ struct ShardGraphKey {
     int p, learning; bool front_done, front_next; int span, ranks, n_inputs; std::vector<std::tuple<int, bool, bool>> per_rank; const void *bank;
     auto tie() const { return std::tie(p, learning, front_done, front_next, span, ranks, n_inputs, per_rank, bank); }
     bool operator<(const ShardGraphKey &o) const { return tie() < o.tie(); }
+};
+
+// ... htm_tm_run: the step's parity, the call's modes, the scan's form, the span of steps, the bank of lists and its shape
+struct TmRunGraphKey {
+    int p; bool recording, resetting; int learning, spec; bool large; int span; const void *lists; int n_rows, n;
+    auto tie() const { return std::tie(p, recording, resetting, learning, spec, large, span, lists, n_rows, n); }
+    bool operator<(const TmRunGraphKey &o) const { return tie() < o.tie(); }
 };
 
 struct htm_handle {
@@ -153,6 +161,7 @@ struct htm_handle {
     int32_t *d_feed_votes;
     bool feeding;
     std::map<RunGraphKey, hipGraphExec_t> graphs;
+    std::map<TmRunGraphKey, hipGraphExec_t> tm_graphs;        // htm_tm_run
     // state import staging (htm_write of the MATCH_* / SEG_POTENTIAL fields, applied at commit)
     std::vector<int> imp_pot, imp_match_seg;
     // ... on a column-sharded handle also the per-segment arrays (written for ALL segment ids; the commit keeps the rows of
@@ -684,6 +693,7 @@ extern "C" void htm_destroy(htm_handle *h) {
     hipStreamSynchronize(h->stream);
     for (auto &kv : h->graphs) hipGraphExecDestroy(kv.second);
     for (auto &kv : h->shard_graphs) hipGraphExecDestroy(kv.second);
+    for (auto &kv : h->tm_graphs) hipGraphExecDestroy(kv.second);
     for (auto &v : h->prof_events)
         for (auto &pr : v) { hipEventDestroy(pr.first); hipEventDestroy(pr.second); }
     for (hipEvent_t e : h->prof_all) hipEventDestroy(e);
@@ -1816,9 +1826,91 @@ extern "C" int htm_prepare_recorded(htm_handle *h, const uint32_t *device_inputs
     return run_recorded(h, device_inputs, n_inputs, n_steps, learning, use_graph, nullptr, true);
 }
 
+// Batched stand-alone Temporal Memory run (include/bithtm_hip.h; htm_tm_feed.h): n_steps of htm_tm_step
+// (return_winner_cell = 1) over a device bank of lists, without the host in the loop.  The launches of one step, in order.
+static void enqueue_tm_run_step(htm_handle *h, int p, const int32_t *lists, int n_rows, int n, int learning) {
+    Dev &d = h->d;
+    enqueue_run_reset(h, p);
+    LAUNCH_ON(h, h->stream, feed_lds(d), "tm_feed", k_tm_feed, std::min((d.C + 255) / 256, 1024), FEED_THREADS, d, p, lists, n_rows, n);
+    LAUNCH(h, "tm_activate", k_tm_activate, std::max(1, (n * d.KP + 255) / 256), 256, d, p, n, 1);
+    enqueue_tm(h, n, learning, 1, p, nullptr, 1, false);
+    if (h->recording) LAUNCH(h, "record", k_tm_feed_record, rec_blocks(d), 256, d, p, h->d_rec, n);
+}
+
+extern "C" int htm_tm_run(htm_handle *h, const int32_t *device_lists, int32_t n_rows, int32_t n, int32_t n_steps, int32_t learning,
+                          int32_t use_graph, const htm_run_record *rec) {
+    if (!h) return HTM_ERR_ARGUMENT;
+    flush_tail(h);
+    if (!device_lists) { h->err = "htm_tm_run: null bank of lists"; return HTM_ERR_ARGUMENT; }
+    Dev &d = h->d;
+    if (n_rows < 1 || n < 1 || n > d.k || n > d.C || n_steps < 0) {
+        h->err = "htm_tm_run: n_rows >= 1, 1 <= n <= active_columns and n_steps >= 0";
+        return HTM_ERR_ARGUMENT;
+    }
+    if (rec) {
+        if (rec->struct_bytes != sizeof(htm_run_record)) { h->err = "htm_tm_run: struct_bytes != sizeof(htm_run_record)"; return HTM_ERR_ARGUMENT; }
+        if (!rec->records && !rec->active_column && !rec->column_prediction) { h->err = "htm_tm_run: no record buffer given"; return HTM_ERR_ARGUMENT; }
+    }
+    if (!h->cfg.enable_tm) { h->err = "htm_tm_run: the handle has no Temporal Memory"; return HTM_ERR_STATE; }
+    if (h->world > 1) { h->err = "htm_tm_run: not available on a column-sharded handle"; return HTM_ERR_STATE; }
+    REFUSE_ON_VIEW(h, "htm_tm_run");
+    REJECT_WHEN_AHEAD(h);
+    if (h->shard_open || h->phase_open) { h->err = "htm_tm_run: a step of the handle is open (htm_shard_begin / htm_sp_phase)"; return HTM_ERR_STATE; }
+    if (h->pin_out || h->feed_bank) { h->err = "htm_tm_run: decoding rows or run feedback are set (htm_set_run_predicted_input, htm_set_run_feedback)"; return HTM_ERR_STATE; }
+    // (k_rec_step sums its counts in 24-bit fields of one word: RecDev::acc)
+    if (rec && d.C >= (1 << 24)) { h->err = "htm_tm_run: a recorded run needs column_dim below 2^24"; return HTM_ERR_STATE; }
+    if (feed_lds(d) > FEED_LDS_MAX) { h->err = "htm_tm_run: the column bitmap of this handle does not fit the LDS (column_dim above 524032)"; return HTM_ERR_ARGUMENT; }
+    if (h->reset_bits && h->reset_n != n_rows) { h->err = "htm_tm_run: the reset bits were set for a bank of another n_rows (htm_set_run_resets)"; return HTM_ERR_ARGUMENT; }
+    if (n_steps == 0) return HTM_OK;
+    HIPCHK(h, hipSetDevice(h->device));
+    learning = learning ? 1 : 0;
+    if (learning) weights_touched(h);
+    const bool graph = (use_graph & 1) && !h->profile && n_steps >= h->knob.eager_below;
+    struct ModesOff { htm_handle *h; ~ModesOff() { h->recording = false; h->resetting = false; } } modes_off{h};
+    if (h->reset_bits) {
+        if (!h->d_reset) { int rc = dalloc(h, &h->d_reset, 1); if (rc) return rc; }
+        LAUNCH(h, "tm_reset", k_reset_begin, 1, 64, h->d_reset, h->reset_bits, n_rows);
+    }
+    h->resetting = h->reset_bits != nullptr;
+    if (rec) {
+        if (!h->d_rec) { int rc = dalloc(h, &h->d_rec, 1); if (rc) return rc; }
+        // the descriptor of this call, and the columns the last completed step predicts (predicted_columns_before of record 0)
+        HIPCHK(h, hipMemsetAsync(h->d_rec, 0, sizeof(RecDev), h->stream));
+        LAUNCH(h, "record", k_rec_begin, rec_blocks(d), 256, d, (int)((h->step_host + 1) & 1), h->d_rec, rec->records, rec->active_column,
+               rec->column_prediction, (uint32_t)h->step_host, n_steps);
+    }
+    h->recording = rec != nullptr;
+    refresh_seg_hint(h);                            // what the last run left
+    const int kGraphSteps = h->knob.graph_steps;
+    for (int t = 0; t < n_steps;) {
+        const int p = (int)(h->step_host & 1);
+        if (!graph) {
+            enqueue_tm_run_step(h, p, device_lists, n_rows, n, learning);
+            h->step_host += 1;
+            t += 1;
+            continue;
+        }
+        // (nothing in a graph depends on the step index: the feed launch reads it, and with it the bank row, from the counter block)
+        const int span = n_steps - t >= kGraphSteps ? kGraphSteps : 1;
+        const TmRunGraphKey key{p, h->recording, h->resetting, learning, scan_spec_blocks(h), scan_pool_is_large(h), span, device_lists, n_rows, n};
+        const hipGraphExec_t exec = cached_graph(h->tm_graphs, key, h->stream, h->err, [&] {
+            for (int i = 0; i < span; ++i) enqueue_tm_run_step(h, (p + i) & 1, device_lists, n_rows, n, learning);
+            return 0;
+        });
+        if (!exec) return HTM_ERR_HIP;
+        HIPCHK(h, hipGraphLaunch(exec, h->stream));
+        h->step_host += span;
+        t += span;
+    }
+    h->phase_active = 0;
+    // leave the segment count where the next call finds it (no wait: it may see the one before)
+    HIPCHK(h, hand_back_segments(h, &d.ctr->S, h->stream));
+    return launch_status(h->err);
+}
+
 extern "C" int htm_graph_count(htm_handle *h) {
     if (!h) return HTM_ERR_ARGUMENT;
-    return (int)std::min<size_t>(h->graphs.size() + h->shard_graphs.size(), 0x7fffffff);
+    return (int)std::min<size_t>(h->graphs.size() + h->shard_graphs.size() + h->tm_graphs.size(), 0x7fffffff);
 }
 
 extern "C" int htm_run_plan(htm_handle *h, int32_t n_steps, int32_t use_graph) {
@@ -2377,7 +2469,8 @@ extern "C" int htm_get_info(htm_handle *h, htm_info *out) {
                  ((c.error & 8) ? " dead-segment report (DEAD_CAP)" : "") +
                  ((c.error & 16) ? " (internal) block hand-off timed out in k_sp_emit" : "") +
                  ((c.error & 32) ? " (internal) the middle role's wait for the activation blocks timed out in k_act_mid_rows" : "") +
-                 ((c.error & 64) ? " (not a capacity) htm_pack_columns met a column id outside this handle's input range" : "");
+                 ((c.error & 64) ? " (not a capacity) htm_pack_columns met a column id outside this handle's input range" : "") +
+                 ((c.error & 128) ? " (not a capacity) htm_tm_run met a list row with a repeated column id or one outside [0, column_dim): the results of its steps are invalid" : "");
         return HTM_ERR_CAPACITY;          // *out is filled in all the same
     }
     return HTM_OK;

@@ -118,7 +118,7 @@ __global__ __launch_bounds__(256) void kgrp_rec_begin(const Dev *__restrict__ ta
 }
 
 __global__ __launch_bounds__(256) void kgrp_rec_step(const Dev *__restrict__ tab, int p, RecDev *const *__restrict__ recs) {
-    role_rec_step(tab[blockIdx.y], p, recs[blockIdx.y]);
+    role_rec_step(tab[blockIdx.y], p, recs[blockIdx.y], tab[blockIdx.y].k);
 }
 
 // ------------------------------------------------------------------------------------------

@@ -76,7 +76,9 @@ __global__ __launch_bounds__(256) void k_rec_begin(Dev d, int q, RecDev *r, htm_
 // words of the packed prediction) and its popcount; per block: ONE 64-bit atomic carrying both counts (predicted columns
 // low, bursting columns in the middle, the block's arrival high: RecDev::acc), whose returned value tells the last block to
 // arrive the totals; it writes the record and leaves the descriptor clean for the next step.  (DESIGN.md section 9 has the measurements.)
-__device__ __forceinline__ void role_rec_step(const Dev &d, int p, RecDev *r) {
+// n_active: entries of the step's winner list (d.k; a stand-alone Temporal Memory run may step with fewer: htm_tm_feed.h -- the
+// record then says n_active, and the slots of the active_column row behind them hold -1)
+__device__ __forceinline__ void role_rec_step(const Dev &d, int p, RecDev *r, int n_active) {
     __shared__ uint32_t s_pred, s_burst;
     const uint32_t slot = d.ctr->step[p] - r->base;
     if (slot >= (uint32_t)r->n) return;           // (the same answer in every block: nothing is counted, nothing written)
@@ -85,7 +87,7 @@ __device__ __forceinline__ void role_rec_step(const Dev &d, int p, RecDev *r) {
     if (threadIdx.x == 0) {
         s_pred = 0;
         s_burst = 0;
-        o.active_columns = d.k;
+        o.active_columns = n_active;
         o.predicted_columns_before = r->prev_pred;
         o.active_cells = c->n_active_cells;
         o.winner_cells = c->n_win[p];
@@ -94,8 +96,9 @@ __device__ __forceinline__ void role_rec_step(const Dev &d, int p, RecDev *r) {
     }
     const int stride = (int)gridDim.x * 256, i0 = (int)(blockIdx.x * 256 + threadIdx.x);
     const bool has_i = i0 < d.k;                  // (grid >= k / 256 blocks: one entry per thread at most)
-    const int col = has_i ? d.active_cols[p][i0] : 0;
-    const bool burst = has_i && d.bursting[i0];
+    const bool listed = i0 < n_active;            // (n_active <= k)
+    const int col = listed ? d.active_cols[p][i0] : -1;
+    const bool burst = listed && d.bursting[i0];
     const int words = (d.C + 31) >> 5;
     uint32_t *out = r->colpred ? r->colpred + (size_t)slot * words : nullptr;
     uint32_t n_pred = 0;
@@ -145,4 +148,4 @@ __device__ __forceinline__ void role_rec_step(const Dev &d, int p, RecDev *r) {
     r->acc = 0;
 }
 
-__global__ __launch_bounds__(256) void k_rec_step(Dev d, int p, RecDev *r) { role_rec_step(d, p, r); }
+__global__ __launch_bounds__(256) void k_rec_step(Dev d, int p, RecDev *r) { role_rec_step(d, p, r, d.k); }

@@ -62,7 +62,30 @@ def bool_to_words(mat):
     return (padded.reshape(C, w, 32) << np.arange(32, dtype=np.uint32)).sum(axis=2).astype(np.uint32).reshape(-1)
 
 
+def check_lists(lists, column_dim):
+    """The bank of active-column lists a stand-alone Temporal Memory run reads (htm_tm_run): int32 [n_rows, n], contiguous, after
+    the host-side check that is made once per bank -- two dimensions with at least one row and one column, every id in
+    [0, column_dim), no id twice in a row, n at most column_dim -- else ValueError."""
+    a = np.asarray(lists)
+    if a.ndim != 2 or a.shape[0] < 1 or a.shape[1] < 1:
+        raise ValueError(f"active-column lists: an integer array [n_rows, n] with at least one row and one column, got shape {a.shape}")
+    if not np.issubdtype(a.dtype, np.integer):
+        raise ValueError(f"active-column lists: integer column ids, got dtype {a.dtype}")
+    if a.shape[1] > column_dim:
+        raise ValueError(f"active-column lists: {a.shape[1]} ids per row, but there are only {column_dim} columns")
+    if a.min() < 0 or a.max() >= column_dim:
+        row = int(np.argwhere((a < 0) | (a >= column_dim))[0][0])
+        raise ValueError(f"active-column lists: row {row} has a column id outside [0, {column_dim})")
+    ordered = np.sort(a, axis=1)
+    twice = (ordered[:, 1:] == ordered[:, :-1]).any(axis=1)
+    if twice.any():
+        raise ValueError(f"active-column lists: row {int(np.flatnonzero(twice)[0])} lists a column twice")
+    return np.ascontiguousarray(a, dtype=np.int32)
+
+
 class Engine:
+    LIST_BANKS = 8                                  # upload_lists: device banks of lists kept per engine
+
     def __init__(self, input_dim, column_dim, cell_dim, active_columns, proximal=None, boosting=None,
                  distal=None, seed=0, device=0, stream=None, shard_rank=0, shard_world=1):
         self.lib = L.load()
@@ -125,6 +148,7 @@ class Engine:
         self.device = int(device)
         self._record_bufs = {}                      # run(record=...): device buffers kept for the next recorded call
         self._reset_bufs = {}                       # run(resets=...): packed reset bits per content
+        self._list_bufs = {}                        # upload_lists: device banks of active-column lists per content
         if self.has_sp:
             c0, c1 = self.column_range          # a sharded handle only ever reads its own rows
             self.set_permanence(proximal.permanence[c0:c1] if hasattr(type(proximal), "permanence") else proximal._permanence[c0:c1],
@@ -151,6 +175,7 @@ class Engine:
         v._banks = []
         v._record_bufs = {}
         v._reset_bufs = {}
+        v._list_bufs = {}
         v._auto_grow = False                        # (the parent's pool grows; a view never adds a segment)
         v.is_view = True
         return v
@@ -165,7 +190,7 @@ class Engine:
             self.lib.htm_destroy(h)             # (synchronises its stream: the record buffers are idle after it)
         for ptr, _ in getattr(self, "_record_bufs", {}).values():
             self.lib.hipFree(ptr)
-        for ptr in getattr(self, "_reset_bufs", {}).values():
+        for ptr in list(getattr(self, "_reset_bufs", {}).values()) + list(getattr(self, "_list_bufs", {}).values()):
             self.lib.hipFree(ptr)
 
     # ---- plumbing
@@ -346,6 +371,57 @@ class Engine:
         assert aw.size == self.cell_words
         self._check(self.lib.htm_tm_scan(self.h, aw.ctypes.data_as(C.c_void_p)), "htm_tm_scan")
         self.steps += 1
+
+    def upload_lists(self, lists, check=True):
+        """int32 [n_rows, n] active-column lists -> device address of the bank tm_run reads.  Checked on the host once per bank
+        (check_lists: ValueError; check=False uploads the rows as they are -- the device checks every row it reads all the same,
+        htm_tm_run) and kept by the engine per content: the same array again costs no upload, and the LIST_BANKS most recent
+        banks stay (freed with the engine)."""
+        a = check_lists(lists, self.column_dim) if check else np.ascontiguousarray(lists, dtype=np.int32)
+        key = (a.shape, a.tobytes())
+        bufs = self._list_bufs
+        if key in bufs:
+            bufs[key] = bufs.pop(key)               # (most recent last)
+            return bufs[key]
+        if len(bufs) >= self.LIST_BANKS:
+            self.sync()                             # (a run that reads the oldest bank may still be queued)
+            self.lib.hipFree(bufs.pop(next(iter(bufs))))
+        ptr = C.c_void_p()
+        self._hip_check(self.lib.hipSetDevice(self.device), "hipSetDevice")
+        self._hip_check(self.lib.hipMalloc(C.byref(ptr), max(a.nbytes, 4)), f"hipMalloc({a.nbytes} bytes)")
+        self._hip_check(self.lib.hipMemcpy(ptr, a.ctypes.data_as(C.c_void_p), a.nbytes, L.HIP_MEMCPY_HOST_TO_DEVICE), "hipMemcpy")
+        bufs[key] = ptr.value
+        return ptr.value
+
+    def tm_run(self, device_lists, n_rows, n, n_steps, learning=True, use_graph=True, record=None, resets=None, check=True):
+        """n_steps stand-alone Temporal Memory steps over a device bank of lists (upload_lists: n_rows rows of n ids), the loop
+        on the device (htm_tm_run).  `record`: None, or fields of RECORD_FIELDS other than "predicted_input": the call then
+        returns {field: numpy array over the steps} as _run does -- "active_column" int32[n_steps, active_columns], each row
+        the step's sorted list in its first n slots and -1 behind them.  `resets`: None, or the device address of reset bits
+        for the bank's rows (upload_resets), set for this call only.  `check`: wait for the call and raise CapacityError if
+        it set a sticky flag -- an overflowed pool, or a row the device found invalid (check_capacity)."""
+        fields = () if record is None else tuple(record)
+        if set(fields) - set(RECORD_FIELDS[:3]) or (record is not None and not fields):
+            raise ValueError(f"record: fields from {RECORD_FIELDS[:3]}, at least one (got {fields})")
+        n_steps = int(n_steps)
+        rec = L.HtmRunRecord()
+        shapes = self.record_shapes()
+        self._record_ptrs({f: self._record_buffer(f, max(n_steps, 1) * shapes[f][0]) for f in fields}, rec)
+        if resets is not None:
+            self.set_run_resets(resets, n_rows)
+        try:
+            self._check(self.lib.htm_tm_run(self.h, C.c_void_p(device_lists), int(n_rows), int(n), n_steps, int(bool(learning)),
+                                            1 if use_graph else 0, C.byref(rec) if fields else None), "htm_tm_run")
+        finally:
+            if resets is not None:
+                self.set_run_resets(None, 0)
+        self.steps += n_steps
+        if check:
+            self.check_capacity()
+        if record is None:
+            return None
+        self.sync()                                 # (the records are written on the engine's stream)
+        return {f: self._record_read(f, n_steps * shapes[f][0], shapes[f][1]).reshape(n_steps, shapes[f][0]) for f in fields}
 
     def upload_bank(self, inputs):
         """bool[n, I] -> device address of the packed bank htm_run reads."""

@@ -27,7 +27,7 @@ import weakref
 import numpy as np
 
 from . import _lib as L
-from .engine import RECORD_COUNTERS, RECORD_FIELDS, Engine, words_to_bool
+from .engine import RECORD_COUNTERS, RECORD_FIELDS, Engine, check_lists, words_to_bool
 from .projections import DenseProjection, PredictiveProjection
 from .regularizations import ExponentialBoosting, GlobalInhibition, _Placeholder
 
@@ -389,13 +389,7 @@ class TemporalMemory:
         active_column = np.asarray(sp_state.active_column, dtype=np.int64)
         eng = self._ensure_engine(max(len(active_column), 1))
         retire_states(eng)
-        if len(active_column) > eng.active_columns:          # the reference takes any number of columns: a larger engine,
-            bigger = Engine(0, self.column_dim, self.cell_dim, max(len(active_column), 2 * eng.active_columns),   # same state
-                            distal=self.distal_projection, seed=self.seed, device=self.device)
-            if eng.steps:
-                bigger.import_tm_state(eng.export_tm_state())
-            self._bind(bigger, False)
-            eng = bigger
+        eng = self._engine_for(eng, len(active_column))
         if getattr(eng, "_epsilon", 1e-8) != epsilon:
             eng.set_epsilon(epsilon)
             eng._epsilon = epsilon
@@ -411,6 +405,78 @@ class TemporalMemory:
             eng.import_prev_state(*adopt)
         eng.tm_step(active_column, learning=learning, return_winner_cell=return_winner_cell)
         return self._new_state(active_column)
+
+    def _engine_for(self, eng, n_active):
+        """The reference takes any number of active columns: where `eng` holds fewer, a larger engine with the same state."""
+        if n_active <= eng.active_columns:
+            return eng
+        bigger = Engine(0, self.column_dim, self.cell_dim, max(n_active, 2 * eng.active_columns),
+                        distal=self.distal_projection, seed=self.seed, device=self.device)
+        if eng.steps:
+            bigger.import_tm_state(eng.export_tm_state())
+        self._bind(bigger, False)
+        return bigger
+
+    def run(self, active_columns, steps, learning=True, use_graph=True, record=None, resets=None):
+        """`steps` timesteps over the rows of `active_columns` (int [n_rows, n]: n distinct column ids per row, in any order),
+        cycled: `steps` times process(SimpleNamespace(active_column=active_columns[t % n_rows]), learning=learning), t being this
+        object's step index, with the lists resident in device memory and no per-step host work (htm_tm_run).  Everything the
+        call leaves -- last_state, the segment store -- is what that loop leaves, bit for bit.  The lists are checked once per
+        array (ValueError for an id outside [0, column_dim) or twice in a row) and kept on the device.
+        `record`: as HierarchicalTemporalMemory.run's -- True for the counters, or a tuple of "counters", "active_column" (each
+        step's sorted list, int32[steps, n]) and "column_prediction"; the call then returns a RunRecord.  "predicted_input" raises
+        ValueError: a stand-alone Temporal Memory has no proximal mask to decode with.
+        `resets`: a bool per row -- reset() before every step that reads a row whose flag is set, on the device inside the run.
+        ValueError for cell_dim above 64 and for a plug-in distal_projection (both step on the host: call process()), and for a
+        Temporal Memory inside a fused HierarchicalTemporalMemory (call its run())."""
+        if self._fused:
+            raise ValueError("this TemporalMemory is fused into a HierarchicalTemporalMemory; call its run()")
+        if self.cell_dim > 64:
+            raise ValueError("run(): cell_dim above 64 steps on the host; call process()")
+        if not self._own_distal:
+            raise ValueError("run() keeps the whole loop on the device: not available with a plug-in distal_projection; call process()")
+        fields = None if record is None else _record_fields(record)
+        if fields and "predicted_input" in fields:
+            raise ValueError("run(record='predicted_input'): a stand-alone TemporalMemory has no proximal mask to decode with")
+        lists = check_lists(active_columns, self.column_dim)
+        n_rows, n = lists.shape
+        steps = int(steps)
+        if steps < 0:
+            raise ValueError(f"steps must not be negative, got {steps}")
+        if resets is not None:
+            resets = np.asarray(resets, dtype=np.bool_).ravel()
+            if resets.shape != (n_rows,):
+                raise ValueError(f"resets: one flag per row of active_columns ({n_rows}), got {resets.shape[0]}")
+        eng = self._ensure_engine(n)
+        retire_states(eng)
+        eng = self._engine_for(eng, n)
+        # A pool left at its default size grows as in HierarchicalTemporalMemory.run: batches the free segments are expected to
+        # last (2 x n new segments per step), with a look at the pool between them
+        done, parts, first_step = 0, [], eng.steps
+        while done < steps:
+            batch = steps - done
+            if getattr(eng, "_auto_grow", False):
+                if _grow_if_needed(eng, 2 * n, force_check=True):
+                    self.grow_pool(*eng._grow_to)
+                    eng = self._engine
+                    _grow_if_needed(eng, 2 * n, force_check=True)
+                batch = max(1, min(batch, eng._free_segments // (2 * n) - 1))
+            if getattr(eng, "_epsilon", 1e-8) != 1e-8:      # (process()'s default, which this loop is made of)
+                eng.set_epsilon(1e-8)
+                eng._epsilon = 1e-8
+            part = eng.tm_run(eng.upload_lists(lists, check=False), n_rows, n, batch, learning=learning, use_graph=use_graph, record=fields,
+                              resets=None if resets is None else eng.upload_resets(resets), check=False)
+            if fields is not None:
+                if "active_column" in part:
+                    part["active_column"] = part["active_column"][:, :n]
+                parts.append(part)
+            done += batch
+        if steps:
+            self._new_state(lists[(eng.steps - 1) % n_rows].astype(np.int64))
+        eng.check_capacity()
+        if fields is None:
+            return None
+        return _join_record(parts, fields, first_step, steps, n, self.column_dim)
 
     def _process_host(self, sp_state, prev_state, learning, return_winner_cell, epsilon):
         """networks.py:91-128 on the host, for a `distal_projection=` object that lives there: its `process` / `update` /

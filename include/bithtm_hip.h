@@ -97,7 +97,8 @@ typedef struct htm_info {
     int32_t capacity_error;             /* sticky: 1 = segment pool, 2 = synapse slots, 4 = work list / growth staging,
                                            8 = dead-segment report of a sharded handle, 16 = (internal) a block of the
                                            in-kernel select exchange never arrived: the step's result is invalid, 64 = htm_pack_columns met a
-                                           column id outside this handle's input range */
+                                           column id outside this handle's input range, 128 = htm_tm_run met a list row with a repeated
+                                           column id or one outside [0, column_dim): the results of that call's steps are invalid */
     int32_t words_per_row;              /* packed input words per SP row (input_dim padded to 128 bits) */
     int32_t new_segment_requests;       /* last step: winners without a matching segment (projections.py:271) */
     int32_t recycled_segments;          /* last step: of those, served by recycling (projections.py:80-85) */
@@ -351,7 +352,7 @@ int htm_set_run_resets(htm_handle *h, const uint32_t *device_bits, int32_t n_inp
 int htm_predicted_input(htm_handle *h, int32_t *host_dst);
 int htm_set_run_predicted_input(htm_handle *h, int32_t *device_votes);
 
-/* hipGraphs the handle holds (captured and instantiated by htm_run / htm_prepare / htm_shard_run and their recorded forms);
+/* hipGraphs the handle holds (captured and instantiated by htm_run / htm_prepare / htm_shard_run / htm_tm_run and their recorded forms);
  * diagnostic: a recorded call with other buffers replays the graphs of the one before and adds none. */
 int htm_graph_count(htm_handle *h);
 
@@ -595,6 +596,41 @@ int htm_pack_columns(htm_handle *dst, const int32_t *device_lists, int32_t k, in
  * handle is ahead (HTM_RUN_CONTINUE); HTM_ERR_ARGUMENT for min_votes < 1, max_bits < 0, n_inputs < 1 and a misaligned bank. */
 int htm_encode_votes(htm_handle *h, int32_t min_votes, int32_t max_bits, uint32_t *device_bank, int32_t bank_rows, int32_t row);
 int htm_set_run_feedback(htm_handle *h, uint32_t *device_bank, int32_t n_inputs, int32_t min_votes, int32_t max_bits);
+
+/* Batched stand-alone Temporal Memory runs: n_steps of
+ *   TemporalMemory.process(sp_state, learning=, return_winner_cell=True)   (networks.py:91-128)
+ * -- of htm_tm_step with return_winner_cell = 1 -- whose sp_state.active_column are the rows of a bank of lists that is ALREADY
+ * IN DEVICE MEMORY: device_lists = int32[n_rows][n], each row n distinct column ids in [0, column_dim), in any order (they are
+ * processed in ascending order, as htm_tm_step's); step t reads row t % n_rows, t = the handle's step index, so the rows cycle
+ * with the index across calls as htm_run's bank does.  Nothing is copied or synchronised, and what a call leaves -- cell words,
+ * winner list, the last scan's State fields, the segment store with its permanences, counters, sticky flags, step index -- is
+ * exactly what the n_steps htm_tm_step calls leave.  n (1 <= n <= active_columns) is one value per call; rows of varying
+ * length are not available.
+ *
+ * Per step: the reset launch where reset bits are set, one launch that clears the step's cell words and sorts the step's row
+ * into the winner list (htm_tm_feed.h: it reads the step index from the counter block), then the launches of htm_tm_step, then
+ * the record launch of a recorded call.  use_graph bit 0: replay hipGraphs of one step or of 16 (one stream, no forked
+ * branches; captured once per bank address, n_rows, n, learning flag and the recorded / resetting modes; calls of fewer than
+ * BITHTM_EAGER_BELOW steps launch eagerly); the other bits are ignored.  htm_set_run_resets applies as to htm_run: bit r = a
+ * reset before every step that reads row r (n_inputs there = n_rows here, HTM_ERR_ARGUMENT otherwise).  As htm_run does, the end
+ * of a call copies the segment count into the pinned hint word (no wait).
+ *
+ * rec: NULL, or as htm_run_recorded's (record i = the i-th step of this call), where records[i].active_columns is n and a row
+ * of active_column (active_columns slots, as ever) holds the sorted list in its first n slots and -1 in the rest;
+ * column_prediction as there; predicted_columns_before of a reset step is 0.
+ *
+ * The lists are the caller's contract, checked on the device all the same: a row with a repeated id or an id outside
+ * [0, column_dim) never makes a launch read or write out of bounds -- the step runs on the row's valid ids plus the lowest
+ * columns not listed -- and raises the sticky bit 128 of htm_info.capacity_error: the results of the call are invalid, and
+ * htm_get_info returns HTM_ERR_CAPACITY from then on.
+ *
+ * HTM_ERR_STATE: a handle without a Temporal Memory, a column-sharded handle, an inference view, a handle that is ahead
+ * (HTM_RUN_CONTINUE), one with an open htm_sp_phase or htm_shard_begin step, one with decoding rows or run feedback set
+ * (htm_set_run_predicted_input, htm_set_run_feedback), a recorded call at column_dim of 2^24 or more.  HTM_ERR_ARGUMENT: NULL
+ * pointers, n_rows < 1, n outside [1, active_columns], n_steps < 0, a wrong rec->struct_bytes or no record buffer, reset bits
+ * set for another n_rows, a column_dim whose bitmap does not fit the sorting block's LDS (above 524 032). */
+int htm_tm_run(htm_handle *h, const int32_t *device_lists, int32_t n_rows, int32_t n, int32_t n_steps, int32_t learning,
+               int32_t use_graph, const htm_run_record *rec);
 
 #ifdef __cplusplus
 }
