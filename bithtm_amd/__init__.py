@@ -8,7 +8,7 @@ C ABI (include/bithtm_hip.h, libbithtm_hip.so).  There is no CPU fallback: impor
 engine without the built library raises ImportError."""
 
 from . import networks
-from .networks import InferenceView  # noqa: F401
+from .networks import InferenceView, flip_noise, noise_threshold  # noqa: F401
 from .engine import CapacityError, HtmError  # noqa: F401
 from .group import ModelGroup  # noqa: F401
 from .stack import RegionStack  # noqa: F401

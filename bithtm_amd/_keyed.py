@@ -7,6 +7,7 @@ Used where the timestep is orchestrated on the host because a plug-in object liv
 import numpy as np
 
 STREAM_LEAST_USED, STREAM_GROWTH, STREAM_SEGMENT_JITTER = 1, 2, 3
+STREAM_INPUT_NOISE = 6                              # (4 and 5: the pre-populated pools of htm_populate, device only)
 
 _M1, _M2 = np.uint32(0x7FEB352D), np.uint32(0x846CA68B)
 

@@ -42,6 +42,7 @@
 #include "htm_decode.h"
 #include "htm_stack.h"
 #include "htm_forecast.h"
+#include "htm_noise.h"
 #include "htm_group.h"
 #include "htm_tm_feed.h"
 
@@ -3056,6 +3057,28 @@ extern "C" int htm_pack_columns(htm_handle *h, const int32_t *device_lists, int3
     HIPCHK(h, hipSetDevice(h->device));
     LAUNCH_ON(h, h->stream, pack_lds(h->d), "pack_columns", k_pack_columns, n_rows, PACK_THREADS, h->d, device_lists, k, stride, device_bank,
               bank_rows, first_row);
+    return launch_status(h->err);
+}
+
+// Device-side input noise (htm_noise.h): ring rows for the steps first_step .. first_step + n_rows - 1 from the rows of a source
+// bank and the keyed flips of those steps, and the ring's reset bits from the source's.  Behind whatever the stream holds -- the
+// held-back tail of htm_step reads no bank, and a Spatial Pooler that is ahead (HTM_RUN_CONTINUE) has read the row of the coming
+// step, which a refill writes again with the words it has
+extern "C" int htm_bank_noise(htm_handle *h, const uint32_t *src_bank, int32_t n_src, uint32_t *dst_bank, int32_t n_dst, uint32_t first_step,
+                              int32_t n_rows, uint32_t seed, uint32_t threshold24, const uint32_t *src_resets, uint32_t *dst_resets) {
+    if (!h) return HTM_ERR_ARGUMENT;
+    if (!src_bank || !dst_bank) { h->err = "htm_bank_noise: null bank"; return HTM_ERR_ARGUMENT; }
+    if (src_bank == dst_bank) { h->err = "htm_bank_noise: the source bank and the destination bank must differ"; return HTM_ERR_ARGUMENT; }
+    if (n_src < 1 || n_dst < 1 || n_rows < 0 || n_rows > n_dst) { h->err = "htm_bank_noise: n_src >= 1, n_dst >= 1 and 0 <= n_rows <= n_dst"; return HTM_ERR_ARGUMENT; }
+    if (threshold24 > (1u << 24)) { h->err = "htm_bank_noise: threshold24 above 2^24"; return HTM_ERR_ARGUMENT; }
+    if ((src_resets == nullptr) != (dst_resets == nullptr)) { h->err = "htm_bank_noise: both reset pointers, or neither"; return HTM_ERR_ARGUMENT; }
+    if ((((uintptr_t)src_bank | (uintptr_t)dst_bank) & 15) != 0) { h->err = "htm_bank_noise: the banks must be 16-byte aligned"; return HTM_ERR_ARGUMENT; }
+    if (!h->cfg.enable_sp) { h->err = "htm_bank_noise: needs a handle with the device's own Spatial Pooler (its input rows are packed)"; return HTM_ERR_STATE; }
+    const int blocks = n_rows + (dst_resets ? noise_reset_blocks(n_dst) : 0);
+    if (blocks == 0) return HTM_OK;
+    HIPCHK(h, hipSetDevice(h->device));
+    LAUNCH(h, "bank_noise", k_bank_noise, blocks, NOISE_THREADS, h->d, src_bank, n_src, dst_bank, n_dst, first_step, n_rows, seed, threshold24,
+           src_resets, dst_resets);
     return launch_status(h->err);
 }
 

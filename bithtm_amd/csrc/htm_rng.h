@@ -7,6 +7,7 @@
 //   stream 2  synapse-growth priority  a = segment id, b = flat presynaptic cell id
 //                                                                    (projections.py:120)
 //   stream 3  matching-segment jitter  a = segment id                (projections.py:235)
+//   stream 6  input flip noise         a = input index, step = the timestep the row is read in   (example.py:52)
 #pragma once
 #include <stdint.h>
 
@@ -15,6 +16,7 @@
 #define HTM_STREAM_SEGMENT_JITTER 3u
 #define HTM_STREAM_POPULATE_CELL 4u      // pre-populated pools (htm_populate): a = segment id, b = synapse index
 #define HTM_STREAM_POPULATE_PERM 5u
+#define HTM_STREAM_INPUT_NOISE 6u        // device-side input noise (htm_bank_noise, htm_noise.h)
 
 __host__ __device__ __forceinline__ uint32_t htm_mix32(uint32_t x) {   // "lowbias32"
     x ^= x >> 16;

@@ -540,6 +540,28 @@ class Engine:
         self._check(self.lib.htm_bank_upload(self.h, zeros.ctypes.data_as(C.c_void_p), int(rows), C.byref(ptr)), "htm_bank_upload")
         return ptr.value
 
+    def zero_resets(self, rows):
+        """Device address of a handle-owned array of reset bits for `rows` bank rows, all clear (freed with the handle)."""
+        words = (int(rows) + 31) // 32
+        return self.zero_bank((words + self.words - 1) // self.words)       # (whole bank rows of zeros: at least `words` words)
+
+    def bank_noise(self, src_bank, n_src, dst_bank, n_dst, first_step, n_rows, seed, threshold24, src_resets=None, dst_resets=None):
+        """Ring rows of the steps first_step .. first_step + n_rows - 1: dst row (step % n_dst) = src row (step % n_src) ^ the
+        keyed flips of that step (htm_bank_noise; networks.flip_noise is the definition), and with the two reset arrays the
+        ring's reset bits from the source's.  Enqueued on the engine's stream, no wait."""
+        self._check(self.lib.htm_bank_noise(self.h, C.c_void_p(src_bank), int(n_src), C.c_void_p(dst_bank), int(n_dst),
+                                            int(first_step) & 0xFFFFFFFF, int(n_rows), int(seed) & 0xFFFFFFFF, int(threshold24),
+                                            C.c_void_p(src_resets) if src_resets else None, C.c_void_p(dst_resets) if dst_resets else None),
+                    "htm_bank_noise")
+
+    def read_resets(self, device_bits, rows):
+        """bool[rows]: reset bits in device memory (upload_resets' layout), after a synchronisation."""
+        self.sync()
+        out = np.empty((int(rows) + 31) // 32, dtype=np.uint32)
+        self._hip_check(self.lib.hipMemcpy(out.ctypes.data_as(C.c_void_p), C.c_void_p(device_bits), out.nbytes, L.HIP_MEMCPY_DEVICE_TO_HOST),
+                        "hipMemcpy")
+        return np.unpackbits(out.view(np.uint8), bitorder="little")[:int(rows)].astype(np.bool_)
+
     def read_bank(self, device_bank, rows):
         """bool[rows, input_dim]: the rows of a device bank, after a synchronisation."""
         self.sync()

@@ -5,6 +5,7 @@ the three counters: :55-57), so that its output can be compared line by line.
     python -m bithtm_amd.example --epochs 8
     python -m bithtm_amd.example --epochs 8 --batched   # one C-ABI call per epoch, hipGraph replay
     python -m bithtm_amd.example --epochs 8 --batched_report   # ... recorded: the per-step lines of the default mode
+    python -m bithtm_amd.example --epochs 8 --batched --device_noise   # ... the bank uploaded once, the flip noise drawn on the device
     python -m bithtm_amd.example --epochs 8 --sequence_length 10   # a sequence reset before every 10th pattern
     python -m bithtm_amd.example --epochs 8 --use_reference_implementation   # example.py:30,36-37 (needs the user's `bithtm`)
 """
@@ -46,7 +47,18 @@ def parse(argv):
     ap.add_argument("--sequence_length", type=int, default=0,
                     help="the bank is sequences of this many patterns: a sequence reset before every such pattern (0: none).  "
                          "Stepwise with the reference's idiom, `last_state = get_empty_state()`; batched with run(resets=)")
+    ap.add_argument("--device_noise", action="store_true",
+                    help="with --batched / --batched_report: upload the bank once and draw the flip noise on the device "
+                         "(run(noise=): the keyed generator under --seed, a fresh draw per timestep) instead of drawing it with "
+                         "np.random and uploading a noisy bank per epoch")
     return ap.parse_args(argv)
+
+
+def epoch_input(bank, opts):
+    """(rows, run()'s noise arguments) of one batched epoch: the bank itself and the device's noise, or a host-drawn noisy bank."""
+    if opts.device_noise:
+        return bank, dict(noise=opts.input_noise_probability)
+    return bank ^ (np.random.rand(*bank.shape) < opts.input_noise_probability), {}
 
 
 def reset_rows(opts):
@@ -95,9 +107,9 @@ def run_stepwise(htm, bank, opts, out):
 def run_batched(htm, bank, opts, out):
     width = digits(opts.epochs)
     for epoch in range(opts.epochs):
-        noisy = bank ^ (np.random.rand(*bank.shape) < opts.input_noise_probability)
+        noisy, noise = epoch_input(bank, opts)
         began = time.time()
-        htm.run(noisy, len(noisy), resets=reset_rows(opts))
+        htm.run(noisy, len(noisy), resets=reset_rows(opts), **noise)
         htm.engine.sync()
         rate = len(noisy) / (time.time() - began)
         print(f"epoch {epoch:{width}d}: {rate:.0f} timesteps/s, {htm.engine.info().segments} segments", file=out)
@@ -107,8 +119,8 @@ def run_batched_report(htm, bank, opts, out):
     # (one draw of the epoch's noise: the same MT19937 values, in the same order, as run_stepwise's draw per step)
     report = Report(opts, htm.spatial_pooler.active_columns)
     for epoch in range(opts.epochs):
-        noisy = bank ^ (np.random.rand(*bank.shape) < opts.input_noise_probability)
-        rec = htm.run(noisy, len(noisy), record=True, resets=reset_rows(opts))
+        noisy, noise = epoch_input(bank, opts)
+        rec = htm.run(noisy, len(noisy), record=True, resets=reset_rows(opts), **noise)
         for index, (b, c, i) in enumerate(zip(rec.bursting_columns, rec.correct_columns, rec.incorrect_columns)):
             print(report.line(epoch, index, int(b), int(c), int(i)), file=out)
 
@@ -128,6 +140,8 @@ def main(argv=None, out=sys.stdout):
         htm = HierarchicalTemporalMemory(opts.input_dim, opts.column_dim, opts.cell_dim,
                                          temporal_memory=ReferenceTemporalMemory(opts.column_dim, opts.cell_dim))
     else:
+        if opts.device_noise and not (opts.batched or opts.batched_report):
+            raise SystemExit("--device_noise draws the noise inside a batched run: use it with --batched or --batched_report")
         htm = HierarchicalTemporalMemory(opts.input_dim, opts.column_dim, opts.cell_dim, seed=opts.seed)
     began = time.time()
     (run_batched if opts.batched else run_batched_report if opts.batched_report else run_stepwise)(htm, bank, opts, out)

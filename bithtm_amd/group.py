@@ -21,7 +21,7 @@ import numpy as np
 from . import _lib as L
 from .engine import HtmError, pack_bits
 from .networks import (HierarchicalTemporalMemory, InferenceView, RunRecord, _cached_bank, _encode_params, _grow_if_needed, _join_record,
-                       _record_fields, retire_states)
+                       _noise_ring, _record_fields, noise_threshold, retire_states)
 
 
 class SharedStream:
@@ -200,16 +200,30 @@ class ModelGroup:
         ptrs = [_cached_bank(m, m.engine, x) for m, x in zip(self.models, inputs)]
         return (C.c_void_p * len(ptrs))(*ptrs)
 
-    def run(self, inputs, steps, learning=None, use_graph=True, record=None, resets=None):
+    # run(noise=): steps per fill of the members' noise rings (see HierarchicalTemporalMemory.noise_chunk)
+    noise_chunk = 1024
+
+    def run(self, inputs, steps, learning=None, use_graph=True, record=None, resets=None, noise=0.0, noise_seed=None):
         """`steps` timesteps of every member, member i over the rows of inputs[i] (bool [B, n_inputs, input_dim]), cycled, as
         its own run(inputs[i], steps) would.  Returns None, or (`record`: as run(record=)) one RunRecord per member.
-        learning=None: True, or False in a group with inference views (which refuses True)."""
+        learning=None: True, or False in a group with inference views (which refuses True).
+        `noise`, `noise_seed`: as run(noise=, noise_seed=), one value or one per member; member i then ends as its own
+        run(inputs[i], steps, noise=noise[i], noise_seed=noise_seed[i]) would.  The default seed is each member's own, so members
+        on the same rows still see different noise.  With all of them 0 the call is the one without noise."""
         learning = self._learning(learning)
+        B = len(self.models)
+        if np.ndim(noise) > 1 or (np.ndim(noise) == 1 and len(noise) != B):
+            raise ValueError(f"noise: one probability or one per member ({B}), got shape {np.shape(noise)}")
+        thresholds = [noise_threshold(p) for p in np.broadcast_to(np.asarray(noise, dtype=np.float64), (B,))]
+        seeds = [None] * B
+        if noise_seed is not None:
+            if np.ndim(noise_seed) > 1 or (np.ndim(noise_seed) == 1 and len(noise_seed) != B):
+                raise ValueError(f"noise_seed: one seed or one per member ({B}), got shape {np.shape(noise_seed)}")
+            seeds = [int(x) for x in np.broadcast_to(np.asarray(noise_seed, dtype=np.int64), (B,))]
         if resets is not None:
             raise NotImplementedError("sequence resets inside a group run are not available yet (the follow-up: k_tm_reset per "
                                       "member inside the group's launches); reset members with model.reset() between group calls")
         inputs = np.asarray(inputs, dtype=np.bool_)
-        B = len(self.models)
         if inputs.ndim != 3 or inputs.shape[0] != B or inputs.shape[2] != self.models[0].engine.input_dim:
             raise ValueError(f"inputs: bool [{B}, n_inputs, {self.models[0].engine.input_dim}], got {inputs.shape}")
         fields = None if record is None else _record_fields(record)
@@ -228,14 +242,29 @@ class ModelGroup:
                 while self._grow(2 * k, True):
                     pass
                 n = max(1, min(n, min(m.engine._free_segments for m in self.models) // (2 * k) - 1))
-            banks = self._banks(inputs)
+            banks, n_inputs = self._banks(inputs), inputs.shape[1]
+            if any(thresholds):
+                # each member's ring filled for the steps of this batch and the one behind it (members without noise: a copy of
+                # their rows), then the group over the rings -- the order forecast() uses for its seed rows
+                n = min(n, int(self.noise_chunk))
+                n_inputs = int(self.noise_chunk) + 2
+                rings = []
+                for m, src, thr, seed in zip(self.models, banks, thresholds, seeds):
+                    e = m.engine
+                    if e.steps + n + 1 > 1 << 32:
+                        raise ValueError("run(noise=): the run would pass step 2^32, where the device's step counter wraps")
+                    ring, ring_resets, _ = _noise_ring(m, e, self.noise_chunk)
+                    e.bank_noise(src, inputs.shape[1], ring, n_inputs, e.steps, n + 1, e.seed if seed is None else seed, thr,
+                                 e.upload_resets(np.zeros(inputs.shape[1], dtype=np.bool_)), ring_resets)
+                    rings.append(ring)
+                banks = (C.c_void_p * B)(*rings)
             if fields is None:
-                self._check(self.lib.htm_group_run(self._g, banks, inputs.shape[1], n, int(bool(learning)), int(bool(use_graph)), None),
+                self._check(self.lib.htm_group_run(self._g, banks, n_inputs, n, int(bool(learning)), int(bool(use_graph)), None),
                             "htm_group_run")
             else:
                 recs, shapes = self._records(fields, n)
                 try:
-                    self._check(self.lib.htm_group_run(self._g, banks, inputs.shape[1], n, int(bool(learning)), int(bool(use_graph)), recs),
+                    self._check(self.lib.htm_group_run(self._g, banks, n_inputs, n, int(bool(learning)), int(bool(use_graph)), recs),
                                 "htm_group_run")
                 finally:
                     self._unset_votes()

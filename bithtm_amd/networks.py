@@ -22,11 +22,13 @@ Differences from the reference, all documented in DESIGN.md:
 """
 
 import copy
+import math
 import weakref
 
 import numpy as np
 
 from . import _lib as L
+from ._keyed import STREAM_INPUT_NOISE, draw_unit
 from .engine import RECORD_COUNTERS, RECORD_FIELDS, Engine, check_lists, words_to_bool
 from .projections import DenseProjection, PredictiveProjection
 from .regularizations import ExponentialBoosting, GlobalInhibition, _Placeholder
@@ -725,7 +727,8 @@ class HierarchicalTemporalMemory:
         with np.load(path) as z:
             self.load_state_dict({k: z[k] for k in z.files})
 
-    def run(self, inputs, steps, learning=True, use_graph=True, pipeline=True, continuing=False, record=None, resets=None):
+    def run(self, inputs, steps, learning=True, use_graph=True, pipeline=True, continuing=False, record=None, resets=None,
+            noise=0.0, noise_seed=None):
         """`steps` timesteps over the rows of the boolean matrix `inputs`, cycled, with the input
         bank resident in device memory and no per-step host work (the loop of example.py:48-53).
         Returns None; read `temporal_memory.last_state` or call process() afterwards.  `continuing=True`: the
@@ -735,11 +738,25 @@ class HierarchicalTemporalMemory:
         counters, or a tuple of "counters", "active_column", "column_prediction", "predicted_input"; the call then returns a
         RunRecord over its `steps` steps.
         `resets`: a bool per row of `inputs` -- a sequence reset (see reset()) before every step that reads a row whose flag is
-        set, on the device inside the run; the flags are uploaded beside the bank and kept with it."""
+        set, on the device inside the run; the flags are uploaded beside the bank and kept with it.
+        `noise`: p in [0, 1] -- every step reads its row with fresh flip noise, process(inputs[t % n] ^ flip_noise(noise_seed, t,
+        input_dim, p)) with t this model's step index (the stream of example.py:52 under the keyed generator; `noise_seed`
+        defaults to the model's seed).  The noise is drawn on the device (htm_bank_noise) into a ring of noise_chunk + 2 rows
+        that the run reads instead of the bank, noise_chunk steps per fill; it depends on (seed, step, input) alone, so calls of
+        a and b steps draw what one call of a + b steps draws, and it never repeats with the bank.  0 (the default) is the run
+        without noise, launch for launch.  `resets` keeps its meaning (a flag per row of `inputs`, expanded on the device)."""
         eng = self._fused_engine("run()")
         if not self.spatial_pooler._plain:
             raise RuntimeError("run() keeps the whole loop on the device: not available with plug-in objects that live on the host")
+        threshold = _noise_threshold_arg(noise)
         fields = None if record is None else _record_fields(record)
+        steps = int(steps)
+        if threshold:
+            if eng.shard_world > 1:
+                raise ValueError("run(noise=): not available on a column-sharded model")
+            if eng.steps + max(steps, 0) + 1 > 1 << 32:
+                raise ValueError("run(noise=): the run would pass step 2^32, where the device's step counter wraps")
+            noise_seed = eng.seed if noise_seed is None else int(noise_seed)
         retire_states(eng)
         inputs = np.asarray(inputs, dtype=np.bool_)
         bank = _cached_bank(self, eng, inputs)
@@ -763,10 +780,24 @@ class HierarchicalTemporalMemory:
                     bank = _cached_bank(self, eng, inputs, fresh=True)
                     _grow_if_needed(eng, 2 * k, force_check=True)
                 n = max(1, min(n, eng._free_segments // (2 * k) - 1))
+            if threshold:
+                n = min(n, int(self.noise_chunk))
             last = done + n >= steps
-            part = eng.run(bank, inputs.shape[0], n, learning=learning, use_graph=use_graph, pipeline=pipeline,
-                           continuing=continuing and last, record=fields,
-                           resets=None if resets is None else eng.upload_resets(resets))
+            if threshold:
+                # rows for the steps of this batch and the one behind it, then the batch over the ring (with the ring's reset
+                # bits where the caller gave flags).  A streamed call ends with the Spatial Pooler ahead: it has read the row of
+                # the step behind the batch and, in the four-launch schedule, of the one behind that -- one row more; the next
+                # call's fill writes those rows again with the words they have
+                ring, ring_resets, rows = _noise_ring(self, eng, self.noise_chunk)
+                flags = eng.upload_resets(resets if resets is not None else np.zeros(inputs.shape[0], dtype=np.bool_))
+                eng.bank_noise(bank, inputs.shape[0], ring, rows, eng.steps, n + (2 if continuing and last else 1), noise_seed,
+                               threshold, flags, ring_resets)
+                part = eng.run(ring, rows, n, learning=learning, use_graph=use_graph, pipeline=pipeline,
+                               continuing=continuing and last, record=fields, resets=None if resets is None else ring_resets)
+            else:
+                part = eng.run(bank, inputs.shape[0], n, learning=learning, use_graph=use_graph, pipeline=pipeline,
+                               continuing=continuing and last, record=fields,
+                               resets=None if resets is None else eng.upload_resets(resets))
             if fields is not None:
                 parts.append(part)
             self._streaming = bool(continuing and last and pipeline)
@@ -776,6 +807,10 @@ class HierarchicalTemporalMemory:
         if fields is None:
             return None
         return _join_record(parts, fields, first_step, steps, k, self.column_dim, eng.input_dim)
+
+    # run(noise=): steps per fill of the noise ring (the ring holds two rows more); an attribute so that a caller, or a test, can
+    # cut a noisy run into smaller batches
+    noise_chunk = 1024
 
     def inference_view(self):
         """An InferenceView of this model: a model that shares this one's weights -- the Spatial Pooler's permanences, the segment
@@ -839,7 +874,7 @@ class HierarchicalTemporalMemory:
         eng.encode_votes(min_votes, max_bits, bank, 1, 0)
         return eng.read_bank(bank, 1)[0]
 
-    def forecast(self, steps, min_votes=1, max_bits=0, record=None, use_graph=True, learning=False):
+    def forecast(self, steps, min_votes=1, max_bits=0, record=None, use_graph=True, learning=False, noise=0.0):
         """What the model expects over the next `steps` steps: from its current state, `steps` times
             x = encode_votes(predicted_input(), min_votes, max_bits);  process(x, learning=False)
         with the whole loop on the device (htm_set_run_feedback: each step's votes are encoded into the bank row the next step
@@ -847,9 +882,12 @@ class HierarchicalTemporalMemory:
         The state it leaves, and everything the record holds, are those of that loop bit for bit.  An input with fewer than
         min_votes votes is never set, so a row may be empty -- and stays empty once the model predicts nothing.  learning=True
         (learning from the model's own output) raises ValueError.  To look ahead without moving this model's own stream,
-        forecast on a view:  view = htm.inference_view(); view.run(context, n); view.forecast(k)."""
+        forecast on a view:  view = htm.inference_view(); view.run(context, n); view.forecast(k).  `noise` other than 0 raises
+        ValueError: a forecast reads the rows the model itself wrote, and flipping them is not offered."""
         if learning:
             raise ValueError("forecast(): learning from the model's own output is not available (learning=False only)")
+        if _noise_threshold_arg(noise):
+            raise ValueError("forecast(): input noise inside a forecast is not available (run(noise=) flips the rows of a bank)")
         min_votes, max_bits = _encode_params(min_votes, max_bits)
         eng = self._forecast_engine("forecast()")
         fields = None if record is None else _record_fields(record)
@@ -898,6 +936,31 @@ def encode_votes(votes, min_votes=1, max_bits=0):
     return x
 
 
+def noise_threshold(p):
+    """ceil(p * 2**24): the integer the device compares a 24-bit draw m with, m < noise_threshold(p) being m * 2**-24 < p for
+    every integer m (p * 2**24 is exact in float64).  ValueError unless 0 <= p <= 1."""
+    p = float(p)
+    if not 0.0 <= p <= 1.0:                         # (a NaN fails both comparisons)
+        raise ValueError(f"noise must lie in [0, 1], got {p}")
+    return int(math.ceil(p * 16777216.0))
+
+
+def _noise_threshold_arg(noise):
+    """run(noise=) -> noise_threshold(noise); 0 = no noise.  One number: a per-member list belongs to ModelGroup.run."""
+    if np.ndim(noise) != 0:
+        raise ValueError(f"noise: one probability in [0, 1], got an array of shape {np.shape(noise)}")
+    return noise_threshold(noise)
+
+
+def flip_noise(seed, step, input_dim, p):
+    """bool[input_dim]: the inputs run(noise=p, noise_seed=seed) flips in the step with index `step` -- example.py:52's
+    np.random.rand(input_dim) < p with the keyed generator's stream 6 in place of np.random.rand:
+    draw_unit(seed, STREAM_INPUT_NOISE, step mod 2**32, arange(input_dim)) < p.  The NumPy definition of what htm_bank_noise
+    draws on the device."""
+    noise_threshold(p)
+    return draw_unit(seed, STREAM_INPUT_NOISE, int(step) & 0xFFFFFFFF, np.arange(int(input_dim), dtype=np.uint32)) < float(p)
+
+
 class InferenceView(HierarchicalTemporalMemory):
     """A model that shares its parent's weights in device memory and owns only its stream state (HierarchicalTemporalMemory.
     inference_view(); include/bithtm_hip.h htm_create_view).  process() and run() default to learning=False, and learning=True
@@ -942,11 +1005,12 @@ class InferenceView(HierarchicalTemporalMemory):
 
     compute = process
 
-    def run(self, inputs, steps, learning=False, use_graph=True, pipeline=True, continuing=False, record=None, resets=None):
+    def run(self, inputs, steps, learning=False, use_graph=True, pipeline=True, continuing=False, record=None, resets=None,
+            noise=0.0, noise_seed=None):
         self._no_learning(learning, "run()")
         self._check_parent()
         return super().run(inputs, steps, learning=False, use_graph=use_graph, pipeline=pipeline, continuing=continuing,
-                           record=record, resets=resets)
+                           record=record, resets=resets, noise=noise, noise_seed=noise_seed)
 
     def reset(self):
         self._check_parent()
@@ -960,9 +1024,9 @@ class InferenceView(HierarchicalTemporalMemory):
         self._check_parent()
         return super().predicted_bits(min_votes, max_bits)
 
-    def forecast(self, steps, min_votes=1, max_bits=0, record=None, use_graph=True, learning=False):
+    def forecast(self, steps, min_votes=1, max_bits=0, record=None, use_graph=True, learning=False, noise=0.0):
         self._check_parent()
-        return super().forecast(steps, min_votes, max_bits, record=record, use_graph=use_graph, learning=learning)
+        return super().forecast(steps, min_votes, max_bits, record=record, use_graph=use_graph, learning=learning, noise=noise)
 
     def inference_view(self):
         raise ValueError("inference_view() of a view: make views of the model that owns the weights")
@@ -991,6 +1055,20 @@ def _cached_bank(owner, eng, inputs, fresh=False):
     if fresh or bank is None or bank[0] != key:
         owner._bank = bank = (key, eng.upload_bank(inputs))
     return bank[1]
+
+
+def _noise_ring(owner, eng, chunk):
+    """(ring bank, its reset bits, rows) of run(noise=) on `eng`: chunk + 2 rows at a fixed address, so that the graphs of the runs
+    over it, which are keyed by the bank, are captured once; kept on `owner` until its engine is re-created (as _zero_bank)."""
+    rows = int(chunk) + 2
+    if rows < 3:
+        raise ValueError(f"noise_chunk must be at least 1, got {chunk}")
+    rings = getattr(owner, "_noise_rings", None)
+    if rings is None or rings[0]() is not eng:
+        owner._noise_rings = rings = (weakref.ref(eng), {})
+    if rows not in rings[1]:
+        rings[1][rows] = (eng.zero_bank(rows), eng.zero_resets(rows), rows)
+    return rings[1][rows]
 
 
 def _join_record(parts, fields, first_step, steps, k, column_dim, input_dim=0):

@@ -632,6 +632,32 @@ int htm_set_run_feedback(htm_handle *h, uint32_t *device_bank, int32_t n_inputs,
 int htm_tm_run(htm_handle *h, const int32_t *device_lists, int32_t n_rows, int32_t n, int32_t n_steps, int32_t learning,
                int32_t use_graph, const htm_run_record *rec);
 
+/* Device-side input noise: the input of example.py:52,
+ *   pattern ^ (np.random.rand(input_dim) < p)                                      (example.py:52)
+ * a fresh draw per timestep, with np.random.rand replaced by the keyed generator (stream 6, HTM_STREAM_INPUT_NOISE):
+ *   flip(seed, step)[i] = i < input_dim and draw24(stream_base(seed, 6, step), i, 0) < threshold24
+ * where threshold24 = ceil(p * 2^24), which makes the integer comparison equal to draw24 * 2^-24 < p for every draw.
+ *
+ * A bulk fill of a ring bank: for step = first_step + r (a uint32: it wraps as the device's step counter does), r in [0, n_rows),
+ *   dst_bank row (step % n_dst) = src_bank row (step % n_src) ^ flip(seed, step)
+ * in the handle's bank layout (words_per_row of htm_info; pad bits 0 provided the source's are; every word of a written row is
+ * written; rows outside the window keep their contents).  A run over (dst_bank, n_dst) from step index first_step then reads,
+ * for n_rows steps, the source rows cycled and freshly flipped -- the noise is a function of (seed, step, input) alone, so it
+ * never repeats with either bank, and successive windows continue one another.  If the uint32 step wraps inside the window and
+ * two of its steps share a ring row, the later step's row stays.
+ *
+ * Reset bits (htm_set_run_resets), both pointers or neither: src_resets = one bit per source row; ALL ceil(n_dst / 32) words of
+ * dst_resets are written -- bit j = the source bit of the step whose row ring row j now holds, 0 for a row outside the window.
+ *
+ * One launch on the handle's stream behind whatever is already there; no copy, no wait, and no state of the handle is read: it may
+ * be called on any handle with the device's own Spatial Pooler (inference views included), also while the handle is ahead
+ * (HTM_RUN_CONTINUE) -- the caller then refills the row of the coming step with the words it had.  HTM_ERR_ARGUMENT: NULL banks,
+ * src_bank == dst_bank, n_src < 1, n_dst < 1, n_rows outside [0, n_dst], threshold24 above 2^24, exactly one reset pointer, a
+ * bank that is not 16-byte aligned.  HTM_ERR_STATE: a handle without the device's Spatial Pooler. */
+int htm_bank_noise(htm_handle *h, const uint32_t *src_bank, int32_t n_src, uint32_t *dst_bank, int32_t n_dst,
+                   uint32_t first_step, int32_t n_rows, uint32_t seed, uint32_t threshold24,
+                   const uint32_t *src_resets, uint32_t *dst_resets);
+
 #ifdef __cplusplus
 }
 #endif
