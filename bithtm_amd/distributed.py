@@ -192,9 +192,8 @@ class LocalGroup:
             eng = Engine(input_dim, column_dim, cell_dim, active_columns, proximal=proximal,
                          boosting=parts.get("boosting") or ExponentialBoosting(column_dim, active_columns),
                          distal=parts.get("distal") or PredictiveProjection(column_dim * cell_dim),
-                         seed=seed, device=device, stream=(self.engines[0].stream_handle() if r else None), shard_rank=r, shard_world=world)
-            if r:
-                eng._stream_owner = self.engines[0]
+                         seed=seed, device=device, stream=(self.engines[0].stream_handle() if r else None), shard_rank=r, shard_world=world,
+                         stream_owner=self.engines[0] if r else None)
             self.engines.append(eng)
         self._handles = (C.c_void_p * world)(*[e.h for e in self.engines])
         self._banks = None

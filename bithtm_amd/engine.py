@@ -1,6 +1,7 @@
 """One device engine = one handle of the C ABI (include/bithtm_hip.h): all device state of one
 SpatialPooler and / or TemporalMemory.  Host logic only; every computation is a HIP kernel."""
 
+import contextlib
 import ctypes as C
 
 import numpy as np
@@ -83,11 +84,20 @@ def check_lists(lists, column_dim):
     return np.ascontiguousarray(a, dtype=np.int32)
 
 
+def run_flags(use_graph=True, pipeline=True, continuing=False):
+    """The flag word of the run calls (include/bithtm_hip.h: HTM_RUN_GRAPH, HTM_RUN_NO_PIPELINE, HTM_RUN_CONTINUE)."""
+    return (1 if use_graph else 0) | (0 if pipeline else 2) | (4 if continuing else 0)
+
+
+_NOTHING_TO_SET = contextlib.nullcontext()         # Engine.this_call: the block of a call without settings of its own
+
+
 class Engine:
     LIST_BANKS = 8                                  # upload_lists: device banks of lists kept per engine
+    POOL_LOOK_EVERY = 128                           # pool_look: host-fed steps between two looks at a growing pool
 
     def __init__(self, input_dim, column_dim, cell_dim, active_columns, proximal=None, boosting=None,
-                 distal=None, seed=0, device=0, stream=None, shard_rank=0, shard_world=1):
+                 distal=None, seed=0, device=0, stream=None, shard_rank=0, shard_world=1, stream_owner=None):
         self.lib = L.load()
         self.input_dim = int(input_dim) if proximal is not None else 0
         self.column_dim = int(column_dim)
@@ -124,7 +134,6 @@ class Engine:
             cfg.segment_sampling_synapses = distal.segment_sampling_synapses
             cap = distal.segment_capacity
             cfg.segment_capacity = int(cap) if cap is not None else max(4096, 512 * self.active_columns)
-            self._auto_grow = cap is None           # a default-sized pool grows like the reference's arrays (networks._grow_if_needed)
             cfg.segment_slots = int(distal.segment_slots)
             cfg.segment_capacity_local = int(getattr(distal, "segment_capacity_local", None) or 0)
         cfg.seed = int(seed) & 0xFFFFFFFF
@@ -132,7 +141,6 @@ class Engine:
         # stream: None = a private stream; "default" = the device's default stream; else a hipStream_t of the caller
         cfg.use_caller_stream = int(stream is not None)
         cfg.stream = stream if (stream and stream != "default") else None
-        self._stream_owner = None                   # (an engine created on another engine's stream keeps that engine alive)
         self.shard_rank, self.shard_world = int(shard_rank), max(int(shard_world), 1)
         per = self.column_dim // self.shard_world
         self.column_range = (self.shard_rank * per, (self.shard_rank + 1) * per)
@@ -144,11 +152,9 @@ class Engine:
             raise HtmError(f"htm_create failed ({rc}): {self.lib.htm_last_error(None).decode()}")
         self.h = handle
         self.steps = 0
-        self._banks = []
         self.device = int(device)
-        self._record_bufs = {}                      # run(record=...): device buffers kept for the next recorded call
-        self._reset_bufs = {}                       # run(resets=...): packed reset bits per content
-        self._list_bufs = {}                        # upload_lists: device banks of active-column lists per content
+        # (a default-sized pool grows like the reference's arrays: pool_look)
+        self._host_state(auto_grow=self.has_tm and distal.segment_capacity is None, stream_owner=stream_owner)
         if self.has_sp:
             c0, c1 = self.column_range          # a sharded handle only ever reads its own rows
             self.set_permanence(proximal.permanence[c0:c1] if hasattr(type(proximal), "permanence") else proximal._permanence[c0:c1],
@@ -157,7 +163,24 @@ class Engine:
 
     # the parent's attributes an inference view shares (shape, configuration, step index; not its buffers)
     _VIEW_ATTRS = ("lib", "input_dim", "column_dim", "cell_dim", "active_columns", "has_sp", "has_tm", "cell_words", "shard_rank",
-                   "shard_world", "column_range", "segment_capacity", "segment_slots", "seed", "device", "words", "steps", "_stream_owner")
+                   "shard_world", "column_range", "segment_capacity", "segment_slots", "seed", "device", "words", "steps")
+
+    def _host_state(self, auto_grow, stream_owner):
+        """The host-side state of one handle, all of it: what __init__ and view_of start with."""
+        self._record_bufs = {}                      # run(record=...): device buffers kept for the next recorded call
+        self._reset_bufs = {}                       # run(resets=...): packed reset bits per content
+        self._list_bufs = {}                        # upload_lists: device banks of active-column lists per content
+        self._live_states = []                      # weak references to the States of the current step (networks.retire_states)
+        self._auto_grow = auto_grow                 # pool_look: the pool's size was left to the library
+        self._since_check = self.POOL_LOOK_EVERY    # host-fed steps since the last look (the first step looks)
+        self._free_segments = 0                     # what the last look found, and the sizes to grow to if it asked for growth
+        self._grow_to = (None, None)
+        self._epsilon = 1e-8                        # use_epsilon: what the handle compares with (htm_create's default)
+        self._stream_owner = stream_owner           # (the object whose stream `stream=` named: kept alive with the engine)
+
+    def carry_from(self, old):
+        """The host state a re-created engine keeps from the one it replaces (grow_pool): whether its pool grows."""
+        self._auto_grow = old._auto_grow
 
     @classmethod
     def view_of(cls, parent):
@@ -172,11 +195,7 @@ class Engine:
         if rc != 0:
             raise HtmError(f"htm_create_view failed ({rc}): {v.lib.htm_last_error(None).decode()}")
         v.h = handle
-        v._banks = []
-        v._record_bufs = {}
-        v._reset_bufs = {}
-        v._list_bufs = {}
-        v._auto_grow = False                        # (the parent's pool grows; a view never adds a segment)
+        v._host_state(auto_grow=False, stream_owner=parent._stream_owner)     # (the parent's pool grows; a view never adds a segment)
         v.is_view = True
         return v
 
@@ -214,6 +233,32 @@ class Engine:
             raise CapacityError(self.lib.htm_last_error(self.h).decode())
         return info
 
+    def pool_look(self, per_step, force=False):
+        """Pools whose size the user did not fix (`segment_capacity=None`) follow the reference's growing arrays
+        (utils.py:113-135): every POOL_LOOK_EVERY host-fed steps (`force`: now -- between two device-side batches, never inside
+        one) the engine is asked how full it is (a synchronisation and a read-back: not more often), and True comes back -- with
+        the sizes to grow to in _grow_to and the free segments in _free_segments -- when the free segments would not last another
+        POOL_LOOK_EVERY steps at `per_step` new segments each (every active column bursting), or a segment has filled three
+        quarters of its slots."""
+        if not self._auto_grow or not self.has_tm:
+            return False
+        every = self.POOL_LOOK_EVERY
+        self._since_check += 1
+        if self._since_check < every and not force:
+            return False
+        self._since_check = 0
+        info = self.check_capacity()
+        self._free_segments = self.segment_capacity - info.segments
+        capacity = slots = None
+        if self._free_segments < (every + 1) * per_step:
+            capacity = max(2 * self.segment_capacity, info.segments + 4 * (every + 1) * per_step)
+        if info.segments and self.segment_slots < 512:
+            nsyn = self.read(L.F_SEG_NSYN, np.int32, info.local_segments)
+            if int(nsyn.max(initial=0)) > 3 * self.segment_slots // 4:      # (a segment gains at most one sample of synapses per step)
+                slots = min(512, 2 * self.segment_slots)
+        self._grow_to = (capacity, slots)
+        return capacity is not None or slots is not None
+
     def sync(self):
         self._check(self.lib.htm_sync(self.h), "htm_sync")
 
@@ -225,8 +270,8 @@ class Engine:
 
     def shard_run(self, device_bank, n_inputs, n_steps, learning=True, use_graph=True, pipeline=True):
         """n_steps column-sharded timesteps, the exchange (RCCL) and the loop inside the library (htm_shard_run)."""
-        flags = (1 if use_graph else 0) | (0 if pipeline else 2)
-        self._check(self.lib.htm_shard_run(self.h, C.c_void_p(device_bank), int(n_inputs), int(n_steps), int(bool(learning)), flags), "htm_shard_run")
+        self._check(self.lib.htm_shard_run(self.h, C.c_void_p(device_bank), int(n_inputs), int(n_steps), int(bool(learning)),
+                                           run_flags(use_graph, pipeline)), "htm_shard_run")
         self.steps += n_steps
 
     def import_prev_state(self, prediction, activation, winner_flat, distal):
@@ -272,12 +317,7 @@ class Engine:
             words = np.zeros((bits.size + 31) // 32 * 4, dtype=np.uint8)
             pb = np.packbits(bits, bitorder="little")
             words[:pb.size] = pb
-            ptr = C.c_void_p()
-            self._hip_check(self.lib.hipSetDevice(self.device), "hipSetDevice")
-            self._hip_check(self.lib.hipMalloc(C.byref(ptr), words.size), f"hipMalloc({words.size} bytes)")
-            self._hip_check(self.lib.hipMemcpy(ptr, words.ctypes.data_as(C.c_void_p), words.size, L.HIP_MEMCPY_HOST_TO_DEVICE),
-                            "hipMemcpy")
-            bufs[key] = ptr.value
+            bufs[key] = self.device_buffer(words.size, words)
         return bufs[key]
 
     def set_run_resets(self, device_bits, n_inputs):
@@ -288,6 +328,39 @@ class Engine:
     def set_epsilon(self, epsilon):
         """TemporalMemory.process(epsilon=) (networks.py:91): 0 < epsilon <= 1, compared as float32; stays until set again."""
         self._check(self.lib.htm_set_epsilon(self.h, C.c_float(float(epsilon))), "htm_set_epsilon")
+
+    def use_epsilon(self, epsilon):
+        """The steps that follow compare with `epsilon`: set_epsilon, unless the last use_epsilon asked for the same."""
+        if self._epsilon != epsilon:
+            self.set_epsilon(epsilon)
+            self._epsilon = epsilon
+
+    def this_call(self, resets=None, n_inputs=0, feedback=None, votes=None):
+        """Settings that hold for the calls inside the block only, set in this order and cleared in reverse on the way out,
+        whatever happens inside: `resets` (set_run_resets on banks of n_inputs rows), `feedback` (set_run_feedback's
+        arguments), `votes` (set_run_predicted_input).  None: left alone -- and with nothing to set, the plain run()'s case,
+        a block that costs nothing (streamed callers make a run() call per chunk)."""
+        if resets is None and feedback is None and votes is None:
+            return _NOTHING_TO_SET
+        return self._settings(resets, n_inputs, feedback, votes)
+
+    @contextlib.contextmanager
+    def _settings(self, resets, n_inputs, feedback, votes):
+        undo = []
+        try:
+            if resets is not None:
+                self.set_run_resets(resets, n_inputs)
+                undo.append(lambda: self.set_run_resets(None, 0))
+            if feedback is not None:
+                self.set_run_feedback(*feedback)
+                undo.append(lambda: self.set_run_feedback(None))
+            if votes is not None:
+                self.set_run_predicted_input(votes)
+                undo.append(lambda: self.set_run_predicted_input(None))
+            yield
+        finally:
+            for clear in reversed(undo):
+                clear()
 
     def read(self, field, dtype, count):
         out = np.empty(int(count), dtype=dtype)
@@ -386,12 +459,8 @@ class Engine:
         if len(bufs) >= self.LIST_BANKS:
             self.sync()                             # (a run that reads the oldest bank may still be queued)
             self.lib.hipFree(bufs.pop(next(iter(bufs))))
-        ptr = C.c_void_p()
-        self._hip_check(self.lib.hipSetDevice(self.device), "hipSetDevice")
-        self._hip_check(self.lib.hipMalloc(C.byref(ptr), max(a.nbytes, 4)), f"hipMalloc({a.nbytes} bytes)")
-        self._hip_check(self.lib.hipMemcpy(ptr, a.ctypes.data_as(C.c_void_p), a.nbytes, L.HIP_MEMCPY_HOST_TO_DEVICE), "hipMemcpy")
-        bufs[key] = ptr.value
-        return ptr.value
+        bufs[key] = self.device_buffer(a.nbytes, a, at_least=4)
+        return bufs[key]
 
     def tm_run(self, device_lists, n_rows, n, n_steps, learning=True, use_graph=True, record=None, resets=None, check=True):
         """n_steps stand-alone Temporal Memory steps over a device bank of lists (upload_lists: n_rows rows of n ids), the loop
@@ -400,28 +469,17 @@ class Engine:
         the step's sorted list in its first n slots and -1 behind them.  `resets`: None, or the device address of reset bits
         for the bank's rows (upload_resets), set for this call only.  `check`: wait for the call and raise CapacityError if
         it set a sticky flag -- an overflowed pool, or a row the device found invalid (check_capacity)."""
-        fields = () if record is None else tuple(record)
-        if set(fields) - set(RECORD_FIELDS[:3]) or (record is not None and not fields):
-            raise ValueError(f"record: fields from {RECORD_FIELDS[:3]}, at least one (got {fields})")
+        fields = () if record is None else self._record_fields(record, RECORD_FIELDS[:3])
         n_steps = int(n_steps)
         rec = L.HtmRunRecord()
-        shapes = self.record_shapes()
-        self._record_ptrs({f: self._record_buffer(f, max(n_steps, 1) * shapes[f][0]) for f in fields}, rec)
-        if resets is not None:
-            self.set_run_resets(resets, n_rows)
-        try:
+        self._record_args(fields, n_steps, rec)
+        with self.this_call(resets, n_rows):
             self._check(self.lib.htm_tm_run(self.h, C.c_void_p(device_lists), int(n_rows), int(n), n_steps, int(bool(learning)),
-                                            1 if use_graph else 0, C.byref(rec) if fields else None), "htm_tm_run")
-        finally:
-            if resets is not None:
-                self.set_run_resets(None, 0)
+                                            run_flags(use_graph), C.byref(rec) if fields else None), "htm_tm_run")
         self.steps += n_steps
         if check:
             self.check_capacity()
-        if record is None:
-            return None
-        self.sync()                                 # (the records are written on the engine's stream)
-        return {f: self._record_read(f, n_steps * shapes[f][0], shapes[f][1]).reshape(n_steps, shapes[f][0]) for f in fields}
+        return None if record is None else self._records_read(fields, n_steps, sync=True)
 
     def upload_bank(self, inputs):
         """bool[n, I] -> device address of the packed bank htm_run reads."""
@@ -439,13 +497,8 @@ class Engine:
             resets=None):
         """`resets`: None, or the device address of reset bits for this bank (upload_resets): a sequence reset before every
         step that reads a row whose bit is set (htm_set_run_resets, set for this call only)."""
-        if resets is None:
+        with _NOTHING_TO_SET if resets is None else self.this_call(resets, n_inputs):
             return self._run(device_bank, n_inputs, n_steps, learning, use_graph, pipeline, continuing, record)
-        self.set_run_resets(resets, n_inputs)
-        try:
-            return self._run(device_bank, n_inputs, n_steps, learning, use_graph, pipeline, continuing, record)
-        finally:
-            self.set_run_resets(None, 0)
 
     def _run(self, device_bank, n_inputs, n_steps, learning=True, use_graph=True, pipeline=True, continuing=False, record=None):
         """`continuing`: the next call is another run() on the same bank (HTM_RUN_CONTINUE, include/bithtm_hip.h).
@@ -456,34 +509,23 @@ class Engine:
         if record is None:
             self.run_into(device_bank, n_inputs, n_steps, {}, learning, use_graph, pipeline, continuing)
             return None
-        fields = tuple(record)
-        unknown = set(fields) - set(RECORD_FIELDS)
-        if unknown or not fields:
-            raise ValueError(f"record: fields from {RECORD_FIELDS}, at least one (got {fields})")
-        n = int(n_steps)
-        shapes = self.record_shapes()
-        self.run_into(device_bank, n_inputs, n, {f: self._record_buffer(f, max(n, 1) * shapes[f][0]) for f in fields}, learning, use_graph,
-                      pipeline, continuing)
-        self.sync()                                 # (the records are written on the engine's stream)
-        return {f: self._record_read(f, n * shapes[f][0], shapes[f][1]).reshape(n, shapes[f][0]) for f in fields}
+        fields, n = self._record_fields(record), int(n_steps)
+        self.run_into(device_bank, n_inputs, n, self._record_buffers(fields, n), learning, use_graph, pipeline, continuing)
+        return self._records_read(fields, n, sync=True)
 
     def run_into(self, device_bank, n_inputs, n_steps, buffers, learning=True, use_graph=True, pipeline=True, continuing=False):
         """The run of _run, enqueued only: `buffers` = {record field: device address of its n_steps rows} (record_shapes() words
         per row; empty: a plain htm_run).  The records stay on the device: nothing is synchronised and nothing read back -- the
         caller orders its own work behind the engine's stream (region stacks feed "active_column" to htm_pack_columns)."""
-        flags = (1 if use_graph else 0) | (0 if pipeline else 2) | (4 if continuing else 0)
-        n = int(n_steps)
+        flags, n = run_flags(use_graph, pipeline, continuing), int(n_steps)
         rec = L.HtmRunRecord()
-        self._record_ptrs(buffers, rec)
-        try:
+        votes = self._record_ptrs(buffers, rec)
+        with _NOTHING_TO_SET if votes is None else self.this_call(votes=votes):
             if not set(buffers) - {"predicted_input"}:
                 self._check(self.lib.htm_run(self.h, C.c_void_p(device_bank), int(n_inputs), n, int(bool(learning)), flags), "htm_run")
             else:
                 self._check(self.lib.htm_run_recorded(self.h, C.c_void_p(device_bank), int(n_inputs), n, int(bool(learning)), flags,
                                                       C.byref(rec)), "htm_run_recorded")
-        finally:
-            if "predicted_input" in buffers:
-                self.set_run_predicted_input(None)
         self.steps += n
 
     def pack_columns(self, device_lists, k, n_rows, stride, device_bank, bank_rows, first_row):
@@ -491,19 +533,42 @@ class Engine:
         self._check(self.lib.htm_pack_columns(self.h, C.c_void_p(device_lists), int(k), int(n_rows), int(stride), C.c_void_p(device_bank),
                                               int(bank_rows), int(first_row)), "htm_pack_columns")
 
+    @staticmethod
+    def _record_fields(record, allowed=RECORD_FIELDS):
+        """The fields of a `record` argument as a tuple; ValueError for one that is not in `allowed`, or for none."""
+        fields = tuple(record)
+        if set(fields) - set(allowed) or not fields:
+            raise ValueError(f"record: fields from {allowed}, at least one (got {fields})")
+        return fields
+
+    def _record_buffers(self, fields, n):
+        """{field: device address of the engine's own record buffer, large enough for n steps}."""
+        shapes = self.record_shapes()
+        return {f: self._record_buffer(f, max(n, 1) * shapes[f][0]) for f in fields}
+
     def _record_args(self, fields, n, rec):
         """The record buffers of n steps for `fields` into `rec` (an HtmRunRecord) and, for "predicted_input", the decoding rows
         (set_run_predicted_input: the caller clears them) -> record_shapes()."""
-        shapes = self.record_shapes()
-        self._record_ptrs({f: self._record_buffer(f, max(n, 1) * shapes[f][0]) for f in fields}, rec)
-        return shapes
+        votes = self._record_ptrs(self._record_buffers(fields, n), rec)
+        if votes is not None:
+            self.set_run_predicted_input(votes)
+        return self.record_shapes()
 
-    def _record_ptrs(self, ptrs, rec):
-        """{field: device address} into `rec`; "predicted_input": the decoding rows are set (the caller clears them)."""
+    @staticmethod
+    def _record_ptrs(ptrs, rec):
+        """{field: device address} into `rec` -> the address of the decoding rows ("predicted_input": they are no part of the
+        structure; set_run_predicted_input takes them), or None."""
         rec.struct_bytes = C.sizeof(L.HtmRunRecord)
         rec.records, rec.active_column, rec.column_prediction = (ptrs.get(f) for f in RECORD_FIELDS[:3])
-        if "predicted_input" in ptrs:
-            self.set_run_predicted_input(ptrs["predicted_input"])
+        return ptrs.get("predicted_input")
+
+    def _records_read(self, fields, n, sync=False):
+        """{field: numpy array [n, words per step]} from the engine's own record buffers (`sync`: after waiting for the engine's
+        stream, on which the records are written)."""
+        if sync:
+            self.sync()
+        shapes = self.record_shapes()
+        return {f: self._record_read(f, n * shapes[f][0], shapes[f][1]).reshape(n, shapes[f][0]) for f in fields}
 
     def record_shapes(self):
         """{record field: (int32 words per step, dtype)} of this engine's shape."""
@@ -574,25 +639,43 @@ class Engine:
     # the next recorded call and grown geometrically.
     def _record_buffer(self, field, elements):
         """Device address of a buffer of at least `elements` 32-bit words for one record field."""
-        ptr, size = self._record_bufs.get(field, (None, 0))
-        if ptr is None or size < elements:
-            size = max(elements, 2 * size)
-            new = C.c_void_p()
-            self._hip_check(self.lib.hipSetDevice(self.device), "hipSetDevice")
-            self._hip_check(self.lib.hipMalloc(C.byref(new), 4 * size), f"hipMalloc({4 * size} bytes)")
-            if ptr is not None:
-                self.sync()
-                self.lib.hipFree(ptr)
-            ptr = new.value
-            self._record_bufs[field] = (ptr, size)
-        return ptr
+        return self.kept_buffer(self._record_bufs, field, elements, spare=2)
 
     def _record_read(self, field, elements, dtype):
         """The first `elements` words of a record buffer (after sync())."""
+        return self.read_words(self._record_bufs[field][0], elements, dtype)
+
+    def device_buffer(self, nbytes, data=None, at_least=0):
+        """Device address of `nbytes` new bytes (never fewer than `at_least`) on the engine's device (the caller frees them:
+        hipFree), with the bytes of the numpy array `data` copied in."""
+        ptr = C.c_void_p()
+        self._hip_check(self.lib.hipSetDevice(self.device), "hipSetDevice")
+        self._hip_check(self.lib.hipMalloc(C.byref(ptr), max(nbytes, at_least)), f"hipMalloc({nbytes} bytes)")
+        if data is not None:
+            self._hip_check(self.lib.hipMemcpy(ptr, data.ctypes.data_as(C.c_void_p), data.nbytes, L.HIP_MEMCPY_HOST_TO_DEVICE), "hipMemcpy")
+        return ptr.value
+
+    def kept_buffer(self, bufs, key, words, spare=1):
+        """Device address of the buffer bufs[key] = (address, 32-bit words), kept across calls: made, or made anew when it holds
+        fewer than `words` words -- then `spare` times its old size at least -- after waiting for the engine's stream (everything
+        that used the old buffer is behind that) and freeing the old one."""
+        ptr, size = bufs.get(key, (None, 0))
+        if ptr is None or size < words:
+            size = max(words, spare * size)
+            new = self.device_buffer(4 * size)
+            if ptr is not None:
+                self.sync()
+                self.lib.hipFree(ptr)
+            ptr = new
+            bufs[key] = (ptr, size)
+        return ptr
+
+    def read_words(self, device_words, elements, dtype):
+        """The first `elements` 32-bit words at a device address (after sync())."""
         out = np.empty(elements, dtype=dtype)
         if elements:
-            self._hip_check(self.lib.hipMemcpy(out.ctypes.data_as(C.c_void_p), self._record_bufs[field][0], 4 * elements,
-                                               L.HIP_MEMCPY_DEVICE_TO_HOST), "hipMemcpy")
+            self._hip_check(self.lib.hipMemcpy(out.ctypes.data_as(C.c_void_p), device_words, 4 * elements, L.HIP_MEMCPY_DEVICE_TO_HOST),
+                            "hipMemcpy")
         return out
 
     def _hip_check(self, rc, what):
@@ -607,24 +690,14 @@ class Engine:
                 resets=None):
         """Build (capture + instantiate) the hipGraphs the run() call with these arguments will replay (`record`: a recorded
         run(), whatever its fields -- htm_prepare_recorded; `resets`: a run with reset bits, whichever)."""
-        if resets is not None:
-            self.set_run_resets(resets, n_inputs)
-            try:
-                return self.prepare(device_bank, n_inputs, n_steps, learning, use_graph, pipeline, continuing, record)
-            finally:
-                self.set_run_resets(None, 0)
-        flags = (1 if use_graph else 0) | (0 if pipeline else 2) | (4 if continuing else 0)
-        if record:
-            self._check(self.lib.htm_prepare_recorded(self.h, C.c_void_p(device_bank), int(n_inputs), int(n_steps),
-                                                      int(bool(learning)), flags), "htm_prepare_recorded")
-            return
-        self._check(self.lib.htm_prepare(self.h, C.c_void_p(device_bank), int(n_inputs), int(n_steps), int(bool(learning)),
-                                         flags), "htm_prepare")
+        prepare, what = (self.lib.htm_prepare_recorded, "htm_prepare_recorded") if record else (self.lib.htm_prepare, "htm_prepare")
+        with self.this_call(resets, n_inputs):
+            self._check(prepare(self.h, C.c_void_p(device_bank), int(n_inputs), int(n_steps), int(bool(learning)),
+                                run_flags(use_graph, pipeline, continuing)), what)
 
     def run_plan(self, n_steps, use_graph=True, pipeline=True, continuing=False, **_):
         """What a run() with these arguments would do now (htm_run_plan): dict(hip_graph, pipelined, lean, scan_large)."""
-        flags = (1 if use_graph else 0) | (0 if pipeline else 2) | (4 if continuing else 0)
-        bits = self._check(self.lib.htm_run_plan(self.h, int(n_steps), flags), "htm_run_plan")
+        bits = self._check(self.lib.htm_run_plan(self.h, int(n_steps), run_flags(use_graph, pipeline, continuing)), "htm_run_plan")
         return dict(hip_graph=bool(bits & L.PLAN_GRAPH), pipelined=bool(bits & L.PLAN_PIPELINED), lean=bool(bits & L.PLAN_LEAN),
                     scan_large=bool(bits & L.PLAN_SCAN_LARGE))
 

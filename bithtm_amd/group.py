@@ -20,8 +20,8 @@ import numpy as np
 
 from . import _lib as L
 from .engine import HtmError, pack_bits
-from .networks import (HierarchicalTemporalMemory, InferenceView, RunRecord, _cached_bank, _encode_params, _grow_if_needed, _join_record,
-                       _noise_ring, _record_fields, noise_threshold, retire_states)
+from .networks import (HierarchicalTemporalMemory, InferenceView, RunRecord, _BatchedCall, _batches, _cached_bank, _encode_params, _noise_ring,
+                       _record_fields, noise_threshold, retire_states)
 
 
 class SharedStream:
@@ -54,7 +54,7 @@ def _refuse_member(i, m):
         return f"member {i} has a layer or a distal projection that lives on the host (plug-in objects)"
     if not m.spatial_pooler._plain:
         return f"member {i} has plug-in Spatial Pooler objects that run on the host"
-    if getattr(m, "_streaming", False):
+    if m._streaming:
         return f"member {i} is in the middle of a streamed run() (continuing=True): end the stream first"
     return None
 
@@ -82,12 +82,13 @@ class ModelGroup:
             for attr in ("input_dim", "column_dim", "cell_dim", "active_columns", "segment_capacity", "segment_slots"):
                 if getattr(e, attr) != getattr(e0, attr):
                     raise ValueError(f"member {i}: {attr} {getattr(e, attr)} differs from member 0's {getattr(e0, attr)}")
-            if not self._has_views(models) and getattr(e, "_auto_grow", False) != getattr(e0, "_auto_grow", False):
+            if not self._has_views(models) and e._auto_grow != e0._auto_grow:
                 raise ValueError(f"member {i}: either every member's segment pool is default-sized (and grows) or none is")
         self.models = models
         self.lib = L.load()
         self._g = None
         self._engines = None
+        self._auto_grow = e0._auto_grow and not self._has_views(models)     # (views never add a segment: nothing to look at)
         self._build()
 
     @staticmethod
@@ -151,7 +152,7 @@ class ModelGroup:
 
     def _current(self):
         for i, m in enumerate(self.models):
-            if getattr(m, "_streaming", False):
+            if m._streaming:
                 raise ValueError(f"member {i} is in the middle of a streamed run() (continuing=True): end the stream first")
         for m in self.models:
             if isinstance(m, InferenceView):
@@ -163,7 +164,7 @@ class ModelGroup:
         """Pool growth of default-sized pools, for all members alike: if any member needs more room, every member grows to the
         largest capacity and slot count any of them asks for (the shapes stay equal).  True if the members were re-created."""
         engines = [m.engine for m in self.models]
-        wanted = [e._grow_to for e in engines if _grow_if_needed(e, per_step, force_check=force_check)]
+        wanted = [e._grow_to for e in engines if e.pool_look(per_step, force=force_check)]
         if not wanted:
             return False
         cap = max([engines[0].segment_capacity] + [c for c, _ in wanted if c])
@@ -176,24 +177,21 @@ class ModelGroup:
 
     def _records(self, fields, n):
         """Per member: the record buffers of n steps (the members' own, as run(record=) uses) -> HtmRunRecord array (None when
-        only "predicted_input" is asked for), shapes.  "predicted_input": each member's decoding rows are set (_unset_votes
+        only "predicted_input" is asked for).  "predicted_input": each member's decoding rows are set (_unset_votes
         clears them)."""
         recs = (L.HtmRunRecord * len(self.models))()
-        shapes = {}
         for i, m in enumerate(self.models):
-            shapes = m.engine._record_args(fields, n, recs[i])
-        return (None if fields == ("predicted_input",) else recs), shapes
+            m.engine._record_args(fields, n, recs[i])
+        return None if fields == ("predicted_input",) else recs
 
     def _unset_votes(self):
         for m in self.models:
             m.engine.set_run_predicted_input(None)
 
-    def _read_records(self, fields, n, shapes):
-        self.models[0].engine.sync()            # (the group enqueues on the first member's stream)
-        for m in self.models[1:]:
+    def _read_records(self, fields, n):
+        for m in self.models:                   # (the group enqueues on the first member's stream)
             m.engine.sync()
-        return [{f: m.engine._record_read(f, n * shapes[f][0], shapes[f][1]).reshape(n, shapes[f][0]) for f in fields}
-                for m in self.models]
+        return [m.engine._records_read(fields, n) for m in self.models]
 
     def _banks(self, inputs):
         """Each member's device bank of its rows of `inputs`, uploaded once and cached as run() caches it."""
@@ -231,22 +229,17 @@ class ModelGroup:
             retire_states(m.engine)
         self._current()
         k = self.models[0].active_columns
-        auto = getattr(self.models[0].engine, "_auto_grow", False) and not self._has_views(self.models)
-        first = [m.engine.steps for m in self.models]
-        parts = [[] for _ in self.models]
-        done = 0
-        while done < steps:
-            n = steps - done
-            if auto:
-                # (cut into batches the smallest free-segment budget of any member lasts, with a look at the pools between them)
-                while self._grow(2 * k, True):
-                    pass
-                n = max(1, min(n, min(m.engine._free_segments for m in self.models) // (2 * k) - 1))
+        call = _BatchedCall([m.temporal_memory for m in self.models], fields)
+
+        def pools():        # cut into batches the smallest free-segment budget of any member lasts, with a look at the pools between them
+            while self._grow(2 * k, True):
+                pass
+            return [(min(m.engine._free_segments for m in self.models), 2 * k, 1)]
+        for _, n in _batches(steps, pools if self._auto_grow else None, cap=int(self.noise_chunk) if any(thresholds) else None):
             banks, n_inputs = self._banks(inputs), inputs.shape[1]
             if any(thresholds):
                 # each member's ring filled for the steps of this batch and the one behind it (members without noise: a copy of
                 # their rows), then the group over the rings -- the order forecast() uses for its seed rows
-                n = min(n, int(self.noise_chunk))
                 n_inputs = int(self.noise_chunk) + 2
                 rings = []
                 for m, src, thr, seed in zip(self.models, banks, thresholds, seeds):
@@ -262,25 +255,19 @@ class ModelGroup:
                 self._check(self.lib.htm_group_run(self._g, banks, n_inputs, n, int(bool(learning)), int(bool(use_graph)), None),
                             "htm_group_run")
             else:
-                recs, shapes = self._records(fields, n)
+                recs = self._records(fields, n)
                 try:
                     self._check(self.lib.htm_group_run(self._g, banks, n_inputs, n, int(bool(learning)), int(bool(use_graph)), recs),
                                 "htm_group_run")
                 finally:
                     self._unset_votes()
-                for i, part in enumerate(self._read_records(fields, n, shapes)):
-                    parts[i].append(part)
+                call.add(self._read_records(fields, n))
             for m in self.models:
                 m.engine.steps += n
-            done += n
         for m in self.models:
-            m.temporal_memory._new_state(None)
             m._streaming = False
-        for m in self.models:
-            m.engine.check_capacity()
-        if fields is None:
-            return None
-        return [_join_record(p, fields, f, steps, k, m.column_dim, m.engine.input_dim) for p, f, m in zip(parts, first, self.models)]
+        records = call.finish([steps] * B, [k] * B)
+        return None if fields is None else records
 
     # forecast(): steps per feeding group run (see HierarchicalTemporalMemory.forecast_chunk)
     forecast_chunk = 1024
@@ -301,19 +288,16 @@ class ModelGroup:
         ptrs = [m._zero_bank(e, chunk + 1) for m, e in zip(self.models, engines)]
         banks = (C.c_void_p * B)(*ptrs)
         rows = np.zeros((B, steps, engines[0].input_dim), dtype=np.bool_)
-        first = [e.steps for e in engines]
-        parts = [[] for _ in self.models]
-        done = 0
-        while done < steps:
-            n = min(chunk, steps - done)
+        call = _BatchedCall([m.temporal_memory for m in self.models], fields)
+        for done, n in _batches(steps, cap=chunk):
             start = [e.steps for e in engines]
-            recs = shapes = None
+            recs = None
             try:
                 for e, ptr, (mv, mb) in zip(engines, ptrs, params):
                     e.encode_votes(mv, mb, ptr, chunk + 1, e.steps % (chunk + 1))
                     e.set_run_feedback(ptr, chunk + 1, mv, mb)
                 if fields is not None:
-                    recs, shapes = self._records(fields, n)
+                    recs = self._records(fields, n)
                 self._check(self.lib.htm_group_run(self._g, banks, chunk + 1, n, 0, int(bool(use_graph)), recs), "htm_group_run")
             finally:
                 for e in engines:
@@ -323,17 +307,11 @@ class ModelGroup:
             for e in engines:
                 e.steps += n
             if fields is not None:
-                for i, part in enumerate(self._read_records(fields, n, shapes)):
-                    parts[i].append(part)
+                call.add(self._read_records(fields, n))
             for i, (e, ptr) in enumerate(zip(engines, ptrs)):
                 rows[i, done:done + n] = e.read_bank(ptr, chunk + 1)[(start[i] + np.arange(n)) % (chunk + 1)]
-            done += n
-        for m in self.models:
-            m.temporal_memory._new_state(None)
-            m.engine.check_capacity()
-        if fields is None:
-            return rows
-        return rows, [_join_record(p, fields, f, steps, k, m.column_dim, m.engine.input_dim) for p, f, m in zip(parts, first, self.models)]
+        records = call.finish([steps] * B, [k] * B)
+        return rows if fields is None else (rows, records)
 
     def process(self, X, learning=None, record=True):
         """One timestep of every member, member i on X[i] (bool [B, input_dim]) -- its own process(X[i]) at once.  Returns a
@@ -348,19 +326,19 @@ class ModelGroup:
         for m in self.models:
             retire_states(m.engine)
         self._current()
-        if getattr(e0, "_auto_grow", False) and not self._has_views(self.models):
+        if self._auto_grow:
             self._grow(self.models[0].active_columns, False)
         words = (e0.input_dim + 31) // 32
         packed = np.ascontiguousarray(np.stack([pack_bits(x, words) for x in X]), dtype=np.uint32)
         steps = [m.engine.steps for m in self.models]
-        recs = shapes = None
+        recs = None
         if record:
-            recs, shapes = self._records(("counters",), 1)
+            recs = self._records(("counters",), 1)
         self._check(self.lib.htm_group_step(self._g, packed.ctypes.data_as(C.c_void_p), int(bool(learning)), recs), "htm_group_step")
         for m in self.models:
             m.engine.steps += 1
             m.temporal_memory._new_state(None)
-        counters = np.concatenate([r["counters"] for r in self._read_records(("counters",), 1, shapes)]) if record else None
+        counters = np.concatenate([r["counters"] for r in self._read_records(("counters",), 1)]) if record else None
         for m in self.models:                       # (an overflow is reported in the tick it happened, recorded or not)
             m.engine.check_capacity()
         return RunRecord(np.asarray(steps, dtype=np.int64), counters=counters) if record else None

@@ -44,7 +44,14 @@ class _Lazy:
         self._engine = engine
         self._step = step
         self._cache = {}
-        engine_states(engine).append(weakref.ref(self))
+        engine._live_states.append(weakref.ref(self))
+
+    @classmethod
+    def _eager(cls, **fields):
+        """A State that never was on a device: its fields are these values."""
+        st = cls.__new__(cls)
+        st._engine, st._step, st._cache = None, -1, fields
+        return st
 
     def _fetch(self):
         raise NotImplementedError
@@ -70,18 +77,10 @@ class _Lazy:
             self._cache[name] = value
 
 
-def engine_states(engine):
-    """Weak references to the States of the engine's current step (a plain list: a host-fed step creates two and retires
-    two, and this is on its path)."""
-    s = getattr(engine, "_live_states", None)
-    if s is None:
-        s = engine._live_states = []
-    return s
-
-
 def retire_states(engine):
-    """Called before a new step is enqueued: pin down every State somebody still holds."""
-    live = getattr(engine, "_live_states", None)
+    """Called before a new step is enqueued: pin down every State somebody still holds (engine._live_states: weak references
+    to the States of the current step -- a plain list: a host-fed step creates two and retires two, and this is on its path)."""
+    live = engine._live_states
     if live:
         for ref in live:
             st = ref()
@@ -97,14 +96,6 @@ class SpatialPooler:
 
         def _fetch(self):
             return self._engine.read_sp_fields()
-
-        @classmethod
-        def _eager(cls, active_column, overlaps, boosted_overlaps):
-            st = cls.__new__(cls)
-            object.__setattr__(st, "_engine", None)
-            object.__setattr__(st, "_step", -1)
-            object.__setattr__(st, "_cache", dict(active_column=active_column, overlaps=overlaps, boosted_overlaps=boosted_overlaps))
-            return st
 
     def __init__(self, input_dim, column_dim, active_columns, proximal_projection=None, boosting=None,
                  inhibition=None, device=0):
@@ -191,7 +182,7 @@ class SpatialPooler:
             boosted = eng.read(L.F_BOOSTED, np.float64, C)
         if commit:
             eng.sp_phase(L.SP_COMMIT)
-        return self.State._eager(active_column, overlaps, boosted)
+        return self.State._eager(active_column=active_column, overlaps=overlaps, boosted_overlaps=boosted)
 
     def process(self, input, learning=True):
         """networks.py:26-35."""
@@ -287,7 +278,7 @@ class TemporalMemory:
         """The reference's segment store grows on demand (DynamicArray2D.add_rows / add_cols, utils.py:113-135); the
         device's pool has a fixed capacity.  This re-creates the engine with a larger pool (default: twice the segments)
         and hands the state over -- a host round trip.  Pools left at their default size grow by themselves (see
-        _grow_if_needed); an explicit `segment_capacity=` is a hard limit and overflowing it raises CapacityError."""
+        Engine.pool_look); an explicit `segment_capacity=` is a hard limit and overflowing it raises CapacityError."""
         if self._fused:
             raise RuntimeError("this TemporalMemory is fused into a HierarchicalTemporalMemory; call its grow_pool()")
         eng = self._ensure_engine(1)
@@ -295,24 +286,24 @@ class TemporalMemory:
         dp = self.distal_projection
         dp.segment_capacity = int(segment_capacity or 2 * eng.segment_capacity)
         dp.segment_slots = int(segment_slots or eng.segment_slots)
-        bigger = Engine(0, self.column_dim, self.cell_dim, eng.active_columns, distal=dp, seed=self.seed, device=self.device)
+        self._recreate(eng, eng.active_columns).carry_from(eng)
+        self._last_ref = None
+
+    def _recreate(self, eng, n_active):
+        """A new engine for n_active active columns and the distal projection's pool sizes, with the state of `eng`."""
+        bigger = Engine(0, self.column_dim, self.cell_dim, n_active, distal=self.distal_projection, seed=self.seed, device=self.device)
         if eng.steps:
             bigger.import_tm_state(eng.export_tm_state())
-        bigger._auto_grow = getattr(eng, "_auto_grow", False)
         self._bind(bigger, False)
-        self._last_ref = None
+        return bigger
 
     def get_empty_state(self):
         """networks.py:59-65."""
-        st = TemporalMemory.State.__new__(TemporalMemory.State)
-        object.__setattr__(st, "_engine", None)
-        object.__setattr__(st, "_step", -1)
-        object.__setattr__(st, "_cache", dict(
+        return TemporalMemory.State._eager(
             active_cell=(np.empty(0, dtype=np.int32), np.empty(0, dtype=np.int32)), winner_cell=None,
             cell_activation=np.zeros((self.column_dim, self.cell_dim), dtype=np.bool_),
             cell_prediction=np.zeros((self.column_dim, self.cell_dim), dtype=np.bool_),
-            active_column_bursting=np.empty(0, dtype=np.bool_), distal_state=None))
-        return st
+            active_column_bursting=np.empty(0, dtype=np.bool_), distal_state=None)
 
     def flatten_cell(self, cell):
         """networks.py:67-71."""
@@ -392,15 +383,11 @@ class TemporalMemory:
         eng = self._ensure_engine(max(len(active_column), 1))
         retire_states(eng)
         eng = self._engine_for(eng, len(active_column))
-        if getattr(eng, "_epsilon", 1e-8) != epsilon:
-            eng.set_epsilon(epsilon)
-            eng._epsilon = epsilon
-        if _grow_if_needed(eng, max(len(active_column), 1)):
+        eng.use_epsilon(epsilon)
+        if eng.pool_look(max(len(active_column), 1)):
             self.grow_pool(*eng._grow_to)
             eng = self._engine
-            if getattr(eng, "_epsilon", 1e-8) != epsilon:
-                eng.set_epsilon(epsilon)
-                eng._epsilon = epsilon
+            eng.use_epsilon(epsilon)
         if adopt == "reset":
             eng.reset()
         elif adopt is not None:
@@ -409,15 +396,11 @@ class TemporalMemory:
         return self._new_state(active_column)
 
     def _engine_for(self, eng, n_active):
-        """The reference takes any number of active columns: where `eng` holds fewer, a larger engine with the same state."""
+        """The reference takes any number of active columns: where `eng` holds fewer, a larger engine with the same state (and
+        a pool of the size the distal projection names: one that has grown since is a fixed size from here on)."""
         if n_active <= eng.active_columns:
             return eng
-        bigger = Engine(0, self.column_dim, self.cell_dim, max(n_active, 2 * eng.active_columns),
-                        distal=self.distal_projection, seed=self.seed, device=self.device)
-        if eng.steps:
-            bigger.import_tm_state(eng.export_tm_state())
-        self._bind(bigger, False)
-        return bigger
+        return self._recreate(eng, max(n_active, 2 * eng.active_columns))
 
     def run(self, active_columns, steps, learning=True, use_graph=True, record=None, resets=None):
         """`steps` timesteps over the rows of `active_columns` (int [n_rows, n]: n distinct column ids per row, in any order),
@@ -454,31 +437,17 @@ class TemporalMemory:
         eng = self._engine_for(eng, n)
         # A pool left at its default size grows as in HierarchicalTemporalMemory.run: batches the free segments are expected to
         # last (2 x n new segments per step), with a look at the pool between them
-        done, parts, first_step = 0, [], eng.steps
-        while done < steps:
-            batch = steps - done
-            if getattr(eng, "_auto_grow", False):
-                if _grow_if_needed(eng, 2 * n, force_check=True):
-                    self.grow_pool(*eng._grow_to)
-                    eng = self._engine
-                    _grow_if_needed(eng, 2 * n, force_check=True)
-                batch = max(1, min(batch, eng._free_segments // (2 * n) - 1))
-            if getattr(eng, "_epsilon", 1e-8) != 1e-8:      # (process()'s default, which this loop is made of)
-                eng.set_epsilon(1e-8)
-                eng._epsilon = 1e-8
+        call = _BatchedCall([self], fields)
+        del eng                                     # (the pool step may re-create the engine: the old one goes, device memory and all, as it does)
+        for _, batch in _batches(steps, lambda: [(_looked_at_pool(self, 2 * n), 2 * n, 1)]):
+            eng = self._engine
+            eng.use_epsilon(1e-8)                           # (process()'s default, which this loop is made of)
             part = eng.tm_run(eng.upload_lists(lists, check=False), n_rows, n, batch, learning=learning, use_graph=use_graph, record=fields,
                               resets=None if resets is None else eng.upload_resets(resets), check=False)
-            if fields is not None:
-                if "active_column" in part:
-                    part["active_column"] = part["active_column"][:, :n]
-                parts.append(part)
-            done += batch
-        if steps:
-            self._new_state(lists[(eng.steps - 1) % n_rows].astype(np.int64))
-        eng.check_capacity()
-        if fields is None:
-            return None
-        return _join_record(parts, fields, first_step, steps, n, self.column_dim)
+            if fields is not None and "active_column" in part:
+                part["active_column"] = part["active_column"][:, :n]
+            call.add([part])
+        return call.finish([steps], [n], [lists[(self._engine.steps - 1) % n_rows].astype(np.int64)] if steps else [])[0]
 
     def _process_host(self, sp_state, prev_state, learning, return_winner_cell, epsilon):
         """networks.py:91-128 on the host, for a `distal_projection=` object that lives there: its `process` / `update` /
@@ -526,12 +495,9 @@ class TemporalMemory:
         cell_prediction = np.asarray(distal_state.prediction).reshape(C, K) > epsilon             # :122
         caller_bursting = np.empty_like(bursting)
         caller_bursting[order] = bursting                                                         # (per column, in the caller's order)
-        st = TemporalMemory.State.__new__(TemporalMemory.State)
-        object.__setattr__(st, "_engine", None)
-        object.__setattr__(st, "_step", -1)
-        object.__setattr__(st, "_cache", dict(active_cell=active_cell, winner_cell=winner_cell, cell_activation=cell_activation,
-                                              cell_prediction=cell_prediction, active_column_bursting=caller_bursting,
-                                              distal_state=distal_state))
+        st = TemporalMemory.State._eager(active_cell=active_cell, winner_cell=winner_cell, cell_activation=cell_activation,
+                                         cell_prediction=cell_prediction, active_column_bursting=caller_bursting,
+                                         distal_state=distal_state)
         self._host_last = st
         self._host_step += 1
         return st
@@ -633,8 +599,7 @@ class HierarchicalTemporalMemory:
             proximal, boosting = sp._engine_parts()
             self._engine = Engine(sp.input_dim, column_dim, cell_dim, sp.active_columns,
                                   proximal=proximal, boosting=boosting, distal=tm.distal_projection,
-                                  seed=tm.seed, device=device, stream=None if stream is None else stream.handle)
-            self._engine._stream_owner = stream
+                                  seed=tm.seed, device=device, stream=None if stream is None else stream.handle, stream_owner=stream)
             sp._bind(self._engine, True)
             tm._bind(self._engine, True)
 
@@ -656,9 +621,8 @@ class HierarchicalTemporalMemory:
             proximal._engine, proximal._permanence = None, state["sp_permanence"]      # (the new engine uploads it)
         owner = eng._stream_owner                   # (the stream the model was created on, if it was given one)
         bigger = Engine(sp.input_dim, self.column_dim, self.cell_dim, sp.active_columns, proximal=proximal, boosting=boosting,
-                        distal=dp, seed=tm.seed, device=tm.device, stream=None if owner is None else owner.handle)
-        bigger._stream_owner = owner
-        bigger._auto_grow = getattr(eng, "_auto_grow", False)
+                        distal=dp, seed=tm.seed, device=tm.device, stream=None if owner is None else owner.handle, stream_owner=owner)
+        bigger.carry_from(eng)
         self._engine = bigger
         sp._bind(bigger, True)
         tm._bind(bigger, True)
@@ -672,7 +636,7 @@ class HierarchicalTemporalMemory:
             sp_state = self.spatial_pooler.process(input, learning=learning)
             return sp_state, self.temporal_memory.process(sp_state, learning=learning)
         retire_states(eng)
-        if _grow_if_needed(eng, self.active_columns):
+        if eng.pool_look(self.active_columns):
             self.grow_pool(*eng._grow_to)
             eng = self._engine
         if not self.spatial_pooler._plain:          # plug-in objects on the host: SP phase by phase, then the TM with its winners
@@ -767,21 +731,19 @@ class HierarchicalTemporalMemory:
         # A pool left at its default size grows like the reference's arrays (utils.py:113-135): the run is cut into batches
         # the free segments are expected to last (2 x active_columns new segments per step: every column bursting, twice),
         # with a look at the pool between them.  An overflow inside a batch is still reported, never silent.
-        auto, k = getattr(eng, "_auto_grow", False), self.active_columns
-        done, parts, first_step = 0, [], eng.steps
-        while done < steps:
-            n = steps - done
-            if auto:
-                if _grow_if_needed(eng, 2 * k, force_check=True):
-                    if getattr(self, "_streaming", False):
-                        raise RuntimeError("the segment pool has to grow in the middle of a streamed run(): end the stream (a run() without continuing=True) first")
-                    self.grow_pool(*eng._grow_to)
-                    eng = self._engine
-                    bank = _cached_bank(self, eng, inputs, fresh=True)
-                    _grow_if_needed(eng, 2 * k, force_check=True)
-                n = max(1, min(n, eng._free_segments // (2 * k) - 1))
-            if threshold:
-                n = min(n, int(self.noise_chunk))
+        k = self.active_columns
+        call = _BatchedCall([self.temporal_memory], fields)
+        del eng                                     # (the pool step may re-create the engine: the old one goes, device memory and all, as it does)
+        refuse = "the segment pool has to grow in the middle of a streamed run(): end the stream (a run() without continuing=True) first"
+
+        def regrown():
+            nonlocal bank
+            bank = _cached_bank(self, self._engine, inputs, fresh=True)
+
+        def pool():
+            return [(_looked_at_pool(self, 2 * k, self._streaming and refuse, regrown), 2 * k, 1)]
+        for done, n in _batches(steps, pool, cap=int(self.noise_chunk) if threshold else None):
+            eng = self._engine
             last = done + n >= steps
             if threshold:
                 # rows for the steps of this batch and the one behind it, then the batch over the ring (with the ring's reset
@@ -798,15 +760,11 @@ class HierarchicalTemporalMemory:
                 part = eng.run(bank, inputs.shape[0], n, learning=learning, use_graph=use_graph, pipeline=pipeline,
                                continuing=continuing and last, record=fields,
                                resets=None if resets is None else eng.upload_resets(resets))
-            if fields is not None:
-                parts.append(part)
+            call.add([part])
             self._streaming = bool(continuing and last and pipeline)
-            done += n
-        self.temporal_memory._new_state(None)
-        eng.check_capacity()
-        if fields is None:
-            return None
-        return _join_record(parts, fields, first_step, steps, k, self.column_dim, eng.input_dim)
+        return call.finish([steps], [k])[0]
+
+    _streaming = False                              # in the middle of a streamed run(): the last one ended with continuing=True
 
     # run(noise=): steps per fill of the noise ring (the ring holds two rows more); an attribute so that a caller, or a test, can
     # cut a noisy run into smaller batches
@@ -825,7 +783,7 @@ class HierarchicalTemporalMemory:
             raise ValueError("inference_view(): cell_dim above 64 steps on the host")
         if eng.shard_world > 1:
             raise ValueError("inference_view(): views of column-sharded models are not available")
-        if getattr(self, "_streaming", False):
+        if self._streaming:
             raise ValueError("inference_view(): this model is in the middle of a streamed run() (continuing=True): end the stream first")
         retire_states(eng)
         return InferenceView(self)
@@ -850,7 +808,7 @@ class HierarchicalTemporalMemory:
         eng = self._fused_engine(what)
         if not self.spatial_pooler._plain:
             raise RuntimeError(f"{what} keeps the whole loop on the device: not available with plug-in objects that live on the host")
-        if getattr(self, "_streaming", False):
+        if self._streaming:
             raise RuntimeError(f"{what} in the middle of a streamed run() (continuing=True): end the stream first")
         return eng
 
@@ -895,24 +853,15 @@ class HierarchicalTemporalMemory:
         chunk = int(self.forecast_chunk)
         bank = self._zero_bank(eng, chunk + 1)
         rows = np.zeros((int(steps), eng.input_dim), dtype=np.bool_)
-        done, parts, first_step = 0, [], eng.steps
-        while done < steps:
-            n, s0 = min(chunk, steps - done), eng.steps
+        call = _BatchedCall([self.temporal_memory], fields)
+        for done, n in _batches(steps, cap=chunk):          # (a forecast never looks at the pool: it does not learn)
+            s0 = eng.steps
             eng.encode_votes(min_votes, max_bits, bank, chunk + 1, s0 % (chunk + 1))
-            eng.set_run_feedback(bank, chunk + 1, min_votes, max_bits)
-            try:
-                part = eng.run(bank, chunk + 1, n, learning=False, use_graph=use_graph, record=fields)
-            finally:
-                eng.set_run_feedback(None)
+            with eng.this_call(feedback=(bank, chunk + 1, min_votes, max_bits)):
+                call.add([eng.run(bank, chunk + 1, n, learning=False, use_graph=use_graph, record=fields)])
             rows[done:done + n] = eng.read_bank(bank, chunk + 1)[(s0 + np.arange(n)) % (chunk + 1)]
-            if fields is not None:
-                parts.append(part)
-            done += n
-        self.temporal_memory._new_state(None)
-        eng.check_capacity()
-        if fields is None:
-            return rows
-        return rows, _join_record(parts, fields, first_step, int(steps), self.active_columns, self.column_dim, eng.input_dim)
+        record = call.finish([int(steps)], [self.active_columns])
+        return rows if fields is None else (rows, record[0])
 
 
 def _encode_params(min_votes, max_bits):
@@ -1083,26 +1032,77 @@ def _join_record(parts, fields, first_step, steps, k, column_dim, input_dim=0):
     return RunRecord(first_step + np.arange(steps, dtype=np.int64), **whole)
 
 
-def _grow_if_needed(eng, per_step, every=128, force_check=False):
-    """Pools whose size the user did not fix (`segment_capacity=None`) follow the reference's growing arrays
-    (utils.py:113-135): every `every` host-fed steps the engine is asked how full it is (a synchronisation and a read-back:
-    not more often), and True comes back -- with the sizes to grow to in eng._grow_to -- when the free segments would not
-    last another `every` steps at `per_step` new segments each (every active column bursting), or a segment has filled three
-    quarters of its slots.  (Never in the middle of a device-side batch.)"""
-    if not getattr(eng, "_auto_grow", False) or not eng.has_tm:
-        return False
-    eng._since_check = getattr(eng, "_since_check", every) + 1
-    if eng._since_check < every and not force_check:
-        return False
-    eng._since_check = 0
-    info = eng.check_capacity()
-    eng._free_segments = eng.segment_capacity - info.segments
-    capacity = slots = None
-    if eng._free_segments < (every + 1) * per_step:
-        capacity = max(2 * eng.segment_capacity, info.segments + 4 * (every + 1) * per_step)
-    if info.segments and eng.segment_slots < 512:
-        nsyn = eng.read(L.F_SEG_NSYN, np.int32, info.local_segments)
-        if int(nsyn.max(initial=0)) > 3 * eng.segment_slots // 4:      # (a segment gains at most one sample of synapses per step)
-            slots = min(512, 2 * eng.segment_slots)
-    eng._grow_to = (capacity, slots)
-    return capacity is not None or slots is not None
+def batch_steps(left, free_segments=None, per_step=1, cap=None, period=1, multiple=1):
+    """Steps the next device-side batch of a run may take, of `left` that remain: what `free_segments` free segments are expected
+    to last at `per_step` new segments per step of the model (2 x active columns: every column bursting, twice), less one.  The
+    model steps once per `period` steps of the run, and the answer is a multiple of `multiple`, at least one (the run must get
+    on: a pool that overflows inside the batch is reported, never silent).  None free segments: a pool nobody looks at, no limit.
+    `cap`: a limit of the caller's own (the steps per noise ring, per forecast bank, per chunk of a stack)."""
+    if free_segments is not None:
+        left = min(left, max(multiple, (free_segments // per_step - 1) * period // multiple * multiple))
+    return left if cap is None else min(left, cap)
+
+
+def _looked_at_pool(model, per_step, refuse=None, regrown=None):
+    """The pool step between two batches of a run on `model` (a HierarchicalTemporalMemory or a TemporalMemory): check, grow,
+    check again -> its engine's free segments, or None for a pool that does not grow.  `refuse`: why the pool must not grow now
+    (RuntimeError).  `regrown()`: what the caller has to upload again once model._engine is a new engine."""
+    eng = model._engine
+    if not eng._auto_grow:
+        return None
+    if eng.pool_look(per_step, force=True):
+        if refuse:
+            raise RuntimeError(refuse)
+        model.grow_pool(*eng._grow_to)
+        eng = model._engine
+        if regrown is not None:
+            regrown()
+        eng.pool_look(per_step, force=True)
+    return eng._free_segments
+
+
+def _batches(steps, pools=None, cap=None, multiple=1):
+    """(steps done, steps of the next batch) until `steps` are done.  `pools()`, called before every batch, looks at the pools the
+    batch draws on -- growing them first where that is due -- and yields (free segments, per_step, period) for each
+    (batch_steps); None: nobody looks.  What pools() returns is always consumed in full before the batch is handed out: a
+    generator may do work of its own between two pools and behind the last (the stack uploads level 0's bank again there).
+    `cap`, `multiple`: batch_steps'."""
+    done = 0
+    while done < steps:
+        n = batch_steps(steps - done, cap=cap)
+        for free, per_step, period in (pools() if pools is not None else ()):
+            n = batch_steps(n, free, per_step, period=period, multiple=multiple)
+        yield done, n
+        done += n
+
+
+class _BatchedCall:
+    """The records and the tail of one batched call over the Temporal Memories `tms` (a fused model's temporal_memory shares
+    the model's engine): the parts every batch adds per member, the step each started at, and at the end the new last_state, the
+    sticky flags and one RunRecord per member."""
+
+    def __init__(self, tms, fields):
+        self.tms, self.fields = tms, fields
+        self.first = [tm._engine.steps for tm in tms]
+        self.parts = [[] for _ in tms]
+
+    def add(self, parts):
+        """One batch's record dictionaries, one per member (ignored in a call without a record)."""
+        if self.fields is not None:
+            for mine, part in zip(self.parts, parts):
+                mine.append(part)
+
+    def finish(self, steps, ks, columns=None, read=None):
+        """`steps`, `ks`: per member, the steps it took and the width of its "active_column" rows; `columns`: per member, the
+        active columns its last step was given (None: the device's own, of a fused model; no entry: no new last_state);
+        `read()`: for a caller whose records stay on the device until the end, what add() takes, read after the wait."""
+        for tm, cols in zip(self.tms, [None] * len(self.tms) if columns is None else columns):
+            tm._new_state(cols)
+        for tm in self.tms:
+            tm._engine.check_capacity()
+        if self.fields is None:
+            return [None] * len(self.tms)
+        if read is not None:
+            self.add(read())
+        return [_join_record(p, self.fields, f, n, k, tm.column_dim, tm._engine.input_dim)
+                for p, f, n, k, tm in zip(self.parts, self.first, steps, ks, self.tms)]

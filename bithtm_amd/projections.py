@@ -242,9 +242,7 @@ class PredictiveProjection:
             return
         eng = self._ensure_engine()
         K, C = eng.cell_dim, eng.column_dim
-        if getattr(eng, "_epsilon", 1e-8) != epsilon:
-            eng.set_epsilon(epsilon)
-            eng._epsilon = epsilon
+        eng.use_epsilon(epsilon)
         self.fill_jittered_potential_info(prev_state)
         learning_output = np.asarray(learning_output, dtype=np.int64).reshape(-1)
         input_activation = self._padded(np.asarray(input_activation, dtype=np.bool_)).reshape(C, K)

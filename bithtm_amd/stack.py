@@ -12,14 +12,13 @@ Level l draws with seed + l.  Nothing flows downwards.
     stack.levels[1].predicted_input()             # the levels stay ordinary models for reading
 """
 
-import ctypes as C
 import os
 
 import numpy as np
 
 from . import _lib as L
 from .group import SharedStream
-from .networks import HierarchicalTemporalMemory, InferenceView, _cached_bank, _grow_if_needed, _join_record, _record_fields, retire_states
+from .networks import HierarchicalTemporalMemory, InferenceView, _BatchedCall, _batches, _cached_bank, _looked_at_pool, _record_fields, retire_states
 
 CHUNK_STEPS = 2048              # level-0 steps per chunk of run() (BITHTM_STACK_CHUNK; rounded down to a multiple of the strides' product)
 
@@ -36,7 +35,7 @@ def _refuse_level(i, m):
         return f"level {i} has a layer, a distal projection or plug-in objects that live on the host"
     if m.engine.shard_world > 1:
         return f"level {i} is column-sharded"
-    if getattr(m, "_streaming", False):
+    if m._streaming:
         return f"level {i} is in the middle of a streamed run() (continuing=True): end the stream first"
     return None
 
@@ -174,31 +173,13 @@ class RegionStack:
     # ---- the device path
     def _check_levels(self):
         for i, m in enumerate(self.levels):
-            if getattr(m, "_streaming", False):
+            if m._streaming:
                 raise ValueError(f"level {i} is in the middle of a streamed run() (continuing=True): end the stream first")
 
     def _buffer(self, level, name, words):
-        """Device address of the stack's buffer (level, name) of at least `words` 32-bit words (kept, grown when too small)."""
-        ptr, size = self._bufs.get((level, name), (None, 0))
-        if ptr is None or size < words:
-            eng = self.levels[0].engine
-            new = C.c_void_p()
-            eng._hip_check(self.lib.hipSetDevice(eng.device), "hipSetDevice")
-            eng._hip_check(self.lib.hipMalloc(C.byref(new), 4 * words), f"hipMalloc({4 * words} bytes)")
-            if ptr is not None:
-                eng.sync()                          # (one stream: everything that used the old buffer is behind this)
-                self.lib.hipFree(ptr)
-            ptr = new.value
-            self._bufs[(level, name)] = (ptr, words)
-        return ptr
-
-    def _read_buffer(self, level, name, words, dtype):
-        out = np.empty(words, dtype=dtype)
-        if words:
-            eng = self.levels[0].engine
-            eng._hip_check(self.lib.hipMemcpy(out.ctypes.data_as(C.c_void_p), self._bufs[(level, name)][0], 4 * words,
-                                              L.HIP_MEMCPY_DEVICE_TO_HOST), "hipMemcpy")
-        return out
+        """Device address of the stack's buffer (level, name) of at least `words` 32-bit words (kept, made anew when too small;
+        one stream: level 0's engine waits for everything that used the old one)."""
+        return self.levels[0].engine.kept_buffer(self._bufs, (level, name), words)
 
     def run(self, inputs, steps, learning=True, use_graph=True, record=None, resets=None):
         """`steps` inputs from the rows of the boolean matrix `inputs`, cycled (as HierarchicalTemporalMemory.run), through all
@@ -244,7 +225,6 @@ class RegionStack:
             retire_states(m.engine)
         period = self._period
         chunk = max(S, min(max(self.chunk_steps, 1), max(steps, 1)) // S * S)
-        first = [m.engine.steps for m in self.levels]
         shapes = [m.engine.record_shapes() for m in self.levels]
         # what each level records: the user's fields over the whole call (read back at its end), and, below another level, its
         # active columns -- over one chunk if the user did not ask for them
@@ -256,19 +236,16 @@ class RegionStack:
             rows.append(want)
         self.last_run_chunks = []
         bank = _cached_bank(m0, m0.engine, inputs)
-        done = 0
-        while done < steps:
-            n = min(chunk, steps - done)
-            for l, m in enumerate(self.levels):     # default-sized pools grow as in single-model runs: a look between chunks
-                eng, k = m.engine, m.active_columns
-                if getattr(eng, "_auto_grow", False):
-                    if _grow_if_needed(eng, 2 * k, force_check=True):
-                        m.grow_pool(*eng._grow_to)
-                        eng = m.engine
-                        _grow_if_needed(eng, 2 * k, force_check=True)
-                        if l == 0:
-                            bank = _cached_bank(m0, eng, inputs, fresh=True)
-                    n = min(n, max(S, (eng._free_segments // (2 * k) - 1) * period[l] // S * S))
+        call = _BatchedCall([m.temporal_memory for m in self.levels], fields)
+
+        def pools():                                # default-sized pools grow as in single-model runs: a look between chunks
+            nonlocal bank
+            for l, m in enumerate(self.levels):
+                eng = m.engine
+                yield _looked_at_pool(m, 2 * m.active_columns), 2 * m.active_columns, period[l]
+                if l == 0 and m.engine is not eng:  # (_batches comes back here before the chunk runs: level 0's bank on its new engine)
+                    bank = _cached_bank(m0, m.engine, inputs, fresh=True)
+        for done, n in _batches(steps, pools, cap=chunk, multiple=S):
             below = None                            # device address of the active-column lists of the level below, this chunk
             for l, m in enumerate(self.levels):
                 eng = m.engine
@@ -292,32 +269,21 @@ class RegionStack:
                         row_flags = np.zeros(n_l, dtype=np.bool_)
                         row_flags[(first_row + np.arange(n_l)) % n_l] = flags[done:done + n:period[l]]
                         bits = eng.upload_resets(row_flags)
-                if bits is not None:
-                    eng.set_run_resets(bits, bank_rows)
-                try:
+                with eng.this_call(bits, bank_rows):
                     # (no HTM_RUN_CONTINUE: an upper level working ahead would read a row of the next chunk before it is packed,
                     # and every level is at rest between chunks, where the pools are looked at)
                     eng.run_into(level_bank, bank_rows, n_l, bufs, learning=learning, use_graph=use_graph)
-                finally:
-                    if bits is not None:
-                        eng.set_run_resets(None, 0)
                 m._streaming = False
                 below = bufs.get("active_column")
-            done += n
             self._steps += n
             self.last_run_chunks.append((n, tuple(m.engine.graph_count() for m in self.levels)))
-        for m in self.levels:
-            m.temporal_memory._new_state(None)
-        for m in self.levels:
-            m.engine.check_capacity()               # (synchronises: an overflow is reported by the call it happened in)
-        if fields is None:
-            return None
-        out = []
-        for l, m in enumerate(self.levels):
-            total = steps // period[l]
-            part = {f: self._read_buffer(l, f, total * shapes[l][f][0], shapes[l][f][1]).reshape(total, shapes[l][f][0]) for f in fields}
-            out.append(_join_record([part], fields, first[l], total, m.active_columns, m.column_dim, m.engine.input_dim))
-        return out
+        totals = [steps // p for p in period]
+
+        def read():                                 # (after finish() has synchronised: an overflow is reported by the call it happened in)
+            return [{f: m0.engine.read_words(self._bufs[(l, f)][0], n * shapes[l][f][0], shapes[l][f][1]).reshape(n, shapes[l][f][0]) for f in fields}
+                    for l, n in enumerate(totals)]
+        records = call.finish(totals, [m.active_columns for m in self.levels], read=read)
+        return None if fields is None else records
 
     # ---- checkpoints
     def state_dict(self):
