@@ -20,6 +20,7 @@
 #include <stdio.h>
 #include <string.h>
 #include <algorithm>
+#include <cfloat>
 #include <climits>
 #include <chrono>
 #include <map>
@@ -133,6 +134,8 @@ struct htm_handle {
     int ahead_n_inputs, ahead_learning;   //   and the front of the one after it
     bool ahead_lean;                      //   ... in the three-launch schedule (else the four-launch one)
     int phase_active;                     // htm_sp_phase: length of the current winner list
+    bool phase_wide;                      // ... the keys of the current step were made from values the HOST supplied (BOOST, SELECT with
+                                          // data): nothing bounds their significant bits, the select resolves all 64 key bits
     bool import_keep;                     // htm_import_begin(HTM_IMPORT_PREV_STATE): the commit leaves the store, the step index and the sticky flags alone
     bool phase_open;                      // ... phases of the current (not yet closed) timestep have run: the Spatial Pooler
                                           // fields htm_read returns are that step's
@@ -1314,6 +1317,7 @@ static int close_open_phases(htm_handle *h) {
     if (h->cfg.enable_sp) HIPCHK(h, hipMemsetAsync(h->d.hist0 + (size_t)p * HIST0_PAR, 0, (size_t)HIST0_PAR * 4, h->stream));
     h->phase_open = false;
     h->phase_active = 0;
+    h->phase_wide = false;
     return 0;
 }
 
@@ -1436,6 +1440,30 @@ extern "C" int htm_sp_phase(htm_handle *h, int32_t phase, const void *data, int6
     Dev &d = h->d;
     const int p = (int)(h->step_host & 1);
     const int c256 = (d.C + 255) / 256;
+    // values from the host are checked before anything is enqueued: a refused call leaves the handle as it was
+    if (phase == HTM_SP_BOOST) {
+        if (!data || count != d.C) { h->err = "htm_sp_phase(BOOST): need column_dim overlaps"; return HTM_ERR_ARGUMENT; }
+        const int32_t *ov = (const int32_t *)data;
+        for (int64_t i = 0; i < count; ++i)
+            if (ov[i] < 0) { h->err = "htm_sp_phase(BOOST): overlaps are counts, column " + std::to_string(i) + " has a negative one"; return HTM_ERR_ARGUMENT; }
+    }
+    if (phase == HTM_SP_SELECT && data) {
+        if (count != d.C) { h->err = "htm_sp_phase(SELECT): need column_dim boosted overlaps"; return HTM_ERR_ARGUMENT; }
+        const double *bo = (const double *)data;
+        for (int64_t i = 0; i < count; ++i)
+            if (!(bo[i] >= 0.0) || bo[i] > DBL_MAX) {       // (NaN fails the first comparison; -0.0 passes: it is zero)
+                h->err = "htm_sp_phase(SELECT): boosted overlaps must be finite and >= 0 (any double in [0, DBL_MAX], -0.0 counts as 0); column " +
+                         std::to_string(i) + " is NaN, infinite or negative";
+                return HTM_ERR_ARGUMENT;
+            }
+    }
+    // Keys made from the host's values are selected at full width: the fused step's shortcuts -- low_zero key bits known to be
+    // zero, the last digits left to role_emit's record exchange -- rest on boosted = float32 factor x overlap <= input_dim,
+    // which a caller's own numbers need not obey.  All SEL_MAX_PASSES digits are launched on a copy of the descriptor (the
+    // handle's own, which htm_step, htm_run and the graphs see, is untouched), then the count and the plain emit.
+    Dev wide = d;
+    wide.sel_passes = SEL_MAX_PASSES;
+    wide.low_zero = 0;
     // the top-digit histogram of this step's keys is accumulated by the phase that makes the keys and consumed (and
     // cleared) by the select: a phase that makes keys starts from a clean one, whatever ran before it in this step
     if (phase == HTM_SP_OVERLAP || phase == HTM_SP_BOOST || (phase == HTM_SP_SELECT && data))
@@ -1446,24 +1474,34 @@ extern "C" int htm_sp_phase(htm_handle *h, int32_t phase, const void *data, int6
             int rc = stage_input(h, (const uint32_t *)data);
             if (rc) return rc;
             LAUNCH(h, "sp_overlap", k_sp_overlap, h->sz.sp_blocks, RB, d, d.input_stage, 1, h->sz.G, p, p, 0, 0);
+            h->phase_wide = false;
             break;
         }
         case HTM_SP_BOOST: {                       // ExponentialBoosting.process on overlaps from the host; data = int32[C]
-            if (!data || count != d.C) { h->err = "htm_sp_phase(BOOST): need column_dim overlaps"; return HTM_ERR_ARGUMENT; }
             HIPCHK(h, hipMemcpyAsync(d.overlap[p], data, (size_t)d.C * 4, hipMemcpyHostToDevice, h->stream));
             HIPCHK(h, hipStreamSynchronize(h->stream));         // (the caller's buffer is borrowed for the call only)
-            LAUNCH(h, "sp_keys", k_sp_keys, std::min((d.C + RB - 1) / RB, 256), RB, d, p, 1);
+            LAUNCH(h, "sp_keys", k_sp_keys, std::min((d.C + RB - 1) / RB, 256), RB, wide, p, SP_KEYS_BOOST);
+            h->phase_wide = true;
             break;
         }
         case HTM_SP_SELECT: {                      // GlobalInhibition.process; data = double[C] boosted overlaps, or NULL: the device's
             if (data) {
-                if (count != d.C) { h->err = "htm_sp_phase(SELECT): need column_dim boosted overlaps"; return HTM_ERR_ARGUMENT; }
                 HIPCHK(h, hipMemcpyAsync(d.boosted[p], data, (size_t)d.C * 8, hipMemcpyHostToDevice, h->stream));
                 HIPCHK(h, hipStreamSynchronize(h->stream));
-                LAUNCH(h, "sp_keys", k_sp_keys, std::min((d.C + RB - 1) / RB, 256), RB, d, p, 0);
+                LAUNCH(h, "sp_keys", k_sp_keys, std::min((d.C + RB - 1) / RB, 256), RB, wide, p, SP_KEYS_HOST);
+                h->phase_wide = true;
             }
-            for (int pass = 1; pass < d.sel_passes; ++pass) LAUNCH(h, "sp_select", k_sel_pass, h->sz.sel_blocks, RB, d, pass, p);
-            enqueue_sp_back(h, d.input_stage, 1, p, 0, 0, false);          // the list and its bitmap, nothing else
+            if (h->phase_wide) {
+                for (int pass = 1; pass < wide.sel_passes; ++pass) LAUNCH(h, "sp_select", k_sel_pass, h->sz.sel_blocks, RB, wide, pass, p);
+                LAUNCH(h, "sp_count", k_sp_count, h->sz.c256_blocks, 256, wide, p);
+                LAUNCH(h, "sp_emit", k_sp_emit, h->sz.c256_blocks, 256, wide, p, 0, 0, 0, 0, h->sz.c256_blocks);
+                // (the k-th key of SP_KEYS_HOST is the double's own bits, not a select_key: it says nothing about where the fused
+                // step's window should be -- the next whole step takes the digit passes, as a handle's first step does)
+                h->window_known = !data;
+            } else {
+                for (int pass = 1; pass < d.sel_passes; ++pass) LAUNCH(h, "sp_select", k_sel_pass, h->sz.sel_blocks, RB, d, pass, p);
+                enqueue_sp_back(h, d.input_stage, 1, p, 0, 0, false);          // the list and its bitmap, nothing else
+            }
             break;
         }
         case HTM_SP_ACTIVE: {                      // a winner list from the host; data = int32[count], distinct, any order
@@ -1502,6 +1540,7 @@ extern "C" int htm_sp_phase(htm_handle *h, int32_t phase, const void *data, int6
     }
     if (phase == HTM_SP_SELECT) h->phase_active = d.k;
     h->phase_open = phase != HTM_SP_COMMIT;
+    if (phase == HTM_SP_COMMIT) h->phase_wide = false;
     return launch_status(h->err);
 }
 

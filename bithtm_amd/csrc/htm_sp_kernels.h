@@ -1363,6 +1363,11 @@ __global__ __launch_bounds__(256) void k_sp_learn(Dev d, const uint32_t *__restr
 // keys + top-digit histogram from boosted overlaps that are already in d.boosted[p] (a foreign boosting object computed
 // them), or from overlaps in d.overlap[p] through the device's own boosting (a foreign proximal projection computed
 // those): what role_overlap does after its popcounts
+// SP_KEYS_HOST: the caller's doubles may be ANY finite value >= 0 (htm_sp_phase has checked that), far outside the exponents
+// select_key's 9 bits order, so the key is the double's own bit pattern -- of non-negative doubles an order-preserving image
+// as it stands, denormals included -- with the sign cleared: -0.0 is zero.  Such keys are only ever compared with each other,
+// by a select that resolves all 64 bits (htm_sp_phase launches it on a descriptor with sel_passes = SEL_MAX_PASSES).
+enum { SP_KEYS_HOST = 0, SP_KEYS_BOOST = 1 };
 __global__ __launch_bounds__(RB) void k_sp_keys(Dev d, int p, int from_overlap) {
     __shared__ uint32_t h[SEL_BINS];
     const int gtid = blockIdx.x * RB + threadIdx.x, nthreads = gridDim.x * RB;
@@ -1384,7 +1389,7 @@ __global__ __launch_bounds__(RB) void k_sp_keys(Dev d, int p, int from_overlap) 
         } else {
             bo = d.boosted[p][c];
         }
-        const u64 key = select_key(bo);
+        const u64 key = from_overlap ? select_key(bo) : (u64)__double_as_longlong(bo) & 0x7FFFFFFFFFFFFFFFull;
         d.key[p][c] = key;
         atomicAdd(&h[(uint32_t)(key >> sel_shift(0))], 1u);
     }

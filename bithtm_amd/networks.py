@@ -31,7 +31,7 @@ from . import _lib as L
 from ._keyed import STREAM_INPUT_NOISE, draw_unit
 from .engine import RECORD_COUNTERS, RECORD_FIELDS, Engine, check_lists, words_to_bool
 from .projections import DenseProjection, PredictiveProjection
-from .regularizations import ExponentialBoosting, GlobalInhibition, _Placeholder
+from .regularizations import ExponentialBoosting, GlobalInhibition, _Placeholder, checked_boosted, checked_overlaps
 
 
 class _Lazy:
@@ -153,14 +153,17 @@ class SpatialPooler:
             eng.sp_phase(L.SP_OVERLAP, input)                                         # :27 (and :28 with the device's boosting)
         else:
             overlaps = np.asarray(self.proximal_projection.process(input))
-            if self._own_boosting:
-                eng.sp_phase(L.SP_BOOST, overlaps, np.int32)                          # :28
+            if self._own_boosting:                                                    # :28 (whole numbers, or a ValueError: never truncated)
+                counts = checked_overlaps(overlaps, f"{type(self.proximal_projection).__name__}.process")
+                eng.sp_phase(L.SP_BOOST, counts, np.int32)
         if not self._own_boosting:
             if overlaps is None:
                 overlaps = eng.read(L.F_OVERLAPS, np.int32, C).astype(np.int64)
             boosted = np.asarray(self.boosting.process(overlaps))                     # :28
         if self._own_inhibition:
-            eng.sp_phase(L.SP_SELECT, None if self._own_boosting else boosted, np.float64)     # :29
+            # (a foreign boosting's values: finite and >= 0, or a ValueError; the State hands back the caller's own array)
+            values = None if self._own_boosting else checked_boosted(boosted, f"{type(self.boosting).__name__}.process")
+            eng.sp_phase(L.SP_SELECT, values, np.float64)                             # :29
             active_column = eng.read(L.F_ACTIVE_COLUMN, np.int32, self.active_columns).astype(np.int64)
         else:
             if boosted is None:

@@ -202,9 +202,17 @@ int htm_tm_scan(htm_handle *h, const uint32_t *active_words);
 typedef enum htm_sp_phase_id {
     HTM_SP_OVERLAP = 1, /* DenseProjection.process (projections.py:18-21) + ExponentialBoosting.process
                            (regularizations.py:15-17); data = packed input as for htm_step */
-    HTM_SP_BOOST = 2,   /* ExponentialBoosting.process on overlaps computed elsewhere; data = int32[column_dim] */
+    HTM_SP_BOOST = 2,   /* ExponentialBoosting.process on overlaps computed elsewhere; data = int32[column_dim], every
+                           entry >= 0 (a negative one: HTM_ERR_ARGUMENT, nothing enqueued).  The product float32 factor x
+                           overlap is rounded once to double (exact up to 29-bit overlaps) */
     HTM_SP_SELECT = 3,  /* GlobalInhibition.process (regularizations.py:28-29) on the device's boosted overlaps
-                           (data = NULL) or on boosted overlaps computed elsewhere (data = double[column_dim]) */
+                           (data = NULL) or on boosted overlaps computed elsewhere (data = double[column_dim]).
+                           Accepted data: every finite double >= 0 -- denormals, values up to DBL_MAX, any mix; -0.0
+                           counts as 0.  The result is exactly the active_columns largest, lower column first among
+                           equal values, over all 64 bits of each value (also after HTM_SP_BOOST: the select of values
+                           that came from the host launches every radix digit and assumes nothing about their width).
+                           NaN, +-inf or a negative value: HTM_ERR_ARGUMENT with a message naming the column, nothing
+                           enqueued, the handle stays usable.  HTM_F_BOOSTED reads back the caller's own values */
     HTM_SP_ACTIVE = 4,  /* a winner list chosen elsewhere; data = int32[count] distinct columns, count <= active_columns */
     HTM_SP_LEARN = 5,   /* DenseProjection.update (projections.py:23-24) on the current winner list; data = packed
                            input, or NULL: the input of HTM_SP_OVERLAP */
