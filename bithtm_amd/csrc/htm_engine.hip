@@ -1577,10 +1577,18 @@ extern "C" int htm_tm_step(htm_handle *h, const int32_t *active_column, int32_t 
 // punishment mask and the previous State chosen by the caller.  The previous step's side -- prev_state, input_activation,
 // winner_input -- is what the handle holds as its previous step (written there with the state import if it is not the
 // handle's own: HTM_IMPORT_PREV_STATE).  columns[i] (distinct, any order, at most active_columns) has learning cells
-// winner_words[i] (bit j = cell j; `output_learning` of :261-262 for that column) of which unaccounted_words[i] need a new
-// segment (:271: learning_output cells whose max jittered potential is below epsilon); punish_words: one word per column
-// of the model, bit j = cell j of `output_punishment` (:269), or NULL for "every cell of a column not listed" (what
-// TemporalMemory passes, networks.py:107-108,111).  Does not close the timestep: htm_tm_scan does.
+// winner_words[i] (bit j = cell j; `output_learning` of :261-262 for that column; bits beyond the column's cells are ignored)
+// of which unaccounted_words[i] need a new segment (:271: learning_output cells whose max jittered potential is below
+// epsilon); punish_words: one word per column of the model, bit j = cell j of `output_punishment` (:269) -- any cells, learning
+// cells included --, or NULL for "every cell of a column not listed" (what TemporalMemory passes, networks.py:107-108,111).
+// Accepted beyond what the fused step forms: several learning cells per column up to all of them, punished learning cells,
+// previous winners that are no subset of the previous activation.  Refused with HTM_ERR_ARGUMENT before anything is
+// enqueued (the handle stays as it was): n above active_columns, a column listed twice or outside [0, column_dim), 65 536
+// learning cells or more in one call (the middle launch packs its two running counts into 16 bits each).
+// Order on one row: the learning update and its growth, then the punishment (:284-293) -- the punished rows are listed first
+// (against the owners they have before any segment is recycled, :264), the middle launch classifies the learning rows only,
+// and the punishment is a second learning launch behind the first (k_tm_ext_punish).
+// Does not close the timestep: htm_tm_scan does.
 extern "C" int htm_tm_update(htm_handle *h, const int32_t *columns, const uint32_t *winner_words, const uint32_t *unaccounted_words,
                              int32_t n, const uint32_t *punish_words) {
     if (!h || (n > 0 && (!columns || !winner_words || !unaccounted_words))) return HTM_ERR_ARGUMENT;
@@ -1589,7 +1597,6 @@ extern "C" int htm_tm_update(htm_handle *h, const int32_t *columns, const uint32
     if (!h->cfg.enable_tm) { h->err = "handle has no Temporal Memory"; return HTM_ERR_STATE; }
     if (h->world > 1) { h->err = "htm_tm_update: not available on a column-sharded handle"; return HTM_ERR_STATE; }
     REFUSE_ON_VIEW(h, "htm_tm_update");
-    weights_touched(h);
     Dev &d = h->d;
     if (n < 0 || n > d.k) { h->err = "htm_tm_update: more columns with learning cells than active_columns"; return HTM_ERR_ARGUMENT; }
     // ascending columns (the order of the winner list, networks.py:103-104 under the ascending-column policy)
@@ -1598,49 +1605,74 @@ extern "C" int htm_tm_update(htm_handle *h, const int32_t *columns, const uint32
     std::sort(order.begin(), order.end(), [&](int a, int b) { return columns[a] < columns[b]; });
     std::vector<int> cols((size_t)n);
     const int WPC = d.WPC;                          // (the words: WPC per listed column)
+    auto cells_of_word = [&](int hw) { const int cells = d.K - 32 * hw; return cells >= 32 ? 0xFFFFFFFFu : cells <= 0 ? 0u : ((1u << cells) - 1u); };
     std::vector<uint32_t> ww((size_t)n * WPC), uw((size_t)n * WPC);
+    long long learning_cells = 0;
     for (int i = 0; i < n; ++i) {
         const int o = order[(size_t)i];
         cols[(size_t)i] = columns[o];
         for (int hw = 0; hw < WPC; ++hw) {
-            ww[(size_t)i * WPC + hw] = winner_words[(size_t)o * WPC + hw];
-            uw[(size_t)i * WPC + hw] = unaccounted_words[(size_t)o * WPC + hw] & winner_words[(size_t)o * WPC + hw];
+            const uint32_t w = winner_words[(size_t)o * WPC + hw] & cells_of_word(hw);
+            ww[(size_t)i * WPC + hw] = w;
+            uw[(size_t)i * WPC + hw] = unaccounted_words[(size_t)o * WPC + hw] & w;
+            learning_cells += __builtin_popcount(w);
         }
-        if (cols[(size_t)i] < 0 || cols[(size_t)i] >= d.C || (i && cols[(size_t)i] == cols[(size_t)i - 1])) { h->err = "htm_tm_update: bad column list"; return HTM_ERR_ARGUMENT; }
+        if (cols[(size_t)i] < 0 || cols[(size_t)i] >= d.C || (i && cols[(size_t)i] == cols[(size_t)i - 1])) {
+            h->err = "htm_tm_update: bad column list (a column listed twice, or outside [0, column_dim))";
+            return HTM_ERR_ARGUMENT;
+        }
     }
+    if (learning_cells >= 65536) {
+        h->err = "htm_tm_update: " + std::to_string(learning_cells) + " learning cells in one call, at most 65535";
+        return HTM_ERR_ARGUMENT;
+    }
+    weights_touched(h);
     HIPCHK(h, hipSetDevice(h->device));
     const int p = (int)(h->step_host & 1);
-    int *d_cols = nullptr;
-    uint32_t *d_ww = nullptr, *d_uw = nullptr, *d_pun = nullptr;
-    auto release = [&]() { if (d_cols) hipFree(d_cols); if (d_ww) hipFree(d_ww); if (d_uw) hipFree(d_uw); if (d_pun) hipFree(d_pun); };
+    int *d_cols = nullptr, *d_pcount = nullptr;
+    uint32_t *d_ww = nullptr, *d_uw = nullptr, *d_pun = nullptr, *d_nopun = nullptr, *d_plist = nullptr;
+    auto release = [&]() {
+        for (void *ptr : {(void *)d_cols, (void *)d_ww, (void *)d_uw, (void *)d_pun, (void *)d_nopun, (void *)d_plist, (void *)d_pcount})
+            if (ptr) hipFree(ptr);
+    };
     const size_t nb = (size_t)std::max(n, 1) * 4, nbw = nb * WPC, pun_bytes = (size_t)d.C * WPC * 4;
     // punish_words == NULL: every cell of a column that is not listed (networks.py:107-108,111).  The mask is built here: the
     // middle launch's own default reads the step's active words, which this entry point does not write (htm_tm_scan does, later)
     std::vector<uint32_t> default_pun;
     if (!punish_words) {
         default_pun.resize((size_t)d.C * WPC);
-        for (size_t w = 0; w < default_pun.size(); ++w) {
-            const int cells = d.K - 32 * (int)(w % WPC);
-            default_pun[w] = cells >= 32 ? 0xFFFFFFFFu : ((1u << cells) - 1u);
-        }
+        for (size_t w = 0; w < default_pun.size(); ++w) default_pun[w] = cells_of_word((int)(w % WPC));
         for (int i = 0; i < n; ++i)
             for (int hw = 0; hw < WPC; ++hw) default_pun[(size_t)cols[(size_t)i] * WPC + hw] = 0u;
         punish_words = default_pun.data();
     }
     if (hipMalloc((void **)&d_cols, nb) != hipSuccess || hipMalloc((void **)&d_ww, nbw) != hipSuccess || hipMalloc((void **)&d_uw, nbw) != hipSuccess ||
-        hipMalloc((void **)&d_pun, pun_bytes) != hipSuccess) { release(); h->err = "htm_tm_update: hipMalloc failed"; return HTM_ERR_HIP; }
+        hipMalloc((void **)&d_pun, pun_bytes) != hipSuccess || hipMalloc((void **)&d_nopun, pun_bytes) != hipSuccess ||
+        hipMalloc((void **)&d_plist, (size_t)std::max(d.work_cap, 1) * 4) != hipSuccess || hipMalloc((void **)&d_pcount, 4) != hipSuccess) {
+        release(); h->err = "htm_tm_update: hipMalloc failed"; return HTM_ERR_HIP;
+    }
     bool ok = true;
     if (n) ok = hipMemcpyAsync(d_cols, cols.data(), nb, hipMemcpyHostToDevice, h->stream) == hipSuccess &&
                 hipMemcpyAsync(d_ww, ww.data(), nbw, hipMemcpyHostToDevice, h->stream) == hipSuccess &&
                 hipMemcpyAsync(d_uw, uw.data(), nbw, hipMemcpyHostToDevice, h->stream) == hipSuccess;
-    if (ok) ok = hipMemcpyAsync(d_pun, punish_words, pun_bytes, hipMemcpyHostToDevice, h->stream) == hipSuccess;
+    if (ok) ok = hipMemcpyAsync(d_pun, punish_words, pun_bytes, hipMemcpyHostToDevice, h->stream) == hipSuccess &&
+                 hipMemsetAsync(d_nopun, 0, pun_bytes, h->stream) == hipSuccess && hipMemsetAsync(d_pcount, 0, 4, h->stream) == hipSuccess &&
+                 // (the step's work counts start at zero: the scan before left them so; a second update without a scan between did not)
+                 hipMemsetAsync(&d.ctr->n_work[p], 0, sizeof(int), h->stream) == hipSuccess &&
+                 hipMemsetAsync(&d.ctr->n_bind[p], 0, sizeof(int), h->stream) == hipSuccess;
     if (!ok) { release(); h->err = "htm_tm_update: hipMemcpy failed"; return HTM_ERR_HIP; }
+    static decltype(&k_tm_learn_ext<1>) const kt_tm_learn_ext[4] = {k_tm_learn_ext<1>, k_tm_learn_ext<2>, k_tm_learn_ext<4>, k_tm_learn_ext<8>};
+    auto learn = [&]() { LAUNCH_ON(h, h->stream, learn_lds(learn_epl(d)), "tm_learn", kt_tm_learn_ext[epl_slot(d)], kLearnBlocks, RB, d, p); };
+    const int pun_blocks = std::max(1, std::min((d.Scap + 255) / 256, 1024));
     hipLaunchKernelGGL(k_tm_ext_winners, dim3(std::min((d.C + 255) / 256, 1024)), dim3(256), 0, h->stream, d, p, d_cols, d_ww, d_uw, n, 0);
     if (n) hipLaunchKernelGGL(k_tm_ext_winners, dim3((n * WPC + 255) / 256), dim3(256), 0, h->stream, d, p, d_cols, d_ww, d_uw, n, 1);
-    d.punish = d_pun;                               // (kernels take Dev by value: set for the middle launch only)
+    hipLaunchKernelGGL(k_tm_ext_punish, dim3(pun_blocks), dim3(256), 0, h->stream, d, p, d_pun, d_plist, d_pcount, 0);
+    d.punish = d_nopun;                             // (kernels take Dev by value: set for the middle launch only -- it lists no punished row)
     LAUNCH(h, "tm_mid", k_mid_rows, 1 + kClassifyBlocks + h->sz.zero_blocks, 256, d, p, n, 1, 1, kClassifyBlocks, nullptr, 1, 0, 0, 0);
     d.punish = nullptr;
-    launch_learn(h, p);
+    learn();                                        // learn and grow ...
+    hipLaunchKernelGGL(k_tm_ext_punish, dim3(pun_blocks), dim3(256), 0, h->stream, d, p, d_pun, d_plist, d_pcount, 1);
+    learn();                                        // ... then punish
     hipError_t e = hipGetLastError();
     const bool synced = hipStreamSynchronize(h->stream) == hipSuccess;       // (the staging buffers are this call's)
     release();

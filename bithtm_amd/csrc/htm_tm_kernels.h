@@ -66,6 +66,42 @@ __global__ __launch_bounds__(256) void k_tm_ext_active(Dev d, int p, const uint3
     }
 }
 
+// PredictiveProjection.update called on its own (htm_tm_update): the punished segments (projections.py:269).  A caller's
+// output_punishment may cover learning cells, so one row can be in both sets -- and the reference applies the two updates one
+// after the other (:284-293: learn and grow, then punish), while two work items of one launch have no order.  So the punished
+// rows are not classified by the middle launch (it is handed an empty mask) but here:
+//   pass 0, BEFORE the middle launch binds new segments: the matching rows whose owner -- the owner they have now, as the
+//           reference reads it (:264) -- is punished are appended to `list`;
+//   pass 1, AFTER the learning launch: the list becomes the work of a second learning launch (punish items only).
+__global__ __launch_bounds__(256) void k_tm_ext_punish(Dev d, int p, const uint32_t *punish, uint32_t *list, int *count, int pass) {
+    Counters *c = d.ctr;
+    if (pass == 1) {
+        const int n = min(*count, d.work_cap);
+        for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) d.work[i] = list[i] | 0x80000000u;
+        if (blockIdx.x == 0 && threadIdx.x == 0) { c->n_work[p] = n; c->n_bind[p] = 0; }
+        return;
+    }
+    if (!c->has_distal) return;
+    const int q = p ^ 1, n = c->S;                   // (unsharded handles only: row == id)
+    for (int base = blockIdx.x * 256; base < n; base += gridDim.x * 256) {
+        const int seg = base + (int)threadIdx.x;
+        bool pun = false;
+        if (seg < n && ((d.match_bits[q][seg >> 5] >> (seg & 31)) & 1u)) {
+            const int cell = d.seg_cell[seg];
+            pun = (punish[cell >> 5] >> (cell & 31)) & 1u;
+        }
+        const u64 m = __ballot(pun);
+        if (!m) continue;
+        int b = 0;
+        if (lane_id() == 0) b = atomicAdd(count, __popcll(m));
+        b = wave_read(b, 0);
+        if (pun) {
+            const int pos = b + __popcll(m & lanemask_lt());
+            if (pos < d.work_cap) list[pos] = (uint32_t)seg; else atomicOr(&c->error, 4);
+        }
+    }
+}
+
 __device__ __forceinline__ bool col_is_local(const Dev &d, int cell) { const int col = cell >> d.LK; return col >= d.c0 && col < d.c1; }
 
 // the global id of a local row (unsharded handles: the row IS the id)
@@ -602,7 +638,13 @@ static_assert(CAND_CAP == 4 * 64, "the growth path holds the staged winners four
 // SELF: the wave also does the segment scan's work for its segment (potential and connected-active count against this
 // step's active cells, from the synapses it holds in registers; publication as in role_scan) -- the schedule in which the
 // learning role and the scan share a launch: the scan leaves the rows on the work list alone (SEG_BUSY).
-template <int EPL, int BS, bool SELF = false>
+// EXT (htm_tm_update, its own kernel k_tm_learn_ext: the fused step's instantiations are compiled without it): the growth search
+// stages only winners the row does NOT hold yet.  The plain form stages every winner below the threshold and drops the held
+// ones afterwards, which assumes a row holds few of the winners: true inside the fused step (winners are active cells: a row
+// connected to more than 224 of them has no room left in its sample) but not for a caller's winner_input outside
+// input_activation -- a row that holds all but a few of more than CAND_CAP winners then overflowed the staging area at every
+// threshold that reaches the absent ones, and the search gave up with a capacity flag and no growth.
+template <int EPL, int BS, bool SELF = false, bool EXT = false>
 __device__ __forceinline__ void role_learn(const Dev &d, int p, int blk, int nblk, LearnShared<EPL, BS> *sh) {
     int (*s_keep)[EPL * 64] = sh->keep;
     u64 (*s_cand)[CAND_CAP] = sh->cand;
@@ -753,12 +795,27 @@ __device__ __forceinline__ void role_learn(const Dev &d, int p, int blk, int nbl
                     for (int b0 = 0; b0 < n_w; b0 += 4 * 64) {
                         uint32_t pr[4];
                         bool take[4];
+                        int wc4[4];
 #pragma unroll
                         for (int j = 0; j < 4; ++j) {
                             const int i = b0 + j * 64 + lane;
                             const int wcell = i < n_w ? winner_at(i) : 0;
+                            wc4[j] = wcell;
                             pr[j] = htm_draw24(base2, gid, enc_to_flat(d, wcell));         // :120
                             take[j] = i < n_w && pr[j] < T;
+                        }
+                        if (EXT && n_keep > 0) {                  // :121-123 before the staging: a held winner is no candidate
+                            const bool any = take[0] || take[1] || take[2] || take[3];
+                            if (__ballot(any)) {
+                                bool present[4] = {false, false, false, false};
+                                for (int f = 0; f < n_keep; ++f) {
+                                    const int kf = s_keep[wv][f];     // (one address for the wave: a broadcast read)
+#pragma unroll
+                                    for (int j = 0; j < 4; ++j) present[j] |= wc4[j] == kf;
+                                }
+#pragma unroll
+                                for (int j = 0; j < 4; ++j) take[j] = take[j] && !present[j];
+                            }
                         }
 #pragma unroll
                         for (int j = 0; j < 4; ++j) {
@@ -780,7 +837,7 @@ __device__ __forceinline__ void role_learn(const Dev &d, int p, int blk, int nbl
                     LSTAMP(3);
                     LCOUNT(11, staged);
                     found = staged;
-                    if (n_keep > 0) {                             // :121-123
+                    if (!EXT && n_keep > 0) {                     // :121-123
                         u64 key[4];
                         int cell[4];
                         bool present[4];
@@ -901,6 +958,13 @@ __global__ __launch_bounds__(RB) void k_tm_learn(Dev d, int p) {
     // (every form of a step's learning launch resets the fan-in counters its k_act_mid_rows may have used: htm_pipeline.h)
     if (blockIdx.x == gridDim.x - 1 && threadIdx.x < FAN_COUNTERS) d.fan[(size_t)(p * FAN_COUNTERS + (int)threadIdx.x) * FAN_STRIDE] = 0u;
     role_learn<EPL, RB>(d, p, blockIdx.x, gridDim.x, (LearnShared<EPL, RB> *)dyn_lds);
+}
+
+// htm_tm_update's learning launches (role_learn, EXT)
+template <int EPL>
+__global__ __launch_bounds__(RB) void k_tm_learn_ext(Dev d, int p) {
+    if (blockIdx.x == gridDim.x - 1 && threadIdx.x < FAN_COUNTERS) d.fan[(size_t)(p * FAN_COUNTERS + (int)threadIdx.x) * FAN_STRIDE] = 0u;   // (as k_tm_learn)
+    role_learn<EPL, RB, false, true>(d, p, blockIdx.x, gridDim.x, (LearnShared<EPL, RB> *)dyn_lds);
 }
 
 // PredictiveProjection.process (projections.py:245-255): per segment, potential = active presynaptic cells;

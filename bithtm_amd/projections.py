@@ -216,12 +216,37 @@ class PredictiveProjection:
         self.fill_jittered_potential_info(state)
         return state.max_jittered_potential, state.matching_segment_jittered_potential
 
+    MAX_LEARNING_CELLS = 65535      # learning cells of one update() call (the device counts them in 16 bits: htm_tm_update)
+
+    def _cell_ids(self, ids, what, distinct=True):
+        """`ids` as int64 flat cell ids after the checks every list of cells gets before anything reaches the device: each in
+        [0, output_dim), none twice -- else ValueError naming the cell."""
+        flat = np.asarray(ids, dtype=np.int64).reshape(-1)
+        bad = np.flatnonzero((flat < 0) | (flat >= self.output_dim))
+        if len(bad):
+            raise ValueError(f"{what}: cell {int(flat[bad[0]])} is outside [0, {self.output_dim})")
+        if distinct and len(flat) > 1:
+            srt = np.sort(flat)
+            twice = np.flatnonzero(srt[1:] == srt[:-1])
+            if len(twice):
+                raise ValueError(f"{what}: cell {int(srt[twice[0]])} is listed more than once")
+        return flat
+
+    def _cell_mask(self, mask, what):
+        mask = np.asarray(mask, dtype=np.bool_).reshape(-1)
+        if len(mask) != self.output_dim:
+            raise ValueError(f"{what}: {len(mask)} entries, the projection has {self.output_dim} cells")
+        return mask
+
     def process(self, active_input, return_jittered_potential_info=True):
-        """projections.py:245-255 on the device (the segment scan): `active_input` = flat ids of the active cells."""
+        """projections.py:245-255 on the device (the segment scan): `active_input` = flat ids of the active cells, distinct,
+        in any order.  A repeated id or one outside [0, output_dim) raises ValueError before anything is enqueued (the
+        reference counts a repeated id twice in segment_potential and once in the activation: no set of active cells
+        reproduces that)."""
         from .engine import CapacityError  # noqa: F401
+        flat = self._cell_ids(active_input, "process: active_input")
         eng = self._ensure_engine()
         K, C = eng.cell_dim, eng.column_dim
-        flat = np.asarray(active_input, dtype=np.int64).reshape(-1)
         wpc = eng.cell_words // C                    # (words per column: the cell j of a column is bit j % 32 of its word j // 32)
         words = np.zeros(C * wpc, dtype=np.uint32)
         np.bitwise_or.at(words, (flat // K) * wpc + (flat % K) // 32, (np.uint32(1) << ((flat % K) % 32).astype(np.uint32)))
@@ -237,15 +262,37 @@ class PredictiveProjection:
                epsilon=1e-8):
         """projections.py:257-293 on the device (segment allocation, learn / punish classification, permanence updates,
         growth).  `prev_state`: the State this object's process() returned last -- or any earlier one, which is then
-        written back as the device's previous step (a host round trip, like TemporalMemory.process(prev_state=))."""
+        written back as the device's previous step (a host round trip, like TemporalMemory.process(prev_state=)); None:
+        nothing happens (:258-259).
+
+        Accepted: any `learning_output` of distinct cells (several per column, every cell of a column), at most
+        MAX_LEARNING_CELLS of them; any `output_punishment` (learning cells included; None: every cell of a column without a
+        learning cell, what TemporalMemory passes); `winner_input` None or empty (no growth) or distinct cells, inside or
+        outside `input_activation`; `output_learning` (it classifies the matching segments, `learning_output` alone
+        decides which cells get a new segment); 0 < epsilon <= 1.  On a segment that both learns and is punished the learning
+        update and its growth come first, then the punishment (:284-293).  New segments are bound in ascending cell order:
+        the reference's ids for an ascending `learning_output`.
+        Refused with ValueError, before anything is enqueued (the next valid call finds the device as it was): a cell id
+        outside [0, output_dim) or listed twice in `learning_output` / `winner_input` (the reference would allocate one
+        segment per occurrence; a bit mask cannot), more than MAX_LEARNING_CELLS learning cells, a mask of another length.
+        Raises CapacityError when the pool or a row's slots ran out; the rows that did not overflow are the reference's."""
         if prev_state is None:                                                    # :258-259
             return
+        learning_output = self._cell_ids(learning_output, "update: learning_output")
+        if len(learning_output) > self.MAX_LEARNING_CELLS:
+            raise ValueError(f"update: {len(learning_output)} learning cells in one call, at most {self.MAX_LEARNING_CELLS} (fewer than 65536)")
+        if winner_input is not None:
+            winner_input = self._cell_ids(winner_input, "update: winner_input")
+        input_activation = self._cell_mask(input_activation, "update: input_activation")
+        if output_punishment is not None:
+            output_punishment = self._cell_mask(output_punishment, "update: output_punishment")
+        if output_learning is not None:
+            output_learning = self._cell_mask(output_learning, "update: output_learning")
         eng = self._ensure_engine()
         K, C = eng.cell_dim, eng.column_dim
         eng.use_epsilon(epsilon)
         self.fill_jittered_potential_info(prev_state)
-        learning_output = np.asarray(learning_output, dtype=np.int64).reshape(-1)
-        input_activation = self._padded(np.asarray(input_activation, dtype=np.bool_)).reshape(C, K)
+        input_activation = self._padded(input_activation).reshape(C, K)
         # the previous step's side of the call: prev_state, input_activation, winner_input
         from types import SimpleNamespace
         prev = SimpleNamespace(matching_segment=prev_state.matching_segment, segment_potential=prev_state.segment_potential,
@@ -254,7 +301,7 @@ class PredictiveProjection:
                                matching_segment_jittered_potential=prev_state.matching_segment_jittered_potential,
                                max_jittered_potential=self._padded(np.asarray(prev_state.max_jittered_potential, dtype=np.float32)))
         eng.import_prev_state(self._padded(np.asarray(prev_state.prediction)).reshape(C, K) > epsilon, input_activation,
-                              None if winner_input is None else np.asarray(winner_input, dtype=np.int64), prev)
+                              winner_input if winner_input is not None and len(winner_input) else None, prev)
         learn_mask = np.zeros(C * K, dtype=np.bool_)
         if output_learning is None:
             learn_mask[learning_output] = True                                    # :261-262
@@ -263,7 +310,9 @@ class PredictiveProjection:
         unacc = learning_output[np.asarray(prev_state.max_jittered_potential)[learning_output] < np.float32(epsilon)]      # :271
         need = np.zeros(C * K, dtype=np.bool_)
         need[unacc] = True
-        learn_mask |= need                          # (a cell that gets a segment is a learning cell: :281 learns on the new segment)
+        # (a cell that gets a segment is a learning cell: :281 learns on the new segment.  It owns no matching segment -- its
+        # maximum is below epsilon -- so its bit changes nothing in the classification a caller's output_learning asked for)
+        learn_mask |= need
         from .engine import bool_to_words
         wpc = eng.cell_words // C
         ww, uw = bool_to_words(learn_mask.reshape(C, K)).reshape(C, wpc), bool_to_words(need.reshape(C, K)).reshape(C, wpc)
@@ -271,4 +320,5 @@ class PredictiveProjection:
         # output_punishment=None: the mask TemporalMemory builds (networks.py:107-108,111) -- every cell of a column without a
         # learning cell -- is built by the library (htm_tm_update's punish_words == NULL)
         eng.tm_update(cols, ww[cols], uw[cols], None if output_punishment is None else
-                      bool_to_words(self._padded(np.asarray(output_punishment, dtype=np.bool_)).reshape(C, K)))
+                      bool_to_words(self._padded(output_punishment).reshape(C, K)))
+        eng.check_capacity()

@@ -180,15 +180,24 @@ int htm_tm_step(htm_handle *h, const int32_t *active_column, int32_t n, int32_t 
 
 /* PredictiveProjection.update / .process (projections.py:257-293, :245-255) called on their own -- a caller that writes its
  * own TemporalMemory.process around the device's segment store (its own winner-cell rule, its own punishment mask).
- *   htm_tm_update  learning: columns[i] (distinct, at most active_columns of them) has the learning cells winner_words[i]
- *                  (bit j = cell j: `learning_output` / `output_learning`; cell_dim above 32: two words per listed column, side
- *                  by side, as in the htm_field arrays), of which unaccounted_words[i] get a new segment
- *                  (:271-281); punish_words = `output_punishment` as one word (two) per column of the model, or NULL = every cell
- *                  of a column not listed (what TemporalMemory.process passes, networks.py:107-108,111).  prev_state,
- *                  input_activation and winner_input of the reference's signature are the handle's previous step (its own
- *                  last one, or whatever was written with htm_import_begin(HTM_IMPORT_PREV_STATE) / htm_write).
- *   htm_tm_scan    the scan against the cells of active_words (one word -- two -- per column of the model), which become the
- *                  step's cell activation; closes the timestep.  PredictiveProjection.State is read with htm_read. */
+ *   htm_tm_update  learning: columns[i] (distinct, any order, at most active_columns of them) has the learning cells
+ *                  winner_words[i] (bit j = cell j: `learning_output` / `output_learning`; cell_dim above 32: two words per listed
+ *                  column, side by side, as in the htm_field arrays; bits beyond the column's cells are ignored) -- any number of
+ *                  cells per column, up to all of them --, of which unaccounted_words[i] get a new segment (:271-281), bound in
+ *                  ascending cell order; punish_words = `output_punishment` as one word (two) per column of the model -- any
+ *                  cells, learning cells included --, or NULL = every cell of a column not listed (what TemporalMemory.process
+ *                  passes, networks.py:107-108,111).  prev_state, input_activation and winner_input of the reference's
+ *                  signature are the handle's previous step (its own last one, or whatever was written with
+ *                  htm_import_begin(HTM_IMPORT_PREV_STATE) / htm_write); the previous winners need not be active cells of the
+ *                  previous activation, and a segment connected to most of them grows exactly the absent ones.
+ *                  On a segment that both learns and is punished the learning update and its growth come first, then the
+ *                  punishment (:284-293).
+ *                  HTM_ERR_ARGUMENT, nothing enqueued, the handle as it was: n above active_columns, a column listed twice or
+ *                  outside [0, column_dim), 65 536 learning cells or more in one call.  HTM_ERR_STATE: a column-sharded handle,
+ *                  an inference view.  A pool or a row that ran out sets the sticky capacity flags (htm_get_info).
+ *   htm_tm_scan    the scan against the cells of active_words (one word -- two -- per column of the model; bits beyond a
+ *                  column's cells are ignored), which become the step's cell activation; closes the timestep.
+ *                  PredictiveProjection.State is read with htm_read. */
 int htm_tm_update(htm_handle *h, const int32_t *columns, const uint32_t *winner_words, const uint32_t *unaccounted_words,
                   int32_t n, const uint32_t *punish_words);
 int htm_tm_scan(htm_handle *h, const uint32_t *active_words);

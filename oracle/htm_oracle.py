@@ -170,6 +170,7 @@ class TemporalMemoryOracle:
         self.perm = np.full((0, slots), -1.0, dtype=np.float32)
         self.segcount = np.zeros(self.N, dtype=np.int32)
         self.step_index = 0
+        self.last_update = None     # update(): what the last call decided (learning / punished segments, allocation), for tests
         self.eps = EPS32                       # TemporalMemory.process(epsilon=) (networks.py:91), as float32; 0 < eps <= 1
         # previous-step state (networks.py:57-65)
         self.prev_prediction = np.zeros((column_dim, cell_dim), dtype=np.bool_)
@@ -295,23 +296,36 @@ class TemporalMemoryOracle:
                 self.perm[seg, free[:t]] = self.d.initial32
                 self.seg_nsyn[seg] += t
 
-    def _learn(self, winner_flat, active_column, step):
-        """projections.py:257-293 (PredictiveProjection.update) + add_output (:79-95)."""
-        d, p, K = self.prev_distal, self.params, self.cell_dim
-        if d is None:                                            # projections.py:258-259
+    def update(self, prev_state, input_activation, learning_output, output_punishment, winner_input=None, output_learning=None,
+               epsilon=1e-8, step=None):
+        """projections.py:257-293 (PredictiveProjection.update) with the reference's own signature, + add_output (:79-95).
+        `prev_state`: a State of process() / _scan (None: nothing happens, :258-259); `input_activation`, `output_punishment`,
+        `output_learning`: bool per cell; `learning_output`, `winner_input`: flat cell ids, in the caller's order
+        (`winner_input` distinct; None or empty: no growth, :191-192 and :115).  `output_learning`, when given, classifies
+        the matching segments (:268) while `learning_output` alone decides which cells are unaccounted (:271).  The
+        three updates run in the reference's order on the same rows: learn (:284-289), grow, punish (:290-293).
+        `step`: the index that keys the growth draws (default: the current one, which update does not advance)."""
+        if prev_state is None:                                               # :258-259
             return
-        m = d.matching_segment
-        mcell = self.seg_cell[m]
-        is_winner = np.zeros(self.N, dtype=np.bool_)
-        is_winner[winner_flat] = True
-        unpredicted = d.prediction[mcell] < 1e-8                              # :266
-        best = np.abs(d.matching_segment_jittered_potential - d.max_jittered_potential[mcell]) < self.eps  # :267
-        learning = m[is_winner[mcell] & (d.matching_segment_active | (unpredicted & best))]     # :268
-        column_active = np.zeros(self.column_dim, dtype=np.bool_)
-        column_active[active_column] = True
-        punished = m[~column_active[mcell // K]]                              # :269, networks.py:107-111
+        d, p = prev_state, self.params
+        step = self.step_index if step is None else step
+        eps32 = np.float32(epsilon)                      # a Python scalar against float32 arrays
+        learning_output = np.asarray(learning_output, dtype=np.int64).reshape(-1)
+        if output_learning is None:                                          # :260-262
+            output_learning = np.zeros(self.N, dtype=np.bool_)
+            output_learning[learning_output] = True
+        output_learning = np.asarray(output_learning, dtype=np.bool_).reshape(-1)
+        output_punishment = np.asarray(output_punishment, dtype=np.bool_).reshape(-1)
+        m = np.asarray(d.matching_segment, dtype=np.int64)
+        mcell = self.seg_cell[m]                                             # :264
+        unpredicted = d.prediction[mcell] < float(epsilon)                   # :266 (float64 counts: any 0 < epsilon <= 1 means "== 0")
+        best = np.abs(d.matching_segment_jittered_potential - d.max_jittered_potential[mcell]) < eps32     # :267
+        learning = m[output_learning[mcell] & (d.matching_segment_active | (unpredicted & best))]          # :268
+        punished = m[output_punishment[mcell]]                               # :269
 
-        unaccounted = winner_flat[d.max_jittered_potential[winner_flat] < self.eps]   # :271
+        unaccounted = learning_output[d.max_jittered_potential[learning_output] < eps32]                   # :271-273
+        recycled = fresh = np.zeros(0, dtype=np.int64)
+        matched_learning = learning
         if len(unaccounted):
             recycled = np.flatnonzero(self.seg_nsyn[:self.S] < p.segment_matching_threshold)[:len(unaccounted)]  # :80-81
             n_r = len(recycled)
@@ -331,12 +345,38 @@ class TemporalMemoryOracle:
                 self.perm[fresh] = -1.0
                 self.S += n_new
             learning = np.concatenate([learning, recycled, fresh])            # :281
+        self.last_update = SimpleNamespace(learning=matched_learning, punished=punished, unaccounted=unaccounted,
+                                           recycled=np.asarray(recycled, dtype=np.int64), fresh=np.asarray(fresh, dtype=np.int64))
 
-        act_pad = self._padded(self.prev_activation)                          # :283
+        act_pad = self._padded(np.asarray(input_activation, dtype=np.bool_))  # :283
         self._update_permanence(learning, act_pad, self.d.learn_active, self.d.learn_inactive, self.d.learn_prune)
-        if self.prev_winner is not None:                                      # :191-192
-            self._grow(learning.astype(np.int64), act_pad, self.prev_winner, step)
+        if winner_input is not None:                                          # :191-192
+            self._grow(learning.astype(np.int64), act_pad, np.asarray(winner_input, dtype=np.int64).reshape(-1), step)
         self._update_permanence(punished, act_pad, self.d.punish_active, self.d.punish_inactive, self.d.punish_prune)
+
+    def process(self, active_input):
+        """projections.py:245-255 (PredictiveProjection.process): the scan against the cells `active_input` (distinct flat ids,
+        any order) keyed by the current step index, which it then advances.  A repeated id is refused: the reference counts it
+        twice in segment_potential (:185-188, the push form) and once in the activation (:70-71), which no set of active
+        cells reproduces."""
+        active_input = np.asarray(active_input, dtype=np.int64).reshape(-1)
+        if len(np.unique(active_input)) != len(active_input):
+            raise ValueError("process: active_input names a cell twice")
+        activation = np.zeros(self.N, dtype=np.bool_)
+        activation[active_input] = True
+        state = self._scan(activation, self.step_index)
+        self.step_index += 1
+        return state
+
+    def _learn(self, winner_flat, active_column, step):
+        """TemporalMemory.process's call of update (networks.py:106-113): the winner cells learn, the cells of columns that
+        are not active are punished (:107-108,111)."""
+        if self.prev_distal is None:
+            return
+        punishment = np.ones((self.column_dim, self.cell_dim), dtype=np.bool_)
+        punishment[active_column] = False
+        self.update(self.prev_distal, self.prev_activation, winner_flat, punishment.reshape(-1), winner_input=self.prev_winner,
+                    epsilon=self.eps, step=step)
 
     # ---- scan
     def _scan(self, activation, step):

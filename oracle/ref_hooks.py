@@ -69,7 +69,7 @@ class KeyedRand:
         self.step = 0
         self.fallback = fallback
         self.log = []          # (step, stream, shape) of every keyed draw
-        self.growth_ties = 0   # rows where a priority tie straddled the cut (see below)
+        self.growth_ties = 0   # rows where a priority tie straddled the growth cut (counted in the add_edge branch below)
 
     def __call__(self, *shape):
         frame = sys._getframe(1)
@@ -86,6 +86,17 @@ class KeyedRand:
             out = np.zeros((len(segs), len(winners) + 1), dtype=np.float64)
             if len(segs) and len(winners):
                 out[:, :-1] = draw_unit(self.seed, STREAM_GROWTH, self.step, segs[:, None], winners[None, :])
+                # a tie between the last priority taken and the first one left out (projections.py:124-127 sorts with an
+                # unstable argsort: which of the two grows is implementation-defined; the oracle takes the lower winner index)
+                n_add = np.asarray(loc["added_output_edges"], dtype=np.int64).reshape(-1)
+                pri = out[:, :-1].astype(np.float32)
+                at = np.asarray(loc["whole_input_to_winner"])[np.asarray(loc["learning_edge_target"])]
+                rows, cols = np.nonzero(at < len(winners))
+                pri[rows, at[rows, cols]] = np.inf                                     # :121 (already connected)
+                pri.sort(axis=1)
+                cut = np.flatnonzero((n_add > 0) & (n_add < len(winners)))
+                last, first_out = pri[cut, n_add[cut] - 1], pri[cut, n_add[cut]]
+                self.growth_ties += int(((last == first_out) & np.isfinite(last)).sum())
             stream = STREAM_GROWTH
         elif name == "fill_jittered_potential_info":       # projections.py:235
             segs = np.asarray(loc["state"].matching_segment, dtype=np.int64)

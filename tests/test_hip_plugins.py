@@ -209,20 +209,14 @@ class OracleProjection:
 
     def process(self, active_input, return_jittered_potential_info=True):
         self.calls["process"] += 1
-        act = np.zeros(self.C * self.K, dtype=np.bool_)
-        act[active_input] = True
-        d = self.o._scan(act.reshape(self.C, self.K), self.o.step_index)
-        self.o.step_index += 1
-        return d
+        return self.o.process(active_input)
 
     def update(self, prev_state, input_activation, learning_output, output_punishment, winner_input=None, output_learning=None, epsilon=1e-8):
         if prev_state is None:
             return
         self.calls["update"] += 1
-        o = self.o
-        o.prev_distal, o.prev_activation, o.prev_winner = prev_state, np.asarray(input_activation).reshape(self.C, self.K), winner_input
-        active_column = np.flatnonzero(~np.asarray(output_punishment).reshape(self.C, self.K).any(axis=1))
-        o._learn(np.asarray(learning_output, dtype=np.int64), active_column, o.step_index)
+        self.o.update(prev_state, input_activation, learning_output, output_punishment, winner_input=winner_input,
+                      output_learning=output_learning, epsilon=epsilon)
 
 
 def _tm_states_equal(t, got, want, K):
