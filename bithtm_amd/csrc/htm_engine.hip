@@ -79,12 +79,19 @@ struct Sizes {
     int sel_passes_fused, sel_passes_full; // launched select digits with / without the in-kernel finish
 };
 
+// The modes of one batched call -- its steps are recorded, reset by the bank's bits, decoded, fed back -- as its setup returns them
+// (begin_run_modes, group_begin_modes).  Whatever enqueues or captures a step takes them by value; a host-fed step has none.
+struct RunModes {
+    bool recording, resetting, decoding, feeding;
+    bool operator<(const RunModes &o) const { return std::tie(recording, resetting, decoding, feeding) < std::tie(o.recording, o.resetting, o.decoding, o.feeding); }
+};
+
 // What the launches of a captured graph depend on besides the handle's fixed sizes.  htm_run: the step's parity, the call's
 // modes, its StepPlan and schedule, the scan's form, the span of steps, the bank
 struct RunGraphKey {
-    int p; bool recording, resetting, decoding, feeding; int learning; bool sp_done, next_sp, next_front, lean; int spec; bool large, emit_fused, wmode;
+    int p; RunModes modes; int learning; bool sp_done, next_sp, next_front, lean; int spec; bool large, emit_fused, wmode;
     int span; const void *bank; int n_inputs;
-    auto tie() const { return std::tie(p, recording, resetting, decoding, feeding, learning, sp_done, next_sp, next_front, lean, spec, large, emit_fused, wmode, span, bank, n_inputs); }
+    auto tie() const { return std::tie(p, modes, learning, sp_done, next_sp, next_front, lean, spec, large, emit_fused, wmode, span, bank, n_inputs); }
     bool operator<(const RunGraphKey &o) const { return tie() < o.tie(); }
 };
 
@@ -98,8 +105,8 @@ struct ShardGraphKey {
 
 // ... htm_tm_run: the step's parity, the call's modes, the scan's form, the span of steps, the bank of lists and its shape
 struct TmRunGraphKey {
-    int p; bool recording, resetting; int learning, spec; bool large; int span; const void *lists; int n_rows, n;
-    auto tie() const { return std::tie(p, recording, resetting, learning, spec, large, span, lists, n_rows, n); }
+    int p; RunModes modes; int learning, spec; bool large; int span; const void *lists; int n_rows, n;
+    auto tie() const { return std::tie(p, modes, learning, spec, large, span, lists, n_rows, n); }
     bool operator<(const TmRunGraphKey &o) const { return tie() < o.tie(); }
 };
 
@@ -139,31 +146,23 @@ struct htm_handle {
     bool import_keep;                     // htm_import_begin(HTM_IMPORT_PREV_STATE): the commit leaves the store, the step index and the sticky flags alone
     bool phase_open;                      // ... phases of the current (not yet closed) timestep have run: the Spatial Pooler
                                           // fields htm_read returns are that step's
-    // recorded runs (htm_run_recorded): the device descriptor every record launch reads, and whether the steps being enqueued
-    // (or captured) now are recorded -- only inside such a call
-    RecDev *d_rec;
-    bool recording;
-    // sequence resets of htm_run (htm_set_run_resets): the caller's device bits and bank size, the device descriptor the reset
-    // launches read (filled by each call that has bits), and whether the steps being enqueued (or captured) now reset
+    RecDev *d_rec;                        // recorded runs (htm_run_recorded): the device descriptor every record launch reads (filled by each such call)
+    // sequence resets of htm_run (htm_set_run_resets): the caller's device bits and bank size, and the device descriptor the reset
+    // launches read (filled by each call that has bits)
     const uint32_t *reset_bits;
     int reset_n;
     ResetDev *d_reset;
-    bool resetting;
     // predicted-input decoding (htm_set_run_predicted_input): the caller's device rows, the device descriptor the decoding
-    // launches read (filled by each call that decodes), whether the steps being enqueued (or captured) now are decoded, and the
-    // output row of htm_predicted_input
+    // launches read (filled by each call that decodes), and the output row of htm_predicted_input
     int32_t *pin_out;
     PinDev *d_pin;
-    bool decoding;
     int32_t *d_pin_buf;
     // run feedback (htm_set_run_feedback): the bank whose runs write their next row and its size, the device descriptor the
-    // feedback launches read (filled when the feedback is set), the scratch votes row (zero between uses: htm_forecast.h), and
-    // whether the steps being enqueued (or captured) now feed back
+    // feedback launches read (filled when the feedback is set), and the scratch votes row (zero between uses: htm_forecast.h)
     uint32_t *feed_bank;
     int feed_n;
     FeedDev *d_feed;
     int32_t *d_feed_votes;
-    bool feeding;
     std::map<RunGraphKey, hipGraphExec_t> graphs;
     std::map<TmRunGraphKey, hipGraphExec_t> tm_graphs;        // htm_tm_run
     // state import staging (htm_write of the MATCH_* / SEG_POTENTIAL fields, applied at commit)
@@ -627,12 +626,12 @@ static void enqueue_cold_start(htm_handle *h, const uint32_t *bank, int n_inputs
 static int reset_blocks(const Dev &d) { return std::max(1, std::min(1024, (d.C * d.KP + 255) / 256)); }
 
 // in a run with reset bits: the reset of the step of parity p if its bank row asks for one (before its activation role)
-static void enqueue_run_reset(htm_handle *h, int p) {
-    if (h->resetting) LAUNCH(h, "tm_reset", k_tm_reset, reset_blocks(h->d), 256, h->d, p, h->d_reset, h->recording ? h->d_rec : nullptr, 0u);
+static void enqueue_run_reset(htm_handle *h, RunModes m, int p) {
+    if (m.resetting) LAUNCH(h, "tm_reset", k_tm_reset, reset_blocks(h->d), 256, h->d, p, h->d_reset, m.recording ? h->d_rec : nullptr, 0u);
 }
 
-static void enqueue_rest(htm_handle *h, int p, const uint32_t *bank, int n_inputs, int learning, StepPlan plan) {
-    enqueue_run_reset(h, p);
+static void enqueue_rest(htm_handle *h, RunModes m, int p, const uint32_t *bank, int n_inputs, int learning, StepPlan plan) {
+    enqueue_run_reset(h, m, p);
     if ((plan.sp_done || plan.next_sp) && can_lean(h)) {
         enqueue_lean(h, p, learning, bank, n_inputs, plan);
     } else if (plan.sp_done || plan.next_sp) {
@@ -647,13 +646,13 @@ static void enqueue_rest(htm_handle *h, int p, const uint32_t *bank, int n_input
 static int rec_blocks(const Dev &d) { return std::max(REC_BLOCKS_MIN, (d.k + 255) / 256); }
 
 // the record of the step of parity p, behind its last launch (htm_record.h); nothing outside a recorded call
-static void enqueue_record(htm_handle *h, int p) {
-    if (h->recording) LAUNCH(h, "record", k_rec_step, rec_blocks(h->d), 256, h->d, p, h->d_rec);
+static void enqueue_record(htm_handle *h, RunModes m, int p) {
+    if (m.recording) LAUNCH(h, "record", k_rec_step, rec_blocks(h->d), 256, h->d, p, h->d_rec);
 }
 
 // the predicted-input votes of the step of parity p, behind its last launch (htm_decode.h); nothing outside a decoding call
-static void enqueue_decode(htm_handle *h, int p) {
-    if (h->decoding) LAUNCH(h, "predicted_input", k_pin_step, pin_blocks(h->d.C), 256, h->d, p, (const PinDev *)h->d_pin);
+static void enqueue_decode(htm_handle *h, RunModes m, int p) {
+    if (m.decoding) LAUNCH(h, "predicted_input", k_pin_step, pin_blocks(h->d.C), 256, h->d, p, (const PinDev *)h->d_pin);
 }
 
 // The four-launch schedule applies the permanence rows of step t + 1 inside step t (k_mid_rows, rows_ahead = 1), before step t's
@@ -663,8 +662,8 @@ static bool decode_unpipelined(const htm_handle *h) { return h->pin_out && !can_
 
 // Run feedback (htm_forecast.h): behind the step of parity p, the votes of the state it leaves into the scratch row, then the
 // bank row the next step reads.  That step's overlap must come behind these two launches: a feeding call runs unpipelined.
-static void enqueue_feed(htm_handle *h, int p) {
-    if (!h->feeding) return;
+static void enqueue_feed(htm_handle *h, RunModes m, int p) {
+    if (!m.feeding) return;
     LAUNCH(h, "feedback_votes", k_feed_votes, pin_blocks(h->d.C), 256, h->d, p, (const FeedDev *)h->d_feed);
     LAUNCH(h, "feedback_encode", k_feed_step, 1, ENC_THREADS, h->d, p, (const FeedDev *)h->d_feed);
 }
@@ -672,13 +671,19 @@ static void enqueue_feed(htm_handle *h, int p) {
 // grid of the launch that zeroes a decoding call's n x I votes (grid-stride)
 static int pin_begin_blocks(int n, int I) { return (int)std::max<size_t>(1, std::min<size_t>(1024, ((size_t)n * I + 255) / 256)); }
 
-static int enqueue_step(htm_handle *h, const uint32_t *bank, int n_inputs, int learning, StepPlan plan, const uint32_t *host_input = nullptr) {
-    if (!plan.sp_done && !plan.next_sp) enqueue_sp_front(h, bank, n_inputs, (int)(h->step_host & 1), step_wmode(h), host_input);
+// everything behind a step's own launches that the call's modes ask for
+static void enqueue_step_outputs(htm_handle *h, RunModes m, int p) {
+    enqueue_record(h, m, p);
+    enqueue_decode(h, m, p);
+    enqueue_feed(h, m, p);
+}
+
+static int enqueue_step(htm_handle *h, RunModes m, const uint32_t *bank, int n_inputs, int learning, StepPlan plan, const uint32_t *host_input = nullptr) {
+    const int p = (int)(h->step_host & 1);
+    if (!plan.sp_done && !plan.next_sp) enqueue_sp_front(h, bank, n_inputs, p, step_wmode(h), host_input);
     enqueue_cold_start(h, bank, n_inputs, learning, plan);
-    enqueue_rest(h, (int)(h->step_host & 1), bank, n_inputs, learning, plan);
-    enqueue_record(h, (int)(h->step_host & 1));
-    enqueue_decode(h, (int)(h->step_host & 1));
-    enqueue_feed(h, (int)(h->step_host & 1));
+    enqueue_rest(h, m, p, bank, n_inputs, learning, plan);
+    enqueue_step_outputs(h, m, p);
     h->step_host += 1;
     return launch_status(h->err);
 }
@@ -1401,7 +1406,7 @@ extern "C" int htm_step(htm_handle *h, const uint32_t *packed_input, int32_t lea
         return launch_status(h->err);
     }
     flush_tail(h);
-    return enqueue_step(h, h->d.input_stage, 1, learning ? 1 : 0, StepPlan{false, false, false}, packed_input);
+    return enqueue_step(h, RunModes{}, h->d.input_stage, 1, learning ? 1 : 0, StepPlan{false, false, false}, packed_input);
 }
 
 extern "C" int htm_sp_step(htm_handle *h, const uint32_t *packed_input, int32_t learning) {
@@ -1717,84 +1722,99 @@ extern "C" int htm_tm_scan(htm_handle *h, const uint32_t *active_words) {
     return HTM_OK;
 }
 
-// htm_run, or (dry) only the capture + instantiation of every hipGraph that htm_run call would replay.  record: the call is
-// recorded (htm_run_recorded / htm_prepare_recorded; rec = its buffers, checked by the caller, NULL when dry); rec_open: ...
-// and its descriptor is already filled (the rest of a call); pin_open: the same for the decoding descriptor
-static int run_or_prepare(htm_handle *h, const uint32_t *device_inputs, int32_t n_inputs, int32_t n_steps, int32_t learning,
-                          int32_t use_graph, bool dry, bool record = false, const htm_run_record *rec = nullptr, bool rec_open = false,
-                          bool pin_open = false) {
+// Whether a batched call of n_steps with these flags (HTM_RUN_*) replays graphs and (htm_run alone) runs pipelined on this handle now
+// (a short call is launched eagerly whatever the flag says: a graph launch on an idle device starts its first kernel
+// about 7 us later than a kernel launch does, and the host submits three launches per 30-us step with time to spare --
+// measured, 20 steps per call: 615 against 638 us; from 64 steps on the graphs are level and then ahead)
+struct RunSchedule { bool graph, pipeline; };
+static RunSchedule run_schedule(const htm_handle *h, int n_steps, int flags) {
+    return {(flags & 1) && !h->profile && n_steps >= h->knob.eager_below, !(flags & 2) && can_pipeline(h) && !decode_unpipelined(h) && !h->feed_bank};
+}
+
+// what every recorded call refuses about an htm_run_record (who: the call, or the group's member, the message names)
+static int check_run_record(const htm_run_record &r, const std::string &who, std::string &err) {
+    if (r.struct_bytes != sizeof(htm_run_record)) { err = who + ": struct_bytes != sizeof(htm_run_record)"; return HTM_ERR_ARGUMENT; }
+    if (!r.records && !r.active_column && !r.column_prediction) { err = who + ": no record buffer given"; return HTM_ERR_ARGUMENT; }
+    return 0;
+}
+
+// The setup of a batched call's modes (htm_run / htm_run_recorded, htm_tm_run): each mode's device descriptor, allocated on
+// demand and -- unless the call only prepares graphs or has no steps (launch = false) -- filled by its begin launch.  n_bank: the
+// rows of the call's bank; recorded: the call is a recorded one (rec: its buffers, checked by the caller; NULL when it only prepares).
+static int begin_run_modes(htm_handle *h, int n_bank, int n_steps, bool recorded, const htm_run_record *rec, bool launch, RunModes *modes) {
+    int rc;
+    if (h->reset_bits) {
+        if (!h->d_reset && (rc = dalloc(h, &h->d_reset, 1))) return rc;
+        if (launch) LAUNCH(h, "tm_reset", k_reset_begin, 1, 64, h->d_reset, h->reset_bits, (int32_t)n_bank);
+    }
+    if (recorded) {
+        if (!h->d_rec && (rc = dalloc(h, &h->d_rec, 1))) return rc;
+        if (launch) {
+            // the descriptor of this call, and the columns the last completed step predicts (predicted_columns_before of record 0)
+            HIPCHK(h, hipMemsetAsync(h->d_rec, 0, sizeof(RecDev), h->stream));
+            LAUNCH(h, "record", k_rec_begin, rec_blocks(h->d), 256, h->d, (int)((h->step_host + 1) & 1), h->d_rec, rec->records,
+                   rec->active_column, rec->column_prediction, (uint32_t)h->step_host, n_steps);
+        }
+    }
+    if (h->pin_out) {
+        if (!h->d_pin && (rc = dalloc(h, &h->d_pin, 1))) return rc;
+        if (launch) LAUNCH(h, "predicted_input", k_pin_begin, pin_begin_blocks(n_steps, h->d.I), 256, h->d_pin, h->pin_out, (uint32_t)h->step_host, n_steps, h->d.I);
+    }
+    *modes = RunModes{recorded, h->reset_bits != nullptr, h->pin_out != nullptr, h->feed_bank != nullptr};
+    return 0;
+}
+
+// htm_run, or (dry) only the capture + instantiation of every hipGraph that call would replay; recorded (rec: NULL when dry) or not
+struct RunCall { const uint32_t *bank; int32_t n_inputs, n_steps, learning, flags; bool dry; const htm_run_record *rec; bool recorded; };
+
+static int run_or_prepare(htm_handle *h, const RunCall &c) {
     if (h) flush_tail(h);
-    if (!h || !device_inputs || n_inputs < 1 || n_steps < 0) return HTM_ERR_ARGUMENT;
+    if (!h || !c.bank || c.n_inputs < 1 || c.n_steps < 0) return HTM_ERR_ARGUMENT;
     if (!h->cfg.enable_sp || !h->cfg.enable_tm) { h->err = "htm_run needs a handle with SP and TM"; return HTM_ERR_STATE; }
     if (h->world > 1) { h->err = "sharded handle: use htm_shard_begin / htm_shard_finish"; return HTM_ERR_STATE; }
     HIPCHK(h, hipSetDevice(h->device));
-    {
-        const int rc = view_enter(h, learning);
-        if (rc) return rc;
-    }
-    if (learning && !dry && n_steps > 0) weights_touched(h);
+    if (int rc = view_enter(h, c.learning)) return rc;
+    const int n_inputs = c.n_inputs, learning = c.learning ? 1 : 0;
+    int n_steps = c.n_steps;
+    if (learning && !c.dry && n_steps > 0) weights_touched(h);
     refresh_exchange_mode(h);
-    learning = learning ? 1 : 0;
-    // (a short call is launched eagerly whatever the flag says: a graph launch on an idle device starts its first kernel
-    // about 7 us later than a kernel launch does, and the host submits three launches per 30-us step with time to spare --
-    // measured, 20 steps per call: 615 against 638 us; from 64 steps on the graphs are level and then ahead)
-    const bool graph = (use_graph & 1) && !h->profile && n_steps >= h->knob.eager_below;
-    const bool pipeline = !(use_graph & 2) && can_pipeline(h) && !decode_unpipelined(h) && !h->feed_bank;
-    const bool resume = sp_is_ahead(h);            // the previous call left the SP one step (and a front) ahead
+    RunSchedule sched = run_schedule(h, n_steps, c.flags);
+    bool resume = sp_is_ahead(h);                  // the previous call left the SP one step (and a front) ahead
     if (h->feed_bank) {                            // (htm_set_run_feedback: what a feeding call refuses)
         if (learning) { h->err = "htm_run: run feedback is set (htm_set_run_feedback): learning must be 0"; return HTM_ERR_ARGUMENT; }
-        if (h->feed_bank != device_inputs || h->feed_n != n_inputs) { h->err = "htm_run: run feedback was set for another bank or n_inputs (htm_set_run_feedback)"; return HTM_ERR_ARGUMENT; }
+        if (h->feed_bank != c.bank || h->feed_n != n_inputs) { h->err = "htm_run: run feedback was set for another bank or n_inputs (htm_set_run_feedback)"; return HTM_ERR_ARGUMENT; }
         if (h->reset_bits) { h->err = "htm_run: run feedback and reset bits are set at the same time (htm_set_run_feedback, htm_set_run_resets)"; return HTM_ERR_ARGUMENT; }
         if (resume) { h->err = "htm_run: run feedback is set while the Spatial Pooler is ahead (HTM_RUN_CONTINUE)"; return HTM_ERR_STATE; }
     }
-    if (resume && (h->ahead_bank != device_inputs || h->ahead_n_inputs != n_inputs || h->ahead_learning != learning)) {
+    if (resume && (h->ahead_bank != c.bank || h->ahead_n_inputs != n_inputs || h->ahead_learning != learning)) {
         h->err = "htm_run: the previous call ended with HTM_RUN_CONTINUE; this one must use the same bank, n_inputs and learning flag";
         return HTM_ERR_STATE;
     }
     // keep looking ahead past the end of this call -- where the pipelined schedule is available (the flag is a promise of
     // the caller's, not a demand: without the schedule the call simply leaves nothing outstanding)
-    const bool cont = (use_graph & 4) && pipeline && n_steps > 0;
+    const bool pipeline = sched.pipeline, cont = (c.flags & 4) && pipeline && n_steps > 0;
     if (h->reset_bits && h->reset_n != n_inputs) { h->err = "htm_run: the reset bits were set for a bank of another n_inputs (htm_set_run_resets)"; return HTM_ERR_ARGUMENT; }
-    if (dry && !graph) return HTM_OK;
-    if (!dry) { int rc = close_open_phases(h); if (rc) return rc; }
-    struct RecordingOff { htm_handle *h; ~RecordingOff() { h->recording = false; h->resetting = false; h->decoding = false; h->feeding = false; } } recording_off{h};
-    if (h->reset_bits && !h->d_reset) { int rc = dalloc(h, &h->d_reset, 1); if (rc) return rc; }
-    if (h->reset_bits && !rec_open && !dry && n_steps > 0)
-        LAUNCH(h, "tm_reset", k_reset_begin, 1, 64, h->d_reset, h->reset_bits, (int32_t)n_inputs);
-    h->resetting = h->reset_bits != nullptr;
-    if (record && !rec_open && !dry && n_steps > 0) {
-        // the descriptor of this call, and the columns the last completed step predicts (predicted_columns_before of record 0)
-        HIPCHK(h, hipMemsetAsync(h->d_rec, 0, sizeof(RecDev), h->stream));
-        LAUNCH(h, "record", k_rec_begin, rec_blocks(h->d), 256, h->d, (int)((h->step_host + 1) & 1), h->d_rec, rec->records,
-               rec->active_column, rec->column_prediction, (uint32_t)h->step_host, n_steps);
-    }
-    h->recording = record;
-    if (h->pin_out && !h->d_pin) { int rc = dalloc(h, &h->d_pin, 1); if (rc) return rc; }
-    if (h->pin_out && !pin_open && !dry && n_steps > 0)
-        LAUNCH(h, "predicted_input", k_pin_begin, pin_begin_blocks(n_steps, h->d.I), 256, h->d_pin, h->pin_out, (uint32_t)h->step_host, n_steps, h->d.I);
-    h->decoding = h->pin_out != nullptr;
-    h->feeding = h->feed_bank != nullptr;
+    if (c.dry && !sched.graph) return HTM_OK;
+    if (!c.dry) { int rc = close_open_phases(h); if (rc) return rc; }
+    RunModes modes;
+    if (int rc = begin_run_modes(h, n_inputs, n_steps, c.recorded, c.rec, !c.dry && n_steps > 0, &modes)) return rc;
     // The SP is ahead but the pipelined schedule is gone (another handle with its own stream has appeared on the device since,
     // or this call asks for HTM_RUN_NO_PIPELINE): the coming step is run as the LAST step of the run that went ahead -- its
     // launches hold no select finish, so nothing in them waits for another block -- and the rest of the call unpipelined.
     if (resume && !pipeline && n_steps > 0) {
-        if (dry) return HTM_OK;                      // (that step is launched eagerly; the rest builds its graphs when it runs)
-        {
-            const int p = (int)(h->step_host & 1);
-            const StepPlan last{true, false, false};
-            enqueue_run_reset(h, p);
-            if (h->ahead_lean) enqueue_lean(h, p, learning, device_inputs, n_inputs, last);
-            else enqueue_pipelined(h, p, learning, device_inputs, n_inputs, last);
-            enqueue_record(h, p);
-            enqueue_decode(h, p);
-            h->step_host += 1;
-            // (the four-launch schedule had begun the step after it: that front is never consumed)
-            HIPCHK(h, hipMemsetAsync(h->d.hist0 + (size_t)(h->step_host & 1) * HIST0_PAR, 0, (size_t)HIST0_PAR * 4, h->stream));
-            h->ahead_bank = nullptr;
-            const int rc = launch_status(h->err);
-            if (rc) return rc;
-        }
-        return run_or_prepare(h, device_inputs, n_inputs, n_steps - 1, learning, use_graph, false, h->recording, nullptr, h->recording, h->decoding);
+        if (c.dry) return HTM_OK;                      // (that step is launched eagerly; the rest builds its graphs when it runs)
+        const int p = (int)(h->step_host & 1);
+        enqueue_run_reset(h, modes, p);
+        (h->ahead_lean ? enqueue_lean : enqueue_pipelined)(h, p, learning, c.bank, n_inputs, StepPlan{true, false, false});
+        enqueue_step_outputs(h, modes, p);
+        h->step_host += 1;
+        // (the four-launch schedule had begun the step after it: that front is never consumed)
+        HIPCHK(h, hipMemsetAsync(h->d.hist0 + (size_t)(h->step_host & 1) * HIST0_PAR, 0, (size_t)HIST0_PAR * 4, h->stream));
+        h->ahead_bank = nullptr;
+        if (int rc = launch_status(h->err)) return rc;
+        n_steps -= 1;
+        resume = false;
+        sched = run_schedule(h, n_steps, c.flags);
     }
     // Graphs hold the launches of one step, or of up to kGraphSteps consecutive steady-state steps (a graph
     // launch boundary costs about 5 us more than a kernel boundary inside a graph: tools/step_timeline.py).
@@ -1808,8 +1828,8 @@ static int run_or_prepare(htm_handle *h, const uint32_t *device_inputs, int32_t 
         const bool lean = pipeline && can_lean(h);      // (looks one step ahead, not two)
         const StepPlan plan{sp_done, pipeline && (t + 1 < n_steps || cont), pipeline && !lean && (t + 2 < n_steps || cont)};
         sp_done = plan.next_sp;
-        if (!graph) {
-            int rc = enqueue_step(h, device_inputs, n_inputs, learning, plan);
+        if (!sched.graph) {
+            int rc = enqueue_step(h, modes, c.bank, n_inputs, learning, plan);
             if (rc) return rc;
             t += 1;
             continue;
@@ -1822,34 +1842,32 @@ static int run_or_prepare(htm_handle *h, const uint32_t *device_inputs, int32_t 
             if (cont && steady > 1 && steady < 2 * kGraphSteps) span = steady;      // a continuing call's (last) stretch: one graph
             else if (steady >= kGraphSteps) span = kGraphSteps;
         }
-        if (!dry) {
-            if (!plan.sp_done && !plan.next_sp) enqueue_sp_front(h, device_inputs, n_inputs, p, step_wmode(h));    // eager
-            enqueue_cold_start(h, device_inputs, n_inputs, learning, plan);                         // eager: first step of a pipelined run
+        if (!c.dry) {
+            if (!plan.sp_done && !plan.next_sp) enqueue_sp_front(h, c.bank, n_inputs, p, step_wmode(h));    // eager
+            enqueue_cold_start(h, c.bank, n_inputs, learning, plan);                         // eager: first step of a pipelined run
         }
-        const RunGraphKey key{p, h->recording, h->resetting, h->decoding, h->feeding, learning, plan.sp_done, plan.next_sp, plan.next_front, lean,
-                              scan_spec_blocks(h), scan_pool_is_large(h), h->emit_fused, step_wmode(h) != 0, span, device_inputs, n_inputs};
+        const RunGraphKey key{p, modes, learning, plan.sp_done, plan.next_sp, plan.next_front, lean,
+                              scan_spec_blocks(h), scan_pool_is_large(h), h->emit_fused, step_wmode(h) != 0, span, c.bank, n_inputs};
         const hipGraphExec_t exec = cached_graph(h->graphs, key, h->stream, h->err, [&] {
             for (int i = 0; i < span; ++i) {
-                enqueue_rest(h, (p + i) & 1, device_inputs, n_inputs, learning, plan);
-                enqueue_record(h, (p + i) & 1);
-                enqueue_decode(h, (p + i) & 1);
-                enqueue_feed(h, (p + i) & 1);
+                enqueue_rest(h, modes, (p + i) & 1, c.bank, n_inputs, learning, plan);
+                enqueue_step_outputs(h, modes, (p + i) & 1);
             }
             return 0;
         });
         if (!exec) return HTM_ERR_HIP;
-        if (!dry) {
+        if (!c.dry) {
             HIPCHK(h, hipGraphLaunch(exec, h->stream));
             h->step_host += span;
         }
         step += span;
         t += span;
     }
-    if (dry) return HTM_OK;
+    if (c.dry) return HTM_OK;
     if (n_steps > 0) {
         if (resume && !cont && n_steps == 1)        // the front computed for the step after this one is never consumed:
             HIPCHK(h, hipMemsetAsync(h->d.hist0 + (size_t)(h->step_host & 1) * HIST0_PAR, 0, (size_t)HIST0_PAR * 4, h->stream));    // its digit histogram
-        h->ahead_bank = cont ? device_inputs : nullptr;
+        h->ahead_bank = cont ? c.bank : nullptr;
         h->ahead_lean = cont && can_lean(h);
         h->ahead_n_inputs = n_inputs;
         h->ahead_learning = learning;
@@ -1860,53 +1878,48 @@ static int run_or_prepare(htm_handle *h, const uint32_t *device_inputs, int32_t 
 }
 
 extern "C" int htm_run(htm_handle *h, const uint32_t *device_inputs, int32_t n_inputs, int32_t n_steps, int32_t learning, int32_t use_graph) {
-    return run_or_prepare(h, device_inputs, n_inputs, n_steps, learning, use_graph, false);
+    return run_or_prepare(h, RunCall{device_inputs, n_inputs, n_steps, learning, use_graph, false, nullptr, false});
 }
 
 extern "C" int htm_prepare(htm_handle *h, const uint32_t *device_inputs, int32_t n_inputs, int32_t n_steps, int32_t learning, int32_t use_graph) {
-    return run_or_prepare(h, device_inputs, n_inputs, n_steps, learning, use_graph, true);
+    return run_or_prepare(h, RunCall{device_inputs, n_inputs, n_steps, learning, use_graph, true, nullptr, false});
 }
 
-// htm_run with a per-step record (include/bithtm_hip.h).  dry (htm_prepare_recorded): the graphs only -- they do not depend
+// htm_run with a per-step record (include/bithtm_hip.h).  c.dry (htm_prepare_recorded): the graphs only -- they do not depend
 // on the buffers, so there is no rec to check.
-static int run_recorded(htm_handle *h, const uint32_t *device_inputs, int32_t n_inputs, int32_t n_steps, int32_t learning,
-                        int32_t use_graph, const htm_run_record *rec, bool dry) {
+static int run_recorded(htm_handle *h, const RunCall &c) {
     if (!h) return HTM_ERR_ARGUMENT;
     if (h->world > 1) { h->err = "htm_run_recorded: a sharded handle has no recorded run"; return HTM_ERR_STATE; }
     // (k_rec_step sums its counts in 24-bit fields of one word: RecDev::acc)
     if (h->d.C >= (1 << 24)) { h->err = "htm_run_recorded: column_dim must be below 2^24"; return HTM_ERR_STATE; }
-    if (!dry) {
-        if (rec->struct_bytes != sizeof(htm_run_record)) { h->err = "htm_run_recorded: struct_bytes != sizeof(htm_run_record)"; return HTM_ERR_ARGUMENT; }
-        if (!rec->records && !rec->active_column && !rec->column_prediction) { h->err = "htm_run_recorded: no record buffer given"; return HTM_ERR_ARGUMENT; }
-    }
-    if (!h->d_rec) {
+    if (!c.dry) { int rc = check_run_record(*c.rec, "htm_run_recorded", h->err); if (rc) return rc; }
+    if (!h->d_rec) {                                // (ahead of whatever the call lets go first)
         HIPCHK(h, hipSetDevice(h->device));
-        int rc = dalloc(h, &h->d_rec, 1);
-        if (rc) return rc;
+        if (int rc = dalloc(h, &h->d_rec, 1)) return rc;
     }
-    return run_or_prepare(h, device_inputs, n_inputs, n_steps, learning, use_graph, dry, true, rec);
+    return run_or_prepare(h, c);
 }
 
 extern "C" int htm_run_recorded(htm_handle *h, const uint32_t *device_inputs, int32_t n_inputs, int32_t n_steps, int32_t learning,
                                 int32_t use_graph, const htm_run_record *rec) {
-    if (!rec) return run_or_prepare(h, device_inputs, n_inputs, n_steps, learning, use_graph, false);
-    return run_recorded(h, device_inputs, n_inputs, n_steps, learning, use_graph, rec, false);
+    if (!rec) return htm_run(h, device_inputs, n_inputs, n_steps, learning, use_graph);
+    return run_recorded(h, RunCall{device_inputs, n_inputs, n_steps, learning, use_graph, false, rec, true});
 }
 
 extern "C" int htm_prepare_recorded(htm_handle *h, const uint32_t *device_inputs, int32_t n_inputs, int32_t n_steps, int32_t learning,
                                     int32_t use_graph) {
-    return run_recorded(h, device_inputs, n_inputs, n_steps, learning, use_graph, nullptr, true);
+    return run_recorded(h, RunCall{device_inputs, n_inputs, n_steps, learning, use_graph, true, nullptr, true});
 }
 
 // Batched stand-alone Temporal Memory run (include/bithtm_hip.h; htm_tm_feed.h): n_steps of htm_tm_step
 // (return_winner_cell = 1) over a device bank of lists, without the host in the loop.  The launches of one step, in order.
-static void enqueue_tm_run_step(htm_handle *h, int p, const int32_t *lists, int n_rows, int n, int learning) {
+static void enqueue_tm_run_step(htm_handle *h, RunModes m, int p, const int32_t *lists, int n_rows, int n, int learning) {
     Dev &d = h->d;
-    enqueue_run_reset(h, p);
+    enqueue_run_reset(h, m, p);
     LAUNCH_ON(h, h->stream, feed_lds(d), "tm_feed", k_tm_feed, std::min((d.C + 255) / 256, 1024), FEED_THREADS, d, p, lists, n_rows, n);
     LAUNCH(h, "tm_activate", k_tm_activate, std::max(1, (n * d.KP + 255) / 256), 256, d, p, n, 1);
     enqueue_tm(h, n, learning, 1, p, nullptr, 1, false);
-    if (h->recording) LAUNCH(h, "record", k_tm_feed_record, rec_blocks(d), 256, d, p, h->d_rec, n);
+    if (m.recording) LAUNCH(h, "record", k_tm_feed_record, rec_blocks(d), 256, d, p, h->d_rec, n);
 }
 
 extern "C" int htm_tm_run(htm_handle *h, const int32_t *device_lists, int32_t n_rows, int32_t n, int32_t n_steps, int32_t learning,
@@ -1919,10 +1932,7 @@ extern "C" int htm_tm_run(htm_handle *h, const int32_t *device_lists, int32_t n_
         h->err = "htm_tm_run: n_rows >= 1, 1 <= n <= active_columns and n_steps >= 0";
         return HTM_ERR_ARGUMENT;
     }
-    if (rec) {
-        if (rec->struct_bytes != sizeof(htm_run_record)) { h->err = "htm_tm_run: struct_bytes != sizeof(htm_run_record)"; return HTM_ERR_ARGUMENT; }
-        if (!rec->records && !rec->active_column && !rec->column_prediction) { h->err = "htm_tm_run: no record buffer given"; return HTM_ERR_ARGUMENT; }
-    }
+    if (rec) { int rc = check_run_record(*rec, "htm_tm_run", h->err); if (rc) return rc; }
     if (!h->cfg.enable_tm) { h->err = "htm_tm_run: the handle has no Temporal Memory"; return HTM_ERR_STATE; }
     if (h->world > 1) { h->err = "htm_tm_run: not available on a column-sharded handle"; return HTM_ERR_STATE; }
     REFUSE_ON_VIEW(h, "htm_tm_run");
@@ -1937,36 +1947,24 @@ extern "C" int htm_tm_run(htm_handle *h, const int32_t *device_lists, int32_t n_
     HIPCHK(h, hipSetDevice(h->device));
     learning = learning ? 1 : 0;
     if (learning) weights_touched(h);
-    const bool graph = (use_graph & 1) && !h->profile && n_steps >= h->knob.eager_below;
-    struct ModesOff { htm_handle *h; ~ModesOff() { h->recording = false; h->resetting = false; } } modes_off{h};
-    if (h->reset_bits) {
-        if (!h->d_reset) { int rc = dalloc(h, &h->d_reset, 1); if (rc) return rc; }
-        LAUNCH(h, "tm_reset", k_reset_begin, 1, 64, h->d_reset, h->reset_bits, n_rows);
-    }
-    h->resetting = h->reset_bits != nullptr;
-    if (rec) {
-        if (!h->d_rec) { int rc = dalloc(h, &h->d_rec, 1); if (rc) return rc; }
-        // the descriptor of this call, and the columns the last completed step predicts (predicted_columns_before of record 0)
-        HIPCHK(h, hipMemsetAsync(h->d_rec, 0, sizeof(RecDev), h->stream));
-        LAUNCH(h, "record", k_rec_begin, rec_blocks(d), 256, d, (int)((h->step_host + 1) & 1), h->d_rec, rec->records, rec->active_column,
-               rec->column_prediction, (uint32_t)h->step_host, n_steps);
-    }
-    h->recording = rec != nullptr;
+    const bool graph = run_schedule(h, n_steps, use_graph).graph;
+    RunModes modes;
+    if (int rc = begin_run_modes(h, n_rows, n_steps, rec != nullptr, rec, true, &modes)) return rc;
     refresh_seg_hint(h);                            // what the last run left
     const int kGraphSteps = h->knob.graph_steps;
     for (int t = 0; t < n_steps;) {
         const int p = (int)(h->step_host & 1);
         if (!graph) {
-            enqueue_tm_run_step(h, p, device_lists, n_rows, n, learning);
+            enqueue_tm_run_step(h, modes, p, device_lists, n_rows, n, learning);
             h->step_host += 1;
             t += 1;
             continue;
         }
         // (nothing in a graph depends on the step index: the feed launch reads it, and with it the bank row, from the counter block)
         const int span = n_steps - t >= kGraphSteps ? kGraphSteps : 1;
-        const TmRunGraphKey key{p, h->recording, h->resetting, learning, scan_spec_blocks(h), scan_pool_is_large(h), span, device_lists, n_rows, n};
+        const TmRunGraphKey key{p, modes, learning, scan_spec_blocks(h), scan_pool_is_large(h), span, device_lists, n_rows, n};
         const hipGraphExec_t exec = cached_graph(h->tm_graphs, key, h->stream, h->err, [&] {
-            for (int i = 0; i < span; ++i) enqueue_tm_run_step(h, (p + i) & 1, device_lists, n_rows, n, learning);
+            for (int i = 0; i < span; ++i) enqueue_tm_run_step(h, modes, (p + i) & 1, device_lists, n_rows, n, learning);
             return 0;
         });
         if (!exec) return HTM_ERR_HIP;
@@ -1990,8 +1988,8 @@ extern "C" int htm_run_plan(htm_handle *h, int32_t n_steps, int32_t use_graph) {
     if (!h->cfg.enable_sp || !h->cfg.enable_tm || h->world > 1) { h->err = "htm_run_plan: htm_run needs an unsharded handle with SP and TM"; return HTM_ERR_STATE; }
     refresh_exchange_mode(h);
     refresh_seg_hint(h);
-    const bool graph = (use_graph & 1) && !h->profile && n_steps >= h->knob.eager_below;
-    const bool pipeline = !(use_graph & 2) && can_pipeline(h) && !decode_unpipelined(h) && !h->feed_bank && n_steps > 1;
+    const RunSchedule sched = run_schedule(h, n_steps, use_graph);
+    const bool graph = sched.graph, pipeline = sched.pipeline && n_steps > 1;
     return (graph ? HTM_PLAN_GRAPH : 0) | (pipeline ? HTM_PLAN_PIPELINED : 0) | (pipeline && can_lean(h) ? HTM_PLAN_LEAN : 0) |
            (scan_pool_is_large(h) ? HTM_PLAN_SCAN_LARGE : 0);
 }
@@ -3206,8 +3204,8 @@ extern "C" int htm_profile_read(htm_handle *h, int32_t max_kernels, const char *
 
 // ... htm_group_run: the step's parity, the call's modes, the form of the group's launches (GroupForm), the span, the bank table
 struct GroupGraphKey {
-    int p; bool recording, decoding, feeding; int learning; bool fuse, large, shared; int spec, span; const void *bank_tab; int n_inputs;
-    auto tie() const { return std::tie(p, recording, decoding, feeding, learning, fuse, large, shared, spec, span, bank_tab, n_inputs); }
+    int p; RunModes modes; int learning; bool fuse, large, shared; int spec, span; const void *bank_tab; int n_inputs;
+    auto tie() const { return std::tie(p, modes, learning, fuse, large, shared, spec, span, bank_tab, n_inputs); }
     bool operator<(const GroupGraphKey &o) const { return tie() < o.tie(); }
 };
 
@@ -3231,7 +3229,6 @@ struct htm_group {
     std::map<std::vector<const void *>, GrpRecArgs *> rec_tabs;
     std::map<std::vector<int32_t *>, int32_t **> pin_tabs;      // the members' decoding outputs (htm_set_run_predicted_input)
     std::map<GroupGraphKey, hipGraphExec_t> graphs;
-    bool recording, decoding, feeding;
     // inference views (htm_create_view): some member is a view; every member aliases one set of weights (then the steps with
     // learning = 0 scan the store once per chunk of share_m members: kgrp_scan_shared, share_chunks x share_blocks blocks)
     bool has_view, shared;
@@ -3419,7 +3416,7 @@ static decltype(&kgrp_tail<1>) const kt_grp_tail[4] = {kgrp_tail<1>, kgrp_tail<2
 static decltype(&kgrp_scan<true, 1>) const kt_grp_scan[4] = {kgrp_scan<true, 1>, kgrp_scan<false, 1>, kgrp_scan<true, 6>, kgrp_scan<false, 6>};
 
 // one step of every member (parity p): the one-role-per-launch schedule of enqueue_rest, unfused (htm_group.h)
-static void group_enqueue_step(htm_group *g, const uint32_t *const *banks, int n_inputs, int learning, int p, const GroupForm &f) {
+static void group_enqueue_step(htm_group *g, RunModes m, const uint32_t *const *banks, int n_inputs, int learning, int p, const GroupForm &f) {
     htm_handle *h = g->m[0];                   // (launch sizes and profiling: the members' are equal)
     const Dev &d = h->d;
     const hipStream_t s = g->stream;
@@ -3453,15 +3450,15 @@ static void group_enqueue_step(htm_group *g, const uint32_t *const *banks, int n
                       tab, p, f.spec);
         }
     }
-    if (g->recording) {
+    if (m.recording) {
         const dim3 g_rec(rec_blocks(d), B);
         LAUNCH_ON(h, s, 0, "group:record", kgrp_rec_step, g_rec, 256, tab, p, g->d_recs);
     }
-    if (g->decoding) {
+    if (m.decoding) {
         const dim3 g_pin(pin_blocks(d.C), B);
         LAUNCH_ON(h, s, 0, "group:predicted_input", kgrp_pin_step, g_pin, 256, tab, p, g->d_pins);
     }
-    if (g->feeding) {                              // (members without feedback leave both launches at once: htm_forecast.h)
+    if (m.feeding) {                              // (members without feedback leave both launches at once: htm_forecast.h)
         const dim3 g_pin(pin_blocks(d.C), B);
         LAUNCH_ON(h, s, 0, "group:feedback_votes", kgrp_feed_votes, g_pin, 256, tab, p, g->d_feeds);
         LAUNCH_ON(h, s, 0, "group:feedback_encode", kgrp_feed_step, dim3(1, B), ENC_THREADS, tab, p, g->d_feeds);
@@ -3491,11 +3488,7 @@ static int group_check(htm_group *g, const uint32_t *const *banks, const htm_run
             std::lock_guard<std::mutex> lock(g_shared_mutex);
             if (h->shared->parent && sp_is_ahead(h->shared->parent)) { g->err = who + ": the view's parent is ahead (HTM_RUN_CONTINUE)"; return HTM_ERR_STATE; }
         }
-        if (records) {
-            const htm_run_record &r = records[i];
-            if (r.struct_bytes != sizeof(htm_run_record)) { g->err = who + ": struct_bytes != sizeof(htm_run_record)"; return HTM_ERR_ARGUMENT; }
-            if (!r.records && !r.active_column && !r.column_prediction) { g->err = who + ": no record buffer given"; return HTM_ERR_ARGUMENT; }
-        }
+        if (records) { int rc = check_run_record(records[i], who, g->err); if (rc) return rc; }
     }
     if (records && h0->d.C >= (1 << 24)) { g->err = "recorded group calls need column_dim below 2^24"; return HTM_ERR_STATE; }
     return 0;
@@ -3521,13 +3514,12 @@ static int group_join(htm_group *g) {
     return 0;
 }
 
-static int group_run(htm_group *g, const uint32_t **bank_tab, int n_inputs, int n_steps, int learning, int use_graph,
-                     const htm_run_record *records) {
+// The setup of a group call's modes, on the members' tables: the record and decoding descriptors of every member filled by one
+// begin launch each (begin_run_modes is a single handle's)
+static int group_begin_modes(htm_group *g, int n_steps, const htm_run_record *records, RunModes *modes) {
     const int B = g->n;
     htm_handle *h0 = g->m[0];
     const hipStream_t s = g->stream;
-    learning = learning ? 1 : 0;
-    struct RecordingOff { htm_group *g; ~RecordingOff() { g->recording = false; g->decoding = false; g->feeding = false; } } recording_off{g};
     if (records) {
         std::vector<GrpRecArgs> rows(B);
         std::vector<const void *> key;
@@ -3536,42 +3528,48 @@ static int group_run(htm_group *g, const uint32_t **bank_tab, int n_inputs, int 
             key.insert(key.end(), {rows[i].rec, rows[i].cols, rows[i].colpred});
         }
         GrpRecArgs *args = nullptr;
-        int rc = group_table(g, g->rec_tabs, key, rows.data(), &args);
-        if (rc) return rc;
+        if (int rc = group_table(g, g->rec_tabs, key, rows.data(), &args)) return rc;
         LAUNCH_ON(h0, s, 0, "group:record", kgrp_rec_clear, B, 64, g->d_recs);
-        const dim3 g_rec(rec_blocks(h0->d), B);
-        LAUNCH_ON(h0, s, 0, "group:record", kgrp_rec_begin, g_rec, 256, g->d_tab, (int)((h0->step_host + 1) & 1), g->d_recs, args, n_steps);
-        g->recording = true;
+        LAUNCH_ON(h0, s, 0, "group:record", kgrp_rec_begin, dim3(rec_blocks(h0->d), B), 256, g->d_tab, (int)((h0->step_host + 1) & 1), g->d_recs, args, n_steps);
     }
     // members with decoding outputs (htm_set_run_predicted_input): their rows zeroed and every member's descriptor filled (the
     // others' with no rows), then one decoding launch behind each step
     std::vector<int32_t *> outs(B);
     for (int i = 0; i < B; ++i) outs[i] = g->m[i]->pin_out;
-    if (std::any_of(outs.begin(), outs.end(), [](int32_t *o) { return o != nullptr; })) {
+    const bool decoding = std::any_of(outs.begin(), outs.end(), [](int32_t *o) { return o != nullptr; });
+    if (decoding) {
         int32_t **out_tab = nullptr;
-        int rc = group_table(g, g->pin_tabs, outs, outs.data(), &out_tab);
-        if (rc) return rc;
-        const dim3 g_begin(pin_begin_blocks(n_steps, h0->d.I), B);
-        LAUNCH_ON(h0, s, 0, "group:predicted_input", kgrp_pin_begin, g_begin, 256, g->d_tab, (int)((h0->step_host + 1) & 1), g->d_pins, out_tab, n_steps);
-        g->decoding = true;
+        if (int rc = group_table(g, g->pin_tabs, outs, outs.data(), &out_tab)) return rc;
+        LAUNCH_ON(h0, s, 0, "group:predicted_input", kgrp_pin_begin, dim3(pin_begin_blocks(n_steps, h0->d.I), B), 256, g->d_tab, (int)((h0->step_host + 1) & 1), g->d_pins, out_tab, n_steps);
     }
-    g->feeding = std::any_of(g->m.begin(), g->m.end(), [](const htm_handle *h) { return h->feed_bank != nullptr; });
+    const bool feeding = std::any_of(g->m.begin(), g->m.end(), [](const htm_handle *h) { return h->feed_bank != nullptr; });
+    *modes = RunModes{records != nullptr, false, decoding, feeding};
+    return 0;
+}
+
+static int group_run(htm_group *g, const uint32_t **bank_tab, int n_inputs, int n_steps, int learning, int use_graph,
+                     const htm_run_record *records) {
+    htm_handle *h0 = g->m[0];
+    const hipStream_t s = g->stream;
+    learning = learning ? 1 : 0;
+    RunModes modes;
+    if (int rc = group_begin_modes(g, n_steps, records, &modes)) return rc;
     GroupForm f = group_form(g);
     f.shared = g->shared && !learning;
-    const bool graph = (use_graph & 1) && !h0->profile && n_steps >= h0->knob.eager_below;
+    const bool graph = run_schedule(h0, n_steps, use_graph).graph;
     const int span_max = h0->knob.graph_steps;
     int p = (int)(h0->step_host & 1);
     for (int t = 0; t < n_steps;) {
         if (!graph) {
-            group_enqueue_step(g, bank_tab, n_inputs, learning, p, f);
+            group_enqueue_step(g, modes, bank_tab, n_inputs, learning, p, f);
             p ^= 1;
             t += 1;
             continue;
         }
         const int span = n_steps - t >= span_max ? span_max : 1;
-        const GroupGraphKey key{p, g->recording, g->decoding, g->feeding, learning, f.fuse, f.large, f.shared, f.spec, span, bank_tab, n_inputs};
+        const GroupGraphKey key{p, modes, learning, f.fuse, f.large, f.shared, f.spec, span, bank_tab, n_inputs};
         const hipGraphExec_t exec = cached_graph(g->graphs, key, s, g->err, [&] {
-            for (int i = 0; i < span; ++i) group_enqueue_step(g, bank_tab, n_inputs, learning, (p + i) & 1, f);
+            for (int i = 0; i < span; ++i) group_enqueue_step(g, modes, bank_tab, n_inputs, learning, (p + i) & 1, f);
             return 0;
         });
         if (!exec) return HTM_ERR_HIP;
