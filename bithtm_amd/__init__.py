@@ -19,3 +19,4 @@ SpatialPooler = networks.SpatialPooler
 TemporalMemory = networks.TemporalMemory
 HierarchicalTemporalMemory = networks.HierarchicalTemporalMemory
 RunRecord = networks.RunRecord
+SPRunRecord = networks.SPRunRecord

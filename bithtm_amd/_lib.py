@@ -49,6 +49,10 @@ class HtmRunRecord(C.Structure):
     _fields_ = [("struct_bytes", C.c_uint32), ("records", C.c_void_p), ("active_column", C.c_void_p), ("column_prediction", C.c_void_p)]
 
 
+class HtmSpRunRecord(C.Structure):
+    _fields_ = [("struct_bytes", C.c_uint32), ("active_column", C.c_void_p), ("active_overlap", C.c_void_p), ("active_boosted", C.c_void_p)]
+
+
 # htm_field
 F_ACTIVE_COLUMN, F_OVERLAPS, F_BOOSTED, F_DUTY_CYCLE, F_CELL_ACTIVATION, F_CELL_PREDICTION = 1, 2, 3, 4, 5, 6
 F_WINNER_WORDS, F_BURSTING, F_WINNER_CELL, F_SEG_CELL, F_SEG_NSYN, F_SEG_PRESYN, F_SEG_PERM = 7, 8, 9, 10, 11, 12, 13
@@ -72,6 +76,7 @@ EXPORTS = {
     "htm_tm_update": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
     "htm_tm_scan": (C.c_int, [C.c_void_p, C.c_void_p]),
     "htm_tm_run": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(HtmRunRecord)]),
+    "htm_sp_run": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(HtmSpRunRecord)]),
     "htm_run": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     "htm_prepare": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     "htm_run_recorded": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(HtmRunRecord)]),

@@ -46,6 +46,7 @@
 #include "htm_noise.h"
 #include "htm_group.h"
 #include "htm_tm_feed.h"
+#include "htm_sp_run.h"
 
 // ------------------------------------------------------------------------------------------
 // host side
@@ -110,6 +111,14 @@ struct TmRunGraphKey {
     bool operator<(const TmRunGraphKey &o) const { return tie() < o.tie(); }
 };
 
+// ... htm_sp_run: the step's parity, the learning flag, whether the steps are recorded, the form of the select (launched count or
+// in-kernel finish; digits or window), the span of steps, the bank
+struct SpRunGraphKey {
+    int p, learning; bool recording, emit_fused; int wmode, span; const void *bank; int n_inputs;
+    auto tie() const { return std::tie(p, learning, recording, emit_fused, wmode, span, bank, n_inputs); }
+    bool operator<(const SpRunGraphKey &o) const { return tie() < o.tie(); }
+};
+
 struct htm_handle {
     htm_config cfg;
     Dev d;
@@ -165,6 +174,8 @@ struct htm_handle {
     int32_t *d_feed_votes;
     std::map<RunGraphKey, hipGraphExec_t> graphs;
     std::map<TmRunGraphKey, hipGraphExec_t> tm_graphs;        // htm_tm_run
+    std::map<SpRunGraphKey, hipGraphExec_t> sp_graphs;        // htm_sp_run
+    SpRecDev *d_sp_rec;                   // ... its recorded calls: the device descriptor the tail launches read (filled by each such call)
     // state import staging (htm_write of the MATCH_* / SEG_POTENTIAL fields, applied at commit)
     std::vector<int> imp_pot, imp_match_seg;
     // ... on a column-sharded handle also the per-segment arrays (written for ALL segment ids; the commit keeps the rows of
@@ -703,6 +714,7 @@ extern "C" void htm_destroy(htm_handle *h) {
     for (auto &kv : h->graphs) hipGraphExecDestroy(kv.second);
     for (auto &kv : h->shard_graphs) hipGraphExecDestroy(kv.second);
     for (auto &kv : h->tm_graphs) hipGraphExecDestroy(kv.second);
+    for (auto &kv : h->sp_graphs) hipGraphExecDestroy(kv.second);
     for (auto &v : h->prof_events)
         for (auto &pr : v) { hipEventDestroy(pr.first); hipEventDestroy(pr.second); }
     for (hipEvent_t e : h->prof_all) hipEventDestroy(e);
@@ -1978,9 +1990,79 @@ extern "C" int htm_tm_run(htm_handle *h, const int32_t *device_lists, int32_t n_
     return launch_status(h->err);
 }
 
+// Batched stand-alone Spatial Pooler run (include/bithtm_hip.h; htm_sp_run.h): n_steps of htm_sp_step over
+// a bank in device memory, without the host in the loop.  The launches of one step, in order: htm_sp_step's front and back,
+// then the tail launch with the winner rows and / or the step's record (none for a step that neither learns nor records).
+static void enqueue_sp_run_step(htm_handle *h, const uint32_t *bank, int n_inputs, int p, int learning, bool recording, int wmode) {
+    Dev &d = h->d;
+    enqueue_sp_front(h, bank, n_inputs, p, wmode);
+    enqueue_sp_back(h, bank, n_inputs, p, 0, EMIT_ALL, false, wmode);
+    const int n_learn = learning ? d.k : 0, n_rec = recording ? (d.k + 255) / 256 : 0;
+    if (n_learn + n_rec)
+        LAUNCH(h, "sp_run_tail", k_sp_run_tail, n_learn + n_rec, 256, d, bank, n_inputs, p, n_learn, recording ? h->d_sp_rec : nullptr);
+}
+
+extern "C" int htm_sp_run(htm_handle *h, const uint32_t *device_inputs, int32_t n_inputs, int32_t n_steps, int32_t learning,
+                          int32_t use_graph, const htm_sp_run_record *rec) {
+    if (!h) return HTM_ERR_ARGUMENT;
+    if (!device_inputs) { h->err = "htm_sp_run: null bank"; return HTM_ERR_ARGUMENT; }
+    if (n_inputs < 1 || n_steps < 0) { h->err = "htm_sp_run: n_inputs >= 1 and n_steps >= 0"; return HTM_ERR_ARGUMENT; }
+    if (rec) {
+        if (rec->struct_bytes != sizeof(htm_sp_run_record)) { h->err = "htm_sp_run: struct_bytes != sizeof(htm_sp_run_record)"; return HTM_ERR_ARGUMENT; }
+        if (!rec->active_column && !rec->active_overlap && !rec->active_boosted) { h->err = "htm_sp_run: no record buffer given"; return HTM_ERR_ARGUMENT; }
+    }
+    // a handle that also owns a Temporal Memory steps both layers together (see htm_sp_step)
+    if (h->cfg.enable_tm) { h->err = "htm_sp_run: the handle also has a Temporal Memory; use htm_run"; return HTM_ERR_STATE; }
+    if (!h->cfg.enable_sp) { h->err = "htm_sp_run: the handle has no Spatial Pooler"; return HTM_ERR_STATE; }
+    if (h->world > 1) { h->err = "htm_sp_run: not available on a column-sharded handle"; return HTM_ERR_STATE; }
+    REFUSE_ON_VIEW(h, "htm_sp_run");
+    REJECT_WHEN_AHEAD(h);
+    if (n_steps == 0) return HTM_OK;
+    flush_tail(h);
+    HIPCHK(h, hipSetDevice(h->device));
+    learning = learning ? 1 : 0;
+    if (learning) weights_touched(h);
+    refresh_exchange_mode(h);
+    // (an open htm_sp_phase step is closed as htm_sp_step closes it: the run's first step starts it over)
+    if (int rc = close_open_phases(h)) return rc;
+    const bool graph = run_schedule(h, n_steps, use_graph).graph, recording = rec != nullptr;
+    if (recording) {
+        if (!h->d_sp_rec) { if (int rc = dalloc(h, &h->d_sp_rec, 1)) return rc; }
+        // the descriptor of this call (not one of the step's launches: htm_profile does not count it)
+        hipLaunchKernelGGL(k_sp_run_begin, dim3(1), dim3(64), 0, h->stream, h->d_sp_rec, rec->active_column, rec->active_overlap, rec->active_boosted,
+                           (uint32_t)h->step_host, n_steps);
+    }
+    const int kGraphSteps = h->knob.graph_steps;
+    for (int t = 0; t < n_steps;) {
+        const int p = (int)(h->step_host & 1), wmode = step_wmode(h);
+        if (!graph) {
+            enqueue_sp_run_step(h, device_inputs, n_inputs, p, learning, recording, wmode);
+            h->step_host += 1;
+            t += 1;
+            continue;
+        }
+        // (nothing in a graph depends on the step index: the kernels read it, and with it the bank row, from the counter block.
+        // The first select of a handle leaves the window behind that the later ones use: that step is a graph of its own.  Spans
+        // start at even steps only: one span graph then serves every call, whatever the parity it starts at)
+        const bool settled = h->window_known || !(h->emit_fused && h->knob.step_window);
+        const int span = settled && p == 0 && n_steps - t >= kGraphSteps ? kGraphSteps : 1;
+        const SpRunGraphKey key{p, learning, recording, h->emit_fused, wmode, span, device_inputs, n_inputs};
+        const hipGraphExec_t exec = cached_graph(h->sp_graphs, key, h->stream, h->err, [&] {
+            for (int i = 0; i < span; ++i) enqueue_sp_run_step(h, device_inputs, n_inputs, (p + i) & 1, learning, recording, wmode);
+            return 0;
+        });
+        if (!exec) return HTM_ERR_HIP;
+        HIPCHK(h, hipGraphLaunch(exec, h->stream));
+        h->window_known = true;                     // (as enqueue_sp_back says of the launches the graph replays)
+        h->step_host += span;
+        t += span;
+    }
+    return launch_status(h->err);
+}
+
 extern "C" int htm_graph_count(htm_handle *h) {
     if (!h) return HTM_ERR_ARGUMENT;
-    return (int)std::min<size_t>(h->graphs.size() + h->shard_graphs.size() + h->tm_graphs.size(), 0x7fffffff);
+    return (int)std::min<size_t>(h->graphs.size() + h->shard_graphs.size() + h->tm_graphs.size() + h->sp_graphs.size(), 0x7fffffff);
 }
 
 extern "C" int htm_run_plan(htm_handle *h, int32_t n_steps, int32_t use_graph) {

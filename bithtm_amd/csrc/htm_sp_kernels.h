@@ -1339,10 +1339,11 @@ __global__ __launch_bounds__(256) void k_sp_emit(Dev d, int p, int want_winner, 
 }
 
 // DenseProjection.update (projections.py:23-24) on the k winner rows, fused with the rebuild
-// of those rows' connected mask.  One block per winner row.
-__global__ __launch_bounds__(256) void k_sp_learn(Dev d, const uint32_t *__restrict__ bank, int n_inputs, int p) {
+// of those rows' connected mask.  One block of 256 threads per winner row: block `b` takes the b-th winner of the step of
+// parity p.  (A role: k_sp_learn and the tail launch of a batched stand-alone run, htm_sp_run.h, both call it.)
+__device__ __forceinline__ void role_sp_learn_row(const Dev &d, const uint32_t *__restrict__ bank, int n_inputs, int p, int b) {
     const uint32_t *in = bank + (size_t)(d.ctr->step[p] % (uint32_t)n_inputs) * d.W;
-    const int row = d.active_cols[p][blockIdx.x];
+    const int row = d.active_cols[p][b];
     double *prow = d.perm + (size_t)row * d.Ipad;
     uint32_t *mrow = d.mask + (size_t)row * d.W;
     for (int i0 = 0; i0 < d.Ipad; i0 += 256) {
@@ -1357,6 +1358,10 @@ __global__ __launch_bounds__(256) void k_sp_learn(Dev d, const uint32_t *__restr
         u64 m = __ballot(conn);
         if (lane_id() == 0 && i < d.Ipad) *(u64 *)&mrow[i >> 5] = m;
     }
+}
+
+__global__ __launch_bounds__(256) void k_sp_learn(Dev d, const uint32_t *__restrict__ bank, int n_inputs, int p) {
+    role_sp_learn_row(d, bank, n_inputs, p, (int)blockIdx.x);
 }
 
 // ---- SpatialPooler.process phase by phase (htm_sp_phase): kernels for values that come from the host ----------

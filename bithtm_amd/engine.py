@@ -36,6 +36,10 @@ def pack_bits(bits, words):
 # run(record=...): the per-step fields htm_run_recorded can write, and the counts of one htm_step_record in its order
 RECORD_FIELDS = ("counters", "active_column", "column_prediction", "predicted_input")
 RECORD_COUNTERS = tuple(name for name, _ in L.HtmStepRecord._fields_)
+# SpatialPooler.run(record=...): the per-step fields htm_sp_run can write, in the order of htm_sp_run_record, with the dtype of
+# each and its 32-bit words per value
+SP_RECORD_FIELDS = ("active_column", "active_overlap", "active_boosted")
+SP_RECORD_TYPES = {"active_column": (np.int32, 1), "active_overlap": (np.int32, 1), "active_boosted": (np.float64, 2)}
 
 
 def words_per_column(cell_dim):
@@ -480,6 +484,29 @@ class Engine:
         if check:
             self.check_capacity()
         return None if record is None else self._records_read(fields, n_steps, sync=True)
+
+    def sp_run(self, device_bank, n_inputs, n_steps, learning=True, use_graph=True, record=None):
+        """n_steps stand-alone Spatial Pooler steps over a device bank (upload_bank: n_inputs rows), the loop on the device
+        (htm_sp_run).  `record`: None, or fields of SP_RECORD_FIELDS: the call then returns {field: numpy array
+        [n_steps, active_columns]} -- int32 columns (ascending), int32 overlaps, float64 boosted overlaps of each step's winners
+        -- read back after one synchronisation."""
+        fields = () if record is None else self._record_fields(record, SP_RECORD_FIELDS)
+        n_steps, k = int(n_steps), self.active_columns
+        rec = L.HtmSpRunRecord()
+        rec.struct_bytes = C.sizeof(L.HtmSpRunRecord)
+        for f in fields:
+            setattr(rec, f, self._record_buffer("sp_" + f, max(n_steps, 1) * k * SP_RECORD_TYPES[f][1]))
+        self._check(self.lib.htm_sp_run(self.h, C.c_void_p(device_bank), int(n_inputs), n_steps, int(bool(learning)),
+                                        run_flags(use_graph), C.byref(rec) if fields else None), "htm_sp_run")
+        self.steps += max(n_steps, 0)
+        if record is None:
+            return None
+        self.sync()
+        out = {}
+        for f in fields:
+            dtype, words = SP_RECORD_TYPES[f]
+            out[f] = self._record_read("sp_" + f, n_steps * k * words, np.uint32).view(dtype).reshape(n_steps, k)
+        return out
 
     def upload_bank(self, inputs):
         """bool[n, I] -> device address of the packed bank htm_run reads."""

@@ -29,7 +29,7 @@ import numpy as np
 
 from . import _lib as L
 from ._keyed import STREAM_INPUT_NOISE, draw_unit
-from .engine import RECORD_COUNTERS, RECORD_FIELDS, Engine, check_lists, words_to_bool
+from .engine import RECORD_COUNTERS, RECORD_FIELDS, SP_RECORD_FIELDS, SP_RECORD_TYPES, Engine, check_lists, words_to_bool
 from .projections import DenseProjection, PredictiveProjection
 from .regularizations import ExponentialBoosting, GlobalInhibition, _Placeholder, checked_boosted, checked_overlaps
 
@@ -199,6 +199,90 @@ class SpatialPooler:
         return self.State(eng, eng.steps)
 
     compute = process
+
+    # run(noise=): steps per fill of the noise ring (as HierarchicalTemporalMemory.noise_chunk)
+    noise_chunk = 1024
+
+    def run(self, inputs, steps, learning=True, use_graph=True, record=None, noise=0.0, noise_seed=None):
+        """`steps` timesteps over the rows of the boolean matrix `inputs`, cycled: `steps` times
+        process(inputs[t % n] ^ flip_noise(noise_seed, t, input_dim, noise), learning), t being this object's step index, with the
+        bank resident in device memory and no per-step host work (htm_sp_run).  Everything the call leaves -- permanences, duty
+        cycle, the State of the next process() -- is what that loop leaves, bit for bit, and successive calls compose: a and then b
+        steps are one call of a + b.  The bank is uploaded once and kept until the inputs change.
+        `record`: None (the call returns None), True (= ("active_column",)) or a tuple of "active_column", "active_overlap",
+        "active_boosted": the call then returns an SPRunRecord over its `steps` steps, written on the device and read back once
+        per call; `record.active_column` is what TemporalMemory.run takes as its lists.
+        `noise`, `noise_seed`: as HierarchicalTemporalMemory.run's (drawn on the device into a ring the run reads instead of the
+        bank, noise_chunk steps per fill; `noise_seed` defaults to 0); 0 is the run without noise, launch for launch.
+        ValueError, before anything is created or enqueued: steps < 0, inputs that are not [n >= 1, input_dim], an unknown record
+        name, noise outside [0, 1], a run that would pass step 2^32, a Spatial Pooler inside a fused HierarchicalTemporalMemory
+        (call its run()), plug-in proximal_projection / boosting / inhibition objects (they step on the host: call process())."""
+        if self._fused:
+            raise ValueError("this SpatialPooler is fused into a HierarchicalTemporalMemory; call its run()")
+        if not self._plain:
+            raise ValueError("run() keeps the whole loop on the device: not available with plug-in proximal_projection / boosting / "
+                             "inhibition objects; call process()")
+        steps = int(steps)
+        if steps < 0:
+            raise ValueError(f"steps must not be negative, got {steps}")
+        inputs = np.asarray(inputs)
+        if inputs.ndim != 2 or inputs.shape[0] < 1 or inputs.shape[1] != self.input_dim:
+            raise ValueError(f"inputs: a boolean matrix [n >= 1, input_dim = {self.input_dim}], got shape {inputs.shape}")
+        inputs = inputs.astype(np.bool_, copy=False)
+        fields = None if record is None else _sp_record_fields(record)
+        threshold = _noise_threshold_arg(noise)
+        first = 0 if self._engine is None else self._engine.steps
+        if first + steps > 1 << 32:
+            raise ValueError("run(): the run would pass step 2^32, where the device's step counter wraps")
+        eng = self._ensure_engine()
+        retire_states(eng)
+        n = inputs.shape[0]
+        bank = _cached_bank(self, eng, inputs)
+        noise_seed = (eng.seed if noise_seed is None else int(noise_seed)) if threshold else None
+        parts = []
+        for _, batch in _batches(steps, cap=int(self.noise_chunk) if threshold else None):
+            if threshold:
+                ring, _, rows = _noise_ring(self, eng, self.noise_chunk)
+                eng.bank_noise(bank, n, ring, rows, eng.steps, batch, noise_seed, threshold)
+                part = eng.sp_run(ring, rows, batch, learning=learning, use_graph=use_graph, record=fields)
+            else:
+                part = eng.sp_run(bank, n, batch, learning=learning, use_graph=use_graph, record=fields)
+            parts.append(part)
+        if fields is None:
+            return None
+        k = self.active_columns
+        whole = {f: parts[0][f] if len(parts) == 1 else np.concatenate([p[f] for p in parts]) if parts else np.zeros((0, k), SP_RECORD_TYPES[f][0])
+                 for f in fields}
+        return SPRunRecord(first + np.arange(steps, dtype=np.int64), **whole)
+
+
+class SPRunRecord:
+    """What SpatialPooler.run(record=...) returns: one numpy array per field over the steps of the call, step i of the call in row
+    i, the k = active_columns winners of a step in ascending column order (include/bithtm_hip.h, htm_sp_run).
+      step_index       int64[steps]        timesteps processed before each step (the engine's step index)
+      active_column    int32[steps, k]     sp_state.active_column of each step ("active_column", else None)
+      active_overlap   int32[steps, k]     sp_state.overlaps[active_column] ("active_overlap", else None)
+      active_boosted   float64[steps, k]   sp_state.boosted_overlaps[active_column] ("active_boosted", else None)
+      fields           the names recorded, in this order"""
+
+    def __init__(self, step_index, active_column=None, active_overlap=None, active_boosted=None):
+        self.step_index = np.asarray(step_index, dtype=np.int64)
+        self.active_column, self.active_overlap, self.active_boosted = active_column, active_overlap, active_boosted
+        self.fields = tuple(f for f in SP_RECORD_FIELDS if getattr(self, f) is not None)
+
+    def __len__(self):
+        return len(self.step_index)
+
+
+def _sp_record_fields(record):
+    """SpatialPooler.run(record=...) -> the fields asked for, each once, in SP_RECORD_FIELDS order: True = the winner lists; else
+    a name or a tuple of names."""
+    if record is True:
+        return ("active_column",)
+    fields = (record,) if isinstance(record, str) else tuple(record)
+    if not fields or set(fields) - set(SP_RECORD_FIELDS):
+        raise ValueError(f"record: True or a tuple of {SP_RECORD_FIELDS} (got {record!r})")
+    return tuple(f for f in SP_RECORD_FIELDS if f in fields)
 
 
 class TemporalMemory:

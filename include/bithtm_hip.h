@@ -369,7 +369,7 @@ int htm_set_run_resets(htm_handle *h, const uint32_t *device_bits, int32_t n_inp
 int htm_predicted_input(htm_handle *h, int32_t *host_dst);
 int htm_set_run_predicted_input(htm_handle *h, int32_t *device_votes);
 
-/* hipGraphs the handle holds (captured and instantiated by htm_run / htm_prepare / htm_shard_run / htm_tm_run and their recorded forms);
+/* hipGraphs the handle holds (captured and instantiated by htm_run / htm_prepare / htm_shard_run / htm_tm_run / htm_sp_run and their recorded forms);
  * diagnostic: a recorded call with other buffers replays the graphs of the one before and adds none. */
 int htm_graph_count(htm_handle *h);
 
@@ -674,6 +674,41 @@ int htm_tm_run(htm_handle *h, const int32_t *device_lists, int32_t n_rows, int32
 int htm_bank_noise(htm_handle *h, const uint32_t *src_bank, int32_t n_src, uint32_t *dst_bank, int32_t n_dst,
                    uint32_t first_step, int32_t n_rows, uint32_t seed, uint32_t threshold24,
                    const uint32_t *src_resets, uint32_t *dst_resets);
+
+/* Batched stand-alone Spatial Pooler runs: n_steps of
+ *   SpatialPooler.process(input, learning)                                         (networks.py:26-35)
+ * -- of htm_sp_step -- whose inputs are the rows of a bank that is ALREADY IN DEVICE MEMORY (htm_bank_upload's layout,
+ * words_per_row of htm_info per row): step t reads row t % n_inputs, t = the handle's step index, so the rows cycle with the index
+ * across calls as htm_run's bank does.  Nothing is copied or synchronised, and what a call leaves -- permanence rows, connected
+ * mask, duty cycle (which moves with learning = 0 too: networks.py:33), step index, and the HTM_F_OVERLAPS / _BOOSTED /
+ * _ACTIVE_COLUMN fields of the last step -- is exactly what the n_steps htm_sp_step calls leave.
+ *
+ * Per step: the launches of htm_sp_step up to the winner list, then one launch with the k winner rows' permanence update
+ * (projections.py:23-24) and, in further blocks of the same launch, the step's record: a recorded learning step costs no launch
+ * more than an unrecorded one, and a step that neither learns nor records has no such launch (htm_sp_run.h).  use_graph bit 0:
+ * replay hipGraphs of one step or of 16 (one stream; captured once per bank address, n_inputs, learning flag and whether
+ * recorded -- not per record buffer: the launches read the buffers from a device-side descriptor the call fills first; calls of
+ * fewer than BITHTM_EAGER_BELOW steps and calls under htm_profile launch eagerly); the other bits are ignored: a Spatial Pooler
+ * alone has nothing to work ahead of -- step t + 1's overlap reads the mask rows step t's learning wrote.
+ *
+ * rec: NULL (nothing is recorded), or the device buffers of a per-step record, any of them NULL; record i = the i-th step of
+ * this call, k = active_columns values per step in the order of the step's winner list (ascending column).  Buffer sizes are the
+ * caller's contract, as in htm_run_recorded.
+ *
+ * HTM_ERR_ARGUMENT, nothing enqueued, the handle as it was: a NULL handle or bank, n_inputs < 1, n_steps < 0, a wrong
+ * rec->struct_bytes, a rec with no buffer.  HTM_ERR_STATE, likewise: a handle that also has a Temporal Memory (use htm_run), a
+ * handle without a Spatial Pooler, a column-sharded handle, an inference view, a handle that is ahead (HTM_RUN_CONTINUE).
+ * n_steps == 0 returns HTM_OK and does nothing.  A call with steps closes an open htm_sp_phase step the way htm_sp_step does: the
+ * phases run so far are dropped and the run's first step starts that timestep over. */
+typedef struct htm_sp_run_record {
+    uint32_t struct_bytes;      /* sizeof(htm_sp_run_record), checked */
+    int32_t *active_column;     /* device, [n_steps * active_columns]: sp_state.active_column of each step, ascending; or NULL */
+    int32_t *active_overlap;    /* device, [n_steps * active_columns]: overlaps[active_column], same order; or NULL */
+    double  *active_boosted;    /* device, [n_steps * active_columns]: boosted_overlaps[active_column], same order; or NULL */
+} htm_sp_run_record;
+
+int htm_sp_run(htm_handle *h, const uint32_t *device_inputs, int32_t n_inputs, int32_t n_steps, int32_t learning, int32_t use_graph,
+               const htm_sp_run_record *rec);
 
 #ifdef __cplusplus
 }
