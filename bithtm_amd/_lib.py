@@ -121,6 +121,8 @@ EXPORTS = {
     "htm_group_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(HtmRunRecord)]),
     "htm_create_view": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p)]),
     "htm_device_bytes": (C.c_int64, [C.c_void_p]),
+    "htm_view_sync": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "htm_bank_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_void_p]),
     "htm_pack_columns": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int32]),
     "htm_encode_votes": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int32]),
     "htm_set_run_feedback": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32]),

@@ -47,6 +47,7 @@
 #include "htm_group.h"
 #include "htm_tm_feed.h"
 #include "htm_sp_run.h"
+#include "htm_fork.h"
 
 // ------------------------------------------------------------------------------------------
 // host side
@@ -1238,6 +1239,128 @@ extern "C" int htm_create_view(htm_handle *parent, htm_handle **out) {
 extern "C" int64_t htm_device_bytes(htm_handle *h) {
     if (!h) return HTM_ERR_ARGUMENT;
     return h->own_bytes;
+}
+
+// ------------------------------------------------------------------------------------------
+// Stream forks (htm_fork.h)
+
+// The buffers of alloc_stream_state that are stream state, as k_stream_fork's table (a handle with SP and TM, unsharded: what
+// views are made of).  Not in it: input_stage and d_cols_stage (a host-fed step writes them before it reads them), work,
+// recyc_cnt, recyc_cnt2, recyc_need and dead_list (the learning role's: a view never learns, and its counts start clean), trace.
+static ForkTable fork_table(const Dev &v, const Dev &s) {
+    ForkTable t;
+    memset(&t, 0, sizeof(t));
+    int blocks = 0;
+    auto add = [&](void *dst, const void *src, size_t bytes, int kind) {
+        ForkEntry &e = t.e[t.n++];
+        e.dst = (unsigned char *)dst;
+        e.src = (const unsigned char *)src;
+        e.bytes = bytes;
+        e.kind = kind;
+        e.first_block = blocks;
+        e.blocks = fork_blocks(bytes);
+        blocks += e.blocks;
+    };
+    const size_t C = v.C, k = v.k, KP = v.KP, WPC = v.WPC, S = v.Lcap;
+    const size_t colwords_padded = (size_t)((C + 255) / 256) * 8;
+    // the largest first: their blocks start first
+    for (int q = 0; q < 2; ++q) add(v.cellmax[q], s.cellmax[q], C * KP * 4, FORK_FIXED);
+    add(v.seg_info, s.seg_info, S * 4, FORK_ROWS);
+    add(v.seg_jit, s.seg_jit, S * 4, FORK_ROWS);
+    for (int q = 0; q < 2; ++q) add(v.match_bits[q], s.match_bits[q], (S + 255) / 256 * 8 * 4, FORK_BITS);
+    for (int q = 0; q < 2; ++q) {
+        add(v.boosted[q], s.boosted[q], C * 8, FORK_FIXED);
+        add(v.key[q], s.key[q], C * 8, FORK_FIXED);
+        add(v.overlap[q], s.overlap[q], C * 4, FORK_FIXED);
+        add(v.act[q], s.act[q], C * WPC * 4, FORK_FIXED);
+        add(v.pred[q], s.pred[q], C * WPC * 4, FORK_FIXED);
+        add(v.win[q], s.win[q], C * WPC * 4, FORK_FIXED);
+        add(v.winners[q], s.winners[q], k * KP * 4, FORK_FIXED);
+        add(v.active_cols[q], s.active_cols[q], (k + 8) * 4, FORK_FIXED);
+        add(v.colbits[q], s.colbits[q], colwords_padded * 4, FORK_FIXED);
+        add(v.col_rank[q], s.col_rank[q], colwords_padded * 2, FORK_FIXED);
+    }
+    add(v.duty, s.duty, C * 4, FORK_FIXED);
+    add(v.hist, s.hist, (size_t)2 * SEL_MAX_PASSES * SEL_BINS * 4, FORK_FIXED);
+    add(v.hist0, s.hist0, (size_t)2 * HIST0_PAR * 4, FORK_FIXED);
+    add(v.sel_blk, s.sel_blk, (C + 255) / 256 * 4, FORK_FIXED);
+    add(v.sel_rec, s.sel_rec, (C + 255) / 256 * 32 * 4, FORK_FIXED);
+    add(v.fan, s.fan, (size_t)2 * FAN_COUNTERS * FAN_STRIDE * 4, FORK_FIXED);
+    add(v.bursting, s.bursting, k, FORK_FIXED);
+    add(v.actw_id, s.actw_id, (k * WPC + 8) * 4, FORK_FIXED);
+    add(v.winw_idx, s.winw_idx, (k * WPC + 8) * 4, FORK_FIXED);
+    add(v.actcnt, s.actcnt, k * WPC + 8, FORK_FIXED);
+    add(v.act_list, s.act_list, (k * WPC + 16) * 4, FORK_FIXED);
+    add(v.unacc_word, s.unacc_word, (k * WPC + 8) * 4, FORK_FIXED);
+    add(v.unacc_list, s.unacc_list, k * KP * 4, FORK_FIXED);
+    static_assert(2 + 2 + 2 + 2 * 10 + 13 <= FORK_MAX_ENTRIES, "k_stream_fork's table holds every entry");
+    return t;
+}
+
+// After the source's (and the parent's) held-back launch: one launch on the shared stream, no copy, no wait.  The view then IS the
+// source as far as a step with learning = 0 can tell, the host's part of the stream included -- and its per-cell maxima are the
+// source's, as current with the weights as the source's own: the view takes the source's generation of the weights and its
+// cm_dense_step, so that the next view_enter has nothing to say and does not wait (a look-ahead syncs before every window).
+extern "C" int htm_view_sync(htm_handle *view, htm_handle *source) {
+    if (!view || !source) return HTM_ERR_ARGUMENT;
+    if (view == source) { view->err = "htm_view_sync: the view and the source are one handle"; return HTM_ERR_STATE; }
+    if (!view->is_view) { view->err = "htm_view_sync: the first handle is not an inference view (htm_create_view)"; return HTM_ERR_STATE; }
+    if (!source->shared || source->shared != view->shared) {
+        view->err = "htm_view_sync: the source is neither the view's parent nor another view of it (the handles do not share weights)";
+        return HTM_ERR_STATE;
+    }
+    if (view->phase_open || view->shard_open || source->phase_open || source->shard_open) {
+        view->err = "htm_view_sync: a step of the view or of the source is open (htm_sp_phase)";
+        return HTM_ERR_STATE;
+    }
+    htm_handle *par;
+    long long wgen;
+    {
+        std::lock_guard<std::mutex> lock(g_shared_mutex);
+        par = view->shared->parent;
+        wgen = view->shared->wgen;
+    }
+    if (sp_is_ahead(view) || sp_is_ahead(source) || (par && sp_is_ahead(par))) {
+        view->err = "htm_view_sync: the view, the source or the parent is ahead (its htm_run ended with HTM_RUN_CONTINUE): finish that run first";
+        return HTM_ERR_STATE;
+    }
+    HIPCHK(view, hipSetDevice(view->device));
+    flush_tail(source);
+    if (par && par != source) flush_tail(par);
+    // (the parent is gone: nobody hands this view a segment count again, and an earlier run of the view may still be copying
+    // its own into the pinned word)
+    if (!par) HIPCHK(view, hipStreamSynchronize(view->stream));
+    const ForkTable t = fork_table(view->d, source->d);
+    const ForkEntry &last = t.e[t.n - 1];
+    LAUNCH(view, "stream_fork", k_stream_fork, last.first_block + last.blocks, FORK_THREADS, t, view->d.ctr, (const Counters *)source->d.ctr);
+    const int rc = launch_status(view->err);
+    if (rc) return rc;
+    // (the pinned word below is written from the host while a copy an earlier run of the view queued into it may still be in
+    // flight.  With a live parent that needs no wait: whichever lands last, the word holds a segment count the shared store has
+    // reached, refresh_seg_hint only ever takes the larger of it and the hint, and the view's next call takes the parent's
+    // count in view_enter before anything reads the bound.  Only a view whose parent is gone keeps what it is given here: that
+    // case waited above.)
+    refresh_seg_hint(source);
+    view->step_host = source->step_host;
+    view->seg_hint = source->seg_hint;
+    if (view->seg_pinned) *view->seg_pinned = source->seg_hint;
+    view->window_known = source->window_known;
+    view->seen_wgen = source->is_view ? source->seen_wgen : wgen;
+    view->dense_step = source->dense_step;
+    return HTM_OK;
+}
+
+// Rows of a device bank, contiguous: dst row r = bank row (first_step + r) % bank_rows -- the rows a run of n steps from step
+// index first_step read, or (with feedback) wrote.  One launch on the handle's stream, no wait.
+extern "C" int htm_bank_rows(htm_handle *h, const uint32_t *device_bank, int32_t bank_rows, int64_t first_step, int32_t n, uint32_t *device_dst) {
+    if (!h || !device_bank || !device_dst) return HTM_ERR_ARGUMENT;
+    if (bank_rows < 1 || first_step < 0 || n < 0 || n > bank_rows) { h->err = "htm_bank_rows: bank_rows >= 1, first_step >= 0 and 0 <= n <= bank_rows"; return HTM_ERR_ARGUMENT; }
+    if ((((uintptr_t)device_bank | (uintptr_t)device_dst) & 15) != 0) { h->err = "htm_bank_rows: the bank and the destination must be 16-byte aligned"; return HTM_ERR_ARGUMENT; }
+    if (!h->cfg.enable_sp) { h->err = "htm_bank_rows: needs a handle with the device's own Spatial Pooler (its input rows are packed)"; return HTM_ERR_STATE; }
+    if (n == 0) return HTM_OK;
+    HIPCHK(h, hipSetDevice(h->device));
+    LAUNCH(h, "bank_rows", k_bank_rows, n, 256, device_bank, (int)bank_rows, (int)(first_step % bank_rows), h->d.W4, device_dst);
+    return launch_status(h->err);
 }
 
 // TemporalMemory.process(..., epsilon=) (networks.py:91): the tolerance of the "best matching" / "least used" ties

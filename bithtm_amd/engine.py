@@ -203,6 +203,17 @@ class Engine:
         v.is_view = True
         return v
 
+    def view_sync(self, source):
+        """This view's stream state becomes that of the engine `source` -- its parent's, or another view's of the same parent --
+        on the device (htm_view_sync: one launch on the shared stream, no wait); the step index comes with it."""
+        self._check(self.lib.htm_view_sync(self.h, source.h), "htm_view_sync")
+        self.steps = source.steps
+
+    def bank_rows(self, device_bank, bank_rows, first_step, n, device_dst):
+        """device_dst row r = row (first_step + r) % bank_rows of a device bank, r < n (htm_bank_rows): enqueued, no wait."""
+        self._check(self.lib.htm_bank_rows(self.h, C.c_void_p(device_bank), int(bank_rows), int(first_step), int(n), C.c_void_p(device_dst)),
+                    "htm_bank_rows")
+
     def device_bytes(self):
         """Device bytes this handle allocated itself (a view does not count the weights it shares: htm_device_bytes)."""
         return int(self._check(self.lib.htm_device_bytes(self.h), "htm_device_bytes"))

@@ -96,13 +96,15 @@ class ModelGroup:
         return any(isinstance(m, InferenceView) for m in models)
 
     @classmethod
-    def views(cls, parent, n):
+    def views(cls, parent, n, fork=False):
         """A group of n inference views of `parent` (parent.inference_view() n times): n input streams over one copy of its
         weights, stepped with learning=False.  The views' scan reads the shared segment store once per step for up to M of
-        them at a time (M: as many members' column bitmaps as fit 64 KiB of LDS, at most 16)."""
+        them at a time (M: as many members' column bitmaps as fit 64 KiB of LDS, at most 16).  `fork=True`: every member is
+        parent.fork() -- it continues the parent's stream from where that is now (one launch per member) instead of starting
+        as after reset()."""
         if n < 1:
             raise ValueError("ModelGroup.views: n must be at least 1")
-        return cls([parent.inference_view() for _ in range(int(n))])
+        return cls([parent.fork() if fork else parent.inference_view() for _ in range(int(n))])
 
     def _learning(self, learning):
         """learning=None: False for a group with inference views, True for any other (as before); True with views: ValueError."""

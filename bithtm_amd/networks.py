@@ -29,7 +29,7 @@ import numpy as np
 
 from . import _lib as L
 from ._keyed import STREAM_INPUT_NOISE, draw_unit
-from .engine import RECORD_COUNTERS, RECORD_FIELDS, SP_RECORD_FIELDS, SP_RECORD_TYPES, Engine, check_lists, words_to_bool
+from .engine import RECORD_COUNTERS, RECORD_FIELDS, SP_RECORD_FIELDS, SP_RECORD_TYPES, Engine, HtmError, check_lists, words_to_bool
 from .projections import DenseProjection, PredictiveProjection
 from .regularizations import ExponentialBoosting, GlobalInhibition, _Placeholder, checked_boosted, checked_overlaps
 
@@ -778,6 +778,35 @@ class HierarchicalTemporalMemory:
         with np.load(path) as z:
             self.load_state_dict({k: z[k] for k in z.files})
 
+    def _run_args(self, eng, what, inputs, steps, record, resets, noise, noise_seed):
+        """The arguments of a batched call over `inputs` (run(), lookahead()), checked -> (noise threshold or 0, record fields
+        or None, noise seed, inputs as a bool matrix, resets as a bool vector or None)."""
+        threshold = _noise_threshold_arg(noise)
+        fields = None if record is None else _record_fields(record)
+        if threshold:
+            if eng.shard_world > 1:
+                raise ValueError(f"{what}(noise=): not available on a column-sharded model")
+            if eng.steps + max(steps, 0) + 1 > 1 << 32:
+                raise ValueError(f"{what}(noise=): the run would pass step 2^32, where the device's step counter wraps")
+            noise_seed = eng.seed if noise_seed is None else int(noise_seed)
+        inputs = np.asarray(inputs, dtype=np.bool_)
+        if resets is not None:
+            resets = np.asarray(resets, dtype=np.bool_).ravel()
+            if resets.shape != (inputs.shape[0],):
+                raise ValueError(f"resets: one flag per row of inputs ({inputs.shape[0]}), got {resets.shape[0]}")
+        return threshold, fields, noise_seed, inputs, resets
+
+    def _batch_source(self, eng, bank, inputs, resets, fill, threshold, noise_seed):
+        """What one batch of a batched call reads -> (device bank, its rows, its reset bits or None): the bank of `inputs`, or
+        with noise the ring, filled here (enqueued) with the rows of the `fill` steps from the engine's current one -- the
+        batch's and the one behind it -- and with the ring's reset bits where the caller gave flags."""
+        if not threshold:
+            return bank, inputs.shape[0], None if resets is None else eng.upload_resets(resets)
+        ring, ring_resets, rows = _noise_ring(self, eng, self.noise_chunk)
+        flags = eng.upload_resets(resets if resets is not None else np.zeros(inputs.shape[0], dtype=np.bool_))
+        eng.bank_noise(bank, inputs.shape[0], ring, rows, eng.steps, fill, noise_seed, threshold, flags, ring_resets)
+        return ring, rows, None if resets is None else ring_resets
+
     def run(self, inputs, steps, learning=True, use_graph=True, pipeline=True, continuing=False, record=None, resets=None,
             noise=0.0, noise_seed=None):
         """`steps` timesteps over the rows of the boolean matrix `inputs`, cycled, with the input
@@ -799,22 +828,10 @@ class HierarchicalTemporalMemory:
         eng = self._fused_engine("run()")
         if not self.spatial_pooler._plain:
             raise RuntimeError("run() keeps the whole loop on the device: not available with plug-in objects that live on the host")
-        threshold = _noise_threshold_arg(noise)
-        fields = None if record is None else _record_fields(record)
         steps = int(steps)
-        if threshold:
-            if eng.shard_world > 1:
-                raise ValueError("run(noise=): not available on a column-sharded model")
-            if eng.steps + max(steps, 0) + 1 > 1 << 32:
-                raise ValueError("run(noise=): the run would pass step 2^32, where the device's step counter wraps")
-            noise_seed = eng.seed if noise_seed is None else int(noise_seed)
+        threshold, fields, noise_seed, inputs, resets = self._run_args(eng, "run", inputs, steps, record, resets, noise, noise_seed)
         retire_states(eng)
-        inputs = np.asarray(inputs, dtype=np.bool_)
         bank = _cached_bank(self, eng, inputs)
-        if resets is not None:
-            resets = np.asarray(resets, dtype=np.bool_).ravel()
-            if resets.shape != (inputs.shape[0],):
-                raise ValueError(f"resets: one flag per row of inputs ({inputs.shape[0]}), got {resets.shape[0]}")
         # A pool left at its default size grows like the reference's arrays (utils.py:113-135): the run is cut into batches
         # the free segments are expected to last (2 x active_columns new segments per step: every column bursting, twice),
         # with a look at the pool between them.  An overflow inside a batch is still reported, never silent.
@@ -832,22 +849,12 @@ class HierarchicalTemporalMemory:
         for done, n in _batches(steps, pool, cap=int(self.noise_chunk) if threshold else None):
             eng = self._engine
             last = done + n >= steps
-            if threshold:
-                # rows for the steps of this batch and the one behind it, then the batch over the ring (with the ring's reset
-                # bits where the caller gave flags).  A streamed call ends with the Spatial Pooler ahead: it has read the row of
-                # the step behind the batch and, in the four-launch schedule, of the one behind that -- one row more; the next
-                # call's fill writes those rows again with the words they have
-                ring, ring_resets, rows = _noise_ring(self, eng, self.noise_chunk)
-                flags = eng.upload_resets(resets if resets is not None else np.zeros(inputs.shape[0], dtype=np.bool_))
-                eng.bank_noise(bank, inputs.shape[0], ring, rows, eng.steps, n + (2 if continuing and last else 1), noise_seed,
-                               threshold, flags, ring_resets)
-                part = eng.run(ring, rows, n, learning=learning, use_graph=use_graph, pipeline=pipeline,
-                               continuing=continuing and last, record=fields, resets=None if resets is None else ring_resets)
-            else:
-                part = eng.run(bank, inputs.shape[0], n, learning=learning, use_graph=use_graph, pipeline=pipeline,
-                               continuing=continuing and last, record=fields,
-                               resets=None if resets is None else eng.upload_resets(resets))
-            call.add([part])
+            # (a streamed call ends with the Spatial Pooler ahead: it has read the row of the step behind the batch and, in the
+            # four-launch schedule, of the one behind that -- one row more; the next call's fill writes those rows again with the
+            # words they have)
+            src, rows, bits = self._batch_source(eng, bank, inputs, resets, n + (2 if continuing and last else 1), threshold, noise_seed)
+            call.add([eng.run(src, rows, n, learning=learning, use_graph=use_graph, pipeline=pipeline, continuing=continuing and last,
+                              record=fields, resets=bits)])
             self._streaming = bool(continuing and last and pipeline)
         return call.finish([steps], [k])[0]
 
@@ -862,18 +869,120 @@ class HierarchicalTemporalMemory:
         store -- in device memory and steps a stream of its own with learning=False (htm_create_view).  It starts as this model
         would be after reset(): same duty cycles and step index, no Temporal Memory state.  This model may keep learning; its
         views always step on its current weights.  Many views in a ModelGroup read the store once per step together."""
-        eng = self._engine
-        if eng is None or not self.spatial_pooler._plain:
-            raise ValueError("inference_view() needs both layers on the device (one engine): this model has a layer, a distal "
-                             "projection or plug-in objects that live on the host")
-        if getattr(self.temporal_memory, "cell_dim", 0) > 64:
-            raise ValueError("inference_view(): cell_dim above 64 steps on the host")
-        if eng.shard_world > 1:
-            raise ValueError("inference_view(): views of column-sharded models are not available")
-        if self._streaming:
-            raise ValueError("inference_view(): this model is in the middle of a streamed run() (continuing=True): end the stream first")
+        eng = self._viewable_engine("inference_view()")
         retire_states(eng)
         return InferenceView(self)
+
+    def _viewable_engine(self, what):
+        """The engine of a model that views can be made of; ValueError (`what`: the caller's name) for any other."""
+        eng = self._engine
+        if eng is None or not self.spatial_pooler._plain:
+            raise ValueError(f"{what} needs both layers on the device (one engine): this model has a layer, a distal "
+                             "projection or plug-in objects that live on the host")
+        if getattr(self.temporal_memory, "cell_dim", 0) > 64:
+            raise ValueError(f"{what}: cell_dim above 64 steps on the host")
+        if eng.shard_world > 1:
+            raise ValueError(f"{what}: views of column-sharded models are not available")
+        if self._streaming:
+            raise ValueError(f"{what}: this model is in the middle of a streamed run() (continuing=True): end the stream first")
+        return eng
+
+    def fork(self):
+        """A new InferenceView that CONTINUES this model's stream: inference_view(), then its stream state made this model's
+        current one on the device (InferenceView.sync; htm_view_sync -- one launch, nothing goes through the host).  Stepping the
+        fork equals stepping a full copy of this model (load_state_dict(state_dict()), no reset()) with learning=False, bit for
+        bit; this model is not changed and may keep learning.  fork().forecast(k) is what this model expects over the next k
+        steps from where it is now.  ValueError where inference_view() raises it, and for a model with a step open phase by
+        phase (the library refuses to make the view)."""
+        self._viewable_engine("fork()")
+        try:
+            view = self.inference_view()
+        except HtmError as e:
+            raise ValueError(f"fork(): {e}") from e
+        return view.sync(self)
+
+    # lookahead(): windows per chunk.  Inside a chunk nothing is waited for or read back; at its end the host waits once and
+    # reads the chunk's forecast rows and records.  The chunk bounds the device buffers (chunk x horizon bank rows, chunk x every
+    # record rows: at 256 windows of horizon 50 and input_dim 1024 the rows are 1.6 MB) and 256 windows are at least 512 steps of
+    # device work, against which one wait (a few tens of microseconds) is noise; a larger chunk buys nothing measurable.  An
+    # attribute so that a caller, or a test, can cut a look-ahead into smaller chunks.
+    lookahead_chunk = 256
+
+    def _forkable_engine(self, what):
+        """The engine of a model fork() works on (a view overrides this: its parent is what views are made of)."""
+        return self._viewable_engine(what)
+
+    def _lookahead_fork(self):
+        """The fork lookahead() forecasts on: one per engine, kept, made anew when the engine was re-created."""
+        kept = getattr(self, "_la_fork", None)
+        if kept is None or kept[0]() is not self._engine:
+            fork = self.fork()                      # (ValueError for a model that has no engine to fork)
+            self._la_fork = kept = (weakref.ref(self._engine), fork)
+        return kept[1]
+
+    def lookahead(self, inputs, steps, horizon, min_votes=1, max_bits=0, every=1, learning=True, use_graph=True, record=None,
+                  resets=None, noise=0.0, noise_seed=None):
+        """Rolling look-ahead: the model runs over `inputs` as run() does (learning or not) and after every `every` steps says
+        what it expects over the next `horizon` steps, its own stream unmoved.  Bit for bit, with W = steps // every:
+            for j in range(W):
+                run(inputs, every, learning=, record=, resets=, noise=, noise_seed=)
+                rows[j] = fork().forecast(horizon, min_votes, max_bits)
+        Returns rows, bool[W, horizon, input_dim], or with `record` the pair (rows, RunRecord over the `steps` steps); the model
+        is left exactly where run(inputs, steps, ...) leaves it.  On the device, per window: the model's steps, one launch that
+        makes a kept fork's stream state the model's (htm_view_sync), the fork's feedback run of `horizon` steps, and a copy of
+        its rows into a result buffer -- nothing waited for or read back inside a chunk of `lookahead_chunk` windows; a
+        default-sized pool is looked at between chunks, as in run().  ValueError: steps not a multiple of every, horizon < 1,
+        every < 1, and what fork(), run() and forecast() refuse."""
+        steps, horizon, every = int(steps), int(horizon), int(every)
+        if horizon < 1 or every < 1:
+            raise ValueError(f"lookahead(): horizon and every must be at least 1, got {horizon} and {every}")
+        if steps < 0 or steps % every:
+            raise ValueError(f"lookahead(): steps ({steps}) must be a multiple of every ({every})")
+        min_votes, max_bits = _encode_params(min_votes, max_bits)
+        eng = self._forkable_engine("lookahead()")
+        threshold, fields, noise_seed, inputs, resets = self._run_args(eng, "lookahead", inputs, steps, record, resets, noise, noise_seed)
+        if inputs.ndim != 2 or inputs.shape[0] < 1 or inputs.shape[1] != eng.input_dim:
+            raise ValueError(f"inputs: bool [n_inputs, {eng.input_dim}], got {inputs.shape}")
+        self._lookahead_fork()                      # (behind every check of the arguments: a refused call makes no view)
+        retire_states(eng)
+        bank = _cached_bank(self, eng, inputs)
+        k, bank_rows = self.active_columns, horizon + 1
+        rows = np.zeros((steps // every, horizon, eng.input_dim), dtype=np.bool_)
+        call = _BatchedCall([self.temporal_memory], fields)
+        del eng                                     # (as in run(): the pool step may re-create the engine)
+
+        def regrown():
+            nonlocal bank
+            bank = _cached_bank(self, self._engine, inputs, fresh=True)
+
+        def pool():
+            return [(_looked_at_pool(self, 2 * k, None, regrown), 2 * k, 1)]
+        for done, n in _batches(steps, pool, cap=max(int(self.lookahead_chunk), 1) * every, multiple=every):
+            eng, fork = self._engine, self._lookahead_fork()
+            feng, windows = fork._engine, n // every
+            shapes = eng.record_shapes()
+            record_bufs = {} if fields is None else eng._record_buffers(fields, n)
+            fbank = fork._zero_bank(feng, bank_rows)
+            out = feng.kept_buffer(feng._record_bufs, "lookahead_rows", windows * horizon * feng.words)
+            with feng.this_call(feedback=(fbank, bank_rows, min_votes, max_bits)):
+                for j in range(windows):
+                    for at, m in _batches(every, cap=int(self.noise_chunk) if threshold else None):
+                        src, src_rows, bits = self._batch_source(eng, bank, inputs, resets, m + 1, threshold, noise_seed)
+                        with eng.this_call(bits, src_rows):
+                            eng.run_into(src, src_rows, m, {f: ptr + 4 * (j * every + at) * shapes[f][0] for f, ptr in record_bufs.items()},
+                                         learning=learning, use_graph=use_graph)
+                    feng.view_sync(eng)
+                    first = feng.steps
+                    feng.encode_votes(min_votes, max_bits, fbank, bank_rows, first % bank_rows)
+                    feng.run_into(fbank, bank_rows, horizon, {}, learning=False, use_graph=use_graph)
+                    feng.bank_rows(fbank, bank_rows, first, horizon, out + 4 * j * horizon * feng.words)
+            call.add([None if fields is None else eng._records_read(fields, n, sync=True)])
+            feng.sync()
+            words = feng.read_words(out, windows * horizon * feng.words, np.uint32).reshape(windows, horizon, feng.words)
+            rows[done // every:done // every + windows] = np.unpackbits(words.view(np.uint8), axis=2, bitorder="little")[:, :, :feng.input_dim]
+            self._streaming = False
+        record = call.finish([steps], [k])[0]
+        return rows if fields is None else (rows, record)
 
     def predicted_input(self):
         """Which input the model expects next: int32[input_dim], the votes of the predicted columns for the inputs they are
@@ -1063,6 +1172,68 @@ class InferenceView(HierarchicalTemporalMemory):
     def forecast(self, steps, min_votes=1, max_bits=0, record=None, use_graph=True, learning=False, noise=0.0):
         self._check_parent()
         return super().forecast(steps, min_votes, max_bits, record=record, use_graph=use_graph, learning=learning, noise=noise)
+
+    def sync(self, source=None):
+        """This view's stream becomes that of `source` -- the parent (the default) or another view of the same parent -- as it is
+        now, on the device (htm_view_sync: one launch, no host copy, no wait): from here the view steps as a full copy of the
+        source would with learning=False, and last_state reads as the source's.  The source is not changed.  Returns self.
+        ValueError: a source that is no model on the device, that is this view, that belongs to another parent or that is in the
+        middle of a streamed run(); a parent whose engine was re-created."""
+        self._check_parent()
+        if source is None:
+            source = self._parent()
+            if source is None:
+                raise ValueError("sync(): the parent model is gone; name the view to continue")
+        if not isinstance(source, HierarchicalTemporalMemory) or source._engine is None:
+            raise ValueError("sync(): the source must be a model with both layers on the device")
+        if source is self:
+            raise ValueError("sync(): a view cannot be synced to itself")
+        if isinstance(source, InferenceView):
+            source._check_parent()
+            owner = source._parent_engine()
+        else:
+            owner = source._engine
+        if owner is not self._parent_engine():          # (both gone: the library compares the weights the handles share)
+            raise ValueError("sync(): the source belongs to another parent (a view continues its parent or a view of the same parent)")
+        if source._streaming or self._streaming:
+            raise ValueError("sync(): the source or the view is in the middle of a streamed run() (continuing=True): end the stream first")
+        retire_states(self._engine)
+        try:
+            self._engine.view_sync(source._engine)
+        except HtmError as e:                       # (what only the library can tell: two views whose parent is gone)
+            raise ValueError(f"sync(): {e}") from e
+        mine, theirs = self.temporal_memory, source.temporal_memory
+        mine._last_ref, mine._host_last = None, None
+        mine._last_cols, mine._was_reset = theirs._last_cols, theirs._was_reset
+        return self
+
+    def fork(self):
+        """A sibling view that continues THIS view's stream (a branch of a what-if stream): a new view of the parent, synced to
+        this view.  ValueError when the parent model is gone."""
+        self._check_parent()
+        parent = self._parent()
+        if parent is None:
+            raise ValueError("fork() of a view: the parent model is gone (new views are made of the model that owns the weights)")
+        try:
+            view = parent.inference_view()
+        except HtmError as e:                       # (the parent has a step open phase by phase)
+            raise ValueError(f"fork(): {e}") from e
+        return view.sync(self)
+
+    def _forkable_engine(self, what):
+        self._check_parent()
+        if self._parent() is None:
+            raise ValueError(f"{what} of a view: the parent model is gone (new views are made of the model that owns the weights)")
+        if self._streaming:
+            raise ValueError(f"{what}: this view is in the middle of a streamed run() (continuing=True): end the stream first")
+        return self._engine
+
+    def lookahead(self, inputs, steps, horizon, min_votes=1, max_bits=0, every=1, learning=False, use_graph=True, record=None,
+                  resets=None, noise=0.0, noise_seed=None):
+        self._no_learning(learning, "lookahead()")
+        self._check_parent()
+        return super().lookahead(inputs, steps, horizon, min_votes, max_bits, every=every, learning=False, use_graph=use_graph,
+                                 record=record, resets=resets, noise=noise, noise_seed=noise_seed)
 
     def inference_view(self):
         raise ValueError("inference_view() of a view: make views of the model that owns the weights")

@@ -566,6 +566,32 @@ int htm_group_step(htm_group *g, const uint32_t *packed_inputs, int32_t learning
 int htm_create_view(htm_handle *parent, htm_handle **out);
 int64_t htm_device_bytes(htm_handle *h);
 
+/* Stream forks: a view that continues ANOTHER handle's stream.
+ *
+ * htm_view_sync: the stream state of `view` (an inference view, htm_create_view) becomes that of `source` -- its parent, or another
+ * view of the same parent -- as `source` is after the calls made on it so far.  One launch on the shared stream (after the held-
+ * back launch of the source and of the parent); no copy through the host, no wait: the per-segment arrays are bounded by the
+ * source's segment count as the DEVICE holds it.  What comes over: the duty cycles, the step index and its parity; the previous
+ * step's prediction, activation and winner words, its winner list and active-column list; the column bitmaps, ranks and
+ * bursting flags; overlaps, boosted overlaps and the select's state; the matching segments of the last scan (info words, jitter,
+ * match bits of both parities -- rows of the view at and above the source's count read "not matching" afterwards) and the
+ * per-cell maxima; n_win, has_winner, has_distal, cm_dense_step and the rest of the counter block, except that the learning
+ * role's counts and the sticky capacity flags start clean, as in htm_create_view.  The host's part of the stream comes over too
+ * (step index, the lower bound of the segment count, whether a select window is known).  Stepping the view from here equals
+ * stepping a full copy of the source (export + import, WITHOUT htm_reset) with learning = 0, bit for bit.  The source is not
+ * changed.  The per-cell maxima the view receives are as current with the weights as the source's: the view's next call does
+ * not wait for the stream (as a view's first call after its parent learned otherwise does).
+ * HTM_ERR_ARGUMENT: a NULL handle (nothing is touched).  HTM_ERR_STATE, nothing enqueued: `view` is not a view; the handles do not
+ * share weights; view == source; either handle has a step open (htm_sp_phase); the view, the source or the parent is ahead
+ * (HTM_RUN_CONTINUE).
+ *
+ * htm_bank_rows: device_dst row r = row (first_step + r) % bank_rows of device_bank, r in [0, n): the rows a run of n steps from
+ * step index first_step read -- or, with htm_set_run_feedback, the forecast rows it left -- made contiguous.  One launch on the
+ * handle's stream; no wait.  Rows are words_per_row words.  HTM_ERR_ARGUMENT: NULL, bank_rows < 1, first_step < 0, n outside
+ * [0, bank_rows], a bank or a destination that is not 16-byte aligned.  HTM_ERR_STATE: a handle without the device's Spatial Pooler. */
+int htm_view_sync(htm_handle *view, htm_handle *source);
+int htm_bank_rows(htm_handle *h, const uint32_t *device_bank, int32_t bank_rows, int64_t first_step, int32_t n, uint32_t *device_dst);
+
 /* Region stacks: L regions on top of each other, region l + 1 reading region l's active columns.  In
  * reference terms a stack is L HierarchicalTemporalMemory objects with input_dim[l+1] == column_dim[l]; the upper one's step u is
  *   x = np.zeros(column_dim[l], bool); x[sp_state.active_column] = True  for the sp_state (networks.py:29,34) of each of the
