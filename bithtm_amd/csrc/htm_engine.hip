@@ -2883,6 +2883,16 @@ extern "C" int64_t htm_read(htm_handle *h, int32_t field, void *dst, int64_t cou
             for (int64_t i = 0; i < n; ++i) ((int *)dst)[i] = (int)i;
             return n;
         }
+        case HTM_F_RECYCLABLE_COUNTS: {
+            // the allocation's own books: recyclable segments per 1 024 ids, then per 2^20 ids (read-only; a column-sharded
+            // handle keeps dead bits per id instead)
+            if (h->world > 1) { h->err = "htm_read: the recyclable counts are not available on a column-sharded handle"; return HTM_ERR_STATE; }
+            const int64_t nb = ((int64_t)c.S + 1023) / 1024, nb2 = (nb + 1023) / 1024;
+            if ((n = need(tm, nb + nb2)) < 0) return n;
+            if (nb && (hipMemcpy(dst, d.recyc_cnt, (size_t)nb * 4, hipMemcpyDeviceToHost) != hipSuccess ||
+                       hipMemcpy((int *)dst + nb, d.recyc_cnt2, (size_t)nb2 * 4, hipMemcpyDeviceToHost) != hipSuccess)) { h->err = "htm_read: hipMemcpy failed"; return HTM_ERR_HIP; }
+            return n;
+        }
         default: h->err = "htm_read: unknown field"; return HTM_ERR_ARGUMENT;
     }
 }

@@ -1659,7 +1659,10 @@ __global__ __launch_bounds__(256) void k_tm_flag_connected(Dev d) {
 __global__ __launch_bounds__(256) void k_tm_recount(Dev d) {
     __shared__ int s_recyc;
     const int S = d.ctr->S, b = blockIdx.x;
-    if (b * 1024 >= S) return;
+    if (b * 1024 >= S) {                           // (ids the pool may grow into: a count left by an earlier, larger pool would be added to)
+        if (threadIdx.x == 0) d.recyc_cnt[b] = 0;
+        return;
+    }
     if (threadIdx.x == 0) s_recyc = 0;
     __syncthreads();
     int v = 0;

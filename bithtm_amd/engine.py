@@ -827,6 +827,16 @@ class Engine:
             perm=self.read(L.F_SEG_PERM, np.float32, S * E).reshape(S, E),
             segcount=self.read(L.F_SEGCOUNT, np.int32, self.column_dim * self.cell_dim))
 
+    def read_recyclable_counts(self):
+        """The allocation's counts of recyclable segments (rows with fewer synapses than segment_matching_threshold) after the
+        last completed step: (int32[nb] per 1 024 ids, int32[nb2] per 2^20 ids), nb = ceil(S / 1024), nb2 = ceil(nb / 1024)
+        (HTM_F_RECYCLABLE_COUNTS; read only, not on a column-sharded handle).  They equal a recount from read_store()'s
+        seg_nsyn: a test that reads them after every step sees a stale count before a later allocation acts on it."""
+        nb = (self.info().segments + 1023) // 1024
+        nb2 = (nb + 1023) // 1024
+        out = self.read(L.F_RECYCLABLE_COUNTS, np.int32, nb + nb2)
+        return out[:nb], out[nb:]
+
     def read_distal(self):
         """PredictiveProjection.State (projections.py:195-203) of the last step, segment ids
         ascending as np.where (projections.py:247) yields them."""

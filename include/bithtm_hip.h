@@ -139,9 +139,15 @@ typedef enum htm_field {
     HTM_F_MATCH_INFO = 17,     /* uint32[M]  potential | activation<<12 | active<<31, same order */
     HTM_F_MATCH_JITTER = 18,   /* float[M]   matching_segment_jittered_potential, same order */
     HTM_F_CELL_MAX_JITTER = 19,/* float[N]   State.max_jittered_potential (projections.py:236-238) */
-    HTM_F_SEG_GID = 20         /* int32[S]   global segment id of each row: 0..S-1, except on a column-sharded handle,
+    HTM_F_SEG_GID = 20,        /* int32[S]   global segment id of each row: 0..S-1, except on a column-sharded handle,
                                              where the per-segment fields above have htm_info.local_segments rows
                                              (the segments of the rank's own cells; -1 = free row) */
+    HTM_F_RECYCLABLE_COUNTS = 21 /* int32[nb + nb2]  READ ONLY (htm_write refuses it): the allocation's counts of recyclable
+                                             segments -- rows with fewer synapses than segment_matching_threshold
+                                             (projections.py:80-81) -- per 1 024 ids, nb = ceil(S / 1024) of them, then per
+                                             2^20 ids, nb2 = ceil(nb / 1024) of them.  For tests and diagnosis: after a
+                                             completed step they equal a recount from HTM_F_SEG_NSYN.  HTM_ERR_STATE on a
+                                             column-sharded handle, which keeps a dead bit per id instead */
 } htm_field;
 
 /* Construction: HierarchicalTemporalMemory.__init__ / SpatialPooler.__init__ /
