@@ -53,6 +53,11 @@ class HtmSpRunRecord(C.Structure):
     _fields_ = [("struct_bytes", C.c_uint32), ("active_column", C.c_void_p), ("active_overlap", C.c_void_p), ("active_boosted", C.c_void_p)]
 
 
+class HtmScalarField(C.Structure):
+    _fields_ = [("minimum", C.c_double), ("scale", C.c_double)] + [(name, C.c_int32) for name in (
+        "offset", "bits", "width", "buckets", "periodic", "reserved")]
+
+
 # htm_field
 F_ACTIVE_COLUMN, F_OVERLAPS, F_BOOSTED, F_DUTY_CYCLE, F_CELL_ACTIVATION, F_CELL_PREDICTION = 1, 2, 3, 4, 5, 6
 F_WINNER_WORDS, F_BURSTING, F_WINNER_CELL, F_SEG_CELL, F_SEG_NSYN, F_SEG_PRESYN, F_SEG_PERM = 7, 8, 9, 10, 11, 12, 13
@@ -129,6 +134,9 @@ EXPORTS = {
     "htm_set_run_feedback": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32]),
     "htm_bank_noise": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_uint32, C.c_int32, C.c_uint32, C.c_uint32,
                                  C.c_void_p, C.c_void_p]),
+    "htm_bank_encode": (C.c_int, [C.c_void_p, C.POINTER(HtmScalarField), C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32]),
+    "htm_decode_votes": (C.c_int, [C.c_void_p, C.POINTER(HtmScalarField), C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]),
+    "htm_predicted_value": (C.c_int, [C.c_void_p, C.POINTER(HtmScalarField), C.c_int32, C.c_void_p]),
 }
 
 # The HIP runtime calls the binding makes itself -- the device buffers of run(record=...) -- resolved through the library's own

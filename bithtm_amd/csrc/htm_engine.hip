@@ -22,6 +22,7 @@
 #include <algorithm>
 #include <cfloat>
 #include <climits>
+#include <cmath>
 #include <chrono>
 #include <map>
 #include <mutex>
@@ -48,6 +49,7 @@
 #include "htm_tm_feed.h"
 #include "htm_sp_run.h"
 #include "htm_fork.h"
+#include "htm_scalar.h"
 
 // ------------------------------------------------------------------------------------------
 // host side
@@ -167,6 +169,7 @@ struct htm_handle {
     int32_t *pin_out;
     PinDev *d_pin;
     int32_t *d_pin_buf;
+    int32_t *d_value_out;                           // htm_predicted_value: the (bucket, score) pairs of its decode launch
     // run feedback (htm_set_run_feedback): the bank whose runs write their next row and its size, the device descriptor the
     // feedback launches read (filled when the feedback is set), and the scratch votes row (zero between uses: htm_forecast.h)
     uint32_t *feed_bank;
@@ -3364,6 +3367,95 @@ extern "C" int htm_bank_noise(htm_handle *h, const uint32_t *src_bank, int32_t n
     LAUNCH(h, "bank_noise", k_bank_noise, blocks, NOISE_THREADS, h->d, src_bank, n_src, dst_bank, n_dst, first_step, n_rows, seed, threshold24,
            src_resets, dst_resets);
     return launch_status(h->err);
+}
+
+// Scalar streams (htm_scalar.h).  The field table of a call, checked -- every field as the definition has it, inside the input
+// row, no two overlapping, and for a decoding call no field above the LDS cap -- and copied into the kernel argument
+static int scalar_table(htm_handle *h, const char *what, const htm_scalar_field *fields, int32_t n_fields, bool decoding, ScalarTab *tab) {
+    const std::string who = what;
+    if (!fields) { h->err = who + ": null field table"; return HTM_ERR_ARGUMENT; }
+    if (n_fields < 1 || n_fields > HTM_SCALAR_MAX_FIELDS) { h->err = who + ": n_fields outside [1, " + std::to_string(HTM_SCALAR_MAX_FIELDS) + "]"; return HTM_ERR_ARGUMENT; }
+    if (!h->cfg.enable_sp) { h->err = who + ": needs a handle with the device's own Spatial Pooler (its input rows are packed)"; return HTM_ERR_STATE; }
+    memset(tab, 0, sizeof(*tab));
+    for (int j = 0; j < n_fields; ++j) {
+        const htm_scalar_field &f = fields[j];
+        const std::string fj = who + ": field " + std::to_string(j);
+        if (f.bits < 1 || f.width < 1 || f.width > f.bits) { h->err = fj + ": bits >= 1 and 1 <= width <= bits"; return HTM_ERR_ARGUMENT; }
+        if (f.buckets != (f.periodic ? f.bits : f.bits - f.width + 1)) { h->err = fj + ": buckets must be bits (periodic) or bits - width + 1"; return HTM_ERR_ARGUMENT; }
+        if (f.offset < 0 || (long long)f.offset + f.bits > (long long)h->d.I) { h->err = fj + ": reaches outside the input row"; return HTM_ERR_ARGUMENT; }
+        if (!std::isfinite(f.minimum) || !std::isfinite(f.scale) || !(f.scale > 0.0)) { h->err = fj + ": minimum and scale must be finite, scale above 0"; return HTM_ERR_ARGUMENT; }
+        if (decoding && f.bits > HTM_DECODE_MAX_BITS) { h->err = fj + ": more than " + std::to_string(HTM_DECODE_MAX_BITS) + " bits (the decode launch's LDS)"; return HTM_ERR_ARGUMENT; }
+        for (int i = 0; i < j; ++i)
+            if (f.offset < fields[i].offset + fields[i].bits && fields[i].offset < f.offset + f.bits) { h->err = fj + ": overlaps field " + std::to_string(i); return HTM_ERR_ARGUMENT; }
+        tab->f[j] = f;
+        tab->f[j].periodic = f.periodic != 0;
+        tab->f[j].reserved = 0;
+    }
+    return 0;
+}
+
+// Bank rows from values: one launch behind whatever the stream holds, no copy, no wait, no state of the handle read (as
+// htm_bank_noise: also on a view, also while the handle is ahead)
+extern "C" int htm_bank_encode(htm_handle *h, const htm_scalar_field *fields, int32_t n_fields, const double *device_values, int32_t n_rows,
+                               uint32_t *device_bank, int32_t bank_rows, int32_t first_row) {
+    if (!h) return HTM_ERR_ARGUMENT;
+    if (!device_values || !device_bank) { h->err = "htm_bank_encode: null values or bank"; return HTM_ERR_ARGUMENT; }
+    ScalarTab tab;
+    int rc = scalar_table(h, "htm_bank_encode", fields, n_fields, false, &tab);
+    if (rc) return rc;
+    if (n_rows < 0 || first_row < 0 || (long long)first_row + n_rows > (long long)bank_rows) {
+        h->err = "htm_bank_encode: n_rows >= 0, first_row >= 0 and first_row + n_rows <= bank_rows";
+        return HTM_ERR_ARGUMENT;
+    }
+    if (((uintptr_t)device_bank & 15) != 0 || ((uintptr_t)device_values & 7) != 0) { h->err = "htm_bank_encode: the bank must be 16-byte aligned, the values 8-byte"; return HTM_ERR_ARGUMENT; }
+    if (n_rows == 0) return HTM_OK;
+    HIPCHK(h, hipSetDevice(h->device));
+    LAUNCH(h, "bank_encode", k_bank_encode, n_rows, scalar_encode_threads(h->d.W), h->d, tab, (int)n_fields, device_values, device_bank, (int)first_row);
+    return launch_status(h->err);
+}
+
+// A bucket and a score per row and field from rows of votes: one launch, no copy, no wait, no state of the handle read
+extern "C" int htm_decode_votes(htm_handle *h, const htm_scalar_field *fields, int32_t n_fields, const int32_t *device_votes, int32_t n_rows,
+                                int32_t *device_out) {
+    if (!h) return HTM_ERR_ARGUMENT;
+    if (!device_votes || !device_out) { h->err = "htm_decode_votes: null votes or output"; return HTM_ERR_ARGUMENT; }
+    ScalarTab tab;
+    int rc = scalar_table(h, "htm_decode_votes", fields, n_fields, true, &tab);
+    if (rc) return rc;
+    if (n_rows < 0) { h->err = "htm_decode_votes: n_rows must not be negative"; return HTM_ERR_ARGUMENT; }
+    if (n_rows == 0) return HTM_OK;
+    HIPCHK(h, hipSetDevice(h->device));
+    LAUNCH(h, "decode_votes", k_decode_votes, dim3(n_rows, n_fields), SCALAR_THREADS, tab, (int)n_fields, h->d.I, device_votes, device_out);
+    return launch_status(h->err);
+}
+
+// htm_predicted_input with the votes kept on the device: the votes row zeroed, the votes launch, the decode launch, and one
+// synchronising copy of 2 x n_fields ints
+extern "C" int htm_predicted_value(htm_handle *h, const htm_scalar_field *fields, int32_t n_fields, int32_t *host_out) {
+    if (!h) return HTM_ERR_ARGUMENT;
+    if (!host_out) { h->err = "htm_predicted_value: null output"; return HTM_ERR_ARGUMENT; }
+    ScalarTab tab;
+    int rc = scalar_table(h, "htm_predicted_value", fields, n_fields, true, &tab);
+    if (rc) return rc;
+    flush_tail(h);
+    REJECT_WHEN_AHEAD(h);
+    rc = pin_refuse(h, "htm_predicted_value");
+    if (rc) return rc;
+    if (h->shard_open || h->phase_open) { h->err = "htm_predicted_value: a step of the handle is open (htm_shard_begin / htm_sp_phase)"; return HTM_ERR_STATE; }
+    rc = view_enter(h, 0);
+    if (rc) return rc;
+    HIPCHK(h, hipSetDevice(h->device));
+    const Dev &d = h->d;
+    if (!h->d_pin_buf) { rc = dalloc(h, &h->d_pin_buf, d.I); if (rc) return rc; }
+    if (!h->d_value_out) { rc = dalloc(h, &h->d_value_out, 2 * HTM_SCALAR_MAX_FIELDS); if (rc) return rc; }
+    HIPCHK(h, hipMemsetAsync(h->d_pin_buf, 0, (size_t)d.I * 4, h->stream));
+    LAUNCH(h, "predicted_input", k_pin, pin_blocks(d.C), 256, d, (int)((h->step_host + 1) & 1), h->d_pin_buf);
+    LAUNCH(h, "decode_votes", k_decode_votes, dim3(1, n_fields), SCALAR_THREADS, tab, (int)n_fields, d.I, (const int32_t *)h->d_pin_buf, h->d_value_out);
+    rc = launch_status(h->err);
+    if (rc) return rc;
+    HIPCHK(h, hipMemcpyAsync(host_out, h->d_value_out, (size_t)n_fields * 8, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return HTM_OK;
 }
 
 extern "C" int htm_profile(htm_handle *h, int32_t enable) {

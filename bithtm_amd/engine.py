@@ -34,7 +34,8 @@ def pack_bits(bits, words):
 
 
 # run(record=...): the per-step fields htm_run_recorded can write, and the counts of one htm_step_record in its order
-RECORD_FIELDS = ("counters", "active_column", "column_prediction", "predicted_input")
+# ("predicted_value": the votes of "predicted_input" decoded on the device per field of an encoder -- with an `encoder=` only)
+RECORD_FIELDS = ("counters", "active_column", "column_prediction", "predicted_input", "predicted_value")
 RECORD_COUNTERS = tuple(name for name, _ in L.HtmStepRecord._fields_)
 # SpatialPooler.run(record=...): the per-step fields htm_sp_run can write, in the order of htm_sp_run_record, with the dtype of
 # each and its 32-bit words per value
@@ -98,6 +99,7 @@ _NOTHING_TO_SET = contextlib.nullcontext()         # Engine.this_call: the block
 
 class Engine:
     LIST_BANKS = 8                                  # upload_lists: device banks of lists kept per engine
+    VALUE_BANKS = 8                                 # encoded_bank: encoded banks (and their values) kept per engine
     POOL_LOOK_EVERY = 128                           # pool_look: host-fed steps between two looks at a growing pool
 
     def __init__(self, input_dim, column_dim, cell_dim, active_columns, proximal=None, boosting=None,
@@ -174,6 +176,7 @@ class Engine:
         self._record_bufs = {}                      # run(record=...): device buffers kept for the next recorded call
         self._reset_bufs = {}                       # run(resets=...): packed reset bits per content
         self._list_bufs = {}                        # upload_lists: device banks of active-column lists per content
+        self._value_bufs = {}                       # encoded_bank: (device values, device bank) per encoder and content
         self._live_states = []                      # weak references to the States of the current step (networks.retire_states)
         self._auto_grow = auto_grow                 # pool_look: the pool's size was left to the library
         self._since_check = self.POOL_LOOK_EVERY    # host-fed steps since the last look (the first step looks)
@@ -226,6 +229,9 @@ class Engine:
             self.lib.hipFree(ptr)
         for ptr in list(getattr(self, "_reset_bufs", {}).values()) + list(getattr(self, "_list_bufs", {}).values()):
             self.lib.hipFree(ptr)
+        for pair in getattr(self, "_value_bufs", {}).values():
+            for ptr in pair:
+                self.lib.hipFree(ptr)
 
     # ---- plumbing
     def _check(self, rc, what):
@@ -532,24 +538,30 @@ class Engine:
         return ptr.value
 
     def run(self, device_bank, n_inputs, n_steps, learning=True, use_graph=True, pipeline=True, continuing=False, record=None,
-            resets=None):
+            resets=None, encoder=None):
         """`resets`: None, or the device address of reset bits for this bank (upload_resets): a sequence reset before every
-        step that reads a row whose bit is set (htm_set_run_resets, set for this call only)."""
+        step that reads a row whose bit is set (htm_set_run_resets, set for this call only).  `encoder`: the ScalarEncoder a
+        "predicted_value" record decodes with."""
         with _NOTHING_TO_SET if resets is None else self.this_call(resets, n_inputs):
-            return self._run(device_bank, n_inputs, n_steps, learning, use_graph, pipeline, continuing, record)
+            return self._run(device_bank, n_inputs, n_steps, learning, use_graph, pipeline, continuing, record, encoder)
 
-    def _run(self, device_bank, n_inputs, n_steps, learning=True, use_graph=True, pipeline=True, continuing=False, record=None):
+    def _run(self, device_bank, n_inputs, n_steps, learning=True, use_graph=True, pipeline=True, continuing=False, record=None,
+             encoder=None):
         """`continuing`: the next call is another run() on the same bank (HTM_RUN_CONTINUE, include/bithtm_hip.h).
         `record`: None, or the fields of a per-step record to keep (RECORD_FIELDS): the call then goes to htm_run_recorded and
         returns {field: numpy array over the n_steps steps} -- "counters" int32[n, 8] (htm_step_record, RECORD_COUNTERS order),
         "active_column" int32[n, k], "column_prediction" uint32[n, ceil(C / 32)], "predicted_input" int32[n, input_dim] (the
-        votes of htm_set_run_predicted_input, set for this call only) -- read back after one synchronisation."""
+        votes of htm_set_run_predicted_input, set for this call only), "predicted_value" int32[n, 2 F] (with `encoder`: the (bucket,
+        score) pairs of its F fields, decoded behind the run from the rows "predicted_input" uses, which stay on the device unless
+        they were asked for too) -- read back after one synchronisation."""
         if record is None:
             self.run_into(device_bank, n_inputs, n_steps, {}, learning, use_graph, pipeline, continuing)
             return None
         fields, n = self._record_fields(record), int(n_steps)
-        self.run_into(device_bank, n_inputs, n, self._record_buffers(fields, n), learning, use_graph, pipeline, continuing)
-        return self._records_read(fields, n, sync=True)
+        buffers = self._record_buffers(fields, n, encoder)
+        self.run_into(device_bank, n_inputs, n, buffers, learning, use_graph, pipeline, continuing)
+        self.decode_records(buffers, n, encoder)
+        return self._records_read(fields, n, sync=True, encoder=encoder)
 
     def run_into(self, device_bank, n_inputs, n_steps, buffers, learning=True, use_graph=True, pipeline=True, continuing=False):
         """The run of _run, enqueued only: `buffers` = {record field: device address of its n_steps rows} (record_shapes() words
@@ -559,7 +571,7 @@ class Engine:
         rec = L.HtmRunRecord()
         votes = self._record_ptrs(buffers, rec)
         with _NOTHING_TO_SET if votes is None else self.this_call(votes=votes):
-            if not set(buffers) - {"predicted_input"}:
+            if not set(buffers) - {"predicted_input", "predicted_value"}:
                 self._check(self.lib.htm_run(self.h, C.c_void_p(device_bank), int(n_inputs), n, int(bool(learning)), flags), "htm_run")
             else:
                 self._check(self.lib.htm_run_recorded(self.h, C.c_void_p(device_bank), int(n_inputs), n, int(bool(learning)), flags,
@@ -579,18 +591,29 @@ class Engine:
             raise ValueError(f"record: fields from {allowed}, at least one (got {fields})")
         return fields
 
-    def _record_buffers(self, fields, n):
-        """{field: device address of the engine's own record buffer, large enough for n steps}."""
-        shapes = self.record_shapes()
+    def _record_buffers(self, fields, n, encoder=None):
+        """{field: device address of the engine's own record buffer, large enough for n steps}; "predicted_value" (ValueError
+        without an `encoder`) brings the rows of "predicted_input" with it: its decode launch reads them."""
+        shapes = self.record_shapes(encoder)
+        if "predicted_value" in fields:
+            if encoder is None:
+                raise ValueError('record "predicted_value" needs an encoder (run(..., encoder=))')
+            fields = tuple(fields) + (("predicted_input",) if "predicted_input" not in fields else ())
         return {f: self._record_buffer(f, max(n, 1) * shapes[f][0]) for f in fields}
 
-    def _record_args(self, fields, n, rec):
+    def decode_records(self, buffers, n, encoder):
+        """Behind a recorded run of n steps into `buffers`: the decode launch of its "predicted_value" rows (enqueued, no wait)."""
+        if "predicted_value" in buffers and n > 0:
+            self.decode_votes(encoder, buffers["predicted_input"], n, buffers["predicted_value"])
+
+    def _record_args(self, fields, n, rec, encoder=None):
         """The record buffers of n steps for `fields` into `rec` (an HtmRunRecord) and, for "predicted_input", the decoding rows
-        (set_run_predicted_input: the caller clears them) -> record_shapes()."""
-        votes = self._record_ptrs(self._record_buffers(fields, n), rec)
+        (set_run_predicted_input: the caller clears them) -> the buffers."""
+        buffers = self._record_buffers(fields, n, encoder)
+        votes = self._record_ptrs(buffers, rec)
         if votes is not None:
             self.set_run_predicted_input(votes)
-        return self.record_shapes()
+        return buffers
 
     @staticmethod
     def _record_ptrs(ptrs, rec):
@@ -600,18 +623,21 @@ class Engine:
         rec.records, rec.active_column, rec.column_prediction = (ptrs.get(f) for f in RECORD_FIELDS[:3])
         return ptrs.get("predicted_input")
 
-    def _records_read(self, fields, n, sync=False):
+    def _records_read(self, fields, n, sync=False, encoder=None):
         """{field: numpy array [n, words per step]} from the engine's own record buffers (`sync`: after waiting for the engine's
         stream, on which the records are written)."""
         if sync:
             self.sync()
-        shapes = self.record_shapes()
+        shapes = self.record_shapes(encoder)
         return {f: self._record_read(f, n * shapes[f][0], shapes[f][1]).reshape(n, shapes[f][0]) for f in fields}
 
-    def record_shapes(self):
-        """{record field: (int32 words per step, dtype)} of this engine's shape."""
-        return {"counters": (len(RECORD_COUNTERS), np.int32), "active_column": (self.active_columns, np.int32),
-                "column_prediction": ((self.column_dim + 31) // 32, np.uint32), "predicted_input": (self.input_dim, np.int32)}
+    def record_shapes(self, encoder=None):
+        """{record field: (int32 words per step, dtype)} of this engine's shape (and, with an encoder, of its "predicted_value")."""
+        shapes = {"counters": (len(RECORD_COUNTERS), np.int32), "active_column": (self.active_columns, np.int32),
+                  "column_prediction": ((self.column_dim + 31) // 32, np.uint32), "predicted_input": (self.input_dim, np.int32)}
+        if encoder is not None:
+            shapes["predicted_value"] = (2 * len(encoder), np.int32)
+        return shapes
 
     def set_run_predicted_input(self, device_votes):
         """Decoding rows of the later run() calls and group calls (htm_set_run_predicted_input); None clears them."""
@@ -623,6 +649,50 @@ class Engine:
         out = np.empty(self.input_dim, dtype=np.int32)
         self._check(self.lib.htm_predicted_input(self.h, out.ctypes.data_as(C.c_void_p)), "htm_predicted_input")
         return out
+
+    # ---- scalar streams (htm_scalar.h; encoders.py is the definition).  Raw device addresses: a caller with a device tensor of
+    # its own encodes in place after ordering its stream against stream_handle()
+    def upload_values(self, values):
+        """float64 [n, F] -> device address of the values htm_bank_encode reads (the caller frees it: hipFree)."""
+        v = np.ascontiguousarray(values, dtype=np.float64)
+        return self.device_buffer(v.nbytes, v, at_least=8)
+
+    def bank_encode(self, encoder, device_values, n_rows, device_bank, bank_rows, first_row=0):
+        """Bank rows first_row .. first_row + n_rows - 1 = encoder.encode of the device values' rows (htm_bank_encode): enqueued on
+        the engine's stream, no wait."""
+        self._check(self.lib.htm_bank_encode(self.h, encoder.table(), len(encoder), C.c_void_p(device_values), int(n_rows),
+                                             C.c_void_p(device_bank), int(bank_rows), int(first_row)), "htm_bank_encode")
+
+    def decode_votes(self, encoder, device_votes, n_rows, device_out):
+        """device_out [n_rows, F, 2] int32 = (bucket, score) per field of the device votes' rows, int32 [n_rows, input_dim]
+        (htm_decode_votes): enqueued on the engine's stream, no wait."""
+        self._check(self.lib.htm_decode_votes(self.h, encoder.table(), len(encoder), C.c_void_p(device_votes), int(n_rows),
+                                              C.c_void_p(device_out)), "htm_decode_votes")
+
+    def predicted_value(self, encoder):
+        """(bucket int32[F], score int32[F]) of the current state's votes (htm_predicted_value): the votes stay on the device."""
+        out = np.empty((len(encoder), 2), dtype=np.int32)
+        self._check(self.lib.htm_predicted_value(self.h, encoder.table(), len(encoder), out.ctypes.data_as(C.c_void_p)), "htm_predicted_value")
+        return out[:, 0].copy(), out[:, 1].copy()
+
+    def encoded_bank(self, encoder, values):
+        """float64 [n, F] -> device address of the bank of encoder.encode(values), encoded on the device: the values are
+        uploaded (8 F bytes per row) and one launch fills the bank (enqueued).  Kept by the engine per encoder and content: the
+        same values again cost nothing, and the VALUE_BANKS most recent banks stay (freed with the engine)."""
+        v = np.ascontiguousarray(values, dtype=np.float64)
+        key = (encoder.key(), v.shape, v.tobytes())
+        bufs = self._value_bufs
+        if key in bufs:
+            bufs[key] = bufs.pop(key)               # (most recent last)
+            return bufs[key][1]
+        if len(bufs) >= self.VALUE_BANKS:
+            self.sync()                             # (a run that reads the oldest bank may still be queued)
+            for ptr in bufs.pop(next(iter(bufs))):
+                self.lib.hipFree(ptr)
+        n = v.shape[0]
+        bufs[key] = pair = (self.upload_values(v), self.device_buffer(n * self.words * 4))
+        self.bank_encode(encoder, pair[0], n, pair[1], n)
+        return pair[1]
 
     def encode_votes(self, min_votes, max_bits, device_bank, bank_rows, row):
         """Row `row` of a device bank = the current state's votes encoded (htm_encode_votes): enqueued on the engine's stream, no

@@ -20,8 +20,8 @@ import numpy as np
 
 from . import _lib as L
 from .engine import HtmError, pack_bits
-from .networks import (HierarchicalTemporalMemory, InferenceView, RunRecord, _BatchedCall, _batches, _cached_bank, _encode_params, _noise_ring,
-                       _record_fields, noise_threshold, retire_states)
+from .networks import (HierarchicalTemporalMemory, InferenceView, RunRecord, _BatchedCall, _batches, _cached_bank, _check_encoder,
+                       _encode_params, _noise_ring, _record_fields, noise_threshold, retire_states)
 
 
 class SharedStream:
@@ -177,39 +177,45 @@ class ModelGroup:
         self._build()
         return True
 
-    def _records(self, fields, n):
-        """Per member: the record buffers of n steps (the members' own, as run(record=) uses) -> HtmRunRecord array (None when
-        only "predicted_input" is asked for).  "predicted_input": each member's decoding rows are set (_unset_votes
-        clears them)."""
+    def _records(self, fields, n, encoder=None):
+        """Per member: the record buffers of n steps (the members' own, as run(record=) uses) -> (HtmRunRecord array -- None when
+        only "predicted_input" / "predicted_value" are asked for -- and each member's {field: device address}, which
+        _read_records takes).  "predicted_input": each member's decoding rows are set (_unset_votes clears them);
+        "predicted_value" (with `encoder`) uses the same rows."""
         recs = (L.HtmRunRecord * len(self.models))()
-        for i, m in enumerate(self.models):
-            m.engine._record_args(fields, n, recs[i])
-        return None if fields == ("predicted_input",) else recs
+        buffers = [m.engine._record_args(fields, n, recs[i], encoder) for i, m in enumerate(self.models)]
+        return (None if not set(fields) - {"predicted_input", "predicted_value"} else recs), buffers
 
     def _unset_votes(self):
         for m in self.models:
             m.engine.set_run_predicted_input(None)
 
-    def _read_records(self, fields, n):
+    def _read_records(self, fields, n, buffers, encoder=None):
+        """`buffers`: what _records returned for this call."""
+        if encoder is not None:                 # (behind the group's launches: on the same stream, or -- members on streams of
+            for m, member in zip(self.models, buffers):             # their own -- behind the wait that ends such a call)
+                m.engine.decode_records(member, n, encoder)
         for m in self.models:                   # (the group enqueues on the first member's stream)
             m.engine.sync()
-        return [m.engine._records_read(fields, n) for m in self.models]
+        return [m.engine._records_read(fields, n, encoder=encoder) for m in self.models]
 
-    def _banks(self, inputs):
+    def _banks(self, inputs, encoder=None):
         """Each member's device bank of its rows of `inputs`, uploaded once and cached as run() caches it."""
-        ptrs = [_cached_bank(m, m.engine, x) for m, x in zip(self.models, inputs)]
+        ptrs = [_cached_bank(m, m.engine, x, encoder=encoder) for m, x in zip(self.models, inputs)]
         return (C.c_void_p * len(ptrs))(*ptrs)
 
     # run(noise=): steps per fill of the members' noise rings (see HierarchicalTemporalMemory.noise_chunk)
     noise_chunk = 1024
 
-    def run(self, inputs, steps, learning=None, use_graph=True, record=None, resets=None, noise=0.0, noise_seed=None):
+    def run(self, inputs, steps, learning=None, use_graph=True, record=None, resets=None, noise=0.0, noise_seed=None, encoder=None):
         """`steps` timesteps of every member, member i over the rows of inputs[i] (bool [B, n_inputs, input_dim]), cycled, as
         its own run(inputs[i], steps) would.  Returns None, or (`record`: as run(record=)) one RunRecord per member.
         learning=None: True, or False in a group with inference views (which refuses True).
         `noise`, `noise_seed`: as run(noise=, noise_seed=), one value or one per member; member i then ends as its own
         run(inputs[i], steps, noise=noise[i], noise_seed=noise_seed[i]) would.  The default seed is each member's own, so members
-        on the same rows still see different noise.  With all of them 0 the call is the one without noise."""
+        on the same rows still see different noise.  With all of them 0 the call is the one without noise.
+        `encoder`: as run(encoder=), one ScalarEncoder for all members: `inputs` is then float64 [B, n_inputs, F], each member's
+        values, encoded on the device into its bank, and `record` may name "predicted_value"."""
         learning = self._learning(learning)
         B = len(self.models)
         if np.ndim(noise) > 1 or (np.ndim(noise) == 1 and len(noise) != B):
@@ -223,22 +229,29 @@ class ModelGroup:
         if resets is not None:
             raise NotImplementedError("sequence resets inside a group run are not available yet (the follow-up: k_tm_reset per "
                                       "member inside the group's launches); reset members with model.reset() between group calls")
-        inputs = np.asarray(inputs, dtype=np.bool_)
-        if inputs.ndim != 3 or inputs.shape[0] != B or inputs.shape[2] != self.models[0].engine.input_dim:
-            raise ValueError(f"inputs: bool [{B}, n_inputs, {self.models[0].engine.input_dim}], got {inputs.shape}")
         fields = None if record is None else _record_fields(record)
+        e0 = self.models[0].engine
+        _check_encoder(encoder, fields, e0.input_dim, e0.column_dim)
+        if encoder is None:
+            inputs = np.asarray(inputs, dtype=np.bool_)
+            if inputs.ndim != 3 or inputs.shape[0] != B or inputs.shape[2] != e0.input_dim:
+                raise ValueError(f"inputs: bool [{B}, n_inputs, {e0.input_dim}], got {inputs.shape}")
+        else:
+            inputs = np.ascontiguousarray(inputs, dtype=np.float64)
+            if inputs.ndim != 3 or inputs.shape[0] != B or inputs.shape[1] < 1 or inputs.shape[2] != len(encoder):
+                raise ValueError(f"inputs: float64 values [{B}, n_inputs, {len(encoder)}], got {inputs.shape}")
         for m in self.models:
             retire_states(m.engine)
         self._current()
         k = self.models[0].active_columns
-        call = _BatchedCall([m.temporal_memory for m in self.models], fields)
+        call = _BatchedCall([m.temporal_memory for m in self.models], fields, encoder)
 
         def pools():        # cut into batches the smallest free-segment budget of any member lasts, with a look at the pools between them
             while self._grow(2 * k, True):
                 pass
             return [(min(m.engine._free_segments for m in self.models), 2 * k, 1)]
         for _, n in _batches(steps, pools if self._auto_grow else None, cap=int(self.noise_chunk) if any(thresholds) else None):
-            banks, n_inputs = self._banks(inputs), inputs.shape[1]
+            banks, n_inputs = self._banks(inputs, encoder), inputs.shape[1]
             if any(thresholds):
                 # each member's ring filled for the steps of this batch and the one behind it (members without noise: a copy of
                 # their rows), then the group over the rings -- the order forecast() uses for its seed rows
@@ -257,13 +270,13 @@ class ModelGroup:
                 self._check(self.lib.htm_group_run(self._g, banks, n_inputs, n, int(bool(learning)), int(bool(use_graph)), None),
                             "htm_group_run")
             else:
-                recs = self._records(fields, n)
+                recs, buffers = self._records(fields, n, encoder)
                 try:
                     self._check(self.lib.htm_group_run(self._g, banks, n_inputs, n, int(bool(learning)), int(bool(use_graph)), recs),
                                 "htm_group_run")
                 finally:
                     self._unset_votes()
-                call.add(self._read_records(fields, n))
+                call.add(self._read_records(fields, n, buffers, encoder))
             for m in self.models:
                 m.engine.steps += n
         for m in self.models:
@@ -274,13 +287,15 @@ class ModelGroup:
     # forecast(): steps per feeding group run (see HierarchicalTemporalMemory.forecast_chunk)
     forecast_chunk = 1024
 
-    def forecast(self, steps, min_votes=1, max_bits=0, record=None, use_graph=True):
+    def forecast(self, steps, min_votes=1, max_bits=0, record=None, use_graph=True, encoder=None):
         """Every member's forecast(steps, min_votes, max_bits) at once: each member rolls forward from its own state on its own
         encoded votes, one launch sequence per step for all members.  min_votes / max_bits: one value, or one per member.
-        Returns bool [B, steps, input_dim]; with `record` (as run(record=)) the pair (rows, one RunRecord per member)."""
+        Returns bool [B, steps, input_dim]; with `record` (as run(record=)) the pair (rows, one RunRecord per member).  `encoder`:
+        the ScalarEncoder a "predicted_value" record decodes with."""
         B, steps = len(self.models), int(steps)
         params = [_encode_params(a, b) for a, b in zip(np.broadcast_to(np.asarray(min_votes), (B,)), np.broadcast_to(np.asarray(max_bits), (B,)))]
         fields = None if record is None else _record_fields(record)
+        _check_encoder(encoder, fields, self.models[0].engine.input_dim, self.models[0].engine.column_dim)
         engines = [m._forecast_engine("forecast()") for m in self.models]
         for e in engines:
             retire_states(e)
@@ -290,7 +305,7 @@ class ModelGroup:
         ptrs = [m._zero_bank(e, chunk + 1) for m, e in zip(self.models, engines)]
         banks = (C.c_void_p * B)(*ptrs)
         rows = np.zeros((B, steps, engines[0].input_dim), dtype=np.bool_)
-        call = _BatchedCall([m.temporal_memory for m in self.models], fields)
+        call = _BatchedCall([m.temporal_memory for m in self.models], fields, encoder)
         for done, n in _batches(steps, cap=chunk):
             start = [e.steps for e in engines]
             recs = None
@@ -299,7 +314,7 @@ class ModelGroup:
                     e.encode_votes(mv, mb, ptr, chunk + 1, e.steps % (chunk + 1))
                     e.set_run_feedback(ptr, chunk + 1, mv, mb)
                 if fields is not None:
-                    recs = self._records(fields, n)
+                    recs, buffers = self._records(fields, n, encoder)
                 self._check(self.lib.htm_group_run(self._g, banks, chunk + 1, n, 0, int(bool(use_graph)), recs), "htm_group_run")
             finally:
                 for e in engines:
@@ -309,11 +324,33 @@ class ModelGroup:
             for e in engines:
                 e.steps += n
             if fields is not None:
-                call.add(self._read_records(fields, n))
+                call.add(self._read_records(fields, n, buffers, encoder))
             for i, (e, ptr) in enumerate(zip(engines, ptrs)):
                 rows[i, done:done + n] = e.read_bank(ptr, chunk + 1)[(start[i] + np.arange(n)) % (chunk + 1)]
         records = call.finish([steps] * B, [k] * B)
         return rows if fields is None else (rows, records)
+
+    def predicted_value(self, encoder):
+        """Every member's predicted_value(encoder): (value float64 [B, F], score int32 [B, F]) -- per member the votes launch, the
+        decode launch and a read-back of 2 F ints (htm_predicted_value)."""
+        pairs = [m.predicted_value(encoder) for m in self.models]
+        return np.stack([v for v, _ in pairs]), np.stack([s for _, s in pairs])
+
+    def forecast_values(self, steps, encoder, min_votes=1, max_bits=0, use_graph=True):
+        """Every member's forecast_values(steps, encoder, min_votes, max_bits) at once: (value float64 [B, steps, F], score int32
+        [B, steps, F]).  Row 0 of a member is its own predicted_value(); the others come from the group forecast's recorded rows."""
+        B, steps = len(self.models), int(steps)
+        bucket = np.full((B, max(steps, 0), len(encoder)), -1, dtype=np.int32)
+        score = np.zeros_like(bucket)
+        if steps > 0:
+            for i, m in enumerate(self.models):
+                m._forecast_engine("forecast_values()")
+                encoder.check_model(m.engine.input_dim, m.engine.column_dim)
+                bucket[i, 0], score[i, 0] = m.engine.predicted_value(encoder)
+            _, recs = self.forecast(steps, min_votes, max_bits, record=("predicted_value",), use_graph=use_graph, encoder=encoder)
+            for i, rec in enumerate(recs):
+                bucket[i, 1:], score[i, 1:] = rec.predicted_bucket[:-1], rec.predicted_score[:-1]
+        return encoder.value_of(bucket), score
 
     def process(self, X, learning=None, record=True):
         """One timestep of every member, member i on X[i] (bool [B, input_dim]) -- its own process(X[i]) at once.  Returns a
@@ -335,12 +372,12 @@ class ModelGroup:
         steps = [m.engine.steps for m in self.models]
         recs = None
         if record:
-            recs = self._records(("counters",), 1)
+            recs, buffers = self._records(("counters",), 1)
         self._check(self.lib.htm_group_step(self._g, packed.ctypes.data_as(C.c_void_p), int(bool(learning)), recs), "htm_group_step")
         for m in self.models:
             m.engine.steps += 1
             m.temporal_memory._new_state(None)
-        counters = np.concatenate([r["counters"] for r in self._read_records(("counters",), 1)]) if record else None
+        counters = np.concatenate([r["counters"] for r in self._read_records(("counters",), 1, buffers)]) if record else None
         for m in self.models:                       # (an overflow is reported in the tick it happened, recorded or not)
             m.engine.check_capacity()
         return RunRecord(np.asarray(steps, dtype=np.int64), counters=counters) if record else None

@@ -508,7 +508,7 @@ class TemporalMemory:
         if not self._own_distal:
             raise ValueError("run() keeps the whole loop on the device: not available with a plug-in distal_projection; call process()")
         fields = None if record is None else _record_fields(record)
-        if fields and "predicted_input" in fields:
+        if fields and {"predicted_input", "predicted_value"} & set(fields):
             raise ValueError("run(record='predicted_input'): a stand-alone TemporalMemory has no proximal mask to decode with")
         lists = check_lists(active_columns, self.column_dim)
         n_rows, n = lists.shape
@@ -614,19 +614,25 @@ class RunRecord:
       column_prediction              bool[steps, C]    cell_prediction.any(axis=1) of each step ("column_prediction", else None)
       predicted_input                int32[steps, input_dim]   the predicted-input votes of the state each step leaves
                                                        (HierarchicalTemporalMemory.predicted_input; "predicted_input", else None)
+      predicted_bucket, predicted_score   int32[steps, F]   those votes decoded per field of the run's encoder, on the device
+                                                       (ScalarEncoder.decode; "predicted_value", else None)
+      predicted_value                float64[steps, F] encoder.value_of(predicted_bucket): NaN where nothing is predicted
     and, from the counters, the per-step report of example.py:55-57 and the raw anomaly score:
       correct_columns   = active_columns - bursting_columns
       incorrect_columns = predicted_columns_before - correct_columns
       anomaly_score     = 1 - correct_columns / active_columns   (float64; 0 for a step without active columns)"""
 
-    def __init__(self, step_index, counters=None, active_column=None, column_prediction=None, predicted_input=None):
+    def __init__(self, step_index, counters=None, active_column=None, column_prediction=None, predicted_input=None,
+                 predicted_bucket=None, predicted_score=None, predicted_value=None):
         self.step_index = np.asarray(step_index, dtype=np.int64)
-        self.fields = tuple(f for f, v in zip(RECORD_FIELDS, (counters, active_column, column_prediction, predicted_input)) if v is not None)
+        self.fields = tuple(f for f, v in zip(RECORD_FIELDS, (counters, active_column, column_prediction, predicted_input, predicted_bucket))
+                            if v is not None)
         for i, name in enumerate(RECORD_COUNTERS):
             setattr(self, name, None if counters is None else np.ascontiguousarray(counters[:, i], dtype=np.int32))
         self.active_column = active_column
         self.column_prediction = column_prediction
         self.predicted_input = predicted_input
+        self.predicted_bucket, self.predicted_score, self.predicted_value = predicted_bucket, predicted_score, predicted_value
 
     def __len__(self):
         return len(self.step_index)
@@ -778,18 +784,20 @@ class HierarchicalTemporalMemory:
         with np.load(path) as z:
             self.load_state_dict({k: z[k] for k in z.files})
 
-    def _run_args(self, eng, what, inputs, steps, record, resets, noise, noise_seed):
+    def _run_args(self, eng, what, inputs, steps, record, resets, noise, noise_seed, encoder=None):
         """The arguments of a batched call over `inputs` (run(), lookahead()), checked -> (noise threshold or 0, record fields
-        or None, noise seed, inputs as a bool matrix, resets as a bool vector or None)."""
+        or None, noise seed, inputs as a bool matrix -- with an `encoder`, as the float64 matrix of its values -- resets as a bool
+        vector or None)."""
         threshold = _noise_threshold_arg(noise)
         fields = None if record is None else _record_fields(record)
+        _check_encoder(encoder, fields, eng.input_dim, self.column_dim)
         if threshold:
             if eng.shard_world > 1:
                 raise ValueError(f"{what}(noise=): not available on a column-sharded model")
             if eng.steps + max(steps, 0) + 1 > 1 << 32:
                 raise ValueError(f"{what}(noise=): the run would pass step 2^32, where the device's step counter wraps")
             noise_seed = eng.seed if noise_seed is None else int(noise_seed)
-        inputs = np.asarray(inputs, dtype=np.bool_)
+        inputs = np.asarray(inputs, dtype=np.bool_) if encoder is None else encoder.bank_values(inputs)
         if resets is not None:
             resets = np.asarray(resets, dtype=np.bool_).ravel()
             if resets.shape != (inputs.shape[0],):
@@ -808,7 +816,7 @@ class HierarchicalTemporalMemory:
         return ring, rows, None if resets is None else ring_resets
 
     def run(self, inputs, steps, learning=True, use_graph=True, pipeline=True, continuing=False, record=None, resets=None,
-            noise=0.0, noise_seed=None):
+            noise=0.0, noise_seed=None, encoder=None):
         """`steps` timesteps over the rows of the boolean matrix `inputs`, cycled, with the input
         bank resident in device memory and no per-step host work (the loop of example.py:48-53).
         Returns None; read `temporal_memory.last_state` or call process() afterwards.  `continuing=True`: the
@@ -824,25 +832,32 @@ class HierarchicalTemporalMemory:
         defaults to the model's seed).  The noise is drawn on the device (htm_bank_noise) into a ring of noise_chunk + 2 rows
         that the run reads instead of the bank, noise_chunk steps per fill; it depends on (seed, step, input) alone, so calls of
         a and b steps draw what one call of a + b steps draws, and it never repeats with the bank.  0 (the default) is the run
-        without noise, launch for launch.  `resets` keeps its meaning (a flag per row of `inputs`, expanded on the device)."""
+        without noise, launch for launch.  `resets` keeps its meaning (a flag per row of `inputs`, expanded on the device).
+        `encoder`: a ScalarEncoder whose input_dim is the model's -- `inputs` is then float64 [n, F], the VALUES of its F fields:
+        run(values, steps, encoder=enc) is run(enc.encode(values), steps), bit for bit, with the values uploaded once (8 F bytes
+        per row) and the bank encoded on the device (htm_bank_encode) and kept until the values change; everything else --
+        resets, noise, streaming, records -- works over that bank unchanged.  With it `record` may name "predicted_value": each
+        step's votes decoded on the device per field (htm_decode_votes, one launch per batch behind the run; steps x F x 2 ints
+        read back, the votes themselves only if "predicted_input" is asked for too) into RunRecord.predicted_bucket, _score,
+        _value.  None (the default) is the call as it was, launch for launch."""
         eng = self._fused_engine("run()")
         if not self.spatial_pooler._plain:
             raise RuntimeError("run() keeps the whole loop on the device: not available with plug-in objects that live on the host")
         steps = int(steps)
-        threshold, fields, noise_seed, inputs, resets = self._run_args(eng, "run", inputs, steps, record, resets, noise, noise_seed)
+        threshold, fields, noise_seed, inputs, resets = self._run_args(eng, "run", inputs, steps, record, resets, noise, noise_seed, encoder)
         retire_states(eng)
-        bank = _cached_bank(self, eng, inputs)
+        bank = _cached_bank(self, eng, inputs, encoder=encoder)
         # A pool left at its default size grows like the reference's arrays (utils.py:113-135): the run is cut into batches
         # the free segments are expected to last (2 x active_columns new segments per step: every column bursting, twice),
         # with a look at the pool between them.  An overflow inside a batch is still reported, never silent.
         k = self.active_columns
-        call = _BatchedCall([self.temporal_memory], fields)
+        call = _BatchedCall([self.temporal_memory], fields, encoder)
         del eng                                     # (the pool step may re-create the engine: the old one goes, device memory and all, as it does)
         refuse = "the segment pool has to grow in the middle of a streamed run(): end the stream (a run() without continuing=True) first"
 
         def regrown():
             nonlocal bank
-            bank = _cached_bank(self, self._engine, inputs, fresh=True)
+            bank = _cached_bank(self, self._engine, inputs, fresh=True, encoder=encoder)
 
         def pool():
             return [(_looked_at_pool(self, 2 * k, self._streaming and refuse, regrown), 2 * k, 1)]
@@ -854,7 +869,7 @@ class HierarchicalTemporalMemory:
             # words they have)
             src, rows, bits = self._batch_source(eng, bank, inputs, resets, n + (2 if continuing and last else 1), threshold, noise_seed)
             call.add([eng.run(src, rows, n, learning=learning, use_graph=use_graph, pipeline=pipeline, continuing=continuing and last,
-                              record=fields, resets=bits)])
+                              record=fields, resets=bits, encoder=encoder)])
             self._streaming = bool(continuing and last and pipeline)
         return call.finish([steps], [k])[0]
 
@@ -921,7 +936,7 @@ class HierarchicalTemporalMemory:
         return kept[1]
 
     def lookahead(self, inputs, steps, horizon, min_votes=1, max_bits=0, every=1, learning=True, use_graph=True, record=None,
-                  resets=None, noise=0.0, noise_seed=None):
+                  resets=None, noise=0.0, noise_seed=None, encoder=None):
         """Rolling look-ahead: the model runs over `inputs` as run() does (learning or not) and after every `every` steps says
         what it expects over the next `horizon` steps, its own stream unmoved.  Bit for bit, with W = steps // every:
             for j in range(W):
@@ -932,7 +947,8 @@ class HierarchicalTemporalMemory:
         makes a kept fork's stream state the model's (htm_view_sync), the fork's feedback run of `horizon` steps, and a copy of
         its rows into a result buffer -- nothing waited for or read back inside a chunk of `lookahead_chunk` windows; a
         default-sized pool is looked at between chunks, as in run().  ValueError: steps not a multiple of every, horizon < 1,
-        every < 1, and what fork(), run() and forecast() refuse."""
+        every < 1, and what fork(), run() and forecast() refuse.  `encoder`: as run()'s -- `inputs` are then values, and the
+        record may name "predicted_value" (decoded once per chunk behind its windows)."""
         steps, horizon, every = int(steps), int(horizon), int(every)
         if horizon < 1 or every < 1:
             raise ValueError(f"lookahead(): horizon and every must be at least 1, got {horizon} and {every}")
@@ -940,28 +956,28 @@ class HierarchicalTemporalMemory:
             raise ValueError(f"lookahead(): steps ({steps}) must be a multiple of every ({every})")
         min_votes, max_bits = _encode_params(min_votes, max_bits)
         eng = self._forkable_engine("lookahead()")
-        threshold, fields, noise_seed, inputs, resets = self._run_args(eng, "lookahead", inputs, steps, record, resets, noise, noise_seed)
-        if inputs.ndim != 2 or inputs.shape[0] < 1 or inputs.shape[1] != eng.input_dim:
+        threshold, fields, noise_seed, inputs, resets = self._run_args(eng, "lookahead", inputs, steps, record, resets, noise, noise_seed, encoder)
+        if encoder is None and (inputs.ndim != 2 or inputs.shape[0] < 1 or inputs.shape[1] != eng.input_dim):
             raise ValueError(f"inputs: bool [n_inputs, {eng.input_dim}], got {inputs.shape}")
         self._lookahead_fork()                      # (behind every check of the arguments: a refused call makes no view)
         retire_states(eng)
-        bank = _cached_bank(self, eng, inputs)
+        bank = _cached_bank(self, eng, inputs, encoder=encoder)
         k, bank_rows = self.active_columns, horizon + 1
         rows = np.zeros((steps // every, horizon, eng.input_dim), dtype=np.bool_)
-        call = _BatchedCall([self.temporal_memory], fields)
+        call = _BatchedCall([self.temporal_memory], fields, encoder)
         del eng                                     # (as in run(): the pool step may re-create the engine)
 
         def regrown():
             nonlocal bank
-            bank = _cached_bank(self, self._engine, inputs, fresh=True)
+            bank = _cached_bank(self, self._engine, inputs, fresh=True, encoder=encoder)
 
         def pool():
             return [(_looked_at_pool(self, 2 * k, None, regrown), 2 * k, 1)]
         for done, n in _batches(steps, pool, cap=max(int(self.lookahead_chunk), 1) * every, multiple=every):
             eng, fork = self._engine, self._lookahead_fork()
             feng, windows = fork._engine, n // every
-            shapes = eng.record_shapes()
-            record_bufs = {} if fields is None else eng._record_buffers(fields, n)
+            shapes = eng.record_shapes(encoder)
+            record_bufs = {} if fields is None else eng._record_buffers(fields, n, encoder)
             fbank = fork._zero_bank(feng, bank_rows)
             out = feng.kept_buffer(feng._record_bufs, "lookahead_rows", windows * horizon * feng.words)
             with feng.this_call(feedback=(fbank, bank_rows, min_votes, max_bits)):
@@ -976,7 +992,8 @@ class HierarchicalTemporalMemory:
                     feng.encode_votes(min_votes, max_bits, fbank, bank_rows, first % bank_rows)
                     feng.run_into(fbank, bank_rows, horizon, {}, learning=False, use_graph=use_graph)
                     feng.bank_rows(fbank, bank_rows, first, horizon, out + 4 * j * horizon * feng.words)
-            call.add([None if fields is None else eng._records_read(fields, n, sync=True)])
+            eng.decode_records(record_bufs, n, encoder)
+            call.add([None if fields is None else eng._records_read(fields, n, sync=True, encoder=encoder)])
             feng.sync()
             words = feng.read_words(out, windows * horizon * feng.words, np.uint32).reshape(windows, horizon, feng.words)
             rows[done // every:done // every + windows] = np.unpackbits(words.view(np.uint8), axis=2, bitorder="little")[:, :, :feng.input_dim]
@@ -995,6 +1012,33 @@ class HierarchicalTemporalMemory:
         if not self.spatial_pooler._plain:
             raise RuntimeError("predicted_input() decodes on the device: not available with plug-in Spatial Pooler objects that live on the host")
         return eng.predicted_input()
+
+    def predicted_value(self, encoder):
+        """Which VALUE the model expects next, per field of `encoder`: (value float64[F], score int32[F]) = the votes of
+        predicted_input() decoded on the device (htm_predicted_value: the votes launch, the decode launch and a read-back of
+        2 F ints; the votes never reach the host) -- encoder.decode(predicted_input()), the value encoder.value_of of the
+        bucket.  A fresh or reset model gives NaN and 0."""
+        if self._engine is None or not self.spatial_pooler._plain:
+            raise RuntimeError("predicted_value() decodes on the device: not available with layers or plug-in objects that live on the host")
+        encoder.check_model(self._engine.input_dim, self.column_dim)
+        bucket, score = self._engine.predicted_value(encoder)
+        return encoder.value_of(bucket), score
+
+    def forecast_values(self, steps, encoder, min_votes=1, max_bits=0, use_graph=True):
+        """The values the model expects at horizons 1 .. steps: (value float64[steps, F], score int32[steps, F]).  The loop is
+        forecast(steps, min_votes, max_bits) and the state left is its state; row j is the decode of the votes that forecast
+        row x_j encodes -- row 0 from the state before the call (predicted_value's path), row j >= 1 from the state forecast
+        step j - 1 leaves (the recorded rows, decoded on the device).  No votes cross to the host."""
+        steps = int(steps)
+        eng = self._forecast_engine("forecast_values()")
+        encoder.check_model(eng.input_dim, self.column_dim)
+        bucket = np.full((max(steps, 0), len(encoder)), -1, dtype=np.int32)
+        score = np.zeros_like(bucket)
+        if steps > 0:
+            bucket[0], score[0] = eng.predicted_value(encoder)
+            _, rec = self.forecast(steps, min_votes, max_bits, record=("predicted_value",), use_graph=use_graph, encoder=encoder)
+            bucket[1:], score[1:] = rec.predicted_bucket[:-1], rec.predicted_score[:-1]
+        return encoder.value_of(bucket), score
 
     # forecast(): steps per feeding run (the device bank holds one row more); an attribute so that a caller, or a test, can cut a
     # forecast into smaller runs
@@ -1028,7 +1072,7 @@ class HierarchicalTemporalMemory:
         eng.encode_votes(min_votes, max_bits, bank, 1, 0)
         return eng.read_bank(bank, 1)[0]
 
-    def forecast(self, steps, min_votes=1, max_bits=0, record=None, use_graph=True, learning=False, noise=0.0):
+    def forecast(self, steps, min_votes=1, max_bits=0, record=None, use_graph=True, learning=False, noise=0.0, encoder=None):
         """What the model expects over the next `steps` steps: from its current state, `steps` times
             x = encode_votes(predicted_input(), min_votes, max_bits);  process(x, learning=False)
         with the whole loop on the device (htm_set_run_feedback: each step's votes are encoded into the bank row the next step
@@ -1037,7 +1081,8 @@ class HierarchicalTemporalMemory:
         min_votes votes is never set, so a row may be empty -- and stays empty once the model predicts nothing.  learning=True
         (learning from the model's own output) raises ValueError.  To look ahead without moving this model's own stream,
         forecast on a view:  view = htm.inference_view(); view.run(context, n); view.forecast(k).  `noise` other than 0 raises
-        ValueError: a forecast reads the rows the model itself wrote, and flipping them is not offered."""
+        ValueError: a forecast reads the rows the model itself wrote, and flipping them is not offered.  `encoder`: the
+        ScalarEncoder a "predicted_value" record decodes with (forecast_values() is the call that returns values)."""
         if learning:
             raise ValueError("forecast(): learning from the model's own output is not available (learning=False only)")
         if _noise_threshold_arg(noise):
@@ -1045,19 +1090,29 @@ class HierarchicalTemporalMemory:
         min_votes, max_bits = _encode_params(min_votes, max_bits)
         eng = self._forecast_engine("forecast()")
         fields = None if record is None else _record_fields(record)
+        _check_encoder(encoder, fields, eng.input_dim, self.column_dim)
         retire_states(eng)
         chunk = int(self.forecast_chunk)
         bank = self._zero_bank(eng, chunk + 1)
         rows = np.zeros((int(steps), eng.input_dim), dtype=np.bool_)
-        call = _BatchedCall([self.temporal_memory], fields)
+        call = _BatchedCall([self.temporal_memory], fields, encoder)
         for done, n in _batches(steps, cap=chunk):          # (a forecast never looks at the pool: it does not learn)
             s0 = eng.steps
             eng.encode_votes(min_votes, max_bits, bank, chunk + 1, s0 % (chunk + 1))
             with eng.this_call(feedback=(bank, chunk + 1, min_votes, max_bits)):
-                call.add([eng.run(bank, chunk + 1, n, learning=False, use_graph=use_graph, record=fields)])
+                call.add([eng.run(bank, chunk + 1, n, learning=False, use_graph=use_graph, record=fields, encoder=encoder)])
             rows[done:done + n] = eng.read_bank(bank, chunk + 1)[(s0 + np.arange(n)) % (chunk + 1)]
         record = call.finish([int(steps)], [self.active_columns])
         return rows if fields is None else (rows, record[0])
+
+
+def _check_encoder(encoder, fields, input_dim, column_dim):
+    """The `encoder=` of a batched call: ValueError for one that does not fit the model, and for a "predicted_value" record
+    without one."""
+    if encoder is not None:
+        encoder.check_model(input_dim, column_dim)
+    elif fields and "predicted_value" in fields:
+        raise ValueError('record "predicted_value" needs an encoder (encoder=): it says which bits are which field')
 
 
 def _encode_params(min_votes, max_bits):
@@ -1151,11 +1206,11 @@ class InferenceView(HierarchicalTemporalMemory):
     compute = process
 
     def run(self, inputs, steps, learning=False, use_graph=True, pipeline=True, continuing=False, record=None, resets=None,
-            noise=0.0, noise_seed=None):
+            noise=0.0, noise_seed=None, encoder=None):
         self._no_learning(learning, "run()")
         self._check_parent()
         return super().run(inputs, steps, learning=False, use_graph=use_graph, pipeline=pipeline, continuing=continuing,
-                           record=record, resets=resets, noise=noise, noise_seed=noise_seed)
+                           record=record, resets=resets, noise=noise, noise_seed=noise_seed, encoder=encoder)
 
     def reset(self):
         self._check_parent()
@@ -1169,9 +1224,18 @@ class InferenceView(HierarchicalTemporalMemory):
         self._check_parent()
         return super().predicted_bits(min_votes, max_bits)
 
-    def forecast(self, steps, min_votes=1, max_bits=0, record=None, use_graph=True, learning=False, noise=0.0):
+    def forecast(self, steps, min_votes=1, max_bits=0, record=None, use_graph=True, learning=False, noise=0.0, encoder=None):
         self._check_parent()
-        return super().forecast(steps, min_votes, max_bits, record=record, use_graph=use_graph, learning=learning, noise=noise)
+        return super().forecast(steps, min_votes, max_bits, record=record, use_graph=use_graph, learning=learning, noise=noise,
+                                encoder=encoder)
+
+    def predicted_value(self, encoder):
+        self._check_parent()
+        return super().predicted_value(encoder)
+
+    def forecast_values(self, steps, encoder, min_votes=1, max_bits=0, use_graph=True):
+        self._check_parent()
+        return super().forecast_values(steps, encoder, min_votes, max_bits, use_graph=use_graph)
 
     def sync(self, source=None):
         """This view's stream becomes that of `source` -- the parent (the default) or another view of the same parent -- as it is
@@ -1229,11 +1293,11 @@ class InferenceView(HierarchicalTemporalMemory):
         return self._engine
 
     def lookahead(self, inputs, steps, horizon, min_votes=1, max_bits=0, every=1, learning=False, use_graph=True, record=None,
-                  resets=None, noise=0.0, noise_seed=None):
+                  resets=None, noise=0.0, noise_seed=None, encoder=None):
         self._no_learning(learning, "lookahead()")
         self._check_parent()
         return super().lookahead(inputs, steps, horizon, min_votes, max_bits, every=every, learning=False, use_graph=use_graph,
-                                 record=record, resets=resets, noise=noise, noise_seed=noise_seed)
+                                 record=record, resets=resets, noise=noise, noise_seed=noise_seed, encoder=encoder)
 
     def inference_view(self):
         raise ValueError("inference_view() of a view: make views of the model that owns the weights")
@@ -1254,13 +1318,14 @@ class InferenceView(HierarchicalTemporalMemory):
         raise ValueError("grow_pool() on an inference view: its pool is its parent's; grow the parent and make new views")
 
 
-def _cached_bank(owner, eng, inputs, fresh=False):
+def _cached_bank(owner, eng, inputs, fresh=False, encoder=None):
     """The device bank of `inputs` (bool [n, input_dim]) on `eng`: uploaded once and kept on `owner` until the inputs change
-    (fresh: uploaded again -- a new engine)."""
-    key = (inputs.shape, inputs.tobytes())
+    (fresh: uploaded again -- a new engine).  With an `encoder`, `inputs` are its values (float64 [n, F]): uploaded as they
+    are and encoded on the device (Engine.encoded_bank), cached in the same way."""
+    key = (inputs.shape, inputs.tobytes()) if encoder is None else (inputs.shape, inputs.tobytes(), encoder.key())
     bank = getattr(owner, "_bank", None)
     if fresh or bank is None or bank[0] != key:
-        owner._bank = bank = (key, eng.upload_bank(inputs))
+        owner._bank = bank = (key, eng.upload_bank(inputs) if encoder is None else eng.encoded_bank(encoder, inputs))
     return bank[1]
 
 
@@ -1278,12 +1343,17 @@ def _noise_ring(owner, eng, chunk):
     return rings[1][rows]
 
 
-def _join_record(parts, fields, first_step, steps, k, column_dim, input_dim=0):
+def _join_record(parts, fields, first_step, steps, k, column_dim, input_dim=0, encoder=None):
     """One contiguous RunRecord from the per-batch records of a run(record=...) (Engine.run's dicts), however many batches the
     pool's growth cut the call into."""
     empty = {"counters": np.zeros((0, len(RECORD_COUNTERS)), np.int32), "active_column": np.zeros((0, k), np.int32),
-             "column_prediction": np.zeros((0, (column_dim + 31) // 32), np.uint32), "predicted_input": np.zeros((0, input_dim), np.int32)}
+             "column_prediction": np.zeros((0, (column_dim + 31) // 32), np.uint32), "predicted_input": np.zeros((0, input_dim), np.int32),
+             "predicted_value": np.zeros((0, 2 * len(encoder or ())), np.int32)}
     whole = {f: np.concatenate([p[f] for p in parts]) if parts else empty[f] for f in fields}
+    if "predicted_value" in whole:                  # (bucket, score) pairs per field -> the record's three arrays
+        pairs = whole.pop("predicted_value").reshape(steps, len(encoder), 2)
+        bucket = np.ascontiguousarray(pairs[:, :, 0])
+        whole.update(predicted_bucket=bucket, predicted_score=np.ascontiguousarray(pairs[:, :, 1]), predicted_value=encoder.value_of(bucket))
     if "column_prediction" in whole:
         words = np.ascontiguousarray(whole["column_prediction"])
         whole["column_prediction"] = np.unpackbits(words.view(np.uint8), axis=1, bitorder="little")[:, :column_dim].astype(bool)
@@ -1339,8 +1409,8 @@ class _BatchedCall:
     the model's engine): the parts every batch adds per member, the step each started at, and at the end the new last_state, the
     sticky flags and one RunRecord per member."""
 
-    def __init__(self, tms, fields):
-        self.tms, self.fields = tms, fields
+    def __init__(self, tms, fields, encoder=None):
+        self.tms, self.fields, self.encoder = tms, fields, encoder
         self.first = [tm._engine.steps for tm in tms]
         self.parts = [[] for _ in tms]
 
@@ -1362,5 +1432,5 @@ class _BatchedCall:
             return [None] * len(self.tms)
         if read is not None:
             self.add(read())
-        return [_join_record(p, self.fields, f, n, k, tm.column_dim, tm._engine.input_dim)
+        return [_join_record(p, self.fields, f, n, k, tm.column_dim, tm._engine.input_dim, self.encoder)
                 for p, f, n, k, tm in zip(self.parts, self.first, steps, ks, self.tms)]

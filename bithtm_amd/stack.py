@@ -18,7 +18,7 @@ import numpy as np
 
 from . import _lib as L
 from .group import SharedStream
-from .networks import HierarchicalTemporalMemory, InferenceView, _BatchedCall, _batches, _cached_bank, _looked_at_pool, _record_fields, retire_states
+from .networks import HierarchicalTemporalMemory, InferenceView, _BatchedCall, _batches, _cached_bank, _check_encoder, _looked_at_pool, _record_fields, retire_states
 
 CHUNK_STEPS = 2048              # level-0 steps per chunk of run() (BITHTM_STACK_CHUNK; rounded down to a multiple of the strides' product)
 
@@ -200,6 +200,7 @@ class RegionStack:
                              "of the strides")
         self._check_levels()
         fields = None if record is None else _record_fields(record)
+        _check_encoder(None, fields, 0, 0)          # (a stack takes no encoder: "predicted_value" is a ValueError)
         m0 = self.levels[0]
         inputs = np.asarray(inputs, dtype=np.bool_)
         if inputs.ndim != 2 or inputs.shape[0] < 1 or inputs.shape[1] != m0.engine.input_dim:

@@ -742,6 +742,55 @@ typedef struct htm_sp_run_record {
 int htm_sp_run(htm_handle *h, const uint32_t *device_inputs, int32_t n_inputs, int32_t n_steps, int32_t learning, int32_t use_graph,
                const htm_sp_run_record *rec);
 
+/* Scalar streams: values in, bank rows out; votes in, a bucket and a score per field out -- so that a
+ * stream of numbers stays on the device from the value to the predicted value.  The reference has no encoder: the definition is
+ * this project's own, and bithtm_amd/encoders.py is its NumPy form.
+ *
+ * A field owns the input bits [offset, offset + bits) and sets `width` of them per value:
+ *   buckets = bits for a periodic field, else bits - width + 1
+ *   scale   = buckets / (maximum - minimum), formed once by the caller in float64 and passed as that double
+ *   bucket(v): t = (v - minimum) * scale, two separately rounded IEEE double operations;
+ *     non-periodic: a NaN t is missing (-1); else floor(t) clamped to [0, buckets - 1] in double, then converted (+-inf and
+ *                   huge values land on the end buckets, v == maximum on the last one)
+ *     periodic:     unless -2^31 <= t < 2^31 the value is missing (NaN and +-inf fail the comparison); else (int64)floor(t) mod
+ *                   buckets, non-negative
+ *   encode:    a bucket b >= 0 sets the bits offset + (b + j) % bits for j < width (a non-periodic field never wraps); a missing
+ *              value sets no bit of its field
+ *   decode:    score[b] = sum over j < width of votes[offset + (b + j) % bits] for b in [0, buckets); the result is the lowest b
+ *              with the largest score, and (-1, 0) where that score is 0.  Votes are counts, never negative; scores are int32.
+ *   The value of a bucket is minimum + (b + 0.5) / scale, formed by the caller from the bucket: the device never forms it.
+ *
+ * htm_bank_encode: bank row first_row + r = encode(device_values row r) for r in [0, n_rows), device_values being
+ * double[n_rows][n_fields], row-major, in DEVICE memory, and the bank in the handle's layout (words_per_row of htm_info per row).
+ * Every word of a written row is written, pad bits 0; rows outside the window keep their contents.
+ * htm_decode_votes: device_out[r][j] = the two int32 (bucket, score) of field j decoded from row r of device_votes, rows of
+ * input_dim int32 as htm_set_run_predicted_input writes them; device_out is [n_rows][n_fields][2].
+ * Both are one launch on the handle's stream behind whatever is already there; no copy, no wait, and no state of the handle is
+ * read: they may be called on any handle with the device's own Spatial Pooler (inference views included), also while the handle
+ * is ahead (HTM_RUN_CONTINUE), as htm_bank_noise.  n_rows == 0 returns HTM_OK and does nothing.
+ * htm_predicted_value: htm_predicted_input with the votes kept on the device, in a buffer of the handle's: after the held-back
+ * tail the votes launch, the decode launch and one synchronising copy of host_out[n_fields][2], (bucket, score) per field.  A
+ * state without predictions gives (-1, 0).  HTM_ERR_STATE as htm_predicted_input.
+ *
+ * HTM_ERR_ARGUMENT, nothing enqueued, the handle as it was: NULL pointers; n_fields outside [1, HTM_SCALAR_MAX_FIELDS]; a field
+ * with bits < 1, width outside [1, bits], buckets not as defined or offset < 0; a field that reaches past input_dim; two fields
+ * that overlap; a minimum or scale that is not finite, or scale <= 0; n_rows < 0; first_row < 0 or first_row + n_rows >
+ * bank_rows; a bank that is not 16-byte aligned (values: 8-byte); for the two decoding calls a field of more than
+ * HTM_DECODE_MAX_BITS bits (the prefix sums of a field live in the decode block's LDS).  HTM_ERR_STATE: a handle without the
+ * device's Spatial Pooler. */
+#define HTM_SCALAR_MAX_FIELDS 16
+#define HTM_DECODE_MAX_BITS 8192
+typedef struct htm_scalar_field {
+    double minimum, scale;
+    int32_t offset, bits, width, buckets, periodic, reserved;
+} htm_scalar_field;
+
+int htm_bank_encode(htm_handle *h, const htm_scalar_field *fields, int32_t n_fields, const double *device_values, int32_t n_rows,
+                    uint32_t *device_bank, int32_t bank_rows, int32_t first_row);
+int htm_decode_votes(htm_handle *h, const htm_scalar_field *fields, int32_t n_fields, const int32_t *device_votes, int32_t n_rows,
+                     int32_t *device_out);
+int htm_predicted_value(htm_handle *h, const htm_scalar_field *fields, int32_t n_fields, int32_t *host_out);
+
 #ifdef __cplusplus
 }
 #endif
