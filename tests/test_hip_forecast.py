@@ -2,7 +2,11 @@
 ModelGroup.forecast; htm_encode_votes / htm_set_run_feedback): the recorded run of the unmodified reference
 (tests/golden/forecast.npz), the stepwise host loop predicted_input() -> encode -> process(learning=False) on a twin in every
 schedule, call and chunk boundaries, the encoding kernel on its own (ties, odd input_dim, votes beyond one radix digit), views
-against full copies, group members against solo forecasts, the graphs of calls without feedback, and the refusals."""
+against full copies, group members against solo forecasts, the graphs of calls without feedback, and the refusals.
+
+The encoding kernel's layout cases -- rows of one chunk and of hundreds per wave, a tie quota that ends on a lane, chunk or
+wave-run boundary, every input on one vote, candidates == max_bits, the raw row's pad bits and neighbours -- and the
+feeding launches at input_dim 1 025 / 2 049 are in tests/test_hip_topdown_geometry.py (cases: tests/topdown_cases.py)."""
 
 import ctypes as C
 

@@ -1,7 +1,11 @@
 """Predicted-input decoding on the device (HierarchicalTemporalMemory.predicted_input, run(record=("predicted_input", ...)),
 ModelGroup.run(record=...); htm_predicted_input / htm_set_run_predicted_input): the reference's votes after every process()
 (tests/golden/predicted_input.npz), batched runs against the same steps taken one by one in every schedule, the overlap
-identity at full size, group members against solo twins, the graphs of undecoded calls, and the refusals."""
+identity at full size, group members against solo twins, the graphs of undecoded calls, and the refusals.
+
+The votes kernel's geometry -- input_dim beyond one pass of its bit loop, partial and empty column chunks, the unroll tail,
+the second cell word, the connected mask on the threshold and under learning -- is held to the definition on hand-built
+states in tests/test_hip_topdown_geometry.py (cases: tests/topdown_cases.py)."""
 
 import ctypes as C
 import os
