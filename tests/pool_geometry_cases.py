@@ -190,18 +190,39 @@ def oracle_snapshot(tm):
     return store_snapshot(tm.seg_cell[:S], tm.presyn[:S], tm.perm[:S], tm.seg_nsyn[:S], tm.segcount)
 
 
-def replay(case, stores=None):
+def empty_oracle(case, params=None):
+    """An empty twin of the case: its shape, permanence and parameters (or `params`), no store, and -- as Case.finish -- one
+    learning=False step of patterns[case.first], whose duty cycle is therefore the case's.  Returns (oracle, sp State, tm State)."""
+    params = params or case.params
+    ora = HTMOracle(case.I, case.C, case.K, active_columns=case.k, seed=case.seed, tm_params=params, permanence=case.permanence.copy())
+    ora.temporal_memory = TemporalMemoryOracle(case.C, case.K, params, seed=case.seed, slots=case.slots)
+    o_sp, o_tm = ora.step(case.patterns[case.first], learning=False)
+    assert np.array_equal(o_sp.active_column, case.A[case.first]) and np.array_equal(ora.spatial_pooler.duty_cycle, case.duty0)
+    return ora, o_sp, o_tm
+
+
+def replay(case, stores=None, n=None, offset=0, seed=None, empty=None):
     """The case's steps on a fresh oracle, one record per step: sp / tm (the States), last (the oracle's last_update), nsyn (the
-    synapse counts after the step), store (store_snapshot; at the steps `stores` names, default all)."""
-    ora = fresh_oracle(case)
+    synapse counts after the step), store (store_snapshot; at the steps `stores` names, default all), perm / duty (the Spatial
+    Pooler's permanences and duty cycles after the step).  The step with index i shows row i % (1 + len(case.steps)) of case.bank(),
+    as a batched run over that bank does: the case's own steps, then -- `n` steps in all, default len(case.steps) -- the bank again.
+    `offset`: the records of the first `offset` steps are left out (a member that took them alone); `seed`: another Temporal Memory
+    seed over the same imported state (the jitter and the growth draws differ, the store does not); `empty`: TMParams of an empty
+    twin (empty_oracle) instead of the case's store."""
+    ora = fresh_oracle(case) if empty is None else empty_oracle(case, empty)[0]
     tm = ora.temporal_memory
+    if seed is not None:
+        tm.seed = int(seed)
+    bank = case.bank()
     out = []
-    for t, j in enumerate(case.steps, 1):
-        o_sp, o_tm = ora.step(case.patterns[j], learning=True)
+    for t in range(1, (len(case.steps) if n is None else n) + 1):
+        assert tm.step_index == t
+        o_sp, o_tm = ora.step(bank[t % len(bank)], learning=True)
         keep = stores is None or t in stores
         out.append(SimpleNamespace(t=t, sp=o_sp, tm=o_tm, last=tm.last_update, nsyn=tm.seg_nsyn[:tm.S].copy(), S=tm.S, slots=tm.slots,
-                                   store=oracle_snapshot(tm) if keep else None))
-    return out
+                                   store=oracle_snapshot(tm) if keep else None, perm=ora.spatial_pooler.permanence.copy(),
+                                   duty=ora.spatial_pooler.duty_cycle.copy()))
+    return out[offset:]
 
 
 # ------------------------------------------------------------------------------------------ allocation

@@ -15,7 +15,7 @@ import numpy as np
 import pytest
 
 import pool_geometry_cases as pg
-from projection_method_cases import store_snapshot
+from pool_geometry_device import compare_step, device_model
 
 pytestmark = pytest.mark.gpu
 
@@ -23,56 +23,6 @@ SCHEDULES = {"two-launch": {}, "three-launch": {"BITHTM_LEAN": "1"}, "four-launc
 WORD_FORM = {"classify-words": {"BITHTM_CLASSIFY_WORDS_ABOVE": "0"},
              "classify-words-four-launch": {"BITHTM_CLASSIFY_WORDS_ABOVE": "0", "BITHTM_LEAN": "0"}}     # (n_cls = 384: the by_xcd mapping)
 MODES = ("host-fed", "batched")
-
-
-def device_model(case, state=None):
-    """The case on the device: its permanence, duty cycle and exported state.  The environment is the caller's (set before this).
-    A pool has at least 64 slots per row (htm_create): the cases of 32 slots keep every row within 32 synapses (their precondition)
-    in a pool of 64, which is what the scan's one-chunk path is for."""
-    from bithtm_amd import _lib as L
-    from hip_impl import make_htm
-    htm = make_htm(case.I, case.C, case.K, case.k, case.seed, case.permanence.copy(), None, case.params,
-                   segment_capacity=case.capacity, segment_slots=max(64, case.slots))
-    eng = htm.engine
-    eng.write(L.F_DUTY_CYCLE, case.duty0, np.float32)
-    eng.import_tm_state(case.state0 if state is None else state)
-    return htm, eng
-
-
-def same_store(what, got, want):
-    S = len(want["seg_cell"])
-    assert len(got["seg_cell"]) == S, (what, "segments", len(got["seg_cell"]), S)
-    for f in ("seg_cell", "segcount", "seg_nsyn", "syn_count"):
-        bad = np.flatnonzero(got[f] != want[f])
-        assert len(bad) == 0, (what, f, bad[:8], got[f][bad[:8]], want[f][bad[:8]])
-    row = np.repeat(np.arange(S), want["syn_count"])
-    for f in ("syn_presyn", "syn_perm_bits"):
-        bad = got[f] != want[f]
-        assert not bad.any(), (what, f, "first rows that differ", np.unique(row[bad])[:8], int(bad.sum()))
-
-
-def compare_step(case, eng, r, h_sp, h_tm, what, store=True):
-    """Everything the module's docstring lists, for the step of oracle record r."""
-    from hip_impl import compare_with_oracle
-    compare_with_oracle(what, r.sp, r.tm, h_sp, h_tm, case.K)
-    od, d = r.tm.distal_state, eng.read_distal()
-    assert np.array_equal(d["segment_potential"], od.segment_potential), (what, "segment_potential",
-                                                                          np.flatnonzero(d["segment_potential"] != od.segment_potential)[:8])
-    got, want = d["max_jittered_potential"].view(np.int32), od.max_jittered_potential.view(np.int32)
-    assert np.array_equal(got, want), (what, "max_jittered_potential: cells", np.flatnonzero(got != want)[:8])
-    assert np.array_equal(d["matching_segment_jittered_potential"].view(np.int32), od.matching_segment_jittered_potential.view(np.int32)), what
-    info = eng.check_capacity()                      # (CapacityError is a failure: every case fits its pool)
-    assert info.segments == r.S, (what, info.segments, r.S)
-    alloc = (info.new_segment_requests, info.recycled_segments, info.appended_segments)
-    assert alloc == (len(r.last.unaccounted), len(r.last.recycled), len(r.last.fresh)), (what, alloc)
-    cnt1, cnt2 = eng.read_recyclable_counts()
-    want1, want2 = pg.recount(r.nsyn, case.params.segment_matching_threshold)
-    assert np.array_equal(cnt1, want1), (what, "recyclable counts per 1 024 ids: blocks", np.flatnonzero(cnt1 != want1)[:8],
-                                         cnt1[cnt1 != want1][:8], want1[cnt1 != want1][:8])
-    assert np.array_equal(cnt2, want2), (what, "recyclable counts per 2^20 ids", cnt2, want2)
-    if store and r.store is not None:
-        st = eng.read_store()
-        same_store(what, store_snapshot(st["seg_cell"], st["presyn"], st["perm"], st["seg_nsyn"], st["segcount"]), r.store)
 
 
 def run_case(name, env, mode, monkeypatch):
