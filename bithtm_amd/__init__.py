@@ -11,7 +11,7 @@ from . import encoders, networks
 from .encoders import ScalarEncoder, ScalarField  # noqa: F401
 from .networks import InferenceView, flip_noise, noise_threshold  # noqa: F401
 from .engine import CapacityError, HtmError  # noqa: F401
-from .group import ModelGroup  # noqa: F401
+from .group import GroupTick, ModelGroup  # noqa: F401
 from .stack import RegionStack  # noqa: F401
 from .projections import DenseProjection, PredictiveProjection  # noqa: F401
 from .regularizations import ExponentialBoosting, GlobalInhibition  # noqa: F401

@@ -58,6 +58,11 @@ class HtmScalarField(C.Structure):
         "offset", "bits", "width", "buckets", "periodic", "reserved")]
 
 
+class HtmLiveRow(C.Structure):
+    """htm_live_row: a member's row of a live tick (htm_live_tick) -- the htm_step_record counters, the step's index, the flags."""
+    _fields_ = HtmStepRecord._fields_ + [("step_index", C.c_int64), ("capacity_error", C.c_int32), ("reserved", C.c_int32)]
+
+
 # htm_field
 F_ACTIVE_COLUMN, F_OVERLAPS, F_BOOSTED, F_DUTY_CYCLE, F_CELL_ACTIVATION, F_CELL_PREDICTION = 1, 2, 3, 4, 5, 6
 F_WINNER_WORDS, F_BURSTING, F_WINNER_CELL, F_SEG_CELL, F_SEG_NSYN, F_SEG_PRESYN, F_SEG_PERM = 7, 8, 9, 10, 11, 12, 13
@@ -137,6 +142,9 @@ EXPORTS = {
     "htm_bank_encode": (C.c_int, [C.c_void_p, C.POINTER(HtmScalarField), C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32]),
     "htm_decode_votes": (C.c_int, [C.c_void_p, C.POINTER(HtmScalarField), C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]),
     "htm_predicted_value": (C.c_int, [C.c_void_p, C.POINTER(HtmScalarField), C.c_int32, C.c_void_p]),
+    "htm_live_tick": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(HtmScalarField), C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
+                                C.c_void_p, C.c_void_p, C.c_void_p]),
+    "htm_live_reset": (C.c_int, [C.c_void_p, C.c_void_p]),
 }
 
 # The HIP runtime calls the binding makes itself -- the device buffers of run(record=...) -- resolved through the library's own

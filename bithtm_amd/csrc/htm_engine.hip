@@ -50,6 +50,7 @@
 #include "htm_sp_run.h"
 #include "htm_fork.h"
 #include "htm_scalar.h"
+#include "htm_live.h"
 
 // ------------------------------------------------------------------------------------------
 // host side
@@ -3540,6 +3541,17 @@ struct htm_group {
     // learning = 0 scan the store once per chunk of share_m members: kgrp_scan_shared, share_chunks x share_blocks blocks)
     bool has_view, shared;
     int share_m, share_chunks, share_blocks;
+    // live ticks (htm_live_tick / htm_live_reset; htm_live.h), allocated by the first such call.  One staging block -- the bank of
+    // the tick's rows [n][W] (copied in, or written by the encode launch), the reset flags [n], the value rows [n][max fields] --
+    // with its pinned host twin, and one result block -- rows [n], decoded pairs [n][max fields][2], vote rows [n][I] -- with its.
+    struct Live {
+        char *h_stage = nullptr, *d_stage = nullptr, *h_out = nullptr, *d_out = nullptr;
+        size_t off_flags = 0, off_values = 0, stage_bytes = 0, off_pairs = 0, off_votes = 0, out_bytes = 0;
+        const uint32_t **bank_tab = nullptr;      // the rows of the staging bank (a constant address: the graphs' key)
+        htm_step_record *d_recs = nullptr;        // the members' record slots [n] ...
+        GrpRecArgs *rec_args = nullptr;           // ... as kgrp_rec_begin takes them
+        int32_t **vote_tab = nullptr;             // the members' vote rows (in the result block) as kgrp_pin_begin takes them
+    } live;
 };
 
 #define GHIPCHK(g, call)                                                                         \
@@ -3569,6 +3581,8 @@ extern "C" void htm_group_destroy(htm_group *g) {
     // (the members may be gone already: nothing here touches them or their streams; hipFree waits for the device)
     for (auto &kv : g->graphs) hipGraphExecDestroy(kv.second);
     for (void *p : g->allocs) hipFree(p);
+    if (g->live.h_stage) hipHostFree(g->live.h_stage);
+    if (g->live.h_out) hipHostFree(g->live.h_out);
     delete g;
 }
 
@@ -3928,4 +3942,179 @@ extern "C" int htm_group_step(htm_group *g, const uint32_t *packed_inputs, int32
     const size_t words = (size_t)(d.I + 31) / 32;
     GHIPCHK(g, hipMemcpy2DAsync(g->stage, (size_t)d.W * 4, packed_inputs, words * 4, words * 4, g->n, hipMemcpyHostToDevice, g->stream));
     return group_run(g, g->stage_tab, 1, 1, learning, 0, records);
+}
+
+// ------------------------------------------------------------------------------------------
+// Live ticks (htm_live.h): the group's staging and result blocks, allocated by the first live call
+static int live_alloc(htm_group *g) {
+    htm_group::Live &lv = g->live;
+    if (lv.vote_tab) return 0;
+    const Dev &d = g->m[0]->d;
+    const size_t n = (size_t)g->n;
+    lv.off_flags = n * (size_t)d.W * 4;             // (W is a multiple of 4 words: the flags and the values stay 8-byte aligned)
+    lv.off_values = (lv.off_flags + n * 4 + 7) & ~(size_t)7;
+    lv.stage_bytes = lv.off_values + n * HTM_SCALAR_MAX_FIELDS * sizeof(double);
+    lv.off_pairs = n * sizeof(htm_live_row);
+    lv.off_votes = lv.off_pairs + n * HTM_SCALAR_MAX_FIELDS * 2 * sizeof(int32_t);
+    lv.out_bytes = lv.off_votes + n * (size_t)d.I * sizeof(int32_t);
+    if (!lv.h_stage && hipHostMalloc((void **)&lv.h_stage, lv.stage_bytes, hipHostMallocDefault) != hipSuccess) { lv.h_stage = nullptr; g->err = "live tick: hipHostMalloc failed"; return HTM_ERR_HIP; }
+    if (!lv.h_out && hipHostMalloc((void **)&lv.h_out, lv.out_bytes, hipHostMallocDefault) != hipSuccess) { lv.h_out = nullptr; g->err = "live tick: hipHostMalloc failed"; return HTM_ERR_HIP; }
+    memset(lv.h_stage, 0, lv.stage_bytes);          // (the words of a staged row beyond ceil(input_dim / 32) stay zero)
+    memset(lv.h_out, 0, lv.out_bytes);
+    if (!lv.d_stage && galloc(g, &lv.d_stage, lv.stage_bytes)) return HTM_ERR_HIP;
+    if (!lv.d_out && galloc(g, &lv.d_out, lv.out_bytes)) return HTM_ERR_HIP;
+    if (!lv.d_recs && galloc(g, &lv.d_recs, n)) return HTM_ERR_HIP;
+    if (!lv.bank_tab && galloc(g, (uint32_t ***)&lv.bank_tab, n)) return HTM_ERR_HIP;
+    if (!lv.rec_args && galloc(g, &lv.rec_args, n)) return HTM_ERR_HIP;
+    int32_t **vote_tab = nullptr;
+    if (galloc(g, &vote_tab, n)) return HTM_ERR_HIP;
+    std::vector<const uint32_t *> banks(n);
+    std::vector<GrpRecArgs> recs(n);
+    std::vector<int32_t *> votes(n);
+    for (size_t i = 0; i < n; ++i) {
+        banks[i] = (const uint32_t *)lv.d_stage + i * (size_t)d.W;
+        recs[i] = GrpRecArgs{lv.d_recs + i, nullptr, nullptr};
+        votes[i] = (int32_t *)(lv.d_out + lv.off_votes) + i * (size_t)d.I;
+    }
+    GHIPCHK(g, hipMemset(lv.d_stage, 0, lv.stage_bytes));
+    GHIPCHK(g, hipMemset(lv.d_out, 0, lv.out_bytes));
+    GHIPCHK(g, hipMemcpy((void *)lv.bank_tab, banks.data(), n * sizeof(uint32_t *), hipMemcpyHostToDevice));
+    GHIPCHK(g, hipMemcpy(lv.rec_args, recs.data(), n * sizeof(GrpRecArgs), hipMemcpyHostToDevice));
+    GHIPCHK(g, hipMemcpy(vote_tab, votes.data(), n * sizeof(int32_t *), hipMemcpyHostToDevice));
+    lv.vote_tab = vote_tab;
+    return 0;
+}
+
+// One tick of every member.  Per member the host only checks arguments, fills its part of the pinned staging block and, after the
+// one wait, copies its results out and notes its segment count (what hand_back_segments leaves for the next call's scan).
+extern "C" int htm_live_tick(htm_group *g, const double *values, const htm_scalar_field *fields, int32_t n_fields, const uint32_t *packed_inputs,
+                             const uint8_t *resets, int32_t learning, int32_t use_graph, htm_live_row *rows, int32_t *decoded, int32_t *votes) {
+    if (!g) return HTM_ERR_ARGUMENT;
+    if (!rows) { g->err = "htm_live_tick: null rows"; return HTM_ERR_ARGUMENT; }
+    if ((values != nullptr) == (packed_inputs != nullptr)) { g->err = "htm_live_tick: give either values (with a field table) or packed_inputs"; return HTM_ERR_ARGUMENT; }
+    htm_handle *h0 = g->m[0];
+    ScalarTab ftab;
+    memset(&ftab, 0, sizeof(ftab));
+    if (values) {
+        if (int rc = scalar_table(h0, "htm_live_tick", fields, n_fields, decoded != nullptr, &ftab)) { g->err = h0->err; return rc; }
+    } else if (fields || n_fields || decoded) {
+        g->err = "htm_live_tick: a field table and decoded pairs go with values, not with packed_inputs";
+        return HTM_ERR_ARGUMENT;
+    }
+    if (learning && g->has_view) { g->err = "htm_live_tick: a group with inference views steps with learning = 0 only"; return HTM_ERR_STATE; }
+    int rc = group_check(g, nullptr, nullptr);
+    if (rc) return rc;
+    GHIPCHK(g, hipSetDevice(g->device));
+    rc = group_join(g);
+    if (rc) return rc;
+    rc = live_alloc(g);
+    if (rc) return rc;
+    htm_group::Live &lv = g->live;
+    const Dev &d = h0->d;
+    const hipStream_t s = g->stream;
+    const int B = g->n, p = (int)(h0->step_host & 1);
+    const int n_dec = decoded ? (int)n_fields : 0;
+    learning = learning ? 1 : 0;
+    // the one copy in: the rows and the flags (a contiguous part of the block), or the flags and the values
+    int32_t *flags = (int32_t *)(lv.h_stage + lv.off_flags);
+    bool resetting = false;
+    for (int i = 0; i < B; ++i) {
+        flags[i] = resets && resets[i] ? LIVE_RESET | (p ? LIVE_PARITY : 0) : 0;
+        resetting |= flags[i] != 0;
+    }
+    size_t c0, c1;
+    if (values) {
+        memcpy(lv.h_stage + lv.off_values, values, (size_t)B * n_fields * sizeof(double));
+        c0 = lv.off_flags;
+        c1 = lv.off_values + (size_t)B * n_fields * sizeof(double);
+    } else {
+        const size_t words = (size_t)(d.I + 31) / 32;
+        for (int i = 0; i < B; ++i) memcpy(lv.h_stage + (size_t)i * d.W * 4, packed_inputs + (size_t)i * words, words * 4);
+        c0 = 0;
+        c1 = lv.off_flags + (size_t)B * 4;
+    }
+    GHIPCHK(g, hipMemcpyAsync(lv.d_stage + c0, lv.h_stage + c0, c1 - c0, hipMemcpyHostToDevice, s));
+    // resets first: the record's begin launch then counts the cleared prediction words (predicted_columns_before = 0)
+    if (resetting) LAUNCH_ON(h0, s, 0, "live:reset", klive_reset, dim3(reset_blocks(d), B), 256, g->d_tab, (const int32_t *)(lv.d_stage + lv.off_flags));
+    LAUNCH_ON(h0, s, 0, "group:record", kgrp_rec_clear, B, 64, g->d_recs);
+    LAUNCH_ON(h0, s, 0, "group:record", kgrp_rec_begin, dim3(rec_blocks(d), B), 256, g->d_tab, p ^ 1, g->d_recs, (const GrpRecArgs *)lv.rec_args, 1);
+    if (values)
+        LAUNCH_ON(h0, s, 0, "live:encode", k_bank_encode, B, scalar_encode_threads(d.W), d, ftab, (int)n_fields, (const double *)(lv.d_stage + lv.off_values),
+                  (uint32_t *)lv.d_stage, 0);
+    const bool decoding = decoded || votes;
+    if (decoding) LAUNCH_ON(h0, s, 0, "group:predicted_input", kgrp_pin_begin, dim3(pin_begin_blocks(1, d.I), B), 256, g->d_tab, p ^ 1, g->d_pins, lv.vote_tab, 1);
+    const RunModes modes{true, false, decoding, false};
+    GroupForm f = group_form(g);
+    f.shared = g->shared && !learning;
+    if (run_schedule(h0, 1, use_graph).graph) {
+        const GroupGraphKey key{p, modes, learning, f.fuse, f.large, f.shared, f.spec, 1, lv.bank_tab, 1};
+        const hipGraphExec_t exec = cached_graph(g->graphs, key, s, g->err, [&] {
+            group_enqueue_step(g, modes, lv.bank_tab, 1, learning, p, f);
+            return 0;
+        });
+        if (!exec) return HTM_ERR_HIP;
+        GHIPCHK(g, hipGraphLaunch(exec, s));
+    } else {
+        group_enqueue_step(g, modes, lv.bank_tab, 1, learning, p, f);
+    }
+    LAUNCH_ON(h0, s, 0, "live:finish", klive_finish, dim3(std::max(n_dec, 1), B), SCALAR_THREADS, g->d_tab, p, ftab, n_dec,
+              (const int32_t *)(lv.d_out + lv.off_votes), (const htm_step_record *)lv.d_recs, (htm_live_row *)lv.d_out, (int32_t *)(lv.d_out + lv.off_pairs));
+    for (htm_handle *h : g->m) {
+        h->step_host += 1;
+        h->window_known = true;
+        if (learning) weights_touched(h);
+    }
+    rc = launch_status(g->err);
+    if (rc) return rc;
+    // the one copy out and the one wait
+    const size_t pair_bytes = (size_t)B * n_dec * 2 * sizeof(int32_t), vote_bytes = (size_t)B * d.I * sizeof(int32_t);
+    const size_t out_bytes = votes ? lv.off_votes + vote_bytes : lv.off_pairs + pair_bytes;
+    GHIPCHK(g, hipMemcpyAsync(lv.h_out, lv.d_out, out_bytes, hipMemcpyDeviceToHost, s));
+    GHIPCHK(g, hipStreamSynchronize(s));
+    memcpy(rows, lv.h_out, (size_t)B * sizeof(htm_live_row));
+    if (decoded) memcpy(decoded, lv.h_out + lv.off_pairs, pair_bytes);
+    if (votes) memcpy(votes, lv.h_out + lv.off_votes, vote_bytes);
+    for (int i = 0; i < B; ++i) {                   // (the segment hint each member's next call -- group or solo -- starts from)
+        htm_handle *h = g->m[i];
+        h->seg_hint = std::max(h->seg_hint, (int)rows[i].record.segments);
+        if (h->seg_pinned) *h->seg_pinned = rows[i].record.segments;
+    }
+    return HTM_OK;
+}
+
+// htm_reset of the flagged members in one launch.  The flags are the call's own (pageable) words: the copy has read them when
+// it returns, as the staging copy of htm_group_step.
+extern "C" int htm_live_reset(htm_group *g, const uint8_t *members) {
+    if (!g) return HTM_ERR_ARGUMENT;
+    std::vector<int32_t> flags((size_t)g->n, 0);
+    bool any = false;
+    for (int i = 0; i < g->n; ++i) {
+        if (members && !members[i]) continue;
+        const htm_handle *h = g->m[i];
+        const std::string who = "htm_live_reset: member " + std::to_string(i);
+        if (sp_is_ahead(h)) { g->err = who + ": the Spatial Pooler is ahead (htm_run ended with HTM_RUN_CONTINUE)"; return HTM_ERR_STATE; }
+        if (h->shard_open) { g->err = who + " has a step open"; return HTM_ERR_STATE; }
+        flags[i] = LIVE_RESET | ((h->step_host & 1) ? LIVE_PARITY : 0);
+        any = true;
+    }
+    if (!any) return HTM_OK;
+    GHIPCHK(g, hipSetDevice(g->device));
+    for (int i = 0; i < g->n; ++i) {                // (the flagged members' own work first, as htm_reset: tails, open phases)
+        if (!flags[i]) continue;
+        htm_handle *h = g->m[i];
+        flush_tail(h);
+        if (int rc = view_enter(h, 0)) { g->err = h->err; return rc; }
+        if (close_open_phases(h)) { g->err = h->err; return HTM_ERR_HIP; }
+        if (h->stream != g->stream) GHIPCHK(g, hipStreamSynchronize(h->stream));
+    }
+    if (int rc = live_alloc(g)) return rc;
+    htm_group::Live &lv = g->live;
+    htm_handle *h0 = g->m[0];
+    const hipStream_t s = g->stream;
+    GHIPCHK(g, hipMemcpyAsync(lv.d_stage + lv.off_flags, flags.data(), flags.size() * 4, hipMemcpyHostToDevice, s));
+    LAUNCH_ON(h0, s, 0, "live:reset", klive_reset, dim3(reset_blocks(h0->d), g->n), 256, g->d_tab, (const int32_t *)(lv.d_stage + lv.off_flags));
+    const int rc = launch_status(g->err);
+    if (rc) return rc;
+    if (g->mixed) GHIPCHK(g, hipStreamSynchronize(s));
+    return HTM_OK;
 }

@@ -25,16 +25,11 @@ __global__ __launch_bounds__(64) void k_reset_begin(ResetDev *r, const uint32_t 
     if (threadIdx.x == 0) { r->bits = bits; r->n = n; }
 }
 
-// p: parity of the step the reset goes before (the previous step's buffers are p ^ 1).  rd: the run's reset bits, or null
-// (htm_reset: unconditional, `step` is the coming step's index).  rec: the recorded call's descriptor, or null: its
-// "predicted before" becomes 0.
-__global__ __launch_bounds__(256) void k_tm_reset(Dev d, int p, const ResetDev *rd, RecDev *rec, uint32_t step) {
+// The reset itself, before the step of parity p (the previous step's buffers are p ^ 1), grid-stride over blockIdx.x: `step` is
+// the coming step's index; rec: the recorded call's descriptor, or null: its "predicted before" becomes 0.  (A role of its own:
+// the masked reset of a model group's live tick, htm_live.h, calls it per member.)
+__device__ __forceinline__ void role_tm_reset(const Dev &d, int p, RecDev *rec, uint32_t step) {
     Counters *c = d.ctr;
-    if (rd) {
-        step = c->step[p];
-        const uint32_t row = step % (uint32_t)rd->n;
-        if (!((rd->bits[row >> 5] >> (row & 31)) & 1u)) return;      // (the same answer in every block)
-    }
     const int q = p ^ 1;
     const int i0 = (int)(blockIdx.x * 256 + threadIdx.x), stride = (int)gridDim.x * 256;
     const int S = d.world > 1 ? c->L : c->S;
@@ -50,4 +45,15 @@ __global__ __launch_bounds__(256) void k_tm_reset(Dev d, int p, const ResetDev *
         c->cm_dense_step = step + 1u;
         if (rec) rec->prev_pred = 0;
     }
+}
+
+// p: parity of the step the reset goes before.  rd: the run's reset bits, or null (htm_reset: unconditional, `step` is the
+// coming step's index).  rec: as role_tm_reset takes it.
+__global__ __launch_bounds__(256) void k_tm_reset(Dev d, int p, const ResetDev *rd, RecDev *rec, uint32_t step) {
+    if (rd) {
+        step = d.ctr->step[p];
+        const uint32_t row = step % (uint32_t)rd->n;
+        if (!((rd->bits[row >> 5] >> (row & 31)) & 1u)) return;      // (the same answer in every block)
+    }
+    role_tm_reset(d, p, rec, step);
 }

@@ -110,14 +110,15 @@ __global__ __launch_bounds__(SCALAR_THREADS) void k_bank_encode(Dev d, ScalarTab
     }
 }
 
-__global__ __launch_bounds__(SCALAR_THREADS) void k_decode_votes(ScalarTab tab, int n_fields, int I, const int32_t *__restrict__ votes,
-                                                                 int32_t *__restrict__ out) {
+// the decode of one field of one vote row (votes: the row's first vote, the field's offset not yet added) into o[0] = bucket,
+// o[1] = score: the body of k_decode_votes, which the finish launch of a model group's live tick (htm_live.h) runs per member
+// and field
+__device__ __forceinline__ void role_decode_votes(const htm_scalar_field &f, const int32_t *__restrict__ votes, int32_t *__restrict__ o) {
     __shared__ uint32_t s_p[HTM_DECODE_MAX_BITS + 1];
     __shared__ uint32_t s_w[SCALAR_WAVES];
     __shared__ u64 s_k[SCALAR_WAVES];
-    const htm_scalar_field &f = tab.f[blockIdx.y];
     const int bits = f.bits, width = f.width, buckets = f.buckets;
-    const int32_t *v = votes + (size_t)blockIdx.x * (size_t)I + f.offset;
+    const int32_t *v = votes + f.offset;
     const int lane = lane_id(), wave = (int)(threadIdx.x >> 6);
     if (threadIdx.x == 0) s_p[0] = 0u;
     uint32_t carry = 0u;
@@ -152,10 +153,14 @@ __global__ __launch_bounds__(SCALAR_THREADS) void k_decode_votes(ScalarTab tab, 
 #pragma unroll
         for (int u = 1; u < SCALAR_WAVES; ++u) best = s_k[u] > best ? s_k[u] : best;
         const int32_t score = (int32_t)(best >> 32);
-        int32_t *o = out + ((size_t)blockIdx.x * n_fields + blockIdx.y) * 2;
         o[0] = score > 0 ? (int32_t)~(uint32_t)best : -1;
         o[1] = score > 0 ? score : 0;
     }
+}
+
+__global__ __launch_bounds__(SCALAR_THREADS) void k_decode_votes(ScalarTab tab, int n_fields, int I, const int32_t *__restrict__ votes,
+                                                                 int32_t *__restrict__ out) {
+    role_decode_votes(tab.f[blockIdx.y], votes + (size_t)blockIdx.x * (size_t)I, out + ((size_t)blockIdx.x * n_fields + blockIdx.y) * 2);
 }
 
 #endif

@@ -19,8 +19,8 @@ import ctypes as C
 import numpy as np
 
 from . import _lib as L
-from .engine import HtmError, pack_bits
-from .networks import (HierarchicalTemporalMemory, InferenceView, RunRecord, _BatchedCall, _batches, _cached_bank, _check_encoder,
+from .engine import CapacityError, HtmError, pack_bits
+from .networks import (RECORD_COUNTERS, HierarchicalTemporalMemory, InferenceView, RunRecord, _BatchedCall, _batches, _cached_bank, _check_encoder,
                        _encode_params, _noise_ring, _record_fields, noise_threshold, retire_states)
 
 
@@ -42,6 +42,29 @@ class SharedStream:
         h, self.handle = getattr(self, "handle", None), None
         if h:
             self.lib.hipStreamDestroy(h)
+
+
+class GroupTick(RunRecord):
+    """What ModelGroup.tick() returns: row i is member i's step of this tick.  RunRecord's counters and derived properties
+    (correct_columns, incorrect_columns, anomaly_score), step_index int64 [B], and
+      capacity_error    int32 [B]   each member's sticky capacity flags after the step (engine.info().capacity_error)
+      predicted_bucket, predicted_score int32 [B, F], predicted_value float64 [B, F]   with an encoder: the votes of the state
+                                    the step leaves, decoded per field on the device; NaN where nothing is predicted
+      predicted_input   int32 [B, input_dim]   with predicted_input=True: those votes themselves"""
+
+    def __init__(self, rows, pairs=None, votes=None, encoder=None):
+        counters = np.stack([rows[name] for name in RECORD_COUNTERS], axis=1)
+        bucket = score = value = None
+        if pairs is not None:
+            bucket, score = np.ascontiguousarray(pairs[:, :, 0]), np.ascontiguousarray(pairs[:, :, 1])
+            value = encoder.value_of(bucket)
+        super().__init__(rows["step_index"], counters=counters, predicted_input=votes, predicted_bucket=bucket, predicted_score=score,
+                         predicted_value=value)
+        self.capacity_error = np.ascontiguousarray(rows["capacity_error"], dtype=np.int32)
+
+
+_CAPACITY_FLAGS = ((1, "segment pool (segment_capacity)"), (2, "synapse slots (segment_slots)"), (4, "work list / growth staging"),
+                   (8, "dead-segment report (DEAD_CAP)"))
 
 
 def _refuse_member(i, m):
@@ -381,3 +404,88 @@ class ModelGroup:
         for m in self.models:                       # (an overflow is reported in the tick it happened, recorded or not)
             m.engine.check_capacity()
         return RunRecord(np.asarray(steps, dtype=np.int64), counters=counters) if record else None
+
+    # ---- live ticks (htm_live_tick / htm_live_reset, include/bithtm_hip.h)
+    def _member_mask(self, mask, what):
+        """bool [B] (None: `None`), ValueError for another shape."""
+        if mask is None:
+            return None
+        mask = np.asarray(mask)
+        if mask.shape != (len(self.models),):
+            raise ValueError(f"{what}: bool [{len(self.models)}], got shape {mask.shape}")
+        return mask.astype(np.bool_)
+
+    def _due_resets(self, mask):
+        """uint8 [B]: the members a device-side reset is due for -- flagged (mask None: all) and past step 0; a fresh member is in
+        the empty state already, as TemporalMemory.reset has it."""
+        return np.array([(mask is None or bool(mask[i])) and m.engine.steps > 0 for i, m in enumerate(self.models)], dtype=np.uint8)
+
+    def reset(self, members=None):
+        """A sequence reset (model.reset()) of the members flagged in `members` (bool [B]; None: all of them), in one launch."""
+        mask = self._member_mask(members, "members")
+        for m in self.models:
+            retire_states(m.engine)
+        self._current()
+        due = self._due_resets(mask)
+        if due.any():
+            self._check(self.lib.htm_live_reset(self._g, due.ctypes.data_as(C.c_void_p)), "htm_live_reset")
+        for i, m in enumerate(self.models):         # (the host side as the member's own reset() leaves it)
+            if mask is None or mask[i]:
+                m.temporal_memory._last_ref = None
+                m.temporal_memory._was_reset = True
+
+    def tick(self, values, encoder=None, resets=None, learning=None, predicted_input=False, use_graph=True):
+        """One live timestep of every member in one call whose copies, launches and waits do not depend on B: member i steps on
+        values[i] -- float64 [B, F] with `encoder` (a ScalarEncoder; NaN: missing), encoded on the device, else bool
+        [B, input_dim] as process() takes it -- after a sequence reset where resets[i] (bool [B], or None).  Returns a GroupTick:
+        every member's counters, step index and capacity flags, with an encoder the decoded prediction of its next values, with
+        predicted_input=True the votes.  Member i ends as after `if resets[i]: m.reset()` and `m.run(values[i][None], 1,
+        learning=learning, encoder=encoder, record=...)`.  A capacity overflow raises CapacityError in the tick where it
+        happened; the exception's `.tick` is the finished GroupTick (the other members' results stand).
+        learning=None: True, or False in a group with inference views (which refuses True)."""
+        learning = self._learning(learning)
+        B = len(self.models)
+        e0 = self.models[0].engine
+        _check_encoder(encoder, None, e0.input_dim, e0.column_dim)
+        if encoder is None:
+            X = np.asarray(values, dtype=np.bool_)
+            if X.shape != (B, e0.input_dim):
+                raise ValueError(f"values: bool [{B}, {e0.input_dim}], got {X.shape}")
+        else:
+            X = np.ascontiguousarray(values, dtype=np.float64)
+            if X.shape != (B, len(encoder)):
+                raise ValueError(f"values: float64 [{B}, {len(encoder)}], got {X.shape}")
+        mask = self._member_mask(resets, "resets")
+        for m in self.models:
+            retire_states(m.engine)
+        self._current()
+        if self._auto_grow:
+            self._grow(self.models[0].active_columns, False)
+        flags = self._due_resets(mask) if mask is not None and mask.any() else None
+        rows = np.zeros(B, dtype=L.HtmLiveRow)
+        pairs = votes = None
+        if encoder is None:
+            words = (e0.input_dim + 31) // 32
+            packed = np.ascontiguousarray(np.stack([pack_bits(x, words) for x in X]), dtype=np.uint32)
+            args = (None, None, 0, packed.ctypes.data_as(C.c_void_p))
+        else:
+            pairs = np.zeros((B, len(encoder), 2), dtype=np.int32)
+            args = (X.ctypes.data_as(C.c_void_p), encoder.table(), len(encoder), None)
+        if predicted_input:
+            votes = np.zeros((B, e0.input_dim), dtype=np.int32)
+
+        def ptr(a):
+            return None if a is None else a.ctypes.data_as(C.c_void_p)
+        self._check(self.lib.htm_live_tick(self._g, *args, ptr(flags), int(bool(learning)), int(bool(use_graph)), ptr(rows), ptr(pairs),
+                                           ptr(votes)), "htm_live_tick")
+        for m in self.models:
+            m.engine.steps += 1
+            m.temporal_memory._new_state(None)
+        tick = GroupTick(rows, pairs, votes, encoder)
+        if tick.capacity_error.any():
+            what = "; ".join(f"member {i}:" + "".join(" " + text for bit, text in _CAPACITY_FLAGS if flag & bit) + f" (flags {flag})"
+                             for i, flag in enumerate(tick.capacity_error.tolist()) if flag)
+            err = CapacityError("capacity exhausted: " + what)
+            err.tick = tick
+            raise err
+        return tick

@@ -791,6 +791,37 @@ int htm_decode_votes(htm_handle *h, const htm_scalar_field *fields, int32_t n_fi
                      int32_t *device_out);
 int htm_predicted_value(htm_handle *h, const htm_scalar_field *fields, int32_t n_fields, int32_t *host_out);
 
+/* Live ticks of a model group: one call per tick of n streams whose copies, launches and waits do not
+ * depend on n.  Every pointer below is HOST memory; the call returns when the results are there.
+ *
+ * htm_live_tick: for each member i, in order: a sequence reset (htm_reset) if resets[i] is not 0, then one step on its input
+ * row -- row i of values, double[n][n_fields], encoded with the field table as htm_bank_encode encodes it (packed_inputs must be
+ * NULL), or row i of packed_inputs as the group's host-fed step takes it (fields NULL, n_fields 0, values NULL).  rows[i] is
+ * member i's record of that step, the index of the step and the member's sticky capacity flags after it (what htm_get_info
+ * reports as capacity_error).  decoded (optional, only with a field table): int32[n][n_fields][2], (bucket, score) of the
+ * votes of the state the step leaves, as htm_predicted_value gives them.  votes (optional): int32[n][input_dim], those votes
+ * themselves, as htm_predicted_input gives them.  Decoding rows a member has set (htm_set_run_predicted_input) are neither
+ * written nor unset.  learning and use_graph as in the group's batched run (a tick is a call of one step: eager below
+ * BITHTM_EAGER_BELOW).  With all members on one stream a tick makes one copy to the device, the launches, one copy back and one
+ * wait; the members' segment hints are taken from the result rows.
+ * Refused with nothing enqueued and the group usable afterwards: everything the group's batched run refuses of its members
+ * (HTM_ERR_STATE: step parities that differ, a member that is ahead or has a step open, reset bits or run feedback set on a
+ * member, learning on a group with inference views), and HTM_ERR_ARGUMENT: NULL rows, neither or both of values and
+ * packed_inputs, a field table the scalar calls above refuse, decoded without a field table.  A NULL group: HTM_ERR_ARGUMENT.
+ *
+ * htm_live_reset: htm_reset of every member whose byte in members is not 0 (NULL: all of them), in one launch and without a
+ * wait; members of either step parity.  Refused as htm_reset refuses a member (ahead, a step open). */
+typedef struct htm_live_row {
+    htm_step_record record;
+    int64_t step_index;
+    int32_t capacity_error;
+    int32_t reserved;
+} htm_live_row;
+
+int htm_live_tick(htm_group *g, const double *values, const htm_scalar_field *fields, int32_t n_fields, const uint32_t *packed_inputs,
+                  const uint8_t *resets, int32_t learning, int32_t use_graph, htm_live_row *rows, int32_t *decoded, int32_t *votes);
+int htm_live_reset(htm_group *g, const uint8_t *members);
+
 #ifdef __cplusplus
 }
 #endif
