@@ -63,6 +63,14 @@ class HtmLiveRow(C.Structure):
     _fields_ = HtmStepRecord._fields_ + [("step_index", C.c_int64), ("capacity_error", C.c_int32), ("reserved", C.c_int32)]
 
 
+class HtmLikelihoodConfig(C.Structure):
+    """htm_likelihood_config: the five parameters of the anomaly likelihood (likelihood.PARAMETERS order)."""
+    _fields_ = [("struct_bytes", C.c_uint32)] + [(name, C.c_int32) for name in (
+        "learning_period", "estimation_samples", "history", "averaging_window", "reestimation_period")]
+
+
+LIKELIHOOD_CHUNK = 512                      # HTM_LIKELIHOOD_CHUNK (csrc/htm_likelihood.h): steps per launch of htm_likelihood_update
+
 # htm_field
 F_ACTIVE_COLUMN, F_OVERLAPS, F_BOOSTED, F_DUTY_CYCLE, F_CELL_ACTIVATION, F_CELL_PREDICTION = 1, 2, 3, 4, 5, 6
 F_WINNER_WORDS, F_BURSTING, F_WINNER_CELL, F_SEG_CELL, F_SEG_NSYN, F_SEG_PRESYN, F_SEG_PERM = 7, 8, 9, 10, 11, 12, 13
@@ -145,6 +153,15 @@ EXPORTS = {
     "htm_live_tick": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(HtmScalarField), C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
                                 C.c_void_p, C.c_void_p, C.c_void_p]),
     "htm_live_reset": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "htm_likelihood_create": (C.c_int, [C.c_void_p, C.POINTER(HtmLikelihoodConfig), C.c_void_p, C.c_int32, C.POINTER(C.c_void_p)]),
+    "htm_likelihood_destroy": (None, [C.c_void_p]),
+    "htm_likelihood_update": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.c_int32, C.c_void_p]),
+    "htm_likelihood_reset": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "htm_likelihood_state_bytes": (C.c_int64, [C.c_void_p]),
+    "htm_likelihood_export": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]),
+    "htm_likelihood_import": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]),
+    "htm_likelihood_tick": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(HtmScalarField), C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
+                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 
 # The HIP runtime calls the binding makes itself -- the device buffers of run(record=...) -- resolved through the library's own

@@ -51,6 +51,7 @@
 #include "htm_fork.h"
 #include "htm_scalar.h"
 #include "htm_live.h"
+#include "htm_likelihood.h"
 
 // ------------------------------------------------------------------------------------------
 // host side
@@ -3543,10 +3544,11 @@ struct htm_group {
     int share_m, share_chunks, share_blocks;
     // live ticks (htm_live_tick / htm_live_reset; htm_live.h), allocated by the first such call.  One staging block -- the bank of
     // the tick's rows [n][W] (copied in, or written by the encode launch), the reset flags [n], the value rows [n][max fields] --
-    // with its pinned host twin, and one result block -- rows [n], decoded pairs [n][max fields][2], vote rows [n][I] -- with its.
+    // with its pinned host twin, and one result block -- the likelihoods [n] of a scored tick (htm_likelihood_tick; the copy out of any
+    // other tick begins behind them), rows [n], decoded pairs [n][max fields][2], vote rows [n][I] -- with its.
     struct Live {
         char *h_stage = nullptr, *d_stage = nullptr, *h_out = nullptr, *d_out = nullptr;
-        size_t off_flags = 0, off_values = 0, stage_bytes = 0, off_pairs = 0, off_votes = 0, out_bytes = 0;
+        size_t off_flags = 0, off_values = 0, stage_bytes = 0, off_rows = 0, off_pairs = 0, off_votes = 0, out_bytes = 0;
         const uint32_t **bank_tab = nullptr;      // the rows of the staging bank (a constant address: the graphs' key)
         htm_step_record *d_recs = nullptr;        // the members' record slots [n] ...
         GrpRecArgs *rec_args = nullptr;           // ... as kgrp_rec_begin takes them
@@ -3945,6 +3947,140 @@ extern "C" int htm_group_step(htm_group *g, const uint32_t *packed_inputs, int32
 }
 
 // ------------------------------------------------------------------------------------------
+// Anomaly likelihood (htm_likelihood.h): the state of n streams in ONE device allocation, laid out as
+// htm_likelihood_export hands it out -- t int64[n], mean double[n], std double[n], flag int32[n] (padded to 8 bytes),
+// q ring int32[n][window], a ring int32[n][history] (padded to 8 bytes) -- the tail table, and the device's pointer table of a
+// call over more than one stream.  The object keeps nothing of the handles its calls come through: no stream, no event.
+struct htm_likelihood {
+    int device = 0, n = 0;
+    LikDev d;
+    char *state = nullptr;
+    size_t bytes = 0;
+    double *tail = nullptr;
+    const htm_step_record **d_tab = nullptr;  // [n] device pointers: the records of the update last enqueued
+    int32_t *d_flags = nullptr;               // htm_likelihood_reset's flags [n]
+};
+
+static int lik_refuse(htm_handle *h, const std::string &msg, int code) {
+    if (h) h->err = msg; else g_create_error = msg;
+    return code;
+}
+
+extern "C" void htm_likelihood_destroy(htm_likelihood *lk) {
+    if (!lk) return;
+    hipSetDevice(lk->device);
+    if (lk->state) hipFree(lk->state);        // (hipFree waits for the device: nothing enqueued still reads them)
+    if (lk->tail) hipFree(lk->tail);
+    if (lk->d_tab) hipFree((void *)lk->d_tab);
+    if (lk->d_flags) hipFree(lk->d_flags);
+    delete lk;
+}
+
+extern "C" int htm_likelihood_create(htm_handle *h, const htm_likelihood_config *cfg, const double *tail_table513, int32_t n_streams, htm_likelihood **out) {
+    if (out) *out = nullptr;
+    if (!h || !cfg || !tail_table513 || !out) return lik_refuse(h, "htm_likelihood_create: null argument", HTM_ERR_ARGUMENT);
+    if (cfg->struct_bytes != sizeof(htm_likelihood_config)) return lik_refuse(h, "htm_likelihood_create: htm_likelihood_config size mismatch", HTM_ERR_ARGUMENT);
+    if (cfg->learning_period < 0 || cfg->estimation_samples < 1 || cfg->history < 1 || cfg->history > HTM_LIKELIHOOD_MAX_HISTORY ||
+        cfg->averaging_window < 1 || cfg->averaging_window > HTM_LIKELIHOOD_MAX_WINDOW || cfg->reestimation_period < 1)
+        return lik_refuse(h, "htm_likelihood_create: learning_period >= 0, estimation_samples >= 1, history in [1, 16384], averaging_window in [1, 64], "
+                             "reestimation_period >= 1", HTM_ERR_ARGUMENT);
+    if (n_streams < 1) return lik_refuse(h, "htm_likelihood_create: n_streams must be at least 1", HTM_ERR_ARGUMENT);
+    if (h->world > 1) return lik_refuse(h, "htm_likelihood_create: not available on a column-sharded handle", HTM_ERR_STATE);
+    HIPCHK(h, hipSetDevice(h->device));
+    htm_likelihood *lk = new htm_likelihood();
+    lk->device = h->device;
+    lk->n = n_streams;
+    const size_t n = (size_t)n_streams;
+    const size_t off_mean = n * 8, off_std = n * 16, off_flag = n * 24, off_q = (off_flag + n * 4 + 7) & ~(size_t)7;
+    const size_t off_a = off_q + n * (size_t)cfg->averaging_window * 4;
+    lk->bytes = (off_a + n * (size_t)cfg->history * 4 + 7) & ~(size_t)7;
+    bool ok = hipMalloc((void **)&lk->state, lk->bytes) == hipSuccess && hipMalloc((void **)&lk->tail, HTM_LIKELIHOOD_TAIL * sizeof(double)) == hipSuccess &&
+              hipMalloc((void **)&lk->d_tab, n * sizeof(void *)) == hipSuccess && hipMalloc((void **)&lk->d_flags, n * sizeof(int32_t)) == hipSuccess;
+    // (synchronous: the state and the table are there when the call returns, whatever stream the first update comes on)
+    ok = ok && hipMemset(lk->state, 0, lk->bytes) == hipSuccess &&
+         hipMemcpy(lk->tail, tail_table513, HTM_LIKELIHOOD_TAIL * sizeof(double), hipMemcpyHostToDevice) == hipSuccess;
+    if (!ok) {
+        htm_likelihood_destroy(lk);
+        return lik_refuse(h, "htm_likelihood_create: device allocation failed", HTM_ERR_HIP);
+    }
+    lk->d.p = LikParams{cfg->learning_period, cfg->estimation_samples, cfg->history, cfg->averaging_window, cfg->reestimation_period};
+    lk->d.t = (int64_t *)lk->state;
+    lk->d.mean = (double *)(lk->state + off_mean);
+    lk->d.std = (double *)(lk->state + off_std);
+    lk->d.flag = (int32_t *)(lk->state + off_flag);
+    lk->d.q_ring = (int32_t *)(lk->state + off_q);
+    lk->d.a_ring = (int32_t *)(lk->state + off_a);
+    lk->d.tail = lk->tail;
+    *out = lk;
+    return HTM_OK;
+}
+
+// what every call on an existing object checks of its handle
+static int lik_check(const char *what, htm_likelihood *lk, htm_handle *h) {
+    if (!lk || !h) return lik_refuse(h, std::string(what) + ": null argument", HTM_ERR_ARGUMENT);
+    if (h->world > 1) return lik_refuse(h, std::string(what) + ": not available on a column-sharded handle", HTM_ERR_STATE);
+    if (h->device != lk->device) return lik_refuse(h, std::string(what) + ": the handle is on another device than the likelihood object", HTM_ERR_ARGUMENT);
+    return 0;
+}
+
+extern "C" int64_t htm_likelihood_state_bytes(const htm_likelihood *lk) { return lk ? (int64_t)lk->bytes : (int64_t)HTM_ERR_ARGUMENT; }
+
+extern "C" int htm_likelihood_update(htm_likelihood *lk, htm_handle *h, const htm_step_record *const *device_records, int32_t n_steps, double *device_out) {
+    if (int rc = lik_check("htm_likelihood_update", lk, h)) return rc;
+    if (!device_records || !device_out) return lik_refuse(h, "htm_likelihood_update: null records or output", HTM_ERR_ARGUMENT);
+    if (n_steps < 0) return lik_refuse(h, "htm_likelihood_update: n_steps must not be negative", HTM_ERR_ARGUMENT);
+    for (int i = 0; i < lk->n; ++i)
+        if (!device_records[i]) return lik_refuse(h, "htm_likelihood_update: stream " + std::to_string(i) + " has no records", HTM_ERR_ARGUMENT);
+    if (n_steps == 0) return HTM_OK;
+    HIPCHK(h, hipSetDevice(lk->device));
+    const htm_step_record *const *tab = nullptr;
+    if (lk->n > 1) {
+        // the one copy of the pointer table, from the call's own (pageable) words: the copy has read them when it returns, as the
+        // staging copy of htm_group_step, so there is no staging of the object's to protect, nothing to wait for and no stream kept
+        HIPCHK(h, hipMemcpyAsync((void *)lk->d_tab, (const void *)device_records, (size_t)lk->n * sizeof(void *), hipMemcpyHostToDevice, h->stream));
+        tab = lk->d_tab;
+    }
+    // launches of at most HTM_LIKELIHOOD_CHUNK steps each, every one over all streams
+    for (int first = 0; first < n_steps; first += HTM_LIKELIHOOD_CHUNK)
+        LAUNCH(h, "likelihood", klik_update, dim3(1, lk->n), HTM_LIKELIHOOD_THREADS, lk->d, tab, tab ? nullptr : device_records[0], first,
+               std::min<int>(HTM_LIKELIHOOD_CHUNK, n_steps - first), (int)n_steps, device_out);
+    return launch_status(h->err);
+}
+
+extern "C" int htm_likelihood_reset(htm_likelihood *lk, htm_handle *h, const uint8_t *streams) {
+    if (int rc = lik_check("htm_likelihood_reset", lk, h)) return rc;
+    HIPCHK(h, hipSetDevice(lk->device));
+    if (streams) {                                  // (the call's own pageable words: the copy has read them when it returns)
+        std::vector<int32_t> flags((size_t)lk->n);
+        for (int i = 0; i < lk->n; ++i) flags[i] = streams[i] ? 1 : 0;
+        HIPCHK(h, hipMemcpyAsync(lk->d_flags, flags.data(), flags.size() * 4, hipMemcpyHostToDevice, h->stream));
+    }
+    LAUNCH(h, "likelihood:reset", klik_reset, dim3(1, lk->n), HTM_LIKELIHOOD_THREADS, lk->d, streams ? (const int32_t *)lk->d_flags : (const int32_t *)nullptr);
+    return launch_status(h->err);
+}
+
+extern "C" int htm_likelihood_export(htm_likelihood *lk, htm_handle *h, void *host_state, int64_t bytes) {
+    if (int rc = lik_check("htm_likelihood_export", lk, h)) return rc;
+    if (!host_state || bytes != (int64_t)lk->bytes) return lik_refuse(h, "htm_likelihood_export: need host_state of htm_likelihood_state_bytes bytes", HTM_ERR_ARGUMENT);
+    HIPCHK(h, hipSetDevice(lk->device));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    HIPCHK(h, hipMemcpy(host_state, lk->state, lk->bytes, hipMemcpyDeviceToHost));
+    return HTM_OK;
+}
+
+extern "C" int htm_likelihood_import(htm_likelihood *lk, htm_handle *h, const void *host_state, int64_t bytes) {
+    if (int rc = lik_check("htm_likelihood_import", lk, h)) return rc;
+    if (!host_state || bytes != (int64_t)lk->bytes) return lik_refuse(h, "htm_likelihood_import: need host_state of htm_likelihood_state_bytes bytes", HTM_ERR_ARGUMENT);
+    // (the values a kernel indexes with are reduced there, but a t below 0 has no meaning)
+    for (int i = 0; i < lk->n; ++i)
+        if (((const int64_t *)host_state)[i] < 0) return lik_refuse(h, "htm_likelihood_import: stream " + std::to_string(i) + " has t < 0", HTM_ERR_ARGUMENT);
+    HIPCHK(h, hipSetDevice(lk->device));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    HIPCHK(h, hipMemcpy(lk->state, host_state, lk->bytes, hipMemcpyHostToDevice));
+    return HTM_OK;
+}
+
+// ------------------------------------------------------------------------------------------
 // Live ticks (htm_live.h): the group's staging and result blocks, allocated by the first live call
 static int live_alloc(htm_group *g) {
     htm_group::Live &lv = g->live;
@@ -3954,7 +4090,8 @@ static int live_alloc(htm_group *g) {
     lv.off_flags = n * (size_t)d.W * 4;             // (W is a multiple of 4 words: the flags and the values stay 8-byte aligned)
     lv.off_values = (lv.off_flags + n * 4 + 7) & ~(size_t)7;
     lv.stage_bytes = lv.off_values + n * HTM_SCALAR_MAX_FIELDS * sizeof(double);
-    lv.off_pairs = n * sizeof(htm_live_row);
+    lv.off_rows = n * sizeof(double);
+    lv.off_pairs = lv.off_rows + n * sizeof(htm_live_row);
     lv.off_votes = lv.off_pairs + n * HTM_SCALAR_MAX_FIELDS * 2 * sizeof(int32_t);
     lv.out_bytes = lv.off_votes + n * (size_t)d.I * sizeof(int32_t);
     if (!lv.h_stage && hipHostMalloc((void **)&lv.h_stage, lv.stage_bytes, hipHostMallocDefault) != hipSuccess) { lv.h_stage = nullptr; g->err = "live tick: hipHostMalloc failed"; return HTM_ERR_HIP; }
@@ -3987,10 +4124,17 @@ static int live_alloc(htm_group *g) {
 
 // One tick of every member.  Per member the host only checks arguments, fills its part of the pinned staging block and, after the
 // one wait, copies its results out and notes its segment count (what hand_back_segments leaves for the next call's scan).
-extern "C" int htm_live_tick(htm_group *g, const double *values, const htm_scalar_field *fields, int32_t n_fields, const uint32_t *packed_inputs,
-                             const uint8_t *resets, int32_t learning, int32_t use_graph, htm_live_row *rows, int32_t *decoded, int32_t *votes) {
+static int live_tick(htm_group *g, const double *values, const htm_scalar_field *fields, int32_t n_fields, const uint32_t *packed_inputs,
+                     const uint8_t *resets, int32_t learning, int32_t use_graph, htm_live_row *rows, int32_t *decoded, int32_t *votes,
+                     htm_likelihood *lk, double *likelihood) {
     if (!g) return HTM_ERR_ARGUMENT;
     if (!rows) { g->err = "htm_live_tick: null rows"; return HTM_ERR_ARGUMENT; }
+    if ((lk != nullptr) != (likelihood != nullptr)) { g->err = "htm_likelihood_tick: lk and likelihood go together"; return HTM_ERR_ARGUMENT; }
+    if (lk && (lk->n != g->n || lk->device != g->device)) {
+        g->err = "htm_likelihood_tick: the likelihood object has " + std::to_string(lk->n) + " streams on device " + std::to_string(lk->device) +
+                 ", the group " + std::to_string(g->n) + " members on device " + std::to_string(g->device);
+        return HTM_ERR_ARGUMENT;
+    }
     if ((values != nullptr) == (packed_inputs != nullptr)) { g->err = "htm_live_tick: give either values (with a field table) or packed_inputs"; return HTM_ERR_ARGUMENT; }
     htm_handle *h0 = g->m[0];
     ScalarTab ftab;
@@ -4058,7 +4202,10 @@ extern "C" int htm_live_tick(htm_group *g, const double *values, const htm_scala
         group_enqueue_step(g, modes, lv.bank_tab, 1, learning, p, f);
     }
     LAUNCH_ON(h0, s, 0, "live:finish", klive_finish, dim3(std::max(n_dec, 1), B), SCALAR_THREADS, g->d_tab, p, ftab, n_dec,
-              (const int32_t *)(lv.d_out + lv.off_votes), (const htm_step_record *)lv.d_recs, (htm_live_row *)lv.d_out, (int32_t *)(lv.d_out + lv.off_pairs));
+              (const int32_t *)(lv.d_out + lv.off_votes), (const htm_step_record *)lv.d_recs, (htm_live_row *)(lv.d_out + lv.off_rows),
+              (int32_t *)(lv.d_out + lv.off_pairs));
+    // a scored tick: every member's stream of the likelihood object takes the step's record, behind the finish launch
+    if (lk) LAUNCH_ON(h0, s, 0, "live:likelihood", klik_tick, dim3(1, B), HTM_LIKELIHOOD_THREADS, lk->d, (const htm_step_record *)lv.d_recs, (double *)lv.d_out);
     for (htm_handle *h : g->m) {
         h->step_host += 1;
         h->window_known = true;
@@ -4068,10 +4215,11 @@ extern "C" int htm_live_tick(htm_group *g, const double *values, const htm_scala
     if (rc) return rc;
     // the one copy out and the one wait
     const size_t pair_bytes = (size_t)B * n_dec * 2 * sizeof(int32_t), vote_bytes = (size_t)B * d.I * sizeof(int32_t);
-    const size_t out_bytes = votes ? lv.off_votes + vote_bytes : lv.off_pairs + pair_bytes;
-    GHIPCHK(g, hipMemcpyAsync(lv.h_out, lv.d_out, out_bytes, hipMemcpyDeviceToHost, s));
+    const size_t out_end = votes ? lv.off_votes + vote_bytes : lv.off_pairs + pair_bytes, out_begin = lk ? 0 : lv.off_rows;
+    GHIPCHK(g, hipMemcpyAsync(lv.h_out + out_begin, lv.d_out + out_begin, out_end - out_begin, hipMemcpyDeviceToHost, s));
     GHIPCHK(g, hipStreamSynchronize(s));
-    memcpy(rows, lv.h_out, (size_t)B * sizeof(htm_live_row));
+    memcpy(rows, lv.h_out + lv.off_rows, (size_t)B * sizeof(htm_live_row));
+    if (lk) memcpy(likelihood, lv.h_out, (size_t)B * sizeof(double));
     if (decoded) memcpy(decoded, lv.h_out + lv.off_pairs, pair_bytes);
     if (votes) memcpy(votes, lv.h_out + lv.off_votes, vote_bytes);
     for (int i = 0; i < B; ++i) {                   // (the segment hint each member's next call -- group or solo -- starts from)
@@ -4080,6 +4228,17 @@ extern "C" int htm_live_tick(htm_group *g, const double *values, const htm_scala
         if (h->seg_pinned) *h->seg_pinned = rows[i].record.segments;
     }
     return HTM_OK;
+}
+
+extern "C" int htm_live_tick(htm_group *g, const double *values, const htm_scalar_field *fields, int32_t n_fields, const uint32_t *packed_inputs,
+                             const uint8_t *resets, int32_t learning, int32_t use_graph, htm_live_row *rows, int32_t *decoded, int32_t *votes) {
+    return live_tick(g, values, fields, n_fields, packed_inputs, resets, learning, use_graph, rows, decoded, votes, nullptr, nullptr);
+}
+
+extern "C" int htm_likelihood_tick(htm_group *g, const double *values, const htm_scalar_field *fields, int32_t n_fields, const uint32_t *packed_inputs,
+                                   const uint8_t *resets, int32_t learning, int32_t use_graph, htm_live_row *rows, int32_t *decoded, int32_t *votes,
+                                   htm_likelihood *lk, double *likelihood) {
+    return live_tick(g, values, fields, n_fields, packed_inputs, resets, learning, use_graph, rows, decoded, votes, lk, likelihood);
 }
 
 // htm_reset of the flagged members in one launch.  The flags are the call's own (pageable) words: the copy has read them when

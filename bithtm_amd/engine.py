@@ -538,22 +538,24 @@ class Engine:
         return ptr.value
 
     def run(self, device_bank, n_inputs, n_steps, learning=True, use_graph=True, pipeline=True, continuing=False, record=None,
-            resets=None, encoder=None):
+            resets=None, encoder=None, likelihood=None):
         """`resets`: None, or the device address of reset bits for this bank (upload_resets): a sequence reset before every
         step that reads a row whose bit is set (htm_set_run_resets, set for this call only).  `encoder`: the ScalarEncoder a
         "predicted_value" record decodes with."""
         with _NOTHING_TO_SET if resets is None else self.this_call(resets, n_inputs):
-            return self._run(device_bank, n_inputs, n_steps, learning, use_graph, pipeline, continuing, record, encoder)
+            return self._run(device_bank, n_inputs, n_steps, learning, use_graph, pipeline, continuing, record, encoder, likelihood)
 
     def _run(self, device_bank, n_inputs, n_steps, learning=True, use_graph=True, pipeline=True, continuing=False, record=None,
-             encoder=None):
+             encoder=None, likelihood=None):
         """`continuing`: the next call is another run() on the same bank (HTM_RUN_CONTINUE, include/bithtm_hip.h).
         `record`: None, or the fields of a per-step record to keep (RECORD_FIELDS): the call then goes to htm_run_recorded and
         returns {field: numpy array over the n_steps steps} -- "counters" int32[n, 8] (htm_step_record, RECORD_COUNTERS order),
         "active_column" int32[n, k], "column_prediction" uint32[n, ceil(C / 32)], "predicted_input" int32[n, input_dim] (the
         votes of htm_set_run_predicted_input, set for this call only), "predicted_value" int32[n, 2 F] (with `encoder`: the (bucket,
         score) pairs of its F fields, decoded behind the run from the rows "predicted_input" uses, which stay on the device unless
-        they were asked for too) -- read back after one synchronisation."""
+        they were asked for too) -- read back after one synchronisation.  `likelihood` (an anomaly.AnomalyLikelihood of one stream;
+        `record` has "counters"): its update over the counters' buffer is enqueued behind the run, before that synchronisation,
+        and "anomaly_likelihood" float64[n] is returned beside the fields."""
         if record is None:
             self.run_into(device_bank, n_inputs, n_steps, {}, learning, use_graph, pipeline, continuing)
             return None
@@ -561,7 +563,12 @@ class Engine:
         buffers = self._record_buffers(fields, n, encoder)
         self.run_into(device_bank, n_inputs, n, buffers, learning, use_graph, pipeline, continuing)
         self.decode_records(buffers, n, encoder)
-        return self._records_read(fields, n, sync=True, encoder=encoder)
+        if likelihood is not None and n > 0:
+            likelihood.enqueue(self, [buffers["counters"]], n)
+        out = self._records_read(fields, n, sync=True, encoder=encoder)
+        if likelihood is not None:
+            out["anomaly_likelihood"] = likelihood.read(self, n)[0] if n > 0 else np.zeros(0, dtype=np.float64)
+        return out
 
     def run_into(self, device_bank, n_inputs, n_steps, buffers, learning=True, use_graph=True, pipeline=True, continuing=False):
         """The run of _run, enqueued only: `buffers` = {record field: device address of its n_steps rows} (record_shapes() words

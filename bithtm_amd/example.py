@@ -5,6 +5,7 @@ the three counters: :55-57), so that its output can be compared line by line.
     python -m bithtm_amd.example --epochs 8
     python -m bithtm_amd.example --epochs 8 --batched   # one C-ABI call per epoch, hipGraph replay
     python -m bithtm_amd.example --epochs 8 --batched_report   # ... recorded: the per-step lines of the default mode
+    python -m bithtm_amd.example --epochs 8 --batched_report --likelihood   # ... with each step's anomaly likelihood
     python -m bithtm_amd.example --epochs 8 --batched --device_noise   # ... the bank uploaded once, the flip noise drawn on the device
     python -m bithtm_amd.example --epochs 8 --sequence_length 10   # a sequence reset before every 10th pattern
     python -m bithtm_amd.example --epochs 8 --use_reference_implementation   # example.py:30,36-37 (needs the user's `bithtm`)
@@ -16,7 +17,7 @@ import time
 
 import numpy as np
 
-from bithtm_amd import HierarchicalTemporalMemory
+from bithtm_amd import AnomalyLikelihood, HierarchicalTemporalMemory
 
 FLAGS = (
     # name, type, default  (the reference's flags, same names and defaults)
@@ -51,6 +52,9 @@ def parse(argv):
                     help="with --batched / --batched_report: upload the bank once and draw the flip noise on the device "
                          "(run(noise=): the keyed generator under --seed, a fresh draw per timestep) instead of drawing it with "
                          "np.random and uploading a noisy bank per epoch")
+    ap.add_argument("--likelihood", action="store_true",
+                    help="with --batched_report: score every step's anomaly likelihood on the device (run(likelihood=), NuPIC's "
+                         "default parameters, one stream over all epochs) and print it as a further column")
     return ap.parse_args(argv)
 
 
@@ -118,11 +122,13 @@ def run_batched(htm, bank, opts, out):
 def run_batched_report(htm, bank, opts, out):
     # (one draw of the epoch's noise: the same MT19937 values, in the same order, as run_stepwise's draw per step)
     report = Report(opts, htm.spatial_pooler.active_columns)
+    scoring = dict(likelihood=AnomalyLikelihood()) if opts.likelihood else {}
     for epoch in range(opts.epochs):
         noisy, noise = epoch_input(bank, opts)
-        rec = htm.run(noisy, len(noisy), record=True, resets=reset_rows(opts), **noise)
+        rec = htm.run(noisy, len(noisy), record=True, resets=reset_rows(opts), **noise, **scoring)
         for index, (b, c, i) in enumerate(zip(rec.bursting_columns, rec.correct_columns, rec.incorrect_columns)):
-            print(report.line(epoch, index, int(b), int(c), int(i)), file=out)
+            scored = f", anomaly likelihood: {rec.anomaly_likelihood[index]:.6f}" if opts.likelihood else ""
+            print(report.line(epoch, index, int(b), int(c), int(i)) + scored, file=out)
 
 
 def main(argv=None, out=sys.stdout):
@@ -140,6 +146,8 @@ def main(argv=None, out=sys.stdout):
         htm = HierarchicalTemporalMemory(opts.input_dim, opts.column_dim, opts.cell_dim,
                                          temporal_memory=ReferenceTemporalMemory(opts.column_dim, opts.cell_dim))
     else:
+        if opts.likelihood and not opts.batched_report:
+            raise SystemExit("--likelihood prints a column of the recorded report: use it with --batched_report")
         if opts.device_noise and not (opts.batched or opts.batched_report):
             raise SystemExit("--device_noise draws the noise inside a batched run: use it with --batched or --batched_report")
         htm = HierarchicalTemporalMemory(opts.input_dim, opts.column_dim, opts.cell_dim, seed=opts.seed)

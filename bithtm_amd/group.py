@@ -21,7 +21,7 @@ import numpy as np
 from . import _lib as L
 from .engine import CapacityError, HtmError, pack_bits
 from .networks import (RECORD_COUNTERS, HierarchicalTemporalMemory, InferenceView, RunRecord, _BatchedCall, _batches, _cached_bank, _check_encoder,
-                       _encode_params, _noise_ring, _record_fields, noise_threshold, retire_states)
+                       _encode_params, _noise_ring, _record_fields, _with_counters, noise_threshold, retire_states)
 
 
 class SharedStream:
@@ -50,16 +50,17 @@ class GroupTick(RunRecord):
       capacity_error    int32 [B]   each member's sticky capacity flags after the step (engine.info().capacity_error)
       predicted_bucket, predicted_score int32 [B, F], predicted_value float64 [B, F]   with an encoder: the votes of the state
                                     the step leaves, decoded per field on the device; NaN where nothing is predicted
-      predicted_input   int32 [B, input_dim]   with predicted_input=True: those votes themselves"""
+      predicted_input   int32 [B, input_dim]   with predicted_input=True: those votes themselves
+      anomaly_likelihood float64 [B]  with likelihood=: each member's anomaly likelihood of this step (log_likelihood: its log scale)"""
 
-    def __init__(self, rows, pairs=None, votes=None, encoder=None):
+    def __init__(self, rows, pairs=None, votes=None, encoder=None, anomaly_likelihood=None):
         counters = np.stack([rows[name] for name in RECORD_COUNTERS], axis=1)
         bucket = score = value = None
         if pairs is not None:
             bucket, score = np.ascontiguousarray(pairs[:, :, 0]), np.ascontiguousarray(pairs[:, :, 1])
             value = encoder.value_of(bucket)
         super().__init__(rows["step_index"], counters=counters, predicted_input=votes, predicted_bucket=bucket, predicted_score=score,
-                         predicted_value=value)
+                         predicted_value=value, anomaly_likelihood=anomaly_likelihood)
         self.capacity_error = np.ascontiguousarray(rows["capacity_error"], dtype=np.int32)
 
 
@@ -230,7 +231,8 @@ class ModelGroup:
     # run(noise=): steps per fill of the members' noise rings (see HierarchicalTemporalMemory.noise_chunk)
     noise_chunk = 1024
 
-    def run(self, inputs, steps, learning=None, use_graph=True, record=None, resets=None, noise=0.0, noise_seed=None, encoder=None):
+    def run(self, inputs, steps, learning=None, use_graph=True, record=None, resets=None, noise=0.0, noise_seed=None, encoder=None,
+            likelihood=None):
         """`steps` timesteps of every member, member i over the rows of inputs[i] (bool [B, n_inputs, input_dim]), cycled, as
         its own run(inputs[i], steps) would.  Returns None, or (`record`: as run(record=)) one RunRecord per member.
         learning=None: True, or False in a group with inference views (which refuses True).
@@ -238,9 +240,16 @@ class ModelGroup:
         run(inputs[i], steps, noise=noise[i], noise_seed=noise_seed[i]) would.  The default seed is each member's own, so members
         on the same rows still see different noise.  With all of them 0 the call is the one without noise.
         `encoder`: as run(encoder=), one ScalarEncoder for all members: `inputs` is then float64 [B, n_inputs, F], each member's
-        values, encoded on the device into its bank, and `record` may name "predicted_value"."""
+        values, encoded on the device into its bank, and `record` may name "predicted_value".
+        `likelihood`: an AnomalyLikelihood of B streams -- the call records the counters (as record=True), behind each batch ONE
+        htm_likelihood_update runs over the members' record buffers (a table of B pointers, never a launch per member) before the
+        read-back, and member i's RunRecord.anomaly_likelihood is stream i's."""
         learning = self._learning(learning)
         B = len(self.models)
+        if likelihood is not None:
+            if likelihood.streams != B:
+                raise ValueError(f"run(likelihood=): an AnomalyLikelihood of {B} streams, got {likelihood.streams}")
+            record = _with_counters(record)
         if np.ndim(noise) > 1 or (np.ndim(noise) == 1 and len(noise) != B):
             raise ValueError(f"noise: one probability or one per member ({B}), got shape {np.shape(noise)}")
         thresholds = [noise_threshold(p) for p in np.broadcast_to(np.asarray(noise, dtype=np.float64), (B,))]
@@ -267,7 +276,7 @@ class ModelGroup:
             retire_states(m.engine)
         self._current()
         k = self.models[0].active_columns
-        call = _BatchedCall([m.temporal_memory for m in self.models], fields, encoder)
+        call = _BatchedCall([m.temporal_memory for m in self.models], fields, encoder, likelihood is not None)
 
         def pools():        # cut into batches the smallest free-segment budget of any member lasts, with a look at the pools between them
             while self._grow(2 * k, True):
@@ -299,7 +308,13 @@ class ModelGroup:
                                 "htm_group_run")
                 finally:
                     self._unset_votes()
-                call.add(self._read_records(fields, n, buffers, encoder))
+                if likelihood is not None:          # (on the group's stream -- the first member's -- behind the run, before the wait)
+                    likelihood.enqueue(self.models[0].engine, [b["counters"] for b in buffers], n)
+                parts = self._read_records(fields, n, buffers, encoder)
+                if likelihood is not None:
+                    for part, row in zip(parts, likelihood.read(self.models[0].engine, n)):
+                        part["anomaly_likelihood"] = row
+                call.add(parts)
             for m in self.models:
                 m.engine.steps += n
         for m in self.models:
@@ -434,7 +449,7 @@ class ModelGroup:
                 m.temporal_memory._last_ref = None
                 m.temporal_memory._was_reset = True
 
-    def tick(self, values, encoder=None, resets=None, learning=None, predicted_input=False, use_graph=True):
+    def tick(self, values, encoder=None, resets=None, learning=None, predicted_input=False, use_graph=True, likelihood=None):
         """One live timestep of every member in one call whose copies, launches and waits do not depend on B: member i steps on
         values[i] -- float64 [B, F] with `encoder` (a ScalarEncoder; NaN: missing), encoded on the device, else bool
         [B, input_dim] as process() takes it -- after a sequence reset where resets[i] (bool [B], or None).  Returns a GroupTick:
@@ -442,10 +457,14 @@ class ModelGroup:
         predicted_input=True the votes.  Member i ends as after `if resets[i]: m.reset()` and `m.run(values[i][None], 1,
         learning=learning, encoder=encoder, record=...)`.  A capacity overflow raises CapacityError in the tick where it
         happened; the exception's `.tick` is the finished GroupTick (the other members' results stand).
-        learning=None: True, or False in a group with inference views (which refuses True)."""
+        learning=None: True, or False in a group with inference views (which refuses True).
+        `likelihood`: an AnomalyLikelihood of B streams -- the tick's records are the streams' next step (htm_likelihood_tick: one
+        launch more, B doubles more in the copy out) and GroupTick.anomaly_likelihood holds the B values."""
         learning = self._learning(learning)
         B = len(self.models)
         e0 = self.models[0].engine
+        if likelihood is not None and likelihood.streams != B:
+            raise ValueError(f"tick(likelihood=): an AnomalyLikelihood of {B} streams, got {likelihood.streams}")
         _check_encoder(encoder, None, e0.input_dim, e0.column_dim)
         if encoder is None:
             X = np.asarray(values, dtype=np.bool_)
@@ -476,12 +495,19 @@ class ModelGroup:
 
         def ptr(a):
             return None if a is None else a.ctypes.data_as(C.c_void_p)
-        self._check(self.lib.htm_live_tick(self._g, *args, ptr(flags), int(bool(learning)), int(bool(use_graph)), ptr(rows), ptr(pairs),
-                                           ptr(votes)), "htm_live_tick")
+        scores = None
+        if likelihood is None:
+            self._check(self.lib.htm_live_tick(self._g, *args, ptr(flags), int(bool(learning)), int(bool(use_graph)), ptr(rows), ptr(pairs),
+                                               ptr(votes)), "htm_live_tick")
+        else:
+            likelihood._bind(e0)
+            scores = np.zeros(B, dtype=np.float64)
+            self._check(self.lib.htm_likelihood_tick(self._g, *args, ptr(flags), int(bool(learning)), int(bool(use_graph)), ptr(rows), ptr(pairs),
+                                                     ptr(votes), likelihood._lk, ptr(scores)), "htm_likelihood_tick")
         for m in self.models:
             m.engine.steps += 1
             m.temporal_memory._new_state(None)
-        tick = GroupTick(rows, pairs, votes, encoder)
+        tick = GroupTick(rows, pairs, votes, encoder, scores)
         if tick.capacity_error.any():
             what = "; ".join(f"member {i}:" + "".join(" " + text for bit, text in _CAPACITY_FLAGS if flag & bit) + f" (flags {flag})"
                              for i, flag in enumerate(tick.capacity_error.tolist()) if flag)

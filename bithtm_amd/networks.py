@@ -29,6 +29,7 @@ import numpy as np
 
 from . import _lib as L
 from ._keyed import STREAM_INPUT_NOISE, draw_unit
+from .likelihood import log_likelihood
 from .engine import RECORD_COUNTERS, RECORD_FIELDS, SP_RECORD_FIELDS, SP_RECORD_TYPES, Engine, HtmError, check_lists, words_to_bool
 from .projections import DenseProjection, PredictiveProjection
 from .regularizations import ExponentialBoosting, GlobalInhibition, _Placeholder, checked_boosted, checked_overlaps
@@ -617,13 +618,15 @@ class RunRecord:
       predicted_bucket, predicted_score   int32[steps, F]   those votes decoded per field of the run's encoder, on the device
                                                        (ScalarEncoder.decode; "predicted_value", else None)
       predicted_value                float64[steps, F] encoder.value_of(predicted_bucket): NaN where nothing is predicted
+      anomaly_likelihood             float64[steps]    with run(likelihood=): the anomaly likelihood of each step (likelihood.py), else
+                                                       None; log_likelihood is NuPIC's log scale of it
     and, from the counters, the per-step report of example.py:55-57 and the raw anomaly score:
       correct_columns   = active_columns - bursting_columns
       incorrect_columns = predicted_columns_before - correct_columns
       anomaly_score     = 1 - correct_columns / active_columns   (float64; 0 for a step without active columns)"""
 
     def __init__(self, step_index, counters=None, active_column=None, column_prediction=None, predicted_input=None,
-                 predicted_bucket=None, predicted_score=None, predicted_value=None):
+                 predicted_bucket=None, predicted_score=None, predicted_value=None, anomaly_likelihood=None):
         self.step_index = np.asarray(step_index, dtype=np.int64)
         self.fields = tuple(f for f, v in zip(RECORD_FIELDS, (counters, active_column, column_prediction, predicted_input, predicted_bucket))
                             if v is not None)
@@ -633,6 +636,7 @@ class RunRecord:
         self.column_prediction = column_prediction
         self.predicted_input = predicted_input
         self.predicted_bucket, self.predicted_score, self.predicted_value = predicted_bucket, predicted_score, predicted_value
+        self.anomaly_likelihood = anomaly_likelihood
 
     def __len__(self):
         return len(self.step_index)
@@ -651,6 +655,10 @@ class RunRecord:
             return None
         active = self.active_columns.astype(np.float64)
         return np.where(active > 0, 1.0 - self.correct_columns / np.maximum(active, 1.0), 0.0)
+
+    @property
+    def log_likelihood(self):
+        return None if self.anomaly_likelihood is None else log_likelihood(self.anomaly_likelihood)
 
 
 def _record_fields(record):
@@ -816,7 +824,7 @@ class HierarchicalTemporalMemory:
         return ring, rows, None if resets is None else ring_resets
 
     def run(self, inputs, steps, learning=True, use_graph=True, pipeline=True, continuing=False, record=None, resets=None,
-            noise=0.0, noise_seed=None, encoder=None):
+            noise=0.0, noise_seed=None, encoder=None, likelihood=None):
         """`steps` timesteps over the rows of the boolean matrix `inputs`, cycled, with the input
         bank resident in device memory and no per-step host work (the loop of example.py:48-53).
         Returns None; read `temporal_memory.last_state` or call process() afterwards.  `continuing=True`: the
@@ -839,8 +847,16 @@ class HierarchicalTemporalMemory:
         resets, noise, streaming, records -- works over that bank unchanged.  With it `record` may name "predicted_value": each
         step's votes decoded on the device per field (htm_decode_votes, one launch per batch behind the run; steps x F x 2 ints
         read back, the votes themselves only if "predicted_input" is asked for too) into RunRecord.predicted_bucket, _score,
-        _value.  None (the default) is the call as it was, launch for launch."""
+        _value.  None (the default) is the call as it was, launch for launch.
+        `likelihood`: an AnomalyLikelihood of one stream -- the run records its counters (as record=True; named fields are
+        recorded too), behind each batch the likelihood's update is enqueued over the batch's record buffer before the read-back
+        (htm_likelihood_update: the run still waits once per batch), and RunRecord.anomaly_likelihood holds each step's value.
+        The object's state continues across calls; the model's resets do not touch it."""
         eng = self._fused_engine("run()")
+        if likelihood is not None:
+            if likelihood.streams != 1:
+                raise ValueError(f"run(likelihood=): an AnomalyLikelihood of one stream, got {likelihood.streams}")
+            record = _with_counters(record)
         if not self.spatial_pooler._plain:
             raise RuntimeError("run() keeps the whole loop on the device: not available with plug-in objects that live on the host")
         steps = int(steps)
@@ -851,7 +867,7 @@ class HierarchicalTemporalMemory:
         # the free segments are expected to last (2 x active_columns new segments per step: every column bursting, twice),
         # with a look at the pool between them.  An overflow inside a batch is still reported, never silent.
         k = self.active_columns
-        call = _BatchedCall([self.temporal_memory], fields, encoder)
+        call = _BatchedCall([self.temporal_memory], fields, encoder, likelihood is not None)
         del eng                                     # (the pool step may re-create the engine: the old one goes, device memory and all, as it does)
         refuse = "the segment pool has to grow in the middle of a streamed run(): end the stream (a run() without continuing=True) first"
 
@@ -869,7 +885,7 @@ class HierarchicalTemporalMemory:
             # words they have)
             src, rows, bits = self._batch_source(eng, bank, inputs, resets, n + (2 if continuing and last else 1), threshold, noise_seed)
             call.add([eng.run(src, rows, n, learning=learning, use_graph=use_graph, pipeline=pipeline, continuing=continuing and last,
-                              record=fields, resets=bits, encoder=encoder)])
+                              record=fields, resets=bits, encoder=encoder, likelihood=likelihood)])
             self._streaming = bool(continuing and last and pipeline)
         return call.finish([steps], [k])[0]
 
@@ -1206,11 +1222,11 @@ class InferenceView(HierarchicalTemporalMemory):
     compute = process
 
     def run(self, inputs, steps, learning=False, use_graph=True, pipeline=True, continuing=False, record=None, resets=None,
-            noise=0.0, noise_seed=None, encoder=None):
+            noise=0.0, noise_seed=None, encoder=None, likelihood=None):
         self._no_learning(learning, "run()")
         self._check_parent()
         return super().run(inputs, steps, learning=False, use_graph=use_graph, pipeline=pipeline, continuing=continuing,
-                           record=record, resets=resets, noise=noise, noise_seed=noise_seed, encoder=encoder)
+                           record=record, resets=resets, noise=noise, noise_seed=noise_seed, encoder=encoder, likelihood=likelihood)
 
     def reset(self):
         self._check_parent()
@@ -1343,7 +1359,15 @@ def _noise_ring(owner, eng, chunk):
     return rings[1][rows]
 
 
-def _join_record(parts, fields, first_step, steps, k, column_dim, input_dim=0, encoder=None):
+def _with_counters(record):
+    """run(record=..., likelihood=): the record with the counters the likelihood reads."""
+    if record is None or record is True:
+        return True
+    fields = (record,) if isinstance(record, str) else tuple(record)
+    return fields if "counters" in fields else ("counters",) + fields
+
+
+def _join_record(parts, fields, first_step, steps, k, column_dim, input_dim=0, encoder=None, likelihood=False):
     """One contiguous RunRecord from the per-batch records of a run(record=...) (Engine.run's dicts), however many batches the
     pool's growth cut the call into."""
     empty = {"counters": np.zeros((0, len(RECORD_COUNTERS)), np.int32), "active_column": np.zeros((0, k), np.int32),
@@ -1357,6 +1381,8 @@ def _join_record(parts, fields, first_step, steps, k, column_dim, input_dim=0, e
     if "column_prediction" in whole:
         words = np.ascontiguousarray(whole["column_prediction"])
         whole["column_prediction"] = np.unpackbits(words.view(np.uint8), axis=1, bitorder="little")[:, :column_dim].astype(bool)
+    if likelihood:                                  # (each batch's part carries its steps' likelihoods beside the fields)
+        whole["anomaly_likelihood"] = np.concatenate([p["anomaly_likelihood"] for p in parts]) if parts else np.zeros(0, np.float64)
     return RunRecord(first_step + np.arange(steps, dtype=np.int64), **whole)
 
 
@@ -1409,8 +1435,8 @@ class _BatchedCall:
     the model's engine): the parts every batch adds per member, the step each started at, and at the end the new last_state, the
     sticky flags and one RunRecord per member."""
 
-    def __init__(self, tms, fields, encoder=None):
-        self.tms, self.fields, self.encoder = tms, fields, encoder
+    def __init__(self, tms, fields, encoder=None, likelihood=False):
+        self.tms, self.fields, self.encoder, self.likelihood = tms, fields, encoder, likelihood
         self.first = [tm._engine.steps for tm in tms]
         self.parts = [[] for _ in tms]
 
@@ -1432,5 +1458,5 @@ class _BatchedCall:
             return [None] * len(self.tms)
         if read is not None:
             self.add(read())
-        return [_join_record(p, self.fields, f, n, k, tm.column_dim, tm._engine.input_dim, self.encoder)
+        return [_join_record(p, self.fields, f, n, k, tm.column_dim, tm._engine.input_dim, self.encoder, self.likelihood)
                 for p, f, n, k, tm in zip(self.parts, self.first, steps, ks, self.tms)]

@@ -822,6 +822,59 @@ int htm_live_tick(htm_group *g, const double *values, const htm_scalar_field *fi
                   const uint8_t *resets, int32_t learning, int32_t use_graph, htm_live_row *rows, int32_t *decoded, int32_t *votes);
 int htm_live_reset(htm_group *g, const uint8_t *members);
 
+/* Anomaly likelihood on the device (the definition is bithtm_amd/likelihood.py, which the device equals
+ * bit for bit): per stream, how improbable the recent short-term average of the raw anomaly score bursting_columns /
+ * active_columns is under the distribution of the stream's own recent history.  An htm_likelihood object holds the state of
+ * n_streams streams in device memory -- per stream t (scores seen so far, int64), the ring of the last averaging_window raw
+ * scores q = (bursting << 16) / active, the ring of the last `history` short-term averages a, the current estimate (mean, std)
+ * and whether there is one.  Sequence resets of a model do not touch it.
+ *
+ * The parameters carry NuPIC's names: learning_period >= 0, estimation_samples >= 1, history in [1, 16384], averaging_window in
+ * [1, 64], reestimation_period >= 1.  tail_table513: 513 doubles in HOST memory, TAIL[i] = 0.5 * erfc((i / 64) / sqrt 2), copied
+ * at creation (data: the device evaluates no erfc).  The object lives on h's device; every later call takes a handle of that
+ * device and enqueues on that handle's stream.
+ *
+ * The update call: device_records is a HOST array of n_streams DEVICE pointers, each to n_steps htm_step_record (of which
+ * active_columns and bursting_columns are read); device_out is DEVICE memory, double[n_streams][n_steps].  The call is enqueued
+ * behind h's stream without a wait: ceil(n_steps / 512) launches, each over all streams, and for n_streams > 1 one copy of the
+ * pointer table, whatever n_streams is (one stream: its pointer goes by value, no copy).  The table is copied from the caller's
+ * array itself, which has been read when the call returns (as htm_group_step reads its rows): the object has no staging of its
+ * own and keeps nothing of h -- no stream, no event -- so h may be destroyed as soon as its work is done, and the next call may
+ * come through any handle of the device.  n_steps == 0 returns HTM_OK and enqueues nothing.
+ * Order across handles is the caller's: calls on one object through handles that share a stream run in the order they were
+ * made; before a call through a handle on ANOTHER stream the caller waits for the earlier stream (htm_sync), as for any device
+ * buffer two streams use.  The export and import calls wait for the passed handle's stream only.
+ * The reset call: the streams whose byte is not 0 (NULL: all) go back to t = 0 with empty rings and no estimate; one launch, no wait.
+ * The export and import calls: the whole state to / from HOST memory of exactly htm_likelihood_state_bytes bytes, after a wait for
+ * h's stream.  Layout, n = n_streams: int64 t[n]; double mean[n]; double std[n]; int32 flag[n], padded to a multiple of 8 bytes;
+ * int32 q_ring[n][averaging_window]; int32 a_ring[n][history], padded to a multiple of 8 bytes.  Ring entry (step mod length)
+ * holds that step's value; entries not written since the last reset are 0.
+ * The scored tick: htm_live_tick with two further arguments, the object (n_streams = the group's size) and likelihood, HOST
+ * double[n]: member i's record of the tick is the next step of stream i.  One launch more than htm_live_tick (klik_tick, grid
+ * (1, n), behind the tick's finish launch), n doubles more in the one copy out, no further copy and no further wait;
+ * htm_live_tick is this call with both NULL.
+ *
+ * HTM_ERR_ARGUMENT, nothing enqueued: NULL pointers (a NULL record pointer of a stream included); a wrong struct_bytes; a
+ * parameter outside its range; n_streams < 1; n_steps < 0; a handle on another device; a state size that is not
+ * htm_likelihood_state_bytes or an imported t < 0; an object whose n_streams differs from the group's size; likelihood
+ * without the object or the object without likelihood.  HTM_ERR_STATE: a column-sharded handle. */
+typedef struct htm_likelihood htm_likelihood;
+typedef struct htm_likelihood_config {
+    uint32_t struct_bytes;
+    int32_t learning_period, estimation_samples, history, averaging_window, reestimation_period;
+} htm_likelihood_config;
+
+int htm_likelihood_create(htm_handle *h, const htm_likelihood_config *cfg, const double *tail_table513, int32_t n_streams, htm_likelihood **out);
+void htm_likelihood_destroy(htm_likelihood *lk);
+int htm_likelihood_update(htm_likelihood *lk, htm_handle *h, const htm_step_record *const *device_records, int32_t n_steps, double *device_out);
+int htm_likelihood_reset(htm_likelihood *lk, htm_handle *h, const uint8_t *streams);
+int64_t htm_likelihood_state_bytes(const htm_likelihood *lk);
+int htm_likelihood_export(htm_likelihood *lk, htm_handle *h, void *host_state, int64_t bytes);
+int htm_likelihood_import(htm_likelihood *lk, htm_handle *h, const void *host_state, int64_t bytes);
+int htm_likelihood_tick(htm_group *g, const double *values, const htm_scalar_field *fields, int32_t n_fields, const uint32_t *packed_inputs,
+                        const uint8_t *resets, int32_t learning, int32_t use_graph, htm_live_row *rows, int32_t *decoded, int32_t *votes,
+                        htm_likelihood *lk, double *likelihood);
+
 #ifdef __cplusplus
 }
 #endif
