@@ -122,6 +122,7 @@ EXPORTS = {
     "htm_shard_group_step": (C.c_int, [C.POINTER(C.c_void_p), C.c_int32, C.POINTER(C.c_void_p), C.c_int32, C.c_void_p, C.c_int32]),
     "htm_populate": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_uint32]),
     "htm_sync": (C.c_int, [C.c_void_p]),
+    "htm_sp_planes_check": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
     "htm_get_stream": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p)]),
     "htm_get_info": (C.c_int, [C.c_void_p, C.POINTER(HtmInfo)]),
     "htm_read": (C.c_int64, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64]),

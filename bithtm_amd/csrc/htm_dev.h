@@ -111,6 +111,7 @@ struct Counters {
     uint32_t sel_win_global;  // column-sharded handles: the same for the global select over the ranks' candidates (k_shard_select)
     u64 sel_pass_prefix[2][SEL_MAX_PASSES + 1];    // radix-select state entering pass p
     uint32_t sel_pass_krem[2][SEL_MAX_PASSES + 1];
+    uint32_t plane_steps;     // steps whose overlap was counted from the byte planes of the mask (role_overlap_planes; telemetry)
 };
 
 struct Dev {
@@ -139,6 +140,7 @@ struct Dev {
     // Spatial Pooler
     double *perm;             // [C][Ipad] float64 permanences (projections.py:16)
     uint32_t *mask;           // [C][W]    bit-packed `permanence >= threshold` (projections.py:19)
+                              // (and again by byte position: planes, at the end of the struct)
     float *duty;              // [C]
     int *overlap[2];          // [C]   parity double buffer, like the select state
     double *boosted[2];       // [C]
@@ -202,6 +204,11 @@ struct Dev {
     unsigned long long *trace;    // [8][4096][2] BITHTM_TRACE=1: device clock at the start / end of every block of the
                                   // pipelined launches (slot = launch + 4 * step parity), else null
     uint32_t trace_until;         // ... of steps with an index below this (BITHTM_TRACE_UNTIL; default: all)
+    // Spatial Pooler, again: the connected mask by byte position (behind everything else: the other fields stay where the kernels'
+    // argument loads have them)
+    int plane_stride;             // C rounded up to a multiple of 256 (the bytes behind C stay zero)
+    uint8_t *planes;              // [4 W][plane_stride] plane j holds, at byte c, byte j of column c's mask row -- a derived copy
+                                  // every writer of the mask keeps exact (k_sp_build_planes, plane_diff_store, plane_diff_store_late); null on sharded handles
 };
 
 // ------------------------------------------------------------------------------------------

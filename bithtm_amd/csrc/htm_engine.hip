@@ -79,6 +79,7 @@ struct Sizes {
     int G;                                // lanes per SP row
     int sp_blocks, sel_blocks, c256_blocks, s1024_blocks, scan_blocks, zero_blocks, cus;
     int lean_learn_blocks, lean_learn_blocks_large, lean_scan_blocks, lean_scan_blocks_large, lean_overlap_blocks, lean2_classify_blocks;
+    int lean2_overlap_blocks;             // blocks of k_act_mid_rows' overlap role: 256 columns each where it reads the byte planes (role_overlap_planes)
     int lean_resident_large;              // blocks of the large-pool k_learn_scan_emit that are resident at once
     bool emit_fits, emit_fits_open;       // the emit grid is resident at once in k_sp_emit / in k_open_emit, as far as this handle's own grids go
     bool emit_fits_lean;                  // ... and in k_learn_scan_emit
@@ -207,6 +208,7 @@ struct htm_handle {
     long long seen_wgen;
     uint32_t dense_step;                  // (the host word a view's counter block takes cm_dense_step from)
     int64_t own_bytes;                    // device bytes this handle allocated itself (htm_device_bytes)
+    unsigned long long *d_planes_bad;     // htm_sp_planes_check's count (allocated by its first call)
 };
 
 // The weights of a parent and its inference views (htm_create_view): freed, with the parent's own stream if it created one, when
@@ -588,9 +590,10 @@ static void enqueue_lean(htm_handle *h, int p, int learning, const uint32_t *ban
     const int n_cls = learning ? kClassifyBlocks : 0, n_ov = plan.next_sp ? h->sz.lean_overlap_blocks : 0;
     if (h->knob.lean == 2) {                        // the two-launch schedule: both of these in one (htm_pipeline.h)
         const int n_cls2 = lean2_classify_blocks(h, learning);
-        const int n_duty = n_ov ? 0 : h->sz.c256_blocks, n_clear = d.WPC * h->sz.c256_blocks;
+        const int n_ov2 = plan.next_sp ? h->sz.lean2_overlap_blocks : 0;
+        const int n_duty = n_ov2 ? 0 : h->sz.c256_blocks, n_clear = d.WPC * h->sz.c256_blocks;
         LAUNCH_ON(h, h->stream, (size_t)SEL_BINS * 4, "tm_activate+tm_mid+sp_learn+sp_overlap", k_act_mid_rows,
-                  n_act + 1 + n_cls2 + n_rows + n_ov + n_duty + n_clear + h->sz.zero_blocks, 256, d, p, d.k, n_act, learning, n_cls2, bank, n_inputs, n_rows, h->sz.G, n_ov,
+                  n_act + 1 + n_cls2 + n_rows + n_ov2 + n_duty + n_clear + h->sz.zero_blocks, 256, d, p, d.k, n_act, learning, n_cls2, bank, n_inputs, n_rows, h->sz.G, n_ov2,
                   n_duty, n_clear, h->knob.lean2_order);
     } else {
         LAUNCH(h, "tm_activate+sp_learn", k_act_rows, n_act + n_rows + (1 + d.WPC) * h->sz.c256_blocks, 256, d, p, d.k, n_act, bank, n_inputs, n_rows, h->sz.c256_blocks);
@@ -761,6 +764,11 @@ static int alloc_weights(htm_handle *h) {
     if (cfg->enable_sp) {
         rc |= dalloc_weights(h, &d.perm, C * d.Ipad);
         rc |= dalloc_weights(h, &d.mask, C * d.W);
+        // the mask again, by byte position (d.planes: the two-launch schedule's overlap reads the planes of the input's non-zero
+        // bytes only); zeroed like the mask, and a view aliases it like the mask.  A shard has none.
+        d.plane_stride = (d.C + 255) & ~255;
+        // (... whose mask words count in 32 bits: plane_diff_store_late takes a row's number from its address)
+        if (h->world == 1 && C * d.W < ((size_t)1 << 32)) rc |= dalloc_weights(h, &d.planes, (size_t)4 * d.W * d.plane_stride);
     }
     if (cfg->enable_tm) {
         const size_t S = d.Lcap, E = d.E, KP = d.KP;
@@ -939,6 +947,7 @@ static void size_launches(htm_handle *h) {
     // the three-launch schedule: waves of one 256-thread block per work item in the steady state; the scan's waves take
     // two groups of segments each, so that emit + learn + scan are all resident at once (tuning knobs)
     z.lean_overlap_blocks = k.lean_overlap ? k.lean_overlap : z.sp_blocks * (RB / 256);
+    z.lean2_overlap_blocks = d.planes ? (d.c1 - d.c0 + 255) / 256 : z.lean_overlap_blocks;
     z.lean_learn_blocks = k.lean_learn ? k.lean_learn : 512;
     z.lean_learn_blocks_large = k.lean_learn_large ? k.lean_learn_large : k.lean_learn ? z.lean_learn_blocks : 768;
     z.lean_scan_blocks = k.lean_scan ? k.lean_scan : (z.scan_blocks > 512 ? std::max(256, (z.scan_blocks * 3 / 8 + 255) & ~255) : z.scan_blocks);
@@ -996,6 +1005,10 @@ static void size_launches(htm_handle *h) {
             resident = per_cu * z.cus;
         else
             (void)hipGetLastError();
+        // (the overlap counted as the column-major role's blocks, also where the launch's own role reads the byte planes and takes
+        // half as many: the slots that role frees are not the classification's to fill -- its blocks poll the fan-in beside the
+        // rows.  Measured at the bench shape with the plane role, 316 free slots: 32 blocks 46.2 k timesteps/s, 64: 45.7, 128:
+        // 45.3, 312: 42.7 -- so every shape keeps the count it had)
         const int others = (d.k * d.KP + 255) / 256 + z.lean_overlap_blocks + d.k + 1;
         // (... but no more than 32 where they leave fewer than 128: measured at the bench shape, 60 free slots -- 32 blocks 42.4 k
         // timesteps/s, 40: 41.9, 56: 41.6)
@@ -1433,6 +1446,7 @@ extern "C" int htm_sp_set_permanence(htm_handle *h, const double *rows, int32_t 
     const long long waves = (long long)row_count * (d.Ipad / 64);
     const int blocks = (int)std::min<long long>((waves + 3) / 4, 8192);
     hipLaunchKernelGGL(k_sp_build_mask, dim3(blocks), dim3(256), 0, h->stream, d, row_begin, row_count);
+    if (d.planes) hipLaunchKernelGGL(k_sp_build_planes, dim3((row_count + 63) / 64, (4 * d.W + 63) / 64), dim3(256), 0, h->stream, d, row_begin, row_count);
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return HTM_OK;
 }
@@ -1448,6 +1462,31 @@ extern "C" int htm_sp_get_permanence(htm_handle *h, double *rows, int32_t row_be
     HIPCHK(h, hipMemcpy2DAsync(rows, (size_t)d.I * 8, d.perm + (size_t)row_begin * d.Ipad, (size_t)d.Ipad * 8,
                                (size_t)d.I * 8, (size_t)row_count, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
+    return HTM_OK;
+}
+
+// The byte planes of the connected mask against the mask itself, compared on the device, and how many steps counted their
+// overlap from the planes.
+extern "C" int htm_sp_planes_check(htm_handle *h, int64_t out[2]) {
+    if (!h || !out) return HTM_ERR_ARGUMENT;
+    flush_tail(h);
+    if (!h->cfg.enable_sp) { h->err = "handle has no Spatial Pooler"; return HTM_ERR_STATE; }
+    Dev &d = h->d;
+    HIPCHK(h, hipSetDevice(h->device));
+    uint32_t steps = 0;
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    HIPCHK(h, hipMemcpy(&steps, &d.ctr->plane_steps, sizeof(steps), hipMemcpyDeviceToHost));
+    out[0] = -1;
+    out[1] = (int64_t)steps;
+    if (!d.planes) return HTM_OK;
+    if (!h->d_planes_bad) { if (int rc = dalloc(h, &h->d_planes_bad, 1)) return rc; }
+    HIPCHK(h, hipMemsetAsync(h->d_planes_bad, 0, sizeof(unsigned long long), h->stream));
+    const size_t total = (size_t)4 * d.W * d.plane_stride;
+    hipLaunchKernelGGL(k_sp_planes_check, dim3((unsigned)std::min<size_t>((total + 255) / 256, 4096)), dim3(256), 0, h->stream, d, h->d_planes_bad);
+    unsigned long long bad = 0;
+    HIPCHK(h, hipMemcpyAsync(&bad, h->d_planes_bad, sizeof(bad), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    out[0] = (int64_t)bad;
     return HTM_OK;
 }
 

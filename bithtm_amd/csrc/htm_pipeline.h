@@ -154,7 +154,7 @@ __global__ __launch_bounds__(256, 8) void k_act_rows(Dev d, int p, int n_active,
     }
     b -= n_act_blocks;
     if (b < n_rows) {
-        role_sp_row<256>(d, p, bank, n_inputs, 0, b, threadIdx.x);
+        role_sp_row<256, false, false>(d, p, bank, n_inputs, 0, b, threadIdx.x);     // (the planes: the late form)
         return;
     }
     b -= n_rows;
@@ -207,7 +207,7 @@ __global__ __launch_bounds__(256) void k_mid_overlap(Dev d, int p, int n_active,
 //
 // Two dependencies used to need the boundary between the two launches.  (1) overlap(t+1) reads the permanence masks rows(t)
 // rewrites: only the k winner rows change, and their blocks hold the new connected bits in registers -- they count them against
-// the coming input themselves (role_sp_row OWN), the overlap role passes over the winners (role_overlap fold = 2) and takes
+// the coming input themselves (role_sp_row OWN), the overlap role passes over the winners (role_overlap_planes, fold = 2) and takes
 // the duty-cycle update along (a column's duty cycle is read and written by the one block that finishes the column).
 // (2) mid(t) reads what activate(t) writes: the activation blocks store through to memory, wait for the acknowledgement and
 // count themselves done on one of 16 counters; the middle role's blocks -- behind them in the grid, so every activation
@@ -216,8 +216,8 @@ __global__ __launch_bounds__(256) void k_mid_overlap(Dev d, int p, int n_active,
 // In place the hand-off costs about 2 us (acknowledgement, atomic, poll: three trips to memory under the launch's traffic;
 // tools/fanin.hip measured 1.1-1.5 us on an idle device) -- what a launch boundary costs: the gain of the schedule is that the
 // winner rows and the overlap now stream UNDER the chain activate -> mid instead of before and after it.
-// All of the launch's blocks are resident at once at the bench shape (activation 164 + overlap 512 + middle 33 + rows 1 311 =
-// 2 020 of the 2 048 slots 64 registers leave); nothing but the middle role waits for another block, so the order of the grid
+// All of the launch's blocks are resident at once at the bench shape (activation 164 + overlap 256 + middle 33 + rows 1 311 =
+// 1 764 of the 2 048 slots 64 registers leave; the overlap role, role_overlap_planes, takes one block per 256 columns); nothing but the middle role waits for another block, so the order of the grid
 // is only a matter of speed.  The counters are reset by k_learn_scan_emit, which always follows.
 __device__ __forceinline__ void fan_signal(const Dev &d, int p, int b) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                // (the write-through stores are acknowledged)
@@ -284,7 +284,10 @@ __global__ __launch_bounds__(256, BITHTM_LEAN2_WAVES) void k_act_mid_rows(Dev d,
         return;
     }
     if (role == 3) {
-        role_overlap<256>(d, bank, n_inputs, G, p, p ^ 1, 1, b, n_overlap_blocks, (uint32_t *)dyn_lds, 1, n_rows > 0 ? 2 : 1);
+        // (from the byte planes of the mask where the handle keeps them -- every handle that takes this launch with an overlap role
+        // does: the host sizes n_overlap_blocks for the role it will get)
+        if (d.planes) role_overlap_planes(d, bank, n_inputs, p, p ^ 1, 1, b, n_overlap_blocks, (uint32_t *)dyn_lds, n_rows > 0 ? 2 : 1);
+        else role_overlap<256>(d, bank, n_inputs, G, p, p ^ 1, 1, b, n_overlap_blocks, (uint32_t *)dyn_lds, 1, n_rows > 0 ? 2 : 1);
         return;
     }
     if (b < n_duty_blocks) {

@@ -23,6 +23,76 @@ __global__ __launch_bounds__(256) void k_sp_build_mask(Dev d, int row_begin, int
     }
 }
 
+// ... and the byte planes of those rows (d.planes), right behind it: block (x, y) transposes the 64 columns from
+// row_begin + 64 x and the mask bytes from 64 y through LDS.  Not on the hot path (htm_sp_set_permanence).
+__global__ __launch_bounds__(256) void k_sp_build_planes(Dev d, int row_begin, int row_count) {
+    __shared__ uint8_t tile[64][68];               // [column][byte], rows 17 words apart
+    const int c0 = row_begin + (int)blockIdx.x * 64, c_end = row_begin + row_count;
+    const int w0 = (int)blockIdx.y * 16;            // first mask word of the tile
+    for (int i = threadIdx.x; i < 64 * 16; i += 256) {
+        const int c = c0 + (i >> 4), w = w0 + (i & 15);
+        const uint32_t v = (c < c_end && w < d.W) ? d.mask[(size_t)c * d.W + w] : 0u;
+        *(uint32_t *)&tile[i >> 4][(i & 15) * 4] = v;
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i < 64 * 64; i += 256) {
+        const int c = c0 + (i & 63), j = w0 * 4 + (i >> 6);
+        if (c < c_end && j < 4 * d.W) d.planes[(size_t)j * d.plane_stride + c] = tile[i & 63][i >> 6];
+    }
+}
+
+// the invariant of the planes, checked: *bad += the plane bytes that differ from the mask's (htm_sp_planes_check; the bytes
+// behind column C included, which stay zero)
+__global__ __launch_bounds__(256) void k_sp_planes_check(Dev d, unsigned long long *bad) {
+    unsigned long long n = 0;
+    const size_t total = (size_t)4 * d.W * d.plane_stride;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
+        const int j = (int)(i / d.plane_stride), c = (int)(i % d.plane_stride);
+        const uint8_t want = c < d.C ? ((const uint8_t *)(d.mask + (size_t)c * d.W))[j] : (uint8_t)0;
+        n += d.planes[i] != want;
+    }
+    n = wave_reduce64(n, 0ull, [](u64 a, u64 b) { return a + b; });
+    if (lane_id() == 0 && n) atomicAdd(bad, n);
+}
+
+// What a wave that has just rebuilt NB consecutive bytes of a winner row's mask (NB = 8 or 16: the words m0, m1 the whole
+// wave holds, wave-uniform) owes the byte planes: lane j < NB compares its new byte with the row's old one -- `old`, fetched
+// from the mask row BEFORE the pass's store, by an unconditional clamped load (plane_old_byte) issued with the pass's row loads
+// -- and stores it to its plane only where it differs: a learned row changes zero to a few bytes.  A plain byte store: the
+// planes are read behind a kernel boundary only, and a byte store leaves the bytes of the neighbouring columns alone (the
+// overlap role of the same launch reads them, and drops this column's count).
+__device__ __forceinline__ uint32_t plane_old_byte(const Dev &d, const uint32_t *mrow, int byte0) {
+    return ((const uint8_t *)mrow)[min(byte0 + (lane_id() & 15), 4 * d.W - 1)];
+}
+template <int NB>
+__device__ __forceinline__ void plane_diff_store(const Dev &d, int row, int byte0, bool valid, u64 m0, u64 m1, uint32_t old) {
+    const int j = lane_id();
+    const uint32_t nb = (uint32_t)(((j & 8) ? m1 : m0) >> (8 * (j & 7))) & 0xFFu;
+    if (d.planes && valid && j < NB && nb != old) d.planes[(size_t)(byte0 + j) * d.plane_stride + row] = (uint8_t)nb;
+}
+// The same for the row kernels off the hot path (k_sp_learn, k_sp_run_tail, the three-launch schedule's k_act_rows): the old
+// bytes are fetched here, behind the pass's work and BEFORE the wave's store of the new mask words -- the caller stores those
+// behind this call -- so nothing of it is live beside the pass's values: a round trip per pass on handles with planes, no
+// register more for the kernel.
+// i0: the pass's first element (the wave's NB bytes start at byte (i0 >> 3) + NB * its number in the block).
+// ROW_FROM_MROW: the row's number is taken from its mask row's address, and only where a byte is stored (k_sp_run_tail, whose
+// row lives in a vector register that is dead by then: a handle keeps planes only where the mask's words count in 32 bits).
+template <int NB, bool ROW_FROM_MROW = false>
+__device__ __forceinline__ void plane_diff_store_late(const Dev &d, const uint32_t *mrow, int row, int i0, u64 m0, u64 m1) {
+    if (!d.planes) return;
+    int t = (int)threadIdx.x;
+    asm volatile("" : "+v"(t));                     // (nothing of this is computed ahead of the loop and kept in registers across it)
+    const int j = t & 63, byte0 = (i0 >> 3) + NB * (t >> 6);
+    if (byte0 * 8 < d.Ipad && j < NB) {
+        const uint32_t old = ((const uint8_t *)mrow)[byte0 + j];
+        const uint32_t nb = (uint32_t)(((j & 8) ? m1 : m0) >> (8 * (j & 7))) & 0xFFu;
+        if (nb != old) {
+            if (ROW_FROM_MROW) row = (int)((uint32_t)(mrow - d.mask) / (uint32_t)d.W);
+            d.planes[(size_t)(byte0 + j) * d.plane_stride + row] = (uint8_t)nb;
+        }
+    }
+}
+
 // DenseProjection.process (projections.py:18-21) + ExponentialBoosting.process
 // (regularizations.py:15-17).  G lanes share one row (G = power of two, W4 16-byte chunks per row).
 // Sharded handles run it on their own rows only: the select that follows picks their own candidates.
@@ -36,6 +106,62 @@ __global__ __launch_bounds__(256) void k_sp_build_mask(Dev d, int row_begin, int
 #else
 #define OV_STAMP(i) do { } while (0)
 #endif
+// one row's share of the step, given its overlap count cn (projections.py:18-21): boosted overlap (regularizations.py:15-17),
+// key, bin of the block's LDS histogram h (hc: the runs' sums, window mode).  Both overlap roles (role_overlap, the column-major
+// mask rows; role_overlap_planes, the byte planes) end in this: the same expressions, order and roundings.
+__device__ __forceinline__ void overlap_finish_row(const Dev &d, int sp, int wmode, int fold, uint32_t wbase, uint32_t *h, uint32_t *hc,
+                                                   bool owner, int row, int cn, float duty, uint32_t cbw) {
+    u64 key = 0;
+    if (owner && fold) {                       // step p's duty cycle first: float32, two separately rounded operations
+        duty = duty * d.mom;
+        if ((cbw >> (row & 31)) & 1u) {
+            if (fold == 2) owner = false;
+            else duty = duty + d.dinc;
+        }
+        if (owner) d.duty[row] = duty;
+    }
+    if (owner) {
+        d.overlap[sp][row] = cn;
+        const float f = htm_exp_f32(d.coef * duty);                // float32 product, documented exp
+        const double bo = (double)f * (double)cn;                  // exact (24-bit x <= 16-bit)
+        d.boosted[sp][row] = bo;
+        key = select_key(bo);
+        d.key[sp][row] = key;
+    }
+    // (plain LDS atomics: hist_add's loop over the distinct digits, a dependent shuffle + ballot + atomic each, cost
+    // 0.3 us per call here)
+    // (the windowed histogram leaves out the bin below the window, where most columns are: the select counts from the
+    // top and never gets there -- if it would, the k-th key is outside the window and the exact fallback takes over)
+    const uint32_t bin = wmode ? win_bin(key, wbase) : (uint32_t)(key >> sel_shift(0));
+    if (owner && (!wmode || bin != 0u)) {
+        atomicAdd(&h[bin], 1u);
+        if (wmode) atomicAdd(&hc[bin >> 6], 1u);
+    }
+}
+
+// the end of role_overlap_planes, as role_overlap ends (there in place: that role's kernels keep the registers they had): the
+// block's LDS histogram into the copies of the select's (window mode: its bins, and the runs' sums counted beside them in the
+// words the window never uses: bins >= WIN_BINS)
+template <int BS>
+__device__ __forceinline__ void overlap_flush_hist(const Dev &d, int sp, int blk, int wmode, const uint32_t *h) {
+    const uint32_t *hc = h + SEL_BINS - SEL_COARSE;
+    uint32_t *g0 = d.hist0 + (size_t)sp * HIST0_PAR + (size_t)(blk & (HIST_REP - 1)) * SEL_BINS;
+    uint32_t *gc = d.hist0 + (size_t)sp * HIST0_PAR + HIST0_FINE + (size_t)(blk & (COARSE_REP - 1)) * COARSE_STRIDE;
+    const int n_fine = wmode ? SEL_BINS - SEL_COARSE : SEL_BINS;
+    {   // (the block's bins first, all of them at once, then the atomics of those that hold anything: one LDS round trip)
+        constexpr int PER = SEL_BINS / BS;
+        uint32_t v[PER];
+#pragma unroll
+        for (int k = 0; k < PER; ++k) v[k] = h[threadIdx.x + k * BS];
+#pragma unroll
+        for (int k = 0; k < PER; ++k) {
+            const int i = threadIdx.x + k * BS;
+            if (v[k] && i < n_fine) atomicAdd(&g0[i], v[k]);
+        }
+    }
+    if (wmode && threadIdx.x < SEL_COARSE && hc[threadIdx.x]) atomicAdd(&gc[threadIdx.x], hc[threadIdx.x]);
+}
+
 template <int BS>
 // wmode: the histogram of the windowed select (win_bin) instead of the top key digit
 // fold (two-launch schedule, k_act_mid_rows: the overlap of step p's successor in the launch that updates step p's permanence
@@ -92,32 +218,7 @@ __device__ __forceinline__ void role_overlap(const Dev &d, const uint32_t *__res
     uint32_t *hc = h + SEL_BINS - SEL_COARSE;       // (window mode only)
     // one row's share of the step: overlap (projections.py:18-21), boosted overlap (regularizations.py:15-17), key, bin
     auto finish_row = [&](bool owner, int row, int cn, float duty, uint32_t cbw) {
-        u64 key = 0;
-        if (owner && fold) {                       // step p's duty cycle first: float32, two separately rounded operations
-            duty = duty * d.mom;
-            if ((cbw >> (row & 31)) & 1u) {
-                if (fold == 2) owner = false;
-                else duty = duty + d.dinc;
-            }
-            if (owner) d.duty[row] = duty;
-        }
-        if (owner) {
-            d.overlap[sp][row] = cn;
-            const float f = htm_exp_f32(d.coef * duty);                // float32 product, documented exp
-            const double bo = (double)f * (double)cn;                  // exact (24-bit x <= 16-bit)
-            d.boosted[sp][row] = bo;
-            key = select_key(bo);
-            d.key[sp][row] = key;
-        }
-        // (plain LDS atomics: hist_add's loop over the distinct digits, a dependent shuffle + ballot + atomic each, cost
-        // 0.3 us per call here)
-        // (the windowed histogram leaves out the bin below the window, where most columns are: the select counts from the
-        // top and never gets there -- if it would, the k-th key is outside the window and the exact fallback takes over)
-        const uint32_t bin = wmode ? win_bin(key, wbase) : (uint32_t)(key >> sel_shift(0));
-        if (owner && (!wmode || bin != 0u)) {
-            atomicAdd(&h[bin], 1u);
-            if (wmode) atomicAdd(&hc[bin >> 6], 1u);
-        }
+        overlap_finish_row(d, sp, wmode, fold, wbase, h, hc, owner, row, cn, duty, cbw);
     };
     for (int row0 = first_row0; row0 < d.c1; row0 += nwaves * rpw * U) {
         const bool first = row0 == first_row0;
@@ -185,6 +286,90 @@ __device__ __forceinline__ void role_overlap(const Dev &d, const uint32_t *__res
     // the runs' sums were counted beside the bins (in the words of the LDS histogram the window never uses: bins >= WIN_BINS)
     if (wmode && threadIdx.x < SEL_COARSE && hc[threadIdx.x]) atomicAdd(&gc[threadIdx.x], hc[threadIdx.x]);
     OV_STAMP(5);
+}
+
+// The overlap role of the two-launch schedule's first launch (k_act_mid_rows) from the byte planes of the mask (d.planes):
+// what role_overlap(..., wmode = 1, fold) leaves, reading only the planes of the coming input's NON-ZERO bytes -- an SDR
+// of 25 bits in 1 024 touches 25 of the 128 planes, 1.6 MB of the mask's 8.4 at the bench shape.
+// Block blk takes columns [256 blk, 256 blk + 256).  The input row's non-zero bytes are compacted into an LDS list of
+// (plane | value << 16); the block's 4 waves share the list's entries, each wave loading, per entry, the plane's 256 bytes of the
+// block's columns (4 columns to a lane, one coalesced 256-byte load, 8 loads in flight, unguarded: a spare slot reads plane 0
+// against the value 0) and counting, per column, popc(word & value << 8 i).  The waves' counts meet in LDS and thread t
+// finishes column 256 blk + t: overlap_finish_row, the expressions of role_overlap.
+// h: SEL_BINS words of LDS -- the list and the waves' counts first, the block's histogram once they are read out.
+// The planes of step p's winner rows are being rewritten in this launch, byte by byte (plane_diff_store); fold == 2 drops
+// those columns' counts, and a byte store leaves the other bytes of the word alone.
+__device__ __forceinline__ void role_overlap_planes(const Dev &d, const uint32_t *__restrict__ bank, int n_inputs, int p, int sp, int step_offset,
+                                                    int blk, int nblk, uint32_t *h, int fold) {
+    constexpr int BS = 256, PB = 8;                // PB: plane loads in flight per wave
+    const int t = threadIdx.x, lane = lane_id(), wv = t >> 6;
+    const int gtid = blk * BS + t, nthreads = nblk * BS;
+    uint32_t *ghist = d.hist + sp * SEL_MAX_PASSES * SEL_BINS;
+    // the column this thread finishes: its duty cycle and bitmap word are asked for before anything is waited for
+    const int row = d.c0 + blk * BS + t;
+    const bool owner = row < d.c1;
+    const int rowc = owner ? row : d.c1 - 1;
+    const float dty = d.duty[rowc];
+    const uint32_t cbw = fold ? d.colbits[p][rowc >> 5] : 0u;
+    if (gtid == 0) {
+        d.ctr->emit_epoch += 1;                     // a new generation of k_sp_emit records
+        d.ctr->plane_steps += 1;
+        d.ctr->sel_pass_prefix[sp][0] = 0;
+        d.ctr->sel_pass_krem[sp][0] = (uint32_t)d.sel_k;
+    }
+    for (int i = gtid; i < (d.sel_passes - 1) * SEL_BINS; i += nthreads) ghist[SEL_BINS + i] = 0;
+    const uint32_t wbase = d.ctr->sel_win[sp];
+    const uint32_t *in = bank;
+    if (n_inputs > 1) in = bank + (size_t)((d.ctr->step[p] + (uint32_t)step_offset) % (uint32_t)n_inputs) * d.W;
+    uint32_t *list = h, *s_n = h + 256;             // up to 256 entries of a chunk; the waves' entry counts
+    uint32_t *s_cnt = h + 512;                      // [4 waves][64 lanes][4 columns]
+    const uint8_t *pl = d.planes + (size_t)(d.c0 + blk * BS + 4 * lane);
+    int cnt[4] = {0, 0, 0, 0};
+    // 256 bytes of the input row at a time (inputs of up to 2 048 bits: once): thread t looks at byte t of them
+    for (int b0 = 0; b0 < 4 * d.W; b0 += BS) {
+        const int bi = b0 + t;
+        const uint32_t byte = bi < 4 * d.W ? (in[bi >> 2] >> (8 * (bi & 3))) & 0xFFu : 0u;
+        const u64 live = __ballot(byte != 0u);
+        if (lane == 0) s_n[wv] = (uint32_t)__popcll(live);
+        lds_barrier();
+        uint32_t pos = (uint32_t)__popcll(live & lanemask_lt()), n = 0;
+#pragma unroll
+        for (int w = 0; w < BS / 64; ++w) {
+            const uint32_t nw = s_n[w];
+            if (w < wv) pos += nw;
+            n += nw;
+        }
+        if (byte != 0u) list[pos] = (uint32_t)bi | (byte << 16);
+        lds_barrier();
+        for (uint32_t e0 = (uint32_t)wv; e0 < n; e0 += (BS / 64) * PB) {
+            uint32_t ent[PB], word[PB];
+#pragma unroll
+            for (int u = 0; u < PB; ++u) {
+                const uint32_t e = e0 + (uint32_t)u * (BS / 64);
+                ent[u] = e < n ? list[e] : 0u;
+            }
+#pragma unroll
+            for (int u = 0; u < PB; ++u) word[u] = *(const uint32_t *)(pl + (size_t)(ent[u] & 0xFFFFu) * d.plane_stride);
+#pragma unroll
+            for (int u = 0; u < PB; ++u) {
+                const uint32_t v = ent[u] >> 16;
+#pragma unroll
+                for (int i = 0; i < 4; ++i) cnt[i] += __popc(word[u] & (v << (8 * i)));
+            }
+        }
+        lds_barrier();                              // (the next chunk rewrites the list)
+    }
+    *(uint4 *)&s_cnt[(wv * 64 + lane) * 4] = make_uint4((uint32_t)cnt[0], (uint32_t)cnt[1], (uint32_t)cnt[2], (uint32_t)cnt[3]);
+    lds_barrier();
+    int cn = 0;
+#pragma unroll
+    for (int w = 0; w < BS / 64; ++w) cn += (int)s_cnt[(w * 64 + (t >> 2)) * 4 + (t & 3)];
+    lds_barrier();
+    for (int i = t; i < SEL_BINS; i += BS) h[i] = 0;
+    lds_barrier();
+    overlap_finish_row(d, sp, 1, fold, wbase, h, h + SEL_BINS - SEL_COARSE, owner, row, cn, dty, cbw);
+    lds_barrier();                                  // (LDS only: the flush does not wait for the stores of the keys)
+    overlap_flush_hist<BS>(d, sp, blk, 1, h);
 }
 
 __global__ __launch_bounds__(RB) void k_sp_overlap(Dev d, const uint32_t *__restrict__ bank, int n_inputs, int G, int p, int sp, int step_offset, int wmode) {
@@ -1341,6 +1526,7 @@ __global__ __launch_bounds__(256) void k_sp_emit(Dev d, int p, int want_winner, 
 // DenseProjection.update (projections.py:23-24) on the k winner rows, fused with the rebuild
 // of those rows' connected mask.  One block of 256 threads per winner row: block `b` takes the b-th winner of the step of
 // parity p.  (A role: k_sp_learn and the tail launch of a batched stand-alone run, htm_sp_run.h, both call it.)
+template <bool ROW_FROM_MROW = false>
 __device__ __forceinline__ void role_sp_learn_row(const Dev &d, const uint32_t *__restrict__ bank, int n_inputs, int p, int b) {
     const uint32_t *in = bank + (size_t)(d.ctr->step[p] % (uint32_t)n_inputs) * d.W;
     const int row = d.active_cols[p][b];
@@ -1356,6 +1542,7 @@ __device__ __forceinline__ void role_sp_learn_row(const Dev &d, const uint32_t *
             conn = v >= d.sp_thr;
         }
         u64 m = __ballot(conn);
+        plane_diff_store_late<8, ROW_FROM_MROW>(d, mrow, ROW_FROM_MROW ? 0 : row, i0, m, 0ull);
         if (lane_id() == 0 && i < d.Ipad) *(u64 *)&mrow[i >> 5] = m;
     }
 }

@@ -39,7 +39,7 @@ __global__ void k_sp_run_begin(SpRecDev *r, int32_t *cols, int32_t *overlap, dou
 __global__ __launch_bounds__(256) void k_sp_run_tail(Dev d, const uint32_t *__restrict__ bank, int n_inputs, int p, int n_learn, const SpRecDev *__restrict__ r) {
     const int b = (int)blockIdx.x;
     if (b < n_learn) {
-        role_sp_learn_row(d, bank, n_inputs, p, b);
+        role_sp_learn_row<true>(d, bank, n_inputs, p, b);
         return;
     }
     const int i = (b - n_learn) * 256 + (int)threadIdx.x;

@@ -184,7 +184,10 @@ __device__ __forceinline__ void shard_bind(const Dev &d, int p, int gid, int cel
 // (regularizations.py:19-21: this column won), the overlap of the NEW connected bits with the coming step's input
 // (projections.py:18-21), boosted overlap and key (regularizations.py:15-17), the key's bin of the select histogram.  The new
 // mask words are in the ballots of the pass: no other block has to wait for them.
-template <int TPR, bool OWN = false>
+// PLANES: how the wave keeps the row's bytes of the mask's byte planes.  true: the old bytes travel with the pass's row loads
+// (plane_old_byte, plane_diff_store).  false: they are fetched behind the pass's work (plane_diff_store_late: a round trip per
+// pass, no register more) -- k_act_rows: the three-launch schedule does not read the planes, and keeps its registers
+template <int TPR, bool OWN = false, bool PLANES = true>
 __device__ __forceinline__ void role_sp_row(const Dev &d, int p, const uint32_t *__restrict__ bank, int n_inputs, int ahead, int ri, int t) {
     ROW_STAMP(0);
     const uint32_t step = ahead ? d.ctr->step[p ^ 1] + 1u : d.ctr->step[p];
@@ -205,7 +208,12 @@ __device__ __forceinline__ void role_sp_row(const Dev &d, int p, const uint32_t 
     for (int i0 = 0; i0 < d.Ipad; i0 += 2 * TPR) {
         const int e0 = i0 + 2 * t;                   // Ipad is a multiple of 128: e0 + 1 < Ipad whenever e0 < Ipad
         bool c0 = false, c1 = false;
+        const int base = i0 + 2 * (t & ~63);         // the wave's 128 elements of the pass: 16 bytes of the mask row
+        uint32_t old = 0u;
         if (e0 < d.Ipad) {
+            // (byte planes: the row's bytes as they were, lanes < 16 -- asked for in front of the pass's row loads, on the same
+            // branch, unguarded and clamped; the wait for the row's values covers it)
+            if (PLANES) old = plane_old_byte(d, mrow, base >> 3);
             // (one pass at a time on purpose: with the second pass's loads in flight beside the first's the first pass waits
             // 2.9 us instead of 1.8 and the launch is a microsecond longer -- 1 311 scattered 8-KB rows read at 3-3.7 TB/s
             // whatever is asked at once: tools/rows_phases.py; again in the two-launch schedule's first launch: 43.65 against 43.85 k
@@ -226,17 +234,31 @@ __device__ __forceinline__ void role_sp_row(const Dev &d, int p, const uint32_t 
                 union { double2 d2; u32x4 u4; } cvt;
                 cvt.d2 = v;
                 double *dst = prow + e0;
+                // (the old bytes are in their register BEFORE the store the compiler cannot see: a wait for them placed behind it
+                // would wait for the write-through store's acknowledgement too -- vmcnt counts in order -- a round trip per pass)
+                if (PLANES) asm volatile("" : "+v"(old));
                 asm volatile("global_store_dwordx4 %0, %1, off sc0 sc1\n\ts_nop 1" ::"v"(dst), "v"(cvt.u4) : "memory");
             }
         }
         const u64 b0 = __ballot(c0), b1 = __ballot(c1);
-        const int base = i0 + 2 * (t & ~63);
-        if (lane_id() == 0 && base < d.Ipad) {
-            u64 *mw = (u64 *)&mrow[base >> 5];
+        if (PLANES) {
             const u64 m0 = spread32((uint32_t)b0) | (spread32((uint32_t)b1) << 1);
             const u64 m1 = spread32((uint32_t)(b0 >> 32)) | (spread32((uint32_t)(b1 >> 32)) << 1);
-            mw[0] = m0;
-            mw[1] = m1;
+            if (lane_id() == 0 && base < d.Ipad) {
+                u64 *mw = (u64 *)&mrow[base >> 5];
+                mw[0] = m0;
+                mw[1] = m1;
+            }
+            plane_diff_store<16>(d, row, base >> 3, base < d.Ipad, m0, m1, old);
+        } else {
+            const u64 m0 = spread32((uint32_t)b0) | (spread32((uint32_t)b1) << 1);
+            const u64 m1 = spread32((uint32_t)(b0 >> 32)) | (spread32((uint32_t)(b1 >> 32)) << 1);
+            plane_diff_store_late<16>(d, mrow, row, i0, m0, m1);
+            if (lane_id() == 0 && base < d.Ipad) {
+                u64 *mw = (u64 *)&mrow[base >> 5];
+                mw[0] = m0;
+                mw[1] = m1;
+            }
         }
         if (i0 == 0) ROW_STAMP(3); else ROW_STAMP(5);
     }

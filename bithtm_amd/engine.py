@@ -283,6 +283,13 @@ class Engine:
     def sync(self):
         self._check(self.lib.htm_sync(self.h), "htm_sync")
 
+    def planes_check(self):
+        """(mismatches, plane_steps): the bytes of the mask's byte planes that differ from the connected mask, compared on the
+        device (-1: the handle keeps no planes -- a shard), and the steps so far whose overlap was counted from the planes."""
+        out = (C.c_int64 * 2)()
+        self._check(self.lib.htm_sp_planes_check(self.h, out), "htm_sp_planes_check")
+        return int(out[0]), int(out[1])
+
     def stream_handle(self):
         """The hipStream_t this engine enqueues on (an integer; 0 = the default stream)."""
         out = C.c_void_p()

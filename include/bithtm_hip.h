@@ -168,6 +168,12 @@ int htm_sp_set_permanence(htm_handle *h, const double *rows, int32_t row_begin, 
  * prediction > epsilon, max potential < epsilon -- then mean what they mean at 1e-8); stays until set again. */
 int htm_set_epsilon(htm_handle *h, float epsilon);
 int htm_sp_get_permanence(htm_handle *h, double *rows, int32_t row_begin, int32_t row_count);
+/* Unsharded handles with a Spatial Pooler keep a second copy of the connected mask, by byte position ("byte planes": plane j
+ * holds byte j of every column's mask row), from which the two-launch schedule of htm_run counts the overlap of an input's
+ * non-zero bytes only; an inference view shares its parent's.  Every kernel that writes the mask keeps the planes exact.  This
+ * is the check of that: out[0] = the plane bytes that differ from the mask's, compared on the device (0 when all is well; -1 on
+ * a handle without planes: a shard), out[1] = the steps so far whose overlap was counted from the planes.  Synchronises. */
+int htm_sp_planes_check(htm_handle *h, int64_t out[2]);
 
 /* One timestep, enqueued asynchronously.  packed_input: input bit i is bit (i & 31) of word
  * (i >> 5); ceil(input_dim / 32) host words.

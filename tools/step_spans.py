@@ -27,7 +27,8 @@ def main():
     c256, n_learn = (w["column_dim"] + 255) // 256, int(os.environ.get("BITHTM_LEAN_LEARN", 512))
     two = os.environ.get("BITHTM_LEAN", "2") == "2"
     k = round(w["column_dim"] * 0.02)
-    n_act, n_ov, n_cls = (k * 32 + 255) // 256, int(os.environ.get("BITHTM_LEAN_OVERLAP", 512)), int(os.environ.get("BITHTM_LEAN2_CLASSIFY", 32))
+    # (the first launch's overlap role counts from the mask's byte planes: 256 columns per block)
+    n_act, n_ov, n_cls = (k * 32 + 255) // 256, c256, int(os.environ.get("BITHTM_LEAN2_CLASSIFY", 32))
     first_roles, at = [], 0                          # (k_act_mid_rows' roles in the grid's order)
     for digit in os.environ.get("BITHTM_LEAN2_ORDER", "0312"):
         n = {"0": n_act, "1": 1 + n_cls, "2": k, "3": n_ov}[digit]

@@ -34,7 +34,8 @@ def roles(launch, k, C):
         n_ov = int(os.environ.get("BITHTM_LEAN_OVERLAP", 512))
         if launch == 0 and TWO:      # two launches per step: k_act_mid_rows, its roles in the grid's order
             m = int(os.environ.get("BITHTM_LEAN2_CLASSIFY", 192 if os.environ.get("TIMELINE_WORKLOAD") == "large" else 32))
-            sizes = {"0": (("tm_activate", n_act),), "1": (("tm_mid block 0", 1), ("tm_mid classify", m)), "2": (("sp rows", k),), "3": (("sp_overlap", n_ov),)}
+            # (this launch's overlap role counts from the mask's byte planes: 256 columns per block, whatever BITHTM_LEAN_OVERLAP says)
+            sizes = {"0": (("tm_activate", n_act),), "1": (("tm_mid block 0", 1), ("tm_mid classify", m)), "2": (("sp rows", k),), "3": (("sp_overlap", c256),)}
             out, at = [], 0
             for digit in os.environ.get("BITHTM_LEAN2_ORDER", "0312"):
                 for name, n in sizes[digit]:
