@@ -373,6 +373,10 @@ static size_t scan_lds_tab(const Dev &d) {
 // ... which needs them to fit (and the ranks 16 bits); otherwise the schedule's scan reads the cell words from memory
 static bool lean_tab(const Dev &d) { return scan_lds_tab(d) <= 64 * 1024 && d.k * d.WPC < 65536; }
 static size_t lean_scan_lds(const Dev &d) { return lean_tab(d) ? scan_lds_tab(d) : scan_lds(d, 1); }
+// the scan's column bitmap fits the LDS
+static bool bitmap_fits_lds(const Dev &d) { return scan_lds(d, 1) <= 64 * 1024; }
+// activation blocks of a step: one active column per lane group of a 256-thread block (role_activate)
+static int act_blocks(const Dev &d) { return (d.k * d.KP + 255) / 256; }
 static const int kClassifyBlocks = 384;           // x 256 segments per pass of the learn / punish classification
 static const int kLearnBlocks = 256;               // x RB/64 waves: one wave per learning / punished segment
 
@@ -417,21 +421,35 @@ static void launch_scan(htm_handle *h, int p, int use_lds) {
 // (and only once a select has left a window behind: the first step of a handle, or after a state import, takes the digits)
 static int step_wmode(const htm_handle *h) { return h->emit_fused && h->knob.step_window && h->world == 1 && h->window_known ? 1 : 0; }
 
+// a host-fed step's packed input as a launch argument (where it fits: d.W <= ARG_INPUT_WORDS)
+static PackedInputArg packed_input_arg(const Dev &d, const uint32_t *host_input) {
+    PackedInputArg in;
+    memset(&in, 0, sizeof(in));
+    memcpy(in.w, host_input, (size_t)((d.I + 31) / 32) * 4);
+    return in;
+}
+
+// the select digits behind the top one, a launch each (d: the handle's descriptor, or a copy with more digits: htm_sp_phase)
+static void launch_sel_passes(htm_handle *h, const Dev &d, int p) {
+    for (int pass = 1; pass < d.sel_passes; ++pass) LAUNCH(h, "sp_select", k_sel_pass, h->sz.sel_blocks, RB, d, pass, p);
+}
+
+// the top-digit histogram of parity p starts clean again: its overlap was computed and no select will consume (and clear) it
+static hipError_t clear_front_hist(htm_handle *h, int p) {
+    return hipMemsetAsync(h->d.hist0 + (size_t)p * HIST0_PAR, 0, (size_t)HIST0_PAR * 4, h->stream);
+}
+
 // Front of SpatialPooler.process for the step with parity sp: overlap + boost + histogram (the windowed one, or the top
 // key digit and then the remaining select digits).  host_input: the packed input of a host-fed step (it rides in the
 // launch's arguments where it fits); else the bank in device memory.
 static void enqueue_sp_front(htm_handle *h, const uint32_t *bank, int n_inputs, int p, int wmode, const uint32_t *host_input = nullptr) {
     Dev &d = h->d;
     if (host_input && d.W <= ARG_INPUT_WORDS) {
-        PackedInputArg in;
-        memset(&in, 0, sizeof(in));
-        memcpy(in.w, host_input, (size_t)((d.I + 31) / 32) * 4);
-        LAUNCH(h, "sp_overlap", k_sp_overlap_arg, h->sz.sp_blocks, RB, d, in, h->sz.G, p, wmode);
+        LAUNCH(h, "sp_overlap", k_sp_overlap_arg, h->sz.sp_blocks, RB, d, packed_input_arg(d, host_input), h->sz.G, p, wmode);
     } else {
         LAUNCH(h, "sp_overlap", k_sp_overlap, h->sz.sp_blocks, RB, d, bank, n_inputs, h->sz.G, p, p, 0, wmode);
     }
-    if (!wmode)
-        for (int pass = 1; pass < d.sel_passes; ++pass) LAUNCH(h, "sp_select", k_sel_pass, h->sz.sel_blocks, RB, d, pass, p);
+    if (!wmode) launch_sel_passes(h, d, p);
 }
 
 // Rest of SpatialPooler.process: count + emit.  mode = EMIT_ALL: all of it, with the TM's per-column
@@ -455,7 +473,22 @@ static void enqueue_sp_back(htm_handle *h, const uint32_t *bank, int n_inputs, i
 // the learning role and the scan: one launch (the learning waves scan their own rows), unless the pool is large (the
 // streaming scan kernels) or somebody is timing the roles one by one (unsharded handles under htm_profile)
 static bool tm_tail_fused(const htm_handle *h) {
-    return h->knob.fuse_tm && !(h->profile && h->world == 1) && !scan_pool_is_large(h) && scan_lds(h->d, 1) <= 64 * 1024;
+    return h->knob.fuse_tm && !(h->profile && h->world == 1) && !scan_pool_is_large(h) && bitmap_fits_lds(h->d);
+}
+
+// Sizes of a launch that begins with the learning role and the small-pool scan (the plain k_learn_scan_emit, k_learn_scan_tail,
+// k_learn_scan_front, kgrp_tail): slot in the kt_* tables, blocks of the two roles, the scan's speculation, and the LDS --
+// the larger of the two roles' and of extra_lds, what the role riding behind them needs.  That role's blocks are added where
+// it is launched.
+struct LearnScan {
+    int slot, n_learn, n_scan, spec;
+    size_t lds;
+    int blocks() const { return n_learn + n_scan; }
+};
+static LearnScan learn_scan(const htm_handle *h, size_t extra_lds = 0) {
+    const Dev &d = h->d;
+    return {epl_slot(d), h->sz.lean_learn_blocks, h->sz.lean_scan_blocks, scan_spec_blocks(h),
+            std::max(std::max(learn_lds(learn_epl(d), 256), scan_lds(d, 1)), extra_lds)};
 }
 
 // k_learn_scan_emit by the form of its scan (lse_kernel): the small-pool scan without its LDS tables (what the fused tail launches) ...
@@ -467,12 +500,11 @@ static decltype(&k_learn_scan_emit<1, 6>) const kt_lse_plain[4] = {k_learn_scan_
 static void enqueue_tm_tail(htm_handle *h, int p) {
     Dev &d = h->d;
     if (tm_tail_fused(h)) {
-        const int epl = learn_epl(d), n_learn = h->sz.lean_learn_blocks, n_scan = h->sz.lean_scan_blocks, spec = scan_spec_blocks(h);
-        const size_t lds = std::max(learn_lds(epl, 256), scan_lds(d, 1));
-        LAUNCH_ON(h, h->stream, lds, "tm_learn+tm_scan", kt_lse_plain[epl_slot(d)], n_learn + n_scan, 256, d, p, 0, n_learn, n_scan, spec);
+        const LearnScan ls = learn_scan(h);
+        LAUNCH_ON(h, h->stream, ls.lds, "tm_learn+tm_scan", kt_lse_plain[ls.slot], ls.blocks(), 256, d, p, 0, ls.n_learn, ls.n_scan, ls.spec);
     } else {
         launch_learn(h, p);
-        launch_scan(h, p, scan_lds(d, 1) <= 64 * 1024);
+        launch_scan(h, p, bitmap_fits_lds(d));
     }
 }
 
@@ -502,11 +534,10 @@ static void enqueue_tm(htm_handle *h, int n_active, int learning, int want_winne
     LAUNCH(h, "tm_mid", k_mid_rows, 1 + n_cls + n_sp_rows + n_duty + h->sz.zero_blocks, 256, d, p, n_active, want_winner, learning, n_cls, bank, n_inputs, n_sp_rows, 0, n_duty);
     if (defer_tail) { h->tail_pending = true; h->tail_p = p; return; }
     if (fuse && (front_wmode >= 0 || n_tail_rows)) {
-        const int epl = learn_epl(d), n_learn = h->sz.lean_learn_blocks, n_scan = h->sz.lean_scan_blocks, spec = scan_spec_blocks(h);
-        const size_t lds = std::max(std::max(learn_lds(epl, 256), scan_lds(d, 1)), (size_t)SEL_BINS * 4);
-        const int grid = n_learn + n_scan + (n_tail_rows ? n_tail_rows : h->sz.lean_overlap_blocks);
+        const LearnScan ls = learn_scan(h, (size_t)SEL_BINS * 4);
+        const int grid = ls.blocks() + (n_tail_rows ? n_tail_rows : h->sz.lean_overlap_blocks);
         const char *name = n_tail_rows ? "tm_learn+tm_scan+sp_learn" : "tm_learn+tm_scan+shard_overlap";
-        LAUNCH_ON(h, h->stream, lds, name, kt_learn_scan_tail[epl_slot(d)], grid, 256, d, p, n_learn, n_scan, spec, bank, n_inputs, h->sz.G, front_wmode, n_tail_rows);
+        LAUNCH_ON(h, h->stream, ls.lds, name, kt_learn_scan_tail[ls.slot], grid, 256, d, p, ls.n_learn, ls.n_scan, ls.spec, bank, n_inputs, h->sz.G, front_wmode, n_tail_rows);
         return;
     }
     enqueue_tm_tail(h, p);
@@ -534,7 +565,7 @@ static bool can_pipeline(const htm_handle *h) {
 // the three-launch schedule (htm_pipeline.h): the scan's LDS bitmap, one select histogram, the learning role and the
 // scan in one launch.  BITHTM_LEAN=0: the four-launch schedule below.
 static bool can_lean(const htm_handle *h) {
-    return h->knob.lean && can_pipeline(h) && scan_lds(h->d, 1) <= 64 * 1024 && h->sz.emit_fits_lean;
+    return h->knob.lean && can_pipeline(h) && bitmap_fits_lds(h->d) && h->sz.emit_fits_lean;
 }
 
 // ... the streaming large-pool scan (which reads the cell words from memory: with the LDS tables it measured 3 % slower -- the
@@ -582,20 +613,27 @@ static int lean2_classify_blocks(const htm_handle *h, int learning) {
     return scan_pool_is_large(h) && !h->knob.lean2_classify ? std::max(h->sz.lean2_classify_blocks, 192) : h->sz.lean2_classify_blocks;
 }
 
+// The two-launch schedule's first launch (k_act_mid_rows, htm_pipeline.h) for the step of parity p, its roles counted in the
+// kernel's order.  n_overlap > 0: the coming step's overlap rides along (a steady-state step); else the duty cycle has blocks
+// of its own (the last step of a call, a host-fed step).  The profile name and the LDS bytes are the call site's.
+static void launch_act_mid_rows(htm_handle *h, const char *name, size_t lds, int p, int learning, const uint32_t *bank, int n_inputs, int n_overlap) {
+    Dev &d = h->d;
+    const int n_act = act_blocks(d), n_cls = lean2_classify_blocks(h, learning), n_rows = learning ? d.k : 0;
+    const int n_duty = n_overlap ? 0 : h->sz.c256_blocks, n_clear = d.WPC * h->sz.c256_blocks;
+    LAUNCH_ON(h, h->stream, lds, name, k_act_mid_rows, n_act + 1 + n_cls + n_rows + n_overlap + n_duty + n_clear + h->sz.zero_blocks, 256,
+              d, p, d.k, n_act, learning, n_cls, bank, n_inputs, n_rows, h->sz.G, n_overlap, n_duty, n_clear, h->knob.lean2_order);
+}
+
 // sp_done: the winner list of this step exists (the previous step's last launch, or the cold start).  next_sp: select
 // the next step's winners beside this step's Temporal Memory.
 static void enqueue_lean(htm_handle *h, int p, int learning, const uint32_t *bank, int n_inputs, StepPlan plan) {
     Dev &d = h->d;
-    const int n_act = (d.k * d.KP + 255) / 256, n_rows = learning ? d.k : 0;
-    const int n_cls = learning ? kClassifyBlocks : 0, n_ov = plan.next_sp ? h->sz.lean_overlap_blocks : 0;
     if (h->knob.lean == 2) {                        // the two-launch schedule: both of these in one (htm_pipeline.h)
-        const int n_cls2 = lean2_classify_blocks(h, learning);
-        const int n_ov2 = plan.next_sp ? h->sz.lean2_overlap_blocks : 0;
-        const int n_duty = n_ov2 ? 0 : h->sz.c256_blocks, n_clear = d.WPC * h->sz.c256_blocks;
-        LAUNCH_ON(h, h->stream, (size_t)SEL_BINS * 4, "tm_activate+tm_mid+sp_learn+sp_overlap", k_act_mid_rows,
-                  n_act + 1 + n_cls2 + n_rows + n_ov2 + n_duty + n_clear + h->sz.zero_blocks, 256, d, p, d.k, n_act, learning, n_cls2, bank, n_inputs, n_rows, h->sz.G, n_ov2,
-                  n_duty, n_clear, h->knob.lean2_order);
+        launch_act_mid_rows(h, "tm_activate+tm_mid+sp_learn+sp_overlap", (size_t)SEL_BINS * 4, p, learning, bank, n_inputs,
+                            plan.next_sp ? h->sz.lean2_overlap_blocks : 0);
     } else {
+        const int n_act = act_blocks(d), n_rows = learning ? d.k : 0;
+        const int n_cls = learning ? kClassifyBlocks : 0, n_ov = plan.next_sp ? h->sz.lean_overlap_blocks : 0;
         LAUNCH(h, "tm_activate+sp_learn", k_act_rows, n_act + n_rows + (1 + d.WPC) * h->sz.c256_blocks, 256, d, p, d.k, n_act, bank, n_inputs, n_rows, h->sz.c256_blocks);
         LAUNCH_ON(h, h->stream, (size_t)SEL_BINS * 4, "tm_mid+sp_overlap", k_mid_overlap, 1 + n_cls + n_ov + h->sz.zero_blocks, 256, d, p, d.k, 1, learning, n_cls,
                   bank, n_inputs, h->sz.G, n_ov);
@@ -612,13 +650,13 @@ static void enqueue_pipelined(htm_handle *h, int p, int learning, const uint32_t
     Dev &d = h->d;
     const int n_cls = learning ? kClassifyBlocks : 0;
     const int n_emit = plan.next_sp ? h->sz.c256_blocks : 0;
-    LAUNCH_ON(h, h->stream, sizeof(EmitShared), "tm_activate+sp_emit", k_open_emit, n_emit + (d.k * d.KP + 255) / 256, 256, d, p, n_emit, d.k);
+    LAUNCH_ON(h, h->stream, sizeof(EmitShared), "tm_activate+sp_emit", k_open_emit, n_emit + act_blocks(d), 256, d, p, n_emit, d.k);
     const int n_rows = (plan.next_sp && learning) ? d.k : 0, n_duty = plan.next_sp ? h->sz.c256_blocks : 0;
     LAUNCH(h, "tm_mid+sp_learn", k_mid_rows, 1 + n_cls + n_rows + n_duty + h->sz.zero_blocks, 256, d, p, d.k, 1, learning, n_cls, bank, n_inputs, n_rows, 1, n_duty);
     // (the front is that of step + 2: same parity as this step)
     LAUNCH_ON(h, h->stream, std::max(learn_lds(learn_epl(d)), (size_t)SEL_BINS * 4), "tm_learn+sp_overlap", kt_learn_overlap[epl_slot(d)],
               kLearnBlocks + (plan.next_front ? h->sz.sp_blocks : 0), RB, d, p, kLearnBlocks, bank, n_inputs, h->sz.G, p, 2);
-    const bool use_lds = scan_lds(d, 1) <= 64 * 1024, large = scan_pool_is_large(h);
+    const bool use_lds = bitmap_fits_lds(d), large = scan_pool_is_large(h);
     const int n_sel = plan.next_front ? 64 : 0, n_clear = plan.next_sp ? h->sz.c256_blocks : 0;
     LAUNCH_ON(h, h->stream, std::max(scan_lds(d, use_lds), sizeof(SelShared)), large ? "tm_scan_large+sp_select" : "tm_scan+sp_select",
               kt_scan_sel[scan_slot(large, use_lds)], h->sz.scan_blocks + n_sel + n_clear, 256, d, p, n_sel, n_clear, p, scan_spec_blocks(h));
@@ -972,7 +1010,7 @@ static void size_launches(htm_handle *h) {
         hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu_open, (const void *)k_open_emit, 256, sizeof(EmitShared)) == hipSuccess) {
         z.emit_fits = z.c256_blocks <= std::min(1024, per_cu_emit * z.cus);
         // the pipelined launch puts the activation blocks of the current step behind the emit blocks
-        z.emit_fits_open = z.emit_fits && z.c256_blocks + (d.k * d.KP + 255) / 256 <= std::min(1024, per_cu_open * z.cus);
+        z.emit_fits_open = z.emit_fits && z.c256_blocks + act_blocks(d) <= std::min(1024, per_cu_open * z.cus);
         // the three-launch schedule: the emit blocks come first in the grid of the learn + scan + emit kernel
         // (asked of every form launch_learn_scan_emit may launch for this handle -- LDS tables or not, small-pool or
         // large-pool scan: they differ in launch bounds and registers -- and the smallest answer counts)
@@ -1009,7 +1047,7 @@ static void size_launches(htm_handle *h) {
         // half as many: the slots that role frees are not the classification's to fill -- its blocks poll the fan-in beside the
         // rows.  Measured at the bench shape with the plane role, 316 free slots: 32 blocks 46.2 k timesteps/s, 64: 45.7, 128:
         // 45.3, 312: 42.7 -- so every shape keeps the count it had)
-        const int others = (d.k * d.KP + 255) / 256 + z.lean_overlap_blocks + d.k + 1;
+        const int others = act_blocks(d) + z.lean_overlap_blocks + d.k + 1;
         // (... but no more than 32 where they leave fewer than 128: measured at the bench shape, 60 free slots -- 32 blocks 42.4 k
         // timesteps/s, 40: 41.9, 56: 41.6)
         const int room = (resident - others) & ~7;
@@ -1498,7 +1536,7 @@ extern "C" int htm_sp_planes_check(htm_handle *h, int64_t out[2]) {
 static int close_open_phases(htm_handle *h) {
     if (!h->phase_open) return 0;
     const int p = (int)(h->step_host & 1);
-    if (h->cfg.enable_sp) HIPCHK(h, hipMemsetAsync(h->d.hist0 + (size_t)p * HIST0_PAR, 0, (size_t)HIST0_PAR * 4, h->stream));
+    if (h->cfg.enable_sp) HIPCHK(h, clear_front_hist(h, p));
     h->phase_open = false;
     h->phase_active = 0;
     h->phase_wide = false;
@@ -1513,6 +1551,53 @@ static int stage_input(htm_handle *h, const uint32_t *packed_input) {
 }
 
 static decltype(&k_learn_scan_front<1>) const kt_learn_scan_front[4] = {k_learn_scan_front<1>, k_learn_scan_front<2>, k_learn_scan_front<4>, k_learn_scan_front<8>};
+
+// One host-fed step (htm_step: one input per call; an input too wide for a launch's arguments is already staged).
+// Three launches per step for a caller that steps and steps: the learning role and the scan of a step need nothing of the
+// NEXT input and nothing the next step's overlap touches -- they are held back and ride beside that overlap (the
+// permanence rows, which the overlap does read, in the middle launch instead).  Any other call lets them go first.
+static int enqueue_hostfed(htm_handle *h, const uint32_t *packed_input, int learning) {
+    Dev &d = h->d;
+    if (!(h->knob.defer_tail && d.W <= ARG_INPUT_WORDS && tm_tail_fused(h) && !h->profile)) {
+        flush_tail(h);
+        return enqueue_step(h, RunModes{}, d.input_stage, 1, learning, StepPlan{false, false, false}, packed_input);
+    }
+    const int p = (int)(h->step_host & 1), wmode = step_wmode(h);
+    // the held-back learning role and scan of the step before ride beside THIS step's select finish (k_learn_scan_emit, the last
+    // launch of htm_run's schedules) where that launch is available: the overlap then has the first launch to itself (4.5 us), and the
+    // select finish -- 7 us of a chain on 256 blocks -- no longer has the GPU to itself.  (The activation, which reads the
+    // predictions that scan leaves, has moved behind it: k_act_mid_rows.)
+    const bool ride_emit = h->knob.step_split && h->tail_pending && wmode && h->emit_fused && can_lean(h);
+    if (ride_emit) {
+        enqueue_sp_front(h, d.input_stage, 1, p, wmode, packed_input);
+        h->tail_pending = false;
+        launch_learn_scan_emit(h, h->tail_p, h->sz.c256_blocks);
+        h->window_known = true;
+    } else if (h->tail_pending) {                   // ... else beside this step's overlap (k_learn_scan_front)
+        const LearnScan ls = learn_scan(h, (size_t)(SEL_BINS + ARG_INPUT_WORDS) * 4);
+        h->tail_pending = false;
+        LAUNCH_ON(h, h->stream, ls.lds, "tm_learn+tm_scan+sp_overlap", kt_learn_scan_front[ls.slot], ls.blocks() + h->sz.lean_overlap_blocks, 256,
+                  d, h->tail_p, ls.n_learn, ls.n_scan, ls.spec, packed_input_arg(d, packed_input), h->sz.G, p, wmode);
+        if (!wmode) launch_sel_passes(h, d, p);
+    } else {
+        enqueue_sp_front(h, d.input_stage, 1, p, wmode, packed_input);
+    }
+    if (h->knob.step_split) {
+        // the select finish on its own (winner list and column bitmap, nothing else), then the two-launch schedule's first launch
+        // in the form its last step takes: activation -> fan-in -> middle role beside the winner rows, the duty cycle and the
+        // clears (k_act_mid_rows without an overlap role).  The activation no longer waits at the end of the select finish's
+        // blocks with nothing beside it, and the rows stream under the Temporal Memory's chain (measured: DESIGN.md section 4)
+        if (!ride_emit) enqueue_sp_back(h, d.input_stage, 1, p, 1, 0, false, wmode);
+        launch_act_mid_rows(h, "tm_activate+tm_mid+sp_learn", 0, p, learning, d.input_stage, 1, 0);
+        h->tail_pending = true;
+        h->tail_p = p;
+    } else {
+        enqueue_sp_back(h, d.input_stage, 1, p, 1, EMIT_ALL, false, wmode);
+        enqueue_tm(h, d.k, learning, 1, p, d.input_stage, 1, true, -1, true);
+    }
+    h->step_host += 1;
+    return launch_status(h->err);
+}
 
 extern "C" int htm_step(htm_handle *h, const uint32_t *packed_input, int32_t learning) {
     if (!h || !packed_input) return HTM_ERR_ARGUMENT;
@@ -1531,61 +1616,7 @@ extern "C" int htm_step(htm_handle *h, const uint32_t *packed_input, int32_t lea
         rc = stage_input(h, packed_input);
         if (rc) return rc;
     }
-    // Three launches per step for a caller that steps and steps: the learning role and the scan of a step need nothing of the
-    // NEXT input and nothing the next step's overlap touches -- they are held back and ride beside that overlap (the
-    // permanence rows, which the overlap does read, in the middle launch instead).  Any other call lets them go first.
-    Dev &d = h->d;
-    if (h->knob.defer_tail && d.W <= ARG_INPUT_WORDS && tm_tail_fused(h) && !h->profile) {
-        const int p = (int)(h->step_host & 1), wmode = step_wmode(h);
-        // the held-back learning role and scan of the step before ride beside THIS step's select finish (k_learn_scan_emit, the last
-        // launch of htm_run's schedules) where that launch is available: the overlap then has the first launch to itself (4.5 us), and the
-        // select finish -- 7 us of a chain on 256 blocks -- no longer has the GPU to itself.  (The activation, which reads the
-        // predictions that scan leaves, has moved behind it: k_act_mid_rows.)
-        const bool ride_emit = h->knob.step_split && h->tail_pending && wmode && h->emit_fused && can_lean(h);
-        bool emitted = false;
-        if (ride_emit) {
-            enqueue_sp_front(h, d.input_stage, 1, p, wmode, packed_input);
-            h->tail_pending = false;
-            launch_learn_scan_emit(h, h->tail_p, h->sz.c256_blocks);
-            h->window_known = true;
-            emitted = true;
-        } else if (h->tail_pending) {
-            PackedInputArg in;
-            memset(&in, 0, sizeof(in));
-            memcpy(in.w, packed_input, (size_t)((d.I + 31) / 32) * 4);
-            const int epl = learn_epl(d), n_learn = h->sz.lean_learn_blocks, n_scan = h->sz.lean_scan_blocks, spec = scan_spec_blocks(h);
-            const size_t lds = std::max(std::max(learn_lds(epl, 256), scan_lds(d, 1)), (size_t)(SEL_BINS + ARG_INPUT_WORDS) * 4);
-            const int grid = n_learn + n_scan + h->sz.lean_overlap_blocks;
-            h->tail_pending = false;
-            LAUNCH_ON(h, h->stream, lds, "tm_learn+tm_scan+sp_overlap", kt_learn_scan_front[epl_slot(d)], grid, 256, d, h->tail_p, n_learn, n_scan, spec, in, h->sz.G, p, wmode);
-            if (!wmode)
-                for (int pass = 1; pass < d.sel_passes; ++pass) LAUNCH(h, "sp_select", k_sel_pass, h->sz.sel_blocks, RB, d, pass, p);
-        } else {
-            enqueue_sp_front(h, d.input_stage, 1, p, wmode, packed_input);
-        }
-        if (h->knob.step_split) {
-            // the select finish on its own (winner list and column bitmap, nothing else), then the two-launch schedule's first launch
-            // in the form its last step takes: activation -> fan-in -> middle role beside the winner rows, the duty cycle and the
-            // clears (k_act_mid_rows without an overlap role).  The activation no longer waits at the end of the select finish's
-            // blocks with nothing beside it, and the rows stream under the Temporal Memory's chain (measured: DESIGN.md section 4)
-            if (!emitted) enqueue_sp_back(h, d.input_stage, 1, p, 1, 0, false, wmode);
-            const int lrn = learning ? 1 : 0;
-            const int n_act = (d.k * d.KP + 255) / 256, n_rows = lrn ? d.k : 0;
-            const int n_cls2 = lean2_classify_blocks(h, lrn);
-            const int n_duty = h->sz.c256_blocks, n_clear = d.WPC * h->sz.c256_blocks;
-            LAUNCH_ON(h, h->stream, 0, "tm_activate+tm_mid+sp_learn", k_act_mid_rows, n_act + 1 + n_cls2 + n_rows + n_duty + n_clear + h->sz.zero_blocks, 256,
-                      d, p, d.k, n_act, lrn, n_cls2, d.input_stage, 1, n_rows, h->sz.G, 0, n_duty, n_clear, h->knob.lean2_order);
-            h->tail_pending = true;
-            h->tail_p = p;
-        } else {
-            enqueue_sp_back(h, d.input_stage, 1, p, 1, EMIT_ALL, false, wmode);
-            enqueue_tm(h, d.k, learning ? 1 : 0, 1, p, d.input_stage, 1, true, -1, true);
-        }
-        h->step_host += 1;
-        return launch_status(h->err);
-    }
-    flush_tail(h);
-    return enqueue_step(h, RunModes{}, h->d.input_stage, 1, learning ? 1 : 0, StepPlan{false, false, false}, packed_input);
+    return enqueue_hostfed(h, packed_input, learning ? 1 : 0);
 }
 
 extern "C" int htm_sp_step(htm_handle *h, const uint32_t *packed_input, int32_t learning) {
@@ -1651,7 +1682,7 @@ extern "C" int htm_sp_phase(htm_handle *h, int32_t phase, const void *data, int6
     // the top-digit histogram of this step's keys is accumulated by the phase that makes the keys and consumed (and
     // cleared) by the select: a phase that makes keys starts from a clean one, whatever ran before it in this step
     if (phase == HTM_SP_OVERLAP || phase == HTM_SP_BOOST || (phase == HTM_SP_SELECT && data))
-        HIPCHK(h, hipMemsetAsync(d.hist0 + (size_t)p * HIST0_PAR, 0, (size_t)HIST0_PAR * 4, h->stream));
+        HIPCHK(h, clear_front_hist(h, p));
     switch (phase) {
         case HTM_SP_OVERLAP: {                     // DenseProjection.process + ExponentialBoosting.process; data = packed input
             if (!data) return HTM_ERR_ARGUMENT;
@@ -1676,14 +1707,14 @@ extern "C" int htm_sp_phase(htm_handle *h, int32_t phase, const void *data, int6
                 h->phase_wide = true;
             }
             if (h->phase_wide) {
-                for (int pass = 1; pass < wide.sel_passes; ++pass) LAUNCH(h, "sp_select", k_sel_pass, h->sz.sel_blocks, RB, wide, pass, p);
+                launch_sel_passes(h, wide, p);
                 LAUNCH(h, "sp_count", k_sp_count, h->sz.c256_blocks, 256, wide, p);
                 LAUNCH(h, "sp_emit", k_sp_emit, h->sz.c256_blocks, 256, wide, p, 0, 0, 0, 0, h->sz.c256_blocks);
                 // (the k-th key of SP_KEYS_HOST is the double's own bits, not a select_key: it says nothing about where the fused
                 // step's window should be -- the next whole step takes the digit passes, as a handle's first step does)
                 h->window_known = !data;
             } else {
-                for (int pass = 1; pass < d.sel_passes; ++pass) LAUNCH(h, "sp_select", k_sel_pass, h->sz.sel_blocks, RB, d, pass, p);
+                launch_sel_passes(h, d, p);
                 enqueue_sp_back(h, d.input_stage, 1, p, 0, 0, false);          // the list and its bitmap, nothing else
             }
             break;
@@ -1891,7 +1922,7 @@ extern "C" int htm_tm_scan(htm_handle *h, const uint32_t *active_words) {
          hipMemsetAsync(&d.ctr->n_active_cells, 0, sizeof(int), h->stream) == hipSuccess;
     if (!ok) { hipFree(d_act); h->err = "htm_tm_scan: staging failed"; return HTM_ERR_HIP; }
     hipLaunchKernelGGL(k_tm_ext_active, dim3(std::min((d.C + 255) / 256, 1024)), dim3(256), 0, h->stream, d, p, d_act);
-    launch_scan(h, p, scan_lds(d, 1) <= 64 * 1024);
+    launch_scan(h, p, bitmap_fits_lds(d));
     hipError_t e = hipGetLastError();
     const bool synced = hipStreamSynchronize(h->stream) == hipSuccess;
     hipFree(d_act);
@@ -1988,7 +2019,7 @@ static int run_or_prepare(htm_handle *h, const RunCall &c) {
         enqueue_step_outputs(h, modes, p);
         h->step_host += 1;
         // (the four-launch schedule had begun the step after it: that front is never consumed)
-        HIPCHK(h, hipMemsetAsync(h->d.hist0 + (size_t)(h->step_host & 1) * HIST0_PAR, 0, (size_t)HIST0_PAR * 4, h->stream));
+        HIPCHK(h, clear_front_hist(h, (int)(h->step_host & 1)));
         h->ahead_bank = nullptr;
         if (int rc = launch_status(h->err)) return rc;
         n_steps -= 1;
@@ -2045,7 +2076,7 @@ static int run_or_prepare(htm_handle *h, const RunCall &c) {
     if (c.dry) return HTM_OK;
     if (n_steps > 0) {
         if (resume && !cont && n_steps == 1)        // the front computed for the step after this one is never consumed:
-            HIPCHK(h, hipMemsetAsync(h->d.hist0 + (size_t)(h->step_host & 1) * HIST0_PAR, 0, (size_t)HIST0_PAR * 4, h->stream));    // its digit histogram
+            HIPCHK(h, clear_front_hist(h, (int)(h->step_host & 1)));    // its digit histogram
         h->ahead_bank = cont ? c.bank : nullptr;
         h->ahead_lean = cont && can_lean(h);
         h->ahead_n_inputs = n_inputs;
@@ -2266,12 +2297,11 @@ static int shard_enqueue_begin(htm_handle *h, const uint32_t *bank, int n_inputs
     const int fused = h->emit_fused ? 1 : 0;
     const int wmode = fused ? h->knob.shard_window : 0;
     if (front_done && h->shard_front_wmode != wmode) {       // the exchange mode changed since the front was computed: start over
-        HIPCHK(h, hipMemsetAsync(d.hist0 + (size_t)p * HIST0_PAR, 0, (size_t)HIST0_PAR * 4, h->stream));
+        HIPCHK(h, clear_front_hist(h, p));
         front_done = false;
     }
     if (!front_done) LAUNCH(h, "shard_overlap", k_shard_overlap, h->sz.sp_blocks, RB, d, bank, n_inputs, h->sz.G, p, wmode, 0);
-    if (!wmode)
-        for (int pass = 1; pass < d.sel_passes; ++pass) LAUNCH(h, "sp_select", k_sel_pass, h->sz.sel_blocks, RB, d, pass, p);
+    if (!wmode) launch_sel_passes(h, d, p);
     if (!fused) LAUNCH(h, "sp_count", k_sp_count, h->sz.c256_blocks, 256, d, p);
     LAUNCH(h, "shard_candidates", k_sp_emit, h->sz.c256_blocks + std::min((d.C + 255) / 256, 64), 256, d, p, 1, fused, EMIT_LOCAL, wmode, h->sz.c256_blocks);
     return 0;
@@ -3767,7 +3797,7 @@ static GroupForm group_form(htm_group *g) {
     const htm_handle *h0 = g->m[0];
     GroupForm f;
     f.large = h0->knob.scan_large >= 0 ? h0->knob.scan_large != 0 : hi > h0->knob.scan_large_above;
-    f.fuse = h0->knob.fuse_tm && !f.large && scan_lds(h0->d, 1) <= 64 * 1024;
+    f.fuse = h0->knob.fuse_tm && !f.large && bitmap_fits_lds(h0->d);
     f.spec = std::min(lo / SCAN_SEGS, h0->sz.scan_blocks) & ~63;
     f.shared = false;                               // (set by the caller for a step without learning)
     return f;
@@ -3795,10 +3825,10 @@ static void group_enqueue_step(htm_group *g, RunModes m, const uint32_t *const *
     LAUNCH_ON(h, s, 0, "group:tm_mid", kgrp_middle, g_mid, 256, tab, p, learning, n_cls, banks, n_inputs, rows_mid);
     const int epl = learn_epl(d);
     if (f.fuse && !f.shared) {
-        const size_t lds = std::max(learn_lds(epl, 256), scan_lds(d, 1));
-        const dim3 g_tail(h->sz.lean_learn_blocks + h->sz.lean_scan_blocks + rows_tail, B);
-        LAUNCH_ON(h, s, lds, rows_tail ? "group:tm_learn+tm_scan+sp_learn" : "group:tm_learn+tm_scan", kt_grp_tail[epl_slot(d)], g_tail, 256, tab, p,
-                  h->sz.lean_learn_blocks, h->sz.lean_scan_blocks, f.spec, banks, n_inputs);
+        const LearnScan ls = learn_scan(h);         // (but the group's speculation: its most conservative member's, group_form)
+        const dim3 g_tail(ls.blocks() + rows_tail, B);
+        LAUNCH_ON(h, s, ls.lds, rows_tail ? "group:tm_learn+tm_scan+sp_learn" : "group:tm_learn+tm_scan", kt_grp_tail[ls.slot], g_tail, 256, tab, p,
+                  ls.n_learn, ls.n_scan, f.spec, banks, n_inputs);
     } else {
         // (f.shared: every member's learning role -- with learning = 0 the previous scan's per-cell maxima cleared, nothing else --
         // then ONE pass over the shared store for each chunk of share_m members: htm_group.h)
@@ -3807,7 +3837,7 @@ static void group_enqueue_step(htm_group *g, RunModes m, const uint32_t *const *
             LAUNCH_ON(h, s, (size_t)g->share_m * d.colwords * 4, "group:tm_scan_shared", kgrp_scan_shared, dim3(g->share_blocks, g->share_chunks), 256, tab, B,
                       g->share_m, p);
         } else {
-            const bool use_lds = scan_lds(d, 1) <= 64 * 1024;
+            const bool use_lds = bitmap_fits_lds(d);
             LAUNCH_ON(h, s, scan_lds(d, use_lds), f.large ? "group:tm_scan_large" : "group:tm_scan", kt_grp_scan[scan_slot(f.large, use_lds)], dim3(h->sz.scan_blocks, B), 256,
                       tab, p, f.spec);
         }

@@ -63,10 +63,7 @@ __global__ __launch_bounds__(256, BITHTM_MID_ROWS_WAVES) void kgrp_middle(const 
         return;
     }
     b -= n_rows;
-    const int nz = (int)gridDim.x - 1 - n_cls - n_rows;
-    const int words4 = (d.ctr->S + 127) >> 7;
-    uint4 *mb = (uint4 *)d.match_bits[p];
-    for (int i = b * 256 + (int)threadIdx.x; i < words4; i += nz * 256) mb[i] = make_uint4(0u, 0u, 0u, 0u);
+    role_zero_match(d, p, b, (int)gridDim.x - 1 - n_cls - n_rows, d.ctr->S);
 }
 
 // the learning role, the scan and (n_rows > 0) this step's permanence rows: k_learn_scan_tail without the shard's overlap
@@ -75,7 +72,7 @@ __global__ __launch_bounds__(256, 6) void kgrp_tail(const Dev *__restrict__ tab,
                                                     const uint32_t *const *__restrict__ banks, int n_inputs) {
     const Dev &d = tab[blockIdx.y];
     int b = blockIdx.x;
-    if (blockIdx.x == gridDim.x - 1 && threadIdx.x < FAN_COUNTERS) d.fan[(size_t)(p * FAN_COUNTERS + (int)threadIdx.x) * FAN_STRIDE] = 0u;
+    fan_reset(d, p);
     if (b < n_learn_blocks) {
         role_learn<EPL, 256, true>(d, p, b, n_learn_blocks, (LearnShared<EPL, 256> *)dyn_lds);
         return;
@@ -93,7 +90,7 @@ __global__ __launch_bounds__(256, 6) void kgrp_tail(const Dev *__restrict__ tab,
 template <int EPL>
 __global__ __launch_bounds__(RB, 7) void kgrp_learn(const Dev *__restrict__ tab, int p) {
     const Dev &d = tab[blockIdx.y];
-    if (blockIdx.x == gridDim.x - 1 && threadIdx.x < FAN_COUNTERS) d.fan[(size_t)(p * FAN_COUNTERS + (int)threadIdx.x) * FAN_STRIDE] = 0u;
+    fan_reset(d, p);
     role_learn<EPL, RB>(d, p, blockIdx.x, gridDim.x, (LearnShared<EPL, RB> *)dyn_lds);
 }
 

@@ -1,6 +1,7 @@
 // The fused launches of htm_run's pipelined schedules -- two per timestep (below: k_act_mid_rows, k_learn_scan_emit), three
 // (BITHTM_LEAN=1: k_act_rows, k_mid_overlap, k_learn_scan_emit), or four where the scan's column bitmap does not fit the LDS
-// -- and the device-clock trace.
+// -- and the device-clock trace.  The small roles these launches share are written once: role_activate (htm_sp_kernels.h),
+// fan_reset and role_zero_match (htm_tm_kernels.h), role_duty and role_clear_dense (below).
 // Part of the single translation unit htm_engine.hip (included there, in this order:
 // htm_dev.h, htm_sp_kernels.h, htm_tm_kernels.h, htm_pipeline.h).
 #ifndef BITHTM_HTM_PIPELINE_H
@@ -42,13 +43,29 @@ struct TraceScope {                                 // BITHTM_TRACE=1: first / l
 // are resident whatever the other blocks do
 __global__ __launch_bounds__(256) void k_open_emit(Dev d, int p, int n_emit_blocks, int n_active) {
     TraceScope ts(d, 0 + 4 * p);
-    if ((int)blockIdx.x < n_emit_blocks) {
-        role_emit(d, p ^ 1, 1, 1, 0, blockIdx.x, n_emit_blocks, (EmitShared *)dyn_lds);
-    } else {                                       // one active column per lane group (a half-wave; the wave where a column has 64 cell slots)
-        const int idx = ((int)blockIdx.x - n_emit_blocks) * tm_groups_per_block(d) + tm_group_of(d, threadIdx.x);
-        const bool ok = idx < n_active;
-        const int a = ok ? d.active_cols[p][idx] : 0;
-        tm_activate_column(d, p, 1, ok, a, idx, tm_pred_words(d, p, ok, a));
+    if ((int)blockIdx.x < n_emit_blocks) role_emit(d, p ^ 1, 1, 1, 0, blockIdx.x, n_emit_blocks, (EmitShared *)dyn_lds);
+    else role_activate(d, p, 1, (int)blockIdx.x - n_emit_blocks, n_active);
+}
+
+// a duty-cycle block (blk-th of its role): columns [c_lo, c_hi), 256 per block, against the winner bitmap of parity p
+// (regularizations.py:19-21, float32, two roundings)
+__device__ __forceinline__ void role_duty(const Dev &d, int p, int blk, int c_lo, int c_hi) {
+    const int c = c_lo + blk * 256 + (int)threadIdx.x;
+    if (c < c_hi) {
+        float dc = d.duty[c] * d.mom;
+        if ((d.colbits[p][c >> 5] >> (c & 31)) & 1u) dc = dc + d.dinc;
+        d.duty[c] = dc;
+    }
+}
+
+// a clear block (blk-th of n_blocks) of the step's dense per-column words: predictions (the scan sets bits), and the active /
+// winner words of the columns that are NOT active (the activation blocks of the same launch write the others)
+// (word w belongs to column w / WPC)
+__device__ __forceinline__ void role_clear_dense(const Dev &d, int p, int blk, int n_blocks) {
+    for (int w = blk * 256 + (int)threadIdx.x; w < d.C * d.WPC; w += n_blocks * 256) {
+        const int cc = w >> (d.LK - 5);
+        d.pred[p][w] = 0;
+        if (!((d.colbits[p][cc >> 5] >> (cc & 31)) & 1u)) { d.act[p][w] = 0; d.win[p][w] = 0; }
     }
 }
 
@@ -75,22 +92,11 @@ __global__ __launch_bounds__(256, BITHTM_MID_ROWS_WAVES) void k_mid_rows(Dev d, 
         return;
     }
     b -= n_rows;
-    const int c = d.c0 + b * 256 + (int)threadIdx.x;              // (own columns)
     if (b < n_duty_blocks) {
-        if (c < d.c1) {
-            float dc = d.duty[c] * d.mom;
-            if ((d.colbits[rows_ahead ? q : p][c >> 5] >> (c & 31)) & 1u) dc = dc + d.dinc;
-            d.duty[c] = dc;
-        }
+        role_duty(d, rows_ahead ? q : p, b, d.c0, d.c1);            // (own columns)
         return;
     }
-    // the remaining blocks: zero the match bits this step's scan (and learning role) will set with atomicOr -- the buffer
-    // holds the bits of the scan two steps back, whose readers are done.  (Rows at or above the segment count never had one.)
-    b -= n_duty_blocks;
-    const int nz = (int)gridDim.x - 1 - n_cls - n_rows - n_duty_blocks;
-    const int words4 = ((d.world > 1 ? d.ctr->L : d.ctr->S) + 127) >> 7;
-    uint4 *mb = (uint4 *)d.match_bits[p];
-    for (int i = b * 256 + (int)threadIdx.x; i < words4; i += nz * 256) mb[i] = make_uint4(0u, 0u, 0u, 0u);
+    role_zero_match(d, p, b - n_duty_blocks, (int)gridDim.x - 1 - n_cls - n_rows - n_duty_blocks, d.world > 1 ? d.ctr->L : d.ctr->S);
 }
 
 template <int EPL>
@@ -145,11 +151,8 @@ __global__ __launch_bounds__(256, 8) void k_act_rows(Dev d, int p, int n_active,
                                                      int n_rows, int n_duty_blocks) {
     TraceScope ts(d, 0 + 4 * p);
     int b = blockIdx.x;
-    if (b < n_act_blocks) {                         // one active column per lane group (a half-wave; the wave where a column has 64 cell slots)
-        const int idx = b * tm_groups_per_block(d) + tm_group_of(d, threadIdx.x);
-        const bool ok = idx < n_active;
-        const int a = ok ? d.active_cols[p][idx] : 0;
-        tm_activate_column(d, p, 1, ok, a, idx, tm_pred_words(d, p, ok, a));
+    if (b < n_act_blocks) {
+        role_activate(d, p, 1, b, n_active);
         return;
     }
     b -= n_act_blocks;
@@ -158,24 +161,11 @@ __global__ __launch_bounds__(256, 8) void k_act_rows(Dev d, int p, int n_active,
         return;
     }
     b -= n_rows;
-    const int c = b * 256 + (int)threadIdx.x;
     if (b < n_duty_blocks) {
-        if (c < d.C) {
-            float dc = d.duty[c] * d.mom;
-            if ((d.colbits[p][c >> 5] >> (c & 31)) & 1u) dc = dc + d.dinc;
-            d.duty[c] = dc;
-        }
+        role_duty(d, p, b, 0, d.C);
         return;
     }
-    // the step's dense per-column words: predictions (the scan sets bits), and the active / winner words of the columns
-    // that are NOT active (the activation blocks of this launch write the others)
-    // (word w belongs to column w / WPC)
-    const int n_clear = (int)gridDim.x - n_act_blocks - n_rows - n_duty_blocks;
-    for (int w = (b - n_duty_blocks) * 256 + (int)threadIdx.x; w < d.C * d.WPC; w += n_clear * 256) {
-        const int cc = w >> (d.LK - 5);
-        d.pred[p][w] = 0;
-        if (!((d.colbits[p][cc >> 5] >> (cc & 31)) & 1u)) { d.act[p][w] = 0; d.win[p][w] = 0; }
-    }
+    role_clear_dense(d, p, b - n_duty_blocks, (int)gridDim.x - n_act_blocks - n_rows - n_duty_blocks);
 }
 
 __global__ __launch_bounds__(256) void k_mid_overlap(Dev d, int p, int n_active, int want_winner, int learning, int n_cls,
@@ -191,11 +181,7 @@ __global__ __launch_bounds__(256) void k_mid_overlap(Dev d, int p, int n_active,
         role_overlap<256>(d, bank, n_inputs, G, p, p ^ 1, 1, b, n_overlap_blocks, (uint32_t *)dyn_lds, 1);
         return;
     }
-    b -= n_overlap_blocks;
-    const int nz = (int)gridDim.x - 1 - n_cls - n_overlap_blocks;      // (see k_mid_rows)
-    const int words4 = ((d.world > 1 ? d.ctr->L : d.ctr->S) + 127) >> 7;
-    uint4 *mb = (uint4 *)d.match_bits[p];
-    for (int i = b * 256 + (int)threadIdx.x; i < words4; i += nz * 256) mb[i] = make_uint4(0u, 0u, 0u, 0u);
+    role_zero_match(d, p, b - n_overlap_blocks, (int)gridDim.x - 1 - n_cls - n_overlap_blocks, d.world > 1 ? d.ctr->L : d.ctr->S);
 }
 
 // ---- the two-launch schedule (the default; BITHTM_LEAN=2) -----------------------------------------------------------
@@ -267,10 +253,7 @@ __global__ __launch_bounds__(256, BITHTM_LEAN2_WAVES) void k_act_mid_rows(Dev d,
         if (b < n) role = r; else b -= n;
     }
     if (role == 0) {
-        const int idx = b * tm_groups_per_block(d) + tm_group_of(d, threadIdx.x);
-        const bool ok = idx < n_active;
-        const int a = ok ? d.active_cols[p][idx] : 0;
-        tm_activate_column<true>(d, p, 1, ok, a, idx, tm_pred_words(d, p, ok, a));
+        role_activate<true>(d, p, 1, b, n_active);
         fan_signal(d, p, b);
         return;
     }
@@ -291,28 +274,15 @@ __global__ __launch_bounds__(256, BITHTM_LEAN2_WAVES) void k_act_mid_rows(Dev d,
         return;
     }
     if (b < n_duty_blocks) {
-        const int c = b * 256 + (int)threadIdx.x;
-        if (c < d.C) {
-            float dc = d.duty[c] * d.mom;
-            if ((d.colbits[p][c >> 5] >> (c & 31)) & 1u) dc = dc + d.dinc;
-            d.duty[c] = dc;
-        }
+        role_duty(d, p, b, 0, d.C);
         return;
     }
     b -= n_duty_blocks;
-    if (b < n_clear_blocks) {                          // (see k_act_rows)
-        for (int w = b * 256 + (int)threadIdx.x; w < d.C * d.WPC; w += n_clear_blocks * 256) {
-            const int cc = w >> (d.LK - 5);
-            d.pred[p][w] = 0;
-            if (!((d.colbits[p][cc >> 5] >> (cc & 31)) & 1u)) { d.act[p][w] = 0; d.win[p][w] = 0; }
-        }
+    if (b < n_clear_blocks) {
+        role_clear_dense(d, p, b, n_clear_blocks);
         return;
     }
-    b -= n_clear_blocks;
-    const int nz = (int)gridDim.x - n_act_blocks - 1 - n_cls - n_rows - n_overlap_blocks - n_duty_blocks - n_clear_blocks;      // (see k_mid_rows)
-    const int words4 = (d.ctr->S + 127) >> 7;
-    uint4 *mb = (uint4 *)d.match_bits[p];
-    for (int i = b * 256 + (int)threadIdx.x; i < words4; i += nz * 256) mb[i] = make_uint4(0u, 0u, 0u, 0u);
+    role_zero_match(d, p, b - n_clear_blocks, (int)gridDim.x - n_act_blocks - 1 - n_cls - n_rows - n_overlap_blocks - n_duty_blocks - n_clear_blocks, d.ctr->S);
 }
 
 // the emit blocks wait for each other's records: they come first in the grid (all resident whatever the others do);
@@ -333,7 +303,7 @@ __global__ __launch_bounds__(256, MINW) void k_learn_scan_emit(Dev d, int p, int
     if (n_scan_blocks < 0) n_scan_blocks = -n_scan_blocks;
     // (the fan-in counters of the step's first launch, k_act_mid_rows, are this launch's to reset: it always follows that one, whatever
     // schedule the steps before and after take)
-    if (blockIdx.x == gridDim.x - 1 && threadIdx.x < FAN_COUNTERS) d.fan[(size_t)(p * FAN_COUNTERS + (int)threadIdx.x) * FAN_STRIDE] = 0u;
+    fan_reset(d, p);
     int b = blockIdx.x, scan_blk;
     if (b < n_emit_blocks) {
         role_emit(d, p ^ 1, 1, 1, 0, b, n_emit_blocks, (EmitShared *)dyn_lds, 1);
@@ -360,7 +330,7 @@ template <int EPL>
 __global__ __launch_bounds__(256, 6) void k_learn_scan_tail(Dev d, int p, int n_learn_blocks, int n_scan_blocks, int n_spec,
                                                             const uint32_t *__restrict__ bank, int n_inputs, int G, int wmode, int n_rows) {
     int b = blockIdx.x;
-    if (blockIdx.x == gridDim.x - 1 && threadIdx.x < FAN_COUNTERS) d.fan[(size_t)(p * FAN_COUNTERS + (int)threadIdx.x) * FAN_STRIDE] = 0u;     // (as k_learn_scan_emit)
+    fan_reset(d, p);                                // (as k_learn_scan_emit)
     if (b < n_learn_blocks) {
         role_learn<EPL, 256, true>(d, p, b, n_learn_blocks, (LearnShared<EPL, 256> *)dyn_lds);
         return;
@@ -383,7 +353,7 @@ __global__ __launch_bounds__(256, 6) void k_learn_scan_front(Dev d, int p_prev, 
                                                              PackedInputArg in, int G, int p, int wmode) {
     int b = blockIdx.x;
     // (the fan-in counters of the held-back step's k_act_mid_rows: see k_learn_scan_emit)
-    if (blockIdx.x == gridDim.x - 1 && threadIdx.x < FAN_COUNTERS) d.fan[(size_t)(p_prev * FAN_COUNTERS + (int)threadIdx.x) * FAN_STRIDE] = 0u;
+    fan_reset(d, p_prev);
     if (b < n_learn_blocks) {
         role_learn<EPL, 256, true>(d, p_prev, b, n_learn_blocks, (LearnShared<EPL, 256> *)dyn_lds);
         return;

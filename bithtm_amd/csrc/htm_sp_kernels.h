@@ -637,6 +637,17 @@ __device__ __forceinline__ void tm_activate_column(const Dev &d, int p, int want
 __device__ __forceinline__ int tm_group_of(const Dev &d, int tid) { return tid >> d.LK; }
 __device__ __forceinline__ int tm_groups_per_block(const Dev &d) { return 256 >> d.LK; }
 
+// an activation block (blk-th of its role): one active column per lane group (a half-wave; the wave where a column has 64 cell slots)
+// SET_BIT: the stand-alone Temporal Memory, whose column bitmap no select has filled
+template <bool WT = false, bool SET_BIT = false>
+__device__ __forceinline__ void role_activate(const Dev &d, int p, int want_winner, int blk, int n_active) {
+    const int idx = blk * tm_groups_per_block(d) + tm_group_of(d, threadIdx.x);
+    const bool ok = idx < n_active;
+    const int a = ok ? d.active_cols[p][idx] : 0;
+    if (SET_BIT && ok && (threadIdx.x & (d.KP - 1)) == 0) atomicOr(&d.colbits[p][a >> 5], 1u << (a & 31));
+    tm_activate_column<WT>(d, p, want_winner, ok, a, idx, tm_pred_words(d, p, ok, a));
+}
+
 // ---- column sharding: the exchange record ----------------------------------------------------
 // One fixed-size record per rank and timestep (oracle/sharded.py record_nbytes): the rank's own
 // candidates -- a superset of its top-min(k, own columns), n of them, n <= CAP slots --, in ascending column order, each

@@ -21,11 +21,7 @@ __global__ __launch_bounds__(256) void k_tm_load_active(Dev d, int p, const int 
 
 // stand-alone TM: per-column activation, one active column per lane group
 __global__ __launch_bounds__(256) void k_tm_activate(Dev d, int p, int n_active, int want_winner) {
-    const int idx = blockIdx.x * tm_groups_per_block(d) + tm_group_of(d, threadIdx.x);
-    const bool ok = idx < n_active;
-    const int a = ok ? d.active_cols[p][idx] : 0;
-    if (ok && (threadIdx.x & (d.KP - 1)) == 0) atomicOr(&d.colbits[p][a >> 5], 1u << (a & 31));
-    tm_activate_column(d, p, want_winner, ok, a, idx, tm_pred_words(d, p, ok, a));
+    role_activate<false, true>(d, p, want_winner, blockIdx.x, n_active);
 }
 
 // PredictiveProjection.update called on its own (htm_tm_update): the learning cells come from the caller, grouped by
@@ -975,17 +971,31 @@ __device__ __forceinline__ void role_learn(const Dev &d, int p, int blk, int nbl
 
 extern __shared__ __attribute__((aligned(16))) unsigned char dyn_lds[];
 
+// every form of a step's learning launch resets the fan-in counters its k_act_mid_rows may have used (htm_pipeline.h): the
+// last block of the grid, for the step of parity p
+__device__ __forceinline__ void fan_reset(const Dev &d, int p) {
+    if (blockIdx.x == gridDim.x - 1 && threadIdx.x < FAN_COUNTERS) d.fan[(size_t)(p * FAN_COUNTERS + (int)threadIdx.x) * FAN_STRIDE] = 0u;
+}
+
+// the remaining blocks of a step's middle launch (blk-th of n_blocks) zero the match bits this step's scan (and learning role)
+// will set with atomicOr -- the buffer holds the bits of the scan two steps back, whose readers are done.  n_segs: the segment
+// count (rows at or above it never had a bit)
+__device__ __forceinline__ void role_zero_match(const Dev &d, int p, int blk, int n_blocks, int n_segs) {
+    const int words4 = (n_segs + 127) >> 7;
+    uint4 *mb = (uint4 *)d.match_bits[p];
+    for (int i = blk * 256 + (int)threadIdx.x; i < words4; i += n_blocks * 256) mb[i] = make_uint4(0u, 0u, 0u, 0u);
+}
+
 template <int EPL>
 __global__ __launch_bounds__(RB) void k_tm_learn(Dev d, int p) {
-    // (every form of a step's learning launch resets the fan-in counters its k_act_mid_rows may have used: htm_pipeline.h)
-    if (blockIdx.x == gridDim.x - 1 && threadIdx.x < FAN_COUNTERS) d.fan[(size_t)(p * FAN_COUNTERS + (int)threadIdx.x) * FAN_STRIDE] = 0u;
+    fan_reset(d, p);
     role_learn<EPL, RB>(d, p, blockIdx.x, gridDim.x, (LearnShared<EPL, RB> *)dyn_lds);
 }
 
 // htm_tm_update's learning launches (role_learn, EXT)
 template <int EPL>
 __global__ __launch_bounds__(RB) void k_tm_learn_ext(Dev d, int p) {
-    if (blockIdx.x == gridDim.x - 1 && threadIdx.x < FAN_COUNTERS) d.fan[(size_t)(p * FAN_COUNTERS + (int)threadIdx.x) * FAN_STRIDE] = 0u;   // (as k_tm_learn)
+    fan_reset(d, p);
     role_learn<EPL, RB, false, true>(d, p, blockIdx.x, gridDim.x, (LearnShared<EPL, RB> *)dyn_lds);
 }
 

@@ -3,9 +3,12 @@ engine's host code, built host-only WITHOUT a sanitizer and loaded through BITHT
 while the stub runtime writes one line per kernel launch, asynchronous memset / copy, capture and graph launch.
 
     trace_driver.py invariants   prints one JSON object: the launch lines of the call patterns the committed test asserts on
-    trace_driver.py full         every batched call pattern in every schedule, with a `# label` line before each pattern: the
-                                 trace file of one build of the engine is compared with another's by diff (a refactor of the
-                                 host code must leave it as it was)
+    trace_driver.py full         every batched call pattern in every schedule, host-fed process() loops under each combination
+                                 of the step's knobs (inputs below, at and above the width of a launch's arguments), the
+                                 stand-alone Spatial Pooler (process, run, phase by phase with plug-in objects) and a
+                                 column-sharded group of two ranks in one process, with a `# label` line before each pattern:
+                                 the trace file of one build of the engine is compared with another's by diff (a refactor of
+                                 the host code must leave it as it was)
 
 Kernels do nothing in the stub, so the device state stays zero: what the trace holds is which launches the host code makes, in
 which order, with which grids -- not what they compute."""
@@ -172,10 +175,80 @@ def stack(use_graph):
     stack.process(BANK[2])
 
 
+STEP_KNOBS = ("BITHTM_STEP_SPLIT", "BITHTM_DEFER_TAIL", "BITHTM_FUSE_TM", "BITHTM_TAIL_ROWS")
+
+
+def host_fed(input_dim, K, off):
+    """A process() loop (htm_step: one input per call) with the knobs `off` of the step set to 0; then an entry point that lets
+    a held-back last launch go, and a step without learning."""
+    for name in STEP_KNOBS:
+        os.environ.pop(name, None)
+    os.environ.update({name: "0" for name in off})
+    np.random.seed(K)
+    htm = B.HierarchicalTemporalMemory(input_dim, C, K, seed=K)      # (the knobs are read when the handle is created)
+    for name in STEP_KNOBS:
+        os.environ.pop(name, None)
+    bank = np.random.RandomState(3).rand(7, input_dim) < 0.1
+    for t in range(6):
+        htm.process(bank[t])
+    htm.run(bank, 3, use_graph=False)
+    htm.process(bank[0], learning=False)
+    htm.process(bank[1])
+
+
+class HostProjection:
+    """Plug-in objects with the reference's methods that live on the host: SpatialPooler.process then runs phase by phase."""
+
+    def process(self, input_activation):
+        return np.arange(C) % 5
+
+    def update(self, input_activation, active_column):
+        pass
+
+
+class HostBoosting:
+    def process(self, overlaps):
+        return np.asarray(overlaps, np.float64) * 1.5
+
+    def update(self, active_column):
+        pass
+
+
+class HostInhibition:
+    def process(self, boosted):
+        return np.sort(np.argsort(-np.asarray(boosted), kind="stable")[:10])
+
+
+def spatial_pooler(use_graph, record):
+    sp = B.SpatialPooler(I, C, 10)
+    sp.process(BANK[0])
+    sp.run(BANK, 12, use_graph=use_graph, record=record)
+    sp.run(BANK, 3, use_graph=use_graph, learning=False)
+    sp.process(BANK[1], learning=False)
+
+
+def sp_phases(**foreign):
+    sp = B.SpatialPooler(I, C, 10, **foreign)
+    for t in range(3):
+        sp.process(BANK[t])
+    sp.process(BANK[3], learning=False)
+
+
+def shard_group(use_graph, pipeline, K):
+    from bithtm_amd.distributed import LocalGroup
+    group = LocalGroup(2, I, C, K, permanence=np.random.RandomState(5).normal(0.0, 0.1, (C, I)), seed=5)
+    group.process(BANK[0])
+    group.upload_bank(BANK)
+    group.run(6, use_graph=use_graph, pipeline=pipeline)
+    group.run(2, stepwise=True)
+    group.run(5, learning=False, use_graph=use_graph, pipeline=pipeline)
+    group.process(BANK[1])
+
+
 def full():
-    def pattern(text, call, *args):                 # (every pattern's models are gone before the next one's are made)
+    def pattern(text, call, *args, **kw):           # (every pattern's models are gone before the next one's are made)
         label(text)
-        call(*args)
+        call(*args, **kw)
         gc.collect()
     run_modes = {"plain": {}, "record": dict(record=ALL), "resets": dict(resets=RESETS), "record+resets": dict(record=ALL, resets=RESETS),
                  "predicted_input": dict(record=("predicted_input",)), "record+resets+predicted_input": dict(record=PIN, resets=RESETS)}
@@ -192,6 +265,18 @@ def full():
         pattern(f"group graph={use_graph} record={record}", group, use_graph, record)
     for use_graph in (True, False):
         pattern(f"stack graph={use_graph}", stack, use_graph)
+    # host-fed steps: an input that rides in the launch's arguments, one just over their width (2080 bits: 65 packed words), and
+    # one exactly at it (2048)
+    for n_off in range(len(STEP_KNOBS) + 1):
+        for off, input_dim, K in itertools.product(itertools.combinations(STEP_KNOBS, n_off), (I, 2080, 2048), (8, 40)):
+            pattern(f"host-fed input_dim={input_dim} K={K} off={','.join(off)}", host_fed, input_dim, K, off)
+    for use_graph, record in itertools.product((True, False), (None, ("active_column", "active_overlap", "active_boosted"))):
+        pattern(f"spatial pooler graph={use_graph} record={record}", spatial_pooler, use_graph, record)
+    for name, foreign in (("proximal_projection", HostProjection), ("boosting", HostBoosting), ("inhibition", HostInhibition)):
+        pattern(f"sp phases, host {name}", sp_phases, **{name: foreign()})
+    pattern("sp phases, host boosting + inhibition", sp_phases, boosting=HostBoosting(), inhibition=HostInhibition())
+    for use_graph, pipeline, K in itertools.product((True, False), (True, False), (8, 32)):       # (a sharded handle: cell_dim <= 32)
+        pattern(f"shard group graph={use_graph} pipeline={pipeline} K={K}", shard_group, use_graph, pipeline, K)
 
 
 if __name__ == "__main__":

@@ -663,6 +663,21 @@ def test_random_small_configurations_agree_with_the_oracle():
     assert done >= 15
 
 
+@pytest.mark.parametrize("K", [8, 40])
+@pytest.mark.parametrize("input_dim, env", [(2080, {}), (2048, {}), (100, {"BITHTM_TAIL_ROWS": "0"}), (2080, {"BITHTM_TAIL_ROWS": "0"}),
+                                            (100, {"BITHTM_TAIL_ROWS": "0", "BITHTM_DEFER_TAIL": "0"})],
+                         ids=lambda v: ",".join(f"{k[7:]}={x}" for k, x in v.items()) or "default" if isinstance(v, dict) else str(v))
+def test_host_fed_steps_by_input_width_and_tail_rows_agree_with_the_oracle(input_dim, env, K, monkeypatch):
+    """process() in lock-step with the oracle where a host-fed step takes another path: an input one packed word wider than a
+    launch's arguments hold (2080 bits = 65 words: staged by a copy, the last launch not held back), one exactly as wide (2048),
+    and the permanence rows kept out of the last launch (BITHTM_TAIL_ROWS=0; with BITHTM_DEFER_TAIL=0 the step that knob is
+    read by).  Twelve steps with learning, every output each step, the stores every fourth."""
+    from hip_impl import lockstep_vs_oracle
+    for k, v in env.items():
+        monkeypatch.setenv(k, v)
+    lockstep_vs_oracle(seed=60 + K, input_dim=input_dim, column_dim=512, cell_dim=K, patterns=5, density=0.1, noise=0.02, steps=12, store_every=4)
+
+
 def test_prev_state_adoption_keeps_the_sticky_capacity_flags():
     """TemporalMemory.process(prev_state=X) writes X back through the state import; that must not forgive an overflow of
     the segment pool the handle keeps (the import of a checkpoint, which replaces the store, does)."""
