@@ -8,6 +8,7 @@ import numpy as np
 
 STREAM_LEAST_USED, STREAM_GROWTH, STREAM_SEGMENT_JITTER = 1, 2, 3
 STREAM_INPUT_NOISE = 6                              # (4 and 5: the pre-populated pools of htm_populate, device only)
+STREAM_FIELD_HASH = 7                               # the bit positions of a hashed encoder field (encoders.HashedField): a = index, step 0
 
 _M1, _M2 = np.uint32(0x7FEB352D), np.uint32(0x846CA68B)
 
@@ -29,3 +30,11 @@ def draw_unit(seed, stream, step, a, b=0):
         base = _mix32(base ^ np.uint32(int(step) & 0xFFFFFFFF))
         h = _mix32(_mix32(base ^ np.asarray(a).astype(np.uint32)) ^ np.asarray(b).astype(np.uint32))
     return (h >> np.uint32(8)).astype(np.float64) * (1.0 / 16777216.0)
+
+
+def draw32(seed, stream, step, a, b=0):
+    """htm_draw32(htm_stream_base(seed, stream, step), a, b) as uint32; `a`, `b` broadcast."""
+    with np.errstate(over="ignore"):
+        base = _mix32(np.uint32((int(seed) + int(stream) * 0x9E3779B9) & 0xFFFFFFFF))
+        base = _mix32(base ^ np.uint32(int(step) & 0xFFFFFFFF))
+        return _mix32(_mix32(base ^ np.asarray(a).astype(np.uint32)) ^ np.asarray(b).astype(np.uint32))

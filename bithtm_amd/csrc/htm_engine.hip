@@ -51,6 +51,7 @@
 #include "htm_fork.h"
 #include "htm_scalar.h"
 #include "htm_live.h"
+#include "htm_fields.h"
 #include "htm_likelihood.h"
 
 // ------------------------------------------------------------------------------------------
@@ -3451,16 +3452,34 @@ static int scalar_table(htm_handle *h, const char *what, const htm_scalar_field 
     for (int j = 0; j < n_fields; ++j) {
         const htm_scalar_field &f = fields[j];
         const std::string fj = who + ": field " + std::to_string(j);
-        if (f.bits < 1 || f.width < 1 || f.width > f.bits) { h->err = fj + ": bits >= 1 and 1 <= width <= bits"; return HTM_ERR_ARGUMENT; }
-        if (f.buckets != (f.periodic ? f.bits : f.bits - f.width + 1)) { h->err = fj + ": buckets must be bits (periodic) or bits - width + 1"; return HTM_ERR_ARGUMENT; }
+        // the kind (htm_fields.h): reserved == 0 is a linear field, as every call before the kinds existed passed it
+        if (f.reserved < 0 || (f.reserved & 3) == 3) { h->err = fj + ": reserved must be 0, or a field kind (1 category, 2 hashed) with a hashed field's seed above it"; return HTM_ERR_ARGUMENT; }
+        const int kind = f.reserved & 3;
+        if (kind != HTM_FIELD_HASHED && (f.reserved >> 2) != 0) { h->err = fj + ": a seed on a field that is not hashed"; return HTM_ERR_ARGUMENT; }
+        if (kind != HTM_FIELD_LINEAR && f.periodic != 0) { h->err = fj + ": only a linear field can be periodic"; return HTM_ERR_ARGUMENT; }
+        if (f.bits < 1 || f.width < 1) { h->err = fj + ": bits >= 1 and width >= 1"; return HTM_ERR_ARGUMENT; }
+        if (kind == HTM_FIELD_LINEAR) {
+            if (f.width > f.bits) { h->err = fj + ": bits >= 1 and 1 <= width <= bits"; return HTM_ERR_ARGUMENT; }
+            if (f.buckets != (f.periodic ? f.bits : f.bits - f.width + 1)) { h->err = fj + ": buckets must be bits (periodic) or bits - width + 1"; return HTM_ERR_ARGUMENT; }
+        } else if (kind == HTM_FIELD_CATEGORY) {
+            if (f.buckets < 1 || (long long)f.buckets * f.width > (long long)f.bits) { h->err = fj + ": a category field needs buckets >= 1 and buckets * width <= bits"; return HTM_ERR_ARGUMENT; }
+        } else {
+            if (f.buckets < 1 || f.width > HTM_HASHED_MAX_WIDTH || f.buckets > INT32_MAX - HTM_HASHED_MAX_WIDTH) {
+                h->err = fj + ": a hashed field needs buckets >= 1 (below 2^31 - " + std::to_string(HTM_HASHED_MAX_WIDTH) + ") and width <= " + std::to_string(HTM_HASHED_MAX_WIDTH);
+                return HTM_ERR_ARGUMENT;
+            }
+            if (decoding && (long long)f.buckets + f.width - 1 > HTM_DECODE_MAX_BITS) {
+                h->err = fj + ": buckets + width - 1 above " + std::to_string(HTM_DECODE_MAX_BITS) + " (the decode launch's LDS)";
+                return HTM_ERR_ARGUMENT;
+            }
+        }
         if (f.offset < 0 || (long long)f.offset + f.bits > (long long)h->d.I) { h->err = fj + ": reaches outside the input row"; return HTM_ERR_ARGUMENT; }
         if (!std::isfinite(f.minimum) || !std::isfinite(f.scale) || !(f.scale > 0.0)) { h->err = fj + ": minimum and scale must be finite, scale above 0"; return HTM_ERR_ARGUMENT; }
-        if (decoding && f.bits > HTM_DECODE_MAX_BITS) { h->err = fj + ": more than " + std::to_string(HTM_DECODE_MAX_BITS) + " bits (the decode launch's LDS)"; return HTM_ERR_ARGUMENT; }
+        if (decoding && kind != HTM_FIELD_HASHED && f.bits > HTM_DECODE_MAX_BITS) { h->err = fj + ": more than " + std::to_string(HTM_DECODE_MAX_BITS) + " bits (the decode launch's LDS)"; return HTM_ERR_ARGUMENT; }
         for (int i = 0; i < j; ++i)
             if (f.offset < fields[i].offset + fields[i].bits && fields[i].offset < f.offset + f.bits) { h->err = fj + ": overlaps field " + std::to_string(i); return HTM_ERR_ARGUMENT; }
         tab->f[j] = f;
-        tab->f[j].periodic = f.periodic != 0;
-        tab->f[j].reserved = 0;
+        tab->f[j].periodic = f.periodic != 0;       // (reserved stays: the kind and the seed, 0 for a linear field)
     }
     return 0;
 }
@@ -3481,7 +3500,10 @@ extern "C" int htm_bank_encode(htm_handle *h, const htm_scalar_field *fields, in
     if (((uintptr_t)device_bank & 15) != 0 || ((uintptr_t)device_values & 7) != 0) { h->err = "htm_bank_encode: the bank must be 16-byte aligned, the values 8-byte"; return HTM_ERR_ARGUMENT; }
     if (n_rows == 0) return HTM_OK;
     HIPCHK(h, hipSetDevice(h->device));
-    LAUNCH(h, "bank_encode", k_bank_encode, n_rows, scalar_encode_threads(h->d.W), h->d, tab, (int)n_fields, device_values, device_bank, (int)first_row);
+    if (fields_mixed(tab.f, n_fields))
+        LAUNCH(h, "bank_encode", kenc_bank, n_rows, scalar_encode_threads(h->d.W), h->d, tab, (int)n_fields, device_values, device_bank, (int)first_row);
+    else
+        LAUNCH(h, "bank_encode", k_bank_encode, n_rows, scalar_encode_threads(h->d.W), h->d, tab, (int)n_fields, device_values, device_bank, (int)first_row);
     return launch_status(h->err);
 }
 
@@ -3496,7 +3518,10 @@ extern "C" int htm_decode_votes(htm_handle *h, const htm_scalar_field *fields, i
     if (n_rows < 0) { h->err = "htm_decode_votes: n_rows must not be negative"; return HTM_ERR_ARGUMENT; }
     if (n_rows == 0) return HTM_OK;
     HIPCHK(h, hipSetDevice(h->device));
-    LAUNCH(h, "decode_votes", k_decode_votes, dim3(n_rows, n_fields), SCALAR_THREADS, tab, (int)n_fields, h->d.I, device_votes, device_out);
+    if (fields_mixed(tab.f, n_fields))
+        LAUNCH(h, "decode_votes", kenc_votes, dim3(n_rows, n_fields), SCALAR_THREADS, tab, (int)n_fields, h->d.I, device_votes, device_out);
+    else
+        LAUNCH(h, "decode_votes", k_decode_votes, dim3(n_rows, n_fields), SCALAR_THREADS, tab, (int)n_fields, h->d.I, device_votes, device_out);
     return launch_status(h->err);
 }
 
@@ -3521,7 +3546,10 @@ extern "C" int htm_predicted_value(htm_handle *h, const htm_scalar_field *fields
     if (!h->d_value_out) { rc = dalloc(h, &h->d_value_out, 2 * HTM_SCALAR_MAX_FIELDS); if (rc) return rc; }
     HIPCHK(h, hipMemsetAsync(h->d_pin_buf, 0, (size_t)d.I * 4, h->stream));
     LAUNCH(h, "predicted_input", k_pin, pin_blocks(d.C), 256, d, (int)((h->step_host + 1) & 1), h->d_pin_buf);
-    LAUNCH(h, "decode_votes", k_decode_votes, dim3(1, n_fields), SCALAR_THREADS, tab, (int)n_fields, d.I, (const int32_t *)h->d_pin_buf, h->d_value_out);
+    if (fields_mixed(tab.f, n_fields))
+        LAUNCH(h, "decode_votes", kenc_votes, dim3(1, n_fields), SCALAR_THREADS, tab, (int)n_fields, d.I, (const int32_t *)h->d_pin_buf, h->d_value_out);
+    else
+        LAUNCH(h, "decode_votes", k_decode_votes, dim3(1, n_fields), SCALAR_THREADS, tab, (int)n_fields, d.I, (const int32_t *)h->d_pin_buf, h->d_value_out);
     rc = launch_status(h->err);
     if (rc) return rc;
     HIPCHK(h, hipMemcpyAsync(host_out, h->d_value_out, (size_t)n_fields * 8, hipMemcpyDeviceToHost, h->stream));
@@ -4251,7 +4279,11 @@ static int live_tick(htm_group *g, const double *values, const htm_scalar_field 
     if (resetting) LAUNCH_ON(h0, s, 0, "live:reset", klive_reset, dim3(reset_blocks(d), B), 256, g->d_tab, (const int32_t *)(lv.d_stage + lv.off_flags));
     LAUNCH_ON(h0, s, 0, "group:record", kgrp_rec_clear, B, 64, g->d_recs);
     LAUNCH_ON(h0, s, 0, "group:record", kgrp_rec_begin, dim3(rec_blocks(d), B), 256, g->d_tab, p ^ 1, g->d_recs, (const GrpRecArgs *)lv.rec_args, 1);
-    if (values)
+    const bool mixed = values && fields_mixed(ftab.f, n_fields);      // (a table with a category or hashed field: the twins of htm_fields.h)
+    if (values && mixed)
+        LAUNCH_ON(h0, s, 0, "live:encode", kenc_bank, B, scalar_encode_threads(d.W), d, ftab, (int)n_fields, (const double *)(lv.d_stage + lv.off_values),
+                  (uint32_t *)lv.d_stage, 0);
+    else if (values)
         LAUNCH_ON(h0, s, 0, "live:encode", k_bank_encode, B, scalar_encode_threads(d.W), d, ftab, (int)n_fields, (const double *)(lv.d_stage + lv.off_values),
                   (uint32_t *)lv.d_stage, 0);
     const bool decoding = decoded || votes;
@@ -4270,9 +4302,14 @@ static int live_tick(htm_group *g, const double *values, const htm_scalar_field 
     } else {
         group_enqueue_step(g, modes, lv.bank_tab, 1, learning, p, f);
     }
-    LAUNCH_ON(h0, s, 0, "live:finish", klive_finish, dim3(std::max(n_dec, 1), B), SCALAR_THREADS, g->d_tab, p, ftab, n_dec,
-              (const int32_t *)(lv.d_out + lv.off_votes), (const htm_step_record *)lv.d_recs, (htm_live_row *)(lv.d_out + lv.off_rows),
-              (int32_t *)(lv.d_out + lv.off_pairs));
+    if (mixed)
+        LAUNCH_ON(h0, s, 0, "live:finish", kenc_finish, dim3(std::max(n_dec, 1), B), SCALAR_THREADS, g->d_tab, p, ftab, n_dec,
+                  (const int32_t *)(lv.d_out + lv.off_votes), (const htm_step_record *)lv.d_recs, (htm_live_row *)(lv.d_out + lv.off_rows),
+                  (int32_t *)(lv.d_out + lv.off_pairs));
+    else
+        LAUNCH_ON(h0, s, 0, "live:finish", klive_finish, dim3(std::max(n_dec, 1), B), SCALAR_THREADS, g->d_tab, p, ftab, n_dec,
+                  (const int32_t *)(lv.d_out + lv.off_votes), (const htm_step_record *)lv.d_recs, (htm_live_row *)(lv.d_out + lv.off_rows),
+                  (int32_t *)(lv.d_out + lv.off_pairs));
     // a scored tick: every member's stream of the likelihood object takes the step's record, behind the finish launch
     if (lk) LAUNCH_ON(h0, s, 0, "live:likelihood", klik_tick, dim3(1, B), HTM_LIKELIHOOD_THREADS, lk->d, (const htm_step_record *)lv.d_recs, (double *)lv.d_out);
     for (htm_handle *h : g->m) {

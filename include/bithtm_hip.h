@@ -783,9 +783,39 @@ int htm_sp_run(htm_handle *h, const uint32_t *device_inputs, int32_t n_inputs, i
  * that overlap; a minimum or scale that is not finite, or scale <= 0; n_rows < 0; first_row < 0 or first_row + n_rows >
  * bank_rows; a bank that is not 16-byte aligned (values: 8-byte); for the two decoding calls a field of more than
  * HTM_DECODE_MAX_BITS bits (the prefix sums of a field live in the decode block's LDS).  HTM_ERR_STATE: a handle without the
- * device's Spatial Pooler. */
+ * device's Spatial Pooler.
+ *
+ * Field kinds.  The member `reserved` carries the kind of a field:
+ *   reserved == 0     a linear field: all of the above, bit for bit
+ *   reserved & 3      the kind otherwise: HTM_FIELD_CATEGORY (1) or HTM_FIELD_HASHED (2); 3 is refused
+ *   reserved >> 2     the seed of a hashed field, 0 <= seed < 2^29; it must be 0 for any other kind
+ * A category field has `buckets` categories of `width` bits each, buckets * width <= bits (trailing bits stay unused), and is
+ * passed with minimum 0 and scale 1:
+ *   bucket(v): t = (v - minimum) * scale as above; missing (-1) unless 0 <= floor(t) < buckets -- an unknown id, NaN and +-inf
+ *              are missing, NOT clamped
+ *   encode:    bucket c sets the bits offset + c * width + j, j < width: no two categories share a bit
+ *   decode:    score[c] = sum over j < width of votes[offset + c * width + j]
+ * A hashed field (a random distributed scalar field) has any `buckets` >= 1 over its `bits`, 1 <= width <=
+ * HTM_HASHED_MAX_WIDTH (width may exceed bits), scale = buckets / (maximum - minimum):
+ *   bucket(v): that of a non-periodic linear field
+ *   pos(i)   = ((uint64_t)htm_draw32(htm_stream_base(seed, 7, 0), i, 0) * bits) >> 32 for i in [0, buckets + width - 1): the
+ *              keyed hash of bithtm_amd/csrc/htm_rng.h, stream 7
+ *   encode:    bucket b sets the bits offset + pos(b + j), j < width; positions may collide, so fewer than width bits may be set
+ *   decode:    G[i] = votes[offset + pos(i)], score[b] = G[b] + ... + G[b + width - 1] (a collided bit counts once per j)
+ * Both decode to the lowest bucket with the largest score, (-1, 0) where that score is 0, as a linear field.
+ * HTM_ERR_ARGUMENT, nothing enqueued, besides the cases above (which hold for every kind, `width <= bits` and `buckets` as
+ * defined for linear fields only): reserved < 0; kind 3; a seed on a field that is not hashed; periodic != 0 on a field that is
+ * not linear; a category field with buckets < 1 or buckets * width > bits; a hashed field with buckets < 1 or width >
+ * HTM_HASHED_MAX_WIDTH; for the decoding calls a hashed field with buckets + width - 1 > HTM_DECODE_MAX_BITS (this replaces the
+ * cap on `bits` for a hashed field: its prefix sums run over positions, not bits).
+ * A caller that left garbage in `reserved` sees a difference to earlier builds of ABI version 4, which ignored the member;
+ * a caller that zeroed it, as documented, sees none. */
 #define HTM_SCALAR_MAX_FIELDS 16
 #define HTM_DECODE_MAX_BITS 8192
+#define HTM_HASHED_MAX_WIDTH 256
+#define HTM_FIELD_LINEAR 0
+#define HTM_FIELD_CATEGORY 1
+#define HTM_FIELD_HASHED 2
 typedef struct htm_scalar_field {
     double minimum, scale;
     int32_t offset, bits, width, buckets, periodic, reserved;
