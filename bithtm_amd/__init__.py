@@ -7,8 +7,9 @@ The classes are host-side shells around hand-written HIP kernels for gfx950 reac
 C ABI (include/bithtm_hip.h, libbithtm_hip.so).  There is no CPU fallback: importing the
 engine without the built library raises ImportError."""
 
-from . import encoders, likelihood, networks
+from . import classifier, encoders, likelihood, networks
 from .anomaly import AnomalyLikelihood  # noqa: F401
+from .sdr_classifier import SDRClassifier  # noqa: F401
 from .encoders import CategoryField, HashedField, ScalarEncoder, ScalarField, date_fields, date_values  # noqa: F401
 from .networks import InferenceView, flip_noise, noise_threshold  # noqa: F401
 from .engine import CapacityError, HtmError  # noqa: F401

@@ -69,6 +69,15 @@ class HtmLikelihoodConfig(C.Structure):
         "learning_period", "estimation_samples", "history", "averaging_window", "reestimation_period")]
 
 
+class HtmClassifierConfig(C.Structure):
+    """htm_classifier_config: the SDR classifier's parameters (buckets, the horizons, the learning rate in units of 2^-16, the
+    patterns' geometry and the most pairs a pattern may have)."""
+    _fields_ = [("struct_bytes", C.c_uint32)] + [(name, C.c_int32) for name in (
+        "buckets", "n_steps", "alpha_q", "units", "cell_dim", "max_pairs")] + [("steps", C.c_int32 * 8)]
+
+
+CLASSIFIER_CHUNK = 512                      # HTM_CLASSIFIER_CHUNK (csrc/htm_classifier.h): steps per launch of a frozen htm_classifier_update
+CLASSIFIER_PAIRS = 16                       # HTM_CLASSIFIER_PAIRS: pairs of a pattern per block
 LIKELIHOOD_CHUNK = 512                      # HTM_LIKELIHOOD_CHUNK (csrc/htm_likelihood.h): steps per launch of htm_likelihood_update
 
 # htm_field
@@ -163,6 +172,17 @@ EXPORTS = {
     "htm_likelihood_import": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]),
     "htm_likelihood_tick": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(HtmScalarField), C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "htm_classifier_create": (C.c_int, [C.c_void_p, C.POINTER(HtmClassifierConfig), C.c_void_p, C.POINTER(C.c_void_p)]),
+    "htm_classifier_destroy": (None, [C.c_void_p]),
+    "htm_classifier_update": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p,
+                                        C.c_int32, C.c_void_p, C.c_void_p]),
+    "htm_classifier_reset": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "htm_classifier_read_weights": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
+    "htm_classifier_write_weights": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
+    "htm_classifier_state_bytes": (C.c_int64, [C.c_void_p]),
+    "htm_classifier_export": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]),
+    "htm_classifier_import": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]),
+    "htm_set_run_active_cells": (C.c_int, [C.c_void_p, C.c_void_p]),
 }
 
 # The HIP runtime calls the binding makes itself -- the device buffers of run(record=...) -- resolved through the library's own

@@ -11,7 +11,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libbithtm_hip.so")
 RESOURCES = os.path.join(HERE, "libbithtm_hip.resources.json")     # what the compiler gave every kernel (written beside the library)
 SOURCES = ["htm_engine.hip"]
-HEADERS = ["htm_dev.h", "htm_sp_kernels.h", "htm_tm_kernels.h", "htm_pipeline.h", "htm_record.h", "htm_reset.h", "htm_decode.h", "htm_stack.h", "htm_forecast.h", "htm_noise.h", "htm_group.h", "htm_tm_feed.h", "htm_sp_run.h", "htm_fork.h", "htm_scalar.h", "htm_live.h", "htm_fields.h", "htm_likelihood.h", "htm_rng.h", "htm_fexp.h",
+HEADERS = ["htm_dev.h", "htm_sp_kernels.h", "htm_tm_kernels.h", "htm_pipeline.h", "htm_record.h", "htm_reset.h", "htm_decode.h", "htm_stack.h", "htm_forecast.h", "htm_noise.h", "htm_group.h", "htm_tm_feed.h", "htm_sp_run.h", "htm_fork.h", "htm_scalar.h", "htm_live.h", "htm_fields.h", "htm_likelihood.h", "htm_classifier.h", "htm_rng.h", "htm_fexp.h",
            os.path.join("..", "..", "include", "bithtm_hip.h")]
 # -ffp-contract=off: several kernels must round exactly like the NumPy expressions they replace
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off",

@@ -53,6 +53,7 @@
 #include "htm_live.h"
 #include "htm_fields.h"
 #include "htm_likelihood.h"
+#include "htm_classifier.h"
 
 // ------------------------------------------------------------------------------------------
 // host side
@@ -91,7 +92,10 @@ struct Sizes {
 // (begin_run_modes, group_begin_modes).  Whatever enqueues or captures a step takes them by value; a host-fed step has none.
 struct RunModes {
     bool recording, resetting, decoding, feeding;
-    bool operator<(const RunModes &o) const { return std::tie(recording, resetting, decoding, feeding) < std::tie(o.recording, o.resetting, o.decoding, o.feeding); }
+    bool capturing = false;               // htm_set_run_active_cells: a recorded htm_run whose steps leave their active-cell words
+    bool operator<(const RunModes &o) const {
+        return std::tie(recording, resetting, decoding, feeding, capturing) < std::tie(o.recording, o.resetting, o.decoding, o.feeding, o.capturing);
+    }
 };
 
 // What the launches of a captured graph depend on besides the handle's fixed sizes.  htm_run: the step's parity, the call's
@@ -174,6 +178,10 @@ struct htm_handle {
     PinDev *d_pin;
     int32_t *d_pin_buf;
     int32_t *d_value_out;                           // htm_predicted_value: the (bucket, score) pairs of its decode launch
+    // pattern capture (htm_set_run_active_cells): the caller's device rows and the device descriptor the capture launches read
+    // (filled when the rows are set)
+    void *cap_out = nullptr;
+    ClsCapDev *d_cap = nullptr;
     // run feedback (htm_set_run_feedback): the bank whose runs write their next row and its size, the device descriptor the
     // feedback launches read (filled when the feedback is set), and the scratch votes row (zero between uses: htm_forecast.h)
     uint32_t *feed_bank;
@@ -701,6 +709,9 @@ static void enqueue_rest(htm_handle *h, RunModes m, int p, const uint32_t *bank,
     }
 }
 
+// grid of the capture launch: a thread per pair of the step's row
+static int cap_blocks(const Dev &d) { return std::max(1, (d.k * d.WPC + 255) / 256); }
+
 // grid of the record launches (htm_record.h): REC_BLOCKS_MIN, or more where the winner list needs a thread per entry
 static int rec_blocks(const Dev &d) { return std::max(REC_BLOCKS_MIN, (d.k + 255) / 256); }
 
@@ -730,9 +741,15 @@ static void enqueue_feed(htm_handle *h, RunModes m, int p) {
 // grid of the launch that zeroes a decoding call's n x I votes (grid-stride)
 static int pin_begin_blocks(int n, int I) { return (int)std::max<size_t>(1, std::min<size_t>(1024, ((size_t)n * I + 255) / 256)); }
 
+// the active-cell words of the step of parity p, directly behind its record launch (htm_classifier.h); nothing outside a capturing call
+static void enqueue_capture(htm_handle *h, RunModes m, int p) {
+    if (m.capturing) LAUNCH(h, "active_cells", kcls_capture, cap_blocks(h->d), 256, h->d, p, (const RecDev *)h->d_rec, (const ClsCapDev *)h->d_cap);
+}
+
 // everything behind a step's own launches that the call's modes ask for
 static void enqueue_step_outputs(htm_handle *h, RunModes m, int p) {
     enqueue_record(h, m, p);
+    enqueue_capture(h, m, p);
     enqueue_decode(h, m, p);
     enqueue_feed(h, m, p);
 }
@@ -1971,7 +1988,7 @@ static int begin_run_modes(htm_handle *h, int n_bank, int n_steps, bool recorded
         if (!h->d_pin && (rc = dalloc(h, &h->d_pin, 1))) return rc;
         if (launch) LAUNCH(h, "predicted_input", k_pin_begin, pin_begin_blocks(n_steps, h->d.I), 256, h->d_pin, h->pin_out, (uint32_t)h->step_host, n_steps, h->d.I);
     }
-    *modes = RunModes{recorded, h->reset_bits != nullptr, h->pin_out != nullptr, h->feed_bank != nullptr};
+    *modes = RunModes{recorded, h->reset_bits != nullptr, h->pin_out != nullptr, h->feed_bank != nullptr, recorded && h->cap_out != nullptr};
     return 0;
 }
 
@@ -1983,6 +2000,7 @@ static int run_or_prepare(htm_handle *h, const RunCall &c) {
     if (!h || !c.bank || c.n_inputs < 1 || c.n_steps < 0) return HTM_ERR_ARGUMENT;
     if (!h->cfg.enable_sp || !h->cfg.enable_tm) { h->err = "htm_run needs a handle with SP and TM"; return HTM_ERR_STATE; }
     if (h->world > 1) { h->err = "sharded handle: use htm_shard_begin / htm_shard_finish"; return HTM_ERR_STATE; }
+    if (h->cap_out && !c.recorded) { h->err = "htm_run: active-cell rows are set (htm_set_run_active_cells): only a recorded run fills them"; return HTM_ERR_ARGUMENT; }
     HIPCHK(h, hipSetDevice(h->device));
     if (int rc = view_enter(h, c.learning)) return rc;
     const int n_inputs = c.n_inputs, learning = c.learning ? 1 : 0;
@@ -2150,6 +2168,7 @@ extern "C" int htm_tm_run(htm_handle *h, const int32_t *device_lists, int32_t n_
     REJECT_WHEN_AHEAD(h);
     if (h->shard_open || h->phase_open) { h->err = "htm_tm_run: a step of the handle is open (htm_shard_begin / htm_sp_phase)"; return HTM_ERR_STATE; }
     if (h->pin_out || h->feed_bank) { h->err = "htm_tm_run: decoding rows or run feedback are set (htm_set_run_predicted_input, htm_set_run_feedback)"; return HTM_ERR_STATE; }
+    if (h->cap_out) { h->err = "htm_tm_run: active-cell rows are set (htm_set_run_active_cells): only a recorded htm_run fills them"; return HTM_ERR_STATE; }
     // (k_rec_step sums its counts in 24-bit fields of one word: RecDev::acc)
     if (rec && d.C >= (1 << 24)) { h->err = "htm_tm_run: a recorded run needs column_dim below 2^24"; return HTM_ERR_STATE; }
     if (feed_lds(d) > FEED_LDS_MAX) { h->err = "htm_tm_run: the column bitmap of this handle does not fit the LDS (column_dim above 524032)"; return HTM_ERR_ARGUMENT; }
@@ -3315,6 +3334,20 @@ extern "C" int htm_set_run_predicted_input(htm_handle *h, int32_t *device_votes)
     return HTM_OK;
 }
 
+// Pattern capture (htm_classifier.h, kcls_capture): the rows go into the device descriptor here, on the handle's stream, from the
+// call's own word (read when the copy returns) -- the runs that follow, and the graphs they replay, read them through it
+extern "C" int htm_set_run_active_cells(htm_handle *h, void *device_pairs) {
+    if (!h) return HTM_ERR_ARGUMENT;
+    if (!device_pairs) { h->cap_out = nullptr; return HTM_OK; }
+    if (int rc = pin_refuse(h, "htm_set_run_active_cells")) return rc;
+    HIPCHK(h, hipSetDevice(h->device));
+    if (!h->d_cap) { if (int rc = dalloc(h, &h->d_cap, 1)) return rc; }
+    const ClsCapDev cap{(ClsPair *)device_pairs};
+    HIPCHK(h, hipMemcpyAsync(h->d_cap, &cap, sizeof(cap), hipMemcpyHostToDevice, h->stream));
+    h->cap_out = device_pairs;
+    return HTM_OK;
+}
+
 // After the held-back tail: the output row zeroed, one launch, a synchronising copy (as htm_read)
 extern "C" int htm_predicted_input(htm_handle *h, int32_t *host_dst) {
     if (!h || !host_dst) return HTM_ERR_ARGUMENT;
@@ -3894,6 +3927,7 @@ static int group_check(htm_group *g, const uint32_t *const *banks, const htm_run
         if (sp_is_ahead(h)) { g->err = who + ": the Spatial Pooler is ahead (htm_run ended with HTM_RUN_CONTINUE)"; return HTM_ERR_STATE; }
         if (h->shard_open) { g->err = who + " has a step open"; return HTM_ERR_STATE; }
         if (h->reset_bits) { g->err = who + " has run reset bits set (htm_set_run_resets): sequence resets inside a group run are not available"; return HTM_ERR_STATE; }
+        if (h->cap_out) { g->err = who + " has active-cell rows set (htm_set_run_active_cells): pattern capture inside a group call is not available"; return HTM_ERR_STATE; }
         if ((h->step_host & 1) != (h0->step_host & 1)) {
             g->err = who + " is at step " + std::to_string(h->step_host) + ", member 0 at step " + std::to_string(h0->step_host) +
                      ": a group steps members of the same step parity only";
@@ -4174,6 +4208,210 @@ extern "C" int htm_likelihood_import(htm_likelihood *lk, htm_handle *h, const vo
     HIPCHK(h, hipSetDevice(lk->device));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     HIPCHK(h, hipMemcpy(lk->state, host_state, lk->bytes, hipMemcpyHostToDevice));
+    return HTM_OK;
+}
+
+// ------------------------------------------------------------------------------------------
+// SDR classifier (htm_classifier.h): the weights, the ring of recent patterns, the count of patterns since the
+// history was emptied and the per-step accumulators in device memory; the total step count, which names the ring's slots, on the
+// host.  As the likelihood object it keeps nothing of the handles its calls come through.
+struct htm_classifier {
+    int device = 0;
+    ClsDev d{};
+    ClsFrozen frozen{};                         // allocated by the first frozen call
+    int64_t total = 0;
+    size_t ring_bytes = 0;
+    std::vector<void *> allocs;
+};
+
+static int cls_refuse(htm_handle *h, const std::string &msg, int code) {
+    if (h) h->err = msg; else g_create_error = msg;
+    return code;
+}
+
+extern "C" void htm_classifier_destroy(htm_classifier *clf) {
+    if (!clf) return;
+    hipSetDevice(clf->device);
+    for (void *p : clf->allocs) hipFree(p);     // (hipFree waits for the device: nothing enqueued still reads them)
+    delete clf;
+}
+
+// zeroed device memory of the object's, ordered on h's stream (null: the allocation failed)
+template <typename T>
+static T *cls_alloc(htm_classifier *clf, htm_handle *h, size_t count) {
+    void *p = nullptr;
+    if (hipMalloc(&p, std::max<size_t>(count, 1) * sizeof(T)) != hipSuccess) return nullptr;
+    clf->allocs.push_back(p);
+    if (hipMemsetAsync(p, 0, std::max<size_t>(count, 1) * sizeof(T), h->stream) != hipSuccess) return nullptr;
+    return (T *)p;
+}
+
+extern "C" int htm_classifier_create(htm_handle *h, const htm_classifier_config *cfg, const int32_t *exp_table2049, htm_classifier **out) {
+    if (out) *out = nullptr;
+    if (!h || !cfg || !exp_table2049 || !out) return cls_refuse(h, "htm_classifier_create: null argument", HTM_ERR_ARGUMENT);
+    if (cfg->struct_bytes != sizeof(htm_classifier_config)) return cls_refuse(h, "htm_classifier_create: htm_classifier_config size mismatch", HTM_ERR_ARGUMENT);
+    bool ok = cfg->buckets >= 1 && cfg->buckets <= HTM_CLASSIFIER_MAX_BUCKETS && cfg->n_steps >= 1 && cfg->n_steps <= HTM_CLASSIFIER_MAX_HORIZONS &&
+              cfg->alpha_q >= 1 && cfg->alpha_q <= 65536 && cfg->cell_dim >= 1 && cfg->cell_dim <= 64 && cfg->units >= cfg->cell_dim &&
+              cfg->units % cfg->cell_dim == 0 && cfg->max_pairs >= 1;
+    for (int i = 0; ok && i < cfg->n_steps; ++i)
+        ok = cfg->steps[i] >= 0 && cfg->steps[i] <= HTM_CLASSIFIER_MAX_HORIZON && (i == 0 || cfg->steps[i] > cfg->steps[i - 1]);
+    if (!ok)
+        return cls_refuse(h, "htm_classifier_create: buckets in [1, 1024], 1 to 8 ascending steps in [0, 64], alpha_q in [1, 65536], cell_dim in [1, 64], "
+                             "units a positive multiple of cell_dim, max_pairs >= 1", HTM_ERR_ARGUMENT);
+    if (h->world > 1) return cls_refuse(h, "htm_classifier_create: not available on a column-sharded handle", HTM_ERR_STATE);
+    HIPCHK(h, hipSetDevice(h->device));
+    htm_classifier *clf = new htm_classifier();
+    clf->device = h->device;
+    ClsDev &d = clf->d;
+    d.B = cfg->buckets;
+    d.B_pad = (cfg->buckets + 3) & ~3;
+    d.H = cfg->n_steps;
+    d.K = cfg->cell_dim;
+    d.WPC = (cfg->cell_dim + 31) / 32;
+    d.n_cols = cfg->units / cfg->cell_dim;
+    d.alpha_q = cfg->alpha_q;
+    d.max_pairs = cfg->max_pairs;
+    d.ring_len = cfg->steps[cfg->n_steps - 1] + 1;
+    for (int i = 0; i < d.H; ++i) d.steps[i] = cfg->steps[i];
+    d.w_stride = (int64_t)cfg->units * d.B_pad;
+    clf->ring_bytes = (size_t)d.ring_len * d.max_pairs * sizeof(ClsPair);
+    d.w = cls_alloc<int32_t>(clf, h, (size_t)d.H * (size_t)d.w_stride);
+    d.ring = cls_alloc<ClsPair>(clf, h, (size_t)d.ring_len * d.max_pairs);
+    d.count = cls_alloc<int64_t>(clf, h, 2);
+    d.acc = cls_alloc<int64_t>(clf, h, (size_t)d.H * 2 * d.B_pad);
+    d.ticket = cls_alloc<uint32_t>(clf, h, HTM_CLASSIFIER_MAX_HORIZONS);
+    d.delta = cls_alloc<int32_t>(clf, h, (size_t)d.H * d.B_pad);
+    d.learn = cls_alloc<int32_t>(clf, h, HTM_CLASSIFIER_MAX_HORIZONS);
+    int32_t *table = cls_alloc<int32_t>(clf, h, HTM_CLASSIFIER_EXP);
+    d.exp_table = table;
+    ok = d.w && d.ring && d.count && d.acc && d.ticket && d.delta && d.learn && table;
+    // an empty ring holds (-1, 0) pairs; the state and the table are there when the call returns, whatever stream the first update comes on
+    std::vector<ClsPair> empty((size_t)d.ring_len * d.max_pairs, ClsPair{-1, 0u});
+    ok = ok && hipMemcpyAsync(d.ring, empty.data(), clf->ring_bytes, hipMemcpyHostToDevice, h->stream) == hipSuccess &&
+         hipMemcpyAsync(table, exp_table2049, HTM_CLASSIFIER_EXP * sizeof(int32_t), hipMemcpyHostToDevice, h->stream) == hipSuccess &&
+         hipStreamSynchronize(h->stream) == hipSuccess;
+    if (!ok) {
+        htm_classifier_destroy(clf);
+        return cls_refuse(h, "htm_classifier_create: device allocation failed", HTM_ERR_HIP);
+    }
+    *out = clf;
+    return HTM_OK;
+}
+
+// what every call on an existing object checks of its handle
+static int cls_check(const char *what, htm_classifier *clf, htm_handle *h) {
+    if (!clf || !h) return cls_refuse(h, std::string(what) + ": null argument", HTM_ERR_ARGUMENT);
+    if (h->world > 1) return cls_refuse(h, std::string(what) + ": not available on a column-sharded handle", HTM_ERR_STATE);
+    if (h->device != clf->device) return cls_refuse(h, std::string(what) + ": the handle is on another device than the classifier", HTM_ERR_ARGUMENT);
+    return 0;
+}
+
+extern "C" int64_t htm_classifier_state_bytes(const htm_classifier *clf) { return clf ? (int64_t)(16 + clf->ring_bytes) : (int64_t)HTM_ERR_ARGUMENT; }
+
+// blocks along x of the launches that split a pattern of n pairs
+static int cls_blocks(int n_pairs) { return (n_pairs + HTM_CLASSIFIER_PAIRS - 1) / HTM_CLASSIFIER_PAIRS; }
+
+extern "C" int htm_classifier_update(htm_classifier *clf, htm_handle *h, const void *device_pairs, int32_t pairs_per_step, int32_t n_steps,
+                                     const int32_t *device_targets, int32_t n_targets, int32_t first_step, const uint32_t *device_reset_bits,
+                                     int32_t learn, int32_t *device_best, int32_t *device_dist) {
+    if (int rc = cls_check("htm_classifier_update", clf, h)) return rc;
+    if (!device_pairs || !device_targets || !device_best) return cls_refuse(h, "htm_classifier_update: null pairs, targets or output", HTM_ERR_ARGUMENT);
+    const ClsDev &d = clf->d;
+    if (pairs_per_step < 1 || pairs_per_step > d.max_pairs)
+        return cls_refuse(h, "htm_classifier_update: pairs_per_step must be in [1, max_pairs = " + std::to_string(d.max_pairs) + "]", HTM_ERR_ARGUMENT);
+    if (n_steps < 0 || n_targets < 1 || first_step < 0) return cls_refuse(h, "htm_classifier_update: n_steps >= 0, n_targets >= 1, first_step >= 0", HTM_ERR_ARGUMENT);
+    if (n_steps == 0) return HTM_OK;
+    HIPCHK(h, hipSetDevice(clf->device));
+    if (!learn && !clf->frozen.acc) {
+        ClsFrozen f;
+        f.acc = cls_alloc<int64_t>(clf, h, (size_t)HTM_CLASSIFIER_CHUNK * d.H * d.B_pad);
+        f.ticket = cls_alloc<uint32_t>(clf, h, (size_t)HTM_CLASSIFIER_CHUNK * d.H);
+        if (!f.acc || !f.ticket) return cls_refuse(h, "htm_classifier_update: device allocation failed", HTM_ERR_HIP);
+        clf->frozen = f;
+    }
+    const ClsStep s{(const ClsPair *)device_pairs, pairs_per_step, device_targets, device_reset_bits, n_targets, first_step, device_best, device_dist, clf->total};
+    if (learn) {
+        const dim3 grid(cls_blocks(d.max_pairs), d.H);
+        for (int i = 0; i < n_steps; ++i) {
+            LAUNCH(h, "classifier:sum", kcls_sum, grid, HTM_CLASSIFIER_THREADS, d, s, i);
+            LAUNCH(h, "classifier:apply", kcls_apply, grid, HTM_CLASSIFIER_THREADS, d, s, i);
+        }
+    } else {
+        for (int first = 0; first < n_steps; first += HTM_CLASSIFIER_CHUNK) {
+            const int n = std::min<int>(HTM_CLASSIFIER_CHUNK, n_steps - first);
+            LAUNCH(h, "classifier:frozen", kcls_frozen, dim3(cls_blocks(pairs_per_step), d.H * n), HTM_CLASSIFIER_THREADS, d, clf->frozen, s, first, n);
+        }
+    }
+    clf->total += n_steps;
+    return launch_status(h->err);
+}
+
+extern "C" int htm_classifier_reset(htm_classifier *clf, htm_handle *h) {
+    if (int rc = cls_check("htm_classifier_reset", clf, h)) return rc;
+    HIPCHK(h, hipSetDevice(clf->device));
+    HIPCHK(h, hipMemsetAsync(clf->d.count, 0, 16, h->stream));
+    return HTM_OK;
+}
+
+// the rows of one horizon's table a weights call names, or a refusal
+static int cls_rows(const char *what, htm_classifier *clf, htm_handle *h, int32_t horizon, int32_t unit0, int32_t n_units, const void *host) {
+    if (int rc = cls_check(what, clf, h)) return rc;
+    const ClsDev &d = clf->d;
+    const int64_t units = d.w_stride / d.B_pad;
+    if (!host || horizon < 0 || horizon >= d.H || unit0 < 0 || n_units < 0 || (int64_t)unit0 + n_units > units)
+        return cls_refuse(h, std::string(what) + ": need host memory, a horizon index below n_steps and rows inside the table", HTM_ERR_ARGUMENT);
+    return 0;
+}
+
+extern "C" int htm_classifier_read_weights(htm_classifier *clf, htm_handle *h, int32_t horizon, int32_t unit0, int32_t n_units, int32_t *host_dst) {
+    if (int rc = cls_rows("htm_classifier_read_weights", clf, h, horizon, unit0, n_units, host_dst)) return rc;
+    if (n_units == 0) return HTM_OK;
+    const ClsDev &d = clf->d;
+    HIPCHK(h, hipSetDevice(clf->device));
+    HIPCHK(h, hipMemcpy2DAsync(host_dst, (size_t)d.B * 4, d.w + (int64_t)horizon * d.w_stride + (int64_t)unit0 * d.B_pad, (size_t)d.B_pad * 4, (size_t)d.B * 4,
+                               (size_t)n_units, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return HTM_OK;
+}
+
+extern "C" int htm_classifier_write_weights(htm_classifier *clf, htm_handle *h, int32_t horizon, int32_t unit0, int32_t n_units, const int32_t *host_src) {
+    if (int rc = cls_rows("htm_classifier_write_weights", clf, h, horizon, unit0, n_units, host_src)) return rc;
+    const ClsDev &d = clf->d;
+    for (size_t i = 0; i < (size_t)n_units * d.B; ++i)
+        if (host_src[i] > HTM_CLASSIFIER_W_LIMIT || host_src[i] < -HTM_CLASSIFIER_W_LIMIT)
+            return cls_refuse(h, "htm_classifier_write_weights: a weight is outside [-2^30, 2^30]", HTM_ERR_ARGUMENT);
+    if (n_units == 0) return HTM_OK;
+    HIPCHK(h, hipSetDevice(clf->device));
+    // (the padding buckets of a row stay 0: nothing ever writes them)
+    HIPCHK(h, hipMemcpy2DAsync(d.w + (int64_t)horizon * d.w_stride + (int64_t)unit0 * d.B_pad, (size_t)d.B_pad * 4, host_src, (size_t)d.B * 4, (size_t)d.B * 4,
+                               (size_t)n_units, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return HTM_OK;
+}
+
+extern "C" int htm_classifier_export(htm_classifier *clf, htm_handle *h, void *host_state, int64_t bytes) {
+    if (int rc = cls_check("htm_classifier_export", clf, h)) return rc;
+    if (!host_state || bytes != htm_classifier_state_bytes(clf)) return cls_refuse(h, "htm_classifier_export: need host_state of htm_classifier_state_bytes bytes", HTM_ERR_ARGUMENT);
+    HIPCHK(h, hipSetDevice(clf->device));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    memcpy(host_state, &clf->total, 8);
+    HIPCHK(h, hipMemcpy((char *)host_state + 8, clf->d.count, 8, hipMemcpyDeviceToHost));
+    HIPCHK(h, hipMemcpy((char *)host_state + 16, clf->d.ring, clf->ring_bytes, hipMemcpyDeviceToHost));
+    return HTM_OK;
+}
+
+extern "C" int htm_classifier_import(htm_classifier *clf, htm_handle *h, const void *host_state, int64_t bytes) {
+    if (int rc = cls_check("htm_classifier_import", clf, h)) return rc;
+    if (!host_state || bytes != htm_classifier_state_bytes(clf)) return cls_refuse(h, "htm_classifier_import: need host_state of htm_classifier_state_bytes bytes", HTM_ERR_ARGUMENT);
+    int64_t head[2];
+    memcpy(head, host_state, 16);
+    // (a learning step looks count steps back in the ring: never before step 0)
+    if (head[1] < 0 || head[1] > head[0]) return cls_refuse(h, "htm_classifier_import: need 0 <= count <= total", HTM_ERR_ARGUMENT);
+    HIPCHK(h, hipSetDevice(clf->device));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    HIPCHK(h, hipMemcpy(clf->d.count, &head[1], 8, hipMemcpyHostToDevice));
+    HIPCHK(h, hipMemcpy(clf->d.ring, (const char *)host_state + 16, clf->ring_bytes, hipMemcpyHostToDevice));
+    clf->total = head[0];
     return HTM_OK;
 }
 

@@ -363,17 +363,17 @@ class Engine:
             self.set_epsilon(epsilon)
             self._epsilon = epsilon
 
-    def this_call(self, resets=None, n_inputs=0, feedback=None, votes=None):
+    def this_call(self, resets=None, n_inputs=0, feedback=None, votes=None, cells=None):
         """Settings that hold for the calls inside the block only, set in this order and cleared in reverse on the way out,
         whatever happens inside: `resets` (set_run_resets on banks of n_inputs rows), `feedback` (set_run_feedback's
-        arguments), `votes` (set_run_predicted_input).  None: left alone -- and with nothing to set, the plain run()'s case,
+        arguments), `votes` (set_run_predicted_input), `cells` (set_run_active_cells).  None: left alone -- and with nothing to set, the plain run()'s case,
         a block that costs nothing (streamed callers make a run() call per chunk)."""
-        if resets is None and feedback is None and votes is None:
+        if resets is None and feedback is None and votes is None and cells is None:
             return _NOTHING_TO_SET
-        return self._settings(resets, n_inputs, feedback, votes)
+        return self._settings(resets, n_inputs, feedback, votes, cells)
 
     @contextlib.contextmanager
-    def _settings(self, resets, n_inputs, feedback, votes):
+    def _settings(self, resets, n_inputs, feedback, votes, cells=None):
         undo = []
         try:
             if resets is not None:
@@ -385,6 +385,9 @@ class Engine:
             if votes is not None:
                 self.set_run_predicted_input(votes)
                 undo.append(lambda: self.set_run_predicted_input(None))
+            if cells is not None:
+                self.set_run_active_cells(cells)
+                undo.append(lambda: self.set_run_active_cells(None))
             yield
         finally:
             for clear in reversed(undo):
@@ -545,15 +548,15 @@ class Engine:
         return ptr.value
 
     def run(self, device_bank, n_inputs, n_steps, learning=True, use_graph=True, pipeline=True, continuing=False, record=None,
-            resets=None, encoder=None, likelihood=None):
+            resets=None, encoder=None, likelihood=None, classifier=None):
         """`resets`: None, or the device address of reset bits for this bank (upload_resets): a sequence reset before every
         step that reads a row whose bit is set (htm_set_run_resets, set for this call only).  `encoder`: the ScalarEncoder a
         "predicted_value" record decodes with."""
         with _NOTHING_TO_SET if resets is None else self.this_call(resets, n_inputs):
-            return self._run(device_bank, n_inputs, n_steps, learning, use_graph, pipeline, continuing, record, encoder, likelihood)
+            return self._run(device_bank, n_inputs, n_steps, learning, use_graph, pipeline, continuing, record, encoder, likelihood, classifier)
 
     def _run(self, device_bank, n_inputs, n_steps, learning=True, use_graph=True, pipeline=True, continuing=False, record=None,
-             encoder=None, likelihood=None):
+             encoder=None, likelihood=None, classifier=None):
         """`continuing`: the next call is another run() on the same bank (HTM_RUN_CONTINUE, include/bithtm_hip.h).
         `record`: None, or the fields of a per-step record to keep (RECORD_FIELDS): the call then goes to htm_run_recorded and
         returns {field: numpy array over the n_steps steps} -- "counters" int32[n, 8] (htm_step_record, RECORD_COUNTERS order),
@@ -562,29 +565,44 @@ class Engine:
         score) pairs of its F fields, decoded behind the run from the rows "predicted_input" uses, which stay on the device unless
         they were asked for too) -- read back after one synchronisation.  `likelihood` (an anomaly.AnomalyLikelihood of one stream;
         `record` has "counters"): its update over the counters' buffer is enqueued behind the run, before that synchronisation,
-        and "anomaly_likelihood" float64[n] is returned beside the fields."""
+        and "anomaly_likelihood" float64[n] is returned beside the fields.  `classifier` (`record` is not None): {"clf": an
+        sdr_classifier.SDRClassifier, "targets": device address of int32 [rows], "rows", "resets": device address of reset bits over
+        those rows or None, "learn", "distribution"} -- the run leaves each step's active-cell words in the classifier's pattern
+        buffer (htm_set_run_active_cells, set for this call only), the classifier's update is enqueued behind the run, before the
+        synchronisation, step i reading target and reset bit (step index + i) % rows, and "classified" int32[n, H, 2] and
+        "class_distribution" (int32[n, H, buckets] or None) are returned beside the fields."""
         if record is None:
             self.run_into(device_bank, n_inputs, n_steps, {}, learning, use_graph, pipeline, continuing)
             return None
         fields, n = self._record_fields(record), int(n_steps)
         buffers = self._record_buffers(fields, n, encoder)
-        self.run_into(device_bank, n_inputs, n, buffers, learning, use_graph, pipeline, continuing)
+        clf = classifier["clf"] if classifier is not None and n > 0 else None
+        cells, first = (clf.pairs_buffer(self, n), self.steps % classifier["rows"]) if clf is not None else (None, 0)
+        self.run_into(device_bank, n_inputs, n, buffers, learning, use_graph, pipeline, continuing, cells=cells)
         self.decode_records(buffers, n, encoder)
         if likelihood is not None and n > 0:
             likelihood.enqueue(self, [buffers["counters"]], n)
+        if clf is not None:
+            clf.enqueue(self, cells, clf.shape[2], n, classifier["targets"], classifier["rows"], first, classifier["resets"], classifier["learn"],
+                        classifier["distribution"])
         out = self._records_read(fields, n, sync=True, encoder=encoder)
         if likelihood is not None:
             out["anomaly_likelihood"] = likelihood.read(self, n)[0] if n > 0 else np.zeros(0, dtype=np.float64)
+        if classifier is not None:
+            c = classifier["clf"]
+            out["classified"], out["class_distribution"] = c.read(self, n, classifier["distribution"]) if n > 0 else (
+                np.zeros((0, len(c.steps), 2), np.int32), np.zeros((0, len(c.steps), c.buckets), np.int32) if classifier["distribution"] else None)
         return out
 
-    def run_into(self, device_bank, n_inputs, n_steps, buffers, learning=True, use_graph=True, pipeline=True, continuing=False):
+    def run_into(self, device_bank, n_inputs, n_steps, buffers, learning=True, use_graph=True, pipeline=True, continuing=False, cells=None):
         """The run of _run, enqueued only: `buffers` = {record field: device address of its n_steps rows} (record_shapes() words
         per row; empty: a plain htm_run).  The records stay on the device: nothing is synchronised and nothing read back -- the
-        caller orders its own work behind the engine's stream (region stacks feed "active_column" to htm_pack_columns)."""
+        caller orders its own work behind the engine's stream (region stacks feed "active_column" to htm_pack_columns).  `cells`: the
+        device address of the rows a recorded run's steps leave their active-cell words in (set_run_active_cells, for this call only)."""
         flags, n = run_flags(use_graph, pipeline, continuing), int(n_steps)
         rec = L.HtmRunRecord()
         votes = self._record_ptrs(buffers, rec)
-        with _NOTHING_TO_SET if votes is None else self.this_call(votes=votes):
+        with self.this_call(votes=votes, cells=cells):
             if not set(buffers) - {"predicted_input", "predicted_value"}:
                 self._check(self.lib.htm_run(self.h, C.c_void_p(device_bank), int(n_inputs), n, int(bool(learning)), flags), "htm_run")
             else:
@@ -657,6 +675,10 @@ class Engine:
         """Decoding rows of the later run() calls and group calls (htm_set_run_predicted_input); None clears them."""
         self._check(self.lib.htm_set_run_predicted_input(self.h, C.c_void_p(device_votes) if device_votes else None),
                     "htm_set_run_predicted_input")
+
+    def set_run_active_cells(self, device_pairs):
+        """Pattern rows of the later recorded run() calls (htm_set_run_active_cells); None clears them."""
+        self._check(self.lib.htm_set_run_active_cells(self.h, C.c_void_p(device_pairs) if device_pairs else None), "htm_set_run_active_cells")
 
     def predicted_input(self):
         """int32[input_dim]: the predicted-input votes of the current state (htm_predicted_input)."""

@@ -6,6 +6,7 @@ the three counters: :55-57), so that its output can be compared line by line.
     python -m bithtm_amd.example --epochs 8 --batched   # one C-ABI call per epoch, hipGraph replay
     python -m bithtm_amd.example --epochs 8 --batched_report   # ... recorded: the per-step lines of the default mode
     python -m bithtm_amd.example --epochs 8 --batched_report --likelihood   # ... with each step's anomaly likelihood
+    python -m bithtm_amd.example --epochs 8 --batched_report --classifier   # ... with an SDR classifier's 1-step hit rate per epoch
     python -m bithtm_amd.example --epochs 8 --batched --device_noise   # ... the bank uploaded once, the flip noise drawn on the device
     python -m bithtm_amd.example --epochs 8 --sequence_length 10   # a sequence reset before every 10th pattern
     python -m bithtm_amd.example --epochs 8 --use_reference_implementation   # example.py:30,36-37 (needs the user's `bithtm`)
@@ -17,7 +18,7 @@ import time
 
 import numpy as np
 
-from bithtm_amd import AnomalyLikelihood, HierarchicalTemporalMemory
+from bithtm_amd import AnomalyLikelihood, HierarchicalTemporalMemory, SDRClassifier
 
 FLAGS = (
     # name, type, default  (the reference's flags, same names and defaults)
@@ -55,6 +56,9 @@ def parse(argv):
     ap.add_argument("--likelihood", action="store_true",
                     help="with --batched_report: score every step's anomaly likelihood on the device (run(likelihood=), NuPIC's "
                          "default parameters, one stream over all epochs) and print it as a further column")
+    ap.add_argument("--classifier", action="store_true",
+                    help="with --batched_report: learn an SDR classifier on the device from each step's active cells to the index of the "
+                         "pattern one step ahead (run(classifier=), one bucket per pattern) and print its 1-step hit rate per epoch")
     return ap.parse_args(argv)
 
 
@@ -123,12 +127,17 @@ def run_batched_report(htm, bank, opts, out):
     # (one draw of the epoch's noise: the same MT19937 values, in the same order, as run_stepwise's draw per step)
     report = Report(opts, htm.spatial_pooler.active_columns)
     scoring = dict(likelihood=AnomalyLikelihood()) if opts.likelihood else {}
+    if opts.classifier:                             # (a step's target is its own pattern's index: horizon 1 learns the one that follows)
+        scoring.update(classifier=SDRClassifier(buckets=len(bank), steps=(1,), alpha=0.1), targets=np.arange(len(bank)))
     for epoch in range(opts.epochs):
         noisy, noise = epoch_input(bank, opts)
         rec = htm.run(noisy, len(noisy), record=True, resets=reset_rows(opts), **noise, **scoring)
         for index, (b, c, i) in enumerate(zip(rec.bursting_columns, rec.correct_columns, rec.incorrect_columns)):
             scored = f", anomaly likelihood: {rec.anomaly_likelihood[index]:.6f}" if opts.likelihood else ""
             print(report.line(epoch, index, int(b), int(c), int(i)) + scored, file=out)
+        if opts.classifier:
+            hits = rec.classified_bucket[:, 0] == (np.arange(len(bank)) + 1) % len(bank)
+            print(f"epoch {epoch:{report.w_epoch}d}: 1-step hit rate of the classifier: {hits.mean():.3f}", file=out)
 
 
 def main(argv=None, out=sys.stdout):
@@ -148,6 +157,10 @@ def main(argv=None, out=sys.stdout):
     else:
         if opts.likelihood and not opts.batched_report:
             raise SystemExit("--likelihood prints a column of the recorded report: use it with --batched_report")
+        if opts.classifier and not opts.batched_report:
+            raise SystemExit("--classifier rides on the recorded report's runs: use it with --batched_report")
+        if opts.classifier and opts.input_patterns > 1024:
+            raise SystemExit("--classifier: one bucket per pattern, at most 1024 patterns")
         if opts.device_noise and not (opts.batched or opts.batched_report):
             raise SystemExit("--device_noise draws the noise inside a batched run: use it with --batched or --batched_report")
         htm = HierarchicalTemporalMemory(opts.input_dim, opts.column_dim, opts.cell_dim, seed=opts.seed)

@@ -21,7 +21,7 @@ import numpy as np
 from . import _lib as L
 from .engine import CapacityError, HtmError, pack_bits
 from .networks import (RECORD_COUNTERS, HierarchicalTemporalMemory, InferenceView, RunRecord, _BatchedCall, _batches, _cached_bank, _check_encoder,
-                       _encode_params, _noise_ring, _record_fields, _with_counters, noise_threshold, retire_states)
+                       _encode_params, _no_classifier, _noise_ring, _record_fields, _with_counters, noise_threshold, retire_states)
 
 
 class SharedStream:
@@ -232,7 +232,7 @@ class ModelGroup:
     noise_chunk = 1024
 
     def run(self, inputs, steps, learning=None, use_graph=True, record=None, resets=None, noise=0.0, noise_seed=None, encoder=None,
-            likelihood=None):
+            likelihood=None, classifier=None):
         """`steps` timesteps of every member, member i over the rows of inputs[i] (bool [B, n_inputs, input_dim]), cycled, as
         its own run(inputs[i], steps) would.  Returns None, or (`record`: as run(record=)) one RunRecord per member.
         learning=None: True, or False in a group with inference views (which refuses True).
@@ -244,6 +244,7 @@ class ModelGroup:
         `likelihood`: an AnomalyLikelihood of B streams -- the call records the counters (as record=True), behind each batch ONE
         htm_likelihood_update runs over the members' record buffers (a table of B pointers, never a launch per member) before the
         read-back, and member i's RunRecord.anomaly_likelihood is stream i's."""
+        _no_classifier(classifier, "ModelGroup.run()")
         learning = self._learning(learning)
         B = len(self.models)
         if likelihood is not None:
@@ -449,7 +450,7 @@ class ModelGroup:
                 m.temporal_memory._last_ref = None
                 m.temporal_memory._was_reset = True
 
-    def tick(self, values, encoder=None, resets=None, learning=None, predicted_input=False, use_graph=True, likelihood=None):
+    def tick(self, values, encoder=None, resets=None, learning=None, predicted_input=False, use_graph=True, likelihood=None, classifier=None):
         """One live timestep of every member in one call whose copies, launches and waits do not depend on B: member i steps on
         values[i] -- float64 [B, F] with `encoder` (a ScalarEncoder; NaN: missing), encoded on the device, else bool
         [B, input_dim] as process() takes it -- after a sequence reset where resets[i] (bool [B], or None).  Returns a GroupTick:
@@ -460,6 +461,7 @@ class ModelGroup:
         learning=None: True, or False in a group with inference views (which refuses True).
         `likelihood`: an AnomalyLikelihood of B streams -- the tick's records are the streams' next step (htm_likelihood_tick: one
         launch more, B doubles more in the copy out) and GroupTick.anomaly_likelihood holds the B values."""
+        _no_classifier(classifier, "ModelGroup.tick()")
         learning = self._learning(learning)
         B = len(self.models)
         e0 = self.models[0].engine

@@ -204,7 +204,7 @@ class SpatialPooler:
     # run(noise=): steps per fill of the noise ring (as HierarchicalTemporalMemory.noise_chunk)
     noise_chunk = 1024
 
-    def run(self, inputs, steps, learning=True, use_graph=True, record=None, noise=0.0, noise_seed=None):
+    def run(self, inputs, steps, learning=True, use_graph=True, record=None, noise=0.0, noise_seed=None, classifier=None):
         """`steps` timesteps over the rows of the boolean matrix `inputs`, cycled: `steps` times
         process(inputs[t % n] ^ flip_noise(noise_seed, t, input_dim, noise), learning), t being this object's step index, with the
         bank resident in device memory and no per-step host work (htm_sp_run).  Everything the call leaves -- permanences, duty
@@ -218,6 +218,7 @@ class SpatialPooler:
         ValueError, before anything is created or enqueued: steps < 0, inputs that are not [n >= 1, input_dim], an unknown record
         name, noise outside [0, 1], a run that would pass step 2^32, a Spatial Pooler inside a fused HierarchicalTemporalMemory
         (call its run()), plug-in proximal_projection / boosting / inhibition objects (they step on the host: call process())."""
+        _no_classifier(classifier, "SpatialPooler.run()")
         if self._fused:
             raise ValueError("this SpatialPooler is fused into a HierarchicalTemporalMemory; call its run()")
         if not self._plain:
@@ -490,7 +491,7 @@ class TemporalMemory:
             return eng
         return self._recreate(eng, max(n_active, 2 * eng.active_columns))
 
-    def run(self, active_columns, steps, learning=True, use_graph=True, record=None, resets=None):
+    def run(self, active_columns, steps, learning=True, use_graph=True, record=None, resets=None, classifier=None):
         """`steps` timesteps over the rows of `active_columns` (int [n_rows, n]: n distinct column ids per row, in any order),
         cycled: `steps` times process(SimpleNamespace(active_column=active_columns[t % n_rows]), learning=learning), t being this
         object's step index, with the lists resident in device memory and no per-step host work (htm_tm_run).  Everything the
@@ -502,6 +503,7 @@ class TemporalMemory:
         `resets`: a bool per row -- reset() before every step that reads a row whose flag is set, on the device inside the run.
         ValueError for cell_dim above 64 and for a plug-in distal_projection (both step on the host: call process()), and for a
         Temporal Memory inside a fused HierarchicalTemporalMemory (call its run())."""
+        _no_classifier(classifier, "TemporalMemory.run()")
         if self._fused:
             raise ValueError("this TemporalMemory is fused into a HierarchicalTemporalMemory; call its run()")
         if self.cell_dim > 64:
@@ -620,13 +622,19 @@ class RunRecord:
       predicted_value                float64[steps, F] encoder.value_of(predicted_bucket): NaN where nothing is predicted
       anomaly_likelihood             float64[steps]    with run(likelihood=): the anomaly likelihood of each step (likelihood.py), else
                                                        None; log_likelihood is NuPIC's log scale of it
+      classified_bucket              int32[steps, H]   with run(classifier=): per horizon of the SDRClassifier the most probable bucket
+                                                       (classifier.py), classified_probability float64[steps, H] its probability (p /
+                                                       65536) and, for a classifier of an encoder field, classified_value float64
+                                                       [steps, H] = field.value_of(bucket); else None
+      class_distribution             int32[steps, H, buckets]   all probabilities in units of 2^-16 ("class_distribution", else None)
     and, from the counters, the per-step report of example.py:55-57 and the raw anomaly score:
       correct_columns   = active_columns - bursting_columns
       incorrect_columns = predicted_columns_before - correct_columns
       anomaly_score     = 1 - correct_columns / active_columns   (float64; 0 for a step without active columns)"""
 
     def __init__(self, step_index, counters=None, active_column=None, column_prediction=None, predicted_input=None,
-                 predicted_bucket=None, predicted_score=None, predicted_value=None, anomaly_likelihood=None):
+                 predicted_bucket=None, predicted_score=None, predicted_value=None, anomaly_likelihood=None, classified=None,
+                 class_distribution=None, classified_field=None):
         self.step_index = np.asarray(step_index, dtype=np.int64)
         self.fields = tuple(f for f, v in zip(RECORD_FIELDS, (counters, active_column, column_prediction, predicted_input, predicted_bucket))
                             if v is not None)
@@ -637,6 +645,13 @@ class RunRecord:
         self.predicted_input = predicted_input
         self.predicted_bucket, self.predicted_score, self.predicted_value = predicted_bucket, predicted_score, predicted_value
         self.anomaly_likelihood = anomaly_likelihood
+        self.classified_bucket = self.classified_probability = self.classified_value = None
+        if classified is not None:              # int32 [steps, H, 2]: (bucket, p in units of 2^-16)
+            self.classified_bucket = np.ascontiguousarray(classified[:, :, 0])
+            self.classified_probability = classified[:, :, 1].astype(np.float64) / 65536.0
+            if classified_field is not None:
+                self.classified_value = classified_field.value_of(self.classified_bucket)
+        self.class_distribution = class_distribution
 
     def __len__(self):
         return len(self.step_index)
@@ -824,7 +839,7 @@ class HierarchicalTemporalMemory:
         return ring, rows, None if resets is None else ring_resets
 
     def run(self, inputs, steps, learning=True, use_graph=True, pipeline=True, continuing=False, record=None, resets=None,
-            noise=0.0, noise_seed=None, encoder=None, likelihood=None):
+            noise=0.0, noise_seed=None, encoder=None, likelihood=None, classifier=None, targets=None, classifier_learning=None):
         """`steps` timesteps over the rows of the boolean matrix `inputs`, cycled, with the input
         bank resident in device memory and no per-step host work (the loop of example.py:48-53).
         Returns None; read `temporal_memory.last_state` or call process() afterwards.  `continuing=True`: the
@@ -851,8 +866,27 @@ class HierarchicalTemporalMemory:
         `likelihood`: an AnomalyLikelihood of one stream -- the run records its counters (as record=True; named fields are
         recorded too), behind each batch the likelihood's update is enqueued over the batch's record buffer before the read-back
         (htm_likelihood_update: the run still waits once per batch), and RunRecord.anomaly_likelihood holds each step's value.
-        The object's state continues across calls; the model's resets do not touch it."""
+        The object's state continues across calls; the model's resets do not touch it.
+        `classifier`: an SDRClassifier -- the run records its counters, every step leaves its active-cell words on the device
+        (htm_set_run_active_cells: one small launch per step) and behind each batch the classifier's update over them is enqueued
+        before the read-back (htm_classifier_update: the run still waits once per batch).  `targets`: int [rows of inputs], the
+        bucket of each row (-1: missing; ValueError at or above the classifier's buckets), uploaded once; None with `encoder`: the
+        bucket of classifier.field among the encoder's fields, taken with encoder.bucket on the host.  A step's target is its own
+        row's; a reset flag of a row also empties the classifier's history.  `classifier_learning`: None follows `learning`.
+        RunRecord.classified_bucket, _probability, _value hold each step's prediction per horizon, and with "class_distribution"
+        named in `record`, RunRecord.class_distribution all probabilities."""
         eng = self._fused_engine("run()")
+        cls = None
+        if classifier is not None:
+            distribution = record is not None and record is not True and "class_distribution" in ((record,) if isinstance(record, str) else tuple(record))
+            if distribution:
+                record = tuple(f for f in ((record,) if isinstance(record, str) else tuple(record)) if f != "class_distribution") or None
+            record = _with_counters(record)
+            if eng.shard_world > 1:
+                raise ValueError("run(classifier=): not available on a column-sharded model")
+            cls = dict(clf=classifier, distribution=distribution, learn=bool(learning if classifier_learning is None else classifier_learning))
+        elif targets is not None or classifier_learning is not None:
+            raise ValueError("run(): targets= and classifier_learning= go with classifier=")
         if likelihood is not None:
             if likelihood.streams != 1:
                 raise ValueError(f"run(likelihood=): an AnomalyLikelihood of one stream, got {likelihood.streams}")
@@ -862,12 +896,17 @@ class HierarchicalTemporalMemory:
         steps = int(steps)
         threshold, fields, noise_seed, inputs, resets = self._run_args(eng, "run", inputs, steps, record, resets, noise, noise_seed, encoder)
         retire_states(eng)
+        if cls is not None:
+            from .sdr_classifier import model_shape
+            classifier._set_shape(*model_shape(eng))
+            cls["host_targets"] = _classifier_targets(classifier, targets, inputs, encoder)
+            cls["rows"] = inputs.shape[0]
         bank = _cached_bank(self, eng, inputs, encoder=encoder)
         # A pool left at its default size grows like the reference's arrays (utils.py:113-135): the run is cut into batches
         # the free segments are expected to last (2 x active_columns new segments per step: every column bursting, twice),
         # with a look at the pool between them.  An overflow inside a batch is still reported, never silent.
         k = self.active_columns
-        call = _BatchedCall([self.temporal_memory], fields, encoder, likelihood is not None)
+        call = _BatchedCall([self.temporal_memory], fields, encoder, likelihood is not None, classifier)
         del eng                                     # (the pool step may re-create the engine: the old one goes, device memory and all, as it does)
         refuse = "the segment pool has to grow in the middle of a streamed run(): end the stream (a run() without continuing=True) first"
 
@@ -884,8 +923,12 @@ class HierarchicalTemporalMemory:
             # four-launch schedule, of the one behind that -- one row more; the next call's fill writes those rows again with the
             # words they have)
             src, rows, bits = self._batch_source(eng, bank, inputs, resets, n + (2 if continuing and last else 1), threshold, noise_seed)
+            if cls is not None:                     # (targets and reset bits by the row of `inputs` a step reads, whatever bank the run reads)
+                if "targets" not in cls:
+                    cls["targets"] = classifier.upload_targets(eng, cls["host_targets"])
+                cls["resets"] = None if resets is None else eng.upload_resets(resets)
             call.add([eng.run(src, rows, n, learning=learning, use_graph=use_graph, pipeline=pipeline, continuing=continuing and last,
-                              record=fields, resets=bits, encoder=encoder, likelihood=likelihood)])
+                              record=fields, resets=bits, encoder=encoder, likelihood=likelihood, classifier=cls)])
             self._streaming = bool(continuing and last and pipeline)
         return call.finish([steps], [k])[0]
 
@@ -952,7 +995,7 @@ class HierarchicalTemporalMemory:
         return kept[1]
 
     def lookahead(self, inputs, steps, horizon, min_votes=1, max_bits=0, every=1, learning=True, use_graph=True, record=None,
-                  resets=None, noise=0.0, noise_seed=None, encoder=None):
+                  resets=None, noise=0.0, noise_seed=None, encoder=None, classifier=None):
         """Rolling look-ahead: the model runs over `inputs` as run() does (learning or not) and after every `every` steps says
         what it expects over the next `horizon` steps, its own stream unmoved.  Bit for bit, with W = steps // every:
             for j in range(W):
@@ -965,6 +1008,7 @@ class HierarchicalTemporalMemory:
         default-sized pool is looked at between chunks, as in run().  ValueError: steps not a multiple of every, horizon < 1,
         every < 1, and what fork(), run() and forecast() refuse.  `encoder`: as run()'s -- `inputs` are then values, and the
         record may name "predicted_value" (decoded once per chunk behind its windows)."""
+        _no_classifier(classifier, "lookahead()")
         steps, horizon, every = int(steps), int(horizon), int(every)
         if horizon < 1 or every < 1:
             raise ValueError(f"lookahead(): horizon and every must be at least 1, got {horizon} and {every}")
@@ -1088,7 +1132,7 @@ class HierarchicalTemporalMemory:
         eng.encode_votes(min_votes, max_bits, bank, 1, 0)
         return eng.read_bank(bank, 1)[0]
 
-    def forecast(self, steps, min_votes=1, max_bits=0, record=None, use_graph=True, learning=False, noise=0.0, encoder=None):
+    def forecast(self, steps, min_votes=1, max_bits=0, record=None, use_graph=True, learning=False, noise=0.0, encoder=None, classifier=None):
         """What the model expects over the next `steps` steps: from its current state, `steps` times
             x = encode_votes(predicted_input(), min_votes, max_bits);  process(x, learning=False)
         with the whole loop on the device (htm_set_run_feedback: each step's votes are encoded into the bank row the next step
@@ -1099,6 +1143,7 @@ class HierarchicalTemporalMemory:
         forecast on a view:  view = htm.inference_view(); view.run(context, n); view.forecast(k).  `noise` other than 0 raises
         ValueError: a forecast reads the rows the model itself wrote, and flipping them is not offered.  `encoder`: the
         ScalarEncoder a "predicted_value" record decodes with (forecast_values() is the call that returns values)."""
+        _no_classifier(classifier, "forecast()")
         if learning:
             raise ValueError("forecast(): learning from the model's own output is not available (learning=False only)")
         if _noise_threshold_arg(noise):
@@ -1222,11 +1267,14 @@ class InferenceView(HierarchicalTemporalMemory):
     compute = process
 
     def run(self, inputs, steps, learning=False, use_graph=True, pipeline=True, continuing=False, record=None, resets=None,
-            noise=0.0, noise_seed=None, encoder=None, likelihood=None):
+            noise=0.0, noise_seed=None, encoder=None, likelihood=None, classifier=None, targets=None, classifier_learning=None):
+        """As the parent's run(), with learning=False.  `classifier_learning` may be True: the classifier's weights are its own, not
+        the parent's."""
         self._no_learning(learning, "run()")
         self._check_parent()
         return super().run(inputs, steps, learning=False, use_graph=use_graph, pipeline=pipeline, continuing=continuing,
-                           record=record, resets=resets, noise=noise, noise_seed=noise_seed, encoder=encoder, likelihood=likelihood)
+                           record=record, resets=resets, noise=noise, noise_seed=noise_seed, encoder=encoder, likelihood=likelihood,
+                           classifier=classifier, targets=targets, classifier_learning=classifier_learning)
 
     def reset(self):
         self._check_parent()
@@ -1367,7 +1415,29 @@ def _with_counters(record):
     return fields if "counters" in fields else ("counters",) + fields
 
 
-def _join_record(parts, fields, first_step, steps, k, column_dim, input_dim=0, encoder=None, likelihood=False):
+def _no_classifier(classifier, what):
+    """The calls an SDRClassifier does not ride on: refused, never silently ignored."""
+    if classifier is not None:
+        raise ValueError(f"{what}: classifier= is not available here -- an SDRClassifier rides on HierarchicalTemporalMemory.run() and "
+                         "InferenceView.run(), or takes patterns through update_patterns()")
+
+
+def _classifier_targets(classifier, targets, inputs, encoder):
+    """run(classifier=, targets=): the target bucket of every row of `inputs` -> int32 [rows]."""
+    if targets is None:
+        if encoder is None or classifier.field is None:
+            raise ValueError("run(classifier=): give targets=, or encoder= and a classifier made with field=")
+        where = [j for j, f in enumerate(encoder.fields) if f is classifier.field]
+        if not where:
+            raise ValueError("run(classifier=): the classifier's field is not one of the encoder's fields")
+        targets = encoder.bucket(inputs)[:, where[0]]
+    targets = classifier.check_targets(targets)
+    if targets.shape != (inputs.shape[0],):
+        raise ValueError(f"targets: one bucket per row of inputs ({inputs.shape[0]}), got {targets.shape[0]}")
+    return targets
+
+
+def _join_record(parts, fields, first_step, steps, k, column_dim, input_dim=0, encoder=None, likelihood=False, classifier=None):
     """One contiguous RunRecord from the per-batch records of a run(record=...) (Engine.run's dicts), however many batches the
     pool's growth cut the call into."""
     empty = {"counters": np.zeros((0, len(RECORD_COUNTERS)), np.int32), "active_column": np.zeros((0, k), np.int32),
@@ -1383,6 +1453,12 @@ def _join_record(parts, fields, first_step, steps, k, column_dim, input_dim=0, e
         whole["column_prediction"] = np.unpackbits(words.view(np.uint8), axis=1, bitorder="little")[:, :column_dim].astype(bool)
     if likelihood:                                  # (each batch's part carries its steps' likelihoods beside the fields)
         whole["anomaly_likelihood"] = np.concatenate([p["anomaly_likelihood"] for p in parts]) if parts else np.zeros(0, np.float64)
+    if classifier is not None:                      # (each batch's part carries its steps' predictions beside the fields)
+        H = len(classifier.steps)
+        whole["classified"] = np.concatenate([p["classified"] for p in parts]) if parts else np.zeros((0, H, 2), np.int32)
+        if parts and parts[0]["class_distribution"] is not None:
+            whole["class_distribution"] = np.concatenate([p["class_distribution"] for p in parts])
+        whole["classified_field"] = classifier.field
     return RunRecord(first_step + np.arange(steps, dtype=np.int64), **whole)
 
 
@@ -1435,8 +1511,8 @@ class _BatchedCall:
     the model's engine): the parts every batch adds per member, the step each started at, and at the end the new last_state, the
     sticky flags and one RunRecord per member."""
 
-    def __init__(self, tms, fields, encoder=None, likelihood=False):
-        self.tms, self.fields, self.encoder, self.likelihood = tms, fields, encoder, likelihood
+    def __init__(self, tms, fields, encoder=None, likelihood=False, classifier=None):
+        self.tms, self.fields, self.encoder, self.likelihood, self.classifier = tms, fields, encoder, likelihood, classifier
         self.first = [tm._engine.steps for tm in tms]
         self.parts = [[] for _ in tms]
 
@@ -1458,5 +1534,5 @@ class _BatchedCall:
             return [None] * len(self.tms)
         if read is not None:
             self.add(read())
-        return [_join_record(p, self.fields, f, n, k, tm.column_dim, tm._engine.input_dim, self.encoder, self.likelihood)
+        return [_join_record(p, self.fields, f, n, k, tm.column_dim, tm._engine.input_dim, self.encoder, self.likelihood, self.classifier)
                 for p, f, n, k, tm in zip(self.parts, self.first, steps, ks, self.tms)]

@@ -911,6 +911,72 @@ int htm_likelihood_tick(htm_group *g, const double *values, const htm_scalar_fie
                         const uint8_t *resets, int32_t learning, int32_t use_graph, htm_live_row *rows, int32_t *decoded, int32_t *votes,
                         htm_likelihood *lk, double *likelihood);
 
+/* SDR classifier on the device (the definition is bithtm_amd/classifier.py, which the device equals bit for
+ * bit): a softmax regression from the cells of the pattern of step t to the bucket seen at step t + h, learned online, one weight
+ * table per horizon h, all in integers.  An htm_classifier object holds in device memory the weights W[h][unit][B_pad] (int32 in
+ * units of 2^-16, clamped to [-2^30, 2^30], B_pad = buckets rounded up to a multiple of 4: n_steps x units x B_pad x 4 bytes), the
+ * ring of the last steps[n_steps - 1] + 1 patterns and the count of patterns since the history was last emptied; the total step count
+ * is kept on the host.
+ *
+ * The config: buckets in [1, 1024]; n_steps in [1, 8] ascending horizons steps[] in [0, 64]; alpha_q = the learning rate in units of
+ * 2^-16, in [1, 65536]; units = column_dim * cell_dim of the patterns' model, a multiple of cell_dim; cell_dim in [1, 64]; max_pairs
+ * >= 1, the most pairs a step's pattern may have (the ring's row).  exp_table2049: 2049 int32 in HOST memory, T[i] = round(2^30 *
+ * exp(-i / 64)), copied at creation (data: the device evaluates no exp).  The object lives on h's device and keeps nothing of h;
+ * every later call takes a handle of that device and enqueues on that handle's stream without a wait.  Order across handles on
+ * different streams is the caller's, as for htm_likelihood.
+ *
+ * A pattern is pairs_per_step pairs (int32 index, uint32 word): bit j of word means unit (index / WPC) * cell_dim + (index % WPC)
+ * * 32 + j, WPC = ceil(cell_dim / 32) -- the word `index` of a model's cell activation.  A pair with index < 0 or word == 0
+ * contributes nothing; the indices of one pattern must be distinct (the caller's promise: a learning step adds to every named row
+ * once).  Bits that name no unit of the table are ignored.
+ *
+ * The update call: device_pairs is DEVICE memory, n_steps x pairs_per_step pairs; device_targets int32[n_targets] in DEVICE memory,
+ * step i reading entry (first_step + i) % n_targets (any value outside [0, buckets) is a missing target); device_reset_bits (DEVICE,
+ * or NULL: no resets) one bit per entry as htm_set_run_resets takes them: the history is emptied before a step whose bit is set.
+ * device_best: DEVICE int32[n_steps][n_horizons][2], per step and horizon the lowest bucket with the largest activation and its
+ * probability in units of 2^-16; device_dist: DEVICE int32[n_steps][n_horizons][buckets] or NULL, all probabilities.  learn != 0:
+ * two launches per step (kcls_sum, kcls_apply); learn == 0: one launch (kcls_frozen) per 512 steps, the weights unchanged, history
+ * and counts advanced as a learning call does.  Successive calls compose: a calls of steps then b are one call of a + b.
+ * The reset call empties the history (the weights stay).  read_weights / write_weights: rows [unit0, unit0 + n_units) of one horizon
+ * (its index in steps[]) to / from HOST int32[n_units][buckets], after a wait for h's stream.  export / import: everything but the
+ * weights to / from HOST memory of exactly htm_classifier_state_bytes bytes, after a wait for h's stream: int64 total; int64 count;
+ * then the ring, (int32 index, uint32 word)[ring_len][max_pairs], slot (step mod ring_len) holding that step's pattern, unused pairs
+ * (-1, 0).
+ *
+ * HTM_ERR_ARGUMENT, nothing enqueued: NULL pointers; a wrong struct_bytes; a parameter outside its range; pairs_per_step outside
+ * [1, max_pairs]; n_steps < 0; n_targets < 1 or first_step < 0; a handle on another device; a horizon or a range of rows outside the
+ * table; a written weight outside [-2^30, 2^30]; a state of another size, or one with count < 0 or count > total.  HTM_ERR_STATE: a
+ * column-sharded handle. */
+typedef struct htm_classifier htm_classifier;
+typedef struct htm_classifier_config {
+    uint32_t struct_bytes;
+    int32_t buckets, n_steps, alpha_q, units, cell_dim, max_pairs;
+    int32_t steps[8];
+} htm_classifier_config;
+
+int htm_classifier_create(htm_handle *h, const htm_classifier_config *cfg, const int32_t *exp_table2049, htm_classifier **out);
+void htm_classifier_destroy(htm_classifier *clf);
+int htm_classifier_update(htm_classifier *clf, htm_handle *h, const void *device_pairs, int32_t pairs_per_step, int32_t n_steps,
+                          const int32_t *device_targets, int32_t n_targets, int32_t first_step, const uint32_t *device_reset_bits,
+                          int32_t learn, int32_t *device_best, int32_t *device_dist);
+int htm_classifier_reset(htm_classifier *clf, htm_handle *h);
+int htm_classifier_read_weights(htm_classifier *clf, htm_handle *h, int32_t horizon, int32_t unit0, int32_t n_units, int32_t *host_dst);
+int htm_classifier_write_weights(htm_classifier *clf, htm_handle *h, int32_t horizon, int32_t unit0, int32_t n_units, const int32_t *host_src);
+int64_t htm_classifier_state_bytes(const htm_classifier *clf);
+int htm_classifier_export(htm_classifier *clf, htm_handle *h, void *host_state, int64_t bytes);
+int htm_classifier_import(htm_classifier *clf, htm_handle *h, const void *host_state, int64_t bytes);
+
+/* Pattern capture for the classifier: after htm_set_run_active_cells(h, device_pairs), an htm_run_recorded call of n steps writes
+ * n x k x WPC pairs (int32 index, uint32 word) into device_pairs (DEVICE memory): row i holds step i's active-cell words of its k
+ * active columns in active_column order -- index = column * WPC + w, word = word `index` of the step's cell activation, k =
+ * active_columns, WPC = ceil(cell_dim / 32) -- which is what htm_classifier_update takes with pairs_per_step = k * WPC.  One small
+ * launch (kcls_capture) directly behind each step's record launch; graphs are captured once and read the rows through a device
+ * descriptor, which this call fills with one 8-byte copy on h's stream.  NULL clears the rows: calls then launch and capture exactly
+ * what they did before.  While rows are set: htm_run (and htm_prepare) without a record is HTM_ERR_ARGUMENT; htm_tm_run and a group
+ * call with such a member are HTM_ERR_STATE.  Setting rows on a column-sharded handle, or on one without the device's own Spatial
+ * Pooler and Temporal Memory, is HTM_ERR_STATE. */
+int htm_set_run_active_cells(htm_handle *h, void *device_pairs);
+
 #ifdef __cplusplus
 }
 #endif
