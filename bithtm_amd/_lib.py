@@ -182,7 +182,19 @@ EXPORTS = {
     "htm_classifier_state_bytes": (C.c_int64, [C.c_void_p]),
     "htm_classifier_export": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]),
     "htm_classifier_import": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]),
+    "htm_classifiers_create": (C.c_int, [C.c_void_p, C.POINTER(HtmClassifierConfig), C.c_void_p, C.c_int32, C.c_void_p, C.POINTER(C.c_void_p)]),
+    "htm_classifiers_update": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p,
+                                         C.c_int32, C.c_void_p, C.c_void_p]),
+    "htm_classifiers_reset": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "htm_classifiers_read_weights": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
+    "htm_classifiers_write_weights": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
+    "htm_classifiers_state_bytes": (C.c_int64, [C.c_void_p]),
+    "htm_classifiers_export": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]),
+    "htm_classifiers_import": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]),
     "htm_set_run_active_cells": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "htm_set_group_run_active_cells": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "htm_classifiers_tick": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(HtmScalarField), C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
+                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
 }
 
 # The HIP runtime calls the binding makes itself -- the device buffers of run(record=...) -- resolved through the library's own

@@ -199,3 +199,68 @@ class ClassifierDefinition:
             for j, (i, w) in enumerate(pattern):
                 out[s, j] = (i, np.uint32(w).view(np.int32))
         return out
+
+
+class ClassifierBankDefinition:
+    """A bank of n streams: n independent ClassifierDefinition objects of one config -- stream i fed
+    (patterns_i, targets_i, resets_i) equals a one-stream object fed the same -- with one `total` for the object, since every call
+    advances all streams by the same number of steps, and per stream its count, its ring and its weights.  weights="shared": every
+    stream reads one weight table (`table`, a ClassifierDefinition whose weights are read where they lie, or a table of the bank's
+    own); learning is refused; inference, rings and counts work as in an own-weights bank.  No arithmetic of its own."""
+
+    def __init__(self, streams, buckets, steps=(1,), alpha=0.001, units=2048, cell_dim=32, alpha_q=None, weights="own", table=None):
+        self.n = int(streams)
+        if self.n < 1:
+            raise ValueError(f"streams must be at least 1, got {streams}")
+        if weights not in ("own", "shared"):
+            raise ValueError(f"weights: 'own' or 'shared', got {weights!r}")
+        self.shared = weights == "shared"
+        self.members = [ClassifierDefinition(buckets, steps, alpha, units, cell_dim, alpha_q) for _ in range(self.n)]
+        if self.shared:
+            self.table = table if table is not None else ClassifierDefinition(buckets, steps, alpha, units, cell_dim, alpha_q)
+            first = self.members[0]
+            if (self.table.buckets, self.table.steps, self.table.units, self.table.cell_dim) != (first.buckets, first.steps, first.units, first.cell_dim):
+                raise ValueError("the shared table was made with another config")
+        elif table is not None:
+            raise ValueError("table= goes with weights='shared'")
+        self.total = 0
+
+    def _attach(self):
+        if self.shared:                                         # (read where it lies: the owner may have replaced its tables)
+            for m in self.members:
+                m.weights = self.table.weights
+
+    def reset(self, streams=None):
+        for i, m in enumerate(self.members):
+            if streams is None or streams[i]:
+                m.reset()
+
+    def update(self, index, words, targets, resets=None, learning=True, first_step=0):
+        """index, words [n, T, P]; targets [n, R]; resets [n, R] or None; step i reads target and reset (first_step + i) % R ->
+        (best int32 [n, T, H, 2], dist int32 [n, T, H, buckets])."""
+        if learning and self.shared:
+            raise ValueError("the streams read one weight table: learning is refused")
+        if len(index) != self.n or len(words) != self.n or len(targets) != self.n or (resets is not None and len(resets) != self.n):
+            raise ValueError(f"the bank has {self.n} streams")
+        self._attach()
+        best, dist = [], []
+        for i, m in enumerate(self.members):
+            assert m.total == self.total
+            b, d = m.update(index[i], words[i], targets[i], None if resets is None else resets[i], learning, first_step)
+            best.append(b)
+            dist.append(d)
+        self.total += len(index[0])
+        return np.stack(best), np.stack(dist)
+
+    @property
+    def counts(self):
+        return [m.count for m in self.members]
+
+    def dense_weights(self):
+        """int32 [n, H, units, buckets] (shared: the one table, n times)."""
+        self._attach()
+        return np.stack([m.dense_weights() for m in self.members])
+
+    def ring_arrays(self, max_pairs):
+        """int32 [n, ring_len, max_pairs, 2]."""
+        return np.stack([m.ring_arrays(max_pairs) for m in self.members])

@@ -367,4 +367,227 @@ __global__ __launch_bounds__(256) void kcls_capture(Dev d, int p, const RecDev *
 }
 
 #endif  // __HIPCC__
+
+// ------------------------------------------------------------------------------------------
+// A bank of classifiers (htm_classifiers_*): n independent streams of one config, member-major -- weights
+// [n][H][units][B_pad] (or one table every member reads: member stride 0), rings [n][ring_len][max_pairs], counts [n], accumulators
+// [n][H][2][B_pad], tickets, deltas and learn flags [n][H].  The kernels are twins of the ones above: the member shares grid y with
+// the horizon (and, frozen, with the step), and everything a block touches is its member's.  Where a block's row lies is the
+// arithmetic below; tests/host_stub/group_classifier_host.cpp evaluates it on the host.
+
+// steps per frozen launch of a bank of n streams: member, step and horizon share grid y (at most 65535 rows)
+CLS_HD static inline int gcls_chunk(int n, int H) { const int most = 65535 / (n * H); return most < HTM_CLASSIFIER_CHUNK ? most : HTM_CLASSIFIER_CHUNK; }
+// block row y of a learning launch: y = member * H + horizon
+CLS_HD static inline int gcls_member(int y, int H) { return y / H; }
+CLS_HD static inline int gcls_horizon(int y, int H) { return y % H; }
+// block row y of a frozen launch over n steps: y = (member * n + step) * H + horizon
+CLS_HD static inline int gcls_frozen_member(int y, int H, int n) { return y / H / n; }
+CLS_HD static inline int gcls_frozen_step(int y, int H, int n) { return y / H % n; }
+// member m's (horizon h's) row of the [n][H] arrays: tickets and learn flags; times B_pad the deltas, times 2 * B_pad the accumulators
+CLS_HD static inline int64_t gcls_row(int m, int H, int h) { return (int64_t)m * H + h; }
+// member m's first output row of a call of n_steps steps: best [n][n_steps][H][2], dist [n][n_steps][H][B]
+CLS_HD static inline int64_t gcls_out_row(int m, int n_steps, int H) { return (int64_t)m * n_steps * H; }
+
+#ifdef __HIPCC__
+
+struct GClsDev {
+    ClsDev c;                   // member 0's
+    int32_t n;                  // streams
+    int64_t w_member;           // H * w_stride, or 0 where every member reads one table
+};
+
+// a call's inputs: per member a device pointer from the call's table, or (no table) member 0's plus a stride per member
+struct GClsStep {
+    const ClsPair *const *pairs_tab;        // [n] -> [n_steps][pairs_per_step]
+    const int32_t *const *targets_tab;      // [n] -> [n_targets]
+    const uint32_t *const *resets_tab;      // [n] -> [ceil(n_targets / 32)], or null
+    const ClsPair *pairs;
+    const int32_t *targets;
+    const uint32_t *reset_bits;             // or null
+    int64_t pairs_stride, targets_stride, resets_stride;        // in elements
+    int32_t pairs_per_step, n_targets, first_step, n_steps;
+    int32_t *best;                          // [n][n_steps][H][2]
+    int32_t *dist;                          // [n][n_steps][H][B] or null
+    int64_t total;
+};
+
+// member m's view of the bank: a ClsDev whose pointers are the member's (its steps[] is not to be indexed: read g.c.steps)
+__device__ __forceinline__ ClsDev gcls_dev(const GClsDev &g, int m) {
+    ClsDev c = g.c;
+    c.w += (int64_t)m * g.w_member;
+    c.ring += (size_t)m * c.ring_len * c.max_pairs;
+    c.count += m;
+    c.acc += gcls_row(m, c.H, 0) * 2 * c.B_pad;
+    c.ticket += gcls_row(m, c.H, 0);
+    c.delta += gcls_row(m, c.H, 0) * c.B_pad;
+    c.learn += gcls_row(m, c.H, 0);
+    return c;
+}
+
+__device__ __forceinline__ ClsStep gcls_step(const GClsStep &g, const ClsDev &c, int m) {
+    ClsStep s;
+    s.pairs = g.pairs_tab ? g.pairs_tab[m] : g.pairs + (int64_t)m * g.pairs_stride;
+    s.targets = g.targets_tab ? g.targets_tab[m] : g.targets + (int64_t)m * g.targets_stride;
+    s.reset_bits = g.resets_tab ? g.resets_tab[m] : g.reset_bits ? g.reset_bits + (int64_t)m * g.resets_stride : nullptr;
+    s.pairs_per_step = g.pairs_per_step;
+    s.n_targets = g.n_targets;
+    s.first_step = g.first_step;
+    s.best = g.best + gcls_out_row(m, g.n_steps, c.H) * 2;
+    s.dist = g.dist ? g.dist + gcls_out_row(m, g.n_steps, c.H) * c.B : nullptr;
+    s.total = g.total;
+    return s;
+}
+
+// grid (ceil(max_pairs / HTM_CLASSIFIER_PAIRS), n * H): step i of a learning call, every member's (kcls_sum's twin)
+__global__ __launch_bounds__(HTM_CLASSIFIER_THREADS) void kgcls_sum(GClsDev gd, GClsStep gs, int i) {
+    __shared__ unsigned long long s_acc[2 * HTM_CLASSIFIER_MAX_BUCKETS];
+    __shared__ int32_t s_e[HTM_CLASSIFIER_MAX_BUCKETS];
+    __shared__ unsigned long long s_red[9];
+    __shared__ uint32_t s_last;
+    const int m = gcls_member((int)blockIdx.y, gd.c.H), h = gcls_horizon((int)blockIdx.y, gd.c.H), tid = (int)threadIdx.x;
+    if (m >= gd.n) return;
+    const ClsDev c = gcls_dev(gd, m);
+    const ClsStep s = gcls_step(gs, c, m);
+    const int horizon = gd.c.steps[h];
+    const int64_t t = s.total + i;
+    const int64_t count = cls_reset_bit(s, i) ? 0 : *c.count;               // patterns of the member's history before P_t enters
+    const int32_t g = s.targets[(int)(((int64_t)s.first_step + i) % s.n_targets)];
+    const bool learns = g >= 0 && g < c.B && (int64_t)horizon <= count;    // (block-uniform per member and horizon)
+    const int lo = (int)blockIdx.x * HTM_CLASSIFIER_PAIRS, hi = min(lo + HTM_CLASSIFIER_PAIRS, c.max_pairs);
+    const ClsPair *row = s.pairs + (size_t)i * s.pairs_per_step;
+    const int32_t *wh = c.w + (int64_t)h * c.w_stride;
+    for (int b = tid; b < 2 * c.B_pad; b += HTM_CLASSIFIER_THREADS) s_acc[b] = 0ull;
+    __syncthreads();
+    cls_sum_rows(c, wh, row, min(lo, s.pairs_per_step), min(hi, s.pairs_per_step), s_acc);
+    if (learns) {
+        if (horizon == 0) cls_sum_rows(c, wh, row, min(lo, s.pairs_per_step), min(hi, s.pairs_per_step), s_acc + c.B_pad);
+        else cls_sum_rows(c, wh, c.ring + (size_t)((t - horizon) % c.ring_len) * c.max_pairs, lo, hi, s_acc + c.B_pad);
+    }
+    if (h == 0) cls_ring_copy(c, row, s.pairs_per_step, lo, hi, (int)(t % c.ring_len));
+    __syncthreads();
+    unsigned long long *acc = (unsigned long long *)c.acc + (size_t)h * 2 * c.B_pad;
+    if (!cls_arrive(acc, s_acc, 2 * c.B_pad, c.ticket + h, gridDim.x, &s_last)) return;
+    cls_take(acc, s_acc, 2 * c.B_pad);
+    if (tid == 0) {
+        __hip_atomic_store(c.ticket + h, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        c.learn[h] = learns ? 1 : 0;
+    }
+    int best;
+    int64_t z;
+    cls_softmax(c, s_acc, s_e, s_red, best, z);
+    cls_write_outputs(c, s, i, h, s_e, best, z);
+    if (!learns) return;                                   // (block-uniform)
+    __syncthreads();                                       // (s_e is read above, written below)
+    cls_softmax(c, s_acc + c.B_pad, s_e, s_red, best, z);
+    int32_t *delta = c.delta + (size_t)h * c.B_pad;
+    for (int b = tid; b < c.B_pad; b += HTM_CLASSIFIER_THREADS) delta[b] = b < c.B ? cls_delta(c.alpha_q, cls_prob(s_e[b], z), b == g) : 0;
+}
+
+// grid (ceil(max_pairs / HTM_CLASSIFIER_PAIRS), n * H), behind kgcls_sum of the same step (kcls_apply's twin)
+__global__ __launch_bounds__(HTM_CLASSIFIER_THREADS) void kgcls_apply(GClsDev gd, GClsStep gs, int i) {
+    const int m = gcls_member((int)blockIdx.y, gd.c.H), h = gcls_horizon((int)blockIdx.y, gd.c.H);
+    const int wave = (int)threadIdx.x >> 6, lane = (int)threadIdx.x & 63;
+    if (m >= gd.n) return;
+    const ClsDev c = gcls_dev(gd, m);
+    const ClsStep s = gcls_step(gs, c, m);
+    if (blockIdx.x == 0 && h == 0 && threadIdx.x == 0) *c.count = (cls_reset_bit(s, i) ? 0 : *c.count) + 1;
+    if (!c.learn[h]) return;
+    const int64_t t = s.total + i;
+    const ClsPair *pairs = c.ring + (size_t)((t - gd.c.steps[h]) % c.ring_len) * c.max_pairs;
+    const int lo = (int)blockIdx.x * HTM_CLASSIFIER_PAIRS, hi = min(lo + HTM_CLASSIFIER_PAIRS, c.max_pairs);
+    int32_t *wh = c.w + (int64_t)h * c.w_stride;
+    const int32_t *delta = c.delta + (size_t)h * c.B_pad;
+    for (int b0 = 0; b0 < c.B_pad; b0 += 256) {
+        const int b = b0 + 4 * lane;
+        if (b >= c.B_pad) continue;
+        const int4 d = *(const int4 *)(delta + b);
+        for (int j = lo + wave; j < hi; j += HTM_CLASSIFIER_THREADS / 64) {
+            const ClsPair pr = pairs[j];
+            uint32_t bits = cls_live_bits(pr.index, pr.word, c.K, c.WPC, c.n_cols);
+            if (!bits) continue;
+            int32_t *row0 = wh + cls_unit0(pr.index, c.K, c.WPC) * c.B_pad + b;
+            while (bits) {
+                const int bit = __ffs(bits) - 1;
+                bits &= bits - 1;
+                int4 *p = (int4 *)(row0 + (int64_t)bit * c.B_pad);
+                int4 v = *p;
+                v.x = cls_clamp(v.x, d.x); v.y = cls_clamp(v.y, d.y); v.z = cls_clamp(v.z, d.z); v.w = cls_clamp(v.w, d.w);
+                *p = v;
+            }
+        }
+    }
+}
+
+// grid (ceil(pairs_per_step / HTM_CLASSIFIER_PAIRS), streams * n * H), n <= gcls_chunk(streams, H): steps [first, first + n) of a frozen
+// call, every member's (kcls_frozen's twin).  The accumulators f are [streams * n * H] rows: a block row's own.
+__global__ __launch_bounds__(HTM_CLASSIFIER_THREADS) void kgcls_frozen(GClsDev gd, ClsFrozen f, GClsStep gs, int first, int n) {
+    __shared__ unsigned long long s_acc[HTM_CLASSIFIER_MAX_BUCKETS];
+    __shared__ int32_t s_e[HTM_CLASSIFIER_MAX_BUCKETS];
+    __shared__ unsigned long long s_red[9];
+    __shared__ uint32_t s_last;
+    __shared__ int s_reset;
+    const int y = (int)blockIdx.y, h = gcls_horizon(y, gd.c.H), zi = gcls_frozen_step(y, gd.c.H, n), m = gcls_frozen_member(y, gd.c.H, n);
+    const int i = first + zi, tid = (int)threadIdx.x;
+    if (m >= gd.n) return;
+    const ClsDev c = gcls_dev(gd, m);
+    const ClsStep s = gcls_step(gs, c, m);
+    const int64_t t = s.total + i;
+    const int lo = (int)blockIdx.x * HTM_CLASSIFIER_PAIRS, hi = min(lo + HTM_CLASSIFIER_PAIRS, s.pairs_per_step);
+    const ClsPair *row = s.pairs + (size_t)i * s.pairs_per_step;
+    // the member's count behind the chunk: the steps since its last reset, or n more (one block per member)
+    if (blockIdx.x == 0 && h == 0 && zi == 0) {
+        if (tid == 0) s_reset = -1;
+        __syncthreads();
+        for (int j = tid; j < n; j += HTM_CLASSIFIER_THREADS)
+            if (cls_reset_bit(s, first + j)) atomicMax(&s_reset, j);
+        __syncthreads();
+        if (tid == 0) *c.count = s_reset < 0 ? *c.count + n : (int64_t)(n - s_reset);
+    }
+    // the member's ring takes the chunk's last ring_len patterns (distinct slots), the whole row of each
+    if (h == 0 && zi >= n - c.ring_len)
+        for (int l = lo; l < c.max_pairs; l += (int)gridDim.x * HTM_CLASSIFIER_PAIRS)
+            cls_ring_copy(c, row, s.pairs_per_step, l, min(l + HTM_CLASSIFIER_PAIRS, c.max_pairs), (int)(t % c.ring_len));
+    for (int b = tid; b < c.B_pad; b += HTM_CLASSIFIER_THREADS) s_acc[b] = 0ull;
+    __syncthreads();
+    cls_sum_rows(c, c.w + (int64_t)h * c.w_stride, row, lo, hi, s_acc);
+    __syncthreads();
+    unsigned long long *acc = (unsigned long long *)f.acc + (size_t)y * c.B_pad;
+    uint32_t *ticket = f.ticket + y;
+    if (!cls_arrive(acc, s_acc, c.B_pad, ticket, gridDim.x, &s_last)) return;
+    cls_take(acc, s_acc, c.B_pad);
+    if (tid == 0) __hip_atomic_store(ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    int best;
+    int64_t z;
+    cls_softmax(c, s_acc, s_e, s_red, best, z);
+    cls_write_outputs(c, s, i, h, s_e, best, z);
+}
+
+// Pattern capture of a recorded group call (htm_set_group_run_active_cells; kcls_capture's twin): grid (blocks, B), block row y being
+// member y of the group's tables -- its Dev, its record descriptor (whose slot names the row) and its capture descriptor.  Directly
+// behind kgrp_rec_step of the step of parity p.  A member without rows, or a step outside the call's records, writes nothing.
+__global__ __launch_bounds__(256) void kgcls_capture(const Dev *__restrict__ tab, int p, RecDev *const *__restrict__ recs, const ClsCapDev *__restrict__ caps) {
+    const Dev &d = tab[blockIdx.y];
+    const RecDev *r = recs[blockIdx.y];
+    ClsPair *rows = caps[blockIdx.y].rows;
+    if (!rows) return;
+    const uint32_t slot = d.ctr->step[p] - r->base;
+    if (slot >= (uint32_t)r->n) return;
+    const int per = d.k * d.WPC, i = (int)(blockIdx.x * 256 + threadIdx.x);
+    if (i >= per) return;
+    const int col = d.active_cols[p][i / d.WPC];
+    ClsPair pr{-1, 0u};
+    if (col >= 0 && col < d.C) {
+        pr.index = col * d.WPC + i % d.WPC;
+        pr.word = d.act[p][pr.index];
+    }
+    rows[(size_t)slot * per + i] = pr;
+}
+
+// the flagged members' histories emptied (flags null: every member's); a thread per member
+__global__ __launch_bounds__(256) void kgcls_reset(int64_t *count, const int32_t *flags, int n) {
+    const int m = (int)(blockIdx.x * 256 + threadIdx.x);
+    if (m < n && (!flags || flags[m])) count[m] = 0;
+}
+
+#endif  // __HIPCC__
 #endif

@@ -25,6 +25,7 @@
 #include <cmath>
 #include <chrono>
 #include <map>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <tuple>
@@ -3668,6 +3669,10 @@ struct htm_group {
     std::map<std::vector<const void *>, GrpRecArgs *> rec_tabs;
     std::map<std::vector<int32_t *>, int32_t **> pin_tabs;      // the members' decoding outputs (htm_set_run_predicted_input)
     std::map<GroupGraphKey, hipGraphExec_t> graphs;
+    // pattern capture (htm_set_group_run_active_cells): each member's capture descriptor (a constant address: graphs read the rows
+    // through it), filled by the setter; capturing: rows are set
+    ClsCapDev *d_caps = nullptr;
+    bool capturing = false;
     // inference views (htm_create_view): some member is a view; every member aliases one set of weights (then the steps with
     // learning = 0 scan the store once per chunk of share_m members: kgrp_scan_shared, share_chunks x share_blocks blocks)
     bool has_view, shared;
@@ -3683,6 +3688,13 @@ struct htm_group {
         htm_step_record *d_recs = nullptr;        // the members' record slots [n] ...
         GrpRecArgs *rec_args = nullptr;           // ... as kgrp_rec_begin takes them
         int32_t **vote_tab = nullptr;             // the members' vote rows (in the result block) as kgrp_pin_begin takes them
+        // a classified tick (htm_classifiers_tick): its outputs best [n][H][2], dist [n][H][buckets] lie in the result block directly
+        // in FRONT of the likelihoods (cls_cap bytes, grown when a tick needs more), so that the copy out stays one; its targets [n]
+        // lie in the staging block directly behind what the tick copies in anyway; the members' captured patterns [n][k * WPC] and
+        // the table of their capture descriptors (a constant address: the tick's graphs read the rows through it)
+        size_t off_lik = 0, cls_cap = 0;
+        ClsPair *cap_rows = nullptr;
+        ClsCapDev *d_caps = nullptr;
     } live;
 };
 
@@ -3869,7 +3881,8 @@ static decltype(&kgrp_tail<1>) const kt_grp_tail[4] = {kgrp_tail<1>, kgrp_tail<2
 static decltype(&kgrp_scan<true, 1>) const kt_grp_scan[4] = {kgrp_scan<true, 1>, kgrp_scan<false, 1>, kgrp_scan<true, 6>, kgrp_scan<false, 6>};
 
 // one step of every member (parity p): the one-role-per-launch schedule of enqueue_rest, unfused (htm_group.h)
-static void group_enqueue_step(htm_group *g, RunModes m, const uint32_t *const *banks, int n_inputs, int learning, int p, const GroupForm &f) {
+static void group_enqueue_step(htm_group *g, RunModes m, const uint32_t *const *banks, int n_inputs, int learning, int p, const GroupForm &f,
+                               const ClsCapDev *caps = nullptr) {
     htm_handle *h = g->m[0];                   // (launch sizes and profiling: the members' are equal)
     const Dev &d = h->d;
     const hipStream_t s = g->stream;
@@ -3907,6 +3920,9 @@ static void group_enqueue_step(htm_group *g, RunModes m, const uint32_t *const *
         const dim3 g_rec(rec_blocks(d), B);
         LAUNCH_ON(h, s, 0, "group:record", kgrp_rec_step, g_rec, 256, tab, p, g->d_recs);
     }
+    // the members' active-cell words, directly behind the record launch (htm_classifier.h); nothing outside a capturing call
+    // (caps: the table of a live tick; the group's own otherwise)
+    if (m.capturing) LAUNCH_ON(h, s, 0, "group:active_cells", kgcls_capture, dim3(cap_blocks(d), B), 256, tab, p, g->d_recs, caps ? caps : (const ClsCapDev *)g->d_caps);
     if (m.decoding) {
         const dim3 g_pin(pin_blocks(d.C), B);
         LAUNCH_ON(h, s, 0, "group:predicted_input", kgrp_pin_step, g_pin, 256, tab, p, g->d_pins);
@@ -3997,7 +4013,7 @@ static int group_begin_modes(htm_group *g, int n_steps, const htm_run_record *re
         LAUNCH_ON(h0, s, 0, "group:predicted_input", kgrp_pin_begin, dim3(pin_begin_blocks(n_steps, h0->d.I), B), 256, g->d_tab, (int)((h0->step_host + 1) & 1), g->d_pins, out_tab, n_steps);
     }
     const bool feeding = std::any_of(g->m.begin(), g->m.end(), [](const htm_handle *h) { return h->feed_bank != nullptr; });
-    *modes = RunModes{records != nullptr, false, decoding, feeding};
+    *modes = RunModes{records != nullptr, false, decoding, feeding, records != nullptr && g->capturing};
     return 0;
 }
 
@@ -4050,7 +4066,9 @@ extern "C" int htm_group_run(htm_group *g, const uint32_t *const *device_banks, 
     if (!device_banks || n_inputs < 1 || n_steps < 0) { g->err = "htm_group_run: need device_banks, n_inputs >= 1 and n_steps >= 0"; return HTM_ERR_ARGUMENT; }
     if (learning && g->has_view) { g->err = "htm_group_run: a group with inference views steps with learning = 0 only"; return HTM_ERR_STATE; }
     int rc = group_check(g, device_banks, records, n_inputs, learning);
-    if (rc || n_steps == 0) return rc;
+    if (rc) return rc;
+    if (g->capturing && !records) { g->err = "htm_group_run: active-cell rows are set (htm_set_group_run_active_cells): only a recorded run fills them"; return HTM_ERR_ARGUMENT; }
+    if (n_steps == 0) return rc;
     GHIPCHK(g, hipSetDevice(g->device));
     rc = group_join(g);
     if (rc) return rc;
@@ -4067,6 +4085,7 @@ extern "C" int htm_group_step(htm_group *g, const uint32_t *packed_inputs, int32
     if (learning && g->has_view) { g->err = "htm_group_step: a group with inference views steps with learning = 0 only"; return HTM_ERR_STATE; }
     int rc = group_check(g, nullptr, records);
     if (rc) return rc;
+    if (g->capturing && !records) { g->err = "htm_group_step: active-cell rows are set (htm_set_group_run_active_cells): only a recorded step fills them"; return HTM_ERR_ARGUMENT; }
     GHIPCHK(g, hipSetDevice(g->device));
     rc = group_join(g);
     if (rc) return rc;
@@ -4075,6 +4094,25 @@ extern "C" int htm_group_step(htm_group *g, const uint32_t *packed_inputs, int32
     const size_t words = (size_t)(d.I + 31) / 32;
     GHIPCHK(g, hipMemcpy2DAsync(g->stage, (size_t)d.W * 4, packed_inputs, words * 4, words * 4, g->n, hipMemcpyHostToDevice, g->stream));
     return group_run(g, g->stage_tab, 1, 1, learning, 0, records);
+}
+
+// Pattern capture of the group's recorded calls (htm_classifier.h, kgcls_capture): the members' rows go into the group's table of
+// capture descriptors with one copy on the group's stream, from the call's own words (read when the copy returns) -- the runs that
+// follow, and the graphs they replay, read the rows through the table.  NULL clears them.
+extern "C" int htm_set_group_run_active_cells(htm_group *g, void *const *device_pairs) {
+    if (!g) return HTM_ERR_ARGUMENT;
+    if (!device_pairs) { g->capturing = false; return HTM_OK; }
+    for (int i = 0; i < g->n; ++i) {
+        if (!device_pairs[i]) { g->err = "htm_set_group_run_active_cells: member " + std::to_string(i) + ": null rows"; return HTM_ERR_ARGUMENT; }
+        if (int rc = pin_refuse(g->m[i], "htm_set_group_run_active_cells")) { g->err = "member " + std::to_string(i) + ": " + g->m[i]->err; return rc; }
+    }
+    GHIPCHK(g, hipSetDevice(g->device));
+    if (!g->d_caps && galloc(g, &g->d_caps, (size_t)g->n)) return HTM_ERR_HIP;
+    std::vector<ClsCapDev> caps((size_t)g->n);
+    for (int i = 0; i < g->n; ++i) caps[i].rows = (ClsPair *)device_pairs[i];
+    GHIPCHK(g, hipMemcpyAsync(g->d_caps, caps.data(), caps.size() * sizeof(ClsCapDev), hipMemcpyHostToDevice, g->stream));
+    g->capturing = true;
+    return HTM_OK;
 }
 
 // ------------------------------------------------------------------------------------------
@@ -4217,11 +4255,18 @@ extern "C" int htm_likelihood_import(htm_likelihood *lk, htm_handle *h, const vo
 // host.  As the likelihood object it keeps nothing of the handles its calls come through.
 struct htm_classifier {
     int device = 0;
-    ClsDev d{};
-    ClsFrozen frozen{};                         // allocated by the first frozen call
+    ClsDev d{};                                 // (of a bank: member 0's)
+    ClsFrozen frozen{};                         // the frozen calls' accumulators: made by the first one, made anew when a call needs more rows
+    size_t frozen_rows = 0;                     // (streams x steps of a launch x horizons) rows they hold
     int64_t total = 0;
-    size_t ring_bytes = 0;
+    size_t ring_bytes = 0;                      // of one stream
     std::vector<void *> allocs;
+    // a bank (htm_classifiers_create): n streams, member-major; a single object has n = 1
+    int n = 1;
+    bool shares = false;                        // the weights are another object's: read here, never written
+    std::shared_ptr<void> weights;              // the weight block, freed with the last object that holds it
+    void **d_tab = nullptr;                     // [3][n] device pointers of a call: pairs, targets, reset bits
+    int32_t *d_flags = nullptr;                 // [n] the streams a reset names
 };
 
 static int cls_refuse(htm_handle *h, const std::string &msg, int code) {
@@ -4246,22 +4291,37 @@ static T *cls_alloc(htm_classifier *clf, htm_handle *h, size_t count) {
     return (T *)p;
 }
 
-extern "C" int htm_classifier_create(htm_handle *h, const htm_classifier_config *cfg, const int32_t *exp_table2049, htm_classifier **out) {
+// the one constructor: n streams of one config, over weights of their own or (share) over the table of an existing object
+static int cls_create(const std::string &what, htm_handle *h, const htm_classifier_config *cfg, const int32_t *exp_table2049, int32_t n, htm_classifier *share,
+                      htm_classifier **out) {
     if (out) *out = nullptr;
-    if (!h || !cfg || !exp_table2049 || !out) return cls_refuse(h, "htm_classifier_create: null argument", HTM_ERR_ARGUMENT);
-    if (cfg->struct_bytes != sizeof(htm_classifier_config)) return cls_refuse(h, "htm_classifier_create: htm_classifier_config size mismatch", HTM_ERR_ARGUMENT);
+    if (!h || !cfg || !exp_table2049 || !out) return cls_refuse(h, what + ": null argument", HTM_ERR_ARGUMENT);
+    if (cfg->struct_bytes != sizeof(htm_classifier_config)) return cls_refuse(h, what + ": htm_classifier_config size mismatch", HTM_ERR_ARGUMENT);
     bool ok = cfg->buckets >= 1 && cfg->buckets <= HTM_CLASSIFIER_MAX_BUCKETS && cfg->n_steps >= 1 && cfg->n_steps <= HTM_CLASSIFIER_MAX_HORIZONS &&
               cfg->alpha_q >= 1 && cfg->alpha_q <= 65536 && cfg->cell_dim >= 1 && cfg->cell_dim <= 64 && cfg->units >= cfg->cell_dim &&
               cfg->units % cfg->cell_dim == 0 && cfg->max_pairs >= 1;
     for (int i = 0; ok && i < cfg->n_steps; ++i)
         ok = cfg->steps[i] >= 0 && cfg->steps[i] <= HTM_CLASSIFIER_MAX_HORIZON && (i == 0 || cfg->steps[i] > cfg->steps[i - 1]);
     if (!ok)
-        return cls_refuse(h, "htm_classifier_create: buckets in [1, 1024], 1 to 8 ascending steps in [0, 64], alpha_q in [1, 65536], cell_dim in [1, 64], "
+        return cls_refuse(h, what + ": buckets in [1, 1024], 1 to 8 ascending steps in [0, 64], alpha_q in [1, 65536], cell_dim in [1, 64], "
                              "units a positive multiple of cell_dim, max_pairs >= 1", HTM_ERR_ARGUMENT);
-    if (h->world > 1) return cls_refuse(h, "htm_classifier_create: not available on a column-sharded handle", HTM_ERR_STATE);
+    if (n < 1 || n > 65535 / cfg->n_steps)
+        return cls_refuse(h, what + ": n_streams must be in [1, 65535 / n_steps = " + std::to_string(65535 / cfg->n_steps) + "] (the member shares grid y with the horizon)",
+                          HTM_ERR_ARGUMENT);
+    if (h->world > 1) return cls_refuse(h, what + ": not available on a column-sharded handle", HTM_ERR_STATE);
+    if (share) {
+        const ClsDev &o = share->d;
+        bool same = share->n == 1 && o.B == cfg->buckets && o.H == cfg->n_steps && o.K == cfg->cell_dim && (int64_t)o.n_cols * o.K == cfg->units &&
+                    o.alpha_q == cfg->alpha_q && o.max_pairs == cfg->max_pairs;
+        for (int i = 0; same && i < o.H; ++i) same = o.steps[i] == cfg->steps[i];
+        if (!same) return cls_refuse(h, what + ": share_weights_of must be a one-stream classifier of the same config", HTM_ERR_ARGUMENT);
+        if (share->device != h->device) return cls_refuse(h, what + ": share_weights_of lives on another device than the handle", HTM_ERR_ARGUMENT);
+    }
     HIPCHK(h, hipSetDevice(h->device));
     htm_classifier *clf = new htm_classifier();
     clf->device = h->device;
+    clf->n = n;
+    clf->shares = share != nullptr;
     ClsDev &d = clf->d;
     d.B = cfg->buckets;
     d.B_pad = (cfg->buckets + 3) & ~3;
@@ -4275,27 +4335,52 @@ extern "C" int htm_classifier_create(htm_handle *h, const htm_classifier_config 
     for (int i = 0; i < d.H; ++i) d.steps[i] = cfg->steps[i];
     d.w_stride = (int64_t)cfg->units * d.B_pad;
     clf->ring_bytes = (size_t)d.ring_len * d.max_pairs * sizeof(ClsPair);
-    d.w = cls_alloc<int32_t>(clf, h, (size_t)d.H * (size_t)d.w_stride);
-    d.ring = cls_alloc<ClsPair>(clf, h, (size_t)d.ring_len * d.max_pairs);
-    d.count = cls_alloc<int64_t>(clf, h, 2);
-    d.acc = cls_alloc<int64_t>(clf, h, (size_t)d.H * 2 * d.B_pad);
-    d.ticket = cls_alloc<uint32_t>(clf, h, HTM_CLASSIFIER_MAX_HORIZONS);
-    d.delta = cls_alloc<int32_t>(clf, h, (size_t)d.H * d.B_pad);
-    d.learn = cls_alloc<int32_t>(clf, h, HTM_CLASSIFIER_MAX_HORIZONS);
+    const size_t N = (size_t)n;
+    if (share) {
+        clf->weights = share->weights;          // (nothing is copied: the table is read where it lies)
+        d.w = share->d.w;
+    } else {
+        d.w = cls_alloc<int32_t>(clf, h, N * d.H * (size_t)d.w_stride);
+        if (d.w) {                              // (the block leaves the object's own list: the last holder frees it)
+            clf->allocs.pop_back();
+            const int device = clf->device;
+            clf->weights = std::shared_ptr<void>((void *)d.w, [device](void *p) { hipSetDevice(device); hipFree(p); });
+        }
+    }
+    d.ring = cls_alloc<ClsPair>(clf, h, N * d.ring_len * d.max_pairs);
+    d.count = cls_alloc<int64_t>(clf, h, N + 1);
+    d.acc = cls_alloc<int64_t>(clf, h, N * d.H * 2 * d.B_pad);
+    d.ticket = cls_alloc<uint32_t>(clf, h, std::max<size_t>(N * d.H, HTM_CLASSIFIER_MAX_HORIZONS));
+    d.delta = cls_alloc<int32_t>(clf, h, N * d.H * d.B_pad);
+    d.learn = cls_alloc<int32_t>(clf, h, std::max<size_t>(N * d.H, HTM_CLASSIFIER_MAX_HORIZONS));
     int32_t *table = cls_alloc<int32_t>(clf, h, HTM_CLASSIFIER_EXP);
     d.exp_table = table;
     ok = d.w && d.ring && d.count && d.acc && d.ticket && d.delta && d.learn && table;
+    if (n > 1) {
+        clf->d_tab = cls_alloc<void *>(clf, h, 3 * N);
+        clf->d_flags = cls_alloc<int32_t>(clf, h, N);
+        ok = ok && clf->d_tab && clf->d_flags;
+    }
     // an empty ring holds (-1, 0) pairs; the state and the table are there when the call returns, whatever stream the first update comes on
-    std::vector<ClsPair> empty((size_t)d.ring_len * d.max_pairs, ClsPair{-1, 0u});
-    ok = ok && hipMemcpyAsync(d.ring, empty.data(), clf->ring_bytes, hipMemcpyHostToDevice, h->stream) == hipSuccess &&
+    std::vector<ClsPair> empty(N * d.ring_len * d.max_pairs, ClsPair{-1, 0u});
+    ok = ok && hipMemcpyAsync(d.ring, empty.data(), N * clf->ring_bytes, hipMemcpyHostToDevice, h->stream) == hipSuccess &&
          hipMemcpyAsync(table, exp_table2049, HTM_CLASSIFIER_EXP * sizeof(int32_t), hipMemcpyHostToDevice, h->stream) == hipSuccess &&
          hipStreamSynchronize(h->stream) == hipSuccess;
     if (!ok) {
         htm_classifier_destroy(clf);
-        return cls_refuse(h, "htm_classifier_create: device allocation failed", HTM_ERR_HIP);
+        return cls_refuse(h, what + ": device allocation failed", HTM_ERR_HIP);
     }
     *out = clf;
     return HTM_OK;
+}
+
+extern "C" int htm_classifier_create(htm_handle *h, const htm_classifier_config *cfg, const int32_t *exp_table2049, htm_classifier **out) {
+    return cls_create("htm_classifier_create", h, cfg, exp_table2049, 1, nullptr, out);
+}
+
+extern "C" int htm_classifiers_create(htm_handle *h, const htm_classifier_config *cfg, const int32_t *exp_table2049, int32_t n_streams,
+                                      htm_classifier *share_weights_of, htm_classifier **out) {
+    return cls_create("htm_classifiers_create", h, cfg, exp_table2049, n_streams, share_weights_of, out);
 }
 
 // what every call on an existing object checks of its handle
@@ -4306,15 +4391,43 @@ static int cls_check(const char *what, htm_classifier *clf, htm_handle *h) {
     return 0;
 }
 
+// ... and what the calls of a one-stream object check besides: a bank has calls of its own (htm_classifiers_*)
+static int cls_check_single(const char *what, htm_classifier *clf, htm_handle *h) {
+    if (int rc = cls_check(what, clf, h)) return rc;
+    if (clf->n > 1) return cls_refuse(h, std::string(what) + ": the object has " + std::to_string(clf->n) + " streams: use the htm_classifiers_ calls", HTM_ERR_ARGUMENT);
+    return 0;
+}
+
 extern "C" int64_t htm_classifier_state_bytes(const htm_classifier *clf) { return clf ? (int64_t)(16 + clf->ring_bytes) : (int64_t)HTM_ERR_ARGUMENT; }
 
 // blocks along x of the launches that split a pattern of n pairs
 static int cls_blocks(int n_pairs) { return (n_pairs + HTM_CLASSIFIER_PAIRS - 1) / HTM_CLASSIFIER_PAIRS; }
 
+// The accumulators of a frozen call, for `rows` block rows (streams x steps of one launch x horizons): [rows][B_pad] sums and [rows]
+// tickets, zero between launches.  Sized by what the calls ask for -- a bank that only ticks needs one step's -- and made anew when a
+// call needs more (hipFree waits for the device: nothing enqueued still uses the old ones).
+static int cls_frozen_rows(const char *what, htm_classifier *clf, htm_handle *h, size_t rows) {
+    if (rows <= clf->frozen_rows) return 0;
+    for (void *p : {(void *)clf->frozen.acc, (void *)clf->frozen.ticket}) {
+        if (!p) continue;
+        clf->allocs.erase(std::remove(clf->allocs.begin(), clf->allocs.end(), p), clf->allocs.end());
+        hipFree(p);
+    }
+    clf->frozen = ClsFrozen{};
+    clf->frozen_rows = 0;
+    ClsFrozen f;
+    f.acc = cls_alloc<int64_t>(clf, h, rows * clf->d.B_pad);
+    f.ticket = cls_alloc<uint32_t>(clf, h, rows);
+    if (!f.acc || !f.ticket) return cls_refuse(h, std::string(what) + ": device allocation failed", HTM_ERR_HIP);
+    clf->frozen = f;
+    clf->frozen_rows = rows;
+    return 0;
+}
+
 extern "C" int htm_classifier_update(htm_classifier *clf, htm_handle *h, const void *device_pairs, int32_t pairs_per_step, int32_t n_steps,
                                      const int32_t *device_targets, int32_t n_targets, int32_t first_step, const uint32_t *device_reset_bits,
                                      int32_t learn, int32_t *device_best, int32_t *device_dist) {
-    if (int rc = cls_check("htm_classifier_update", clf, h)) return rc;
+    if (int rc = cls_check_single("htm_classifier_update", clf, h)) return rc;
     if (!device_pairs || !device_targets || !device_best) return cls_refuse(h, "htm_classifier_update: null pairs, targets or output", HTM_ERR_ARGUMENT);
     const ClsDev &d = clf->d;
     if (pairs_per_step < 1 || pairs_per_step > d.max_pairs)
@@ -4322,13 +4435,8 @@ extern "C" int htm_classifier_update(htm_classifier *clf, htm_handle *h, const v
     if (n_steps < 0 || n_targets < 1 || first_step < 0) return cls_refuse(h, "htm_classifier_update: n_steps >= 0, n_targets >= 1, first_step >= 0", HTM_ERR_ARGUMENT);
     if (n_steps == 0) return HTM_OK;
     HIPCHK(h, hipSetDevice(clf->device));
-    if (!learn && !clf->frozen.acc) {
-        ClsFrozen f;
-        f.acc = cls_alloc<int64_t>(clf, h, (size_t)HTM_CLASSIFIER_CHUNK * d.H * d.B_pad);
-        f.ticket = cls_alloc<uint32_t>(clf, h, (size_t)HTM_CLASSIFIER_CHUNK * d.H);
-        if (!f.acc || !f.ticket) return cls_refuse(h, "htm_classifier_update: device allocation failed", HTM_ERR_HIP);
-        clf->frozen = f;
-    }
+    if (learn && clf->shares) return cls_refuse(h, "htm_classifier_update: the object reads another object's weights: learn must be 0", HTM_ERR_STATE);
+    if (!learn) { if (int rc = cls_frozen_rows("htm_classifier_update", clf, h, (size_t)HTM_CLASSIFIER_CHUNK * d.H)) return rc; }
     const ClsStep s{(const ClsPair *)device_pairs, pairs_per_step, device_targets, device_reset_bits, n_targets, first_step, device_best, device_dist, clf->total};
     if (learn) {
         const dim3 grid(cls_blocks(d.max_pairs), d.H);
@@ -4347,7 +4455,7 @@ extern "C" int htm_classifier_update(htm_classifier *clf, htm_handle *h, const v
 }
 
 extern "C" int htm_classifier_reset(htm_classifier *clf, htm_handle *h) {
-    if (int rc = cls_check("htm_classifier_reset", clf, h)) return rc;
+    if (int rc = cls_check_single("htm_classifier_reset", clf, h)) return rc;
     HIPCHK(h, hipSetDevice(clf->device));
     HIPCHK(h, hipMemsetAsync(clf->d.count, 0, 16, h->stream));
     return HTM_OK;
@@ -4355,7 +4463,7 @@ extern "C" int htm_classifier_reset(htm_classifier *clf, htm_handle *h) {
 
 // the rows of one horizon's table a weights call names, or a refusal
 static int cls_rows(const char *what, htm_classifier *clf, htm_handle *h, int32_t horizon, int32_t unit0, int32_t n_units, const void *host) {
-    if (int rc = cls_check(what, clf, h)) return rc;
+    if (int rc = cls_check_single(what, clf, h)) return rc;
     const ClsDev &d = clf->d;
     const int64_t units = d.w_stride / d.B_pad;
     if (!host || horizon < 0 || horizon >= d.H || unit0 < 0 || n_units < 0 || (int64_t)unit0 + n_units > units)
@@ -4376,6 +4484,7 @@ extern "C" int htm_classifier_read_weights(htm_classifier *clf, htm_handle *h, i
 
 extern "C" int htm_classifier_write_weights(htm_classifier *clf, htm_handle *h, int32_t horizon, int32_t unit0, int32_t n_units, const int32_t *host_src) {
     if (int rc = cls_rows("htm_classifier_write_weights", clf, h, horizon, unit0, n_units, host_src)) return rc;
+    if (clf->shares) return cls_refuse(h, "htm_classifier_write_weights: the object reads another object's weights: write them there", HTM_ERR_STATE);
     const ClsDev &d = clf->d;
     for (size_t i = 0; i < (size_t)n_units * d.B; ++i)
         if (host_src[i] > HTM_CLASSIFIER_W_LIMIT || host_src[i] < -HTM_CLASSIFIER_W_LIMIT)
@@ -4390,7 +4499,7 @@ extern "C" int htm_classifier_write_weights(htm_classifier *clf, htm_handle *h, 
 }
 
 extern "C" int htm_classifier_export(htm_classifier *clf, htm_handle *h, void *host_state, int64_t bytes) {
-    if (int rc = cls_check("htm_classifier_export", clf, h)) return rc;
+    if (int rc = cls_check_single("htm_classifier_export", clf, h)) return rc;
     if (!host_state || bytes != htm_classifier_state_bytes(clf)) return cls_refuse(h, "htm_classifier_export: need host_state of htm_classifier_state_bytes bytes", HTM_ERR_ARGUMENT);
     HIPCHK(h, hipSetDevice(clf->device));
     HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -4401,7 +4510,7 @@ extern "C" int htm_classifier_export(htm_classifier *clf, htm_handle *h, void *h
 }
 
 extern "C" int htm_classifier_import(htm_classifier *clf, htm_handle *h, const void *host_state, int64_t bytes) {
-    if (int rc = cls_check("htm_classifier_import", clf, h)) return rc;
+    if (int rc = cls_check_single("htm_classifier_import", clf, h)) return rc;
     if (!host_state || bytes != htm_classifier_state_bytes(clf)) return cls_refuse(h, "htm_classifier_import: need host_state of htm_classifier_state_bytes bytes", HTM_ERR_ARGUMENT);
     int64_t head[2];
     memcpy(head, host_state, 16);
@@ -4416,44 +4525,241 @@ extern "C" int htm_classifier_import(htm_classifier *clf, htm_handle *h, const v
 }
 
 // ------------------------------------------------------------------------------------------
+// A bank of classifiers (htm_classifier.h, the kgcls_ kernels): n streams of one config in one object, every
+// call over all of them in the launches of one.  The total is the object's: every call advances all streams by the same steps.
+static GClsDev gcls_of(const htm_classifier *clf) { return GClsDev{clf->d, clf->n, clf->shares ? 0 : (int64_t)clf->d.H * clf->d.w_stride}; }
+
+// The launches of an update over every stream, enqueued on stream s: 2 per step when learning, one per gcls_chunk steps otherwise.
+// gs holds the call's inputs (a table in device memory, or member 0's pointers and strides); the caller has checked them.
+static int gcls_prepare(htm_classifier *clf, htm_handle *h, int32_t learn, int32_t n_steps) {
+    const ClsDev &d = clf->d;
+    const int chunk = gcls_chunk(clf->n, d.H);
+    if (learn) return 0;                            // (a frozen call: accumulators for the steps of its largest launch)
+    return cls_frozen_rows("htm_classifiers_update", clf, h, (size_t)clf->n * std::min<int>(chunk, std::max(n_steps, 1)) * d.H);
+}
+
+static int gcls_enqueue(htm_classifier *clf, htm_handle *h, hipStream_t s, GClsStep gs, int32_t learn) {
+    const ClsDev &d = clf->d;
+    const int chunk = gcls_chunk(clf->n, d.H);
+    if (int rc = gcls_prepare(clf, h, learn, gs.n_steps)) return rc;
+    gs.total = clf->total;
+    const GClsDev gd = gcls_of(clf);
+    if (learn) {
+        const dim3 grid(cls_blocks(d.max_pairs), clf->n * d.H);
+        for (int i = 0; i < gs.n_steps; ++i) {
+            LAUNCH_ON(h, s, 0, "classifiers:sum", kgcls_sum, grid, HTM_CLASSIFIER_THREADS, gd, gs, i);
+            LAUNCH_ON(h, s, 0, "classifiers:apply", kgcls_apply, grid, HTM_CLASSIFIER_THREADS, gd, gs, i);
+        }
+    } else {
+        for (int first = 0; first < gs.n_steps; first += chunk) {
+            const int n = std::min<int>(chunk, gs.n_steps - first);
+            LAUNCH_ON(h, s, 0, "classifiers:frozen", kgcls_frozen, dim3(cls_blocks(gs.pairs_per_step), clf->n * n * d.H), HTM_CLASSIFIER_THREADS, gd, clf->frozen, gs,
+                      first, n);
+        }
+    }
+    clf->total += gs.n_steps;
+    return 0;
+}
+
+extern "C" int htm_classifiers_update(htm_classifier *clf, htm_handle *h, const void *const *device_pairs, int32_t pairs_per_step, int32_t n_steps,
+                                      const int32_t *const *device_targets, int32_t n_targets, int32_t first_step, const uint32_t *const *device_reset_bits,
+                                      int32_t learn, int32_t *device_best, int32_t *device_dist) {
+    if (int rc = cls_check("htm_classifiers_update", clf, h)) return rc;
+    if (!device_pairs || !device_targets || !device_best) return cls_refuse(h, "htm_classifiers_update: null pairs, targets or output", HTM_ERR_ARGUMENT);
+    const ClsDev &d = clf->d;
+    const size_t n = (size_t)clf->n;
+    for (size_t i = 0; i < n; ++i)
+        if (!device_pairs[i] || !device_targets[i] || (device_reset_bits && !device_reset_bits[i]))
+            return cls_refuse(h, "htm_classifiers_update: stream " + std::to_string(i) + " has no pairs, targets or reset bits", HTM_ERR_ARGUMENT);
+    if (pairs_per_step < 1 || pairs_per_step > d.max_pairs)
+        return cls_refuse(h, "htm_classifiers_update: pairs_per_step must be in [1, max_pairs = " + std::to_string(d.max_pairs) + "]", HTM_ERR_ARGUMENT);
+    if (n_steps < 0 || n_targets < 1 || first_step < 0) return cls_refuse(h, "htm_classifiers_update: n_steps >= 0, n_targets >= 1, first_step >= 0", HTM_ERR_ARGUMENT);
+    if (learn && clf->shares)
+        return cls_refuse(h, "htm_classifiers_update: the streams read another object's weight table: learn must be 0", HTM_ERR_STATE);
+    if (n_steps == 0) return HTM_OK;
+    HIPCHK(h, hipSetDevice(clf->device));
+    GClsStep gs;
+    memset(&gs, 0, sizeof(gs));
+    if (n > 1) {
+        // the one copy of the pointer table, from the call's own (pageable) words: the copy has read them when it returns (htm_likelihood_update)
+        std::vector<const void *> tab(3 * n, nullptr);
+        for (size_t i = 0; i < n; ++i) {
+            tab[i] = device_pairs[i];
+            tab[n + i] = device_targets[i];
+            if (device_reset_bits) tab[2 * n + i] = device_reset_bits[i];
+        }
+        HIPCHK(h, hipMemcpyAsync((void *)clf->d_tab, (const void *)tab.data(), 3 * n * sizeof(void *), hipMemcpyHostToDevice, h->stream));
+        gs.pairs_tab = (const ClsPair *const *)clf->d_tab;
+        gs.targets_tab = (const int32_t *const *)(clf->d_tab + n);
+        gs.resets_tab = device_reset_bits ? (const uint32_t *const *)(clf->d_tab + 2 * n) : nullptr;
+    } else {
+        gs.pairs = (const ClsPair *)device_pairs[0];
+        gs.targets = device_targets[0];
+        gs.reset_bits = device_reset_bits ? device_reset_bits[0] : nullptr;
+    }
+    gs.pairs_per_step = pairs_per_step;
+    gs.n_targets = n_targets;
+    gs.first_step = first_step;
+    gs.n_steps = n_steps;
+    gs.best = device_best;
+    gs.dist = device_dist;
+    if (int rc = gcls_enqueue(clf, h, h->stream, gs, learn)) return rc;
+    return launch_status(h->err);
+}
+
+extern "C" int htm_classifiers_reset(htm_classifier *clf, htm_handle *h, const uint8_t *streams) {
+    if (int rc = cls_check("htm_classifiers_reset", clf, h)) return rc;
+    HIPCHK(h, hipSetDevice(clf->device));
+    if (!streams || clf->n == 1) {
+        if (!streams || streams[0]) HIPCHK(h, hipMemsetAsync(clf->d.count, 0, (size_t)clf->n * 8, h->stream));
+        return HTM_OK;
+    }
+    std::vector<int32_t> flags((size_t)clf->n);     // (the call's own pageable words: the copy has read them when it returns)
+    for (int i = 0; i < clf->n; ++i) flags[i] = streams[i] ? 1 : 0;
+    HIPCHK(h, hipMemcpyAsync(clf->d_flags, flags.data(), flags.size() * 4, hipMemcpyHostToDevice, h->stream));
+    LAUNCH(h, "classifiers:reset", kgcls_reset, (clf->n + 255) / 256, 256, clf->d.count, (const int32_t *)clf->d_flags, clf->n);
+    return launch_status(h->err);
+}
+
+// the rows of one stream's, one horizon's table a weights call names, or a refusal -> the first of them through *rows
+static int gcls_rows(const char *what, htm_classifier *clf, htm_handle *h, int32_t stream, int32_t horizon, int32_t unit0, int32_t n_units, const void *host,
+                     int32_t **rows) {
+    if (int rc = cls_check(what, clf, h)) return rc;
+    const ClsDev &d = clf->d;
+    const int64_t units = d.w_stride / d.B_pad;
+    if (!host || stream < 0 || stream >= clf->n || horizon < 0 || horizon >= d.H || unit0 < 0 || n_units < 0 || (int64_t)unit0 + n_units > units)
+        return cls_refuse(h, std::string(what) + ": need host memory, a stream below n_streams, a horizon index below n_steps and rows inside the table", HTM_ERR_ARGUMENT);
+    *rows = d.w + (int64_t)stream * gcls_of(clf).w_member + (int64_t)horizon * d.w_stride + (int64_t)unit0 * d.B_pad;
+    return 0;
+}
+
+extern "C" int htm_classifiers_read_weights(htm_classifier *clf, htm_handle *h, int32_t stream, int32_t horizon, int32_t unit0, int32_t n_units, int32_t *host_dst) {
+    int32_t *rows = nullptr;
+    if (int rc = gcls_rows("htm_classifiers_read_weights", clf, h, stream, horizon, unit0, n_units, host_dst, &rows)) return rc;
+    if (n_units == 0) return HTM_OK;
+    const ClsDev &d = clf->d;
+    HIPCHK(h, hipSetDevice(clf->device));
+    HIPCHK(h, hipMemcpy2DAsync(host_dst, (size_t)d.B * 4, rows, (size_t)d.B_pad * 4, (size_t)d.B * 4, (size_t)n_units, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return HTM_OK;
+}
+
+extern "C" int htm_classifiers_write_weights(htm_classifier *clf, htm_handle *h, int32_t stream, int32_t horizon, int32_t unit0, int32_t n_units,
+                                             const int32_t *host_src) {
+    int32_t *rows = nullptr;
+    if (int rc = gcls_rows("htm_classifiers_write_weights", clf, h, stream, horizon, unit0, n_units, host_src, &rows)) return rc;
+    if (clf->shares) return cls_refuse(h, "htm_classifiers_write_weights: the streams read another object's weights: write them there", HTM_ERR_STATE);
+    const ClsDev &d = clf->d;
+    for (size_t i = 0; i < (size_t)n_units * d.B; ++i)
+        if (host_src[i] > HTM_CLASSIFIER_W_LIMIT || host_src[i] < -HTM_CLASSIFIER_W_LIMIT)
+            return cls_refuse(h, "htm_classifiers_write_weights: a weight is outside [-2^30, 2^30]", HTM_ERR_ARGUMENT);
+    if (n_units == 0) return HTM_OK;
+    HIPCHK(h, hipSetDevice(clf->device));
+    HIPCHK(h, hipMemcpy2DAsync(rows, (size_t)d.B_pad * 4, host_src, (size_t)d.B * 4, (size_t)d.B * 4, (size_t)n_units, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return HTM_OK;
+}
+
+// the state of a bank: int64 total; int64 count[n]; the rings [n][ring_len][max_pairs]
+extern "C" int64_t htm_classifiers_state_bytes(const htm_classifier *clf) {
+    return clf ? (int64_t)(8 + (size_t)clf->n * 8 + (size_t)clf->n * clf->ring_bytes) : (int64_t)HTM_ERR_ARGUMENT;
+}
+
+extern "C" int htm_classifiers_export(htm_classifier *clf, htm_handle *h, void *host_state, int64_t bytes) {
+    if (int rc = cls_check("htm_classifiers_export", clf, h)) return rc;
+    if (!host_state || bytes != htm_classifiers_state_bytes(clf)) return cls_refuse(h, "htm_classifiers_export: need host_state of htm_classifiers_state_bytes bytes", HTM_ERR_ARGUMENT);
+    const size_t n = (size_t)clf->n;
+    HIPCHK(h, hipSetDevice(clf->device));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    memcpy(host_state, &clf->total, 8);
+    HIPCHK(h, hipMemcpy((char *)host_state + 8, clf->d.count, n * 8, hipMemcpyDeviceToHost));
+    HIPCHK(h, hipMemcpy((char *)host_state + 8 + n * 8, clf->d.ring, n * clf->ring_bytes, hipMemcpyDeviceToHost));
+    return HTM_OK;
+}
+
+extern "C" int htm_classifiers_import(htm_classifier *clf, htm_handle *h, const void *host_state, int64_t bytes) {
+    if (int rc = cls_check("htm_classifiers_import", clf, h)) return rc;
+    if (!host_state || bytes != htm_classifiers_state_bytes(clf)) return cls_refuse(h, "htm_classifiers_import: need host_state of htm_classifiers_state_bytes bytes", HTM_ERR_ARGUMENT);
+    const size_t n = (size_t)clf->n;
+    std::vector<int64_t> head(n + 1);
+    memcpy(head.data(), host_state, (n + 1) * 8);
+    for (size_t i = 1; i <= n; ++i)                 // (a learning step looks count steps back in the ring: never before step 0)
+        if (head[i] < 0 || head[i] > head[0]) return cls_refuse(h, "htm_classifiers_import: need 0 <= count <= total in stream " + std::to_string(i - 1), HTM_ERR_ARGUMENT);
+    HIPCHK(h, hipSetDevice(clf->device));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    HIPCHK(h, hipMemcpy(clf->d.count, head.data() + 1, n * 8, hipMemcpyHostToDevice));
+    HIPCHK(h, hipMemcpy(clf->d.ring, (const char *)host_state + 8 + n * 8, n * clf->ring_bytes, hipMemcpyHostToDevice));
+    clf->total = head[0];
+    return HTM_OK;
+}
+
+// ------------------------------------------------------------------------------------------
 // Live ticks (htm_live.h): the group's staging and result blocks, allocated by the first live call
-static int live_alloc(htm_group *g) {
+static int live_alloc(htm_group *g, size_t cls_need = 0) {
     htm_group::Live &lv = g->live;
-    if (lv.vote_tab) return 0;
+    if (lv.vote_tab && cls_need <= lv.cls_cap) return 0;
     const Dev &d = g->m[0]->d;
     const size_t n = (size_t)g->n;
-    lv.off_flags = n * (size_t)d.W * 4;             // (W is a multiple of 4 words: the flags and the values stay 8-byte aligned)
-    lv.off_values = (lv.off_flags + n * 4 + 7) & ~(size_t)7;
-    lv.stage_bytes = lv.off_values + n * HTM_SCALAR_MAX_FIELDS * sizeof(double);
-    lv.off_rows = n * sizeof(double);
+    if (!lv.vote_tab) {
+        lv.off_flags = n * (size_t)d.W * 4;             // (W is a multiple of 4 words: the flags and the values stay 8-byte aligned)
+        lv.off_values = (lv.off_flags + n * 4 + 7) & ~(size_t)7;
+        lv.stage_bytes = lv.off_values + n * HTM_SCALAR_MAX_FIELDS * sizeof(double) + n * sizeof(int32_t);    // (... and a classified tick's targets)
+        if (!lv.h_stage && hipHostMalloc((void **)&lv.h_stage, lv.stage_bytes, hipHostMallocDefault) != hipSuccess) { lv.h_stage = nullptr; g->err = "live tick: hipHostMalloc failed"; return HTM_ERR_HIP; }
+        memset(lv.h_stage, 0, lv.stage_bytes);          // (the words of a staged row beyond ceil(input_dim / 32) stay zero)
+        if (!lv.d_stage && galloc(g, &lv.d_stage, lv.stage_bytes)) return HTM_ERR_HIP;
+        if (!lv.d_recs && galloc(g, &lv.d_recs, n)) return HTM_ERR_HIP;
+        if (!lv.bank_tab && galloc(g, (uint32_t ***)&lv.bank_tab, n)) return HTM_ERR_HIP;
+        if (!lv.rec_args && galloc(g, &lv.rec_args, n)) return HTM_ERR_HIP;
+        std::vector<const uint32_t *> banks(n);
+        std::vector<GrpRecArgs> recs(n);
+        for (size_t i = 0; i < n; ++i) {
+            banks[i] = (const uint32_t *)lv.d_stage + i * (size_t)d.W;
+            recs[i] = GrpRecArgs{lv.d_recs + i, nullptr, nullptr};
+        }
+        GHIPCHK(g, hipMemset(lv.d_stage, 0, lv.stage_bytes));
+        GHIPCHK(g, hipMemcpy((void *)lv.bank_tab, banks.data(), n * sizeof(uint32_t *), hipMemcpyHostToDevice));
+        GHIPCHK(g, hipMemcpy(lv.rec_args, recs.data(), n * sizeof(GrpRecArgs), hipMemcpyHostToDevice));
+    } else {
+        // a classified tick that needs more room in front of the likelihoods: the result block anew (nothing enqueued reads the old one
+        // behind the wait; the vote table keeps its address, which is all the tick's graphs hold)
+        GHIPCHK(g, hipStreamSynchronize(g->stream));
+        hipHostFree(lv.h_out);
+        g->allocs.erase(std::remove(g->allocs.begin(), g->allocs.end(), (void *)lv.d_out), g->allocs.end());
+        hipFree(lv.d_out);
+        lv.h_out = lv.d_out = nullptr;
+    }
+    lv.cls_cap = (cls_need + 7) & ~(size_t)7;
+    lv.off_lik = lv.cls_cap;
+    lv.off_rows = lv.off_lik + n * sizeof(double);
     lv.off_pairs = lv.off_rows + n * sizeof(htm_live_row);
     lv.off_votes = lv.off_pairs + n * HTM_SCALAR_MAX_FIELDS * 2 * sizeof(int32_t);
     lv.out_bytes = lv.off_votes + n * (size_t)d.I * sizeof(int32_t);
-    if (!lv.h_stage && hipHostMalloc((void **)&lv.h_stage, lv.stage_bytes, hipHostMallocDefault) != hipSuccess) { lv.h_stage = nullptr; g->err = "live tick: hipHostMalloc failed"; return HTM_ERR_HIP; }
     if (!lv.h_out && hipHostMalloc((void **)&lv.h_out, lv.out_bytes, hipHostMallocDefault) != hipSuccess) { lv.h_out = nullptr; g->err = "live tick: hipHostMalloc failed"; return HTM_ERR_HIP; }
-    memset(lv.h_stage, 0, lv.stage_bytes);          // (the words of a staged row beyond ceil(input_dim / 32) stay zero)
     memset(lv.h_out, 0, lv.out_bytes);
-    if (!lv.d_stage && galloc(g, &lv.d_stage, lv.stage_bytes)) return HTM_ERR_HIP;
     if (!lv.d_out && galloc(g, &lv.d_out, lv.out_bytes)) return HTM_ERR_HIP;
-    if (!lv.d_recs && galloc(g, &lv.d_recs, n)) return HTM_ERR_HIP;
-    if (!lv.bank_tab && galloc(g, (uint32_t ***)&lv.bank_tab, n)) return HTM_ERR_HIP;
-    if (!lv.rec_args && galloc(g, &lv.rec_args, n)) return HTM_ERR_HIP;
-    int32_t **vote_tab = nullptr;
-    if (galloc(g, &vote_tab, n)) return HTM_ERR_HIP;
-    std::vector<const uint32_t *> banks(n);
-    std::vector<GrpRecArgs> recs(n);
+    int32_t **vote_tab = lv.vote_tab;
+    if (!vote_tab && galloc(g, &vote_tab, n)) return HTM_ERR_HIP;
     std::vector<int32_t *> votes(n);
-    for (size_t i = 0; i < n; ++i) {
-        banks[i] = (const uint32_t *)lv.d_stage + i * (size_t)d.W;
-        recs[i] = GrpRecArgs{lv.d_recs + i, nullptr, nullptr};
-        votes[i] = (int32_t *)(lv.d_out + lv.off_votes) + i * (size_t)d.I;
-    }
-    GHIPCHK(g, hipMemset(lv.d_stage, 0, lv.stage_bytes));
+    for (size_t i = 0; i < n; ++i) votes[i] = (int32_t *)(lv.d_out + lv.off_votes) + i * (size_t)d.I;
     GHIPCHK(g, hipMemset(lv.d_out, 0, lv.out_bytes));
-    GHIPCHK(g, hipMemcpy((void *)lv.bank_tab, banks.data(), n * sizeof(uint32_t *), hipMemcpyHostToDevice));
-    GHIPCHK(g, hipMemcpy(lv.rec_args, recs.data(), n * sizeof(GrpRecArgs), hipMemcpyHostToDevice));
     GHIPCHK(g, hipMemcpy(vote_tab, votes.data(), n * sizeof(int32_t *), hipMemcpyHostToDevice));
     lv.vote_tab = vote_tab;
+    return 0;
+}
+
+// the rows a classified tick captures its members' patterns into, and the table of their descriptors, allocated by the first such tick
+static int live_alloc_capture(htm_group *g) {
+    htm_group::Live &lv = g->live;
+    if (lv.d_caps) return 0;
+    const Dev &d = g->m[0]->d;
+    const size_t n = (size_t)g->n, per = (size_t)d.k * d.WPC;
+    if (!lv.cap_rows && galloc(g, &lv.cap_rows, n * per)) return HTM_ERR_HIP;
+    ClsCapDev *caps = nullptr;
+    if (galloc(g, &caps, n)) return HTM_ERR_HIP;
+    std::vector<ClsCapDev> rows(n);
+    for (size_t i = 0; i < n; ++i) rows[i].rows = lv.cap_rows + i * per;
+    GHIPCHK(g, hipMemcpy(caps, rows.data(), n * sizeof(ClsCapDev), hipMemcpyHostToDevice));
+    lv.d_caps = caps;
     return 0;
 }
 
@@ -4461,9 +4767,33 @@ static int live_alloc(htm_group *g) {
 // one wait, copies its results out and notes its segment count (what hand_back_segments leaves for the next call's scan).
 static int live_tick(htm_group *g, const double *values, const htm_scalar_field *fields, int32_t n_fields, const uint32_t *packed_inputs,
                      const uint8_t *resets, int32_t learning, int32_t use_graph, htm_live_row *rows, int32_t *decoded, int32_t *votes,
-                     htm_likelihood *lk, double *likelihood) {
+                     htm_likelihood *lk, double *likelihood, htm_classifier *clf = nullptr, const int32_t *targets = nullptr, int32_t cls_learn = 0,
+                     int32_t *best = nullptr, int32_t *dist = nullptr) {
     if (!g) return HTM_ERR_ARGUMENT;
     if (!rows) { g->err = "htm_live_tick: null rows"; return HTM_ERR_ARGUMENT; }
+    // a classified tick (htm_classifiers_tick): every refusal before anything is enqueued
+    if ((clf != nullptr) != (best != nullptr) || (clf != nullptr) != (targets != nullptr) || (dist && !clf)) {
+        g->err = "htm_classifiers_tick: clf, targets and best go together (dist only with them)";
+        return HTM_ERR_ARGUMENT;
+    }
+    if (clf) {
+        const Dev &d0 = g->m[0]->d;
+        const ClsDev &c = clf->d;
+        if (clf->n != g->n || clf->device != g->device) {
+            g->err = "htm_classifiers_tick: the classifier has " + std::to_string(clf->n) + " streams on device " + std::to_string(clf->device) + ", the group " +
+                     std::to_string(g->n) + " members on device " + std::to_string(g->device);
+            return HTM_ERR_ARGUMENT;
+        }
+        if (c.n_cols != d0.C || c.K != d0.K || c.max_pairs < d0.k * d0.WPC) {
+            g->err = "htm_classifiers_tick: the classifier was made for " + std::to_string(c.n_cols) + " columns of " + std::to_string(c.K) + " cells and patterns of " +
+                     std::to_string(c.max_pairs) + " pairs, the members have " + std::to_string(d0.C) + " x " + std::to_string(d0.K) + " and " +
+                     std::to_string(d0.k * d0.WPC) + " pairs a step";
+            return HTM_ERR_ARGUMENT;
+        }
+        if (cls_learn && clf->shares) { g->err = "htm_classifiers_tick: the streams read another object's weights: learn must be 0"; return HTM_ERR_STATE; }
+        for (int i = 0; i < g->n; ++i)
+            if (int rc = pin_refuse(g->m[i], "htm_classifiers_tick")) { g->err = "member " + std::to_string(i) + ": " + g->m[i]->err; return rc; }
+    }
     if ((lk != nullptr) != (likelihood != nullptr)) { g->err = "htm_likelihood_tick: lk and likelihood go together"; return HTM_ERR_ARGUMENT; }
     if (lk && (lk->n != g->n || lk->device != g->device)) {
         g->err = "htm_likelihood_tick: the likelihood object has " + std::to_string(lk->n) + " streams on device " + std::to_string(lk->device) +
@@ -4486,8 +4816,16 @@ static int live_tick(htm_group *g, const double *values, const htm_scalar_field 
     GHIPCHK(g, hipSetDevice(g->device));
     rc = group_join(g);
     if (rc) return rc;
-    rc = live_alloc(g);
+    // (the classification's bytes in the result block: best, then dist)
+    const size_t best_bytes = clf ? (size_t)g->n * clf->d.H * 2 * sizeof(int32_t) : 0, dist_bytes = dist ? (size_t)g->n * clf->d.H * clf->d.B * sizeof(int32_t) : 0;
+    const size_t cls_bytes = (best_bytes + dist_bytes + 7) & ~(size_t)7;
+    rc = live_alloc(g, cls_bytes);
     if (rc) return rc;
+    if (clf) {
+        rc = live_alloc_capture(g);
+        if (rc) return rc;
+        if (gcls_prepare(clf, h0, cls_learn, 1)) { g->err = h0->err; return HTM_ERR_HIP; }
+    }
     htm_group::Live &lv = g->live;
     const Dev &d = h0->d;
     const hipStream_t s = g->stream;
@@ -4512,6 +4850,12 @@ static int live_tick(htm_group *g, const double *values, const htm_scalar_field 
         c0 = 0;
         c1 = lv.off_flags + (size_t)B * 4;
     }
+    // a classified tick's targets ride behind them in the same copy (a tick of packed rows: where the values would lie)
+    const size_t off_targets = values ? c1 : lv.off_values;
+    if (clf) {
+        memcpy(lv.h_stage + off_targets, targets, (size_t)B * sizeof(int32_t));
+        c1 = off_targets + (size_t)B * sizeof(int32_t);
+    }
     GHIPCHK(g, hipMemcpyAsync(lv.d_stage + c0, lv.h_stage + c0, c1 - c0, hipMemcpyHostToDevice, s));
     // resets first: the record's begin launch then counts the cleared prediction words (predicted_columns_before = 0)
     if (resetting) LAUNCH_ON(h0, s, 0, "live:reset", klive_reset, dim3(reset_blocks(d), B), 256, g->d_tab, (const int32_t *)(lv.d_stage + lv.off_flags));
@@ -4526,19 +4870,19 @@ static int live_tick(htm_group *g, const double *values, const htm_scalar_field 
                   (uint32_t *)lv.d_stage, 0);
     const bool decoding = decoded || votes;
     if (decoding) LAUNCH_ON(h0, s, 0, "group:predicted_input", kgrp_pin_begin, dim3(pin_begin_blocks(1, d.I), B), 256, g->d_tab, p ^ 1, g->d_pins, lv.vote_tab, 1);
-    const RunModes modes{true, false, decoding, false};
+    const RunModes modes{true, false, decoding, false, clf != nullptr};       // (a classified tick captures its step's patterns)
     GroupForm f = group_form(g);
     f.shared = g->shared && !learning;
     if (run_schedule(h0, 1, use_graph).graph) {
         const GroupGraphKey key{p, modes, learning, f.fuse, f.large, f.shared, f.spec, 1, lv.bank_tab, 1};
         const hipGraphExec_t exec = cached_graph(g->graphs, key, s, g->err, [&] {
-            group_enqueue_step(g, modes, lv.bank_tab, 1, learning, p, f);
+            group_enqueue_step(g, modes, lv.bank_tab, 1, learning, p, f, lv.d_caps);
             return 0;
         });
         if (!exec) return HTM_ERR_HIP;
         GHIPCHK(g, hipGraphLaunch(exec, s));
     } else {
-        group_enqueue_step(g, modes, lv.bank_tab, 1, learning, p, f);
+        group_enqueue_step(g, modes, lv.bank_tab, 1, learning, p, f, lv.d_caps);
     }
     if (mixed)
         LAUNCH_ON(h0, s, 0, "live:finish", kenc_finish, dim3(std::max(n_dec, 1), B), SCALAR_THREADS, g->d_tab, p, ftab, n_dec,
@@ -4549,7 +4893,27 @@ static int live_tick(htm_group *g, const double *values, const htm_scalar_field 
                   (const int32_t *)(lv.d_out + lv.off_votes), (const htm_step_record *)lv.d_recs, (htm_live_row *)(lv.d_out + lv.off_rows),
                   (int32_t *)(lv.d_out + lv.off_pairs));
     // a scored tick: every member's stream of the likelihood object takes the step's record, behind the finish launch
-    if (lk) LAUNCH_ON(h0, s, 0, "live:likelihood", klik_tick, dim3(1, B), HTM_LIKELIHOOD_THREADS, lk->d, (const htm_step_record *)lv.d_recs, (double *)lv.d_out);
+    if (lk) LAUNCH_ON(h0, s, 0, "live:likelihood", klik_tick, dim3(1, B), HTM_LIKELIHOOD_THREADS, lk->d, (const htm_step_record *)lv.d_recs, (double *)(lv.d_out + lv.off_lik));
+    // a classified tick: every member's stream of the bank takes the step's captured pattern -- sum + apply when it learns, else the
+    // frozen launch over one step; a member's reset flag (bit 0 of its word) also empties its stream's history
+    const size_t cls_begin = lv.off_lik - cls_bytes;
+    if (clf) {
+        GClsStep gs;
+        memset(&gs, 0, sizeof(gs));
+        gs.pairs = lv.cap_rows;
+        gs.pairs_stride = (int64_t)d.k * d.WPC;
+        gs.targets = (const int32_t *)(lv.d_stage + off_targets);
+        gs.targets_stride = 1;
+        gs.reset_bits = (const uint32_t *)(lv.d_stage + lv.off_flags);
+        gs.resets_stride = 1;
+        gs.pairs_per_step = d.k * d.WPC;
+        gs.n_targets = 1;
+        gs.first_step = 0;
+        gs.n_steps = 1;
+        gs.best = (int32_t *)(lv.d_out + cls_begin);
+        gs.dist = dist ? (int32_t *)(lv.d_out + cls_begin + best_bytes) : nullptr;
+        if (gcls_enqueue(clf, h0, s, gs, cls_learn)) { g->err = h0->err; return HTM_ERR_HIP; }
+    }
     for (htm_handle *h : g->m) {
         h->step_host += 1;
         h->window_known = true;
@@ -4559,11 +4923,13 @@ static int live_tick(htm_group *g, const double *values, const htm_scalar_field 
     if (rc) return rc;
     // the one copy out and the one wait
     const size_t pair_bytes = (size_t)B * n_dec * 2 * sizeof(int32_t), vote_bytes = (size_t)B * d.I * sizeof(int32_t);
-    const size_t out_end = votes ? lv.off_votes + vote_bytes : lv.off_pairs + pair_bytes, out_begin = lk ? 0 : lv.off_rows;
+    const size_t out_end = votes ? lv.off_votes + vote_bytes : lv.off_pairs + pair_bytes, out_begin = clf ? cls_begin : lk ? lv.off_lik : lv.off_rows;
     GHIPCHK(g, hipMemcpyAsync(lv.h_out + out_begin, lv.d_out + out_begin, out_end - out_begin, hipMemcpyDeviceToHost, s));
     GHIPCHK(g, hipStreamSynchronize(s));
     memcpy(rows, lv.h_out + lv.off_rows, (size_t)B * sizeof(htm_live_row));
-    if (lk) memcpy(likelihood, lv.h_out, (size_t)B * sizeof(double));
+    if (lk) memcpy(likelihood, lv.h_out + lv.off_lik, (size_t)B * sizeof(double));
+    if (clf) memcpy(best, lv.h_out + cls_begin, best_bytes);
+    if (dist) memcpy(dist, lv.h_out + cls_begin + best_bytes, dist_bytes);
     if (decoded) memcpy(decoded, lv.h_out + lv.off_pairs, pair_bytes);
     if (votes) memcpy(votes, lv.h_out + lv.off_votes, vote_bytes);
     for (int i = 0; i < B; ++i) {                   // (the segment hint each member's next call -- group or solo -- starts from)
@@ -4583,6 +4949,15 @@ extern "C" int htm_likelihood_tick(htm_group *g, const double *values, const htm
                                    const uint8_t *resets, int32_t learning, int32_t use_graph, htm_live_row *rows, int32_t *decoded, int32_t *votes,
                                    htm_likelihood *lk, double *likelihood) {
     return live_tick(g, values, fields, n_fields, packed_inputs, resets, learning, use_graph, rows, decoded, votes, lk, likelihood);
+}
+
+// htm_likelihood_tick with a bank of classifiers riding on it (lk and likelihood may be NULL: an unscored, classified tick)
+extern "C" int htm_classifiers_tick(htm_group *g, const double *values, const htm_scalar_field *fields, int32_t n_fields, const uint32_t *packed_inputs,
+                                    const uint8_t *resets, int32_t learning, int32_t use_graph, htm_live_row *rows, int32_t *decoded, int32_t *votes,
+                                    htm_likelihood *lk, double *likelihood, htm_classifier *clf, const int32_t *targets, int32_t learn, int32_t *best,
+                                    int32_t *dist) {
+    return live_tick(g, values, fields, n_fields, packed_inputs, resets, learning, use_graph, rows, decoded, votes, lk, likelihood, clf, targets, learn ? 1 : 0,
+                     best, dist);
 }
 
 // htm_reset of the flagged members in one launch.  The flags are the call's own (pageable) words: the copy has read them when

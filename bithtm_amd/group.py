@@ -22,6 +22,7 @@ from . import _lib as L
 from .engine import CapacityError, HtmError, pack_bits
 from .networks import (RECORD_COUNTERS, HierarchicalTemporalMemory, InferenceView, RunRecord, _BatchedCall, _batches, _cached_bank, _check_encoder,
                        _encode_params, _no_classifier, _noise_ring, _record_fields, _with_counters, noise_threshold, retire_states)
+from .sdr_classifier import SDRClassifierBank, model_shape
 
 
 class SharedStream:
@@ -51,16 +52,21 @@ class GroupTick(RunRecord):
       predicted_bucket, predicted_score int32 [B, F], predicted_value float64 [B, F]   with an encoder: the votes of the state
                                     the step leaves, decoded per field on the device; NaN where nothing is predicted
       predicted_input   int32 [B, input_dim]   with predicted_input=True: those votes themselves
-      anomaly_likelihood float64 [B]  with likelihood=: each member's anomaly likelihood of this step (log_likelihood: its log scale)"""
+      anomaly_likelihood float64 [B]  with likelihood=: each member's anomaly likelihood of this step (log_likelihood: its log scale)
+      classified_bucket int32 [B, H], classified_probability float64 [B, H]   with classifier=: per horizon of the SDRClassifierBank
+                                    each member's most probable bucket and its probability; classified_value float64 [B, H] for a
+                                    bank of an encoder field; class_distribution int32 [B, H, buckets] with class_distribution=True"""
 
-    def __init__(self, rows, pairs=None, votes=None, encoder=None, anomaly_likelihood=None):
+    def __init__(self, rows, pairs=None, votes=None, encoder=None, anomaly_likelihood=None, classified=None, class_distribution=None,
+                 classified_field=None):
         counters = np.stack([rows[name] for name in RECORD_COUNTERS], axis=1)
         bucket = score = value = None
         if pairs is not None:
             bucket, score = np.ascontiguousarray(pairs[:, :, 0]), np.ascontiguousarray(pairs[:, :, 1])
             value = encoder.value_of(bucket)
         super().__init__(rows["step_index"], counters=counters, predicted_input=votes, predicted_bucket=bucket, predicted_score=score,
-                         predicted_value=value, anomaly_likelihood=anomaly_likelihood)
+                         predicted_value=value, anomaly_likelihood=anomaly_likelihood, classified=classified,
+                         class_distribution=class_distribution, classified_field=classified_field)
         self.capacity_error = np.ascontiguousarray(rows["capacity_error"], dtype=np.int32)
 
 
@@ -228,11 +234,27 @@ class ModelGroup:
         ptrs = [_cached_bank(m, m.engine, x, encoder=encoder) for m, x in zip(self.models, inputs)]
         return (C.c_void_p * len(ptrs))(*ptrs)
 
+    def _bank_targets(self, bank, targets, inputs, encoder, what):
+        """run() / tick() with classifier=: the members' target buckets -> int32 [B, rows] (tick: rows = 1).  `inputs`: the members'
+        rows [B, rows, ...]; None `targets` with an encoder and a bank made with field=: encoder.bucket of the field, on the host."""
+        B = len(self.models)
+        if targets is None:
+            if encoder is None or bank.field is None:
+                raise ValueError(f"{what}(classifier=): give targets=, or encoder= and a bank made with field=")
+            where = [j for j, f in enumerate(encoder.fields) if f is bank.field]
+            if not where:
+                raise ValueError(f"{what}(classifier=): the bank's field is not one of the encoder's fields")
+            targets = np.stack([encoder.bucket(inputs[i])[:, where[0]] for i in range(B)])
+        targets = np.asarray(targets)
+        if targets.ndim != 2 or targets.shape != (B, inputs.shape[1]):
+            raise ValueError(f"targets: int [{B}, {inputs.shape[1]}], one bucket per member and row, got {list(targets.shape)}")
+        return bank.check_targets(targets)
+
     # run(noise=): steps per fill of the members' noise rings (see HierarchicalTemporalMemory.noise_chunk)
     noise_chunk = 1024
 
     def run(self, inputs, steps, learning=None, use_graph=True, record=None, resets=None, noise=0.0, noise_seed=None, encoder=None,
-            likelihood=None, classifier=None):
+            likelihood=None, classifier=None, targets=None, classifier_learning=None):
         """`steps` timesteps of every member, member i over the rows of inputs[i] (bool [B, n_inputs, input_dim]), cycled, as
         its own run(inputs[i], steps) would.  Returns None, or (`record`: as run(record=)) one RunRecord per member.
         learning=None: True, or False in a group with inference views (which refuses True).
@@ -243,10 +265,33 @@ class ModelGroup:
         values, encoded on the device into its bank, and `record` may name "predicted_value".
         `likelihood`: an AnomalyLikelihood of B streams -- the call records the counters (as record=True), behind each batch ONE
         htm_likelihood_update runs over the members' record buffers (a table of B pointers, never a launch per member) before the
-        read-back, and member i's RunRecord.anomaly_likelihood is stream i's."""
-        _no_classifier(classifier, "ModelGroup.run()")
+        read-back, and member i's RunRecord.anomaly_likelihood is stream i's.
+        `classifier`: an SDRClassifierBank of B streams (a one-stream SDRClassifier is refused) -- the call records the counters,
+        every step leaves every member's active-cell words on the device (htm_set_group_run_active_cells: one small launch per
+        step for all members, set for this call only), and behind each batch ONE htm_classifiers_update runs over the members'
+        patterns before the read-back, never a launch sequence per member.  `targets`: int [B, n_inputs], the bucket of each
+        member's rows (-1: missing), uploaded once; None with `encoder`: the bucket of the bank's field among the encoder's.  With
+        `noise`, targets index the row of `inputs`.  `classifier_learning`: None follows `learning`.  Member i's RunRecord gains
+        classified_bucket, _probability, _value and (with "class_distribution" named in `record`) class_distribution, as
+        run(classifier=) of the member alone with stream i as its classifier would give them."""
+        bank = classifier if isinstance(classifier, SDRClassifierBank) else None
+        if bank is None:
+            _no_classifier(classifier, "ModelGroup.run()")
         learning = self._learning(learning)
         B = len(self.models)
+        cls_learn = distribution = False
+        if bank is not None:
+            if bank.streams != B:
+                raise ValueError(f"run(classifier=): an SDRClassifierBank of {B} streams, got {bank.streams}")
+            cls_learn = bool(learning if classifier_learning is None else classifier_learning)
+            bank._no_shared_learning(cls_learn)
+            names = () if record is None or record is True else ((record,) if isinstance(record, str) else tuple(record))
+            distribution = "class_distribution" in names
+            if distribution:
+                record = tuple(f for f in names if f != "class_distribution") or None
+            record = _with_counters(record)
+        elif targets is not None or classifier_learning is not None:
+            raise ValueError("run(): targets= and classifier_learning= go with classifier=")
         if likelihood is not None:
             if likelihood.streams != B:
                 raise ValueError(f"run(likelihood=): an AnomalyLikelihood of {B} streams, got {likelihood.streams}")
@@ -273,11 +318,16 @@ class ModelGroup:
             inputs = np.ascontiguousarray(inputs, dtype=np.float64)
             if inputs.ndim != 3 or inputs.shape[0] != B or inputs.shape[1] < 1 or inputs.shape[2] != len(encoder):
                 raise ValueError(f"inputs: float64 values [{B}, n_inputs, {len(encoder)}], got {inputs.shape}")
+        host_targets = None
+        if bank is not None:
+            bank._set_shape(*model_shape(e0))
+            host_targets = self._bank_targets(bank, targets, inputs, encoder, "run")
         for m in self.models:
             retire_states(m.engine)
         self._current()
         k = self.models[0].active_columns
-        call = _BatchedCall([m.temporal_memory for m in self.models], fields, encoder, likelihood is not None)
+        call = _BatchedCall([m.temporal_memory for m in self.models], fields, encoder, likelihood is not None, bank)
+        device_targets = None
 
         def pools():        # cut into batches the smallest free-segment budget of any member lasts, with a look at the pools between them
             while self._grow(2 * k, True):
@@ -304,14 +354,33 @@ class ModelGroup:
                             "htm_group_run")
             else:
                 recs, buffers = self._records(fields, n, encoder)
+                if bank is not None:
+                    # every member's rows of this batch in one buffer [B][n][pairs]; the targets by the row of `inputs` a step reads:
+                    # member i's rolled by its distance from member 0's step, so that one first_step serves all members
+                    e0, rows_in, per = self.models[0].engine, inputs.shape[1], bank.shape[2]
+                    cells = bank.pairs_buffer(e0, n)
+                    cell_rows = [cells + i * n * per * 8 for i in range(B)]
+                    if device_targets is None:
+                        rolled = np.stack([np.roll(t, -((m.engine.steps - e0.steps) % rows_in)) for t, m in zip(host_targets, self.models)])
+                        device_targets = bank.upload_targets(e0, rolled)
+                    self._check(self.lib.htm_set_group_run_active_cells(self._g, (C.c_void_p * B)(*cell_rows)), "htm_set_group_run_active_cells")
                 try:
                     self._check(self.lib.htm_group_run(self._g, banks, n_inputs, n, int(bool(learning)), int(bool(use_graph)), recs),
                                 "htm_group_run")
                 finally:
                     self._unset_votes()
+                    if bank is not None:
+                        self.lib.htm_set_group_run_active_cells(self._g, None)
                 if likelihood is not None:          # (on the group's stream -- the first member's -- behind the run, before the wait)
                     likelihood.enqueue(self.models[0].engine, [b["counters"] for b in buffers], n)
+                if bank is not None:                # (likewise: ONE update over every member's patterns)
+                    bank.enqueue(e0, cell_rows, per, n, [device_targets + i * rows_in * 4 for i in range(B)], rows_in, e0.steps % rows_in, None, cls_learn,
+                                 distribution)
                 parts = self._read_records(fields, n, buffers, encoder)
+                if bank is not None:
+                    best, dist = bank.read(e0, n, distribution)
+                    for i, part in enumerate(parts):
+                        part["classified"], part["class_distribution"] = best[i].copy(), (dist[i].copy() if dist is not None else None)
                 if likelihood is not None:
                     for part, row in zip(parts, likelihood.read(self.models[0].engine, n)):
                         part["anomaly_likelihood"] = row
@@ -450,7 +519,8 @@ class ModelGroup:
                 m.temporal_memory._last_ref = None
                 m.temporal_memory._was_reset = True
 
-    def tick(self, values, encoder=None, resets=None, learning=None, predicted_input=False, use_graph=True, likelihood=None, classifier=None):
+    def tick(self, values, encoder=None, resets=None, learning=None, predicted_input=False, use_graph=True, likelihood=None, classifier=None,
+             targets=None, classifier_learning=None, class_distribution=False):
         """One live timestep of every member in one call whose copies, launches and waits do not depend on B: member i steps on
         values[i] -- float64 [B, F] with `encoder` (a ScalarEncoder; NaN: missing), encoded on the device, else bool
         [B, input_dim] as process() takes it -- after a sequence reset where resets[i] (bool [B], or None).  Returns a GroupTick:
@@ -460,11 +530,27 @@ class ModelGroup:
         happened; the exception's `.tick` is the finished GroupTick (the other members' results stand).
         learning=None: True, or False in a group with inference views (which refuses True).
         `likelihood`: an AnomalyLikelihood of B streams -- the tick's records are the streams' next step (htm_likelihood_tick: one
-        launch more, B doubles more in the copy out) and GroupTick.anomaly_likelihood holds the B values."""
-        _no_classifier(classifier, "ModelGroup.tick()")
+        launch more, B doubles more in the copy out) and GroupTick.anomaly_likelihood holds the B values.
+        `classifier`: an SDRClassifierBank of B streams (a one-stream SDRClassifier is refused) -- the tick's patterns are the
+        streams' next step (htm_classifiers_tick: three launches more when the bank learns, two when it is frozen, whatever B is;
+        still one copy in, one copy out and one wait).  `targets`: int [B], each member's bucket of this tick (-1: missing); None
+        with `encoder` and a bank made with field=: the bucket of this tick's value (NaN: missing).  `classifier_learning`: None
+        follows `learning`.  A member's reset flag also empties its stream's history.  GroupTick.classified_bucket, _probability,
+        _value hold the predictions, with class_distribution=True GroupTick.class_distribution all probabilities."""
+        bank = classifier if isinstance(classifier, SDRClassifierBank) else None
+        if bank is None:
+            _no_classifier(classifier, "ModelGroup.tick()")
         learning = self._learning(learning)
         B = len(self.models)
         e0 = self.models[0].engine
+        cls_learn = False
+        if bank is not None:
+            if bank.streams != B:
+                raise ValueError(f"tick(classifier=): an SDRClassifierBank of {B} streams, got {bank.streams}")
+            cls_learn = bool(learning if classifier_learning is None else classifier_learning)
+            bank._no_shared_learning(cls_learn)
+        elif targets is not None or classifier_learning is not None or class_distribution:
+            raise ValueError("tick(): targets=, classifier_learning= and class_distribution= go with classifier=")
         if likelihood is not None and likelihood.streams != B:
             raise ValueError(f"tick(likelihood=): an AnomalyLikelihood of {B} streams, got {likelihood.streams}")
         _check_encoder(encoder, None, e0.input_dim, e0.column_dim)
@@ -477,12 +563,24 @@ class ModelGroup:
             if X.shape != (B, len(encoder)):
                 raise ValueError(f"values: float64 [{B}, {len(encoder)}], got {X.shape}")
         mask = self._member_mask(resets, "resets")
+        host_targets = None
+        if bank is not None:
+            bank._set_shape(*model_shape(e0))
+            host_targets = np.ascontiguousarray(self._bank_targets(bank, None if targets is None else np.asarray(targets)[:, None]
+                                                                   if np.ndim(targets) == 1 else targets, X[:, None], encoder, "tick")[:, 0])
         for m in self.models:
             retire_states(m.engine)
         self._current()
         if self._auto_grow:
             self._grow(self.models[0].active_columns, False)
         flags = self._due_resets(mask) if mask is not None and mask.any() else None
+        e0 = self.models[0].engine
+        if bank is not None:
+            bank._bind(e0)
+            if mask is not None:                    # (a flagged member that has not stepped yet gets no device-side reset: its stream's history still goes)
+                fresh = np.array([bool(mask[i]) and m.engine.steps == 0 for i, m in enumerate(self.models)])
+                if fresh.any():
+                    bank.reset(fresh)
         rows = np.zeros(B, dtype=L.HtmLiveRow)
         pairs = votes = None
         if encoder is None:
@@ -497,8 +595,19 @@ class ModelGroup:
 
         def ptr(a):
             return None if a is None else a.ctypes.data_as(C.c_void_p)
-        scores = None
-        if likelihood is None:
+        scores = best = dist = None
+        if bank is not None:
+            H = len(bank.steps)
+            best = np.zeros((B, H, 2), dtype=np.int32)
+            dist = np.zeros((B, H, bank.buckets), dtype=np.int32) if class_distribution else None
+            lk = None
+            if likelihood is not None:
+                likelihood._bind(e0)
+                scores, lk = np.zeros(B, dtype=np.float64), likelihood._lk
+            self._check(self.lib.htm_classifiers_tick(self._g, *args, ptr(flags), int(bool(learning)), int(bool(use_graph)), ptr(rows), ptr(pairs),
+                                                      ptr(votes), lk, ptr(scores), bank._clf, ptr(host_targets), int(cls_learn), ptr(best), ptr(dist)),
+                        "htm_classifiers_tick")
+        elif likelihood is None:
             self._check(self.lib.htm_live_tick(self._g, *args, ptr(flags), int(bool(learning)), int(bool(use_graph)), ptr(rows), ptr(pairs),
                                                ptr(votes)), "htm_live_tick")
         else:
@@ -509,7 +618,7 @@ class ModelGroup:
         for m in self.models:
             m.engine.steps += 1
             m.temporal_memory._new_state(None)
-        tick = GroupTick(rows, pairs, votes, encoder, scores)
+        tick = GroupTick(rows, pairs, votes, encoder, scores, best, dist, bank.field if bank is not None else None)
         if tick.capacity_error.any():
             what = "; ".join(f"member {i}:" + "".join(" " + text for bit, text in _CAPACITY_FLAGS if flag & bit) + f" (flags {flag})"
                              for i, flag in enumerate(tick.capacity_error.tolist()) if flag)

@@ -875,6 +875,10 @@ class HierarchicalTemporalMemory:
         row's; a reset flag of a row also empties the classifier's history.  `classifier_learning`: None follows `learning`.
         RunRecord.classified_bucket, _probability, _value hold each step's prediction per horizon, and with "class_distribution"
         named in `record`, RunRecord.class_distribution all probabilities."""
+        if classifier is not None:
+            from .sdr_classifier import SDRClassifierBank
+            if isinstance(classifier, SDRClassifierBank):            # (many streams; this call has one)
+                _no_classifier(classifier, "run() with an SDRClassifierBank")
         eng = self._fused_engine("run()")
         cls = None
         if classifier is not None:
@@ -1419,7 +1423,8 @@ def _no_classifier(classifier, what):
     """The calls an SDRClassifier does not ride on: refused, never silently ignored."""
     if classifier is not None:
         raise ValueError(f"{what}: classifier= is not available here -- an SDRClassifier rides on HierarchicalTemporalMemory.run() and "
-                         "InferenceView.run(), or takes patterns through update_patterns()")
+                         "InferenceView.run(), or takes patterns through update_patterns(); ModelGroup.run() and tick() take an "
+                         "SDRClassifierBank of as many streams as the group has members")
 
 
 def _classifier_targets(classifier, targets, inputs, encoder):

@@ -19,12 +19,15 @@ from .classifier import EXP_TABLE, W_LIMIT, check_params, check_patterns
 from .engine import HtmError
 
 
-class SDRClassifier:
-    """The classifier of `buckets` buckets (or of an encoder field's: `field`, whose value_of also names the values) for the
-    horizons `steps` with learning rate `alpha`.  The shape of the patterns -- units = column_dim * cell_dim, cell_dim, and the pairs
-    a pattern has at most -- comes from the model of the first run(classifier=), or from `shape=(column_dim, cell_dim, max_pairs)`
-    for stand-alone use.  The object binds to a device lazily, as AnomalyLikelihood does; every update continues where the last one
-    ended, whichever door it came through."""
+class _DeviceClassifier:
+    """What a one-stream classifier and a bank of streams have in common: the parameters, the shape of the patterns, the lazy binding
+    to a device (as AnomalyLikelihood binds), the device object's life and the upload of a run's targets.  What depends on the number
+    of streams -- the shapes of targets, outputs and state -- is the subclasses': neither is an instance of the other."""
+
+    _create_name = None
+
+    def _create(self, engine, cfg, out):
+        raise NotImplementedError
 
     def __init__(self, buckets=None, field=None, steps=(1,), alpha=0.001, shape=None):
         if (buckets is None) == (field is None):
@@ -68,9 +71,9 @@ class SDRClassifier:
             cfg = L.HtmClassifierConfig(C.sizeof(L.HtmClassifierConfig), self.buckets, len(self.steps), self.alpha_q, self.units, self.shape[1],
                                         self.shape[2], (C.c_int32 * 8)(*self.steps))
             out = C.c_void_p()
-            rc = self.lib.htm_classifier_create(engine.h, C.byref(cfg), EXP_TABLE.ctypes.data_as(C.c_void_p), C.byref(out))
+            rc = self._create(engine, cfg, out)
             if rc != 0:
-                raise HtmError(f"htm_classifier_create failed ({rc}): {self.lib.htm_last_error(engine.h).decode()}")
+                raise HtmError(f"{self._create_name} failed ({rc}): {self.lib.htm_last_error(engine.h).decode()}")
             self._clf, self.device = out, engine.device
             self._last = weakref.ref(engine)
             if self._pending is not None:
@@ -117,7 +120,6 @@ class SDRClassifier:
         if rc < 0:
             raise HtmError(f"{what} failed ({rc}): {self.lib.htm_last_error(engine.h).decode()}")
 
-    # ---- the update behind captured steps (what run() calls; nothing here waits)
     def upload_targets(self, engine, targets):
         """int [n] -> the device address of the targets of a run's rows (kept until the next upload)."""
         self._bind(engine)
@@ -126,6 +128,20 @@ class SDRClassifier:
         engine._hip_check(self.lib.hipMemcpy(ptr, targets.ctypes.data_as(C.c_void_p), targets.nbytes, L.HIP_MEMCPY_HOST_TO_DEVICE), "hipMemcpy")
         return ptr
 
+
+class SDRClassifier(_DeviceClassifier):
+    """The classifier of `buckets` buckets (or of an encoder field's: `field`, whose value_of also names the values) for the
+    horizons `steps` with learning rate `alpha`.  The shape of the patterns -- units = column_dim * cell_dim, cell_dim, and the pairs
+    a pattern has at most -- comes from the model of the first run(classifier=), or from `shape=(column_dim, cell_dim, max_pairs)`
+    for stand-alone use.  The object binds to a device lazily, as AnomalyLikelihood does; every update continues where the last one
+    ended, whichever door it came through."""
+
+    _create_name = "htm_classifier_create"
+
+    def _create(self, engine, cfg, out):
+        return self.lib.htm_classifier_create(engine.h, C.byref(cfg), EXP_TABLE.ctypes.data_as(C.c_void_p), C.byref(out))
+
+    # ---- the update behind captured steps (what run() calls; nothing here waits)
     def pairs_buffer(self, engine, n):
         """The device address of a buffer for n steps' patterns of max_pairs pairs (kept)."""
         self._bind(engine)
@@ -275,6 +291,253 @@ class SDRClassifier:
             w = np.ascontiguousarray(state["weights"][h])
             self._check(engine, self.lib.htm_classifier_write_weights(self._clf, engine.h, h, 0, self.units, w.ctypes.data_as(C.c_void_p)),
                         "htm_classifier_write_weights")
+
+
+class SDRClassifierBank(_DeviceClassifier):
+    """`streams` independent SDRClassifier streams of one config in one device object (htm_classifiers_*): stream
+    i fed (patterns_i, targets_i, resets_i) equals an SDRClassifier fed the same, bit for bit, and every call steps all streams in
+    the launches of one -- two per step when learning, one per chunk of steps otherwise, whatever `streams` is.
+
+        bank = SDRClassifierBank(64, buckets=50, steps=(1, 5), shape=(2048, 32, 40))
+        best, dist = bank.update_patterns(index, words, targets)        # index, words [64, T, P], targets [64, T]
+        views = SDRClassifierBank.shared(clf, 4)                        # four frozen streams over clf's weights, read where they lie
+
+    Memory: streams x the one-stream object's, except shared(), which adds only rings, counts and accumulators."""
+
+    _create_name = "htm_classifiers_create"
+
+    def __init__(self, streams, buckets=None, field=None, steps=(1,), alpha=0.001, shape=None):
+        super().__init__(buckets=buckets, field=field, steps=steps, alpha=alpha, shape=shape)
+        self.streams = int(streams)
+        if not 1 <= self.streams <= 65535 // len(self.steps):
+            raise ValueError(f"SDRClassifierBank: streams must be in [1, 65535 // len(steps) = {65535 // len(self.steps)}], got {streams}")
+        self.source = None                      # shared(): the SDRClassifier whose weights the streams read
+
+    @classmethod
+    def shared(cls, clf, streams):
+        """A bank of `streams` frozen streams that read the weights of `clf`, a bound SDRClassifier: no copy -- what clf learns later
+        (through htm.run(classifier=clf), say) the next call here sees.  The bank keeps a reference to clf; its own state is the
+        streams' histories.  Learning through the bank is refused."""
+        if not isinstance(clf, SDRClassifier):
+            raise ValueError("SDRClassifierBank.shared(): clf is a one-stream SDRClassifier")
+        if clf._clf is None:
+            raise ValueError("SDRClassifierBank.shared(): clf is not bound to a device yet (use it with a model, or clf.bind(model))")
+        bank = cls.__new__(cls)
+        _DeviceClassifier.__init__(bank, buckets=clf.buckets, steps=clf.steps, shape=clf.shape)
+        bank.field, bank.alpha_q = clf.field, clf.alpha_q
+        bank.streams = int(streams)
+        if not 1 <= bank.streams <= 65535 // len(bank.steps):
+            raise ValueError(f"SDRClassifierBank: streams must be in [1, 65535 // len(steps) = {65535 // len(bank.steps)}], got {streams}")
+        bank.source = clf
+        bank._last = clf._last                  # (its calls go through the engine clf's last call came through, until a model brings its own)
+        return bank
+
+    def _create(self, engine, cfg, out):
+        share = None
+        if self.source is not None:
+            if self.source._clf is None or self.source.device != engine.device:
+                raise ValueError(f"the shared classifier lives on device {self.source.device}, the model on device {engine.device}")
+            share = self.source._clf
+        return self.lib.htm_classifiers_create(engine.h, C.byref(cfg), EXP_TABLE.ctypes.data_as(C.c_void_p), self.streams, share, C.byref(out))
+
+    def _bind(self, engine):
+        if self.source is not None:             # (what the owner's last engine enqueued on the weights is waited for first)
+            owner = self.source._last() if self.source._last is not None else None
+            if owner is not None and owner is not engine and getattr(owner, "h", None):
+                owner.sync()
+        return super()._bind(engine)
+
+    def _no_shared_learning(self, learning):
+        if learning and self.source is not None:
+            raise ValueError("SDRClassifierBank.shared(): the streams read one weight table -- learning is refused (the owner learns through its own calls)")
+
+    # ---- the update over device memory (nothing here waits)
+    def pairs_buffer(self, engine, n):
+        """The device address of a buffer for n steps' patterns of max_pairs pairs of every stream, [streams][n][max_pairs] (kept)."""
+        self._bind(engine)
+        return engine.kept_buffer(self._bufs, "pairs", 2 * self.streams * max(int(n), 1) * self.shape[2], spare=2)
+
+    def enqueue(self, engine, device_pairs, pairs_per_step, n, device_targets, n_targets, first_step, device_resets, learning, distribution=False):
+        """htm_classifiers_update over n steps of every stream: device_pairs, device_targets and device_resets (or None) are
+        sequences of `streams` device addresses -> nothing; read(engine, n, distribution) after the stream's wait gives the results."""
+        self._no_shared_learning(learning)
+        self._bind(engine)
+        n, H, S = int(n), len(self.steps), self.streams
+        best = engine.kept_buffer(self._bufs, "best", S * max(n, 1) * H * 2, spare=2)
+        dist = engine.kept_buffer(self._bufs, "dist", S * max(n, 1) * H * self.buckets, spare=2) if distribution else None
+        table = lambda a: (C.c_void_p * S)(*[int(x) for x in a])
+        self._check(engine, self.lib.htm_classifiers_update(self._clf, engine.h, table(device_pairs), int(pairs_per_step), n, table(device_targets), int(n_targets),
+                                                            int(first_step), table(device_resets) if device_resets is not None else None,
+                                                            int(bool(learning)), C.c_void_p(best), C.c_void_p(dist) if dist else None),
+                    "htm_classifiers_update")
+
+    def read(self, engine, n, distribution=False):
+        """(best int32 [streams, n, H, 2], dist int32 [streams, n, H, buckets] or None) of the last enqueue, after the stream's wait."""
+        n, H, S = int(n), len(self.steps), self.streams
+        best = engine.read_words(self._bufs["best"][0], S * n * H * 2, np.int32).reshape(S, n, H, 2)
+        dist = engine.read_words(self._bufs["dist"][0], S * n * H * self.buckets, np.int32).reshape(S, n, H, self.buckets) if distribution else None
+        return best, dist
+
+    def check_targets(self, targets):
+        """int [streams, n] -> int32: -1 (any negative value) is missing; ValueError for a bucket at or above `buckets`."""
+        t = np.asarray(targets)
+        if t.ndim != 2 or t.shape[0] != self.streams or t.dtype.kind not in "iu":
+            raise ValueError(f"targets: int [{self.streams}, n], got {t.dtype} {list(t.shape)}")
+        if t.size and int(t.max()) >= self.buckets:
+            raise ValueError(f"targets: bucket {int(t.max())} is at or above buckets = {self.buckets}")
+        return np.ascontiguousarray(np.where(t < 0, -1, t).astype(np.int32))
+
+    # ---- the stand-alone door
+    def update_patterns(self, index, words, targets, learning=True, resets=None, device=None, distribution=True):
+        """T further steps of every stream: index int [streams, T, n], words uint32 [streams, T, n], targets int [streams, T] (-1:
+        missing), resets bool [streams, T] or None, each stream's as SDRClassifier.update_patterns takes them -> (best int32
+        [streams, T, H, 2], dist int32 [streams, T, H, buckets] or None)."""
+        self._no_shared_learning(learning)
+        if self.shape is None:
+            raise RuntimeError("the classifier does not know the shape of its patterns yet: use it with a model, or give SDRClassifierBank(shape=)")
+        index, words = np.asarray(index), np.asarray(words)
+        S = self.streams
+        if index.ndim != 3 or index.shape[0] != S or words.shape != index.shape:
+            raise ValueError(f"patterns: index int [{S}, T, n] and words uint32 [{S}, T, n], got {list(index.shape)} and {list(words.shape)}")
+        checked = [check_patterns(index[i], words[i], self.units, self.shape[1]) for i in range(S)]
+        index, words = np.stack([c[0] for c in checked]), np.stack([c[1] for c in checked])
+        _, T, n = index.shape
+        if not 1 <= n <= self.shape[2]:
+            raise ValueError(f"patterns: 1 to max_pairs = {self.shape[2]} pairs per step, got {n}")
+        targets = self.check_targets(targets)
+        if targets.shape != (S, T):
+            raise ValueError(f"targets: int [{S}, {T}], got {list(targets.shape)}")
+        if resets is not None:
+            resets = np.asarray(resets, dtype=np.bool_)
+            if resets.shape != (S, T):
+                raise ValueError(f"resets: bool [{S}, {T}], got {list(resets.shape)}")
+        H = len(self.steps)
+        if T == 0:
+            return np.zeros((S, 0, H, 2), np.int32), (np.zeros((S, 0, H, self.buckets), np.int32) if distribution else None)
+        engine = self._engine(device)
+        pairs = np.empty((S, T, n, 2), dtype=np.int32)
+        pairs[..., 0], pairs[..., 1] = index, words.view(np.int32)
+        buf = engine.device_buffer(pairs.nbytes, pairs)
+        tbuf = engine.device_buffer(targets.nbytes, targets)
+        rbuf, rtab = None, None
+        try:
+            if resets is not None:
+                row = (T + 31) // 32 * 4
+                bits = np.zeros((S, row), dtype=np.uint8)
+                pb = np.packbits(resets, axis=1, bitorder="little")
+                bits[:, :pb.shape[1]] = pb
+                rbuf = engine.device_buffer(bits.nbytes, bits)
+                rtab = [rbuf + i * row for i in range(S)]
+            self.enqueue(engine, [buf + i * T * n * 8 for i in range(S)], n, T, [tbuf + i * T * 4 for i in range(S)], T, 0, rtab, learning, distribution)
+            engine.sync()
+            best, dist = self.read(engine, T, distribution)
+            return best.copy(), (dist.copy() if dist is not None else None)
+        finally:
+            engine.sync()
+            for p in (buf, tbuf, rbuf):
+                if p:
+                    self.lib.hipFree(p)
+
+    # ---- reset, state
+    def reset(self, streams=None):
+        """Empty the history of every stream, or of those `streams` (bool [streams]) names (the weights stay)."""
+        flags = None
+        if streams is not None:
+            flags = np.ascontiguousarray(np.asarray(streams, dtype=np.bool_).ravel()).astype(np.uint8)
+            if flags.shape != (self.streams,):
+                raise ValueError(f"streams: bool [{self.streams}], got {list(flags.shape)}")
+        if self._clf is None:
+            if self._pending is not None:
+                self._pending["count"] = np.where(flags.astype(bool), 0, self._pending["count"]) if flags is not None else np.zeros(self.streams, np.int64)
+            return
+        engine = self._engine()
+        self._check(engine, self.lib.htm_classifiers_reset(self._clf, engine.h, flags.ctypes.data_as(C.c_void_p) if flags is not None else None),
+                    "htm_classifiers_reset")
+
+    def _empty_state(self):
+        S = self.streams
+        ring = np.zeros((S, self.ring_len, self.shape[2], 2), dtype=np.int32)
+        ring[..., 0] = -1
+        return dict(total=np.int64(0), count=np.zeros(S, np.int64), ring=ring,
+                    weights=np.zeros((self._tables, len(self.steps), self.units, self.buckets), np.int32))
+
+    @property
+    def _tables(self):
+        """Weight tables a state holds: one per stream, or the owner's one."""
+        return 1 if self.source is not None else self.streams
+
+    def state_dict(self):
+        """{"params": int64 [streams, buckets, alpha_q, column_dim, cell_dim, max_pairs, steps...], "total": int64, "count": int64
+        [streams], "ring": int32 [streams, ring_len, max_pairs, 2], "weights": int32 [streams, H, units, buckets]} read from the
+        device (shared(): "weights" is the owner's table, once: [1, H, units, buckets])."""
+        if self.shape is None:
+            raise RuntimeError("the classifier does not know the shape of its patterns yet")
+        S = self.streams
+        params = np.asarray((S, self.buckets, self.alpha_q) + self.shape + self.steps, dtype=np.int64)
+        if self._clf is None and self.source is not None:          # (the weights are the owner's, on its device: bound through its engine)
+            self._engine()
+        if self._clf is None:
+            state = self._pending if self._pending is not None else self._empty_state()
+            return dict({k: np.array(v) for k, v in state.items()}, params=params)
+        engine = self._engine()
+        ring_bytes = self.ring_len * self.shape[2] * 8
+        size = 8 + S * 8 + S * ring_bytes
+        assert size == self.lib.htm_classifiers_state_bytes(self._clf)
+        blob = np.zeros(size, dtype=np.uint8)
+        self._check(engine, self.lib.htm_classifiers_export(self._clf, engine.h, blob.ctypes.data_as(C.c_void_p), size), "htm_classifiers_export")
+        head = blob[:8 + S * 8].view(np.int64)
+        tables = self._tables
+        weights = np.zeros((tables, len(self.steps), self.units, self.buckets), dtype=np.int32)
+        for i in range(tables):
+            for h in range(len(self.steps)):
+                self._check(engine, self.lib.htm_classifiers_read_weights(self._clf, engine.h, i, h, 0, self.units, weights[i, h].ctypes.data_as(C.c_void_p)),
+                            "htm_classifiers_read_weights")
+        return dict(params=params, total=np.int64(head[0]), count=head[1:].copy(),
+                    ring=blob[8 + S * 8:].view(np.int32).reshape(S, self.ring_len, self.shape[2], 2).copy(), weights=weights)
+
+    def load_state_dict(self, state):
+        """The state of a state_dict() of a bank with the same parameters and shape (shared(): the weights are the owner's and are
+        not written)."""
+        params = tuple(int(x) for x in state["params"])
+        if self.shape is None and len(params) == 6 + len(self.steps):
+            self._set_shape(*params[3:6])
+        S = self.streams
+        mine = (S, self.buckets, self.alpha_q) + (self.shape or ()) + self.steps
+        if params != mine:
+            raise ValueError(f"the state was saved with parameters {params} (streams, buckets, alpha_q, column_dim, cell_dim, max_pairs, steps...), this object has {mine}")
+        total = int(state["total"])
+        count = np.ascontiguousarray(state["count"], dtype=np.int64)
+        if count.shape != (S,) or (count < 0).any() or (count > total).any():
+            raise ValueError(f"state: count int64 [{S}] with 0 <= count <= total, got {count.tolist()}, total {total}")
+        ring = np.ascontiguousarray(state["ring"], dtype=np.int32)
+        weights = np.ascontiguousarray(state["weights"], dtype=np.int32)
+        tables = self._tables
+        if ring.shape != (S, self.ring_len, self.shape[2], 2):
+            raise ValueError(f"state['ring']: int32 {[S, self.ring_len, self.shape[2], 2]}, got {list(ring.shape)}")
+        if weights.shape != (tables, len(self.steps), self.units, self.buckets):
+            raise ValueError(f"state['weights']: int32 {[tables, len(self.steps), self.units, self.buckets]}, got {list(weights.shape)}")
+        if weights.size and (weights.max() > W_LIMIT or weights.min() < -W_LIMIT):
+            raise ValueError("state['weights']: a weight is outside [-2^30, 2^30]")
+        clean = dict(total=np.int64(total), count=count.copy(), ring=ring.copy(), weights=weights.copy())
+        if self._clf is None:
+            self._pending = clean
+        else:
+            self._import(self._engine(), clean)
+
+    def _import(self, engine, state):
+        S = self.streams
+        blob = np.zeros(8 + S * 8 + state["ring"].nbytes, dtype=np.uint8)
+        head = blob[:8 + S * 8].view(np.int64)
+        head[0], head[1:] = state["total"], state["count"]
+        blob[8 + S * 8:] = state["ring"].view(np.uint8).ravel()
+        self._check(engine, self.lib.htm_classifiers_import(self._clf, engine.h, blob.ctypes.data_as(C.c_void_p), blob.size), "htm_classifiers_import")
+        if self.source is not None:
+            return
+        for i in range(S):
+            for h in range(len(self.steps)):
+                w = np.ascontiguousarray(state["weights"][i, h])
+                self._check(engine, self.lib.htm_classifiers_write_weights(self._clf, engine.h, i, h, 0, self.units, w.ctypes.data_as(C.c_void_p)),
+                            "htm_classifiers_write_weights")
 
 
 def model_shape(engine):

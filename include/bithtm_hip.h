@@ -966,6 +966,45 @@ int64_t htm_classifier_state_bytes(const htm_classifier *clf);
 int htm_classifier_export(htm_classifier *clf, htm_handle *h, void *host_state, int64_t bytes);
 int htm_classifier_import(htm_classifier *clf, htm_handle *h, const void *host_state, int64_t bytes);
 
+/* A bank of classifiers: n_streams independent streams of one config in one htm_classifier object -- stream i
+ * fed (pairs_i, targets_i, resets_i) equals a one-stream object fed the same, bit for bit -- with every call over all streams in the
+ * launches of one.  Device memory, member-major: weights [n_streams][n_steps][units][B_pad], rings [n_streams][ring_len][max_pairs],
+ * counts [n_streams], and the learning accumulators per stream and horizon; one total on the host, since every call advances all
+ * streams by the same number of steps.  n_streams is in [1, 65535 / n_steps] (the member shares grid y with the horizon).
+ *
+ * share_weights_of (or NULL): an existing one-stream htm_classifier of the same config on h's device.  The new object then reads
+ * that object's weight table where it lies -- nothing is copied, and what the other object learns later is seen here -- and owns only
+ * rings, counts and accumulators.  The table is reference-counted inside the library: either object may be destroyed first
+ * (htm_classifier_destroy destroys a bank too).  The order between the other object's learning calls and this object's calls on
+ * different streams is the caller's.
+ *
+ * The update call: device_pairs, device_targets and device_reset_bits (or NULL: no resets) are HOST arrays of n_streams DEVICE
+ * pointers, each what the one-stream update call takes; they are copied as one pointer table per call, read before the call returns
+ * (n_streams == 1: passed by value, no copy).  device_best: DEVICE int32[n_streams][n_steps][n_horizons][2]; device_dist: DEVICE
+ * int32[n_streams][n_steps][n_horizons][buckets] or NULL.  Enqueued on h's stream without a wait.  learn != 0: two launches per step
+ * (kgcls_sum, kgcls_apply, grid y = n_streams x n_horizons); learn == 0: one launch (kgcls_frozen) per min(512, 65535 / (n_streams x
+ * n_horizons)) steps.  The reset call empties the history of the streams whose byte of streams (HOST uint8[n_streams]) is not 0, or of
+ * all (NULL).  read_weights / write_weights take the stream besides what the one-stream calls take.  export / import: HOST memory of
+ * exactly htm_classifiers_state_bytes bytes: int64 total; int64 count[n_streams]; then the rings.
+ *
+ * HTM_ERR_ARGUMENT, nothing enqueued: what the one-stream calls refuse; n_streams outside its range; a share_weights_of of another
+ * config, with more than one stream or on another device; a NULL entry of a pointer array; a stream outside [0, n_streams); the
+ * one-stream update, reset, weights, export or import call on an object with more than one stream.  HTM_ERR_STATE: learn != 0 on an
+ * object that shares its weights, whatever its n_streams and through either update call (the owner alone writes its table); weights
+ * written through an object that shares them. */
+int htm_classifiers_create(htm_handle *h, const htm_classifier_config *cfg, const int32_t *exp_table2049, int32_t n_streams,
+                           htm_classifier *share_weights_of, htm_classifier **out);
+int htm_classifiers_update(htm_classifier *clf, htm_handle *h, const void *const *device_pairs, int32_t pairs_per_step, int32_t n_steps,
+                           const int32_t *const *device_targets, int32_t n_targets, int32_t first_step, const uint32_t *const *device_reset_bits,
+                           int32_t learn, int32_t *device_best, int32_t *device_dist);
+int htm_classifiers_reset(htm_classifier *clf, htm_handle *h, const uint8_t *streams);
+int htm_classifiers_read_weights(htm_classifier *clf, htm_handle *h, int32_t stream, int32_t horizon, int32_t unit0, int32_t n_units, int32_t *host_dst);
+int htm_classifiers_write_weights(htm_classifier *clf, htm_handle *h, int32_t stream, int32_t horizon, int32_t unit0, int32_t n_units,
+                                  const int32_t *host_src);
+int64_t htm_classifiers_state_bytes(const htm_classifier *clf);
+int htm_classifiers_export(htm_classifier *clf, htm_handle *h, void *host_state, int64_t bytes);
+int htm_classifiers_import(htm_classifier *clf, htm_handle *h, const void *host_state, int64_t bytes);
+
 /* Pattern capture for the classifier: after htm_set_run_active_cells(h, device_pairs), an htm_run_recorded call of n steps writes
  * n x k x WPC pairs (int32 index, uint32 word) into device_pairs (DEVICE memory): row i holds step i's active-cell words of its k
  * active columns in active_column order -- index = column * WPC + w, word = word `index` of the step's cell activation, k =
@@ -976,6 +1015,34 @@ int htm_classifier_import(htm_classifier *clf, htm_handle *h, const void *host_s
  * call with such a member are HTM_ERR_STATE.  Setting rows on a column-sharded handle, or on one without the device's own Spatial
  * Pooler and Temporal Memory, is HTM_ERR_STATE. */
 int htm_set_run_active_cells(htm_handle *h, void *device_pairs);
+
+/* Pattern capture for a group: device_pairs is a HOST array of one DEVICE pointer per member (read before the
+ * call returns; one copy on the group's stream fills the group's table of capture descriptors).  After it a recorded htm_group_run (or
+ * htm_group_step) of n steps leaves each member's n x k x WPC pairs in its rows, exactly as htm_set_run_active_cells does for a
+ * recorded htm_run of the member alone: one launch (kgcls_capture, grid y = member) directly behind each step's record launch,
+ * inside the group's graphs, which are captured once per mode.  NULL clears the rows: calls then launch what they did before.  While
+ * rows are set, a group run or step without records is HTM_ERR_ARGUMENT.  HTM_ERR_ARGUMENT: a NULL entry.  HTM_ERR_STATE: a
+ * column-sharded member, or one without the device's own Spatial Pooler and Temporal Memory.  A member with rows of its own
+ * (htm_set_run_active_cells) still makes every group call HTM_ERR_STATE. */
+int htm_set_group_run_active_cells(htm_group *g, void *const *device_pairs);
+
+/* The classified tick: htm_likelihood_tick -- which is this call with the five classifier arguments NULL / 0 --
+ * with a bank of classifiers riding on it; lk and likelihood may be NULL (an unscored, classified tick).  clf: a bank of as many
+ * streams as the group has members, on the group's device, made for the members' column_dim x cell_dim with max_pairs >= k x WPC.
+ * targets: HOST int32[B], member i's bucket of this tick (outside [0, buckets): missing); it rides in the tick's pinned staging block:
+ * still ONE copy in.  best: HOST int32[B][n_horizons][2]; dist: HOST int32[B][n_horizons][buckets] or NULL; they ride in the tick's
+ * result block: still ONE copy out and ONE wait.  Launches: kgcls_capture behind the step's record launch (inside the tick's graph,
+ * which is keyed on it), then, behind the finish launch (and the likelihood launch of a scored tick), kgcls_sum + kgcls_apply when
+ * learn != 0, or kgcls_frozen over one step otherwise: 3 launches more for a learning tick, 2 for a frozen one, at every B.  A
+ * member's reset flag also empties its stream's history before its pattern enters it; the object's total advances by one.
+ * Refused with nothing enqueued, the group staying usable -- HTM_ERR_ARGUMENT: clf, targets and best not given together, dist without
+ * them; n_streams other than the group's size; another device; another column_dim or cell_dim than the members'; max_pairs below k x
+ * WPC.  HTM_ERR_STATE: learn != 0 on an object that shares its weights; a member that is column-sharded or lacks the device's own
+ * Spatial Pooler and Temporal Memory. */
+int htm_classifiers_tick(htm_group *g, const double *values, const htm_scalar_field *fields, int32_t n_fields, const uint32_t *packed_inputs,
+                         const uint8_t *resets, int32_t learning, int32_t use_graph, htm_live_row *rows, int32_t *decoded, int32_t *votes,
+                         htm_likelihood *lk, double *likelihood, htm_classifier *clf, const int32_t *targets, int32_t learn, int32_t *best,
+                         int32_t *dist);
 
 #ifdef __cplusplus
 }
