@@ -16,6 +16,9 @@
 // A frozen call (learn == 0) has no dependence between its steps: kcls_frozen is kcls_sum's P_t half, up to
 // HTM_CLASSIFIER_CHUNK steps per launch (step and horizon share grid y) over accumulators sized for the chunk.  No block ever waits for another.
 // kcls_capture fills a recorded run's pattern rows (htm_set_run_active_cells).
+// Each of the four is written once, as a device function over the ClsDev and ClsStep of one stream (cls_sum_block, cls_apply_block,
+// cls_frozen_block, cls_capture_rows); the kcls_ kernels call it for the object's one stream, the kgcls_ kernels of a bank (below) for
+// the stream of the block's row.
 // The arithmetic is in the __host__ __device__ functions at the top: tests/host_stub/classifier_host.cpp evaluates them on the host.
 // Part of the single translation unit htm_engine.hip (included after htm_likelihood.h).
 #ifndef BITHTM_HTM_CLASSIFIER_H
@@ -232,18 +235,18 @@ __device__ __forceinline__ void cls_ring_copy(const ClsDev &c, const ClsPair *__
     for (int j = lo + (int)threadIdx.x; j < hi; j += HTM_CLASSIFIER_THREADS) dst[j] = j < n_pairs ? row[j] : ClsPair{-1, 0u};
 }
 
-// grid (ceil(max_pairs / HTM_CLASSIFIER_PAIRS), H): step i of a learning call
-__global__ __launch_bounds__(HTM_CLASSIFIER_THREADS) void kcls_sum(ClsDev c, ClsStep s, int i) {
+// Step i of a learning call, horizon index h (its `horizon` = steps[h], read by the kernel from its own argument), the block's share:
+// the body of kcls_sum and kgcls_sum, over the ClsDev and ClsStep of the block's stream.  Grid x = ceil(max_pairs / HTM_CLASSIFIER_PAIRS).
+__device__ __forceinline__ void cls_sum_block(const ClsDev &c, const ClsStep &s, int h, int horizon, int i) {
     __shared__ unsigned long long s_acc[2 * HTM_CLASSIFIER_MAX_BUCKETS];
     __shared__ int32_t s_e[HTM_CLASSIFIER_MAX_BUCKETS];
     __shared__ unsigned long long s_red[9];
     __shared__ uint32_t s_last;
-    const int h = (int)blockIdx.y, tid = (int)threadIdx.x;
-    const int horizon = c.steps[h];
+    const int tid = (int)threadIdx.x;
     const int64_t t = s.total + i;
-    const int64_t count = cls_reset_bit(s, i) ? 0 : *c.count;               // patterns of the history before P_t enters
+    const int64_t count = cls_reset_bit(s, i) ? 0 : *c.count;               // patterns of the stream's history before P_t enters
     const int32_t g = s.targets[(int)(((int64_t)s.first_step + i) % s.n_targets)];
-    const bool learns = g >= 0 && g < c.B && (int64_t)horizon <= count;    // (the history then holds P_(t-h))
+    const bool learns = g >= 0 && g < c.B && (int64_t)horizon <= count;    // (the history then holds P_(t-h); block-uniform)
     const int lo = (int)blockIdx.x * HTM_CLASSIFIER_PAIRS, hi = min(lo + HTM_CLASSIFIER_PAIRS, c.max_pairs);
     const ClsPair *row = s.pairs + (size_t)i * s.pairs_per_step;
     const int32_t *wh = c.w + (int64_t)h * c.w_stride;
@@ -274,13 +277,13 @@ __global__ __launch_bounds__(HTM_CLASSIFIER_THREADS) void kcls_sum(ClsDev c, Cls
     for (int b = tid; b < c.B_pad; b += HTM_CLASSIFIER_THREADS) delta[b] = b < c.B ? cls_delta(c.alpha_q, cls_prob(s_e[b], z), b == g) : 0;
 }
 
-// grid (ceil(max_pairs / HTM_CLASSIFIER_PAIRS), H), behind kcls_sum of the same step
-__global__ __launch_bounds__(HTM_CLASSIFIER_THREADS) void kcls_apply(ClsDev c, ClsStep s, int i) {
-    const int h = (int)blockIdx.y, wave = (int)threadIdx.x >> 6, lane = (int)threadIdx.x & 63;
+// Behind cls_sum_block of the same step, on the same grid: the body of kcls_apply and kgcls_apply
+__device__ __forceinline__ void cls_apply_block(const ClsDev &c, const ClsStep &s, int h, int horizon, int i) {
+    const int wave = (int)threadIdx.x >> 6, lane = (int)threadIdx.x & 63;
     if (blockIdx.x == 0 && h == 0 && threadIdx.x == 0) *c.count = (cls_reset_bit(s, i) ? 0 : *c.count) + 1;
     if (!c.learn[h]) return;
     const int64_t t = s.total + i;
-    const ClsPair *pairs = c.ring + (size_t)((t - c.steps[h]) % c.ring_len) * c.max_pairs;
+    const ClsPair *pairs = c.ring + (size_t)((t - horizon) % c.ring_len) * c.max_pairs;
     const int lo = (int)blockIdx.x * HTM_CLASSIFIER_PAIRS, hi = min(lo + HTM_CLASSIFIER_PAIRS, c.max_pairs);
     int32_t *wh = c.w + (int64_t)h * c.w_stride;
     const int32_t *delta = c.delta + (size_t)h * c.B_pad;
@@ -305,19 +308,19 @@ __global__ __launch_bounds__(HTM_CLASSIFIER_THREADS) void kcls_apply(ClsDev c, C
     }
 }
 
-// grid (ceil(pairs_per_step / HTM_CLASSIFIER_PAIRS), H * n), n <= HTM_CLASSIFIER_CHUNK: steps [first, first + n) of a frozen call, block row y
-// being horizon y % H of step first + y / H
-__global__ __launch_bounds__(HTM_CLASSIFIER_THREADS) void kcls_frozen(ClsDev c, ClsFrozen f, ClsStep s, int first, int n) {
+// Step first + zi of the n steps [first, first + n) of a frozen launch, horizon index h, the block's share: the body of kcls_frozen and
+// kgcls_frozen.  A block row's row of the accumulators f is its own: blockIdx.y.  Grid x = ceil(pairs_per_step / HTM_CLASSIFIER_PAIRS).
+__device__ __forceinline__ void cls_frozen_block(const ClsDev &c, const ClsFrozen &f, const ClsStep &s, int h, int zi, int first, int n) {
     __shared__ unsigned long long s_acc[HTM_CLASSIFIER_MAX_BUCKETS];
     __shared__ int32_t s_e[HTM_CLASSIFIER_MAX_BUCKETS];
     __shared__ unsigned long long s_red[9];
     __shared__ uint32_t s_last;
     __shared__ int s_reset;
-    const int h = (int)blockIdx.y % c.H, zi = (int)blockIdx.y / c.H, i = first + zi, tid = (int)threadIdx.x;
+    const int i = first + zi, tid = (int)threadIdx.x;
     const int64_t t = s.total + i;
     const int lo = (int)blockIdx.x * HTM_CLASSIFIER_PAIRS, hi = min(lo + HTM_CLASSIFIER_PAIRS, s.pairs_per_step);
     const ClsPair *row = s.pairs + (size_t)i * s.pairs_per_step;
-    // the count behind the chunk: the steps since its last reset, or n more (one block; nobody reads the count in this launch)
+    // the stream's count behind the chunk: the steps since its last reset, or n more (one block; nobody reads the count in this launch)
     if (blockIdx.x == 0 && h == 0 && zi == 0) {
         if (tid == 0) s_reset = -1;
         __syncthreads();
@@ -326,7 +329,7 @@ __global__ __launch_bounds__(HTM_CLASSIFIER_THREADS) void kcls_frozen(ClsDev c, 
         __syncthreads();
         if (tid == 0) *c.count = s_reset < 0 ? *c.count + n : (int64_t)(n - s_reset);
     }
-    // the ring takes the chunk's last ring_len patterns (distinct slots), the whole row of each
+    // the stream's ring takes the chunk's last ring_len patterns (distinct slots), the whole row of each
     if (h == 0 && zi >= n - c.ring_len)
         for (int l = lo; l < c.max_pairs; l += (int)gridDim.x * HTM_CLASSIFIER_PAIRS)
             cls_ring_copy(c, row, s.pairs_per_step, l, min(l + HTM_CLASSIFIER_PAIRS, c.max_pairs), (int)(t % c.ring_len));
@@ -334,8 +337,8 @@ __global__ __launch_bounds__(HTM_CLASSIFIER_THREADS) void kcls_frozen(ClsDev c, 
     __syncthreads();
     cls_sum_rows(c, c.w + (int64_t)h * c.w_stride, row, lo, hi, s_acc);
     __syncthreads();
-    unsigned long long *acc = (unsigned long long *)f.acc + ((size_t)zi * c.H + h) * c.B_pad;
-    uint32_t *ticket = f.ticket + (size_t)zi * c.H + h;
+    unsigned long long *acc = (unsigned long long *)f.acc + (size_t)blockIdx.y * c.B_pad;
+    uint32_t *ticket = f.ticket + blockIdx.y;
     if (!cls_arrive(acc, s_acc, c.B_pad, ticket, gridDim.x, &s_last)) return;
     cls_take(acc, s_acc, c.B_pad);
     if (tid == 0) __hip_atomic_store(ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -345,14 +348,31 @@ __global__ __launch_bounds__(HTM_CLASSIFIER_THREADS) void kcls_frozen(ClsDev c, 
     cls_write_outputs(c, s, i, h, s_e, best, z);
 }
 
+// grid (ceil(max_pairs / HTM_CLASSIFIER_PAIRS), H): step i of a learning call
+__global__ __launch_bounds__(HTM_CLASSIFIER_THREADS) void kcls_sum(ClsDev c, ClsStep s, int i) {
+    cls_sum_block(c, s, (int)blockIdx.y, c.steps[blockIdx.y], i);
+}
+
+// the same grid, behind kcls_sum of the same step
+__global__ __launch_bounds__(HTM_CLASSIFIER_THREADS) void kcls_apply(ClsDev c, ClsStep s, int i) {
+    cls_apply_block(c, s, (int)blockIdx.y, c.steps[blockIdx.y], i);
+}
+
+// grid (ceil(pairs_per_step / HTM_CLASSIFIER_PAIRS), H * n), n <= HTM_CLASSIFIER_CHUNK: steps [first, first + n) of a frozen call, block row y
+// being horizon y % H of step first + y / H; the accumulators f hold HTM_CLASSIFIER_CHUNK * H rows
+__global__ __launch_bounds__(HTM_CLASSIFIER_THREADS) void kcls_frozen(ClsDev c, ClsFrozen f, ClsStep s, int first, int n) {
+    cls_frozen_block(c, f, s, (int)blockIdx.y % c.H, (int)blockIdx.y / c.H, first, n);
+}
+
 // Pattern capture of a recorded htm_run (htm_set_run_active_cells): the device descriptor of the caller's rows (one per handle; graphs
 // hold its address, the setter fills it)
 struct ClsCapDev { ClsPair *rows; };       // [n][k * WPC]
 
 // Directly behind the record launch of the step of parity p (htm_record.h: every buffer of step t still holds there in every
 // schedule): row `slot` of the call takes the k * WPC active-cell words of the step's active columns, in active_cols order.  The slot
-// is the record's; a step outside the call's records writes nothing.  A thread per pair: grid >= k * WPC / 256 blocks.
-__global__ __launch_bounds__(256) void kcls_capture(Dev d, int p, const RecDev *r, const ClsCapDev *cap) {
+// is the record's; a step outside the call's records writes nothing.  A thread per pair: grid x >= k * WPC / 256 blocks.  The body of
+// kcls_capture and kgcls_capture, over the Dev, the record descriptor and the capture descriptor of the block's model.
+__device__ __forceinline__ void cls_capture_rows(const Dev &d, int p, const RecDev *r, const ClsCapDev &cap) {
     const uint32_t slot = d.ctr->step[p] - r->base;
     if (slot >= (uint32_t)r->n) return;
     const int per = d.k * d.WPC, i = (int)(blockIdx.x * 256 + threadIdx.x);
@@ -363,16 +383,19 @@ __global__ __launch_bounds__(256) void kcls_capture(Dev d, int p, const RecDev *
         pr.index = col * d.WPC + i % d.WPC;
         pr.word = d.act[p][pr.index];
     }
-    cap->rows[(size_t)slot * per + i] = pr;
+    cap.rows[(size_t)slot * per + i] = pr;
 }
+
+__global__ __launch_bounds__(256) void kcls_capture(Dev d, int p, const RecDev *r, const ClsCapDev *cap) { cls_capture_rows(d, p, r, *cap); }
 
 #endif  // __HIPCC__
 
 // ------------------------------------------------------------------------------------------
 // A bank of classifiers (htm_classifiers_*): n independent streams of one config, member-major -- weights
 // [n][H][units][B_pad] (or one table every member reads: member stride 0), rings [n][ring_len][max_pairs], counts [n], accumulators
-// [n][H][2][B_pad], tickets, deltas and learn flags [n][H].  The kernels are twins of the ones above: the member shares grid y with
-// the horizon (and, frozen, with the step), and everything a block touches is its member's.  Where a block's row lies is the
+// [n][H][2][B_pad], tickets, deltas and learn flags [n][H].  Its kernels run the bodies above (cls_sum_block, cls_apply_block,
+// cls_frozen_block, cls_capture_rows): the member shares grid y with the horizon (and, frozen, with the step), a block makes its
+// member's ClsDev and ClsStep (gcls_dev, gcls_step) and everything it touches is its member's.  Where a block's row lies is the
 // arithmetic below; tests/host_stub/group_classifier_host.cpp evaluates it on the host.
 
 // steps per frozen launch of a bank of n streams: member, step and horizon share grid y (at most 65535 rows)
@@ -438,149 +461,37 @@ __device__ __forceinline__ ClsStep gcls_step(const GClsStep &g, const ClsDev &c,
     return s;
 }
 
-// grid (ceil(max_pairs / HTM_CLASSIFIER_PAIRS), n * H): step i of a learning call, every member's (kcls_sum's twin)
+// grid (ceil(max_pairs / HTM_CLASSIFIER_PAIRS), n * H): step i of a learning call, every member's
 __global__ __launch_bounds__(HTM_CLASSIFIER_THREADS) void kgcls_sum(GClsDev gd, GClsStep gs, int i) {
-    __shared__ unsigned long long s_acc[2 * HTM_CLASSIFIER_MAX_BUCKETS];
-    __shared__ int32_t s_e[HTM_CLASSIFIER_MAX_BUCKETS];
-    __shared__ unsigned long long s_red[9];
-    __shared__ uint32_t s_last;
-    const int m = gcls_member((int)blockIdx.y, gd.c.H), h = gcls_horizon((int)blockIdx.y, gd.c.H), tid = (int)threadIdx.x;
+    const int m = gcls_member((int)blockIdx.y, gd.c.H), h = gcls_horizon((int)blockIdx.y, gd.c.H);
     if (m >= gd.n) return;
     const ClsDev c = gcls_dev(gd, m);
-    const ClsStep s = gcls_step(gs, c, m);
-    const int horizon = gd.c.steps[h];
-    const int64_t t = s.total + i;
-    const int64_t count = cls_reset_bit(s, i) ? 0 : *c.count;               // patterns of the member's history before P_t enters
-    const int32_t g = s.targets[(int)(((int64_t)s.first_step + i) % s.n_targets)];
-    const bool learns = g >= 0 && g < c.B && (int64_t)horizon <= count;    // (block-uniform per member and horizon)
-    const int lo = (int)blockIdx.x * HTM_CLASSIFIER_PAIRS, hi = min(lo + HTM_CLASSIFIER_PAIRS, c.max_pairs);
-    const ClsPair *row = s.pairs + (size_t)i * s.pairs_per_step;
-    const int32_t *wh = c.w + (int64_t)h * c.w_stride;
-    for (int b = tid; b < 2 * c.B_pad; b += HTM_CLASSIFIER_THREADS) s_acc[b] = 0ull;
-    __syncthreads();
-    cls_sum_rows(c, wh, row, min(lo, s.pairs_per_step), min(hi, s.pairs_per_step), s_acc);
-    if (learns) {
-        if (horizon == 0) cls_sum_rows(c, wh, row, min(lo, s.pairs_per_step), min(hi, s.pairs_per_step), s_acc + c.B_pad);
-        else cls_sum_rows(c, wh, c.ring + (size_t)((t - horizon) % c.ring_len) * c.max_pairs, lo, hi, s_acc + c.B_pad);
-    }
-    if (h == 0) cls_ring_copy(c, row, s.pairs_per_step, lo, hi, (int)(t % c.ring_len));
-    __syncthreads();
-    unsigned long long *acc = (unsigned long long *)c.acc + (size_t)h * 2 * c.B_pad;
-    if (!cls_arrive(acc, s_acc, 2 * c.B_pad, c.ticket + h, gridDim.x, &s_last)) return;
-    cls_take(acc, s_acc, 2 * c.B_pad);
-    if (tid == 0) {
-        __hip_atomic_store(c.ticket + h, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        c.learn[h] = learns ? 1 : 0;
-    }
-    int best;
-    int64_t z;
-    cls_softmax(c, s_acc, s_e, s_red, best, z);
-    cls_write_outputs(c, s, i, h, s_e, best, z);
-    if (!learns) return;                                   // (block-uniform)
-    __syncthreads();                                       // (s_e is read above, written below)
-    cls_softmax(c, s_acc + c.B_pad, s_e, s_red, best, z);
-    int32_t *delta = c.delta + (size_t)h * c.B_pad;
-    for (int b = tid; b < c.B_pad; b += HTM_CLASSIFIER_THREADS) delta[b] = b < c.B ? cls_delta(c.alpha_q, cls_prob(s_e[b], z), b == g) : 0;
+    cls_sum_block(c, gcls_step(gs, c, m), h, gd.c.steps[h], i);
 }
 
-// grid (ceil(max_pairs / HTM_CLASSIFIER_PAIRS), n * H), behind kgcls_sum of the same step (kcls_apply's twin)
+// the same grid, behind kgcls_sum of the same step
 __global__ __launch_bounds__(HTM_CLASSIFIER_THREADS) void kgcls_apply(GClsDev gd, GClsStep gs, int i) {
     const int m = gcls_member((int)blockIdx.y, gd.c.H), h = gcls_horizon((int)blockIdx.y, gd.c.H);
-    const int wave = (int)threadIdx.x >> 6, lane = (int)threadIdx.x & 63;
     if (m >= gd.n) return;
     const ClsDev c = gcls_dev(gd, m);
-    const ClsStep s = gcls_step(gs, c, m);
-    if (blockIdx.x == 0 && h == 0 && threadIdx.x == 0) *c.count = (cls_reset_bit(s, i) ? 0 : *c.count) + 1;
-    if (!c.learn[h]) return;
-    const int64_t t = s.total + i;
-    const ClsPair *pairs = c.ring + (size_t)((t - gd.c.steps[h]) % c.ring_len) * c.max_pairs;
-    const int lo = (int)blockIdx.x * HTM_CLASSIFIER_PAIRS, hi = min(lo + HTM_CLASSIFIER_PAIRS, c.max_pairs);
-    int32_t *wh = c.w + (int64_t)h * c.w_stride;
-    const int32_t *delta = c.delta + (size_t)h * c.B_pad;
-    for (int b0 = 0; b0 < c.B_pad; b0 += 256) {
-        const int b = b0 + 4 * lane;
-        if (b >= c.B_pad) continue;
-        const int4 d = *(const int4 *)(delta + b);
-        for (int j = lo + wave; j < hi; j += HTM_CLASSIFIER_THREADS / 64) {
-            const ClsPair pr = pairs[j];
-            uint32_t bits = cls_live_bits(pr.index, pr.word, c.K, c.WPC, c.n_cols);
-            if (!bits) continue;
-            int32_t *row0 = wh + cls_unit0(pr.index, c.K, c.WPC) * c.B_pad + b;
-            while (bits) {
-                const int bit = __ffs(bits) - 1;
-                bits &= bits - 1;
-                int4 *p = (int4 *)(row0 + (int64_t)bit * c.B_pad);
-                int4 v = *p;
-                v.x = cls_clamp(v.x, d.x); v.y = cls_clamp(v.y, d.y); v.z = cls_clamp(v.z, d.z); v.w = cls_clamp(v.w, d.w);
-                *p = v;
-            }
-        }
-    }
+    cls_apply_block(c, gcls_step(gs, c, m), h, gd.c.steps[h], i);
 }
 
 // grid (ceil(pairs_per_step / HTM_CLASSIFIER_PAIRS), streams * n * H), n <= gcls_chunk(streams, H): steps [first, first + n) of a frozen
-// call, every member's (kcls_frozen's twin).  The accumulators f are [streams * n * H] rows: a block row's own.
+// call, every member's.  The accumulators f are [streams * n * H] rows: a block row's own.
 __global__ __launch_bounds__(HTM_CLASSIFIER_THREADS) void kgcls_frozen(GClsDev gd, ClsFrozen f, GClsStep gs, int first, int n) {
-    __shared__ unsigned long long s_acc[HTM_CLASSIFIER_MAX_BUCKETS];
-    __shared__ int32_t s_e[HTM_CLASSIFIER_MAX_BUCKETS];
-    __shared__ unsigned long long s_red[9];
-    __shared__ uint32_t s_last;
-    __shared__ int s_reset;
     const int y = (int)blockIdx.y, h = gcls_horizon(y, gd.c.H), zi = gcls_frozen_step(y, gd.c.H, n), m = gcls_frozen_member(y, gd.c.H, n);
-    const int i = first + zi, tid = (int)threadIdx.x;
     if (m >= gd.n) return;
     const ClsDev c = gcls_dev(gd, m);
-    const ClsStep s = gcls_step(gs, c, m);
-    const int64_t t = s.total + i;
-    const int lo = (int)blockIdx.x * HTM_CLASSIFIER_PAIRS, hi = min(lo + HTM_CLASSIFIER_PAIRS, s.pairs_per_step);
-    const ClsPair *row = s.pairs + (size_t)i * s.pairs_per_step;
-    // the member's count behind the chunk: the steps since its last reset, or n more (one block per member)
-    if (blockIdx.x == 0 && h == 0 && zi == 0) {
-        if (tid == 0) s_reset = -1;
-        __syncthreads();
-        for (int j = tid; j < n; j += HTM_CLASSIFIER_THREADS)
-            if (cls_reset_bit(s, first + j)) atomicMax(&s_reset, j);
-        __syncthreads();
-        if (tid == 0) *c.count = s_reset < 0 ? *c.count + n : (int64_t)(n - s_reset);
-    }
-    // the member's ring takes the chunk's last ring_len patterns (distinct slots), the whole row of each
-    if (h == 0 && zi >= n - c.ring_len)
-        for (int l = lo; l < c.max_pairs; l += (int)gridDim.x * HTM_CLASSIFIER_PAIRS)
-            cls_ring_copy(c, row, s.pairs_per_step, l, min(l + HTM_CLASSIFIER_PAIRS, c.max_pairs), (int)(t % c.ring_len));
-    for (int b = tid; b < c.B_pad; b += HTM_CLASSIFIER_THREADS) s_acc[b] = 0ull;
-    __syncthreads();
-    cls_sum_rows(c, c.w + (int64_t)h * c.w_stride, row, lo, hi, s_acc);
-    __syncthreads();
-    unsigned long long *acc = (unsigned long long *)f.acc + (size_t)y * c.B_pad;
-    uint32_t *ticket = f.ticket + y;
-    if (!cls_arrive(acc, s_acc, c.B_pad, ticket, gridDim.x, &s_last)) return;
-    cls_take(acc, s_acc, c.B_pad);
-    if (tid == 0) __hip_atomic_store(ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    int best;
-    int64_t z;
-    cls_softmax(c, s_acc, s_e, s_red, best, z);
-    cls_write_outputs(c, s, i, h, s_e, best, z);
+    cls_frozen_block(c, f, gcls_step(gs, c, m), h, zi, first, n);
 }
 
-// Pattern capture of a recorded group call (htm_set_group_run_active_cells; kcls_capture's twin): grid (blocks, B), block row y being
-// member y of the group's tables -- its Dev, its record descriptor (whose slot names the row) and its capture descriptor.  Directly
-// behind kgrp_rec_step of the step of parity p.  A member without rows, or a step outside the call's records, writes nothing.
+// Pattern capture of a recorded group call (htm_set_group_run_active_cells): grid (blocks, B), block row y being member y of the
+// group's tables -- its Dev, its record descriptor (whose slot names the row) and its capture descriptor.  Directly behind
+// kgrp_rec_step of the step of parity p.  A member without rows, or a step outside the call's records, writes nothing.
 __global__ __launch_bounds__(256) void kgcls_capture(const Dev *__restrict__ tab, int p, RecDev *const *__restrict__ recs, const ClsCapDev *__restrict__ caps) {
-    const Dev &d = tab[blockIdx.y];
-    const RecDev *r = recs[blockIdx.y];
-    ClsPair *rows = caps[blockIdx.y].rows;
-    if (!rows) return;
-    const uint32_t slot = d.ctr->step[p] - r->base;
-    if (slot >= (uint32_t)r->n) return;
-    const int per = d.k * d.WPC, i = (int)(blockIdx.x * 256 + threadIdx.x);
-    if (i >= per) return;
-    const int col = d.active_cols[p][i / d.WPC];
-    ClsPair pr{-1, 0u};
-    if (col >= 0 && col < d.C) {
-        pr.index = col * d.WPC + i % d.WPC;
-        pr.word = d.act[p][pr.index];
-    }
-    rows[(size_t)slot * per + i] = pr;
+    if (!caps[blockIdx.y].rows) return;
+    cls_capture_rows(tab[blockIdx.y], p, recs[blockIdx.y], caps[blockIdx.y]);
 }
 
 // the flagged members' histories emptied (flags null: every member's); a thread per member

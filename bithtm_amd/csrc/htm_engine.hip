@@ -4398,8 +4398,6 @@ static int cls_check_single(const char *what, htm_classifier *clf, htm_handle *h
     return 0;
 }
 
-extern "C" int64_t htm_classifier_state_bytes(const htm_classifier *clf) { return clf ? (int64_t)(16 + clf->ring_bytes) : (int64_t)HTM_ERR_ARGUMENT; }
-
 // blocks along x of the launches that split a pattern of n pairs
 static int cls_blocks(int n_pairs) { return (n_pairs + HTM_CLASSIFIER_PAIRS - 1) / HTM_CLASSIFIER_PAIRS; }
 
@@ -4424,162 +4422,74 @@ static int cls_frozen_rows(const char *what, htm_classifier *clf, htm_handle *h,
     return 0;
 }
 
-extern "C" int htm_classifier_update(htm_classifier *clf, htm_handle *h, const void *device_pairs, int32_t pairs_per_step, int32_t n_steps,
-                                     const int32_t *device_targets, int32_t n_targets, int32_t first_step, const uint32_t *device_reset_bits,
-                                     int32_t learn, int32_t *device_best, int32_t *device_dist) {
-    if (int rc = cls_check_single("htm_classifier_update", clf, h)) return rc;
-    if (!device_pairs || !device_targets || !device_best) return cls_refuse(h, "htm_classifier_update: null pairs, targets or output", HTM_ERR_ARGUMENT);
-    const ClsDev &d = clf->d;
-    if (pairs_per_step < 1 || pairs_per_step > d.max_pairs)
-        return cls_refuse(h, "htm_classifier_update: pairs_per_step must be in [1, max_pairs = " + std::to_string(d.max_pairs) + "]", HTM_ERR_ARGUMENT);
-    if (n_steps < 0 || n_targets < 1 || first_step < 0) return cls_refuse(h, "htm_classifier_update: n_steps >= 0, n_targets >= 1, first_step >= 0", HTM_ERR_ARGUMENT);
-    if (n_steps == 0) return HTM_OK;
-    HIPCHK(h, hipSetDevice(clf->device));
-    if (learn && clf->shares) return cls_refuse(h, "htm_classifier_update: the object reads another object's weights: learn must be 0", HTM_ERR_STATE);
-    if (!learn) { if (int rc = cls_frozen_rows("htm_classifier_update", clf, h, (size_t)HTM_CLASSIFIER_CHUNK * d.H)) return rc; }
-    const ClsStep s{(const ClsPair *)device_pairs, pairs_per_step, device_targets, device_reset_bits, n_targets, first_step, device_best, device_dist, clf->total};
-    if (learn) {
-        const dim3 grid(cls_blocks(d.max_pairs), d.H);
-        for (int i = 0; i < n_steps; ++i) {
-            LAUNCH(h, "classifier:sum", kcls_sum, grid, HTM_CLASSIFIER_THREADS, d, s, i);
-            LAUNCH(h, "classifier:apply", kcls_apply, grid, HTM_CLASSIFIER_THREADS, d, s, i);
-        }
-    } else {
-        for (int first = 0; first < n_steps; first += HTM_CLASSIFIER_CHUNK) {
-            const int n = std::min<int>(HTM_CLASSIFIER_CHUNK, n_steps - first);
-            LAUNCH(h, "classifier:frozen", kcls_frozen, dim3(cls_blocks(pairs_per_step), d.H * n), HTM_CLASSIFIER_THREADS, d, clf->frozen, s, first, n);
-        }
-    }
-    clf->total += n_steps;
-    return launch_status(h->err);
-}
+// Every call below is written once, over the n streams of the object (DESIGN.md sections 24 and 25); the htm_classifier_ and
+// htm_classifiers_ entry points are two doors to it.  `what` names the function that was called, `bank` its door: the one-stream door
+// takes only objects of n = 1 and launches the kcls_ kernels, the bank's launches the kgcls_ kernels, at n = 1 as well.  The total is
+// the object's: every call advances all streams by the same steps.
+static int cls_door(const char *what, bool bank, htm_classifier *clf, htm_handle *h) { return bank ? cls_check(what, clf, h) : cls_check_single(what, clf, h); }
 
-extern "C" int htm_classifier_reset(htm_classifier *clf, htm_handle *h) {
-    if (int rc = cls_check_single("htm_classifier_reset", clf, h)) return rc;
-    HIPCHK(h, hipSetDevice(clf->device));
-    HIPCHK(h, hipMemsetAsync(clf->d.count, 0, 16, h->stream));
-    return HTM_OK;
-}
-
-// the rows of one horizon's table a weights call names, or a refusal
-static int cls_rows(const char *what, htm_classifier *clf, htm_handle *h, int32_t horizon, int32_t unit0, int32_t n_units, const void *host) {
-    if (int rc = cls_check_single(what, clf, h)) return rc;
-    const ClsDev &d = clf->d;
-    const int64_t units = d.w_stride / d.B_pad;
-    if (!host || horizon < 0 || horizon >= d.H || unit0 < 0 || n_units < 0 || (int64_t)unit0 + n_units > units)
-        return cls_refuse(h, std::string(what) + ": need host memory, a horizon index below n_steps and rows inside the table", HTM_ERR_ARGUMENT);
-    return 0;
-}
-
-extern "C" int htm_classifier_read_weights(htm_classifier *clf, htm_handle *h, int32_t horizon, int32_t unit0, int32_t n_units, int32_t *host_dst) {
-    if (int rc = cls_rows("htm_classifier_read_weights", clf, h, horizon, unit0, n_units, host_dst)) return rc;
-    if (n_units == 0) return HTM_OK;
-    const ClsDev &d = clf->d;
-    HIPCHK(h, hipSetDevice(clf->device));
-    HIPCHK(h, hipMemcpy2DAsync(host_dst, (size_t)d.B * 4, d.w + (int64_t)horizon * d.w_stride + (int64_t)unit0 * d.B_pad, (size_t)d.B_pad * 4, (size_t)d.B * 4,
-                               (size_t)n_units, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    return HTM_OK;
-}
-
-extern "C" int htm_classifier_write_weights(htm_classifier *clf, htm_handle *h, int32_t horizon, int32_t unit0, int32_t n_units, const int32_t *host_src) {
-    if (int rc = cls_rows("htm_classifier_write_weights", clf, h, horizon, unit0, n_units, host_src)) return rc;
-    if (clf->shares) return cls_refuse(h, "htm_classifier_write_weights: the object reads another object's weights: write them there", HTM_ERR_STATE);
-    const ClsDev &d = clf->d;
-    for (size_t i = 0; i < (size_t)n_units * d.B; ++i)
-        if (host_src[i] > HTM_CLASSIFIER_W_LIMIT || host_src[i] < -HTM_CLASSIFIER_W_LIMIT)
-            return cls_refuse(h, "htm_classifier_write_weights: a weight is outside [-2^30, 2^30]", HTM_ERR_ARGUMENT);
-    if (n_units == 0) return HTM_OK;
-    HIPCHK(h, hipSetDevice(clf->device));
-    // (the padding buckets of a row stay 0: nothing ever writes them)
-    HIPCHK(h, hipMemcpy2DAsync(d.w + (int64_t)horizon * d.w_stride + (int64_t)unit0 * d.B_pad, (size_t)d.B_pad * 4, host_src, (size_t)d.B * 4, (size_t)d.B * 4,
-                               (size_t)n_units, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    return HTM_OK;
-}
-
-extern "C" int htm_classifier_export(htm_classifier *clf, htm_handle *h, void *host_state, int64_t bytes) {
-    if (int rc = cls_check_single("htm_classifier_export", clf, h)) return rc;
-    if (!host_state || bytes != htm_classifier_state_bytes(clf)) return cls_refuse(h, "htm_classifier_export: need host_state of htm_classifier_state_bytes bytes", HTM_ERR_ARGUMENT);
-    HIPCHK(h, hipSetDevice(clf->device));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    memcpy(host_state, &clf->total, 8);
-    HIPCHK(h, hipMemcpy((char *)host_state + 8, clf->d.count, 8, hipMemcpyDeviceToHost));
-    HIPCHK(h, hipMemcpy((char *)host_state + 16, clf->d.ring, clf->ring_bytes, hipMemcpyDeviceToHost));
-    return HTM_OK;
-}
-
-extern "C" int htm_classifier_import(htm_classifier *clf, htm_handle *h, const void *host_state, int64_t bytes) {
-    if (int rc = cls_check_single("htm_classifier_import", clf, h)) return rc;
-    if (!host_state || bytes != htm_classifier_state_bytes(clf)) return cls_refuse(h, "htm_classifier_import: need host_state of htm_classifier_state_bytes bytes", HTM_ERR_ARGUMENT);
-    int64_t head[2];
-    memcpy(head, host_state, 16);
-    // (a learning step looks count steps back in the ring: never before step 0)
-    if (head[1] < 0 || head[1] > head[0]) return cls_refuse(h, "htm_classifier_import: need 0 <= count <= total", HTM_ERR_ARGUMENT);
-    HIPCHK(h, hipSetDevice(clf->device));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    HIPCHK(h, hipMemcpy(clf->d.count, &head[1], 8, hipMemcpyHostToDevice));
-    HIPCHK(h, hipMemcpy(clf->d.ring, (const char *)host_state + 16, clf->ring_bytes, hipMemcpyHostToDevice));
-    clf->total = head[0];
-    return HTM_OK;
-}
-
-// ------------------------------------------------------------------------------------------
-// A bank of classifiers (htm_classifier.h, the kgcls_ kernels): n streams of one config in one object, every
-// call over all of them in the launches of one.  The total is the object's: every call advances all streams by the same steps.
 static GClsDev gcls_of(const htm_classifier *clf) { return GClsDev{clf->d, clf->n, clf->shares ? 0 : (int64_t)clf->d.H * clf->d.w_stride}; }
+
+// the accumulators of a frozen call of n_steps steps: for the steps of its largest launch; through the one-stream door for a whole chunk
+static int cls_prepare(htm_classifier *clf, htm_handle *h, int32_t learn, int32_t n_steps, bool bank = true) {
+    const ClsDev &d = clf->d;
+    if (learn) return 0;
+    const size_t steps = bank ? std::min<int>(gcls_chunk(clf->n, d.H), std::max(n_steps, 1)) : HTM_CLASSIFIER_CHUNK;
+    return cls_frozen_rows(bank ? "htm_classifiers_update" : "htm_classifier_update", clf, h, (size_t)clf->n * steps * d.H);
+}
 
 // The launches of an update over every stream, enqueued on stream s: 2 per step when learning, one per gcls_chunk steps otherwise.
 // gs holds the call's inputs (a table in device memory, or member 0's pointers and strides); the caller has checked them.
-static int gcls_prepare(htm_classifier *clf, htm_handle *h, int32_t learn, int32_t n_steps) {
+static int cls_enqueue(htm_classifier *clf, htm_handle *h, hipStream_t s, GClsStep gs, int32_t learn, bool bank = true) {
     const ClsDev &d = clf->d;
-    const int chunk = gcls_chunk(clf->n, d.H);
-    if (learn) return 0;                            // (a frozen call: accumulators for the steps of its largest launch)
-    return cls_frozen_rows("htm_classifiers_update", clf, h, (size_t)clf->n * std::min<int>(chunk, std::max(n_steps, 1)) * d.H);
-}
-
-static int gcls_enqueue(htm_classifier *clf, htm_handle *h, hipStream_t s, GClsStep gs, int32_t learn) {
-    const ClsDev &d = clf->d;
-    const int chunk = gcls_chunk(clf->n, d.H);
-    if (int rc = gcls_prepare(clf, h, learn, gs.n_steps)) return rc;
+    const int chunk = gcls_chunk(clf->n, d.H);      // (one stream: HTM_CLASSIFIER_CHUNK)
+    if (int rc = cls_prepare(clf, h, learn, gs.n_steps, bank)) return rc;
     gs.total = clf->total;
     const GClsDev gd = gcls_of(clf);
+    const ClsStep one{gs.pairs, gs.pairs_per_step, gs.targets, gs.reset_bits, gs.n_targets, gs.first_step, gs.best, gs.dist, gs.total};
     if (learn) {
         const dim3 grid(cls_blocks(d.max_pairs), clf->n * d.H);
         for (int i = 0; i < gs.n_steps; ++i) {
-            LAUNCH_ON(h, s, 0, "classifiers:sum", kgcls_sum, grid, HTM_CLASSIFIER_THREADS, gd, gs, i);
-            LAUNCH_ON(h, s, 0, "classifiers:apply", kgcls_apply, grid, HTM_CLASSIFIER_THREADS, gd, gs, i);
+            if (bank) {
+                LAUNCH_ON(h, s, 0, "classifiers:sum", kgcls_sum, grid, HTM_CLASSIFIER_THREADS, gd, gs, i);
+                LAUNCH_ON(h, s, 0, "classifiers:apply", kgcls_apply, grid, HTM_CLASSIFIER_THREADS, gd, gs, i);
+            } else {
+                LAUNCH_ON(h, s, 0, "classifier:sum", kcls_sum, grid, HTM_CLASSIFIER_THREADS, d, one, i);
+                LAUNCH_ON(h, s, 0, "classifier:apply", kcls_apply, grid, HTM_CLASSIFIER_THREADS, d, one, i);
+            }
         }
     } else {
         for (int first = 0; first < gs.n_steps; first += chunk) {
             const int n = std::min<int>(chunk, gs.n_steps - first);
-            LAUNCH_ON(h, s, 0, "classifiers:frozen", kgcls_frozen, dim3(cls_blocks(gs.pairs_per_step), clf->n * n * d.H), HTM_CLASSIFIER_THREADS, gd, clf->frozen, gs,
-                      first, n);
+            const dim3 grid(cls_blocks(gs.pairs_per_step), clf->n * n * d.H);
+            if (bank) LAUNCH_ON(h, s, 0, "classifiers:frozen", kgcls_frozen, grid, HTM_CLASSIFIER_THREADS, gd, clf->frozen, gs, first, n);
+            else LAUNCH_ON(h, s, 0, "classifier:frozen", kcls_frozen, grid, HTM_CLASSIFIER_THREADS, d, clf->frozen, one, first, n);
         }
     }
     clf->total += gs.n_steps;
     return 0;
 }
 
-extern "C" int htm_classifiers_update(htm_classifier *clf, htm_handle *h, const void *const *device_pairs, int32_t pairs_per_step, int32_t n_steps,
-                                      const int32_t *const *device_targets, int32_t n_targets, int32_t first_step, const uint32_t *const *device_reset_bits,
-                                      int32_t learn, int32_t *device_best, int32_t *device_dist) {
-    if (int rc = cls_check("htm_classifiers_update", clf, h)) return rc;
-    if (!device_pairs || !device_targets || !device_best) return cls_refuse(h, "htm_classifiers_update: null pairs, targets or output", HTM_ERR_ARGUMENT);
+// the inputs per stream: tables of n device pointers (reset bits: or null)
+static int cls_update(const char *what, bool bank, htm_classifier *clf, htm_handle *h, const void *const *device_pairs, int32_t pairs_per_step, int32_t n_steps,
+                      const int32_t *const *device_targets, int32_t n_targets, int32_t first_step, const uint32_t *const *device_reset_bits, int32_t learn,
+                      int32_t *device_best, int32_t *device_dist) {
+    if (int rc = cls_door(what, bank, clf, h)) return rc;
+    const std::string w = std::string(what) + ": ";
+    if (!device_pairs || !device_targets || !device_best) return cls_refuse(h, w + "null pairs, targets or output", HTM_ERR_ARGUMENT);
     const ClsDev &d = clf->d;
     const size_t n = (size_t)clf->n;
     for (size_t i = 0; i < n; ++i)
         if (!device_pairs[i] || !device_targets[i] || (device_reset_bits && !device_reset_bits[i]))
-            return cls_refuse(h, "htm_classifiers_update: stream " + std::to_string(i) + " has no pairs, targets or reset bits", HTM_ERR_ARGUMENT);
+            return cls_refuse(h, w + "stream " + std::to_string(i) + " has no pairs, targets or reset bits", HTM_ERR_ARGUMENT);
     if (pairs_per_step < 1 || pairs_per_step > d.max_pairs)
-        return cls_refuse(h, "htm_classifiers_update: pairs_per_step must be in [1, max_pairs = " + std::to_string(d.max_pairs) + "]", HTM_ERR_ARGUMENT);
-    if (n_steps < 0 || n_targets < 1 || first_step < 0) return cls_refuse(h, "htm_classifiers_update: n_steps >= 0, n_targets >= 1, first_step >= 0", HTM_ERR_ARGUMENT);
-    if (learn && clf->shares)
-        return cls_refuse(h, "htm_classifiers_update: the streams read another object's weight table: learn must be 0", HTM_ERR_STATE);
+        return cls_refuse(h, w + "pairs_per_step must be in [1, max_pairs = " + std::to_string(d.max_pairs) + "]", HTM_ERR_ARGUMENT);
+    if (n_steps < 0 || n_targets < 1 || first_step < 0) return cls_refuse(h, w + "n_steps >= 0, n_targets >= 1, first_step >= 0", HTM_ERR_ARGUMENT);
+    // (an empty call that would learn on another object's table: refused through the bank's door, nothing through the one-stream door)
+    if (learn && clf->shares && (bank || n_steps > 0)) return cls_refuse(h, w + "the streams read another object's weight table: learn must be 0", HTM_ERR_STATE);
     if (n_steps == 0) return HTM_OK;
     HIPCHK(h, hipSetDevice(clf->device));
-    GClsStep gs;
-    memset(&gs, 0, sizeof(gs));
+    GClsStep gs{};
     if (n > 1) {
         // the one copy of the pointer table, from the call's own (pageable) words: the copy has read them when it returns (htm_likelihood_update)
         std::vector<const void *> tab(3 * n, nullptr);
@@ -4597,18 +4507,28 @@ extern "C" int htm_classifiers_update(htm_classifier *clf, htm_handle *h, const 
         gs.targets = device_targets[0];
         gs.reset_bits = device_reset_bits ? device_reset_bits[0] : nullptr;
     }
-    gs.pairs_per_step = pairs_per_step;
-    gs.n_targets = n_targets;
-    gs.first_step = first_step;
-    gs.n_steps = n_steps;
-    gs.best = device_best;
-    gs.dist = device_dist;
-    if (int rc = gcls_enqueue(clf, h, h->stream, gs, learn)) return rc;
+    gs.pairs_per_step = pairs_per_step; gs.n_targets = n_targets; gs.first_step = first_step; gs.n_steps = n_steps;
+    gs.best = device_best; gs.dist = device_dist;
+    if (int rc = cls_enqueue(clf, h, h->stream, gs, learn, bank)) return rc;
     return launch_status(h->err);
 }
 
-extern "C" int htm_classifiers_reset(htm_classifier *clf, htm_handle *h, const uint8_t *streams) {
-    if (int rc = cls_check("htm_classifiers_reset", clf, h)) return rc;
+extern "C" int htm_classifier_update(htm_classifier *clf, htm_handle *h, const void *device_pairs, int32_t pairs_per_step, int32_t n_steps,
+                                     const int32_t *device_targets, int32_t n_targets, int32_t first_step, const uint32_t *device_reset_bits,
+                                     int32_t learn, int32_t *device_best, int32_t *device_dist) {
+    return cls_update("htm_classifier_update", false, clf, h, &device_pairs, pairs_per_step, n_steps, &device_targets, n_targets, first_step,
+                      device_reset_bits ? &device_reset_bits : nullptr, learn, device_best, device_dist);
+}
+extern "C" int htm_classifiers_update(htm_classifier *clf, htm_handle *h, const void *const *device_pairs, int32_t pairs_per_step, int32_t n_steps,
+                                      const int32_t *const *device_targets, int32_t n_targets, int32_t first_step, const uint32_t *const *device_reset_bits,
+                                      int32_t learn, int32_t *device_best, int32_t *device_dist) {
+    return cls_update("htm_classifiers_update", true, clf, h, device_pairs, pairs_per_step, n_steps, device_targets, n_targets, first_step, device_reset_bits, learn,
+                      device_best, device_dist);
+}
+
+// the histories of the streams that `streams` names emptied (null: every stream's)
+static int cls_reset(const char *what, bool bank, htm_classifier *clf, htm_handle *h, const uint8_t *streams) {
+    if (int rc = cls_door(what, bank, clf, h)) return rc;
     HIPCHK(h, hipSetDevice(clf->device));
     if (!streams || clf->n == 1) {
         if (!streams || streams[0]) HIPCHK(h, hipMemsetAsync(clf->d.count, 0, (size_t)clf->n * 8, h->stream));
@@ -4621,76 +4541,88 @@ extern "C" int htm_classifiers_reset(htm_classifier *clf, htm_handle *h, const u
     return launch_status(h->err);
 }
 
-// the rows of one stream's, one horizon's table a weights call names, or a refusal -> the first of them through *rows
-static int gcls_rows(const char *what, htm_classifier *clf, htm_handle *h, int32_t stream, int32_t horizon, int32_t unit0, int32_t n_units, const void *host,
-                     int32_t **rows) {
-    if (int rc = cls_check(what, clf, h)) return rc;
+extern "C" int htm_classifier_reset(htm_classifier *clf, htm_handle *h) { return cls_reset("htm_classifier_reset", false, clf, h, nullptr); }
+extern "C" int htm_classifiers_reset(htm_classifier *clf, htm_handle *h, const uint8_t *streams) { return cls_reset("htm_classifiers_reset", true, clf, h, streams); }
+
+// The rows [unit0, unit0 + n_units) of one stream's, one horizon's table copied to the host (write == 0) or from it; host rows are B
+// words, device rows B_pad.  (The padding buckets of a row stay 0: nothing ever writes them.)
+static int cls_weights(const char *what, bool bank, bool write, htm_classifier *clf, htm_handle *h, int32_t stream, int32_t horizon, int32_t unit0, int32_t n_units,
+                       int32_t *host) {
+    if (int rc = cls_door(what, bank, clf, h)) return rc;
     const ClsDev &d = clf->d;
     const int64_t units = d.w_stride / d.B_pad;
     if (!host || stream < 0 || stream >= clf->n || horizon < 0 || horizon >= d.H || unit0 < 0 || n_units < 0 || (int64_t)unit0 + n_units > units)
         return cls_refuse(h, std::string(what) + ": need host memory, a stream below n_streams, a horizon index below n_steps and rows inside the table", HTM_ERR_ARGUMENT);
-    *rows = d.w + (int64_t)stream * gcls_of(clf).w_member + (int64_t)horizon * d.w_stride + (int64_t)unit0 * d.B_pad;
-    return 0;
+    if (write && clf->shares) return cls_refuse(h, std::string(what) + ": the object reads another object's weights: write them there", HTM_ERR_STATE);
+    for (size_t i = 0; write && i < (size_t)n_units * d.B; ++i)
+        if (host[i] > HTM_CLASSIFIER_W_LIMIT || host[i] < -HTM_CLASSIFIER_W_LIMIT)
+            return cls_refuse(h, std::string(what) + ": a weight is outside [-2^30, 2^30]", HTM_ERR_ARGUMENT);
+    if (n_units == 0) return HTM_OK;
+    int32_t *rows = d.w + (int64_t)stream * gcls_of(clf).w_member + (int64_t)horizon * d.w_stride + (int64_t)unit0 * d.B_pad;
+    const size_t host_pitch = (size_t)d.B * 4, dev_pitch = (size_t)d.B_pad * 4;
+    HIPCHK(h, hipSetDevice(clf->device));
+    if (write) HIPCHK(h, hipMemcpy2DAsync(rows, dev_pitch, host, host_pitch, host_pitch, (size_t)n_units, hipMemcpyHostToDevice, h->stream));
+    else HIPCHK(h, hipMemcpy2DAsync(host, host_pitch, rows, dev_pitch, host_pitch, (size_t)n_units, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return HTM_OK;
 }
 
+extern "C" int htm_classifier_read_weights(htm_classifier *clf, htm_handle *h, int32_t horizon, int32_t unit0, int32_t n_units, int32_t *host_dst) {
+    return cls_weights("htm_classifier_read_weights", false, false, clf, h, 0, horizon, unit0, n_units, host_dst);
+}
+extern "C" int htm_classifier_write_weights(htm_classifier *clf, htm_handle *h, int32_t horizon, int32_t unit0, int32_t n_units, const int32_t *host_src) {
+    return cls_weights("htm_classifier_write_weights", false, true, clf, h, 0, horizon, unit0, n_units, (int32_t *)host_src);
+}
 extern "C" int htm_classifiers_read_weights(htm_classifier *clf, htm_handle *h, int32_t stream, int32_t horizon, int32_t unit0, int32_t n_units, int32_t *host_dst) {
-    int32_t *rows = nullptr;
-    if (int rc = gcls_rows("htm_classifiers_read_weights", clf, h, stream, horizon, unit0, n_units, host_dst, &rows)) return rc;
-    if (n_units == 0) return HTM_OK;
-    const ClsDev &d = clf->d;
+    return cls_weights("htm_classifiers_read_weights", true, false, clf, h, stream, horizon, unit0, n_units, host_dst);
+}
+extern "C" int htm_classifiers_write_weights(htm_classifier *clf, htm_handle *h, int32_t stream, int32_t horizon, int32_t unit0, int32_t n_units, const int32_t *host_src) {
+    return cls_weights("htm_classifiers_write_weights", true, true, clf, h, stream, horizon, unit0, n_units, (int32_t *)host_src);
+}
+
+// The state of n streams: int64 total; int64 count[n]; the rings [n][ring_len][max_pairs] -- at n = 1 the (total, count, ring) of the
+// one-stream door.  The size calls have no handle to refuse through: the one-stream one gives one stream's size for any object.
+static int64_t cls_state_bytes(const htm_classifier *clf, size_t n) { return clf ? (int64_t)(8 + n * 8 + n * clf->ring_bytes) : (int64_t)HTM_ERR_ARGUMENT; }
+
+extern "C" int64_t htm_classifier_state_bytes(const htm_classifier *clf) { return cls_state_bytes(clf, 1); }
+extern "C" int64_t htm_classifiers_state_bytes(const htm_classifier *clf) { return cls_state_bytes(clf, clf ? (size_t)clf->n : 1); }
+
+// the state copied to the host blob (load == 0) or from it, behind everything enqueued on h's stream
+static int cls_state(const char *what, bool bank, bool load, htm_classifier *clf, htm_handle *h, void *host_state, int64_t bytes) {
+    if (int rc = cls_door(what, bank, clf, h)) return rc;
+    const size_t n = (size_t)clf->n;
+    if (!host_state || bytes != cls_state_bytes(clf, n)) return cls_refuse(h, std::string(what) + ": need host_state of the state_bytes call's bytes", HTM_ERR_ARGUMENT);
+    char *ring = (char *)host_state + (n + 1) * 8;
+    std::vector<int64_t> head(n + 1);               // total, count[n]
+    if (load) memcpy(head.data(), host_state, (n + 1) * 8);
+    for (size_t i = 1; load && i <= n; ++i)         // (a learning step looks count steps back in the ring: never before step 0)
+        if (head[i] < 0 || head[i] > head[0])
+            return cls_refuse(h, std::string(what) + ": need 0 <= count <= total in stream " + std::to_string(i - 1), HTM_ERR_ARGUMENT);
     HIPCHK(h, hipSetDevice(clf->device));
-    HIPCHK(h, hipMemcpy2DAsync(host_dst, (size_t)d.B * 4, rows, (size_t)d.B_pad * 4, (size_t)d.B * 4, (size_t)n_units, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
+    if (load) {
+        HIPCHK(h, hipMemcpy(clf->d.count, head.data() + 1, n * 8, hipMemcpyHostToDevice));
+        HIPCHK(h, hipMemcpy(clf->d.ring, ring, n * clf->ring_bytes, hipMemcpyHostToDevice));
+        clf->total = head[0];
+    } else {
+        memcpy(host_state, &clf->total, 8);
+        HIPCHK(h, hipMemcpy((char *)host_state + 8, clf->d.count, n * 8, hipMemcpyDeviceToHost));
+        HIPCHK(h, hipMemcpy(ring, clf->d.ring, n * clf->ring_bytes, hipMemcpyDeviceToHost));
+    }
     return HTM_OK;
 }
 
-extern "C" int htm_classifiers_write_weights(htm_classifier *clf, htm_handle *h, int32_t stream, int32_t horizon, int32_t unit0, int32_t n_units,
-                                             const int32_t *host_src) {
-    int32_t *rows = nullptr;
-    if (int rc = gcls_rows("htm_classifiers_write_weights", clf, h, stream, horizon, unit0, n_units, host_src, &rows)) return rc;
-    if (clf->shares) return cls_refuse(h, "htm_classifiers_write_weights: the streams read another object's weights: write them there", HTM_ERR_STATE);
-    const ClsDev &d = clf->d;
-    for (size_t i = 0; i < (size_t)n_units * d.B; ++i)
-        if (host_src[i] > HTM_CLASSIFIER_W_LIMIT || host_src[i] < -HTM_CLASSIFIER_W_LIMIT)
-            return cls_refuse(h, "htm_classifiers_write_weights: a weight is outside [-2^30, 2^30]", HTM_ERR_ARGUMENT);
-    if (n_units == 0) return HTM_OK;
-    HIPCHK(h, hipSetDevice(clf->device));
-    HIPCHK(h, hipMemcpy2DAsync(rows, (size_t)d.B_pad * 4, host_src, (size_t)d.B * 4, (size_t)d.B * 4, (size_t)n_units, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    return HTM_OK;
+extern "C" int htm_classifier_export(htm_classifier *clf, htm_handle *h, void *host_state, int64_t bytes) {
+    return cls_state("htm_classifier_export", false, false, clf, h, host_state, bytes);
 }
-
-// the state of a bank: int64 total; int64 count[n]; the rings [n][ring_len][max_pairs]
-extern "C" int64_t htm_classifiers_state_bytes(const htm_classifier *clf) {
-    return clf ? (int64_t)(8 + (size_t)clf->n * 8 + (size_t)clf->n * clf->ring_bytes) : (int64_t)HTM_ERR_ARGUMENT;
+extern "C" int htm_classifier_import(htm_classifier *clf, htm_handle *h, const void *host_state, int64_t bytes) {
+    return cls_state("htm_classifier_import", false, true, clf, h, (void *)host_state, bytes);
 }
-
 extern "C" int htm_classifiers_export(htm_classifier *clf, htm_handle *h, void *host_state, int64_t bytes) {
-    if (int rc = cls_check("htm_classifiers_export", clf, h)) return rc;
-    if (!host_state || bytes != htm_classifiers_state_bytes(clf)) return cls_refuse(h, "htm_classifiers_export: need host_state of htm_classifiers_state_bytes bytes", HTM_ERR_ARGUMENT);
-    const size_t n = (size_t)clf->n;
-    HIPCHK(h, hipSetDevice(clf->device));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    memcpy(host_state, &clf->total, 8);
-    HIPCHK(h, hipMemcpy((char *)host_state + 8, clf->d.count, n * 8, hipMemcpyDeviceToHost));
-    HIPCHK(h, hipMemcpy((char *)host_state + 8 + n * 8, clf->d.ring, n * clf->ring_bytes, hipMemcpyDeviceToHost));
-    return HTM_OK;
+    return cls_state("htm_classifiers_export", true, false, clf, h, host_state, bytes);
 }
-
 extern "C" int htm_classifiers_import(htm_classifier *clf, htm_handle *h, const void *host_state, int64_t bytes) {
-    if (int rc = cls_check("htm_classifiers_import", clf, h)) return rc;
-    if (!host_state || bytes != htm_classifiers_state_bytes(clf)) return cls_refuse(h, "htm_classifiers_import: need host_state of htm_classifiers_state_bytes bytes", HTM_ERR_ARGUMENT);
-    const size_t n = (size_t)clf->n;
-    std::vector<int64_t> head(n + 1);
-    memcpy(head.data(), host_state, (n + 1) * 8);
-    for (size_t i = 1; i <= n; ++i)                 // (a learning step looks count steps back in the ring: never before step 0)
-        if (head[i] < 0 || head[i] > head[0]) return cls_refuse(h, "htm_classifiers_import: need 0 <= count <= total in stream " + std::to_string(i - 1), HTM_ERR_ARGUMENT);
-    HIPCHK(h, hipSetDevice(clf->device));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    HIPCHK(h, hipMemcpy(clf->d.count, head.data() + 1, n * 8, hipMemcpyHostToDevice));
-    HIPCHK(h, hipMemcpy(clf->d.ring, (const char *)host_state + 8 + n * 8, n * clf->ring_bytes, hipMemcpyHostToDevice));
-    clf->total = head[0];
-    return HTM_OK;
+    return cls_state("htm_classifiers_import", true, true, clf, h, (void *)host_state, bytes);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -4824,7 +4756,7 @@ static int live_tick(htm_group *g, const double *values, const htm_scalar_field 
     if (clf) {
         rc = live_alloc_capture(g);
         if (rc) return rc;
-        if (gcls_prepare(clf, h0, cls_learn, 1)) { g->err = h0->err; return HTM_ERR_HIP; }
+        if (cls_prepare(clf, h0, cls_learn, 1)) { g->err = h0->err; return HTM_ERR_HIP; }
     }
     htm_group::Live &lv = g->live;
     const Dev &d = h0->d;
@@ -4912,7 +4844,7 @@ static int live_tick(htm_group *g, const double *values, const htm_scalar_field 
         gs.n_steps = 1;
         gs.best = (int32_t *)(lv.d_out + cls_begin);
         gs.dist = dist ? (int32_t *)(lv.d_out + cls_begin + best_bytes) : nullptr;
-        if (gcls_enqueue(clf, h0, s, gs, cls_learn)) { g->err = h0->err; return HTM_ERR_HIP; }
+        if (cls_enqueue(clf, h0, s, gs, cls_learn)) { g->err = h0->err; return HTM_ERR_HIP; }
     }
     for (htm_handle *h : g->m) {
         h->step_host += 1;

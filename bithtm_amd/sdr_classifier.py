@@ -20,14 +20,43 @@ from .engine import HtmError
 
 
 class _DeviceClassifier:
-    """What a one-stream classifier and a bank of streams have in common: the parameters, the shape of the patterns, the lazy binding
-    to a device (as AnomalyLikelihood binds), the device object's life and the upload of a run's targets.  What depends on the number
-    of streams -- the shapes of targets, outputs and state -- is the subclasses': neither is an instance of the other."""
+    """`streams` classifier streams of one config in one device object: the parameters, the shape of the patterns, the lazy binding to
+    a device (as AnomalyLikelihood binds), the device object's life, and every call, written once over a leading stream axis --
+    targets [streams, n], patterns [streams, T, n], outputs [streams, n, H, ...], state per stream.  SDRClassifierBank is this with
+    its own axis; SDRClassifier is the one stream whose arguments and results come without the axis (_lift puts it on, _drop takes it
+    off) and whose calls go through the one-stream C functions.  Neither is an instance of the other."""
 
     _create_name = None
+    _prefix = None                              # of the C functions the calls go through: htm_classifier_ or htm_classifiers_
+    _single = False                             # the public arrays come without the stream axis
+    streams = 1
+    source = None                               # SDRClassifierBank.shared(): the SDRClassifier whose weights the streams read
 
     def _create(self, engine, cfg, out):
         raise NotImplementedError
+
+    def _pointers(self, a):
+        """A call's device addresses -- one, or a sequence of `streams`; None: none -- as the update's C function takes them."""
+        if self._single:
+            return C.c_void_p(a) if a else None
+        return (C.c_void_p * self.streams)(*[int(x) for x in a]) if a is not None else None
+
+    def _no_shared_learning(self, learning):
+        pass                                    # (SDRClassifierBank.shared() refuses here)
+
+    @property
+    def _axis(self):
+        """The stream axis in the shapes of the public arrays: (streams,), or nothing for the one stream."""
+        return () if self._single else (self.streams,)
+
+    def _lift(self, a):
+        return a[None] if self._single else a
+
+    def _drop(self, a):
+        return a[0] if self._single else a
+
+    def _dims(self, *tail):
+        return "[" + ", ".join(str(x) for x in self._axis + tail) + "]"
 
     def __init__(self, buckets=None, field=None, steps=(1,), alpha=0.001, shape=None):
         if (buckets is None) == (field is None):
@@ -120,6 +149,11 @@ class _DeviceClassifier:
         if rc < 0:
             raise HtmError(f"{what} failed ({rc}): {self.lib.htm_last_error(engine.h).decode()}")
 
+    def _call(self, engine, name, *args):
+        """The C function `name` of this object's set on (object, handle, *args)."""
+        what = self._prefix + name
+        self._check(engine, getattr(self.lib, what)(self._clf, engine.h, *args), what)
+
     def upload_targets(self, engine, targets):
         """int [n] -> the device address of the targets of a run's rows (kept until the next upload)."""
         self._bind(engine)
@@ -128,88 +162,92 @@ class _DeviceClassifier:
         engine._hip_check(self.lib.hipMemcpy(ptr, targets.ctypes.data_as(C.c_void_p), targets.nbytes, L.HIP_MEMCPY_HOST_TO_DEVICE), "hipMemcpy")
         return ptr
 
+    def _weights(self, engine, name, i, h, rows):
+        """read_weights or write_weights over the whole table of stream i's horizon h (the one-stream functions take no stream)."""
+        self._call(engine, name, *(() if self._single else (i,)), h, 0, self.units, rows.ctypes.data_as(C.c_void_p))
 
-class SDRClassifier(_DeviceClassifier):
-    """The classifier of `buckets` buckets (or of an encoder field's: `field`, whose value_of also names the values) for the
-    horizons `steps` with learning rate `alpha`.  The shape of the patterns -- units = column_dim * cell_dim, cell_dim, and the pairs
-    a pattern has at most -- comes from the model of the first run(classifier=), or from `shape=(column_dim, cell_dim, max_pairs)`
-    for stand-alone use.  The object binds to a device lazily, as AnomalyLikelihood does; every update continues where the last one
-    ended, whichever door it came through."""
-
-    _create_name = "htm_classifier_create"
-
-    def _create(self, engine, cfg, out):
-        return self.lib.htm_classifier_create(engine.h, C.byref(cfg), EXP_TABLE.ctypes.data_as(C.c_void_p), C.byref(out))
-
-    # ---- the update behind captured steps (what run() calls; nothing here waits)
+    # ---- the update over device memory (what run() calls; nothing here waits)
     def pairs_buffer(self, engine, n):
-        """The device address of a buffer for n steps' patterns of max_pairs pairs (kept)."""
+        """The device address of a buffer for n steps' patterns of max_pairs pairs of every stream, [streams][n][max_pairs] (kept)."""
         self._bind(engine)
-        return engine.kept_buffer(self._bufs, "pairs", 2 * max(int(n), 1) * self.shape[2], spare=2)
+        return engine.kept_buffer(self._bufs, "pairs", 2 * self.streams * max(int(n), 1) * self.shape[2], spare=2)
 
     def enqueue(self, engine, device_pairs, pairs_per_step, n, device_targets, n_targets, first_step, device_resets, learning, distribution=False):
-        """htm_classifier_update over n steps' patterns in device memory, enqueued on `engine`'s stream -> nothing; read(engine, n,
-        distribution) after the stream's wait gives the results."""
+        """The update over n steps' patterns in device memory, enqueued on `engine`'s stream: device_pairs, device_targets and
+        device_resets (or None) are device addresses, one each (SDRClassifier) or a sequence of `streams` each (a bank) -> nothing;
+        read(engine, n, distribution) after the stream's wait gives the results."""
+        self._no_shared_learning(learning)
         self._bind(engine)
-        n, H = int(n), len(self.steps)
-        best = engine.kept_buffer(self._bufs, "best", max(n, 1) * H * 2, spare=2)
-        dist = engine.kept_buffer(self._bufs, "dist", max(n, 1) * H * self.buckets, spare=2) if distribution else None
-        self._check(engine, self.lib.htm_classifier_update(self._clf, engine.h, C.c_void_p(device_pairs), int(pairs_per_step), n, C.c_void_p(device_targets),
-                                                           int(n_targets), int(first_step), C.c_void_p(device_resets) if device_resets else None,
-                                                           int(bool(learning)), C.c_void_p(best), C.c_void_p(dist) if dist else None),
-                    "htm_classifier_update")
+        n, H, S = int(n), len(self.steps), self.streams
+        best = engine.kept_buffer(self._bufs, "best", S * max(n, 1) * H * 2, spare=2)
+        dist = engine.kept_buffer(self._bufs, "dist", S * max(n, 1) * H * self.buckets, spare=2) if distribution else None
+        self._call(engine, "update", self._pointers(device_pairs), int(pairs_per_step), n, self._pointers(device_targets), int(n_targets), int(first_step),
+                   self._pointers(device_resets), int(bool(learning)), C.c_void_p(best), C.c_void_p(dist) if dist else None)
 
     def read(self, engine, n, distribution=False):
-        """(best int32 [n, H, 2], dist int32 [n, H, buckets] or None) of the last enqueue, after the engine's stream has been waited for."""
-        n, H = int(n), len(self.steps)
-        best = engine.read_words(self._bufs["best"][0], n * H * 2, np.int32).reshape(n, H, 2)
-        dist = engine.read_words(self._bufs["dist"][0], n * H * self.buckets, np.int32).reshape(n, H, self.buckets) if distribution else None
-        return best, dist
+        """(best int32 [streams, n, H, 2], dist int32 [streams, n, H, buckets] or None) of the last enqueue, after the engine's stream
+        has been waited for (SDRClassifier: without the stream axis)."""
+        n, H, S = int(n), len(self.steps), self.streams
+        best = engine.read_words(self._bufs["best"][0], S * n * H * 2, np.int32).reshape(S, n, H, 2)
+        dist = engine.read_words(self._bufs["dist"][0], S * n * H * self.buckets, np.int32).reshape(S, n, H, self.buckets) if distribution else None
+        return self._drop(best), (self._drop(dist) if distribution else None)
 
     def check_targets(self, targets):
-        """int [n] -> int32 [n]: -1 (any negative value) is missing; ValueError for a bucket at or above `buckets`."""
+        """int [streams, n] (SDRClassifier: [n]) -> int32: -1 (any negative value) is missing; ValueError for a bucket at or above
+        `buckets`."""
         t = np.asarray(targets)
-        if t.ndim != 1 or t.dtype.kind not in "iu":
-            raise ValueError(f"targets: int [n], got {t.dtype} {list(t.shape)}")
+        if t.ndim != (1 if self._single else 2) or self._lift(t).shape[0] != self.streams or t.dtype.kind not in "iu":
+            raise ValueError(f"targets: int {self._dims('n')}, got {t.dtype} {list(t.shape)}")
         if t.size and int(t.max()) >= self.buckets:
             raise ValueError(f"targets: bucket {int(t.max())} is at or above buckets = {self.buckets}")
-        return np.where(t < 0, -1, t).astype(np.int32)
+        return np.ascontiguousarray(np.where(t < 0, -1, t).astype(np.int32))
 
     # ---- the stand-alone door
     def update_patterns(self, index, words, targets, learning=True, resets=None, device=None, distribution=True):
-        """T further steps from their patterns: index int [T, n], words uint32 [T, n] (pair j of step t is (index[t, j], words[t, j]);
-        a negative index or a zero word contributes nothing), targets int [T] (-1: missing), resets bool [T] or None.  Checked here:
-        the indices of a step are distinct and inside the table, no word has a bit at or above cell_dim, n <= max_pairs.  ->
-        (best int32 [T, H, 2] as (bucket, p in units of 2^-16), dist int32 [T, H, buckets] or None)."""
+        """T further steps of every stream from their patterns: index int [streams, T, n], words uint32 [streams, T, n] (pair j of step
+        t is (index[.., t, j], words[.., t, j]); a negative index or a zero word contributes nothing), targets int [streams, T] (-1:
+        missing), resets bool [streams, T] or None; SDRClassifier: all without the stream axis.  Checked here: the indices of a step
+        are distinct and inside the table, no word has a bit at or above cell_dim, n <= max_pairs.  -> (best int32 [streams, T, H, 2]
+        as (bucket, p in units of 2^-16), dist int32 [streams, T, H, buckets] or None)."""
+        self._no_shared_learning(learning)
         if self.shape is None:
-            raise RuntimeError("the classifier does not know the shape of its patterns yet: use it with a model, or give SDRClassifier(shape=)")
-        index, words = check_patterns(index, words, self.units, self.shape[1])
-        T, n = index.shape
+            raise RuntimeError(f"the classifier does not know the shape of its patterns yet: use it with a model, or give {type(self).__name__}(shape=)")
+        index, words = np.asarray(index), np.asarray(words)
+        S = self.streams
+        if not self._single and (index.ndim != 3 or index.shape[0] != S or words.shape != index.shape):
+            raise ValueError(f"patterns: index int [{S}, T, n] and words uint32 [{S}, T, n], got {list(index.shape)} and {list(words.shape)}")
+        checked = [check_patterns(i, w, self.units, self.shape[1]) for i, w in zip(self._lift(index), self._lift(words))]
+        index, words = np.stack([c[0] for c in checked]), np.stack([c[1] for c in checked])
+        _, T, n = index.shape
         if not 1 <= n <= self.shape[2]:
             raise ValueError(f"patterns: 1 to max_pairs = {self.shape[2]} pairs per step, got {n}")
-        targets = self.check_targets(targets)
-        if targets.shape != (T,):
-            raise ValueError(f"targets: int [{T}], got {list(targets.shape)}")
+        targets = self._lift(self.check_targets(targets))
+        if targets.shape != (S, T):
+            raise ValueError(f"targets: int {self._dims(T)}, got {list(self._drop(targets).shape)}")
         if resets is not None:
-            resets = np.asarray(resets, dtype=np.bool_).ravel()
-            if resets.shape != (T,):
-                raise ValueError(f"resets: bool [{T}], got {list(resets.shape)}")
+            resets = np.asarray(resets, dtype=np.bool_)
+            resets = self._lift(resets.ravel() if self._single else resets)
+            if resets.shape != (S, T):
+                raise ValueError(f"resets: bool {self._dims(T)}, got {list(self._drop(resets).shape)}")
         H = len(self.steps)
         if T == 0:
-            return np.zeros((0, H, 2), np.int32), (np.zeros((0, H, self.buckets), np.int32) if distribution else None)
+            return self._drop(np.zeros((S, 0, H, 2), np.int32)), (self._drop(np.zeros((S, 0, H, self.buckets), np.int32)) if distribution else None)
         engine = self._engine(device)
-        pairs = np.empty((T, n, 2), dtype=np.int32)
-        pairs[:, :, 0], pairs[:, :, 1] = index, words.view(np.int32)
+        pairs = np.empty((S, T, n, 2), dtype=np.int32)
+        pairs[..., 0], pairs[..., 1] = index, words.view(np.int32)
         buf = engine.device_buffer(pairs.nbytes, pairs)
         tbuf = engine.device_buffer(targets.nbytes, targets)
-        rbuf = None
+        rbuf, rtab = None, None
         try:
             if resets is not None:
-                bits = np.zeros((T + 31) // 32 * 4, dtype=np.uint8)
-                pb = np.packbits(resets, bitorder="little")
-                bits[:pb.size] = pb
+                row = (T + 31) // 32 * 4
+                bits = np.zeros((S, row), dtype=np.uint8)
+                pb = np.packbits(resets, axis=1, bitorder="little")
+                bits[:, :pb.shape[1]] = pb
                 rbuf = engine.device_buffer(bits.nbytes, bits)
-            self.enqueue(engine, buf, n, T, tbuf, T, 0, rbuf, learning, distribution)
+                rtab = self._drop([rbuf + i * row for i in range(S)])
+            self.enqueue(engine, self._drop([buf + i * T * n * 8 for i in range(S)]), n, T, self._drop([tbuf + i * T * 4 for i in range(S)]), T, 0, rtab, learning,
+                         distribution)
             engine.sync()
             best, dist = self.read(engine, T, distribution)
             return best.copy(), (dist.copy() if dist is not None else None)
@@ -219,78 +257,117 @@ class SDRClassifier(_DeviceClassifier):
                 if p:
                     self.lib.hipFree(p)
 
-    # ---- reset, state
-    def reset(self):
-        """Empty the history: the next steps learn nothing from the patterns before them (the weights stay)."""
+    # ---- reset, state: kept with the stream axis (count [streams], ring [streams, ...], weights [tables, ...]), also while pending
+    def _reset(self, flags, *args):
+        """Empty the history of every stream, or of those `flags` (bool [streams]) names; args: what the C call takes for them."""
         if self._clf is None:
             if self._pending is not None:
-                self._pending["count"] = np.int64(0)
+                self._pending["count"] = np.where(flags, 0, self._pending["count"]) if flags is not None else np.zeros(self.streams, np.int64)
             return
-        engine = self._engine()
-        self._check(engine, self.lib.htm_classifier_reset(self._clf, engine.h), "htm_classifier_reset")
+        self._call(self._engine(), "reset", *args)
+
+    @property
+    def _tables(self):
+        """Weight tables a state holds: one per stream, or the owner's one."""
+        return 1 if self.source is not None else self.streams
 
     def _empty_state(self):
-        ring = np.zeros((self.ring_len, self.shape[2], 2), dtype=np.int32)
-        ring[:, :, 0] = -1
-        return dict(total=np.int64(0), count=np.int64(0), ring=ring, weights=np.zeros((len(self.steps), self.units, self.buckets), np.int32))
+        ring = np.zeros((self.streams, self.ring_len, self.shape[2], 2), dtype=np.int32)
+        ring[..., 0] = -1
+        return dict(total=np.int64(0), count=np.zeros(self.streams, np.int64), ring=ring,
+                    weights=np.zeros((self._tables, len(self.steps), self.units, self.buckets), np.int32))
+
+    def _params(self):
+        return self._axis + (self.buckets, self.alpha_q) + (self.shape or ()) + self.steps
 
     def state_dict(self):
-        """{"params": int64 [buckets, alpha_q, column_dim, cell_dim, max_pairs, steps...], "total", "count": int64, "ring": int32
-        [ring_len, max_pairs, 2], "weights": int32 [H, units, buckets]} -- the whole state, read from the device.  Dense: H x units x
-        buckets x 4 bytes of host memory (16 MiB per horizon at 2 048 x 32 units and 64 buckets): meant for small models."""
+        """{"params": int64 [streams, buckets, alpha_q, column_dim, cell_dim, max_pairs, steps...], "total": int64, "count": int64
+        [streams], "ring": int32 [streams, ring_len, max_pairs, 2], "weights": int32 [streams, H, units, buckets]} -- the whole state,
+        read from the device (shared(): "weights" is the owner's table, once: [1, H, units, buckets]; SDRClassifier: no streams in
+        "params" and no stream axis, "count" one int64).  Dense: H x units x buckets x 4 bytes of host memory per table (16 MiB per
+        horizon at 2 048 x 32 units and 64 buckets): meant for small models."""
         if self.shape is None:
             raise RuntimeError("the classifier does not know the shape of its patterns yet")
-        params = np.asarray((self.buckets, self.alpha_q) + self.shape + self.steps, dtype=np.int64)
+        if self._clf is None and self.source is not None:          # (the weights are the owner's, on its device: bound through its engine)
+            self._engine()
         if self._clf is None:
             state = self._pending if self._pending is not None else self._empty_state()
-            return dict({k: np.array(v) for k, v in state.items()}, params=params)
-        engine = self._engine()
-        size = 16 + self.ring_len * self.shape[2] * 8
-        assert size == self.lib.htm_classifier_state_bytes(self._clf)
-        blob = np.zeros(size, dtype=np.uint8)
-        self._check(engine, self.lib.htm_classifier_export(self._clf, engine.h, blob.ctypes.data_as(C.c_void_p), size), "htm_classifier_export")
-        head = blob[:16].view(np.int64)
-        weights = np.zeros((len(self.steps), self.units, self.buckets), dtype=np.int32)
-        for h in range(len(self.steps)):
-            self._check(engine, self.lib.htm_classifier_read_weights(self._clf, engine.h, h, 0, self.units, weights[h].ctypes.data_as(C.c_void_p)),
-                        "htm_classifier_read_weights")
-        return dict(params=params, total=np.int64(head[0]), count=np.int64(head[1]),
-                    ring=blob[16:].view(np.int32).reshape(self.ring_len, self.shape[2], 2).copy(), weights=weights)
+        else:
+            engine = self._engine()
+            S, H = self.streams, len(self.steps)
+            size = 8 + S * 8 + S * self.ring_len * self.shape[2] * 8
+            assert size == getattr(self.lib, self._prefix + "state_bytes")(self._clf)
+            blob = np.zeros(size, dtype=np.uint8)
+            self._call(engine, "export", blob.ctypes.data_as(C.c_void_p), size)
+            head = blob[:8 + S * 8].view(np.int64)
+            weights = np.zeros((self._tables, H, self.units, self.buckets), dtype=np.int32)
+            for i in range(self._tables):
+                for h in range(H):
+                    self._weights(engine, "read_weights", i, h, weights[i, h])
+            state = dict(total=np.int64(head[0]), count=head[1:], ring=blob[8 + S * 8:].view(np.int32).reshape(S, self.ring_len, self.shape[2], 2), weights=weights)
+        out = {k: np.array(v if k == "total" else self._drop(v))[()] for k, v in state.items()}       # (copies; [()]: a scalar of a 0-d array)
+        return dict(out, params=np.asarray(self._params(), dtype=np.int64))
 
     def load_state_dict(self, state):
-        """The state of a state_dict() of an object with the same parameters and shape."""
+        """The state of a state_dict() of an object with the same parameters and shape (shared(): the weights are the owner's and are
+        not written)."""
         params = tuple(int(x) for x in state["params"])
-        if self.shape is None and len(params) == 5 + len(self.steps):
-            self._set_shape(*params[2:5])
-        mine = (self.buckets, self.alpha_q) + (self.shape or ()) + self.steps
-        if params != mine:
-            raise ValueError(f"the state was saved with parameters {params} (buckets, alpha_q, column_dim, cell_dim, max_pairs, steps...), this object has {mine}")
-        total, count = int(state["total"]), int(state["count"])
-        if not 0 <= count <= total:
-            raise ValueError(f"state: 0 <= count <= total, got count {count}, total {total}")
-        ring = np.ascontiguousarray(state["ring"], dtype=np.int32)
-        weights = np.ascontiguousarray(state["weights"], dtype=np.int32)
-        if ring.shape != (self.ring_len, self.shape[2], 2):
-            raise ValueError(f"state['ring']: int32 {[self.ring_len, self.shape[2], 2]}, got {list(ring.shape)}")
-        if weights.shape != (len(self.steps), self.units, self.buckets):
-            raise ValueError(f"state['weights']: int32 {[len(self.steps), self.units, self.buckets]}, got {list(weights.shape)}")
+        at = 2 if self._single else 3
+        if self.shape is None and len(params) == at + 3 + len(self.steps):
+            self._set_shape(*params[at:at + 3])
+        if params != self._params():
+            raise ValueError(f"the state was saved with parameters {params} ({'' if self._single else 'streams, '}buckets, alpha_q, column_dim, cell_dim, max_pairs, "
+                             f"steps...), this object has {self._params()}")
+        S, tables = self.streams, self._tables
+        total = int(state["total"])
+        count = self._lift(np.asarray(state["count"], dtype=np.int64))
+        if count.shape != (S,) or (count < 0).any() or (count > total).any():
+            raise ValueError(f"state: count int64 {self._dims()} with 0 <= count <= total, got {count.tolist()}, total {total}")
+        ring = self._lift(np.ascontiguousarray(state["ring"], dtype=np.int32))
+        weights = self._lift(np.ascontiguousarray(state["weights"], dtype=np.int32))
+        for name, a, want in (("ring", ring, (S, self.ring_len, self.shape[2], 2)), ("weights", weights, (tables, len(self.steps), self.units, self.buckets))):
+            if a.shape != want:
+                raise ValueError(f"state['{name}']: int32 {list(want[self._single:])}, got {list(self._drop(a).shape)}")
         if weights.size and (weights.max() > W_LIMIT or weights.min() < -W_LIMIT):
             raise ValueError("state['weights']: a weight is outside [-2^30, 2^30]")
-        clean = dict(total=np.int64(total), count=np.int64(count), ring=ring.copy(), weights=weights.copy())
+        clean = dict(total=np.int64(total), count=count.copy(), ring=ring.copy(), weights=weights.copy())
         if self._clf is None:
             self._pending = clean
         else:
             self._import(self._engine(), clean)
 
     def _import(self, engine, state):
-        blob = np.zeros(16 + state["ring"].nbytes, dtype=np.uint8)
-        blob[:16].view(np.int64)[:] = (state["total"], state["count"])
-        blob[16:] = state["ring"].view(np.uint8).ravel()
-        self._check(engine, self.lib.htm_classifier_import(self._clf, engine.h, blob.ctypes.data_as(C.c_void_p), blob.size), "htm_classifier_import")
-        for h in range(len(self.steps)):
-            w = np.ascontiguousarray(state["weights"][h])
-            self._check(engine, self.lib.htm_classifier_write_weights(self._clf, engine.h, h, 0, self.units, w.ctypes.data_as(C.c_void_p)),
-                        "htm_classifier_write_weights")
+        S = self.streams
+        blob = np.zeros(8 + S * 8 + state["ring"].nbytes, dtype=np.uint8)
+        head = blob[:8 + S * 8].view(np.int64)
+        head[0], head[1:] = state["total"], state["count"]
+        blob[8 + S * 8:] = state["ring"].view(np.uint8).ravel()
+        self._call(engine, "import", blob.ctypes.data_as(C.c_void_p), blob.size)
+        if self.source is not None:
+            return
+        for i in range(S):
+            for h in range(len(self.steps)):
+                self._weights(engine, "write_weights", i, h, np.ascontiguousarray(state["weights"][i, h]))
+
+
+class SDRClassifier(_DeviceClassifier):
+    """The classifier of `buckets` buckets (or of an encoder field's: `field`, whose value_of also names the values) for the
+    horizons `steps` with learning rate `alpha`.  The shape of the patterns -- units = column_dim * cell_dim, cell_dim, and the pairs
+    a pattern has at most -- comes from the model of the first run(classifier=), or from `shape=(column_dim, cell_dim, max_pairs)`
+    for stand-alone use.  The object binds to a device lazily, as AnomalyLikelihood does; every update continues where the last one
+    ended, whichever door it came through.  The calls are _DeviceClassifier's for one stream, without the stream axis: targets int
+    [n], patterns [T, n], best [n, H, 2], a state of "count": int64 and "ring": int32 [ring_len, max_pairs, 2]."""
+
+    _create_name = "htm_classifier_create"
+    _prefix = "htm_classifier_"
+    _single = True
+
+    def _create(self, engine, cfg, out):
+        return self.lib.htm_classifier_create(engine.h, C.byref(cfg), EXP_TABLE.ctypes.data_as(C.c_void_p), C.byref(out))
+
+    def reset(self):
+        """Empty the history: the next steps learn nothing from the patterns before them (the weights stay)."""
+        self._reset(None)
 
 
 class SDRClassifierBank(_DeviceClassifier):
@@ -305,13 +382,16 @@ class SDRClassifierBank(_DeviceClassifier):
     Memory: streams x the one-stream object's, except shared(), which adds only rings, counts and accumulators."""
 
     _create_name = "htm_classifiers_create"
+    _prefix = "htm_classifiers_"
 
     def __init__(self, streams, buckets=None, field=None, steps=(1,), alpha=0.001, shape=None):
         super().__init__(buckets=buckets, field=field, steps=steps, alpha=alpha, shape=shape)
+        self._set_streams(streams)
+
+    def _set_streams(self, streams):
         self.streams = int(streams)
         if not 1 <= self.streams <= 65535 // len(self.steps):
             raise ValueError(f"SDRClassifierBank: streams must be in [1, 65535 // len(steps) = {65535 // len(self.steps)}], got {streams}")
-        self.source = None                      # shared(): the SDRClassifier whose weights the streams read
 
     @classmethod
     def shared(cls, clf, streams):
@@ -325,9 +405,7 @@ class SDRClassifierBank(_DeviceClassifier):
         bank = cls.__new__(cls)
         _DeviceClassifier.__init__(bank, buckets=clf.buckets, steps=clf.steps, shape=clf.shape)
         bank.field, bank.alpha_q = clf.field, clf.alpha_q
-        bank.streams = int(streams)
-        if not 1 <= bank.streams <= 65535 // len(bank.steps):
-            raise ValueError(f"SDRClassifierBank: streams must be in [1, 65535 // len(steps) = {65535 // len(bank.steps)}], got {streams}")
+        bank._set_streams(streams)
         bank.source = clf
         bank._last = clf._last                  # (its calls go through the engine clf's last call came through, until a model brings its own)
         return bank
@@ -351,94 +429,6 @@ class SDRClassifierBank(_DeviceClassifier):
         if learning and self.source is not None:
             raise ValueError("SDRClassifierBank.shared(): the streams read one weight table -- learning is refused (the owner learns through its own calls)")
 
-    # ---- the update over device memory (nothing here waits)
-    def pairs_buffer(self, engine, n):
-        """The device address of a buffer for n steps' patterns of max_pairs pairs of every stream, [streams][n][max_pairs] (kept)."""
-        self._bind(engine)
-        return engine.kept_buffer(self._bufs, "pairs", 2 * self.streams * max(int(n), 1) * self.shape[2], spare=2)
-
-    def enqueue(self, engine, device_pairs, pairs_per_step, n, device_targets, n_targets, first_step, device_resets, learning, distribution=False):
-        """htm_classifiers_update over n steps of every stream: device_pairs, device_targets and device_resets (or None) are
-        sequences of `streams` device addresses -> nothing; read(engine, n, distribution) after the stream's wait gives the results."""
-        self._no_shared_learning(learning)
-        self._bind(engine)
-        n, H, S = int(n), len(self.steps), self.streams
-        best = engine.kept_buffer(self._bufs, "best", S * max(n, 1) * H * 2, spare=2)
-        dist = engine.kept_buffer(self._bufs, "dist", S * max(n, 1) * H * self.buckets, spare=2) if distribution else None
-        table = lambda a: (C.c_void_p * S)(*[int(x) for x in a])
-        self._check(engine, self.lib.htm_classifiers_update(self._clf, engine.h, table(device_pairs), int(pairs_per_step), n, table(device_targets), int(n_targets),
-                                                            int(first_step), table(device_resets) if device_resets is not None else None,
-                                                            int(bool(learning)), C.c_void_p(best), C.c_void_p(dist) if dist else None),
-                    "htm_classifiers_update")
-
-    def read(self, engine, n, distribution=False):
-        """(best int32 [streams, n, H, 2], dist int32 [streams, n, H, buckets] or None) of the last enqueue, after the stream's wait."""
-        n, H, S = int(n), len(self.steps), self.streams
-        best = engine.read_words(self._bufs["best"][0], S * n * H * 2, np.int32).reshape(S, n, H, 2)
-        dist = engine.read_words(self._bufs["dist"][0], S * n * H * self.buckets, np.int32).reshape(S, n, H, self.buckets) if distribution else None
-        return best, dist
-
-    def check_targets(self, targets):
-        """int [streams, n] -> int32: -1 (any negative value) is missing; ValueError for a bucket at or above `buckets`."""
-        t = np.asarray(targets)
-        if t.ndim != 2 or t.shape[0] != self.streams or t.dtype.kind not in "iu":
-            raise ValueError(f"targets: int [{self.streams}, n], got {t.dtype} {list(t.shape)}")
-        if t.size and int(t.max()) >= self.buckets:
-            raise ValueError(f"targets: bucket {int(t.max())} is at or above buckets = {self.buckets}")
-        return np.ascontiguousarray(np.where(t < 0, -1, t).astype(np.int32))
-
-    # ---- the stand-alone door
-    def update_patterns(self, index, words, targets, learning=True, resets=None, device=None, distribution=True):
-        """T further steps of every stream: index int [streams, T, n], words uint32 [streams, T, n], targets int [streams, T] (-1:
-        missing), resets bool [streams, T] or None, each stream's as SDRClassifier.update_patterns takes them -> (best int32
-        [streams, T, H, 2], dist int32 [streams, T, H, buckets] or None)."""
-        self._no_shared_learning(learning)
-        if self.shape is None:
-            raise RuntimeError("the classifier does not know the shape of its patterns yet: use it with a model, or give SDRClassifierBank(shape=)")
-        index, words = np.asarray(index), np.asarray(words)
-        S = self.streams
-        if index.ndim != 3 or index.shape[0] != S or words.shape != index.shape:
-            raise ValueError(f"patterns: index int [{S}, T, n] and words uint32 [{S}, T, n], got {list(index.shape)} and {list(words.shape)}")
-        checked = [check_patterns(index[i], words[i], self.units, self.shape[1]) for i in range(S)]
-        index, words = np.stack([c[0] for c in checked]), np.stack([c[1] for c in checked])
-        _, T, n = index.shape
-        if not 1 <= n <= self.shape[2]:
-            raise ValueError(f"patterns: 1 to max_pairs = {self.shape[2]} pairs per step, got {n}")
-        targets = self.check_targets(targets)
-        if targets.shape != (S, T):
-            raise ValueError(f"targets: int [{S}, {T}], got {list(targets.shape)}")
-        if resets is not None:
-            resets = np.asarray(resets, dtype=np.bool_)
-            if resets.shape != (S, T):
-                raise ValueError(f"resets: bool [{S}, {T}], got {list(resets.shape)}")
-        H = len(self.steps)
-        if T == 0:
-            return np.zeros((S, 0, H, 2), np.int32), (np.zeros((S, 0, H, self.buckets), np.int32) if distribution else None)
-        engine = self._engine(device)
-        pairs = np.empty((S, T, n, 2), dtype=np.int32)
-        pairs[..., 0], pairs[..., 1] = index, words.view(np.int32)
-        buf = engine.device_buffer(pairs.nbytes, pairs)
-        tbuf = engine.device_buffer(targets.nbytes, targets)
-        rbuf, rtab = None, None
-        try:
-            if resets is not None:
-                row = (T + 31) // 32 * 4
-                bits = np.zeros((S, row), dtype=np.uint8)
-                pb = np.packbits(resets, axis=1, bitorder="little")
-                bits[:, :pb.shape[1]] = pb
-                rbuf = engine.device_buffer(bits.nbytes, bits)
-                rtab = [rbuf + i * row for i in range(S)]
-            self.enqueue(engine, [buf + i * T * n * 8 for i in range(S)], n, T, [tbuf + i * T * 4 for i in range(S)], T, 0, rtab, learning, distribution)
-            engine.sync()
-            best, dist = self.read(engine, T, distribution)
-            return best.copy(), (dist.copy() if dist is not None else None)
-        finally:
-            engine.sync()
-            for p in (buf, tbuf, rbuf):
-                if p:
-                    self.lib.hipFree(p)
-
-    # ---- reset, state
     def reset(self, streams=None):
         """Empty the history of every stream, or of those `streams` (bool [streams]) names (the weights stay)."""
         flags = None
@@ -446,98 +436,7 @@ class SDRClassifierBank(_DeviceClassifier):
             flags = np.ascontiguousarray(np.asarray(streams, dtype=np.bool_).ravel()).astype(np.uint8)
             if flags.shape != (self.streams,):
                 raise ValueError(f"streams: bool [{self.streams}], got {list(flags.shape)}")
-        if self._clf is None:
-            if self._pending is not None:
-                self._pending["count"] = np.where(flags.astype(bool), 0, self._pending["count"]) if flags is not None else np.zeros(self.streams, np.int64)
-            return
-        engine = self._engine()
-        self._check(engine, self.lib.htm_classifiers_reset(self._clf, engine.h, flags.ctypes.data_as(C.c_void_p) if flags is not None else None),
-                    "htm_classifiers_reset")
-
-    def _empty_state(self):
-        S = self.streams
-        ring = np.zeros((S, self.ring_len, self.shape[2], 2), dtype=np.int32)
-        ring[..., 0] = -1
-        return dict(total=np.int64(0), count=np.zeros(S, np.int64), ring=ring,
-                    weights=np.zeros((self._tables, len(self.steps), self.units, self.buckets), np.int32))
-
-    @property
-    def _tables(self):
-        """Weight tables a state holds: one per stream, or the owner's one."""
-        return 1 if self.source is not None else self.streams
-
-    def state_dict(self):
-        """{"params": int64 [streams, buckets, alpha_q, column_dim, cell_dim, max_pairs, steps...], "total": int64, "count": int64
-        [streams], "ring": int32 [streams, ring_len, max_pairs, 2], "weights": int32 [streams, H, units, buckets]} read from the
-        device (shared(): "weights" is the owner's table, once: [1, H, units, buckets])."""
-        if self.shape is None:
-            raise RuntimeError("the classifier does not know the shape of its patterns yet")
-        S = self.streams
-        params = np.asarray((S, self.buckets, self.alpha_q) + self.shape + self.steps, dtype=np.int64)
-        if self._clf is None and self.source is not None:          # (the weights are the owner's, on its device: bound through its engine)
-            self._engine()
-        if self._clf is None:
-            state = self._pending if self._pending is not None else self._empty_state()
-            return dict({k: np.array(v) for k, v in state.items()}, params=params)
-        engine = self._engine()
-        ring_bytes = self.ring_len * self.shape[2] * 8
-        size = 8 + S * 8 + S * ring_bytes
-        assert size == self.lib.htm_classifiers_state_bytes(self._clf)
-        blob = np.zeros(size, dtype=np.uint8)
-        self._check(engine, self.lib.htm_classifiers_export(self._clf, engine.h, blob.ctypes.data_as(C.c_void_p), size), "htm_classifiers_export")
-        head = blob[:8 + S * 8].view(np.int64)
-        tables = self._tables
-        weights = np.zeros((tables, len(self.steps), self.units, self.buckets), dtype=np.int32)
-        for i in range(tables):
-            for h in range(len(self.steps)):
-                self._check(engine, self.lib.htm_classifiers_read_weights(self._clf, engine.h, i, h, 0, self.units, weights[i, h].ctypes.data_as(C.c_void_p)),
-                            "htm_classifiers_read_weights")
-        return dict(params=params, total=np.int64(head[0]), count=head[1:].copy(),
-                    ring=blob[8 + S * 8:].view(np.int32).reshape(S, self.ring_len, self.shape[2], 2).copy(), weights=weights)
-
-    def load_state_dict(self, state):
-        """The state of a state_dict() of a bank with the same parameters and shape (shared(): the weights are the owner's and are
-        not written)."""
-        params = tuple(int(x) for x in state["params"])
-        if self.shape is None and len(params) == 6 + len(self.steps):
-            self._set_shape(*params[3:6])
-        S = self.streams
-        mine = (S, self.buckets, self.alpha_q) + (self.shape or ()) + self.steps
-        if params != mine:
-            raise ValueError(f"the state was saved with parameters {params} (streams, buckets, alpha_q, column_dim, cell_dim, max_pairs, steps...), this object has {mine}")
-        total = int(state["total"])
-        count = np.ascontiguousarray(state["count"], dtype=np.int64)
-        if count.shape != (S,) or (count < 0).any() or (count > total).any():
-            raise ValueError(f"state: count int64 [{S}] with 0 <= count <= total, got {count.tolist()}, total {total}")
-        ring = np.ascontiguousarray(state["ring"], dtype=np.int32)
-        weights = np.ascontiguousarray(state["weights"], dtype=np.int32)
-        tables = self._tables
-        if ring.shape != (S, self.ring_len, self.shape[2], 2):
-            raise ValueError(f"state['ring']: int32 {[S, self.ring_len, self.shape[2], 2]}, got {list(ring.shape)}")
-        if weights.shape != (tables, len(self.steps), self.units, self.buckets):
-            raise ValueError(f"state['weights']: int32 {[tables, len(self.steps), self.units, self.buckets]}, got {list(weights.shape)}")
-        if weights.size and (weights.max() > W_LIMIT or weights.min() < -W_LIMIT):
-            raise ValueError("state['weights']: a weight is outside [-2^30, 2^30]")
-        clean = dict(total=np.int64(total), count=count.copy(), ring=ring.copy(), weights=weights.copy())
-        if self._clf is None:
-            self._pending = clean
-        else:
-            self._import(self._engine(), clean)
-
-    def _import(self, engine, state):
-        S = self.streams
-        blob = np.zeros(8 + S * 8 + state["ring"].nbytes, dtype=np.uint8)
-        head = blob[:8 + S * 8].view(np.int64)
-        head[0], head[1:] = state["total"], state["count"]
-        blob[8 + S * 8:] = state["ring"].view(np.uint8).ravel()
-        self._check(engine, self.lib.htm_classifiers_import(self._clf, engine.h, blob.ctypes.data_as(C.c_void_p), blob.size), "htm_classifiers_import")
-        if self.source is not None:
-            return
-        for i in range(S):
-            for h in range(len(self.steps)):
-                w = np.ascontiguousarray(state["weights"][i, h])
-                self._check(engine, self.lib.htm_classifiers_write_weights(self._clf, engine.h, i, h, 0, self.units, w.ctypes.data_as(C.c_void_p)),
-                            "htm_classifiers_write_weights")
+        self._reset(flags, flags.ctypes.data_as(C.c_void_p) if flags is not None else None)
 
 
 def model_shape(engine):
