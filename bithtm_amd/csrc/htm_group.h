@@ -59,7 +59,7 @@ __global__ __launch_bounds__(256, BITHTM_MID_ROWS_WAVES) void kgrp_middle(const 
     }
     b -= 1 + n_cls;
     if (b < n_rows) {
-        role_sp_row<256>(d, p, banks[blockIdx.y], n_inputs, 0, b, threadIdx.x);
+        role_sp_row<256, false, true, false>(d, p, banks[blockIdx.y], n_inputs, 0, b, threadIdx.x);     // (HOLD off: the launch's scratch)
         return;
     }
     b -= n_rows;

@@ -183,7 +183,10 @@ __device__ __forceinline__ void shard_bind(const Dev &d, int p, int gid, int cel
 // PLANES: how the wave keeps the row's bytes of the mask's byte planes.  true: the old bytes travel with the pass's row loads
 // (plane_old_byte, plane_diff_store).  false: they are fetched behind the pass's work (plane_diff_store_late: a round trip per
 // pass, no register more) -- k_act_rows: the three-launch schedule does not read the planes, and keeps its registers
-template <int TPR, bool OWN = false, bool PLANES = true>
+// HOLD: the two increments and the threshold sit in registers before the first pass (below).  Not in k_act_rows: 21 registers for
+// the 18 the launch is held to (tests/golden/kernel_resources_before_likelihood.json).  Not in the model groups' middle launch,
+// which sits at 64 registers with 36 bytes of scratch: left as it was, not measured.  Neither is on the two-launch step's path
+template <int TPR, bool OWN = false, bool PLANES = true, bool HOLD = PLANES>
 __device__ __forceinline__ void role_sp_row(const Dev &d, int p, const uint32_t *__restrict__ bank, int n_inputs, int ahead, int ri, int t) {
     ROW_STAMP(0);
     const uint32_t step = ahead ? d.ctr->step[p ^ 1] + 1u : d.ctr->step[p];
@@ -201,6 +204,14 @@ __device__ __forceinline__ void role_sp_row(const Dev &d, int p, const uint32_t 
         wbase = d.ctr->sel_win[p ^ 1];
     }
     int own_cn = 0;
+    // (the increments and the threshold in registers before the first pass, opaque to the compiler: left to it, `bit ? don : doff`
+    // becomes a select of two ADDRESSES and a load behind the row's values -- a dependent cache round trip, and the second element's
+    // is issued only once the first's has arrived: two per pass.  With them the pass is branch-free; the row blocks' median time
+    // in the two-launch step's first launch went from 6.7 to 4.0 us, tools/rows_phases.py)
+    double don = d.sp_don, doff = d.sp_doff, thr = d.sp_thr;
+    if (HOLD) asm volatile("" : "+v"(don), "+v"(doff), "+v"(thr));
+    auto delta = [&](bool on) -> double { return HOLD ? (on ? don : doff) : (on ? d.sp_don : d.sp_doff); };
+    auto connected = [&](double v) -> bool { return HOLD ? v >= thr : v >= d.sp_thr; };
     for (int i0 = 0; i0 < d.Ipad; i0 += 2 * TPR) {
         const int e0 = i0 + 2 * t;                   // Ipad is a multiple of 128: e0 + 1 < Ipad whenever e0 < Ipad
         bool c0 = false, c1 = false;
@@ -219,8 +230,8 @@ __device__ __forceinline__ void role_sp_row(const Dev &d, int p, const uint32_t 
             // (OWN: the coming input's bits of the thread's two elements, asked for with the row -- the lane that stores the mask
             // words fetching the coming input's words once it had them cost every pass a round trip: 1.6 us instead of 0.76)
             const uint32_t nbits = OWN ? in_next[e0 >> 5] >> (e0 & 31) : 0u;
-            if (e0 < d.I) { v.x = v.x + ((bits & 1u) ? d.sp_don : d.sp_doff); c0 = v.x >= d.sp_thr; }
-            if (e0 + 1 < d.I) { v.y = v.y + ((bits & 2u) ? d.sp_don : d.sp_doff); c1 = v.y >= d.sp_thr; }
+            if (e0 < d.I) { v.x = v.x + delta(bits & 1u); c0 = connected(v.x); }
+            if (e0 + 1 < d.I) { v.y = v.y + delta(bits & 2u); c1 = connected(v.y); }
             if (OWN) own_cn += (int)(c0 && (nbits & 1u)) + (int)(c1 && (nbits & 2u));
             if (i0 == 0) ROW_STAMP(2); else ROW_STAMP(4);       // (the pass's values are here)
             {   // 16-byte write-through store (sc0 sc1): nothing of the rows stays dirty in L2 for the kernel-end release
@@ -457,6 +468,10 @@ __device__ __forceinline__ void role_mid(const Dev &d, int p, int n_active, int 
     const int nb2 = (nb + 1023) >> 10;
     const int cnt2_first = ((int)threadIdx.x < 256 && (int)threadIdx.x < nb2) ? d.recyc_cnt2[threadIdx.x] : 0;
     const int prev_has_winner = c->has_winner[p ^ 1], prev_n_win = c->n_win[p ^ 1];
+    // (and whether a scan has run: set by a scan or an import, nothing of this launch writes it.  Before the wait where there is
+    // one, same_launch: behind it the load was a round trip at the head of what is now the launch's longest chain; the launches
+    // without a wait keep their order, and with it the registers and scratch they are held to)
+    const int has_distal_early = same_launch ? c->has_distal : 0;
     wait();
     for (int base = 0; base < n_slots; base += LPT * BS) {
         const int i0 = base + LPT * (int)threadIdx.x;
@@ -517,7 +532,8 @@ __device__ __forceinline__ void role_mid(const Dev &d, int p, int n_active, int 
     n_cells = wave_sum(n_cells);
     if (lane_id() == 0) atomicAdd(&s_cells, n_cells);
     lds_barrier();                                  // (LDS only: the winner lists' stores need not be acknowledged for the count to be read)
-    const int n_un = (learning && c->has_distal) ? (int)carry_u : 0;
+    const int has_distal = same_launch ? has_distal_early : c->has_distal;
+    const int n_un = (learning && has_distal) ? (int)carry_u : 0;
     if (threadIdx.x == 0) {
         c->n_win[p] = want_winner ? (int)carry_w : 0;
         c->has_winner[p] = want_winner;
