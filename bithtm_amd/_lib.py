@@ -76,6 +76,24 @@ class HtmClassifierConfig(C.Structure):
         "buckets", "n_steps", "alpha_q", "units", "cell_dim", "max_pairs")] + [("steps", C.c_int32 * 8)]
 
 
+class HtmKnnConfig(C.Structure):
+    """htm_knn_config: the KNN classifier's parameters (labels, k, the least overlap of a candidate, the slots of the store, the
+    patterns' geometry and the most pairs a pattern may have)."""
+    _fields_ = [("struct_bytes", C.c_uint32)] + [(name, C.c_int32) for name in (
+        "labels", "k", "min_overlap", "capacity", "units", "cell_dim", "max_pairs")]
+
+
+class HtmKnnInfo(C.Structure):
+    """htm_knn_info_t: the parameters again, the slots in use, the form of the distance launch, the step total and the sizes."""
+    _fields_ = HtmKnnConfig._fields_ + [(name, C.c_int32) for name in ("count", "table_in_lds", "queries_per_block", "bin_shift")] + [
+        (name, C.c_int64) for name in ("total", "state_bytes", "device_bytes")]
+
+
+KNN_CHUNK = 64                              # HTM_KNN_CHUNK (csrc/htm_knn.h): query steps per launch of htm_knn_update
+KNN_SLOTS = 256                             # HTM_KNN_SLOTS: slots per block of the distance launch
+KNN_QUERIES = 8                             # HTM_KNN_QUERIES: queries a block stages at most
+KNN_TABLE_BYTES = 48 * 1024                 # HTM_KNN_TABLE_BYTES: LDS for a block's staged tables
+KNN_BINS = 2048                             # HTM_KNN_BINS: bins of the select's histogram
 CLASSIFIER_CHUNK = 512                      # HTM_CLASSIFIER_CHUNK (csrc/htm_classifier.h): steps per launch of a frozen htm_classifier_update
 CLASSIFIER_PAIRS = 16                       # HTM_CLASSIFIER_PAIRS: pairs of a pattern per block
 LIKELIHOOD_CHUNK = 512                      # HTM_LIKELIHOOD_CHUNK (csrc/htm_likelihood.h): steps per launch of htm_likelihood_update
@@ -195,6 +213,15 @@ EXPORTS = {
     "htm_set_group_run_active_cells": (C.c_int, [C.c_void_p, C.c_void_p]),
     "htm_classifiers_tick": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(HtmScalarField), C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
+    "htm_knn_create": (C.c_int, [C.c_void_p, C.POINTER(HtmKnnConfig), C.POINTER(C.c_void_p)]),
+    "htm_knn_destroy": (None, [C.c_void_p]),
+    "htm_knn_labels": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_void_p)]),
+    "htm_knn_update": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p,
+                                 C.c_void_p]),
+    "htm_knn_reset": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "htm_knn_export": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]),
+    "htm_knn_import": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]),
+    "htm_knn_info": (C.c_int, [C.c_void_p, C.POINTER(HtmKnnInfo)]),
 }
 
 # The HIP runtime calls the binding makes itself -- the device buffers of run(record=...) -- resolved through the library's own

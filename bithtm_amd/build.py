@@ -10,8 +10,12 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libbithtm_hip.so")
 RESOURCES = os.path.join(HERE, "libbithtm_hip.resources.json")     # what the compiler gave every kernel (written beside the library)
+# Features added after the classifier banks report their kernels into a file of their own, keyed by the header that defines them:
+# tests/test_group_classifier_cpu.py holds the set of kernels in RESOURCES to what it was with the banks, and a feature's own test
+# holds its kernels' figures (kernel_resources("htm_knn.h"): tests/test_knn_cpu.py).  all_kernel_resources() is every kernel of the library.
+OWN_REPORTS = {"htm_knn.h": os.path.join(HERE, "libbithtm_hip.knn.resources.json")}
 SOURCES = ["htm_engine.hip"]
-HEADERS = ["htm_dev.h", "htm_sp_kernels.h", "htm_tm_kernels.h", "htm_pipeline.h", "htm_record.h", "htm_reset.h", "htm_decode.h", "htm_stack.h", "htm_forecast.h", "htm_noise.h", "htm_group.h", "htm_tm_feed.h", "htm_sp_run.h", "htm_fork.h", "htm_scalar.h", "htm_live.h", "htm_fields.h", "htm_likelihood.h", "htm_classifier.h", "htm_rng.h", "htm_fexp.h",
+HEADERS = ["htm_dev.h", "htm_sp_kernels.h", "htm_tm_kernels.h", "htm_pipeline.h", "htm_record.h", "htm_reset.h", "htm_decode.h", "htm_stack.h", "htm_forecast.h", "htm_noise.h", "htm_group.h", "htm_tm_feed.h", "htm_sp_run.h", "htm_fork.h", "htm_scalar.h", "htm_live.h", "htm_fields.h", "htm_likelihood.h", "htm_classifier.h", "htm_knn.h", "htm_rng.h", "htm_fexp.h",
            os.path.join("..", "..", "include", "bithtm_hip.h")]
 # -ffp-contract=off: several kernels must round exactly like the NumPy expressions they replace
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off",
@@ -20,7 +24,7 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-ffp
 
 
 def _stale():
-    if not os.path.exists(LIB) or not os.path.exists(RESOURCES):
+    if not os.path.exists(LIB) or not all(os.path.exists(r) for r in [RESOURCES] + list(OWN_REPORTS.values())):
         return True
     t = os.path.getmtime(LIB)
     deps = [os.path.join(CSRC, s) for s in SOURCES + HEADERS] + [os.path.abspath(__file__)]
@@ -29,18 +33,18 @@ def _stale():
 
 def _kernel_resources(log):
     """The compiler's per-kernel remarks -> {mangled name: {"vgprs", "agprs", "sgprs", "scratch_bytes_per_lane", "occupancy",
-    "lds_bytes"}}.  k_learn_scan_emit lives at 80 VGPRs (6 waves per SIMD) with NO scratch: a single spilled register slows
+    "lds_bytes"}} per header that defines the kernel: {header file name: {...}}.  k_learn_scan_emit lives at 80 VGPRs (6 waves per SIMD) with NO scratch: a single spilled register slows
     every role of that launch by microseconds (LABNOTES.md) -- tests/test_host_and_abi.py holds the build to it."""
     fields = {"VGPRs": "vgprs", "AGPRs": "agprs", "SGPRs": "sgprs", "ScratchSize [bytes/lane]": "scratch_bytes_per_lane",
               "Occupancy [waves/SIMD]": "occupancy", "LDS Size [bytes/block]": "lds_bytes"}
     out, cur = {}, None
     for line in log.splitlines():
-        m = re.search(r"remark: +([^:]+): (\S+) \[-Rpass-analysis=kernel-resource-usage\]", line)
+        m = re.search(r"^(?:(\S+?):\d+:\d+: )?remark: +([^:]+): (\S+) \[-Rpass-analysis=kernel-resource-usage\]", line)
         if not m:
             continue
-        key, val = m.group(1).strip(), m.group(2)
+        key, val = m.group(2).strip(), m.group(3)
         if key == "Function Name":
-            cur = out.setdefault(val, {})
+            cur = out.setdefault(os.path.basename(m.group(1) or ""), {}).setdefault(val, {})
         elif cur is not None and key in fields:
             cur[fields[key]] = int(val)
     return out
@@ -74,8 +78,12 @@ def build(force=False, verbose=False):
     r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
     if r.returncode != 0:
         raise RuntimeError("hipcc failed:\n" + r.stdout)
+    by_header = _kernel_resources(r.stdout)
+    for header, path in OWN_REPORTS.items():
+        with open(path, "w") as f:
+            json.dump(by_header.pop(header, {}), f, indent=0, sort_keys=True)
     with open(RESOURCES, "w") as f:
-        json.dump(_kernel_resources(r.stdout), f, indent=0, sort_keys=True)
+        json.dump({k: v for kernels in by_header.values() for k, v in kernels.items()}, f, indent=0, sort_keys=True)
     if verbose:
         rest = _without_remarks(r.stdout)
         if rest.strip():
@@ -83,13 +91,21 @@ def build(force=False, verbose=False):
     return LIB
 
 
-def kernel_resources():
-    """{mangled kernel name: resources} of the library as last built here (None if it was built elsewhere)."""
+def kernel_resources(header=None):
+    """{mangled kernel name: resources} of the library as last built here (None if it was built elsewhere): the kernels of RESOURCES,
+    or those the header `header` of OWN_REPORTS defines."""
     build()
-    if not os.path.exists(RESOURCES):
+    path = RESOURCES if header is None else OWN_REPORTS[header]
+    if not os.path.exists(path):
         return None
-    with open(RESOURCES) as f:
+    with open(path) as f:
         return json.load(f)
+
+
+def all_kernel_resources():
+    """Every kernel of the library: RESOURCES and the reports of OWN_REPORTS together (None if it was built elsewhere)."""
+    parts = [kernel_resources()] + [kernel_resources(h) for h in OWN_REPORTS]
+    return None if any(p is None for p in parts) else {k: v for p in parts for k, v in p.items()}
 
 
 if __name__ == "__main__":

@@ -55,6 +55,7 @@
 #include "htm_fields.h"
 #include "htm_likelihood.h"
 #include "htm_classifier.h"
+#include "htm_knn.h"
 
 // ------------------------------------------------------------------------------------------
 // host side
@@ -4623,6 +4624,251 @@ extern "C" int htm_classifiers_export(htm_classifier *clf, htm_handle *h, void *
 }
 extern "C" int htm_classifiers_import(htm_classifier *clf, htm_handle *h, const void *host_state, int64_t bytes) {
     return cls_state("htm_classifiers_import", true, true, clf, h, (void *)host_state, bytes);
+}
+
+// ------------------------------------------------------------------------------------------
+// KNN classifier (htm_knn.h): the store, its labels and stamps and the scratch of an update in device memory;
+// the slots in use, the step total and the labels of the learning calls on the host -- every store is decided here, nothing is read
+// back.  As the classifier it keeps nothing of the handles its calls come through.
+struct htm_knn {
+    int device = 0;
+    KnnDev d{};
+    int32_t count = 0;
+    int64_t total = 0;
+    int64_t device_bytes = 0;
+    std::vector<void *> allocs;
+    std::vector<int32_t> labels;                // htm_knn_labels: the labels a learning call reads, as the host gave them
+    int32_t *d_labels = nullptr;                // ... and their device array, of labels_cap words
+    size_t labels_cap = 0;
+    int32_t *d_pos = nullptr;                   // the slot of every step of the call in flight, of pos_cap words
+    size_t pos_cap = 0;
+};
+
+extern "C" void htm_knn_destroy(htm_knn *knn) {
+    if (!knn) return;
+    hipSetDevice(knn->device);
+    for (void *p : knn->allocs) hipFree(p);     // (hipFree waits for the device: nothing enqueued still reads them)
+    delete knn;
+}
+
+// zeroed device memory of the object's, ordered on h's stream (null: the allocation failed)
+template <typename T>
+static T *knn_alloc(htm_knn *knn, htm_handle *h, size_t count) {
+    void *p = nullptr;
+    const size_t bytes = std::max<size_t>(count, 1) * sizeof(T);
+    if (hipMalloc(&p, bytes) != hipSuccess) return nullptr;
+    knn->allocs.push_back(p);
+    knn->device_bytes += (int64_t)bytes;
+    if (hipMemsetAsync(p, 0, bytes, h->stream) != hipSuccess) return nullptr;
+    return (T *)p;
+}
+
+// a scratch array of the object's grown to `count` words (hipFree waits for the device: nothing enqueued still uses the old one)
+static int knn_grow(const char *what, htm_knn *knn, htm_handle *h, int32_t **p, size_t *cap, size_t count) {
+    if (count <= *cap) return 0;
+    if (*p) {
+        knn->allocs.erase(std::remove(knn->allocs.begin(), knn->allocs.end(), (void *)*p), knn->allocs.end());
+        knn->device_bytes -= (int64_t)(*cap * 4);
+        hipFree(*p);
+        *p = nullptr;
+        *cap = 0;
+    }
+    count = std::max<size_t>(count, 256);
+    int32_t *q = knn_alloc<int32_t>(knn, h, count);
+    if (!q) return cls_refuse(h, std::string(what) + ": device allocation failed", HTM_ERR_HIP);
+    *p = q;
+    *cap = count;
+    return 0;
+}
+
+extern "C" int htm_knn_create(htm_handle *h, const htm_knn_config *cfg, htm_knn **out) {
+    const std::string what = "htm_knn_create";
+    if (out) *out = nullptr;
+    if (!h || !cfg || !out) return cls_refuse(h, what + ": null argument", HTM_ERR_ARGUMENT);
+    if (cfg->struct_bytes != sizeof(htm_knn_config)) return cls_refuse(h, what + ": htm_knn_config size mismatch", HTM_ERR_ARGUMENT);
+    const bool ok = cfg->labels >= 1 && cfg->labels <= HTM_KNN_MAX_LABELS && cfg->k >= 1 && cfg->k <= HTM_KNN_MAX_K && cfg->min_overlap >= 1 &&
+                    cfg->min_overlap <= 65535 && cfg->capacity >= 1 && cfg->capacity <= HTM_KNN_MAX_CAPACITY && cfg->cell_dim >= 1 && cfg->cell_dim <= 64 &&
+                    cfg->units >= cfg->cell_dim && cfg->units % cfg->cell_dim == 0 && cfg->max_pairs >= 1 && cfg->max_pairs <= HTM_KNN_MAX_PAIRS;
+    if (!ok)
+        return cls_refuse(h, what + ": labels in [1, 1024], k in [1, 64], min_overlap in [1, 65535], capacity in [1, 2^20], cell_dim in [1, 64], "
+                             "units a positive multiple of cell_dim, max_pairs in [1, 2047]", HTM_ERR_ARGUMENT);
+    if (h->world > 1) return cls_refuse(h, what + ": not available on a column-sharded handle", HTM_ERR_STATE);
+    HIPCHK(h, hipSetDevice(h->device));
+    htm_knn *knn = new htm_knn();
+    knn->device = h->device;
+    KnnDev &d = knn->d;
+    d.labels = cfg->labels;
+    d.k = cfg->k;
+    d.min_overlap = cfg->min_overlap;
+    d.capacity = cfg->capacity;
+    d.K = cfg->cell_dim;
+    d.WPC = (cfg->cell_dim + 31) / 32;
+    d.n_cols = cfg->units / cfg->cell_dim;
+    d.max_pairs = cfg->max_pairs;
+    const int64_t words = knn_table_words(d.n_cols, d.WPC);
+    d.words = (int32_t)words;
+    d.queries = knn_queries(words);
+    d.in_lds = knn_in_lds(words);
+    d.bitmap = knn_has_bitmap(words);
+    d.shift = knn_shift(knn_max_overlap(d.max_pairs, d.K));
+    const size_t cap = (size_t)d.capacity;
+    d.store = knn_alloc<ClsPair>(knn, h, cap * d.max_pairs);
+    d.label = knn_alloc<int32_t>(knn, h, cap);
+    d.stamp = knn_alloc<int64_t>(knn, h, cap);
+    d.ovl = knn_alloc<uint16_t>(knn, h, (size_t)HTM_KNN_CHUNK * cap);
+    d.table = d.in_lds ? nullptr : knn_alloc<uint32_t>(knn, h, (size_t)HTM_KNN_CHUNK * (size_t)words);
+    // (the state is there when the call returns, whatever stream the first update comes on)
+    if (words > INT32_MAX || !d.store || !d.label || !d.stamp || !d.ovl || (!d.in_lds && !d.table) || hipStreamSynchronize(h->stream) != hipSuccess) {
+        htm_knn_destroy(knn);
+        return cls_refuse(h, what + ": device allocation failed", HTM_ERR_HIP);
+    }
+    *out = knn;
+    return HTM_OK;
+}
+
+// what every call on an existing object checks of its handle
+static int knn_check(const char *what, htm_knn *knn, htm_handle *h) {
+    if (!knn || !h) return cls_refuse(h, std::string(what) + ": null argument", HTM_ERR_ARGUMENT);
+    if (h->world > 1) return cls_refuse(h, std::string(what) + ": not available on a column-sharded handle", HTM_ERR_STATE);
+    if (h->device != knn->device) return cls_refuse(h, std::string(what) + ": the handle is on another device than the KNN classifier", HTM_ERR_ARGUMENT);
+    return 0;
+}
+
+extern "C" int htm_knn_labels(htm_knn *knn, htm_handle *h, const int32_t *host_labels, int32_t n_labels, const int32_t **device_labels) {
+    const char *what = "htm_knn_labels";
+    if (device_labels) *device_labels = nullptr;
+    if (int rc = knn_check(what, knn, h)) return rc;
+    if (!host_labels || !device_labels || n_labels < 1) return cls_refuse(h, std::string(what) + ": need host labels, n_labels >= 1 and a place for the address", HTM_ERR_ARGUMENT);
+    HIPCHK(h, hipSetDevice(knn->device));
+    if (int rc = knn_grow(what, knn, h, &knn->d_labels, &knn->labels_cap, (size_t)n_labels)) return rc;
+    knn->labels.assign(host_labels, host_labels + n_labels);
+    // (from the call's own pageable words: the copy has read them when it returns)
+    HIPCHK(h, hipMemcpyAsync(knn->d_labels, host_labels, (size_t)n_labels * 4, hipMemcpyHostToDevice, h->stream));
+    *device_labels = knn->d_labels;
+    return HTM_OK;
+}
+
+extern "C" int htm_knn_update(htm_knn *knn, htm_handle *h, const void *device_pairs, int32_t pairs_per_step, int32_t n_steps,
+                              const int32_t *device_labels, int32_t n_labels, int32_t first_step, int32_t learn, int32_t *device_best,
+                              int32_t *device_votes) {
+    const char *what = "htm_knn_update";
+    if (int rc = knn_check(what, knn, h)) return rc;
+    const std::string w = std::string(what) + ": ";
+    if (!device_pairs || !device_labels || !device_best) return cls_refuse(h, w + "null pairs, labels or output", HTM_ERR_ARGUMENT);
+    const KnnDev &d = knn->d;
+    if (pairs_per_step < 1 || pairs_per_step > d.max_pairs)
+        return cls_refuse(h, w + "pairs_per_step must be in [1, max_pairs = " + std::to_string(d.max_pairs) + "]", HTM_ERR_ARGUMENT);
+    if (n_steps < 0 || n_labels < 1 || first_step < 0) return cls_refuse(h, w + "n_steps >= 0, n_labels >= 1, first_step >= 0", HTM_ERR_ARGUMENT);
+    // what the call stores: counted on the host, from the labels the host gave
+    int64_t stored = 0;
+    if (learn && n_steps > 0) {
+        if (device_labels != knn->d_labels || (size_t)n_labels != knn->labels.size())
+            return cls_refuse(h, w + "a learning call reads the labels of htm_knn_labels (its address, its n_labels): the host counts what is stored", HTM_ERR_ARGUMENT);
+        for (int i = 0; i < n_steps; ++i) {
+            const int32_t g = knn->labels[(size_t)(((int64_t)first_step + i) % n_labels)];
+            stored += g >= 0 && g < d.labels;
+        }
+    }
+    if (knn->count + stored > d.capacity)
+        return cls_refuse(h, w + "the call would store " + std::to_string(stored) + " patterns in a store of " + std::to_string(knn->count) + " of capacity = " +
+                                 std::to_string(d.capacity) + " slots", HTM_ERR_CAPACITY);
+    if (n_steps == 0) return HTM_OK;
+    HIPCHK(h, hipSetDevice(knn->device));
+    if (stored)
+        if (int rc = knn_grow(what, knn, h, &knn->d_pos, &knn->pos_cap, (size_t)n_steps)) return rc;
+    KnnStep s{(const ClsPair *)device_pairs, pairs_per_step, device_labels, n_labels, first_step, n_steps, device_best, device_votes, knn->total, knn->count,
+              knn->count + (int32_t)stored};
+    const hipStream_t st = h->stream;
+    if (stored) {
+        LAUNCH_ON(h, st, 0, "knn:place", kknn_place, 1, 256, d, s, knn->d_pos);
+        LAUNCH_ON(h, st, 0, "knn:append", kknn_append, (unsigned)(((int64_t)n_steps * d.max_pairs + 255) / 256), 256, d, s, (const int32_t *)knn->d_pos);
+    }
+    for (int first = 0; first < n_steps; first += HTM_KNN_CHUNK) {
+        const int nq = std::min<int>(HTM_KNN_CHUNK, n_steps - first);
+        const unsigned scatter = (unsigned)(((int64_t)nq * pairs_per_step + 255) / 256);
+        if (s.count > 0) {
+            const dim3 grid(knn_slot_blocks(s.count), knn_query_groups(nq, d.queries));
+            if (d.in_lds) {
+                LAUNCH_ON(h, st, (size_t)knn_distance_lds(d.words), "knn:distance", kknn_distance_lds, grid, 256, d, s, first, nq);
+            } else {
+                LAUNCH_ON(h, st, 0, "knn:scatter", kknn_scatter, scatter, 256, d, s, first, nq, 1);
+                LAUNCH_ON(h, st, (size_t)knn_distance_lds(d.words), "knn:distance", kknn_distance_global, grid, 256, d, s, first, nq);
+            }
+        }
+        LAUNCH_ON(h, st, 0, "knn:select", kknn_select, nq, 256, d, s, first);
+        if (s.count > 0 && !d.in_lds) LAUNCH_ON(h, st, 0, "knn:clear", kknn_scatter, scatter, 256, d, s, first, nq, 0);
+    }
+    knn->count = s.count;
+    knn->total += n_steps;
+    return launch_status(h->err);
+}
+
+// the store emptied: the slots in use are the host's (the launches enqueued before carry their own count)
+extern "C" int htm_knn_reset(htm_knn *knn, htm_handle *h) {
+    if (int rc = knn_check("htm_knn_reset", knn, h)) return rc;
+    knn->count = 0;
+    return HTM_OK;
+}
+
+// The state: int64 total; int64 count; count x max_pairs pairs; count int64 stamps; count int32 labels
+static int64_t knn_state_bytes(const htm_knn *knn, int64_t count) { return 16 + count * ((int64_t)knn->d.max_pairs * 8 + 12); }
+
+extern "C" int htm_knn_info(const htm_knn *knn, htm_knn_info_t *out) {
+    if (!knn || !out || out->struct_bytes != sizeof(htm_knn_info_t)) return HTM_ERR_ARGUMENT;
+    const KnnDev &d = knn->d;
+    *out = htm_knn_info_t{(uint32_t)sizeof(htm_knn_info_t), d.labels, d.k, d.min_overlap, d.capacity, d.n_cols * d.K, d.K, d.max_pairs, knn->count, d.in_lds,
+                          d.queries, d.shift, knn->total, knn_state_bytes(knn, knn->count), knn->device_bytes};
+    return HTM_OK;
+}
+
+// the state copied to the host blob (load == 0) or from it, behind everything enqueued on h's stream
+static int knn_state(const char *what, bool load, htm_knn *knn, htm_handle *h, void *host_state, int64_t bytes) {
+    if (int rc = knn_check(what, knn, h)) return rc;
+    const std::string w = std::string(what) + ": ";
+    if (!host_state || bytes < 16) return cls_refuse(h, w + "need host_state of htm_knn_info's state_bytes", HTM_ERR_ARGUMENT);
+    const KnnDev &d = knn->d;
+    int64_t head[2] = {knn->total, knn->count};
+    if (load) memcpy(head, host_state, 16);
+    if (head[1] < 0 || head[1] > d.capacity || head[0] < 0 || bytes != knn_state_bytes(knn, head[1]))
+        return cls_refuse(h, w + "need host_state of 16 + count x (8 max_pairs + 12) bytes with 0 <= count <= capacity, total >= 0", HTM_ERR_ARGUMENT);
+    const size_t n = (size_t)head[1], pair_bytes = n * d.max_pairs * 8;
+    char *pairs = (char *)host_state + 16, *stamps = pairs + pair_bytes, *labels = stamps + n * 8;
+    if (load) {
+        int64_t last = -1;
+        for (size_t i = 0; i < n; ++i) {
+            int64_t stamp;
+            int32_t label;
+            memcpy(&stamp, stamps + i * 8, 8);
+            memcpy(&label, labels + i * 4, 4);
+            if (stamp <= last || stamp >= head[0]) return cls_refuse(h, w + "the stamps must ascend and lie below total (slot " + std::to_string(i) + ")", HTM_ERR_ARGUMENT);
+            if (label < 0 || label >= d.labels) return cls_refuse(h, w + "a label outside [0, labels) in slot " + std::to_string(i), HTM_ERR_ARGUMENT);
+            last = stamp;
+        }
+    }
+    HIPCHK(h, hipSetDevice(knn->device));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    if (load) {
+        if (n) {
+            HIPCHK(h, hipMemcpy(d.store, pairs, pair_bytes, hipMemcpyHostToDevice));
+            HIPCHK(h, hipMemcpy(d.stamp, stamps, n * 8, hipMemcpyHostToDevice));
+            HIPCHK(h, hipMemcpy(d.label, labels, n * 4, hipMemcpyHostToDevice));
+        }
+        knn->total = head[0];
+        knn->count = (int32_t)head[1];
+    } else {
+        memcpy(host_state, head, 16);
+        if (n) {
+            HIPCHK(h, hipMemcpy(pairs, d.store, pair_bytes, hipMemcpyDeviceToHost));
+            HIPCHK(h, hipMemcpy(stamps, d.stamp, n * 8, hipMemcpyDeviceToHost));
+            HIPCHK(h, hipMemcpy(labels, d.label, n * 4, hipMemcpyDeviceToHost));
+        }
+    }
+    return HTM_OK;
+}
+
+extern "C" int htm_knn_export(htm_knn *knn, htm_handle *h, void *host_state, int64_t bytes) { return knn_state("htm_knn_export", false, knn, h, host_state, bytes); }
+extern "C" int htm_knn_import(htm_knn *knn, htm_handle *h, const void *host_state, int64_t bytes) {
+    return knn_state("htm_knn_import", true, knn, h, (void *)host_state, bytes);
 }
 
 // ------------------------------------------------------------------------------------------

@@ -548,15 +548,15 @@ class Engine:
         return ptr.value
 
     def run(self, device_bank, n_inputs, n_steps, learning=True, use_graph=True, pipeline=True, continuing=False, record=None,
-            resets=None, encoder=None, likelihood=None, classifier=None):
+            resets=None, encoder=None, likelihood=None, classifier=None, knn=None):
         """`resets`: None, or the device address of reset bits for this bank (upload_resets): a sequence reset before every
         step that reads a row whose bit is set (htm_set_run_resets, set for this call only).  `encoder`: the ScalarEncoder a
         "predicted_value" record decodes with."""
         with _NOTHING_TO_SET if resets is None else self.this_call(resets, n_inputs):
-            return self._run(device_bank, n_inputs, n_steps, learning, use_graph, pipeline, continuing, record, encoder, likelihood, classifier)
+            return self._run(device_bank, n_inputs, n_steps, learning, use_graph, pipeline, continuing, record, encoder, likelihood, classifier, knn)
 
     def _run(self, device_bank, n_inputs, n_steps, learning=True, use_graph=True, pipeline=True, continuing=False, record=None,
-             encoder=None, likelihood=None, classifier=None):
+             encoder=None, likelihood=None, classifier=None, knn=None):
         """`continuing`: the next call is another run() on the same bank (HTM_RUN_CONTINUE, include/bithtm_hip.h).
         `record`: None, or the fields of a per-step record to keep (RECORD_FIELDS): the call then goes to htm_run_recorded and
         returns {field: numpy array over the n_steps steps} -- "counters" int32[n, 8] (htm_step_record, RECORD_COUNTERS order),
@@ -570,7 +570,11 @@ class Engine:
         those rows or None, "learn", "distribution"} -- the run leaves each step's active-cell words in the classifier's pattern
         buffer (htm_set_run_active_cells, set for this call only), the classifier's update is enqueued behind the run, before the
         synchronisation, step i reading target and reset bit (step index + i) % rows, and "classified" int32[n, H, 2] and
-        "class_distribution" (int32[n, H, buckets] or None) are returned beside the fields."""
+        "class_distribution" (int32[n, H, buckets] or None) are returned beside the fields.  `knn` (`record` is not None): {"knn": a
+        knn_classifier.KNNClassifier, "labels": device address of int32 [rows] (its upload_labels), "host_labels": the same labels
+        int32 [rows], "learn", "votes"} -- the KNN update over the same captured rows (the classifier's buffer when both ride on the
+        run: one capture launch per step either way) is enqueued next to the classifier's, step i reading label (step index + i) %
+        rows, and "knn" int32[n, 5] and "knn_votes_all" (int32[n, labels] or None) are returned beside the fields."""
         if record is None:
             self.run_into(device_bank, n_inputs, n_steps, {}, learning, use_graph, pipeline, continuing)
             return None
@@ -578,6 +582,11 @@ class Engine:
         buffers = self._record_buffers(fields, n, encoder)
         clf = classifier["clf"] if classifier is not None and n > 0 else None
         cells, first = (clf.pairs_buffer(self, n), self.steps % classifier["rows"]) if clf is not None else (None, 0)
+        near = knn["knn"] if knn is not None and n > 0 else None
+        if near is not None:
+            knn_first = self.steps % len(knn["host_labels"])
+            near.check_room(near.stored_by(knn["host_labels"], knn_first, n, knn["learn"]))      # (refused before the run is enqueued)
+            cells = near.pairs_buffer(self, n) if cells is None else cells
         self.run_into(device_bank, n_inputs, n, buffers, learning, use_graph, pipeline, continuing, cells=cells)
         self.decode_records(buffers, n, encoder)
         if likelihood is not None and n > 0:
@@ -585,6 +594,8 @@ class Engine:
         if clf is not None:
             clf.enqueue(self, cells, clf.shape[2], n, classifier["targets"], classifier["rows"], first, classifier["resets"], classifier["learn"],
                         classifier["distribution"])
+        if near is not None:
+            near.enqueue(self, cells, near.shape[2], n, knn["labels"], knn["host_labels"], knn_first, knn["learn"], knn["votes"])
         out = self._records_read(fields, n, sync=True, encoder=encoder)
         if likelihood is not None:
             out["anomaly_likelihood"] = likelihood.read(self, n)[0] if n > 0 else np.zeros(0, dtype=np.float64)
@@ -592,6 +603,10 @@ class Engine:
             c = classifier["clf"]
             out["classified"], out["class_distribution"] = c.read(self, n, classifier["distribution"]) if n > 0 else (
                 np.zeros((0, len(c.steps), 2), np.int32), np.zeros((0, len(c.steps), c.buckets), np.int32) if classifier["distribution"] else None)
+        if knn is not None:
+            c = knn["knn"]
+            out["knn"], out["knn_votes_all"] = c.read(self, n, knn["votes"]) if n > 0 else (
+                np.zeros((0, 5), np.int32), np.zeros((0, c.labels), np.int32) if knn["votes"] else None)
         return out
 
     def run_into(self, device_bank, n_inputs, n_steps, buffers, learning=True, use_graph=True, pipeline=True, continuing=False, cells=None):

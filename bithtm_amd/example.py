@@ -7,6 +7,7 @@ the three counters: :55-57), so that its output can be compared line by line.
     python -m bithtm_amd.example --epochs 8 --batched_report   # ... recorded: the per-step lines of the default mode
     python -m bithtm_amd.example --epochs 8 --batched_report --likelihood   # ... with each step's anomaly likelihood
     python -m bithtm_amd.example --epochs 8 --batched_report --classifier   # ... with an SDR classifier's 1-step hit rate per epoch
+    python -m bithtm_amd.example --epochs 8 --batched_report --knn   # ... a KNN classifier stores the first epochs' labelled steps, names the later ones
     python -m bithtm_amd.example --epochs 8 --batched --device_noise   # ... the bank uploaded once, the flip noise drawn on the device
     python -m bithtm_amd.example --epochs 8 --sequence_length 10   # a sequence reset before every 10th pattern
     python -m bithtm_amd.example --epochs 8 --use_reference_implementation   # example.py:30,36-37 (needs the user's `bithtm`)
@@ -18,7 +19,7 @@ import time
 
 import numpy as np
 
-from bithtm_amd import AnomalyLikelihood, HierarchicalTemporalMemory, SDRClassifier
+from bithtm_amd import AnomalyLikelihood, HierarchicalTemporalMemory, KNNClassifier, SDRClassifier
 
 FLAGS = (
     # name, type, default  (the reference's flags, same names and defaults)
@@ -59,6 +60,9 @@ def parse(argv):
     ap.add_argument("--classifier", action="store_true",
                     help="with --batched_report: learn an SDR classifier on the device from each step's active cells to the index of the "
                          "pattern one step ahead (run(classifier=), one bucket per pattern) and print its 1-step hit rate per epoch")
+    ap.add_argument("--knn", action="store_true",
+                    help="with --batched_report: label each step of the first half of the epochs with its pattern's index and store its "
+                         "active cells in a KNN classifier on the device (run(knn=), k = 3); print the hit rate of the later epochs")
     return ap.parse_args(argv)
 
 
@@ -129,8 +133,13 @@ def run_batched_report(htm, bank, opts, out):
     scoring = dict(likelihood=AnomalyLikelihood()) if opts.likelihood else {}
     if opts.classifier:                             # (a step's target is its own pattern's index: horizon 1 learns the one that follows)
         scoring.update(classifier=SDRClassifier(buckets=len(bank), steps=(1,), alpha=0.1), targets=np.arange(len(bank)))
+    labelled = max(opts.epochs // 2, 1)             # (--knn: the epochs whose steps are labelled and stored)
+    if opts.knn:
+        scoring.update(knn=KNNClassifier(len(bank), k=3, capacity=len(bank) * labelled))
     for epoch in range(opts.epochs):
         noisy, noise = epoch_input(bank, opts)
+        if opts.knn:
+            scoring.update(labels=np.arange(len(bank)) if epoch < labelled else None)
         rec = htm.run(noisy, len(noisy), record=True, resets=reset_rows(opts), **noise, **scoring)
         for index, (b, c, i) in enumerate(zip(rec.bursting_columns, rec.correct_columns, rec.incorrect_columns)):
             scored = f", anomaly likelihood: {rec.anomaly_likelihood[index]:.6f}" if opts.likelihood else ""
@@ -138,6 +147,9 @@ def run_batched_report(htm, bank, opts, out):
         if opts.classifier:
             hits = rec.classified_bucket[:, 0] == (np.arange(len(bank)) + 1) % len(bank)
             print(f"epoch {epoch:{report.w_epoch}d}: 1-step hit rate of the classifier: {hits.mean():.3f}", file=out)
+        if opts.knn and epoch >= labelled:
+            hits = rec.knn_label == np.arange(len(bank))
+            print(f"epoch {epoch:{report.w_epoch}d}: hit rate of the KNN classifier over {scoring['knn'].count} stored steps: {hits.mean():.3f}", file=out)
 
 
 def main(argv=None, out=sys.stdout):
@@ -161,6 +173,10 @@ def main(argv=None, out=sys.stdout):
             raise SystemExit("--classifier rides on the recorded report's runs: use it with --batched_report")
         if opts.classifier and opts.input_patterns > 1024:
             raise SystemExit("--classifier: one bucket per pattern, at most 1024 patterns")
+        if opts.knn and not opts.batched_report:
+            raise SystemExit("--knn rides on the recorded report's runs: use it with --batched_report")
+        if opts.knn and opts.input_patterns > 1024:
+            raise SystemExit("--knn: one label per pattern, at most 1024 patterns")
         if opts.device_noise and not (opts.batched or opts.batched_report):
             raise SystemExit("--device_noise draws the noise inside a batched run: use it with --batched or --batched_report")
         htm = HierarchicalTemporalMemory(opts.input_dim, opts.column_dim, opts.cell_dim, seed=opts.seed)

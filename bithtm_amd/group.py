@@ -21,7 +21,7 @@ import numpy as np
 from . import _lib as L
 from .engine import CapacityError, HtmError, pack_bits
 from .networks import (RECORD_COUNTERS, HierarchicalTemporalMemory, InferenceView, RunRecord, _BatchedCall, _batches, _cached_bank, _check_encoder,
-                       _encode_params, _no_classifier, _noise_ring, _record_fields, _with_counters, noise_threshold, retire_states)
+                       _encode_params, _no_classifier, _no_knn, _noise_ring, _record_fields, _with_counters, noise_threshold, retire_states)
 from .sdr_classifier import SDRClassifierBank, model_shape
 
 
@@ -254,7 +254,7 @@ class ModelGroup:
     noise_chunk = 1024
 
     def run(self, inputs, steps, learning=None, use_graph=True, record=None, resets=None, noise=0.0, noise_seed=None, encoder=None,
-            likelihood=None, classifier=None, targets=None, classifier_learning=None):
+            likelihood=None, classifier=None, targets=None, classifier_learning=None, knn=None):
         """`steps` timesteps of every member, member i over the rows of inputs[i] (bool [B, n_inputs, input_dim]), cycled, as
         its own run(inputs[i], steps) would.  Returns None, or (`record`: as run(record=)) one RunRecord per member.
         learning=None: True, or False in a group with inference views (which refuses True).
@@ -273,7 +273,9 @@ class ModelGroup:
         member's rows (-1: missing), uploaded once; None with `encoder`: the bucket of the bank's field among the encoder's.  With
         `noise`, targets index the row of `inputs`.  `classifier_learning`: None follows `learning`.  Member i's RunRecord gains
         classified_bucket, _probability, _value and (with "class_distribution" named in `record`) class_distribution, as
-        run(classifier=) of the member alone with stream i as its classifier would give them."""
+        run(classifier=) of the member alone with stream i as its classifier would give them.  `knn`: refused (a KNNClassifier has
+        one stream and rides on a model's or a view's own run())."""
+        _no_knn(knn, "ModelGroup.run()")
         bank = classifier if isinstance(classifier, SDRClassifierBank) else None
         if bank is None:
             _no_classifier(classifier, "ModelGroup.run()")
@@ -520,7 +522,7 @@ class ModelGroup:
                 m.temporal_memory._was_reset = True
 
     def tick(self, values, encoder=None, resets=None, learning=None, predicted_input=False, use_graph=True, likelihood=None, classifier=None,
-             targets=None, classifier_learning=None, class_distribution=False):
+             targets=None, classifier_learning=None, class_distribution=False, knn=None):
         """One live timestep of every member in one call whose copies, launches and waits do not depend on B: member i steps on
         values[i] -- float64 [B, F] with `encoder` (a ScalarEncoder; NaN: missing), encoded on the device, else bool
         [B, input_dim] as process() takes it -- after a sequence reset where resets[i] (bool [B], or None).  Returns a GroupTick:
@@ -536,7 +538,9 @@ class ModelGroup:
         still one copy in, one copy out and one wait).  `targets`: int [B], each member's bucket of this tick (-1: missing); None
         with `encoder` and a bank made with field=: the bucket of this tick's value (NaN: missing).  `classifier_learning`: None
         follows `learning`.  A member's reset flag also empties its stream's history.  GroupTick.classified_bucket, _probability,
-        _value hold the predictions, with class_distribution=True GroupTick.class_distribution all probabilities."""
+        _value hold the predictions, with class_distribution=True GroupTick.class_distribution all probabilities.  `knn`: refused, as
+        in run()."""
+        _no_knn(knn, "ModelGroup.tick()")
         bank = classifier if isinstance(classifier, SDRClassifierBank) else None
         if bank is None:
             _no_classifier(classifier, "ModelGroup.tick()")

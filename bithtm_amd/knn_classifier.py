@@ -1,0 +1,296 @@
+"""KNNClassifier: NuPIC's KNN classifier over active-cell patterns, kept on the device (htm_knn_*, include/bithtm_hip.h; DESIGN.md
+section 26).  The definition is knn.py; the device equals it bit for bit.
+
+    knn = KNNClassifier(labels=12, k=3, capacity=16384)              # bound to a device, and to a model's shape, at first use
+    model.run(inputs, 600, knn=knn, labels=names)                   # names int [rows of inputs], -1: no label: the labelled steps are stored
+    rec = view.run(inputs, 200, knn=knn)                            # rec.knn_label, knn_votes, knn_overlap, knn_nearest_slot, knn_nearest_step
+    best, votes = knn.update_patterns(index, words, labels)         # the stand-alone door: patterns as (word index, word) pairs
+
+Memory: capacity x (8 max_pairs + 12) bytes of store and 128 x capacity bytes of overlaps -- 7.6 MiB at 16 384 slots of 40 pairs."""
+
+import ctypes as C
+import weakref
+
+import numpy as np
+
+from . import _lib as L
+from .classifier import check_patterns
+from .engine import HtmError
+from .knn import MAX_PAIRS, check_params, is_label
+from .sdr_classifier import model_shape
+
+
+class KNNClassifier:
+    """The classifier of `labels` labels: a step's result is the label most of its `k` nearest stored patterns carry, nearest by
+    overlap (at least `min_overlap`), in a store of `capacity` slots that never overwrites.  The shape of the patterns --
+    column_dim, cell_dim and the pairs a pattern has at most -- comes from the model of the first run(knn=), or from
+    `shape=(column_dim, cell_dim, max_pairs)` for stand-alone use.  The object binds to a device lazily, as SDRClassifier does;
+    every update continues where the last one ended, whichever door it came through."""
+
+    def __init__(self, labels, k=1, min_overlap=1, capacity=4096, shape=None):
+        self.labels, self.k, self.min_overlap, self.capacity = check_params(labels, k, min_overlap, capacity)
+        self.shape = None
+        if shape is not None:
+            self._set_shape(*shape)
+        self.lib = None
+        self.device = None
+        self._knn = None
+        self._last = None                       # weak reference to the engine of the last call
+        self._home = None                       # a small model of the object's own, made when no other handle is there
+        self._bufs = {}                         # the device buffers of a call's outputs: name -> (address, words)
+        self._pending = None                    # a state loaded before the object was bound
+        self._count, self._total = 0, 0         # the host's mirror: nothing is read back to know them
+
+    def _set_shape(self, column_dim, cell_dim, max_pairs):
+        column_dim, cell_dim, max_pairs = int(column_dim), int(cell_dim), int(max_pairs)
+        if column_dim < 1 or not 1 <= cell_dim <= 64 or not 1 <= max_pairs <= MAX_PAIRS:
+            raise ValueError(f"KNNClassifier: shape = (column_dim >= 1, cell_dim in [1, 64], max_pairs in [1, {MAX_PAIRS}]), got "
+                             f"{(column_dim, cell_dim, max_pairs)}")
+        shape = (column_dim, cell_dim, max_pairs)
+        if self.shape is not None and self.shape != shape:
+            raise ValueError(f"the KNN classifier was made for patterns of shape {self.shape} (column_dim, cell_dim, pairs), this call has {shape}")
+        self.shape = shape
+
+    @property
+    def units(self):
+        return self.shape[0] * self.shape[1]
+
+    @property
+    def count(self):
+        """Slots in use."""
+        return int(self._pending["count"]) if self._knn is None and self._pending is not None else self._count
+
+    @property
+    def total(self):
+        """Steps seen."""
+        return int(self._pending["total"]) if self._knn is None and self._pending is not None else self._total
+
+    # ---- binding
+    def _bind(self, engine):
+        if self.shape is None:
+            raise RuntimeError("the KNN classifier does not know the shape of its patterns yet: use it with a model, or give KNNClassifier(shape=)")
+        if self._knn is None:
+            self.lib = engine.lib
+            cfg = L.HtmKnnConfig(C.sizeof(L.HtmKnnConfig), self.labels, self.k, self.min_overlap, self.capacity, self.units, self.shape[1], self.shape[2])
+            out = C.c_void_p()
+            rc = self.lib.htm_knn_create(engine.h, C.byref(cfg), C.byref(out))
+            if rc != 0:
+                raise HtmError(f"htm_knn_create failed ({rc}): {self.lib.htm_last_error(engine.h).decode()}")
+            self._knn, self.device = out, engine.device
+            self._last = weakref.ref(engine)
+            if self._pending is not None:
+                pending, self._pending = self._pending, None
+                self._import(engine, pending)
+        elif engine.device != self.device:
+            raise ValueError(f"the KNN classifier lives on device {self.device}, the model on device {engine.device}")
+        # the library orders calls on one stream only: what the last engine enqueued is waited for before another engine touches the state
+        last = self._last() if self._last is not None else None
+        if last is not None and last is not engine and getattr(last, "h", None):
+            last.sync()
+        self._last = weakref.ref(engine)
+        return engine
+
+    def bind(self, model):
+        """Bind the object to `model`'s device now -- and, unless it was given one, to the shape of the model's patterns.  Returns
+        the object."""
+        if self.shape is None:
+            self._set_shape(*model_shape(model.engine))
+        self._bind(model.engine)
+        return self
+
+    def _engine(self, device=None):
+        engine = self._last() if self._last is not None else None
+        if engine is not None and getattr(engine, "h", None) and device in (None, engine.device):
+            return self._bind(engine)
+        if self._knn is not None and device not in (None, self.device):
+            raise ValueError(f"the KNN classifier lives on device {self.device}, not {device}")
+        if self._home is None:
+            if device is None and self.device is None:
+                raise RuntimeError("the KNN classifier is not bound to a device yet: use it with a model, or give update_patterns(device=)")
+            from .networks import HierarchicalTemporalMemory
+            self._home = HierarchicalTemporalMemory(32, 64, 4, active_columns=4, device=self.device if device is None else int(device))
+        return self._bind(self._home.engine)
+
+    def __del__(self):
+        knn, self._knn = getattr(self, "_knn", None), None
+        if knn:
+            self.lib.htm_knn_destroy(knn)
+        for ptr, _ in getattr(self, "_bufs", {}).values():
+            self.lib.hipFree(ptr)
+
+    def _call(self, engine, name, *args):
+        what = "htm_knn_" + name
+        rc = getattr(self.lib, what)(self._knn, engine.h, *args)
+        if rc < 0:
+            raise HtmError(f"{what} failed ({rc}): {self.lib.htm_last_error(engine.h).decode()}")
+
+    def info(self):
+        """htm_knn_info of the bound object as a dict (the form of the distance launch among it)."""
+        out = L.HtmKnnInfo(C.sizeof(L.HtmKnnInfo))
+        if self._knn is None or self.lib.htm_knn_info(self._knn, C.byref(out)) != 0:
+            raise RuntimeError("the KNN classifier is not bound to a device yet")
+        return {name: int(getattr(out, name)) for name, _ in L.HtmKnnInfo._fields_[1:]}
+
+    # ---- what a call stores, decided here
+    def check_labels(self, labels):
+        """int [n] -> int32: any value outside [0, labels) is no label (-1)."""
+        g = np.asarray(labels)
+        if g.ndim != 1 or g.dtype.kind not in "iu":
+            raise ValueError(f"labels: int [n], got {g.dtype} {list(g.shape)}")
+        g = g.astype(np.int64)
+        return np.ascontiguousarray(np.where((g < 0) | (g >= self.labels), -1, g).astype(np.int32))
+
+    def stored_by(self, labels, first_step, n, learning):
+        """The patterns a call of n steps would store: step i reads labels[(first_step + i) % len(labels)]."""
+        if not learning or n <= 0:
+            return 0
+        rows = len(labels)
+        whole, rest = divmod(int(n), rows)
+        flags = np.asarray(labels) >= 0
+        at = (int(first_step) + np.arange(rest)) % rows
+        return int(whole * flags.sum() + flags[at].sum())
+
+    def check_room(self, stored):
+        """ValueError for a call that would take count past capacity: refused before anything is enqueued."""
+        if self.count + stored > self.capacity:
+            raise ValueError(f"knn: the call would store {stored} patterns in a store of {self.count} of capacity = {self.capacity} slots")
+
+    def upload_labels(self, engine, labels):
+        """int32 [n] (check_labels) -> the device address of the labels of a run's rows (the object's own array: htm_knn_labels)."""
+        self._bind(engine)
+        labels = np.ascontiguousarray(labels, dtype=np.int32)
+        out = C.c_void_p()
+        self._call(engine, "labels", labels.ctypes.data_as(C.c_void_p), labels.size, C.byref(out))
+        return out.value
+
+    # ---- the update over device memory (what run() calls; nothing here waits)
+    def pairs_buffer(self, engine, n):
+        """The device address of a buffer for n steps' patterns of max_pairs pairs (kept)."""
+        self._bind(engine)
+        return engine.kept_buffer(self._bufs, "pairs", 2 * max(int(n), 1) * self.shape[2], spare=2)
+
+    def enqueue(self, engine, device_pairs, pairs_per_step, n, device_labels, host_labels, first_step, learning, votes=False):
+        """The update over n steps' patterns in device memory, enqueued on `engine`'s stream: device_labels is upload_labels' address
+        of host_labels (int32 [rows]) -> nothing; read(engine, n, votes) after the stream's wait gives the results.  ValueError,
+        with nothing enqueued, for a call that does not fit the store."""
+        self._bind(engine)
+        n = int(n)
+        stored = self.stored_by(host_labels, first_step, n, learning)
+        self.check_room(stored)
+        best = engine.kept_buffer(self._bufs, "best", max(n, 1) * 5, spare=2)
+        all_votes = engine.kept_buffer(self._bufs, "votes", max(n, 1) * self.labels, spare=2) if votes else None
+        self._call(engine, "update", C.c_void_p(device_pairs), int(pairs_per_step), n, C.c_void_p(device_labels), len(host_labels), int(first_step),
+                   int(bool(learning)), C.c_void_p(best), C.c_void_p(all_votes) if all_votes else None)
+        self._count += stored
+        self._total += n
+
+    def read(self, engine, n, votes=False):
+        """(best int32 [n, 5], votes int32 [n, labels] or None) of the last enqueue, after the engine's stream has been waited for."""
+        n = int(n)
+        best = engine.read_words(self._bufs["best"][0], n * 5, np.int32).reshape(n, 5)
+        return best, (engine.read_words(self._bufs["votes"][0], n * self.labels, np.int32).reshape(n, self.labels) if votes else None)
+
+    # ---- the stand-alone door
+    def update_patterns(self, index, words, labels, learning=True, votes=False, device=None):
+        """T further steps from their patterns: index int [T, n], words uint32 [T, n] (pair j of step t is (index[t, j], words[t, j]);
+        a negative index or a zero word contributes nothing), labels int [T] (outside [0, labels): none).  Checked here: the indices
+        of a step are distinct and inside the table, no word has a bit at or above cell_dim, n <= max_pairs, the labelled steps fit
+        the store.  -> (best int32 [T, 5]: label, votes, nearest_overlap, nearest_slot, nearest_step; votes int32 [T, labels] or
+        None)."""
+        if self.shape is None:
+            raise RuntimeError("the KNN classifier does not know the shape of its patterns yet: use it with a model, or give KNNClassifier(shape=)")
+        index, words = check_patterns(index, words, self.units, self.shape[1])
+        T, n = index.shape
+        if not 1 <= n <= self.shape[2]:
+            raise ValueError(f"patterns: 1 to max_pairs = {self.shape[2]} pairs per step, got {n}")
+        labels = self.check_labels(labels)
+        if labels.shape != (T,):
+            raise ValueError(f"labels: int [{T}], got {list(labels.shape)}")
+        self.check_room(self.stored_by(labels, 0, T, learning))
+        if T == 0:
+            return np.zeros((0, 5), np.int32), (np.zeros((0, self.labels), np.int32) if votes else None)
+        engine = self._engine(device)
+        pairs = np.empty((T, n, 2), dtype=np.int32)
+        pairs[..., 0], pairs[..., 1] = index, words.view(np.int32)
+        buf = engine.device_buffer(pairs.nbytes, pairs)
+        try:
+            self.enqueue(engine, buf, n, T, self.upload_labels(engine, labels), labels, 0, learning, votes)
+            engine.sync()
+            best, all_votes = self.read(engine, T, votes)
+            return best.copy(), (all_votes.copy() if votes else None)
+        finally:
+            engine.sync()
+            self.lib.hipFree(buf)
+
+    # ---- reset, state
+    def reset(self):
+        """Empty the store (count = 0; the step total stays)."""
+        if self._knn is None:
+            if self._pending is not None:
+                self._pending = dict(self._empty_state(), total=self._pending["total"])
+            return
+        self._call(self._engine(), "reset")
+        self._count = 0
+
+    def _empty_state(self):
+        pairs = np.zeros((0, self.shape[2], 2), dtype=np.int32)
+        return dict(total=np.int64(0), count=np.int64(0), pairs=pairs, labels=np.zeros(0, np.int32), stamps=np.zeros(0, np.int64))
+
+    def _params(self):
+        return (self.labels, self.k, self.min_overlap, self.capacity) + (self.shape or ())
+
+    def state_dict(self):
+        """{"params": int64 [labels, k, min_overlap, capacity, column_dim, cell_dim, max_pairs], "total": int64, "count": int64,
+        "pairs": int32 [count, max_pairs, 2], "labels": int32 [count], "stamps": int64 [count]} -- the whole state, read from the
+        device."""
+        if self.shape is None:
+            raise RuntimeError("the KNN classifier does not know the shape of its patterns yet")
+        if self._knn is None:
+            state = self._pending if self._pending is not None else self._empty_state()
+        else:
+            engine = self._engine()
+            n, P = self._count, self.shape[2]
+            size = 16 + n * (8 * P + 12)
+            assert size == self.info()["state_bytes"]
+            blob = np.zeros(size, dtype=np.uint8)
+            self._call(engine, "export", blob.ctypes.data_as(C.c_void_p), size)
+            head = blob[:16].view(np.int64)
+            at = 16 + n * P * 8
+            state = dict(total=np.int64(head[0]), count=np.int64(head[1]), pairs=blob[16:at].view(np.int32).reshape(n, P, 2),
+                         stamps=blob[at:at + n * 8].view(np.int64), labels=blob[at + n * 8:].view(np.int32))
+        out = {k: np.array(v)[()] for k, v in state.items()}           # (copies; [()]: a scalar of a 0-d array)
+        return dict(out, params=np.asarray(self._params(), dtype=np.int64))
+
+    def load_state_dict(self, state):
+        """The state of a state_dict() of an object with the same parameters and shape."""
+        params = tuple(int(x) for x in state["params"])
+        if self.shape is None and len(params) == 7:
+            self._set_shape(*params[4:])
+        if params != self._params():
+            raise ValueError(f"the state was saved with parameters {params} (labels, k, min_overlap, capacity, column_dim, cell_dim, max_pairs), "
+                             f"this object has {self._params()}")
+        total, count = int(state["total"]), int(state["count"])
+        pairs = np.ascontiguousarray(state["pairs"], dtype=np.int32)
+        labels = np.ascontiguousarray(state["labels"], dtype=np.int32)
+        stamps = np.ascontiguousarray(state["stamps"], dtype=np.int64)
+        if not 0 <= count <= self.capacity or total < 0:
+            raise ValueError(f"state: 0 <= count <= capacity = {self.capacity} and total >= 0, got count {count}, total {total}")
+        for name, a, want in (("pairs", pairs, (count, self.shape[2], 2)), ("labels", labels, (count,)), ("stamps", stamps, (count,))):
+            if a.shape != want:
+                raise ValueError(f"state['{name}']: {list(want)}, got {list(a.shape)}")
+        if count and (labels.min() < 0 or labels.max() >= self.labels):
+            raise ValueError(f"state['labels']: a label outside [0, {self.labels})")
+        if count and (stamps[0] < 0 or stamps[-1] >= total or (np.diff(stamps) <= 0).any()):
+            raise ValueError("state['stamps']: the stamps ascend and lie below total")
+        clean = dict(total=np.int64(total), count=np.int64(count), pairs=pairs.copy(), labels=labels.copy(), stamps=stamps.copy())
+        if self._knn is None:
+            self._pending = clean
+        else:
+            self._import(self._engine(), clean)
+
+    def _import(self, engine, state):
+        n = int(state["count"])
+        blob = np.concatenate([np.array([state["total"], n], dtype=np.int64).view(np.uint8), state["pairs"].view(np.uint8).ravel(),
+                               state["stamps"].view(np.uint8).ravel(), state["labels"].view(np.uint8).ravel()])
+        self._call(engine, "import", blob.ctypes.data_as(C.c_void_p), blob.size)
+        self._count, self._total = n, int(state["total"])

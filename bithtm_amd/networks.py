@@ -204,7 +204,7 @@ class SpatialPooler:
     # run(noise=): steps per fill of the noise ring (as HierarchicalTemporalMemory.noise_chunk)
     noise_chunk = 1024
 
-    def run(self, inputs, steps, learning=True, use_graph=True, record=None, noise=0.0, noise_seed=None, classifier=None):
+    def run(self, inputs, steps, learning=True, use_graph=True, record=None, noise=0.0, noise_seed=None, classifier=None, knn=None):
         """`steps` timesteps over the rows of the boolean matrix `inputs`, cycled: `steps` times
         process(inputs[t % n] ^ flip_noise(noise_seed, t, input_dim, noise), learning), t being this object's step index, with the
         bank resident in device memory and no per-step host work (htm_sp_run).  Everything the call leaves -- permanences, duty
@@ -219,6 +219,7 @@ class SpatialPooler:
         name, noise outside [0, 1], a run that would pass step 2^32, a Spatial Pooler inside a fused HierarchicalTemporalMemory
         (call its run()), plug-in proximal_projection / boosting / inhibition objects (they step on the host: call process())."""
         _no_classifier(classifier, "SpatialPooler.run()")
+        _no_knn(knn, "SpatialPooler.run()")
         if self._fused:
             raise ValueError("this SpatialPooler is fused into a HierarchicalTemporalMemory; call its run()")
         if not self._plain:
@@ -491,7 +492,7 @@ class TemporalMemory:
             return eng
         return self._recreate(eng, max(n_active, 2 * eng.active_columns))
 
-    def run(self, active_columns, steps, learning=True, use_graph=True, record=None, resets=None, classifier=None):
+    def run(self, active_columns, steps, learning=True, use_graph=True, record=None, resets=None, classifier=None, knn=None):
         """`steps` timesteps over the rows of `active_columns` (int [n_rows, n]: n distinct column ids per row, in any order),
         cycled: `steps` times process(SimpleNamespace(active_column=active_columns[t % n_rows]), learning=learning), t being this
         object's step index, with the lists resident in device memory and no per-step host work (htm_tm_run).  Everything the
@@ -504,6 +505,7 @@ class TemporalMemory:
         ValueError for cell_dim above 64 and for a plug-in distal_projection (both step on the host: call process()), and for a
         Temporal Memory inside a fused HierarchicalTemporalMemory (call its run())."""
         _no_classifier(classifier, "TemporalMemory.run()")
+        _no_knn(knn, "TemporalMemory.run()")
         if self._fused:
             raise ValueError("this TemporalMemory is fused into a HierarchicalTemporalMemory; call its run()")
         if self.cell_dim > 64:
@@ -627,6 +629,10 @@ class RunRecord:
                                                        65536) and, for a classifier of an encoder field, classified_value float64
                                                        [steps, H] = field.value_of(bucket); else None
       class_distribution             int32[steps, H, buckets]   all probabilities in units of 2^-16 ("class_distribution", else None)
+      knn_label, knn_votes, knn_overlap, knn_nearest_slot, knn_nearest_step   int32[steps]   with run(knn=): the label most of the
+                                                       KNNClassifier's nearest stored patterns carry (-1: no neighbour) and its votes,
+                                                       the nearest one's overlap, slot and storing step (knn.py); else None
+      knn_votes_all                  int32[steps, labels]   every label's votes ("knn_votes_all", else None)
     and, from the counters, the per-step report of example.py:55-57 and the raw anomaly score:
       correct_columns   = active_columns - bursting_columns
       incorrect_columns = predicted_columns_before - correct_columns
@@ -634,7 +640,7 @@ class RunRecord:
 
     def __init__(self, step_index, counters=None, active_column=None, column_prediction=None, predicted_input=None,
                  predicted_bucket=None, predicted_score=None, predicted_value=None, anomaly_likelihood=None, classified=None,
-                 class_distribution=None, classified_field=None):
+                 class_distribution=None, classified_field=None, knn=None, knn_votes_all=None):
         self.step_index = np.asarray(step_index, dtype=np.int64)
         self.fields = tuple(f for f, v in zip(RECORD_FIELDS, (counters, active_column, column_prediction, predicted_input, predicted_bucket))
                             if v is not None)
@@ -652,6 +658,9 @@ class RunRecord:
             if classified_field is not None:
                 self.classified_value = classified_field.value_of(self.classified_bucket)
         self.class_distribution = class_distribution
+        for i, name in enumerate(KNN_ROW):      # int32 [steps, 5]: knn.ROW order
+            setattr(self, name, None if knn is None else np.ascontiguousarray(knn[:, i]))
+        self.knn_votes_all = knn_votes_all
 
     def __len__(self):
         return len(self.step_index)
@@ -674,6 +683,9 @@ class RunRecord:
     @property
     def log_likelihood(self):
         return None if self.anomaly_likelihood is None else log_likelihood(self.anomaly_likelihood)
+
+
+KNN_ROW = ("knn_label", "knn_votes", "knn_overlap", "knn_nearest_slot", "knn_nearest_step")
 
 
 def _record_fields(record):
@@ -839,7 +851,8 @@ class HierarchicalTemporalMemory:
         return ring, rows, None if resets is None else ring_resets
 
     def run(self, inputs, steps, learning=True, use_graph=True, pipeline=True, continuing=False, record=None, resets=None,
-            noise=0.0, noise_seed=None, encoder=None, likelihood=None, classifier=None, targets=None, classifier_learning=None):
+            noise=0.0, noise_seed=None, encoder=None, likelihood=None, classifier=None, targets=None, classifier_learning=None,
+            knn=None, labels=None, knn_learning=None):
         """`steps` timesteps over the rows of the boolean matrix `inputs`, cycled, with the input
         bank resident in device memory and no per-step host work (the loop of example.py:48-53).
         Returns None; read `temporal_memory.last_state` or call process() afterwards.  `continuing=True`: the
@@ -874,7 +887,15 @@ class HierarchicalTemporalMemory:
         bucket of classifier.field among the encoder's fields, taken with encoder.bucket on the host.  A step's target is its own
         row's; a reset flag of a row also empties the classifier's history.  `classifier_learning`: None follows `learning`.
         RunRecord.classified_bucket, _probability, _value hold each step's prediction per horizon, and with "class_distribution"
-        named in `record`, RunRecord.class_distribution all probabilities."""
+        named in `record`, RunRecord.class_distribution all probabilities.
+        `knn`: a KNNClassifier -- it rides on the run as the classifier does, over the same captured active-cell words (one
+        capture launch per step, shared when both are given), its update enqueued next to the classifier's behind each batch
+        (htm_knn_update: a fixed number of launches per 64 steps).  `labels`: int [rows of inputs], the label of each row (-1, or
+        anything outside [0, knn.labels): none), uploaded once; None: nothing is labelled.  A step's label is its own row's; a
+        labelled step of a learning call is stored after it was inferred.  `knn_learning`: None follows `learning`.  ValueError
+        before anything is enqueued when the call's labelled steps do not fit knn.capacity.  The model's resets do not touch the
+        object.  RunRecord.knn_label, knn_votes, knn_overlap, knn_nearest_slot, knn_nearest_step hold each step's result, and with
+        "knn_votes_all" named in `record`, RunRecord.knn_votes_all every label's votes."""
         if classifier is not None:
             from .sdr_classifier import SDRClassifierBank
             if isinstance(classifier, SDRClassifierBank):            # (many streams; this call has one)
@@ -891,6 +912,17 @@ class HierarchicalTemporalMemory:
             cls = dict(clf=classifier, distribution=distribution, learn=bool(learning if classifier_learning is None else classifier_learning))
         elif targets is not None or classifier_learning is not None:
             raise ValueError("run(): targets= and classifier_learning= go with classifier=")
+        near = None
+        if knn is not None:
+            named = () if record is None or record is True else ((record,) if isinstance(record, str) else tuple(record))
+            if "knn_votes_all" in named:
+                record = tuple(f for f in named if f != "knn_votes_all") or None
+            record = _with_counters(record)
+            if eng.shard_world > 1:
+                raise ValueError("run(knn=): not available on a column-sharded model")
+            near = dict(knn=knn, votes="knn_votes_all" in named, learn=bool(learning if knn_learning is None else knn_learning))
+        elif labels is not None or knn_learning is not None:
+            raise ValueError("run(): labels= and knn_learning= go with knn=")
         if likelihood is not None:
             if likelihood.streams != 1:
                 raise ValueError(f"run(likelihood=): an AnomalyLikelihood of one stream, got {likelihood.streams}")
@@ -905,12 +937,19 @@ class HierarchicalTemporalMemory:
             classifier._set_shape(*model_shape(eng))
             cls["host_targets"] = _classifier_targets(classifier, targets, inputs, encoder)
             cls["rows"] = inputs.shape[0]
+        if near is not None:
+            from .sdr_classifier import model_shape
+            knn._set_shape(*model_shape(eng))
+            near["host_labels"] = knn.check_labels(np.full(inputs.shape[0], -1) if labels is None else labels)
+            if near["host_labels"].shape != (inputs.shape[0],):
+                raise ValueError(f"labels: one label per row of inputs ({inputs.shape[0]}), got {near['host_labels'].shape[0]}")
+            knn.check_room(knn.stored_by(near["host_labels"], eng.steps % inputs.shape[0], steps, near["learn"]))
         bank = _cached_bank(self, eng, inputs, encoder=encoder)
         # A pool left at its default size grows like the reference's arrays (utils.py:113-135): the run is cut into batches
         # the free segments are expected to last (2 x active_columns new segments per step: every column bursting, twice),
         # with a look at the pool between them.  An overflow inside a batch is still reported, never silent.
         k = self.active_columns
-        call = _BatchedCall([self.temporal_memory], fields, encoder, likelihood is not None, classifier)
+        call = _BatchedCall([self.temporal_memory], fields, encoder, likelihood is not None, classifier, knn)
         del eng                                     # (the pool step may re-create the engine: the old one goes, device memory and all, as it does)
         refuse = "the segment pool has to grow in the middle of a streamed run(): end the stream (a run() without continuing=True) first"
 
@@ -931,8 +970,10 @@ class HierarchicalTemporalMemory:
                 if "targets" not in cls:
                     cls["targets"] = classifier.upload_targets(eng, cls["host_targets"])
                 cls["resets"] = None if resets is None else eng.upload_resets(resets)
+            if near is not None and near.get("engine") is not eng:      # (the labels by the row of `inputs` a step reads, as the targets)
+                near["labels"], near["engine"] = knn.upload_labels(eng, near["host_labels"]), eng
             call.add([eng.run(src, rows, n, learning=learning, use_graph=use_graph, pipeline=pipeline, continuing=continuing and last,
-                              record=fields, resets=bits, encoder=encoder, likelihood=likelihood, classifier=cls)])
+                              record=fields, resets=bits, encoder=encoder, likelihood=likelihood, classifier=cls, knn=near)])
             self._streaming = bool(continuing and last and pipeline)
         return call.finish([steps], [k])[0]
 
@@ -999,7 +1040,7 @@ class HierarchicalTemporalMemory:
         return kept[1]
 
     def lookahead(self, inputs, steps, horizon, min_votes=1, max_bits=0, every=1, learning=True, use_graph=True, record=None,
-                  resets=None, noise=0.0, noise_seed=None, encoder=None, classifier=None):
+                  resets=None, noise=0.0, noise_seed=None, encoder=None, classifier=None, knn=None):
         """Rolling look-ahead: the model runs over `inputs` as run() does (learning or not) and after every `every` steps says
         what it expects over the next `horizon` steps, its own stream unmoved.  Bit for bit, with W = steps // every:
             for j in range(W):
@@ -1013,6 +1054,7 @@ class HierarchicalTemporalMemory:
         every < 1, and what fork(), run() and forecast() refuse.  `encoder`: as run()'s -- `inputs` are then values, and the
         record may name "predicted_value" (decoded once per chunk behind its windows)."""
         _no_classifier(classifier, "lookahead()")
+        _no_knn(knn, "lookahead()")
         steps, horizon, every = int(steps), int(horizon), int(every)
         if horizon < 1 or every < 1:
             raise ValueError(f"lookahead(): horizon and every must be at least 1, got {horizon} and {every}")
@@ -1136,7 +1178,8 @@ class HierarchicalTemporalMemory:
         eng.encode_votes(min_votes, max_bits, bank, 1, 0)
         return eng.read_bank(bank, 1)[0]
 
-    def forecast(self, steps, min_votes=1, max_bits=0, record=None, use_graph=True, learning=False, noise=0.0, encoder=None, classifier=None):
+    def forecast(self, steps, min_votes=1, max_bits=0, record=None, use_graph=True, learning=False, noise=0.0, encoder=None, classifier=None,
+                 knn=None):
         """What the model expects over the next `steps` steps: from its current state, `steps` times
             x = encode_votes(predicted_input(), min_votes, max_bits);  process(x, learning=False)
         with the whole loop on the device (htm_set_run_feedback: each step's votes are encoded into the bank row the next step
@@ -1148,6 +1191,7 @@ class HierarchicalTemporalMemory:
         ValueError: a forecast reads the rows the model itself wrote, and flipping them is not offered.  `encoder`: the
         ScalarEncoder a "predicted_value" record decodes with (forecast_values() is the call that returns values)."""
         _no_classifier(classifier, "forecast()")
+        _no_knn(knn, "forecast()")
         if learning:
             raise ValueError("forecast(): learning from the model's own output is not available (learning=False only)")
         if _noise_threshold_arg(noise):
@@ -1271,14 +1315,16 @@ class InferenceView(HierarchicalTemporalMemory):
     compute = process
 
     def run(self, inputs, steps, learning=False, use_graph=True, pipeline=True, continuing=False, record=None, resets=None,
-            noise=0.0, noise_seed=None, encoder=None, likelihood=None, classifier=None, targets=None, classifier_learning=None):
+            noise=0.0, noise_seed=None, encoder=None, likelihood=None, classifier=None, targets=None, classifier_learning=None,
+            knn=None, labels=None):
         """As the parent's run(), with learning=False.  `classifier_learning` may be True: the classifier's weights are its own, not
-        the parent's."""
+        the parent's.  `knn`: a view never stores -- its steps are inferred over the store as it is (`labels` are taken and ignored)."""
         self._no_learning(learning, "run()")
         self._check_parent()
         return super().run(inputs, steps, learning=False, use_graph=use_graph, pipeline=pipeline, continuing=continuing,
                            record=record, resets=resets, noise=noise, noise_seed=noise_seed, encoder=encoder, likelihood=likelihood,
-                           classifier=classifier, targets=targets, classifier_learning=classifier_learning)
+                           classifier=classifier, targets=targets, classifier_learning=classifier_learning, knn=knn, labels=labels,
+                           knn_learning=None if knn is None else False)
 
     def reset(self):
         self._check_parent()
@@ -1427,6 +1473,13 @@ def _no_classifier(classifier, what):
                          "SDRClassifierBank of as many streams as the group has members")
 
 
+def _no_knn(knn, what):
+    """The calls a KNNClassifier does not ride on: refused, never silently ignored."""
+    if knn is not None:
+        raise ValueError(f"{what}: knn= is not available here -- a KNNClassifier rides on HierarchicalTemporalMemory.run() and "
+                         "InferenceView.run(), or takes patterns through update_patterns()")
+
+
 def _classifier_targets(classifier, targets, inputs, encoder):
     """run(classifier=, targets=): the target bucket of every row of `inputs` -> int32 [rows]."""
     if targets is None:
@@ -1442,7 +1495,7 @@ def _classifier_targets(classifier, targets, inputs, encoder):
     return targets
 
 
-def _join_record(parts, fields, first_step, steps, k, column_dim, input_dim=0, encoder=None, likelihood=False, classifier=None):
+def _join_record(parts, fields, first_step, steps, k, column_dim, input_dim=0, encoder=None, likelihood=False, classifier=None, knn=None):
     """One contiguous RunRecord from the per-batch records of a run(record=...) (Engine.run's dicts), however many batches the
     pool's growth cut the call into."""
     empty = {"counters": np.zeros((0, len(RECORD_COUNTERS)), np.int32), "active_column": np.zeros((0, k), np.int32),
@@ -1464,6 +1517,10 @@ def _join_record(parts, fields, first_step, steps, k, column_dim, input_dim=0, e
         if parts and parts[0]["class_distribution"] is not None:
             whole["class_distribution"] = np.concatenate([p["class_distribution"] for p in parts])
         whole["classified_field"] = classifier.field
+    if knn is not None:                             # (likewise: each batch's part carries its steps' result rows)
+        whole["knn"] = np.concatenate([p["knn"] for p in parts]) if parts else np.zeros((0, 5), np.int32)
+        if parts and parts[0]["knn_votes_all"] is not None:
+            whole["knn_votes_all"] = np.concatenate([p["knn_votes_all"] for p in parts])
     return RunRecord(first_step + np.arange(steps, dtype=np.int64), **whole)
 
 
@@ -1516,8 +1573,8 @@ class _BatchedCall:
     the model's engine): the parts every batch adds per member, the step each started at, and at the end the new last_state, the
     sticky flags and one RunRecord per member."""
 
-    def __init__(self, tms, fields, encoder=None, likelihood=False, classifier=None):
-        self.tms, self.fields, self.encoder, self.likelihood, self.classifier = tms, fields, encoder, likelihood, classifier
+    def __init__(self, tms, fields, encoder=None, likelihood=False, classifier=None, knn=None):
+        self.tms, self.fields, self.encoder, self.likelihood, self.classifier, self.knn = tms, fields, encoder, likelihood, classifier, knn
         self.first = [tm._engine.steps for tm in tms]
         self.parts = [[] for _ in tms]
 
@@ -1539,5 +1596,5 @@ class _BatchedCall:
             return [None] * len(self.tms)
         if read is not None:
             self.add(read())
-        return [_join_record(p, self.fields, f, n, k, tm.column_dim, tm._engine.input_dim, self.encoder, self.likelihood, self.classifier)
+        return [_join_record(p, self.fields, f, n, k, tm.column_dim, tm._engine.input_dim, self.encoder, self.likelihood, self.classifier, self.knn)
                 for p, f, n, k, tm in zip(self.parts, self.first, steps, ks, self.tms)]

@@ -1044,6 +1044,64 @@ int htm_classifiers_tick(htm_group *g, const double *values, const htm_scalar_fi
                          htm_likelihood *lk, double *likelihood, htm_classifier *clf, const int32_t *targets, int32_t learn, int32_t *best,
                          int32_t *dist);
 
+/* KNN classifier over active-cell patterns (the definition is bithtm_amd/knn.py, which the device equals bit
+ * for bit): the patterns of labelled steps are stored, a later step gets the label most of its k nearest stored patterns carry.  An
+ * htm_knn object holds in device memory the store -- `capacity` slots of max_pairs (int32 index, uint32 word) pairs (unused pairs
+ * (-1, 0)), an int32 label and an int64 stamp (the object's step total at the storing step) per slot -- and the scratch of an update;
+ * the slots in use (`count`) and the step total are kept on the HOST: every store is decided by what the host knows, nothing is read
+ * back.  Patterns are htm_classifier_update's (htm_set_run_active_cells captures them); overlap(P, Q) is the sum of popcount(wP & wQ)
+ * over the indices both hold, live bits only.
+ *
+ * htm_knn_update: n_steps steps over device_pairs [n_steps][pairs_per_step] (DEVICE memory), step i with the label device_labels
+ * [(first_step + i) % n_labels] (outside [0, labels): none).  Each step first infers over the store as it is -- candidates: the slots
+ * with overlap >= min_overlap; neighbours: the first k by (overlap descending, slot ascending) -- into device_best [n_steps][5] (the
+ * lowest label with the most votes, its votes, the first neighbour's overlap, slot and the low 32 bits of its stamp; -1, 0, 0, -1, -1
+ * without a neighbour) and device_votes [n_steps][labels] (or NULL); then, with learn != 0 and a label, its pattern goes into slot
+ * `count` (the store never overwrites).  Everything is enqueued on h's stream, nothing waits: two launches per call that stores
+ * (kknn_place, kknn_append), then per chunk of 64 steps kknn_distance_lds and kknn_select -- or, where one dense table of column_dim x
+ * WPC words exceeds 48 KiB, kknn_scatter, kknn_distance_global, kknn_select, kknn_scatter.  A learning call takes its labels from
+ * htm_knn_labels: that call copies n_labels HOST labels into the object's own device array (on h's stream; the words are read before
+ * it returns), keeps them on the host and returns the device array's address in *device_labels; a call with learn != 0 must pass
+ * that address and that n_labels, so that the host can count what the call stores.  A call with learn == 0 may read any device array.
+ * htm_knn_reset empties the store (count = 0; the total stays).  htm_knn_export / _import copy the state to / from HOST memory after a
+ * wait for h's stream: int64 total; int64 count; then count x max_pairs pairs, count int64 stamps, count int32 labels -- 16 + count x
+ * (8 max_pairs + 12) bytes, htm_knn_info's state_bytes.  An object may be used through any handle of its device; the order between
+ * calls is that of the streams they come on.
+ *
+ * HTM_ERR_ARGUMENT, nothing enqueued, the object as it was: NULL pointers; a wrong struct_bytes; labels outside [1, 1024], k outside
+ * [1, 64], min_overlap outside [1, 65535], capacity outside [1, 2^20], cell_dim outside [1, 64], units no positive multiple of
+ * cell_dim, max_pairs outside [1, 2047]; pairs_per_step outside [1, max_pairs]; n_steps < 0, n_labels < 1, first_step < 0; a learning
+ * call with other labels than htm_knn_labels'; a handle on another device; a state of another size than its own count says, with count
+ * above capacity, a label outside [0, labels), or stamps that do not ascend below total.  HTM_ERR_CAPACITY, likewise: a call whose
+ * labelled steps would take count past capacity.  HTM_ERR_STATE: a column-sharded handle. */
+typedef struct htm_knn htm_knn;
+typedef struct htm_knn_config {
+    uint32_t struct_bytes;
+    int32_t labels, k, min_overlap, capacity, units, cell_dim, max_pairs;
+} htm_knn_config;
+typedef struct htm_knn_info_t {
+    uint32_t struct_bytes;
+    int32_t labels, k, min_overlap, capacity, units, cell_dim, max_pairs;
+    int32_t count;                  /* slots in use */
+    int32_t table_in_lds;           /* 1: kknn_distance_lds; 0: the global-table form */
+    int32_t queries_per_block;      /* queries one block of the distance launch stages: the store is read once per that many steps */
+    int32_t bin_shift;              /* the select's histogram bins overlaps >> bin_shift */
+    int64_t total;                  /* steps seen */
+    int64_t state_bytes;            /* of htm_knn_export now */
+    int64_t device_bytes;           /* device memory the object holds */
+} htm_knn_info_t;
+
+int htm_knn_create(htm_handle *h, const htm_knn_config *cfg, htm_knn **out);
+void htm_knn_destroy(htm_knn *knn);
+int htm_knn_labels(htm_knn *knn, htm_handle *h, const int32_t *host_labels, int32_t n_labels, const int32_t **device_labels);
+int htm_knn_update(htm_knn *knn, htm_handle *h, const void *device_pairs, int32_t pairs_per_step, int32_t n_steps,
+                   const int32_t *device_labels, int32_t n_labels, int32_t first_step, int32_t learn, int32_t *device_best,
+                   int32_t *device_votes);
+int htm_knn_reset(htm_knn *knn, htm_handle *h);
+int htm_knn_export(htm_knn *knn, htm_handle *h, void *host_state, int64_t bytes);
+int htm_knn_import(htm_knn *knn, htm_handle *h, const void *host_state, int64_t bytes);
+int htm_knn_info(const htm_knn *knn, htm_knn_info_t *out);
+
 #ifdef __cplusplus
 }
 #endif
