@@ -56,6 +56,7 @@
 #include "htm_likelihood.h"
 #include "htm_classifier.h"
 #include "htm_knn.h"
+#include "htm_handover.h"
 
 // ------------------------------------------------------------------------------------------
 // host side
@@ -74,6 +75,7 @@ struct Knobs {
     uint32_t trace_until;
     int lean, lean2_classify, lean2_order, step_split, fuse_tm, shard_window, step_window, tail_rows, scan_large, scan_large_above, scan_dyn;
     int defer_tail, shared_scan, shared_members;
+    int handover_cap;                     // BITHTM_HANDOVER_LDS_CAP (test knob)
     int lean_overlap, lean_learn, lean_learn_large, lean_scan, lean_scan_large, scan_blocks, sel_launch_digits;
     int cand_d, cand_pairwise, cls_rows_max, win_offset, cand_zoom, cand_speculate, cand_take_all, poll_delay, cand_others;   // (Dev's)
 };
@@ -627,12 +629,20 @@ static int lean2_classify_blocks(const htm_handle *h, int learning) {
 // The two-launch schedule's first launch (k_act_mid_rows, htm_pipeline.h) for the step of parity p, its roles counted in the
 // kernel's order.  n_overlap > 0: the coming step's overlap rides along (a steady-state step); else the duty cycle has blocks
 // of its own (the last step of a call, a host-fed step).  The profile name and the LDS bytes are the call site's.
-static void launch_act_mid_rows(htm_handle *h, const char *name, size_t lds, int p, int learning, const uint32_t *bank, int n_inputs, int n_overlap) {
+// handover: the batched run's form of the launch (k_first_handover, htm_handover.h: block 0 keeps its list in the dynamic LDS, so
+// the launch asks for SEL_BINS * 4 bytes whether or not an overlap role rides along); else k_act_mid_rows
+static void launch_act_mid_rows(htm_handle *h, const char *name, size_t lds, int p, int learning, const uint32_t *bank, int n_inputs, int n_overlap,
+                                bool handover = false) {
     Dev &d = h->d;
     const int n_act = act_blocks(d), n_cls = lean2_classify_blocks(h, learning), n_rows = learning ? d.k : 0;
     const int n_duty = n_overlap ? 0 : h->sz.c256_blocks, n_clear = d.WPC * h->sz.c256_blocks;
-    LAUNCH_ON(h, h->stream, lds, name, k_act_mid_rows, n_act + 1 + n_cls + n_rows + n_overlap + n_duty + n_clear + h->sz.zero_blocks, 256,
-              d, p, d.k, n_act, learning, n_cls, bank, n_inputs, n_rows, h->sz.G, n_overlap, n_duty, n_clear, h->knob.lean2_order);
+    const int grid = n_act + 1 + n_cls + n_rows + n_overlap + n_duty + n_clear + h->sz.zero_blocks;
+    if (handover)
+        LAUNCH_ON(h, h->stream, std::max(lds, (size_t)SEL_BINS * 4), name, k_first_handover, grid, 256,
+                  d, p, d.k, n_act, learning, n_cls, bank, n_inputs, n_rows, h->sz.G, n_overlap, n_duty, n_clear, h->knob.lean2_order, h->knob.handover_cap);
+    else
+        LAUNCH_ON(h, h->stream, lds, name, k_act_mid_rows, grid, 256,
+                  d, p, d.k, n_act, learning, n_cls, bank, n_inputs, n_rows, h->sz.G, n_overlap, n_duty, n_clear, h->knob.lean2_order);
 }
 
 // sp_done: the winner list of this step exists (the previous step's last launch, or the cold start).  next_sp: select
@@ -641,7 +651,7 @@ static void enqueue_lean(htm_handle *h, int p, int learning, const uint32_t *ban
     Dev &d = h->d;
     if (h->knob.lean == 2) {                        // the two-launch schedule: both of these in one (htm_pipeline.h)
         launch_act_mid_rows(h, "tm_activate+tm_mid+sp_learn+sp_overlap", (size_t)SEL_BINS * 4, p, learning, bank, n_inputs,
-                            plan.next_sp ? h->sz.lean2_overlap_blocks : 0);
+                            plan.next_sp ? h->sz.lean2_overlap_blocks : 0, true);
     } else {
         const int n_act = act_blocks(d), n_rows = learning ? d.k : 0;
         const int n_cls = learning ? kClassifyBlocks : 0, n_ov = plan.next_sp ? h->sz.lean_overlap_blocks : 0;
@@ -974,6 +984,8 @@ static Knobs read_knobs() {
     k.cand_d = env_int("BITHTM_CAND_D", CAND_D, 0, CAND_D);
     k.cand_pairwise = env_int("BITHTM_CAND_PAIRWISE", CAND_PAIRWISE, 0);
     k.cls_rows_max = env_int("BITHTM_CLASSIFY_WORDS_ABOVE", -1, 0);
+    // (test knob: entries of the list of winners without a segment that block 0 of k_first_handover keeps in LDS; the rest goes through memory)
+    k.handover_cap = env_int("BITHTM_HANDOVER_LDS_CAP", HANDOVER_LIST_MAX, 0, HANDOVER_LIST_MAX);
     k.win_offset = env_int("BITHTM_SEL_WINDOW_OFFSET", 0, 0);
     k.cand_zoom = env_int("BITHTM_CAND_ZOOM", -1);      // (the pairs above which a merge is cut to a sub-bin; -1 = more pairs than blocks by a quarter)
     k.cand_speculate = env_flag("BITHTM_CAND_SPECULATE", 1);     // (0 = always the general path)
@@ -1059,8 +1071,10 @@ static void size_launches(htm_handle *h) {
         // overlap and the winner rows -- a block that waits for a slot starts a round late, and the middle role's blocks wait for
         // the activation whenever they start (bench shape: 164 + 512 + 1 311 + 1 of 2 048 slots leave 60; small models get 384)
         int per_cu = 0, resident = 1536;
-        if (have_prop && hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void *)k_act_mid_rows, 256, (size_t)SEL_BINS * 4) == hipSuccess)
-            resident = per_cu * z.cus;
+        int per_cu_run = 0;                           // (the batched run's form of the launch, k_first_handover: the same 8 blocks per CU)
+        if (have_prop && hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void *)k_act_mid_rows, 256, (size_t)SEL_BINS * 4) == hipSuccess &&
+            hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu_run, (const void *)k_first_handover, 256, (size_t)SEL_BINS * 4) == hipSuccess)
+            resident = std::min(per_cu, per_cu_run) * z.cus;
         else
             (void)hipGetLastError();
         // (the overlap counted as the column-major role's blocks, also where the launch's own role reads the byte planes and takes

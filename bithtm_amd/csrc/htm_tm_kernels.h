@@ -320,8 +320,15 @@ __device__ __forceinline__ T ld_agent(const T *ptr, int same_launch) {
 // fan-in there; everything the role can fetch and decide WITHOUT the activation's output is done before (a classification
 // block: the match words, its first rows' owner cells, jitter, prediction bits and per-cell maxima -- three round trips that
 // now run under the activation instead of behind it)
+// PRE_NSYN (k_first_handover, htm_handover.h): a classified row's synapse count is fetched with the rest of the row, BEFORE the wait,
+// and `count | SEG_BUSY` is stored behind the winner bit -- not read, changed and written there, a round trip at the end of the
+// launch's second longest chain.  Nothing in the launch writes the count of a row with a match bit in between: each row is
+// classified by one thread; block 0 binds rows at or above the scan's count, which have no bit, and rows with fewer synapses than
+// the matching threshold -- a row with a match bit had at least that many when the last launch ended (the scan counted them, and
+// a row the learning role pruned or grew was scanned again by that role, which sets or leaves out the bit itself); the learning
+// role and the scan are the next launch's.
 struct NoWait { __device__ __forceinline__ void operator()() const {} };
-template <int BS, typename Wait = NoWait>
+template <int BS, typename Wait = NoWait, bool PRE_NSYN = false>
 __device__ __forceinline__ void role_mid(const Dev &d, int p, int n_active, int want_winner, int learning, int blk, int n_cls, int same_launch = 0,
                                          Wait wait = Wait()) {
     Counters *c = d.ctr;
@@ -339,7 +346,8 @@ __device__ __forceinline__ void role_mid(const Dev &d, int p, int n_active, int 
         // learns if its cell is a winner), then the winner bit
         bool waited = false;
         auto wait_once = [&]() { if (!waited) { wait(); waited = true; } };           // (block-uniform call sites)
-        auto gather = [&](int seg, bool &cand, bool &punish, int &cell) {
+        auto gather = [&](int seg, bool &cand, bool &punish, int &cell, int &nsyn) {
+            if (PRE_NSYN) nsyn = d.seg_nsyn[seg];
             const uint32_t info = d.seg_info[seg];
             cell = d.seg_cell[seg];
             const float jit = d.seg_jit[seg];
@@ -355,6 +363,9 @@ __device__ __forceinline__ void role_mid(const Dev &d, int p, int n_active, int 
         auto decide = [&](bool cand, int cell) {                                          // :268
             return cand && ((ld_agent(&d.win[p][cell >> 5], same_launch) >> (cell & 31)) & 1u);
         };
+        auto mark_busy = [&](int seg, int nsyn) {
+            if (PRE_NSYN) d.seg_nsyn[seg] = nsyn | (int)SEG_BUSY; else d.seg_nsyn[seg] |= (int)SEG_BUSY;
+        };
         // (... up to 8 rows per thread; 2 where the role's blocks wait for the activation of their own launch: few blocks, whatever they
         // do after the wait is at the end of the launch's longest chain)
         if (n <= (d.cls_rows_max >= 0 ? d.cls_rows_max : (same_launch ? 2 : 8) * n_cls * BS)) {
@@ -363,11 +374,11 @@ __device__ __forceinline__ void role_mid(const Dev &d, int p, int n_active, int 
             for (int i0 = (blk - 1) * BS; i0 < n; i0 += n_cls * BS) {
                 const int seg = i0 + (int)threadIdx.x;
                 bool cand = false, punish = false;
-                int cell = 0;
-                if (seg < n && ((d.match_bits[q][seg >> 5] >> (seg & 31)) & 1u)) gather(seg, cand, punish, cell);
+                int cell = 0, nsyn = 0;
+                if (seg < n && ((d.match_bits[q][seg >> 5] >> (seg & 31)) & 1u)) gather(seg, cand, punish, cell, nsyn);
                 wait_once();
                 const bool learn = decide(cand, cell);
-                if (learn || punish) d.seg_nsyn[seg] |= (int)SEG_BUSY;
+                if (learn || punish) mark_busy(seg, nsyn);
                 const u64 ml = __ballot(learn), mp = __ballot(punish);
                 const int n_l = __popcll(ml), n_p = __popcll(mp);
                 if (n_l + n_p == 0) continue;
@@ -423,11 +434,11 @@ __device__ __forceinline__ void role_mid(const Dev &d, int p, int n_active, int 
                 const bool on = i < listed && ((s_bits[min(i, BS - 1)] >> (threadIdx.x & 31)) & 1u);
                 const int seg = on ? s_words[i] * 32 + (int)(threadIdx.x & 31) : 0;
                 bool cand = false, punish = false;
-                int cell = 0;
-                if (on) gather(seg, cand, punish, cell);
+                int cell = 0, nsyn = 0;
+                if (on) gather(seg, cand, punish, cell, nsyn);
                 wait_once();
                 const bool learn = decide(cand, cell);
-                if (learn || punish) d.seg_nsyn[seg] |= (int)SEG_BUSY;
+                if (learn || punish) mark_busy(seg, nsyn);
                 const u64 ml = __ballot(learn), mp = __ballot(punish);
                 const int n_l = __popcll(ml), n_p = __popcll(mp);
                 if (n_l + n_p == 0) continue;

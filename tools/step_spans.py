@@ -4,7 +4,7 @@
 tools/step_timeline.py shows two consecutive steps in detail; the trace holds no more than two.  This repeats the run
 with the traced pair moved along and prints, per step, the span of each launch and when the last block of each role
 of the last launch ended -- which role the launch waited for, and how often; in the two-launch schedule the same for the
-first launch (activation, overlap, middle role, winner rows).
+first launch (activation, overlap, the middle role's block 0 and its classification blocks, winner rows).
 
     python tools/step_spans.py [pairs]
 """
@@ -17,6 +17,7 @@ os.environ["BITHTM_TRACE"] = "1"
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import bench  # noqa: E402
 
+FIRST = ("act", "overlap", "mid0", "cls", "rows")      # (the first launch's roles as printed: mid0 = the middle role's block 0, cls = its classification blocks)
 WARMUP = int(os.environ.get("BITHTM_SPANS_WARMUP", 1500))      # (the state: bench.py times at 8 604 steps by default, 979 at the driver's arguments)
 
 
@@ -31,9 +32,9 @@ def main():
     n_act, n_ov, n_cls = (k * 32 + 255) // 256, c256, int(os.environ.get("BITHTM_LEAN2_CLASSIFY", 32))
     first_roles, at = [], 0                          # (k_act_mid_rows' roles in the grid's order)
     for digit in os.environ.get("BITHTM_LEAN2_ORDER", "0312"):
-        n = {"0": n_act, "1": 1 + n_cls, "2": k, "3": n_ov}[digit]
-        first_roles.append((at, at + n, {"0": "act", "1": "mid", "2": "rows", "3": "overlap"}[digit]))
-        at += n
+        for name, n in {"0": (("act", n_act),), "1": (("mid0", 1), ("cls", n_cls)), "2": (("rows", k),), "3": (("overlap", n_ov),)}[digit]:
+            first_roles.append((at, at + n, name))
+            at += n
     rows = []
     for u in range(pairs):
         steps = 35 + 2 * u
@@ -61,20 +62,25 @@ def main():
             launches = (0, 2) if two else (0, 1, 2)
             if all(i in rec for i in launches) and "scan" in rec:
                 rows.append((rec[0][0], [(rec[i][1] - rec[i][0]) / 100 for i in launches], rec["emit"], rec["learn"], rec["scan"],
-                             [rec.get(n, 0.0) for n in ("act", "overlap", "mid", "rows")]))
+                             [rec.get(n, 0.0) for n in FIRST]))
         del htm, eng
     if two:
-        print("launch spans (us): act_mid_rows  learn_scan_emit | last block of act / overlap / mid / rows | of emit / learn / scan")
+        print("launch spans (us): act_mid_rows  learn_scan_emit | last block of act / overlap / mid0 / cls / rows | of emit / learn / scan")
     else:
         print("launch spans (us): act_rows  mid_overlap  learn_scan_emit | last block of emit / learn / scan")
     for _, sp, e, l, s, fr in rows:
         who = max((e, "emit"), (l, "learn"), (s, "scan"))[1]
         if two:
-            who0 = max(zip(fr, ("act", "overlap", "mid", "rows")))[1]
+            who0 = max(zip(fr, FIRST))[1]
             print(f"  {sp[0]:6.2f} {sp[1]:6.2f} | " + " ".join(f"{x:6.2f}" for x in fr) + f"  <- {who0:7s} | {e:6.2f} {l:6.2f} {s:6.2f}  <- {who}")
         else:
             print(f"  {sp[0]:6.2f} {sp[1]:6.2f} {sp[2]:6.2f} | {e:6.2f} {l:6.2f} {s:6.2f}  <- {who}")
     a = np.array([r[1] for r in rows])
+    if two:
+        f = np.array([r[5] for r in rows])
+        last = [FIRST[i] for i in f.argmax(axis=1)]
+        print("first launch, mean end of " + "  ".join(f"{n} {x:.2f}" for n, x in zip(FIRST, f.mean(axis=0))) + " us; last role: "
+              + ", ".join(f"{n} in {last.count(n)}" for n in FIRST if n in last) + f" of {len(rows)} steps")
     print(f"mean spans over {len(rows)} steps: " + " ".join(f"{x:.2f}" for x in a.mean(axis=0)) + f" us; last launch: "
           f"median {np.median(a[:, -1]):.2f}, above 11 us in {int((a[:, -1] > 11).sum())} steps")
 
