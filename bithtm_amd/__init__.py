@@ -10,7 +10,7 @@ engine without the built library raises ImportError."""
 from . import classifier, encoders, likelihood, networks
 from .anomaly import AnomalyLikelihood  # noqa: F401
 from .sdr_classifier import SDRClassifier, SDRClassifierBank  # noqa: F401
-from .knn_classifier import KNNClassifier  # noqa: F401
+from .knn_classifier import KNNClassifier, KNNClassifierBank  # noqa: F401
 from .encoders import CategoryField, HashedField, ScalarEncoder, ScalarField, date_fields, date_values  # noqa: F401
 from .networks import InferenceView, flip_noise, noise_threshold  # noqa: F401
 from .engine import CapacityError, HtmError  # noqa: F401

@@ -89,6 +89,16 @@ class HtmKnnInfo(C.Structure):
         (name, C.c_int64) for name in ("total", "state_bytes", "device_bytes")]
 
 
+class HtmKnnsInfo(C.Structure):
+    """htm_knns_info_t: a bank's parameters, its streams, whether they share a store, the chunk, the form of the distance launch,
+    the largest count, the step total and the sizes."""
+    _fields_ = HtmKnnConfig._fields_ + [(name, C.c_int32) for name in (
+        "n_streams", "shared", "chunk", "table_in_lds", "queries_per_block", "bin_shift", "max_count", "reserved")] + [
+        (name, C.c_int64) for name in ("total", "state_bytes", "device_bytes", "scratch_bytes")]
+
+
+KNNS_SCRATCH_BYTES = 256 << 20              # HTM_KNNS_SCRATCH_BYTES (csrc/htm_knn_bank.h): the most scratch a bank's update may hold
+KNNS_MAX_STREAMS = 65535                    # HTM_KNNS_MAX_STREAMS
 KNN_CHUNK = 64                              # HTM_KNN_CHUNK (csrc/htm_knn.h): query steps per launch of htm_knn_update
 KNN_SLOTS = 256                             # HTM_KNN_SLOTS: slots per block of the distance launch
 KNN_QUERIES = 8                             # HTM_KNN_QUERIES: queries a block stages at most
@@ -222,6 +232,17 @@ EXPORTS = {
     "htm_knn_export": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]),
     "htm_knn_import": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]),
     "htm_knn_info": (C.c_int, [C.c_void_p, C.POINTER(HtmKnnInfo)]),
+    "htm_knns_create": (C.c_int, [C.c_void_p, C.POINTER(HtmKnnConfig), C.c_int32, C.c_void_p, C.POINTER(C.c_void_p)]),
+    "htm_knns_labels": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_void_p)]),
+    "htm_knns_update": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p,
+                                  C.c_void_p]),
+    "htm_knns_reset": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "htm_knns_export": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]),
+    "htm_knns_import": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]),
+    "htm_knns_info": (C.c_int, [C.c_void_p, C.POINTER(HtmKnnsInfo), C.c_void_p]),
+    "htm_knns_tick": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(HtmScalarField), C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
+                                C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
+                                C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
 }
 
 # The HIP runtime calls the binding makes itself -- the device buffers of run(record=...) -- resolved through the library's own

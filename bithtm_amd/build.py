@@ -17,8 +17,11 @@ OWN_REPORTS = {"htm_knn.h": os.path.join(HERE, "libbithtm_hip.knn.resources.json
 # ... and kernels added later still, whose reports all_kernel_resources() -- held to RESOURCES + OWN_REPORTS by tests/test_knn_cpu.py -- does
 # not return either: every_kernel_resources() is every kernel of the library (tests/test_handover_cpu.py).
 LATER_REPORTS = {"htm_handover.h": os.path.join(HERE, "libbithtm_hip.handover.resources.json")}
+# ... and the banks of KNN classifiers, which none of the three functions above returns (tests/test_handover_cpu.py holds
+# every_kernel_resources() to the three reports it had): library_kernel_resources() is every kernel of the library.
+BANK_REPORTS = {"htm_knn_bank.h": os.path.join(HERE, "libbithtm_hip.knn_bank.resources.json")}
 SOURCES = ["htm_engine.hip"]
-HEADERS = ["htm_dev.h", "htm_sp_kernels.h", "htm_tm_kernels.h", "htm_pipeline.h", "htm_record.h", "htm_reset.h", "htm_decode.h", "htm_stack.h", "htm_forecast.h", "htm_noise.h", "htm_group.h", "htm_tm_feed.h", "htm_sp_run.h", "htm_fork.h", "htm_scalar.h", "htm_live.h", "htm_fields.h", "htm_likelihood.h", "htm_classifier.h", "htm_knn.h", "htm_handover.h", "htm_rng.h", "htm_fexp.h",
+HEADERS = ["htm_dev.h", "htm_sp_kernels.h", "htm_tm_kernels.h", "htm_pipeline.h", "htm_record.h", "htm_reset.h", "htm_decode.h", "htm_stack.h", "htm_forecast.h", "htm_noise.h", "htm_group.h", "htm_tm_feed.h", "htm_sp_run.h", "htm_fork.h", "htm_scalar.h", "htm_live.h", "htm_fields.h", "htm_likelihood.h", "htm_classifier.h", "htm_knn.h", "htm_knn_bank.h", "htm_handover.h", "htm_rng.h", "htm_fexp.h",
            os.path.join("..", "..", "include", "bithtm_hip.h")]
 # -ffp-contract=off: several kernels must round exactly like the NumPy expressions they replace
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off",
@@ -27,7 +30,7 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-ffp
 
 
 def _stale():
-    if not os.path.exists(LIB) or not all(os.path.exists(r) for r in [RESOURCES] + list(OWN_REPORTS.values()) + list(LATER_REPORTS.values())):
+    if not os.path.exists(LIB) or not all(os.path.exists(r) for r in [RESOURCES] + list(OWN_REPORTS.values()) + list(LATER_REPORTS.values()) + list(BANK_REPORTS.values())):
         return True
     t = os.path.getmtime(LIB)
     deps = [os.path.join(CSRC, s) for s in SOURCES + HEADERS] + [os.path.abspath(__file__)]
@@ -82,7 +85,7 @@ def build(force=False, verbose=False):
     if r.returncode != 0:
         raise RuntimeError("hipcc failed:\n" + r.stdout)
     by_header = _kernel_resources(r.stdout)
-    for header, path in list(OWN_REPORTS.items()) + list(LATER_REPORTS.items()):
+    for header, path in list(OWN_REPORTS.items()) + list(LATER_REPORTS.items()) + list(BANK_REPORTS.items()):
         with open(path, "w") as f:
             json.dump(by_header.pop(header, {}), f, indent=0, sort_keys=True)
     with open(RESOURCES, "w") as f:
@@ -96,9 +99,9 @@ def build(force=False, verbose=False):
 
 def kernel_resources(header=None):
     """{mangled kernel name: resources} of the library as last built here (None if it was built elsewhere): the kernels of RESOURCES,
-    or those the header `header` of OWN_REPORTS or LATER_REPORTS defines."""
+    or those the header `header` of OWN_REPORTS, LATER_REPORTS or BANK_REPORTS defines."""
     build()
-    path = RESOURCES if header is None else OWN_REPORTS[header] if header in OWN_REPORTS else LATER_REPORTS[header]
+    path = RESOURCES if header is None else {**OWN_REPORTS, **LATER_REPORTS, **BANK_REPORTS}[header]
     if not os.path.exists(path):
         return None
     with open(path) as f:
@@ -115,6 +118,12 @@ def all_kernel_resources():
 def every_kernel_resources():
     """Every kernel of the library: all_kernel_resources() and the reports of LATER_REPORTS together (None if it was built elsewhere)."""
     parts = [all_kernel_resources()] + [kernel_resources(h) for h in LATER_REPORTS]
+    return None if any(p is None for p in parts) else {k: v for p in parts for k, v in p.items()}
+
+
+def library_kernel_resources():
+    """Every kernel of the library: every_kernel_resources() and the reports of BANK_REPORTS together (None if it was built elsewhere)."""
+    parts = [every_kernel_resources()] + [kernel_resources(h) for h in BANK_REPORTS]
     return None if any(p is None for p in parts) else {k: v for p in parts for k, v in p.items()}
 
 

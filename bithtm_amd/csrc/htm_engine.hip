@@ -56,6 +56,7 @@
 #include "htm_likelihood.h"
 #include "htm_classifier.h"
 #include "htm_knn.h"
+#include "htm_knn_bank.h"
 #include "htm_handover.h"
 
 // ------------------------------------------------------------------------------------------
@@ -4656,13 +4657,22 @@ struct htm_knn {
     size_t labels_cap = 0;
     int32_t *d_pos = nullptr;                   // the slot of every step of the call in flight, of pos_cap words
     size_t pos_cap = 0;
+    // a bank (htm_knns_*; htm_knn_bank.h): n stores member-major in d's arrays, or n frozen streams over `source`'s
+    int32_t n = 1, chunk = HTM_KNN_CHUNK;
+    int refs = 1;                               // the object itself and every bank that shares its store
+    htm_knn *source = nullptr;
+    std::vector<int32_t> counts;                // [n] (count is the largest of them)
+    void **d_tab = nullptr;                     // [n] input pointers, then [n][2] counts: the table of the update in flight
+    bool is_bank = false;
 };
 
 extern "C" void htm_knn_destroy(htm_knn *knn) {
-    if (!knn) return;
+    if (!knn || --knn->refs > 0) return;        // (a store that banks still read lives until the last of them goes)
     hipSetDevice(knn->device);
     for (void *p : knn->allocs) hipFree(p);     // (hipFree waits for the device: nothing enqueued still reads them)
+    htm_knn *source = knn->source;
     delete knn;
+    htm_knn_destroy(source);
 }
 
 // zeroed device memory of the object's, ordered on h's stream (null: the allocation failed)
@@ -4741,10 +4751,12 @@ extern "C" int htm_knn_create(htm_handle *h, const htm_knn_config *cfg, htm_knn 
 }
 
 // what every call on an existing object checks of its handle
-static int knn_check(const char *what, htm_knn *knn, htm_handle *h) {
+static int knn_check(const char *what, htm_knn *knn, htm_handle *h, bool bank = false) {
     if (!knn || !h) return cls_refuse(h, std::string(what) + ": null argument", HTM_ERR_ARGUMENT);
     if (h->world > 1) return cls_refuse(h, std::string(what) + ": not available on a column-sharded handle", HTM_ERR_STATE);
     if (h->device != knn->device) return cls_refuse(h, std::string(what) + ": the handle is on another device than the KNN classifier", HTM_ERR_ARGUMENT);
+    if (!bank && knn->is_bank) return cls_refuse(h, std::string(what) + ": the object is a bank of streams: use the htm_knns_ calls", HTM_ERR_STATE);
+    if (bank && !knn->is_bank) return cls_refuse(h, std::string(what) + ": the object is a one-stream KNN classifier: use the htm_knn_ calls", HTM_ERR_STATE);
     return 0;
 }
 
@@ -4886,6 +4898,334 @@ extern "C" int htm_knn_import(htm_knn *knn, htm_handle *h, const void *host_stat
 }
 
 // ------------------------------------------------------------------------------------------
+// Banks of KNN classifiers (htm_knn_bank.h): n stores in one object, or n frozen streams over the store of a
+// bound one-stream object.  As there, the counts and the total are the host's.
+extern "C" int htm_knns_create(htm_handle *h, const htm_knn_config *cfg, int32_t n_streams, htm_knn *share_store_of, htm_knn **out) {
+    const std::string what = "htm_knns_create";
+    if (out) *out = nullptr;
+    if (!h || !cfg || !out) return cls_refuse(h, what + ": null argument", HTM_ERR_ARGUMENT);
+    if (cfg->struct_bytes != sizeof(htm_knn_config)) return cls_refuse(h, what + ": htm_knn_config size mismatch", HTM_ERR_ARGUMENT);
+    const bool ok = cfg->labels >= 1 && cfg->labels <= HTM_KNN_MAX_LABELS && cfg->k >= 1 && cfg->k <= HTM_KNN_MAX_K && cfg->min_overlap >= 1 &&
+                    cfg->min_overlap <= 65535 && cfg->capacity >= 1 && cfg->capacity <= HTM_KNN_MAX_CAPACITY && cfg->cell_dim >= 1 && cfg->cell_dim <= 64 &&
+                    cfg->units >= cfg->cell_dim && cfg->units % cfg->cell_dim == 0 && cfg->max_pairs >= 1 && cfg->max_pairs <= HTM_KNN_MAX_PAIRS;
+    if (!ok)
+        return cls_refuse(h, what + ": labels in [1, 1024], k in [1, 64], min_overlap in [1, 65535], capacity in [1, 2^20], cell_dim in [1, 64], "
+                             "units a positive multiple of cell_dim, max_pairs in [1, 2047]", HTM_ERR_ARGUMENT);
+    if (n_streams < 1 || n_streams > HTM_KNNS_MAX_STREAMS) return cls_refuse(h, what + ": n_streams must be in [1, 65535]", HTM_ERR_ARGUMENT);
+    if (h->world > 1) return cls_refuse(h, what + ": not available on a column-sharded handle", HTM_ERR_STATE);
+    const htm_knn *src = share_store_of;
+    if (src) {
+        if (src->is_bank) return cls_refuse(h, what + ": share_store_of is a bank: only a one-stream object's store is shared", HTM_ERR_ARGUMENT);
+        if (src->device != h->device) return cls_refuse(h, what + ": share_store_of is on another device than the handle", HTM_ERR_ARGUMENT);
+        const KnnDev &sd = src->d;
+        if (sd.labels != cfg->labels || sd.k != cfg->k || sd.min_overlap != cfg->min_overlap || sd.capacity != cfg->capacity || sd.K != cfg->cell_dim ||
+            sd.n_cols * sd.K != cfg->units || sd.max_pairs != cfg->max_pairs)
+            return cls_refuse(h, what + ": share_store_of was made with another config", HTM_ERR_ARGUMENT);
+    }
+    const int64_t words = knn_table_words(cfg->units / cfg->cell_dim, (cfg->cell_dim + 31) / 32);
+    // (the streams of a shared store are one flat batch of queries: a chunk that takes a tick's n queries in one launch where that fits)
+    const int chunk = src ? gknn_shared_chunk(n_streams, cfg->capacity, words) : gknn_chunk(n_streams, cfg->capacity, words);
+    if (words > INT32_MAX || chunk < 1)
+        return cls_refuse(h, what + ": the scratch of one query step of " + std::to_string(n_streams) + " streams does not fit " +
+                                 std::to_string(HTM_KNNS_SCRATCH_BYTES >> 20) + " MiB: fewer streams or a smaller capacity", HTM_ERR_ARGUMENT);
+    HIPCHK(h, hipSetDevice(h->device));
+    htm_knn *knn = new htm_knn();
+    knn->device = h->device;
+    knn->is_bank = true;
+    knn->n = n_streams;
+    knn->chunk = chunk;
+    knn->counts.assign((size_t)n_streams, 0);
+    KnnDev &d = knn->d;
+    const size_t cap = (size_t)cfg->capacity, n = (size_t)n_streams;
+    bool bad;
+    if (src) {
+        d = src->d;                                 // (the store, labels and stamps where they lie; the scratch is the bank's own)
+        d.ovl = knn_alloc<uint16_t>(knn, h, (size_t)chunk * cap);
+        d.table = d.in_lds ? nullptr : knn_alloc<uint32_t>(knn, h, (size_t)chunk * (size_t)words);
+        bad = !d.ovl || (!d.in_lds && !d.table);
+    } else {
+        d.labels = cfg->labels;
+        d.k = cfg->k;
+        d.min_overlap = cfg->min_overlap;
+        d.capacity = cfg->capacity;
+        d.K = cfg->cell_dim;
+        d.WPC = (cfg->cell_dim + 31) / 32;
+        d.n_cols = cfg->units / cfg->cell_dim;
+        d.max_pairs = cfg->max_pairs;
+        d.words = (int32_t)words;
+        d.queries = knn_queries(words);
+        d.in_lds = knn_in_lds(words);
+        d.bitmap = knn_has_bitmap(words);
+        d.shift = knn_shift(knn_max_overlap(d.max_pairs, d.K));
+        d.store = knn_alloc<ClsPair>(knn, h, n * cap * d.max_pairs);
+        d.label = knn_alloc<int32_t>(knn, h, n * cap);
+        d.stamp = knn_alloc<int64_t>(knn, h, n * cap);
+        d.ovl = knn_alloc<uint16_t>(knn, h, n * (size_t)chunk * cap);
+        d.table = d.in_lds ? nullptr : knn_alloc<uint32_t>(knn, h, n * (size_t)chunk * (size_t)words);
+        knn->d_tab = knn_alloc<void *>(knn, h, 2 * n);      // (n pointers and n x 2 counts of 4 bytes)
+        bad = !d.store || !d.label || !d.stamp || !d.ovl || (!d.in_lds && !d.table) || !knn->d_tab;
+    }
+    if (bad || hipStreamSynchronize(h->stream) != hipSuccess) {
+        htm_knn_destroy(knn);
+        return cls_refuse(h, what + ": device allocation failed", HTM_ERR_HIP);
+    }
+    if (share_store_of) {
+        knn->source = share_store_of;
+        ++share_store_of->refs;
+    }
+    *out = knn;
+    return HTM_OK;
+}
+
+// host labels [n][n_labels] into the object's own array
+extern "C" int htm_knns_labels(htm_knn *knn, htm_handle *h, const int32_t *host_labels, int32_t n_labels, const int32_t **device_labels) {
+    const char *what = "htm_knns_labels";
+    if (device_labels) *device_labels = nullptr;
+    if (int rc = knn_check(what, knn, h, true)) return rc;
+    if (!host_labels || !device_labels || n_labels < 1) return cls_refuse(h, std::string(what) + ": need host labels, n_labels >= 1 and a place for the address", HTM_ERR_ARGUMENT);
+    const size_t words = (size_t)knn->n * (size_t)n_labels;
+    HIPCHK(h, hipSetDevice(knn->device));
+    if (int rc = knn_grow(what, knn, h, &knn->d_labels, &knn->labels_cap, words)) return rc;
+    knn->labels.assign(host_labels, host_labels + words);
+    HIPCHK(h, hipMemcpyAsync(knn->d_labels, host_labels, words * 4, hipMemcpyHostToDevice, h->stream));
+    *device_labels = knn->d_labels;
+    return HTM_OK;
+}
+
+// the launches of the queries [0, nq_all) of one flat batch against a one-stream view (d, s) in chunks: what htm_knn_update enqueues
+static int knn_enqueue_queries(htm_handle *h, hipStream_t st, const KnnDev &d, const KnnStep &s, int chunk) {
+    for (int first = 0; first < s.n_steps; first += chunk) {
+        const int nq = std::min<int>(chunk, s.n_steps - first);
+        const unsigned scatter = (unsigned)(((int64_t)nq * s.pairs_per_step + 255) / 256);
+        if (s.count > 0) {
+            const dim3 grid(knn_slot_blocks(s.count), knn_query_groups(nq, d.queries));
+            if (d.in_lds) {
+                LAUNCH_ON(h, st, (size_t)knn_distance_lds(d.words), "knns:distance", kknn_distance_lds, grid, 256, d, s, first, nq);
+            } else {
+                LAUNCH_ON(h, st, 0, "knns:scatter", kknn_scatter, scatter, 256, d, s, first, nq, 1);
+                LAUNCH_ON(h, st, (size_t)knn_distance_lds(d.words), "knns:distance", kknn_distance_global, grid, 256, d, s, first, nq);
+            }
+        }
+        LAUNCH_ON(h, st, 0, "knns:select", kknn_select, nq, 256, d, s, first);
+        if (s.count > 0 && !d.in_lds) LAUNCH_ON(h, st, 0, "knns:clear", kknn_scatter, scatter, 256, d, s, first, nq, 0);
+    }
+    return 0;
+}
+
+// The launches of an update of a bank's own stores, enqueued on stream st: gs holds the call's inputs, `largest` the largest count
+// behind the call's append, `stores` whether any stream stores; `place`: the slots come from kgknn_place (a tick's come with gs.pos).
+static int knns_enqueue(htm_knn *knn, htm_handle *h, hipStream_t st, const GKnnStep &gs, int32_t largest, bool stores, bool place) {
+    const KnnDev &d = knn->d;
+    const GKnnDev g{d, knn->n, knn->chunk};
+    const int n_steps = gs.s.n_steps, pairs_per_step = gs.s.pairs_per_step;
+    if (stores) {
+        if (place) LAUNCH_ON(h, st, 0, "knns:place", kgknn_place, knn->n, 256, g, gs);
+        LAUNCH_ON(h, st, 0, "knns:append", kgknn_append, dim3((unsigned)(((int64_t)n_steps * d.max_pairs + 255) / 256), knn->n), 256, g, gs);
+    }
+    for (int first = 0; first < n_steps; first += knn->chunk) {
+        const int nq = std::min<int>(knn->chunk, n_steps - first);
+        const dim3 scatter((unsigned)(((int64_t)nq * pairs_per_step + 255) / 256), knn->n);
+        if (largest > 0) {
+            const dim3 grid(knn_slot_blocks(largest), gknn_distance_rows(knn->n, nq, d.queries));
+            if (d.in_lds) {
+                LAUNCH_ON(h, st, (size_t)knn_distance_lds(d.words), "knns:distance", kgknn_distance_lds, grid, 256, g, gs, first, nq);
+            } else {
+                LAUNCH_ON(h, st, 0, "knns:scatter", kgknn_scatter, scatter, 256, g, gs, first, nq, 1);
+                LAUNCH_ON(h, st, (size_t)knn_distance_lds(d.words), "knns:distance", kgknn_distance_global, grid, 256, g, gs, first, nq);
+            }
+        }
+        LAUNCH_ON(h, st, 0, "knns:select", kgknn_select, dim3(nq, knn->n), 256, g, gs, first);
+        if (largest > 0 && !d.in_lds) LAUNCH_ON(h, st, 0, "knns:clear", kgknn_scatter, scatter, 256, g, gs, first, nq, 0);
+    }
+    return 0;
+}
+
+// the n x n_steps frozen queries of a sharing bank, one flat batch over the source's store as it is now: every slot in [0, count) is seen
+static int knns_enqueue_shared(htm_knn *knn, htm_handle *h, hipStream_t st, const ClsPair *pairs, int32_t pairs_per_step, int64_t queries, int32_t *best,
+                               int32_t *votes) {
+    KnnDev d = knn->d;
+    const KnnDev &sd = knn->source->d;
+    d.store = sd.store; d.label = sd.label; d.stamp = sd.stamp;
+    const int32_t count = knn->source->count;
+    const KnnStep s{pairs, pairs_per_step, nullptr, 1, 0, (int32_t)queries, best, votes, INT64_MAX / 2, count, count};
+    return knn_enqueue_queries(h, st, d, s, knn->chunk);
+}
+
+extern "C" int htm_knns_update(htm_knn *knn, htm_handle *h, const void *const *device_pairs, int32_t pairs_per_step, int32_t n_steps,
+                               const int32_t *device_labels, int32_t n_labels, int32_t first_step, int32_t learn, int32_t *device_best,
+                               int32_t *device_votes) {
+    const char *what = "htm_knns_update";
+    if (int rc = knn_check(what, knn, h, true)) return rc;
+    const std::string w = std::string(what) + ": ";
+    if (!device_pairs || !device_best || (learn && !device_labels)) return cls_refuse(h, w + "null pairs, labels or output", HTM_ERR_ARGUMENT);
+    const size_t n = (size_t)knn->n;
+    for (size_t i = 0; i < n; ++i)
+        if (!device_pairs[i]) return cls_refuse(h, w + "stream " + std::to_string(i) + " has no pairs", HTM_ERR_ARGUMENT);
+    KnnDev d = knn->d;
+    if (pairs_per_step < 1 || pairs_per_step > d.max_pairs)
+        return cls_refuse(h, w + "pairs_per_step must be in [1, max_pairs = " + std::to_string(d.max_pairs) + "]", HTM_ERR_ARGUMENT);
+    if (n_steps < 0 || n_labels < 1 || first_step < 0) return cls_refuse(h, w + "n_steps >= 0, n_labels >= 1, first_step >= 0", HTM_ERR_ARGUMENT);
+    if (learn && knn->source) return cls_refuse(h, w + "the streams read another object's store: learn must be 0", HTM_ERR_STATE);
+    if ((int64_t)n * n_steps > INT32_MAX / 8) return cls_refuse(h, w + "n_streams x n_steps must stay below 2^28", HTM_ERR_ARGUMENT);
+    // what every stream stores: counted on the host, from the labels the host gave; one stream past its capacity refuses the call
+    std::vector<int32_t> after(knn->counts);
+    int64_t stored_all = 0;
+    if (learn && n_steps > 0) {
+        if (device_labels != knn->d_labels || (size_t)n_labels * n != knn->labels.size())
+            return cls_refuse(h, w + "a learning call reads the labels of htm_knns_labels (its address, its n_labels): the host counts what is stored", HTM_ERR_ARGUMENT);
+        for (size_t m = 0; m < n; ++m) {
+            int64_t stored = 0;
+            for (int i = 0; i < n_steps; ++i) {
+                const int32_t g = knn->labels[m * (size_t)n_labels + (size_t)(((int64_t)first_step + i) % n_labels)];
+                stored += g >= 0 && g < d.labels;
+            }
+            if (knn->counts[m] + stored > d.capacity)
+                return cls_refuse(h, w + "stream " + std::to_string(m) + ": the call would store " + std::to_string(stored) + " patterns in a store of " +
+                                         std::to_string(knn->counts[m]) + " of capacity = " + std::to_string(d.capacity) + " slots", HTM_ERR_CAPACITY);
+            after[m] += (int32_t)stored;
+            stored_all += stored;
+        }
+    }
+    if (n_steps == 0) return HTM_OK;
+    HIPCHK(h, hipSetDevice(knn->device));
+    const hipStream_t st = h->stream;
+    if (knn->source) {
+        // one flat batch of n x n_steps frozen queries over the source's store as it is now: every slot in [0, count) is seen
+        const char *first_row = (const char *)device_pairs[0];
+        const size_t row_bytes = (size_t)n_steps * pairs_per_step * sizeof(ClsPair);
+        for (size_t i = 1; i < n; ++i)
+            if ((const char *)device_pairs[i] != first_row + i * row_bytes)
+                return cls_refuse(h, w + "the streams of a shared store are one batch: their pairs must lie one behind the other in stream order", HTM_ERR_ARGUMENT);
+        if (int rc = knns_enqueue_shared(knn, h, st, (const ClsPair *)device_pairs[0], pairs_per_step, (int64_t)n * n_steps, device_best, device_votes)) return rc;
+        knn->total += n_steps;
+        return launch_status(h->err);
+    }
+    if (stored_all)
+        if (int rc = knn_grow(what, knn, h, &knn->d_pos, &knn->pos_cap, n * (size_t)n_steps)) return rc;
+    // the one copy of the table, from the call's own (pageable) words: the copy has read them when it returns
+    std::vector<void *> tab(2 * n, nullptr);
+    int32_t *tab_counts = (int32_t *)(tab.data() + n);
+    int32_t largest = 0;
+    for (size_t m = 0; m < n; ++m) {
+        tab[m] = (void *)device_pairs[m];
+        tab_counts[2 * m] = knn->counts[m];
+        tab_counts[2 * m + 1] = after[m];
+        largest = std::max(largest, after[m]);
+    }
+    HIPCHK(h, hipMemcpyAsync((void *)knn->d_tab, (const void *)tab.data(), 2 * n * sizeof(void *), hipMemcpyHostToDevice, st));
+    GKnnStep gs{};
+    gs.s = KnnStep{nullptr, pairs_per_step, device_labels, n_labels, first_step, n_steps, device_best, device_votes, knn->total, 0, 0};
+    gs.pairs = (const ClsPair *const *)knn->d_tab;
+    gs.counts = (const int32_t *)(knn->d_tab + n);
+    gs.pos = stored_all ? knn->d_pos : nullptr;
+    if (int rc = knns_enqueue(knn, h, st, gs, largest, stored_all > 0, true)) return rc;
+    knn->counts = after;
+    knn->count = largest;
+    knn->total += n_steps;
+    return launch_status(h->err);
+}
+
+// the stores of the streams that `streams` names emptied (null: every stream's); the launches enqueued before carry their own counts
+extern "C" int htm_knns_reset(htm_knn *knn, htm_handle *h, const uint8_t *streams) {
+    if (int rc = knn_check("htm_knns_reset", knn, h, true)) return rc;
+    knn->count = 0;
+    for (size_t m = 0; m < (size_t)knn->n; ++m) {
+        if (!streams || streams[m]) knn->counts[m] = 0;
+        knn->count = std::max(knn->count, knn->counts[m]);
+    }
+    return HTM_OK;
+}
+
+// The state: int64 total; int64 count[n]; then the streams' pairs, the streams' int64 stamps, the streams' int32 labels, each in
+// stream order (a sharing bank: its counts are 0 -- its state is the total)
+static int64_t knns_state_bytes(const htm_knn *knn, const std::vector<int32_t> &counts) {
+    int64_t all = 0;
+    for (int32_t c : counts) all += c;
+    return 8 * (1 + (int64_t)knn->n) + all * ((int64_t)knn->d.max_pairs * 8 + 12);
+}
+
+extern "C" int htm_knns_info(const htm_knn *knn, htm_knns_info_t *out, int32_t *counts) {
+    if (!knn || !out || out->struct_bytes != sizeof(htm_knns_info_t) || !knn->is_bank) return HTM_ERR_ARGUMENT;
+    const KnnDev &d = knn->d;
+    const int64_t scratch = knn->source ? gknn_scratch_bytes(1, knn->chunk, d.capacity, d.words) : gknn_scratch_bytes(knn->n, knn->chunk, d.capacity, d.words);
+    *out = htm_knns_info_t{(uint32_t)sizeof(htm_knns_info_t), d.labels, d.k, d.min_overlap, d.capacity, d.n_cols * d.K, d.K, d.max_pairs, knn->n,
+                           knn->source ? 1 : 0, knn->chunk, d.in_lds, d.queries, d.shift, knn->source ? knn->source->count : knn->count, 0, knn->total,
+                           knns_state_bytes(knn, knn->counts), knn->device_bytes, scratch};
+    if (counts)
+        for (size_t m = 0; m < (size_t)knn->n; ++m) counts[m] = knn->counts[m];
+    return HTM_OK;
+}
+
+static int knns_state(const char *what, bool load, htm_knn *knn, htm_handle *h, void *host_state, int64_t bytes) {
+    if (int rc = knn_check(what, knn, h, true)) return rc;
+    const std::string w = std::string(what) + ": ";
+    const size_t n = (size_t)knn->n;
+    const int64_t head_bytes = 8 * (1 + (int64_t)n);
+    if (!host_state || bytes < head_bytes) return cls_refuse(h, w + "need host_state of htm_knns_info's state_bytes", HTM_ERR_ARGUMENT);
+    const KnnDev &d = knn->d;
+    std::vector<int64_t> head(1 + n);
+    head[0] = knn->total;
+    for (size_t m = 0; m < n; ++m) head[1 + m] = knn->counts[m];
+    if (load) memcpy(head.data(), host_state, (size_t)head_bytes);
+    std::vector<int32_t> counts(n);
+    bool ok = head[0] >= 0;
+    for (size_t m = 0; m < n; ++m) {
+        ok = ok && head[1 + m] >= 0 && head[1 + m] <= (knn->source ? 0 : d.capacity);
+        counts[m] = ok ? (int32_t)head[1 + m] : 0;
+    }
+    if (!ok || bytes != knns_state_bytes(knn, counts))
+        return cls_refuse(h, w + "need host_state of 8 (1 + n) + the counts x (8 max_pairs + 12) bytes with 0 <= count <= capacity (0 on a shared store), total >= 0",
+                          HTM_ERR_ARGUMENT);
+    size_t all = 0;
+    for (int32_t c : counts) all += (size_t)c;
+    const size_t row = (size_t)d.max_pairs * 8;
+    char *pairs = (char *)host_state + head_bytes, *stamps = pairs + all * row, *labels = stamps + all * 8;
+    if (load) {
+        size_t at = 0;
+        for (size_t m = 0; m < n; ++m) {
+            int64_t last = -1;
+            for (size_t i = 0; i < (size_t)counts[m]; ++i, ++at) {
+                int64_t stamp;
+                int32_t label;
+                memcpy(&stamp, stamps + at * 8, 8);
+                memcpy(&label, labels + at * 4, 4);
+                if (stamp <= last || stamp >= head[0])
+                    return cls_refuse(h, w + "the stamps must ascend and lie below total (stream " + std::to_string(m) + ", slot " + std::to_string(i) + ")", HTM_ERR_ARGUMENT);
+                if (label < 0 || label >= d.labels)
+                    return cls_refuse(h, w + "a label outside [0, labels) in stream " + std::to_string(m) + ", slot " + std::to_string(i), HTM_ERR_ARGUMENT);
+                last = stamp;
+            }
+        }
+    }
+    HIPCHK(h, hipSetDevice(knn->device));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    const hipMemcpyKind kind = load ? hipMemcpyHostToDevice : hipMemcpyDeviceToHost;
+    if (!load) memcpy(host_state, head.data(), (size_t)head_bytes);
+    size_t at = 0;
+    for (size_t m = 0; m < n; ++m) {
+        const size_t c = (size_t)counts[m], cap = (size_t)d.capacity;
+        if (c) {
+            void *dev[3] = {d.store + m * cap * d.max_pairs, d.stamp + m * cap, d.label + m * cap};
+            void *host[3] = {pairs + at * row, stamps + at * 8, labels + at * 4};
+            const size_t size[3] = {c * row, c * 8, c * 4};
+            for (int a = 0; a < 3; ++a) HIPCHK(h, hipMemcpy(load ? dev[a] : host[a], load ? host[a] : dev[a], size[a], kind));
+        }
+        at += c;
+    }
+    if (load) {
+        knn->total = head[0];
+        knn->counts = counts;
+        knn->count = n ? *std::max_element(counts.begin(), counts.end()) : 0;
+    }
+    return HTM_OK;
+}
+
+extern "C" int htm_knns_export(htm_knn *knn, htm_handle *h, void *host_state, int64_t bytes) { return knns_state("htm_knns_export", false, knn, h, host_state, bytes); }
+extern "C" int htm_knns_import(htm_knn *knn, htm_handle *h, const void *host_state, int64_t bytes) {
+    return knns_state("htm_knns_import", true, knn, h, (void *)host_state, bytes);
+}
+
+// ------------------------------------------------------------------------------------------
 // Live ticks (htm_live.h): the group's staging and result blocks, allocated by the first live call
 static int live_alloc(htm_group *g, size_t cls_need = 0) {
     htm_group::Live &lv = g->live;
@@ -4895,7 +5235,8 @@ static int live_alloc(htm_group *g, size_t cls_need = 0) {
     if (!lv.vote_tab) {
         lv.off_flags = n * (size_t)d.W * 4;             // (W is a multiple of 4 words: the flags and the values stay 8-byte aligned)
         lv.off_values = (lv.off_flags + n * 4 + 7) & ~(size_t)7;
-        lv.stage_bytes = lv.off_values + n * HTM_SCALAR_MAX_FIELDS * sizeof(double) + n * sizeof(int32_t);    // (... and a classified tick's targets)
+        // (... a classified tick's targets, and a tick with a KNN bank's labels, counts and slots: four words per member)
+        lv.stage_bytes = lv.off_values + n * HTM_SCALAR_MAX_FIELDS * sizeof(double) + n * sizeof(int32_t) + n * 4 * sizeof(int32_t);
         if (!lv.h_stage && hipHostMalloc((void **)&lv.h_stage, lv.stage_bytes, hipHostMallocDefault) != hipSuccess) { lv.h_stage = nullptr; g->err = "live tick: hipHostMalloc failed"; return HTM_ERR_HIP; }
         memset(lv.h_stage, 0, lv.stage_bytes);          // (the words of a staged row beyond ceil(input_dim / 32) stay zero)
         if (!lv.d_stage && galloc(g, &lv.d_stage, lv.stage_bytes)) return HTM_ERR_HIP;
@@ -4960,7 +5301,8 @@ static int live_alloc_capture(htm_group *g) {
 static int live_tick(htm_group *g, const double *values, const htm_scalar_field *fields, int32_t n_fields, const uint32_t *packed_inputs,
                      const uint8_t *resets, int32_t learning, int32_t use_graph, htm_live_row *rows, int32_t *decoded, int32_t *votes,
                      htm_likelihood *lk, double *likelihood, htm_classifier *clf = nullptr, const int32_t *targets = nullptr, int32_t cls_learn = 0,
-                     int32_t *best = nullptr, int32_t *dist = nullptr) {
+                     int32_t *best = nullptr, int32_t *dist = nullptr, htm_knn *knn = nullptr, const int32_t *knn_labels = nullptr, int32_t knn_learn = 0,
+                     int32_t *knn_best = nullptr, int32_t *knn_votes = nullptr) {
     if (!g) return HTM_ERR_ARGUMENT;
     if (!rows) { g->err = "htm_live_tick: null rows"; return HTM_ERR_ARGUMENT; }
     // a classified tick (htm_classifiers_tick): every refusal before anything is enqueued
@@ -4986,6 +5328,46 @@ static int live_tick(htm_group *g, const double *values, const htm_scalar_field 
         for (int i = 0; i < g->n; ++i)
             if (int rc = pin_refuse(g->m[i], "htm_classifiers_tick")) { g->err = "member " + std::to_string(i) + ": " + g->m[i]->err; return rc; }
     }
+    // a tick with a bank of KNN classifiers (htm_knns_tick): likewise.  The host knows every label, so it knows every stream's slot
+    std::vector<int32_t> knn_after;
+    int32_t knn_largest = 0;
+    bool knn_stores = false;
+    if ((knn != nullptr) != (knn_best != nullptr) || ((knn_labels || knn_learn || knn_votes) && !knn)) {
+        g->err = "htm_knns_tick: knn and knn_best go together (labels, knn_learn and knn_votes only with them)";
+        return HTM_ERR_ARGUMENT;
+    }
+    if (knn) {
+        const Dev &d0 = g->m[0]->d;
+        const KnnDev &c = knn->d;
+        if (!knn->is_bank) { g->err = "htm_knns_tick: the object is a one-stream KNN classifier: a tick takes a bank (htm_knns_create)"; return HTM_ERR_ARGUMENT; }
+        if (knn->n != g->n || knn->device != g->device) {
+            g->err = "htm_knns_tick: the bank has " + std::to_string(knn->n) + " streams on device " + std::to_string(knn->device) + ", the group " +
+                     std::to_string(g->n) + " members on device " + std::to_string(g->device);
+            return HTM_ERR_ARGUMENT;
+        }
+        if (c.n_cols != d0.C || c.K != d0.K || c.max_pairs < d0.k * d0.WPC) {
+            g->err = "htm_knns_tick: the bank was made for " + std::to_string(c.n_cols) + " columns of " + std::to_string(c.K) + " cells and patterns of " +
+                     std::to_string(c.max_pairs) + " pairs, the members have " + std::to_string(d0.C) + " x " + std::to_string(d0.K) + " and " +
+                     std::to_string(d0.k * d0.WPC) + " pairs a step";
+            return HTM_ERR_ARGUMENT;
+        }
+        if (knn_learn && knn->source) { g->err = "htm_knns_tick: the streams read another object's store: learn must be 0"; return HTM_ERR_STATE; }
+        if (knn_learn && !knn_labels) { g->err = "htm_knns_tick: a learning tick needs the members' labels"; return HTM_ERR_ARGUMENT; }
+        knn_after = knn->counts;
+        for (int i = 0; i < g->n; ++i) {
+            const bool labelled = knn_learn && knn_labels[i] >= 0 && knn_labels[i] < c.labels;
+            if (labelled && knn->counts[(size_t)i] + 1 > c.capacity) {
+                g->err = "htm_knns_tick: stream " + std::to_string(i) + ": the tick would store 1 pattern in a store of " + std::to_string(knn->counts[(size_t)i]) +
+                         " of capacity = " + std::to_string(c.capacity) + " slots";
+                return HTM_ERR_CAPACITY;
+            }
+            knn_after[(size_t)i] += labelled;
+            knn_stores |= labelled;
+            knn_largest = std::max(knn_largest, knn_after[(size_t)i]);
+        }
+        for (int i = 0; i < g->n; ++i)
+            if (int rc = pin_refuse(g->m[i], "htm_knns_tick")) { g->err = "member " + std::to_string(i) + ": " + g->m[i]->err; return rc; }
+    }
     if ((lk != nullptr) != (likelihood != nullptr)) { g->err = "htm_likelihood_tick: lk and likelihood go together"; return HTM_ERR_ARGUMENT; }
     if (lk && (lk->n != g->n || lk->device != g->device)) {
         g->err = "htm_likelihood_tick: the likelihood object has " + std::to_string(lk->n) + " streams on device " + std::to_string(lk->device) +
@@ -5010,12 +5392,16 @@ static int live_tick(htm_group *g, const double *values, const htm_scalar_field 
     if (rc) return rc;
     // (the classification's bytes in the result block: best, then dist)
     const size_t best_bytes = clf ? (size_t)g->n * clf->d.H * 2 * sizeof(int32_t) : 0, dist_bytes = dist ? (size_t)g->n * clf->d.H * clf->d.B * sizeof(int32_t) : 0;
-    const size_t cls_bytes = (best_bytes + dist_bytes + 7) & ~(size_t)7;
+    // (... and behind them a KNN bank's rows [B][5] and votes [B][labels])
+    const size_t knn_best_bytes = knn ? (size_t)g->n * 5 * sizeof(int32_t) : 0, knn_votes_bytes = knn_votes ? (size_t)g->n * knn->d.labels * sizeof(int32_t) : 0;
+    const size_t cls_bytes = (best_bytes + dist_bytes + knn_best_bytes + knn_votes_bytes + 7) & ~(size_t)7;
     rc = live_alloc(g, cls_bytes);
     if (rc) return rc;
-    if (clf) {
+    if (clf || knn) {
         rc = live_alloc_capture(g);
         if (rc) return rc;
+    }
+    if (clf) {
         if (cls_prepare(clf, h0, cls_learn, 1)) { g->err = h0->err; return HTM_ERR_HIP; }
     }
     htm_group::Live &lv = g->live;
@@ -5048,6 +5434,20 @@ static int live_tick(htm_group *g, const double *values, const htm_scalar_field 
         memcpy(lv.h_stage + off_targets, targets, (size_t)B * sizeof(int32_t));
         c1 = off_targets + (size_t)B * sizeof(int32_t);
     }
+    // ... and behind those a KNN bank's words: every member's label [B], its stream's counts before and behind the tick [B][2] and the
+    // slot its pattern goes into [B] (-1: it stores nothing)
+    const size_t off_knn = c1;
+    if (knn && !knn->source) {
+        int32_t *w = (int32_t *)(lv.h_stage + off_knn);
+        for (int i = 0; i < B; ++i) {
+            const bool stores = knn_after[(size_t)i] != knn->counts[(size_t)i];
+            w[i] = stores ? knn_labels[i] : -1;
+            w[B + 2 * i] = knn->counts[(size_t)i];
+            w[B + 2 * i + 1] = knn_after[(size_t)i];
+            w[3 * B + i] = stores ? knn->counts[(size_t)i] : -1;
+        }
+        c1 = off_knn + (size_t)B * 4 * sizeof(int32_t);
+    }
     GHIPCHK(g, hipMemcpyAsync(lv.d_stage + c0, lv.h_stage + c0, c1 - c0, hipMemcpyHostToDevice, s));
     // resets first: the record's begin launch then counts the cleared prediction words (predicted_columns_before = 0)
     if (resetting) LAUNCH_ON(h0, s, 0, "live:reset", klive_reset, dim3(reset_blocks(d), B), 256, g->d_tab, (const int32_t *)(lv.d_stage + lv.off_flags));
@@ -5062,7 +5462,7 @@ static int live_tick(htm_group *g, const double *values, const htm_scalar_field 
                   (uint32_t *)lv.d_stage, 0);
     const bool decoding = decoded || votes;
     if (decoding) LAUNCH_ON(h0, s, 0, "group:predicted_input", kgrp_pin_begin, dim3(pin_begin_blocks(1, d.I), B), 256, g->d_tab, p ^ 1, g->d_pins, lv.vote_tab, 1);
-    const RunModes modes{true, false, decoding, false, clf != nullptr};       // (a classified tick captures its step's patterns)
+    const RunModes modes{true, false, decoding, false, clf != nullptr || knn != nullptr};     // (a classified tick captures its step's patterns, once)
     GroupForm f = group_form(g);
     f.shared = g->shared && !learning;
     if (run_schedule(h0, 1, use_graph).graph) {
@@ -5106,6 +5506,29 @@ static int live_tick(htm_group *g, const double *values, const htm_scalar_field 
         gs.dist = dist ? (int32_t *)(lv.d_out + cls_begin + best_bytes) : nullptr;
         if (cls_enqueue(clf, h0, s, gs, cls_learn)) { g->err = h0->err; return HTM_ERR_HIP; }
     }
+    // a tick with a KNN bank: every member's stream takes the step's captured pattern -- append (when any stream stores: the slots came
+    // in the staging copy, there is no place launch), distance, select; the frozen streams of a shared store are one flat batch of B
+    // queries.  A member's reset flag does not touch its store: the store is not sequence state.
+    const size_t knn_begin = cls_begin + best_bytes + dist_bytes;
+    if (knn) {
+        int32_t *out_best = (int32_t *)(lv.d_out + knn_begin), *out_votes = knn_votes ? (int32_t *)(lv.d_out + knn_begin + knn_best_bytes) : nullptr;
+        const int32_t per = d.k * d.WPC;
+        if (knn->source) {
+            if (knns_enqueue_shared(knn, h0, s, lv.cap_rows, per, B, out_best, out_votes)) { g->err = h0->err; return HTM_ERR_HIP; }
+        } else {
+            const int32_t *w = (const int32_t *)(lv.d_stage + off_knn);
+            GKnnStep gs{};
+            gs.s = KnnStep{lv.cap_rows, per, w, 1, 0, 1, out_best, out_votes, knn->total, 0, 0};
+            gs.pairs = nullptr;
+            gs.pairs_stride = per;
+            gs.counts = w + B;
+            gs.pos = (int32_t *)(lv.d_stage + off_knn) + 3 * B;
+            if (knns_enqueue(knn, h0, s, gs, knn_largest, knn_stores, false)) { g->err = h0->err; return HTM_ERR_HIP; }
+            knn->counts = knn_after;
+            knn->count = knn_largest;
+        }
+        knn->total += 1;
+    }
     for (htm_handle *h : g->m) {
         h->step_host += 1;
         h->window_known = true;
@@ -5115,13 +5538,15 @@ static int live_tick(htm_group *g, const double *values, const htm_scalar_field 
     if (rc) return rc;
     // the one copy out and the one wait
     const size_t pair_bytes = (size_t)B * n_dec * 2 * sizeof(int32_t), vote_bytes = (size_t)B * d.I * sizeof(int32_t);
-    const size_t out_end = votes ? lv.off_votes + vote_bytes : lv.off_pairs + pair_bytes, out_begin = clf ? cls_begin : lk ? lv.off_lik : lv.off_rows;
+    const size_t out_end = votes ? lv.off_votes + vote_bytes : lv.off_pairs + pair_bytes, out_begin = clf || knn ? cls_begin : lk ? lv.off_lik : lv.off_rows;
     GHIPCHK(g, hipMemcpyAsync(lv.h_out + out_begin, lv.d_out + out_begin, out_end - out_begin, hipMemcpyDeviceToHost, s));
     GHIPCHK(g, hipStreamSynchronize(s));
     memcpy(rows, lv.h_out + lv.off_rows, (size_t)B * sizeof(htm_live_row));
     if (lk) memcpy(likelihood, lv.h_out + lv.off_lik, (size_t)B * sizeof(double));
     if (clf) memcpy(best, lv.h_out + cls_begin, best_bytes);
     if (dist) memcpy(dist, lv.h_out + cls_begin + best_bytes, dist_bytes);
+    if (knn) memcpy(knn_best, lv.h_out + knn_begin, knn_best_bytes);
+    if (knn_votes) memcpy(knn_votes, lv.h_out + knn_begin + knn_best_bytes, knn_votes_bytes);
     if (decoded) memcpy(decoded, lv.h_out + lv.off_pairs, pair_bytes);
     if (votes) memcpy(votes, lv.h_out + lv.off_votes, vote_bytes);
     for (int i = 0; i < B; ++i) {                   // (the segment hint each member's next call -- group or solo -- starts from)
@@ -5150,6 +5575,16 @@ extern "C" int htm_classifiers_tick(htm_group *g, const double *values, const ht
                                     int32_t *dist) {
     return live_tick(g, values, fields, n_fields, packed_inputs, resets, learning, use_graph, rows, decoded, votes, lk, likelihood, clf, targets, learn ? 1 : 0,
                      best, dist);
+}
+
+// htm_classifiers_tick with a bank of KNN classifiers riding on it (lk, likelihood and the classifier's arguments may be NULL)
+extern "C" int htm_knns_tick(htm_group *g, const double *values, const htm_scalar_field *fields, int32_t n_fields, const uint32_t *packed_inputs,
+                             const uint8_t *resets, int32_t learning, int32_t use_graph, htm_live_row *rows, int32_t *decoded, int32_t *votes,
+                             htm_likelihood *lk, double *likelihood, htm_classifier *clf, const int32_t *targets, int32_t learn, int32_t *best, int32_t *dist,
+                             htm_knn *knn, const int32_t *labels, int32_t knn_learn, int32_t *knn_best, int32_t *knn_votes) {
+    if (g && !knn) { g->err = "htm_knns_tick: null knn"; return HTM_ERR_ARGUMENT; }
+    return live_tick(g, values, fields, n_fields, packed_inputs, resets, learning, use_graph, rows, decoded, votes, lk, likelihood, clf, targets, learn ? 1 : 0,
+                     best, dist, knn, labels, knn_learn ? 1 : 0, knn_best, knn_votes);
 }
 
 // htm_reset of the flagged members in one launch.  The flags are the call's own (pageable) words: the copy has read them when

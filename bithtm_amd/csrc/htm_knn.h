@@ -23,6 +23,8 @@
 // table only for the pairs whose word the query holds: a query holds a few per cent of the words, and the 4-byte gathers were the cost.  No block waits for
 // another, nothing is accumulated across blocks, every sum is an integer.  The arithmetic is in the __host__ __device__ functions at
 // the top: tests/host_stub/knn_host.cpp evaluates them on the host.
+// Every kernel's body is a __device__ function (knn_place_block, knn_append_pair, knn_scatter_pair, knn_distance_block,
+// knn_select_block): htm_knn_bank.h calls the same bodies with a member's offsets.
 // Part of the single translation unit htm_engine.hip (included after htm_classifier.h, whose pairs and live bits it shares).
 #ifndef BITHTM_HTM_KNN_H
 #define BITHTM_HTM_KNN_H
@@ -112,7 +114,7 @@ __device__ __forceinline__ uint2 knn_load_pair(const ClsPair *p) { return *(cons
 
 // one block: pos[i] = the slot step i of the call stores its pattern in (count0 + the labelled steps before it), -1 for a step
 // without a label.  A thread takes a run of steps; the runs' counts are scanned in LDS.
-__global__ __launch_bounds__(256) void kknn_place(KnnDev d, KnnStep s, int32_t *__restrict__ pos) {
+__device__ __forceinline__ void knn_place_block(const KnnDev &d, const KnnStep &s, int32_t *__restrict__ pos) {
     __shared__ int s_scan[256];
     const int tid = (int)threadIdx.x, run = (s.n_steps + 255) / 256;
     const int lo = min(tid * run, s.n_steps), hi = min(lo + run, s.n_steps);
@@ -130,9 +132,10 @@ __global__ __launch_bounds__(256) void kknn_place(KnnDev d, KnnStep s, int32_t *
     for (int i = lo; i < hi; ++i) pos[i] = knn_label_of(d, s, i) >= 0 ? at++ : -1;
 }
 
-// a thread per pair of the call's steps: the labelled steps' rows into their slots (padded with (-1, 0)), label and stamp with pair 0
-__global__ __launch_bounds__(256) void kknn_append(KnnDev d, KnnStep s, const int32_t *__restrict__ pos) {
-    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+__global__ __launch_bounds__(256) void kknn_place(KnnDev d, KnnStep s, int32_t *__restrict__ pos) { knn_place_block(d, s, pos); }
+
+// pair e of the call's steps: a labelled step's row into its slot (padded with (-1, 0)), label and stamp with pair 0
+__device__ __forceinline__ void knn_append_pair(const KnnDev &d, const KnnStep &s, const int32_t *__restrict__ pos, int64_t e) {
     const int i = (int)(e / d.max_pairs), j = (int)(e % d.max_pairs);
     if (i >= s.n_steps) return;
     const int slot = pos[i];
@@ -146,10 +149,14 @@ __global__ __launch_bounds__(256) void kknn_append(KnnDev d, KnnStep s, const in
     }
 }
 
-// a thread per pair of the chunk's queries [first, first + nq): the live bits into the query's row of the global table (fill), or
-// the same words zeroed again (fill == 0)
-__global__ __launch_bounds__(256) void kknn_scatter(KnnDev d, KnnStep s, int first, int nq, int fill) {
-    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+// a thread per pair of the call's steps
+__global__ __launch_bounds__(256) void kknn_append(KnnDev d, KnnStep s, const int32_t *__restrict__ pos) {
+    knn_append_pair(d, s, pos, (int64_t)blockIdx.x * 256 + threadIdx.x);
+}
+
+// pair e of the chunk's queries [first, first + nq): the live bits into the query's row of the global table (fill), or the same
+// word zeroed again (fill == 0)
+__device__ __forceinline__ void knn_scatter_pair(const KnnDev &d, const KnnStep &s, int first, int nq, int fill, int64_t e) {
     const int q = (int)(e / s.pairs_per_step), j = (int)(e % s.pairs_per_step);
     if (q >= nq) return;
     const uint2 pr = knn_load_pair(s.pairs + (size_t)(first + q) * s.pairs_per_step + j);
@@ -159,16 +166,21 @@ __global__ __launch_bounds__(256) void kknn_scatter(KnnDev d, KnnStep s, int fir
     if (fill) atomicOr(w, bits); else *w = 0u;
 }
 
-// Block (x, y) of the distance launch over the queries [first, first + nq) and the slots [0, s.count): the overlaps of the queries
-// of group y with the slots of block x.  TABLE_IN_LDS: the group's tables are staged in `lds` (dynamic: queries * words words);
+// a thread per pair of the chunk's queries
+__global__ __launch_bounds__(256) void kknn_scatter(KnnDev d, KnnStep s, int first, int nq, int fill) {
+    knn_scatter_pair(d, s, first, nq, fill, (int64_t)blockIdx.x * 256 + threadIdx.x);
+}
+
+// Block (bx, by) of the distance launch over the queries [first, first + nq) and the slots [0, s.count): the overlaps of the queries
+// of group by with the slots of block bx (the one-stream kernels: the block's own x and y; a bank's: inside its member).  TABLE_IN_LDS: the group's tables are staged in `lds` (dynamic: queries * words words);
 // otherwise they are rows of d.table, filled by kknn_scatter, and `lds` holds the group's presence bitmaps (d.bitmap: queries *
 // knn_bitmap_words words; a pair whose bit is not set adds nothing and reads nothing).
 template <bool TABLE_IN_LDS>
-__device__ __forceinline__ void knn_distance_block(const KnnDev &d, const KnnStep &s, int first, int nq, uint32_t *lds) {
+__device__ __forceinline__ void knn_distance_block(const KnnDev &d, const KnnStep &s, int first, int nq, uint32_t *lds, int bx, int by) {
     __shared__ int s_ov[HTM_KNN_QUERIES * HTM_KNN_SLOTS];
     const int tid = (int)threadIdx.x;
-    const int q0 = (int)blockIdx.y * d.queries, nqb = min(d.queries, nq - q0);
-    const int slot0 = knn_block_first((int)blockIdx.x), ns = knn_block_last((int)blockIdx.x, s.count) - slot0;
+    const int q0 = by * d.queries, nqb = min(d.queries, nq - q0);
+    const int slot0 = knn_block_first(bx), ns = knn_block_last(bx, s.count) - slot0;
     for (int e = tid; e < nqb * HTM_KNN_SLOTS; e += 256) s_ov[e] = 0;
     const uint32_t *tab;
     if (TABLE_IN_LDS) {
@@ -226,13 +238,13 @@ __device__ __forceinline__ void knn_distance_block(const KnnDev &d, const KnnSte
 // grid (knn_slot_blocks(count), knn_query_groups(nq, queries)), dynamic LDS knn_distance_lds(words) bytes
 __global__ __launch_bounds__(256) void kknn_distance_lds(KnnDev d, KnnStep s, int first, int nq) {
     extern __shared__ uint32_t knn_tables[];
-    knn_distance_block<true>(d, s, first, nq, knn_tables);
+    knn_distance_block<true>(d, s, first, nq, knn_tables, (int)blockIdx.x, (int)blockIdx.y);
 }
 
 // the same grid, between kknn_scatter(fill) and kknn_scatter(clear) of the chunk
 __global__ __launch_bounds__(256) void kknn_distance_global(KnnDev d, KnnStep s, int first, int nq) {
     extern __shared__ uint32_t knn_tables[];
-    knn_distance_block<false>(d, s, first, nq, knn_tables);
+    knn_distance_block<false>(d, s, first, nq, knn_tables, (int)blockIdx.x, (int)blockIdx.y);
 }
 
 // the largest of v over the block (every thread calls it; s_red: 4 words of 64 bits)
@@ -249,8 +261,8 @@ __device__ __forceinline__ unsigned long long knn_block_max(unsigned long long v
     return v;
 }
 
-// grid nq: block q selects for query first + q over the overlaps d.ovl[q][0 .. count)
-__global__ __launch_bounds__(256) void kknn_select(KnnDev d, KnnStep s, int first) {
+// one block selects for query first + q over the overlaps d.ovl[q][0 .. count)
+__device__ __forceinline__ void knn_select_block(const KnnDev &d, const KnnStep &s, int first, int q) {
     __shared__ int s_hist[HTM_KNN_BINS];
     __shared__ int s_votes[HTM_KNN_MAX_LABELS];
     __shared__ int s_scan[256];
@@ -258,7 +270,7 @@ __global__ __launch_bounds__(256) void kknn_select(KnnDev d, KnnStep s, int firs
     __shared__ int s_wave[4];
     __shared__ unsigned long long s_red[4];
     const int tid = (int)threadIdx.x, wave = tid >> 6, lane = tid & 63;
-    const int q = (int)blockIdx.x, i = first + q, count = s.count;
+    const int i = first + q, count = s.count;
     const uint16_t *__restrict__ row = d.ovl + (size_t)q * d.capacity;
     for (int b = tid; b < HTM_KNN_BINS; b += 256) s_hist[b] = 0;
     for (int l = tid; l < d.labels; l += 256) s_votes[l] = 0;
@@ -368,6 +380,9 @@ __global__ __launch_bounds__(256) void kknn_select(KnnDev d, KnnStep s, int firs
         for (int l = tid; l < d.labels; l += 256) o[l] = s_votes[l];
     }
 }
+
+// grid nq: block q selects for query first + q
+__global__ __launch_bounds__(256) void kknn_select(KnnDev d, KnnStep s, int first) { knn_select_block(d, s, first, (int)blockIdx.x); }
 
 #endif  // __HIPCC__
 #endif

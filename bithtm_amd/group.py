@@ -22,6 +22,7 @@ from . import _lib as L
 from .engine import CapacityError, HtmError, pack_bits
 from .networks import (RECORD_COUNTERS, HierarchicalTemporalMemory, InferenceView, RunRecord, _BatchedCall, _batches, _cached_bank, _check_encoder,
                        _encode_params, _no_classifier, _no_knn, _noise_ring, _record_fields, _with_counters, noise_threshold, retire_states)
+from .knn_classifier import KNNClassifierBank
 from .sdr_classifier import SDRClassifierBank, model_shape
 
 
@@ -55,10 +56,12 @@ class GroupTick(RunRecord):
       anomaly_likelihood float64 [B]  with likelihood=: each member's anomaly likelihood of this step (log_likelihood: its log scale)
       classified_bucket int32 [B, H], classified_probability float64 [B, H]   with classifier=: per horizon of the SDRClassifierBank
                                     each member's most probable bucket and its probability; classified_value float64 [B, H] for a
-                                    bank of an encoder field; class_distribution int32 [B, H, buckets] with class_distribution=True"""
+                                    bank of an encoder field; class_distribution int32 [B, H, buckets] with class_distribution=True
+      knn_label, knn_votes, knn_overlap, knn_nearest_slot, knn_nearest_step int32 [B]   with knn=: each member's result row of the
+                                    KNNClassifierBank (knn.ROW); knn_votes_all int32 [B, labels] with knn_votes_all=True"""
 
     def __init__(self, rows, pairs=None, votes=None, encoder=None, anomaly_likelihood=None, classified=None, class_distribution=None,
-                 classified_field=None):
+                 classified_field=None, knn=None, knn_votes_all=None):
         counters = np.stack([rows[name] for name in RECORD_COUNTERS], axis=1)
         bucket = score = value = None
         if pairs is not None:
@@ -66,7 +69,7 @@ class GroupTick(RunRecord):
             value = encoder.value_of(bucket)
         super().__init__(rows["step_index"], counters=counters, predicted_input=votes, predicted_bucket=bucket, predicted_score=score,
                          predicted_value=value, anomaly_likelihood=anomaly_likelihood, classified=classified,
-                         class_distribution=class_distribution, classified_field=classified_field)
+                         class_distribution=class_distribution, classified_field=classified_field, knn=knn, knn_votes_all=knn_votes_all)
         self.capacity_error = np.ascontiguousarray(rows["capacity_error"], dtype=np.int32)
 
 
@@ -254,7 +257,7 @@ class ModelGroup:
     noise_chunk = 1024
 
     def run(self, inputs, steps, learning=None, use_graph=True, record=None, resets=None, noise=0.0, noise_seed=None, encoder=None,
-            likelihood=None, classifier=None, targets=None, classifier_learning=None, knn=None):
+            likelihood=None, classifier=None, targets=None, classifier_learning=None, knn=None, labels=None, knn_learning=None):
         """`steps` timesteps of every member, member i over the rows of inputs[i] (bool [B, n_inputs, input_dim]), cycled, as
         its own run(inputs[i], steps) would.  Returns None, or (`record`: as run(record=)) one RunRecord per member.
         learning=None: True, or False in a group with inference views (which refuses True).
@@ -273,9 +276,18 @@ class ModelGroup:
         member's rows (-1: missing), uploaded once; None with `encoder`: the bucket of the bank's field among the encoder's.  With
         `noise`, targets index the row of `inputs`.  `classifier_learning`: None follows `learning`.  Member i's RunRecord gains
         classified_bucket, _probability, _value and (with "class_distribution" named in `record`) class_distribution, as
-        run(classifier=) of the member alone with stream i as its classifier would give them.  `knn`: refused (a KNNClassifier has
-        one stream and rides on a model's or a view's own run())."""
-        _no_knn(knn, "ModelGroup.run()")
+        run(classifier=) of the member alone with stream i as its classifier would give them.
+        `knn`: a KNNClassifierBank of B streams (a one-stream KNNClassifier is refused; over views: KNNClassifierBank.shared) -- it
+        rides on the call as the classifier bank does, over the same captured words (with both, the steps' patterns are captured
+        once), and behind each batch ONE htm_knns_update runs over every member's patterns.  `labels`: int [B, n_inputs], the label
+        of each member's rows (-1, or anything outside [0, knn.labels): none), rolled per member as the targets are and uploaded
+        once; None: nothing is labelled.  `knn_learning`: None follows `learning`.  ValueError before anything is enqueued when any
+        stream's labelled steps do not fit its store.  Member i's RunRecord gains knn_label, knn_votes, knn_overlap,
+        knn_nearest_slot, knn_nearest_step and (with "knn_votes_all" named in `record`) knn_votes_all, as run(knn=) of the member
+        alone with stream i as its KNNClassifier would give them."""
+        near = knn if isinstance(knn, KNNClassifierBank) else None
+        if near is None:
+            _no_knn(knn, "ModelGroup.run()")
         bank = classifier if isinstance(classifier, SDRClassifierBank) else None
         if bank is None:
             _no_classifier(classifier, "ModelGroup.run()")
@@ -294,6 +306,19 @@ class ModelGroup:
             record = _with_counters(record)
         elif targets is not None or classifier_learning is not None:
             raise ValueError("run(): targets= and classifier_learning= go with classifier=")
+        knn_learn = votes_all = False
+        if near is not None:
+            if near.streams != B:
+                raise ValueError(f"run(knn=): a KNNClassifierBank of {B} streams, got {near.streams}")
+            knn_learn = bool(learning if knn_learning is None else knn_learning)
+            near._no_shared_learning(knn_learn)
+            names = () if record is None or record is True else ((record,) if isinstance(record, str) else tuple(record))
+            votes_all = "knn_votes_all" in names
+            if votes_all:
+                record = tuple(f for f in names if f != "knn_votes_all") or None
+            record = _with_counters(record)
+        elif labels is not None or knn_learning is not None:
+            raise ValueError("run(): labels= and knn_learning= go with knn=")
         if likelihood is not None:
             if likelihood.streams != B:
                 raise ValueError(f"run(likelihood=): an AnomalyLikelihood of {B} streams, got {likelihood.streams}")
@@ -324,12 +349,24 @@ class ModelGroup:
         if bank is not None:
             bank._set_shape(*model_shape(e0))
             host_targets = self._bank_targets(bank, targets, inputs, encoder, "run")
+        host_labels = None
+        if near is not None:
+            near._set_shape(*model_shape(e0))
+            host_labels = near.check_labels(np.full((B, inputs.shape[1]), -1) if labels is None else labels)
+            if host_labels.shape != (B, inputs.shape[1]):
+                raise ValueError(f"labels: int [{B}, {inputs.shape[1]}], one label per member and row, got {list(host_labels.shape)}")
         for m in self.models:
             retire_states(m.engine)
         self._current()
         k = self.models[0].active_columns
-        call = _BatchedCall([m.temporal_memory for m in self.models], fields, encoder, likelihood is not None, bank)
-        device_targets = None
+        if near is not None:
+            # member i's labels rolled by its distance from member 0's step, so that one first_step serves all members; the whole
+            # call's room is looked at before its first batch
+            e0, rows_in = self.models[0].engine, inputs.shape[1]
+            host_labels = np.stack([np.roll(g, -((m.engine.steps - e0.steps) % rows_in)) for g, m in zip(host_labels, self.models)])
+            near.check_room(near.stored_by(host_labels, e0.steps % rows_in, int(steps), knn_learn))
+        call = _BatchedCall([m.temporal_memory for m in self.models], fields, encoder, likelihood is not None, bank, near)
+        device_targets = device_labels = None
 
         def pools():        # cut into batches the smallest free-segment budget of any member lasts, with a look at the pools between them
             while self._grow(2 * k, True):
@@ -356,6 +393,13 @@ class ModelGroup:
                             "htm_group_run")
             else:
                 recs, buffers = self._records(fields, n, encoder)
+                if near is not None and bank is None:       # (with a classifier bank as well: its capture below serves both)
+                    e0, rows_in, per = self.models[0].engine, inputs.shape[1], near.shape[2]
+                    cells = near.pairs_buffer(e0, n)
+                    cell_rows = [cells + i * n * per * 8 for i in range(B)]
+                    self._check(self.lib.htm_set_group_run_active_cells(self._g, (C.c_void_p * B)(*cell_rows)), "htm_set_group_run_active_cells")
+                if near is not None and knn_learn and device_labels is None:
+                    device_labels = near.upload_labels(self.models[0].engine, host_labels)
                 if bank is not None:
                     # every member's rows of this batch in one buffer [B][n][pairs]; the targets by the row of `inputs` a step reads:
                     # member i's rolled by its distance from member 0's step, so that one first_step serves all members
@@ -371,14 +415,20 @@ class ModelGroup:
                                 "htm_group_run")
                 finally:
                     self._unset_votes()
-                    if bank is not None:
+                    if bank is not None or near is not None:
                         self.lib.htm_set_group_run_active_cells(self._g, None)
                 if likelihood is not None:          # (on the group's stream -- the first member's -- behind the run, before the wait)
                     likelihood.enqueue(self.models[0].engine, [b["counters"] for b in buffers], n)
                 if bank is not None:                # (likewise: ONE update over every member's patterns)
                     bank.enqueue(e0, cell_rows, per, n, [device_targets + i * rows_in * 4 for i in range(B)], rows_in, e0.steps % rows_in, None, cls_learn,
                                  distribution)
+                if near is not None:                # (likewise, over the same captured words)
+                    near.enqueue(e0, cell_rows, per, n, device_labels, host_labels if knn_learn else None, e0.steps % rows_in, knn_learn, votes_all)
                 parts = self._read_records(fields, n, buffers, encoder)
+                if near is not None:
+                    rows5, votes = near.read(e0, n, votes_all)
+                    for i, part in enumerate(parts):
+                        part["knn"], part["knn_votes_all"] = rows5[i].copy(), (votes[i].copy() if votes is not None else None)
                 if bank is not None:
                     best, dist = bank.read(e0, n, distribution)
                     for i, part in enumerate(parts):
@@ -522,7 +572,7 @@ class ModelGroup:
                 m.temporal_memory._was_reset = True
 
     def tick(self, values, encoder=None, resets=None, learning=None, predicted_input=False, use_graph=True, likelihood=None, classifier=None,
-             targets=None, classifier_learning=None, class_distribution=False, knn=None):
+             targets=None, classifier_learning=None, class_distribution=False, knn=None, labels=None, knn_learning=None, knn_votes_all=False):
         """One live timestep of every member in one call whose copies, launches and waits do not depend on B: member i steps on
         values[i] -- float64 [B, F] with `encoder` (a ScalarEncoder; NaN: missing), encoded on the device, else bool
         [B, input_dim] as process() takes it -- after a sequence reset where resets[i] (bool [B], or None).  Returns a GroupTick:
@@ -538,9 +588,17 @@ class ModelGroup:
         still one copy in, one copy out and one wait).  `targets`: int [B], each member's bucket of this tick (-1: missing); None
         with `encoder` and a bank made with field=: the bucket of this tick's value (NaN: missing).  `classifier_learning`: None
         follows `learning`.  A member's reset flag also empties its stream's history.  GroupTick.classified_bucket, _probability,
-        _value hold the predictions, with class_distribution=True GroupTick.class_distribution all probabilities.  `knn`: refused, as
-        in run()."""
-        _no_knn(knn, "ModelGroup.tick()")
+        _value hold the predictions, with class_distribution=True GroupTick.class_distribution all probabilities.
+        `knn`: a KNNClassifierBank of B streams (a one-stream KNNClassifier is refused; over views: KNNClassifierBank.shared) -- the
+        tick's patterns are the streams' next step (htm_knns_tick: the capture launch, then three launches when any stream stores, two when none does,
+        whatever B is; still one copy in, one copy out and one wait; with `classifier` the patterns are captured once).  `labels`:
+        int [B], each member's label of this tick (-1, or anything outside [0, knn.labels): none); None: nothing is labelled.
+        `knn_learning`: None follows `learning`.  ValueError before anything is enqueued when a labelled stream is full.  A member's
+        reset flag does not touch its store.  GroupTick.knn_label, knn_votes, knn_overlap, knn_nearest_slot, knn_nearest_step hold
+        the results, with knn_votes_all=True GroupTick.knn_votes_all every label's votes."""
+        near = knn if isinstance(knn, KNNClassifierBank) else None
+        if near is None:
+            _no_knn(knn, "ModelGroup.tick()")
         bank = classifier if isinstance(classifier, SDRClassifierBank) else None
         if bank is None:
             _no_classifier(classifier, "ModelGroup.tick()")
@@ -555,6 +613,14 @@ class ModelGroup:
             bank._no_shared_learning(cls_learn)
         elif targets is not None or classifier_learning is not None or class_distribution:
             raise ValueError("tick(): targets=, classifier_learning= and class_distribution= go with classifier=")
+        knn_learn = False
+        if near is not None:
+            if near.streams != B:
+                raise ValueError(f"tick(knn=): a KNNClassifierBank of {B} streams, got {near.streams}")
+            knn_learn = bool(learning if knn_learning is None else knn_learning)
+            near._no_shared_learning(knn_learn)
+        elif labels is not None or knn_learning is not None or knn_votes_all:
+            raise ValueError("tick(): labels=, knn_learning= and knn_votes_all= go with knn=")
         if likelihood is not None and likelihood.streams != B:
             raise ValueError(f"tick(likelihood=): an AnomalyLikelihood of {B} streams, got {likelihood.streams}")
         _check_encoder(encoder, None, e0.input_dim, e0.column_dim)
@@ -572,6 +638,15 @@ class ModelGroup:
             bank._set_shape(*model_shape(e0))
             host_targets = np.ascontiguousarray(self._bank_targets(bank, None if targets is None else np.asarray(targets)[:, None]
                                                                    if np.ndim(targets) == 1 else targets, X[:, None], encoder, "tick")[:, 0])
+        host_labels = None
+        if near is not None:
+            near._set_shape(*model_shape(e0))
+            host_labels = near.check_labels(np.full((B, 1), -1) if labels is None else np.asarray(labels)[:, None] if np.ndim(labels) == 1 else labels)
+            if host_labels.shape != (B, 1):
+                raise ValueError(f"labels: int [{B}], one label per member, got {list(np.shape(labels))}")
+            host_labels = np.ascontiguousarray(host_labels[:, 0])
+            stored = ((host_labels >= 0) & knn_learn).astype(np.int64)
+            near.check_room(stored)
         for m in self.models:
             retire_states(m.engine)
         self._current()
@@ -599,11 +674,25 @@ class ModelGroup:
 
         def ptr(a):
             return None if a is None else a.ctypes.data_as(C.c_void_p)
-        scores = best = dist = None
+        scores = best = dist = knn_rows = knn_votes = None
         if bank is not None:
             H = len(bank.steps)
             best = np.zeros((B, H, 2), dtype=np.int32)
             dist = np.zeros((B, H, bank.buckets), dtype=np.int32) if class_distribution else None
+        if near is not None:
+            near._bind(e0)
+            knn_rows = np.zeros((B, 5), dtype=np.int32)
+            knn_votes = np.zeros((B, near.labels), dtype=np.int32) if knn_votes_all else None
+            lk = None
+            if likelihood is not None:
+                likelihood._bind(e0)
+                scores, lk = np.zeros(B, dtype=np.float64), likelihood._lk
+            self._check(self.lib.htm_knns_tick(self._g, *args, ptr(flags), int(bool(learning)), int(bool(use_graph)), ptr(rows), ptr(pairs), ptr(votes), lk,
+                                               ptr(scores), bank._clf if bank is not None else None, ptr(host_targets), int(cls_learn), ptr(best), ptr(dist),
+                                               near._knn, ptr(host_labels), int(knn_learn), ptr(knn_rows), ptr(knn_votes)), "htm_knns_tick")
+            near._counts += stored
+            near._total += 1
+        elif bank is not None:
             lk = None
             if likelihood is not None:
                 likelihood._bind(e0)
@@ -622,7 +711,7 @@ class ModelGroup:
         for m in self.models:
             m.engine.steps += 1
             m.temporal_memory._new_state(None)
-        tick = GroupTick(rows, pairs, votes, encoder, scores, best, dist, bank.field if bank is not None else None)
+        tick = GroupTick(rows, pairs, votes, encoder, scores, best, dist, bank.field if bank is not None else None, knn_rows, knn_votes)
         if tick.capacity_error.any():
             what = "; ".join(f"member {i}:" + "".join(" " + text for bit, text in _CAPACITY_FLAGS if flag & bit) + f" (flags {flag})"
                              for i, flag in enumerate(tick.capacity_error.tolist()) if flag)

@@ -136,6 +136,15 @@ class KNNDefinition:
             best[t], votes[t] = self.step(zip(index[t], words[t]), mine[t], learning)
         return best, votes
 
+    def load_store(self, pairs, labels, stamps, total):
+        """The inverse of store_arrays(): the store becomes these slots (pairs int [count, n, 2], labels [count], stamps [count]) and
+        the step total `total` -- a state as the device object's load_state_dict takes it, without stepping through it."""
+        if len(pairs) > self.capacity or not len(pairs) == len(labels) == len(stamps):
+            raise ValueError(f"a store of at most capacity = {self.capacity} slots with a label and a stamp each, got {len(pairs)}, {len(labels)}, {len(stamps)}")
+        self.slots = [[(int(i), int(w) & 0xFFFFFFFF) for i, w in p] for p in np.asarray(pairs).tolist()]
+        self._live = [self._dense(p) for p in self.slots]
+        self.labels_of, self.stamps, self.total = [int(g) for g in labels], [int(t) for t in stamps], int(total)
+
     def store_arrays(self):
         """The store as the device keeps it: (pairs int32 [count, max_pairs, 2] with unused pairs (-1, 0), labels int32 [count],
         stamps int64 [count])."""
@@ -145,3 +154,70 @@ class KNNDefinition:
             for j, (i, w) in enumerate(pattern):
                 pairs[s, j] = (i, np.uint32(w).view(np.int32))
         return pairs, np.asarray(self.labels_of, dtype=np.int32).reshape(-1), np.asarray(self.stamps, dtype=np.int64).reshape(-1)
+
+
+class KNNBankDefinition:
+    """`streams` independent KNNDefinitions with ONE step total: every update steps all of them by the same
+    steps.  Stream i fed (patterns_i, labels_i) equals a KNNDefinition fed the same, row for row and store for store.  shared():
+    frozen streams that infer over another definition's store."""
+
+    def __init__(self, streams, labels, k=1, min_overlap=1, capacity=4096, column_dim=2048, cell_dim=32, max_pairs=40):
+        self.streams = int(streams)
+        if self.streams < 1:
+            raise ValueError(f"streams must be at least 1, got {streams}")
+        self.defs = [KNNDefinition(labels, k, min_overlap, capacity, column_dim, cell_dim, max_pairs) for _ in range(self.streams)]
+        self.labels, self.capacity = self.defs[0].labels, self.defs[0].capacity
+        self.source = None
+        self.total = 0
+
+    @classmethod
+    def shared(cls, definition, streams):
+        """`streams` frozen streams over `definition`'s store as it is at each call: every slot in [0, count) is seen, whatever its
+        stamp.  They store nothing, learning is refused, and their own state is the step total."""
+        d = definition
+        bank = cls(streams, d.labels, d.k, d.min_overlap, d.capacity, d.column_dim, d.cell_dim, d.max_pairs)
+        bank.defs, bank.source = [], d
+        return bank
+
+    @property
+    def count(self):
+        return [0] * self.streams if self.source is not None else [d.count for d in self.defs]
+
+    def reset(self, streams=None):
+        """Empty the stores `streams` (bool [streams]) names, or all of them; the total stays."""
+        for i, d in enumerate(self.defs):
+            if streams is None or streams[i]:
+                d.reset()
+
+    def update(self, index, words, labels=None, learning=True, first_step=0):
+        """index, words [S, T, n], labels [S, R]: stream i's step t reads labels[i][(first_step + t) % R] -> (best int32 [S, T, 5],
+        votes int32 [S, T, labels]).  ValueError, with every store unchanged, when ANY stream's labelled steps do not fit its store."""
+        S, T = self.streams, len(index[0]) if len(index) else 0
+        if len(index) != S or len(words) != S:
+            raise ValueError(f"patterns of {S} streams, got {len(index)}")
+        best = np.zeros((S, T, 5), dtype=np.int32)
+        votes = np.zeros((S, T, self.labels), dtype=np.int32)
+        if self.source is not None:
+            if learning:
+                raise ValueError("the streams read another definition's store: learning is refused")
+            for i in range(S):
+                for t in range(T):
+                    best[i, t], votes[i, t] = self.source.infer([(int(a), int(w) & 0xFFFFFFFF) for a, w in zip(index[i][t], words[i][t])])
+            self.total += T
+            return best, votes
+        if labels is None:                          # (nothing is labelled)
+            labels = [[-1]] * S
+        if len(labels) != S:
+            raise ValueError(f"labels of {S} streams, got {len(labels)}")
+        for i, d in enumerate(self.defs):
+            mine = [int(labels[i][(first_step + t) % len(labels[i])]) for t in range(T)]
+            stored = sum(is_label(g, self.labels) for g in mine) if learning else 0
+            if d.count + stored > d.capacity:
+                raise ValueError(f"stream {i}: the call would store {stored} patterns in a store of {d.count} of capacity = {d.capacity} slots")
+        for i, d in enumerate(self.defs):
+            d.total = self.total                    # (the one total: a stream's stamps are the bank's steps)
+            best[i], votes[i] = d.update(index[i], words[i], labels[i], learning, first_step)
+        self.total += T
+        for d in self.defs:
+            d.total = self.total
+        return best, votes

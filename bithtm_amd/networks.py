@@ -914,6 +914,9 @@ class HierarchicalTemporalMemory:
             raise ValueError("run(): targets= and classifier_learning= go with classifier=")
         near = None
         if knn is not None:
+            from .knn_classifier import KNNClassifierBank
+            if isinstance(knn, KNNClassifierBank):                  # (many streams; this call has one)
+                _no_knn(knn, "run() with a KNNClassifierBank")
             named = () if record is None or record is True else ((record,) if isinstance(record, str) else tuple(record))
             if "knn_votes_all" in named:
                 record = tuple(f for f in named if f != "knn_votes_all") or None
@@ -1477,7 +1480,8 @@ def _no_knn(knn, what):
     """The calls a KNNClassifier does not ride on: refused, never silently ignored."""
     if knn is not None:
         raise ValueError(f"{what}: knn= is not available here -- a KNNClassifier rides on HierarchicalTemporalMemory.run() and "
-                         "InferenceView.run(), or takes patterns through update_patterns()")
+                         "InferenceView.run(), or takes patterns through update_patterns(); ModelGroup.run() and tick() take a KNNClassifierBank of as "
+                         "many streams as the group has members")
 
 
 def _classifier_targets(classifier, targets, inputs, encoder):

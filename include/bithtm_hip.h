@@ -1102,6 +1102,73 @@ int htm_knn_export(htm_knn *knn, htm_handle *h, void *host_state, int64_t bytes)
 int htm_knn_import(htm_knn *knn, htm_handle *h, const void *host_state, int64_t bytes);
 int htm_knn_info(const htm_knn *knn, htm_knn_info_t *out);
 
+/* Banks of KNN classifiers (the definition is bithtm_amd/knn.py's KNNBankDefinition): n_streams independent
+ * stores of one config in one htm_knn object, member-major in device memory, stepped by one launch sequence whatever n_streams is;
+ * stream i equals a one-stream object fed the same.  The streams' counts and the one step total are the HOST's.  The object is
+ * destroyed with htm_knn_destroy.
+ *
+ * htm_knns_create: share_store_of == NULL: n_streams own stores.  The scratch of an update -- the overlaps [n][chunk][capacity] of 16
+ * bits and, where a table exceeds 48 KiB, the tables [n][chunk][words] -- is bounded: chunk, the query steps per launch, is the
+ * largest power of two <= 64 whose scratch fits 256 MiB with n x chunk <= 65 535.  share_store_of: a one-stream object of the same
+ * config and device -- the n_streams streams are frozen (learn != 0: HTM_ERR_STATE) and infer over THAT object's store as it is at
+ * each call, every slot in [0, count) seen; nothing is copied, the store lives until the last object that reads it is destroyed, and
+ * the bank owns only its scratch (under the same budget: refused where one query's does not fit).  Its streams' queries are one flat batch: a block of the distance launch streams the store once
+ * per queries_per_block queries, whichever stream they belong to; device_pairs[i] must lie one behind the other in stream order.
+ *
+ * htm_knns_labels: host labels [n][n_labels] into the object's own device array, as htm_knn_labels.  htm_knns_update: device_pairs
+ * holds n_streams DEVICE addresses (a host array), each [n_steps][pairs_per_step]; stream i's step j reads label
+ * device_labels[i][(first_step + j) % n_labels] (device_labels may be NULL with learn == 0); device_best is [n][n_steps][5],
+ * device_votes [n][n_steps][labels] or NULL.  One copy (the table of addresses and per-stream counts), then kgknn_place and
+ * kgknn_append when any stream stores, and per chunk kgknn_distance_lds, kgknn_select (or kgknn_scatter, kgknn_distance_global,
+ * kgknn_select, kgknn_scatter).  htm_knns_reset empties the stores `streams` names (uint8 [n]; NULL: all); the total stays.
+ * htm_knns_export / _import: int64 total; int64 count[n]; the streams' pairs, then their int64 stamps, then their int32 labels, each
+ * in stream order -- htm_knns_info's state_bytes (a sharing bank: counts 0).  htm_knns_info also copies the n counts to `counts`
+ * (or NULL).
+ *
+ * Refused with nothing enqueued and every store as it was: what the one-stream calls refuse; n_streams outside [1, 65535]; a scratch
+ * that does not fit at chunk 1; share_store_of of another config, a bank, or another device; HTM_ERR_CAPACITY when ANY stream's
+ * labelled steps would take it past capacity; HTM_ERR_STATE for the htm_knn_ labels, update, reset, export and import calls on a
+ * bank and the htm_knns_ calls on a one-stream object. */
+typedef struct htm_knns_info_t {
+    uint32_t struct_bytes;
+    int32_t labels, k, min_overlap, capacity, units, cell_dim, max_pairs;
+    int32_t n_streams;
+    int32_t shared;           /* 1: the streams read another object's store */
+    int32_t chunk;                  /* query steps per launch */
+    int32_t table_in_lds, queries_per_block, bin_shift;
+    int32_t max_count;              /* the largest count (a sharing bank: the source's count) */
+    int32_t reserved;
+    int64_t total;
+    int64_t state_bytes;            /* of htm_knns_export now */
+    int64_t device_bytes;           /* device memory the object holds */
+    int64_t scratch_bytes;          /* ... of which the scratch of an update */
+} htm_knns_info_t;
+
+int htm_knns_create(htm_handle *h, const htm_knn_config *cfg, int32_t n_streams, htm_knn *share_store_of, htm_knn **out);
+int htm_knns_labels(htm_knn *knn, htm_handle *h, const int32_t *host_labels, int32_t n_labels, const int32_t **device_labels);
+int htm_knns_update(htm_knn *knn, htm_handle *h, const void *const *device_pairs, int32_t pairs_per_step, int32_t n_steps,
+                    const int32_t *device_labels, int32_t n_labels, int32_t first_step, int32_t learn, int32_t *device_best,
+                    int32_t *device_votes);
+int htm_knns_reset(htm_knn *knn, htm_handle *h, const uint8_t *streams);
+int htm_knns_export(htm_knn *knn, htm_handle *h, void *host_state, int64_t bytes);
+int htm_knns_import(htm_knn *knn, htm_handle *h, const void *host_state, int64_t bytes);
+int htm_knns_info(const htm_knn *knn, htm_knns_info_t *out, int32_t *counts);
+
+/* htm_classifiers_tick with a bank of KNN classifiers riding on it: the tick's captured patterns are the streams' next step.  lk,
+ * likelihood and clf, targets, best, dist may be NULL (each group as in htm_classifiers_tick); with clf and knn the step's patterns
+ * are captured once.  labels: HOST int32 [n], each member's label of this tick (outside [0, labels): none; NULL with knn_learn == 0);
+ * knn_best: HOST int32 [n][5]; knn_votes: HOST int32 [n][labels] or NULL.  The host knows every label, so it knows every stream's
+ * slot: the labels, the counts and the slots ride in the tick's staging copy and there is no place launch -- still one copy in, one
+ * copy out and one wait, and behind the tick's launches kgknn_append (when any stream stores), kgknn_distance_lds and kgknn_select
+ * (two kgknn_scatter more in the global-table form), whatever n is; a sharing bank: kknn_distance_lds and kknn_select over the n
+ * queries as one batch.  A member's reset flag does not touch its store.  Refused with nothing enqueued: what htm_classifiers_tick
+ * refuses; a one-stream object; another stream count, device or shape than the group's; knn_learn != 0 on a sharing bank
+ * (HTM_ERR_STATE) or without labels; a labelled tick of a stream at capacity (HTM_ERR_CAPACITY). */
+int htm_knns_tick(htm_group *g, const double *values, const htm_scalar_field *fields, int32_t n_fields, const uint32_t *packed_inputs,
+                  const uint8_t *resets, int32_t learning, int32_t use_graph, htm_live_row *rows, int32_t *decoded, int32_t *votes,
+                  htm_likelihood *lk, double *likelihood, htm_classifier *clf, const int32_t *targets, int32_t learn, int32_t *best,
+                  int32_t *dist, htm_knn *knn, const int32_t *labels, int32_t knn_learn, int32_t *knn_best, int32_t *knn_votes);
+
 #ifdef __cplusplus
 }
 #endif
