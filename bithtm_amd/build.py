@@ -20,8 +20,12 @@ LATER_REPORTS = {"htm_handover.h": os.path.join(HERE, "libbithtm_hip.handover.re
 # ... and the banks of KNN classifiers, which none of the three functions above returns (tests/test_handover_cpu.py holds
 # every_kernel_resources() to the three reports it had): library_kernel_resources() is every kernel of the library.
 BANK_REPORTS = {"htm_knn_bank.h": os.path.join(HERE, "libbithtm_hip.knn_bank.resources.json")}
+# ... and the last launch of the batched run's two-launch step with its list role, which none of the four functions above returns
+# (tests/test_group_knn_cpu.py holds library_kernel_resources() to the four reports it had): whole_library_kernel_resources() is every
+# kernel of the library (tests/test_winner_list_cpu.py).
+LAST_REPORTS = {"htm_handover_last.h": os.path.join(HERE, "libbithtm_hip.handover_last.resources.json")}
 SOURCES = ["htm_engine.hip"]
-HEADERS = ["htm_dev.h", "htm_sp_kernels.h", "htm_tm_kernels.h", "htm_pipeline.h", "htm_record.h", "htm_reset.h", "htm_decode.h", "htm_stack.h", "htm_forecast.h", "htm_noise.h", "htm_group.h", "htm_tm_feed.h", "htm_sp_run.h", "htm_fork.h", "htm_scalar.h", "htm_live.h", "htm_fields.h", "htm_likelihood.h", "htm_classifier.h", "htm_knn.h", "htm_knn_bank.h", "htm_handover.h", "htm_rng.h", "htm_fexp.h",
+HEADERS = ["htm_dev.h", "htm_sp_kernels.h", "htm_tm_kernels.h", "htm_pipeline.h", "htm_record.h", "htm_reset.h", "htm_decode.h", "htm_stack.h", "htm_forecast.h", "htm_noise.h", "htm_group.h", "htm_tm_feed.h", "htm_sp_run.h", "htm_fork.h", "htm_scalar.h", "htm_live.h", "htm_fields.h", "htm_likelihood.h", "htm_classifier.h", "htm_knn.h", "htm_knn_bank.h", "htm_handover.h", "htm_handover_last.h", "htm_rng.h", "htm_fexp.h",
            os.path.join("..", "..", "include", "bithtm_hip.h")]
 # -ffp-contract=off: several kernels must round exactly like the NumPy expressions they replace
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off",
@@ -30,7 +34,7 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-ffp
 
 
 def _stale():
-    if not os.path.exists(LIB) or not all(os.path.exists(r) for r in [RESOURCES] + list(OWN_REPORTS.values()) + list(LATER_REPORTS.values()) + list(BANK_REPORTS.values())):
+    if not os.path.exists(LIB) or not all(os.path.exists(r) for r in [RESOURCES] + list(OWN_REPORTS.values()) + list(LATER_REPORTS.values()) + list(BANK_REPORTS.values()) + list(LAST_REPORTS.values())):
         return True
     t = os.path.getmtime(LIB)
     deps = [os.path.join(CSRC, s) for s in SOURCES + HEADERS] + [os.path.abspath(__file__)]
@@ -85,7 +89,7 @@ def build(force=False, verbose=False):
     if r.returncode != 0:
         raise RuntimeError("hipcc failed:\n" + r.stdout)
     by_header = _kernel_resources(r.stdout)
-    for header, path in list(OWN_REPORTS.items()) + list(LATER_REPORTS.items()) + list(BANK_REPORTS.items()):
+    for header, path in list(OWN_REPORTS.items()) + list(LATER_REPORTS.items()) + list(BANK_REPORTS.items()) + list(LAST_REPORTS.items()):
         with open(path, "w") as f:
             json.dump(by_header.pop(header, {}), f, indent=0, sort_keys=True)
     with open(RESOURCES, "w") as f:
@@ -99,9 +103,9 @@ def build(force=False, verbose=False):
 
 def kernel_resources(header=None):
     """{mangled kernel name: resources} of the library as last built here (None if it was built elsewhere): the kernels of RESOURCES,
-    or those the header `header` of OWN_REPORTS, LATER_REPORTS or BANK_REPORTS defines."""
+    or those the header `header` of OWN_REPORTS, LATER_REPORTS, BANK_REPORTS or LAST_REPORTS defines."""
     build()
-    path = RESOURCES if header is None else {**OWN_REPORTS, **LATER_REPORTS, **BANK_REPORTS}[header]
+    path = RESOURCES if header is None else {**OWN_REPORTS, **LATER_REPORTS, **BANK_REPORTS, **LAST_REPORTS}[header]
     if not os.path.exists(path):
         return None
     with open(path) as f:
@@ -122,8 +126,15 @@ def every_kernel_resources():
 
 
 def library_kernel_resources():
-    """Every kernel of the library: every_kernel_resources() and the reports of BANK_REPORTS together (None if it was built elsewhere)."""
+    """Every kernel the library had with the KNN classifier banks: every_kernel_resources() and the reports of BANK_REPORTS together
+    (None if it was built elsewhere).  The kernels of LAST_REPORTS are not among them: whole_library_kernel_resources()."""
     parts = [every_kernel_resources()] + [kernel_resources(h) for h in BANK_REPORTS]
+    return None if any(p is None for p in parts) else {k: v for p in parts for k, v in p.items()}
+
+
+def whole_library_kernel_resources():
+    """Every kernel of the library: library_kernel_resources() and the reports of LAST_REPORTS together (None if it was built elsewhere)."""
+    parts = [library_kernel_resources()] + [kernel_resources(h) for h in LAST_REPORTS]
     return None if any(p is None for p in parts) else {k: v for p in parts for k, v in p.items()}
 
 

@@ -58,6 +58,7 @@
 #include "htm_knn.h"
 #include "htm_knn_bank.h"
 #include "htm_handover.h"
+#include "htm_handover_last.h"
 
 // ------------------------------------------------------------------------------------------
 // host side
@@ -588,7 +589,16 @@ static decltype(&k_learn_scan_emit<1, 6>) const kt_lse_large[4] = {k_learn_scan_
                                                                    k_learn_scan_emit<4, 4, false>, k_learn_scan_emit<8, 4, false>};
 static decltype(&k_learn_scan_emit<1, 6>) const kt_lse_tab[4] = {k_learn_scan_emit<1, 6, true>, k_learn_scan_emit<2, 6, true>,
                                                                  k_learn_scan_emit<4, 6, true>, k_learn_scan_emit<8, 6, true>};
-static decltype(&k_learn_scan_emit<1, 6>) lse_kernel(const Dev &d, int form) {
+// ... and the forms with the list role at the end of the grid (k_last_handover, htm_handover_last.h): the last launch of a step
+// whose first launch is k_first_handover
+static decltype(&k_learn_scan_emit<1, 6>) const kt_lsel_large[4] = {k_last_handover<1, 4, false>, k_last_handover<2, 4, false>,
+                                                                    k_last_handover<4, 4, false>, k_last_handover<8, 4, false>};
+static decltype(&k_learn_scan_emit<1, 6>) const kt_lsel_tab[4] = {k_last_handover<1, 6, true>, k_last_handover<2, 6, true>,
+                                                                  k_last_handover<4, 6, true>, k_last_handover<8, 6, true>};
+static decltype(&k_learn_scan_emit<1, 6>) const kt_lsel_plain[4] = {k_last_handover<1, 6, false>, k_last_handover<2, 6, false>,
+                                                                    k_last_handover<4, 6, false>, k_last_handover<8, 6, false>};
+static decltype(&k_learn_scan_emit<1, 6>) lse_kernel(const Dev &d, int form, bool list = false) {
+    if (list) return (form == LSE_TAB ? kt_lsel_tab : form == LSE_LARGE ? kt_lsel_large : kt_lsel_plain)[epl_slot(d)];
     return (form == LSE_TAB ? kt_lse_tab : form == LSE_LARGE ? kt_lse_large : kt_lse_plain)[epl_slot(d)];
 }
 
@@ -597,7 +607,9 @@ static int lse_form(const htm_handle *h) { return scan_pool_is_large(h) ? LSE_LA
 
 // the last launch of a step in the two- and three-launch schedules: learn(p) + scan(p) beside the select finish + winner list of the
 // step of the other parity (n_emit blocks of it, or none)
-static void launch_learn_scan_emit(htm_handle *h, int p, int n_emit) {
+// list: the step's first launch was k_first_handover -- the kernel with the list role, one block behind the scan's (it writes the
+// step's winner list where that launch's block 0 did not, and resets its flag words: such a step ALWAYS ends in this form)
+static void launch_learn_scan_emit(htm_handle *h, int p, int n_emit, bool list = false) {
     Dev &d = h->d;
     const int epl = learn_epl(d);
     const size_t lds = std::max(std::max(learn_lds(epl, 256), lean_scan_lds(d)), sizeof(EmitShared));
@@ -610,12 +622,12 @@ static void launch_learn_scan_emit(htm_handle *h, int p, int n_emit) {
     const int n_learn = dyn ? h->sz.lean_learn_blocks_large : h->sz.lean_learn_blocks;
     int n_scan = large ? h->sz.lean_scan_blocks_large : h->sz.lean_scan_blocks;
     if (dyn) n_scan = std::max(64, h->sz.lean_resident_large - n_emit - n_learn);
-    const int grid = n_emit + n_learn + n_scan;
+    const int grid = n_emit + n_learn + n_scan + (list ? 1 : 0);
     if (large && !dyn) n_scan = -n_scan;
     const int spec = dyn ? 0 : scan_spec_blocks(h);
     // (the launch's name says which form of the scan it holds: htm_profile_read is how tests and bench.py tell)
     const char *lse_name = large ? "tm_learn+tm_scan_large+sp_emit" : "tm_learn+tm_scan+sp_emit";
-    LAUNCH_ON(h, h->stream, lds, lse_name, lse_kernel(d, lse_form(h)), grid, 256, d, p, n_emit, n_learn, n_scan, spec);
+    LAUNCH_ON(h, h->stream, lds, lse_name, lse_kernel(d, lse_form(h), list), grid, 256, d, p, n_emit, n_learn, n_scan, spec);
 }
 
 // classification blocks of k_act_mid_rows (the two-launch schedule's first launch)
@@ -660,7 +672,7 @@ static void enqueue_lean(htm_handle *h, int p, int learning, const uint32_t *ban
         LAUNCH_ON(h, h->stream, (size_t)SEL_BINS * 4, "tm_mid+sp_overlap", k_mid_overlap, 1 + n_cls + n_ov + h->sz.zero_blocks, 256, d, p, d.k, 1, learning, n_cls,
                   bank, n_inputs, h->sz.G, n_ov);
     }
-    launch_learn_scan_emit(h, p, plan.next_sp ? h->sz.c256_blocks : 0);
+    launch_learn_scan_emit(h, p, plan.next_sp ? h->sz.c256_blocks : 0, h->knob.lean == 2);
 }
 
 static decltype(&k_learn_overlap<1>) const kt_learn_overlap[4] = {k_learn_overlap<1>, k_learn_overlap<2>, k_learn_overlap<4>, k_learn_overlap<8>};
@@ -1054,7 +1066,10 @@ static void size_launches(htm_handle *h) {
         for (int form = LSE_TAB; asked && form <= LSE_LARGE; ++form) {
             if (form == LSE_TAB && !lean_tab(d)) continue;           // (never launched without the tables)
             int per_cu = 0;
-            asked = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void *)lse_kernel(d, form), 256, lean_lds) == hipSuccess;
+            int per_cu_list = 0;                      // (the batched run's form of the launch, with the list role: the same figures)
+            asked = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void *)lse_kernel(d, form), 256, lean_lds) == hipSuccess &&
+                    hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu_list, (const void *)lse_kernel(d, form, true), 256, lean_lds) == hipSuccess;
+            per_cu = std::min(per_cu, per_cu_list);
             per_cu_lean = std::min(per_cu_lean, per_cu);
             if (asked && form == LSE_LARGE) z.lean_resident_large = per_cu * z.cus;
         }

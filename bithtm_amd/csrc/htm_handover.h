@@ -5,7 +5,9 @@
 // Block 0 (role_handover_block0).  At the bench shape's steady state no winner is without a segment (n_un == 0 in every traced
 // step: profiles/r22_block0_stamps.txt, tools/block0_stamps.py): behind the fan-in the block loads the column lists, stores the
 // winner list and the step's counts, and ends -- about 2.3 us for one trip and a handful of stores; none of the allocation below
-// runs there.  In role_mid's block 0 the compiler places the scalar loads of the kernel's own arguments (Dev is passed by value:
+// runs there.  (Since round 23 not even that: where no activation block raised its flag -- fan_flag, below -- block 0 ends behind
+// the wait, and the winner list and the counts are built by the step's last launch, k_last_handover, htm_handover_last.h.  What
+// follows is the block where a winner does lack a segment.)  In role_mid's block 0 the compiler places the scalar loads of the kernel's own arguments (Dev is passed by value:
 // the list pointers, the output pointers) where a field is first used, behind the wait and behind the lists; here they are read
 // before the wait and pinned in registers.  On its own that cannot be told from noise (r22_ab_summary.txt); it is kept because it
 // takes loads off the chain and costs nothing.
@@ -76,8 +78,17 @@ __device__ __forceinline__ void role_handover_block0(const Dev &d, int p, int n_
 #endif
     c = (Counters *)ctr;
     HSTAMP(0, wall_clock64());
-    wait();
+    // Nothing can need a segment (learning off, or no distal state yet: every `unacc` word is 0), or -- behind the wait -- no activation
+    // block raised its flag: the block has no binding to make, and the step's winner list and counts are the list role's, one launch
+    // later (role_winner_list, htm_handover_last.h, told by n_un == 0).  With learning off the block needs nothing of the activation
+    // and does not wait for it.
+    auto nothing_to_bind = [&]() {
+        if (threadIdx.x == 0) { c->n_un = 0; c->n_bind[p] = 0; }
+    };
+    if (!learning || !has_distal) { nothing_to_bind(); return; }
+    const bool flagged = wait();
     HSTAMP(1, wall_clock64());
+    if (!flagged) { HSTAMP(6, 0ull); nothing_to_bind(); return; }
     uint32_t carry_w = 0, carry_u = 0, n_cells = 0;
     // the words of the LAST pass stay in registers: their winners are stored at the end of the block (one pass covers 2 048 words)
     uint32_t ww[LPT];
@@ -259,6 +270,52 @@ __device__ __forceinline__ void role_handover_block0(const Dev &d, int p, int n_
 #define BITHTM_HANDOVER_PRE_NSYN true
 #endif
 
+// ---- the flag: "a winner of this step has no segment" -----------------------------------------------------------------------------
+// Word 1 of each fan-in counter line (word 0 is the counter fan_wait polls; the lines are 128 bytes apart).  An activation block that
+// holds a winner without a segment stores 1 there, agent scope, AHEAD of fan_signal's s_waitcnt vmcnt(0): the store is acknowledged
+// before the block counts itself done.  Block 0 reads a line's counter and flag with ONE 8-byte load per lane, so a count that holds
+// an arrival comes with that block's flag: it cannot see every arrival and miss a flag.  Reset with the counters by the step's last
+// launch (fan_reset_flags, htm_handover_last.h).  At the steady state no block stores anything.
+__device__ __forceinline__ uint32_t *fan_line(const Dev &d, int p, int i) { return d.fan + (size_t)(p * FAN_COUNTERS + i) * FAN_STRIDE; }
+static_assert(FAN_STRIDE >= 2 && (FAN_STRIDE * 4) % 8 == 0, "a line holds the counter and the flag, 8 bytes aligned");
+
+__device__ __forceinline__ void fan_flag(const Dev &d, int p, int b, bool raise) {
+    if (__ballot(raise) != 0 && lane_id() == 0)
+        __hip_atomic_store(fan_line(d, p, b & (FAN_COUNTERS - 1)) + 1, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// fan_wait (htm_pipeline.h: the same bounded spin, error bit 32) that also tells whether any arrived block raised its flag
+__device__ __forceinline__ bool fan_wait_flagged(const Dev &d, int p, uint32_t target) {
+    __shared__ uint32_t s_flagged;
+    if (threadIdx.x < 64) {
+        u64 flags = 0;
+        for (int looks = 0;; ++looks) {
+            const u64 v = threadIdx.x < FAN_COUNTERS
+                              ? __hip_atomic_load((const u64 *)fan_line(d, p, (int)threadIdx.x), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0ull;
+            flags = __ballot((uint32_t)(v >> 32) != 0u);
+            if (wave_sum((uint32_t)v) >= target) break;
+            if (looks >= (1 << 18)) {                                // (an activation block never arrived)
+                if (threadIdx.x == 0) atomicOr(&d.ctr->error, 32);
+                break;
+            }
+            __builtin_amdgcn_s_sleep(BITHTM_FAN_SLEEP);
+        }
+        if (threadIdx.x == 0) s_flagged = flags != 0 ? 1u : 0u;
+    }
+    __syncthreads();
+    return s_flagged != 0u;
+}
+
+// role_activate<true> (htm_sp_kernels.h), returning whether the lane group's column has a winner without a segment
+__device__ __forceinline__ bool role_activate_unacc(const Dev &d, int p, int blk, int n_active) {
+    const int idx = blk * tm_groups_per_block(d) + tm_group_of(d, threadIdx.x);
+    const bool ok = idx < n_active;
+    const int a = ok ? d.active_cols[p][idx] : 0;
+    const ColumnWords w = tm_column_words(d, p, 1, ok, a, tm_pred_words(d, p, ok, a));
+    tm_store_column<true>(d, p, ok, a, idx, w);
+    return ok && w.unacc != 0;
+}
+
 // grid and arguments: k_act_mid_rows' (htm_pipeline.h); list_cap: entries of the list of winners without a segment kept in LDS
 __global__ __launch_bounds__(256, BITHTM_LEAN2_WAVES) void k_first_handover(Dev d, int p, int n_active, int n_act_blocks, int learning, int n_cls,
                                                         const uint32_t *__restrict__ bank, int n_inputs, int n_rows, int G, int n_overlap_blocks,
@@ -273,13 +330,13 @@ __global__ __launch_bounds__(256, BITHTM_LEAN2_WAVES) void k_first_handover(Dev 
         if (b < n) role = r; else b -= n;
     }
     if (role == 0) {
-        role_activate<true>(d, p, 1, b, n_active);
+        fan_flag(d, p, b, role_activate_unacc(d, p, b, n_active));
         fan_signal(d, p, b);
         return;
     }
     if (role == 1) {
         auto wait = [&]() { fan_wait(d, p, (uint32_t)n_act_blocks); };
-        if (b == 0) role_handover_block0(d, p, n_active, learning, list_cap, (uint32_t *)dyn_lds, wait);
+        if (b == 0) role_handover_block0(d, p, n_active, learning, list_cap, (uint32_t *)dyn_lds, [&]() { return fan_wait_flagged(d, p, (uint32_t)n_act_blocks); });
         else { __builtin_assume(b > 0); role_mid<256, decltype(wait), BITHTM_HANDOVER_PRE_NSYN>(d, p, n_active, 1, learning, b, n_cls, 1, wait); }   // (role_mid's own block 0 is not this kernel's)
         return;
     }

@@ -24,9 +24,10 @@ LAUNCHES = ("tm_activate+sp_emit", "tm_mid+sp_learn", "tm_learn+sp_overlap", "tm
 TWO = os.environ.get("BITHTM_LEAN", "2") == "2"          # the default schedule: two launches per step
 LEAN = ("tm_activate+tm_mid+sp_learn+sp_overlap" if TWO else "tm_activate+sp_learn", "tm_mid+sp_overlap", "tm_learn+tm_scan+sp_emit", "-")
 LEAN_ON = os.environ.get("BITHTM_LEAN", "2") != "0"
+HAS_LIST = os.environ.get("TIMELINE_LIST", "1") != "0"      # (0: a library whose last launch has no list role)
 
 
-def roles(launch, k, C):
+def roles(launch, k, C, last=4096):
     """(first block, last block + 1, name) of the roles of each launch, as bench's handle lays them out."""
     c256, cls = (C + 255) // 256, 96
     if LEAN_ON:                                      # the three-launch schedule (htm_pipeline.h); block counts as htm_create sets them
@@ -46,6 +47,8 @@ def roles(launch, k, C):
             return ((0, n_act, "tm_activate"), (n_act, n_act + k, "sp rows"), (n_act + k, n_act + k + c256, "sp duty"), (n_act + k + c256, 4096, "clear"))
         if launch == 1:
             return ((0, 1, "tm_mid block 0"), (1, 1 + 4 * cls, "tm_mid classify"), (1 + 4 * cls, 1 + 4 * cls + n_ov, "sp_overlap"), (1 + 4 * cls + n_ov, 4096, "zero match bits"))
+        if launch == 2 and TWO and HAS_LIST:         # (k_last_handover: the list role is the grid's last block, `last`)
+            return ((0, c256, "sp_emit"), (c256, c256 + n_learn, "tm_learn"), (c256 + n_learn, last, "tm_scan"), (last, last + 1, "winner list"))
         if launch == 2:
             return ((0, c256, "sp_emit"), (c256, c256 + n_learn, "tm_learn"), (c256 + n_learn, 4096, "tm_scan"))
         return ()
@@ -86,7 +89,7 @@ def main():
         gap = "" if prev is None or first - prev > 3000 else f"  gap {(first - prev) / 100:5.2f}"
         print(f"parity {slot // 4} {(LEAN if LEAN_ON else LAUNCHES)[slot % 4]:24s} {(first - t0) / 100:7.2f} .. {(last - t0) / 100:7.2f} us  span {(last - first) / 100:6.2f}{gap}")
         prev = last
-        for lo, hi, name in roles(slot % 4, k, C):
+        for lo, hi, name in roles(slot % 4, k, C, int(blocks.max())):
             sel = blocks[(blocks >= lo) & (blocks < hi)]
             if len(sel):
                 st, en = t[slot][sel, 0] - first, t[slot][sel, 1] - first
