@@ -4657,13 +4657,16 @@ extern "C" int htm_classifiers_import(htm_classifier *clf, htm_handle *h, const 
 }
 
 // ------------------------------------------------------------------------------------------
-// KNN classifier (htm_knn.h): the store, its labels and stamps and the scratch of an update in device memory;
-// the slots in use, the step total and the labels of the learning calls on the host -- every store is decided here, nothing is read
-// back.  As the classifier it keeps nothing of the handles its calls come through.
+// KNN classifiers (htm_knn.h, htm_knn_bank.h; DESIGN.md sections 26 and 27): the stores, their labels and stamps and the scratch of an
+// update in device memory; the slots in use, the step total and the labels of the learning calls on the host -- every store is decided
+// here, nothing is read back.  As the classifier it keeps nothing of the handles its calls come through.  Every host call is written
+// once, as knn_<call>(what, bank, ...): `bank` is the door the call came through (htm_knns_*; false: htm_knn_*), and the one-stream
+// object is the n == 1 case with the one-stream kernels.
 struct htm_knn {
     int device = 0;
     KnnDev d{};
-    int32_t count = 0;
+    std::vector<int32_t> counts;                // [n] the slots in use ...
+    int32_t count = 0;                          // ... and the largest of them
     int64_t total = 0;
     int64_t device_bytes = 0;
     std::vector<void *> allocs;
@@ -4672,12 +4675,11 @@ struct htm_knn {
     size_t labels_cap = 0;
     int32_t *d_pos = nullptr;                   // the slot of every step of the call in flight, of pos_cap words
     size_t pos_cap = 0;
-    // a bank (htm_knns_*; htm_knn_bank.h): n stores member-major in d's arrays, or n frozen streams over `source`'s
+    // n streams (a one-stream object: 1): n stores member-major in d's arrays, or, in a bank, n frozen streams over `source`'s
     int32_t n = 1, chunk = HTM_KNN_CHUNK;
     int refs = 1;                               // the object itself and every bank that shares its store
     htm_knn *source = nullptr;
-    std::vector<int32_t> counts;                // [n] (count is the largest of them)
-    void **d_tab = nullptr;                     // [n] input pointers, then [n][2] counts: the table of the update in flight
+    void **d_tab = nullptr;                     // a bank's [n] input pointers, then [n][2] counts: the table of the update in flight
     bool is_bank = false;
 };
 
@@ -4720,10 +4722,9 @@ static int knn_grow(const char *what, htm_knn *knn, htm_handle *h, int32_t **p, 
     return 0;
 }
 
-extern "C" int htm_knn_create(htm_handle *h, const htm_knn_config *cfg, htm_knn **out) {
-    const std::string what = "htm_knn_create";
-    if (out) *out = nullptr;
-    if (!h || !cfg || !out) return cls_refuse(h, what + ": null argument", HTM_ERR_ARGUMENT);
+// what a create call checks of its handle and its config (and of n_streams, where a bank's checks have it), and the scalar fields of
+// the KnnDev the config asks for; *words: the words of one query's table, not yet narrowed
+static int knn_config(const std::string &what, htm_handle *h, const htm_knn_config *cfg, int32_t n_streams, KnnDev *dev, int64_t *words) {
     if (cfg->struct_bytes != sizeof(htm_knn_config)) return cls_refuse(h, what + ": htm_knn_config size mismatch", HTM_ERR_ARGUMENT);
     const bool ok = cfg->labels >= 1 && cfg->labels <= HTM_KNN_MAX_LABELS && cfg->k >= 1 && cfg->k <= HTM_KNN_MAX_K && cfg->min_overlap >= 1 &&
                     cfg->min_overlap <= 65535 && cfg->capacity >= 1 && cfg->capacity <= HTM_KNN_MAX_CAPACITY && cfg->cell_dim >= 1 && cfg->cell_dim <= 64 &&
@@ -4731,11 +4732,9 @@ extern "C" int htm_knn_create(htm_handle *h, const htm_knn_config *cfg, htm_knn 
     if (!ok)
         return cls_refuse(h, what + ": labels in [1, 1024], k in [1, 64], min_overlap in [1, 65535], capacity in [1, 2^20], cell_dim in [1, 64], "
                              "units a positive multiple of cell_dim, max_pairs in [1, 2047]", HTM_ERR_ARGUMENT);
+    if (n_streams < 1 || n_streams > HTM_KNNS_MAX_STREAMS) return cls_refuse(h, what + ": n_streams must be in [1, 65535]", HTM_ERR_ARGUMENT);
     if (h->world > 1) return cls_refuse(h, what + ": not available on a column-sharded handle", HTM_ERR_STATE);
-    HIPCHK(h, hipSetDevice(h->device));
-    htm_knn *knn = new htm_knn();
-    knn->device = h->device;
-    KnnDev &d = knn->d;
+    KnnDev d{};
     d.labels = cfg->labels;
     d.k = cfg->k;
     d.min_overlap = cfg->min_overlap;
@@ -4744,25 +4743,72 @@ extern "C" int htm_knn_create(htm_handle *h, const htm_knn_config *cfg, htm_knn 
     d.WPC = (cfg->cell_dim + 31) / 32;
     d.n_cols = cfg->units / cfg->cell_dim;
     d.max_pairs = cfg->max_pairs;
-    const int64_t words = knn_table_words(d.n_cols, d.WPC);
-    d.words = (int32_t)words;
-    d.queries = knn_queries(words);
-    d.in_lds = knn_in_lds(words);
-    d.bitmap = knn_has_bitmap(words);
+    *words = knn_table_words(d.n_cols, d.WPC);
+    d.words = (int32_t)*words;
+    d.queries = knn_queries(*words);
+    d.in_lds = knn_in_lds(*words);
+    d.bitmap = knn_has_bitmap(*words);
     d.shift = knn_shift(knn_max_overlap(d.max_pairs, d.K));
-    const size_t cap = (size_t)d.capacity;
-    d.store = knn_alloc<ClsPair>(knn, h, cap * d.max_pairs);
-    d.label = knn_alloc<int32_t>(knn, h, cap);
-    d.stamp = knn_alloc<int64_t>(knn, h, cap);
-    d.ovl = knn_alloc<uint16_t>(knn, h, (size_t)HTM_KNN_CHUNK * cap);
-    d.table = d.in_lds ? nullptr : knn_alloc<uint32_t>(knn, h, (size_t)HTM_KNN_CHUNK * (size_t)words);
+    *dev = d;
+    return 0;
+}
+
+// A one-stream object (bank == false: n_streams 1, chunks of HTM_KNN_CHUNK, no table of an update), a bank of n_streams stores, or a
+// bank of n_streams frozen streams over the store of `share`: that one holds scratch only.
+static int knn_create(const std::string &what, bool bank, htm_handle *h, const htm_knn_config *cfg, int32_t n_streams, htm_knn *share, htm_knn **out) {
+    if (out) *out = nullptr;
+    if (!h || !cfg || !out) return cls_refuse(h, what + ": null argument", HTM_ERR_ARGUMENT);
+    KnnDev d{};
+    int64_t words = 0;
+    if (int rc = knn_config(what, h, cfg, n_streams, &d, &words)) return rc;
+    if (share) {
+        if (share->is_bank) return cls_refuse(h, what + ": share_store_of is a bank: only a one-stream object's store is shared", HTM_ERR_ARGUMENT);
+        if (share->device != h->device) return cls_refuse(h, what + ": share_store_of is on another device than the handle", HTM_ERR_ARGUMENT);
+        const KnnDev &sd = share->d;
+        if (sd.labels != d.labels || sd.k != d.k || sd.min_overlap != d.min_overlap || sd.capacity != d.capacity || sd.K != d.K || sd.n_cols != d.n_cols ||
+            sd.max_pairs != d.max_pairs)
+            return cls_refuse(h, what + ": share_store_of was made with another config", HTM_ERR_ARGUMENT);
+        d.store = sd.store; d.label = sd.label; d.stamp = sd.stamp;     // (where they lie; the scratch is the bank's own)
+    }
+    // (the streams of a shared store are one flat batch of queries: a chunk that takes a tick's n queries in one launch where that fits)
+    const int chunk = !bank ? HTM_KNN_CHUNK : share ? gknn_shared_chunk(n_streams, d.capacity, words) : gknn_chunk(n_streams, d.capacity, words);
+    if (bank && (words > INT32_MAX || chunk < 1))
+        return cls_refuse(h, what + ": the scratch of one query step of " + std::to_string(n_streams) + " streams does not fit " +
+                                 std::to_string(HTM_KNNS_SCRATCH_BYTES >> 20) + " MiB: fewer streams or a smaller capacity", HTM_ERR_ARGUMENT);
+    HIPCHK(h, hipSetDevice(h->device));
+    htm_knn *knn = new htm_knn();
+    knn->device = h->device;
+    knn->is_bank = bank;
+    knn->n = n_streams;
+    knn->chunk = chunk;
+    knn->counts.assign((size_t)n_streams, 0);
+    const size_t cap = (size_t)d.capacity, n = (size_t)n_streams, rows = (share ? 1 : n) * (size_t)chunk;
+    if (!share) {
+        d.store = knn_alloc<ClsPair>(knn, h, n * cap * d.max_pairs);
+        d.label = knn_alloc<int32_t>(knn, h, n * cap);
+        d.stamp = knn_alloc<int64_t>(knn, h, n * cap);
+    }
+    d.ovl = knn_alloc<uint16_t>(knn, h, rows * cap);
+    d.table = d.in_lds ? nullptr : knn_alloc<uint32_t>(knn, h, rows * (size_t)words);
+    if (bank && !share) knn->d_tab = knn_alloc<void *>(knn, h, 2 * n);      // (n pointers and n x 2 counts of 4 bytes)
+    knn->d = d;
     // (the state is there when the call returns, whatever stream the first update comes on)
-    if (words > INT32_MAX || !d.store || !d.label || !d.stamp || !d.ovl || (!d.in_lds && !d.table) || hipStreamSynchronize(h->stream) != hipSuccess) {
+    if (words > INT32_MAX || !d.store || !d.label || !d.stamp || !d.ovl || (!d.in_lds && !d.table) || (bank && !share && !knn->d_tab) ||
+        hipStreamSynchronize(h->stream) != hipSuccess) {
         htm_knn_destroy(knn);
         return cls_refuse(h, what + ": device allocation failed", HTM_ERR_HIP);
     }
+    if (share) {
+        knn->source = share;
+        ++share->refs;
+    }
     *out = knn;
     return HTM_OK;
+}
+
+extern "C" int htm_knn_create(htm_handle *h, const htm_knn_config *cfg, htm_knn **out) { return knn_create("htm_knn_create", false, h, cfg, 1, nullptr, out); }
+extern "C" int htm_knns_create(htm_handle *h, const htm_knn_config *cfg, int32_t n_streams, htm_knn *share_store_of, htm_knn **out) {
+    return knn_create("htm_knns_create", true, h, cfg, n_streams, share_store_of, out);
 }
 
 // what every call on an existing object checks of its handle
@@ -4775,254 +4821,46 @@ static int knn_check(const char *what, htm_knn *knn, htm_handle *h, bool bank = 
     return 0;
 }
 
-extern "C" int htm_knn_labels(htm_knn *knn, htm_handle *h, const int32_t *host_labels, int32_t n_labels, const int32_t **device_labels) {
-    const char *what = "htm_knn_labels";
-    if (device_labels) *device_labels = nullptr;
-    if (int rc = knn_check(what, knn, h)) return rc;
-    if (!host_labels || !device_labels || n_labels < 1) return cls_refuse(h, std::string(what) + ": need host labels, n_labels >= 1 and a place for the address", HTM_ERR_ARGUMENT);
-    HIPCHK(h, hipSetDevice(knn->device));
-    if (int rc = knn_grow(what, knn, h, &knn->d_labels, &knn->labels_cap, (size_t)n_labels)) return rc;
-    knn->labels.assign(host_labels, host_labels + n_labels);
-    // (from the call's own pageable words: the copy has read them when it returns)
-    HIPCHK(h, hipMemcpyAsync(knn->d_labels, host_labels, (size_t)n_labels * 4, hipMemcpyHostToDevice, h->stream));
-    *device_labels = knn->d_labels;
-    return HTM_OK;
-}
-
-extern "C" int htm_knn_update(htm_knn *knn, htm_handle *h, const void *device_pairs, int32_t pairs_per_step, int32_t n_steps,
-                              const int32_t *device_labels, int32_t n_labels, int32_t first_step, int32_t learn, int32_t *device_best,
-                              int32_t *device_votes) {
-    const char *what = "htm_knn_update";
-    if (int rc = knn_check(what, knn, h)) return rc;
-    const std::string w = std::string(what) + ": ";
-    if (!device_pairs || !device_labels || !device_best) return cls_refuse(h, w + "null pairs, labels or output", HTM_ERR_ARGUMENT);
-    const KnnDev &d = knn->d;
-    if (pairs_per_step < 1 || pairs_per_step > d.max_pairs)
-        return cls_refuse(h, w + "pairs_per_step must be in [1, max_pairs = " + std::to_string(d.max_pairs) + "]", HTM_ERR_ARGUMENT);
-    if (n_steps < 0 || n_labels < 1 || first_step < 0) return cls_refuse(h, w + "n_steps >= 0, n_labels >= 1, first_step >= 0", HTM_ERR_ARGUMENT);
-    // what the call stores: counted on the host, from the labels the host gave
-    int64_t stored = 0;
-    if (learn && n_steps > 0) {
-        if (device_labels != knn->d_labels || (size_t)n_labels != knn->labels.size())
-            return cls_refuse(h, w + "a learning call reads the labels of htm_knn_labels (its address, its n_labels): the host counts what is stored", HTM_ERR_ARGUMENT);
-        for (int i = 0; i < n_steps; ++i) {
-            const int32_t g = knn->labels[(size_t)(((int64_t)first_step + i) % n_labels)];
-            stored += g >= 0 && g < d.labels;
-        }
-    }
-    if (knn->count + stored > d.capacity)
-        return cls_refuse(h, w + "the call would store " + std::to_string(stored) + " patterns in a store of " + std::to_string(knn->count) + " of capacity = " +
-                                 std::to_string(d.capacity) + " slots", HTM_ERR_CAPACITY);
-    if (n_steps == 0) return HTM_OK;
-    HIPCHK(h, hipSetDevice(knn->device));
-    if (stored)
-        if (int rc = knn_grow(what, knn, h, &knn->d_pos, &knn->pos_cap, (size_t)n_steps)) return rc;
-    KnnStep s{(const ClsPair *)device_pairs, pairs_per_step, device_labels, n_labels, first_step, n_steps, device_best, device_votes, knn->total, knn->count,
-              knn->count + (int32_t)stored};
-    const hipStream_t st = h->stream;
-    if (stored) {
-        LAUNCH_ON(h, st, 0, "knn:place", kknn_place, 1, 256, d, s, knn->d_pos);
-        LAUNCH_ON(h, st, 0, "knn:append", kknn_append, (unsigned)(((int64_t)n_steps * d.max_pairs + 255) / 256), 256, d, s, (const int32_t *)knn->d_pos);
-    }
-    for (int first = 0; first < n_steps; first += HTM_KNN_CHUNK) {
-        const int nq = std::min<int>(HTM_KNN_CHUNK, n_steps - first);
-        const unsigned scatter = (unsigned)(((int64_t)nq * pairs_per_step + 255) / 256);
-        if (s.count > 0) {
-            const dim3 grid(knn_slot_blocks(s.count), knn_query_groups(nq, d.queries));
-            if (d.in_lds) {
-                LAUNCH_ON(h, st, (size_t)knn_distance_lds(d.words), "knn:distance", kknn_distance_lds, grid, 256, d, s, first, nq);
-            } else {
-                LAUNCH_ON(h, st, 0, "knn:scatter", kknn_scatter, scatter, 256, d, s, first, nq, 1);
-                LAUNCH_ON(h, st, (size_t)knn_distance_lds(d.words), "knn:distance", kknn_distance_global, grid, 256, d, s, first, nq);
-            }
-        }
-        LAUNCH_ON(h, st, 0, "knn:select", kknn_select, nq, 256, d, s, first);
-        if (s.count > 0 && !d.in_lds) LAUNCH_ON(h, st, 0, "knn:clear", kknn_scatter, scatter, 256, d, s, first, nq, 0);
-    }
-    knn->count = s.count;
-    knn->total += n_steps;
-    return launch_status(h->err);
-}
-
-// the store emptied: the slots in use are the host's (the launches enqueued before carry their own count)
-extern "C" int htm_knn_reset(htm_knn *knn, htm_handle *h) {
-    if (int rc = knn_check("htm_knn_reset", knn, h)) return rc;
-    knn->count = 0;
-    return HTM_OK;
-}
-
-// The state: int64 total; int64 count; count x max_pairs pairs; count int64 stamps; count int32 labels
-static int64_t knn_state_bytes(const htm_knn *knn, int64_t count) { return 16 + count * ((int64_t)knn->d.max_pairs * 8 + 12); }
-
-extern "C" int htm_knn_info(const htm_knn *knn, htm_knn_info_t *out) {
-    if (!knn || !out || out->struct_bytes != sizeof(htm_knn_info_t)) return HTM_ERR_ARGUMENT;
-    const KnnDev &d = knn->d;
-    *out = htm_knn_info_t{(uint32_t)sizeof(htm_knn_info_t), d.labels, d.k, d.min_overlap, d.capacity, d.n_cols * d.K, d.K, d.max_pairs, knn->count, d.in_lds,
-                          d.queries, d.shift, knn->total, knn_state_bytes(knn, knn->count), knn->device_bytes};
-    return HTM_OK;
-}
-
-// the state copied to the host blob (load == 0) or from it, behind everything enqueued on h's stream
-static int knn_state(const char *what, bool load, htm_knn *knn, htm_handle *h, void *host_state, int64_t bytes) {
-    if (int rc = knn_check(what, knn, h)) return rc;
-    const std::string w = std::string(what) + ": ";
-    if (!host_state || bytes < 16) return cls_refuse(h, w + "need host_state of htm_knn_info's state_bytes", HTM_ERR_ARGUMENT);
-    const KnnDev &d = knn->d;
-    int64_t head[2] = {knn->total, knn->count};
-    if (load) memcpy(head, host_state, 16);
-    if (head[1] < 0 || head[1] > d.capacity || head[0] < 0 || bytes != knn_state_bytes(knn, head[1]))
-        return cls_refuse(h, w + "need host_state of 16 + count x (8 max_pairs + 12) bytes with 0 <= count <= capacity, total >= 0", HTM_ERR_ARGUMENT);
-    const size_t n = (size_t)head[1], pair_bytes = n * d.max_pairs * 8;
-    char *pairs = (char *)host_state + 16, *stamps = pairs + pair_bytes, *labels = stamps + n * 8;
-    if (load) {
-        int64_t last = -1;
-        for (size_t i = 0; i < n; ++i) {
-            int64_t stamp;
-            int32_t label;
-            memcpy(&stamp, stamps + i * 8, 8);
-            memcpy(&label, labels + i * 4, 4);
-            if (stamp <= last || stamp >= head[0]) return cls_refuse(h, w + "the stamps must ascend and lie below total (slot " + std::to_string(i) + ")", HTM_ERR_ARGUMENT);
-            if (label < 0 || label >= d.labels) return cls_refuse(h, w + "a label outside [0, labels) in slot " + std::to_string(i), HTM_ERR_ARGUMENT);
-            last = stamp;
-        }
-    }
-    HIPCHK(h, hipSetDevice(knn->device));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    if (load) {
-        if (n) {
-            HIPCHK(h, hipMemcpy(d.store, pairs, pair_bytes, hipMemcpyHostToDevice));
-            HIPCHK(h, hipMemcpy(d.stamp, stamps, n * 8, hipMemcpyHostToDevice));
-            HIPCHK(h, hipMemcpy(d.label, labels, n * 4, hipMemcpyHostToDevice));
-        }
-        knn->total = head[0];
-        knn->count = (int32_t)head[1];
-    } else {
-        memcpy(host_state, head, 16);
-        if (n) {
-            HIPCHK(h, hipMemcpy(pairs, d.store, pair_bytes, hipMemcpyDeviceToHost));
-            HIPCHK(h, hipMemcpy(stamps, d.stamp, n * 8, hipMemcpyDeviceToHost));
-            HIPCHK(h, hipMemcpy(labels, d.label, n * 4, hipMemcpyDeviceToHost));
-        }
-    }
-    return HTM_OK;
-}
-
-extern "C" int htm_knn_export(htm_knn *knn, htm_handle *h, void *host_state, int64_t bytes) { return knn_state("htm_knn_export", false, knn, h, host_state, bytes); }
-extern "C" int htm_knn_import(htm_knn *knn, htm_handle *h, const void *host_state, int64_t bytes) {
-    return knn_state("htm_knn_import", true, knn, h, (void *)host_state, bytes);
-}
-
-// ------------------------------------------------------------------------------------------
-// Banks of KNN classifiers (htm_knn_bank.h): n stores in one object, or n frozen streams over the store of a
-// bound one-stream object.  As there, the counts and the total are the host's.
-extern "C" int htm_knns_create(htm_handle *h, const htm_knn_config *cfg, int32_t n_streams, htm_knn *share_store_of, htm_knn **out) {
-    const std::string what = "htm_knns_create";
-    if (out) *out = nullptr;
-    if (!h || !cfg || !out) return cls_refuse(h, what + ": null argument", HTM_ERR_ARGUMENT);
-    if (cfg->struct_bytes != sizeof(htm_knn_config)) return cls_refuse(h, what + ": htm_knn_config size mismatch", HTM_ERR_ARGUMENT);
-    const bool ok = cfg->labels >= 1 && cfg->labels <= HTM_KNN_MAX_LABELS && cfg->k >= 1 && cfg->k <= HTM_KNN_MAX_K && cfg->min_overlap >= 1 &&
-                    cfg->min_overlap <= 65535 && cfg->capacity >= 1 && cfg->capacity <= HTM_KNN_MAX_CAPACITY && cfg->cell_dim >= 1 && cfg->cell_dim <= 64 &&
-                    cfg->units >= cfg->cell_dim && cfg->units % cfg->cell_dim == 0 && cfg->max_pairs >= 1 && cfg->max_pairs <= HTM_KNN_MAX_PAIRS;
-    if (!ok)
-        return cls_refuse(h, what + ": labels in [1, 1024], k in [1, 64], min_overlap in [1, 65535], capacity in [1, 2^20], cell_dim in [1, 64], "
-                             "units a positive multiple of cell_dim, max_pairs in [1, 2047]", HTM_ERR_ARGUMENT);
-    if (n_streams < 1 || n_streams > HTM_KNNS_MAX_STREAMS) return cls_refuse(h, what + ": n_streams must be in [1, 65535]", HTM_ERR_ARGUMENT);
-    if (h->world > 1) return cls_refuse(h, what + ": not available on a column-sharded handle", HTM_ERR_STATE);
-    const htm_knn *src = share_store_of;
-    if (src) {
-        if (src->is_bank) return cls_refuse(h, what + ": share_store_of is a bank: only a one-stream object's store is shared", HTM_ERR_ARGUMENT);
-        if (src->device != h->device) return cls_refuse(h, what + ": share_store_of is on another device than the handle", HTM_ERR_ARGUMENT);
-        const KnnDev &sd = src->d;
-        if (sd.labels != cfg->labels || sd.k != cfg->k || sd.min_overlap != cfg->min_overlap || sd.capacity != cfg->capacity || sd.K != cfg->cell_dim ||
-            sd.n_cols * sd.K != cfg->units || sd.max_pairs != cfg->max_pairs)
-            return cls_refuse(h, what + ": share_store_of was made with another config", HTM_ERR_ARGUMENT);
-    }
-    const int64_t words = knn_table_words(cfg->units / cfg->cell_dim, (cfg->cell_dim + 31) / 32);
-    // (the streams of a shared store are one flat batch of queries: a chunk that takes a tick's n queries in one launch where that fits)
-    const int chunk = src ? gknn_shared_chunk(n_streams, cfg->capacity, words) : gknn_chunk(n_streams, cfg->capacity, words);
-    if (words > INT32_MAX || chunk < 1)
-        return cls_refuse(h, what + ": the scratch of one query step of " + std::to_string(n_streams) + " streams does not fit " +
-                                 std::to_string(HTM_KNNS_SCRATCH_BYTES >> 20) + " MiB: fewer streams or a smaller capacity", HTM_ERR_ARGUMENT);
-    HIPCHK(h, hipSetDevice(h->device));
-    htm_knn *knn = new htm_knn();
-    knn->device = h->device;
-    knn->is_bank = true;
-    knn->n = n_streams;
-    knn->chunk = chunk;
-    knn->counts.assign((size_t)n_streams, 0);
-    KnnDev &d = knn->d;
-    const size_t cap = (size_t)cfg->capacity, n = (size_t)n_streams;
-    bool bad;
-    if (src) {
-        d = src->d;                                 // (the store, labels and stamps where they lie; the scratch is the bank's own)
-        d.ovl = knn_alloc<uint16_t>(knn, h, (size_t)chunk * cap);
-        d.table = d.in_lds ? nullptr : knn_alloc<uint32_t>(knn, h, (size_t)chunk * (size_t)words);
-        bad = !d.ovl || (!d.in_lds && !d.table);
-    } else {
-        d.labels = cfg->labels;
-        d.k = cfg->k;
-        d.min_overlap = cfg->min_overlap;
-        d.capacity = cfg->capacity;
-        d.K = cfg->cell_dim;
-        d.WPC = (cfg->cell_dim + 31) / 32;
-        d.n_cols = cfg->units / cfg->cell_dim;
-        d.max_pairs = cfg->max_pairs;
-        d.words = (int32_t)words;
-        d.queries = knn_queries(words);
-        d.in_lds = knn_in_lds(words);
-        d.bitmap = knn_has_bitmap(words);
-        d.shift = knn_shift(knn_max_overlap(d.max_pairs, d.K));
-        d.store = knn_alloc<ClsPair>(knn, h, n * cap * d.max_pairs);
-        d.label = knn_alloc<int32_t>(knn, h, n * cap);
-        d.stamp = knn_alloc<int64_t>(knn, h, n * cap);
-        d.ovl = knn_alloc<uint16_t>(knn, h, n * (size_t)chunk * cap);
-        d.table = d.in_lds ? nullptr : knn_alloc<uint32_t>(knn, h, n * (size_t)chunk * (size_t)words);
-        knn->d_tab = knn_alloc<void *>(knn, h, 2 * n);      // (n pointers and n x 2 counts of 4 bytes)
-        bad = !d.store || !d.label || !d.stamp || !d.ovl || (!d.in_lds && !d.table) || !knn->d_tab;
-    }
-    if (bad || hipStreamSynchronize(h->stream) != hipSuccess) {
-        htm_knn_destroy(knn);
-        return cls_refuse(h, what + ": device allocation failed", HTM_ERR_HIP);
-    }
-    if (share_store_of) {
-        knn->source = share_store_of;
-        ++share_store_of->refs;
-    }
-    *out = knn;
-    return HTM_OK;
-}
-
 // host labels [n][n_labels] into the object's own array
-extern "C" int htm_knns_labels(htm_knn *knn, htm_handle *h, const int32_t *host_labels, int32_t n_labels, const int32_t **device_labels) {
-    const char *what = "htm_knns_labels";
+static int knn_labels(const char *what, bool bank, htm_knn *knn, htm_handle *h, const int32_t *host_labels, int32_t n_labels, const int32_t **device_labels) {
     if (device_labels) *device_labels = nullptr;
-    if (int rc = knn_check(what, knn, h, true)) return rc;
+    if (int rc = knn_check(what, knn, h, bank)) return rc;
     if (!host_labels || !device_labels || n_labels < 1) return cls_refuse(h, std::string(what) + ": need host labels, n_labels >= 1 and a place for the address", HTM_ERR_ARGUMENT);
     const size_t words = (size_t)knn->n * (size_t)n_labels;
     HIPCHK(h, hipSetDevice(knn->device));
     if (int rc = knn_grow(what, knn, h, &knn->d_labels, &knn->labels_cap, words)) return rc;
     knn->labels.assign(host_labels, host_labels + words);
+    // (from the call's own pageable words: the copy has read them when it returns)
     HIPCHK(h, hipMemcpyAsync(knn->d_labels, host_labels, words * 4, hipMemcpyHostToDevice, h->stream));
     *device_labels = knn->d_labels;
     return HTM_OK;
 }
 
-// the launches of the queries [0, nq_all) of one flat batch against a one-stream view (d, s) in chunks: what htm_knn_update enqueues
-static int knn_enqueue_queries(htm_handle *h, hipStream_t st, const KnnDev &d, const KnnStep &s, int chunk) {
+extern "C" int htm_knn_labels(htm_knn *knn, htm_handle *h, const int32_t *host_labels, int32_t n_labels, const int32_t **device_labels) {
+    return knn_labels("htm_knn_labels", false, knn, h, host_labels, n_labels, device_labels);
+}
+extern "C" int htm_knns_labels(htm_knn *knn, htm_handle *h, const int32_t *host_labels, int32_t n_labels, const int32_t **device_labels) {
+    return knn_labels("htm_knns_labels", true, knn, h, host_labels, n_labels, device_labels);
+}
+
+// the launches of the queries [0, s.n_steps) of one flat batch against a one-stream view (d, s) in chunks, profiled as knn:... for a
+// one-stream object's call and as knns:... for a sharing bank's
+#define KNN_NAME(bank, tail) ((bank) ? "knns:" tail : "knn:" tail)
+static int knn_enqueue_queries(htm_handle *h, hipStream_t st, bool bank, const KnnDev &d, const KnnStep &s, int chunk) {
     for (int first = 0; first < s.n_steps; first += chunk) {
         const int nq = std::min<int>(chunk, s.n_steps - first);
         const unsigned scatter = (unsigned)(((int64_t)nq * s.pairs_per_step + 255) / 256);
         if (s.count > 0) {
             const dim3 grid(knn_slot_blocks(s.count), knn_query_groups(nq, d.queries));
             if (d.in_lds) {
-                LAUNCH_ON(h, st, (size_t)knn_distance_lds(d.words), "knns:distance", kknn_distance_lds, grid, 256, d, s, first, nq);
+                LAUNCH_ON(h, st, (size_t)knn_distance_lds(d.words), KNN_NAME(bank, "distance"), kknn_distance_lds, grid, 256, d, s, first, nq);
             } else {
-                LAUNCH_ON(h, st, 0, "knns:scatter", kknn_scatter, scatter, 256, d, s, first, nq, 1);
-                LAUNCH_ON(h, st, (size_t)knn_distance_lds(d.words), "knns:distance", kknn_distance_global, grid, 256, d, s, first, nq);
+                LAUNCH_ON(h, st, 0, KNN_NAME(bank, "scatter"), kknn_scatter, scatter, 256, d, s, first, nq, 1);
+                LAUNCH_ON(h, st, (size_t)knn_distance_lds(d.words), KNN_NAME(bank, "distance"), kknn_distance_global, grid, 256, d, s, first, nq);
             }
         }
-        LAUNCH_ON(h, st, 0, "knns:select", kknn_select, nq, 256, d, s, first);
-        if (s.count > 0 && !d.in_lds) LAUNCH_ON(h, st, 0, "knns:clear", kknn_scatter, scatter, 256, d, s, first, nq, 0);
+        LAUNCH_ON(h, st, 0, KNN_NAME(bank, "select"), kknn_select, nq, 256, d, s, first);
+        if (s.count > 0 && !d.in_lds) LAUNCH_ON(h, st, 0, KNN_NAME(bank, "clear"), kknn_scatter, scatter, 256, d, s, first, nq, 0);
     }
     return 0;
 }
@@ -5063,40 +4901,52 @@ static int knns_enqueue_shared(htm_knn *knn, htm_handle *h, hipStream_t st, cons
     d.store = sd.store; d.label = sd.label; d.stamp = sd.stamp;
     const int32_t count = knn->source->count;
     const KnnStep s{pairs, pairs_per_step, nullptr, 1, 0, (int32_t)queries, best, votes, INT64_MAX / 2, count, count};
-    return knn_enqueue_queries(h, st, d, s, knn->chunk);
+    return knn_enqueue_queries(h, st, true, d, s, knn->chunk);
 }
 
-extern "C" int htm_knns_update(htm_knn *knn, htm_handle *h, const void *const *device_pairs, int32_t pairs_per_step, int32_t n_steps,
-                               const int32_t *device_labels, int32_t n_labels, int32_t first_step, int32_t learn, int32_t *device_best,
-                               int32_t *device_votes) {
-    const char *what = "htm_knns_update";
-    if (int rc = knn_check(what, knn, h, true)) return rc;
+// the steps of [first_step, first_step + n_steps) that stream m stores: counted on the host, from the labels the host gave
+static int64_t knn_stored(const htm_knn *knn, size_t m, int32_t first_step, int32_t n_steps, int32_t n_labels) {
+    int64_t stored = 0;
+    for (int i = 0; i < n_steps; ++i) {
+        const int32_t g = knn->labels[m * (size_t)n_labels + (size_t)(((int64_t)first_step + i) % n_labels)];
+        stored += g >= 0 && g < knn->d.labels;
+    }
+    return stored;
+}
+
+// the refusal of a call that would take stream m past its capacity (the stream is named through the bank's door)
+static int knn_refuse_full(htm_handle *h, const std::string &w, bool bank, size_t m, int64_t stored, int32_t count, int32_t capacity) {
+    return cls_refuse(h, w + (bank ? "stream " + std::to_string(m) + ": " : "") + "the call would store " + std::to_string(stored) + " patterns in a store of " +
+                             std::to_string(count) + " of capacity = " + std::to_string(capacity) + " slots", HTM_ERR_CAPACITY);
+}
+
+// One update of every stream over n_steps steps' patterns: device_pairs holds the streams' n addresses.  A one-stream object always
+// needs its labels; a bank only to learn.
+static int knn_update(const char *what, bool bank, htm_knn *knn, htm_handle *h, const void *const *device_pairs, int32_t pairs_per_step, int32_t n_steps,
+                      const int32_t *device_labels, int32_t n_labels, int32_t first_step, int32_t learn, int32_t *device_best, int32_t *device_votes) {
+    if (int rc = knn_check(what, knn, h, bank)) return rc;
     const std::string w = std::string(what) + ": ";
-    if (!device_pairs || !device_best || (learn && !device_labels)) return cls_refuse(h, w + "null pairs, labels or output", HTM_ERR_ARGUMENT);
+    if (!device_pairs || (!bank && !device_pairs[0]) || !device_best || ((learn || !bank) && !device_labels))
+        return cls_refuse(h, w + "null pairs, labels or output", HTM_ERR_ARGUMENT);
     const size_t n = (size_t)knn->n;
     for (size_t i = 0; i < n; ++i)
         if (!device_pairs[i]) return cls_refuse(h, w + "stream " + std::to_string(i) + " has no pairs", HTM_ERR_ARGUMENT);
-    KnnDev d = knn->d;
+    const KnnDev &d = knn->d;
     if (pairs_per_step < 1 || pairs_per_step > d.max_pairs)
         return cls_refuse(h, w + "pairs_per_step must be in [1, max_pairs = " + std::to_string(d.max_pairs) + "]", HTM_ERR_ARGUMENT);
     if (n_steps < 0 || n_labels < 1 || first_step < 0) return cls_refuse(h, w + "n_steps >= 0, n_labels >= 1, first_step >= 0", HTM_ERR_ARGUMENT);
     if (learn && knn->source) return cls_refuse(h, w + "the streams read another object's store: learn must be 0", HTM_ERR_STATE);
-    if ((int64_t)n * n_steps > INT32_MAX / 8) return cls_refuse(h, w + "n_streams x n_steps must stay below 2^28", HTM_ERR_ARGUMENT);
-    // what every stream stores: counted on the host, from the labels the host gave; one stream past its capacity refuses the call
+    if (bank && (int64_t)n * n_steps > INT32_MAX / 8) return cls_refuse(h, w + "n_streams x n_steps must stay below 2^28", HTM_ERR_ARGUMENT);
+    // what every stream stores; one stream past its capacity refuses the call
     std::vector<int32_t> after(knn->counts);
     int64_t stored_all = 0;
     if (learn && n_steps > 0) {
         if (device_labels != knn->d_labels || (size_t)n_labels * n != knn->labels.size())
-            return cls_refuse(h, w + "a learning call reads the labels of htm_knns_labels (its address, its n_labels): the host counts what is stored", HTM_ERR_ARGUMENT);
+            return cls_refuse(h, w + "a learning call reads the labels of " + (bank ? "htm_knns_labels" : "htm_knn_labels") +
+                                     " (its address, its n_labels): the host counts what is stored", HTM_ERR_ARGUMENT);
         for (size_t m = 0; m < n; ++m) {
-            int64_t stored = 0;
-            for (int i = 0; i < n_steps; ++i) {
-                const int32_t g = knn->labels[m * (size_t)n_labels + (size_t)(((int64_t)first_step + i) % n_labels)];
-                stored += g >= 0 && g < d.labels;
-            }
-            if (knn->counts[m] + stored > d.capacity)
-                return cls_refuse(h, w + "stream " + std::to_string(m) + ": the call would store " + std::to_string(stored) + " patterns in a store of " +
-                                         std::to_string(knn->counts[m]) + " of capacity = " + std::to_string(d.capacity) + " slots", HTM_ERR_CAPACITY);
+            const int64_t stored = knn_stored(knn, m, first_step, n_steps, n_labels);
+            if (knn->counts[m] + stored > d.capacity) return knn_refuse_full(h, w, bank, m, stored, knn->counts[m], d.capacity);
             after[m] += (int32_t)stored;
             stored_all += stored;
         }
@@ -5117,32 +4967,55 @@ extern "C" int htm_knns_update(htm_knn *knn, htm_handle *h, const void *const *d
     }
     if (stored_all)
         if (int rc = knn_grow(what, knn, h, &knn->d_pos, &knn->pos_cap, n * (size_t)n_steps)) return rc;
-    // the one copy of the table, from the call's own (pageable) words: the copy has read them when it returns
-    std::vector<void *> tab(2 * n, nullptr);
-    int32_t *tab_counts = (int32_t *)(tab.data() + n);
     int32_t largest = 0;
-    for (size_t m = 0; m < n; ++m) {
-        tab[m] = (void *)device_pairs[m];
-        tab_counts[2 * m] = knn->counts[m];
-        tab_counts[2 * m + 1] = after[m];
-        largest = std::max(largest, after[m]);
+    for (int32_t c : after) largest = std::max(largest, c);
+    if (!bank) {
+        // the one-stream kernels over the object's own store
+        const KnnStep s{(const ClsPair *)device_pairs[0], pairs_per_step, device_labels, n_labels, first_step, n_steps, device_best, device_votes, knn->total,
+                        knn->counts[0], after[0]};
+        if (stored_all) {
+            LAUNCH_ON(h, st, 0, "knn:place", kknn_place, 1, 256, d, s, knn->d_pos);
+            LAUNCH_ON(h, st, 0, "knn:append", kknn_append, (unsigned)(((int64_t)n_steps * d.max_pairs + 255) / 256), 256, d, s, (const int32_t *)knn->d_pos);
+        }
+        if (int rc = knn_enqueue_queries(h, st, false, d, s, knn->chunk)) return rc;
+    } else {
+        // the one copy of the table, from the call's own (pageable) words: the copy has read them when it returns
+        std::vector<void *> tab(2 * n, nullptr);
+        int32_t *tab_counts = (int32_t *)(tab.data() + n);
+        for (size_t m = 0; m < n; ++m) {
+            tab[m] = (void *)device_pairs[m];
+            tab_counts[2 * m] = knn->counts[m];
+            tab_counts[2 * m + 1] = after[m];
+        }
+        HIPCHK(h, hipMemcpyAsync((void *)knn->d_tab, (const void *)tab.data(), 2 * n * sizeof(void *), hipMemcpyHostToDevice, st));
+        GKnnStep gs{};
+        gs.s = KnnStep{nullptr, pairs_per_step, device_labels, n_labels, first_step, n_steps, device_best, device_votes, knn->total, 0, 0};
+        gs.pairs = (const ClsPair *const *)knn->d_tab;
+        gs.counts = (const int32_t *)(knn->d_tab + n);
+        gs.pos = stored_all ? knn->d_pos : nullptr;
+        if (int rc = knns_enqueue(knn, h, st, gs, largest, stored_all > 0, true)) return rc;
     }
-    HIPCHK(h, hipMemcpyAsync((void *)knn->d_tab, (const void *)tab.data(), 2 * n * sizeof(void *), hipMemcpyHostToDevice, st));
-    GKnnStep gs{};
-    gs.s = KnnStep{nullptr, pairs_per_step, device_labels, n_labels, first_step, n_steps, device_best, device_votes, knn->total, 0, 0};
-    gs.pairs = (const ClsPair *const *)knn->d_tab;
-    gs.counts = (const int32_t *)(knn->d_tab + n);
-    gs.pos = stored_all ? knn->d_pos : nullptr;
-    if (int rc = knns_enqueue(knn, h, st, gs, largest, stored_all > 0, true)) return rc;
-    knn->counts = after;
+    knn->counts.swap(after);
     knn->count = largest;
     knn->total += n_steps;
     return launch_status(h->err);
 }
 
-// the stores of the streams that `streams` names emptied (null: every stream's); the launches enqueued before carry their own counts
-extern "C" int htm_knns_reset(htm_knn *knn, htm_handle *h, const uint8_t *streams) {
-    if (int rc = knn_check("htm_knns_reset", knn, h, true)) return rc;
+extern "C" int htm_knn_update(htm_knn *knn, htm_handle *h, const void *device_pairs, int32_t pairs_per_step, int32_t n_steps,
+                              const int32_t *device_labels, int32_t n_labels, int32_t first_step, int32_t learn, int32_t *device_best,
+                              int32_t *device_votes) {
+    return knn_update("htm_knn_update", false, knn, h, &device_pairs, pairs_per_step, n_steps, device_labels, n_labels, first_step, learn, device_best, device_votes);
+}
+extern "C" int htm_knns_update(htm_knn *knn, htm_handle *h, const void *const *device_pairs, int32_t pairs_per_step, int32_t n_steps,
+                               const int32_t *device_labels, int32_t n_labels, int32_t first_step, int32_t learn, int32_t *device_best,
+                               int32_t *device_votes) {
+    return knn_update("htm_knns_update", true, knn, h, device_pairs, pairs_per_step, n_steps, device_labels, n_labels, first_step, learn, device_best, device_votes);
+}
+
+// the stores of the streams that `streams` names emptied (null: every stream's): the slots in use are the host's (the launches enqueued
+// before carry their own counts)
+static int knn_reset(const char *what, bool bank, htm_knn *knn, htm_handle *h, const uint8_t *streams) {
+    if (int rc = knn_check(what, knn, h, bank)) return rc;
     knn->count = 0;
     for (size_t m = 0; m < (size_t)knn->n; ++m) {
         if (!streams || streams[m]) knn->counts[m] = 0;
@@ -5151,12 +5024,26 @@ extern "C" int htm_knns_reset(htm_knn *knn, htm_handle *h, const uint8_t *stream
     return HTM_OK;
 }
 
+extern "C" int htm_knn_reset(htm_knn *knn, htm_handle *h) { return knn_reset("htm_knn_reset", false, knn, h, nullptr); }
+extern "C" int htm_knns_reset(htm_knn *knn, htm_handle *h, const uint8_t *streams) { return knn_reset("htm_knns_reset", true, knn, h, streams); }
+
 // The state: int64 total; int64 count[n]; then the streams' pairs, the streams' int64 stamps, the streams' int32 labels, each in
-// stream order (a sharing bank: its counts are 0 -- its state is the total)
-static int64_t knns_state_bytes(const htm_knn *knn, const std::vector<int32_t> &counts) {
+// stream order: `slots` slots of n streams in all (one stream: total, count, its pairs, stamps and labels; a sharing bank: its counts
+// are 0 -- its state is the total)
+static int64_t knn_state_bytes(const htm_knn *knn, int64_t n, int64_t slots) { return 8 * (1 + n) + slots * ((int64_t)knn->d.max_pairs * 8 + 12); }
+
+static int64_t knn_slots(const std::vector<int32_t> &counts) {
     int64_t all = 0;
     for (int32_t c : counts) all += c;
-    return 8 * (1 + (int64_t)knn->n) + all * ((int64_t)knn->d.max_pairs * 8 + 12);
+    return all;
+}
+
+extern "C" int htm_knn_info(const htm_knn *knn, htm_knn_info_t *out) {
+    if (!knn || !out || out->struct_bytes != sizeof(htm_knn_info_t)) return HTM_ERR_ARGUMENT;
+    const KnnDev &d = knn->d;
+    *out = htm_knn_info_t{(uint32_t)sizeof(htm_knn_info_t), d.labels, d.k, d.min_overlap, d.capacity, d.n_cols * d.K, d.K, d.max_pairs, knn->count, d.in_lds,
+                          d.queries, d.shift, knn->total, knn_state_bytes(knn, 1, knn->count), knn->device_bytes};
+    return HTM_OK;
 }
 
 extern "C" int htm_knns_info(const htm_knn *knn, htm_knns_info_t *out, int32_t *counts) {
@@ -5165,18 +5052,20 @@ extern "C" int htm_knns_info(const htm_knn *knn, htm_knns_info_t *out, int32_t *
     const int64_t scratch = knn->source ? gknn_scratch_bytes(1, knn->chunk, d.capacity, d.words) : gknn_scratch_bytes(knn->n, knn->chunk, d.capacity, d.words);
     *out = htm_knns_info_t{(uint32_t)sizeof(htm_knns_info_t), d.labels, d.k, d.min_overlap, d.capacity, d.n_cols * d.K, d.K, d.max_pairs, knn->n,
                            knn->source ? 1 : 0, knn->chunk, d.in_lds, d.queries, d.shift, knn->source ? knn->source->count : knn->count, 0, knn->total,
-                           knns_state_bytes(knn, knn->counts), knn->device_bytes, scratch};
+                           knn_state_bytes(knn, knn->n, knn_slots(knn->counts)), knn->device_bytes, scratch};
     if (counts)
         for (size_t m = 0; m < (size_t)knn->n; ++m) counts[m] = knn->counts[m];
     return HTM_OK;
 }
 
-static int knns_state(const char *what, bool load, htm_knn *knn, htm_handle *h, void *host_state, int64_t bytes) {
-    if (int rc = knn_check(what, knn, h, true)) return rc;
+// the state copied to the host blob (load == 0) or from it, behind everything enqueued on h's stream
+static int knn_state(const char *what, bool bank, bool load, htm_knn *knn, htm_handle *h, void *host_state, int64_t bytes) {
+    if (int rc = knn_check(what, knn, h, bank)) return rc;
     const std::string w = std::string(what) + ": ";
     const size_t n = (size_t)knn->n;
     const int64_t head_bytes = 8 * (1 + (int64_t)n);
-    if (!host_state || bytes < head_bytes) return cls_refuse(h, w + "need host_state of htm_knns_info's state_bytes", HTM_ERR_ARGUMENT);
+    if (!host_state || bytes < head_bytes)
+        return cls_refuse(h, w + "need host_state of " + (bank ? "htm_knns_info" : "htm_knn_info") + "'s state_bytes", HTM_ERR_ARGUMENT);
     const KnnDev &d = knn->d;
     std::vector<int64_t> head(1 + n);
     head[0] = knn->total;
@@ -5188,11 +5077,10 @@ static int knns_state(const char *what, bool load, htm_knn *knn, htm_handle *h, 
         ok = ok && head[1 + m] >= 0 && head[1 + m] <= (knn->source ? 0 : d.capacity);
         counts[m] = ok ? (int32_t)head[1 + m] : 0;
     }
-    if (!ok || bytes != knns_state_bytes(knn, counts))
-        return cls_refuse(h, w + "need host_state of 8 (1 + n) + the counts x (8 max_pairs + 12) bytes with 0 <= count <= capacity (0 on a shared store), total >= 0",
-                          HTM_ERR_ARGUMENT);
-    size_t all = 0;
-    for (int32_t c : counts) all += (size_t)c;
+    const size_t all = (size_t)knn_slots(counts);
+    if (!ok || bytes != knn_state_bytes(knn, (int64_t)n, (int64_t)all))
+        return cls_refuse(h, w + (bank ? "need host_state of 8 (1 + n) + the counts x (8 max_pairs + 12) bytes with 0 <= count <= capacity (0 on a shared store), total >= 0"
+                                       : "need host_state of 16 + count x (8 max_pairs + 12) bytes with 0 <= count <= capacity, total >= 0"), HTM_ERR_ARGUMENT);
     const size_t row = (size_t)d.max_pairs * 8;
     char *pairs = (char *)host_state + head_bytes, *stamps = pairs + all * row, *labels = stamps + all * 8;
     if (load) {
@@ -5204,10 +5092,9 @@ static int knns_state(const char *what, bool load, htm_knn *knn, htm_handle *h, 
                 int32_t label;
                 memcpy(&stamp, stamps + at * 8, 8);
                 memcpy(&label, labels + at * 4, 4);
-                if (stamp <= last || stamp >= head[0])
-                    return cls_refuse(h, w + "the stamps must ascend and lie below total (stream " + std::to_string(m) + ", slot " + std::to_string(i) + ")", HTM_ERR_ARGUMENT);
-                if (label < 0 || label >= d.labels)
-                    return cls_refuse(h, w + "a label outside [0, labels) in stream " + std::to_string(m) + ", slot " + std::to_string(i), HTM_ERR_ARGUMENT);
+                const auto slot = [&] { return (bank ? "stream " + std::to_string(m) + ", " : "") + "slot " + std::to_string(i); };
+                if (stamp <= last || stamp >= head[0]) return cls_refuse(h, w + "the stamps must ascend and lie below total (" + slot() + ")", HTM_ERR_ARGUMENT);
+                if (label < 0 || label >= d.labels) return cls_refuse(h, w + "a label outside [0, labels) in " + slot(), HTM_ERR_ARGUMENT);
                 last = stamp;
             }
         }
@@ -5235,9 +5122,13 @@ static int knns_state(const char *what, bool load, htm_knn *knn, htm_handle *h, 
     return HTM_OK;
 }
 
-extern "C" int htm_knns_export(htm_knn *knn, htm_handle *h, void *host_state, int64_t bytes) { return knns_state("htm_knns_export", false, knn, h, host_state, bytes); }
+extern "C" int htm_knn_export(htm_knn *knn, htm_handle *h, void *host_state, int64_t bytes) { return knn_state("htm_knn_export", false, false, knn, h, host_state, bytes); }
+extern "C" int htm_knn_import(htm_knn *knn, htm_handle *h, const void *host_state, int64_t bytes) {
+    return knn_state("htm_knn_import", false, true, knn, h, (void *)host_state, bytes);
+}
+extern "C" int htm_knns_export(htm_knn *knn, htm_handle *h, void *host_state, int64_t bytes) { return knn_state("htm_knns_export", true, false, knn, h, host_state, bytes); }
 extern "C" int htm_knns_import(htm_knn *knn, htm_handle *h, const void *host_state, int64_t bytes) {
-    return knns_state("htm_knns_import", true, knn, h, (void *)host_state, bytes);
+    return knn_state("htm_knns_import", true, true, knn, h, (void *)host_state, bytes);
 }
 
 // ------------------------------------------------------------------------------------------

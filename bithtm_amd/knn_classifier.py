@@ -21,11 +21,18 @@ from .sdr_classifier import model_shape
 
 
 class _DeviceKNN:
-    """What a one-stream KNNClassifier and a KNNClassifierBank share: the parameters, the shape of the patterns, the lazy binding to a
-    device and the device object's life.  Neither is an instance of the other."""
+    """`streams` KNN classifier streams of one config in one device object: the parameters, the shape of the patterns, the lazy binding
+    to a device, the device object's life, and every call, written once over a leading stream axis -- labels [streams, n], patterns
+    [streams, T, n], best [streams, n, 5], votes [streams, n, labels], counts int64 [streams], a state whose stores lie one behind the
+    other in stream order.  KNNClassifierBank is this with its own axis; KNNClassifier is the one stream whose arguments and results
+    come without the axis (_lift puts it on, _drop takes it off) and whose calls go through the one-stream C functions.  Neither is an
+    instance of the other."""
 
-    _prefix = "htm_knn_"                        # of the C functions the calls go through
-    _what = "KNNClassifier"
+    _prefix = None                              # of the C functions the calls go through: htm_knn_ or htm_knns_
+    _what = None
+    _single = False                             # the public arrays come without the stream axis
+    streams = 1
+    source = None                               # KNNClassifierBank.shared(): the KNNClassifier whose store the streams read
 
     def _init(self, labels, k, min_overlap, capacity, shape):
         self.labels, self.k, self.min_overlap, self.capacity = check_params(labels, k, min_overlap, capacity)
@@ -39,9 +46,31 @@ class _DeviceKNN:
         self._home = None                       # a small model of the object's own, made when no other handle is there
         self._bufs = {}                         # the device buffers of a call's outputs: name -> (address, words)
         self._pending = None                    # a state loaded before the object was bound
+        self._counts, self._total = np.zeros(self.streams, dtype=np.int64), 0       # the host's mirror: nothing is read back to know them
 
     def _create(self, engine, cfg, out):
-        return self.lib.htm_knn_create(engine.h, C.byref(cfg), C.byref(out))
+        raise NotImplementedError
+
+    def _pointers(self, a):
+        """A call's device addresses of its pairs -- one, or a sequence of `streams` -- as the update's C function takes them."""
+        return C.c_void_p(a) if self._single else (C.c_void_p * self.streams)(*[int(x) for x in a])
+
+    def _no_shared_learning(self, learning):
+        pass                                    # (KNNClassifierBank.shared() refuses here)
+
+    @property
+    def _axis(self):
+        """The stream axis in the shapes of the public arrays: (streams,), or nothing for the one stream."""
+        return () if self._single else (self.streams,)
+
+    def _lift(self, a):
+        return a[None] if self._single else a
+
+    def _drop(self, a):
+        return a[0] if self._single else a
+
+    def _dims(self, *tail):
+        return "[" + ", ".join(str(x) for x in self._axis + tail) + "]"
 
     def _set_shape(self, column_dim, cell_dim, max_pairs):
         column_dim, cell_dim, max_pairs = int(column_dim), int(cell_dim), int(max_pairs)
@@ -61,6 +90,12 @@ class _DeviceKNN:
     def total(self):
         """Steps seen."""
         return int(self._pending["total"]) if self._knn is None and self._pending is not None else self._total
+
+    @property
+    def count(self):
+        """Slots in use: per stream, int64 [streams] (shared(): zeros -- the store is the owner's); KNNClassifier: an int."""
+        counts = self._pending["count"] if self._knn is None and self._pending is not None else self._counts
+        return int(counts[0]) if self._single else np.array(counts, dtype=np.int64)
 
     # ---- binding
     def _bind(self, engine):
@@ -121,22 +156,234 @@ class _DeviceKNN:
         if rc < 0:
             raise HtmError(f"{what} failed ({rc}): {self.lib.htm_last_error(engine.h).decode()}")
 
+    # ---- what a call stores, decided here
+    def check_labels(self, labels):
+        """int [streams, n] -> int32: any value outside [0, labels) is no label (-1)."""
+        g = np.asarray(labels)
+        if g.ndim != len(self._axis) + 1 or self._lift(g).shape[0] != self.streams or g.dtype.kind not in "iu":
+            raise ValueError(f"labels: int {self._dims('n')}, got {g.dtype} {list(g.shape)}")
+        g = g.astype(np.int64)
+        return np.ascontiguousarray(np.where((g < 0) | (g >= self.labels), -1, g).astype(np.int32))
+
+    def stored_by(self, labels, first_step, n, learning):
+        """int64 [streams] (KNNClassifier: an int): the patterns a call of n steps would store per stream; step i reads
+        labels[s][(first_step + i) % rows]."""
+        stored = np.zeros(self.streams, dtype=np.int64)
+        if learning and n > 0:
+            flags = self._lift(np.asarray(labels)) >= 0
+            rows = flags.shape[1]
+            whole, rest = divmod(int(n), rows)
+            at = (int(first_step) + np.arange(rest)) % rows
+            stored = (whole * flags.sum(axis=1) + flags[:, at].sum(axis=1)).astype(np.int64)
+        return int(stored[0]) if self._single else stored
+
+    def check_room(self, stored):
+        """ValueError for a call that would take ANY stream past capacity: refused as a whole before anything is enqueued."""
+        stored, count = self._lift(np.asarray(stored)), self._lift(np.asarray(self.count))
+        over = np.nonzero(count + stored > self.capacity)[0]
+        if over.size:
+            i = int(over[0])
+            raise ValueError(f"knn: {'' if self._single else f'stream {i}: '}the call would store {int(stored[i])} patterns in a store of {int(count[i])} "
+                             f"of capacity = {self.capacity} slots")
+
+    def upload_labels(self, engine, labels):
+        """int32 [streams, n] (check_labels) -> the device address of the labels of a run's rows (the object's own array: the C labels
+        call)."""
+        self._bind(engine)
+        labels = np.ascontiguousarray(labels, dtype=np.int32)
+        out = C.c_void_p()
+        self._call(engine, "labels", labels.ctypes.data_as(C.c_void_p), self._lift(labels).shape[1], C.byref(out))
+        return out.value
+
+    # ---- the update over device memory (what run() and ModelGroup.run() call; nothing here waits)
+    def pairs_buffer(self, engine, n):
+        """The device address of a buffer [streams][n][max_pairs] pairs (kept)."""
+        self._bind(engine)
+        return engine.kept_buffer(self._bufs, "pairs", 2 * self.streams * max(int(n), 1) * self.shape[2], spare=2)
+
+    def enqueue(self, engine, device_pairs, pairs_per_step, n, device_labels, host_labels, first_step, learning, votes=False):
+        """ONE update of every stream over n steps' patterns in device memory (device_pairs: `streams` addresses; KNNClassifier: one),
+        enqueued on `engine`'s stream; device_labels is upload_labels' address of host_labels (int32 [streams, rows]; a bank takes
+        None for both in a frozen call).  read(engine, n, votes) after the stream's wait gives the results.  ValueError, with
+        nothing enqueued, for a call in which any stream does not fit its store."""
+        self._bind(engine)
+        n, S = int(n), self.streams
+        self._no_shared_learning(learning)
+        stored = self.stored_by(host_labels, first_step, n, learning and host_labels is not None)
+        self.check_room(stored)
+        rows = self._lift(host_labels).shape[1] if host_labels is not None else 1
+        best = engine.kept_buffer(self._bufs, "best", S * max(n, 1) * 5, spare=2)
+        all_votes = engine.kept_buffer(self._bufs, "votes", S * max(n, 1) * self.labels, spare=2) if votes else None
+        self._call(engine, "update", self._pointers(device_pairs), int(pairs_per_step), n, C.c_void_p(device_labels) if device_labels else None, rows,
+                   int(first_step), int(bool(learning)), C.c_void_p(best), C.c_void_p(all_votes) if all_votes else None)
+        self._counts += stored
+        self._total += n
+
+    def read(self, engine, n, votes=False):
+        """(best int32 [streams, n, 5], votes int32 [streams, n, labels] or None) of the last enqueue, after the engine's stream has
+        been waited for."""
+        n, S = int(n), self.streams
+        best = engine.read_words(self._bufs["best"][0], S * n * 5, np.int32).reshape(S, n, 5)
+        all_votes = engine.read_words(self._bufs["votes"][0], S * n * self.labels, np.int32).reshape(S, n, self.labels) if votes else None
+        return self._drop(best), (self._drop(all_votes) if votes else None)
+
+    # ---- the stand-alone door
+    def update_patterns(self, index, words, labels=None, learning=True, votes=False, device=None):
+        """T further steps of every stream from their patterns: index int [S, T, n], words uint32 [S, T, n] (pair j of step t is
+        (index[t, j], words[t, j]); a negative index or a zero word contributes nothing), labels int [S, T] (outside [0, labels):
+        none; a bank's None: nothing is labelled).  Checked here: the indices of a step are distinct and inside the table, no word
+        has a bit at or above cell_dim, n <= max_pairs, every stream's labelled steps fit its store -- a call in which any stream's
+        do not is refused as a whole.  -> (best int32 [S, T, 5]: label, votes, nearest_overlap, nearest_slot, nearest_step; votes
+        int32 [S, T, labels] or None)."""
+        if self.shape is None:
+            raise RuntimeError(f"the KNN classifier does not know the shape of its patterns yet: use it with a model, or give {self._what}(shape=)")
+        S = self.streams
+        if not self._single:
+            index, words = np.asarray(index), np.asarray(words)
+            if index.ndim != 3 or index.shape[0] != S or words.shape != index.shape:
+                raise ValueError(f"patterns: index int [{S}, T, n] and words uint32 [{S}, T, n], got {index.shape} and {words.shape}")
+            index, words = (a.reshape(S * a.shape[1], a.shape[2]) for a in (index, words))
+        index, words = check_patterns(index, words, self.units, self.shape[1])              # (every stream's steps, one behind the other)
+        T, n = index.shape[0] // S, index.shape[1]
+        if not 1 <= n <= self.shape[2]:
+            raise ValueError(f"patterns: 1 to max_pairs = {self.shape[2]} pairs per step, got {n}")
+        labels = self._lift(self.check_labels(np.full((S, max(T, 1)), -1) if labels is None and not self._single else labels))
+        if (T or self._single) and labels.shape != (S, T):
+            raise ValueError(f"labels: int {self._dims(T)}, got {list(self._drop(labels).shape)}")
+        learning = bool(learning)
+        self._no_shared_learning(learning)
+        self.check_room(self.stored_by(self._drop(labels), 0, T, learning))
+        if T == 0:
+            return self._drop(np.zeros((S, 0, 5), np.int32)), (self._drop(np.zeros((S, 0, self.labels), np.int32)) if votes else None)
+        engine = self._engine(device)
+        pairs = np.empty((S, T, n, 2), dtype=np.int32)
+        pairs[..., 0], pairs[..., 1] = index.reshape(S, T, n), words.view(np.int32).reshape(S, T, n)
+        buf = engine.device_buffer(pairs.nbytes, pairs)
+        try:
+            labelled = learning or self._single             # (the one stream always passes its labels)
+            device_labels = self.upload_labels(engine, self._drop(labels)) if labelled else None
+            self.enqueue(engine, self._drop([buf + i * T * n * 8 for i in range(S)]), n, T, device_labels, self._drop(labels) if labelled else None, 0, learning,
+                         votes)
+            engine.sync()
+            best, all_votes = self.read(engine, T, votes)
+            return best.copy(), (all_votes.copy() if votes else None)
+        finally:
+            engine.sync()
+            self.lib.hipFree(buf)
+
+    # ---- reset, state: kept with the stream axis (count int64 [streams], the stores one behind the other), also while pending
+    def _reset(self, flags):
+        """Empty every stream's store, or those `flags` (uint8 [streams]) names."""
+        if self._knn is None:
+            if self._pending is not None:
+                keep = np.zeros(self.streams, bool) if flags is None else flags == 0
+                self._pending = self._select(self._pending, keep)
+            return
+        self._call(self._engine(), "reset", *(() if self._single else (flags.ctypes.data_as(C.c_void_p) if flags is not None else None,)))
+        self._counts = np.where(flags == 0, self._counts, 0) if flags is not None else np.zeros(self.streams, dtype=np.int64)
+
+    def _select(self, state, keep):
+        """`state` with the stores of the streams not in `keep` (bool [streams]) emptied."""
+        counts = np.asarray(state["count"], dtype=np.int64)
+        rows = np.repeat(keep, counts)
+        return dict(total=state["total"], count=np.where(keep, counts, 0), pairs=state["pairs"][rows], labels=state["labels"][rows], stamps=state["stamps"][rows])
+
+    def _empty_state(self):
+        pairs = np.zeros((0, self.shape[2], 2), dtype=np.int32)
+        return dict(total=np.int64(0), count=np.zeros(self.streams, np.int64), pairs=pairs, labels=np.zeros(0, np.int32), stamps=np.zeros(0, np.int64))
+
+    def _params(self):
+        return (self.labels, self.k, self.min_overlap, self.capacity) + (self.shape or ())
+
+    def state_dict(self):
+        """{"params": int64 [labels, k, min_overlap, capacity, column_dim, cell_dim, max_pairs], "streams": int64, "total": int64,
+        "count": int64 [streams], "pairs": int32 [sum of count, max_pairs, 2], "labels": int32 [sum], "stamps": int64 [sum]} -- the
+        streams' stores one behind the other in stream order, read from the device (shared(): counts 0 -- the store is the owner's;
+        KNNClassifier: "count" one int64 and no "streams")."""
+        if self.shape is None:
+            raise RuntimeError("the KNN classifier does not know the shape of its patterns yet")
+        if self._knn is None:
+            state = self._pending if self._pending is not None else self._empty_state()
+        else:
+            engine = self._engine()
+            S, n, P = self.streams, int(self._counts.sum()), self.shape[2]
+            head = 8 * (1 + S)
+            size = head + n * (8 * P + 12)
+            assert size == self.info()["state_bytes"]
+            blob = np.zeros(size, dtype=np.uint8)
+            self._call(engine, "export", blob.ctypes.data_as(C.c_void_p), size)
+            words = blob[:head].view(np.int64)
+            at = head + n * P * 8
+            state = dict(total=np.int64(words[0]), count=words[1:], pairs=blob[head:at].view(np.int32).reshape(n, P, 2),
+                         stamps=blob[at:at + n * 8].view(np.int64), labels=blob[at + n * 8:].view(np.int32))
+        out = {k: np.array(self._drop(v) if k == "count" else v)[()] for k, v in state.items()}        # (copies; [()]: a scalar of a 0-d array)
+        return dict(out, params=np.asarray(self._params(), dtype=np.int64), **({} if self._single else {"streams": np.int64(self.streams)}))
+
+    def load_state_dict(self, state):
+        """The state of a state_dict() of an object with the same parameters, shape and streams."""
+        params = tuple(int(x) for x in state["params"])
+        if self.shape is None and len(params) == 7:
+            self._set_shape(*params[4:])
+        streams = 1 if self._single else int(state["streams"])
+        if params != self._params() or streams != self.streams:
+            theirs, mine = ("", "") if self._single else (f" and {streams} streams", f" and {self.streams}")
+            raise ValueError(f"the state was saved with parameters {params} (labels, k, min_overlap, capacity, column_dim, cell_dim, max_pairs){theirs}, "
+                             f"this object has {self._params()}{mine}")
+        total = int(state["total"])
+        counts = np.ascontiguousarray(self._lift(np.asarray(int(state["count"]) if self._single else state["count"], dtype=np.int64)))
+        pairs = np.ascontiguousarray(state["pairs"], dtype=np.int32)
+        labels = np.ascontiguousarray(state["labels"], dtype=np.int32)
+        stamps = np.ascontiguousarray(state["stamps"], dtype=np.int64)
+        top = 0 if self.source is not None else self.capacity
+        if counts.shape != (self.streams,) or (counts < 0).any() or (counts > top).any() or total < 0:
+            if self._single:
+                raise ValueError(f"state: 0 <= count <= capacity = {self.capacity} and total >= 0, got count {int(counts[0])}, total {total}")
+            raise ValueError(f"state: count int64 [{self.streams}] with 0 <= count <= {top} and total >= 0, got count {counts.tolist()}, total {total}")
+        n = int(counts.sum())
+        for name, a, want in (("pairs", pairs, (n, self.shape[2], 2)), ("labels", labels, (n,)), ("stamps", stamps, (n,))):
+            if a.shape != want:
+                raise ValueError(f"state['{name}']: {list(want)}, got {list(a.shape)}")
+        if n and (labels.min() < 0 or labels.max() >= self.labels):
+            raise ValueError(f"state['labels']: a label outside [0, {self.labels})")
+        at = 0
+        for c in counts.tolist():
+            mine = stamps[at:at + c]
+            if c and (mine[0] < 0 or mine[-1] >= total or (np.diff(mine) <= 0).any()):
+                whose = "the" if self._single else "every stream's"
+                raise ValueError(f"state['stamps']: {whose} stamps ascend and lie below total")
+            at += c
+        clean = dict(total=np.int64(total), count=counts.copy(), pairs=pairs.copy(), labels=labels.copy(), stamps=stamps.copy())
+        if self._knn is None:
+            self._pending = clean
+        else:
+            self._import(self._engine(), clean)
+
+    def _import(self, engine, state):
+        head = np.concatenate([[int(state["total"])], np.asarray(state["count"], dtype=np.int64)]).astype(np.int64)
+        blob = np.concatenate([head.view(np.uint8), state["pairs"].view(np.uint8).ravel(), state["stamps"].view(np.uint8).ravel(),
+                               state["labels"].view(np.uint8).ravel()])
+        self._call(engine, "import", blob.ctypes.data_as(C.c_void_p), blob.size)
+        self._counts, self._total = np.asarray(state["count"], dtype=np.int64).copy(), int(state["total"])
+
 
 class KNNClassifier(_DeviceKNN):
     """The classifier of `labels` labels: a step's result is the label most of its `k` nearest stored patterns carry, nearest by
     overlap (at least `min_overlap`), in a store of `capacity` slots that never overwrites.  The shape of the patterns --
     column_dim, cell_dim and the pairs a pattern has at most -- comes from the model of the first run(knn=), or from
     `shape=(column_dim, cell_dim, max_pairs)` for stand-alone use.  The object binds to a device lazily, as SDRClassifier does;
-    every update continues where the last one ended, whichever door it came through."""
+    every update continues where the last one ended, whichever door it came through.  The calls are _DeviceKNN's for one stream,
+    without the stream axis: labels int [n], patterns [T, n], best [n, 5], votes [n, labels], `count` an int, a state of "count": int64
+    and no "streams"."""
+
+    _prefix = "htm_knn_"
+    _what = "KNNClassifier"
+    _single = True
 
     def __init__(self, labels, k=1, min_overlap=1, capacity=4096, shape=None):
         self._init(labels, k, min_overlap, capacity, shape)
-        self._count, self._total = 0, 0         # the host's mirror: nothing is read back to know them
 
-    @property
-    def count(self):
-        """Slots in use."""
-        return int(self._pending["count"]) if self._knn is None and self._pending is not None else self._count
+    def _create(self, engine, cfg, out):
+        return self.lib.htm_knn_create(engine.h, C.byref(cfg), C.byref(out))
 
     def info(self):
         """htm_knn_info of the bound object as a dict (the form of the distance launch among it)."""
@@ -145,169 +392,14 @@ class KNNClassifier(_DeviceKNN):
             raise RuntimeError("the KNN classifier is not bound to a device yet")
         return {name: int(getattr(out, name)) for name, _ in L.HtmKnnInfo._fields_[1:]}
 
-    # ---- what a call stores, decided here
-    def check_labels(self, labels):
-        """int [n] -> int32: any value outside [0, labels) is no label (-1)."""
-        g = np.asarray(labels)
-        if g.ndim != 1 or g.dtype.kind not in "iu":
-            raise ValueError(f"labels: int [n], got {g.dtype} {list(g.shape)}")
-        g = g.astype(np.int64)
-        return np.ascontiguousarray(np.where((g < 0) | (g >= self.labels), -1, g).astype(np.int32))
-
-    def stored_by(self, labels, first_step, n, learning):
-        """The patterns a call of n steps would store: step i reads labels[(first_step + i) % len(labels)]."""
-        if not learning or n <= 0:
-            return 0
-        rows = len(labels)
-        whole, rest = divmod(int(n), rows)
-        flags = np.asarray(labels) >= 0
-        at = (int(first_step) + np.arange(rest)) % rows
-        return int(whole * flags.sum() + flags[at].sum())
-
-    def check_room(self, stored):
-        """ValueError for a call that would take count past capacity: refused before anything is enqueued."""
-        if self.count + stored > self.capacity:
-            raise ValueError(f"knn: the call would store {stored} patterns in a store of {self.count} of capacity = {self.capacity} slots")
-
-    def upload_labels(self, engine, labels):
-        """int32 [n] (check_labels) -> the device address of the labels of a run's rows (the object's own array: htm_knn_labels)."""
-        self._bind(engine)
-        labels = np.ascontiguousarray(labels, dtype=np.int32)
-        out = C.c_void_p()
-        self._call(engine, "labels", labels.ctypes.data_as(C.c_void_p), labels.size, C.byref(out))
-        return out.value
-
-    # ---- the update over device memory (what run() calls; nothing here waits)
-    def pairs_buffer(self, engine, n):
-        """The device address of a buffer for n steps' patterns of max_pairs pairs (kept)."""
-        self._bind(engine)
-        return engine.kept_buffer(self._bufs, "pairs", 2 * max(int(n), 1) * self.shape[2], spare=2)
-
-    def enqueue(self, engine, device_pairs, pairs_per_step, n, device_labels, host_labels, first_step, learning, votes=False):
-        """The update over n steps' patterns in device memory, enqueued on `engine`'s stream: device_labels is upload_labels' address
-        of host_labels (int32 [rows]) -> nothing; read(engine, n, votes) after the stream's wait gives the results.  ValueError,
-        with nothing enqueued, for a call that does not fit the store."""
-        self._bind(engine)
-        n = int(n)
-        stored = self.stored_by(host_labels, first_step, n, learning)
-        self.check_room(stored)
-        best = engine.kept_buffer(self._bufs, "best", max(n, 1) * 5, spare=2)
-        all_votes = engine.kept_buffer(self._bufs, "votes", max(n, 1) * self.labels, spare=2) if votes else None
-        self._call(engine, "update", C.c_void_p(device_pairs), int(pairs_per_step), n, C.c_void_p(device_labels), len(host_labels), int(first_step),
-                   int(bool(learning)), C.c_void_p(best), C.c_void_p(all_votes) if all_votes else None)
-        self._count += stored
-        self._total += n
-
-    def read(self, engine, n, votes=False):
-        """(best int32 [n, 5], votes int32 [n, labels] or None) of the last enqueue, after the engine's stream has been waited for."""
-        n = int(n)
-        best = engine.read_words(self._bufs["best"][0], n * 5, np.int32).reshape(n, 5)
-        return best, (engine.read_words(self._bufs["votes"][0], n * self.labels, np.int32).reshape(n, self.labels) if votes else None)
-
-    # ---- the stand-alone door
     def update_patterns(self, index, words, labels, learning=True, votes=False, device=None):
-        """T further steps from their patterns: index int [T, n], words uint32 [T, n] (pair j of step t is (index[t, j], words[t, j]);
-        a negative index or a zero word contributes nothing), labels int [T] (outside [0, labels): none).  Checked here: the indices
-        of a step are distinct and inside the table, no word has a bit at or above cell_dim, n <= max_pairs, the labelled steps fit
-        the store.  -> (best int32 [T, 5]: label, votes, nearest_overlap, nearest_slot, nearest_step; votes int32 [T, labels] or
-        None)."""
-        if self.shape is None:
-            raise RuntimeError("the KNN classifier does not know the shape of its patterns yet: use it with a model, or give KNNClassifier(shape=)")
-        index, words = check_patterns(index, words, self.units, self.shape[1])
-        T, n = index.shape
-        if not 1 <= n <= self.shape[2]:
-            raise ValueError(f"patterns: 1 to max_pairs = {self.shape[2]} pairs per step, got {n}")
-        labels = self.check_labels(labels)
-        if labels.shape != (T,):
-            raise ValueError(f"labels: int [{T}], got {list(labels.shape)}")
-        self.check_room(self.stored_by(labels, 0, T, learning))
-        if T == 0:
-            return np.zeros((0, 5), np.int32), (np.zeros((0, self.labels), np.int32) if votes else None)
-        engine = self._engine(device)
-        pairs = np.empty((T, n, 2), dtype=np.int32)
-        pairs[..., 0], pairs[..., 1] = index, words.view(np.int32)
-        buf = engine.device_buffer(pairs.nbytes, pairs)
-        try:
-            self.enqueue(engine, buf, n, T, self.upload_labels(engine, labels), labels, 0, learning, votes)
-            engine.sync()
-            best, all_votes = self.read(engine, T, votes)
-            return best.copy(), (all_votes.copy() if votes else None)
-        finally:
-            engine.sync()
-            self.lib.hipFree(buf)
+        """T further steps from their patterns: index int [T, n], words uint32 [T, n], labels int [T] -> (best int32 [T, 5], votes int32
+        [T, labels] or None), as _DeviceKNN.update_patterns describes them."""
+        return super().update_patterns(index, words, labels, learning, votes, device)
 
-    # ---- reset, state
     def reset(self):
         """Empty the store (count = 0; the step total stays)."""
-        if self._knn is None:
-            if self._pending is not None:
-                self._pending = dict(self._empty_state(), total=self._pending["total"])
-            return
-        self._call(self._engine(), "reset")
-        self._count = 0
-
-    def _empty_state(self):
-        pairs = np.zeros((0, self.shape[2], 2), dtype=np.int32)
-        return dict(total=np.int64(0), count=np.int64(0), pairs=pairs, labels=np.zeros(0, np.int32), stamps=np.zeros(0, np.int64))
-
-    def _params(self):
-        return (self.labels, self.k, self.min_overlap, self.capacity) + (self.shape or ())
-
-    def state_dict(self):
-        """{"params": int64 [labels, k, min_overlap, capacity, column_dim, cell_dim, max_pairs], "total": int64, "count": int64,
-        "pairs": int32 [count, max_pairs, 2], "labels": int32 [count], "stamps": int64 [count]} -- the whole state, read from the
-        device."""
-        if self.shape is None:
-            raise RuntimeError("the KNN classifier does not know the shape of its patterns yet")
-        if self._knn is None:
-            state = self._pending if self._pending is not None else self._empty_state()
-        else:
-            engine = self._engine()
-            n, P = self._count, self.shape[2]
-            size = 16 + n * (8 * P + 12)
-            assert size == self.info()["state_bytes"]
-            blob = np.zeros(size, dtype=np.uint8)
-            self._call(engine, "export", blob.ctypes.data_as(C.c_void_p), size)
-            head = blob[:16].view(np.int64)
-            at = 16 + n * P * 8
-            state = dict(total=np.int64(head[0]), count=np.int64(head[1]), pairs=blob[16:at].view(np.int32).reshape(n, P, 2),
-                         stamps=blob[at:at + n * 8].view(np.int64), labels=blob[at + n * 8:].view(np.int32))
-        out = {k: np.array(v)[()] for k, v in state.items()}           # (copies; [()]: a scalar of a 0-d array)
-        return dict(out, params=np.asarray(self._params(), dtype=np.int64))
-
-    def load_state_dict(self, state):
-        """The state of a state_dict() of an object with the same parameters and shape."""
-        params = tuple(int(x) for x in state["params"])
-        if self.shape is None and len(params) == 7:
-            self._set_shape(*params[4:])
-        if params != self._params():
-            raise ValueError(f"the state was saved with parameters {params} (labels, k, min_overlap, capacity, column_dim, cell_dim, max_pairs), "
-                             f"this object has {self._params()}")
-        total, count = int(state["total"]), int(state["count"])
-        pairs = np.ascontiguousarray(state["pairs"], dtype=np.int32)
-        labels = np.ascontiguousarray(state["labels"], dtype=np.int32)
-        stamps = np.ascontiguousarray(state["stamps"], dtype=np.int64)
-        if not 0 <= count <= self.capacity or total < 0:
-            raise ValueError(f"state: 0 <= count <= capacity = {self.capacity} and total >= 0, got count {count}, total {total}")
-        for name, a, want in (("pairs", pairs, (count, self.shape[2], 2)), ("labels", labels, (count,)), ("stamps", stamps, (count,))):
-            if a.shape != want:
-                raise ValueError(f"state['{name}']: {list(want)}, got {list(a.shape)}")
-        if count and (labels.min() < 0 or labels.max() >= self.labels):
-            raise ValueError(f"state['labels']: a label outside [0, {self.labels})")
-        if count and (stamps[0] < 0 or stamps[-1] >= total or (np.diff(stamps) <= 0).any()):
-            raise ValueError("state['stamps']: the stamps ascend and lie below total")
-        clean = dict(total=np.int64(total), count=np.int64(count), pairs=pairs.copy(), labels=labels.copy(), stamps=stamps.copy())
-        if self._knn is None:
-            self._pending = clean
-        else:
-            self._import(self._engine(), clean)
-
-    def _import(self, engine, state):
-        n = int(state["count"])
-        blob = np.concatenate([np.array([state["total"], n], dtype=np.int64).view(np.uint8), state["pairs"].view(np.uint8).ravel(),
-                               state["stamps"].view(np.uint8).ravel(), state["labels"].view(np.uint8).ravel()])
-        self._call(engine, "import", blob.ctypes.data_as(C.c_void_p), blob.size)
-        self._count, self._total = n, int(state["total"])
+        self._reset(None)
 
 
 class KNNClassifierBank(_DeviceKNN):
@@ -324,17 +416,13 @@ class KNNClassifierBank(_DeviceKNN):
 
     _prefix = "htm_knns_"
     _what = "KNNClassifierBank"
-    source = None                               # shared(): the KNNClassifier whose store the streams read
 
     def __init__(self, streams, labels, k=1, min_overlap=1, capacity=4096, shape=None):
         self._init(labels, k, min_overlap, capacity, shape)
-        self._set_streams(streams)
-
-    def _set_streams(self, streams):
         self.streams = int(streams)
         if not 1 <= self.streams <= L.KNNS_MAX_STREAMS:
             raise ValueError(f"KNNClassifierBank: streams must be in [1, {L.KNNS_MAX_STREAMS}], got {streams}")
-        self._counts, self._total = np.zeros(self.streams, dtype=np.int64), 0
+        self._counts = np.zeros(self.streams, dtype=np.int64)
 
     @classmethod
     def shared(cls, knn, streams):
@@ -369,13 +457,6 @@ class KNNClassifierBank(_DeviceKNN):
         if learning and self.source is not None:
             raise ValueError("KNNClassifierBank.shared(): the streams read one store -- learning is refused (the owner stores through its own calls)")
 
-    @property
-    def count(self):
-        """Slots in use per stream, int64 [streams] (shared(): zeros -- the store is the owner's)."""
-        if self._knn is None and self._pending is not None:
-            return np.array(self._pending["count"], dtype=np.int64)
-        return self._counts.copy()
-
     def info(self):
         """htm_knns_info of the bound object as a dict (the chunk and the scratch and device bytes among it)."""
         out = L.HtmKnnsInfo(C.sizeof(L.HtmKnnsInfo))
@@ -383,112 +464,6 @@ class KNNClassifierBank(_DeviceKNN):
             raise RuntimeError("the KNN classifier bank is not bound to a device yet")
         return {name: int(getattr(out, name)) for name, _ in L.HtmKnnsInfo._fields_[1:] if name != "reserved"}
 
-    # ---- what a call stores, decided here
-    def check_labels(self, labels):
-        """int [streams, n] -> int32: any value outside [0, labels) is no label (-1)."""
-        g = np.asarray(labels)
-        if g.ndim != 2 or g.shape[0] != self.streams or g.dtype.kind not in "iu":
-            raise ValueError(f"labels: int [{self.streams}, n], got {g.dtype} {list(g.shape)}")
-        g = g.astype(np.int64)
-        return np.ascontiguousarray(np.where((g < 0) | (g >= self.labels), -1, g).astype(np.int32))
-
-    def stored_by(self, labels, first_step, n, learning):
-        """int64 [streams]: the patterns a call of n steps would store per stream; step i reads labels[s][(first_step + i) % rows]."""
-        if not learning or n <= 0:
-            return np.zeros(self.streams, dtype=np.int64)
-        rows = labels.shape[1]
-        whole, rest = divmod(int(n), rows)
-        flags = np.asarray(labels) >= 0
-        at = (int(first_step) + np.arange(rest)) % rows
-        return (whole * flags.sum(axis=1) + flags[:, at].sum(axis=1)).astype(np.int64)
-
-    def check_room(self, stored):
-        """ValueError for a call that would take ANY stream past capacity: refused as a whole before anything is enqueued."""
-        over = np.nonzero(self.count + stored > self.capacity)[0]
-        if over.size:
-            i = int(over[0])
-            raise ValueError(f"knn: stream {i}: the call would store {int(stored[i])} patterns in a store of {int(self.count[i])} of capacity = "
-                             f"{self.capacity} slots")
-
-    def upload_labels(self, engine, labels):
-        """int32 [streams, n] (check_labels) -> the device address of the labels (the object's own array: htm_knns_labels)."""
-        self._bind(engine)
-        labels = np.ascontiguousarray(labels, dtype=np.int32)
-        out = C.c_void_p()
-        self._call(engine, "labels", labels.ctypes.data_as(C.c_void_p), labels.shape[1], C.byref(out))
-        return out.value
-
-    # ---- the update over device memory (what ModelGroup.run() calls; nothing here waits)
-    def pairs_buffer(self, engine, n):
-        """The device address of a buffer [streams][n][max_pairs] pairs (kept)."""
-        self._bind(engine)
-        return engine.kept_buffer(self._bufs, "pairs", 2 * self.streams * max(int(n), 1) * self.shape[2], spare=2)
-
-    def enqueue(self, engine, device_pairs, pairs_per_step, n, device_labels, host_labels, first_step, learning, votes=False):
-        """ONE update of every stream over n steps' patterns in device memory (device_pairs: `streams` addresses), enqueued on
-        `engine`'s stream; device_labels is upload_labels' address of host_labels (int32 [streams, rows]; both None for a frozen
-        call).  read(engine, n, votes) after the stream's wait gives the results.  ValueError, with nothing enqueued, for a call in
-        which any stream does not fit its store."""
-        self._bind(engine)
-        n = int(n)
-        self._no_shared_learning(learning)
-        stored = self.stored_by(host_labels, first_step, n, learning) if host_labels is not None else np.zeros(self.streams, np.int64)
-        self.check_room(stored)
-        rows = host_labels.shape[1] if host_labels is not None else 1
-        best = engine.kept_buffer(self._bufs, "best", self.streams * max(n, 1) * 5, spare=2)
-        all_votes = engine.kept_buffer(self._bufs, "votes", self.streams * max(n, 1) * self.labels, spare=2) if votes else None
-        table = (C.c_void_p * self.streams)(*[int(x) for x in device_pairs])
-        self._call(engine, "update", table, int(pairs_per_step), n, C.c_void_p(device_labels) if device_labels else None, rows, int(first_step),
-                   int(bool(learning)), C.c_void_p(best), C.c_void_p(all_votes) if all_votes else None)
-        self._counts += stored
-        self._total += n
-
-    def read(self, engine, n, votes=False):
-        """(best int32 [streams, n, 5], votes int32 [streams, n, labels] or None) of the last enqueue, after the engine's stream has
-        been waited for."""
-        n, S = int(n), self.streams
-        best = engine.read_words(self._bufs["best"][0], S * n * 5, np.int32).reshape(S, n, 5)
-        return best, (engine.read_words(self._bufs["votes"][0], S * n * self.labels, np.int32).reshape(S, n, self.labels) if votes else None)
-
-    # ---- the stand-alone door
-    def update_patterns(self, index, words, labels=None, learning=True, votes=False, device=None):
-        """T further steps of every stream from their patterns: index int [S, T, n], words uint32 [S, T, n], labels int [S, T] (outside
-        [0, labels): none; None: nothing is labelled).  Checked as KNNClassifier.update_patterns checks them; a call in which any
-        stream's labelled steps do not fit its store is refused as a whole.  -> (best int32 [S, T, 5], votes int32 [S, T, labels] or
-        None)."""
-        if self.shape is None:
-            raise RuntimeError("the KNN classifier does not know the shape of its patterns yet: use it with a model, or give KNNClassifierBank(shape=)")
-        index, words = np.asarray(index), np.asarray(words)
-        S = self.streams
-        if index.ndim != 3 or index.shape[0] != S or words.shape != index.shape:
-            raise ValueError(f"patterns: index int [{S}, T, n] and words uint32 [{S}, T, n], got {index.shape} and {words.shape}")
-        _, T, n = index.shape
-        flat_i, flat_w = check_patterns(index.reshape(S * T, n), words.reshape(S * T, n), self.units, self.shape[1])
-        if not 1 <= n <= self.shape[2]:
-            raise ValueError(f"patterns: 1 to max_pairs = {self.shape[2]} pairs per step, got {n}")
-        labels = self.check_labels(np.full((S, max(T, 1)), -1) if labels is None else labels)
-        if T and labels.shape != (S, T):
-            raise ValueError(f"labels: int [{S}, {T}], got {list(labels.shape)}")
-        learning = bool(learning)
-        self._no_shared_learning(learning)
-        self.check_room(self.stored_by(labels, 0, T, learning))
-        if T == 0:
-            return np.zeros((S, 0, 5), np.int32), (np.zeros((S, 0, self.labels), np.int32) if votes else None)
-        engine = self._engine(device)
-        pairs = np.empty((S, T, n, 2), dtype=np.int32)
-        pairs[..., 0], pairs[..., 1] = flat_i.reshape(S, T, n), flat_w.view(np.int32).reshape(S, T, n)
-        buf = engine.device_buffer(pairs.nbytes, pairs)
-        try:
-            device_labels = self.upload_labels(engine, labels) if learning else None
-            self.enqueue(engine, [buf + i * T * n * 8 for i in range(S)], n, T, device_labels, labels if learning else None, 0, learning, votes)
-            engine.sync()
-            best, all_votes = self.read(engine, T, votes)
-            return best.copy(), (all_votes.copy() if votes else None)
-        finally:
-            engine.sync()
-            self.lib.hipFree(buf)
-
-    # ---- reset, state
     def reset(self, streams=None):
         """Empty every stream's store, or those `streams` (bool [streams]) names (the total stays)."""
         flags = None
@@ -496,49 +471,7 @@ class KNNClassifierBank(_DeviceKNN):
             flags = np.ascontiguousarray(np.asarray(streams, dtype=np.bool_).ravel()).astype(np.uint8)
             if flags.shape != (self.streams,):
                 raise ValueError(f"streams: bool [{self.streams}], got {list(flags.shape)}")
-        if self._knn is None:
-            if self._pending is not None:
-                keep = np.zeros(self.streams, bool) if flags is None else flags == 0
-                self._pending = self._select(self._pending, keep)
-            return
-        self._call(self._engine(), "reset", flags.ctypes.data_as(C.c_void_p) if flags is not None else None)
-        self._counts = np.where(flags == 0, self._counts, 0) if flags is not None else np.zeros(self.streams, dtype=np.int64)
-
-    def _select(self, state, keep):
-        """`state` with the stores of the streams not in `keep` (bool [streams]) emptied."""
-        counts = np.asarray(state["count"], dtype=np.int64)
-        rows = np.repeat(keep, counts)
-        return dict(total=state["total"], count=np.where(keep, counts, 0), pairs=state["pairs"][rows], labels=state["labels"][rows], stamps=state["stamps"][rows])
-
-    def _empty_state(self):
-        pairs = np.zeros((0, self.shape[2], 2), dtype=np.int32)
-        return dict(total=np.int64(0), count=np.zeros(self.streams, np.int64), pairs=pairs, labels=np.zeros(0, np.int32), stamps=np.zeros(0, np.int64))
-
-    def _params(self):
-        return (self.labels, self.k, self.min_overlap, self.capacity) + (self.shape or ())
-
-    def state_dict(self):
-        """{"params": int64 [labels, k, min_overlap, capacity, column_dim, cell_dim, max_pairs], "streams": int64, "total": int64,
-        "count": int64 [streams], "pairs": int32 [sum of count, max_pairs, 2], "labels": int32 [sum], "stamps": int64 [sum]} -- the
-        streams' stores one behind the other in stream order, read from the device (shared(): counts 0 -- the store is the owner's)."""
-        if self.shape is None:
-            raise RuntimeError("the KNN classifier does not know the shape of its patterns yet")
-        if self._knn is None:
-            state = self._pending if self._pending is not None else self._empty_state()
-        else:
-            engine = self._engine()
-            S, n, P = self.streams, int(self._counts.sum()), self.shape[2]
-            head = 8 * (1 + S)
-            size = head + n * (8 * P + 12)
-            assert size == self.info()["state_bytes"]
-            blob = np.zeros(size, dtype=np.uint8)
-            self._call(engine, "export", blob.ctypes.data_as(C.c_void_p), size)
-            words = blob[:head].view(np.int64)
-            at = head + n * P * 8
-            state = dict(total=np.int64(words[0]), count=words[1:].copy(), pairs=blob[head:at].view(np.int32).reshape(n, P, 2),
-                         stamps=blob[at:at + n * 8].view(np.int64), labels=blob[at + n * 8:].view(np.int32))
-        out = {k: np.array(v)[()] for k, v in state.items()}
-        return dict(out, params=np.asarray(self._params(), dtype=np.int64), streams=np.int64(self.streams))
+        self._reset(flags)
 
     def stream_state(self, i):
         """Stream i's state as a one-stream KNNClassifier of the same parameters loads it (load_state_dict)."""
@@ -550,44 +483,3 @@ class KNNClassifierBank(_DeviceKNN):
         hi = lo + int(state["count"][i])
         return dict(params=state["params"], total=state["total"], count=np.int64(hi - lo), pairs=state["pairs"][lo:hi].copy(),
                     labels=state["labels"][lo:hi].copy(), stamps=state["stamps"][lo:hi].copy())
-
-    def load_state_dict(self, state):
-        """The state of a state_dict() of a bank with the same parameters, shape and streams."""
-        params = tuple(int(x) for x in state["params"])
-        if self.shape is None and len(params) == 7:
-            self._set_shape(*params[4:])
-        if params != self._params() or int(state["streams"]) != self.streams:
-            raise ValueError(f"the state was saved with parameters {params} (labels, k, min_overlap, capacity, column_dim, cell_dim, max_pairs) and "
-                             f"{int(state['streams'])} streams, this object has {self._params()} and {self.streams}")
-        total = int(state["total"])
-        counts = np.ascontiguousarray(state["count"], dtype=np.int64)
-        pairs = np.ascontiguousarray(state["pairs"], dtype=np.int32)
-        labels = np.ascontiguousarray(state["labels"], dtype=np.int32)
-        stamps = np.ascontiguousarray(state["stamps"], dtype=np.int64)
-        top = 0 if self.source is not None else self.capacity
-        if counts.shape != (self.streams,) or (counts < 0).any() or (counts > top).any() or total < 0:
-            raise ValueError(f"state: count int64 [{self.streams}] with 0 <= count <= {top} and total >= 0, got count {counts.tolist()}, total {total}")
-        n = int(counts.sum())
-        for name, a, want in (("pairs", pairs, (n, self.shape[2], 2)), ("labels", labels, (n,)), ("stamps", stamps, (n,))):
-            if a.shape != want:
-                raise ValueError(f"state['{name}']: {list(want)}, got {list(a.shape)}")
-        if n and (labels.min() < 0 or labels.max() >= self.labels):
-            raise ValueError(f"state['labels']: a label outside [0, {self.labels})")
-        at = 0
-        for c in counts.tolist():
-            mine = stamps[at:at + c]
-            if c and (mine[0] < 0 or mine[-1] >= total or (np.diff(mine) <= 0).any()):
-                raise ValueError("state['stamps']: every stream's stamps ascend and lie below total")
-            at += c
-        clean = dict(total=np.int64(total), count=counts.copy(), pairs=pairs.copy(), labels=labels.copy(), stamps=stamps.copy())
-        if self._knn is None:
-            self._pending = clean
-        else:
-            self._import(self._engine(), clean)
-
-    def _import(self, engine, state):
-        head = np.concatenate([[int(state["total"])], np.asarray(state["count"], dtype=np.int64)]).astype(np.int64)
-        blob = np.concatenate([head.view(np.uint8), state["pairs"].view(np.uint8).ravel(), state["stamps"].view(np.uint8).ravel(),
-                               state["labels"].view(np.uint8).ravel()])
-        self._call(engine, "import", blob.ctypes.data_as(C.c_void_p), blob.size)
-        self._counts, self._total = np.asarray(state["count"], dtype=np.int64).copy(), int(state["total"])

@@ -271,6 +271,12 @@ def _shape(lines):
 
 
 @needs_hipcc
+def test_the_host_code_makes_every_launch_copy_wait_and_refusal_of_the_commit_before_the_fold(traces):
+    from test_knn_cpu import _same_as_recorded
+    _same_as_recorded("group", traces)              # ("tick_waits" among it: a tick's one wait)
+
+
+@needs_hipcc
 def test_the_earlier_calls_launch_what_they_launched_before_the_banks(traces):
     """tests/golden/group_knn_traces_before.json: the output of `group_knn_driver.py before` on the commit before the banks."""
     with open(os.path.join(ROOT, "tests", "golden", "group_knn_traces_before.json")) as f:

@@ -390,6 +390,25 @@ def traces(tmp_path_factory):
     return json.loads(r.stdout.splitlines()[-1])
 
 
+def _same_as_recorded(section, traces):
+    """The driver's whole output equals tests/golden/knn_host_traces_parent.json, recorded from the commit before the one-stream and
+    the bank host calls were folded into one (the same fixture, the same driver): every key, every line, the refusals' texts."""
+    with open(os.path.join(ROOT, "tests", "golden", "knn_host_traces_parent.json")) as f:
+        want = json.load(f)[section]
+    assert sorted(traces) == sorted(want)
+    for key in want:
+        if isinstance(want[key], dict):
+            assert sorted(traces[key]) == sorted(want[key]), key
+            for name in want[key]:
+                assert traces[key][name] == want[key][name], (key, name)
+        assert traces[key] == want[key], key
+
+
+@needs_hipcc
+def test_the_host_code_makes_every_launch_copy_and_refusal_of_the_commit_before_the_fold(traces):
+    _same_as_recorded("knn", traces)
+
+
 @needs_hipcc
 def test_an_update_is_two_launches_per_chunk_and_two_more_for_a_call_that_stores(traces):
     lds = QUERIES * 256 * 4                          # (eight staged tables of 256 words)
