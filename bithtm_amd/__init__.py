@@ -11,7 +11,7 @@ from . import classifier, encoders, likelihood, networks
 from .anomaly import AnomalyLikelihood  # noqa: F401
 from .sdr_classifier import SDRClassifier, SDRClassifierBank  # noqa: F401
 from .knn_classifier import KNNClassifier, KNNClassifierBank  # noqa: F401
-from .encoders import CategoryField, HashedField, ScalarEncoder, ScalarField, date_fields, date_values  # noqa: F401
+from .encoders import CategoryField, CoordinateField, HashedField, ScalarEncoder, ScalarField, date_fields, date_values, geo_values  # noqa: F401
 from .networks import InferenceView, flip_noise, noise_threshold  # noqa: F401
 from .engine import CapacityError, HtmError  # noqa: F401
 from .group import GroupTick, ModelGroup  # noqa: F401

@@ -9,6 +9,7 @@ import numpy as np
 STREAM_LEAST_USED, STREAM_GROWTH, STREAM_SEGMENT_JITTER = 1, 2, 3
 STREAM_INPUT_NOISE = 6                              # (4 and 5: the pre-populated pools of htm_populate, device only)
 STREAM_FIELD_HASH = 7                               # the bit positions of a hashed encoder field (encoders.HashedField): a = index, step 0
+STREAM_COORDINATE = 8                               # the cells of a coordinate field (encoders.CoordinateField): a = x, b = y; step 0 order, step 1 bit
 
 _M1, _M2 = np.uint32(0x7FEB352D), np.uint32(0x846CA68B)
 

@@ -53,6 +53,7 @@
 #include "htm_scalar.h"
 #include "htm_live.h"
 #include "htm_fields.h"
+#include "htm_coord.h"
 #include "htm_likelihood.h"
 #include "htm_classifier.h"
 #include "htm_knn.h"
@@ -3518,16 +3519,37 @@ static int scalar_table(htm_handle *h, const char *what, const htm_scalar_field 
         const htm_scalar_field &f = fields[j];
         const std::string fj = who + ": field " + std::to_string(j);
         // the kind (htm_fields.h): reserved == 0 is a linear field, as every call before the kinds existed passed it
-        if (f.reserved < 0 || (f.reserved & 3) == 3) { h->err = fj + ": reserved must be 0, or a field kind (1 category, 2 hashed) with a hashed field's seed above it"; return HTM_ERR_ARGUMENT; }
+        if (f.reserved < 0) { h->err = fj + ": reserved must be 0, or a field kind (1 category, 2 hashed, 3 coordinate) with a hashed or coordinate field's seed above it"; return HTM_ERR_ARGUMENT; }
         const int kind = f.reserved & 3;
-        if (kind != HTM_FIELD_HASHED && (f.reserved >> 2) != 0) { h->err = fj + ": a seed on a field that is not hashed"; return HTM_ERR_ARGUMENT; }
         if (kind != HTM_FIELD_LINEAR && f.periodic != 0) { h->err = fj + ": only a linear field can be periodic"; return HTM_ERR_ARGUMENT; }
+        if (kind == HTM_FIELD_COORDINATE && f.bits == 0) {
+            // a continuation of a coordinate group (htm_coord.h): the y or the radius column, right behind its head; it holds no bits
+            const int head = j >= 1 && coord_head(fields[j - 1]) ? j - 1 : j >= 2 && coord_head(fields[j - 2]) && coord_tail(fields[j - 1]) ? j - 2 : -1;
+            if (head < 0) { h->err = fj + ": a coordinate continuation (kind 3, bits 0) that is not the first or second entry behind a head"; return HTM_ERR_ARGUMENT; }
+            if (f.reserved != HTM_FIELD_COORDINATE || f.width != 0 || f.buckets != 0 || f.offset != fields[head].offset) {
+                h->err = fj + ": a coordinate continuation takes reserved 3, width 0, buckets 0 and its head's offset";
+                return HTM_ERR_ARGUMENT;
+            }
+            if (!std::isfinite(f.minimum) || !std::isfinite(f.scale) || !(f.scale > 0.0)) { h->err = fj + ": minimum and scale must be finite, scale above 0"; return HTM_ERR_ARGUMENT; }
+            tab->f[j] = f;
+            continue;
+        }
+        if (kind != HTM_FIELD_HASHED && kind != HTM_FIELD_COORDINATE && (f.reserved >> 2) != 0) { h->err = fj + ": a seed on a field that is neither hashed nor a coordinate head"; return HTM_ERR_ARGUMENT; }
         if (f.bits < 1 || f.width < 1) { h->err = fj + ": bits >= 1 and width >= 1"; return HTM_ERR_ARGUMENT; }
         if (kind == HTM_FIELD_LINEAR) {
             if (f.width > f.bits) { h->err = fj + ": bits >= 1 and 1 <= width <= bits"; return HTM_ERR_ARGUMENT; }
             if (f.buckets != (f.periodic ? f.bits : f.bits - f.width + 1)) { h->err = fj + ": buckets must be bits (periodic) or bits - width + 1"; return HTM_ERR_ARGUMENT; }
         } else if (kind == HTM_FIELD_CATEGORY) {
             if (f.buckets < 1 || (long long)f.buckets * f.width > (long long)f.bits) { h->err = fj + ": a category field needs buckets >= 1 and buckets * width <= bits"; return HTM_ERR_ARGUMENT; }
+        } else if (kind == HTM_FIELD_COORDINATE) {
+            if (f.width > HTM_HASHED_MAX_WIDTH || f.buckets < 0 || f.buckets > HTM_COORD_MAX_RADIUS) {
+                h->err = fj + ": a coordinate field needs width <= " + std::to_string(HTM_HASHED_MAX_WIDTH) + " and max_radius (buckets) in [0, " + std::to_string(HTM_COORD_MAX_RADIUS) + "]";
+                return HTM_ERR_ARGUMENT;
+            }
+            if (j + 2 >= n_fields || !coord_tail(fields[j + 1]) || !coord_tail(fields[j + 2])) {
+                h->err = fj + ": a coordinate head (kind 3, bits >= 1) must be followed by its two continuations (kind 3, bits 0): the y and the radius column";
+                return HTM_ERR_ARGUMENT;
+            }
         } else {
             if (f.buckets < 1 || f.width > HTM_HASHED_MAX_WIDTH || f.buckets > INT32_MAX - HTM_HASHED_MAX_WIDTH) {
                 h->err = fj + ": a hashed field needs buckets >= 1 (below 2^31 - " + std::to_string(HTM_HASHED_MAX_WIDTH) + ") and width <= " + std::to_string(HTM_HASHED_MAX_WIDTH);
@@ -3540,14 +3562,26 @@ static int scalar_table(htm_handle *h, const char *what, const htm_scalar_field 
         }
         if (f.offset < 0 || (long long)f.offset + f.bits > (long long)h->d.I) { h->err = fj + ": reaches outside the input row"; return HTM_ERR_ARGUMENT; }
         if (!std::isfinite(f.minimum) || !std::isfinite(f.scale) || !(f.scale > 0.0)) { h->err = fj + ": minimum and scale must be finite, scale above 0"; return HTM_ERR_ARGUMENT; }
-        if (decoding && kind != HTM_FIELD_HASHED && f.bits > HTM_DECODE_MAX_BITS) { h->err = fj + ": more than " + std::to_string(HTM_DECODE_MAX_BITS) + " bits (the decode launch's LDS)"; return HTM_ERR_ARGUMENT; }
-        for (int i = 0; i < j; ++i)
-            if (f.offset < fields[i].offset + fields[i].bits && fields[i].offset < f.offset + f.bits) { h->err = fj + ": overlaps field " + std::to_string(i); return HTM_ERR_ARGUMENT; }
+        if (decoding && kind != HTM_FIELD_HASHED && kind != HTM_FIELD_COORDINATE && f.bits > HTM_DECODE_MAX_BITS) { h->err = fj + ": more than " + std::to_string(HTM_DECODE_MAX_BITS) + " bits (the decode launch's LDS)"; return HTM_ERR_ARGUMENT; }
+        for (int i = 0; i < j; ++i)                 // (a continuation has no bits: it overlaps nothing)
+            if (fields[i].bits > 0 && f.offset < fields[i].offset + fields[i].bits && fields[i].offset < f.offset + f.bits) { h->err = fj + ": overlaps field " + std::to_string(i); return HTM_ERR_ARGUMENT; }
         tab->f[j] = f;
         tab->f[j].periodic = f.periodic != 0;       // (reserved stays: the kind and the seed, 0 for a linear field)
     }
     return 0;
 }
+
+// The kernels of a checked table: those of htm_coord.h where it holds a coordinate field, else the twins of htm_fields.h where it
+// holds a category or hashed field, else the linear kernels of htm_scalar.h and htm_live.h.  kcoord_bank's block is SCALAR_THREADS
+// threads whatever the row's width (its select wants them); the others' follow the row
+enum FieldPath { FIELDS_LINEAR, FIELDS_MIXED, FIELDS_COORDINATE };
+static FieldPath field_path(const ScalarTab &tab, int n_fields) {
+    return fields_coordinate(tab.f, n_fields) ? FIELDS_COORDINATE : fields_mixed(tab.f, n_fields) ? FIELDS_MIXED : FIELDS_LINEAR;
+}
+static decltype(&k_bank_encode) encode_kernel(FieldPath p) { return p == FIELDS_COORDINATE ? kcoord_bank : p == FIELDS_MIXED ? kenc_bank : k_bank_encode; }
+static int encode_threads(FieldPath p, int W) { return p == FIELDS_COORDINATE ? SCALAR_THREADS : scalar_encode_threads(W); }
+static decltype(&k_decode_votes) votes_kernel(FieldPath p) { return p == FIELDS_COORDINATE ? kcoord_votes : p == FIELDS_MIXED ? kenc_votes : k_decode_votes; }
+static decltype(&klive_finish) finish_kernel(FieldPath p) { return p == FIELDS_COORDINATE ? kcoord_finish : p == FIELDS_MIXED ? kenc_finish : klive_finish; }
 
 // Bank rows from values: one launch behind whatever the stream holds, no copy, no wait, no state of the handle read (as
 // htm_bank_noise: also on a view, also while the handle is ahead)
@@ -3565,10 +3599,8 @@ extern "C" int htm_bank_encode(htm_handle *h, const htm_scalar_field *fields, in
     if (((uintptr_t)device_bank & 15) != 0 || ((uintptr_t)device_values & 7) != 0) { h->err = "htm_bank_encode: the bank must be 16-byte aligned, the values 8-byte"; return HTM_ERR_ARGUMENT; }
     if (n_rows == 0) return HTM_OK;
     HIPCHK(h, hipSetDevice(h->device));
-    if (fields_mixed(tab.f, n_fields))
-        LAUNCH(h, "bank_encode", kenc_bank, n_rows, scalar_encode_threads(h->d.W), h->d, tab, (int)n_fields, device_values, device_bank, (int)first_row);
-    else
-        LAUNCH(h, "bank_encode", k_bank_encode, n_rows, scalar_encode_threads(h->d.W), h->d, tab, (int)n_fields, device_values, device_bank, (int)first_row);
+    const FieldPath path = field_path(tab, n_fields);
+    LAUNCH(h, "bank_encode", encode_kernel(path), n_rows, encode_threads(path, h->d.W), h->d, tab, (int)n_fields, device_values, device_bank, (int)first_row);
     return launch_status(h->err);
 }
 
@@ -3583,10 +3615,7 @@ extern "C" int htm_decode_votes(htm_handle *h, const htm_scalar_field *fields, i
     if (n_rows < 0) { h->err = "htm_decode_votes: n_rows must not be negative"; return HTM_ERR_ARGUMENT; }
     if (n_rows == 0) return HTM_OK;
     HIPCHK(h, hipSetDevice(h->device));
-    if (fields_mixed(tab.f, n_fields))
-        LAUNCH(h, "decode_votes", kenc_votes, dim3(n_rows, n_fields), SCALAR_THREADS, tab, (int)n_fields, h->d.I, device_votes, device_out);
-    else
-        LAUNCH(h, "decode_votes", k_decode_votes, dim3(n_rows, n_fields), SCALAR_THREADS, tab, (int)n_fields, h->d.I, device_votes, device_out);
+    LAUNCH(h, "decode_votes", votes_kernel(field_path(tab, n_fields)), dim3(n_rows, n_fields), SCALAR_THREADS, tab, (int)n_fields, h->d.I, device_votes, device_out);
     return launch_status(h->err);
 }
 
@@ -3611,10 +3640,7 @@ extern "C" int htm_predicted_value(htm_handle *h, const htm_scalar_field *fields
     if (!h->d_value_out) { rc = dalloc(h, &h->d_value_out, 2 * HTM_SCALAR_MAX_FIELDS); if (rc) return rc; }
     HIPCHK(h, hipMemsetAsync(h->d_pin_buf, 0, (size_t)d.I * 4, h->stream));
     LAUNCH(h, "predicted_input", k_pin, pin_blocks(d.C), 256, d, (int)((h->step_host + 1) & 1), h->d_pin_buf);
-    if (fields_mixed(tab.f, n_fields))
-        LAUNCH(h, "decode_votes", kenc_votes, dim3(1, n_fields), SCALAR_THREADS, tab, (int)n_fields, d.I, (const int32_t *)h->d_pin_buf, h->d_value_out);
-    else
-        LAUNCH(h, "decode_votes", k_decode_votes, dim3(1, n_fields), SCALAR_THREADS, tab, (int)n_fields, d.I, (const int32_t *)h->d_pin_buf, h->d_value_out);
+    LAUNCH(h, "decode_votes", votes_kernel(field_path(tab, n_fields)), dim3(1, n_fields), SCALAR_THREADS, tab, (int)n_fields, d.I, (const int32_t *)h->d_pin_buf, h->d_value_out);
     rc = launch_status(h->err);
     if (rc) return rc;
     HIPCHK(h, hipMemcpyAsync(host_out, h->d_value_out, (size_t)n_fields * 8, hipMemcpyDeviceToHost, h->stream));
@@ -5359,12 +5385,9 @@ static int live_tick(htm_group *g, const double *values, const htm_scalar_field 
     if (resetting) LAUNCH_ON(h0, s, 0, "live:reset", klive_reset, dim3(reset_blocks(d), B), 256, g->d_tab, (const int32_t *)(lv.d_stage + lv.off_flags));
     LAUNCH_ON(h0, s, 0, "group:record", kgrp_rec_clear, B, 64, g->d_recs);
     LAUNCH_ON(h0, s, 0, "group:record", kgrp_rec_begin, dim3(rec_blocks(d), B), 256, g->d_tab, p ^ 1, g->d_recs, (const GrpRecArgs *)lv.rec_args, 1);
-    const bool mixed = values && fields_mixed(ftab.f, n_fields);      // (a table with a category or hashed field: the twins of htm_fields.h)
-    if (values && mixed)
-        LAUNCH_ON(h0, s, 0, "live:encode", kenc_bank, B, scalar_encode_threads(d.W), d, ftab, (int)n_fields, (const double *)(lv.d_stage + lv.off_values),
-                  (uint32_t *)lv.d_stage, 0);
-    else if (values)
-        LAUNCH_ON(h0, s, 0, "live:encode", k_bank_encode, B, scalar_encode_threads(d.W), d, ftab, (int)n_fields, (const double *)(lv.d_stage + lv.off_values),
+    const FieldPath path = values ? field_path(ftab, n_fields) : FIELDS_LINEAR;       // (the table's kernels: htm_scalar.h, htm_fields.h or htm_coord.h)
+    if (values)
+        LAUNCH_ON(h0, s, 0, "live:encode", encode_kernel(path), B, encode_threads(path, d.W), d, ftab, (int)n_fields, (const double *)(lv.d_stage + lv.off_values),
                   (uint32_t *)lv.d_stage, 0);
     const bool decoding = decoded || votes;
     if (decoding) LAUNCH_ON(h0, s, 0, "group:predicted_input", kgrp_pin_begin, dim3(pin_begin_blocks(1, d.I), B), 256, g->d_tab, p ^ 1, g->d_pins, lv.vote_tab, 1);
@@ -5382,14 +5405,9 @@ static int live_tick(htm_group *g, const double *values, const htm_scalar_field 
     } else {
         group_enqueue_step(g, modes, lv.bank_tab, 1, learning, p, f, lv.d_caps);
     }
-    if (mixed)
-        LAUNCH_ON(h0, s, 0, "live:finish", kenc_finish, dim3(std::max(n_dec, 1), B), SCALAR_THREADS, g->d_tab, p, ftab, n_dec,
-                  (const int32_t *)(lv.d_out + lv.off_votes), (const htm_step_record *)lv.d_recs, (htm_live_row *)(lv.d_out + lv.off_rows),
-                  (int32_t *)(lv.d_out + lv.off_pairs));
-    else
-        LAUNCH_ON(h0, s, 0, "live:finish", klive_finish, dim3(std::max(n_dec, 1), B), SCALAR_THREADS, g->d_tab, p, ftab, n_dec,
-                  (const int32_t *)(lv.d_out + lv.off_votes), (const htm_step_record *)lv.d_recs, (htm_live_row *)(lv.d_out + lv.off_rows),
-                  (int32_t *)(lv.d_out + lv.off_pairs));
+    LAUNCH_ON(h0, s, 0, "live:finish", finish_kernel(path), dim3(std::max(n_dec, 1), B), SCALAR_THREADS, g->d_tab, p, ftab, n_dec,
+              (const int32_t *)(lv.d_out + lv.off_votes), (const htm_step_record *)lv.d_recs, (htm_live_row *)(lv.d_out + lv.off_rows),
+              (int32_t *)(lv.d_out + lv.off_pairs));
     // a scored tick: every member's stream of the likelihood object takes the step's record, behind the finish launch
     if (lk) LAUNCH_ON(h0, s, 0, "live:likelihood", klik_tick, dim3(1, B), HTM_LIKELIHOOD_THREADS, lk->d, (const htm_step_record *)lv.d_recs, (double *)(lv.d_out + lv.off_lik));
     // a classified tick: every member's stream of the bank takes the step's captured pattern -- sum + apply when it learns, else the

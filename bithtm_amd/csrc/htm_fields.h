@@ -19,6 +19,8 @@
 //   kenc_votes   k_decode_votes' contract, over role_field_votes: role_decode_votes with the scanned element votes[offset +
 //                pos(i)] for a hashed field (pos hashed on the fly) and the window P[(c + 1) * width] - P[c * width] for a category.
 //   kenc_finish  klive_finish's body over that role.
+// (A table with a coordinate field -- kind HTM_FIELD_COORDINATE, a group of three entries -- launches the kernels of htm_coord.h
+// instead, which are these with the coordinate kind added; field_elements and field_bucket below are never asked about that kind.)
 // The arithmetic (field_kind, field_pos, field_bucket) is __host__ __device__ and this file can be included without hipcc -- after
 // htm_rng.h, with __host__, __device__ and __forceinline__ defined away: tests/host_stub/field_kinds_host.cpp evaluates it on the
 // host against the Python definition.  Part of the single translation unit htm_engine.hip (included after htm_live.h).

@@ -9,6 +9,7 @@
 //   stream 3  matching-segment jitter  a = segment id                (projections.py:235)
 //   stream 6  input flip noise         a = input index, step = the timestep the row is read in   (example.py:52)
 //   stream 7  hashed field positions   a = position index, step 0, seed = the field's own (draw32; the oracle does not encode)
+//   stream 8  coordinate field cells    a = x, b = y, seed = the field's own; step 0 = a cell's order (draw24), step 1 = its bit (draw32)
 #pragma once
 #include <stdint.h>
 
@@ -19,6 +20,7 @@
 #define HTM_STREAM_POPULATE_PERM 5u
 #define HTM_STREAM_INPUT_NOISE 6u        // device-side input noise (htm_bank_noise, htm_noise.h)
 #define HTM_STREAM_FIELD_HASH 7u         // bit positions of a hashed encoder field (htm_fields.h): a = position index, step 0
+#define HTM_STREAM_COORDINATE 8u         // the cells of a coordinate encoder field (htm_coord.h): a = x, b = y, step 0 order, step 1 bit
 
 __host__ __device__ __forceinline__ uint32_t htm_mix32(uint32_t x) {   // "lowbias32"
     x ^= x >> 16;

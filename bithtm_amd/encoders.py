@@ -24,18 +24,32 @@ Two further field kinds stand beside that linear one in the same row (bithtm_amd
                        score[b] = G[b] + ... + G[b + width - 1] (a collided bit counted once per j)
     Both decode to the lowest bucket with the largest score, (-1, 0) where that score is 0.
 
-date_fields / date_values put a timestamp into such fields on the host (time of day, day of week, a weekend flag).
+A coordinate field (bithtm_amd/csrc/htm_coord.h) reads THREE value columns -- x, y and a radius in cells:
+
+    CoordinateField:   cell of an axis: t = (v - origin) * scale, scale = 1 / resolution; missing unless -2**30 <= t < 2**30 (NaN
+                       and +-inf fail the comparison); else c = int32(floor(t))
+                       radius: t = (v - 0.0) * 1.0; missing if NaN or t < 0; else r = int(min(floor(t), float(max_radius)))
+                       candidates: the N = (2r + 1)**2 cells cx - r <= x <= cx + r, cy - r <= y <= cy + r, index
+                       i = (y - (cy - r)) * (2r + 1) + (x - (cx - r));  order(x, y) = htm_draw24(htm_stream_base(seed, 8, 0), x, y),
+                       bit(x, y) = (htm_draw32(htm_stream_base(seed, 8, 1), x, y) * bits) >> 32
+                       the row gets offset + bit(p) of the min(width, N) candidates p of the largest order, ties at the cut to the
+                       lower index; a row in which any of the three is missing gets no bit.  There is no decode: (-1, 0), NaN.
+
+date_fields / date_values put a timestamp into such fields on the host (time of day, day of week, a weekend flag); geo_values
+puts longitude, latitude and speed into the three columns of a coordinate field.
 """
 
 import numpy as np
 
 from . import _lib as L
-from ._keyed import STREAM_FIELD_HASH, draw32
+from ._keyed import STREAM_COORDINATE, STREAM_FIELD_HASH, draw32
 
 MAX_FIELDS = 16                                     # HTM_SCALAR_MAX_FIELDS
 DECODE_MAX_BITS = 8192                              # HTM_DECODE_MAX_BITS: bits per field htm_decode_votes takes
 HASHED_MAX_WIDTH = 256                              # HTM_HASHED_MAX_WIDTH: the positions of a hashed window live in the encode block's LDS
 FIELD_LINEAR, FIELD_CATEGORY, FIELD_HASHED = 0, 1, 2        # htm_scalar_field.reserved & 3 (HTM_FIELD_CATEGORY, HTM_FIELD_HASHED)
+FIELD_COORDINATE = 3                                # HTM_FIELD_COORDINATE: a group of three table entries, one per value column
+COORD_MAX_RADIUS = 127                              # HTM_COORD_MAX_RADIUS: (2 * 127 + 1)**2 = 65 025 candidates at the most
 
 
 class ScalarField:
@@ -194,16 +208,126 @@ class HashedField(ScalarField):
         return ScalarField.key(self) + (self.kind, self.buckets, self.seed)
 
 
+class CoordinateAxis(ScalarField):
+    """The y column or the radius column of a CoordinateField: a table entry of its own (the C ABI counts value columns) that holds
+    no bits -- bits, width and buckets 0, at its field's offset.  Made by the field; `field` is the CoordinateField it belongs to."""
+
+    kind, kind_code = "coordinate-axis", FIELD_COORDINATE
+
+    def __init__(self, field, minimum, scale):
+        self.field, self.minimum, self.maximum, self.scale = field, float(minimum), float("nan"), float(scale)
+        self.bits = self.width = self.buckets = 0
+        self.periodic = False
+
+    def value_of(self, bucket):
+        return np.full(np.shape(bucket), np.nan)
+
+    def key(self):
+        return ScalarField.key(self) + (self.kind, 0, 0)
+
+
+class CoordinateField(ScalarField):
+    """A 2-D position and a radius over `bits` input bits, NuPIC's CoordinateEncoder: of the (2r + 1)**2 integer cells of the square
+    of radius r round the position's cell, the `width` that a keyed hash (stream 8 of htm_rng.h under `seed`) ranks highest each set
+    one bit.  Nearby positions share most of their bits; positions more than 2r apart share next to none.  The field reads three
+    value columns -- x, y and the radius in cells (clamped to `max_radius`) -- and stands in a ScalarEncoder as three entries: itself
+    at x, and `axes` (two CoordinateAxis objects) behind it.  A cell is `resolution` wide (a scalar, or an (x, y) pair) and cell 0
+    begins at `origin`.  There is no decode: the three columns decode to (-1, 0) and their value is NaN."""
+
+    kind, kind_code = "coordinate", FIELD_COORDINATE
+
+    def __init__(self, bits, width, max_radius, resolution=1.0, origin=(0.0, 0.0), seed=0):
+        bits, width, max_radius, seed = int(bits), int(width), int(max_radius), int(seed)
+        if bits < 1 or not 1 <= width <= HASHED_MAX_WIDTH:
+            raise ValueError(f"CoordinateField: bits >= 1 and 1 <= width <= {HASHED_MAX_WIDTH}, got bits {bits}, width {width}")
+        if not 0 <= max_radius <= COORD_MAX_RADIUS:
+            raise ValueError(f"CoordinateField: 0 <= max_radius <= {COORD_MAX_RADIUS}, got {max_radius}")
+        if not 0 <= seed < 1 << 29:
+            raise ValueError(f"CoordinateField: 0 <= seed < 2**29, got {seed}")
+        res = np.broadcast_to(np.asarray(resolution, dtype=np.float64), (2,)) if np.ndim(resolution) <= 1 and np.size(resolution) in (1, 2) else None
+        org = np.asarray(origin, dtype=np.float64)
+        if res is None or not (np.isfinite(res).all() and (res > 0.0).all()):
+            raise ValueError(f"CoordinateField: resolution must be a positive finite number or an (x, y) pair of them, got {resolution}")
+        if org.shape != (2,) or not np.isfinite(org).all():
+            raise ValueError(f"CoordinateField: origin must be a finite (x, y) pair, got {origin}")
+        scales = [1.0 / float(r) for r in res]
+        if not all(np.isfinite(x) and x > 0.0 for x in scales):
+            raise ValueError(f"CoordinateField: 1 / resolution is not a positive finite double ({scales})")
+        self.minimum, self.maximum, self.scale = float(org[0]), float("nan"), scales[0]
+        self.bits, self.width, self.periodic, self.seed = bits, width, False, seed
+        self.max_radius = self.buckets = max_radius         # (the table's `buckets` member carries max_radius)
+        self.axes = (CoordinateAxis(self, float(org[1]), scales[1]), CoordinateAxis(self, 0.0, 1.0))
+
+    def cells(self, values):
+        """float64 [..., 3] (x, y, radius) -> (cx int64 [...], cy int64 [...], r int64 [...], ok bool [...]): the centre's cell, the
+        clamped radius, and whether the row has all three (where it has not, the other three are 0)."""
+        v = np.asarray(values, dtype=np.float64)
+        ok, out = np.ones(v.shape[:-1], dtype=np.bool_), []
+        with np.errstate(invalid="ignore", over="ignore"):
+            for j, axis in enumerate((self, self.axes[0])):
+                t = (v[..., j] - axis.minimum) * axis.scale
+                good = (t >= -1073741824.0) & (t < 1073741824.0)
+                out.append(np.floor(np.where(good, t, 0.0)).astype(np.int64))
+                ok &= good
+            t = (v[..., 2] - self.axes[1].minimum) * self.axes[1].scale
+            good = ~np.isnan(t) & ~(t < 0.0)
+            out.append(np.minimum(np.floor(np.where(good, t, 0.0)), float(self.max_radius)).astype(np.int64))
+            ok &= good
+        return tuple(np.where(ok, a, 0) for a in out) + (ok,)
+
+    def order(self, x, y):
+        """int [...] cells -> int64 [...]: order(x, y) of the definition, in [0, 2**24)."""
+        return (draw32(self.seed, STREAM_COORDINATE, 0, np.asarray(x, np.int64), np.asarray(y, np.int64)) >> np.uint32(8)).astype(np.int64)
+
+    def bit(self, x, y):
+        """int [...] cells -> int64 [...]: bit(x, y) of the definition, in [0, bits)."""
+        h = draw32(self.seed, STREAM_COORDINATE, 1, np.asarray(x, np.int64), np.asarray(y, np.int64))
+        return ((h.astype(np.uint64) * np.uint64(self.bits)) >> np.uint64(32)).astype(np.int64)
+
+    def candidates(self, cx, cy, r):
+        """One row's candidates in index order: (x int64 [N], y int64 [N]), N = (2r + 1)**2, y-major."""
+        side = 2 * int(r) + 1
+        i = np.arange(side * side, dtype=np.int64)
+        return int(cx) - int(r) + i % side, int(cy) - int(r) + i // side
+
+    def selected(self, cx, cy, r):
+        """One row's winners: int64 [min(width, N)] candidate indices, by falling order, equal orders by rising index."""
+        x, y = self.candidates(cx, cy, r)
+        if x.size <= self.width:
+            return np.arange(x.size, dtype=np.int64)
+        return np.argsort(-self.order(x, y), kind="stable")[:self.width]
+
+    def positions(self, cx, cy, r):
+        """One row's bits, counted from the field's offset: int64 [min(width, N)], possibly with repeats."""
+        x, y = self.candidates(cx, cy, r)
+        pick = self.selected(cx, cy, r)
+        return self.bit(x[pick], y[pick])
+
+    def value_of(self, bucket):
+        return np.full(np.shape(bucket), np.nan)
+
+    def key(self):
+        return ScalarField.key(self) + (self.kind, self.max_radius, self.seed)
+
+
 class ScalarEncoder:
-    """1 to 16 ScalarFields side by side: field j occupies the input bits [offset_j, offset_j + bits_j), offset_j the sum of the
-    earlier fields' bits.  `input_dim` defaults to the sum of the bits; a larger one leaves the trailing bits 0."""
+    """1 to 16 value columns side by side: a ScalarField is one column and occupies the input bits [offset_j, offset_j + bits_j),
+    offset_j the sum of the earlier fields' bits; a CoordinateField is three columns (x, y, radius) -- `fields` holds the field at x
+    and its two axis objects, of 0 bits at the field's offset, behind it.  `input_dim` defaults to the sum of the bits; a larger
+    one leaves the trailing bits 0."""
 
     def __init__(self, fields, input_dim=None):
-        self.fields = tuple(fields)
-        if not 1 <= len(self.fields) <= MAX_FIELDS or not all(isinstance(f, ScalarField) for f in self.fields):
-            raise ValueError(f"ScalarEncoder: 1 to {MAX_FIELDS} ScalarFields, got {len(self.fields)}")
-        self.offsets = tuple(int(x) for x in np.cumsum([0] + [f.bits for f in self.fields[:-1]]))
-        total = self.offsets[-1] + self.fields[-1].bits
+        fields = tuple(fields)
+        if not all(isinstance(f, ScalarField) and not isinstance(f, CoordinateAxis) for f in fields):
+            raise ValueError("ScalarEncoder: every field must be a ScalarField (a CoordinateField brings its axes itself)")
+        self.fields = tuple(c for f in fields for c in ((f,) + f.axes if f.kind_code == FIELD_COORDINATE else (f,)))
+        if not 1 <= len(self.fields) <= MAX_FIELDS:
+            raise ValueError(f"ScalarEncoder: 1 to {MAX_FIELDS} value columns (a CoordinateField is three), got {len(self.fields)}")
+        offsets, total = [], 0
+        for f in self.fields:
+            offsets.append(offsets[-1] if isinstance(f, CoordinateAxis) else total)
+            total += f.bits
+        self.offsets = tuple(offsets)
         self.input_dim = total if input_dim is None else int(input_dim)
         if self.input_dim < total:
             raise ValueError(f"ScalarEncoder: the fields take {total} bits, input_dim is {self.input_dim}")
@@ -220,15 +344,28 @@ class ScalarEncoder:
     def bucket(self, values):
         """float64 [..., F] -> int32 [..., F]."""
         v = self._values(values)
-        return np.stack([f.bucket(v[..., j]) for j, f in enumerate(self.fields)], axis=-1)
+        cols = []
+        for j, f in enumerate(self.fields):
+            if f.kind_code != FIELD_COORDINATE:
+                cols.append(f.bucket(v[..., j]))
+            elif f.kind == "coordinate":            # (0 in its three columns where the field has a value, -1 where one is missing)
+                cols += [np.where(f.cells(v[..., j:j + 3])[3], 0, -1).astype(np.int32)] * 3
+        return np.stack(cols, axis=-1)
 
     def encode(self, values):
         """float64 [..., F] -> bool [..., input_dim]."""
         b = self.bucket(values)
         out = np.zeros(b.shape[:-1] + (self.input_dim,), dtype=np.bool_)
         flat, bflat = out.reshape(-1, self.input_dim), b.reshape(-1, len(self.fields)).astype(np.int64)
+        vflat = self._values(values).reshape(-1, len(self.fields))
         for j, (f, off) in enumerate(zip(self.fields, self.offsets)):
             rows = np.flatnonzero(bflat[:, j] >= 0)
+            if f.kind_code == FIELD_COORDINATE:
+                if f.kind == "coordinate":
+                    cx, cy, r, _ = f.cells(vflat[rows, j:j + 3])
+                    for i, row in enumerate(rows):
+                        flat[row, off + f.positions(cx[i], cy[i], r[i])] = True
+                continue
             flat[rows[:, None], off + f.window(bflat[rows, j])] = True
         return out
 
@@ -240,6 +377,9 @@ class ScalarEncoder:
         buckets = np.empty(votes.shape[:-1] + (len(self.fields),), dtype=np.int32)
         scores = np.empty_like(buckets)
         for j, (f, off) in enumerate(zip(self.fields, self.offsets)):
+            if f.kind_code == FIELD_COORDINATE:     # (no decode)
+                buckets[..., j], scores[..., j] = -1, 0
+                continue
             score = f.scores(votes[..., off:off + f.bits].astype(np.int64))
             best = np.argmax(score, axis=-1)                        # (the first of equal maxima: the lowest bucket)
             top = np.take_along_axis(score, best[..., None], -1)[..., 0]
@@ -269,6 +409,8 @@ class ScalarEncoder:
             raise ValueError(f"encoder: its input_dim {self.input_dim} is not the model's {int(input_dim)}")
         if column_dim is not None:
             for f in self.fields:
+                if f.kind_code == FIELD_COORDINATE:                 # (not decoded: no score, no prefix sums)
+                    continue
                 if int(column_dim) * f.width >= 1 << 31:
                     raise ValueError(f"encoder: column_dim * width = {int(column_dim) * f.width} does not fit an int32 score")
                 if f.kind_code == FIELD_HASHED and f.decode_elements() > DECODE_MAX_BITS:
@@ -324,3 +466,24 @@ def date_values(times, time_of_day=True, day_of_week=True, weekend=True):
     if not parts:
         raise ValueError("date_values: every part is left out")
     return np.where(nat[..., None], np.nan, np.stack(parts, axis=-1))
+
+
+EARTH_RADIUS = 6378137.0                            # metres: the sphere of the spherical Mercator projection (EPSG:3857)
+
+
+def geo_values(longitude, latitude, speed, scale, timestep=1.0, width=21):
+    """Degrees and metres per second -> float64 [..., 3], the three value columns of CoordinateField(resolution=scale), as NuPIC's
+    GeospatialCoordinateEncoder forms them: the spherical Mercator metres x = R * lon, y = R * ln tan(pi / 4 + lat / 2) (angles in
+    radians, R = 6 378 137), and the radius in cells max(rint(speed * timestep / scale / 2 * 1.5), ceil((sqrt(width) - 1) / 2)) --
+    `scale` metres per cell, `timestep` seconds between readings, `width` the field's.  NaN in, NaN out."""
+    lon, lat, speed = np.broadcast_arrays(np.asarray(longitude, np.float64), np.asarray(latitude, np.float64), np.asarray(speed, np.float64))
+    scale, timestep = float(scale), float(timestep)
+    if not (np.isfinite(scale) and scale > 0.0 and np.isfinite(timestep) and timestep > 0.0 and int(width) >= 1):
+        raise ValueError(f"geo_values: scale and timestep above 0 and width >= 1, got {scale}, {timestep}, {width}")
+    with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
+        x = EARTH_RADIUS * np.deg2rad(lon)
+        y = EARTH_RADIUS * np.log(np.tan(np.pi / 4.0 + np.deg2rad(lat) / 2.0))
+        least = np.ceil((np.sqrt(float(int(width))) - 1.0) / 2.0)
+        cells = speed * timestep / scale / 2.0 * 1.5
+        radius = np.where(np.isnan(cells), np.nan, np.maximum(np.rint(cells), least))
+    return np.stack([x, y, radius], axis=-1)

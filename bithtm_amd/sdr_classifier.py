@@ -16,6 +16,7 @@ import numpy as np
 
 from . import _lib as L
 from .classifier import EXP_TABLE, W_LIMIT, check_params, check_patterns
+from .encoders import FIELD_COORDINATE
 from .engine import HtmError
 
 
@@ -61,6 +62,8 @@ class _DeviceClassifier:
     def __init__(self, buckets=None, field=None, steps=(1,), alpha=0.001, shape=None):
         if (buckets is None) == (field is None):
             raise ValueError("SDRClassifier: give buckets= or field=, one of them")
+        if field is not None and getattr(field, "kind_code", None) == FIELD_COORDINATE:
+            raise ValueError("SDRClassifier: a coordinate field (or one of its axes) has no buckets to classify: give another field")
         self.field = field
         self.buckets, self.steps, self.alpha_q = check_params(field.buckets if buckets is None else buckets, steps, alpha)
         self.shape = None

@@ -787,8 +787,8 @@ int htm_sp_run(htm_handle *h, const uint32_t *device_inputs, int32_t n_inputs, i
  *
  * Field kinds.  The member `reserved` carries the kind of a field:
  *   reserved == 0     a linear field: all of the above, bit for bit
- *   reserved & 3      the kind otherwise: HTM_FIELD_CATEGORY (1) or HTM_FIELD_HASHED (2); 3 is refused
- *   reserved >> 2     the seed of a hashed field, 0 <= seed < 2^29; it must be 0 for any other kind
+ *   reserved & 3      the kind otherwise: HTM_FIELD_CATEGORY (1), HTM_FIELD_HASHED (2) or HTM_FIELD_COORDINATE (3, below)
+ *   reserved >> 2     the seed of a hashed field or of a coordinate field's head, 0 <= seed < 2^29; it must be 0 anywhere else
  * A category field has `buckets` categories of `width` bits each, buckets * width <= bits (trailing bits stay unused), and is
  * passed with minimum 0 and scale 1:
  *   bucket(v): t = (v - minimum) * scale as above; missing (-1) unless 0 <= floor(t) < buckets -- an unknown id, NaN and +-inf
@@ -804,18 +804,44 @@ int htm_sp_run(htm_handle *h, const uint32_t *device_inputs, int32_t n_inputs, i
  *   decode:    G[i] = votes[offset + pos(i)], score[b] = G[b] + ... + G[b + width - 1] (a collided bit counts once per j)
  * Both decode to the lowest bucket with the largest score, (-1, 0) where that score is 0, as a linear field.
  * HTM_ERR_ARGUMENT, nothing enqueued, besides the cases above (which hold for every kind, `width <= bits` and `buckets` as
- * defined for linear fields only): reserved < 0; kind 3; a seed on a field that is not hashed; periodic != 0 on a field that is
+ * defined for linear fields only): reserved < 0; an entry of kind 3 outside a coordinate group (below: a lone entry of kind 3
+ * is refused as it always was); a seed on a field that is neither hashed nor a coordinate head; periodic != 0 on a field that is
  * not linear; a category field with buckets < 1 or buckets * width > bits; a hashed field with buckets < 1 or width >
  * HTM_HASHED_MAX_WIDTH; for the decoding calls a hashed field with buckets + width - 1 > HTM_DECODE_MAX_BITS (this replaces the
  * cap on `bits` for a hashed field: its prefix sums run over positions, not bits).
  * A caller that left garbage in `reserved` sees a difference to earlier builds of ABI version 4, which ignored the member;
- * a caller that zeroed it, as documented, sees none. */
+ * a caller that zeroed it, as documented, sees none.
+ *
+ * Coordinate fields: a 2-D position and a radius in, the `width` highest-ranked cells of the square round
+ * the position out -- near positions share most of their bits, positions more than two radii apart next to none.  The field reads
+ * THREE value columns (x, y, radius in cells) and is a group of three consecutive table entries, one per column; n_fields, the
+ * values' last axis and the decode output's field axis go on counting value columns:
+ *   head (x)     minimum = x origin, scale = 1 / resolution, offset, bits >= 1, 1 <= width <= HTM_HASHED_MAX_WIDTH,
+ *                buckets = max_radius in [0, HTM_COORD_MAX_RADIUS], periodic 0, reserved = 3 | seed << 2
+ *   y            minimum = y origin, scale = 1 / resolution, the head's offset, bits 0, width 0, buckets 0, periodic 0, reserved 3
+ *   radius       minimum finite, scale > 0 (0 and 1 for a radius given in cells), the rest as the y entry
+ *   cell(v):     t = (v - minimum) * scale; missing unless -2^30 <= t < 2^30 (NaN and +-inf fail); else c = (int32_t)floor(t)
+ *   radius(v):   t = (v - minimum) * scale; missing if NaN or t < 0; else r = (int)min(floor(t), (double)max_radius): +inf is max_radius
+ *   candidates:  the N = (2r + 1)^2 cells cx - r <= x <= cx + r, cy - r <= y <= cy + r, index i = (y - (cy - r)) * (2r + 1) + (x - (cx - r))
+ *   order(x, y) = htm_draw24(htm_stream_base(seed, 8, 0), (uint32_t)x, (uint32_t)y)
+ *   bit(x, y)   = ((uint64_t)htm_draw32(htm_stream_base(seed, 8, 1), (uint32_t)x, (uint32_t)y) * bits) >> 32
+ *   encode:      the min(width, N) candidates of the largest order, ties at the cut to the lower index i, each set offset +
+ *                bit(p); bits may collide; a row in which any of the three values is missing gets no bit of the field
+ *   decode:      none: every one of the three columns decodes to (-1, 0)
+ * HTM_ERR_ARGUMENT, nothing enqueued: a head (kind 3, bits >= 1) not followed by exactly two continuations (kind 3, bits 0) --
+ * the end of the table included; a continuation not behind a head, a third one included; max_radius outside [0,
+ * HTM_COORD_MAX_RADIUS]; width outside [1, HTM_HASHED_MAX_WIDTH]; periodic != 0; a continuation with a seed, a width, buckets
+ * or an offset other than the head's; and on the head what every kind is held to (inside the row, no overlap, a finite minimum and
+ * scale > 0 -- the latter two on the continuations too).  Continuations hold no bits and take no part in the overlap check; no
+ * entry of the group is held to HTM_DECODE_MAX_BITS. */
 #define HTM_SCALAR_MAX_FIELDS 16
 #define HTM_DECODE_MAX_BITS 8192
 #define HTM_HASHED_MAX_WIDTH 256
+#define HTM_COORD_MAX_RADIUS 127
 #define HTM_FIELD_LINEAR 0
 #define HTM_FIELD_CATEGORY 1
 #define HTM_FIELD_HASHED 2
+#define HTM_FIELD_COORDINATE 3
 typedef struct htm_scalar_field {
     double minimum, scale;
     int32_t offset, bits, width, buckets, periodic, reserved;
