@@ -97,6 +97,14 @@ class HtmKnnsInfo(C.Structure):
         (name, C.c_int64) for name in ("total", "state_bytes", "device_bytes", "scratch_bytes")]
 
 
+class HtmPoolLink(C.Structure):
+    """htm_pool_link: the parameters of a pooling link (pooling.PoolingLink.PARAMETERS order)."""
+    _fields_ = [("struct_bytes", C.c_uint32)] + [(name, C.c_int32) for name in (
+        "stride", "active_weight", "predicted_weight", "decay", "ceiling", "union_bits", "reserved")]
+
+
+POOL_MAX_COLUMNS = 256 * 1024               # HTM_POOL_MAX_COLUMNS (csrc/htm_pool.h): the most lower columns htm_pool_columns serves
+POOL_SCRATCH_BYTES = 256 << 20              # the most scratch a stack gives a pooled link's htm_pool_columns calls
 KNNS_SCRATCH_BYTES = 256 << 20              # HTM_KNNS_SCRATCH_BYTES (csrc/htm_knn_bank.h): the most scratch a bank's update may hold
 KNNS_MAX_STREAMS = 65535                    # HTM_KNNS_MAX_STREAMS
 KNN_CHUNK = 64                              # HTM_KNN_CHUNK (csrc/htm_knn.h): query steps per launch of htm_knn_update
@@ -181,6 +189,8 @@ EXPORTS = {
     "htm_view_sync": (C.c_int, [C.c_void_p, C.c_void_p]),
     "htm_bank_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_void_p]),
     "htm_pack_columns": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int32]),
+    "htm_pool_columns": (C.c_int, [C.c_void_p, HtmPoolLink, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                   C.c_int64, C.c_void_p, C.c_int32, C.c_int32]),
     "htm_encode_votes": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int32]),
     "htm_set_run_feedback": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32]),
     "htm_bank_noise": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_uint32, C.c_int32, C.c_uint32, C.c_uint32,

@@ -44,6 +44,7 @@
 #include "htm_reset.h"
 #include "htm_decode.h"
 #include "htm_stack.h"
+#include "htm_pool.h"
 #include "htm_forecast.h"
 #include "htm_noise.h"
 #include "htm_group.h"
@@ -3482,6 +3483,77 @@ extern "C" int htm_pack_columns(htm_handle *h, const int32_t *device_lists, int3
     HIPCHK(h, hipSetDevice(h->device));
     LAUNCH_ON(h, h->stream, pack_lds(h->d), "pack_columns", k_pack_columns, n_rows, PACK_THREADS, h->d, device_lists, k, stride, device_bank,
               bank_rows, first_row);
+    return launch_status(h->err);
+}
+
+// Pooling links (htm_pool.h): bank rows for h from the lists and the column predictions a lower region's recorded run left on the
+// device, through the link's state arrays; per batch of the windows that fit the caller's scratch, the pack launch at stride 1,
+// the scan and the select
+extern "C" int htm_pool_columns(htm_handle *h, htm_pool_link link, const int32_t *device_lists, int32_t k, const uint32_t *device_column_prediction,
+                                int32_t n_rows, uint8_t *device_persistence, uint32_t *device_prev, const uint32_t *device_reset_bits,
+                                void *device_scratch, int64_t scratch_bytes, uint32_t *device_bank, int32_t bank_rows, int32_t first_row) {
+    if (!h || !device_lists || !device_bank) return HTM_ERR_ARGUMENT;
+    if (!device_column_prediction || !device_persistence || !device_prev || !device_scratch) {
+        h->err = "htm_pool_columns: null column prediction, state or scratch";
+        return HTM_ERR_ARGUMENT;
+    }
+    if (link.struct_bytes != sizeof(htm_pool_link)) { h->err = "htm_pool_columns: struct_bytes != sizeof(htm_pool_link)"; return HTM_ERR_ARGUMENT; }
+    if (k < 1 || link.stride < 1 || n_rows < 0 || bank_rows < 1 || first_row < 0 || first_row >= bank_rows) {
+        h->err = "htm_pool_columns: k >= 1, stride >= 1, n_rows >= 0, bank_rows >= 1 and 0 <= first_row < bank_rows";
+        return HTM_ERR_ARGUMENT;
+    }
+    if (link.active_weight < 0 || link.active_weight > 255 || link.predicted_weight < 0 || link.predicted_weight > 255 ||
+        (link.active_weight == 0 && link.predicted_weight == 0)) {
+        h->err = "htm_pool_columns: 0 <= active_weight, predicted_weight <= 255, not both 0";
+        return HTM_ERR_ARGUMENT;
+    }
+    if (link.decay < 1 || link.decay > 255 || link.ceiling < 1 || link.ceiling > 255) {
+        h->err = "htm_pool_columns: 1 <= decay <= 255 and 1 <= ceiling <= 255";
+        return HTM_ERR_ARGUMENT;
+    }
+    if (((uintptr_t)device_bank & 15) != 0) { h->err = "htm_pool_columns: the bank must be 16-byte aligned"; return HTM_ERR_ARGUMENT; }
+    if ((((uintptr_t)device_persistence | (uintptr_t)device_prev | (uintptr_t)device_scratch) & 15) != 0) {
+        h->err = "htm_pool_columns: the persistence, the prev words and the scratch must be 16-byte aligned";
+        return HTM_ERR_ARGUMENT;
+    }
+    if (!h->cfg.enable_sp) { h->err = "htm_pool_columns: needs a handle with the device's own Spatial Pooler (its input rows are packed)"; return HTM_ERR_STATE; }
+    if (h->world > 1) { h->err = "htm_pool_columns: not available on a column-sharded handle"; return HTM_ERR_STATE; }
+    REJECT_WHEN_AHEAD(h);
+    const int C = h->d.I, W = h->d.W;
+    if (C > POOL_MAX_COLUMNS) { h->err = "htm_pool_columns: more lower columns (the handle's input_dim) than HTM_POOL_MAX_COLUMNS (262144)"; return HTM_ERR_ARGUMENT; }
+    if (link.union_bits < 1 || link.union_bits > C) { h->err = "htm_pool_columns: 1 <= union_bits <= the handle's input_dim"; return HTM_ERR_ARGUMENT; }
+    const size_t window = pool_window_bytes(W, link.stride);
+    if (scratch_bytes < 0 || (uint64_t)scratch_bytes < (uint64_t)window) {
+        h->err = "htm_pool_columns: the scratch is too small for one window (" + std::to_string(window) + " bytes)";
+        return HTM_ERR_ARGUMENT;
+    }
+    if (n_rows == 0) return HTM_OK;
+    HIPCHK(h, hipSetDevice(h->device));
+    // (a batch's steps are the pack launch's grid: 32-bit)
+    const int per_batch = (int)std::min<uint64_t>(std::min<uint64_t>((uint64_t)n_rows, (uint64_t)scratch_bytes / window), (uint64_t)(INT32_MAX / link.stride));
+    const int PW = (C + 31) / 32;
+    for (long long r0 = 0; r0 < n_rows; r0 += per_batch) {
+        const int n = (int)std::min<long long>(per_batch, n_rows - r0);
+        const size_t steps = (size_t)n * (size_t)link.stride, first_step = (size_t)r0 * (size_t)link.stride;
+        uint32_t *bitmaps = (uint32_t *)device_scratch;
+        PoolDev a;
+        a.C = C; a.W = W; a.PW = PW;
+        a.stride = link.stride; a.n_windows = n;
+        a.active_weight = link.active_weight; a.predicted_weight = link.predicted_weight; a.decay = link.decay; a.ceiling = link.ceiling;
+        a.union_bits = link.union_bits;
+        a.bank_rows = bank_rows; a.first_row = (int)(((long long)first_row + r0) % bank_rows);
+        a.bitmaps = bitmaps;
+        a.colpred = device_column_prediction + first_step * (size_t)PW;
+        a.resets = device_reset_bits;
+        a.persistence = device_persistence; a.prev = device_prev;
+        a.snap = (uint8_t *)device_scratch + steps * (size_t)W * 4;           // (a multiple of 16 bytes: W is a multiple of 4)
+        a.bank = device_bank;
+        // the bitmap rows: one per step, row s of the scratch (bank_rows = the batch's steps, no rotation)
+        LAUNCH_ON(h, h->stream, pack_lds(h->d), "pool_pack", k_pack_columns, (int)steps, PACK_THREADS, h->d, device_lists + first_step * (size_t)k, k, 1, bitmaps,
+                  (int)steps, 0);
+        LAUNCH(h, "pool_scan", kpool_scan, (W * 32 + POOL_THREADS - 1) / POOL_THREADS, POOL_THREADS, a);
+        LAUNCH_ON(h, h->stream, pool_select_lds(W), "pool_select", kpool_select, n, POOL_THREADS, a);
+    }
     return launch_status(h->err);
 }
 

@@ -630,6 +630,17 @@ class Engine:
         self._check(self.lib.htm_pack_columns(self.h, C.c_void_p(device_lists), int(k), int(n_rows), int(stride), C.c_void_p(device_bank),
                                               int(bank_rows), int(first_row)), "htm_pack_columns")
 
+    def pool_columns(self, link, device_lists, k, device_column_prediction, n_rows, device_persistence, device_prev, device_reset_bits,
+                     device_scratch, scratch_bytes, device_bank, bank_rows, first_row):
+        """Bank rows of this engine from the recorded active-column lists and column predictions of n_rows windows, through a
+        pooling link's state arrays on the device (htm_pool_columns; `link`: a resolved pooling.PoolingLink): enqueued on its
+        stream, no wait."""
+        p = L.HtmPoolLink(C.sizeof(L.HtmPoolLink), link.stride, link.active_weight, link.predicted_weight, link.decay, link.ceiling, link.union_bits, 0)
+        self._check(self.lib.htm_pool_columns(self.h, p, C.c_void_p(device_lists), int(k), C.c_void_p(device_column_prediction), int(n_rows),
+                                              C.c_void_p(device_persistence), C.c_void_p(device_prev),
+                                              C.c_void_p(device_reset_bits) if device_reset_bits else None, C.c_void_p(device_scratch),
+                                              int(scratch_bytes), C.c_void_p(device_bank), int(bank_rows), int(first_row)), "htm_pool_columns")
+
     @staticmethod
     def _record_fields(record, allowed=RECORD_FIELDS):
         """The fields of a `record` argument as a tuple; ValueError for one that is not in `allowed`, or for none."""

@@ -626,6 +626,46 @@ int htm_bank_rows(htm_handle *h, const uint32_t *device_bank, int32_t bank_rows,
 int htm_pack_columns(htm_handle *dst, const int32_t *device_lists, int32_t k, int32_t n_rows, int32_t stride,
                      uint32_t *device_bank, int32_t bank_rows, int32_t first_row);
 
+/* Pooling links (DESIGN.md sections 14 and 29; the definition: bithtm_amd/pooling.py): the link of a region stack that gives the
+ * upper region a decaying union of the lower region's columns instead of their OR.  The link's state over a lower region of C
+ * columns is persistence uint8[C] and prev (bit c: the column prediction the lower region's last step left), both 0 at first.
+ * Per lower step with the active columns A (a row of device_lists) and its column prediction (a row of column_prediction as
+ * htm_run_recorded leaves it, ceil(C / 32) words):
+ *   P    = max(P - decay, 0)                                                   every column
+ *   P[A] = min(ceiling, P[A] + (prev[A] ? predicted_weight : active_weight))
+ *   prev = column prediction
+ * and per window of `stride` steps
+ *   bank row (first_row + r) % bank_rows = a bit for each of the union_bits columns with the largest P among those with P > 0,
+ *   ties at the cut to the lower column index (np.lexsort((arange(C), -P))[:union_bits]); fewer positive columns: fewer bits.
+ * device_reset_bits (or NULL): bit (first_row + r) % bank_rows set = P and prev are cleared before window r's first step -- the
+ * bits the upper region's run takes for the same rows (htm_set_run_resets).
+ *
+ * htm_pool_columns: n_rows windows, i.e. n_rows * stride rows of device_lists (k ids each) and of device_column_prediction, into
+ * n_rows rows of device_bank, with device_bank, bank_rows and first_row exactly as htm_pack_columns takes them; C is dst's
+ * input_dim.  device_persistence (C bytes) and device_prev (ceil(C / 32) words) are read at the start and left as the last step
+ * leaves them.  device_scratch is the caller's, scratch_bytes of it: a window needs (stride + 8) * 4 * words_per_row bytes, and
+ * the call works in batches of as many windows as fit (three launches per batch, the state arrays carrying the state from one
+ * batch to the next).  Enqueued on dst's stream; no copy, no wait, no allocation.  An id outside [0, C) counts for nothing and
+ * raises bit 64 of htm_info.capacity_error (sticky), as in htm_pack_columns.  Rows outside the n_rows written keep their contents.
+ *
+ * HTM_ERR_ARGUMENT, nothing enqueued: htm_pack_columns' refusals (NULL pointers -- the reset bits alone may be NULL --, k < 1,
+ * stride < 1, n_rows < 0, bank_rows < 1, first_row outside [0, bank_rows), a bank that is not 16-byte aligned); struct_bytes !=
+ * sizeof(htm_pool_link); active_weight or predicted_weight outside [0, 255] or both 0; decay or ceiling outside [1, 255];
+ * union_bits outside [1, C]; C above HTM_POOL_MAX_COLUMNS; a persistence, prev or scratch address that is not 16-byte aligned; a
+ * scratch too small for one window.  HTM_ERR_STATE, nothing enqueued: as htm_pack_columns. */
+#define HTM_POOL_MAX_COLUMNS 262144
+typedef struct htm_pool_link {
+    uint32_t struct_bytes;              /* sizeof(htm_pool_link) */
+    int32_t stride;
+    int32_t active_weight, predicted_weight;
+    int32_t decay, ceiling;
+    int32_t union_bits;
+    int32_t reserved;                   /* 0 */
+} htm_pool_link;
+int htm_pool_columns(htm_handle *dst, htm_pool_link link, const int32_t *device_lists, int32_t k, const uint32_t *device_column_prediction,
+                     int32_t n_rows, uint8_t *device_persistence, uint32_t *device_prev, const uint32_t *device_reset_bits,
+                     void *device_scratch, int64_t scratch_bytes, uint32_t *device_bank, int32_t bank_rows, int32_t first_row);
+
 /* Closed-loop forecasting: what the model expects over the next n steps, its own predicted input fed back
  * as the next input on the device.  With votes = the predicted-input votes of a state (htm_predicted_input above),
  *   encode(votes, min_votes, max_bits):  x = votes >= min_votes; if max_bits > 0 and x.sum() > max_bits, only the max_bits inputs
