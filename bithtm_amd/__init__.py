@@ -16,6 +16,7 @@ from .networks import InferenceView, flip_noise, noise_threshold  # noqa: F401
 from .engine import CapacityError, HtmError  # noqa: F401
 from .group import GroupTick, ModelGroup  # noqa: F401
 from .stack import RegionStack  # noqa: F401
+from .group_stack import GroupStack  # noqa: F401
 from .pooling import PoolingLink  # noqa: F401
 from .projections import DenseProjection, PredictiveProjection  # noqa: F401
 from .regularizations import ExponentialBoosting, GlobalInhibition  # noqa: F401

@@ -231,6 +231,9 @@ EXPORTS = {
     "htm_classifiers_import": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]),
     "htm_set_run_active_cells": (C.c_int, [C.c_void_p, C.c_void_p]),
     "htm_set_group_run_active_cells": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "htm_group_pack_columns": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]),
+    "htm_group_pool_columns": (C.c_int, [C.c_void_p, HtmPoolLink, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                         C.c_int64, C.c_void_p, C.c_int32, C.c_void_p]),
     "htm_classifiers_tick": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(HtmScalarField), C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
     "htm_knn_create": (C.c_int, [C.c_void_p, C.POINTER(HtmKnnConfig), C.POINTER(C.c_void_p)]),

@@ -30,8 +30,11 @@ COORD_REPORTS = {"htm_coord.h": os.path.join(HERE, "libbithtm_hip.coord.resource
 # ... and the pooling links' kernels, which none of the five functions above returns either: kernel_resources("htm_pool.h")
 # (tests/test_pooling_cpu.py).
 POOL_REPORTS = {"htm_pool.h": os.path.join(HERE, "libbithtm_hip.pool.resources.json")}
+# ... and the member-indexed link kernels of stacks of model groups: kernel_resources("htm_group_stack.h")
+# (tests/test_group_stack_cpu.py).
+GROUP_STACK_REPORTS = {"htm_group_stack.h": os.path.join(HERE, "libbithtm_hip.group_stack.resources.json")}
 SOURCES = ["htm_engine.hip"]
-HEADERS = ["htm_dev.h", "htm_sp_kernels.h", "htm_tm_kernels.h", "htm_pipeline.h", "htm_record.h", "htm_reset.h", "htm_decode.h", "htm_stack.h", "htm_pool.h", "htm_forecast.h", "htm_noise.h", "htm_group.h", "htm_tm_feed.h", "htm_sp_run.h", "htm_fork.h", "htm_scalar.h", "htm_live.h", "htm_fields.h", "htm_coord.h", "htm_likelihood.h", "htm_classifier.h", "htm_knn.h", "htm_knn_bank.h", "htm_handover.h", "htm_handover_last.h", "htm_rng.h", "htm_fexp.h",
+HEADERS = ["htm_dev.h", "htm_sp_kernels.h", "htm_tm_kernels.h", "htm_pipeline.h", "htm_record.h", "htm_reset.h", "htm_decode.h", "htm_stack.h", "htm_pool.h", "htm_pool_select.inc", "htm_group_stack.h", "htm_forecast.h", "htm_noise.h", "htm_group.h", "htm_tm_feed.h", "htm_sp_run.h", "htm_fork.h", "htm_scalar.h", "htm_live.h", "htm_fields.h", "htm_coord.h", "htm_likelihood.h", "htm_classifier.h", "htm_knn.h", "htm_knn_bank.h", "htm_handover.h", "htm_handover_last.h", "htm_rng.h", "htm_fexp.h",
            os.path.join("..", "..", "include", "bithtm_hip.h")]
 # -ffp-contract=off: several kernels must round exactly like the NumPy expressions they replace
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off",
@@ -40,7 +43,7 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-ffp
 
 
 def _stale():
-    if not os.path.exists(LIB) or not all(os.path.exists(r) for r in [RESOURCES] + list(OWN_REPORTS.values()) + list(LATER_REPORTS.values()) + list(BANK_REPORTS.values()) + list(LAST_REPORTS.values()) + list(COORD_REPORTS.values()) + list(POOL_REPORTS.values())):
+    if not os.path.exists(LIB) or not all(os.path.exists(r) for r in [RESOURCES] + list(OWN_REPORTS.values()) + list(LATER_REPORTS.values()) + list(BANK_REPORTS.values()) + list(LAST_REPORTS.values()) + list(COORD_REPORTS.values()) + list(POOL_REPORTS.values()) + list(GROUP_STACK_REPORTS.values())):
         return True
     t = os.path.getmtime(LIB)
     deps = [os.path.join(CSRC, s) for s in SOURCES + HEADERS] + [os.path.abspath(__file__)]
@@ -95,7 +98,7 @@ def build(force=False, verbose=False):
     if r.returncode != 0:
         raise RuntimeError("hipcc failed:\n" + r.stdout)
     by_header = _kernel_resources(r.stdout)
-    for header, path in list(OWN_REPORTS.items()) + list(LATER_REPORTS.items()) + list(BANK_REPORTS.items()) + list(LAST_REPORTS.items()) + list(COORD_REPORTS.items()) + list(POOL_REPORTS.items()):
+    for header, path in list(OWN_REPORTS.items()) + list(LATER_REPORTS.items()) + list(BANK_REPORTS.items()) + list(LAST_REPORTS.items()) + list(COORD_REPORTS.items()) + list(POOL_REPORTS.items()) + list(GROUP_STACK_REPORTS.items()):
         with open(path, "w") as f:
             json.dump(by_header.pop(header, {}), f, indent=0, sort_keys=True)
     with open(RESOURCES, "w") as f:
@@ -109,9 +112,9 @@ def build(force=False, verbose=False):
 
 def kernel_resources(header=None):
     """{mangled kernel name: resources} of the library as last built here (None if it was built elsewhere): the kernels of RESOURCES,
-    or those the header `header` of OWN_REPORTS, LATER_REPORTS, BANK_REPORTS, LAST_REPORTS, COORD_REPORTS or POOL_REPORTS defines."""
+    or those the header `header` of OWN_REPORTS, LATER_REPORTS, BANK_REPORTS, LAST_REPORTS, COORD_REPORTS, POOL_REPORTS or GROUP_STACK_REPORTS defines."""
     build()
-    path = RESOURCES if header is None else {**OWN_REPORTS, **LATER_REPORTS, **BANK_REPORTS, **LAST_REPORTS, **COORD_REPORTS, **POOL_REPORTS}[header]
+    path = RESOURCES if header is None else {**OWN_REPORTS, **LATER_REPORTS, **BANK_REPORTS, **LAST_REPORTS, **COORD_REPORTS, **POOL_REPORTS, **GROUP_STACK_REPORTS}[header]
     if not os.path.exists(path):
         return None
     with open(path) as f:

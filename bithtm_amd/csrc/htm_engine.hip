@@ -61,6 +61,7 @@
 #include "htm_knn_bank.h"
 #include "htm_handover.h"
 #include "htm_handover_last.h"
+#include "htm_group_stack.h"
 
 // ------------------------------------------------------------------------------------------
 // host side
@@ -3802,6 +3803,12 @@ struct htm_group {
     // through it), filled by the setter; capturing: rows are set
     ClsCapDev *d_caps = nullptr;
     bool capturing = false;
+    // stacks of groups (htm_group_pack_columns / htm_group_pool_columns; htm_group_stack.h): the link table of the call last
+    // enqueued and the host rows its copy was made from
+    char *link_tab = nullptr;
+    size_t link_tab_bytes = 0;
+    std::vector<GrpPackRow> pack_rows;
+    std::vector<char> link_rows;
     // inference views (htm_create_view): some member is a view; every member aliases one set of weights (then the steps with
     // learning = 0 scan the store once per chunk of share_m members: kgrp_scan_shared, share_chunks x share_blocks blocks)
     bool has_view, shared;
@@ -4242,6 +4249,162 @@ extern "C" int htm_set_group_run_active_cells(htm_group *g, void *const *device_
     GHIPCHK(g, hipMemcpyAsync(g->d_caps, caps.data(), caps.size() * sizeof(ClsCapDev), hipMemcpyHostToDevice, g->stream));
     g->capturing = true;
     return HTM_OK;
+}
+
+// ------------------------------------------------------------------------------------------
+// Stacks of model groups (htm_group_stack.h): the links of B streams' hierarchies, every launch covering all
+// members (grid y = member).  A call's per-member pointers go into the group's link table -- one buffer, grown when a call needs
+// more, filled by ONE copy on the group's stream from a vector the group keeps (the copy has read it when it returns; the launches
+// behind it on the stream read the table, and the next call's copy orders itself behind them).
+
+// what both entries refuse about the group's members, before anything is enqueued
+static int gstack_check(htm_group *g, const char *what) {
+    if (g->n > GSTACK_MAX_MEMBERS) { g->err = std::string(what) + ": more than 65535 members"; return HTM_ERR_ARGUMENT; }
+    for (int i = 0; i < g->n; ++i) {
+        const htm_handle *h = g->m[i];
+        const std::string who = std::string(what) + ": member " + std::to_string(i);
+        if (!h->cfg.enable_sp) { g->err = who + " needs the device's own Spatial Pooler (its input rows are packed)"; return HTM_ERR_STATE; }
+        if (h->world > 1) { g->err = who + " is column-sharded"; return HTM_ERR_STATE; }
+        if (sp_is_ahead(h)) { g->err = who + ": the Spatial Pooler is ahead (htm_run ended with HTM_RUN_CONTINUE)"; return HTM_ERR_STATE; }
+        if (h->stream != g->stream) { g->err = who + " enqueues on another stream than the group's"; return HTM_ERR_STATE; }
+    }
+    return 0;
+}
+
+// the group's link table with room for `bytes`, filled from `rows` by one copy on the group's stream
+static int gstack_table(htm_group *g, const void *rows, size_t bytes, char **out) {
+    if (g->link_tab_bytes < bytes) {
+        char *t = nullptr;
+        if (galloc(g, &t, bytes)) return HTM_ERR_HIP;       // (the old one stays in g->allocs until the group goes: launches may still read it)
+        g->link_tab = t;
+        g->link_tab_bytes = bytes;
+    }
+    GHIPCHK(g, hipMemcpyAsync(g->link_tab, rows, bytes, hipMemcpyHostToDevice, g->stream));
+    *out = g->link_tab;
+    return 0;
+}
+
+extern "C" int htm_group_pack_columns(htm_group *g, const int32_t *const *device_lists, int32_t k, int32_t n_rows, int32_t stride,
+                                      uint32_t *const *device_banks, int32_t bank_rows, const int32_t *first_rows) {
+    if (!g) return HTM_ERR_ARGUMENT;
+    if (!device_lists || !device_banks || !first_rows) { g->err = "htm_group_pack_columns: null lists, banks or first_rows"; return HTM_ERR_ARGUMENT; }
+    if (k < 1 || stride < 1 || n_rows < 0 || bank_rows < 1) {
+        g->err = "htm_group_pack_columns: k >= 1, stride >= 1, n_rows >= 0 and bank_rows >= 1";
+        return HTM_ERR_ARGUMENT;
+    }
+    if (g->n > GSTACK_MAX_MEMBERS) { g->err = "htm_group_pack_columns: more than 65535 members"; return HTM_ERR_ARGUMENT; }
+    for (int i = 0; i < g->n; ++i) {
+        const std::string who = "htm_group_pack_columns: member " + std::to_string(i);
+        if (!device_lists[i] || !device_banks[i]) { g->err = who + ": null lists or bank"; return HTM_ERR_ARGUMENT; }
+        if (first_rows[i] < 0 || first_rows[i] >= bank_rows) { g->err = who + ": 0 <= first_row < bank_rows"; return HTM_ERR_ARGUMENT; }
+        if (((uintptr_t)device_banks[i] & 15) != 0) { g->err = who + ": the bank must be 16-byte aligned"; return HTM_ERR_ARGUMENT; }
+    }
+    if (int rc = gstack_check(g, "htm_group_pack_columns")) return rc;
+    htm_handle *h0 = g->m[0];
+    if (pack_lds(h0->d) > PACK_LDS_MAX) { g->err = "htm_group_pack_columns: an input row of the members does not fit the LDS (input_dim above 524288)"; return HTM_ERR_ARGUMENT; }
+    if (n_rows == 0) return HTM_OK;
+    GHIPCHK(g, hipSetDevice(g->device));
+    g->pack_rows.resize((size_t)g->n);
+    for (int i = 0; i < g->n; ++i) g->pack_rows[i] = GrpPackRow{device_lists[i], device_banks[i], first_rows[i], 0};
+    char *tab = nullptr;
+    if (int rc = gstack_table(g, g->pack_rows.data(), (size_t)g->n * sizeof(GrpPackRow), &tab)) return rc;
+    LAUNCH_ON(h0, g->stream, pack_lds(h0->d), "group:pack_columns", kgrp_pack_columns, dim3(n_rows, g->n), PACK_THREADS, (const Dev *)g->d_tab,
+              (const GrpPackRow *)tab, 0ll, k, stride, bank_rows);
+    return launch_status(g->err);
+}
+
+// The scratch: member m's part begins m * per_batch * (stride + 8) * 4 W bytes in, per_batch = floor(scratch_bytes / (B * (stride
+// + 8) * 4 W)) windows; inside it, the batch's per_batch * stride bitmap rows, then its per_batch snapshot rows (htm_pool.h).  The
+// table: B PoolDev of the whole call, then B GrpPackRow of the pack launches into the bitmap rows -- one copy.
+extern "C" int htm_group_pool_columns(htm_group *g, htm_pool_link link, const int32_t *const *device_lists, int32_t k,
+                                      const uint32_t *const *device_column_prediction, int32_t n_rows, uint8_t *const *device_persistence,
+                                      uint32_t *const *device_prev, const uint32_t *const *device_reset_bits, void *device_scratch, int64_t scratch_bytes,
+                                      uint32_t *const *device_banks, int32_t bank_rows, const int32_t *first_rows) {
+    if (!g) return HTM_ERR_ARGUMENT;
+    if (!device_lists || !device_banks || !first_rows || !device_column_prediction || !device_persistence || !device_prev || !device_scratch) {
+        g->err = "htm_group_pool_columns: null lists, banks, first_rows, column predictions, state or scratch";
+        return HTM_ERR_ARGUMENT;
+    }
+    if (link.struct_bytes != sizeof(htm_pool_link)) { g->err = "htm_group_pool_columns: struct_bytes != sizeof(htm_pool_link)"; return HTM_ERR_ARGUMENT; }
+    if (k < 1 || link.stride < 1 || n_rows < 0 || bank_rows < 1) {
+        g->err = "htm_group_pool_columns: k >= 1, stride >= 1, n_rows >= 0 and bank_rows >= 1";
+        return HTM_ERR_ARGUMENT;
+    }
+    if (link.active_weight < 0 || link.active_weight > 255 || link.predicted_weight < 0 || link.predicted_weight > 255 ||
+        (link.active_weight == 0 && link.predicted_weight == 0)) {
+        g->err = "htm_group_pool_columns: 0 <= active_weight, predicted_weight <= 255, not both 0";
+        return HTM_ERR_ARGUMENT;
+    }
+    if (link.decay < 1 || link.decay > 255 || link.ceiling < 1 || link.ceiling > 255) {
+        g->err = "htm_group_pool_columns: 1 <= decay <= 255 and 1 <= ceiling <= 255";
+        return HTM_ERR_ARGUMENT;
+    }
+    if (g->n > GSTACK_MAX_MEMBERS) { g->err = "htm_group_pool_columns: more than 65535 members"; return HTM_ERR_ARGUMENT; }
+    if (((uintptr_t)device_scratch & 15) != 0) { g->err = "htm_group_pool_columns: the scratch must be 16-byte aligned"; return HTM_ERR_ARGUMENT; }
+    for (int i = 0; i < g->n; ++i) {
+        const std::string who = "htm_group_pool_columns: member " + std::to_string(i);
+        if (!device_lists[i] || !device_banks[i] || !device_column_prediction[i] || !device_persistence[i] || !device_prev[i]) {
+            g->err = who + ": null lists, bank, column prediction or state";
+            return HTM_ERR_ARGUMENT;
+        }
+        if (first_rows[i] < 0 || first_rows[i] >= bank_rows) { g->err = who + ": 0 <= first_row < bank_rows"; return HTM_ERR_ARGUMENT; }
+        if (((uintptr_t)device_banks[i] & 15) != 0) { g->err = who + ": the bank must be 16-byte aligned"; return HTM_ERR_ARGUMENT; }
+        if ((((uintptr_t)device_persistence[i] | (uintptr_t)device_prev[i]) & 15) != 0) {
+            g->err = who + ": the persistence and the prev words must be 16-byte aligned";
+            return HTM_ERR_ARGUMENT;
+        }
+    }
+    if (int rc = gstack_check(g, "htm_group_pool_columns")) return rc;
+    htm_handle *h0 = g->m[0];
+    const int C = h0->d.I, W = h0->d.W, B = g->n;
+    if (C > POOL_MAX_COLUMNS) { g->err = "htm_group_pool_columns: more lower columns (the members' input_dim) than HTM_POOL_MAX_COLUMNS (262144)"; return HTM_ERR_ARGUMENT; }
+    if (link.union_bits < 1 || link.union_bits > C) { g->err = "htm_group_pool_columns: 1 <= union_bits <= the members' input_dim"; return HTM_ERR_ARGUMENT; }
+    const size_t window = pool_window_bytes(W, link.stride);
+    if (scratch_bytes < 0 || (uint64_t)scratch_bytes / window < (uint64_t)B) {
+        g->err = "htm_group_pool_columns: the scratch is too small for one window of every member (" + std::to_string(window) + " bytes each)";
+        return HTM_ERR_ARGUMENT;
+    }
+    if (n_rows == 0) return HTM_OK;
+    GHIPCHK(g, hipSetDevice(g->device));
+    // (a batch's steps are the pack launch's grid: 32-bit)
+    const int per_batch = (int)std::min<uint64_t>(std::min<uint64_t>((uint64_t)n_rows, (uint64_t)scratch_bytes / ((uint64_t)B * window)), (uint64_t)(INT32_MAX / link.stride));
+    const int PW = (C + 31) / 32;
+    const size_t member_bytes = gpool_member_bytes(W, link.stride, per_batch);
+    const size_t pool_bytes = (size_t)B * sizeof(PoolDev), bytes = pool_bytes + (size_t)B * sizeof(GrpPackRow);
+    g->link_rows.resize(bytes);
+    PoolDev *pools = (PoolDev *)g->link_rows.data();
+    GrpPackRow *packs = (GrpPackRow *)(g->link_rows.data() + pool_bytes);
+    for (int i = 0; i < B; ++i) {
+        char *part = (char *)device_scratch + (size_t)i * member_bytes;
+        PoolDev a;
+        a.C = C; a.W = W; a.PW = PW;
+        a.stride = link.stride; a.n_windows = n_rows;
+        a.active_weight = link.active_weight; a.predicted_weight = link.predicted_weight; a.decay = link.decay; a.ceiling = link.ceiling;
+        a.union_bits = link.union_bits;
+        a.bank_rows = bank_rows; a.first_row = first_rows[i];
+        a.bitmaps = (const uint32_t *)part;
+        a.colpred = device_column_prediction[i];
+        a.resets = device_reset_bits ? device_reset_bits[i] : nullptr;
+        a.persistence = device_persistence[i]; a.prev = device_prev[i];
+        a.snap = (uint8_t *)part + (size_t)per_batch * (size_t)link.stride * (size_t)W * 4;      // (a multiple of 16 bytes: W is a multiple of 4)
+        a.bank = device_banks[i];
+        pools[i] = a;
+        packs[i] = GrpPackRow{device_lists[i], (uint32_t *)part, 0, 0};
+    }
+    char *tab = nullptr;
+    if (int rc = gstack_table(g, g->link_rows.data(), bytes, &tab)) return rc;
+    const PoolDev *d_pools = (const PoolDev *)tab;
+    const GrpPackRow *d_packs = (const GrpPackRow *)(tab + pool_bytes);
+    for (long long r0 = 0; r0 < n_rows; r0 += per_batch) {
+        const int n = (int)std::min<long long>(per_batch, n_rows - r0);
+        const long long steps = (long long)n * link.stride, first_step = r0 * link.stride;
+        // the bitmap rows: one per step, row s of the member's part (bank_rows = the batch's steps, no rotation)
+        LAUNCH_ON(h0, g->stream, pack_lds(h0->d), "group:pool_pack", kgrp_pack_columns, dim3((int)steps, B), PACK_THREADS, (const Dev *)g->d_tab, d_packs,
+                  first_step * (long long)k, k, 1, (int)steps);
+        LAUNCH_ON(h0, g->stream, 0, "group:pool_scan", kgpool_scan, dim3((W * 32 + POOL_THREADS - 1) / POOL_THREADS, B), POOL_THREADS, d_pools, (int)r0, n);
+        LAUNCH_ON(h0, g->stream, pool_select_lds(W), "group:pool_select", kgpool_select, dim3(n, B), POOL_THREADS, d_pools, (int)r0, n);
+    }
+    return launch_status(g->err);
 }
 
 // ------------------------------------------------------------------------------------------

@@ -21,9 +21,10 @@
 
 static inline size_t pack_lds(const Dev &d) { return (size_t)d.W * 4; }
 
-__global__ __launch_bounds__(PACK_THREADS) void k_pack_columns(Dev d, const int32_t *__restrict__ lists, int32_t k, int32_t stride,
-                                                               uint32_t *__restrict__ bank, int32_t bank_rows, int32_t first_row) {
-    extern __shared__ __attribute__((aligned(16))) uint32_t s_row[];            // [d.W], d.W = 4 * d.W4
+// The block's work on output row blockIdx.x of the handle `d`, written once: k_pack_columns below and the member-indexed
+// kgrp_pack_columns (htm_group_stack.h) call it.  s_row: the launch's dynamic LDS, [d.W] words.
+__device__ __forceinline__ void pack_columns_block(const Dev &d, const int32_t *__restrict__ lists, int32_t k, int32_t stride,
+                                                   uint32_t *__restrict__ bank, int32_t bank_rows, int32_t first_row, uint32_t *s_row) {
     uint4 *s_row4 = reinterpret_cast<uint4 *>(s_row);
     for (int w = (int)threadIdx.x; w < d.W4; w += PACK_THREADS) s_row4[w] = make_uint4(0u, 0u, 0u, 0u);
     __syncthreads();
@@ -41,6 +42,12 @@ __global__ __launch_bounds__(PACK_THREADS) void k_pack_columns(Dev d, const int3
     const size_t row = (size_t)(((long long)first_row + (long long)r) % bank_rows);
     uint4 *dst = reinterpret_cast<uint4 *>(bank + row * (size_t)d.W);           // (rows are W words = 16 W4 bytes: aligned as the bank is)
     for (int w = (int)threadIdx.x; w < d.W4; w += PACK_THREADS) dst[w] = s_row4[w];
+}
+
+__global__ __launch_bounds__(PACK_THREADS) void k_pack_columns(Dev d, const int32_t *__restrict__ lists, int32_t k, int32_t stride,
+                                                               uint32_t *__restrict__ bank, int32_t bank_rows, int32_t first_row) {
+    extern __shared__ __attribute__((aligned(16))) uint32_t s_row[];            // [d.W], d.W = 4 * d.W4
+    pack_columns_block(d, lists, k, stride, bank, bank_rows, first_row, s_row);
 }
 
 #endif

@@ -444,6 +444,62 @@ class ModelGroup:
         records = call.finish([steps] * B, [k] * B)
         return None if fields is None else records
 
+    def run_into(self, banks, n_inputs, n_steps, buffers, learning=None, use_graph=True):
+        """The group's counterpart of Engine.run_into -- a run of every member, enqueued only: member i over the `n_inputs` rows of
+        the device bank banks[i], its records into buffers[i] = {record field: device address of its n_steps rows} (empty
+        dictionaries: a plain htm_group_run).  Nothing is synchronised, nothing is read back, no pool is looked at: the caller
+        orders its own work behind the group's stream (stacks of groups feed "active_column" to htm_group_pack_columns)."""
+        learning = self._learning(learning)
+        B, n = len(self.models), int(n_steps)
+        if len(banks) != B or len(buffers) != B:
+            raise ValueError(f"run_into(): {B} banks and {B} buffer dictionaries, one per member")
+        for m in self.models:
+            retire_states(m.engine)
+        self._current()
+        recs = (L.HtmRunRecord * B)()
+        votes = [m.engine._record_ptrs(b, recs[i]) for i, (m, b) in enumerate(zip(self.models, buffers))]
+        recorded = any(set(b) - {"predicted_input", "predicted_value"} for b in buffers)
+        try:
+            for m, v in zip(self.models, votes):
+                if v is not None:
+                    m.engine.set_run_predicted_input(v)
+            self._check(self.lib.htm_group_run(self._g, (C.c_void_p * B)(*banks), int(n_inputs), n, int(bool(learning)), int(bool(use_graph)),
+                                               recs if recorded else None), "htm_group_run")
+        finally:
+            if any(v is not None for v in votes):
+                self._unset_votes()
+        for m in self.models:
+            m.engine.steps += n
+            m._streaming = False
+
+    def _link_tables(self, lists, banks, first_rows):
+        B = len(self.models)
+        if not (len(lists) == len(banks) == len(first_rows) == B):
+            raise ValueError(f"{B} lists, banks and first rows, one per member")
+        return (C.c_void_p * B)(*lists), (C.c_void_p * B)(*banks), (C.c_int32 * B)(*[int(r) for r in first_rows])
+
+    def pack_columns(self, lists, k, n_rows, stride, banks, bank_rows, first_rows):
+        """Bank rows of every member from recorded active-column lists (htm_group_pack_columns: Engine.pack_columns of member i
+        with the i-th entries, in ONE launch): enqueued on the group's stream, no wait."""
+        self._current()
+        lists, banks, first = self._link_tables(lists, banks, first_rows)
+        self._check(self.lib.htm_group_pack_columns(self._g, lists, int(k), int(n_rows), int(stride), banks, int(bank_rows), first), "htm_group_pack_columns")
+
+    def pool_columns(self, link, lists, k, column_predictions, n_rows, persistences, prevs, reset_bits, scratch, scratch_bytes, banks, bank_rows, first_rows):
+        """Bank rows of every member through a pooling link (htm_group_pool_columns: Engine.pool_columns of member i with the i-th
+        entries, three launches per batch whatever B is; `reset_bits`: None, or one address or None per member): enqueued on the
+        group's stream, no wait."""
+        self._current()
+        B = len(self.models)
+        lists, banks, first = self._link_tables(lists, banks, first_rows)
+        if not (len(column_predictions) == len(persistences) == len(prevs) == B) or (reset_bits is not None and len(reset_bits) != B):
+            raise ValueError(f"{B} column predictions, persistences, prevs and reset bits, one per member")
+        p = L.HtmPoolLink(C.sizeof(L.HtmPoolLink), link.stride, link.active_weight, link.predicted_weight, link.decay, link.ceiling, link.union_bits, 0)
+        table = lambda ptrs: (C.c_void_p * B)(*ptrs)
+        self._check(self.lib.htm_group_pool_columns(self._g, p, lists, int(k), table(column_predictions), int(n_rows), table(persistences), table(prevs),
+                                                    None if reset_bits is None else table(reset_bits), C.c_void_p(scratch), int(scratch_bytes), banks,
+                                                    int(bank_rows), first), "htm_group_pool_columns")
+
     # forecast(): steps per feeding group run (see HierarchicalTemporalMemory.forecast_chunk)
     forecast_chunk = 1024
 

@@ -83,26 +83,33 @@ def _resolve(link, l, column_dim, active_columns):
         raise ValueError(f"link {l}: {e}") from None
 
 
+def _check_shape(input_dim, levels, strides, links):
+    """The constructor's arguments of a stack -> (levels as tuples of ints, the links as _check_links returns them); every
+    ValueError of a shape that cannot be built, before anything touches a device."""
+    levels = [tuple(int(v) for v in lv) for lv in levels]
+    if not levels or any(len(lv) not in (2, 3) for lv in levels):
+        raise ValueError("levels: a non-empty list of (column_dim, cell_dim) or (column_dim, cell_dim, active_columns)")
+    links = _check_links(strides, links, len(levels) - 1)
+    for i, lv in enumerate(levels):
+        if lv[0] < 1 or lv[1] < 1 or (len(lv) == 3 and not 1 <= lv[2] <= lv[0]):
+            raise ValueError(f"level {i}: column_dim and cell_dim >= 1, 1 <= active_columns <= column_dim (got {lv})")
+        if lv[1] > 64:
+            raise ValueError(f"level {i} has cell_dim {lv[1]} > 64: its Temporal Memory steps on the host")
+    if int(input_dim) < 1:
+        raise ValueError(f"input_dim must be at least 1 (got {input_dim})")
+    for i, link in enumerate(links):            # (a pooling link that does not fit its lower level: before anything touches a device)
+        if isinstance(link, PoolingLink):
+            _resolve(link, i, levels[i][0], levels[i][2] if len(levels[i]) == 3 else None)
+    return levels, links
+
+
 class RegionStack:
     """L fused HierarchicalTemporalMemory models chained through their active columns (see the module's docstring).  `levels`:
     a list of (column_dim, cell_dim) or (column_dim, cell_dim, active_columns), bottom first; `strides`: one per link.  All
     levels enqueue on ONE stream (so each keeps its fastest schedule, and the device path needs no events between them)."""
 
     def __init__(self, input_dim, levels, strides=None, seed=0, device=0, links=None):
-        levels = [tuple(int(v) for v in lv) for lv in levels]
-        if not levels or any(len(lv) not in (2, 3) for lv in levels):
-            raise ValueError("levels: a non-empty list of (column_dim, cell_dim) or (column_dim, cell_dim, active_columns)")
-        links = _check_links(strides, links, len(levels) - 1)
-        for i, lv in enumerate(levels):
-            if lv[0] < 1 or lv[1] < 1 or (len(lv) == 3 and not 1 <= lv[2] <= lv[0]):
-                raise ValueError(f"level {i}: column_dim and cell_dim >= 1, 1 <= active_columns <= column_dim (got {lv})")
-            if lv[1] > 64:
-                raise ValueError(f"level {i} has cell_dim {lv[1]} > 64: its Temporal Memory steps on the host")
-        if int(input_dim) < 1:
-            raise ValueError(f"input_dim must be at least 1 (got {input_dim})")
-        for i, link in enumerate(links):            # (a pooling link that does not fit its lower level: before anything touches a device)
-            if isinstance(link, PoolingLink):
-                _resolve(link, i, levels[i][0], levels[i][2] if len(levels[i]) == 3 else None)
+        levels, links = _check_shape(input_dim, levels, strides, links)
         stream = SharedStream(device)
         models, below = [], int(input_dim)
         for i, lv in enumerate(levels):

@@ -1092,6 +1092,34 @@ int htm_set_run_active_cells(htm_handle *h, void *device_pairs);
  * (htm_set_run_active_cells) still makes every group call HTM_ERR_STATE. */
 int htm_set_group_run_active_cells(htm_group *g, void *const *device_pairs);
 
+/* Stacks of model groups: the links of B streams' hierarchies, every launch covering all members (grid y =
+ * member).  dst is the group of the UPPER level's members.  For member i the effect is exactly that of htm_pack_columns /
+ * htm_pool_columns on member i with the i-th entries of the arrays: its bank rows, the rows left untouched, the persistence and prev
+ * it ends with, and bit 64 of ITS htm_info.capacity_error for an id outside its range -- no other member's.
+ * device_lists, device_banks, device_column_prediction, device_persistence, device_prev, device_reset_bits (the array, or any of its
+ * entries, may be NULL: no reset bits) and first_rows are HOST arrays of one entry per member, read before the call returns: they go
+ * to the device as ONE table per call (one copy on the group's stream into a buffer the group keeps; the batches' offsets go by
+ * value).  k, n_rows, stride / link, bank_rows are the same for every member.  Enqueued on the group's stream: no wait, and no
+ * allocation once the group's table has its size.
+ * htm_group_pack_columns: ONE launch (kgrp_pack_columns, grid (n_rows, B)).
+ * htm_group_pool_columns: per batch three launches whatever B is (kgrp_pack_columns at stride 1, kgpool_scan, kgpool_select); a
+ * batch is floor(scratch_bytes / (B * (stride + 8) * 4 * words_per_row)) windows of every member.  The scratch: member i's part
+ * begins i * batch * (stride + 8) * 4 * words_per_row bytes in and is laid out as htm_pool_columns lays out a batch (batch * stride
+ * bitmap rows, then batch snapshot rows of 32 * words_per_row bytes).
+ * HTM_ERR_ARGUMENT, nothing enqueued: everything the solo entries refuse, the alignment checked per member; a NULL array or a
+ * NULL entry (but the reset bits); a first_rows[i] outside [0, bank_rows); a scratch too small for one window of all members; more
+ * than 65535 members.  HTM_ERR_STATE, nothing enqueued: a member without the device's own Spatial Pooler, a column-sharded member, a
+ * member that is ahead (HTM_RUN_CONTINUE), a member that enqueues on another stream than the group's. */
+int htm_group_pack_columns(htm_group *dst, const int32_t *const *device_lists /* HOST array (as every array here): one DEVICE pointer per member */,
+                           int32_t k, int32_t n_rows, int32_t stride,
+                           uint32_t *const *device_banks, int32_t bank_rows, const int32_t *first_rows);
+int htm_group_pool_columns(htm_group *dst, htm_pool_link link, const int32_t *const *device_lists, int32_t k,
+                           const uint32_t *const *device_column_prediction, int32_t n_rows,
+                           uint8_t *const *device_persistence, uint32_t *const *device_prev,
+                           const uint32_t *const *device_reset_bits /* or NULL (entries may be NULL too) */,
+                           void *device_scratch, int64_t scratch_bytes,
+                           uint32_t *const *device_banks, int32_t bank_rows, const int32_t *first_rows);
+
 /* The classified tick: htm_likelihood_tick -- which is this call with the five classifier arguments NULL / 0 --
  * with a bank of classifiers riding on it; lk and likelihood may be NULL (an unscored, classified tick).  clf: a bank of as many
  * streams as the group has members, on the group's device, made for the members' column_dim x cell_dim with max_pairs >= k x WPC.
